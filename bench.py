@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/s of the batched HIP propagator on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps, writes what the last of them computed when ``--dump-outputs`` is
+given, and prints the one compact JSON line.  Everything else the benchmark measures (``value_with_join``, the
+dispatch-stamped pass and the rooflines, ``extra``, ``cpu_baseline``, at N > 1 the exchange legs) runs with ``--full`` only.
 
 N > 1 works both ways: as typed (this process starts ``python -m torch.distributed.run --nproc-per-node N
 bench.py ...`` as a CHILD, before anything here has touched the GPU, relays its output and exits with its
@@ -20,9 +24,9 @@ ballot and the per-wave reward sums: bsk_set_step_stats is on).  Actions and sta
 the timed region starts.  ``value_with_join`` is the same loop with the two batch scalars joined on the
 device after every step (bsk_get_batch_stats_device).
 
-Output.  The LAST stdout line is the compact JSON record the driver reads (< 4 096 bytes: contract keys,
-``value_with_join``, ``roofline``, ``cpu_baseline``, at N > 1 the rank / device / communicator counts and the
-exchange timings).  The whole record of the run - every other measurement point - is an EARLIER line
+Output.  The LAST stdout line is the compact JSON record the driver reads (< 4 096 bytes: contract keys; with ``--full``
+also ``value_with_join``, ``roofline``, ``cpu_baseline``, at N > 1 the rank / device / communicator counts and the
+exchange timings).  With ``--full`` the whole record of the run - every other measurement point - is an EARLIER line
 prefixed ``EXTRA `` and ``bench_extra.json`` beside this file.  (``--full-line``: tooling gets the whole record
 as the one line instead.)
 
@@ -34,7 +38,7 @@ bounded from above by the timed loop's wall time per launch (launches of one str
 says which of the two is reported).  ``--scenario`` / ``--features`` / ``--fsw-timing`` / ``--lds-scratch`` select
 other kernels of the same path for measurement; the default line is the contract's.
 
-Besides the contract keys the record carries ``roofline`` (dominant kernel: HBM-bound at K = 1 with
+Besides the contract keys the ``--full`` record carries ``roofline`` (dominant kernel: HBM-bound at K = 1 with
 340 algorithmic bytes per env-step; fp64-issue-bound for K >> 1, the harmonics and the
 scenario levels, with EXECUTED flops from the committed SQ_INSTS_VALU_*_F64 counter passes),
 ``cpu_baseline`` (the CPU oracle on this box's host cores, rank 0 at N = 1 only) and ``extra`` (EXTRA line only).
@@ -82,7 +86,16 @@ def parse(argv=None):
     p.add_argument("--full-line", action="store_true",
                    help="measurement tooling only: print the whole record as the ONE stdout line (no EXTRA line, no compact line, no "
                         "bench_extra.json) - what tools/*.sh parse; the driver's commands never pass it")
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="measure everything beyond the headline: value_with_join, the dispatch-stamped pass and the rooflines, the "
+                        "extra points, the CPU baseline, at N > 1 the exchange legs; the EXTRA line and bench_extra.json")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one computed (obs, reward, done, reason, state; at N > 1 rank 0's "
+                        "shard) as DIR/<name>.npy in float64, at most 64 MiB in all (dump_outputs)")
+    a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 # ---------------------------------------------------------------------------------------------
@@ -107,10 +120,11 @@ def _pick(d, keys, keep_null=("traffic",)):
     return {k: _sig(d[k]) for k in keys if k in d and (d[k] is not None or k in keep_null)}
 
 
-def headline(out):
+def headline(out, full=True):
     """-> dict: the contract keys + ``roofline`` reduced to what a reader recomputes from + ``cpu_baseline`` + (ranks > 1) the
     rank / device / communicator counts and the exchange timings; ``json.dumps`` of it is < HEADLINE_LIMIT bytes by
-    construction (tests/test_bench_host.py::test_headline_line_is_small)."""
+    construction (tests/test_bench_host.py::test_headline_line_is_small).  ``full`` False (a plain run): no pointer to the
+    EXTRA line, which such a run does not print."""
     cfg = out.get("config", {})
     h = {k: _sig(out[k]) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                    "vs_baseline", "dtype", "data") if k in out}
@@ -152,13 +166,14 @@ def headline(out):
         c3 = ex.get("config3")
         if c3:
             h["config3_env_steps_per_s"] = _sig(c3.get("env_steps_per_s"))
-    h["extra"] = EXTRA_FILE + " / the 'EXTRA ' line above"
+    if full:
+        h["extra"] = EXTRA_FILE + " / the 'EXTRA ' line above"
     return h
 
 
-def headline_line(out):
+def headline_line(out, full=True):
     """The compact line as text; if a future key ever pushes it over the limit the optional parts go first, never the contract keys."""
-    h = headline(out)
+    h = headline(out, full)
     line = json.dumps(h)
     for k in ("gather", "strong_65536_total", "small_batch_crossover_n", "rk4_substeps_per_s", "extra"):
         if len(line) < HEADLINE_LIMIT:
@@ -171,12 +186,17 @@ def headline_line(out):
 FULL_LINE = False       # --full-line (set by main): tooling gets the record as one line
 
 
-def emit(out, stream=None, extra_path=None):
-    """Rank 0's output: bench_extra.json + the EXTRA line (the whole record), then - LAST - the compact line."""
+def emit(out, stream=None, extra_path=None, full_run=True):
+    """Rank 0's output: bench_extra.json + the EXTRA line (the whole record), then - LAST - the compact line.  A plain run
+    (``full_run`` False) prints the compact line alone: its record holds nothing more."""
     stream = stream or sys.stdout
     full = json.dumps(out)
     if FULL_LINE and extra_path is None:
         stream.write(full + "\n")
+        stream.flush()
+        return
+    if not full_run:
+        stream.write(headline_line(out, full=False) + "\n")
         stream.flush()
         return
     try:
@@ -246,6 +266,27 @@ def timed_run(prop, d_act_ptr, substeps, steps, warmup, barrier, device_sync, jo
     t1 = time.perf_counter()   # this rank's K steps are done; the MAX over ranks is taken by the caller
     barrier()
     return t1 - t0
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """``--dump-outputs``: write ``arrays`` (name -> array with the spacecraft on its LAST axis) as ``path/<name>.npy`` in float64,
+    so that two builds can be compared output for output.  If together they exceed ``limit`` bytes, every array keeps the same
+    fixed, seeded sample of spacecraft (in index order), and the indices go to ``path/env_index.npy``.  -> the names written."""
+    import numpy as np
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[-1]
+    per_env = 8 * sum(v.size // n for v in arrays.values())
+    if per_env * n > limit:
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=max(1, limit // (per_env + 8)), replace=False))
+        arrays = {k: v[..., idx] for k, v in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
+    return sorted(arrays)
 
 
 def kernel_time(prop, d_act_ptr, substeps, launches, stride=None):
@@ -961,46 +1002,13 @@ def main():
 
     el_local = timed_run(prop, d_act.data_ptr(), a.substeps, a.steps, a.warmup, barrier, sync)
     el = max_over_ranks(el_local)
-    el_join = max_over_ranks(timed_run(prop, d_act.data_ptr(), a.substeps, 1 if a.no_join else a.steps, 0 if a.no_join else a.warmup, barrier, sync, join=True))
-    rsum_dev, ndone_dev = prop.batch_stats()
-    _, rew_j, _, why_j = prop.get_obs()
-    join_ok = bool(abs(rsum_dev - float(rew_j.sum())) <= 1e-9 * max(1.0, abs(float(rew_j.sum()))) and ndone_dev == int((why_j != 0).sum()))
-    assert join_ok or os.environ.get("BENCH_ALLOW_NONFINITE") == "1", "device-side batch scalars differ from the host sums of the same step"
-    kernel_ms, n_launch, kstats = kernel_time(prop, d_act.data_ptr(), a.substeps, min(STAMPED_LAUNCHES, max(a.steps, 4)))
+    # what the last timed step computed, read before anything else steps the handle (--full times more launches on it below)
     obs, rew, done, why = prop.get_obs()
     # (BENCH_ALLOW_NONFINITE=1: timing-only ablation builds whose results are deliberately wrong)
     assert os.environ.get("BENCH_ALLOW_NONFINITE") == "1" or (np.isfinite(obs).all() and np.isfinite(rew).all())
-    info = prop.kernel_info()
-    key = profile_key(a, sh)
-    wall_us = el_local / a.steps * 1e6
-
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"obs": obs, "reward": rew, "done": done, "reason": why, "state": prop.get_state()})
     value = n * world * a.steps / el
-    kernel_s = kernel_ms * 1e-3
-    traffic_bytes, traffic_src = pmc_traffic(n, a.substeps) if (not sh and a.scenario == "bare") else (None, None)
-    hbm = hbm_roofline(n, kernel_s, info, traffic_bytes, traffic_src, n_launch, static_o3=a.scenario == "bare" and not sh)
-    hbm.update(kstats)
-    settle_roofline(hbm, key, kernel_ms * 1e3, wall_us, BYTES_PER_ENV_STEP * n, HBM_PEAK_GBS, fp)
-    hbm["frac_of_copy_ceiling"] = hbm["achieved"] / HBM_COPY_CEILING_GBS
-    # which roofline bounds this configuration: K = 1 of the bare / power / full propagator streams its state once
-    # per launch (HBM); many sub-steps per launch and the harmonics are fp64-issue bound
-    mix_key = "sh" if sh else a.scenario
-    fp64_bound = sh or a.substeps >= 10
-    fp64 = fp64_roofline(mix_key, float(n) * a.substeps, kernel_s, info)
-    fp64.update(kstats)
-    flop = fp64.get("flop_per_launch")
-    if sh:
-        # config 5, algorithmic flops as SURVEY.md §8(d) / DESIGN.md §4 count them: 9 fp64 instructions (7 FMA + 2 MUL
-        # = 16 flop) per (l, m) entry of the padded Pines stream (2 592 entries at degree 70), four field evaluations
-        # per RK4 step, + ~450 fp64 instructions for the rest of the step.  `roofline.achieved` is this figure; the
-        # counter-derived one (every executed fp64 instruction, column ends and the redundant RK4 of the second wave
-        # included) is kept beside it.
-        fp64["executed_flop_per_launch"] = flop
-        flop = float(n) * SH_FLOP_PER_RK4 * a.substeps
-        fp64["algorithmic_flop_per_env_step"] = SH_FLOP_PER_RK4 * a.substeps
-    settle_roofline(fp64, key, kernel_ms * 1e3, wall_us, flop, FP64_PEAK_TFLOPS, fp)
-    if sh and fp64.get("executed_flop_per_launch"):
-        fp64["executed_tflops"] = fp64["executed_flop_per_launch"] / fp64["kernel_us"] / 1e6
-        fp64["executed_frac"] = fp64["executed_tflops"] / FP64_PEAK_TFLOPS
     out = {
         "metric": "env steps/sec at 65k parallel spacecraft, 1/2/4/8 MI355X; HBM GB/s vs roofline",
         "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -1012,28 +1020,67 @@ def main():
                    "envs_per_gpu": n, "substeps": a.substeps, "scenario": a.scenario, "lds_scratch": bool(a.lds_scratch), "fsw_timing": a.fsw_timing, "features": a.features,
                    "sharding": "env ranges, no step-path collective", "kernel_fingerprint": fp,
                    "batch_stats": "per-wave sums in the step launch; join on demand"},
-        "value_with_join": None if a.no_join else n * world * a.steps / el_join,
-        "ms_per_step_with_join": None if a.no_join else el_join / a.steps * 1e3, "join_matches_host_sum": join_ok,
-        "roofline": fp64 if fp64_bound else hbm,
         "rk4_substeps_per_s": value * a.substeps,
     }
-    if fp64_bound:
-        out["roofline_hbm"] = hbm
     if sh:
         out["sh"] = {"degree": 70, "field_evals_per_s": n * world * a.steps * a.substeps * 4 / el}
+    if a.full:
+        el_join = max_over_ranks(timed_run(prop, d_act.data_ptr(), a.substeps, 1 if a.no_join else a.steps, 0 if a.no_join else a.warmup, barrier, sync, join=True))
+        rsum_dev, ndone_dev = prop.batch_stats()
+        _, rew_j, _, why_j = prop.get_obs()
+        join_ok = bool(abs(rsum_dev - float(rew_j.sum())) <= 1e-9 * max(1.0, abs(float(rew_j.sum()))) and ndone_dev == int((why_j != 0).sum()))
+        assert join_ok or os.environ.get("BENCH_ALLOW_NONFINITE") == "1", "device-side batch scalars differ from the host sums of the same step"
+        kernel_ms, n_launch, kstats = kernel_time(prop, d_act.data_ptr(), a.substeps, min(STAMPED_LAUNCHES, max(a.steps, 4)))
+        obs, rew, done, why = prop.get_obs()
+        assert os.environ.get("BENCH_ALLOW_NONFINITE") == "1" or (np.isfinite(obs).all() and np.isfinite(rew).all())
+        info = prop.kernel_info()
+        key = profile_key(a, sh)
+        wall_us = el_local / a.steps * 1e6
+        kernel_s = kernel_ms * 1e-3
+        traffic_bytes, traffic_src = pmc_traffic(n, a.substeps) if (not sh and a.scenario == "bare") else (None, None)
+        hbm = hbm_roofline(n, kernel_s, info, traffic_bytes, traffic_src, n_launch, static_o3=a.scenario == "bare" and not sh)
+        hbm.update(kstats)
+        settle_roofline(hbm, key, kernel_ms * 1e3, wall_us, BYTES_PER_ENV_STEP * n, HBM_PEAK_GBS, fp)
+        hbm["frac_of_copy_ceiling"] = hbm["achieved"] / HBM_COPY_CEILING_GBS
+        # which roofline bounds this configuration: K = 1 of the bare / power / full propagator streams its state once
+        # per launch (HBM); many sub-steps per launch and the harmonics are fp64-issue bound
+        mix_key = "sh" if sh else a.scenario
+        fp64_bound = sh or a.substeps >= 10
+        fp64 = fp64_roofline(mix_key, float(n) * a.substeps, kernel_s, info)
+        fp64.update(kstats)
+        flop = fp64.get("flop_per_launch")
+        if sh:
+            # config 5, algorithmic flops as SURVEY.md §8(d) / DESIGN.md §4 count them: 9 fp64 instructions (7 FMA + 2 MUL
+            # = 16 flop) per (l, m) entry of the padded Pines stream (2 592 entries at degree 70), four field evaluations
+            # per RK4 step, + ~450 fp64 instructions for the rest of the step.  `roofline.achieved` is this figure; the
+            # counter-derived one (every executed fp64 instruction, column ends and the redundant RK4 of the second wave
+            # included) is kept beside it.
+            fp64["executed_flop_per_launch"] = flop
+            flop = float(n) * SH_FLOP_PER_RK4 * a.substeps
+            fp64["algorithmic_flop_per_env_step"] = SH_FLOP_PER_RK4 * a.substeps
+        settle_roofline(fp64, key, kernel_ms * 1e3, wall_us, flop, FP64_PEAK_TFLOPS, fp)
+        if sh and fp64.get("executed_flop_per_launch"):
+            fp64["executed_tflops"] = fp64["executed_flop_per_launch"] / fp64["kernel_us"] / 1e6
+            fp64["executed_frac"] = fp64["executed_tflops"] / FP64_PEAK_TFLOPS
+        out.update({
+            "value_with_join": None if a.no_join else n * world * a.steps / el_join,
+            "ms_per_step_with_join": None if a.no_join else el_join / a.steps * 1e3, "join_matches_host_sum": join_ok,
+            "roofline": fp64 if fp64_bound else hbm})
+        if fp64_bound:
+            out["roofline_hbm"] = hbm
 
     ranks = rank_identity(torch, dist, rank, local, world)
     if rank == 0:
         out["ranks"] = ranks
         out["distinct_devices"] = len({(r["pci_bus_id"], r["uuid"], r["hip_device"]) for r in ranks})
     clock = None
-    if dist is not None:
+    if dist is not None and a.full:
         out["gather"] = gather_legs(prop, dist, torch, world, n)
         clock = out["gather"].pop("_clock")
         out["gather_ms"] = out["gather"]["all_gather_ms"]
 
     extra = {}
-    default_line = not a.no_extra and not sh and a.scenario == "bare" and not a.lds_scratch and a.features is None
+    default_line = a.full and not a.no_extra and not sh and a.scenario == "bare" and not a.lds_scratch and a.features is None
     if world == 1 and default_line:
         dp = d_act.data_ptr()
         # reference-faithful env step: 180 s of sim time = 1 800 RK4 sub-steps, 180 FSW updates
@@ -1206,7 +1253,7 @@ def main():
         pf.close()
     if extra and rank == 0:
         out["extra"] = extra
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         # the CPU oracle on this box's host cores, like for like beside every GPU point of the line (bounded samples)
         if sh:
             out["cpu_baseline"] = cpu_baseline(cfg, n_rw, a.substeps, budget_s=10.0, n=256, sh=70)
@@ -1228,13 +1275,13 @@ def main():
             extra["small_batch"]["crossover"] = cross
             out["small_batch_crossover_n"] = cross["n"]
     hang = os.environ.get("BENCH_FAULT_HANG_LEG") == "1"
-    if dist is not None and (not rehearsal or hang) and os.environ.get("BSKGPU_DIRECT_RCCL", "1") != "0":
+    if dist is not None and a.full and (not rehearsal or hang) and os.environ.get("BSKGPU_DIRECT_RCCL", "1") != "0":
         # last, and under a watchdog: if the direct-RCCL leg (a second communicator, never run on more than one rank
         # before the driver's 8-GPU node) hangs, every rank gives up after 90 s and rank 0 still prints the line
         guarded_leg(out, rank, float(os.environ.get("BENCH_LEG_DEADLINE_S", "90")), lambda: direct_rccl_leg(prop, dist, torch, world, clock))
     prop.close()
     if rank == 0:
-        emit(out)
+        emit(out, full_run=a.full)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

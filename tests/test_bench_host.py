@@ -26,6 +26,64 @@ def test_defaults_and_constants(monkeypatch):
     assert b.BYTES_PER_ENV_STEP == 340.0 and b.HBM_PEAK_GBS == 8000.0
 
 
+def test_plain_run_is_the_default_and_steps_are_checked():
+    b = _load_bench()
+    a = b.parse([])
+    assert not a.full and a.dump_outputs is None
+    a = b.parse(["--full", "--dump-outputs", "out", "--steps", "1", "--warmup", "0"])
+    assert a.full and a.dump_outputs == "out" and a.steps == 1 and a.warmup == 0
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            b.parse(bad)
+
+
+def test_plain_run_prints_the_compact_line_alone(tmp_path):
+    """A plain run's record holds the contract keys only: emit() prints its compact line and nothing else - no EXTRA line, no
+    bench_extra.json, no pointer to either."""
+    import io
+    b, out = _canned_run(1)
+    for k in ("value_with_join", "roofline", "small_batch_crossover_n", "cpu_baseline", "extra"):
+        out.pop(k)
+    buf, path = io.StringIO(), str(tmp_path / "bench_extra.json")
+    b.emit(out, stream=buf, extra_path=path, full_run=False)
+    lines = buf.getvalue().splitlines()
+    assert len(lines) == 1 and not os.path.exists(path)
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert d[k] == out[k], k
+    assert "extra" not in d and "roofline" not in d
+
+
+def test_dump_outputs_writes_float64_and_samples_above_the_limit(tmp_path):
+    """--dump-outputs: every array as float64, whole when the total fits; above the limit every array keeps the same seeded sample
+    of spacecraft (the last axis), the indices beside them, the total within the limit, the same sample on every run."""
+    import numpy as np
+    b = _load_bench()
+    n = 1000
+    rng = np.random.default_rng(1)
+    arrays = {"obs": rng.normal(size=(5, n)), "reward": rng.normal(size=n), "done": rng.random(n) < 0.5,
+              "reason": rng.integers(0, 4, n).astype(np.uint8)}
+    assert b.dump_outputs(str(tmp_path / "a"), arrays) == ["done", "obs", "reason", "reward"]
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "a" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v.astype(np.float64)), k
+    limit = 8 * 9 * 300                       # room for 300 of the 1 000 spacecraft (8 values each, + the index)
+    names = b.dump_outputs(str(tmp_path / "b"), arrays, limit=limit)
+    assert names == ["done", "env_index", "obs", "reason", "reward"]
+    idx = np.load(tmp_path / "b" / "env_index.npy")
+    assert idx.shape == (300,) and np.all(np.diff(idx) > 0) and idx.min() >= 0 and idx.max() < n
+    total = 0
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "b" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v[..., idx.astype(np.int64)].astype(np.float64)), k
+        total += got.nbytes
+    assert total + idx.nbytes <= limit
+    b.dump_outputs(str(tmp_path / "c"), arrays, limit=limit)
+    assert np.array_equal(np.load(tmp_path / "c" / "env_index.npy"), idx)
+    # the bench's own outputs at its default size fit whole: obs, reward, done, reason and the 47-field state of 65 536 spacecraft
+    assert 8 * (5 + 3 + 47) * 65536 <= b.DUMP_LIMIT_BYTES == 64 << 20
+
+
 def test_pmc_traffic_comes_from_committed_profile():
     b = _load_bench()
     t, src = b.pmc_traffic(65536, 1)

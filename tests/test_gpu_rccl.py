@@ -64,7 +64,7 @@ def test_bench_collective_legs_on_rccl_single_rank(tmp_path):
     root = os.path.dirname(HERE)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "5",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("BENCH_REHEARSAL", None)
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
@@ -103,7 +103,7 @@ def test_a_hung_leg_under_the_launcher_still_yields_the_line_and_a_failure():
     import json
     root = os.path.dirname(HERE)
     env = dict(os.environ, BENCH_REHEARSAL="1", BENCH_FAULT_HANG_LEG="1", BENCH_LEG_DEADLINE_S="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "50", "--warmup", "5", "--no-extra", "--no-cpu-baseline"],
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "50", "--warmup", "5", "--full", "--no-extra", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=600, env=env)
     assert res.returncode != 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -124,7 +124,7 @@ def test_rehearsal_of_gpus_4_ends_in_one_compact_line_and_status_0():
     root = os.path.dirname(HERE)
     env = dict(os.environ, BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("BENCH_FAULT_HANG_LEG", None)
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "50", "--warmup", "5"],
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "50", "--warmup", "5", "--full"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     out_lines = [l for l in res.stdout.splitlines() if l.strip()]

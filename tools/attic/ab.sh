@@ -6,6 +6,6 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 for args in "$@"; do
   for lib in $R/basilisk_env_amd/variants/*.so; do
     name=$(basename "$lib" .so)
-    BSKGPU_LIB=$lib python3 $R/bench.py --no-cpu-baseline --no-extra --full-line $args 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('%-14s %-52s kernel_us %10.2f med %10.2f ms/step %9.4f vgpr %d'%('$name', '$args', r['kernel_us'], r.get('median_us',0), d['ms_per_step'], r['vgprs']))"
+    BSKGPU_LIB=$lib python3 $R/bench.py --full --no-cpu-baseline --no-extra --full-line $args 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('%-14s %-52s kernel_us %10.2f med %10.2f ms/step %9.4f vgpr %d'%('$name', '$args', r['kernel_us'], r.get('median_us',0), d['ms_per_step'], r['vgprs']))"
   done
 done

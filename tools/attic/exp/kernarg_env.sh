@@ -1,5 +1,5 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
-line() { python3 bench.py --no-cpu-baseline --no-extra --full-line --steps 20000 --warmup 2000 2>/dev/null | python3 -c "
+line() { python3 bench.py --full --no-cpu-baseline --no-extra --full-line --steps 20000 --warmup 2000 2>/dev/null | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('$1 wall_us %6.3f stamped %6.3f' % (r['wall_us_per_launch'], r['kernel_us_stamped']))"; }

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/pad_trace; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for rep in a b c; do for pad in 0 32; do
   export BSKGPU_STRIDE_PAD=$pad
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_pad${pad}${rep} -- python3 $R/bench.py --no-cpu-baseline --no-extra --full-line --steps 40000 --warmup 4000 > $O/kt_pad${pad}${rep}.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_pad${pad}${rep} -- python3 $R/bench.py --full --no-cpu-baseline --no-extra --full-line --steps 40000 --warmup 4000 > $O/kt_pad${pad}${rep}.log 2>&1
 done; done
 cd $R; python3 - $O <<'PY'
 import glob, os, sys

@@ -15,7 +15,7 @@ for key in $KEYS; do
     full)  ARGS="--scenario full --substeps 600 --steps 3 --warmup 1" ;;
     sh)    ARGS="--gravity sh --substeps 2 --steps 3 --warmup 1" ;;
   esac
-  B="python3 $R/bench.py --no-cpu-baseline --no-extra --full-line $ARGS"
+  B="python3 $R/bench.py --full --no-cpu-baseline --no-extra --full-line $ARGS"
   timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_WAVES --output-format csv -d $O/${key}_f -- $B > $O/${key}_f.log 2>&1 && echo ${key}_f ok
   timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAVES GRBM_GUI_ACTIVE --output-format csv -d $O/${key}_t -- $B > $O/${key}_t.log 2>&1 && echo ${key}_t ok
 done

@@ -6,7 +6,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-r04}; IDX=${2:-2}
 O=$R/gpurun_out/$TAG; mkdir -p $O
-B="python3 $R/bench.py --no-cpu-baseline --no-extra --full-line"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-extra --full-line"
 cd /tmp && export TMPDIR=/tmp
 $B --steps 40000 --warmup 4000 > $O/ab_65k_b${IDX}_plain.json 2>/dev/null && echo plain ok
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_65k_b$IDX -- $B --steps 40000 --warmup 4000 > $O/kt_65k_b$IDX.log 2>&1 && echo kt_65k_b$IDX ok

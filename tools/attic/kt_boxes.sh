@@ -8,7 +8,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-r04}; IDX=${2:-2}
 O=$R/gpurun_out/$TAG; mkdir -p $O
-B="python3 $R/bench.py --no-cpu-baseline --no-extra --full-line"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-extra --full-line"
 cd /tmp && export TMPDIR=/tmp
 run() {  # name args
   $B $2 > $O/ab_$1_b${IDX}_plain.json 2>/dev/null

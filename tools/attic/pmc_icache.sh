@@ -5,7 +5,7 @@ TAG=${1:-x}; shift
 O=$R/gpurun_out/pmci_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-extra --full-line $*"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-extra --full-line $*"
 timeout -k 10 300 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_IFETCH --output-format csv -d $O/a -- $B > $O/a.log 2>&1
 python3 - <<PY
 import csv,glob,collections,statistics

@@ -7,7 +7,7 @@ O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L > $O/counters_list.txt 2>&1
-B="python3 $R/bench.py --no-cpu-baseline --no-extra --full-line"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-extra --full-line"
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_65k -- $B > $O/kt_65k.log 2>&1 && echo kt_65k ok
 timeout -k 10 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch_65k -- $B --steps 50 > $O/fetch_65k.log 2>&1 && echo fetch_65k ok
 timeout -k 10 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write_65k -- $B --steps 50 > $O/write_65k.log 2>&1 && echo write_65k ok

@@ -8,8 +8,8 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 ab() {  # name, bench args...
   name=$1; shift
-  python3 $R/bench.py --no-cpu-baseline --no-extra --full-line "$@" > $O/ab_${name}_plain.json 2>> $O/ab.err && echo ab_${name}_plain ok
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$name -- python3 $R/bench.py --no-cpu-baseline --no-extra --full-line "$@" > $O/ab_${name}_rocprof.json 2> $O/kt_$name.log && echo ab_${name}_rocprof ok
+  python3 $R/bench.py --full --no-cpu-baseline --no-extra --full-line "$@" > $O/ab_${name}_plain.json 2>> $O/ab.err && echo ab_${name}_plain ok
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$name -- python3 $R/bench.py --full --no-cpu-baseline --no-extra --full-line "$@" > $O/ab_${name}_rocprof.json 2> $O/kt_$name.log && echo ab_${name}_rocprof ok
 }
 ab 65k --steps 40000 --warmup 4000
 ab full_k1800 --scenario full --substeps 1800 --steps 20 --warmup 10

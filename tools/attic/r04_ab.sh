@@ -10,7 +10,7 @@ mkdir -p $O
 VARS=${*:-$(cd $R/basilisk_env_amd/variants && ls *.so | sed 's/\.so$//')}
 cd $R
 line() {  # name args
-  BSKGPU_LIB=$R/basilisk_env_amd/variants/$1.so python3 bench.py --no-cpu-baseline --no-extra --full-line $2 2>>$O/err.log | python3 -c "
+  BSKGPU_LIB=$R/basilisk_env_amd/variants/$1.so python3 bench.py --full --no-cpu-baseline --no-extra --full-line $2 2>>$O/err.log | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('%-12s %-44s kernel_us %10.2f med %10.2f wall_us %10.2f vgpr %d' % ('$1', '$2', r['kernel_us_stamped'], r.get('median_us',0), r['wall_us_per_launch'], r['vgprs']))"
@@ -26,7 +26,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in $VARS; do
   for sc in full bare; do
     A="--substeps 600 --steps 3 --warmup 1"; [ $sc = full ] && A="--scenario full $A"
-    BSKGPU_LIB=$R/basilisk_env_amd/variants/$v.so timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAVES --output-format csv -d $O/pmc_${v}_$sc -- python3 $R/bench.py --no-cpu-baseline --no-extra --full-line $A > $O/pmc_${v}_$sc.log 2>&1
+    BSKGPU_LIB=$R/basilisk_env_amd/variants/$v.so timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAVES --output-format csv -d $O/pmc_${v}_$sc -- python3 $R/bench.py --full --no-cpu-baseline --no-extra --full-line $A > $O/pmc_${v}_$sc.log 2>&1
     python3 - <<PY | tee -a $O/ab.txt
 import csv, glob, collections
 tot = collections.Counter(); n = 0

@@ -6,8 +6,8 @@ EXTRA=${2:-}
 O=$R/gpurun_out
 cd $R
 for sc in bare power full; do
-  python bench.py --no-cpu-baseline --no-extra --full-line $EXTRA --scenario $sc --steps 200 --warmup 20 > $O/scen_${TAG}_${sc}_k1.json 2>> $O/scen_$TAG.err
-  python bench.py --no-cpu-baseline --no-extra --full-line $EXTRA --scenario $sc --substeps 1800 --steps 4 --warmup 1 > $O/scen_${TAG}_${sc}_k1800.json 2>> $O/scen_$TAG.err
+  python bench.py --full --no-cpu-baseline --no-extra --full-line $EXTRA --scenario $sc --steps 200 --warmup 20 > $O/scen_${TAG}_${sc}_k1.json 2>> $O/scen_$TAG.err
+  python bench.py --full --no-cpu-baseline --no-extra --full-line $EXTRA --scenario $sc --substeps 1800 --steps 4 --warmup 1 > $O/scen_${TAG}_${sc}_k1800.json 2>> $O/scen_$TAG.err
 done
 python - <<PY
 import json,glob

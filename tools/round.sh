@@ -14,7 +14,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=${1:?usage: tools/round.sh TAG PHASE...}; shift
 O=$R/gpurun_out/$TAG
 mkdir -p $O
-B="python3 $R/bench.py --no-cpu-baseline --no-extra --no-join --full-line"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-extra --no-join --full-line"
 prof() { tag=$1; shift; ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 "$@" > $O/$tag.log 2>&1 ) && echo $tag ok || echo $tag FAILED; }
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU"
 # name : bench arguments   (the keys of kernel_trace.json: tools/kernel_trace_summary.py)
@@ -86,7 +86,7 @@ phase_isa() {    # executed instruction mix per RK4 sub-step and wave, for bench
 # reads; refused above 4 096 bytes) and NAME.extra.json (the whole record)
 line() {
   name=$1; shift
-  ( cd $R && python bench.py "$@" > $O/$name.out 2>> $O/bench.err ) || { echo "$name FAILED (rc $?)"; return 1; }
+  ( cd $R && python bench.py --full "$@" > $O/$name.out 2>> $O/bench.err ) || { echo "$name FAILED (rc $?)"; return 1; }
   tail -n 1 $O/$name.out > $O/$name.json
   grep '^EXTRA ' $O/$name.out | tail -n 1 | sed 's/^EXTRA //' > $O/$name.extra.json
   sz=$(wc -c < $O/$name.json)
