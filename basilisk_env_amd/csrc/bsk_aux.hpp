@@ -34,7 +34,7 @@ struct StatsSeal {
 };
 hipError_t launch_seal(const StatsSeal& seal, hipStream_t s);
 // batch scalars of the last step (stats_kernel + stats_join_kernel): scratch wave_sum f64[n_waves], done_part u32[stats_done_parts()];
-// have_wave_sums: the step kernel filled wave_sum[] (StepBuffers::wave_sum) - the join kernel alone
+// have_wave_sums: the step kernel filled wave_sum[] (TailArgs::wave_sum) - the join kernel alone
 hipError_t launch_stats(const double* reward, int n, const unsigned long long* done_mask, int n_waves, double* wsum,
                         unsigned* done_part, double* out_sum, long long* out_done, double* out2, bool have_wave_sums, const StatsSeal& seal,
                         hipStream_t s);

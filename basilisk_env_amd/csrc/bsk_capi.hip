@@ -244,7 +244,6 @@ int build_params(const bsk_config& c, bsk::StepParams& p, bsk::ColdCfg& k, bool&
     p.sh_degree = 0;
     p.sh_split = 2;
     p.sh_bodies = p.sh_bodies0 = p.sh_bodies1 = p.sh_chunk1 = 0;
-    p.sh_form = 4;
     const bool full = (c.flags & (BSK_FLAG_SUN_THIRD_BODY | BSK_FLAG_DRAG | BSK_FLAG_DESAT)) != 0;
     p.ex.desat = (c.flags & BSK_FLAG_DESAT) ? 1 : 0;
     p.ex.pad_ = 0;
@@ -448,18 +447,21 @@ struct bsk_handle {
     // bare levels: no spacecraft of the batch / of the reset pool started its episode with an empty battery (bsk_launch.hpp:
     // StepArgs::static_charge).  Known after a reset of the whole batch; withdrawn by bsk_set_state until the next one.
     bool charge_pos = false, pool_charge_pos = false;
-    // pair form of the step kernel (bsk_device.hpp: PairLds): used for launches of >= pair_min_substeps sub-steps of batches
-    // of <= pair_max_envs spacecraft where it is built (power / full-scenario levels, point mass or J2, diagonal hub).  Measured
-    // (profiles/r03/pair_form.txt): -13 % per env step up to one pair per CU (16 384 spacecraft), level with the single-wave
-    // form up to three pairs per CU, 7 % slower at four (65 536).  BSKGPU_PAIR=0 / 1 forces it off / on for every launch.
-    bool pair_ok = false, last_pair = false;
-    int pair_min_substeps = 16, pair_max_envs = 16384;
-    // three-wave form (bsk_device.hpp: TriX): the pair form with the dynamics wave cut into a translational and a rotational
-    // wave; full-scenario level only, preferred over the pair form where both apply (profiles/r03/tri_form.txt: -16 % against
-    // the pair form up to one workgroup per CU, twice the time above).  BSKGPU_TRI=0 / 1 forces it off / on.
-    bool tri_ok = false, last_tri = false;
-    bool last_rollout = false, last_rollout_act = false;    // the last launch was bsk_step_n's rollout kernel (with per-step actions); bsk_kernel_info
-    int tri_min_substeps = 16, tri_max_envs = 16384;
+    // Form policy of the step kernel (choose_form).  Pair form (bsk_device.hpp: PairLds): launches of >= pair_min_substeps sub-steps
+    // of batches of <= pair_max_envs spacecraft where it is built (power / full-scenario levels, point mass or J2, diagonal hub).
+    // Measured (profiles/r03/pair_form.txt): -13 % per env step up to one pair per CU (16 384 spacecraft), level with the
+    // single-wave form up to three pairs per CU, 7 % slower at four (65 536).  Three-wave form (bsk_device.hpp: TriX): the pair form
+    // with the dynamics wave cut into a translational and a rotational wave; full-scenario level only, preferred over the pair form
+    // where both apply (profiles/r03/tri_form.txt: -16 % against the pair form up to one workgroup per CU, twice the time above).
+    // BSKGPU_PAIR / BSKGPU_TRI = 0 | 1 force a form off / on for every launch (bsk_create).  Harmonics run sh_form (bsk_set_gravity_sh).
+    struct {
+        bool pair_ok = false, tri_ok = false;
+        int pair_min_substeps = 16, pair_max_envs = 16384;
+        int tri_min_substeps = 16, tri_max_envs = 16384;
+        int sh_form = bsk::FORM_SH_DPP;
+    } policy;
+    // what the last launch ran (bsk_kernel_info): the step kernel in `form`, or bsk_step_n's rollout kernel (with per-step actions)
+    struct { int form; bool rollout, act; } last = {bsk::FORM_SINGLE, false, false};
 };
 
 namespace {
@@ -588,31 +590,29 @@ int check_device_error(bsk_handle* h) {
 
 void fill_buffers(bsk_handle* h, bsk::StepBuffers& b, const void* d_actions, int substeps, int act_shift, bool static_charge) {
     b.cold = h->d_cold;
-    b.st = h->d_state;
-    b.cnt = h->d_cnt;
     b.act = (const int*)d_actions;
     b.act_shift = act_shift;
-    b.static_charge = static_charge ? 1 : 0;
-    b.ep_return = h->d_ep_return; b.term_return = h->d_term_return; b.term_len = h->d_term_len; b.done = h->d_done;
-    b.obs_rm = h->d_obs_rm; b.err = h->h_err; b.dbg = h->d_dbg;
+    bsk::TailArgs& t = b.tail;
+    t.obs_cfg = h->sp.obs;
+    t.st = h->d_state; t.cnt = h->d_cnt; t.obs = h->d_obs; t.reward = h->d_reward; t.done_mask = h->d_done_mask; t.reason = h->d_reason;
+    t.stride = h->stride; t.ostride = h->ostride; t.n = h->n; t.substeps = substeps;
+    t.pool = h->d_pool; t.term_obs = h->d_term_obs; t.episodes = h->d_episodes; t.n_pool = h->n_pool; t.n_fields = h->nf;
+    t.fsw_lag = h->sp.fsw_lag; t.nav_lag = h->sp.nav_lag; t.env_base = h->env_base; t.static_charge = static_charge ? 1 : 0;
+    t.ep_return = h->d_ep_return; t.term_return = h->d_term_return; t.term_len = h->d_term_len; t.done = h->d_done;
+    t.obs_rm = h->d_obs_rm; t.err = h->h_err; t.dbg = h->d_dbg;
     // (above 2 Mi spacecraft one workgroup joining 32 768+ wave sums AND as many done ballots is no faster than the two-level form; a
     // handle whose launches have been captured keeps the two-level form too: "the last launch wrote the wave sums" is host-side
     // knowledge, and a replayed graph steps without telling the host)
-    b.wave_sum = (h->step_stats && !h->replayable && h->n <= (1 << 21)) ? h->d_wave_sum : nullptr;
-    b.obs = h->d_obs;
-    b.reward = h->d_reward;
-    b.done_mask = h->d_done_mask;
-    b.reason = h->d_reason;
-    b.stride = h->stride;
-    b.ostride = h->ostride;
-    b.n = h->n;
-    b.substeps = substeps;
-    b.pool = h->d_pool;
-    b.term_obs = h->d_term_obs;
-    b.episodes = h->d_episodes;
-    b.n_pool = h->n_pool;
-    b.n_fields = h->nf;
-    b.env_base = h->env_base;
+    t.wave_sum = (h->step_stats && !h->replayable && h->n <= (1 << 21)) ? h->d_wave_sum : nullptr;
+}
+
+// The form of the step kernel a launch of `substeps` sub-steps runs (bsk_handle::policy).  substeps = 0: the handle's single-wave
+// form (every wave-split form needs >= 1), which bsk_kernel_info reports before the first launch.
+int choose_form(const bsk_handle* h, int substeps) {
+    const auto& f = h->policy;
+    if (f.tri_ok && substeps >= f.tri_min_substeps && h->n <= f.tri_max_envs) return bsk::FORM_TRI;
+    if (f.pair_ok && substeps >= f.pair_min_substeps && h->n <= f.pair_max_envs) return bsk::FORM_PAIR;
+    return h->cfg.gravity_model == BSK_GRAV_SH ? f.sh_form : bsk::FORM_SINGLE;
 }
 
 // Dispatch-timestamp sampling.  stride == 1: every launch is stamped.  stride > 1: launches
@@ -651,14 +651,12 @@ int do_step(bsk_handle* h, const void* d_actions, int substeps, int act_shift) {
                  !replayable && (h->sp.feat == bsk::FEAT_BARE || h->sp.feat == bsk::FEAT_LDSS) && h->charge_pos && (h->n_pool == 0 || h->pool_charge_pos));
     hipEvent_t e0, e1;
     { int rc = stamp_events(h, e0, e1); if (rc) return rc; }
-    h->sp.tri = (h->tri_ok && substeps >= h->tri_min_substeps && h->n <= h->tri_max_envs) ? 1 : 0;
-    h->sp.pair = (!h->sp.tri && h->pair_ok && substeps >= h->pair_min_substeps && h->n <= h->pair_max_envs) ? 1 : 0;
-    h->last_pair = h->sp.pair != 0;
-    h->last_tri = h->sp.tri != 0;
-    h->last_rollout = false;
-    HIP_TRY(bsk::launch_step(h->cfg.gravity_model, h->cfg.n_rw, h->diag, h->sp.feat, h->sp, b, h->block, h->stream, e0, e1));
+    h->last = {choose_form(h, substeps), false, false};
+    const bsk::StepLaunch go{h->sp, b, h->stream, e0, e1};
+    bsk::KernelDesc d;
+    HIP_TRY(bsk::dispatch_step(h->cfg.gravity_model, h->cfg.n_rw, h->diag, h->sp.feat, h->last.form, h->block, h->n, &go, &d));
     h->stats_fresh = false;
-    h->wave_sums_fresh = b.wave_sum != nullptr;
+    h->wave_sums_fresh = b.tail.wave_sum != nullptr;
     h->stepped = true;
     return BSK_OK;
 }
@@ -823,23 +821,24 @@ int bsk_create(const bsk_config* cfg, int n_envs, int device_id, void* stream, b
     if (cfg->flags & BSK_FLAG_POWER) h->block = 64;
     // both wave-split forms pay while every workgroup has a CU (and its LDS) to itself: 64 spacecraft per CU of THIS device
     // (256 CUs on a whole MI355X; fewer in a partitioned mode)
-    if (prop.multiProcessorCount > 0) h->pair_max_envs = h->tri_max_envs = 64 * prop.multiProcessorCount;
-    h->pair_ok = bsk::pair_available(cfg->gravity_model, h->diag, h->sp.feat);
+    if (prop.multiProcessorCount > 0) h->policy.pair_max_envs = h->policy.tri_max_envs = 64 * prop.multiProcessorCount;
+    h->policy.pair_ok = bsk::form_built(cfg->gravity_model, h->diag, h->sp.feat, bsk::FORM_PAIR);
+    h->policy.tri_ok = bsk::form_built(cfg->gravity_model, h->diag, h->sp.feat, bsk::FORM_TRI);
     h->sp.pair_shift = 31;     // no swap: the hardware already places one wave 0 and one wave 1 of different workgroups on a SIMD (tools/micro/placement.hip)
 #if BSK_TUNABLES
     if (const char* ps = std::getenv("BSKGPU_PAIR_SHIFT")) h->sp.pair_shift = std::max(0, std::min(31, std::atoi(ps)));
 #endif
     if (const char* pv = std::getenv("BSKGPU_PAIR")) {
         const int v = std::atoi(pv);
-        if (v == 0) h->pair_ok = false;
-        else { h->pair_min_substeps = 1; h->pair_max_envs = 1 << 28; }   // every launch (measurement / tests)
+        if (v == 0) h->policy.pair_ok = false;
+        else { h->policy.pair_min_substeps = 1; h->policy.pair_max_envs = 1 << 28; }   // every launch (measurement / tests)
     }
-    h->tri_ok = bsk::tri_available(cfg->gravity_model, h->diag, h->sp.feat);
     if (const char* tv = std::getenv("BSKGPU_TRI")) {
         const int v = std::atoi(tv);
-        if (v == 0) h->tri_ok = false;
-        else { h->tri_min_substeps = 1; h->tri_max_envs = 1 << 28; }     // every launch (measurement / tests)
+        if (v == 0) h->policy.tri_ok = false;
+        else { h->policy.tri_min_substeps = 1; h->policy.tri_max_envs = 1 << 28; }     // every launch (measurement / tests)
     }
+    h->last.form = choose_form(h, 0);
     if (stream) { h->stream = (hipStream_t)stream; h->own_stream = false; }
     else {
         hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
@@ -939,12 +938,13 @@ int bsk_set_gravity_sh(bsk_handle* h, int degree, const double* cbar, const doub
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
     }
-    h->sp.sh_form = (h->n < 2 * (4 * n_cu) * 64) ? 5 : 4;
+    h->policy.sh_form = (h->n < 2 * (4 * n_cu) * 64) ? bsk::FORM_SH_DPP2 : bsk::FORM_SH_DPP;
     if (const char* f = std::getenv("BSKGPU_SH_FORM")) {
         const int v = std::atoi(f);
-        if (v == 1 || v == 4 || v == 5) h->sp.sh_form = v;
+        if (v == 1 || v == 4 || v == 5) h->policy.sh_form = v;
     }
-    h->sp.sh_tab = h->sp.sh_form == 1 ? h->d_sh_tab : h->d_sh_tab4;
+    h->sp.sh_tab = h->policy.sh_form == bsk::FORM_SINGLE ? h->d_sh_tab : h->d_sh_tab4;
+    h->last.form = h->policy.sh_form;     // (every launch of a harmonics handle runs it)
     return BSK_OK;
 }
 
@@ -1038,10 +1038,10 @@ int bsk_step_n(bsk_handle* h, const int32_t* d_actions, int32_t constant_action,
     r.n_steps = n_steps; r.const_action = constant_action;
     hipEvent_t e0, e1;
     { int rc = stamp_events(h, e0, e1); if (rc) return rc; }
-    h->last_pair = h->last_tri = false;
-    h->last_rollout = true;
-    h->last_rollout_act = d_actions != nullptr;
-    HIP_TRY(bsk::launch_rollout(h->cfg.gravity_model, h->cfg.n_rw, h->diag, h->sp, b, r, h->block, h->stream, e0, e1));
+    h->last = {bsk::FORM_SINGLE, true, d_actions != nullptr};
+    const bsk::RolloutLaunch go{{h->sp, b, h->stream, e0, e1}, r};
+    bsk::KernelDesc d;
+    HIP_TRY(bsk::dispatch_rollout(h->cfg.gravity_model, h->cfg.n_rw, h->diag, h->last.act, h->block, h->n, &go, &d));
     h->stats_fresh = false;
     h->wave_sums_fresh = false;
     h->stepped = true;
@@ -1391,29 +1391,27 @@ int bsk_profile_end(bsk_handle* h, double* mean_kernel_ms, int* n_launches) {
 int bsk_kernel_info(bsk_handle* h, char* name, int name_cap, int* vgprs, int* lds_bytes, int* block, int* grid) {
     if (!h) return fail(BSK_EINVAL, "handle is NULL");
     DeviceGuard guard(h->device);
-    const bool sh = h->cfg.gravity_model == BSK_GRAV_SH;
-    // (the kernel of the LAST launch: the pair form is chosen per launch by its number of sub-steps)
-    const void* fp = h->last_rollout ? bsk::rollout_kernel_ptr(h->cfg.gravity_model, h->cfg.n_rw, h->diag, h->last_rollout_act)
-                                     : bsk::step_kernel_ptr(h->cfg.gravity_model, h->cfg.n_rw, h->diag, h->sp.feat, h->sp.sh_form, h->last_pair, h->last_tri);
-    if (!fp) return fail(BSK_EINVAL, "no kernel variant for this config");
+    const int g = h->cfg.gravity_model, form = h->last.form;
+    bsk::KernelDesc d;
+    if (h->last.rollout) (void)bsk::dispatch_rollout(g, h->cfg.n_rw, h->diag, h->last.act, h->block, h->n, nullptr, &d);
+    else (void)bsk::dispatch_step(g, h->cfg.n_rw, h->diag, h->sp.feat, form, h->block, h->n, nullptr, &d);
+    if (!d.fn) return fail(BSK_EINVAL, "no kernel variant for this config");
     hipFuncAttributes at;
-    HIP_TRY(hipFuncGetAttributes(&at, fp));
-    if (name && name_cap > 0 && h->last_rollout)
-        std::snprintf(name, name_cap, "rollout_kernel<%s,%d,%s,%s>", h->cfg.gravity_model == BSK_GRAV_PM ? "PM" : "PM_J2", h->cfg.n_rw, h->diag ? "diag" : "full",
-                      h->last_rollout_act ? "actions" : "constant");
+    HIP_TRY(hipFuncGetAttributes(&at, d.fn));
+    static const char* const GRAV[] = {"PM", "PM_J2"};                                              // BSK_GRAV_PM, _PM_J2
+    static const char* const SH_FORM[] = {"", "SH/scalar", "", "", "SH/dpp", "SH/dpp2"};            // BSK_GRAV_SH, by form
+    static const char* const LEVEL[] = {",lds-scratch", "", ",power", ",scenario", ",scenario/generic-facets"};  // FEAT_LDSS ..
+    static const char* const SPLIT[] = {"", "", ",pair", ",tri", "", ""};                          // by form
+    const char* hub = h->diag ? "diag" : "full";
+    if (name && name_cap > 0 && h->last.rollout)
+        std::snprintf(name, name_cap, "rollout_kernel<%s,%d,%s,%s>", GRAV[g], h->cfg.n_rw, hub, h->last.act ? "actions" : "constant");
     else if (name && name_cap > 0)
-        std::snprintf(name, name_cap, "step_kernel<%s,%d,%s>",
-                      h->cfg.gravity_model == BSK_GRAV_PM ? "PM" : (h->cfg.gravity_model == BSK_GRAV_PM_J2 ? "PM_J2" : (h->sp.sh_form == 5 ? "SH/dpp2" : (h->sp.sh_form == 4 ? "SH/dpp" : "SH/scalar"))), h->cfg.n_rw,
-                      h->sp.feat >= 2 ? (h->sp.feat == 3 ? (h->diag ? "diag,scenario/generic-facets" : "full,scenario/generic-facets")
-                                                         : (h->last_tri ? "diag,scenario,tri" : (h->last_pair ? "diag,scenario,pair" : (h->diag ? "diag,scenario" : "full,scenario"))))
-                                      : (h->sp.feat == 1 ? (h->last_pair ? "diag,power,pair" : (h->diag ? "diag,power" : "full,power"))
-                                                         : (h->sp.feat == -1 ? (h->diag ? "diag,lds-scratch" : "full,lds-scratch") : (h->diag ? "diag" : "full"))));
+        std::snprintf(name, name_cap, "step_kernel<%s,%d,%s%s%s>", g == BSK_GRAV_SH ? SH_FORM[form] : GRAV[g], h->cfg.n_rw, hub,
+                      LEVEL[h->sp.feat - bsk::FEAT_LDSS], SPLIT[form]);
     if (vgprs) *vgprs = at.numRegs;
     if (lds_bytes) *lds_bytes = (int)at.sharedSizeBytes;
-    // the two-wave harmonics form launches 256-thread workgroups of 2 x 64 spacecraft x 2 halves
-    const int blk = (sh && h->sp.sh_form == 5) ? 256 : (h->last_tri ? 192 : (h->last_pair ? 128 : h->block));
-    if (block) *block = blk;
-    if (grid) *grid = (sh && h->sp.sh_form == 5) ? (h->n + 127) / 128 : ((h->last_pair || h->last_tri) ? (h->n + 63) / 64 : (h->n + blk - 1) / blk);
+    if (block) *block = d.shape.block;
+    if (grid) *grid = d.shape.grid;
     return BSK_OK;
 }
 

@@ -280,8 +280,7 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     if constexpr (NRW > 0) z0 = navlag && tick == 0 && substeps_eff > 0;
     unsigned long long dbg_waitA = 0, dbg_waitB = 0, dbg_chain = 0, dbg_bar = 0;      // (probe builds only: bsk_probes.hpp)
     if constexpr (PAIR) {
-        static_assert(!PAIR || (FEAT >= FEAT_POWER && FEAT != FEAT_FULLG && GRAV != BSK_GRAV_SH), "pair form: power / full-scenario levels, point mass or J2");
-        static_assert(!TRI || FEAT == FEAT_FULL, "three-wave form: the full-scenario level");
+        static_assert(form_built(GRAV, DIAG, FEAT, SPLIT), "a wave-split form this cell is not built in (bsk_launch.hpp: form_built)");
         // ---- pair form: both waves run the SAME control flow on the same counters (every decision below is a function of
         // cnt / substeps / actions, identical in the two waves), so their barrier counts agree by construction; what each
         // wave does between two barriers depends on its role and contains no barrier.
@@ -1035,37 +1034,22 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
 }
 
 template <int GRAV, int NRW, bool DIAG, int FEAT, int SPLIT>
-static hipError_t launch_t(const StepParams& p, const StepBuffers& b, int block, hipStream_t s, hipEvent_t ev0,
-                           hipEvent_t ev1) {
+static hipError_t launch_t(const StepLaunch& go, const LaunchShape& sh) {
+    const StepParams& p = go.p;
+    const StepBuffers& b = go.b;
     StepArgs<NRW, DIAG> a;
     fill_hot<GRAV, NRW, DIAG>(p, a.hot);
-    a.cold = b.cold; a.st = b.st; a.cnt = b.cnt; a.act = b.act;
-    a.stride = b.stride; a.n = b.n; a.substeps = b.substeps;
+    a.cold = b.cold; a.st = b.tail.st; a.cnt = b.tail.cnt; a.act = b.act;
+    a.stride = b.tail.stride; a.n = b.tail.n; a.substeps = b.tail.substeps;
     a.nav_lag = p.nav_lag; a.fsw_lag = p.fsw_lag;
-    a.pair_shift = p.pair_shift; a.act_shift = b.act_shift; a.ep_return = b.ep_return;
-    a.static_charge = b.static_charge; a.pad2_ = 0;
+    a.pair_shift = p.pair_shift; a.act_shift = b.act_shift; a.ep_return = b.tail.ep_return;
+    a.static_charge = b.tail.static_charge; a.pad2_ = 0;
     a.power = p.pc;
     a.extra = p.ex;
-    a.tail.obs_cfg = p.obs; a.tail.st = b.st; a.tail.cnt = b.cnt; a.tail.obs = b.obs; a.tail.reward = b.reward;
-    a.tail.done_mask = b.done_mask; a.tail.reason = b.reason;
-    a.tail.stride = b.stride; a.tail.ostride = b.ostride; a.tail.n = b.n; a.tail.substeps = b.substeps;
-    a.tail.pool = b.pool; a.tail.term_obs = b.term_obs; a.tail.episodes = b.episodes;
-    a.tail.n_pool = b.n_pool; a.tail.n_fields = b.n_fields;
-    a.tail.fsw_lag = p.fsw_lag; a.tail.nav_lag = p.nav_lag;
-    a.tail.env_base = b.env_base; a.tail.static_charge = b.static_charge;
-    a.tail.ep_return = b.ep_return; a.tail.term_return = b.term_return; a.tail.term_len = b.term_len; a.tail.done = b.done;
-    a.tail.obs_rm = b.obs_rm; a.tail.err = b.err; a.tail.dbg = b.dbg; a.tail.wave_sum = b.wave_sum;
-    if (SPLIT == 5) block = 256;
-    if (SPLIT == 2) block = 128;      // pair form: dynamics wave + FSW / environment wave of the same 64 spacecraft
-    if (SPLIT == 3) block = 192;      // three-wave form: rotational, FSW / environment and translational wave
-    const int grid = SPLIT == 5 ? (b.n + 127) / 128 : ((SPLIT == 2 || SPLIT == 3) ? (b.n + 63) / 64 : (b.n + block - 1) / block);
-    // the power system keeps a per-wave tick record and penumbra queue in dynamic LDS (bsk_device.hpp: PowerLds)
-    const size_t lds = SPLIT == 3 ? sizeof(TriLds) : SPLIT == 2 ? sizeof(PairLds)
-                     : FEAT >= FEAT_POWER ? sizeof(PowerLds) * (size_t)(block / 64)
-                                          : (FEAT == FEAT_LDSS ? sizeof(AccLds) * (size_t)(block / 64) : 0);
+    a.tail = b.tail;
     // hipExtLaunchKernelGGL stamps ev0/ev1 from the dispatch packet itself (no marker packets), so
     // their difference is the kernel's own duration, as rocprofv3 --kernel-trace reports it.
-    if (lds > 48 * 1024) {   // the two-wave harmonics form with the power system: 4 waves x 29 KB of dynamic LDS
+    if (sh.lds > 48 * 1024) {   // the two-wave harmonics form with the power system: 4 waves x 29 KB of dynamic LDS
         // the attribute belongs to (kernel, DEVICE): one bit per device and instantiation, set once the call has
         // succeeded there (handles on different devices are stepped from different threads: atomic, and a lost race
         // only repeats an idempotent call)
@@ -1076,12 +1060,12 @@ static hipError_t launch_t(const StepParams& p, const StepBuffers& b, int block,
         const unsigned long long bit = 1ull << (dev & 63);
         if (!(raised.load(std::memory_order_acquire) & bit)) {
             e = hipFuncSetAttribute((const void*)&step_kernel<GRAV, NRW, DIAG, FEAT, SPLIT>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.lds);
             if (e != hipSuccess) return e;
             raised.fetch_or(bit, std::memory_order_release);
         }
     }
-    hipExtLaunchKernelGGL((step_kernel<GRAV, NRW, DIAG, FEAT, SPLIT>), dim3(grid), dim3(block), lds, s, ev0, ev1, 0, a);
+    hipExtLaunchKernelGGL((step_kernel<GRAV, NRW, DIAG, FEAT, SPLIT>), dim3(sh.grid), dim3(sh.block), sh.lds, go.s, go.ev0, go.ev1, 0, a);
     return hipGetLastError();
 }
 
@@ -1108,11 +1092,9 @@ static hipError_t launch_t(const StepParams& p, const StepBuffers& b, int block,
 #define BSK_TU_CAT2(a, b) a##b
 #define BSK_TU_CAT(a, b) BSK_TU_CAT2(a, b)
 #define BSK_VARIANTS(X) BSK_TU_CAT(BSK_UNIT, BSK_TU)(X)
-#define BSK_LAUNCH_UNIT BSK_TU_CAT(launch_step_tu, BSK_TU)
-#define BSK_PTR_UNIT BSK_TU_CAT(step_kernel_ptr_tu, BSK_TU)
+#define BSK_STEP_UNIT BSK_TU_CAT(dispatch_step_tu, BSK_TU)
 #else
-#define BSK_LAUNCH_UNIT launch_step_unit
-#define BSK_PTR_UNIT step_kernel_ptr_unit
+#define BSK_STEP_UNIT dispatch_step     // one-unit builds (variant / probe libraries): the dispatcher is this unit itself
 #if defined(BSK_ONLY)                                // whatever the command line lists: -D'BSK_ONLY(X)=X(BSK_GRAV_SH,4,true,2)'
 #define BSK_VARIANTS(X) BSK_ONLY(X)
 #elif defined(BSK_FAST_BUILD) && BSK_FAST_BUILD == 3 // only the kernel the drop-in env runs, in its three forms (tests/test_dpp_build.py)
@@ -1127,76 +1109,30 @@ static hipError_t launch_t(const StepParams& p, const StepBuffers& b, int block,
 #endif
 #endif
 
-// pair form (SPLIT == 2): built for the power / full-scenario levels of the point-mass and J2 kernels with a diagonal hub
-template <int G, int R, bool D, int P>
-static hipError_t launch_pair(const StepParams& p, const StepBuffers& b, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    if constexpr (D && G != BSK_GRAV_SH && (P == FEAT_POWER || P == FEAT_FULL)) return launch_t<G, R, D, P, 2>(p, b, 128, s, ev0, ev1);
-    else return hipErrorInvalidValue;
-}
-template <int G, int R, bool D, int P>
-static const void* pair_ptr() {
-    if constexpr (D && G != BSK_GRAV_SH && (P == FEAT_POWER || P == FEAT_FULL)) return (const void*)&step_kernel<G, R, D, P, 2>;
-    else return nullptr;
-}
-// three-wave form (SPLIT == 3): the full-scenario level of the same kernels
-template <int G, int R, bool D, int P>
-static hipError_t launch_tri(const StepParams& p, const StepBuffers& b, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    if constexpr (D && G != BSK_GRAV_SH && P == FEAT_FULL) return launch_t<G, R, D, P, 3>(p, b, 192, s, ev0, ev1);
-    else return hipErrorInvalidValue;
-}
-template <int G, int R, bool D, int P>
-static const void* tri_ptr() {
-    if constexpr (D && G != BSK_GRAV_SH && P == FEAT_FULL) return (const void*)&step_kernel<G, R, D, P, 3>;
-    else return nullptr;
+template <int G, int R, bool D, int P, int S>
+static hipError_t step_form(int block, int n, const StepLaunch* go, KernelDesc* d) {
+    if constexpr (form_built(G, D, P, S)) {
+        d->fn = (const void*)&step_kernel<G, R, D, P, S>;
+        d->shape = launch_shape(S, P, block, n);
+        return go ? launch_t<G, R, D, P, S>(*go, d->shape) : hipSuccess;
+    } else {
+        return hipErrorInvalidValue;
+    }
 }
 
-// this unit's share of the dispatch: *handled says whether the configuration is one of its instantiations
-hipError_t BSK_LAUNCH_UNIT(int grav, int nrw, bool diag, int feat, const StepParams& p, const StepBuffers& b, int block,
-                           hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool* handled) {
-    *handled = true;
-#define CASE(G, R, D, P) \
-    if (grav == G && nrw == R && diag == D && feat == P) {                                                 \
-        if (p.tri) return launch_tri<G, R, D, P>(p, b, s, ev0, ev1);                                        \
-        if (p.pair) return launch_pair<G, R, D, P>(p, b, s, ev0, ev1);                                      \
-        if (G == BSK_GRAV_SH && p.sh_form == 4) return launch_t<G, R, D, P, (G == BSK_GRAV_SH ? 4 : 1)>(p, b, block, s, ev0, ev1); \
-        if (G == BSK_GRAV_SH && p.sh_form == 5) return launch_t<G, R, D, P, (G == BSK_GRAV_SH ? 5 : 1)>(p, b, block, s, ev0, ev1); \
-        return launch_t<G, R, D, P, 1>(p, b, block, s, ev0, ev1);                                           \
-    }
-    BSK_VARIANTS(CASE)
+// this unit's share of the dispatch (bsk_launch.hpp: dispatch_step).  The wave-split forms are listed first: the order in which the
+// kernels are first instantiated is their order in the code object, and with it every PC-relative offset to the shared constants.
+hipError_t BSK_STEP_UNIT(int grav, int nrw, bool diag, int feat, int form, int block, int n, const StepLaunch* go, KernelDesc* d) {
+#define CASE(G, R, D, P, S) \
+    if (grav == G && nrw == R && diag == D && feat == P && form == S) return step_form<G, R, D, P, S>(block, n, go, d);
+#define SPLIT_FORMS(G, R, D, P) CASE(G, R, D, P, FORM_TRI) CASE(G, R, D, P, FORM_PAIR)
+#define ONE_WAVE_FORMS(G, R, D, P) CASE(G, R, D, P, FORM_SH_DPP) CASE(G, R, D, P, FORM_SH_DPP2) CASE(G, R, D, P, FORM_SINGLE)
+    BSK_VARIANTS(SPLIT_FORMS)
+    BSK_VARIANTS(ONE_WAVE_FORMS)
+#undef ONE_WAVE_FORMS
+#undef SPLIT_FORMS
 #undef CASE
-    *handled = false;
     return hipErrorInvalidValue;
 }
-
-const void* BSK_PTR_UNIT(int grav, int nrw, bool diag, int feat, int sh_form, bool pair, bool tri, bool* handled) {
-    *handled = true;
-#define CASE(G, R, D, P) \
-    if (grav == G && nrw == R && diag == D && feat == P) {                                                                     \
-        if (tri) return tri_ptr<G, R, D, P>();                                                                                 \
-        if (pair) return pair_ptr<G, R, D, P>();                                                                               \
-        if (G == BSK_GRAV_SH && sh_form == 4) return (const void*)&step_kernel<G, R, D, P, (G == BSK_GRAV_SH ? 4 : 1)>;        \
-        if (G == BSK_GRAV_SH && sh_form == 5) return (const void*)&step_kernel<G, R, D, P, (G == BSK_GRAV_SH ? 5 : 1)>;        \
-        return (const void*)&step_kernel<G, R, D, P, 1>;                                                                       \
-    }
-    BSK_VARIANTS(CASE)
-#undef CASE
-    *handled = false;
-    return nullptr;
-}
-
-#ifndef BSK_TU
-// one-unit builds (variant / probe libraries): the dispatcher is this unit itself
-hipError_t launch_step(int grav, int nrw, bool diag, int feat, const StepParams& p, const StepBuffers& b, int block,
-                       hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    bool handled = false;
-    return launch_step_unit(grav, nrw, diag, feat, p, b, block, s, ev0, ev1, &handled);
-}
-const void* step_kernel_ptr(int grav, int nrw, bool diag, int feat, int sh_form, bool pair, bool tri) {
-    bool handled = false;
-    return step_kernel_ptr_unit(grav, nrw, diag, feat, sh_form, pair, tri, &handled);
-}
-bool pair_available(int grav, bool diag, int feat) { return diag && grav != BSK_GRAV_SH && (feat == FEAT_POWER || feat == FEAT_FULL); }
-bool tri_available(int grav, bool diag, int feat) { return diag && grav != BSK_GRAV_SH && feat == FEAT_FULL; }
-#endif
 
 }  // namespace bsk

@@ -83,45 +83,20 @@ struct StepParams {
     int32_t sh_degree;
     int32_t sh_split;       // first Pines column of the second half of the walk
     int32_t sh_bodies, sh_bodies0, sh_bodies1, sh_chunk1;   // DPP stream: bodies (whole / per half), first chunk of half 1
-    int sh_form;            // 1 scalar-load stream, 4 DPP broadcast, 5 DPP broadcast over two cooperating waves
-    int pair;               // this launch runs the pair form (dynamics wave + FSW / environment wave per 64 spacecraft)
-    int pair_shift;
-    int tri;                // this launch runs the three-wave form (rotational / FSW + environment / translational wave)
+    int pair_shift;         // StepArgs::pair_shift
     int feat;               // FEAT_BARE / FEAT_POWER / FEAT_FULL
     int fsw_lag, nav_lag;
     PowerCfg pc;
     ExtraCfg ex;
 };
 
+// What a launch reads and writes beyond the handle's constants: the kernels' post-loop block whole (bsk_capi.hip: fill_buffers)
+// and the loop's own inputs.
 struct StepBuffers {
+    TailArgs tail;
     const ColdCfg* cold;
-    double* st;
-    int2* cnt;
     const int* act;
-    double* obs;
-    double* reward;
-    unsigned long long* done_mask;
-    unsigned char* reason;
-    int64_t stride;
-    int64_t ostride;
-    int n;
-    int substeps;
-    const double* pool;
-    double* term_obs;
-    int* episodes;
-    int n_pool;
-    int n_fields;
-    unsigned env_base;
     int act_shift;
-    int static_charge;
-    double* ep_return;
-    double* term_return;
-    int* term_len;
-    unsigned char* done;
-    double* obs_rm;
-    int* err;
-    unsigned long long* dbg;
-    double* wave_sum;
 };
 
 // the loop's constants as the kernels take them (by value in the kernarg segment)
@@ -152,9 +127,48 @@ inline void fill_hot(const StepParams& p, HotCfg<NRW, DIAG>& h) {
     h.planet_rate = p.planet_rate;
 }
 
-hipError_t launch_step(int grav, int nrw, bool diag, int feat, const StepParams& p, const StepBuffers& b, int block,
-                       hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
-const void* step_kernel_ptr(int grav, int nrw, bool diag, int feat, int sh_form, bool pair, bool tri = false);
-bool pair_available(int grav, bool diag, int feat);
-bool tri_available(int grav, bool diag, int feat);
+// Form of a step-kernel launch: the value of step_kernel's SPLIT argument.
+enum Form : int {
+    FORM_SINGLE = 1,    // one wave per 64 spacecraft (harmonics: the scalar-load stream)
+    FORM_PAIR = 2,      // dynamics wave + FSW / environment wave of the same 64 spacecraft (bsk_device.hpp: PairLds)
+    FORM_TRI = 3,       // rotational, FSW / environment and translational wave of the same 64 spacecraft (TriLds)
+    FORM_SH_DPP = 4,    // harmonics: DPP broadcast stream
+    FORM_SH_DPP2 = 5,   // harmonics: DPP broadcast stream, the walk split over two cooperating waves
+};
+
+// The forms built for a cell (gravity model, hub kind, feature level).  The wave-split forms exist for the power (pair) and
+// full-scenario (pair, three-wave) levels of the point-mass and J2 kernels with a diagonal hub; the DPP forms for harmonics.
+constexpr bool form_built(int grav, bool diag, int feat, int form) {
+    switch (form) {
+    case FORM_SINGLE: return true;
+    case FORM_PAIR: return diag && grav != BSK_GRAV_SH && (feat == FEAT_POWER || feat == FEAT_FULL);
+    case FORM_TRI: return diag && grav != BSK_GRAV_SH && feat == FEAT_FULL;
+    case FORM_SH_DPP: case FORM_SH_DPP2: return grav == BSK_GRAV_SH;
+    default: return false;
+    }
+}
+
+struct LaunchShape { int block, grid; size_t lds; };     // lds: dynamic LDS bytes
+
+// How a form is launched over n spacecraft.  `block` is the handle's workgroup size; the wave-split forms fix their own.
+constexpr LaunchShape launch_shape(int form, int feat, int block, int n) {
+    if (form == FORM_PAIR) return {128, (n + 63) / 64, sizeof(PairLds)};
+    if (form == FORM_TRI) return {192, (n + 63) / 64, sizeof(TriLds)};
+    // the two-wave harmonics form: 256-thread workgroups of 2 x 64 spacecraft x 2 halves of the walk
+    if (form == FORM_SH_DPP2) block = 256;
+    const int grid = form == FORM_SH_DPP2 ? (n + 127) / 128 : (n + block - 1) / block;
+    // the power system keeps a per-wave tick record and penumbra queue in dynamic LDS (PowerLds), the LDS-scratch level its
+    // RK4 accumulator (AccLds)
+    const size_t waves = (size_t)(block / 64);
+    return {block, grid, feat >= FEAT_POWER ? sizeof(PowerLds) * waves : feat == FEAT_LDSS ? sizeof(AccLds) * waves : 0};
+}
+
+// A kernel instantiation: its address (what hipFuncGetAttributes takes) and how it is launched.
+struct KernelDesc { const void* fn = nullptr; LaunchShape shape{}; };
+
+struct StepLaunch { const StepParams& p; const StepBuffers& b; hipStream_t s; hipEvent_t ev0, ev1; };
+
+// The step kernel of (gravity model, wheels, hub kind, feature level) in `form`: launched when `go` is given, otherwise only
+// described.  *d describes it whenever it is built (d->fn stays NULL, and hipErrorInvalidValue is returned, where it is not).
+hipError_t dispatch_step(int grav, int nrw, bool diag, int feat, int form, int block, int n, const StepLaunch* go, KernelDesc* d);
 }  // namespace bsk

@@ -313,47 +313,35 @@ __global__ __launch_bounds__(256, 2) void rollout_kernel(const RolloutArgs<NRW, 
 }
 
 template <int GRAV, int NRW, bool DIAG, bool ACT>
-static hipError_t launch_r(const StepParams& p, const StepBuffers& b, const RolloutBuffers& r, int block, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+static hipError_t rollout_form(int block, int n, const RolloutLaunch* go, KernelDesc* d) {
+    d->fn = (const void*)&rollout_kernel<GRAV, NRW, DIAG, ACT>;
+    d->shape = launch_shape(FORM_SINGLE, FEAT_BARE, block, n);
+    if (!go) return hipSuccess;
     RolloutArgs<NRW, DIAG> a;
-    fill_hot<GRAV, NRW, DIAG>(p, a.hot);
-    a.cold = b.cold;
-    a.tail.obs_cfg = p.obs; a.tail.st = b.st; a.tail.cnt = b.cnt; a.tail.obs = b.obs; a.tail.reward = b.reward;
-    a.tail.done_mask = b.done_mask; a.tail.reason = b.reason;
-    a.tail.stride = b.stride; a.tail.ostride = b.ostride; a.tail.n = b.n; a.tail.substeps = b.substeps;
-    a.tail.pool = b.pool; a.tail.term_obs = b.term_obs; a.tail.episodes = b.episodes;
-    a.tail.n_pool = b.n_pool; a.tail.n_fields = b.n_fields;
-    a.tail.fsw_lag = p.fsw_lag; a.tail.nav_lag = p.nav_lag;
-    a.tail.env_base = b.env_base; a.tail.static_charge = 0;
-    a.tail.ep_return = b.ep_return; a.tail.term_return = b.term_return; a.tail.term_len = b.term_len; a.tail.done = b.done;
-    a.tail.obs_rm = b.obs_rm; a.tail.err = b.err; a.tail.dbg = b.dbg; a.tail.wave_sum = nullptr;
+    fill_hot<GRAV, NRW, DIAG>(go->p, a.hot);
+    a.cold = go->b.cold;
+    a.tail = go->b.tail;
+    // the step kernel's two shortcuts, which rollout_kernel has not got: it always loads the charge and writes no wave sums
+    a.tail.static_charge = 0;
+    a.tail.wave_sum = nullptr;
+    const RolloutBuffers& r = go->r;
     a.actions = r.actions; a.obs_hist = r.obs_hist; a.reward_hist = r.reward_hist; a.reason_hist = r.reason_hist;
     a.n_steps = r.n_steps; a.const_action = r.const_action;
-    const int grid = (b.n + block - 1) / block;
-    hipExtLaunchKernelGGL((rollout_kernel<GRAV, NRW, DIAG, ACT>), dim3(grid), dim3(block), 0, s, ev0, ev1, 0, a);
+    hipExtLaunchKernelGGL((rollout_kernel<GRAV, NRW, DIAG, ACT>), dim3(d->shape.grid), dim3(d->shape.block), 0, go->s, go->ev0, go->ev1, 0, a);
     return hipGetLastError();
 }
 
 bool rollout_available(int grav, int feat) { return (grav == BSK_GRAV_PM || grav == BSK_GRAV_PM_J2) && feat == FEAT_BARE; }
 
-hipError_t launch_rollout(int grav, int nrw, bool diag, const StepParams& p, const StepBuffers& b, const RolloutBuffers& r, int block,
-                          hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-#define CASE(G, R, D) if (grav == G && nrw == R && diag == D) return r.actions ? launch_r<G, R, D, true>(p, b, r, block, s, ev0, ev1) : launch_r<G, R, D, false>(p, b, r, block, s, ev0, ev1);
+hipError_t dispatch_rollout(int grav, int nrw, bool diag, bool act, int block, int n, const RolloutLaunch* go, KernelDesc* d) {
+#define CASE(G, R, D) \
+    if (grav == G && nrw == R && diag == D) return act ? rollout_form<G, R, D, true>(block, n, go, d) : rollout_form<G, R, D, false>(block, n, go, d);
     CASE(BSK_GRAV_PM, 0, true) CASE(BSK_GRAV_PM, 3, true) CASE(BSK_GRAV_PM, 4, true)
     CASE(BSK_GRAV_PM_J2, 0, true) CASE(BSK_GRAV_PM_J2, 3, true) CASE(BSK_GRAV_PM_J2, 4, true)
     CASE(BSK_GRAV_PM, 0, false) CASE(BSK_GRAV_PM, 3, false) CASE(BSK_GRAV_PM, 4, false)
     CASE(BSK_GRAV_PM_J2, 0, false) CASE(BSK_GRAV_PM_J2, 3, false) CASE(BSK_GRAV_PM_J2, 4, false)
 #undef CASE
     return hipErrorInvalidValue;
-}
-
-const void* rollout_kernel_ptr(int grav, int nrw, bool diag, bool act) {
-#define CASE(G, R, D) if (grav == G && nrw == R && diag == D) return act ? (const void*)&rollout_kernel<G, R, D, true> : (const void*)&rollout_kernel<G, R, D, false>;
-    CASE(BSK_GRAV_PM, 0, true) CASE(BSK_GRAV_PM, 3, true) CASE(BSK_GRAV_PM, 4, true)
-    CASE(BSK_GRAV_PM_J2, 0, true) CASE(BSK_GRAV_PM_J2, 3, true) CASE(BSK_GRAV_PM_J2, 4, true)
-    CASE(BSK_GRAV_PM, 0, false) CASE(BSK_GRAV_PM, 3, false) CASE(BSK_GRAV_PM, 4, false)
-    CASE(BSK_GRAV_PM_J2, 0, false) CASE(BSK_GRAV_PM_J2, 3, false) CASE(BSK_GRAV_PM_J2, 4, false)
-#undef CASE
-    return nullptr;
 }
 
 }  // namespace bsk

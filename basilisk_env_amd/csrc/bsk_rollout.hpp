@@ -12,10 +12,11 @@ struct RolloutBuffers {
     int n_steps, const_action;
 };
 
+struct RolloutLaunch : StepLaunch { const RolloutBuffers& r; };
+
 // built for: point mass / J2 at the bare level (every wheel set, diagonal and general hub)
 bool rollout_available(int grav, int feat);
-hipError_t launch_rollout(int grav, int nrw, bool diag, const StepParams& p, const StepBuffers& b, const RolloutBuffers& r, int block,
-                          hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
-const void* rollout_kernel_ptr(int grav, int nrw, bool diag, bool act);
+// the rollout kernel of (gravity model, wheels, hub kind, per-step actions or not), as dispatch_step (bsk_launch.hpp) does it
+hipError_t dispatch_rollout(int grav, int nrw, bool diag, bool act, int block, int n, const RolloutLaunch* go, KernelDesc* d);
 
 }  // namespace bsk

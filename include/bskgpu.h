@@ -382,7 +382,9 @@ int bsk_calibrate_fp64(int device_id, int waves_per_simd, int repeats, double* t
  * sub-steps in a wave-split form of the same arithmetic (bit-identical results: "...,pair" at the power level - a dynamics and
  * an FSW + environment wave per 64 spacecraft, 128-thread workgroups - and "...,tri" at the full-scenario level - a
  * translational, a rotational and the FSW + environment wave, 192-thread workgroups), everything else the
- * single-wave form.  BSKGPU_PAIR / BSKGPU_TRI = 0 | 1 in the environment of bsk_create switch a form off / on for every launch. */
+ * single-wave form.  BSKGPU_PAIR / BSKGPU_TRI = 0 | 1 in the environment of bsk_create switch a form off / on for every launch.
+ * Before the first launch: the single-wave form of the config (harmonics: the form of the last bsk_set_gravity_sh, the one-wave
+ * DPP form before any). */
 int bsk_kernel_info(bsk_handle* h, char* name, int name_cap, int* vgprs, int* lds_bytes,
                     int* block, int* grid);
 
