@@ -45,6 +45,35 @@ hipError_t launch_scatter_reset(double* st, int64_t stride, int nf, const double
 hipError_t launch_hist_row(const double* obs, const double* reward, const unsigned char* reason, int64_t stride, int n, double* obs_row,
                            double* reward_row, unsigned char* reason_row, hipStream_t s);
 
+// bsk_fork.hip: one handle's per-env buffers as the fork kernel reads or writes them (any optional pointer may be NULL: that handle
+// lacks the buffer).  `st` rows are `stride` apart, every other [stride] array is `ostride` long.
+struct ForkSide {
+    double* st;                    // [nf][stride]
+    int64_t stride;
+    int2* cnt;                     // [ostride] the whole {steps | phase << 20, ticks} word
+    double* obs;                   // [5][ostride]
+    int64_t ostride;
+    double* reward;                // [ostride]
+    unsigned char* reason;         // [ostride]
+    unsigned long long* done_mask; // [ostride / 64]
+    double* obs_rm;                // [n][5] or NULL
+    double* ep_return;             // [ostride] or NULL (ep_return, term_return, term_len, done: BSK_FLAG_EPISODE_STATS)
+    double* term_return;
+    int* term_len;
+    unsigned char* done;
+    double* term_obs;              // [5][ostride] or NULL (no IC pool staged)
+    int* episodes;                 // [ostride] or NULL
+    int n;
+};
+// env j of dst <- env map[j] of src (map[j] outside [0, src.n): j untouched).  identity: env j of src instead of map[j], for the
+// second half of an in-handle fork (src = the gather scratch).  err: raised with BSK_DEVERR_FORK_MAP on an out-of-range entry
+// other than -1 (NULL: not raised).  seal_word: the destination's StatsSeal::word, whose seal the fork lifts (NULL: none).
+hipError_t launch_fork(const ForkSide& src, const ForkSide& dst, int nf, const int* map, bool identity, int* err,
+                       unsigned long long* seal_word, hipStream_t s);
+// one action per group of `group` consecutive branches from their rollout histories (bsk_select_branches)
+hipError_t launch_select(const double* reward_hist, const unsigned char* reason_hist, const int* first_action, int n_steps, int n_branch,
+                         int group, double gamma, double* values, double* best_value, int* best_action, hipStream_t s);
+
 // first-level workgroups of stats_kernel at most = entries of the `done_part` scratch
 int stats_done_parts();
 

@@ -462,6 +462,14 @@ struct bsk_handle {
     } policy;
     // what the last launch ran (bsk_kernel_info): the step kernel in `form`, or bsk_step_n's rollout kernel (with per-step actions)
     struct { int form; bool rollout, act; } last = {bsk::FORM_SINGLE, false, false};
+    // the coefficients of the last bsk_set_gravity_sh (bsk_fork_device refuses to fork between handles of different fields)
+    std::vector<double> sh_cbar, sh_sbar;
+    // bsk_fork_device: the in-handle fork's gather scratch (every per-env buffer a handle can have, one allocation, kept for the
+    // handle's lifetime), the host map's staging buffer, and the events that order two handles' streams around a fork
+    bsk::ForkSide fork_scratch = {};
+    void* d_fork_block = nullptr;
+    int* d_map_stage = nullptr;
+    hipEvent_t ev_fork_in = nullptr, ev_fork_out = nullptr;
 };
 
 namespace {
@@ -584,6 +592,8 @@ int check_device_error(bsk_handle* h) {
     if (e == bsk::BSK_DEVERR_TRI_EXCHANGE)
         return fail(BSK_EHIP, "step kernel (three-wave form): a wave waited 2^20 polls for its partner's stage value and gave up; "
                               "the results of that launch are invalid (observations were set to NaN)");
+    if (e == bsk::BSK_DEVERR_FORK_MAP)
+        return fail(BSK_EHIP, "bsk_fork_device: a map entry was neither -1 nor a source env index; those envs were left unchanged");
     return fail(BSK_EHIP, "step kernel raised device error " + std::to_string(e));
 }
 #define SYNC_CHECKED(h) do { HIP_SYNC(hipStreamSynchronize((h)->stream)); int rc_ = check_device_error(h); if (rc_) return rc_; } while (0)
@@ -658,6 +668,93 @@ int do_step(bsk_handle* h, const void* d_actions, int substeps, int act_shift) {
     h->stats_fresh = false;
     h->wave_sums_fresh = b.tail.wave_sum != nullptr;
     h->stepped = true;
+    return BSK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Forks (bsk_fork_device; kernels: bsk_fork.hip)
+bsk::ForkSide fork_side(const bsk_handle* h) {
+    bsk::ForkSide f;
+    f.st = h->d_state; f.stride = h->stride; f.cnt = h->d_cnt; f.obs = h->d_obs; f.ostride = h->ostride; f.reward = h->d_reward;
+    f.reason = h->d_reason; f.done_mask = h->d_done_mask; f.obs_rm = h->d_obs_rm; f.ep_return = h->d_ep_return;
+    f.term_return = h->d_term_return; f.term_len = h->d_term_len; f.done = h->d_done; f.term_obs = h->d_term_obs;
+    f.episodes = h->d_episodes; f.n = h->n;
+    return f;
+}
+
+// the flags that change what a step writes or the form it runs in, never its arithmetic: free to differ between fork partners
+constexpr uint32_t FORK_FREE_FLAGS = BSK_FLAG_AUTO_RESET | BSK_FLAG_EPISODE_STATS | BSK_FLAG_OBS_ROWMAJOR | BSK_FLAG_LDS_SCRATCH;
+
+int fork_compatible(const bsk_handle* dst, const bsk_handle* src) {
+    if (dst->device != src->device) return fail(BSK_EINVAL, "bsk_fork_device: the handles live on different devices");
+    if (dst->cfg.n_rw != src->cfg.n_rw) return fail(BSK_EINVAL, "bsk_fork_device: the handles have different n_rw");
+    bsk_config a = dst->cfg, b = src->cfg;
+    a.flags &= ~FORK_FREE_FLAGS;
+    b.flags &= ~FORK_FREE_FLAGS;
+    if (std::memcmp(&a, &b, sizeof a) != 0)
+        return fail(BSK_EINVAL, "bsk_fork_device: the handles' bsk_configs differ (beyond AUTO_RESET / EPISODE_STATS / OBS_ROWMAJOR / LDS_SCRATCH)");
+    if (dst->sim_time != src->sim_time) return fail(BSK_EINVAL, "bsk_fork_device: the handles' bsk_set_sim_time values differ");
+    if (dst->cfg.gravity_model == BSK_GRAV_SH && (dst->sh_cbar != src->sh_cbar || dst->sh_sbar != src->sh_sbar))
+        return fail(BSK_EINVAL, "bsk_fork_device: the handles' spherical-harmonic coefficients differ");
+    return BSK_OK;
+}
+
+// the in-handle fork's gather target: every buffer a handle can have (the optional ones too: a pool staged after the scratch was
+// made must still be forked), laid out with the handle's strides
+int ensure_fork_scratch(bsk_handle* h) {
+    if (h->d_fork_block) return BSK_OK;
+    const size_t S = (size_t)h->ostride;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t sizes[] = {(size_t)h->nf * h->stride * sizeof(double), S * sizeof(int2), 5 * S * sizeof(double), S * sizeof(double), S,
+                            S / 64 * sizeof(unsigned long long), 5 * S * sizeof(double), S * sizeof(double), S * sizeof(double), S * sizeof(int),
+                            S, 5 * S * sizeof(double), S * sizeof(int)};
+    size_t off[13], total = 0;
+    for (int k = 0; k < 13; ++k) { off[k] = total; total += up(sizes[k]); }
+    void* blk = nullptr;
+    HIP_TRY(hipMalloc(&blk, total));
+    char* p = (char*)blk;
+    bsk::ForkSide& f = h->fork_scratch;
+    f.st = (double*)(p + off[0]); f.stride = h->stride; f.cnt = (int2*)(p + off[1]); f.obs = (double*)(p + off[2]); f.ostride = h->ostride;
+    f.reward = (double*)(p + off[3]); f.reason = (unsigned char*)(p + off[4]); f.done_mask = (unsigned long long*)(p + off[5]);
+    f.obs_rm = (double*)(p + off[6]); f.ep_return = (double*)(p + off[7]); f.term_return = (double*)(p + off[8]); f.term_len = (int*)(p + off[9]);
+    f.done = (unsigned char*)(p + off[10]); f.term_obs = (double*)(p + off[11]); f.episodes = (int*)(p + off[12]); f.n = h->n;
+    h->d_fork_block = blk;
+    return BSK_OK;
+}
+
+int do_fork(bsk_handle* dst, bsk_handle* src, const int32_t* d_map) {
+    int rc = fork_compatible(dst, src);
+    if (rc) return rc;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(dst->stream, &cap));
+    if (src == dst) {
+        // every destination receives its source's values from BEFORE the call (a permutation is a valid map): gather into the
+        // scratch, then copy the mapped envs back
+        if (!dst->d_fork_block && cap != hipStreamCaptureStatusNone)
+            return fail(BSK_EINVAL, "bsk_fork_device: the first in-handle fork of a handle allocates its scratch and cannot be captured; "
+                                    "make one in-handle fork outside the capture first");
+        if ((rc = ensure_fork_scratch(dst))) return rc;
+        (void)note_capture(dst);
+        HIP_TRY(bsk::launch_fork(fork_side(dst), dst->fork_scratch, dst->nf, d_map, false, dst->h_err, nullptr, dst->stream));
+        HIP_TRY(bsk::launch_fork(dst->fork_scratch, fork_side(dst), dst->nf, d_map, true, nullptr, dst->d_seal, dst->stream));
+    } else {
+        const bool two_streams = src->stream != dst->stream;
+        if (two_streams) {
+            if (!dst->ev_fork_in) HIP_TRY(hipEventCreateWithFlags(&dst->ev_fork_in, hipEventDisableTiming));
+            if (!dst->ev_fork_out) HIP_TRY(hipEventCreateWithFlags(&dst->ev_fork_out, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(dst->ev_fork_in, src->stream));           // the fork reads what src's queued work leaves
+            HIP_TRY(hipStreamWaitEvent(dst->stream, dst->ev_fork_in, 0));
+        }
+        (void)note_capture(dst);
+        HIP_TRY(bsk::launch_fork(fork_side(src), fork_side(dst), dst->nf, d_map, false, dst->h_err, dst->d_seal, dst->stream));
+        if (two_streams) {
+            HIP_TRY(hipEventRecord(dst->ev_fork_out, dst->stream));          // later work on src cannot overwrite rows the fork still reads
+            HIP_TRY(hipStreamWaitEvent(src->stream, dst->ev_fork_out, 0));
+        }
+    }
+    dst->charge_pos = false;        // (a forked env may carry an empty battery: the bare levels read the charge again, as after bsk_set_state)
+    dst->stats_fresh = dst->wave_sums_fresh = false;
+    dst->stepped = true;
     return BSK_OK;
 }
 
@@ -904,6 +1001,10 @@ void bsk_destroy(bsk_handle* h) {
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_err) (void)hipHostFree(h->h_err);
+    for (void* p : {h->d_fork_block, (void*)h->d_map_stage})
+        if (p) (void)hipFree(p);
+    for (hipEvent_t ev : {h->ev_fork_in, h->ev_fork_out})
+        if (ev) (void)hipEventDestroy(ev);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -924,6 +1025,8 @@ int bsk_set_gravity_sh(bsk_handle* h, int degree, const double* cbar, const doub
     HIP_COPY(hipMemcpy(h->d_sh_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMalloc(&h->d_sh_tab4, tab4.size() * sizeof(double)));
     HIP_COPY(hipMemcpy(h->d_sh_tab4, tab4.data(), tab4.size() * sizeof(double), hipMemcpyHostToDevice));
+    h->sh_cbar.assign(cbar, cbar + (size_t)(degree + 1) * (degree + 2) / 2);
+    h->sh_sbar.assign(sbar, sbar + (size_t)(degree + 1) * (degree + 2) / 2);
     h->sp.sh_degree = degree;
     h->sp.sh_split = lay.split;
     h->sp.sh_chunk1 = lay.chunk1;
@@ -1328,6 +1431,37 @@ int bsk_set_sim_time(bsk_handle* h, double t) {
     if (!h) return fail(BSK_EINVAL, "handle is NULL");
     h->sim_time = t;
     for (int i = 0; i < 3; ++i) h->sp.pc.sun_r0[i] = h->cfg.sun_r0[i] + h->cfg.sun_v[i] * t;
+    return BSK_OK;
+}
+
+int bsk_fork_device(bsk_handle* dst, bsk_handle* src, const int32_t* d_map) {
+    if (!dst || !src || !d_map) return fail(BSK_EINVAL, "dst/src/d_map is NULL");
+    DeviceGuard guard(dst->device);
+    return do_fork(dst, src, d_map);      // asynchronous on dst's stream: no copy, no synchronisation
+}
+
+int bsk_fork(bsk_handle* dst, bsk_handle* src, const int32_t* map) {
+    if (!dst || !src || !map) return fail(BSK_EINVAL, "dst/src/map is NULL");
+    DeviceGuard guard(dst->device);
+    if (!dst->d_map_stage) HIP_TRY(hipMalloc(&dst->d_map_stage, (size_t)dst->ostride * sizeof(int)));   // kept for the handle's lifetime
+    HIP_COPY(hipMemcpyAsync(dst->d_map_stage, map, (size_t)dst->n * sizeof(int), hipMemcpyHostToDevice, dst->stream));
+    int rc = do_fork(dst, src, dst->d_map_stage);
+    if (rc) {
+        HIP_SYNC(hipStreamSynchronize(dst->stream));     // (the pageable map must have left before the caller may free it)
+        return rc;
+    }
+    SYNC_CHECKED(dst);
+    return BSK_OK;
+}
+
+int bsk_select_branches(const double* d_reward_hist, const uint8_t* d_reason_hist, const int32_t* d_first_action, int n_steps, int n_branch,
+                        int group, double gamma, double* d_values, double* d_best_value, int32_t* d_best_action, void* stream) {
+    if (!d_reward_hist || !d_reason_hist || !d_first_action || !d_best_action)
+        return fail(BSK_EINVAL, "reward_hist/reason_hist/first_action/best_action is NULL");
+    if (n_steps < 1 || n_branch < 1 || group < 1) return fail(BSK_EINVAL, "n_steps, n_branch and group must be >= 1");
+    if (n_branch % group != 0) return fail(BSK_EINVAL, "n_branch must be a multiple of group");
+    HIP_TRY(bsk::launch_select(d_reward_hist, d_reason_hist, d_first_action, n_steps, n_branch, group, gamma, d_values, d_best_value,
+                               d_best_action, (hipStream_t)stream));
     return BSK_OK;
 }
 

@@ -452,7 +452,8 @@ constexpr int PART_ALL = 0, PART_ROT = 1, PART_TRA = 2;   // which half of the s
 //  * a poll that does not see its tag within TRI_SPIN_LIMIT reads gives up for the rest of the launch and raises `err` (the
 //    observation is then NaN): every wave reaches the end of the kernel whatever the other one does.
 constexpr int TRI_SPIN_LIMIT = 1 << 20;
-enum { BSK_DEVERR_TRI_EXCHANGE = 1 };      // values of the handle's device error word (bsk_capi.hip: check_device_error)
+enum { BSK_DEVERR_TRI_EXCHANGE = 1, BSK_DEVERR_FORK_MAP = 2 };      // values of the handle's device error word (bsk_capi.hip: check_device_error;
+                                                                    // FORK_MAP: bsk_fork.hip)
 struct TriX {
     double v[4][4][64];                       // translational -> rotational: stage velocity; row 3: the next tick's density
     double s[4][3][64];                       // rotational -> translational: stage attitude

@@ -70,6 +70,33 @@ class _DevArray(object):
         return make_capsule(a["data"][0], a["shape"], a["typestr"], a["strides"], device_id=self._device, owner=self)
 
 
+def _device_ptr(obj, n, typestr="<i4"):
+    """Device address of ``n`` contiguous ``typestr`` elements: an integer pointer, an object with ``__cuda_array_interface__``
+    (torch, cupy, the propagator's own views) or a DLPack producer (``__dlpack__``)."""
+    if isinstance(obj, (int, np.integer)):
+        if not obj:
+            raise ValueError("device pointer is NULL")
+        return int(obj)
+    cai = getattr(obj, "__cuda_array_interface__", None)
+    if cai is not None:
+        shape = tuple(cai["shape"])
+        if cai["typestr"] != typestr or int(np.prod(shape)) != n or (cai.get("strides") not in (None, (np.dtype(typestr).itemsize,))):
+            raise ValueError("expected %d contiguous %s elements, got shape %r typestr %r" % (n, typestr, shape, cai["typestr"]))
+        return int(cai["data"][0])
+    if hasattr(obj, "__dlpack__"):
+        from ... import _dlpack
+        cap = obj.__dlpack__()
+        addr = _dlpack._api.PyCapsule_GetPointer(cap, _dlpack._NAME)
+        t = _dlpack.DLManagedTensor.from_address(addr).dl_tensor
+        shape = [t.shape[k] for k in range(t.ndim)]
+        want = _dlpack.typestr_to_dl(typestr)
+        contiguous = not t.strides or t.ndim == 0 or all(t.strides[k] == int(np.prod(shape[k + 1:])) for k in range(t.ndim))
+        if (t.dtype.code, t.dtype.bits, t.dtype.lanes) != (want.code, want.bits, want.lanes) or int(np.prod(shape)) != n or not contiguous:
+            raise ValueError("expected %d contiguous %s elements from the DLPack producer" % (n, typestr))
+        return int(t.data) + int(t.byte_offset)      # (the producer's capsule, unconsumed, releases the export when it dies)
+    raise TypeError("expected a device pointer, __cuda_array_interface__ or __dlpack__, got %r" % type(obj))
+
+
 class BatchedPropagator(object):
     def __init__(self, cfg, n_envs, device=0, stream=None):
         if not isinstance(cfg, BskConfig):
@@ -84,6 +111,8 @@ class BatchedPropagator(object):
         check(self._lib.bsk_create(C.byref(self.cfg), self.n_envs, self.device,
                                    C.c_void_p(stream) if stream else None, C.byref(h)))
         self._h = h
+        self.sim_time = 0.0          # (set_sim_time)
+        self.gravity_sh = None       # (degree, cbar, sbar) of the last set_gravity_sh
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
@@ -120,6 +149,29 @@ class BatchedPropagator(object):
         if cbar.shape != (sh_size(degree),) or sbar.shape != cbar.shape:
             raise ValueError("cbar/sbar must have %d entries for degree %d" % (sh_size(degree), degree))
         check(self._lib.bsk_set_gravity_sh(self._handle(), int(degree), cbar.ctypes.data, sbar.ctypes.data))
+        self.gravity_sh = (int(degree), cbar.copy(), sbar.copy())      # (what a fork partner must be given: fork_from)
+
+    # ------------------------------------------------------------------ forks
+    def fork_from(self, src, index):
+        """Env j of this propagator becomes an exact copy of env ``index[j]`` of ``src`` (``index[j] == -1``: env j is left as it
+        is); ``src`` may be ``self`` (a permutation is fine: every env receives its source's values from before the call).
+        ``index``: a numpy integer array of ``n_envs`` entries (host path: staged, synchronises, raises on a bad entry), or int32
+        device memory - an integer device pointer, or an object with ``__cuda_array_interface__`` or ``__dlpack__`` (device
+        path: enqueued on this handle's stream, no copy, no synchronisation, capturable; a bad entry is reported by the next
+        synchronising call).  Both handles need the same config up to the output / form flags, the same sim time and the same
+        harmonics (include/bskgpu.h: bsk_fork_device)."""
+        if not isinstance(src, BatchedPropagator):
+            raise TypeError("src must be a BatchedPropagator")
+        if isinstance(index, (np.ndarray, list, tuple)):
+            idx = np.asarray(index)
+            if idx.shape != (self.n_envs,) or not np.issubdtype(idx.dtype, np.integer):
+                raise ValueError("index must be an integer array of shape (%d,)" % self.n_envs)
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            check(self._lib.bsk_fork(self._handle(), src._handle(), idx.ctypes.data))
+            return
+        ptr = _device_ptr(index, self.n_envs)
+        self._fork_index = index          # (alive until the next fork: the kernel reads it asynchronously)
+        check(self._lib.bsk_fork_device(self._handle(), src._handle(), C.c_void_p(ptr)))
 
     # ------------------------------------------------------------------ state
     def reset(self, ic, mask=None):
@@ -368,6 +420,7 @@ class BatchedPropagator(object):
 
     def set_sim_time(self, t):
         check(self._lib.bsk_set_sim_time(self._handle(), float(t)))
+        self.sim_time = float(t)
 
     def set_env_base(self, base):
         """Global index of this handle's env 0 (sharded batches; the device-side reset hashes the global index)."""

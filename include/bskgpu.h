@@ -345,6 +345,41 @@ int bsk_set_env_base(bsk_handle* h, int64_t env_base);
  * sun_r0 + sun_v * t is evaluated at the start of an env step (default 0). */
 int bsk_set_sim_time(bsk_handle* h, double t_seconds);
 
+/* Forks (branching a batch: tree search, receding-horizon lookahead, population training that copies the best envs over the worst).
+ * bsk_fork_device: env j of dst becomes an exact copy of env map[j] of src (map[j] == -1: env j is left as it is).
+ * d_map: int32[n_dst] in DEVICE memory.  src may be dst.  Copied per forked env: every field of the state slab, the counter word
+ * (steps, ticks and FSW phase), the observation rows, reward, reason and done-mask bit; the row-major observation, ep_return,
+ * term_return, term_len, the done byte, terminal observation and episode count where dst has the buffer - from src where src has it
+ * too, else zero (the row-major observation is then the same observation taken from src's rows).  NOT copied: env_base - a forked
+ * env that later auto-resets restarts from pool_slot(dst's env_base + j, copied episode count), the bsk_set_ic_pool rule.
+ *  - Compatibility: BSK_EINVAL unless both handles are on one device, have equal n_rw and byte-identical bsk_configs except for the
+ *    flag bits AUTO_RESET, EPISODE_STATS, OBS_ROWMAJOR and LDS_SCRATCH (they change outputs or the kernel form, never the
+ *    arithmetic), equal bsk_set_sim_time values and, at BSK_GRAV_SH, equal bsk_set_gravity_sh coefficients.
+ *  - A map entry that is neither -1 nor in [0, n_src) is treated as -1 (nothing out of range is read) and raises dst's device error
+ *    word: the next synchronising entry point on dst returns BSK_EHIP once.
+ *  - Ordering: enqueued on dst's stream, no copy and no synchronisation (capturable into a HIP graph).  When the streams differ,
+ *    dst's stream first waits for the work queued on src's stream, and src's stream then waits for the fork, so that later work on
+ *    src cannot overwrite rows the fork still reads (under capture, keep both handles on the capturing stream).
+ *  - In-handle forks (src == dst; overlapping maps such as permutations allowed): every destination receives its source's values
+ *    from before the call.  They gather into a scratch block the first in-handle fork allocates and the handle keeps; that first
+ *    call cannot be captured (BSK_EINVAL under capture).
+ *  - Afterwards dst behaves as after bsk_set_state (the bare levels read the battery charge again), and bsk_get_batch_stats reports
+ *    the sums over its buffers as the fork left them (a reset's seal on the last step's scalars is lifted on the device).
+ * bsk_fork: the same with the map in host memory (staged on dst's stream); synchronises dst's stream and reports the device error. */
+int bsk_fork_device(bsk_handle* dst, bsk_handle* src, const int32_t* d_map);
+int bsk_fork(bsk_handle* dst, bsk_handle* src, const int32_t* map);
+/* Choosing among rollouts: n_branch branches in groups of `group` consecutive ones (n_branch a multiple of group), histories
+ * d_reward_hist f64[n_steps][n_branch] and d_reason_hist u8[n_steps][n_branch] (bsk_step_n's layout), all in DEVICE memory.
+ * Value of branch b:  v = 0, g = 1; for t = 0 .. n_steps-1: v = v + g * reward[t][b]; g = g * gamma; stop after the first t with
+ * reason[t][b] != 0 (its reward included) - each operation rounded on its own, no FMA, so a restatement in numpy gives the same bits.
+ * Best branch of a group: the greatest value, ties to the lowest index, NaN loses to every number (a group of NaNs picks its first).
+ * Outputs: d_values f64[n_branch] (may be NULL), d_best_value f64[n_groups] (may be NULL), d_best_action int32[n_groups] =
+ * d_first_action[best branch].  Enqueued on `stream` (a hipStream_t, NULL = the null stream) of the current device; no copy, no
+ * synchronisation, capturable. */
+int bsk_select_branches(const double* d_reward_hist, const uint8_t* d_reason_hist, const int32_t* d_first_action,
+                        int n_steps, int n_branch, int group, double gamma,
+                        double* d_values, double* d_best_value, int32_t* d_best_action, void* stream);
+
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the
  * three-wave form's barrier-free exchange gives up after 2^20 polls instead of hanging, and says so here. */
