@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct bsk_beam_slot;              // (include/bskgpu.h)
+
 namespace bsk {
 
 // what a reset leaves in the output buffers of the envs it restarts (init_outputs_kernel)
@@ -73,6 +75,9 @@ hipError_t launch_fork(const ForkSide& src, const ForkSide& dst, int nf, const i
 // one action per group of `group` consecutive branches from their rollout histories (bsk_select_branches)
 hipError_t launch_select(const double* reward_hist, const unsigned char* reason_hist, const int* first_action, int n_steps, int n_branch,
                          int group, double gamma, double* values, double* best_value, int* best_action, hipStream_t s);
+// one level of a beam search: the `width` best of every root's 3 * width candidates (bsk_beam_select)
+hipError_t launch_beam(const double* reward, const unsigned char* reason, int n_roots, int width, int level, double weight,
+                       const bsk_beam_slot* in, bsk_beam_slot* out, int* map, double* best_value, int* best_action, hipStream_t s);
 
 // first-level workgroups of stats_kernel at most = entries of the `done_part` scratch
 int stats_done_parts();

@@ -1465,6 +1465,21 @@ int bsk_select_branches(const double* d_reward_hist, const uint8_t* d_reason_his
     return BSK_OK;
 }
 
+int bsk_beam_select(const double* d_reward, const uint8_t* d_reason, int n_roots, int width, int level, double weight,
+                    const bsk_beam_slot* d_in, bsk_beam_slot* d_out, int32_t* d_map, double* d_best_value, int32_t* d_best_action,
+                    void* stream) {
+    if (!d_reward || !d_reason || !d_out || !d_map || !d_best_value || !d_best_action || (!d_in && level != 0))
+        return fail(BSK_EINVAL, "reward/reason/out/map/best_value/best_action is NULL, or in is NULL at a level above 0");
+    if (width < 1 || width > BSK_BEAM_MAX_WIDTH) return fail(BSK_EINVAL, "width must be in 1..81");
+    if (n_roots < 1 || level < 0) return fail(BSK_EINVAL, "n_roots must be >= 1 and level >= 0");
+    if ((int64_t)3 * width * n_roots >= ((int64_t)1 << 31)) return fail(BSK_EINVAL, "3 * width * n_roots candidates must stay below 2^31");
+    if (!std::isfinite(weight)) return fail(BSK_EINVAL, "weight must be finite");
+    if (d_in == d_out) return fail(BSK_EINVAL, "in and out must be distinct slot buffers");
+    HIP_TRY(bsk::launch_beam(d_reward, d_reason, n_roots, width, level, weight, d_in, d_out, d_map, d_best_value, d_best_action,
+                             (hipStream_t)stream));
+    return BSK_OK;
+}
+
 int bsk_set_env_base(bsk_handle* h, int64_t env_base) {
     if (!h) return fail(BSK_EINVAL, "handle is NULL");
     if (env_base < 0 || env_base > 0xFFFFFFFFll) return fail(BSK_EINVAL, "env_base must be in 0..2^32-1");

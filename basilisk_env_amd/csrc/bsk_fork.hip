@@ -3,7 +3,9 @@
 //   fork_kernel     env j of one handle becomes an exact copy of env map[j] of another (or the same) handle: every buffer that
 //                   decides an env's future or reports its present (bsk_fork_device, include/bskgpu.h)
 //   select_kernel   discounted value of every branch of a rollout history, best branch per group of `group` (bsk_select_branches)
-// Compiled with -ffp-contract=off (Makefile): select_kernel's additions and products are the ones a numpy restatement makes.
+//   beam_kernel     one level of a beam search: the `width` best of every root's 3 * width candidates (bsk_beam_select)
+// Compiled with -ffp-contract=off (Makefile): select_kernel's and beam_kernel's additions and products are the ones a numpy
+// restatement makes.
 #include "bsk_device.hpp"
 #include "bsk_aux.hpp"
 
@@ -134,6 +136,88 @@ hipError_t launch_select(const double* reward_hist, const unsigned char* reason_
     const int n_groups = n_branch / group;
     hipLaunchKernelGGL(select_kernel, dim3((n_groups + 3) / 4), dim3(256), 0, s, reward_hist, reason_hist, first_action, n_steps, n_branch,
                        group, n_groups, gamma, values, best_value, best_action);
+    return hipGetLastError();
+}
+
+// One level of a beam search.  A workgroup takes 256 / (3 * width) whole roots, one thread per candidate, so that small widths fill
+// the workgroup with roots instead of idle lanes (width 1: 85 roots, width 9: 9, width 81: 1).  Each thread builds its candidate
+// from the parent slot, puts (value, valid) in LDS and counts the candidates of its root that come before it; the order is total,
+// so that count is its rank and no two candidates share one.  The threads of rank < width write their slot: plain stores, one
+// barrier, no atomics.  Nothing outside the 3 * width * n_roots candidates and the width * n_roots parent slots is read.
+constexpr int BEAM_BLOCK = 256;
+__global__ __launch_bounds__(BEAM_BLOCK) void beam_kernel(const double* __restrict__ reward, const unsigned char* __restrict__ reason,
+                                                           int n_roots, int width, int level, double weight,
+                                                           const bsk_beam_slot* __restrict__ in, bsk_beam_slot* __restrict__ out,
+                                                           int* __restrict__ map, double* __restrict__ best_value,
+                                                           int* __restrict__ best_action) {
+#pragma clang fp contract(off)
+    __shared__ double s_value[BEAM_BLOCK];
+    __shared__ unsigned char s_valid[BEAM_BLOCK];
+    const int nc = 3 * width;                                  // candidates per root (<= 243)
+    const int per = BEAM_BLOCK / nc;                           // roots per workgroup
+    const int t = (int)threadIdx.x;
+    const int lr = t / nc, i = t - lr * nc;                    // root within the workgroup, candidate within the root
+    const int root = (int)blockIdx.x * per + lr;
+    const bool active = lr < per && root < n_roots;
+    const int c = active ? root * nc + i : 0;                  // (< 3 * width * n_roots < 2^31)
+    double v = __builtin_nan("");                              // an invalid candidate: NaN, first -1, no flags
+    int first = -1;
+    unsigned flags = 0u;
+    if (active) {
+        const int a = i % 3;
+        if (level == 0) {
+            if (i < 3) {                                       // slot 0 of the root is the one real parent
+                v = 0.0 + weight * reward[c];
+                first = a;
+                flags = BSK_BEAM_VALID | (reason[c] == 0 ? BSK_BEAM_LIVE : 0u);
+            }
+        } else {
+            const bsk_beam_slot ps = in[c / 3];
+            const bool live = (ps.flags & BSK_BEAM_LIVE) != 0u;
+            if ((ps.flags & BSK_BEAM_VALID) && (live || a == 0)) {   // a finished sequence continues as one candidate
+                if (live) {
+                    const double p = weight * reward[c];
+                    v = ps.value + p;
+                } else {
+                    v = ps.value;
+                }
+                first = ps.first;
+                flags = BSK_BEAM_VALID | (live && reason[c] == 0 ? BSK_BEAM_LIVE : 0u);
+            }
+        }
+    }
+    const bool ok = flags != 0u;
+    s_value[t] = v;
+    s_valid[t] = ok ? 1 : 0;
+    __syncthreads();
+    if (!active) return;
+    const int base = lr * nc;
+    int rank = 0;
+    for (int j = 0; j < nc; ++j) {                             // candidates of this root that come before candidate i
+        const bool okj = s_valid[base + j] != 0;
+        const bool before = okj != ok ? okj : (ok ? beats(s_value[base + j], j, v, i) : j < i);
+        rank += before ? 1 : 0;
+    }
+    if (rank < width) {
+        const int s = root * width + rank;
+        bsk_beam_slot o;
+        o.value = v;
+        o.first = first;
+        o.flags = flags;
+        out[s] = o;
+        map[s] = ok ? c : -1;
+        if (rank == 0) {
+            best_value[root] = v;
+            best_action[root] = first;
+        }
+    }
+}
+
+hipError_t launch_beam(const double* reward, const unsigned char* reason, int n_roots, int width, int level, double weight,
+                       const bsk_beam_slot* in, bsk_beam_slot* out, int* map, double* best_value, int* best_action, hipStream_t s) {
+    const int per = BEAM_BLOCK / (3 * width);
+    hipLaunchKernelGGL(beam_kernel, dim3((n_roots + per - 1) / per), dim3(BEAM_BLOCK), 0, s, reward, reason, n_roots, width, level, weight,
+                       in, out, map, best_value, best_action);
     return hipGetLastError();
 }
 

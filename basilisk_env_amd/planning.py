@@ -6,6 +6,10 @@ greatest discounted return (``bsk_select_branches``).  Branch b takes base-3 dig
 the branch's return stops after the first step that ends its episode (that step's reward and penalty included).  All three are
 enqueued on the root's stream from buffers built once, so ``plan()`` - and a step of the root on the planned actions - can be
 captured into one HIP graph.  An extra beside the reference surface: the reference has no forking or planning.
+
+``BeamPlanner`` looks further ahead than 3**depth branches allow: per root it keeps the ``width`` best action sequences, and every
+level forks them into their 3 children (``bsk_fork_device``), steps the children once (``bsk_step_device``), keeps the ``width``
+best children (``bsk_beam_select``) and forks them back, so its cost grows linearly with the ``horizon``.
 """
 import ctypes as C
 
@@ -15,6 +19,10 @@ from . import _lib
 from ._lib import FLAG_AUTO_RESET, FLAG_EPISODE_STATS, FLAG_LDS_SCRATCH, FLAG_OBS_ROWMAJOR, GRAV_SH, check
 
 MAX_DEPTH = 6
+MAX_WIDTH = 81                  # BSK_BEAM_MAX_WIDTH: 3 * width candidates of a root fit one 256-thread workgroup
+# bsk_beam_slot (include/bskgpu.h): one beam entry; flags bit 0 valid, bit 1 live
+BEAM_SLOT = np.dtype([("value", "<f8"), ("first", "<i4"), ("flags", "<u4")])
+BEAM_VALID, BEAM_LIVE = 1, 2
 # the flags a branch handle drops: they change what a step writes or the kernel's form, never its arithmetic (bsk_fork_device)
 BRANCH_CLEARED_FLAGS = FLAG_AUTO_RESET | FLAG_EPISODE_STATS | FLAG_OBS_ROWMAJOR | FLAG_LDS_SCRATCH
 
@@ -79,44 +87,116 @@ def select_best(values, group):
     return best, v[np.arange(v.shape[0]), best]
 
 
-class LookaheadPlanner(object):
-    """Exhaustive lookahead of ``depth`` env steps (3**depth branches per root), then ``tail_steps`` steps of ``tail_action``.
+def check_beam_args(n_roots, width, horizon, gamma):
+    """Argument rules of ``BeamPlanner`` (no device needed) -> the level weights w_t, f64[horizon]."""
+    if not (isinstance(width, (int, np.integer)) and 1 <= width <= MAX_WIDTH):
+        raise ValueError("width must be an integer in 1..%d" % MAX_WIDTH)
+    if not (isinstance(horizon, (int, np.integer)) and horizon >= 1):
+        raise ValueError("horizon must be a positive integer")
+    if not np.isfinite(gamma):
+        raise ValueError("gamma must be finite")
+    if 3 * int(width) * int(n_roots) >= 2 ** 31:
+        raise ValueError("3 * width * n_roots = %d children: must stay below 2**31" % (3 * int(width) * int(n_roots)))
+    w = level_weights(gamma, horizon)
+    if not np.isfinite(w).all():
+        raise ValueError("gamma**t overflows within the horizon")
+    return w
 
-    ``root``: a ``BatchedPropagator`` (``substeps`` required) or a ``LeoPowerAttVecEnv`` (its ``propagator`` and ``substeps``).
-    The planner owns a branch propagator of ``n_roots * 3**depth`` envs on the root's device and stream with the root's config
-    minus ``BRANCH_CLEARED_FLAGS``, the root's sim time and spherical-harmonic field, and device buffers built once: the fork map,
-    the action table, the histories and the outputs.  A later ``set_sim_time`` / ``set_gravity_sh`` on the root needs a new planner
-    (the fork refuses partners that differ)."""
 
-    def __init__(self, root, depth=2, tail_steps=0, tail_action=0, gamma=1.0, substeps=None):
+def level_weights(gamma, horizon):
+    """w_0 = 1, w_t = w_{t-1} * gamma: the factors bsk_select_branches applies to step t, rounded in the same order."""
+    w, out = 1.0, []
+    for _ in range(int(horizon)):
+        out.append(w)
+        w = w * float(gamma)
+    return np.array(out)
+
+
+def beam_candidates(reward, reason, n_roots, width, level, weight, slots_in=None):
+    """The 3 * width * n_roots candidates of one beam level (bsk_beam_select, include/bskgpu.h) -> BEAM_SLOT[]: candidate c is
+    child c % 3 of slot c // 3.  Level 0 ignores ``slots_in``: only slot 0 of each root is a parent.  Later levels: valid iff the
+    parent is valid and live, or the action is 0 (a finished sequence continues as one candidate); value = value[p] + w * r[c]
+    while the parent is live (product, then sum), else value[p].  Invalid candidates: value NaN, first -1, flags 0."""
+    n = 3 * int(width) * int(n_roots)
+    r = np.asarray(reward, dtype=np.float64)[:n]
+    q = np.asarray(reason)[:n]
+    c = np.arange(n)
+    p, a = c // 3, c % 3
+    with np.errstate(invalid="ignore", over="ignore"):
+        if level == 0:
+            valid = p % int(width) == 0
+            live = q == 0
+            value = np.float64(0.0) + weight * r
+            first = a
+        else:
+            par = np.asarray(slots_in).view(BEAM_SLOT)[p]
+            p_live = (par["flags"] & BEAM_LIVE) != 0
+            valid = ((par["flags"] & BEAM_VALID) != 0) & (p_live | (a == 0))
+            live = p_live & (q == 0)
+            value = np.where(p_live, par["value"] + weight * r, par["value"])
+            first = par["first"]
+    out = np.zeros(n, dtype=BEAM_SLOT)
+    out["value"] = np.where(valid, value, np.nan)
+    out["first"] = np.where(valid, first, -1)
+    out["flags"] = np.where(valid, BEAM_VALID | np.where(live, BEAM_LIVE, 0), 0)
+    return out
+
+
+def beam_order(cand, n_roots):
+    """Candidate indices of every root in rank order -> int64[n_roots][3 * width]: valid before invalid; valid ones by the greater
+    value, NaN after every number, equal values to the lower index (select_best's rule); invalid ones by index."""
+    n = len(cand)
+    c = np.arange(n)
+    valid = (cand["flags"] & BEAM_VALID) != 0
+    key = np.where(valid, -cand["value"], 0.0)             # (ascending sorts put NaN last; -0.0 and 0.0 compare equal)
+    return np.lexsort((c, key, ~valid, c // (n // int(n_roots)))).reshape(int(n_roots), -1)
+
+
+def beam_select_ref(reward, reason, n_roots, width, level, weight, slots_in=None):
+    """numpy restatement of one ``bsk_beam_select`` level (include/bskgpu.h), bit for bit -> (slots_out BEAM_SLOT[n_roots * width],
+    map int32[n_roots * width], best_value f64[n_roots], best_action int32[n_roots])."""
+    cand = beam_candidates(reward, reason, n_roots, width, level, weight, slots_in)
+    keep = beam_order(cand, n_roots)[:, :int(width)].ravel()
+    out = cand[keep]
+    fmap = np.where((out["flags"] & BEAM_VALID) != 0, keep, -1).astype(np.int32)
+    return out, fmap, out["value"][::int(width)].copy(), out["first"][::int(width)].copy()
+
+
+class _BranchPlanner(object):
+    """What both planners share: the root checks, branch handles on the root's device and stream (the root's config minus
+    ``BRANCH_CLEARED_FLAGS``, its sim time and spherical-harmonic field), device buffers built once, and reading them back."""
+    _handle_names = ()
+
+    def _attach(self, root, substeps):
         from .simulators.dynamics import BatchedPropagator
         prop = getattr(root, "propagator", root)
         if substeps is None:
             substeps = getattr(root, "substeps", None)
         if not isinstance(prop, BatchedPropagator):
-            raise TypeError("LookaheadPlanner needs a BatchedPropagator or a LeoPowerAttVecEnv over one (sharded propagators are not "
-                            "supported: fork within each shard)")
+            raise TypeError("%s needs a BatchedPropagator or a LeoPowerAttVecEnv over one (sharded propagators are not "
+                            "supported: fork within each shard)" % type(self).__name__)
         if substeps is None or int(substeps) < 1:
             raise ValueError("substeps (RK4 steps per env step) is required for a BatchedPropagator root")
-        self.n_roots = int(prop.n_envs)
-        self.n_branch = check_args(self.n_roots, depth, tail_steps, tail_action, gamma)
-        self.depth, self.tail_steps, self.tail_action, self.gamma = int(depth), int(tail_steps), int(tail_action), float(gamma)
-        self.group = 3 ** self.depth
-        self.n_steps = self.depth + self.tail_steps
-        self.substeps = int(substeps)
-        self.root = prop
+        self.root, self.substeps, self.n_roots = prop, int(substeps), int(prop.n_envs)
+        self._buffers = []
+
+    def _open(self, sizes):
+        """Creates the branch handles ``sizes`` names ((attribute, n_envs) pairs), then ``_build()``."""
+        from .simulators.dynamics import BatchedPropagator
+        prop = self.root
         if prop.cfg.gravity_model == GRAV_SH and prop.gravity_sh is None:
             raise ValueError("the root has no spherical-harmonic field yet (set_gravity_sh)")
-        self._buffers = []
         cfg = prop.cfg.copy()
         cfg.flags &= ~BRANCH_CLEARED_FLAGS
         self.stream = prop.stream_ptr()
-        self.branch = BatchedPropagator(cfg, self.n_branch, device=prop.device, stream=self.stream)
         try:
-            if prop.sim_time:
-                self.branch.set_sim_time(prop.sim_time)
-            if prop.gravity_sh is not None:
-                self.branch.set_gravity_sh(*prop.gravity_sh)
+            for name, n in sizes:
+                h = BatchedPropagator(cfg, n, device=prop.device, stream=self.stream)
+                setattr(self, name, h)
+                if prop.sim_time:
+                    h.set_sim_time(prop.sim_time)
+                if prop.gravity_sh is not None:
+                    h.set_gravity_sh(*prop.gravity_sh)
             self._build()
         except BaseException:
             self.close()
@@ -134,6 +214,62 @@ class LookaheadPlanner(object):
             _hip.stream_sync(self.stream)              # (pageable source: the copy must be done before `host` goes)
         return b
 
+    def _read(self, buf, dtype, count):
+        from . import _hip
+        out = np.empty(count, dtype=dtype)
+        _hip.check(_hip.runtime().hipMemcpyAsync(C.c_void_p(out.ctypes.data), C.c_void_p(buf.ptr), out.nbytes, _hip.hipMemcpyDeviceToHost,
+                                                 C.c_void_p(self.stream)), "hipMemcpyAsync")
+        self.root.sync()
+        for name in self._handle_names:
+            getattr(self, name).sync()  # (reports a fork's device error, if any)
+        return out
+
+    def _actions_view(self):
+        from .simulators.dynamics.propagator import _DevArray
+        return _DevArray(self.d_best_action.ptr, (self.n_roots,), "<i4", owner=self.root, device=self.root.device, stream=self.stream)
+
+    def plan_host(self):
+        """``plan()``, then -> (actions int32 (n_roots,), values f64 (n_roots,)) on the host (synchronises)."""
+        self.plan()
+        return self.last_actions(), self.last_values()
+
+    def last_actions(self):
+        return self._read(self.d_best_action, np.int32, self.n_roots)
+
+    def last_values(self):
+        """best value per root of the last plan (the best branch's, or the best kept sequence's)"""
+        return self._read(self.d_best_value, np.float64, self.n_roots)
+
+    def close(self):
+        for name in self._handle_names:
+            h = getattr(self, name, None)
+            if h is not None:
+                h.sync()
+                h.close()
+                setattr(self, name, None)
+        for b in getattr(self, "_buffers", []):
+            b.free()
+        self._buffers = []
+
+
+class LookaheadPlanner(_BranchPlanner):
+    """Exhaustive lookahead of ``depth`` env steps (3**depth branches per root), then ``tail_steps`` steps of ``tail_action``.
+
+    ``root``: a ``BatchedPropagator`` (``substeps`` required) or a ``LeoPowerAttVecEnv`` (its ``propagator`` and ``substeps``).
+    The planner owns a branch propagator of ``n_roots * 3**depth`` envs on the root's device and stream with the root's config
+    minus ``BRANCH_CLEARED_FLAGS``, the root's sim time and spherical-harmonic field, and device buffers built once: the fork map,
+    the action table, the histories and the outputs.  A later ``set_sim_time`` / ``set_gravity_sh`` on the root needs a new planner
+    (the fork refuses partners that differ)."""
+    _handle_names = ("branch",)
+
+    def __init__(self, root, depth=2, tail_steps=0, tail_action=0, gamma=1.0, substeps=None):
+        self._attach(root, substeps)
+        self.n_branch = check_args(self.n_roots, depth, tail_steps, tail_action, gamma)
+        self.depth, self.tail_steps, self.tail_action, self.gamma = int(depth), int(tail_steps), int(tail_action), float(gamma)
+        self.group = 3 ** self.depth
+        self.n_steps = self.depth + self.tail_steps
+        self._open([("branch", self.n_branch)])
+
     def _build(self):
         nb, T = self.n_branch, self.n_steps
         table = action_table(self.n_roots, self.depth, self.tail_steps, self.tail_action)
@@ -150,7 +286,6 @@ class LookaheadPlanner(object):
         """fork -> ``depth + tail_steps`` env steps of every branch -> per-root choice, all enqueued on the root's stream (no copy,
         no synchronisation).  -> int32 (n_roots,) device view of the chosen actions (``__cuda_array_interface__`` / DLPack):
         ``root.step_device(view.__cuda_array_interface__["data"][0], ...)`` and ``torch.from_dlpack(view)`` take it as it is."""
-        from .simulators.dynamics.propagator import _DevArray
         self.branch.fork_from(self.root, self.d_map.ptr)
         self.branch.step_n(self.n_steps, self.substeps, self.d_actions.ptr, d_reward_hist=self.d_reward_hist.ptr,
                            d_reason_hist=self.d_reason_hist.ptr)
@@ -158,48 +293,92 @@ class LookaheadPlanner(object):
                                               C.c_void_p(self.d_first_action.ptr), self.n_steps, self.n_branch, self.group, self.gamma,
                                               C.c_void_p(self.d_values.ptr), C.c_void_p(self.d_best_value.ptr),
                                               C.c_void_p(self.d_best_action.ptr), C.c_void_p(self.stream)))
-        return _DevArray(self.d_best_action.ptr, (self.n_roots,), "<i4", owner=self.root, device=self.root.device, stream=self.stream)
-
-    def _read(self, buf, dtype, count):
-        from . import _hip
-        out = np.empty(count, dtype=dtype)
-        _hip.check(_hip.runtime().hipMemcpyAsync(C.c_void_p(out.ctypes.data), C.c_void_p(buf.ptr), out.nbytes, _hip.hipMemcpyDeviceToHost,
-                                                 C.c_void_p(self.stream)), "hipMemcpyAsync")
-        self.root.sync()
-        self.branch.sync()           # (reports a fork's device error, if any)
-        return out
-
-    def plan_host(self):
-        """``plan()``, then -> (actions int32 (n_roots,), values f64 (n_roots,)) on the host (synchronises)."""
-        self.plan()
-        return self.last_actions(), self.last_values()
-
-    def last_actions(self):
-        return self._read(self.d_best_action, np.int32, self.n_roots)
-
-    def last_values(self):
-        """best branch value per root of the last plan"""
-        return self._read(self.d_best_value, np.float64, self.n_roots)
+        return self._actions_view()
 
     def last_branch_values(self):
         """value of every branch of the last plan, f64 (n_roots, 3**depth)"""
         return self._read(self.d_values, np.float64, self.n_branch).reshape(self.n_roots, self.group)
 
-    def close(self):
-        if getattr(self, "branch", None) is not None:
-            self.branch.sync()
-            self.branch.close()
-            self.branch = None
-        for b in getattr(self, "_buffers", []):
-            b.free()
-        self._buffers = []
+
+class BeamPlanner(_BranchPlanner):
+    """Beam search over ``horizon`` env steps, keeping the ``width`` best action sequences of every root (bsk_beam_select).
+
+    ``root`` as for ``LookaheadPlanner`` (same refusals).  The planner owns two branch propagators on the root's stream: ``beam``
+    (``n_roots * width`` envs, the kept sequences: slot s belongs to root s // width) and ``children`` (``3 * width * n_roots``
+    envs: child c is slot c // 3 after action c % 3), and builds every device buffer once.  ``plan()`` forks the root into every
+    slot, then per level forks the slots into their children, steps the children once, keeps the ``width`` best children of every
+    root and forks them back into the slots (not after the last level): 4 * horizon launches, capturable into one HIP graph.
+    A sequence whose episode has ended continues with action 0 alone and keeps its value.  With ``width >= 3**horizon`` the
+    best value equals ``LookaheadPlanner(depth=horizon)``'s bit for bit; ``width == 1`` is a greedy one-step lookahead.  Without
+    ``FLAG_DESAT`` actions 1 and 2 command the same thing: their children tie exactly and both take a slot."""
+    _handle_names = ("beam", "children")
+
+    def __init__(self, root, width=9, horizon=32, gamma=1.0, substeps=None):
+        self._attach(root, substeps)
+        self.weights = check_beam_args(self.n_roots, width, horizon, gamma)
+        self.width, self.horizon, self.gamma = int(width), int(horizon), float(gamma)
+        self.n_slots = self.n_roots * self.width
+        self.n_children = 3 * self.n_slots
+        self._open([("beam", self.n_slots), ("children", self.n_children)])
+
+    def _build(self):
+        ns, nc = self.n_slots, self.n_children
+        self.d_root_map = self._dev(4 * ns, (np.arange(ns) // self.width).astype(np.int32))
+        self.d_child_map = self._dev(4 * nc, (np.arange(nc) // 3).astype(np.int32))
+        self.d_actions = self._dev(4 * nc, (np.arange(nc) % 3).astype(np.int32))
+        self.d_slots = [self._dev(BEAM_SLOT.itemsize * ns), self._dev(BEAM_SLOT.itemsize * ns)]
+        self.d_maps = self._dev(4 * ns * self.horizon)                      # int32[horizon][n_slots]
+        self.d_best_value = self._dev(8 * self.n_roots)
+        self.d_best_action = self._dev(4 * self.n_roots)
+        views = self.children.device_views()
+        self._d_reward = views["reward"].__cuda_array_interface__["data"][0]
+        self._d_reason = views["reason"].__cuda_array_interface__["data"][0]
+
+    def plan(self):
+        """root -> every slot, then ``horizon`` levels of fork -> step -> select -> fork back, all enqueued on the root's stream
+        (no copy, no synchronisation).  -> int32 (n_roots,) device view of the chosen actions, as ``LookaheadPlanner.plan()``."""
+        lib = _lib.load()
+        vp = C.c_void_p
+        self.beam.fork_from(self.root, self.d_root_map.ptr)
+        for t in range(self.horizon):
+            self.children.fork_from(self.beam, self.d_child_map.ptr)
+            self.children.step_device(self.d_actions.ptr, self.substeps)
+            d_map = self.d_maps.ptr + 4 * self.n_slots * t
+            d_in = vp(self.d_slots[(t + 1) % 2].ptr) if t else None
+            check(lib.bsk_beam_select(vp(self._d_reward), vp(self._d_reason), self.n_roots, self.width, t, float(self.weights[t]),
+                                      d_in, vp(self.d_slots[t % 2].ptr), vp(d_map), vp(self.d_best_value.ptr),
+                                      vp(self.d_best_action.ptr), vp(self.stream)))
+            if t + 1 < self.horizon:
+                self.beam.fork_from(self.children, d_map)
+        return self._actions_view()
+
+    def _last_slots(self):
+        return self._read(self.d_slots[(self.horizon - 1) % 2], BEAM_SLOT, self.n_slots)
+
+    def last_beam_values(self):
+        """discounted value of every kept sequence of the last plan, f64 (n_roots, width) in rank order (NaN: no sequence)"""
+        return self._last_slots()["value"].reshape(self.n_roots, self.width)
+
+    def last_sequences(self):
+        """the kept action sequences of the last plan, int32 (n_roots, width, horizon) in rank order, rebuilt from the level maps
+        (the candidate c of a slot took action c % 3 from slot c // 3 of the level before).  A sequence whose episode ended
+        continues with action 0; a slot without a sequence reads -1."""
+        maps = self._read(self.d_maps, np.int32, self.n_slots * self.horizon).reshape(self.horizon, self.n_slots)
+        seq = np.full((self.n_slots, self.horizon), -1, dtype=np.int32)
+        c = maps[-1].astype(np.int64)
+        for t in range(self.horizon - 1, -1, -1):
+            ok = c >= 0
+            seq[ok, t] = c[ok] % 3
+            if t:
+                c = np.where(ok, maps[t - 1][np.where(ok, c // 3, 0)], -1)
+        return seq.reshape(self.n_roots, self.width, self.horizon)
 
 
-def demo(n=64, steps=40, depth=2, substeps=600, seed=0):
+def demo(n=64, steps=40, depth=2, substeps=600, seed=0, beam=None):
     """A small batch of the full scenario (power system, Sun, drag, desaturation) run for ``steps`` env steps of ``substeps`` RK4
     steps under the planner and under each constant action, from the same initial conditions; prints the mean return per env
-    (rewards summed until an env's episode ends).  Informative only: how the planner compares with constant actions is not a
-    property the project asserts."""
+    (rewards summed until an env's episode ends).  ``beam``: (width, horizon) adds a ``BeamPlanner`` line.  Informative only: how
+    the planners compare with constant actions is not a property the project asserts."""
     from ._lib import FLAG_DESAT, FLAG_DRAG, FLAG_POWER, FLAG_SUN_THIRD_BODY, GRAV_PM_J2
     from .simulators.dynamics import BatchedPropagator, default_config
     from .simulators.initial_conditions.batch import sample_ic_batch
@@ -208,10 +387,14 @@ def demo(n=64, steps=40, depth=2, substeps=600, seed=0):
     cfg.max_length = int(steps)
     ic = sample_ic_batch(n, 4, seed=seed)
     results = {}
-    for policy in ("planner", 0, 1, 2):
+    for policy in ("planner",) + (("beam",) if beam else ()) + (0, 1, 2):
         p = BatchedPropagator(cfg, n)
         p.reset(ic)
-        planner = LookaheadPlanner(p, depth=depth, substeps=substeps) if policy == "planner" else None
+        planner = None
+        if policy == "planner":
+            planner = LookaheadPlanner(p, depth=depth, substeps=substeps)
+        elif policy == "beam":
+            planner = BeamPlanner(p, width=beam[0], horizon=beam[1], substeps=substeps)
         ret, live = np.zeros(n), np.ones(n, dtype=bool)
         for _ in range(int(steps)):
             act = planner.plan_host()[0] if planner else np.full(n, policy, np.int32)
@@ -225,10 +408,12 @@ def demo(n=64, steps=40, depth=2, substeps=600, seed=0):
         if planner:
             planner.close()
         p.close()
+    names = {"planner": "planner d=%d" % depth, "beam": "beam w=%d h=%d" % tuple(beam) if beam else ""}
     for policy, r in results.items():
-        print("%-12s mean return %.6f" % ("planner d=%d" % depth if policy == "planner" else "action %d" % policy, r))
+        print("%-12s mean return %.6f" % (names.get(policy, "action %s" % policy), r))
     return results
 
 
 if __name__ == "__main__":
-    demo()
+    import sys
+    demo(beam=(9, 32) if "--beam" in sys.argv[1:] else None)

@@ -379,6 +379,39 @@ int bsk_fork(bsk_handle* dst, bsk_handle* src, const int32_t* map);
 int bsk_select_branches(const double* d_reward_hist, const uint8_t* d_reason_hist, const int32_t* d_first_action,
                         int n_steps, int n_branch, int group, double gamma,
                         double* d_values, double* d_best_value, int32_t* d_best_action, void* stream);
+/* One level of a beam search (BeamPlanner in basilisk_env_amd/planning.py): the `width` best action sequences of every root.
+ * Slot s (n_roots * width of them) belongs to root s / width and holds a bsk_beam_slot: `value` the discounted return so far,
+ * `first` the sequence's first action, flags bit 0 (BSK_BEAM_VALID) the slot holds a sequence, bit 1 (BSK_BEAM_LIVE) no step of it
+ * has ended its episode yet.  Candidate c (3 * width * n_roots of them) is env c of the children handle after one env step:
+ * parent slot p = c / 3, action a = c % 3, d_reward f64[] and d_reason u8[] the children's outputs (bsk_get_obs_device).
+ *  - level 0 (d_in ignored, may be NULL): c is valid iff p % width == 0 (slot 0 of each root is the one real parent);
+ *    value = 0.0 + weight * reward[c], live = reason[c] == 0, first = a.
+ *  - level >= 1: c is valid iff p is valid and (p is live or a == 0): a finished sequence continues as ONE candidate, not three.
+ *    value = p live ? value[p] + weight * reward[c] : value[p] (product and sum each rounded on their own, no FMA: the order of
+ *    bsk_select_branches), live = live[p] && reason[c] == 0, first = first[p].
+ *  - an invalid candidate has value NaN, first -1 and no flags.
+ *  - order within a root: valid candidates before invalid ones; valid ones by bsk_select_branches' rule (the greater value first,
+ *    NaN after every number, equal values to the lower index); invalid ones by index.
+ * Outputs: the candidate of rank r < width fills d_out[root * width + r], and d_map[root * width + r] = c when it is valid, -1
+ * otherwise (the map of bsk_fork_device that moves the children into the next level's parents); d_best_value[root] and
+ * d_best_action[root] are the value and first action of rank 0 (valid whenever the root has a valid candidate, as at level 0
+ * and whenever d_in is the previous level's d_out).  `weight` is the level's discount w_t: w_0 = 1, w_t = w_{t-1} * gamma.
+ * Without BSK_FLAG_DESAT actions 1 and 2 command the same thing: their children tie exactly and both take a slot.
+ * BSK_EINVAL (before any launch): a NULL pointer other than d_in at level 0, width outside 1..BSK_BEAM_MAX_WIDTH, n_roots < 1,
+ * 3 * width * n_roots >= 2^31, level < 0, a non-finite weight, d_in == d_out.  d_in and d_out are distinct buffers (the caller
+ * double-buffers them).  Enqueued on `stream` (a hipStream_t, NULL = the null stream) of the current device; no copy, no
+ * synchronisation, capturable. */
+#define BSK_BEAM_MAX_WIDTH 81
+#define BSK_BEAM_VALID 1u
+#define BSK_BEAM_LIVE 2u
+typedef struct bsk_beam_slot {
+    double value;
+    int32_t first;
+    uint32_t flags;
+} bsk_beam_slot;
+int bsk_beam_select(const double* d_reward, const uint8_t* d_reason, int n_roots, int width, int level, double weight,
+                    const bsk_beam_slot* d_in, bsk_beam_slot* d_out, int32_t* d_map, double* d_best_value, int32_t* d_best_action,
+                    void* stream);
 
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the
