@@ -63,11 +63,26 @@ class BskConfig(C.Structure):
         return out
 
 
+POLICY_RELU, POLICY_TANH = 0, 1
+POLICY_GREEDY, POLICY_SAMPLE = 0, 1
+
+
+class BskPolicySpec(C.Structure):
+    """Mirror of ``struct bsk_policy_spec`` (include/bskgpu.h)."""
+    _fields_ = [
+        ("abi_version", u32), ("struct_size", u32),
+        ("n_hidden", i32), ("hidden", i32 * 3), ("activation", i32),
+        ("has_value", i32), ("v_n_hidden", i32), ("v_hidden", i32 * 3), ("v_activation", i32),
+    ]
+
+
 EXPORTS = [
     "bsk_default_config", "bsk_create", "bsk_destroy", "bsk_set_gravity_sh", "bsk_reset", "bsk_step",
     "bsk_step_device", "bsk_step_device_i64", "bsk_step_n", "bsk_get_episode_device", "bsk_get_batch_stats_device", "bsk_set_step_stats", "bsk_reset_from_pool_device", "bsk_debug_counters", "bsk_debug_words", "bsk_get_obs", "bsk_get_obs_rowmajor", "bsk_get_obs_device", "bsk_get_obs_state", "bsk_get_stream", "bsk_get_terminal_obs_device", "bsk_get_state_device", "bsk_get_batch_stats", "bsk_n_fields",
     "bsk_get_state", "bsk_set_state", "bsk_get_counters", "bsk_set_counters", "bsk_set_ic_pool", "bsk_sample_ic_pool", "bsk_reset_from_pool", "bsk_get_ic_pool", "bsk_get_terminal_obs", "bsk_set_env_base", "bsk_set_sim_time", "bsk_sync",
     "bsk_fork_device", "bsk_fork", "bsk_select_branches", "bsk_beam_select",
+    "bsk_policy_n_params", "bsk_policy_create", "bsk_policy_set_params", "bsk_policy_destroy", "bsk_policy_set_rng", "bsk_policy_get_rng",
+    "bsk_policy_act", "bsk_policy_rollout",
     "bsk_profile_begin", "bsk_profile_set_stride", "bsk_profile_end", "bsk_profile_end_samples", "bsk_calibrate_fp64", "bsk_kernel_info", "bsk_last_error", "bsk_version",
 ]
 
@@ -133,10 +148,17 @@ def load():
                        ("bsk_step_n", [vp, vp, C.c_int32, C.c_int, C.c_int, vp, vp, vp]),
                        ("bsk_fork_device", [vp, vp, vp]), ("bsk_fork", [vp, vp, vp]),
                        ("bsk_select_branches", [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp]),
-                       ("bsk_beam_select", [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp])):
+                       ("bsk_beam_select", [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp]),
+                       ("bsk_policy_n_params", [P(BskPolicySpec)]), ("bsk_policy_create", [P(BskPolicySpec), vp, C.c_int, P(vp)]),
+                       ("bsk_policy_set_params", [vp, vp]), ("bsk_policy_destroy", [vp]), ("bsk_policy_set_rng", [vp, C.c_uint64, C.c_uint64]),
+                       ("bsk_policy_get_rng", [vp, P(C.c_uint64), P(C.c_uint64)]),
+                       ("bsk_policy_act", [vp, vp, C.c_int64, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, C.c_int64, vp]),
+                       ("bsk_policy_rollout", [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp])):
         # (a BSKGPU_LIB variant built from an older tree - kernel A/B against a previous round - may predate these)
         if hasattr(lib, name) or not os.environ.get("BSKGPU_LIB"):
             getattr(lib, name).argtypes = args
+    if hasattr(lib, "bsk_policy_destroy"):
+        lib.bsk_policy_destroy.restype = None
     lib.bsk_get_obs.argtypes = [vp, vp, vp, vp, vp]
     lib.bsk_get_obs_device.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(C.c_int64)]
     lib.bsk_get_obs_state.argtypes = [vp, vp, vp, vp, vp]

@@ -8,6 +8,7 @@
 //   reset_from_pool_kernel / init_outputs_kernel    device-side (re)start from the staged pool, first observations
 #include "bsk_device.hpp"
 #include "bsk_aux.hpp"
+#include "bsk_philox.hpp"
 
 #include <algorithm>
 
@@ -216,22 +217,9 @@ __global__ void scatter_reset_kernel(double* __restrict__ st, int64_t stride, in
 }
 
 // ---------------------------------------------------------------------------------------------
-// On-device initial-condition sampler (row f4).  Philox4x32-10 (Salmon et al. 2011), written out by
-// hand: counter (slot, draw, 0, 0), key (seed_lo, seed_hi); every call yields four 32-bit words =
-// two 53-bit uniforms, so each pool slot is reproducible independently of every other slot.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned* out) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1,
-                       n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// On-device initial-condition sampler (row f4).  Philox4x32-10 (bsk_philox.hpp): counter (slot, draw, 0, 0), key (seed_lo,
+// seed_hi); every call yields four 32-bit words = two 53-bit uniforms, so each pool slot is reproducible independently of every
+// other slot.
 // two uniforms in [0, 1) with 53 random bits each (same bit recipe as numpy's random_double)
 __device__ __forceinline__ void philox_u2(unsigned slot, unsigned draw, unsigned k0, unsigned k1, double& a, double& b) {
     unsigned w[4];

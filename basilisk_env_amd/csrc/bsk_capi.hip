@@ -16,6 +16,7 @@
 #include "../../include/bskgpu.h"
 #include "bsk_aux.hpp"
 #include "bsk_launch.hpp"
+#include "bsk_policy.hpp"
 #include "bsk_rollout.hpp"
 
 namespace {
@@ -472,6 +473,16 @@ struct bsk_handle {
     hipEvent_t ev_fork_in = nullptr, ev_fork_out = nullptr;
 };
 
+// bsk_policy_*: the fused MLP policy (kernel and layout: bsk_policy.hip)
+struct bsk_policy {
+    bsk::PolicyLayout lay;
+    int device = 0;
+    float* d_params = nullptr;             // the device layout of the parameters (bsk_policy.hpp)
+    unsigned long long* d_rng = nullptr;   // {seed, draw}: read by sample-mode launches, draw advanced behind each of them
+    int* d_act = nullptr;                  // bsk_policy_rollout's scratch row of actions (d_action_hist == NULL)
+    int act_cap = 0;
+};
+
 namespace {
 
 struct DeviceGuard {
@@ -755,6 +766,51 @@ int do_fork(bsk_handle* dst, bsk_handle* src, const int32_t* d_map) {
     dst->charge_pos = false;        // (a forked env may carry an empty battery: the bare levels read the charge again, as after bsk_set_state)
     dst->stats_fresh = dst->wave_sums_fresh = false;
     dst->stepped = true;
+    return BSK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// The policy (bsk_policy_*; kernel: bsk_policy.hip)
+int policy_spec_layout(const bsk_policy_spec* spec, bsk::PolicyLayout& lay) {
+    if (!spec) return fail(BSK_EINVAL, "spec is NULL");
+    if (spec->abi_version != BSK_ABI_VERSION || spec->struct_size != sizeof(bsk_policy_spec))
+        return fail(BSK_EABI, "bsk_policy_spec abi_version / struct_size mismatch");
+    if (const char* why = bsk::policy_layout(*spec, lay)) return fail(BSK_EINVAL, std::string("bsk_policy_spec: ") + why);
+    return BSK_OK;
+}
+
+// every argument of a policy launch, checked before anything is enqueued
+int policy_check_act(const bsk_policy* p, const double* d_obs, int64_t obs_stride, int n, int64_t env_base, int mode,
+                     const int32_t* d_action, const float* d_value, const float* d_logits, int64_t out_stride) {
+    if (!p || !d_obs || !d_action) return fail(BSK_EINVAL, "policy/d_obs/d_action is NULL");
+    if (n < 1 || n > (1 << 28)) return fail(BSK_EINVAL, "n must be in 1..2^28");
+    if (obs_stride < n) return fail(BSK_EINVAL, "obs_stride must be >= n");
+    if (env_base < 0) return fail(BSK_EINVAL, "env_base must be >= 0");
+    if (mode != BSK_POLICY_GREEDY && mode != BSK_POLICY_SAMPLE) return fail(BSK_EINVAL, "mode must be BSK_POLICY_GREEDY or BSK_POLICY_SAMPLE");
+    if (d_value && p->lay.v.n_layers == 0) return fail(BSK_EINVAL, "d_value given, but the policy has no value network");
+    if (d_logits && out_stride < n) return fail(BSK_EINVAL, "out_stride must be >= n");
+    return BSK_OK;
+}
+
+int policy_launch(bsk_policy* p, const double* d_obs, int64_t obs_stride, int n, int64_t env_base, int mode, int32_t* d_action,
+                  float* d_logp, float* d_value, float* d_logits, int64_t out_stride, hipStream_t stream) {
+    bsk::PolicyArgs a;
+    a.params = p->d_params; a.a = p->lay.a; a.v = p->lay.v; a.obs = d_obs; a.obs_stride = obs_stride; a.n = n;
+    a.env_base = (unsigned long long)env_base; a.mode = mode; a.rng = p->d_rng; a.action = d_action; a.logp = d_logp;
+    a.value = d_value; a.logits = d_logits; a.out_stride = out_stride; a.width = p->lay.width;
+    if (!d_value) a.v.n_layers = 0;            // (nobody asked for the value: its network is not evaluated)
+    HIP_TRY(bsk::launch_policy(a, stream));
+    if (mode == BSK_POLICY_SAMPLE) HIP_TRY(bsk::launch_policy_advance(p->d_rng, stream));
+    return BSK_OK;
+}
+
+// The entry points that touch the parameters or the draw counter from the host come after everything queued on the policy's device:
+// a policy keeps no stream of its own, and the stream of its last launch may be gone with the handle that owned it.
+int policy_upload(bsk_policy* p, const float* params) {
+    std::vector<float> dev;
+    bsk::policy_pack(p->lay, params, dev);
+    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old parameters)
+    HIP_COPY(hipMemcpy(p->d_params, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice));
     return BSK_OK;
 }
 
@@ -1477,6 +1533,131 @@ int bsk_beam_select(const double* d_reward, const uint8_t* d_reason, int n_roots
     if (d_in == d_out) return fail(BSK_EINVAL, "in and out must be distinct slot buffers");
     HIP_TRY(bsk::launch_beam(d_reward, d_reason, n_roots, width, level, weight, d_in, d_out, d_map, d_best_value, d_best_action,
                              (hipStream_t)stream));
+    return BSK_OK;
+}
+
+int bsk_policy_n_params(const bsk_policy_spec* spec) {
+    bsk::PolicyLayout lay;
+    int rc = policy_spec_layout(spec, lay);
+    return rc ? rc : lay.n_params;
+}
+
+int bsk_policy_create(const bsk_policy_spec* spec, const float* params, int device_id, bsk_policy** out) {
+    if (!out) return fail(BSK_EINVAL, "out is NULL");
+    *out = nullptr;
+    bsk::PolicyLayout lay;
+    int rc = policy_spec_layout(spec, lay);
+    if (rc) return rc;
+    if (!params) return fail(BSK_EINVAL, "params is NULL");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(BSK_ENODEV, "no HIP device visible: libbskgpu has no CPU fallback");
+    if (device_id < 0 || device_id >= ndev) return fail(BSK_ENODEV, "device_id out of range");
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device_id));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(BSK_ENODEV, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    DeviceGuard guard(device_id);
+    bsk_policy* p = new bsk_policy();
+    p->lay = lay;
+    p->device = device_id;
+    const unsigned long long rng0[2] = {0ull, 0ull};
+    auto init = [&]() -> int {
+        HIP_TRY(hipMalloc(&p->d_params, (size_t)lay.n_device * sizeof(float)));
+        HIP_TRY(hipMalloc(&p->d_rng, sizeof rng0));
+        HIP_COPY(hipMemcpy(p->d_rng, rng0, sizeof rng0, hipMemcpyHostToDevice));
+        return policy_upload(p, params);
+    };
+    rc = init();
+    if (rc) { bsk_policy_destroy(p); return rc; }
+    *out = p;
+    return BSK_OK;
+}
+
+int bsk_policy_set_params(bsk_policy* p, const float* params) {
+    if (!p || !params) return fail(BSK_EINVAL, "policy/params is NULL");
+    DeviceGuard guard(p->device);
+    return policy_upload(p, params);
+}
+
+void bsk_policy_destroy(bsk_policy* p) {
+    if (!p) return;
+    DeviceGuard guard(p->device);
+    if (p->d_params || p->d_rng) (void)hipDeviceSynchronize();
+    if (p->d_params) (void)hipFree(p->d_params);
+    if (p->d_rng) (void)hipFree(p->d_rng);
+    if (p->d_act) (void)hipFree(p->d_act);
+    delete p;
+}
+
+int bsk_policy_set_rng(bsk_policy* p, uint64_t seed, uint64_t draw) {
+    if (!p) return fail(BSK_EINVAL, "policy is NULL");
+    DeviceGuard guard(p->device);
+    const unsigned long long w[2] = {seed, draw};
+    HIP_SYNC(hipDeviceSynchronize());
+    HIP_COPY(hipMemcpy(p->d_rng, w, sizeof w, hipMemcpyHostToDevice));
+    return BSK_OK;
+}
+
+int bsk_policy_get_rng(bsk_policy* p, uint64_t* seed, uint64_t* draw) {
+    if (!p) return fail(BSK_EINVAL, "policy is NULL");
+    DeviceGuard guard(p->device);
+    unsigned long long w[2];
+    HIP_SYNC(hipDeviceSynchronize());
+    HIP_COPY(hipMemcpy(w, p->d_rng, sizeof w, hipMemcpyDeviceToHost));
+    if (seed) *seed = w[0];
+    if (draw) *draw = w[1];
+    return BSK_OK;
+}
+
+int bsk_policy_act(bsk_policy* p, const double* d_obs, int64_t obs_stride, int n, int64_t env_base, int mode,
+                   int32_t* d_action, float* d_logp, float* d_value, float* d_logits, int64_t out_stride, void* stream) {
+    int rc = policy_check_act(p, d_obs, obs_stride, n, env_base, mode, d_action, d_value, d_logits, out_stride);
+    if (rc) return rc;
+    DeviceGuard guard(p->device);
+    return policy_launch(p, d_obs, obs_stride, n, env_base, mode, d_action, d_logp, d_value, d_logits, out_stride, (hipStream_t)stream);
+}
+
+int bsk_policy_rollout(bsk_policy* p, bsk_handle* h, int mode, int substeps, int n_steps,
+                       double* d_obs_hist, double* d_reward_hist, uint8_t* d_reason_hist,
+                       int32_t* d_action_hist, float* d_logp_hist, float* d_value_hist) {
+    if (!p || !h) return fail(BSK_EINVAL, "policy/handle is NULL");
+    if (substeps < 1 || n_steps < 1) return fail(BSK_EINVAL, "substeps and n_steps must be >= 1");
+    if (p->device != h->device) return fail(BSK_EINVAL, "bsk_policy_rollout: the policy and the handle live on different devices");
+    int rc = policy_check_act(p, h->d_obs, h->ostride, h->n, (int64_t)h->env_base, mode, h->d_act, d_value_hist, nullptr, 0);
+    if (rc) return rc;
+    if (h->cfg.gravity_model == BSK_GRAV_SH && !h->sp.sh_tab)
+        return fail(BSK_EINVAL, "BSK_GRAV_SH: call bsk_set_gravity_sh before stepping");
+    if ((h->cfg.flags & BSK_FLAG_AUTO_RESET) && h->n_pool == 0)
+        return fail(BSK_EINVAL, "BSK_FLAG_AUTO_RESET: call bsk_set_ic_pool before stepping");
+    DeviceGuard guard(h->device);
+    if (!d_action_hist && p->act_cap < h->n) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        HIP_TRY(hipStreamIsCapturing(h->stream, &cap));
+        if (cap != hipStreamCaptureStatusNone)
+            return fail(BSK_EINVAL, "bsk_policy_rollout: the first rollout without d_action_hist allocates the policy's scratch row and "
+                                    "cannot be captured; make one such call outside the capture first");
+        if (p->d_act) {
+            HIP_SYNC(hipDeviceSynchronize());                   // (a queued rollout may still use the smaller row)
+            (void)hipFree(p->d_act);
+            p->d_act = nullptr;
+            p->act_cap = 0;
+        }
+        HIP_TRY(hipMalloc(&p->d_act, (size_t)h->ostride * sizeof(int)));
+        p->act_cap = (int)h->ostride;
+    }
+    const size_t n = (size_t)h->n;
+    for (int t = 0; t < n_steps; ++t) {
+        int32_t* act = d_action_hist ? d_action_hist + t * n : p->d_act;
+        rc = policy_launch(p, h->d_obs, h->ostride, h->n, (int64_t)h->env_base, mode, act, d_logp_hist ? d_logp_hist + t * n : nullptr,
+                           d_value_hist ? d_value_hist + t * n : nullptr, nullptr, 0, h->stream);
+        if (rc) return rc;
+        if ((rc = do_step(h, act, substeps, 1))) return rc;
+        if (d_obs_hist || d_reward_hist || d_reason_hist)
+            HIP_TRY(bsk::launch_hist_row(h->d_obs, h->d_reward, h->d_reason, h->ostride, h->n, d_obs_hist ? d_obs_hist + t * 5 * n : nullptr,
+                                         d_reward_hist ? d_reward_hist + t * n : nullptr, d_reason_hist ? d_reason_hist + t * n : nullptr,
+                                         h->stream));
+    }
     return BSK_OK;
 }
 

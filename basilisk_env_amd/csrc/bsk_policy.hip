@@ -1,0 +1,213 @@
+// bsk_policy.hip — a small fused MLP policy over the five observation rows (a translation unit of its own; touches neither the
+// step nor the rollout kernels):
+//   policy_kernel           action network (5 -> hidden... -> 3 logits) and optional value network (5 -> hidden... -> 1) for n
+//                           spacecraft in one launch: greedy or sampled action, log-probability, value, logits (bsk_policy_act)
+//   policy_advance_kernel   the policy's draw counter += 1, behind a sample-mode launch
+// The arithmetic is the definition in include/bskgpu.h: every layer output is ONE k-ordered chain of f32 fused multiply-adds that
+// starts from the bias.  Each fmaf below is written out, so the chain does not depend on -ffp-contract.
+#include "../../include/bskgpu.h"
+#include "bsk_philox.hpp"
+#include "bsk_policy.hpp"
+
+namespace bsk {
+
+// One lane per spacecraft and POLICY_WAVES waves per 64 spacecraft: the waves of a workgroup share the spacecraft and split each hidden
+// layer's units between them, 16 at a time.  65 536 spacecraft are only 1 024 wave-columns, one per SIMD: with one wave each, a launch
+// is as long as one wave's whole chain with nothing to hide its load latencies behind (measured: 31.8 us for relu [64, 64]); four
+// waves cut the chain into four and give every SIMD four waves to switch between.  The weights are wave-uniform: a lane's 16
+// neighbouring units share the input h_k, so per k a wave makes one LDS read (h_k of its 64 spacecraft), one scalar load (16
+// consecutive weights of Wt[k][j0 .. j0+16), SGPR operands) and 8 independent v_pk_fma_f32 - no weight ever enters a VGPR or the
+// LDS.  Activations go from layer to layer through LDS columns [unit][lane]: conflict-free, one barrier per layer.  Every unit's
+// chain is evaluated by exactly one wave in the definition's order, so the split changes no bit.  (A v_mfma_f32_32x32x2_f32 form of
+// the hidden layers was measured level with this one at [64, 64]: docs/KERNEL_NOTES.md.)
+constexpr int POLICY_LANES = 64;
+constexpr int POLICY_WAVES = 4;
+constexpr int POLICY_BLOCK = POLICY_LANES * POLICY_WAVES;
+
+__device__ __forceinline__ float policy_act(float z, int act) {
+    return act == BSK_POLICY_TANH ? tanhf(z) : (z > 0.0f ? z : 0.0f);
+}
+
+// a hidden layer: hout[j] = act(b[j] + sum_k Wt[k][j] * hin[k]), k ascending; wave w takes the blocks of POLICY_JB units w, w + 4, ...
+__device__ __forceinline__ void policy_hidden(const float* __restrict__ wt, const float* __restrict__ bias, int K, int N, int act,
+                                              const float* hin, float* hout, int lane, int wave) {
+    for (int j0 = wave * POLICY_JB; j0 < N; j0 += POLICY_WAVES * POLICY_JB) {
+        float z[POLICY_JB];
+#pragma unroll
+        for (int jj = 0; jj < POLICY_JB; ++jj) z[jj] = bias[j0 + jj];
+#pragma unroll 4
+        for (int k = 0; k < K; ++k) {
+            const float h = hin[k * POLICY_LANES + lane];
+            const float* __restrict__ w = wt + k * N + j0;
+#pragma unroll
+            for (int jj = 0; jj < POLICY_JB; ++jj) z[jj] = __builtin_fmaf(w[jj], h, z[jj]);
+        }
+#pragma unroll
+        for (int jj = 0; jj < POLICY_JB; ++jj) hout[(j0 + jj) * POLICY_LANES + lane] = policy_act(z[jj], act);
+    }
+}
+
+// the output layer (linear): POLICY_OB rows, the ones beyond the fan-out are zero rows of the device layout.  Wave 0 alone evaluates
+// it: it is the wave that reads the observations and stores the results.
+__device__ __forceinline__ void policy_output(const float* __restrict__ wt, const float* __restrict__ bias, int K, const float* hin,
+                                              int lane, float* out) {
+#pragma unroll
+    for (int jj = 0; jj < POLICY_OB; ++jj) out[jj] = bias[jj];
+#pragma unroll 4
+    for (int k = 0; k < K; ++k) {
+        const float h = hin[k * POLICY_LANES + lane];
+        const float* __restrict__ w = wt + k * POLICY_OB;
+#pragma unroll
+        for (int jj = 0; jj < POLICY_OB; ++jj) out[jj] = __builtin_fmaf(w[jj], h, out[jj]);
+    }
+}
+
+__device__ __forceinline__ void policy_net(const float* __restrict__ params, const PolicyNet& net, const float* x, float* buf0,
+                                           float* buf1, int lane, int wave, float* out) {
+    __syncthreads();                       // (the previous network's last reads of the buffers)
+    if (wave == 0) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) buf0[i * POLICY_LANES + lane] = x[i];
+    }
+    __syncthreads();
+    float* hin = buf0;
+    float* hout = buf1;
+    const int last = net.n_layers - 1;
+    for (int l = 0; l < last; ++l) {
+        policy_hidden(params + net.w[l], params + net.b[l], net.K[l], net.N[l], net.act, hin, hout, lane, wave);
+        __syncthreads();                   // (layer l + 1 reads what every wave wrote, and overwrites what every wave has read)
+        float* t = hin; hin = hout; hout = t;
+    }
+    if (wave == 0) policy_output(params + net.w[last], params + net.b[last], net.K[last], hin, lane, out);
+}
+
+// (value, index) order of the greedy choice: the greater logit wins, equal logits go to the lower index, a NaN loses to every
+// number (bsk_fork.hip: beats() - the rule of bsk_select_branches)
+__device__ __forceinline__ bool policy_beats(float a, float b) {      // a (the later index) displaces b (the earlier one)
+    const bool na = a != a, nb = b != b;
+    if (na != nb) return nb;
+    return !na && a > b;
+}
+
+__global__ __launch_bounds__(POLICY_BLOCK) void policy_kernel(const PolicyArgs p) {
+    extern __shared__ float policy_lds[];
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));       // (wave-uniform: weight addresses stay scalar)
+    const int64_t j = (int64_t)blockIdx.x * POLICY_LANES + lane;
+    const bool live = j < p.n;
+    float* buf0 = policy_lds;
+    float* buf1 = policy_lds + p.width * POLICY_LANES;
+    const float* __restrict__ params = p.params;
+
+    float x[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const double o = live && wave == 0 ? p.obs[(int64_t)i * p.obs_stride + j] : 0.0;       // (tail lanes read nothing)
+        x[i] = __builtin_fmaf((float)o, params[i], params[5 + i]);
+    }
+    float l[POLICY_OB] = {0.0f, 0.0f, 0.0f, 0.0f};
+    policy_net(params, p.a, x, buf0, buf1, lane, wave, l);
+    float val[POLICY_OB] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (p.v.n_layers > 0) policy_net(params, p.v, x, buf0, buf1, lane, wave, val);      // (workgroup-uniform)
+    if (wave != 0) return;                 // (no barrier from here on)
+
+    const float m = fmaxf(fmaxf(l[0], l[1]), l[2]);
+    const float e0 = expf(l[0] - m), e1 = expf(l[1] - m), e2 = expf(l[2] - m);
+    const float s = (e0 + e1) + e2;
+    int a = 0;
+    if (p.mode == BSK_POLICY_SAMPLE) {
+        const unsigned long long seed = p.rng[0], draw = p.rng[1], env = p.env_base + (unsigned long long)j;
+        unsigned w[4];
+        philox4x32_10((unsigned)env, (unsigned)(env >> 32), (unsigned)draw, (unsigned)(draw >> 32), (unsigned)seed, (unsigned)(seed >> 32), w);
+        const float u = (float)(w[0] >> 8) * 0x1p-24f;
+        const float c0 = e0 / s, c1 = c0 + e1 / s;
+        a = u < c0 ? 0 : (u < c1 ? 1 : 2);
+    } else {
+        float best = l[0];
+        if (policy_beats(l[1], best)) { best = l[1]; a = 1; }
+        if (policy_beats(l[2], best)) { best = l[2]; a = 2; }
+    }
+    if (!live) return;
+    p.action[j] = a;
+    if (p.logp) p.logp[j] = ((a == 0 ? l[0] : (a == 1 ? l[1] : l[2])) - m) - logf(s);
+    if (p.value) p.value[j] = val[0];
+    if (p.logits) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) p.logits[(int64_t)i * p.out_stride + j] = l[i];
+    }
+}
+
+__global__ void policy_advance_kernel(unsigned long long* rng) { rng[1] += 1ull; }
+
+hipError_t launch_policy(const PolicyArgs& args, hipStream_t s) {
+    const size_t lds = (size_t)2 * args.width * POLICY_LANES * sizeof(float);
+    hipLaunchKernelGGL(policy_kernel, dim3((unsigned)((args.n + POLICY_LANES - 1) / POLICY_LANES)), dim3(POLICY_BLOCK), lds, s, args);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_advance(unsigned long long* rng, hipStream_t s) {
+    hipLaunchKernelGGL(policy_advance_kernel, dim3(1), dim3(1), 0, s, rng);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// host side: the spec's rules, the C-ABI parameter count and the device layout
+static const char* policy_net_layout(int n_hidden, const int32_t* hidden, int activation, int n_out, int out_block, int& n_params,
+                                     int& n_device, int& width, PolicyNet& net) {
+    if (n_hidden < 0 || n_hidden > POLICY_MAX_LAYERS - 1) return "a network has 0 to 3 hidden layers";
+    if (activation != BSK_POLICY_RELU && activation != BSK_POLICY_TANH) return "activation must be BSK_POLICY_RELU or BSK_POLICY_TANH";
+    net = PolicyNet{};
+    net.n_layers = n_hidden + 1;
+    net.act = activation;
+    int K = 5;
+    for (int l = 0; l <= n_hidden; ++l) {
+        const bool out = l == n_hidden;
+        const int fan_out = out ? n_out : hidden[l];
+        if (!out && (fan_out < 16 || fan_out > 128 || fan_out % 16 != 0)) return "a hidden layer is 16 ... 128 units wide, in multiples of 16";
+        const int N = out ? out_block : fan_out;
+        net.K[l] = K;
+        net.N[l] = N;
+        net.w[l] = n_device;
+        n_device += (K * N + 15) / 16 * 16;
+        net.b[l] = n_device;
+        n_device += (N + 15) / 16 * 16;
+        n_params += K * fan_out + fan_out;
+        if (K > width) width = K;
+        K = fan_out;
+    }
+    return nullptr;
+}
+
+const char* policy_layout(const bsk_policy_spec& spec, PolicyLayout& out) {
+    out = PolicyLayout{};
+    out.n_params = 10;
+    out.n_device = POLICY_HEAD;
+    out.width = 8;
+    if (const char* why = policy_net_layout(spec.n_hidden, spec.hidden, spec.activation, 3, POLICY_OB, out.n_params, out.n_device, out.width, out.a))
+        return why;
+    if (spec.has_value != 0 && spec.has_value != 1) return "has_value must be 0 or 1";
+    if (spec.has_value)
+        return policy_net_layout(spec.v_n_hidden, spec.v_hidden, spec.v_activation, 1, POLICY_OB, out.n_params, out.n_device, out.width, out.v);
+    return nullptr;
+}
+
+void policy_pack(const PolicyLayout& lay, const float* params, std::vector<float>& dev) {
+    dev.assign((size_t)lay.n_device, 0.0f);
+    for (int i = 0; i < 10; ++i) dev[i] = params[i];
+    const float* src = params + 10;
+    const PolicyNet* nets[2] = {&lay.a, &lay.v};
+    const int n_out[2] = {3, 1};
+    for (int t = 0; t < 2; ++t) {
+        const PolicyNet& net = *nets[t];
+        for (int l = 0; l < net.n_layers; ++l) {
+            const int K = net.K[l], N = net.N[l], fan_out = l == net.n_layers - 1 ? n_out[t] : N;
+            for (int jo = 0; jo < fan_out; ++jo)
+                for (int k = 0; k < K; ++k) dev[(size_t)net.w[l] + (size_t)k * N + jo] = src[(size_t)jo * K + k];
+            src += (size_t)fan_out * K;
+            for (int jo = 0; jo < fan_out; ++jo) dev[(size_t)net.b[l] + jo] = src[jo];
+            src += fan_out;
+        }
+    }
+}
+
+}  // namespace bsk

@@ -494,6 +494,50 @@ class LeoPowerAttVecEnv(_Base):
         done = tv["done"] if "done" in tv else tv["reason"].ne(0)
         return tv["obs_n51"], tv["reward"], done, info
 
+    def step_policy(self, policy, mode="greedy"):
+        """``step_tensors`` with the action chosen on the device by a ``DevicePolicy`` (basilisk_env_amd/policy.py): one policy
+        launch on the observation buffers as they stand and one step launch on its actions, both on the env's stream - no torch
+        kernel, no copy, no synchronisation.  Same preconditions and return value as ``step_tensors``; ``info`` also holds
+        ``action`` (N,) int32, ``logp`` (N,) float32 and, with a value network, ``value`` (N,) float32 of the observation the action
+        was chosen FROM: zero-copy views of the policy's output buffers, valid until its next launch.  A first call (and one
+        after the policy's buffers grew) allocates them: make it outside a graph capture."""
+        import torch
+        from ..simulators.dynamics import BatchedPropagator
+        if self.auto_reset and not self.device_reset:
+            raise ValueError("step_policy needs device_reset_pool > 0 (device-side auto-reset) or auto_reset=False")
+        prop = self.propagator
+        if not isinstance(prop, BatchedPropagator):
+            raise TypeError("step_policy needs an env over one BatchedPropagator (sharded batches: one policy per shard)")
+        tv = self._torch_views()
+        pv = tv.get("policy")
+        if pv is None or pv["policy"] is not policy or pv["out"] is not policy._out:
+            if policy.device != prop.device:
+                raise ValueError("the policy lives on device %d, the env on device %d" % (policy.device, prop.device))
+            want = ("logp", "value") if policy.spec.value_hidden is not None else ("logp",)
+            pv = {"policy": policy, "want": want, "obs_ptr": tv["obs"].data_ptr(), "stride": tv["obs"].stride(0), "views": None, "out": None}
+        self._order_streams(tv, before=True)
+        out = policy.enqueue(pv["obs_ptr"], pv["stride"], self.num_envs, mode, pv["want"], getattr(prop, "env_base", 0), tv["stream"])
+        if pv["out"] is not out:
+            from ..simulators.dynamics.propagator import _DevArray
+            kw = {"owner": prop, "device": prop.device, "stream": tv["stream"]}
+            pv["views"] = {k: torch.as_tensor(_DevArray(out[k].ptr, (self.num_envs,), "<i4" if k == "action" else "<f4", **kw), device=tv["device"])
+                           for k in ("action",) + pv["want"]}
+            pv["out"] = out
+            tv["policy"] = pv
+        self._dev_actions = pv["views"]["action"]
+        prop.step_device(out["action"].ptr, self.substeps)
+        self._order_streams(tv, before=False)
+        self._ic = None if self.device_reset else self._ic
+        info = {"reason": tv["reason"]}
+        info.update(pv["views"])
+        if "terminal_obs_n51" in tv:
+            info["terminal_observation"] = tv["terminal_obs_n51"]
+            info["episodes"] = tv["episodes"]
+        if "terminal_return" in tv:
+            info["episode_r"], info["episode_l"], info["episode_return"] = tv["terminal_return"], tv["terminal_length"], tv["episode_return"]
+        done = tv["done"] if "done" in tv else tv["reason"].ne(0)
+        return tv["obs_n51"], tv["reward"], done, info
+
     def close(self):
         self._tviews = None            # torch views alias device buffers the propagator is about to free
         self._dev_actions = None

@@ -1,0 +1,486 @@
+"""A small MLP policy evaluated on the GPU by the library itself, and closed-loop rollouts built from it.
+
+``DevicePolicy`` holds one or two multilayer perceptrons over the five observation rows (``bsk_policy_*``, include/bskgpu.h): the
+action network (5 -> hidden... -> 3 logits) and an optional value network (5 -> hidden... -> 1).  ``act`` is ONE launch that reads
+the observation rows where the step kernel leaves them and writes int32 actions ``step_device`` reads in place (plus, when asked,
+log-probability, value and logits); ``rollout`` closes the loop on the device for whole episodes.  Both are enqueue-only and can be
+captured into a HIP graph.  An extra beside the reference surface: the reference's agent runs its network in
+stable-baselines, outside the env.
+
+The arithmetic is fixed to the bit (include/bskgpu.h): every layer output is one k-ordered chain of f32 fused multiply-adds from
+the bias.  ``mlp_ref`` / ``act_ref`` restate it in numpy - for ``relu`` networks logits, value and greedy actions come out equal
+to the kernel's bit for bit - and need no device, like the argument rules.
+"""
+import ctypes as C
+from collections import namedtuple
+
+import numpy as np
+
+from . import _lib
+from ._lib import POLICY_GREEDY, POLICY_RELU, POLICY_SAMPLE, POLICY_TANH, BskPolicySpec, check
+
+MAX_HIDDEN_LAYERS = 3
+ACTIVATIONS = {"relu": POLICY_RELU, "tanh": POLICY_TANH}
+MODES = {"greedy": POLICY_GREEDY, "sample": POLICY_SAMPLE}
+
+#: hidden: widths of the action network's hidden layers; value_hidden: the value network's, or None (no value network)
+Spec = namedtuple("Spec", "hidden activation value_hidden value_activation")
+
+
+def _check_net(hidden, activation, what):
+    hidden = tuple(hidden)
+    if len(hidden) > MAX_HIDDEN_LAYERS:
+        raise ValueError("%s: 0 to %d hidden layers, got %d" % (what, MAX_HIDDEN_LAYERS, len(hidden)))
+    for w in hidden:
+        if not (isinstance(w, (int, np.integer)) and 16 <= w <= 128 and w % 16 == 0):
+            raise ValueError("%s: a hidden layer is 16 ... 128 units wide in multiples of 16, got %r" % (what, w))
+    if activation not in ACTIVATIONS:
+        raise ValueError("%s: activation must be 'relu' or 'tanh', got %r" % (what, activation))
+    return tuple(int(w) for w in hidden)
+
+
+def check_spec(hidden, activation="relu", value_hidden=None, value_activation=None):
+    """Argument rules of a policy (no device needed) -> ``Spec``.  ``value_hidden=None``: no value network; its activation
+    defaults to the action network's."""
+    hidden = _check_net(hidden, activation, "action network")
+    if value_hidden is None:
+        if value_activation is not None:
+            raise ValueError("value_activation given without a value network")
+        return Spec(hidden, activation, None, None)
+    value_activation = activation if value_activation is None else value_activation
+    return Spec(hidden, activation, _check_net(value_hidden, value_activation, "value network"), value_activation)
+
+
+def _as_spec(spec):
+    return spec if isinstance(spec, Spec) else check_spec(*spec)
+
+
+def c_spec(spec):
+    """``Spec`` -> the C-ABI's ``bsk_policy_spec``."""
+    spec = _as_spec(spec)
+    c = BskPolicySpec()
+    c.abi_version, c.struct_size = _lib.BSK_ABI_VERSION, C.sizeof(BskPolicySpec)
+    c.n_hidden, c.activation = len(spec.hidden), ACTIVATIONS[spec.activation]
+    for k, w in enumerate(spec.hidden):
+        c.hidden[k] = w
+    if spec.value_hidden is not None:
+        c.has_value, c.v_n_hidden, c.v_activation = 1, len(spec.value_hidden), ACTIVATIONS[spec.value_activation]
+        for k, w in enumerate(spec.value_hidden):
+            c.v_hidden[k] = w
+    return c
+
+
+def layer_shapes(spec):
+    """-> ([(out, in), ...] of the action network, the same of the value network or None)."""
+    spec = _as_spec(spec)
+
+    def net(hidden, n_out):
+        widths = (5,) + tuple(hidden) + (n_out,)
+        return [(widths[k + 1], widths[k]) for k in range(len(widths) - 1)]
+    return net(spec.hidden, 3), (None if spec.value_hidden is None else net(spec.value_hidden, 1))
+
+
+def n_params(spec):
+    """Floats in the parameter block: in_scale[5], in_shift[5], then W[out][in] and b[out] per layer (``bsk_policy_n_params``)."""
+    a, v = layer_shapes(spec)
+    return 10 + sum(o * i + o for o, i in a + (v or []))
+
+
+def pack_params(spec, layers, value_layers=None, in_scale=None, in_shift=None):
+    """The parameter block of include/bskgpu.h as one float32 array: ``in_scale[5]``, ``in_shift[5]`` (default 1 and 0), then per
+    layer ``W[out][in]`` row-major (``nn.Linear.weight``) and ``b[out]``; the action network's ``layers`` = [(W, b), ...] first,
+    then ``value_layers``."""
+    spec = _as_spec(spec)
+    a, v = layer_shapes(spec)
+    if (v is None) != (value_layers is None):
+        raise ValueError("value_layers must be given exactly when the spec has a value network")
+    parts = [np.ones(5, np.float32) if in_scale is None else np.asarray(in_scale, np.float32).reshape(-1),
+             np.zeros(5, np.float32) if in_shift is None else np.asarray(in_shift, np.float32).reshape(-1)]
+    if parts[0].shape != (5,) or parts[1].shape != (5,):
+        raise ValueError("in_scale and in_shift have 5 entries each")
+    for shapes, given, what in ((a, layers, "layers"), (v, value_layers, "value_layers")):
+        if shapes is None:
+            continue
+        given = list(given)
+        if len(given) != len(shapes):
+            raise ValueError("%s: expected %d (W, b) pairs, got %d" % (what, len(shapes), len(given)))
+        for (o, i), (W, b) in zip(shapes, given):
+            W, b = np.asarray(W, np.float32), np.asarray(b, np.float32)
+            if W.shape != (o, i) or b.shape != (o,):
+                raise ValueError("%s: expected W %r and b %r, got %r and %r" % (what, (o, i), (o,), W.shape, b.shape))
+            parts += [W.reshape(-1), b]
+    return np.ascontiguousarray(np.concatenate(parts))
+
+
+def unpack_params(spec, params):
+    """-> in_scale (5,), in_shift (5,), [(W, b), ...] of the action network, the same of the value network or None."""
+    spec = _as_spec(spec)
+    p = np.asarray(params, np.float32).reshape(-1)
+    if p.size != n_params(spec):
+        raise ValueError("expected %d parameters, got %d" % (n_params(spec), p.size))
+    at = [10]
+
+    def net(shapes):
+        out = []
+        for o, i in shapes:
+            W = p[at[0]:at[0] + o * i].reshape(o, i)
+            b = p[at[0] + o * i:at[0] + o * i + o]
+            at[0] += o * i + o
+            out.append((W, b))
+        return out
+    a, v = layer_shapes(spec)
+    return p[:5], p[5:10], net(a), (None if v is None else net(v))
+
+
+def fma32(a, b, c):
+    """float32 arrays (broadcast against each other) -> float32: a * b + c rounded ONCE, what ``fmaf`` / ``v_fma_f32`` / one step
+    of an f32 MFMA accumulator give.  The product of two float32 is exact in float64 (48 bits); TwoSum gives the exact residual of
+    the float64 addition; the float64 sum is rounded to odd with it, and rounding that to float32 equals rounding the exact sum."""
+    p = np.asarray(a, np.float32).astype(np.float64) * np.asarray(b, np.float32).astype(np.float64)
+    c = np.asarray(c, np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = p + c
+        t = s - p
+        err = (p - (s - t)) + (c - t)                                        # TwoSum: s + err == p + c exactly
+    s = np.ascontiguousarray(s)
+    bits = s.view(np.int64)
+    fix = (err != 0) & ((bits & 1) == 0) & np.isfinite(s) & (s != 0)
+    bits = np.where(fix, bits + np.where((err > 0) == (s > 0), 1, -1), bits)  # round to odd in 53 bits
+    return np.where((s == 0) & (err != 0), err, bits.view(np.float64)).astype(np.float32)
+
+
+def _forward32(layers, activation, x, chunk=2048):
+    """the definition's chain, units x spacecraft; ``chunk`` spacecraft at a time (the working set stays in cache), the chunks
+    spread over a few threads (numpy's array operations release the interpreter lock)"""
+    n = x.shape[1]
+    out = np.empty((layers[-1][0].shape[0], n), np.float32)
+
+    def run(lo):
+        h = x[:, lo:lo + chunk]
+        for li, (W, b) in enumerate(layers):
+            z = np.broadcast_to(b[:, None], (W.shape[0], h.shape[1])).astype(np.float32)
+            for k in range(W.shape[1]):
+                z = fma32(W[:, k:k + 1], h[k:k + 1, :], z)
+            if li + 1 < len(layers):
+                with np.errstate(invalid="ignore"):
+                    z = np.tanh(z) if activation == "tanh" else np.where(z > 0, z, np.float32(0))
+            h = z.astype(np.float32)
+        out[:, lo:lo + chunk] = h
+    starts = range(0, n, chunk)
+    if len(starts) < 4:
+        for lo in starts:
+            run(lo)
+    else:
+        import os
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max(1, min(8, os.cpu_count() or 1))) as pool:
+            list(pool.map(run, starts))
+    return out
+
+
+def _forward64(layers, activation, x):
+    h = x
+    for li, (W, b) in enumerate(layers):
+        h = W.astype(np.float64) @ h + b.astype(np.float64)[:, None]
+        if li + 1 < len(layers):
+            h = np.tanh(h) if activation == "tanh" else np.maximum(h, 0.0)
+    return h
+
+
+def mlp_ref(spec, params, obs, fp64=False):
+    """numpy restatement of the policy's networks (include/bskgpu.h).  ``obs``: (5, n) float64 -> logits (3, n), value (n,) or None.
+    Default: the definition itself - float32, every layer output one k-ordered ``fma32`` chain from the bias: bit for bit the
+    kernel's logits and value for ``relu`` networks (``tanh`` is the host's here and the device library's there).
+    ``fp64=True``: the same float32 parameters and float32-converted inputs carried through in float64 (what error bounds are
+    derived against)."""
+    spec = _as_spec(spec)
+    scale, shift, a, v = unpack_params(spec, params)
+    o32 = np.asarray(obs, np.float64).reshape(5, -1).astype(np.float32)
+    if fp64:
+        x = o32.astype(np.float64) * scale.astype(np.float64)[:, None] + shift.astype(np.float64)[:, None]
+        return _forward64(a, spec.activation, x), (None if v is None else _forward64(v, spec.value_activation, x)[0])
+    x = fma32(o32, scale[:, None], shift[:, None])
+    return _forward32(a, spec.activation, x), (None if v is None else _forward32(v, spec.value_activation, x)[0])
+
+
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+_MASK32, _SH32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al. 2011) on uint64 arrays that hold 32-bit words -> the four output words (csrc/bsk_philox.hpp)."""
+    c0, c1, c2, c3, k0, k1 = (np.asarray(w, np.uint64) for w in (c0, c1, c2, c3, k0, k1))
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
+        c0, c1, c2, c3 = ((p1 >> _SH32) ^ c1 ^ k0) & _MASK32, p1 & _MASK32, ((p0 >> _SH32) ^ c3 ^ k1) & _MASK32, p0 & _MASK32
+        k0, k1 = (k0 + _PHILOX_W0) & _MASK32, (k1 + _PHILOX_W1) & _MASK32
+    return c0, c1, c2, c3
+
+
+def sample_uniform(n, seed=0, draw=0, env_base=0):
+    """u of sample mode for spacecraft env_base .. env_base + n - 1: (w0 >> 8) * 2**-24 with w0 the first Philox word of counter
+    (env_lo, env_hi, draw_lo, draw_hi) under key (seed_lo, seed_hi) -> float32 (n,)."""
+    env = np.uint64(int(env_base)) + np.arange(int(n), dtype=np.uint64)
+    seed, draw = np.uint64(int(seed)), np.uint64(int(draw))
+    w0 = philox4x32_10(env & _MASK32, env >> _SH32, draw & _MASK32, draw >> _SH32, seed & _MASK32, seed >> _SH32)[0]
+    return (w0 >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+
+
+def softmax_ref(logits):
+    """-> m, e (3, n), s of include/bskgpu.h step 5, float32 operations in the kernel's order (``exp`` is the host's)."""
+    l = np.asarray(logits, np.float32).reshape(3, -1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        m = np.fmax(np.fmax(l[0], l[1]), l[2])
+        e = np.exp(l - m)
+        s = (e[0] + e[1]) + e[2]
+    return m, e, s
+
+
+def act_ref(logits, mode="greedy", seed=0, draw=0, env_base=0):
+    """numpy restatement of the action choice.  ``logits`` (3, n) float32 -> action int32 (n,), logp float32 (n,).
+    greedy: the greatest logit, ties to the lowest index, a NaN loses to every number (three NaNs pick 0).
+    sample: p_i = e_i / s, action = 0 if u < p_0, else 1 if u < p_0 + p_1, else 2 (``sample_uniform``)."""
+    if mode not in MODES:
+        raise ValueError("mode must be 'greedy' or 'sample'")
+    l = np.asarray(logits, np.float32).reshape(3, -1)
+    m, e, s = softmax_ref(l)
+    if mode == "sample":
+        u = sample_uniform(l.shape[1], seed, draw, env_base)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            c0 = e[0] / s
+            c1 = c0 + e[1] / s
+        a = np.where(u < c0, 0, np.where(u < c1, 1, 2)).astype(np.int32)
+    else:
+        a = np.zeros(l.shape[1], np.int32)
+        best = l[0].copy()
+        for i in (1, 2):
+            na, nb = np.isnan(l[i]), np.isnan(best)
+            with np.errstate(invalid="ignore"):
+                win = np.where(na != nb, nb, ~na & (l[i] > best))
+            a[win] = i
+            best[win] = l[i][win]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        logp = (np.take_along_axis(l, a[None, :].astype(np.int64), axis=0)[0] - m) - np.log(s)
+    return a, logp.astype(np.float32)
+
+
+def torch_layers(module):
+    """An ``nn.Sequential`` of ``Linear`` / ``ReLU`` / ``Tanh`` -> (hidden widths, activation, [(W, b), ...] as float32 numpy).
+    Every ``Linear`` but the last is followed by one activation, the same one throughout; anything else is a ``ValueError``."""
+    import torch.nn as nn
+    mods = list(module) if isinstance(module, nn.Sequential) else None
+    if not mods:
+        raise ValueError("expected a non-empty nn.Sequential of Linear / ReLU / Tanh")
+    layers, acts, expect_linear = [], set(), True
+    for m in mods:
+        if expect_linear and isinstance(m, nn.Linear):
+            W = m.weight.detach().cpu().float().numpy()
+            b = m.bias.detach().cpu().float().numpy() if m.bias is not None else np.zeros(W.shape[0], np.float32)
+            layers.append((np.ascontiguousarray(W), np.ascontiguousarray(b)))
+            expect_linear = False
+        elif not expect_linear and type(m) in (nn.ReLU, nn.Tanh):
+            acts.add("relu" if type(m) is nn.ReLU else "tanh")
+            expect_linear = True
+        else:
+            raise ValueError("unsupported module sequence at %r: Linear layers, each but the last followed by ReLU or Tanh" % (m,))
+    if expect_linear:
+        raise ValueError("the network must end with a Linear layer")
+    if len(acts) > 1:
+        raise ValueError("one hidden activation per network: found both ReLU and Tanh")
+    return tuple(W.shape[0] for W, _ in layers[:-1]), (acts.pop() if acts else "relu"), layers
+
+
+class _ViewOwner(object):
+    """What a view of the policy's output buffers keeps alive - the policy, which owns them - and waits for when a consumer on
+    another stream takes the view (the propagator's stream, where the launch went)."""
+
+    def __init__(self, policy, prop):
+        self.policy, self.prop = policy, prop
+
+    def sync(self):
+        self.prop.sync()
+
+
+class DevicePolicy(object):
+    """The policy on one GPU.  ``spec``: a ``Spec`` (``check_spec``); ``params``: its float32 parameter block (``pack_params``).
+    Not thread-safe, and one stream at a time: the draw counter and the output buffers are single.  Output buffers are sized for
+    the largest batch seen so far; a call that must grow them allocates, so make the first call of a size outside a graph capture."""
+
+    def __init__(self, spec, params, device=0):
+        self.spec = _as_spec(spec)
+        p = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
+        if p.size != n_params(self.spec):
+            raise ValueError("expected %d parameters, got %d" % (n_params(self.spec), p.size))
+        self._lib = _lib.load()
+        self.device = int(device)
+        self._cs = c_spec(self.spec)
+        h = C.c_void_p()
+        check(self._lib.bsk_policy_create(C.byref(self._cs), p.ctypes.data, self.device, C.byref(h)))
+        self._p = h
+        self._out, self._out_n, self._source = None, 0, None
+
+    @classmethod
+    def from_torch(cls, module, value_module=None, in_scale=None, in_shift=None, device=0):
+        """From an ``nn.Sequential`` of ``Linear`` / ``ReLU`` / ``Tanh`` (5 inputs, 3 outputs) and, optionally, one for the value
+        (5 inputs, 1 output).  Weights are cast to float32."""
+        hidden, act, layers = torch_layers(module)
+        vh = va = vl = None
+        if value_module is not None:
+            vh, va, vl = torch_layers(value_module)
+        spec = check_spec(hidden, act, vh, va)
+        return cls(spec, pack_params(spec, layers, vl, in_scale, in_shift), device=device)
+
+    # ------------------------------------------------------------------ lifecycle
+    def close(self):
+        if getattr(self, "_p", None):
+            self._lib.bsk_policy_destroy(self._p)
+            self._p = None
+        for b in (getattr(self, "_out", None) or {}).values():
+            b.free()
+        self._out = self._source = None
+
+    def __del__(self):
+        try:
+            import sys
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._p:
+            raise RuntimeError("policy is closed")
+        return self._p
+
+    def sync(self):
+        """Waits for everything queued on the policy's device (the policy keeps no stream of its own)."""
+        from . import _hip
+        with _hip.device_guard(self.device):
+            _hip.check(_hip.runtime().hipDeviceSynchronize(), "hipDeviceSynchronize")
+
+    def set_params(self, params):
+        p = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
+        if p.size != n_params(self.spec):
+            raise ValueError("expected %d parameters, got %d" % (n_params(self.spec), p.size))
+        check(self._lib.bsk_policy_set_params(self._handle(), p.ctypes.data))
+
+    def set_rng(self, seed, draw=0):
+        check(self._lib.bsk_policy_set_rng(self._handle(), int(seed), int(draw)))
+
+    def get_rng(self):
+        """-> (seed, draw); synchronises."""
+        s, d = C.c_uint64(), C.c_uint64()
+        check(self._lib.bsk_policy_get_rng(self._handle(), C.byref(s), C.byref(d)))
+        return s.value, d.value
+
+    # ------------------------------------------------------------------ evaluation
+    def _buffers(self, n):
+        if self._out is None or self._out_n < n:
+            from . import _hip
+            if self._out:
+                self.sync()
+                for b in self._out.values():
+                    b.free()
+            self._out = {"action": _hip.DeviceBuffer(4 * n, self.device), "logp": _hip.DeviceBuffer(4 * n, self.device),
+                         "value": _hip.DeviceBuffer(4 * n, self.device), "logits": _hip.DeviceBuffer(12 * n, self.device)}
+            self._out_n = n
+        return self._out
+
+    def enqueue(self, obs_ptr, obs_stride, n, mode="greedy", want=(), env_base=0, stream=0):
+        """``bsk_policy_act`` on raw arguments (what ``act`` resolves its source to, for loops that resolve it once): observations
+        f64[5][obs_stride] at ``obs_ptr``.  -> the policy's output buffers by name (``_hip.DeviceBuffer``: ``action`` int32[n],
+        ``logp`` / ``value`` f32[n], ``logits`` f32[3][n]); only ``action`` and the names in ``want`` are written."""
+        if mode not in MODES:
+            raise ValueError("mode must be 'greedy' or 'sample'")
+        out = self._buffers(int(n))
+        vp = lambda name: C.c_void_p(out[name].ptr) if name in want else None      # noqa: E731
+        check(self._lib.bsk_policy_act(self._handle(), C.c_void_p(int(obs_ptr)), int(obs_stride), int(n), int(env_base), MODES[mode],
+                                       C.c_void_p(out["action"].ptr), vp("logp"), vp("value"), vp("logits"), int(n), C.c_void_p(int(stream))))
+        return out
+
+    def act(self, source, mode="greedy", want=("logp", "value", "logits"), env_base=None, stream=None):
+        """One launch: actions (and what ``want`` names) for every spacecraft of ``source`` - a ``BatchedPropagator`` (or an env
+        with a ``propagator``): its own observation buffers, stream and env_base - or any device array of shape (5, n) float64 with
+        contiguous rows (``__cuda_array_interface__``: a torch tensor, a propagator view), evaluated on ``stream`` (an integer
+        hipStream_t, default the null stream).  Enqueue-only: no copy, no synchronisation.
+        -> dict of device views (``__cuda_array_interface__`` / DLPack) valid until the next call: ``action`` int32 (n,) - whose
+        pointer ``step_device`` takes as it is - and ``logp`` (n,), ``value`` (n,), ``logits`` (3, n) float32 where wanted."""
+        from .simulators.dynamics.propagator import _DevArray
+        if mode not in MODES:
+            raise ValueError("mode must be 'greedy' or 'sample'")
+        want = tuple(want)
+        for w in want:
+            if w not in ("logp", "value", "logits"):
+                raise ValueError("want: 'logp', 'value' and / or 'logits', got %r" % (w,))
+        if "value" in want and self.spec.value_hidden is None:
+            raise ValueError("want 'value': the policy has no value network")
+        prop = getattr(source, "propagator", source)
+        if hasattr(prop, "device_views") and hasattr(prop, "stream_ptr"):
+            if prop.device != self.device:
+                raise ValueError("the policy lives on device %d, the propagator on device %d" % (self.device, prop.device))
+            v = prop.device_views()
+            ptr, stride, n = v["obs"].__cuda_array_interface__["data"][0], v["stride"], prop.n_envs
+            stream = prop.stream_ptr() if stream is None else stream
+            env_base = getattr(prop, "env_base", 0) if env_base is None else env_base
+            owner = _ViewOwner(self, prop)
+        else:
+            cai = getattr(source, "__cuda_array_interface__", None)
+            if cai is None:
+                raise TypeError("expected a BatchedPropagator or a device array with __cuda_array_interface__, got %r" % type(source))
+            shape, strides = tuple(cai["shape"]), cai.get("strides")
+            if cai["typestr"] != "<f8" or len(shape) != 2 or shape[0] != 5 or shape[1] < 1:
+                raise ValueError("observations: a float64 device array of shape (5, n), got %r %r" % (cai["typestr"], shape))
+            strides = (shape[1] * 8, 8) if strides is None else tuple(strides)
+            if strides[1] != 8 or strides[0] % 8 or strides[0] < shape[1] * 8:
+                raise ValueError("observations: rows must be contiguous and at least n elements apart")
+            ptr, stride, n = int(cai["data"][0]), strides[0] // 8, shape[1]
+            owner = self
+            self._source = source                  # (the launch reads it after this call returns)
+        stream = int(stream or 0)
+        out = self.enqueue(ptr, stride, n, mode, want, int(env_base or 0), stream)
+        kw = {"owner": owner, "device": self.device, "stream": stream}
+        res = {"action": _DevArray(out["action"].ptr, (n,), "<i4", **kw)}
+        for name in want:
+            res[name] = _DevArray(out[name].ptr, (3, n) if name == "logits" else (n,), "<f4", **kw)
+        return res
+
+    def rollout_device(self, prop, n_steps, substeps, mode="greedy", d_obs_hist=None, d_reward_hist=None, d_reason_hist=None,
+                       d_action_hist=None, d_logp_hist=None, d_value_hist=None):
+        """``bsk_policy_rollout`` with device pointers (or None) for the history rows: ``n_steps`` rounds of policy -> step -> history
+        row enqueued on the propagator's stream, no copy, no synchronisation (capturable once a first rollout without
+        ``d_action_hist`` has allocated the policy's scratch row)."""
+        if mode not in MODES:
+            raise ValueError("mode must be 'greedy' or 'sample'")
+        prop = getattr(prop, "propagator", prop)
+        vp = lambda p: C.c_void_p(int(p)) if p else None      # noqa: E731
+        check(self._lib.bsk_policy_rollout(self._handle(), prop._handle(), MODES[mode], int(substeps), int(n_steps), vp(d_obs_hist),
+                                           vp(d_reward_hist), vp(d_reason_hist), vp(d_action_hist), vp(d_logp_hist), vp(d_value_hist)))
+
+    def rollout(self, prop, n_steps, substeps, mode="greedy"):
+        """Closed-loop rollout with host results: -> dict of numpy arrays ``obs`` (n_steps, 5, n), ``reward`` (n_steps, n), ``reason``
+        (n_steps, n) uint8 - ``step_n``'s rows - and ``action`` int32, ``logp`` float32, ``value`` float32 (with a value network)
+        (n_steps, n) of the observation each action was chosen FROM.  Allocates device scratch per call and synchronises: the
+        convenience form; a training process hands ``rollout_device`` its own buffers."""
+        from . import _hip
+        prop = getattr(prop, "propagator", prop)
+        n, T = prop.n_envs, int(n_steps)
+        names = [("obs", np.float64, (T, 5, n)), ("reward", np.float64, (T, n)), ("reason", np.uint8, (T, n)),
+                 ("action", np.int32, (T, n)), ("logp", np.float32, (T, n))]
+        if self.spec.value_hidden is not None:
+            names.append(("value", np.float32, (T, n)))
+        host = {k: np.empty(shape, dtype=dt) for k, dt, shape in names}
+        bufs = {k: _hip.DeviceBuffer(host[k].nbytes, self.device) for k in host}
+        try:
+            self.rollout_device(prop, T, substeps, mode, bufs["obs"].ptr, bufs["reward"].ptr, bufs["reason"].ptr, bufs["action"].ptr,
+                                bufs["logp"].ptr, bufs["value"].ptr if "value" in bufs else None)
+            stream = C.c_void_p(prop.stream_ptr())
+            for k, dst in host.items():
+                _hip.check(_hip.runtime().hipMemcpyAsync(C.c_void_p(dst.ctypes.data), C.c_void_p(bufs[k].ptr), dst.nbytes,
+                                                         _hip.hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")
+            prop.sync()
+        finally:
+            for b in bufs.values():
+                b.free()
+        return host

@@ -413,6 +413,82 @@ int bsk_beam_select(const double* d_reward, const uint8_t* d_reason, int n_roots
                     const bsk_beam_slot* d_in, bsk_beam_slot* d_out, int32_t* d_map, double* d_best_value, int32_t* d_best_action,
                     void* stream);
 
+/* A policy of the library's own: one or two multilayer perceptrons over the five observation rows, evaluated by ONE launch - action
+ * (and, optionally, its log-probability, the value and the three logits) out.  An extra beside the reference surface, like forks
+ * and planning: the reference's agent (stable-baselines MlpPolicy) runs its network outside the env.
+ *  - action network: 5 inputs, n_hidden = 0..3 hidden layers, each 16 ... 128 units wide in multiples of 16, 3 outputs (logits);
+ *    optional value network (has_value = 1): the same rules for v_n_hidden / v_hidden, 1 output; one hidden activation per network,
+ *    BSK_POLICY_RELU (z > 0 ? z : 0) or BSK_POLICY_TANH.
+ *  - `params`, f32: in_scale[5], in_shift[5], then per layer W[out][in] row-major (torch's nn.Linear.weight) and b[out]; the action
+ *    network's layers first, then the value network's.  bsk_policy_n_params floats in all.
+ * Evaluation per spacecraft, all in f32:
+ *  1. x_i = fmaf((float)obs_i, in_scale_i, in_shift_i), obs_i the f64 observation converted round-to-nearest-even;
+ *  2. per layer and output j: z_j = b_j, then for k = 0, 1, ... ascending z_j = fmaf(W[j][k], h_k, z_j) - one k-ordered chain of fused
+ *     multiply-adds from the bias, one rounding per step, nothing wider inside (no split-K, no pairwise sums);
+ *  3. hidden h = act(z); the last layer is linear;
+ *  4. BSK_POLICY_GREEDY: the index of the greatest logit, ties to the lowest index, a NaN loses to every number (three NaNs pick 0):
+ *     the rule of bsk_select_branches;
+ *  5. BSK_POLICY_SAMPLE: m = max logits, e_i = expf(l_i - m), p_i = e_i / ((e_0 + e_1) + e_2), u = (w0 >> 8) * 2^-24 with w0 the first
+ *     word of philox4x32_10(counter = (env_lo, env_hi, draw_lo, draw_hi), key = (seed_lo, seed_hi)), env = env_base + j (64 bit),
+ *     draw the policy's 64-bit draw counter; action = 0 if u < p_0, else 1 if u < p_0 + p_1, else 2;
+ *  6. logp = (l_a - m) - logf((e_0 + e_1) + e_2) of the chosen action a (either mode), value, and the logits.
+ * For RELU networks logits and value are therefore reproducible bit for bit by any restatement that makes the same chain
+ * (basilisk_env_amd/policy.py does, in numpy).  Non-finite observations are outside the numerical contract; nothing out of range
+ * is read or written for them and the action stays in {0, 1, 2}.
+ * A policy belongs to one device.  It is not thread-safe and serves ONE stream at a time: its draw counter and its scratch row of
+ * actions are single, so two streams' launches would race on them. */
+#define BSK_POLICY_RELU 0
+#define BSK_POLICY_TANH 1
+#define BSK_POLICY_GREEDY 0
+#define BSK_POLICY_SAMPLE 1
+typedef struct bsk_policy_spec {
+    uint32_t abi_version; /* = BSK_ABI_VERSION */
+    uint32_t struct_size; /* = sizeof(bsk_policy_spec) */
+    int32_t n_hidden;     /* action network: hidden layers, 0..3 */
+    int32_t hidden[3];
+    int32_t activation;
+    int32_t has_value;    /* 0 / 1 */
+    int32_t v_n_hidden;   /* value network (ignored without has_value) */
+    int32_t v_hidden[3];
+    int32_t v_activation;
+} bsk_policy_spec;
+typedef struct bsk_policy bsk_policy;
+/* Floats in `params` for this spec, or BSK_EINVAL / BSK_EABI. */
+int bsk_policy_n_params(const bsk_policy_spec* spec);
+/* `params`: host pointer, copied.  seed = 0, draw = 0.  BSK_ENODEV when no gfx950 device is usable (the spec is checked first). */
+int bsk_policy_create(const bsk_policy_spec* spec, const float* params, int device_id, bsk_policy** out);
+/* New parameters (host pointer), ordered after everything queued on the policy's device (a policy keeps no stream of its own).
+ * Synchronises the device. */
+int bsk_policy_set_params(bsk_policy* p, const float* params);
+void bsk_policy_destroy(bsk_policy* p);
+/* Seed and draw counter of sample mode.  A sample-mode launch reads the counter on the device and a one-thread launch behind it adds
+ * one, so that a launch captured into a HIP graph draws new numbers on every replay; greedy launches leave it alone.  Both entry
+ * points are ordered after everything queued on the policy's device and synchronise it. */
+int bsk_policy_set_rng(bsk_policy* p, uint64_t seed, uint64_t draw);
+int bsk_policy_get_rng(bsk_policy* p, uint64_t* seed, uint64_t* draw);
+/* Evaluate the policy for n spacecraft.  Raw DEVICE pointers, like bsk_select_branches: enqueued on `stream` (a hipStream_t, NULL =
+ * the null stream) of the policy's device; no copy, no synchronisation, capturable.
+ *   d_obs     f64[5][obs_stride], obs_stride >= n: the layout of bsk_get_obs_device (no row-major copy needed)
+ *   env_base  >= 0: global index of spacecraft 0 (sample mode's counter; what bsk_set_env_base gives a sharded handle)
+ *   d_action  int32[n] in {0, 1, 2}: what bsk_step_device reads in place
+ *   d_logp    f32[n] or NULL;  d_value f32[n] or NULL (non-NULL without a value network: BSK_EINVAL)
+ *   d_logits  f32[3][out_stride] or NULL (out_stride >= n)
+ * Every argument is checked before anything is launched. */
+int bsk_policy_act(bsk_policy* p, const double* d_obs, int64_t obs_stride, int n, int64_t env_base, int mode,
+                   int32_t* d_action, float* d_logp, float* d_value, float* d_logits, int64_t out_stride, void* stream);
+/* Closed-loop rollout: per env step t = 0 .. n_steps-1, (a) the policy on the handle's own observation buffers with the handle's
+ * env_base - actions into row t of d_action_hist (int32[n_steps][n_envs]; a scratch row of the policy when NULL), log-probability and
+ * value into row t of d_logp_hist / d_value_hist (f32[n_steps][n_envs], may be NULL): they belong to the observation the action was
+ * chosen FROM; (b) bsk_step_device with those actions; (c) row t of bsk_step_n's histories (each may be NULL).  All DEVICE memory,
+ * enqueued on the handle's stream: no copy, no synchronisation, capturable once the policy's scratch row exists (a first call that
+ * must allocate it returns BSK_EINVAL under capture: the rule of in-handle forks).  Afterwards every buffer of the handle holds, bit
+ * for bit, what n_steps rounds of bsk_policy_act + bsk_step_device leave, and the draw counter has advanced by n_steps in sample
+ * mode.  Works at every level and with the harmonics; with BSK_FLAG_AUTO_RESET episodes restart inside the rollout as in bsk_step_n.
+ * BSK_EINVAL when policy and handle live on different devices. */
+int bsk_policy_rollout(bsk_policy* p, bsk_handle* h, int mode, int substeps, int n_steps,
+                       double* d_obs_hist, double* d_reward_hist, uint8_t* d_reason_hist,
+                       int32_t* d_action_hist, float* d_logp_hist, float* d_value_hist);
+
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the
  * three-wave form's barrier-free exchange gives up after 2^20 polls instead of hanging, and says so here. */
