@@ -1,0 +1,170 @@
+"""CPU: the registry of ``bsk_config`` constants (tests/_config_space.py) - complete, inside the range where the oracle and the
+50-digit model agree, and every one-field change visible to the oracle by 1 000 x the tolerance the GPU tests apply
+(tests/test_gpu_config_space.py), so that a kernel reading a stale or mis-indexed copy of a constant cannot pass there."""
+import contextlib
+import io
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+
+import _config_space as CS
+from basilisk_env_amd import _lib
+from basilisk_env_amd._lib import FLAG_DESAT, GRAV_PM, GRAV_PM_J2, GRAV_SH
+from basilisk_env_amd.simulators.dynamics.config import default_config
+from helpers import general_hub, max_group_err
+from oracle import oracle
+
+
+def test_every_config_field_is_classified():
+    """A field added to ``bsk_config`` fails here until tests/_config_space.py says what it is and how to vary it."""
+    names = [name for name, _ in _lib.BskConfig._fields_]
+    assert sorted(names) == sorted(CS.FIELDS), (set(names) ^ set(CS.FIELDS))
+    for name, e in CS.FIELDS.items():
+        assert e["kind"] in ("abi", "structure", "physical"), name
+        if e["kind"] == "physical":
+            assert callable(e["draw"]) and callable(e["one"]) and len(e["live"]) >= 1, name
+    # what the issue lists as never varied on the GPU is physical here, every item of it
+    never = ("mu req j2 mass inertia js u_max u_min K P sigma_R0N ctrl_axes wheel_limit power_max reward_mult failure_penalty r_min "
+             "panel_normal panel_area panel_efficiency power_draw storage_capacity solar_flux sun_r0 mu_sun n_thr thr_max_counter "
+             "thr_pos thr_dir thr_max_thrust thr_min_fire_time thr_min_on_time hs_min facet_area facet_cd").split()
+    assert all(CS.FIELDS[n]["kind"] == "physical" for n in never)
+    assert [n for n, e in CS.FIELDS.items() if e.get("invariant")] == ["ctrl_axes"]
+
+
+@pytest.mark.parametrize("hub", ["diag", "full"])
+@pytest.mark.parametrize("n_rw", [0, 3, 4])
+def test_draws_are_asymmetric_and_land_in_their_family(n_rw, hub):
+    """What the default hides: per-wheel js, unequal facet pairs, full vectors, a general map - and the hub kind build_params
+    will see (csrc/bsk_capi.hip: every off-diagonal of I and of I - sum js g g^T exactly zero, or not)."""
+    d = default_config(n_rw, GRAV_PM_J2)
+    for seed in range(20):
+        c = CS.draw_config(np.random.default_rng(seed), n_rw, GRAV_PM_J2, "full", hub)
+        I = np.array(list(c.inertia)).reshape(3, 3)
+        D = I.copy()
+        for i in range(n_rw):
+            g = np.array(list(c.gs[i]))
+            assert abs(np.linalg.norm(g) - 1.0) < 1e-9 and c.js[i] > 0.0
+            for a in range(3):            # in build_params' own order of operations: the zeros must be exact
+                for b in range(3):
+                    D[a, b] -= c.js[i] * g[a] * g[b]
+        off = [D[a, b] for a in range(3) for b in range(3) if a != b] + [I[a, b] for a in range(3) for b in range(3) if a != b]
+        assert all(v == 0.0 for v in off) == (hub == "diag"), (seed, off)
+        js = [c.js[i] for i in range(n_rw)]
+        if n_rw == 3 or (n_rw == 4 and hub == "full"):
+            assert len(set(js)) == n_rw
+        if n_rw == 4 and hub == "diag":
+            assert len(set(js)) == 1 and js[0] != d.js[0]
+        assert len(set(c.facet_cd)) == 8 and all(c.facet_area[2 * i] != c.facet_area[2 * i + 1] for i in range(4))
+        assert min(abs(v) for v in c.sigma_R0N) > 0.0 and min(abs(v) for v in c.panel_normal) > 0.0
+        assert abs(np.linalg.norm(list(c.panel_normal)) - 1.0) < 1e-12
+        assert abs(np.linalg.det(np.array(list(c.ctrl_axes)).reshape(3, 3))) > 1e-3 and c.ctrl_axes[1] != 0.0
+        assert c.failure_penalty != 1.0 and c.reward_mult != d.reward_mult and c.n_thr != 8 and c.thr_max_counter != 4
+        assert 6.6e6 < c.r_min < 7.2e6 and c.req * 1.0 < 6.527e6
+        for i in range(8):
+            assert abs(np.linalg.norm(list(c.thr_dir[i])) - 1.0) < 1e-12 and c.thr_dir[i][2] != 0.0
+        for name in CS.physical_fields():          # nothing physical is left at its default
+            a, b = getattr(c, name), getattr(d, name)
+            same = (np.array_equal(np.ctypeslib.as_array(a), np.ctypeslib.as_array(b)) if hasattr(a, "__len__") else a == b)
+            if n_rw == 0 and name == "js":
+                continue
+            assert not same, (name, seed)
+
+
+CASES = [(n_rw, grav, level) for n_rw in (0, 3, 4) for grav in (GRAV_PM, GRAV_PM_J2, GRAV_SH) for level in ("bare", "power", "full", "fullg")]
+
+
+@pytest.mark.parametrize("n_rw,grav,level", CASES)
+def test_oracle_matches_the_50_digit_model_over_the_drawn_space(n_rw, grav, level):
+    """The reference pair on ``draw_config`` cases, at the tolerances of tests/test_oracle_random_golden.py: the oracle may serve
+    as the GPU tests' reference everywhere the draws go.  The hub kind alternates over the cases."""
+    import make_golden as G
+    case_no = CASES.index((n_rw, grav, level))
+    rng = np.random.default_rng(52000 + case_no)
+    hub = "full" if case_no % 2 else "diag"
+    drawn = CS.draw_config(rng, n_rw, grav, level, hub)
+    sh = None
+    if grav == GRAV_SH:
+        from basilisk_env_amd.simulators.dynamics.gravity_sh import synthetic_sh_coefficients
+        cbar, sbar = synthetic_sh_coefficients(CS.SH_DEGREE, seed=case_no)
+        sh = (CS.SH_DEGREE, cbar * 100.0, sbar)
+    n = 2
+    hi = 3 if (drawn.flags & FLAG_DESAT) else 2
+    schedule = [(rng.integers(0, hi, n), int(rng.integers(5, 13))) for _ in range(3)]
+    if drawn.flags & FLAG_DESAT:
+        schedule[1] = (np.full(n, 2), schedule[1][1])
+
+    def ic_edit(cfg, ic):
+        if n_rw:
+            ic[12:12 + n_rw] *= 2.0           # wheel momentum above hs_min: the desaturation request is not empty
+
+    with contextlib.redirect_stdout(io.StringIO()):
+        case = G.run_case("drawn", n_rw, grav, n, 900 + case_no, schedule, cfg_edit=lambda cfg: CS.copy_into(cfg, drawn), sh=sh, ic_edit=ic_edit)
+    st = np.array(case["ic"])
+    steps, ticks = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    tag = (n_rw, grav, level, hub)
+    for call in case["calls"]:
+        o = oracle.step(drawn, st, steps, ticks, np.array(call["actions"], np.int32), call["substeps"],
+                        cbar=None if sh is None else sh[1], sbar=None if sh is None else sh[2])
+        errs = max_group_err(st, np.array(call["state"]), n_rw)
+        assert max(errs.values()) < 1e-12, (tag, errs)
+        assert np.abs(o[0] - np.array(call["obs"])).max() < 1e-11, tag
+        assert np.abs(o[1] - np.array(call["reward"])).max() < 1e-13 and (o[3] == np.array(call["reason"])).all(), tag
+        t = 12 + n_rw
+        assert np.abs(st[t + 7] - np.array(call["state"])[t + 7]).max() < 1e-8, tag          # battery charge [W s]
+        if drawn.flags & FLAG_DESAT:
+            assert np.array_equal(st[t + 16:t + 26], np.array(call["state"])[t + 16:t + 26]), tag   # burst bookkeeping
+
+
+def _runs(sc, edit, form, n=64, seed=1):
+    base = sc.config()
+    if form == "fullhub":
+        general_hub(base)
+    ic, sched = sc.ic(n, seed), sc.schedule(n, seed)
+    a = CS.run_oracle(base, ic, sched, sc.sim_time0, sc.sh(), sc.ticks0)
+    b = CS.run_oracle(edit(base.copy(), form), ic, sched, sc.sim_time0, sc.sh(), sc.ticks0)
+    return CS.change(a, b, sc.n_rw)
+
+
+def test_every_one_field_change_is_visible_to_the_oracle(capsys):
+    """The power of the GPU tests: in each of its live scenarios, the oracle with and without the one-field change differs by at
+    least 1 000 x the GPU tolerance on some quantity (CS.LIVE: 1e-8 relative on a state group, 1e-8 on an observation, 1e-9 on
+    a reward) or changes the done reason of a tenth of the batch.  ``ctrl_axes`` is dead by algebra and asserted INVARIANT
+    instead (to 1e-13: the map is formed through a different inverse).  Prints the measured change per field and scenario."""
+    rows, dead = [], []
+    for name, sc, forms, edit in CS.one_field_cases():
+        for form in ("single", "fullhub") if name == "js" else ("single",):
+            c = _runs(sc, edit, form)
+            what = max(CS.LIVE, key=lambda k: c[k] / CS.LIVE[k])
+            need = "(invariant: must stay < 1e-13)" if CS.FIELDS[name]["invariant"] else "(needs >= %.0e)" % CS.LIVE[what]
+            rows.append("%-18s %-22s %-8s %-6s %9.2e  %s" % (name, sc.name, form, what, c[what], need))
+            if CS.FIELDS[name]["invariant"]:
+                if not (c["state"] < 1e-13 and c["obs"] < 1e-13 and c["reward"] < 1e-15 and c["reason"] == 0.0):
+                    dead.append((name, sc.name, "not invariant", c))
+            elif not CS.is_live(c):
+                dead.append((name, sc.name, form, c))
+    with capsys.disabled():
+        print("\nfield              scenario               form     moved   change")
+        print("\n".join(rows))
+    assert not dead, dead
+
+
+def test_done_orbit_splits_the_batch_without_ties():
+    """``r_min`` at the one-field value raises BSK_DONE_ORBIT for about half of the sampled orbits, and no spacecraft of the
+    batches the GPU tests use sits within a relative 2e-15 of it (where r.r < r_min^2 and |r| < r_min may round apart)."""
+    from basilisk_env_amd._lib import DONE_ORBIT
+    for seed in (1, 2, 3, 4):          # (4: the batch of the GPU module's done-reason tests)
+        sc = CS.Scenario("bare")
+        cfg = sc.config()
+        CS._one_r_min(cfg, None, None)
+        ic = sc.ic(1000, seed)
+        out = CS.run_oracle(cfg, ic, sc.schedule(1000, seed))
+        for st, _, _, why, _, _ in out:
+            share = float(((why & DONE_ORBIT) != 0).mean())
+            assert 0.3 < share < 0.7, share
+            r = np.linalg.norm(st[0:3], axis=0)
+            assert np.array_equal((why & DONE_ORBIT) != 0, r < cfg.r_min)
+            assert not (np.abs(r / cfg.r_min - 1.0) < 2e-15).any()
