@@ -11,6 +11,8 @@ from oracle import oracle
 
 
 class OraclePropagator(object):
+    omp = False               # the oracle's OpenMP build, on every core the process may use
+
     def __init__(self, cfg, n_envs, device=0, stream=None):
         self.cfg = cfg.copy()
         self.n_envs = int(n_envs)
@@ -63,7 +65,7 @@ class OraclePropagator(object):
 
     def step(self, actions, substeps):
         self._out = oracle.step(self.cfg, self.state, self.steps, self.ticks, np.asarray(actions, np.int32), substeps,
-                                sim_time0=self._t0, cbar=self._cbar, sbar=self._sbar)
+                                sim_time0=self._t0, cbar=self._cbar, sbar=self._sbar, omp=self.omp)
         if self._pool is not None:
             self._auto_reset()
 
@@ -132,3 +134,8 @@ class OraclePropagator(object):
 
     def set_env_base(self, base):
         self.env_base = int(base)
+
+
+class OmpOraclePropagator(OraclePropagator):
+    """The stand-in with the oracle on every usable core (65 536 spacecraft of the full scenario; whole episodes)."""
+    omp = True

@@ -20,7 +20,7 @@ import sys
 import numpy as np
 import pytest
 
-from _oracle_backend import OraclePropagator
+from _oracle_backend import OmpOraclePropagator as _OmpOracle
 from basilisk_env_amd._lib import (FLAG_DESAT, FLAG_DRAG, FLAG_POWER, FLAG_SUN_THIRD_BODY, GRAV_PM_J2, GRAV_SH)
 from basilisk_env_amd.simulators.dynamics import BatchedPropagator, default_config
 from basilisk_env_amd.simulators.dynamics.gravity_sh import synthetic_sh_coefficients
@@ -249,16 +249,6 @@ def test_rollout_4mi_x_100_final_state_and_sampled_history():
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # 4. the RL-loop leg
-class _OmpOracle(OraclePropagator):
-    """tests/_oracle_backend.py's stand-in with the oracle on every usable core (65 536 envs of the full scenario)."""
-
-    def step(self, actions, substeps):
-        self._out = oracle.step(self.cfg, self.state, self.steps, self.ticks, np.asarray(actions, np.int32), substeps,
-                                sim_time0=self._t0, cbar=self._cbar, sbar=self._sbar, omp=True)
-        if self._pool is not None:
-            self._auto_reset()
-
-
 @pytest.mark.parametrize("k,steps", [(1, 40), (1800, 2)])
 def test_rl_loop_leg_against_the_oracle_env(k, steps):
     """bench.py's rl_loop: 65 536 envs of the full scenario, a device Philox pool of 4 096 ICs, device-side auto-reset, a
