@@ -83,6 +83,8 @@ EXPORTS = [
     "bsk_fork_device", "bsk_fork", "bsk_select_branches", "bsk_beam_select",
     "bsk_policy_n_params", "bsk_policy_create", "bsk_policy_set_params", "bsk_policy_destroy", "bsk_policy_set_rng", "bsk_policy_get_rng",
     "bsk_policy_act", "bsk_policy_rollout",
+    "bsk_population_create", "bsk_population_destroy", "bsk_population_set_rng", "bsk_population_get_rng", "bsk_population_set_params",
+    "bsk_population_set_params_device", "bsk_population_get_member", "bsk_population_act", "bsk_population_rollout",
     "bsk_profile_begin", "bsk_profile_set_stride", "bsk_profile_end", "bsk_profile_end_samples", "bsk_calibrate_fp64", "bsk_kernel_info", "bsk_last_error", "bsk_version",
 ]
 
@@ -153,12 +155,21 @@ def load():
                        ("bsk_policy_set_params", [vp, vp]), ("bsk_policy_destroy", [vp]), ("bsk_policy_set_rng", [vp, C.c_uint64, C.c_uint64]),
                        ("bsk_policy_get_rng", [vp, P(C.c_uint64), P(C.c_uint64)]),
                        ("bsk_policy_act", [vp, vp, C.c_int64, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, C.c_int64, vp]),
-                       ("bsk_policy_rollout", [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp])):
+                       ("bsk_policy_rollout", [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+                       ("bsk_population_create", [P(BskPolicySpec), C.c_int, vp, C.c_int, P(vp)]), ("bsk_population_destroy", [vp]),
+                       ("bsk_population_set_rng", [vp, C.c_uint64, C.c_uint64]),
+                       ("bsk_population_get_rng", [vp, P(C.c_uint64), P(C.c_uint64)]), ("bsk_population_set_params", [vp, vp]),
+                       ("bsk_population_set_params_device", [vp, vp, C.c_int, C.c_int, vp]),
+                       ("bsk_population_get_member", [vp, C.c_int, vp]),
+                       ("bsk_population_act", [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, C.c_int64, vp]),
+                       ("bsk_population_rollout", [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])):
         # (a BSKGPU_LIB variant built from an older tree - kernel A/B against a previous round - may predate these)
         if hasattr(lib, name) or not os.environ.get("BSKGPU_LIB"):
             getattr(lib, name).argtypes = args
     if hasattr(lib, "bsk_policy_destroy"):
         lib.bsk_policy_destroy.restype = None
+    if hasattr(lib, "bsk_population_destroy"):
+        lib.bsk_population_destroy.restype = None
     lib.bsk_get_obs.argtypes = [vp, vp, vp, vp, vp]
     lib.bsk_get_obs_device.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(C.c_int64)]
     lib.bsk_get_obs_state.argtypes = [vp, vp, vp, vp, vp]

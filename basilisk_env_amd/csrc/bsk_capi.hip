@@ -17,6 +17,7 @@
 #include "bsk_aux.hpp"
 #include "bsk_launch.hpp"
 #include "bsk_policy.hpp"
+#include "bsk_population.hpp"
 #include "bsk_rollout.hpp"
 
 namespace {
@@ -483,6 +484,22 @@ struct bsk_policy {
     int act_cap = 0;
 };
 
+// bsk_population_*: n_members parameter blocks of one spec, member m driving envs [m * E, (m + 1) * E) (bsk_policy.hip,
+// bsk_population.hip)
+struct bsk_population {
+    bsk::PolicyLayout lay;
+    int device = 0;
+    int n_members = 0;
+    float* d_params = nullptr;             // [n_members][lay.n_device]: one device layout per member
+    unsigned long long* d_rng = nullptr;   // {seed, draw}, one pair for the whole population
+    // bsk_population_rollout's scratch, one allocation sized for the largest handle seen: the running value of every env and a
+    // row of actions (d_action_hist == NULL)
+    void* d_scratch = nullptr;
+    bsk::FitnessAcc acc = {};
+    int* d_act = nullptr;
+    int scratch_cap = 0;
+};
+
 namespace {
 
 struct DeviceGuard {
@@ -811,6 +828,33 @@ int policy_upload(bsk_policy* p, const float* params) {
     bsk::policy_pack(p->lay, params, dev);
     HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old parameters)
     HIP_COPY(hipMemcpy(p->d_params, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice));
+    return BSK_OK;
+}
+
+// The population: bsk_policy_act's checks with the member rule on top, all before anything is enqueued
+int population_check_act(const bsk_population* p, const double* d_obs, int64_t obs_stride, int n, int envs_per_member, int64_t env_base,
+                         int mode, const int32_t* d_action, const float* d_value, const float* d_logits, int64_t out_stride) {
+    if (!p || !d_obs || !d_action) return fail(BSK_EINVAL, "population/d_obs/d_action is NULL");
+    if (n < 1 || n > (1 << 28)) return fail(BSK_EINVAL, "n must be in 1..2^28");
+    if (envs_per_member < 64 || envs_per_member % 64 != 0) return fail(BSK_EINVAL, "envs_per_member must be a positive multiple of 64");
+    if ((int64_t)p->n_members * envs_per_member != (int64_t)n) return fail(BSK_EINVAL, "n must be n_members * envs_per_member");
+    if (obs_stride < n) return fail(BSK_EINVAL, "obs_stride must be >= n");
+    if (env_base < 0) return fail(BSK_EINVAL, "env_base must be >= 0");
+    if (mode != BSK_POLICY_GREEDY && mode != BSK_POLICY_SAMPLE) return fail(BSK_EINVAL, "mode must be BSK_POLICY_GREEDY or BSK_POLICY_SAMPLE");
+    if (d_value && p->lay.v.n_layers == 0) return fail(BSK_EINVAL, "d_value given, but the population has no value network");
+    if (d_logits && out_stride < n) return fail(BSK_EINVAL, "out_stride must be >= n");
+    return BSK_OK;
+}
+
+int population_launch(bsk_population* p, const double* d_obs, int64_t obs_stride, int n, int envs_per_member, int64_t env_base, int mode,
+                      int32_t* d_action, float* d_logp, float* d_value, float* d_logits, int64_t out_stride, hipStream_t stream) {
+    bsk::PolicyArgs a;
+    a.params = p->d_params; a.a = p->lay.a; a.v = p->lay.v; a.obs = d_obs; a.obs_stride = obs_stride; a.n = n;
+    a.env_base = (unsigned long long)env_base; a.mode = mode; a.rng = p->d_rng; a.action = d_action; a.logp = d_logp;
+    a.value = d_value; a.logits = d_logits; a.out_stride = out_stride; a.width = p->lay.width;
+    if (!d_value) a.v.n_layers = 0;            // (nobody asked for the value: its network is not evaluated)
+    HIP_TRY(bsk::launch_policy_population(a, envs_per_member, p->lay.n_device, stream));
+    if (mode == BSK_POLICY_SAMPLE) HIP_TRY(bsk::launch_policy_advance(p->d_rng, stream));
     return BSK_OK;
 }
 
@@ -1658,6 +1702,178 @@ int bsk_policy_rollout(bsk_policy* p, bsk_handle* h, int mode, int substeps, int
                                          d_reward_hist ? d_reward_hist + t * n : nullptr, d_reason_hist ? d_reason_hist + t * n : nullptr,
                                          h->stream));
     }
+    return BSK_OK;
+}
+
+int bsk_population_create(const bsk_policy_spec* spec, int n_members, const float* params, int device_id, bsk_population** out) {
+    if (!out) return fail(BSK_EINVAL, "out is NULL");
+    *out = nullptr;
+    bsk::PolicyLayout lay;
+    int rc = policy_spec_layout(spec, lay);
+    if (rc) return rc;
+    if (n_members < 1 || n_members > (1 << 22)) return fail(BSK_EINVAL, "n_members must be in 1..2^22");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(BSK_ENODEV, "no HIP device visible: libbskgpu has no CPU fallback");
+    if (device_id < 0 || device_id >= ndev) return fail(BSK_ENODEV, "device_id out of range");
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device_id));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(BSK_ENODEV, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    DeviceGuard guard(device_id);
+    bsk_population* p = new bsk_population();
+    p->lay = lay;
+    p->device = device_id;
+    p->n_members = n_members;
+    const unsigned long long rng0[2] = {0ull, 0ull};
+    auto init = [&]() -> int {
+        const size_t bytes = (size_t)n_members * (size_t)lay.n_device * sizeof(float);
+        HIP_TRY(hipMalloc(&p->d_params, bytes));
+        HIP_TRY(hipMalloc(&p->d_rng, sizeof rng0));
+        HIP_COPY(hipMemcpy(p->d_rng, rng0, sizeof rng0, hipMemcpyHostToDevice));
+        if (params) return bsk_population_set_params(p, params);
+        HIP_TRY(hipMemset(p->d_params, 0, bytes));        // (all-zero members pack to all-zero device blocks)
+        HIP_SYNC(hipDeviceSynchronize());
+        return BSK_OK;
+    };
+    rc = init();
+    if (rc) { bsk_population_destroy(p); return rc; }
+    *out = p;
+    return BSK_OK;
+}
+
+void bsk_population_destroy(bsk_population* p) {
+    if (!p) return;
+    DeviceGuard guard(p->device);
+    if (p->d_params || p->d_rng || p->d_scratch) (void)hipDeviceSynchronize();
+    if (p->d_params) (void)hipFree(p->d_params);
+    if (p->d_rng) (void)hipFree(p->d_rng);
+    if (p->d_scratch) (void)hipFree(p->d_scratch);
+    delete p;
+}
+
+int bsk_population_set_params(bsk_population* p, const float* params) {
+    if (!p || !params) return fail(BSK_EINVAL, "population/params is NULL");
+    DeviceGuard guard(p->device);
+    const size_t nd = (size_t)p->lay.n_device;
+    std::vector<float> all((size_t)p->n_members * nd), one;
+    for (int m = 0; m < p->n_members; ++m) {
+        bsk::policy_pack(p->lay, params + (size_t)m * (size_t)p->lay.n_params, one);
+        std::memcpy(all.data() + (size_t)m * nd, one.data(), nd * sizeof(float));
+    }
+    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old parameters)
+    HIP_COPY(hipMemcpy(p->d_params, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
+    return BSK_OK;
+}
+
+int bsk_population_set_params_device(bsk_population* p, const float* d_params, int first, int count, void* stream) {
+    if (!p || !d_params) return fail(BSK_EINVAL, "population/d_params is NULL");
+    if (first < 0 || count < 1 || first > p->n_members - count)
+        return fail(BSK_EINVAL, "first / count must name members inside the population (first >= 0, count >= 1, first + count <= n_members)");
+    DeviceGuard guard(p->device);
+    HIP_TRY(bsk::launch_policy_pack(p->lay, d_params, p->d_params + (size_t)first * (size_t)p->lay.n_device, count, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
+}
+
+int bsk_population_get_member(bsk_population* p, int member, float* params) {
+    if (!p || !params) return fail(BSK_EINVAL, "population/params is NULL");
+    if (member < 0 || member >= p->n_members) return fail(BSK_EINVAL, "member must be in 0..n_members-1");
+    DeviceGuard guard(p->device);
+    std::vector<float> dev((size_t)p->lay.n_device);
+    HIP_SYNC(hipDeviceSynchronize());
+    HIP_COPY(hipMemcpy(dev.data(), p->d_params + (size_t)member * dev.size(), dev.size() * sizeof(float), hipMemcpyDeviceToHost));
+    bsk::policy_unpack(p->lay, dev.data(), params);
+    return BSK_OK;
+}
+
+int bsk_population_set_rng(bsk_population* p, uint64_t seed, uint64_t draw) {
+    if (!p) return fail(BSK_EINVAL, "population is NULL");
+    DeviceGuard guard(p->device);
+    const unsigned long long w[2] = {seed, draw};
+    HIP_SYNC(hipDeviceSynchronize());
+    HIP_COPY(hipMemcpy(p->d_rng, w, sizeof w, hipMemcpyHostToDevice));
+    return BSK_OK;
+}
+
+int bsk_population_get_rng(bsk_population* p, uint64_t* seed, uint64_t* draw) {
+    if (!p) return fail(BSK_EINVAL, "population is NULL");
+    DeviceGuard guard(p->device);
+    unsigned long long w[2];
+    HIP_SYNC(hipDeviceSynchronize());
+    HIP_COPY(hipMemcpy(w, p->d_rng, sizeof w, hipMemcpyDeviceToHost));
+    if (seed) *seed = w[0];
+    if (draw) *draw = w[1];
+    return BSK_OK;
+}
+
+int bsk_population_act(bsk_population* p, const double* d_obs, int64_t obs_stride, int n, int envs_per_member, int64_t env_base, int mode,
+                       int32_t* d_action, float* d_logp, float* d_value, float* d_logits, int64_t out_stride, void* stream) {
+    int rc = population_check_act(p, d_obs, obs_stride, n, envs_per_member, env_base, mode, d_action, d_value, d_logits, out_stride);
+    if (rc) return rc;
+    DeviceGuard guard(p->device);
+    return population_launch(p, d_obs, obs_stride, n, envs_per_member, env_base, mode, d_action, d_logp, d_value, d_logits, out_stride,
+                             (hipStream_t)stream);
+}
+
+int bsk_population_rollout(bsk_population* p, bsk_handle* h, int mode, int substeps, int n_steps, double gamma,
+                           double* d_obs_hist, double* d_reward_hist, uint8_t* d_reason_hist,
+                           int32_t* d_action_hist, float* d_logp_hist, float* d_value_hist,
+                           double* d_env_value, int32_t* d_env_len, double* d_fitness, double* d_mean_len) {
+    if (!p || !h) return fail(BSK_EINVAL, "population/handle is NULL");
+    if (substeps < 1 || n_steps < 1) return fail(BSK_EINVAL, "substeps and n_steps must be >= 1");
+    if (!std::isfinite(gamma)) return fail(BSK_EINVAL, "gamma must be finite");
+    if (p->device != h->device) return fail(BSK_EINVAL, "bsk_population_rollout: the population and the handle live on different devices");
+    if (h->n % p->n_members != 0)
+        return fail(BSK_EINVAL, "bsk_population_rollout: the handle's n_envs must be n_members * envs_per_member");
+    const int E = h->n / p->n_members;
+    int rc = population_check_act(p, h->d_obs, h->ostride, h->n, E, (int64_t)h->env_base, mode, h->d_act, d_value_hist, nullptr, 0);
+    if (rc) return rc;
+    if (h->cfg.gravity_model == BSK_GRAV_SH && !h->sp.sh_tab)
+        return fail(BSK_EINVAL, "BSK_GRAV_SH: call bsk_set_gravity_sh before stepping");
+    if ((h->cfg.flags & BSK_FLAG_AUTO_RESET) && h->n_pool == 0)
+        return fail(BSK_EINVAL, "BSK_FLAG_AUTO_RESET: call bsk_set_ic_pool before stepping");
+    DeviceGuard guard(h->device);
+    if (p->scratch_cap < h->n) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        HIP_TRY(hipStreamIsCapturing(h->stream, &cap));
+        if (cap != hipStreamCaptureStatusNone)
+            return fail(BSK_EINVAL, "bsk_population_rollout: the first rollout of a size allocates the population's scratch rows and "
+                                    "cannot be captured; make one such call outside the capture first");
+        if (p->d_scratch) {
+            HIP_SYNC(hipDeviceSynchronize());                   // (a queued rollout may still use the smaller rows)
+            (void)hipFree(p->d_scratch);
+            p->d_scratch = nullptr;
+            p->scratch_cap = 0;
+        }
+        const size_t n = (size_t)h->n;                          // (a multiple of 64: every row below starts 8-byte aligned)
+        HIP_TRY(hipMalloc(&p->d_scratch, n * (8 + 8 + 4 + 4 + 1)));
+        char* at = (char*)p->d_scratch;
+        p->acc.v = (double*)at; at += n * 8;
+        p->acc.g = (double*)at; at += n * 8;
+        p->acc.len = (int*)at; at += n * 4;
+        p->d_act = (int*)at; at += n * 4;
+        p->acc.alive = (unsigned char*)at;
+        p->scratch_cap = h->n;
+    }
+    const size_t n = (size_t)h->n;
+    const bool want_fitness = d_env_value || d_env_len || d_fitness || d_mean_len;
+    for (int t = 0; t < n_steps; ++t) {
+        int32_t* act = d_action_hist ? d_action_hist + t * n : p->d_act;
+        rc = population_launch(p, h->d_obs, h->ostride, h->n, E, (int64_t)h->env_base, mode, act, d_logp_hist ? d_logp_hist + t * n : nullptr,
+                               d_value_hist ? d_value_hist + t * n : nullptr, nullptr, 0, h->stream);
+        if (rc) return rc;
+        if ((rc = do_step(h, act, substeps, 1))) return rc;
+        double* obs_row = d_obs_hist ? d_obs_hist + t * 5 * n : nullptr;
+        double* reward_row = d_reward_hist ? d_reward_hist + t * n : nullptr;
+        uint8_t* reason_row = d_reason_hist ? d_reason_hist + t * n : nullptr;
+        // the history rows and the value rule in ONE launch; with no fitness output asked for, the rows alone (or nothing)
+        if (want_fitness)
+            HIP_TRY(bsk::launch_fitness_row(h->d_obs, h->d_reward, h->d_reason, h->ostride, h->n, obs_row, reward_row, reason_row, p->acc,
+                                            gamma, t == 0, h->stream));
+        else
+            HIP_TRY(bsk::launch_hist_row(h->d_obs, h->d_reward, h->d_reason, h->ostride, h->n, obs_row, reward_row, reason_row, h->stream));
+    }
+    HIP_TRY(bsk::launch_fitness_join(p->acc, p->n_members, E, d_env_value, d_env_len, d_fitness, d_mean_len, h->stream));
     return BSK_OK;
 }
 

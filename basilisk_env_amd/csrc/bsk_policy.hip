@@ -2,6 +2,9 @@
 // step nor the rollout kernels):
 //   policy_kernel           action network (5 -> hidden... -> 3 logits) and optional value network (5 -> hidden... -> 1) for n
 //                           spacecraft in one launch: greedy or sampled action, log-probability, value, logits (bsk_policy_act)
+//   policy_population_kernel  the same for a population: every envs_per_member spacecraft under a parameter block of their own
+//                           (bsk_population_act); it shares every device function with policy_kernel
+//   policy_pack_kernel      C-ABI parameter blocks in device memory -> the device layout (bsk_population_set_params_device)
 //   policy_advance_kernel   the policy's draw counter += 1, behind a sample-mode launch
 // The arithmetic is the definition in include/bskgpu.h: every layer output is ONE k-ordered chain of f32 fused multiply-adds that
 // starts from the bias.  Each fmaf below is written out, so the chain does not depend on -ffp-contract.
@@ -89,15 +92,14 @@ __device__ __forceinline__ bool policy_beats(float a, float b) {      // a (the 
     return !na && a > b;
 }
 
-__global__ __launch_bounds__(POLICY_BLOCK) void policy_kernel(const PolicyArgs p) {
-    extern __shared__ float policy_lds[];
+// One workgroup's 64 spacecraft under the parameter block `params` (workgroup-uniform): the body of both kernels below.
+__device__ __forceinline__ void policy_eval(const PolicyArgs& p, const float* __restrict__ params, float* policy_lds) {
     const int lane = (int)(threadIdx.x & 63u);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));       // (wave-uniform: weight addresses stay scalar)
     const int64_t j = (int64_t)blockIdx.x * POLICY_LANES + lane;
     const bool live = j < p.n;
     float* buf0 = policy_lds;
     float* buf1 = policy_lds + p.width * POLICY_LANES;
-    const float* __restrict__ params = p.params;
 
     float x[5];
 #pragma unroll
@@ -137,11 +139,74 @@ __global__ __launch_bounds__(POLICY_BLOCK) void policy_kernel(const PolicyArgs p
     }
 }
 
+__global__ __launch_bounds__(POLICY_BLOCK) void policy_kernel(const PolicyArgs p) {
+    extern __shared__ float policy_lds[];
+    policy_eval(p, p.params, policy_lds);
+}
+
+// The population form (bsk_population_act): workgroup b serves the same 64 spacecraft and takes the parameter block of member
+// b / wg_per_member, wg_per_member = envs_per_member / 64.  The block address depends on blockIdx alone, so it is as scalar as
+// p.params is above and policy_hidden's weight loads stay one scalar load of 16 consecutive floats: nothing else differs.
+__global__ __launch_bounds__(POLICY_BLOCK) void policy_population_kernel(const PolicyArgs p, int wg_per_member, int n_device) {
+    extern __shared__ float policy_lds[];
+    const unsigned member = blockIdx.x / (unsigned)wg_per_member;
+    policy_eval(p, p.params + (size_t)member * (size_t)n_device, policy_lds);
+}
+
+// The C-ABI parameter blocks of `count` members (src, n_params floats each, DEVICE memory) -> their device layouts (dst, n_device
+// floats each): what policy_pack makes on the host, bit for bit.  A gather - every float of the device block is written by exactly
+// one thread, from its source element or as a zero of the padding - so there is no ordering between threads to get wrong.
+__global__ __launch_bounds__(256) void policy_pack_kernel(const float* __restrict__ src, float* __restrict__ dst, const PolicyPackMap map) {
+    const int d = (int)(blockIdx.y * blockDim.x + threadIdx.x);        // (members along x: there may be more than 65 535 of them)
+    if (d >= map.n_device) return;
+    const float* __restrict__ from = src + (size_t)blockIdx.x * (size_t)map.n_params;
+    float x = 0.0f;
+    if (d < 10) x = from[d];
+    for (int l = 0; l < map.n_layers; ++l) {
+        const PolicyPackMap::Layer& y = map.layer[l];
+        if (d >= y.w && d < y.w + y.K * y.N) {
+            const int k = (d - y.w) / y.N, jo = (d - y.w) % y.N;
+            if (jo < y.fan_out) x = from[y.src + jo * y.K + k];
+        } else if (d >= y.b && d < y.b + y.fan_out) {
+            x = from[y.src + y.fan_out * y.K + (d - y.b)];
+        }
+    }
+    dst[(size_t)blockIdx.x * (size_t)map.n_device + d] = x;
+}
+
 __global__ void policy_advance_kernel(unsigned long long* rng) { rng[1] += 1ull; }
 
 hipError_t launch_policy(const PolicyArgs& args, hipStream_t s) {
     const size_t lds = (size_t)2 * args.width * POLICY_LANES * sizeof(float);
     hipLaunchKernelGGL(policy_kernel, dim3((unsigned)((args.n + POLICY_LANES - 1) / POLICY_LANES)), dim3(POLICY_BLOCK), lds, s, args);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_population(const PolicyArgs& args, int envs_per_member, int n_device, hipStream_t s) {
+    const size_t lds = (size_t)2 * args.width * POLICY_LANES * sizeof(float);
+    hipLaunchKernelGGL(policy_population_kernel, dim3((unsigned)((args.n + POLICY_LANES - 1) / POLICY_LANES)), dim3(POLICY_BLOCK), lds, s,
+                       args, envs_per_member / POLICY_LANES, n_device);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_pack(const PolicyLayout& lay, const float* src, float* dst, int count, hipStream_t s) {
+    PolicyPackMap map = {};
+    map.n_params = lay.n_params;
+    map.n_device = lay.n_device;
+    const PolicyNet* nets[2] = {&lay.a, &lay.v};
+    const int n_out[2] = {3, 1};
+    int at = 10;
+    for (int t = 0; t < 2; ++t) {
+        const PolicyNet& net = *nets[t];
+        for (int l = 0; l < net.n_layers; ++l) {
+            PolicyPackMap::Layer& y = map.layer[map.n_layers++];
+            y.K = net.K[l]; y.N = net.N[l]; y.w = net.w[l]; y.b = net.b[l];
+            y.fan_out = l == net.n_layers - 1 ? n_out[t] : net.N[l];
+            y.src = at;
+            at += y.fan_out * y.K + y.fan_out;
+        }
+    }
+    hipLaunchKernelGGL(policy_pack_kernel, dim3((unsigned)count, (unsigned)((lay.n_device + 255) / 256)), dim3(256), 0, s, src, dst, map);
     return hipGetLastError();
 }
 
@@ -206,6 +271,25 @@ void policy_pack(const PolicyLayout& lay, const float* params, std::vector<float
             src += (size_t)fan_out * K;
             for (int jo = 0; jo < fan_out; ++jo) dev[(size_t)net.b[l] + jo] = src[jo];
             src += fan_out;
+        }
+    }
+}
+
+// the inverse of policy_pack: one member's device block -> its C-ABI parameter block (n_params floats)
+void policy_unpack(const PolicyLayout& lay, const float* dev, float* params) {
+    for (int i = 0; i < 10; ++i) params[i] = dev[i];
+    float* dst = params + 10;
+    const PolicyNet* nets[2] = {&lay.a, &lay.v};
+    const int n_out[2] = {3, 1};
+    for (int t = 0; t < 2; ++t) {
+        const PolicyNet& net = *nets[t];
+        for (int l = 0; l < net.n_layers; ++l) {
+            const int K = net.K[l], N = net.N[l], fan_out = l == net.n_layers - 1 ? n_out[t] : N;
+            for (int jo = 0; jo < fan_out; ++jo)
+                for (int k = 0; k < K; ++k) dst[(size_t)jo * K + k] = dev[(size_t)net.w[l] + (size_t)k * N + jo];
+            dst += (size_t)fan_out * K;
+            for (int jo = 0; jo < fan_out; ++jo) dst[jo] = dev[(size_t)net.b[l] + jo];
+            dst += fan_out;
         }
     }
 }

@@ -52,7 +52,24 @@ struct PolicyLayout {
 const char* policy_layout(const bsk_policy_spec& spec, PolicyLayout& out);
 void policy_pack(const PolicyLayout& lay, const float* params, std::vector<float>& device_block);
 
+// the inverse: one device block -> the C-ABI block of n_params floats (the padding is dropped)
+void policy_unpack(const PolicyLayout& lay, const float* device_block, float* params);
+
+// What the pack kernel walks: per layer (action network first) where its Wt[K][N] and b[N] lie in the device block and where its
+// W[fan_out][K], b[fan_out] start in the C-ABI block.
+struct PolicyPackMap {
+    struct Layer { int K, N, fan_out, w, b, src; };
+    int n_layers;                  // of both networks together
+    int n_params, n_device;
+    Layer layer[2 * POLICY_MAX_LAYERS];
+};
+
 hipError_t launch_policy(const PolicyArgs& args, hipStream_t s);
+// The population form: args.params holds one device block of n_device floats per member, spacecraft j runs member
+// j / envs_per_member; envs_per_member is a multiple of 64 and args.n a multiple of envs_per_member.
+hipError_t launch_policy_population(const PolicyArgs& args, int envs_per_member, int n_device, hipStream_t s);
+// `count` C-ABI blocks at src (device memory) -> `count` device blocks at dst, equal to policy_pack's bit for bit; enqueue-only
+hipError_t launch_policy_pack(const PolicyLayout& lay, const float* src, float* dst, int count, hipStream_t s);
 // draw += 1, one thread, behind a sample-mode policy launch on the same stream (a replayed graph draws new numbers)
 hipError_t launch_policy_advance(unsigned long long* rng, hipStream_t s);
 

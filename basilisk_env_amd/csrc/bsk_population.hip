@@ -1,0 +1,95 @@
+// bsk_population.hip — the fitness of a population rollout, formed on the device (bsk_population_rollout; definition in
+// include/bskgpu.h):
+//   fitness_row_kernel    row t of the rollout's histories AND one step of every env's value rule, one launch per env step
+//   fitness_join_kernel   one wave per member: the per-member mean of the values and of the episode lengths, in a fixed order
+// Compiled with -ffp-contract=off (Makefile), as bsk_fork.hip is: the additions and products are the ones a numpy restatement makes.
+#include "bsk_population.hpp"
+
+namespace bsk {
+
+// The per-env rule is bsk_select_branches' (bsk_fork.hip: select_kernel), one step per launch: while alive
+//   v = v + g * reward;  len += 1;  g = g * gamma;  alive ends after the first step with reason != 0 (that step's reward included)
+// - product and sum each rounded on their own.  With BSK_FLAG_AUTO_RESET the env goes on stepping; its later episodes find alive = 0.
+__global__ __launch_bounds__(256) void fitness_row_kernel(const double* __restrict__ obs, const double* __restrict__ reward,
+                                                          const unsigned char* __restrict__ reason, int64_t stride, int n,
+                                                          double* __restrict__ obs_row, double* __restrict__ reward_row,
+                                                          unsigned char* __restrict__ reason_row, const FitnessAcc acc, double gamma,
+                                                          int first) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (obs_row) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) obs_row[(int64_t)k * n + i] = obs[(int64_t)k * stride + i];
+    }
+    const double r = reward[i];
+    const unsigned char q = reason[i];
+    if (reward_row) reward_row[i] = r;
+    if (reason_row) reason_row[i] = q;
+    const bool alive = first || acc.alive[i] != 0;
+    if (!alive) return;
+    const double v = first ? 0.0 : acc.v[i];
+    const double g = first ? 1.0 : acc.g[i];
+    const int len = first ? 0 : acc.len[i];
+    const double p = g * r;
+    acc.v[i] = v + p;
+    acc.g[i] = g * gamma;
+    acc.len[i] = len + 1;
+    if (first || q != 0) acc.alive[i] = q != 0 ? 0 : 1;
+}
+
+hipError_t launch_fitness_row(const double* obs, const double* reward, const unsigned char* reason, int64_t stride, int n, double* obs_row,
+                              double* reward_row, unsigned char* reason_row, const FitnessAcc& acc, double gamma, bool first,
+                              hipStream_t s) {
+    hipLaunchKernelGGL(fitness_row_kernel, dim3((n + 255) / 256), dim3(256), 0, s, obs, reward, reason, stride, n, obs_row, reward_row,
+                       reason_row, acc, gamma, first ? 1 : 0);
+    return hipGetLastError();
+}
+
+// Member m is the envs m * E .. m * E + E - 1 (E a multiple of 64).  Lane l adds its elements l, l + 64, l + 128, ... in ascending
+// order, starting FROM the first (not from zero: -0.0 stays -0.0); then s[l] = s[l] + s[l + stride] for l < stride, stride = 32, 16,
+// ..., 1; the mean is s[0] / E.  No atomics, no dependence on the launch shape: numpy repeats it (policy.py: population_fitness_ref).
+__device__ __forceinline__ double fitness_tree(double s, int lane) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_down(s, off, 64);
+        if (lane < off) s = s + o;
+    }
+    return s;
+}
+
+__global__ __launch_bounds__(256) void fitness_join_kernel(const FitnessAcc acc, int n_members, int E, double* __restrict__ env_value,
+                                                           int* __restrict__ env_len, double* __restrict__ fitness,
+                                                           double* __restrict__ mean_len) {
+#pragma clang fp contract(off)
+    const int m = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));     // (wave-uniform)
+    const int lane = (int)(threadIdx.x & 63u);
+    if (m >= n_members) return;
+    const int64_t at0 = (int64_t)m * E + lane;
+    double sv = 0.0, sl = 0.0;
+    for (int c = 0; c < E; c += 64) {
+        const double v = acc.v[at0 + c];
+        const int len = acc.len[at0 + c];
+        if (env_value) env_value[at0 + c] = v;
+        if (env_len) env_len[at0 + c] = len;
+        sv = c == 0 ? v : sv + v;
+        sl = c == 0 ? (double)len : sl + (double)len;
+    }
+    sv = fitness_tree(sv, lane);
+    sl = fitness_tree(sl, lane);
+    if (lane == 0) {
+        if (fitness) fitness[m] = sv / (double)E;
+        if (mean_len) mean_len[m] = sl / (double)E;
+    }
+}
+
+hipError_t launch_fitness_join(const FitnessAcc& acc, int n_members, int envs_per_member, double* env_value, int* env_len,
+                               double* fitness, double* mean_len, hipStream_t s) {
+    if (!env_value && !env_len && !fitness && !mean_len) return hipSuccess;
+    hipLaunchKernelGGL(fitness_join_kernel, dim3((n_members + 3) / 4), dim3(256), 0, s, acc, n_members, envs_per_member, env_value,
+                       env_len, fitness, mean_len);
+    return hipGetLastError();
+}
+
+}  // namespace bsk

@@ -10,6 +10,10 @@ stable-baselines, outside the env.
 The arithmetic is fixed to the bit (include/bskgpu.h): every layer output is one k-ordered chain of f32 fused multiply-adds from
 the bias.  ``mlp_ref`` / ``act_ref`` restate it in numpy - for ``relu`` networks logits, value and greedy actions come out equal
 to the kernel's bit for bit - and need no device, like the argument rules.
+
+``PolicyPopulation`` holds P parameter sets of one spec (``bsk_population_*``): member m drives envs [m * E, (m + 1) * E) of one
+propagator, one launch per env step serves all members, and the per-member fitness of a rollout is formed on the device
+(``population_fitness_ref`` restates it in numpy, bit for bit).  ``EvolutionStrategy`` is the host-side loop around it.
 """
 import ctypes as C
 from collections import namedtuple
@@ -302,6 +306,35 @@ class _ViewOwner(object):
         self.prop.sync()
 
 
+def _observation_source(pol, source, env_base, stream):
+    """What ``act`` evaluates: a ``BatchedPropagator`` (or an env with a ``propagator``) - its own observation buffers, stream and
+    env_base - or a device array (5, n) float64 with contiguous rows.  -> (pointer, row stride, n, stream, env_base, owner of the
+    output views); ``pol`` is the policy or population that acts."""
+    prop = getattr(source, "propagator", source)
+    if hasattr(prop, "device_views") and hasattr(prop, "stream_ptr"):
+        if prop.device != pol.device:
+            raise ValueError("the policy lives on device %d, the propagator on device %d" % (pol.device, prop.device))
+        v = prop.device_views()
+        ptr, stride, n = v["obs"].__cuda_array_interface__["data"][0], v["stride"], prop.n_envs
+        stream = prop.stream_ptr() if stream is None else stream
+        env_base = getattr(prop, "env_base", 0) if env_base is None else env_base
+        owner = _ViewOwner(pol, prop)
+    else:
+        cai = getattr(source, "__cuda_array_interface__", None)
+        if cai is None:
+            raise TypeError("expected a BatchedPropagator or a device array with __cuda_array_interface__, got %r" % type(source))
+        shape, strides = tuple(cai["shape"]), cai.get("strides")
+        if cai["typestr"] != "<f8" or len(shape) != 2 or shape[0] != 5 or shape[1] < 1:
+            raise ValueError("observations: a float64 device array of shape (5, n), got %r %r" % (cai["typestr"], shape))
+        strides = (shape[1] * 8, 8) if strides is None else tuple(strides)
+        if strides[1] != 8 or strides[0] % 8 or strides[0] < shape[1] * 8:
+            raise ValueError("observations: rows must be contiguous and at least n elements apart")
+        ptr, stride, n = int(cai["data"][0]), strides[0] // 8, shape[1]
+        owner = pol
+        pol._source = source                   # (the launch reads it after this call returns)
+    return ptr, stride, n, int(stream or 0), int(env_base or 0), owner
+
+
 class DevicePolicy(object):
     """The policy on one GPU.  ``spec``: a ``Spec`` (``check_spec``); ``params``: its float32 parameter block (``pack_params``).
     Not thread-safe, and one stream at a time: the draw counter and the output buffers are single.  Output buffers are sized for
@@ -416,30 +449,8 @@ class DevicePolicy(object):
                 raise ValueError("want: 'logp', 'value' and / or 'logits', got %r" % (w,))
         if "value" in want and self.spec.value_hidden is None:
             raise ValueError("want 'value': the policy has no value network")
-        prop = getattr(source, "propagator", source)
-        if hasattr(prop, "device_views") and hasattr(prop, "stream_ptr"):
-            if prop.device != self.device:
-                raise ValueError("the policy lives on device %d, the propagator on device %d" % (self.device, prop.device))
-            v = prop.device_views()
-            ptr, stride, n = v["obs"].__cuda_array_interface__["data"][0], v["stride"], prop.n_envs
-            stream = prop.stream_ptr() if stream is None else stream
-            env_base = getattr(prop, "env_base", 0) if env_base is None else env_base
-            owner = _ViewOwner(self, prop)
-        else:
-            cai = getattr(source, "__cuda_array_interface__", None)
-            if cai is None:
-                raise TypeError("expected a BatchedPropagator or a device array with __cuda_array_interface__, got %r" % type(source))
-            shape, strides = tuple(cai["shape"]), cai.get("strides")
-            if cai["typestr"] != "<f8" or len(shape) != 2 or shape[0] != 5 or shape[1] < 1:
-                raise ValueError("observations: a float64 device array of shape (5, n), got %r %r" % (cai["typestr"], shape))
-            strides = (shape[1] * 8, 8) if strides is None else tuple(strides)
-            if strides[1] != 8 or strides[0] % 8 or strides[0] < shape[1] * 8:
-                raise ValueError("observations: rows must be contiguous and at least n elements apart")
-            ptr, stride, n = int(cai["data"][0]), strides[0] // 8, shape[1]
-            owner = self
-            self._source = source                  # (the launch reads it after this call returns)
-        stream = int(stream or 0)
-        out = self.enqueue(ptr, stride, n, mode, want, int(env_base or 0), stream)
+        ptr, stride, n, stream, env_base, owner = _observation_source(self, source, env_base, stream)
+        out = self.enqueue(ptr, stride, n, mode, want, env_base, stream)
         kw = {"owner": owner, "device": self.device, "stream": stream}
         res = {"action": _DevArray(out["action"].ptr, (n,), "<i4", **kw)}
         for name in want:
@@ -484,3 +495,268 @@ class DevicePolicy(object):
             for b in bufs.values():
                 b.free()
         return host
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Populations: P parameter sets on the device, member m driving envs [m * E, (m + 1) * E) of one handle (bsk_population_*)
+
+def population_fitness_ref(reward_hist, reason_hist, gamma, n_members):
+    """numpy restatement of the device fitness (include/bskgpu.h).  ``reward_hist`` (T, n) float64, ``reason_hist`` (T, n): the
+    rows a rollout records; n = n_members * E, E a multiple of 64.  -> dict: ``env_value`` (n,) float64 and ``env_len`` (n,) int32 -
+    per env v = v + g * reward, len += 1, g = g * gamma while alive, alive until the first step with reason != 0 (included) - and
+    ``fitness`` / ``mean_len`` (n_members,) float64: per member, lane l adds its elements l, l + 64, ... ascending from the first,
+    then s[l] = s[l] + s[l + stride] for stride 32 ... 1, then s[0] / E.  Every operation rounds on its own, in the kernel's order:
+    the results are equal bit for bit."""
+    r = np.asarray(reward_hist, np.float64)
+    q = np.asarray(reason_hist)
+    if r.ndim != 2 or q.shape != r.shape:
+        raise ValueError("reward_hist and reason_hist: (n_steps, n) each")
+    n, P = r.shape[1], int(n_members)
+    if P < 1 or n % P or (n // P) % 64 or n == 0:
+        raise ValueError("n must be n_members * envs_per_member, envs_per_member a positive multiple of 64")
+    E = n // P
+    gamma = np.float64(gamma)
+    v, g = np.zeros(n, np.float64), np.ones(n, np.float64)
+    length, alive = np.zeros(n, np.int32), np.ones(n, bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for t in range(r.shape[0]):
+            p = g * r[t]
+            v = np.where(alive, v + p, v)
+            g = np.where(alive, g * gamma, g)
+            length += alive
+            alive &= q[t] == 0
+
+        def mean(x):
+            x = x.reshape(P, E // 64, 64)
+            s = x[:, 0, :].copy()
+            for i in range(1, E // 64):
+                s = s + x[:, i, :]
+            for stride in (32, 16, 8, 4, 2, 1):
+                s[:, :stride] = s[:, :stride] + s[:, stride:2 * stride]
+            return s[:, 0] / np.float64(E)
+        return {"env_value": v, "env_len": length, "fitness": mean(v), "mean_len": mean(length.astype(np.float64))}
+
+
+class PolicyPopulation(object):
+    """``n_members`` parameter sets of one ``spec`` on one GPU.  With ``envs_per_member`` = E (a multiple of 64), spacecraft j is
+    driven by member j // E: ONE policy launch per env step serves every member, and ``rollout_device`` / ``evaluate`` form the
+    per-member fitness on the device.  ``params``: float32 (P, n_params), one ``pack_params`` block per row, or None with
+    ``n_members`` given (all-zero members).  Not thread-safe, one stream at a time, like ``DevicePolicy``."""
+
+    def __init__(self, spec, params=None, device=0, n_members=None):
+        self.spec = _as_spec(spec)
+        self.n_params = n_params(self.spec)
+        if params is None:
+            if n_members is None:
+                raise ValueError("give params (P, n_params) or n_members")
+            p, self.n_members = None, int(n_members)
+        else:
+            p = self._blocks(params, None)
+            self.n_members = p.shape[0]
+            if n_members is not None and int(n_members) != self.n_members:
+                raise ValueError("params has %d rows, n_members is %d" % (self.n_members, n_members))
+        self._lib = _lib.load()
+        self.device = int(device)
+        self._cs = c_spec(self.spec)
+        h = C.c_void_p()
+        check(self._lib.bsk_population_create(C.byref(self._cs), self.n_members, None if p is None else p.ctypes.data, self.device,
+                                              C.byref(h)))
+        self._p = h
+        self._out, self._out_n, self._source = None, 0, None
+
+    def _blocks(self, params, count):
+        p = np.ascontiguousarray(params, dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] != self.n_params or p.shape[0] < 1 or (count is not None and p.shape[0] != count):
+            raise ValueError("expected parameters of shape (%s, %d), got %r" % ("P" if count is None else count, self.n_params, p.shape))
+        return p
+
+    # ------------------------------------------------------------------ lifecycle
+    def close(self):
+        if getattr(self, "_p", None):
+            self._lib.bsk_population_destroy(self._p)
+            self._p = None
+        for b in (getattr(self, "_out", None) or {}).values():
+            b.free()
+        self._out = self._source = None
+
+    def __del__(self):
+        try:
+            import sys
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._p:
+            raise RuntimeError("population is closed")
+        return self._p
+
+    def sync(self):
+        """Waits for everything queued on the population's device (it keeps no stream of its own)."""
+        from . import _hip
+        with _hip.device_guard(self.device):
+            _hip.check(_hip.runtime().hipDeviceSynchronize(), "hipDeviceSynchronize")
+
+    # ------------------------------------------------------------------ parameters
+    def set_params(self, params):
+        """All members from a host array (P, n_params); synchronises the device."""
+        p = self._blocks(params, self.n_members)
+        check(self._lib.bsk_population_set_params(self._handle(), p.ctypes.data))
+
+    def set_params_device(self, src, first=0, count=None, stream=0):
+        """Members ``first .. first + count - 1`` from DEVICE memory: ``src`` a raw pointer to ``count`` blocks of n_params float32
+        (``count`` defaults to the members from ``first`` on), or anything with ``__cuda_array_interface__`` - a contiguous float32
+        array of (count, n_params) or count * n_params elements.  One launch on ``stream``: no copy, no synchronisation,
+        capturable.  A source array must stay alive until the launch has run."""
+        cai = getattr(src, "__cuda_array_interface__", None)
+        if cai is not None:
+            size = int(np.prod(cai["shape"])) if len(cai["shape"]) else 1
+            if cai["typestr"] != "<f4" or size % self.n_params or size == 0:
+                raise ValueError("device parameters: float32, a multiple of %d elements, got %r %r" % (self.n_params, cai["typestr"], cai["shape"]))
+            shape, strides = tuple(cai["shape"]), cai.get("strides")
+            dense = tuple(4 * int(np.prod(shape[k + 1:], dtype=np.int64)) for k in range(len(shape)))
+            if strides is not None and tuple(strides) != dense:
+                raise ValueError("device parameters must be contiguous")
+            if count is None:
+                count = size // self.n_params
+            elif int(count) * self.n_params != size:
+                raise ValueError("device parameters: %d members need %d elements, got %d" % (count, int(count) * self.n_params, size))
+            self._source = src
+            src = cai["data"][0]
+        if count is None:
+            count = self.n_members - int(first)
+        check(self._lib.bsk_population_set_params_device(self._handle(), C.c_void_p(int(src)) if src else None, int(first), int(count),
+                                                         C.c_void_p(int(stream or 0))))
+
+    def member(self, m):
+        """Member ``m``'s parameter block (n_params,) float32 - what ``DevicePolicy(spec, block)`` takes.  Synchronises."""
+        out = np.empty(self.n_params, np.float32)
+        check(self._lib.bsk_population_get_member(self._handle(), int(m), out.ctypes.data))
+        return out
+
+    def set_rng(self, seed, draw=0):
+        check(self._lib.bsk_population_set_rng(self._handle(), int(seed), int(draw)))
+
+    def get_rng(self):
+        """-> (seed, draw); synchronises."""
+        s, d = C.c_uint64(), C.c_uint64()
+        check(self._lib.bsk_population_get_rng(self._handle(), C.byref(s), C.byref(d)))
+        return s.value, d.value
+
+    # ------------------------------------------------------------------ evaluation
+    _buffers = DevicePolicy._buffers
+
+    def act(self, source, envs_per_member=None, mode="greedy", want=("logp", "value", "logits"), env_base=None, stream=None):
+        """``DevicePolicy.act`` under the member rule: spacecraft j of ``source`` (a propagator, or a device array (5, n) float64)
+        is evaluated with member j // envs_per_member (default n // n_members).  One launch, enqueue-only.  -> the same dict of
+        device views."""
+        from .simulators.dynamics.propagator import _DevArray
+        if mode not in MODES:
+            raise ValueError("mode must be 'greedy' or 'sample'")
+        want = tuple(want)
+        for w in want:
+            if w not in ("logp", "value", "logits"):
+                raise ValueError("want: 'logp', 'value' and / or 'logits', got %r" % (w,))
+        if "value" in want and self.spec.value_hidden is None:
+            raise ValueError("want 'value': the population has no value network")
+        ptr, stride, n, stream, env_base, owner = _observation_source(self, source, env_base, stream)
+        E = n // self.n_members if envs_per_member is None else int(envs_per_member)
+        out = self._buffers(n)
+        vp = lambda name: C.c_void_p(out[name].ptr) if name in want else None      # noqa: E731
+        check(self._lib.bsk_population_act(self._handle(), C.c_void_p(ptr), stride, n, E, env_base, MODES[mode],
+                                           C.c_void_p(out["action"].ptr), vp("logp"), vp("value"), vp("logits"), n, C.c_void_p(stream)))
+        kw = {"owner": owner, "device": self.device, "stream": stream}
+        res = {"action": _DevArray(out["action"].ptr, (n,), "<i4", **kw)}
+        for name in want:
+            res[name] = _DevArray(out[name].ptr, (3, n) if name == "logits" else (n,), "<f4", **kw)
+        return res
+
+    def rollout_device(self, prop, n_steps, substeps, mode="greedy", gamma=1.0, d_obs_hist=None, d_reward_hist=None, d_reason_hist=None,
+                       d_action_hist=None, d_logp_hist=None, d_value_hist=None, d_env_value=None, d_env_len=None, d_fitness=None,
+                       d_mean_len=None):
+        """``bsk_population_rollout`` with device pointers (or None): one generation on the propagator's stream - per env step the
+        policy launch for every member, the step, and one launch for the history rows and the running values; then the fitness
+        (``d_env_value`` f64[n], ``d_env_len`` i32[n], ``d_fitness`` f64[P], ``d_mean_len`` f64[P]).  No copy, no synchronisation;
+        capturable after a first rollout of the size has allocated the population's scratch rows."""
+        if mode not in MODES:
+            raise ValueError("mode must be 'greedy' or 'sample'")
+        prop = getattr(prop, "propagator", prop)
+        vp = lambda p: C.c_void_p(int(p)) if p else None      # noqa: E731
+        check(self._lib.bsk_population_rollout(self._handle(), prop._handle(), MODES[mode], int(substeps), int(n_steps), float(gamma),
+                                               vp(d_obs_hist), vp(d_reward_hist), vp(d_reason_hist), vp(d_action_hist), vp(d_logp_hist),
+                                               vp(d_value_hist), vp(d_env_value), vp(d_env_len), vp(d_fitness), vp(d_mean_len)))
+
+    def evaluate(self, prop, n_steps, substeps, mode="greedy", gamma=1.0):
+        """One generation with host results: -> dict ``fitness`` (P,), ``mean_len`` (P,), ``env_value`` (n,) float64 and ``env_len``
+        (n,) int32.  Allocates device scratch per call and synchronises: the convenience form; a search loop that keeps its
+        candidates on the device hands ``rollout_device`` its own buffers."""
+        from . import _hip
+        prop = getattr(prop, "propagator", prop)
+        n, P = prop.n_envs, self.n_members
+        host = {"env_value": np.empty(n, np.float64), "env_len": np.empty(n, np.int32), "fitness": np.empty(P, np.float64),
+                "mean_len": np.empty(P, np.float64)}
+        bufs = {k: _hip.DeviceBuffer(a.nbytes, self.device) for k, a in host.items()}
+        try:
+            self.rollout_device(prop, n_steps, substeps, mode, gamma, d_env_value=bufs["env_value"].ptr, d_env_len=bufs["env_len"].ptr,
+                                d_fitness=bufs["fitness"].ptr, d_mean_len=bufs["mean_len"].ptr)
+            stream = C.c_void_p(prop.stream_ptr())
+            for k, dst in host.items():
+                _hip.check(_hip.runtime().hipMemcpyAsync(C.c_void_p(dst.ctypes.data), C.c_void_p(bufs[k].ptr), dst.nbytes,
+                                                         _hip.hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")
+            prop.sync()
+        finally:
+            for b in bufs.values():
+                b.free()
+        return host
+
+
+def centred_ranks(fitness):
+    """(P,) fitness -> (P,) float64 utilities 0.5 (best) ... -0.5 (worst), evenly spaced.  The order is the library's ``beats`` rule
+    (bsk_select_branches): the greater value first, a NaN below every number, equal values (and NaNs) to the lower index."""
+    f = np.asarray(fitness, np.float64).reshape(-1)
+    nan = np.isnan(f)
+    order = np.lexsort((-np.where(nan, 0.0, f), nan))          # (stable: ties keep ascending index)
+    u = np.empty(f.size, np.float64)
+    u[order] = 0.5 - np.arange(f.size) / max(f.size - 1, 1)
+    return u
+
+
+class EvolutionStrategy(object):
+    """A small antithetic evolution strategy with centred-rank utilities (Salimans et al. 2017, "Evolution Strategies as a Scalable
+    Alternative to Reinforcement Learning"), host-side numpy: the piece that turns ``PolicyPopulation.evaluate`` into a search.
+    ``ask()`` -> (P, n) float32 members theta + sigma * eps_i (even rows) and theta - sigma * eps_i (odd rows), P even;
+    ``tell(fitness)`` moves theta by lr / (P * sigma) * sum_k u_k * (+-eps_k), u the ``centred_ranks`` of the fitness (greater is
+    better).  The first ``frozen`` floats - a policy block's in_scale and in_shift - are never perturbed nor moved.  Seeded: the
+    same seed asks the same members."""
+
+    def __init__(self, theta, population, sigma=0.1, lr=0.05, seed=0, frozen=10):
+        self.theta = np.array(theta, dtype=np.float64).reshape(-1)
+        self.population, self.sigma, self.lr, self.frozen = int(population), float(sigma), float(lr), int(frozen)
+        if self.population < 2 or self.population % 2:
+            raise ValueError("population must be even and >= 2")
+        if not (self.sigma > 0.0) or not (0 <= self.frozen <= self.theta.size):
+            raise ValueError("sigma must be positive and frozen within the parameter block")
+        self._rng = np.random.default_rng(seed)
+        self._eps = None
+
+    def ask(self):
+        eps = self._rng.standard_normal((self.population // 2, self.theta.size))
+        eps[:, :self.frozen] = 0.0
+        self._eps = eps
+        members = np.empty((self.population, self.theta.size), np.float64)
+        members[0::2] = self.theta + self.sigma * eps
+        members[1::2] = self.theta - self.sigma * eps
+        return members.astype(np.float32)
+
+    def tell(self, fitness):
+        if self._eps is None:
+            raise RuntimeError("tell() follows ask()")
+        u = centred_ranks(fitness)
+        if u.size != self.population:
+            raise ValueError("expected %d fitness values, got %d" % (self.population, u.size))
+        step = (u[0::2] - u[1::2]) @ self._eps
+        self.theta = self.theta + self.lr / (self.population * self.sigma) * step
+        self._eps = None
+        return self.theta.astype(np.float32)

@@ -489,6 +489,70 @@ int bsk_policy_rollout(bsk_policy* p, bsk_handle* h, int mode, int substeps, int
                        double* d_obs_hist, double* d_reward_hist, uint8_t* d_reason_hist,
                        int32_t* d_action_hist, float* d_logp_hist, float* d_value_hist);
 
+/* A population of policies: n_members parameter sets of ONE spec on the device, evaluated side by side - what forks were made for
+ * ("population training"): evolution strategies, CEM, population-based training.  The library has no autograd; gradient-free
+ * search over the parameters is how a policy is trained on it.
+ * Member <-> env rule: with envs_per_member = E, spacecraft j belongs to member j / E - member m drives the envs [m * E, (m + 1) * E)
+ * of one handle (or the columns of one observation block).  E is a multiple of 64 and n = n_members * E exactly: a group of 64
+ * spacecraft never straddles two members.
+ * Evaluation is the policy's, steps 1-6 above, with member j / E's parameter block (its own in_scale / in_shift included) in place
+ * of the single one; the same code evaluates both, so bsk_population_act equals, bit for bit and for either activation, n_members
+ * calls of bsk_policy_act with member m's parameters on columns [m * E, (m + 1) * E) and env_base + m * E.  One draw counter serves
+ * the population: sample mode reads philox at counter (env_base + j, draw) and one launch advances draw by one.
+ * Parameter blocks are in the C-ABI layout of bsk_policy_create, bsk_policy_n_params(spec) floats per member, member after member.
+ * Fitness (bsk_population_rollout), per env - the value rule of bsk_select_branches, accumulated step by step with no
+ * [n_steps][n] history: v = 0, g = 1, len = 0, alive; after each env step t, while alive:
+ *     v = v + g * reward  (product and sum each rounded on their own, no FMA);  len += 1;  g = g * gamma;
+ *     the env stops being alive after the first step with reason != 0 (that step's reward is included).
+ *   With BSK_FLAG_AUTO_RESET the env restarts and goes on stepping; its later episodes do not count.
+ * Per member, in f64 and in this order (numpy repeats it: basilisk_env_amd/policy.py population_fitness_ref):
+ *     s[l] = v[m*E + l], then s[l] = s[l] + v[m*E + l + 64*i] for i = 1, 2, ... ascending      (l = 0 .. 63)
+ *     for stride = 32, 16, 8, 4, 2, 1:  s[l] = s[l] + s[l + stride] for l < stride
+ *     fitness[m] = s[0] / E
+ *   and mean_len[m] the same over (double)len.  No atomics: the result does not depend on the launch shape.
+ * A population belongs to one device, is not thread-safe and serves ONE stream at a time (its draw counter, running values and
+ * scratch row of actions are single). */
+typedef struct bsk_population bsk_population;
+/* `params`: host pointer to n_members blocks, copied; NULL: every member all-zero.  seed = 0, draw = 0.  Checked in this order:
+ * the spec (BSK_EINVAL / BSK_EABI), n_members in 1..2^22 (BSK_EINVAL), then the device (BSK_ENODEV when no gfx950 device is
+ * usable). */
+int bsk_population_create(const bsk_policy_spec* spec, int n_members, const float* params, int device_id, bsk_population** out);
+void bsk_population_destroy(bsk_population* pop);
+/* As bsk_policy_set_rng / bsk_policy_get_rng: ordered after everything queued on the population's device, and synchronise it. */
+int bsk_population_set_rng(bsk_population* pop, uint64_t seed, uint64_t draw);
+int bsk_population_get_rng(bsk_population* pop, uint64_t* seed, uint64_t* draw);
+/* New parameters for ALL members from a host pointer (n_members blocks).  Ordered after everything queued on the population's
+ * device; synchronises it. */
+int bsk_population_set_params(bsk_population* pop, const float* params);
+/* New parameters for the members first .. first + count - 1 from DEVICE memory (d_params: count blocks): one launch on `stream` (a
+ * hipStream_t, NULL = the null stream) repacks them into the device's layout - the same bits bsk_population_set_params leaves -
+ * with no copy and no synchronisation; capturable.  Other members keep theirs.  The caller orders it against launches that read
+ * the population (the same stream does).  BSK_EINVAL: NULL pointers, first < 0, count < 1, first + count > n_members. */
+int bsk_population_set_params_device(bsk_population* pop, const float* d_params, int first, int count, void* stream);
+/* Member `member`'s parameters in the C-ABI layout (host pointer, bsk_policy_n_params floats): the block bsk_policy_create takes.
+ * Synchronises the device.  BSK_EINVAL for a member outside 0..n_members-1. */
+int bsk_population_get_member(bsk_population* pop, int member, float* params);
+/* bsk_policy_act with the member rule: arguments, layouts and checks as there, plus envs_per_member.  BSK_EINVAL (before anything
+ * is launched) also when envs_per_member is not a positive multiple of 64 or n != n_members * envs_per_member. */
+int bsk_population_act(bsk_population* pop, const double* d_obs, int64_t obs_stride, int n, int envs_per_member, int64_t env_base,
+                       int mode, int32_t* d_action, float* d_logp, float* d_value, float* d_logits, int64_t out_stride, void* stream);
+/* One generation: bsk_policy_rollout under the member rule, envs_per_member = n_envs / n_members, with the fitness formed on the
+ * device.  Per env step ONE policy launch serves all members, then bsk_step_device, then one launch that writes row t of the
+ * histories (the six pointers of bsk_policy_rollout, each may be NULL) and advances every env's value; behind the last step one
+ * launch writes
+ *   d_env_value f64[n_envs], d_env_len int32[n_envs]: v and len of every env;  d_fitness f64[n_members], d_mean_len f64[n_members]
+ * (each may be NULL).  The handle's buffers end as n_members separate bsk_policy_rollout calls on handles of E envs with env_base
+ * + m * E would leave them, bit for bit.  All DEVICE memory, enqueued on the handle's stream: no copy, no synchronisation,
+ * capturable once the population's scratch rows fit the handle (a first call of a size must allocate them and returns BSK_EINVAL
+ * under capture).  Uses the handle's env_base; works at every level, with the harmonics and with BSK_FLAG_AUTO_RESET.
+ * BSK_EINVAL before anything is launched: a NULL population or handle, substeps or n_steps < 1, a bad mode, n_envs not
+ * n_members * E with E a positive multiple of 64, d_value_hist without a value network, population and handle on different
+ * devices, a non-finite gamma, and bsk_step_n's preconditions (harmonics not set, auto-reset without a pool). */
+int bsk_population_rollout(bsk_population* pop, bsk_handle* h, int mode, int substeps, int n_steps, double gamma,
+                           double* d_obs_hist, double* d_reward_hist, uint8_t* d_reason_hist,
+                           int32_t* d_action_hist, float* d_logp_hist, float* d_value_hist,
+                           double* d_env_value, int32_t* d_env_len, double* d_fitness, double* d_mean_len);
+
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the
  * three-wave form's barrier-free exchange gives up after 2^20 polls instead of hanging, and says so here. */
