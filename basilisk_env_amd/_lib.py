@@ -85,6 +85,7 @@ EXPORTS = [
     "bsk_policy_act", "bsk_policy_rollout",
     "bsk_population_create", "bsk_population_destroy", "bsk_population_set_rng", "bsk_population_get_rng", "bsk_population_set_params",
     "bsk_population_set_params_device", "bsk_population_get_member", "bsk_population_act", "bsk_population_rollout",
+    "bsk_es_create", "bsk_es_destroy", "bsk_es_ask", "bsk_es_tell", "bsk_es_get_state", "bsk_es_set_state",
     "bsk_profile_begin", "bsk_profile_set_stride", "bsk_profile_end", "bsk_profile_end_samples", "bsk_calibrate_fp64", "bsk_kernel_info", "bsk_last_error", "bsk_version",
 ]
 
@@ -162,7 +163,10 @@ def load():
                        ("bsk_population_set_params_device", [vp, vp, C.c_int, C.c_int, vp]),
                        ("bsk_population_get_member", [vp, C.c_int, vp]),
                        ("bsk_population_act", [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, C.c_int64, vp]),
-                       ("bsk_population_rollout", [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])):
+                       ("bsk_population_rollout", [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+                       ("bsk_es_create", [P(BskPolicySpec), C.c_int, vp, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_int, P(vp)]),
+                       ("bsk_es_destroy", [vp]), ("bsk_es_ask", [vp, vp, vp]), ("bsk_es_tell", [vp, vp, vp]),
+                       ("bsk_es_get_state", [vp, vp, P(C.c_uint64)]), ("bsk_es_set_state", [vp, vp, C.c_uint64])):
         # (a BSKGPU_LIB variant built from an older tree - kernel A/B against a previous round - may predate these)
         if hasattr(lib, name) or not os.environ.get("BSKGPU_LIB"):
             getattr(lib, name).argtypes = args
@@ -170,6 +174,8 @@ def load():
         lib.bsk_policy_destroy.restype = None
     if hasattr(lib, "bsk_population_destroy"):
         lib.bsk_population_destroy.restype = None
+    if hasattr(lib, "bsk_es_destroy"):
+        lib.bsk_es_destroy.restype = None
     lib.bsk_get_obs.argtypes = [vp, vp, vp, vp, vp]
     lib.bsk_get_obs_device.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(C.c_int64)]
     lib.bsk_get_obs_state.argtypes = [vp, vp, vp, vp, vp]

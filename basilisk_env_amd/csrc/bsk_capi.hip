@@ -15,6 +15,7 @@
 
 #include "../../include/bskgpu.h"
 #include "bsk_aux.hpp"
+#include "bsk_es.hpp"
 #include "bsk_launch.hpp"
 #include "bsk_policy.hpp"
 #include "bsk_population.hpp"
@@ -498,6 +499,18 @@ struct bsk_population {
     bsk::FitnessAcc acc = {};
     int* d_act = nullptr;
     int scratch_cap = 0;
+};
+
+// bsk_es_*: the evolution strategy whose candidates never leave the device (bsk_es.hip)
+struct bsk_es {
+    bsk::PolicyLayout lay;
+    int device = 0;
+    int n_members = 0;
+    double sigma = 0.0, lr = 0.0;
+    int frozen = 0;
+    unsigned long long* d_state = nullptr; // {seed, generation}: generation advanced behind every tell
+    double* d_theta = nullptr;             // [lay.n_params]
+    double* d_w = nullptr;                 // [n_members / 2]: bsk_es_tell's scratch, the utility difference of every pair
 };
 
 namespace {
@@ -1874,6 +1887,116 @@ int bsk_population_rollout(bsk_population* p, bsk_handle* h, int mode, int subst
             HIP_TRY(bsk::launch_hist_row(h->d_obs, h->d_reward, h->d_reason, h->ostride, h->n, obs_row, reward_row, reason_row, h->stream));
     }
     HIP_TRY(bsk::launch_fitness_join(p->acc, p->n_members, E, d_env_value, d_env_len, d_fitness, d_mean_len, h->stream));
+    return BSK_OK;
+}
+
+int bsk_es_create(const bsk_policy_spec* spec, int n_members, const float* theta, double sigma, double lr, int frozen, uint64_t seed,
+                  int device_id, bsk_es** out) {
+    if (!out) return fail(BSK_EINVAL, "out is NULL");
+    *out = nullptr;
+    bsk::PolicyLayout lay;
+    int rc = policy_spec_layout(spec, lay);
+    if (rc) return rc;
+    if (n_members < 2 || n_members > 65536 || n_members % 2 != 0)
+        return fail(BSK_EINVAL, "bsk_es_create: n_members must be even and in 2..65536 (the ranking compares every pair of members)");
+    if (!std::isfinite(sigma) || !(sigma > 0.0)) return fail(BSK_EINVAL, "bsk_es_create: sigma must be finite and positive");
+    if (!std::isfinite(lr)) return fail(BSK_EINVAL, "bsk_es_create: lr must be finite");
+    if (frozen < 0 || frozen > lay.n_params) return fail(BSK_EINVAL, "bsk_es_create: frozen must be in 0..n_params");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(BSK_ENODEV, "no HIP device visible: libbskgpu has no CPU fallback");
+    if (device_id < 0 || device_id >= ndev) return fail(BSK_ENODEV, "device_id out of range");
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device_id));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(BSK_ENODEV, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    DeviceGuard guard(device_id);
+    bsk_es* es = new bsk_es();
+    es->lay = lay;
+    es->device = device_id;
+    es->n_members = n_members;
+    es->sigma = sigma;
+    es->lr = lr;
+    es->frozen = frozen;
+    const unsigned long long state0[2] = {seed, 0ull};
+    std::vector<double> theta0((size_t)lay.n_params, 0.0);
+    if (theta)
+        for (int j = 0; j < lay.n_params; ++j) theta0[(size_t)j] = (double)theta[j];
+    auto init = [&]() -> int {
+        HIP_TRY(hipMalloc(&es->d_state, sizeof state0));
+        HIP_TRY(hipMalloc(&es->d_theta, theta0.size() * sizeof(double)));
+        HIP_TRY(hipMalloc(&es->d_w, (size_t)(n_members / 2) * sizeof(double)));
+        HIP_COPY(hipMemcpy(es->d_state, state0, sizeof state0, hipMemcpyHostToDevice));
+        HIP_COPY(hipMemcpy(es->d_theta, theta0.data(), theta0.size() * sizeof(double), hipMemcpyHostToDevice));
+        return BSK_OK;
+    };
+    rc = init();
+    if (rc) { bsk_es_destroy(es); return rc; }
+    *out = es;
+    return BSK_OK;
+}
+
+void bsk_es_destroy(bsk_es* es) {
+    if (!es) return;
+    DeviceGuard guard(es->device);
+    if (es->d_state || es->d_theta || es->d_w) (void)hipDeviceSynchronize();
+    if (es->d_state) (void)hipFree(es->d_state);
+    if (es->d_theta) (void)hipFree(es->d_theta);
+    if (es->d_w) (void)hipFree(es->d_w);
+    delete es;
+}
+
+static bsk::EsArgs es_args(const bsk_es* es) {
+    bsk::EsArgs a;
+    a.state = es->d_state;
+    a.theta = es->d_theta;
+    a.sigma = es->sigma;
+    a.frozen = es->frozen;
+    a.pairs = es->n_members / 2;
+    return a;
+}
+
+int bsk_es_ask(bsk_es* es, bsk_population* pop, void* stream) {
+    if (!es || !pop) return fail(BSK_EINVAL, "es/population is NULL");
+    if (pop->n_members != es->n_members) return fail(BSK_EINVAL, "bsk_es_ask: the population's n_members differs from the optimiser's");
+    if (std::memcmp(&pop->lay, &es->lay, sizeof(bsk::PolicyLayout)) != 0)      // (all-int, value-initialised: policy_layout)
+        return fail(BSK_EINVAL, "bsk_es_ask: the population's spec differs from the optimiser's");
+    if (pop->device != es->device) return fail(BSK_EINVAL, "bsk_es_ask: the optimiser and the population live on different devices");
+    DeviceGuard guard(es->device);
+    HIP_TRY(bsk::launch_es_ask(es->lay, es_args(es), pop->d_params, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
+}
+
+int bsk_es_tell(bsk_es* es, const double* d_fitness, void* stream) {
+    if (!es || !d_fitness) return fail(BSK_EINVAL, "es/d_fitness is NULL");
+    DeviceGuard guard(es->device);
+    const double c = es->lr / ((double)es->n_members * es->sigma);
+    HIP_TRY(bsk::launch_es_rank(d_fitness, es->n_members, es->d_w, (hipStream_t)stream));
+    HIP_TRY(bsk::launch_es_tell(es_args(es), es->lay.n_params, es->d_w, c, (hipStream_t)stream));
+    HIP_TRY(bsk::launch_es_advance(es->d_state, (hipStream_t)stream));
+    return BSK_OK;
+}
+
+int bsk_es_get_state(bsk_es* es, double* theta, uint64_t* generation) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    DeviceGuard guard(es->device);
+    HIP_SYNC(hipDeviceSynchronize());
+    if (theta) HIP_COPY(hipMemcpy(theta, es->d_theta, (size_t)es->lay.n_params * sizeof(double), hipMemcpyDeviceToHost));
+    if (generation) {
+        unsigned long long w[2];
+        HIP_COPY(hipMemcpy(w, es->d_state, sizeof w, hipMemcpyDeviceToHost));
+        *generation = w[1];
+    }
+    return BSK_OK;
+}
+
+int bsk_es_set_state(bsk_es* es, const double* theta, uint64_t generation) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    DeviceGuard guard(es->device);
+    const unsigned long long g = generation;
+    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old state)
+    if (theta) HIP_COPY(hipMemcpy(es->d_theta, theta, (size_t)es->lay.n_params * sizeof(double), hipMemcpyHostToDevice));
+    HIP_COPY(hipMemcpy(es->d_state + 1, &g, sizeof g, hipMemcpyHostToDevice));
     return BSK_OK;
 }
 

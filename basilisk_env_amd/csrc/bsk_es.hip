@@ -1,0 +1,191 @@
+// bsk_es.hip — an antithetic evolution strategy with centred-rank utilities, on the device (bsk_es_*; definition in
+// include/bskgpu.h):
+//   es_ask_kernel      theta +- sigma * z straight into a population's device layout, z regenerated from a counter
+//   es_rank_kernel     one thread per member: how many members beat it -> the utility difference of every pair
+//   es_tell_kernel     one wave per parameter: the utilities contracted with the regenerated noise in a fixed order
+//   es_advance_kernel  the generation counter += 1
+// The noise is never stored: z(g, i, j) is one Philox4x32-10 call and an inverse normal CDF made of f64 + - * /, sqrt and integer
+// operations.  Compiled with -ffp-contract=off (Makefile), as bsk_population.hip is: every operation rounds on its own, and numpy
+// repeats all of it bit for bit (policy.py: es_noise_ref, es_ask_ref, es_tell_ref).
+#include "bsk_es.hpp"
+
+#include "bsk_philox.hpp"
+
+namespace bsk {
+
+// c0 + c1 x + ... + c7 x^7, Horner from the highest coefficient
+__device__ __forceinline__ double es_poly7(double x, double c0, double c1, double c2, double c3, double c4, double c5, double c6,
+                                           double c7) {
+#pragma clang fp contract(off)
+    double y = c7;
+    y = y * x + c6;
+    y = y * x + c5;
+    y = y * x + c4;
+    y = y * x + c3;
+    y = y * x + c2;
+    y = y * x + c1;
+    y = y * x + c0;
+    return y;
+}
+
+// ln(p) for a positive normal p: p = m * 2^e with m in [sqrt(1/2), sqrt(2)), ln(m) = 2 atanh(s) with s = (m - 1) / (m + 1) as its
+// series to s^23 (|s| < 0.1716: the first term left out is below 2^-64 of the sum)
+__device__ __forceinline__ double es_log(double p) {
+#pragma clang fp contract(off)
+    const long long bits = __double_as_longlong(p);
+    int e = (int)((bits >> 52) & 0x7ff) - 1022;
+    double m = __longlong_as_double((bits & 0x000fffffffffffffll) | 0x3fe0000000000000ll);     // [0.5, 1): frexp
+    if (m < 0.7071067811865476) { m = m + m; e -= 1; }
+    const double s = (m - 1.0) / (m + 1.0), s2 = s * s;
+    double t = 1.0 / 23.0;
+#pragma unroll
+    for (int k = 10; k >= 0; --k) t = t * s2 + 1.0 / (double)(2 * k + 1);
+    return (double)e * 0.6931471805599453 + (2.0 * s) * t;
+}
+
+// The inverse normal CDF of u in (0, 1): Wichura's AS 241 (PPND16) with the logarithm above
+__device__ __forceinline__ double es_inverse_normal(double u) {
+#pragma clang fp contract(off)
+    const double q = u - 0.5;
+    if (fabs(q) <= 0.425) {
+        const double r = 0.180625 - q * q;
+        return q * es_poly7(r, 3.3871328727963666080, 1.3314166789178437745e2, 1.9715909503065514427e3, 1.3731693765509461125e4,
+                            4.5921953931549871457e4, 6.7265770927008700853e4, 3.3430575583588128105e4, 2.5090809287301226727e3) /
+               es_poly7(r, 1.0, 4.2313330701600911252e1, 6.8718700749205790830e2, 5.3941960214247511077e3, 2.1213794301586595867e4,
+                        3.9307895800092710610e4, 2.8729085735721942674e4, 5.2264952788528545610e3);
+    }
+    const double p = q < 0.0 ? u : 1.0 - u;
+    const double r = sqrt(-es_log(p));
+    double z;
+    if (r <= 5.0) {
+        const double x = r - 1.6;
+        z = es_poly7(x, 1.42343711074968357734, 4.63033784615654529590, 5.76949722146069140550, 3.64784832476320460504,
+                     1.27045825245236838258, 2.41780725177450611770e-1, 2.27238449892691845833e-2, 7.74545014278341407640e-4) /
+            es_poly7(x, 1.0, 2.05319162663775882187, 1.67638483018380384940, 6.89767334985100004550e-1, 1.48103976427480074590e-1,
+                     1.51986665636164571966e-2, 5.47593808499534494600e-4, 1.05075007164441684324e-9);
+    } else {
+        const double x = r - 5.0;
+        z = es_poly7(x, 6.65790464350110377720, 5.46378491116411436990, 1.78482653991729133580, 2.96560571828504891230e-1,
+                     2.65321895265761230930e-2, 1.24266094738807843860e-3, 2.71155556874348757815e-5, 2.01033439929228813265e-7) /
+            es_poly7(x, 1.0, 5.99832206555887937690e-1, 1.36929880922735805310e-1, 1.48753612908506148525e-2, 7.86869131145613259100e-4,
+                     1.84631831751005468180e-5, 1.42151175831644588870e-7, 2.04426310338993978564e-15);
+    }
+    return q < 0.0 ? -z : z;
+}
+
+// z(g, i, j): key (seed), counter (j, i, g); 52 bits of the first two words -> u = (k + 0.5) * 2^-52, exact and inside (0, 1)
+__device__ __forceinline__ double es_noise(unsigned long long seed, unsigned long long g, unsigned i, unsigned j) {
+    unsigned w[4];
+    philox4x32_10(j, i, (unsigned)g, (unsigned)(g >> 32), (unsigned)seed, (unsigned)(seed >> 32), w);
+    const unsigned long long k = ((unsigned long long)(w[0] >> 6) << 26) + (unsigned long long)(w[1] >> 6);
+    return es_inverse_normal(((double)k + 0.5) * 0x1p-52);
+}
+
+// Pair blockIdx.x, float d of the device layout: policy_pack_kernel's gather with theta +- sigma * z in place of a source block.
+// Both members of the pair from ONE evaluation of z; every float of both device blocks is written by exactly one thread.
+__global__ __launch_bounds__(256) void es_ask_kernel(const EsArgs es, float* __restrict__ dst, const PolicyPackMap map) {
+#pragma clang fp contract(off)
+    const int d = (int)(blockIdx.y * blockDim.x + threadIdx.x);
+    if (d >= map.n_device) return;
+    const int j = policy_pack_source(map, d);
+    float plus = 0.0f, minus = 0.0f;
+    if (j >= 0) {
+        const double t = es.theta[j];
+        if (j < es.frozen) {
+            plus = minus = (float)t;
+        } else {
+            const double step = es.sigma * es_noise(es.state[0], es.state[1], blockIdx.x, (unsigned)j);
+            plus = (float)(t + step);
+            minus = (float)(t - step);
+        }
+    }
+    float* at = dst + (size_t)(2u * blockIdx.x) * (size_t)map.n_device + d;
+    at[0] = plus;
+    at[map.n_device] = minus;
+}
+
+// a (index ia) comes before b (index ib): bsk_fork.hip's beats() - the greater value, a NaN below every number, ties to the lower index
+__device__ __forceinline__ bool es_beats(double a, int ia, double b, int ib) {
+    const bool na = a != a, nb = b != b;
+    if (na != nb) return nb;
+    if (!na && a != b) return a > b;
+    return ia < ib;
+}
+
+// Thread k counts the members that beat member k, the fitness staged through LDS 256 values at a time (every thread of the
+// workgroup reads the same word: a broadcast); u_k = 0.5 - rank_k / max(P - 1, 1); the even thread of a pair writes u_2i - u_2i+1.
+__global__ __launch_bounds__(256) void es_rank_kernel(const double* __restrict__ fitness, int P, double* __restrict__ w) {
+#pragma clang fp contract(off)
+    __shared__ double tile[256];
+    const int k = (int)(blockIdx.x * 256u + threadIdx.x);
+    const bool live = k < P;
+    const double f = live ? fitness[k] : 0.0;
+    int rank = 0;
+    for (int base = 0; base < P; base += 256) {
+        const int m = base + (int)threadIdx.x;
+        __syncthreads();                   // (the previous tile's last reads)
+        tile[threadIdx.x] = m < P ? fitness[m] : 0.0;
+        __syncthreads();
+        const int count = P - base < 256 ? P - base : 256;
+        if (live)
+            for (int t = 0; t < count; ++t) rank += es_beats(tile[t], base + t, f, k) ? 1 : 0;
+    }
+    const double u = 0.5 - (double)rank / (double)(P - 1 > 1 ? P - 1 : 1);
+    const double odd = __shfl_down(u, 1, 64);       // (P is even: members 2i and 2i + 1 are neighbours in one wave)
+    if (live && (k & 1) == 0) w[k >> 1] = u - odd;
+}
+
+// the fitness tree (bsk_population.hip): s[l] = s[l] + s[l + stride] for l < stride, stride = 32 ... 1
+__device__ __forceinline__ double es_tree(double s, int lane) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_down(s, off, 64);
+        if (lane < off) s = s + o;
+    }
+    return s;
+}
+
+// One wave per parameter j >= frozen.  Lane l adds w_i * z(g, i, j) over its pairs i = l, l + 64, ... ascending, starting FROM the
+// first (+0.0 with no pair at all); the lanes join in the tree; lane 0 moves theta_j.  No atomics, no dependence on the launch shape.
+__global__ __launch_bounds__(256) void es_tell_kernel(const EsArgs es, int n_params, const double* __restrict__ w, double c) {
+#pragma clang fp contract(off)
+    const int j = es.frozen + (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));     // (wave-uniform)
+    const int lane = (int)(threadIdx.x & 63u);
+    if (j >= n_params) return;
+    const unsigned long long seed = es.state[0], g = es.state[1];
+    double s = 0.0;
+    for (int i = lane; i < es.pairs; i += 64) {
+        const double t = w[i] * es_noise(seed, g, (unsigned)i, (unsigned)j);
+        s = i == lane ? t : s + t;
+    }
+    s = es_tree(s, lane);
+    if (lane == 0) es.theta[j] = es.theta[j] + c * s;
+}
+
+__global__ void es_advance_kernel(unsigned long long* state) { state[1] += 1ull; }
+
+hipError_t launch_es_ask(const PolicyLayout& lay, const EsArgs& es, float* d_params, hipStream_t s) {
+    const PolicyPackMap map = policy_pack_map(lay);
+    hipLaunchKernelGGL(es_ask_kernel, dim3((unsigned)es.pairs, (unsigned)((lay.n_device + 255) / 256)), dim3(256), 0, s, es, d_params, map);
+    return hipGetLastError();
+}
+
+hipError_t launch_es_rank(const double* fitness, int n_members, double* w, hipStream_t s) {
+    hipLaunchKernelGGL(es_rank_kernel, dim3((unsigned)((n_members + 255) / 256)), dim3(256), 0, s, fitness, n_members, w);
+    return hipGetLastError();
+}
+
+hipError_t launch_es_tell(const EsArgs& es, int n_params, const double* w, double c, hipStream_t s) {
+    const int moving = n_params - es.frozen;
+    if (moving < 1) return hipSuccess;
+    hipLaunchKernelGGL(es_tell_kernel, dim3((unsigned)((moving + 3) / 4)), dim3(256), 0, s, es, n_params, w, c);
+    return hipGetLastError();
+}
+
+hipError_t launch_es_advance(unsigned long long* state, hipStream_t s) {
+    hipLaunchKernelGGL(es_advance_kernel, dim3(1), dim3(1), 0, s, state);
+    return hipGetLastError();
+}
+
+}  // namespace bsk

@@ -1,0 +1,28 @@
+// bsk_es.hpp — the evolution strategy on the device (bsk_es.hip; internal): what bsk_es_ask / bsk_es_tell launch.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "bsk_policy.hpp"
+
+namespace bsk {
+
+struct EsArgs {
+    const unsigned long long* state;   // {seed, generation}: device words, like the policy's {seed, draw}
+    double* theta;                     // [n_params], the C-ABI parameter layout
+    double sigma;
+    int frozen;                        // the first `frozen` parameters are neither perturbed nor moved
+    int pairs;                         // n_members / 2
+};
+
+// The members of this generation into d_params ([2 * pairs][lay.n_device], a population's device layout): one launch, every
+// float written exactly once.
+hipError_t launch_es_ask(const PolicyLayout& lay, const EsArgs& es, float* d_params, hipStream_t s);
+// fitness f64[n_members] -> w f64[n_members / 2]: the difference of the centred-rank utilities of each pair's two members
+hipError_t launch_es_rank(const double* fitness, int n_members, double* w, hipStream_t s);
+// theta_j = theta_j + c * sum_i w_i * z(g, i, j) for every j >= frozen, the sum in the fixed order of include/bskgpu.h
+hipError_t launch_es_tell(const EsArgs& es, int n_params, const double* w, double c, hipStream_t s);
+// generation += 1, one thread, behind a tell on the same stream (a replayed graph moves on to the next generation)
+hipError_t launch_es_advance(unsigned long long* state, hipStream_t s);
+
+}  // namespace bsk

@@ -160,18 +160,8 @@ __global__ __launch_bounds__(256) void policy_pack_kernel(const float* __restric
     const int d = (int)(blockIdx.y * blockDim.x + threadIdx.x);        // (members along x: there may be more than 65 535 of them)
     if (d >= map.n_device) return;
     const float* __restrict__ from = src + (size_t)blockIdx.x * (size_t)map.n_params;
-    float x = 0.0f;
-    if (d < 10) x = from[d];
-    for (int l = 0; l < map.n_layers; ++l) {
-        const PolicyPackMap::Layer& y = map.layer[l];
-        if (d >= y.w && d < y.w + y.K * y.N) {
-            const int k = (d - y.w) / y.N, jo = (d - y.w) % y.N;
-            if (jo < y.fan_out) x = from[y.src + jo * y.K + k];
-        } else if (d >= y.b && d < y.b + y.fan_out) {
-            x = from[y.src + y.fan_out * y.K + (d - y.b)];
-        }
-    }
-    dst[(size_t)blockIdx.x * (size_t)map.n_device + d] = x;
+    const int j = policy_pack_source(map, d);
+    dst[(size_t)blockIdx.x * (size_t)map.n_device + d] = j >= 0 ? from[j] : 0.0f;
 }
 
 __global__ void policy_advance_kernel(unsigned long long* rng) { rng[1] += 1ull; }
@@ -189,7 +179,7 @@ hipError_t launch_policy_population(const PolicyArgs& args, int envs_per_member,
     return hipGetLastError();
 }
 
-hipError_t launch_policy_pack(const PolicyLayout& lay, const float* src, float* dst, int count, hipStream_t s) {
+PolicyPackMap policy_pack_map(const PolicyLayout& lay) {
     PolicyPackMap map = {};
     map.n_params = lay.n_params;
     map.n_device = lay.n_device;
@@ -206,6 +196,11 @@ hipError_t launch_policy_pack(const PolicyLayout& lay, const float* src, float* 
             at += y.fan_out * y.K + y.fan_out;
         }
     }
+    return map;
+}
+
+hipError_t launch_policy_pack(const PolicyLayout& lay, const float* src, float* dst, int count, hipStream_t s) {
+    const PolicyPackMap map = policy_pack_map(lay);
     hipLaunchKernelGGL(policy_pack_kernel, dim3((unsigned)count, (unsigned)((lay.n_device + 255) / 256)), dim3(256), 0, s, src, dst, map);
     return hipGetLastError();
 }

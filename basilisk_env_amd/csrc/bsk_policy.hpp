@@ -63,6 +63,21 @@ struct PolicyPackMap {
     int n_params, n_device;
     Layer layer[2 * POLICY_MAX_LAYERS];
 };
+PolicyPackMap policy_pack_map(const PolicyLayout& lay);
+// Where float d of a device block comes from: the index of its source in the C-ABI block, or -1 for a zero of the padding.
+__device__ __forceinline__ int policy_pack_source(const PolicyPackMap& map, int d) {
+    int j = d < 10 ? d : -1;
+    for (int l = 0; l < map.n_layers; ++l) {
+        const PolicyPackMap::Layer& y = map.layer[l];
+        if (d >= y.w && d < y.w + y.K * y.N) {
+            const int k = (d - y.w) / y.N, jo = (d - y.w) % y.N;
+            if (jo < y.fan_out) j = y.src + jo * y.K + k;
+        } else if (d >= y.b && d < y.b + y.fan_out) {
+            j = y.src + y.fan_out * y.K + (d - y.b);
+        }
+    }
+    return j;
+}
 
 hipError_t launch_policy(const PolicyArgs& args, hipStream_t s);
 // The population form: args.params holds one device block of n_device floats per member, spacecraft j runs member

@@ -13,7 +13,9 @@ to the kernel's bit for bit - and need no device, like the argument rules.
 
 ``PolicyPopulation`` holds P parameter sets of one spec (``bsk_population_*``): member m drives envs [m * E, (m + 1) * E) of one
 propagator, one launch per env step serves all members, and the per-member fitness of a rollout is formed on the device
-(``population_fitness_ref`` restates it in numpy, bit for bit).  ``EvolutionStrategy`` is the host-side loop around it.
+(``population_fitness_ref`` restates it in numpy, bit for bit).  ``EvolutionStrategy`` is the host-side loop around it;
+``DeviceEvolutionStrategy`` (``bsk_es_*``) keeps theta on the device and asks, ranks and updates there, its noise regenerated from
+a counter instead of stored (``es_noise_ref`` / ``es_ask_ref`` / ``es_tell_ref`` restate it in numpy, bit for bit).
 """
 import ctypes as C
 from collections import namedtuple
@@ -760,3 +762,227 @@ class EvolutionStrategy(object):
         self.theta = self.theta + self.lr / (self.population * self.sigma) * step
         self._eps = None
         return self.theta.astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The evolution strategy on the device (bsk_es_*; definition in include/bskgpu.h, kernels in csrc/bsk_es.hip) and its restatement
+
+# Wichura's AS 241 (PPND16), coefficients lowest first
+_PPND_A = (3.3871328727963666080, 1.3314166789178437745e2, 1.9715909503065514427e3, 1.3731693765509461125e4,
+           4.5921953931549871457e4, 6.7265770927008700853e4, 3.3430575583588128105e4, 2.5090809287301226727e3)
+_PPND_B = (1.0, 4.2313330701600911252e1, 6.8718700749205790830e2, 5.3941960214247511077e3,
+           2.1213794301586595867e4, 3.9307895800092710610e4, 2.8729085735721942674e4, 5.2264952788528545610e3)
+_PPND_C = (1.42343711074968357734, 4.63033784615654529590, 5.76949722146069140550, 3.64784832476320460504,
+           1.27045825245236838258, 2.41780725177450611770e-1, 2.27238449892691845833e-2, 7.74545014278341407640e-4)
+_PPND_D = (1.0, 2.05319162663775882187, 1.67638483018380384940, 6.89767334985100004550e-1,
+           1.48103976427480074590e-1, 1.51986665636164571966e-2, 5.47593808499534494600e-4, 1.05075007164441684324e-9)
+_PPND_E = (6.65790464350110377720, 5.46378491116411436990, 1.78482653991729133580, 2.96560571828504891230e-1,
+           2.65321895265761230930e-2, 1.24266094738807843860e-3, 2.71155556874348757815e-5, 2.01033439929228813265e-7)
+_PPND_F = (1.0, 5.99832206555887937690e-1, 1.36929880922735805310e-1, 1.48753612908506148525e-2,
+           7.86869131145613259100e-4, 1.84631831751005468180e-5, 1.42151175831644588870e-7, 2.04426310338993978564e-15)
+
+
+def _horner(coef, x):
+    y = np.full_like(x, coef[-1])
+    for c in coef[-2::-1]:
+        y = y * x + c
+    return y
+
+
+def _series_log(p):
+    """ln(p) of include/bskgpu.h for p in (0, 0.5): frexp, then the atanh series in (m - 1) / (m + 1) - no library logarithm"""
+    m, e = np.frexp(p)
+    low = m < 0.7071067811865476
+    m = np.where(low, m + m, m)
+    e = np.where(low, e - 1, e).astype(np.float64)
+    s = (m - 1.0) / (m + 1.0)
+    s2 = s * s
+    t = np.full_like(s, 1.0 / 23.0)
+    for k in range(10, -1, -1):
+        t = t * s2 + 1.0 / (2 * k + 1)
+    return e * 0.6931471805599453 + (2.0 * s) * t
+
+
+def es_uniform_ref(k):
+    """52-bit integers k -> u = (k + 0.5) * 2**-52, exact and inside (0, 1)"""
+    return (np.asarray(k, np.uint64).astype(np.float64) + 0.5) * 2.0 ** -52
+
+
+def es_inverse_normal_ref(u):
+    """The inverse normal CDF of include/bskgpu.h on float64 u in (0, 1): AS 241 with a series logarithm, every operation one of
+    f64 + - * /, sqrt or an integer operation, each rounded on its own - the device's bits."""
+    u = np.asarray(u, np.float64)
+    q = u - 0.5
+    centre = np.abs(q) <= 0.425
+    r = 0.180625 - q * q
+    z = q * _horner(_PPND_A, r) / _horner(_PPND_B, r)
+    if not centre.all():
+        tail = ~centre
+        p = np.where(q[tail] < 0, u[tail], 1.0 - u[tail])
+        r = np.sqrt(-_series_log(p))
+        x, y = r - 1.6, r - 5.0
+        t = np.where(r <= 5.0, _horner(_PPND_C, x) / _horner(_PPND_D, x), _horner(_PPND_E, y) / _horner(_PPND_F, y))
+        z[tail] = np.where(q[tail] < 0, -t, t)
+    return z
+
+
+def es_noise_ref(seed, generation, pairs, n_params):
+    """z(g, i, j) of include/bskgpu.h -> float64 (pairs, n_params): Philox4x32-10 under key (seed lo, seed hi) at counter
+    (j, i, g lo, g hi); k = (w0 >> 6) * 2**26 + (w1 >> 6); u = (k + 0.5) * 2**-52; z = the inverse normal CDF of u."""
+    seed, g = np.uint64(int(seed)), np.uint64(int(generation))
+    j = np.broadcast_to(np.arange(int(n_params), dtype=np.uint64)[None, :], (int(pairs), int(n_params)))
+    i = np.broadcast_to(np.arange(int(pairs), dtype=np.uint64)[:, None], j.shape)
+    w0, w1, _, _ = philox4x32_10(j, i, g & _MASK32, g >> _SH32, seed & _MASK32, seed >> _SH32)
+    k = ((w0 >> np.uint64(6)) << np.uint64(26)) + (w1 >> np.uint64(6))
+    return es_inverse_normal_ref(es_uniform_ref(k))
+
+
+def es_ask_ref(theta, sigma, frozen, P, seed, generation):
+    """The members ``bsk_es_ask`` writes -> float32 (P, n_params): rows 2i / 2i + 1 are theta +- sigma * z(g, i, :), product and
+    sum each rounded in float64, then rounded to float32; the first ``frozen`` columns are (float)theta."""
+    theta = np.asarray(theta, np.float64).reshape(-1)
+    P, frozen = int(P), int(frozen)
+    step = np.float64(sigma) * es_noise_ref(seed, generation, P // 2, theta.size)
+    step[:, :frozen] = 0.0
+    members = np.empty((P, theta.size), np.float64)
+    members[0::2] = theta + step
+    members[1::2] = theta - step
+    members[:, :frozen] = theta[:frozen]
+    return members.astype(np.float32)
+
+
+def es_tell_ref(theta, fitness, sigma, lr, frozen, seed, generation):
+    """The theta ``bsk_es_tell`` leaves -> float64 (n_params,): w_i = u_2i - u_2i+1 of the ``centred_ranks``; per parameter
+    j >= frozen lane l = 0 .. 63 sums w_i * z(g, i, j) over its pairs i = l, l + 64, ... ascending from the first (+0.0 with no
+    pair), the lanes join as the fitness tree does (stride 32 ... 1), and theta_j = theta_j + lr / (P * sigma) * s[0]."""
+    theta = np.array(theta, dtype=np.float64).reshape(-1)
+    u = centred_ranks(fitness)
+    P, frozen = u.size, int(frozen)
+    if P < 2 or P % 2:
+        raise ValueError("expected an even number of fitness values, at least 2")
+    w = u[0::2] - u[1::2]
+    with np.errstate(invalid="ignore", over="ignore"):
+        terms = w[:, None] * es_noise_ref(seed, generation, P // 2, theta.size)
+        s = np.zeros((64, theta.size), np.float64)
+        s[:min(64, P // 2)] = terms[:64]
+        for at in range(64, P // 2, 64):
+            chunk = terms[at:at + 64]
+            s[:len(chunk)] = s[:len(chunk)] + chunk
+        for stride in (32, 16, 8, 4, 2, 1):
+            s[:stride] = s[:stride] + s[stride:2 * stride]
+        c = float(lr) / (float(P) * float(sigma))
+        theta[frozen:] = theta[frozen:] + c * s[0, frozen:]
+    return theta
+
+
+class DeviceEvolutionStrategy(object):
+    """``EvolutionStrategy``'s search with theta, the ranking and the update on the device (``bsk_es_*``): ``ask`` writes the
+    ``population`` = P members straight into a ``PolicyPopulation``'s device layout, ``tell`` reads the P float64 fitness values
+    a rollout left in device memory; both are enqueue-only and capturable, and the noise is regenerated from (seed, generation,
+    pair, parameter) instead of stored.  ``theta``: the float32 parameter block the search starts from (None: zeros).  Equal bit
+    for bit to ``es_ask_ref`` / ``es_tell_ref``.  Not thread-safe, one stream at a time."""
+
+    def __init__(self, spec, theta, population, sigma=0.1, lr=0.05, seed=0, frozen=10, device=0):
+        self.spec = _as_spec(spec)
+        self.n_params = n_params(self.spec)
+        self.population, self.sigma, self.lr, self.frozen = int(population), float(sigma), float(lr), int(frozen)
+        self.seed, self.device = int(seed), int(device)
+        t = None
+        if theta is not None:
+            t = np.ascontiguousarray(theta, dtype=np.float32).reshape(-1)
+            if t.size != self.n_params:
+                raise ValueError("expected %d parameters, got %d" % (self.n_params, t.size))
+        self._lib = _lib.load()
+        self._cs = c_spec(self.spec)
+        h = C.c_void_p()
+        check(self._lib.bsk_es_create(C.byref(self._cs), self.population, None if t is None else t.ctypes.data, self.sigma, self.lr,
+                                      self.frozen, self.seed, self.device, C.byref(h)))
+        self._p = h
+        self._fitness = self._source = None
+
+    # ------------------------------------------------------------------ lifecycle
+    def close(self):
+        if getattr(self, "_p", None):
+            self._lib.bsk_es_destroy(self._p)
+            self._p = None
+        if getattr(self, "_fitness", None) is not None:
+            self._fitness.free()
+        self._fitness = self._source = None
+
+    def __del__(self):
+        try:
+            import sys
+            if sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._p:
+            raise RuntimeError("evolution strategy is closed")
+        return self._p
+
+    # ------------------------------------------------------------------ state
+    @property
+    def theta(self):
+        """float64 (n_params,); synchronises."""
+        out = np.empty(self.n_params, np.float64)
+        check(self._lib.bsk_es_get_state(self._handle(), out.ctypes.data, None))
+        return out
+
+    @property
+    def generation(self):
+        """The generation the next ``ask`` / ``tell`` draw their noise for; synchronises."""
+        g = C.c_uint64()
+        check(self._lib.bsk_es_get_state(self._handle(), None, C.byref(g)))
+        return g.value
+
+    def set_state(self, theta=None, generation=0):
+        """New theta (float64 (n_params,), or None: keep) and generation counter; synchronises."""
+        t = None
+        if theta is not None:
+            t = np.ascontiguousarray(theta, dtype=np.float64).reshape(-1)
+            if t.size != self.n_params:
+                raise ValueError("expected %d parameters, got %d" % (self.n_params, t.size))
+        check(self._lib.bsk_es_set_state(self._handle(), None if t is None else t.ctypes.data, int(generation)))
+
+    # ------------------------------------------------------------------ the search
+    def ask(self, pop, stream=0):
+        """This generation's members into every member of ``pop`` (a ``PolicyPopulation`` of the same spec and size): one launch
+        on ``stream``, no copy, no synchronisation."""
+        check(self._lib.bsk_es_ask(self._handle(), pop._handle(), C.c_void_p(int(stream or 0))))
+
+    def tell(self, d_fitness, stream=0):
+        """``d_fitness``: P float64 in DEVICE memory (greater is better) - a raw pointer or anything with
+        ``__cuda_array_interface__``.  Ranks them, moves theta and advances the generation: three launches on ``stream``."""
+        cai = getattr(d_fitness, "__cuda_array_interface__", None)
+        if cai is not None:
+            size = int(np.prod(cai["shape"])) if len(cai["shape"]) else 1
+            strides = cai.get("strides")
+            if cai["typestr"] != "<f8" or size != self.population or (strides is not None and len(cai["shape"]) == 1 and strides[0] != 8):
+                raise ValueError("device fitness: %d contiguous float64, got %r %r" % (self.population, cai["typestr"], cai["shape"]))
+            self._source = d_fitness
+            d_fitness = cai["data"][0]
+        check(self._lib.bsk_es_tell(self._handle(), C.c_void_p(int(d_fitness)) if d_fitness else None, C.c_void_p(int(stream or 0))))
+
+    def fitness_buffer(self):
+        """The device buffer of P float64 ``run_generation`` has the rollout write the fitness to (``_hip.DeviceBuffer``)."""
+        if self._fitness is None:
+            from . import _hip
+            self._fitness = _hip.DeviceBuffer(8 * self.population, self.device)
+        return self._fitness
+
+    def run_generation(self, prop, pop, n_steps, substeps, mode="greedy", gamma=1.0, reset=True):
+        """One generation on the propagator's stream: every env restarted from the propagator's IC pool (``reset``; needs an
+        auto-reset pool), ``ask``, ``pop.rollout_device`` with the fitness into ``fitness_buffer()``, ``tell``.  Nothing else is
+        issued - no copy, no synchronisation - so after one warming call (it allocates the buffer and the population's scratch
+        rows) a call can be captured into a graph and replayed generation after generation."""
+        prop = getattr(prop, "propagator", prop)
+        fit = self.fitness_buffer()
+        stream = prop.stream_ptr()
+        if reset:
+            prop.reset_from_pool_device(None)
+        self.ask(pop, stream)
+        pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr)
+        self.tell(fit.ptr, stream)

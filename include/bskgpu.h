@@ -553,6 +553,76 @@ int bsk_population_rollout(bsk_population* pop, bsk_handle* h, int mode, int sub
                            int32_t* d_action_hist, float* d_logp_hist, float* d_value_hist,
                            double* d_env_value, int32_t* d_env_len, double* d_fitness, double* d_mean_len);
 
+/* An evolution strategy on the device: antithetic Gaussian perturbations with centred-rank utilities (Salimans et al. 2017), the
+ * optimiser a population was given bsk_population_set_params_device for - its candidates never leave the device and its noise is
+ * never stored: ask and tell regenerate it from (seed, generation, pair, parameter).  Reset, ask, rollout and tell are one stream
+ * of launches, so a captured graph replays generation after generation with no host in the loop.
+ * An optimiser holds theta f64[n_params] (the C-ABI parameter layout of bsk_policy_create), sigma > 0, lr, frozen (the first
+ * `frozen` floats are never perturbed nor moved; 10 covers in_scale and in_shift), an even n_members = P, a 64-bit seed and a
+ * 64-bit generation counter g kept in device words like the policy's {seed, draw}.
+ * Noise z(g, i, j) of generation g, pair i = 0 .. P/2 - 1, parameter j: ONE Philox4x32-10 call under the key (seed low word, seed
+ * high word) at the counter (j, i, g low word, g high word).  From its words w0, w1: k = (w0 >> 6) * 2^26 + (w1 >> 6), a 52-bit
+ * integer; u = (k + 0.5) * 2^-52, exact and inside (0, 1); z = the inverse normal CDF of u in f64 + - * /, sqrt and integer
+ * operations only, each rounded on its own (no FMA, no library log / exp), so that numpy repeats it bit for bit
+ * (basilisk_env_amd/policy.py: es_noise_ref).  It is Wichura's AS 241 (PPND16) with a series logarithm; |z| <= 8.2096:
+ *     q = u - 0.5
+ *     |q| <= 0.425:  r = 0.180625 - q*q;  z = q * A(r) / B(r)
+ *     else:  p = (q < 0) ? u : 1 - u  (exact);  r = sqrt(-ln(p));
+ *            z = (r <= 5) ? C(r - 1.6) / D(r - 1.6) : E(r - 5) / F(r - 5);  z = (q < 0) ? -z : z
+ *     ln(p): p = m * 2^e, m in [0.5, 1) (frexp); if m < 0.7071067811865476: m = 2m, e = e - 1
+ *            s = (m - 1) / (m + 1); s2 = s*s; t = 1/23; for k = 10 .. 0: t = t*s2 + 1/(2k+1)   (the constants rounded to f64)
+ *            ln(p) = e * 0.6931471805599453 + (2 * s) * t
+ *     A .. F: degree 7, Horner from the highest coefficient (X = X*x + coef); AS 241's coefficients, lowest first:
+ *     A: 3.3871328727963666080, 1.3314166789178437745e2, 1.9715909503065514427e3, 1.3731693765509461125e4,
+ *        4.5921953931549871457e4, 6.7265770927008700853e4, 3.3430575583588128105e4, 2.5090809287301226727e3
+ *     B: 1, 4.2313330701600911252e1, 6.8718700749205790830e2, 5.3941960214247511077e3,
+ *        2.1213794301586595867e4, 3.9307895800092710610e4, 2.8729085735721942674e4, 5.2264952788528545610e3
+ *     C: 1.42343711074968357734, 4.63033784615654529590, 5.76949722146069140550, 3.64784832476320460504,
+ *        1.27045825245236838258, 2.41780725177450611770e-1, 2.27238449892691845833e-2, 7.74545014278341407640e-4
+ *     D: 1, 2.05319162663775882187, 1.67638483018380384940, 6.89767334985100004550e-1,
+ *        1.48103976427480074590e-1, 1.51986665636164571966e-2, 5.47593808499534494600e-4, 1.05075007164441684324e-9
+ *     E: 6.65790464350110377720, 5.46378491116411436990, 1.78482653991729133580, 2.96560571828504891230e-1,
+ *        2.65321895265761230930e-2, 1.24266094738807843860e-3, 2.71155556874348757815e-5, 2.01033439929228813265e-7
+ *     F: 1, 5.99832206555887937690e-1, 1.36929880922735805310e-1, 1.48753612908506148525e-2,
+ *        7.86869131145613259100e-4, 1.84631831751005468180e-5, 1.42151175831644588870e-7, 2.04426310338993978564e-15
+ * ask: member 2i is (float)(theta_j + sigma * z(g,i,j)), member 2i + 1 is (float)(theta_j - sigma * z(g,i,j)); for j < frozen both
+ *   are (float)theta_j.  Product and sum each round in f64, the conversion rounds to nearest even.  Written straight into the
+ *   population's device layout (its padding as zeros), every float exactly once.
+ * tell, given fitness f64[P] in device memory (greater is better):
+ *   1. rank_k = the number of members that beat member k under the rule of bsk_select_branches: the greater value wins, a NaN is
+ *      below every number, ties (and NaNs) go to the lower index.
+ *   2. u_k = 0.5 - (double)rank_k / max(P - 1, 1)  (basilisk_env_amd/policy.py: centred_ranks);  w_i = u_2i - u_2i+1.
+ *   3. for every j >= frozen, in the fitness tree's order:
+ *        s[l] = w_l * z(g,l,j), or +0.0 when l >= P/2                                  (l = 0 .. 63)
+ *        s[l] = s[l] + w_(l+64m) * z(g, l+64m, j) for m = 1, 2, ... ascending while l + 64m < P/2
+ *        for stride = 32, 16, 8, 4, 2, 1:  s[l] = s[l] + s[l + stride] for l < stride
+ *        theta_j = theta_j + c * s[0],  c = lr / ((double)P * sigma) formed once on the host
+ *      No atomics: the result does not depend on the launch shape (policy.py: es_tell_ref repeats it bit for bit).
+ *   4. behind the update a one-thread launch makes generation = generation + 1, so a captured graph advances on every replay.
+ *   tell does not require that ask ran: it uses generation g's noise either way, and the caller orders the two.
+ * An optimiser belongs to one device, is not thread-safe and serves ONE stream at a time (its scratch is single). */
+typedef struct bsk_es bsk_es;
+/* `theta`: host pointer to bsk_policy_n_params(spec) floats, copied (as doubles); NULL: zeros.  generation = 0.  All device scratch
+ * is allocated here.  Checked in this order: the spec (BSK_EINVAL / BSK_EABI); BSK_EINVAL for n_members odd, below 2 or above
+ * 65536 (the ranking compares every pair of members), sigma not finite or not positive, lr not finite, frozen outside
+ * 0..n_params; then the device (BSK_ENODEV when no gfx950 device is usable). */
+int bsk_es_create(const bsk_policy_spec* spec, int n_members, const float* theta, double sigma, double lr, int frozen, uint64_t seed,
+                  int device_id, bsk_es** out);
+void bsk_es_destroy(bsk_es* es);
+/* This generation's members into ALL members of `pop`: one launch on `stream` (a hipStream_t, NULL = the null stream), no copy, no
+ * synchronisation; capturable.  The caller orders it against launches that read the population (the same stream does).
+ * BSK_EINVAL before anything is launched: NULL pointers, a population with a different n_members or a different spec, or one on
+ * a different device. */
+int bsk_es_ask(bsk_es* es, bsk_population* pop, void* stream);
+/* Ranks d_fitness (DEVICE memory, f64[n_members]: what bsk_population_rollout's d_fitness holds), moves theta and advances the
+ * generation: three launches on `stream`, no copy, no synchronisation; capturable.  BSK_EINVAL for NULL pointers. */
+int bsk_es_tell(bsk_es* es, const double* d_fitness, void* stream);
+/* theta (host pointer, f64[n_params], or NULL) and the generation counter (or NULL).  Ordered after everything queued on the
+ * optimiser's device; synchronises it. */
+int bsk_es_get_state(bsk_es* es, double* theta, uint64_t* generation);
+/* A new theta (host pointer, f64[n_params]; NULL: keep) and generation counter.  Synchronises the device. */
+int bsk_es_set_state(bsk_es* es, const double* theta, uint64_t generation);
+
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the
  * three-wave form's barrier-free exchange gives up after 2^20 polls instead of hanging, and says so here. */

@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""Cost of a generation of the evolution strategy ("The evolution strategy on the device"): 65 536 spacecraft,
+`tanh [64, 64]`, K = 1, P = 64 and 1 024 members, a 200-step generation after a warming one.
+
+  python tools/es_measure.py loop
+      host clock around one generation and a synchronisation, profiler off; three runs, alternating:
+        host    the loop as it was before the optimiser moved: `EvolutionStrategy.ask` -> `set_params` -> reset from the pool ->
+                `evaluate` -> `tell`
+        device  `DeviceEvolutionStrategy.run_generation`
+        graph   the same call captured once into a HIP graph and replayed
+        rollout reset from the pool and `rollout_device` alone: what the device loop is expected to approach
+  python tools/es_measure.py kernel
+      per P one warming and three measured generations of `run_generation`.  Run it under the profiler in a run of its own:
+      rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o es -- python tools/es_measure.py kernel
+  python tools/es_measure.py stats DIR/.../es_kernel_trace.csv
+      per measured generation of that run the times of es_ask_kernel, es_rank_kernel and es_tell_kernel and the sum over every
+      other kernel of the generation (the generations are recognised by the es_advance_kernel that ends each)
+"""
+import csv
+import os
+import sys
+import time
+
+import numpy as np
+
+N, T, WARM_T, ROUNDS = 65536, 200, 10, 3
+MEMBERS = (64, 1024)
+GAMMA = 0.99
+
+
+def _setup():
+    import torch
+    from basilisk_env_amd import policy as P
+    from basilisk_env_amd.envs.leoPowerAttitudeVecEnv import LeoPowerAttVecEnv
+    side = torch.cuda.Stream()
+    env = LeoPowerAttVecEnv(N, device_reset_pool=4096, device_sampler=True, stream=side.cuda_stream)
+    env.reset_tensors()
+    prop = env.propagator
+    prop.step(np.zeros(N, np.int32), 1)
+    spec = P.check_spec((64, 64), "tanh")
+    rng = np.random.default_rng(7)
+    a, _ = P.layer_shapes(spec)
+    layers = [(rng.normal(0.0, np.sqrt(1.0 / i), (o, i)).astype(np.float32), rng.normal(0.0, 0.3, o).astype(np.float32)) for o, i in a]
+    theta = P.pack_params(spec, layers, None, [2.0, 50.0, 1.5, 1.25, 0.75], [-0.5, 0.1, -0.3, -0.6, 0.2])
+    return torch, P, side, env, prop, spec, theta
+
+
+def loop():
+    torch, P, side, env, prop, spec, theta = _setup()
+    with torch.cuda.stream(side):
+        variants = []
+        for m in MEMBERS:
+            pop = P.PolicyPopulation(spec, n_members=m)
+            host = P.EvolutionStrategy(theta, m, sigma=0.1, lr=0.05, seed=1)
+            dev = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
+            rep = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
+            fit = torch.zeros(m, dtype=torch.float64, device="cuda")
+
+            def host_gen(steps, pop=pop, host=host):
+                pop.set_params(host.ask())
+                prop.reset_from_pool_device(None)
+                host.tell(pop.evaluate(prop, steps, 1, "greedy", GAMMA)["fitness"])
+
+            def device_gen(steps, pop=pop, dev=dev):
+                dev.run_generation(prop, pop, steps, 1, "greedy", GAMMA)
+
+            def rollout_gen(steps, pop=pop, fit=fit):
+                prop.reset_from_pool_device(None)
+                pop.rollout_device(prop, steps, 1, "greedy", GAMMA, d_fitness=fit.data_ptr())
+
+            rep.run_generation(prop, pop, WARM_T, 1, "greedy", GAMMA)
+            prop.sync()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                rep.run_generation(prop, pop, T, 1, "greedy", GAMMA)
+
+            def graph_gen(steps, graph=graph):
+                if steps == T:
+                    graph.replay()
+
+            variants += [("host   P = %d" % m, host_gen), ("device P = %d" % m, device_gen), ("graph  P = %d" % m, graph_gen),
+                         ("rollout P = %d" % m, rollout_gen)]
+        res = {name: [] for name, _ in variants}
+        for _ in range(ROUNDS):
+            for name, run in variants:
+                run(WARM_T)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run(T)
+                torch.cuda.synchronize()
+                res[name].append((time.perf_counter() - t0) * 1e6)
+        for name, _ in variants:
+            print("%-18s us per %d-step generation: %s" % (name, T, ", ".join("%.0f" % x for x in res[name])))
+    env.close()
+
+
+def kernel():
+    torch, P, side, env, prop, spec, theta = _setup()
+    with torch.cuda.stream(side):
+        for m in MEMBERS:
+            pop = P.PolicyPopulation(spec, n_members=m)
+            dev = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
+            dev.run_generation(prop, pop, WARM_T, 1, "greedy", GAMMA)
+            for _ in range(ROUNDS):
+                dev.run_generation(prop, pop, T, 1, "greedy", GAMMA)
+            prop.sync()
+    print("per P in %r: one warming generation of %d steps, then %d of %d steps" % (MEMBERS, WARM_T, ROUNDS, T))
+    env.close()
+
+
+def stats(path):
+    rows = []
+    with open(path) as f:
+        for r in csv.DictReader(f):
+            rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]) - int(r["Start_Timestamp"]), r["Kernel_Name"]))
+    rows.sort()
+    gens, cur, seen = [], {}, False
+    for _, d, name in rows:
+        key = next((k for k in ("es_ask_kernel", "es_rank_kernel", "es_tell_kernel", "es_advance_kernel") if k in name), "rest")
+        seen = seen or key == "es_ask_kernel"
+        if not seen:
+            continue                           # (the set-up's launches, before the first generation)
+        cur[key] = cur.get(key, 0) + d
+        if key == "es_advance_kernel":
+            gens.append(cur)
+            cur = {}
+    assert len(gens) == len(MEMBERS) * (1 + ROUNDS), len(gens)
+    for b, m in enumerate(MEMBERS):
+        for g in gens[b * (1 + ROUNDS) + 1:(b + 1) * (1 + ROUNDS)]:
+            print("P = %-5d ask %8.1f us, rank %7.1f us, tell %8.1f us, every other kernel of the generation %9.1f us" %
+                  (m, g["es_ask_kernel"] / 1e3, g["es_rank_kernel"] / 1e3, g["es_tell_kernel"] / 1e3, g["rest"] / 1e3))
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    what = sys.argv[1] if len(sys.argv) > 1 else ""
+    if what == "loop":
+        loop()
+    elif what == "kernel":
+        kernel()
+    elif what == "stats":
+        stats(sys.argv[2])
+    else:
+        sys.exit(__doc__)
