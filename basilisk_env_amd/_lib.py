@@ -65,6 +65,7 @@ class BskConfig(C.Structure):
 
 POLICY_RELU, POLICY_TANH = 0, 1
 POLICY_GREEDY, POLICY_SAMPLE = 0, 1
+ES_SGD, ES_ADAM = 0, 1
 
 
 class BskPolicySpec(C.Structure):
@@ -79,13 +80,14 @@ class BskPolicySpec(C.Structure):
 EXPORTS = [
     "bsk_default_config", "bsk_create", "bsk_destroy", "bsk_set_gravity_sh", "bsk_reset", "bsk_step",
     "bsk_step_device", "bsk_step_device_i64", "bsk_step_n", "bsk_get_episode_device", "bsk_get_batch_stats_device", "bsk_set_step_stats", "bsk_reset_from_pool_device", "bsk_debug_counters", "bsk_debug_words", "bsk_get_obs", "bsk_get_obs_rowmajor", "bsk_get_obs_device", "bsk_get_obs_state", "bsk_get_stream", "bsk_get_terminal_obs_device", "bsk_get_state_device", "bsk_get_batch_stats", "bsk_n_fields",
-    "bsk_get_state", "bsk_set_state", "bsk_get_counters", "bsk_set_counters", "bsk_set_ic_pool", "bsk_sample_ic_pool", "bsk_reset_from_pool", "bsk_get_ic_pool", "bsk_get_terminal_obs", "bsk_set_env_base", "bsk_set_sim_time", "bsk_sync",
+    "bsk_get_state", "bsk_set_state", "bsk_get_counters", "bsk_set_counters", "bsk_set_ic_pool", "bsk_sample_ic_pool", "bsk_reset_from_pool", "bsk_reset_from_pool_shared", "bsk_get_ic_pool", "bsk_get_terminal_obs", "bsk_set_env_base", "bsk_set_sim_time", "bsk_sync",
     "bsk_fork_device", "bsk_fork", "bsk_select_branches", "bsk_beam_select",
     "bsk_policy_n_params", "bsk_policy_create", "bsk_policy_set_params", "bsk_policy_destroy", "bsk_policy_set_rng", "bsk_policy_get_rng",
     "bsk_policy_act", "bsk_policy_rollout",
     "bsk_population_create", "bsk_population_destroy", "bsk_population_set_rng", "bsk_population_get_rng", "bsk_population_set_params",
     "bsk_population_set_params_device", "bsk_population_get_member", "bsk_population_act", "bsk_population_rollout",
     "bsk_es_create", "bsk_es_destroy", "bsk_es_ask", "bsk_es_tell", "bsk_es_get_state", "bsk_es_set_state",
+    "bsk_es_generation_device", "bsk_es_set_optimizer", "bsk_es_get_moments", "bsk_es_set_moments",
     "bsk_profile_begin", "bsk_profile_set_stride", "bsk_profile_end", "bsk_profile_end_samples", "bsk_calibrate_fp64", "bsk_kernel_info", "bsk_last_error", "bsk_version",
 ]
 
@@ -166,7 +168,10 @@ def load():
                        ("bsk_population_rollout", [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
                        ("bsk_es_create", [P(BskPolicySpec), C.c_int, vp, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_int, P(vp)]),
                        ("bsk_es_destroy", [vp]), ("bsk_es_ask", [vp, vp, vp]), ("bsk_es_tell", [vp, vp, vp]),
-                       ("bsk_es_get_state", [vp, vp, P(C.c_uint64)]), ("bsk_es_set_state", [vp, vp, C.c_uint64])):
+                       ("bsk_es_get_state", [vp, vp, P(C.c_uint64)]), ("bsk_es_set_state", [vp, vp, C.c_uint64]),
+                       ("bsk_reset_from_pool_shared", [vp, C.c_int, vp, vp]), ("bsk_es_generation_device", [vp, P(vp)]),
+                       ("bsk_es_set_optimizer", [vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]),
+                       ("bsk_es_get_moments", [vp, vp, vp, vp]), ("bsk_es_set_moments", [vp, vp, vp, vp])):
         # (a BSKGPU_LIB variant built from an older tree - kernel A/B against a previous round - may predate these)
         if hasattr(lib, name) or not os.environ.get("BSKGPU_LIB"):
             getattr(lib, name).argtypes = args

@@ -298,6 +298,25 @@ __global__ void reset_from_pool_kernel(double* __restrict__ st, int64_t stride, 
     init_outputs(ro, st, stride, i);
 }
 
+// The same reset with a slot rule that members of a population SHARE: the global index only through q = g mod envs_per_member, and
+// an epoch word read from device memory in place of the env's own episode count (a replayed graph draws anew).  No floating-point
+// operation of its own: the first observation is init_outputs', as in every other reset.
+__global__ void reset_from_pool_shared_kernel(double* __restrict__ st, int64_t stride, int nf, const double* __restrict__ pool,
+                                              int n_pool, const unsigned char* __restrict__ mask, int n, int2* __restrict__ cnt,
+                                              int* __restrict__ episodes, unsigned env_base, unsigned envs_per_member,
+                                              const unsigned long long* __restrict__ epoch, const ResetOut ro) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || (mask && !mask[i])) return;
+    episodes[i] = episodes[i] + 1;
+    const unsigned e = epoch ? (unsigned)*epoch : 0u;
+    const unsigned q = ((unsigned)i + env_base) % envs_per_member;
+    const unsigned slot = (q * 2654435761u + e * 40503u + 12345u) % (unsigned)n_pool;
+    for (int f = 0; f < nf; ++f) st[f * stride + i] = pool[(int64_t)f * n_pool + slot];
+    cnt[i] = make_int2(0, 0);
+    init_outputs(ro, st, stride, i);
+}
+
 // after a reset from host initial conditions: all n envs (idx == NULL) or the m listed ones
 __global__ void init_outputs_kernel(const double* __restrict__ st, int64_t stride, const int* __restrict__ idx, int m, const ResetOut ro) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -315,6 +334,14 @@ hipError_t launch_reset_from_pool(double* st, int64_t stride, int nf, const doub
                                   int n, int2* cnt, int* episodes, unsigned env_base, const ResetOut& ro, hipStream_t s) {
     hipLaunchKernelGGL(reset_from_pool_kernel, dim3((n + 255) / 256), dim3(256), 0, s, st, stride, nf, pool, n_pool, mask, n, cnt,
                        episodes, env_base, ro);
+    return hipGetLastError();
+}
+
+hipError_t launch_reset_from_pool_shared(double* st, int64_t stride, int nf, const double* pool, int n_pool, const unsigned char* mask,
+                                         int n, int2* cnt, int* episodes, unsigned env_base, unsigned envs_per_member,
+                                         const unsigned long long* epoch, const ResetOut& ro, hipStream_t s) {
+    hipLaunchKernelGGL(reset_from_pool_shared_kernel, dim3((n + 255) / 256), dim3(256), 0, s, st, stride, nf, pool, n_pool, mask, n, cnt,
+                       episodes, env_base, envs_per_member, epoch, ro);
     return hipGetLastError();
 }
 

@@ -24,6 +24,10 @@ struct ResetOut {
 hipError_t launch_sample_pool(double* pool, int n_pool, int n_rw, unsigned long long seed, double mu, hipStream_t s);
 hipError_t launch_reset_from_pool(double* st, int64_t stride, int nf, const double* pool, int n_pool, const unsigned char* mask,
                                   int n, int2* cnt, int* episodes, unsigned env_base, const ResetOut& ro, hipStream_t s);
+// bsk_reset_from_pool_shared: slot from (env_base + env) mod envs_per_member and the low word of *epoch (NULL: 0), include/bskgpu.h
+hipError_t launch_reset_from_pool_shared(double* st, int64_t stride, int nf, const double* pool, int n_pool, const unsigned char* mask,
+                                         int n, int2* cnt, int* episodes, unsigned env_base, unsigned envs_per_member,
+                                         const unsigned long long* epoch, const ResetOut& ro, hipStream_t s);
 // first observation [|sigma_BN|, |omega|, |Omega|/limit, charge/3600/power_max, 1], zero reward / reason / done / episode
 // return of freshly reset envs: all n (idx == NULL) or the m listed ones
 hipError_t launch_init_outputs(const double* st, int64_t stride, const int* idx, int m, const ResetOut& ro, hipStream_t s);

@@ -511,6 +511,10 @@ struct bsk_es {
     unsigned long long* d_state = nullptr; // {seed, generation}: generation advanced behind every tell
     double* d_theta = nullptr;             // [lay.n_params]
     double* d_w = nullptr;                 // [n_members / 2]: bsk_es_tell's scratch, the utility difference of every pair
+    // bsk_es_set_optimizer: BSK_ES_SGD until Adam is selected; then ONE allocation [m | v | beta_pow] of 2 * n_params + 2 doubles
+    int optimizer = BSK_ES_SGD;
+    double beta1 = 0.0, beta2 = 0.0, eps = 0.0, weight_decay = 0.0;
+    double* d_adam = nullptr;
 };
 
 namespace {
@@ -1480,6 +1484,20 @@ int bsk_reset_from_pool_device(bsk_handle* h, const uint8_t* d_mask) {
     return BSK_OK;       // asynchronous on the handle's stream: no host data, no copy, no synchronisation
 }
 
+int bsk_reset_from_pool_shared(bsk_handle* h, int envs_per_member, const uint64_t* d_epoch, const uint8_t* d_mask) {
+    if (!h) return fail(BSK_EINVAL, "handle is NULL");
+    if (h->n_pool == 0) return fail(BSK_EINVAL, "no IC pool staged (bsk_set_ic_pool / bsk_sample_ic_pool)");
+    if (envs_per_member < 1) return fail(BSK_EINVAL, "bsk_reset_from_pool_shared: envs_per_member must be >= 1");
+    DeviceGuard guard(h->device);
+    if (h->stepped) { int rc = snapshot_stats(h); if (rc) return rc; }   // the last step's batch scalars, before its rewards are overwritten
+    HIP_TRY(bsk::launch_reset_from_pool_shared(h->d_state, h->stride, h->nf, h->d_pool, h->n_pool, d_mask, h->n, h->d_cnt, h->d_episodes,
+                                               h->env_base, (unsigned)envs_per_member, (const unsigned long long*)d_epoch, reset_out(h),
+                                               h->stream));
+    h->charge_pos = (d_mask ? h->charge_pos : true) && h->pool_charge_pos;
+    { int rc = seal_stats(h); if (rc) return rc; }
+    return BSK_OK;       // asynchronous on the handle's stream: no host data, no copy, no synchronisation
+}
+
 int bsk_get_episode_device(bsk_handle* h, double** d_ep_return, double** d_term_return, int32_t** d_term_len, uint8_t** d_done,
                            double** d_obs_rowmajor) {
     if (!h) return fail(BSK_EINVAL, "handle is NULL");
@@ -1939,10 +1957,11 @@ int bsk_es_create(const bsk_policy_spec* spec, int n_members, const float* theta
 void bsk_es_destroy(bsk_es* es) {
     if (!es) return;
     DeviceGuard guard(es->device);
-    if (es->d_state || es->d_theta || es->d_w) (void)hipDeviceSynchronize();
+    if (es->d_state || es->d_theta || es->d_w || es->d_adam) (void)hipDeviceSynchronize();
     if (es->d_state) (void)hipFree(es->d_state);
     if (es->d_theta) (void)hipFree(es->d_theta);
     if (es->d_w) (void)hipFree(es->d_w);
+    if (es->d_adam) (void)hipFree(es->d_adam);
     delete es;
 }
 
@@ -1970,8 +1989,23 @@ int bsk_es_ask(bsk_es* es, bsk_population* pop, void* stream) {
 int bsk_es_tell(bsk_es* es, const double* d_fitness, void* stream) {
     if (!es || !d_fitness) return fail(BSK_EINVAL, "es/d_fitness is NULL");
     DeviceGuard guard(es->device);
-    const double c = es->lr / ((double)es->n_members * es->sigma);
     HIP_TRY(bsk::launch_es_rank(d_fitness, es->n_members, es->d_w, (hipStream_t)stream));
+    if (es->optimizer == BSK_ES_ADAM) {
+        const size_t np = (size_t)es->lay.n_params;
+        bsk::EsAdam ad;
+        ad.m = es->d_adam;
+        ad.v = es->d_adam + np;
+        ad.beta_pow = es->d_adam + 2 * np;
+        ad.beta1 = es->beta1; ad.beta2 = es->beta2;
+        ad.a1 = 1.0 - es->beta1; ad.a2 = 1.0 - es->beta2;
+        ad.eps = es->eps; ad.weight_decay = es->weight_decay;
+        ad.cg = 1.0 / ((double)es->n_members * es->sigma);
+        ad.lr = es->lr;
+        HIP_TRY(bsk::launch_es_tell_adam(es_args(es), es->lay.n_params, es->d_w, ad, (hipStream_t)stream));
+        HIP_TRY(bsk::launch_es_advance_adam(es->d_state, es->d_adam + 2 * np, es->beta1, es->beta2, (hipStream_t)stream));
+        return BSK_OK;
+    }
+    const double c = es->lr / ((double)es->n_members * es->sigma);
     HIP_TRY(bsk::launch_es_tell(es_args(es), es->lay.n_params, es->d_w, c, (hipStream_t)stream));
     HIP_TRY(bsk::launch_es_advance(es->d_state, (hipStream_t)stream));
     return BSK_OK;
@@ -1997,6 +2031,62 @@ int bsk_es_set_state(bsk_es* es, const double* theta, uint64_t generation) {
     HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old state)
     if (theta) HIP_COPY(hipMemcpy(es->d_theta, theta, (size_t)es->lay.n_params * sizeof(double), hipMemcpyHostToDevice));
     HIP_COPY(hipMemcpy(es->d_state + 1, &g, sizeof g, hipMemcpyHostToDevice));
+    return BSK_OK;
+}
+
+int bsk_es_generation_device(bsk_es* es, const uint64_t** d_generation) {
+    if (!es || !d_generation) return fail(BSK_EINVAL, "es/d_generation is NULL");
+    *d_generation = (const uint64_t*)(es->d_state + 1);
+    return BSK_OK;
+}
+
+int bsk_es_set_optimizer(bsk_es* es, int kind, double beta1, double beta2, double eps, double weight_decay) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    if (kind != BSK_ES_SGD && kind != BSK_ES_ADAM) return fail(BSK_EINVAL, "bsk_es_set_optimizer: kind must be BSK_ES_SGD or BSK_ES_ADAM");
+    if (kind == BSK_ES_ADAM) {
+        if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+            return fail(BSK_EINVAL, "bsk_es_set_optimizer: beta1 and beta2 must be in [0, 1)");
+        if (!std::isfinite(eps) || !(eps > 0.0)) return fail(BSK_EINVAL, "bsk_es_set_optimizer: eps must be finite and positive");
+        if (!std::isfinite(weight_decay) || weight_decay < 0.0)
+            return fail(BSK_EINVAL, "bsk_es_set_optimizer: weight_decay must be finite and not negative");
+    }
+    DeviceGuard guard(es->device);
+    HIP_SYNC(hipDeviceSynchronize());                     // (queued tells still use the old rule and the old moments)
+    if (kind == BSK_ES_SGD) {
+        es->optimizer = BSK_ES_SGD;
+        return BSK_OK;
+    }
+    const size_t np = (size_t)es->lay.n_params;
+    if (!es->d_adam) HIP_TRY(hipMalloc(&es->d_adam, (2 * np + 2) * sizeof(double)));
+    const double one[2] = {1.0, 1.0};
+    HIP_TRY(hipMemset(es->d_adam, 0, 2 * np * sizeof(double)));
+    HIP_COPY(hipMemcpy(es->d_adam + 2 * np, one, sizeof one, hipMemcpyHostToDevice));
+    es->optimizer = BSK_ES_ADAM;
+    es->beta1 = beta1; es->beta2 = beta2; es->eps = eps; es->weight_decay = weight_decay;
+    return BSK_OK;
+}
+
+int bsk_es_get_moments(bsk_es* es, double* m, double* v, double* beta_pow) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    if (es->optimizer != BSK_ES_ADAM) return fail(BSK_EINVAL, "bsk_es_get_moments: the optimiser is BSK_ES_SGD, it has no moments");
+    DeviceGuard guard(es->device);
+    const size_t np = (size_t)es->lay.n_params;
+    HIP_SYNC(hipDeviceSynchronize());
+    if (m) HIP_COPY(hipMemcpy(m, es->d_adam, np * sizeof(double), hipMemcpyDeviceToHost));
+    if (v) HIP_COPY(hipMemcpy(v, es->d_adam + np, np * sizeof(double), hipMemcpyDeviceToHost));
+    if (beta_pow) HIP_COPY(hipMemcpy(beta_pow, es->d_adam + 2 * np, 2 * sizeof(double), hipMemcpyDeviceToHost));
+    return BSK_OK;
+}
+
+int bsk_es_set_moments(bsk_es* es, const double* m, const double* v, const double* beta_pow) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    if (es->optimizer != BSK_ES_ADAM) return fail(BSK_EINVAL, "bsk_es_set_moments: the optimiser is BSK_ES_SGD, it has no moments");
+    DeviceGuard guard(es->device);
+    const size_t np = (size_t)es->lay.n_params;
+    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old moments)
+    if (m) HIP_COPY(hipMemcpy(es->d_adam, m, np * sizeof(double), hipMemcpyHostToDevice));
+    if (v) HIP_COPY(hipMemcpy(es->d_adam + np, v, np * sizeof(double), hipMemcpyHostToDevice));
+    if (beta_pow) HIP_COPY(hipMemcpy(es->d_adam + 2 * np, beta_pow, 2 * sizeof(double), hipMemcpyHostToDevice));
     return BSK_OK;
 }
 

@@ -3,10 +3,11 @@
 //   es_ask_kernel      theta +- sigma * z straight into a population's device layout, z regenerated from a counter
 //   es_rank_kernel     one thread per member: how many members beat it -> the utility difference of every pair
 //   es_tell_kernel     one wave per parameter: the utilities contracted with the regenerated noise in a fixed order
-//   es_advance_kernel  the generation counter += 1
+//   es_tell_adam_kernel     the same contraction driven through Adam with an L2 penalty
+//   es_advance_kernel  the generation counter += 1 (es_advance_adam_kernel: and Adam's two running powers)
 // The noise is never stored: z(g, i, j) is one Philox4x32-10 call and an inverse normal CDF made of f64 + - * /, sqrt and integer
 // operations.  Compiled with -ffp-contract=off (Makefile), as bsk_population.hip is: every operation rounds on its own, and numpy
-// repeats all of it bit for bit (policy.py: es_noise_ref, es_ask_ref, es_tell_ref).
+// repeats all of it bit for bit (policy.py: es_noise_ref, es_ask_ref, es_tell_ref, es_tell_adam_ref).
 #include "bsk_es.hpp"
 
 #include "bsk_philox.hpp"
@@ -146,24 +147,58 @@ __device__ __forceinline__ double es_tree(double s, int lane) {
     return s;
 }
 
-// One wave per parameter j >= frozen.  Lane l adds w_i * z(g, i, j) over its pairs i = l, l + 64, ... ascending, starting FROM the
-// first (+0.0 with no pair at all); the lanes join in the tree; lane 0 moves theta_j.  No atomics, no dependence on the launch shape.
+// s[0] of parameter j (include/bskgpu.h, tell step 3), valid in lane 0: lane l adds w_i * z(g, i, j) over its pairs i = l, l + 64,
+// ... ascending, starting FROM the first (+0.0 with no pair at all); the lanes join in the tree.  ONE text behind both update
+// kernels, so that the order of the sum cannot diverge between them.  It is a macro and not a device function because
+// es_tell_kernel keeps the instruction stream it had: behind a call - the structure by reference, its fields by value, the whole
+// wave as a template - the same loop came out with another schedule of the Philox key's scalar instructions, every time.
+#define ES_PAIR_SUM(es, w, j, lane, s)                                                \
+    const unsigned long long seed = es.state[0], g = es.state[1];                     \
+    double s = 0.0;                                                                   \
+    for (int i = lane; i < es.pairs; i += 64) {                                       \
+        const double t = w[i] * es_noise(seed, g, (unsigned)i, (unsigned)j);          \
+        s = i == lane ? t : s + t;                                                    \
+    }                                                                                 \
+    s = es_tree(s, lane)
+
+// One wave per parameter j >= frozen: the sum above, then lane 0 moves theta_j.  No atomics, no dependence on the launch shape.
 __global__ __launch_bounds__(256) void es_tell_kernel(const EsArgs es, int n_params, const double* __restrict__ w, double c) {
 #pragma clang fp contract(off)
     const int j = es.frozen + (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));     // (wave-uniform)
     const int lane = (int)(threadIdx.x & 63u);
     if (j >= n_params) return;
-    const unsigned long long seed = es.state[0], g = es.state[1];
-    double s = 0.0;
-    for (int i = lane; i < es.pairs; i += 64) {
-        const double t = w[i] * es_noise(seed, g, (unsigned)i, (unsigned)j);
-        s = i == lane ? t : s + t;
-    }
-    s = es_tree(s, lane);
+    ES_PAIR_SUM(es, w, j, lane, s);
     if (lane == 0) es.theta[j] = es.theta[j] + c * s;
 }
 
+// The same wave per parameter with Adam and an L2 penalty behind the sum (include/bskgpu.h: every operation on its own, plain /
+// and sqrt).  beta_pow is read here and moved on by es_advance_adam_kernel behind this launch, never by this kernel.
+__global__ __launch_bounds__(256) void es_tell_adam_kernel(const EsArgs es, int n_params, const double* __restrict__ w, const EsAdam ad) {
+#pragma clang fp contract(off)
+    const int j = es.frozen + (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));     // (wave-uniform)
+    const int lane = (int)(threadIdx.x & 63u);
+    if (j >= n_params) return;
+    ES_PAIR_SUM(es, w, j, lane, s);
+    if (lane == 0) {
+        const double p1 = ad.beta_pow[0] * ad.beta1, p2 = ad.beta_pow[1] * ad.beta2;
+        const double t = es.theta[j];
+        const double grad = ad.cg * s - ad.weight_decay * t;
+        const double m = ad.beta1 * ad.m[j] + ad.a1 * grad;
+        const double v = ad.beta2 * ad.v[j] + (ad.a2 * grad) * grad;
+        ad.m[j] = m;
+        ad.v[j] = v;
+        es.theta[j] = t + (ad.lr * (m / (1.0 - p1))) / (sqrt(v / (1.0 - p2)) + ad.eps);
+    }
+}
+
 __global__ void es_advance_kernel(unsigned long long* state) { state[1] += 1ull; }
+
+__global__ void es_advance_adam_kernel(unsigned long long* state, double* beta_pow, double beta1, double beta2) {
+#pragma clang fp contract(off)
+    beta_pow[0] = beta_pow[0] * beta1;
+    beta_pow[1] = beta_pow[1] * beta2;
+    state[1] += 1ull;
+}
 
 hipError_t launch_es_ask(const PolicyLayout& lay, const EsArgs& es, float* d_params, hipStream_t s) {
     const PolicyPackMap map = policy_pack_map(lay);
@@ -180,6 +215,18 @@ hipError_t launch_es_tell(const EsArgs& es, int n_params, const double* w, doubl
     const int moving = n_params - es.frozen;
     if (moving < 1) return hipSuccess;
     hipLaunchKernelGGL(es_tell_kernel, dim3((unsigned)((moving + 3) / 4)), dim3(256), 0, s, es, n_params, w, c);
+    return hipGetLastError();
+}
+
+hipError_t launch_es_tell_adam(const EsArgs& es, int n_params, const double* w, const EsAdam& ad, hipStream_t s) {
+    const int moving = n_params - es.frozen;
+    if (moving < 1) return hipSuccess;
+    hipLaunchKernelGGL(es_tell_adam_kernel, dim3((unsigned)((moving + 3) / 4)), dim3(256), 0, s, es, n_params, w, ad);
+    return hipGetLastError();
+}
+
+hipError_t launch_es_advance_adam(unsigned long long* state, double* beta_pow, double beta1, double beta2, hipStream_t s) {
+    hipLaunchKernelGGL(es_advance_adam_kernel, dim3(1), dim3(1), 0, s, state, beta_pow, beta1, beta2);
     return hipGetLastError();
 }
 

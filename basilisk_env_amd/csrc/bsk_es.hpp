@@ -15,6 +15,16 @@ struct EsArgs {
     int pairs;                         // n_members / 2
 };
 
+// bsk_es_set_optimizer(BSK_ES_ADAM): the moments, the running powers of beta1 / beta2 and the constants formed once on the host
+struct EsAdam {
+    double* m;                         // [n_params], first moment; frozen parameters keep 0
+    double* v;                         // [n_params], second moment
+    const double* beta_pow;            // {beta1^t, beta2^t} after t tells: device words, moved by launch_es_advance_adam
+    double beta1, beta2, a1, a2;       // a1 = 1 - beta1, a2 = 1 - beta2
+    double eps, weight_decay;
+    double cg, lr;                     // cg = 1 / ((double)P * sigma)
+};
+
 // The members of this generation into d_params ([2 * pairs][lay.n_device], a population's device layout): one launch, every
 // float written exactly once.
 hipError_t launch_es_ask(const PolicyLayout& lay, const EsArgs& es, float* d_params, hipStream_t s);
@@ -22,6 +32,10 @@ hipError_t launch_es_ask(const PolicyLayout& lay, const EsArgs& es, float* d_par
 hipError_t launch_es_rank(const double* fitness, int n_members, double* w, hipStream_t s);
 // theta_j = theta_j + c * sum_i w_i * z(g, i, j) for every j >= frozen, the sum in the fixed order of include/bskgpu.h
 hipError_t launch_es_tell(const EsArgs& es, int n_params, const double* w, double c, hipStream_t s);
+// the same sum through Adam: g = cg * s[0] - weight_decay * theta_j, the moments, the bias-corrected step (include/bskgpu.h)
+hipError_t launch_es_tell_adam(const EsArgs& es, int n_params, const double* w, const EsAdam& ad, hipStream_t s);
+// generation += 1 and beta_pow *= {beta1, beta2}, one thread, behind launch_es_tell_adam on the same stream
+hipError_t launch_es_advance_adam(unsigned long long* state, double* beta_pow, double beta1, double beta2, hipStream_t s);
 // generation += 1, one thread, behind a tell on the same stream (a replayed graph moves on to the next generation)
 hipError_t launch_es_advance(unsigned long long* state, hipStream_t s);
 

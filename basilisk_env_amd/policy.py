@@ -856,23 +856,86 @@ def es_tell_ref(theta, fitness, sigma, lr, frozen, seed, generation):
     j >= frozen lane l = 0 .. 63 sums w_i * z(g, i, j) over its pairs i = l, l + 64, ... ascending from the first (+0.0 with no
     pair), the lanes join as the fitness tree does (stride 32 ... 1), and theta_j = theta_j + lr / (P * sigma) * s[0]."""
     theta = np.array(theta, dtype=np.float64).reshape(-1)
+    frozen = int(frozen)
+    s0, P = _es_pair_sum(fitness, theta.size, seed, generation)
+    with np.errstate(invalid="ignore", over="ignore"):
+        c = float(lr) / (float(P) * float(sigma))
+        theta[frozen:] = theta[frozen:] + c * s0[frozen:]
+    return theta
+
+
+def _es_pair_sum(fitness, n_params, seed, generation):
+    """Steps 1 - 3 of ``bsk_es_tell`` up to s[0] -> (float64 (n_params,), P): the one sum behind ``es_tell_ref`` and
+    ``es_tell_adam_ref``, as ``ES_PAIR_SUM`` (csrc/bsk_es.hip) is behind the two update kernels."""
     u = centred_ranks(fitness)
-    P, frozen = u.size, int(frozen)
+    P = u.size
     if P < 2 or P % 2:
         raise ValueError("expected an even number of fitness values, at least 2")
     w = u[0::2] - u[1::2]
     with np.errstate(invalid="ignore", over="ignore"):
-        terms = w[:, None] * es_noise_ref(seed, generation, P // 2, theta.size)
-        s = np.zeros((64, theta.size), np.float64)
+        terms = w[:, None] * es_noise_ref(seed, generation, P // 2, n_params)
+        s = np.zeros((64, int(n_params)), np.float64)
         s[:min(64, P // 2)] = terms[:64]
         for at in range(64, P // 2, 64):
             chunk = terms[at:at + 64]
             s[:len(chunk)] = s[:len(chunk)] + chunk
         for stride in (32, 16, 8, 4, 2, 1):
             s[:stride] = s[:stride] + s[stride:2 * stride]
-        c = float(lr) / (float(P) * float(sigma))
-        theta[frozen:] = theta[frozen:] + c * s[0, frozen:]
-    return theta
+    return s[0].copy(), P
+
+
+def check_adam(beta1, beta2, eps, weight_decay):
+    """The argument rules of ``bsk_es_set_optimizer(BSK_ES_ADAM, ...)`` -> the four as floats; ValueError where it returns
+    BSK_EINVAL.  Needs no device."""
+    beta1, beta2, eps, weight_decay = float(beta1), float(beta2), float(eps), float(weight_decay)
+    if not (0.0 <= beta1 < 1.0) or not (0.0 <= beta2 < 1.0):
+        raise ValueError("beta1 and beta2 must be in [0, 1)")
+    if not np.isfinite(eps) or not (eps > 0.0):
+        raise ValueError("eps must be finite and positive")
+    if not np.isfinite(weight_decay) or weight_decay < 0.0:
+        raise ValueError("weight_decay must be finite and not negative")
+    return beta1, beta2, eps, weight_decay
+
+
+def es_tell_adam_ref(theta, m, v, beta_pow, fitness, sigma, lr, frozen, seed, generation, beta1, beta2, eps, weight_decay):
+    """What ``bsk_es_tell`` leaves under ``BSK_ES_ADAM`` -> (theta, m, v, beta_pow), float64: s[0] of ``es_tell_ref``'s sum, then
+    per parameter j >= frozen, every operation rounded on its own (include/bskgpu.h), cg = 1 / (P * sigma):
+    g = cg * s[0] - weight_decay * theta_j; m_j = beta1 * m_j + (1 - beta1) * g; v_j = beta2 * v_j + ((1 - beta2) * g) * g;
+    theta_j = theta_j + (lr * (m_j / (1 - p1))) / (sqrt(v_j / (1 - p2)) + eps) with p = beta_pow * beta, the beta_pow returned."""
+    theta = np.array(theta, dtype=np.float64).reshape(-1)
+    m, v = np.array(m, dtype=np.float64).reshape(-1), np.array(v, dtype=np.float64).reshape(-1)
+    bp = np.array(beta_pow, dtype=np.float64).reshape(2)
+    frozen = int(frozen)
+    if m.size != theta.size or v.size != theta.size:
+        raise ValueError("m and v have theta's size")
+    b1, b2, eps, wd = (np.float64(x) for x in check_adam(beta1, beta2, eps, weight_decay))
+    s0, P = _es_pair_sum(fitness, theta.size, seed, generation)
+    lr = np.float64(lr)
+    cg = np.float64(1.0) / (np.float64(P) * np.float64(sigma))
+    a1, a2 = np.float64(1.0) - b1, np.float64(1.0) - b2
+    p1, p2 = bp[0] * b1, bp[1] * b2
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        t = theta[frozen:]
+        g = cg * s0[frozen:] - wd * t
+        mj = b1 * m[frozen:] + a1 * g
+        vj = b2 * v[frozen:] + (a2 * g) * g
+        m[frozen:], v[frozen:] = mj, vj
+        theta[frozen:] = t + (lr * (mj / (np.float64(1.0) - p1))) / (np.sqrt(vj / (np.float64(1.0) - p2)) + eps)
+    return theta, m, v, np.array([p1, p2], np.float64)
+
+
+def shared_slot_ref(n, envs_per_member, epoch, n_pool, env_base=0):
+    """The IC-pool slots ``bsk_reset_from_pool_shared`` restarts envs 0 .. n - 1 from -> uint32 (n,): g = (env_base + env) mod 2^32,
+    q = g mod envs_per_member, e = epoch mod 2^32, slot = (q * 2654435761 + e * 40503 + 12345) mod 2^32 mod n_pool.  Envs with equal
+    q share a slot.  Needs no device."""
+    n, E, n_pool = int(n), int(envs_per_member), int(n_pool)
+    if E < 1 or n_pool < 1:
+        raise ValueError("envs_per_member and n_pool must be >= 1")
+    mask = np.uint64(0xFFFFFFFF)
+    g = (np.arange(n, dtype=np.uint64) + np.uint64(int(env_base) & 0xFFFFFFFF)) & mask
+    q = g % np.uint64(E)
+    e = np.uint64(int(epoch) & 0xFFFFFFFF)
+    return (((q * np.uint64(2654435761) + e * np.uint64(40503) + np.uint64(12345)) & mask) % np.uint64(n_pool)).astype(np.uint32)
 
 
 class DeviceEvolutionStrategy(object):
@@ -880,9 +943,17 @@ class DeviceEvolutionStrategy(object):
     ``population`` = P members straight into a ``PolicyPopulation``'s device layout, ``tell`` reads the P float64 fitness values
     a rollout left in device memory; both are enqueue-only and capturable, and the noise is regenerated from (seed, generation,
     pair, parameter) instead of stored.  ``theta``: the float32 parameter block the search starts from (None: zeros).  Equal bit
-    for bit to ``es_ask_ref`` / ``es_tell_ref``.  Not thread-safe, one stream at a time."""
+    for bit to ``es_ask_ref`` / ``es_tell_ref``.  ``optimizer="adam"`` drives the same estimate through Adam with the L2 penalty
+    ``weight_decay`` (``bsk_es_set_optimizer``; ``es_tell_adam_ref``); ``"sgd"``, the default, ignores the four Adam arguments.
+    Not thread-safe, one stream at a time."""
 
-    def __init__(self, spec, theta, population, sigma=0.1, lr=0.05, seed=0, frozen=10, device=0):
+    def __init__(self, spec, theta, population, sigma=0.1, lr=0.05, seed=0, frozen=10, device=0, optimizer="sgd", beta1=0.9,
+                 beta2=0.999, eps=1e-8, weight_decay=0.0):
+        if optimizer not in ("sgd", "adam"):
+            raise ValueError("optimizer must be 'sgd' or 'adam', got %r" % (optimizer,))
+        if optimizer == "adam":
+            beta1, beta2, eps, weight_decay = check_adam(beta1, beta2, eps, weight_decay)
+        self.optimizer, self.adam = optimizer, (beta1, beta2, eps, weight_decay)
         self.spec = _as_spec(spec)
         self.n_params = n_params(self.spec)
         self.population, self.sigma, self.lr, self.frozen = int(population), float(sigma), float(lr), int(frozen)
@@ -899,6 +970,8 @@ class DeviceEvolutionStrategy(object):
                                       self.frozen, self.seed, self.device, C.byref(h)))
         self._p = h
         self._fitness = self._source = None
+        if optimizer == "adam":
+            self.set_optimizer("adam", beta1, beta2, eps, weight_decay)
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
@@ -947,6 +1020,41 @@ class DeviceEvolutionStrategy(object):
                 raise ValueError("expected %d parameters, got %d" % (self.n_params, t.size))
         check(self._lib.bsk_es_set_state(self._handle(), None if t is None else t.ctypes.data, int(generation)))
 
+    def generation_ptr(self):
+        """The generation counter as a DEVICE uint64 word, valid until ``close``: the epoch of ``reset_from_pool_shared``."""
+        p = C.c_void_p()
+        check(self._lib.bsk_es_generation_device(self._handle(), C.byref(p)))
+        return p.value
+
+    def set_optimizer(self, optimizer, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0):
+        """``"adam"``: Adam with an L2 penalty from zero moments (every selection zeroes them); ``"sgd"``: the plain step.  Theta and
+        the generation stay; synchronises."""
+        if optimizer not in ("sgd", "adam"):
+            raise ValueError("optimizer must be 'sgd' or 'adam', got %r" % (optimizer,))
+        if optimizer == "adam":
+            beta1, beta2, eps, weight_decay = check_adam(beta1, beta2, eps, weight_decay)
+        check(self._lib.bsk_es_set_optimizer(self._handle(), _lib.ES_ADAM if optimizer == "adam" else _lib.ES_SGD, float(beta1), float(beta2),
+                                             float(eps), float(weight_decay)))
+        self.optimizer, self.adam = optimizer, (float(beta1), float(beta2), float(eps), float(weight_decay))
+
+    @property
+    def moments(self):
+        """Adam's (m, v, beta_pow): float64 (n_params,), (n_params,), (2,); synchronises.  An error while the optimiser is SGD."""
+        m, v, bp = np.empty(self.n_params, np.float64), np.empty(self.n_params, np.float64), np.empty(2, np.float64)
+        check(self._lib.bsk_es_get_moments(self._handle(), m.ctypes.data, v.ctypes.data, bp.ctypes.data))
+        return m, v, bp
+
+    def set_moments(self, m=None, v=None, beta_pow=None):
+        """New Adam moments (float64 (n_params,) each) and running powers (float64 (2,)); None keeps; synchronises."""
+        arrs = []
+        for a, size in ((m, self.n_params), (v, self.n_params), (beta_pow, 2)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+                if a.size != size:
+                    raise ValueError("expected %d values, got %d" % (size, a.size))
+            arrs.append(a)
+        check(self._lib.bsk_es_set_moments(self._handle(), *[None if a is None else a.ctypes.data for a in arrs]))
+
     # ------------------------------------------------------------------ the search
     def ask(self, pop, stream=0):
         """This generation's members into every member of ``pop`` (a ``PolicyPopulation`` of the same spec and size): one launch
@@ -973,15 +1081,20 @@ class DeviceEvolutionStrategy(object):
             self._fitness = _hip.DeviceBuffer(8 * self.population, self.device)
         return self._fitness
 
-    def run_generation(self, prop, pop, n_steps, substeps, mode="greedy", gamma=1.0, reset=True):
+    def run_generation(self, prop, pop, n_steps, substeps, mode="greedy", gamma=1.0, reset=True, shared_episodes=False):
         """One generation on the propagator's stream: every env restarted from the propagator's IC pool (``reset``; needs an
         auto-reset pool), ``ask``, ``pop.rollout_device`` with the fitness into ``fitness_buffer()``, ``tell``.  Nothing else is
         issued - no copy, no synchronisation - so after one warming call (it allocates the buffer and the population's scratch
-        rows) a call can be captured into a graph and replayed generation after generation."""
+        rows) a call can be captured into a graph and replayed generation after generation.  ``shared_episodes``: the reset is
+        ``reset_from_pool_shared`` with E = n_envs // population and the generation word as the epoch, so that all members of a
+        generation are scored on the same E initial conditions and every generation draws new ones; nothing else in the stream
+        changes.  That is exact for ``greedy``: sample mode still draws its uniform per global env index."""
         prop = getattr(prop, "propagator", prop)
         fit = self.fitness_buffer()
         stream = prop.stream_ptr()
-        if reset:
+        if reset and shared_episodes:
+            prop.reset_from_pool_shared(prop.n_envs // self.population, self.generation_ptr())
+        elif reset:
             prop.reset_from_pool_device(None)
         self.ask(pop, stream)
         pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr)

@@ -395,6 +395,15 @@ class BatchedPropagator(object):
         no host data, no copy, no synchronisation."""
         check(self._lib.bsk_reset_from_pool_device(self._handle(), C.c_void_p(int(d_mask_ptr)) if d_mask_ptr else None))
 
+    def reset_from_pool_shared(self, envs_per_member, d_epoch_ptr=None, d_mask_ptr=None):
+        """``reset_from_pool_device`` with the slot rule the members of a population share (``bsk_reset_from_pool_shared``;
+        ``policy.shared_slot_ref``): env ``j`` restarts from the slot of ``q = (env_base + j) mod envs_per_member`` under the epoch
+        in the DEVICE word ``d_epoch_ptr`` (uint64, its low 32 bits; None: 0), so every member of a generation meets the same
+        episodes.  Enqueued on the handle's stream, no copy, no synchronisation.  Exact for ``greedy``; sample mode still draws its
+        uniform per global env index."""
+        check(self._lib.bsk_reset_from_pool_shared(self._handle(), int(envs_per_member), C.c_void_p(int(d_epoch_ptr)) if d_epoch_ptr else None,
+                                                   C.c_void_p(int(d_mask_ptr)) if d_mask_ptr else None))
+
     def batch_stats_device(self):
         """-> device pointer of f64[2] = {sum of rewards, number of done envs} of the last step, produced on the handle's
         stream without synchronising (the operand of a sharded batch's one all-reduce)."""

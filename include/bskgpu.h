@@ -329,6 +329,22 @@ int bsk_sample_ic_pool(bsk_handle* h, int n_pool, uint64_t seed);
 int bsk_reset_from_pool(bsk_handle* h, const uint8_t* mask);
 /* Same with the mask (or NULL) in DEVICE memory, asynchronous on the handle's stream: no host data, no copy, no synchronisation. */
 int bsk_reset_from_pool_device(bsk_handle* h, const uint8_t* d_mask);
+/* bsk_reset_from_pool_device with a slot rule that the members of a population SHARE (bsk_population_rollout: member m drives envs
+ * [m E, (m + 1) E), E = envs_per_member), so that every member of a generation is scored on the same E episodes:
+ *     g = (uint32)(env_base + env)           the 32-bit global index of the rule above
+ *     q = g mod envs_per_member
+ *     e = the low 32 bits of *d_epoch, a DEVICE word the kernel reads when it runs (NULL: e = 0)
+ *     slot = (q * 2654435761 + e * 40503 + 12345) mod 2^32 mod n_pool
+ * Envs with equal q restart from the same slot, and a new epoch draws anew: with the optimiser's generation word
+ * (bsk_es_generation_device) as the epoch a replayed graph moves on by itself.  Everything else is bsk_reset_from_pool_device:
+ * counters zeroed, the env's episode count + 1 (auto-resets inside a rollout go on with the per-env rule above), the new episode's
+ * first observation written, reward / reason / done / ep_return zeroed, the batch-scalar snapshot before and its seal after; d_mask
+ * (DEVICE memory, or NULL for every env) as there.  Enqueue-only on the handle's stream: no copy, no synchronisation; capturable.
+ * envs_per_member is any value >= 1 - no multiple of 64, and it need not divide n_envs.  An episode is a deterministic function of
+ * its initial condition and the actions, so identical members then score identically under BSK_POLICY_GREEDY; BSK_POLICY_SAMPLE
+ * still draws its uniform per GLOBAL env index, so sampled actions differ between members on the same initial condition.
+ * BSK_EINVAL before anything is launched: a NULL handle, no pool staged, envs_per_member < 1. */
+int bsk_reset_from_pool_shared(bsk_handle* h, int envs_per_member, const uint64_t* d_epoch, const uint8_t* d_mask);
 /* Host copy of the staged pool, SoA [n_fields][n_pool] (n_pool as staged; the caller sizes the buffer):
  * lets the host replay a device-side reset (reset_init, leoPowerAttitudeEnvironment.py:202-216). */
 int bsk_get_ic_pool(bsk_handle* h, double* ic_pool);
@@ -622,6 +638,37 @@ int bsk_es_tell(bsk_es* es, const double* d_fitness, void* stream);
 int bsk_es_get_state(bsk_es* es, double* theta, uint64_t* generation);
 /* A new theta (host pointer, f64[n_params]; NULL: keep) and generation counter.  Synchronises the device. */
 int bsk_es_set_state(bsk_es* es, const double* theta, uint64_t generation);
+
+/* The generation counter as a DEVICE word (read-only for the caller; valid for the optimiser's lifetime): the epoch of
+ * bsk_reset_from_pool_shared.  No launch, no copy, no synchronisation.  BSK_EINVAL for NULL pointers. */
+int bsk_es_generation_device(bsk_es* es, const uint64_t** d_generation);
+
+/* The update rule of bsk_es_tell.  BSK_ES_SGD (the default) is step 3 above.  BSK_ES_ADAM drives the same estimate through Adam
+ * (Kingma & Ba 2015) with an L2 penalty, as the reference implementation of Salimans et al. 2017 does.  Every operation is rounded
+ * on its own in f64, no FMA; / and sqrt are the plain correctly rounded ones, as in the inverse normal CDF above
+ * (basilisk_env_amd/policy.py: es_tell_adam_ref repeats it bit for bit).  Steps 1 - 3 are unchanged up to s[0] (the same ranking
+ * kernel, the same lane-strided sum and tree: ONE device function behind both update kernels).  State: m, v f64[n_params] and two
+ * device words beta_pow = {beta1^t, beta2^t} after t tells.  Constants formed once on the host:
+ * cg = 1.0 / ((double)P * sigma), a1 = 1.0 - beta1, a2 = 1.0 - beta2.  For every j >= frozen:
+ *     p1 = beta_pow[0] * beta1          p2 = beta_pow[1] * beta2
+ *     g  = cg * s[0] - weight_decay * theta_j
+ *     m_j = beta1 * m_j + a1 * g
+ *     v_j = beta2 * v_j + (a2 * g) * g
+ *     theta_j = theta_j + (lr * (m_j / (1.0 - p1))) / (sqrt(v_j / (1.0 - p2)) + eps)
+ * (greater fitness is better: g is an ascent direction and the penalty pulls theta towards zero).  Behind the update the one-thread
+ * launch of step 4 stores beta_pow[0] = beta_pow[0] * beta1, beta_pow[1] = beta_pow[1] * beta2 and generation + 1.  tell stays three
+ * launches, no copy, no synchronisation, capturable.  Frozen parameters have no moments that move: their m and v stay 0.
+ * bsk_es_set_optimizer synchronises the device; on the first selection of Adam it allocates m, v and beta_pow, on EVERY selection of
+ * Adam it zeroes m and v and sets beta_pow = {1.0, 1.0}; theta and the generation are left alone.  BSK_ES_SGD ignores the other
+ * arguments and restores step 3 (the moments are kept allocated, unused).  BSK_EINVAL before anything is launched: a NULL
+ * optimiser, an unknown kind; for Adam beta1 or beta2 outside [0, 1), eps not finite or <= 0, weight_decay not finite or < 0. */
+#define BSK_ES_SGD 0
+#define BSK_ES_ADAM 1
+int bsk_es_set_optimizer(bsk_es* es, int kind, double beta1, double beta2, double eps, double weight_decay);
+/* The moments to / from host memory: m, v f64[n_params], beta_pow f64[2]; each may be NULL (get: not asked for; set: keep).
+ * Synchronise the device.  BSK_EINVAL for a NULL optimiser and while the optimiser is BSK_ES_SGD. */
+int bsk_es_get_moments(bsk_es* es, double* m, double* v, double* beta_pow);
+int bsk_es_set_moments(bsk_es* es, const double* m, const double* v, const double* beta_pow);
 
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the

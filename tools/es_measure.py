@@ -9,12 +9,16 @@
         device  `DeviceEvolutionStrategy.run_generation`
         graph   the same call captured once into a HIP graph and replayed
         rollout reset from the pool and `rollout_device` alone: what the device loop is expected to approach
-  python tools/es_measure.py kernel
-      per P one warming and three measured generations of `run_generation`.  Run it under the profiler in a run of its own:
+        adam    `run_generation` of an optimiser created with optimizer="adam"
+        shared  `run_generation(..., shared_episodes=True)`: the reset that gives all members the same episodes
+  python tools/es_measure.py kernel [adam]
+      per P one warming and three measured generations of `run_generation` (`adam`: of an optimizer="adam" optimiser on shared
+      episodes).  Run it under the profiler in a run of its own:
       rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o es -- python tools/es_measure.py kernel
   python tools/es_measure.py stats DIR/.../es_kernel_trace.csv
-      per measured generation of that run the times of es_ask_kernel, es_rank_kernel and es_tell_kernel and the sum over every
-      other kernel of the generation (the generations are recognised by the es_advance_kernel that ends each)
+      per measured generation of that run the times of es_ask_kernel, es_rank_kernel and es_tell_kernel (or es_tell_adam_kernel)
+      and the sum over every other kernel of the generation (the generations are recognised by the es_advance_kernel or
+      es_advance_adam_kernel that ends each)
 """
 import csv
 import os
@@ -54,6 +58,8 @@ def loop():
             host = P.EvolutionStrategy(theta, m, sigma=0.1, lr=0.05, seed=1)
             dev = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
             rep = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
+            adam = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1, optimizer="adam")
+            shared = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
             fit = torch.zeros(m, dtype=torch.float64, device="cuda")
 
             def host_gen(steps, pop=pop, host=host):
@@ -68,6 +74,12 @@ def loop():
                 prop.reset_from_pool_device(None)
                 pop.rollout_device(prop, steps, 1, "greedy", GAMMA, d_fitness=fit.data_ptr())
 
+            def adam_gen(steps, pop=pop, adam=adam):
+                adam.run_generation(prop, pop, steps, 1, "greedy", GAMMA)
+
+            def shared_gen(steps, pop=pop, shared=shared):
+                shared.run_generation(prop, pop, steps, 1, "greedy", GAMMA, shared_episodes=True)
+
             rep.run_generation(prop, pop, WARM_T, 1, "greedy", GAMMA)
             prop.sync()
             graph = torch.cuda.CUDAGraph()
@@ -79,7 +91,7 @@ def loop():
                     graph.replay()
 
             variants += [("host   P = %d" % m, host_gen), ("device P = %d" % m, device_gen), ("graph  P = %d" % m, graph_gen),
-                         ("rollout P = %d" % m, rollout_gen)]
+                         ("rollout P = %d" % m, rollout_gen), ("adam   P = %d" % m, adam_gen), ("shared P = %d" % m, shared_gen)]
         res = {name: [] for name, _ in variants}
         for _ in range(ROUNDS):
             for name, run in variants:
@@ -94,15 +106,15 @@ def loop():
     env.close()
 
 
-def kernel():
+def kernel(adam=False):
     torch, P, side, env, prop, spec, theta = _setup()
     with torch.cuda.stream(side):
         for m in MEMBERS:
             pop = P.PolicyPopulation(spec, n_members=m)
-            dev = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
-            dev.run_generation(prop, pop, WARM_T, 1, "greedy", GAMMA)
+            dev = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1, optimizer="adam" if adam else "sgd")
+            dev.run_generation(prop, pop, WARM_T, 1, "greedy", GAMMA, shared_episodes=adam)
             for _ in range(ROUNDS):
-                dev.run_generation(prop, pop, T, 1, "greedy", GAMMA)
+                dev.run_generation(prop, pop, T, 1, "greedy", GAMMA, shared_episodes=adam)
             prop.sync()
     print("per P in %r: one warming generation of %d steps, then %d of %d steps" % (MEMBERS, WARM_T, ROUNDS, T))
     env.close()
@@ -116,7 +128,7 @@ def stats(path):
     rows.sort()
     gens, cur, seen = [], {}, False
     for _, d, name in rows:
-        key = next((k for k in ("es_ask_kernel", "es_rank_kernel", "es_tell_kernel", "es_advance_kernel") if k in name), "rest")
+        key = next((k for k in ("es_ask_kernel", "es_rank_kernel", "es_tell_kernel", "es_advance_kernel") if k in name.replace("_adam", "")), "rest")
         seen = seen or key == "es_ask_kernel"
         if not seen:
             continue                           # (the set-up's launches, before the first generation)
@@ -127,6 +139,7 @@ def stats(path):
     assert len(gens) == len(MEMBERS) * (1 + ROUNDS), len(gens)
     for b, m in enumerate(MEMBERS):
         for g in gens[b * (1 + ROUNDS) + 1:(b + 1) * (1 + ROUNDS)]:
+            # (tell: es_tell_kernel, or es_tell_adam_kernel in a `kernel adam` run)
             print("P = %-5d ask %8.1f us, rank %7.1f us, tell %8.1f us, every other kernel of the generation %9.1f us" %
                   (m, g["es_ask_kernel"] / 1e3, g["es_rank_kernel"] / 1e3, g["es_tell_kernel"] / 1e3, g["rest"] / 1e3))
 
@@ -137,7 +150,7 @@ if __name__ == "__main__":
     if what == "loop":
         loop()
     elif what == "kernel":
-        kernel()
+        kernel(adam=len(sys.argv) > 2 and sys.argv[2] == "adam")
     elif what == "stats":
         stats(sys.argv[2])
     else:
