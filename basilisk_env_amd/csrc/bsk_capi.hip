@@ -1,27 +1,18 @@
 // bsk_capi.hip — C-ABI of libbskgpu.so (see include/bskgpu.h for the contract and the reference
-// interfaces each entry point replaces).  Host side only: handle management, HBM allocation,
+// interfaces each entry point replaces): the environment handle.  Host side only: handle management, HBM allocation,
 // uploads/downloads, launch geometry.  No CPU compute path exists here by design: without a
-// gfx950 device bsk_create fails with BSK_ENODEV.
-#include <hip/hip_runtime.h>
-
+// gfx950 device bsk_create fails with BSK_ENODEV.  (bsk_config.hip: the configuration arithmetic; bsk_capi_policy.hip: policy,
+// population and evolution strategy; bsk_capi.hpp: what the three share.)
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
-#include <string>
-#include <vector>
 
-#include "../../include/bskgpu.h"
-#include "bsk_aux.hpp"
-#include "bsk_es.hpp"
-#include "bsk_launch.hpp"
-#include "bsk_policy.hpp"
-#include "bsk_population.hpp"
+#include "bsk_capi.hpp"
 #include "bsk_rollout.hpp"
 
-namespace {
+namespace bsk { namespace capi __attribute__((visibility("hidden"))) {
 
 thread_local std::string g_err;
 
@@ -30,535 +21,26 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return fail(e_ == hipErrorOutOfMemory ? BSK_ENOMEM : BSK_EHIP,                              \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                             \
-    } while (0)
-
-// how many copies / stream synchronisations this library has issued (bsk_debug_counters: tests assert that the
-// device-resident entry points issue none)
 std::atomic<long long> g_n_copies{0}, g_n_syncs{0};
-#define HIP_COPY(expr) do { g_n_copies.fetch_add(1, std::memory_order_relaxed); HIP_TRY(expr); } while (0)
-#define HIP_SYNC(expr) do { g_n_syncs.fetch_add(1, std::memory_order_relaxed); HIP_TRY(expr); } while (0)
 
-bool inv3(const double* m, double* o) {
-    double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
-    double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
-    if (!(std::fabs(det) > 0.0)) return false;
-    double id = 1.0 / det;
-    o[0] = c00 * id; o[1] = (m[2] * m[7] - m[1] * m[8]) * id; o[2] = (m[1] * m[5] - m[2] * m[4]) * id;
-    o[3] = c01 * id; o[4] = (m[0] * m[8] - m[2] * m[6]) * id; o[5] = (m[2] * m[3] - m[0] * m[5]) * id;
-    o[6] = c02 * id; o[7] = (m[1] * m[6] - m[0] * m[7]) * id; o[8] = (m[0] * m[4] - m[1] * m[3]) * id;
-    return true;
-}
-
-// Low-precision solar position (Astronomical Almanac), equatorial frame, metres, Earth-centred.
-// Stands in for the SPICE de430 lookup at reference leoPowerAttitudeSimulator.py:219-225.
-void sun_position(double jd, double out[3]) {
-    const double D2R = M_PI / 180.0, AU = 149597870700.0;
-    double n = jd - 2451545.0;
-    double L = std::fmod(280.460 + 0.9856474 * n, 360.0), g = std::fmod(357.528 + 0.9856003 * n, 360.0) * D2R;
-    double lam = (L + 1.915 * std::sin(g) + 0.020 * std::sin(2 * g)) * D2R;
-    double eps = (23.439 - 0.0000004 * n) * D2R;
-    double R = (1.00014 - 0.01671 * std::cos(g) - 0.00014 * std::cos(2 * g)) * AU;
-    out[0] = R * std::cos(lam);
-    out[1] = R * std::cos(eps) * std::sin(lam);
-    out[2] = R * std::sin(eps) * std::sin(lam);
-}
-
-// Fused Pines coefficient stream for gravity_sh (bsk_device.hpp), iteration order
-// M = 1..d+1, L = M..d+1, 8 doubles per step:
-//   [0] L == M: A[M][M] (diagonal constant);  L == M+1: A[M+1][M]/(u A[M][M]);  else n1[L][M]
-//   [1] n2[L][M] (L >= M+2)                      -- recursion A[L][M] = u n1 A[L-1][M] - n2 A[L-2][M]
-//   [2,3] M (Cbar, Sbar)[L][M]                   -- a1 / a2 sums            (L <= d)
-//   [4,5] nq1[L][M-1] (Cbar, Sbar)[L][M-1]       -- a3 sum                  (L <= d)
-//   [6,7] nq2[L-1][M-1] (Cbar, Sbar)[L-1][M-1]   -- a4 sum                  (L >= 2)
-// Constants as Basilisk's gravityEffector documents them (SURVEY.md §8 note N1).
-void build_sh_table(int d, const double* cbar, const double* sbar, std::vector<double>& tab) {
-    auto K = [](int i) { return i == 0 ? 1.0 : 2.0; };
-    auto idx = [](int l, int m) { return l * (l + 1) / 2 + m; };
-    std::vector<double> diag(d + 2), sd(d + 2);
-    diag[0] = 1.0;
-    for (int l = 1; l <= d + 1; ++l) diag[l] = std::sqrt((double)(2 * l + 1) * K(l) / ((double)(2 * l) * K(l - 1))) * diag[l - 1];
-    for (int l = 1; l <= d + 1; ++l) sd[l] = std::sqrt((double)(2 * l) * K(l - 1) / K(l)) * diag[l];
-    auto n1 = [](int l, int m) { return std::sqrt((double)(2 * l + 1) * (double)(2 * l - 1) / ((double)(l - m) * (double)(l + m))); };
-    auto n2 = [](int l, int m) {
-        return std::sqrt((double)(l + m - 1) * (double)(2 * l + 1) * (double)(l - m - 1) /
-                         ((double)(l + m) * (double)(l - m) * (double)(2 * l - 3)));
-    };
-    auto nq1 = [&](int l, int m) { return std::sqrt((double)(l - m) * K(m) * (double)(l + m + 1) / K(m + 1)); };
-    auto nq2 = [&](int l, int m) {
-        return std::sqrt((double)(l + m + 2) * (double)(l + m + 1) * (double)(2 * l + 1) * K(m) / ((double)(2 * l + 3) * K(m + 1)));
-    };
-    tab.clear();
-    tab.reserve((size_t)(d + 1) * (d + 2) / 2 * 8);
-    for (int M = 1; M <= d + 1; ++M)
-        for (int L = M; L <= d + 1; ++L) {
-            double e[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (L == M) e[0] = diag[M];
-            else if (L == M + 1) e[0] = sd[M + 1] / diag[M];
-            else { e[0] = n1(L, M); e[1] = n2(L, M); }
-            if (L <= d) {
-                e[2] = M * cbar[idx(L, M)];
-                e[3] = M * sbar[idx(L, M)];
-                const double q = nq1(L, M - 1);
-                e[4] = q * cbar[idx(L, M - 1)];
-                e[5] = q * sbar[idx(L, M - 1)];
-            }
-            if (L >= 2) {
-                const double q = nq2(L - 1, M - 1);
-                e[6] = q * cbar[idx(L - 1, M - 1)];
-                e[7] = q * sbar[idx(L - 1, M - 1)];
-            }
-            tab.insert(tab.end(), e, e + 8);
-        }
-    tab.insert(tab.end(), 16, 0.0);   // spare entries: the kernel's software pipeline reads ahead
-}
-
-// Stream of the DPP-broadcast form (bsk_device.hpp: gravity_sh_dpp): same iteration order, 8 doubles
-// per entry, but (i) the recursion is rescaled column by column, Bt_L = B_L / alpha_L with
-// alpha_M = alpha_(M+1) = 1, alpha_L = n2(L, M) alpha_(L-2), so entry[0] = n1 alpha_(L-1) / alpha_L is
-// the only recursion constant and the six coefficient products carry alpha_L; (ii) every column is
-// padded to an even number of entries (a 128-byte chunk = 2 entries never straddles a column);
-// (iii) the stream is padded to whole SH_RING-chunk bodies plus two bodies of read-ahead slack.
-// The walk is cut into two halves of (nearly) equal entry count at a column boundary: `split` is the first
-// column of the second half, `chunk1` its first chunk; the kernels add the halves' partial sums in a fixed
-// order whether one wave or two walk them.
-struct ShLayout {
-    int split, chunk1, bodies, bodies0, bodies1;
-};
-ShLayout build_sh_table_dpp(int d, const double* cbar, const double* sbar, std::vector<double>& tab) {
-    auto K = [](int i) { return i == 0 ? 1.0L : 2.0L; };
-    auto idx = [](int l, int m) { return l * (l + 1) / 2 + m; };
-    std::vector<long double> diag(d + 2), sd(d + 2), alpha(d + 3);
-    diag[0] = 1.0L;
-    for (int l = 1; l <= d + 1; ++l) diag[l] = sqrtl((long double)(2 * l + 1) * K(l) / ((long double)(2 * l) * K(l - 1))) * diag[l - 1];
-    for (int l = 1; l <= d + 1; ++l) sd[l] = sqrtl((long double)(2 * l) * K(l - 1) / K(l)) * diag[l];
-    auto n1 = [](int l, int m) { return sqrtl((long double)(2 * l + 1) * (long double)(2 * l - 1) / ((long double)(l - m) * (long double)(l + m))); };
-    auto n2 = [](int l, int m) {
-        return sqrtl((long double)(l + m - 1) * (long double)(2 * l + 1) * (long double)(l - m - 1) /
-                     ((long double)(l + m) * (long double)(l - m) * (long double)(2 * l - 3)));
-    };
-    auto nq1 = [&](int l, int m) { return sqrtl((long double)(l - m) * K(m) * (long double)(l + m + 1) / K(m + 1)); };
-    auto nq2 = [&](int l, int m) {
-        return sqrtl((long double)(l + m + 2) * (long double)(l + m + 1) * (long double)(2 * l + 1) * K(m) /
-                     ((long double)(2 * l + 3) * K(m + 1)));
-    };
-    tab.clear();
-    std::vector<size_t> col_chunk(d + 3, 0);   // first chunk of column M
-    for (int M = 1; M <= d + 1; ++M) {
-        col_chunk[M] = tab.size() / 16;
-        for (int L = M; L <= d + 1; ++L) {
-            long double e[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            alpha[L] = (L <= M + 1) ? 1.0L : n2(L, M) * alpha[L - 2];
-            if (L == M) e[0] = diag[M];
-            else if (L == M + 1) e[0] = sd[M + 1] / diag[M];
-            else e[0] = n1(L, M) * alpha[L - 1] / alpha[L];
-            if (L <= d) {
-                e[2] = M * (long double)cbar[idx(L, M)];
-                e[3] = M * (long double)sbar[idx(L, M)];
-                const long double q = nq1(L, M - 1);
-                e[4] = q * cbar[idx(L, M - 1)];
-                e[5] = q * sbar[idx(L, M - 1)];
-            }
-            if (L >= 2) {
-                const long double q = nq2(L - 1, M - 1);
-                e[6] = q * cbar[idx(L - 1, M - 1)];
-                e[7] = q * sbar[idx(L - 1, M - 1)];
-            }
-            for (int k = 0; k < 8; ++k) tab.push_back((double)(k >= 2 ? e[k] * alpha[L] : e[k]));
-        }
-        if ((d + 1 - M + 1) & 1) tab.insert(tab.end(), 8, 0.0);   // odd column: one all-zero entry
-    }
-    const size_t chunks = tab.size() / 16, R = bsk::SH_RING;
-    col_chunk[d + 2] = chunks;
-    ShLayout lay;
-    // Balance the halves by issue slots, not by chunks: a column end costs about two chunks' worth (flush,
-    // combine, restart, two taken branches) and the second half has many short columns; it also raises
-    // (s + i t) to its first column's power first (about a third of a chunk per column skipped).
-    auto cost0 = [&](int sp) { return (double)col_chunk[sp] + 2.0 * (sp - 1); };
-    auto cost1 = [&](int sp) { return (double)(chunks - col_chunk[sp]) + 2.0 * (d + 2 - sp) + 0.33 * (sp - 1); };
-    lay.split = 2;                                   // 1 < split <= d + 1: both halves own at least one column
-    while (lay.split < d + 1 && cost0(lay.split + 1) <= cost1(lay.split + 1)) ++lay.split;
-    lay.chunk1 = (int)col_chunk[lay.split];
-    lay.bodies = (int)((chunks + R - 1) / R);
-    lay.bodies0 = (int)((col_chunk[lay.split] + R - 1) / R);
-    lay.bodies1 = (int)((chunks - col_chunk[lay.split] + R - 1) / R);
-    tab.resize(((size_t)lay.bodies * R + 2 * R) * 16, 0.0);
-    return lay;
-}
-
-int build_params(const bsk_config& c, bsk::StepParams& p, bsk::ColdCfg& k, bool& diag) {
-    std::memset(&p, 0, sizeof p);
-    std::memset(&k, 0, sizeof k);
-    p.dt = c.dt;
-    p.mu = c.mu;
-    p.j2k = 1.5 * c.j2 * c.mu * c.req * c.req;
-    std::memcpy(p.inertia, c.inertia, sizeof p.inertia);
-    std::memcpy(k.inertia, c.inertia, sizeof k.inertia);
-    double D[9];
-    std::memcpy(D, c.inertia, sizeof D);
-    for (int i = 0; i < c.n_rw; ++i) {
-        double nrm = std::sqrt(c.gs[i][0] * c.gs[i][0] + c.gs[i][1] * c.gs[i][1] + c.gs[i][2] * c.gs[i][2]);
-        if (!(std::fabs(nrm - 1.0) < 1e-9)) return fail(BSK_EINVAL, "wheel spin axis is not a unit vector");
-        if (!(c.js[i] > 0.0)) return fail(BSK_EINVAL, "wheel inertia js must be positive");
-        for (int a = 0; a < 3; ++a) {
-            p.gs[i][a] = c.gs[i][a];
-            for (int b = 0; b < 3; ++b) D[3 * a + b] -= c.js[i] * c.gs[i][a] * c.gs[i][b];
-        }
-        p.js[i] = c.js[i];
-    }
-    if (!inv3(D, p.dinv)) return fail(BSK_EINVAL, "hub inertia minus wheel inertia is singular");
-    for (int i = 0; i < 9; ++i) { p.dmat[i] = D[i]; p.wmat[i] = c.inertia[i] - D[i]; }
-    // Diagonal fast path: only when every off-diagonal of I_sc and of (I_sc - sum Js g g^T) is
-    // EXACTLY zero (true for the reference's cuboid hub with the triad or the symmetric pyramid).
-    diag = true;
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b)
-            if (a != b && (c.inertia[3 * a + b] != 0.0 || D[3 * a + b] != 0.0)) diag = false;
-    if (c.n_rw > 0) {
-        // rwMotorTorque: map = CGs^T (CGs CGs^T)^-1 C,  CGs = C Gs
-        double cgs[3][BSK_MAX_RW], M[9] = {0}, Mi[9];
-        for (int a = 0; a < 3; ++a)
-            for (int i = 0; i < c.n_rw; ++i)
-                cgs[a][i] = c.ctrl_axes[3 * a] * c.gs[i][0] + c.ctrl_axes[3 * a + 1] * c.gs[i][1] +
-                            c.ctrl_axes[3 * a + 2] * c.gs[i][2];
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b)
-                for (int i = 0; i < c.n_rw; ++i) M[3 * a + b] += cgs[a][i] * cgs[b][i];
-        if (!inv3(M, Mi)) return fail(BSK_EINVAL, "wheel set does not span the control axes");
-        for (int i = 0; i < c.n_rw; ++i) {
-            double t[3];
-            for (int a = 0; a < 3; ++a) t[a] = cgs[0][i] * Mi[a] + cgs[1][i] * Mi[3 + a] + cgs[2][i] * Mi[6 + a];
-            for (int b = 0; b < 3; ++b)
-                k.map[i][b] = t[0] * c.ctrl_axes[b] + t[1] * c.ctrl_axes[3 + b] + t[2] * c.ctrl_axes[6 + b];
-        }
-    }
-    p.f_coulomb = c.f_coulomb;
-    p.fsw_every = c.fsw_every;
-    p.fsw_lag = c.fsw_lag;
-    p.nav_lag = c.nav_lag;
-    p.req = c.req;
-    p.planet_rate = c.planet_rate;
-    p.sh_tab = nullptr;
-    p.sh_degree = 0;
-    p.sh_split = 2;
-    p.sh_bodies = p.sh_bodies0 = p.sh_bodies1 = p.sh_chunk1 = 0;
-    const bool full = (c.flags & (BSK_FLAG_SUN_THIRD_BODY | BSK_FLAG_DRAG | BSK_FLAG_DESAT)) != 0;
-    p.ex.desat = (c.flags & BSK_FLAG_DESAT) ? 1 : 0;
-    p.ex.pad_ = 0;
-    k.n_thr = c.n_thr;
-    k.hs_min = c.hs_min;
-    k.inv_max_thrust = c.thr_max_thrust > 0.0 ? 1.0 / c.thr_max_thrust : 0.0;
-    k.thr_min_fire_time = c.thr_min_fire_time;
-    k.thr_min_on_time = c.thr_min_on_time;
-    k.thr_max_counter = c.thr_max_counter;
-    k.fsw_lag = c.fsw_lag;
-    k.nav_lag = c.nav_lag;
-    for (int i = 0; i < c.n_rw; ++i) { k.js[i] = c.js[i]; for (int j = 0; j < 3; ++j) k.gs[i][j] = c.gs[i][j]; }
-    if (c.flags & BSK_FLAG_DESAT) {
-        double dd[9] = {0}, ddi[9], Dm[BSK_MAX_THR][3];
-        for (int i = 0; i < c.n_thr; ++i) {
-            const double* r = c.thr_pos[i];
-            const double* g = c.thr_dir[i];
-            Dm[i][0] = r[1] * g[2] - r[2] * g[1]; Dm[i][1] = r[2] * g[0] - r[0] * g[2]; Dm[i][2] = r[0] * g[1] - r[1] * g[0];
-            for (int j = 0; j < 3; ++j) { k.thr_f[i][j] = c.thr_max_thrust * g[j]; k.thr_l[i][j] = c.thr_max_thrust * Dm[i][j]; }
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b) dd[3 * a + b] += Dm[i][a] * Dm[i][b];
-        }
-        if (!inv3(dd, ddi)) return fail(BSK_EINVAL, "thruster set does not span the three torque axes");
-        for (int i = 0; i < c.n_thr; ++i)
-            for (int a = 0; a < 3; ++a) k.thr_map[i][a] = ddi[3 * a] * Dm[i][0] + ddi[3 * a + 1] * Dm[i][1] + ddi[3 * a + 2] * Dm[i][2];
-    }
-    p.feat = full ? bsk::FEAT_FULL : ((c.flags & BSK_FLAG_POWER) ? bsk::FEAT_POWER : bsk::FEAT_BARE);   // FEAT_FULLG: below
-    if (c.flags & BSK_FLAG_LDS_SCRATCH) p.feat = bsk::FEAT_LDSS;
-    p.ex.mu_sun = (c.flags & BSK_FLAG_SUN_THIRD_BODY) ? c.mu_sun : 0.0;
-    p.ex.base_density = (c.flags & BSK_FLAG_DRAG) ? c.base_density : 0.0;
-    p.ex.inv_scale_height = c.scale_height > 0.0 ? 1.0 / c.scale_height : 0.0;
-    p.ex.inv_mass = c.mass > 0.0 ? 1.0 / c.mass : 0.0;
-    p.ex.rho_skip = 1e-25;
-    k.n_facets = c.n_facets;
-    k.facet_axis = 1;
-    for (int i = 0; i < c.n_facets && i < 8; ++i) {
-        // axis-aligned normal: exactly one component is +-1, the others exactly 0
-        int axis = -1, nz = 0;
-        for (int j = 0; j < 3; ++j)
-            if (c.facet_normal[i][j] != 0.0) { ++nz; axis = j; }
-        if (nz != 1 || std::fabs(c.facet_normal[i][axis]) != 1.0) { k.facet_axis = 0; break; }
-        const int sgn = c.facet_normal[i][axis] > 0.0 ? 0 : 1;
-        const double acd = c.facet_area[i] * c.facet_cd[i];
-        k.fa_c[sgn][axis] += acd;
-        for (int j = 0; j < 3; ++j) k.fa_r[sgn][axis][j] += acd * c.facet_pos[i][j];
-    }
-    // half sums / half differences of the +e_k and -e_k tables (bsk_device.hpp: facet_drag)
-    for (int axis = 0; axis < 3; ++axis) {
-        const double cp = k.fa_c[0][axis], cm = k.fa_c[1][axis];
-        k.fa_c[0][axis] = 0.5 * (cp + cm);
-        k.fa_c[1][axis] = 0.5 * (cp - cm);
-        for (int j = 0; j < 3; ++j) {
-            const double rp = k.fa_r[0][axis][j], rm = k.fa_r[1][axis][j];
-            k.fa_r[0][axis][j] = 0.5 * (rp + rm);
-            k.fa_r[1][axis][j] = 0.5 * (rp - rm);
-        }
-    }
-    if (k.facet_axis) {
-        bool diagonal = true;
-        for (int sgn = 0; sgn < 2; ++sgn)
-            for (int axis = 0; axis < 3; ++axis)
-                for (int j = 0; j < 3; ++j)
-                    if (j != axis && k.fa_r[sgn][axis][j] != 0.0) diagonal = false;
-        if (diagonal) k.facet_axis = 2;   // facet centres on their own normal axes: 12 table values suffice
-    }
-    // any other facet set with live drag runs the generic-geometry variant of the full-scenario kernel
-    if (full && (c.flags & BSK_FLAG_DRAG) && c.base_density != 0.0 && k.facet_axis != 2) p.feat = bsk::FEAT_FULLG;
-    for (int i = 0; i < 8; ++i) {
-        k.facet_acd[i] = c.facet_area[i] * c.facet_cd[i];
-        for (int j = 0; j < 3; ++j) { k.facet_n[i][j] = c.facet_normal[i][j]; k.facet_r[i][j] = c.facet_pos[i][j]; }
-    }
-    {
-        const double AU = 149597870700.0, RSUN = 695000.0e3;
-        for (int i = 0; i < 3; ++i) { p.pc.nB[i] = c.panel_normal[i]; p.pc.sun_r0[i] = c.sun_r0[i]; p.pc.sun_v[i] = c.sun_v[i]; }
-        p.pc.kflux = c.panel_area * c.panel_efficiency * c.solar_flux * AU * AU;
-        p.pc.draw = c.power_draw;
-        p.pc.cap = c.storage_capacity;
-        p.pc.req = c.req;
-        p.pc.rsun = RSUN;
-        p.pc.rs_plus = RSUN + c.req;
-        p.pc.rs_minus = RSUN - c.req;
-    }
-    k.u_max = c.u_max;
-    k.u_min = c.u_min;
-    k.K = c.K;
-    k.P = c.P;
-    std::memcpy(p.obs.sigma_R0N, c.sigma_R0N, sizeof p.obs.sigma_R0N);
-    std::memcpy(k.sigma_R0N, c.sigma_R0N, sizeof k.sigma_R0N);
-    p.obs.inv_wheel_limit = 1.0 / c.wheel_limit;
-    p.obs.charge_scale = 1.0 / 3600.0 / c.power_max;
-    p.obs.reward_mult = c.reward_mult;
-    p.obs.failure_penalty = c.failure_penalty;
-    p.obs.r_min2 = c.r_min * c.r_min;
-    p.obs.max_length = c.max_length;
-    p.obs.pad_ = 0;
-    // broadcast table of the full-scenario kernels (bsk_device.hpp: KTab, KA_* / KB_* / KC_*)
-    for (int i = 0; i < c.n_rw; ++i) {
-        for (int j = 0; j < 3; ++j) k.kt[bsk::KA_G + 3 * i + j] = c.gs[i][j];
-        k.kt[bsk::KA_JS + i] = c.js[i];
-        k.kt[16 + bsk::KB_IJS + i] = 1.0 / c.js[i];
-        for (int j = 0; j < 3; ++j) k.kt[48 + bsk::KD_JG + 3 * i + j] = c.js[i] * c.gs[i][j];
-        k.kt[48 + bsk::KD_HIJS + i] = c.dt / c.js[i];
-    }
-    for (int sgn = 0; sgn < 2; ++sgn)
-        for (int axis = 0; axis < 3; ++axis) {
-            k.kt[16 + bsk::KB_FAC + 3 * sgn + axis] = k.fa_c[sgn][axis] * p.ex.inv_mass;   // area table carries 1/m
-            k.kt[16 + bsk::KB_FAD + 3 * sgn + axis] = k.fa_r[sgn][axis][axis];
-        }
-    k.kt[32 + bsk::KC_IMASS] = p.ex.inv_mass;
-    for (int j = 0; j < 3; ++j) k.kt[32 + bsk::KC_NB + j] = c.panel_normal[j];
-    k.kt[32 + bsk::KC_KFLUX] = p.pc.kflux;
-    k.kt[32 + bsk::KC_RHO0] = p.ex.base_density;
-    k.kt[32 + bsk::KC_NIH] = -p.ex.inv_scale_height;
-    k.kt[32 + bsk::KC_REQIH] = c.req * p.ex.inv_scale_height;
-    k.kt[32 + bsk::KC_RSKIP] = p.ex.rho_skip;
-    k.kt[32 + bsk::KC_LOG2E] = 1.4426950408889634074;
-    k.kt[32 + bsk::KC_I6] = 1.0 / 6.0; k.kt[32 + bsk::KC_I24] = 1.0 / 24.0; k.kt[32 + bsk::KC_I120] = 1.0 / 120.0;   // Atmo::advance
-    k.kt[32 + bsk::KC_I720] = 1.0 / 720.0;
-    {   // row E: rho0 / k!, k = 0..13 (bsk_device.hpp: atmosphere_density), -ln2 split in two parts
-        long double f = 1.0L;
-        for (int i = 0; i < 14; ++i) {
-            if (i > 1) f *= (long double)i;
-            k.kt[64 + bsk::KE_POLY + i] = (double)((long double)p.ex.base_density / f);
-        }
-        k.kt[64 + bsk::KE_NLN2HI] = -6.93147180369123816490e-01;
-        k.kt[64 + bsk::KE_NLN2LO] = -1.90821492927058770002e-10;
-    }
-    // thruster subset table: row m = sums over the set bits of m, ascending thruster index
-    for (int m = 0; m < (1 << BSK_MAX_THR); ++m) {
-        double f[6] = {0, 0, 0, 0, 0, 0};
-        for (int i = 0; i < c.n_thr && i < BSK_MAX_THR; ++i)
-            if (m & (1 << i))
-                for (int j = 0; j < 3; ++j) { f[j] += k.thr_f[i][j]; f[3 + j] += k.thr_l[i][j]; }
-        for (int j = 0; j < 6; ++j) k.thr_tab[m][j] = f[j];
-    }
+int open_device(int device_id, hipDeviceProp_t* prop_out) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(BSK_ENODEV, "no HIP device visible: libbskgpu has no CPU fallback");
+    if (device_id < 0 || device_id >= ndev) return fail(BSK_ENODEV, "device_id out of range");
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device_id));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(BSK_ENODEV, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    if (prop_out) *prop_out = prop;
     return BSK_OK;
 }
 
-}  // namespace
+} }  // namespace bsk::capi
 
-struct bsk_handle {
-    bsk_config cfg;
-    bsk::StepParams sp;
-    bsk::ColdCfg cold;
-    bool diag = false;
-    bsk::ColdCfg* d_cold = nullptr;
-    int n = 0, nf = 0, device = 0, block = 64;
-    int64_t stride = 0;      // of the state slab's field rows (padded: bsk_create)
-    int64_t ostride = 0;     // of the observation / terminal-observation rows and the size of every per-env array
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    double* d_state = nullptr;
-    int2* d_cnt = nullptr;
-    int* d_act = nullptr;
-    double* d_obs = nullptr;
-    double* d_reward = nullptr;
-    unsigned long long* d_done_mask = nullptr;
-    unsigned char* d_reason = nullptr;
-    double* d_stat_sum = nullptr;
-    long long* d_stat_done = nullptr;
-    double* d_wave_sum = nullptr;              // stats_kernel scratch: one reward sum per 64 envs
-    unsigned* d_done_part = nullptr;           // stats_kernel scratch: finished envs per first-level workgroup
-    // masked-reset staging
-    double* d_ic_stage = nullptr;
-    int* d_idx_stage = nullptr;
-    unsigned char* d_mask_stage = nullptr;
-    size_t stage_cap = 0;
-    double* d_sh_tab = nullptr;    // scalar-load stream (form 1)
-    double* d_sh_tab4 = nullptr;   // DPP-broadcast stream (forms 4 and 5, default)
-    double* d_pool = nullptr;
-    double* d_term_obs = nullptr;
-    int* d_episodes = nullptr;
-    int n_pool = 0, pool_cap = 0;
-    // profiling
-    std::vector<hipEvent_t> ev;
-    int ev_used = 0;
-    int ev_stride = 1, ev_seq = 0;
-    hipEvent_t ev_warm[2] = {nullptr, nullptr};
-    bool prof = false;
-    double sim_time = 0.0;
-    unsigned env_base = 0;   // global index of env 0 (bsk_set_env_base)
-    // device-resident surface (BSK_FLAG_EPISODE_STATS / BSK_FLAG_OBS_ROWMAJOR)
-    double* d_ep_return = nullptr;
-    double* d_term_return = nullptr;
-    int* d_term_len = nullptr;
-    unsigned char* d_done = nullptr;
-    double* d_obs_rm = nullptr;
-    unsigned long long* d_dbg = nullptr;   // one word per wave for probe builds (bsk_probes.hpp)
-    unsigned long long* d_seal = nullptr;   // [3] what env 0's counters were behind the last reset entry point (bsk_aux.hip: stats_sealed)
-    double* d_stats2 = nullptr;   // {sum of rewards, number of done envs} of the last step, as two doubles (all-reduce operand)
-    bool stats_fresh = false;     // d_stat_sum / d_stat_done / d_stats2 hold the LAST STEP's batch scalars (snapshot_stats)
-    bool step_stats = false;      // bsk_set_step_stats: step launches write d_wave_sum themselves (a request = the join kernel alone)
-    bool wave_sums_fresh = false; // ... and the last launch that wrote rewards did so
-    bool stepped = false;         // some step has run since the handle was created
-    // A launch of this handle has been recorded into a HIP graph (note_capture): replays advance the device without this
-    // host-side state, so from then on nothing evaluated at enqueue time is trusted - the batch scalars are formed again
-    // whenever asked for (stats_fresh ignored) and the bare levels read the battery charge again (static_charge off).
-    bool replayable = false;
-    // error word the kernels can raise (page-locked host memory, device-visible): checked by every synchronising entry point
-    int* h_err = nullptr;
-    // bare levels: no spacecraft of the batch / of the reset pool started its episode with an empty battery (bsk_launch.hpp:
-    // StepArgs::static_charge).  Known after a reset of the whole batch; withdrawn by bsk_set_state until the next one.
-    bool charge_pos = false, pool_charge_pos = false;
-    // Form policy of the step kernel (choose_form).  Pair form (bsk_device.hpp: PairLds): launches of >= pair_min_substeps sub-steps
-    // of batches of <= pair_max_envs spacecraft where it is built (power / full-scenario levels, point mass or J2, diagonal hub).
-    // Measured (profiles/r03/pair_form.txt): -13 % per env step up to one pair per CU (16 384 spacecraft), level with the
-    // single-wave form up to three pairs per CU, 7 % slower at four (65 536).  Three-wave form (bsk_device.hpp: TriX): the pair form
-    // with the dynamics wave cut into a translational and a rotational wave; full-scenario level only, preferred over the pair form
-    // where both apply (profiles/r03/tri_form.txt: -16 % against the pair form up to one workgroup per CU, twice the time above).
-    // BSKGPU_PAIR / BSKGPU_TRI = 0 | 1 force a form off / on for every launch (bsk_create).  Harmonics run sh_form (bsk_set_gravity_sh).
-    struct {
-        bool pair_ok = false, tri_ok = false;
-        int pair_min_substeps = 16, pair_max_envs = 16384;
-        int tri_min_substeps = 16, tri_max_envs = 16384;
-        int sh_form = bsk::FORM_SH_DPP;
-    } policy;
-    // what the last launch ran (bsk_kernel_info): the step kernel in `form`, or bsk_step_n's rollout kernel (with per-step actions)
-    struct { int form; bool rollout, act; } last = {bsk::FORM_SINGLE, false, false};
-    // the coefficients of the last bsk_set_gravity_sh (bsk_fork_device refuses to fork between handles of different fields)
-    std::vector<double> sh_cbar, sh_sbar;
-    // bsk_fork_device: the in-handle fork's gather scratch (every per-env buffer a handle can have, one allocation, kept for the
-    // handle's lifetime), the host map's staging buffer, and the events that order two handles' streams around a fork
-    bsk::ForkSide fork_scratch = {};
-    void* d_fork_block = nullptr;
-    int* d_map_stage = nullptr;
-    hipEvent_t ev_fork_in = nullptr, ev_fork_out = nullptr;
-};
-
-// bsk_policy_*: the fused MLP policy (kernel and layout: bsk_policy.hip)
-struct bsk_policy {
-    bsk::PolicyLayout lay;
-    int device = 0;
-    float* d_params = nullptr;             // the device layout of the parameters (bsk_policy.hpp)
-    unsigned long long* d_rng = nullptr;   // {seed, draw}: read by sample-mode launches, draw advanced behind each of them
-    int* d_act = nullptr;                  // bsk_policy_rollout's scratch row of actions (d_action_hist == NULL)
-    int act_cap = 0;
-};
-
-// bsk_population_*: n_members parameter blocks of one spec, member m driving envs [m * E, (m + 1) * E) (bsk_policy.hip,
-// bsk_population.hip)
-struct bsk_population {
-    bsk::PolicyLayout lay;
-    int device = 0;
-    int n_members = 0;
-    float* d_params = nullptr;             // [n_members][lay.n_device]: one device layout per member
-    unsigned long long* d_rng = nullptr;   // {seed, draw}, one pair for the whole population
-    // bsk_population_rollout's scratch, one allocation sized for the largest handle seen: the running value of every env and a
-    // row of actions (d_action_hist == NULL)
-    void* d_scratch = nullptr;
-    bsk::FitnessAcc acc = {};
-    int* d_act = nullptr;
-    int scratch_cap = 0;
-};
-
-// bsk_es_*: the evolution strategy whose candidates never leave the device (bsk_es.hip)
-struct bsk_es {
-    bsk::PolicyLayout lay;
-    int device = 0;
-    int n_members = 0;
-    double sigma = 0.0, lr = 0.0;
-    int frozen = 0;
-    unsigned long long* d_state = nullptr; // {seed, generation}: generation advanced behind every tell
-    double* d_theta = nullptr;             // [lay.n_params]
-    double* d_w = nullptr;                 // [n_members / 2]: bsk_es_tell's scratch, the utility difference of every pair
-    // bsk_es_set_optimizer: BSK_ES_SGD until Adam is selected; then ONE allocation [m | v | beta_pow] of 2 * n_params + 2 doubles
-    int optimizer = BSK_ES_SGD;
-    double beta1 = 0.0, beta2 = 0.0, eps = 0.0, weight_decay = 0.0;
-    double* d_adam = nullptr;
-};
+using namespace bsk::capi;
 
 namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-        else prev = -1;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-int validate(const bsk_config& c) {
-    if (c.abi_version != BSK_ABI_VERSION || c.struct_size != sizeof(bsk_config))
-        return fail(BSK_EABI, "bsk_config abi_version/struct_size mismatch (header " + std::to_string(BSK_ABI_VERSION) +
-                                  "/" + std::to_string(sizeof(bsk_config)) + ")");
-    if (!(c.dt > 0.0)) return fail(BSK_EINVAL, "dt must be positive");
-    if (c.fsw_every < 1 || c.fsw_every > 2047) return fail(BSK_EINVAL, "fsw_every must be in 1..2047");
-    if (c.max_length < 0 || c.max_length > 1000000) return fail(BSK_EINVAL, "max_length must be in 0..1000000");
-    if (c.fsw_lag != 0 && c.fsw_lag != 1) return fail(BSK_EINVAL, "fsw_lag must be 0 or 1");
-    if (c.nav_lag != 0 && c.nav_lag != 1) return fail(BSK_EINVAL, "nav_lag must be 0 or 1");
-    if (c.n_rw != 0 && c.n_rw != 3 && c.n_rw != 4) return fail(BSK_EINVAL, "n_rw must be 0, 3 or 4");
-    if (c.gravity_model != BSK_GRAV_PM && c.gravity_model != BSK_GRAV_PM_J2 && c.gravity_model != BSK_GRAV_SH)
-        return fail(BSK_EINVAL, "unknown gravity_model");
-    if (c.gravity_model == BSK_GRAV_SH && (c.sh_degree < 2 || c.sh_degree > BSK_MAX_SH_DEGREE))
-        return fail(BSK_EINVAL, "sh_degree must be in 2..70 for BSK_GRAV_SH");
-    if ((c.flags & (BSK_FLAG_SUN_THIRD_BODY | BSK_FLAG_DRAG | BSK_FLAG_DESAT)) && !(c.flags & BSK_FLAG_POWER))
-        return fail(BSK_EINVAL, "BSK_FLAG_SUN_THIRD_BODY / BSK_FLAG_DRAG / BSK_FLAG_DESAT are built in the full-scenario kernel: set BSK_FLAG_POWER too");
-    if ((c.flags & BSK_FLAG_DESAT) && (c.n_thr < 3 || c.n_thr > BSK_MAX_THR || c.n_rw == 0 || !(c.thr_max_thrust > 0.0) || !(c.mass > 0.0)))
-        return fail(BSK_EINVAL, "BSK_FLAG_DESAT needs 3..8 thrusters, wheels, thr_max_thrust > 0 and mass > 0");
-    if ((c.flags & BSK_FLAG_DRAG) && (c.n_facets < 0 || c.n_facets > 8 || !(c.scale_height > 0.0) || !(c.mass > 0.0)))
-        return fail(BSK_EINVAL, "BSK_FLAG_DRAG needs 0..8 facets, scale_height > 0 and mass > 0");
-    if ((c.flags & BSK_FLAG_LDS_SCRATCH) && ((c.flags & BSK_FLAG_POWER) || c.gravity_model == BSK_GRAV_SH))
-        return fail(BSK_EINVAL, "BSK_FLAG_LDS_SCRATCH is built for the bare propagator (point mass / J2, no power system) only");
-    if (!(c.mu > 0.0) || !(c.req > 0.0)) return fail(BSK_EINVAL, "mu and req must be positive");
-    if (!(c.wheel_limit > 0.0) || !(c.power_max > 0.0)) return fail(BSK_EINVAL, "wheel_limit and power_max must be positive");
-    if ((c.flags & BSK_FLAG_POWER) && !(c.storage_capacity > 0.0 && c.sun_r0[0] * c.sun_r0[0] + c.sun_r0[1] * c.sun_r0[1] + c.sun_r0[2] * c.sun_r0[2] > 0.0))
-        return fail(BSK_EINVAL, "BSK_FLAG_POWER needs storage_capacity > 0 and a Sun position");
-    return BSK_OK;
-}
 
 // Extra elements per field row of the state slab.  An EMPIRICAL constant, not a derived one: with the slab's rows an odd multiple of
 // 256 B apart the K = 1 launch of 65 536 spacecraft is 2 - 3 % shorter than with rows at a power-of-two distance (6.20 against 6.36 us
@@ -694,12 +176,20 @@ int stamp_events(bsk_handle* h, hipEvent_t& e0, hipEvent_t& e1) {
     }
     return BSK_OK;
 }
+}  // namespace
 
-int do_step(bsk_handle* h, const void* d_actions, int substeps, int act_shift) {
+namespace bsk { namespace capi __attribute__((visibility("hidden"))) {
+
+int check_steppable(const bsk_handle* h) {
     if (h->cfg.gravity_model == BSK_GRAV_SH && !h->sp.sh_tab)
         return fail(BSK_EINVAL, "BSK_GRAV_SH: call bsk_set_gravity_sh before stepping");
     if ((h->cfg.flags & BSK_FLAG_AUTO_RESET) && h->n_pool == 0)
         return fail(BSK_EINVAL, "BSK_FLAG_AUTO_RESET: call bsk_set_ic_pool before stepping");
+    return BSK_OK;
+}
+
+int do_step(bsk_handle* h, const void* d_actions, int substeps, int act_shift) {
+    { int rc = check_steppable(h); if (rc) return rc; }
     bsk::StepBuffers b;
     const bool replayable = note_capture(h);      // (a captured launch must not freeze a host-side decision into the graph)
     fill_buffers(h, b, d_actions, substeps, act_shift,
@@ -715,6 +205,9 @@ int do_step(bsk_handle* h, const void* d_actions, int substeps, int act_shift) {
     h->stepped = true;
     return BSK_OK;
 }
+} }  // namespace bsk::capi
+
+namespace {
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Forks (bsk_fork_device; kernels: bsk_fork.hip)
@@ -802,79 +295,6 @@ int do_fork(bsk_handle* dst, bsk_handle* src, const int32_t* d_map) {
     dst->stepped = true;
     return BSK_OK;
 }
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// The policy (bsk_policy_*; kernel: bsk_policy.hip)
-int policy_spec_layout(const bsk_policy_spec* spec, bsk::PolicyLayout& lay) {
-    if (!spec) return fail(BSK_EINVAL, "spec is NULL");
-    if (spec->abi_version != BSK_ABI_VERSION || spec->struct_size != sizeof(bsk_policy_spec))
-        return fail(BSK_EABI, "bsk_policy_spec abi_version / struct_size mismatch");
-    if (const char* why = bsk::policy_layout(*spec, lay)) return fail(BSK_EINVAL, std::string("bsk_policy_spec: ") + why);
-    return BSK_OK;
-}
-
-// every argument of a policy launch, checked before anything is enqueued
-int policy_check_act(const bsk_policy* p, const double* d_obs, int64_t obs_stride, int n, int64_t env_base, int mode,
-                     const int32_t* d_action, const float* d_value, const float* d_logits, int64_t out_stride) {
-    if (!p || !d_obs || !d_action) return fail(BSK_EINVAL, "policy/d_obs/d_action is NULL");
-    if (n < 1 || n > (1 << 28)) return fail(BSK_EINVAL, "n must be in 1..2^28");
-    if (obs_stride < n) return fail(BSK_EINVAL, "obs_stride must be >= n");
-    if (env_base < 0) return fail(BSK_EINVAL, "env_base must be >= 0");
-    if (mode != BSK_POLICY_GREEDY && mode != BSK_POLICY_SAMPLE) return fail(BSK_EINVAL, "mode must be BSK_POLICY_GREEDY or BSK_POLICY_SAMPLE");
-    if (d_value && p->lay.v.n_layers == 0) return fail(BSK_EINVAL, "d_value given, but the policy has no value network");
-    if (d_logits && out_stride < n) return fail(BSK_EINVAL, "out_stride must be >= n");
-    return BSK_OK;
-}
-
-int policy_launch(bsk_policy* p, const double* d_obs, int64_t obs_stride, int n, int64_t env_base, int mode, int32_t* d_action,
-                  float* d_logp, float* d_value, float* d_logits, int64_t out_stride, hipStream_t stream) {
-    bsk::PolicyArgs a;
-    a.params = p->d_params; a.a = p->lay.a; a.v = p->lay.v; a.obs = d_obs; a.obs_stride = obs_stride; a.n = n;
-    a.env_base = (unsigned long long)env_base; a.mode = mode; a.rng = p->d_rng; a.action = d_action; a.logp = d_logp;
-    a.value = d_value; a.logits = d_logits; a.out_stride = out_stride; a.width = p->lay.width;
-    if (!d_value) a.v.n_layers = 0;            // (nobody asked for the value: its network is not evaluated)
-    HIP_TRY(bsk::launch_policy(a, stream));
-    if (mode == BSK_POLICY_SAMPLE) HIP_TRY(bsk::launch_policy_advance(p->d_rng, stream));
-    return BSK_OK;
-}
-
-// The entry points that touch the parameters or the draw counter from the host come after everything queued on the policy's device:
-// a policy keeps no stream of its own, and the stream of its last launch may be gone with the handle that owned it.
-int policy_upload(bsk_policy* p, const float* params) {
-    std::vector<float> dev;
-    bsk::policy_pack(p->lay, params, dev);
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old parameters)
-    HIP_COPY(hipMemcpy(p->d_params, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice));
-    return BSK_OK;
-}
-
-// The population: bsk_policy_act's checks with the member rule on top, all before anything is enqueued
-int population_check_act(const bsk_population* p, const double* d_obs, int64_t obs_stride, int n, int envs_per_member, int64_t env_base,
-                         int mode, const int32_t* d_action, const float* d_value, const float* d_logits, int64_t out_stride) {
-    if (!p || !d_obs || !d_action) return fail(BSK_EINVAL, "population/d_obs/d_action is NULL");
-    if (n < 1 || n > (1 << 28)) return fail(BSK_EINVAL, "n must be in 1..2^28");
-    if (envs_per_member < 64 || envs_per_member % 64 != 0) return fail(BSK_EINVAL, "envs_per_member must be a positive multiple of 64");
-    if ((int64_t)p->n_members * envs_per_member != (int64_t)n) return fail(BSK_EINVAL, "n must be n_members * envs_per_member");
-    if (obs_stride < n) return fail(BSK_EINVAL, "obs_stride must be >= n");
-    if (env_base < 0) return fail(BSK_EINVAL, "env_base must be >= 0");
-    if (mode != BSK_POLICY_GREEDY && mode != BSK_POLICY_SAMPLE) return fail(BSK_EINVAL, "mode must be BSK_POLICY_GREEDY or BSK_POLICY_SAMPLE");
-    if (d_value && p->lay.v.n_layers == 0) return fail(BSK_EINVAL, "d_value given, but the population has no value network");
-    if (d_logits && out_stride < n) return fail(BSK_EINVAL, "out_stride must be >= n");
-    return BSK_OK;
-}
-
-int population_launch(bsk_population* p, const double* d_obs, int64_t obs_stride, int n, int envs_per_member, int64_t env_base, int mode,
-                      int32_t* d_action, float* d_logp, float* d_value, float* d_logits, int64_t out_stride, hipStream_t stream) {
-    bsk::PolicyArgs a;
-    a.params = p->d_params; a.a = p->lay.a; a.v = p->lay.v; a.obs = d_obs; a.obs_stride = obs_stride; a.n = n;
-    a.env_base = (unsigned long long)env_base; a.mode = mode; a.rng = p->d_rng; a.action = d_action; a.logp = d_logp;
-    a.value = d_value; a.logits = d_logits; a.out_stride = out_stride; a.width = p->lay.width;
-    if (!d_value) a.v.n_layers = 0;            // (nobody asked for the value: its network is not evaluated)
-    HIP_TRY(bsk::launch_policy_population(a, envs_per_member, p->lay.n_device, stream));
-    if (mode == BSK_POLICY_SAMPLE) HIP_TRY(bsk::launch_policy_advance(p->d_rng, stream));
-    return BSK_OK;
-}
-
 }  // namespace
 
 static int ensure_pool_buffers(bsk_handle* h, int n_pool);
@@ -884,119 +304,14 @@ extern "C" {
 const char* bsk_last_error(void) { return g_err.c_str(); }
 const char* bsk_version(void) { return "bskgpu 0.1 (gfx950)"; }
 
-int bsk_default_config(bsk_config* c, int n_rw, int gravity_model) {
-    if (!c) return fail(BSK_EINVAL, "cfg is NULL");
-    if (n_rw != 0 && n_rw != 3 && n_rw != 4) return fail(BSK_EINVAL, "n_rw must be 0, 3 or 4");
-    std::memset(c, 0, sizeof *c);
-    c->abi_version = BSK_ABI_VERSION;
-    c->struct_size = sizeof *c;
-    c->dt = 0.1;
-    c->fsw_every = 10;
-    c->gravity_model = gravity_model;
-    c->sh_degree = 0;
-    c->n_rw = n_rw;
-    c->flags = 0;
-    c->max_length = 540;
-    c->fsw_lag = 1;
-    c->nav_lag = 1;
-    c->mu = 0.3986004415e15;
-    c->req = 6378136.6;
-    c->j2 = std::sqrt(5.0) * 4.841693e-4;
-    c->planet_rate = 7.2921159e-5;
-    const double m = 330.0, w = 1.38, dpt = 1.04, ht = 1.58;
-    c->mass = m;
-    c->inertia[0] = 1. / 12. * m * (w * w + dpt * dpt);
-    c->inertia[4] = 1. / 12. * m * (dpt * dpt + ht * ht);
-    c->inertia[8] = 1. / 12. * m * (w * w + ht * ht);
-    const double D2R = M_PI / 180.0;
-    if (n_rw == 3) {
-        for (int i = 0; i < 3; ++i) c->gs[i][i] = 1.0;
-    } else if (n_rw == 4) {
-        // one quadrant's components with explicit signs: exactly symmetric set (see
-        // actuatorPrimatives.balancedHR16Pyramid), so sum(g g^T) is exactly diagonal
-        const double el = 40.0 * D2R, az = 45.0 * D2R;
-        double cx = std::cos(az) * std::cos(el), cy = std::sin(az) * std::cos(el), cz = std::sin(el);
-        const double nn = std::sqrt(cx * cx + cy * cy + cz * cz);
-        cx /= nn; cy /= nn; cz /= nn;
-        const int sx[4] = {1, -1, -1, 1}, sy[4] = {1, 1, -1, -1};
-        for (int i = 0; i < 4; ++i) {
-            c->gs[i][0] = sx[i] * cx;
-            c->gs[i][1] = sy[i] * cy;
-            c->gs[i][2] = cz;
-        }
-    }
-    for (int i = 0; i < n_rw; ++i) c->js[i] = 50.0 / (6000.0 * M_PI * 2.0 / 60.0);
-    c->u_max = 0.2;
-    c->u_min = 0.00001;
-    c->f_coulomb = 0.0005;
-    c->K = 7.0;
-    c->P = 35.0;
-    c->sigma_R0N[0] = 1.0;
-    c->ctrl_axes[0] = c->ctrl_axes[4] = c->ctrl_axes[8] = 1.0;
-    c->wheel_limit = 3000.0 * (2.0 * M_PI / 60.0);
-    c->power_max = 20.0;
-    c->reward_mult = 1.0 / 540.0;
-    c->failure_penalty = 1.0;
-    c->r_min = 6378.1366 / 1000.0;
-    c->panel_normal[1] = -1.0;
-    c->panel_area = 0.2 * 0.3;
-    c->panel_efficiency = 0.20;
-    c->power_draw = -5.0;
-    c->storage_capacity = 20.0 * 3600.0;
-    c->solar_flux = 1372.5398;
-    // epoch 2021 MAY 04 07:47:48.965 UTC (JD 2459338.5 + 07:47:48.965)
-    const double jd0 = 2459338.5 + (7.0 * 3600.0 + 47.0 * 60.0 + 48.965) / 86400.0;
-    double p0[3], p1[3];
-    sun_position(jd0, p0);
-    sun_position(jd0 + 1.0, p1);
-    for (int k = 0; k < 3; ++k) {
-        c->sun_r0[k] = p0[k];
-        c->sun_v[k] = (p1[k] - p0[k]) / 86400.0;
-    }
-    c->mu_sun = 1.32712440018e20;
-    c->hs_min = 4.0;
-    c->thr_max_counter = 4;
-    c->thr_min_fire_time = 0.002;
-    {   // idealMonarc1Octet (actuatorPrimatives.py:66-161), MOOG Monarc-1: 0.9 N, MinOnTime 0.02 s
-        const double x = 3.874945160902288e-2, y = 1.206182747348013, z = 0.85245, x2 = 3.8749451609022656e-2;
-        const double loc[8][3] = {{x, -y, z}, {x, -y, -z}, {-x2, -y, z}, {-x2, -y, -z}, {-x, y, z}, {-x, y, -z}, {x2, y, z}, {x2, y, -z}};
-        const double a = 0.7071067811865476, b = 0.7071067811865475;
-        const double dir[8][3] = {{-a, b, 0}, {-a, b, 0}, {b, a, 0}, {b, a, 0}, {a, -b, 0}, {a, -b, 0}, {-b, -a, 0}, {-b, -a, 0}};
-        c->n_thr = 8;
-        for (int i = 0; i < 8; ++i)
-            for (int k = 0; k < 3; ++k) { c->thr_pos[i][k] = loc[i][k]; c->thr_dir[i][k] = dir[i][k]; }
-        c->thr_max_thrust = 0.9;
-        c->thr_min_on_time = 0.020;
-    }
-    c->base_density = 1.22;
-    c->scale_height = 8.0e3;
-    // 6U cubesat facets + two 1x2 m panels, Cd 2.2 (leoPowerAttitudeSimulator.py:272-281)
-    const double fa[8] = {0.2 * 0.3, 0.2 * 0.3, 0.1 * 0.2, 0.1 * 0.2, 0.1 * 0.3, 0.1 * 0.3, 1. * 2., 1. * 2.};
-    const double fn[8][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}, {0, 1, 0}, {0, -1, 0}};
-    const double fp[8][3] = {{0.05, 0, 0}, {0.05, 0, 0}, {0, 0.15, 0}, {0, -0.15, 0}, {0, 0, 0.1}, {0, 0, -0.1}, {0, 2., 0}, {0, 2., 0}};
-    c->n_facets = 8;
-    for (int i = 0; i < 8; ++i) {
-        c->facet_area[i] = fa[i];
-        c->facet_cd[i] = 2.2;
-        for (int k = 0; k < 3; ++k) { c->facet_normal[i][k] = fn[i][k]; c->facet_pos[i][k] = fp[i][k]; }
-    }
-    return BSK_OK;
-}
-
 int bsk_create(const bsk_config* cfg, int n_envs, int device_id, void* stream, bsk_handle** out) {
     if (!cfg || !out) return fail(BSK_EINVAL, "cfg/out is NULL");
     *out = nullptr;
     if (n_envs < 1 || n_envs > (1 << 28)) return fail(BSK_EINVAL, "n_envs must be in 1..2^28");
     int rc = validate(*cfg);
     if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(BSK_ENODEV, "no HIP device visible: libbskgpu has no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return fail(BSK_ENODEV, "device_id out of range");
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device_id));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(BSK_ENODEV, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    if ((rc = open_device(device_id, &prop))) return rc;
     DeviceGuard guard(device_id);
 
     bsk_handle* h = new bsk_handle();
@@ -1610,486 +925,6 @@ int bsk_beam_select(const double* d_reward, const uint8_t* d_reason, int n_roots
                              (hipStream_t)stream));
     return BSK_OK;
 }
-
-int bsk_policy_n_params(const bsk_policy_spec* spec) {
-    bsk::PolicyLayout lay;
-    int rc = policy_spec_layout(spec, lay);
-    return rc ? rc : lay.n_params;
-}
-
-int bsk_policy_create(const bsk_policy_spec* spec, const float* params, int device_id, bsk_policy** out) {
-    if (!out) return fail(BSK_EINVAL, "out is NULL");
-    *out = nullptr;
-    bsk::PolicyLayout lay;
-    int rc = policy_spec_layout(spec, lay);
-    if (rc) return rc;
-    if (!params) return fail(BSK_EINVAL, "params is NULL");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(BSK_ENODEV, "no HIP device visible: libbskgpu has no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return fail(BSK_ENODEV, "device_id out of range");
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device_id));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(BSK_ENODEV, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
-    DeviceGuard guard(device_id);
-    bsk_policy* p = new bsk_policy();
-    p->lay = lay;
-    p->device = device_id;
-    const unsigned long long rng0[2] = {0ull, 0ull};
-    auto init = [&]() -> int {
-        HIP_TRY(hipMalloc(&p->d_params, (size_t)lay.n_device * sizeof(float)));
-        HIP_TRY(hipMalloc(&p->d_rng, sizeof rng0));
-        HIP_COPY(hipMemcpy(p->d_rng, rng0, sizeof rng0, hipMemcpyHostToDevice));
-        return policy_upload(p, params);
-    };
-    rc = init();
-    if (rc) { bsk_policy_destroy(p); return rc; }
-    *out = p;
-    return BSK_OK;
-}
-
-int bsk_policy_set_params(bsk_policy* p, const float* params) {
-    if (!p || !params) return fail(BSK_EINVAL, "policy/params is NULL");
-    DeviceGuard guard(p->device);
-    return policy_upload(p, params);
-}
-
-void bsk_policy_destroy(bsk_policy* p) {
-    if (!p) return;
-    DeviceGuard guard(p->device);
-    if (p->d_params || p->d_rng) (void)hipDeviceSynchronize();
-    if (p->d_params) (void)hipFree(p->d_params);
-    if (p->d_rng) (void)hipFree(p->d_rng);
-    if (p->d_act) (void)hipFree(p->d_act);
-    delete p;
-}
-
-int bsk_policy_set_rng(bsk_policy* p, uint64_t seed, uint64_t draw) {
-    if (!p) return fail(BSK_EINVAL, "policy is NULL");
-    DeviceGuard guard(p->device);
-    const unsigned long long w[2] = {seed, draw};
-    HIP_SYNC(hipDeviceSynchronize());
-    HIP_COPY(hipMemcpy(p->d_rng, w, sizeof w, hipMemcpyHostToDevice));
-    return BSK_OK;
-}
-
-int bsk_policy_get_rng(bsk_policy* p, uint64_t* seed, uint64_t* draw) {
-    if (!p) return fail(BSK_EINVAL, "policy is NULL");
-    DeviceGuard guard(p->device);
-    unsigned long long w[2];
-    HIP_SYNC(hipDeviceSynchronize());
-    HIP_COPY(hipMemcpy(w, p->d_rng, sizeof w, hipMemcpyDeviceToHost));
-    if (seed) *seed = w[0];
-    if (draw) *draw = w[1];
-    return BSK_OK;
-}
-
-int bsk_policy_act(bsk_policy* p, const double* d_obs, int64_t obs_stride, int n, int64_t env_base, int mode,
-                   int32_t* d_action, float* d_logp, float* d_value, float* d_logits, int64_t out_stride, void* stream) {
-    int rc = policy_check_act(p, d_obs, obs_stride, n, env_base, mode, d_action, d_value, d_logits, out_stride);
-    if (rc) return rc;
-    DeviceGuard guard(p->device);
-    return policy_launch(p, d_obs, obs_stride, n, env_base, mode, d_action, d_logp, d_value, d_logits, out_stride, (hipStream_t)stream);
-}
-
-int bsk_policy_rollout(bsk_policy* p, bsk_handle* h, int mode, int substeps, int n_steps,
-                       double* d_obs_hist, double* d_reward_hist, uint8_t* d_reason_hist,
-                       int32_t* d_action_hist, float* d_logp_hist, float* d_value_hist) {
-    if (!p || !h) return fail(BSK_EINVAL, "policy/handle is NULL");
-    if (substeps < 1 || n_steps < 1) return fail(BSK_EINVAL, "substeps and n_steps must be >= 1");
-    if (p->device != h->device) return fail(BSK_EINVAL, "bsk_policy_rollout: the policy and the handle live on different devices");
-    int rc = policy_check_act(p, h->d_obs, h->ostride, h->n, (int64_t)h->env_base, mode, h->d_act, d_value_hist, nullptr, 0);
-    if (rc) return rc;
-    if (h->cfg.gravity_model == BSK_GRAV_SH && !h->sp.sh_tab)
-        return fail(BSK_EINVAL, "BSK_GRAV_SH: call bsk_set_gravity_sh before stepping");
-    if ((h->cfg.flags & BSK_FLAG_AUTO_RESET) && h->n_pool == 0)
-        return fail(BSK_EINVAL, "BSK_FLAG_AUTO_RESET: call bsk_set_ic_pool before stepping");
-    DeviceGuard guard(h->device);
-    if (!d_action_hist && p->act_cap < h->n) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        HIP_TRY(hipStreamIsCapturing(h->stream, &cap));
-        if (cap != hipStreamCaptureStatusNone)
-            return fail(BSK_EINVAL, "bsk_policy_rollout: the first rollout without d_action_hist allocates the policy's scratch row and "
-                                    "cannot be captured; make one such call outside the capture first");
-        if (p->d_act) {
-            HIP_SYNC(hipDeviceSynchronize());                   // (a queued rollout may still use the smaller row)
-            (void)hipFree(p->d_act);
-            p->d_act = nullptr;
-            p->act_cap = 0;
-        }
-        HIP_TRY(hipMalloc(&p->d_act, (size_t)h->ostride * sizeof(int)));
-        p->act_cap = (int)h->ostride;
-    }
-    const size_t n = (size_t)h->n;
-    for (int t = 0; t < n_steps; ++t) {
-        int32_t* act = d_action_hist ? d_action_hist + t * n : p->d_act;
-        rc = policy_launch(p, h->d_obs, h->ostride, h->n, (int64_t)h->env_base, mode, act, d_logp_hist ? d_logp_hist + t * n : nullptr,
-                           d_value_hist ? d_value_hist + t * n : nullptr, nullptr, 0, h->stream);
-        if (rc) return rc;
-        if ((rc = do_step(h, act, substeps, 1))) return rc;
-        if (d_obs_hist || d_reward_hist || d_reason_hist)
-            HIP_TRY(bsk::launch_hist_row(h->d_obs, h->d_reward, h->d_reason, h->ostride, h->n, d_obs_hist ? d_obs_hist + t * 5 * n : nullptr,
-                                         d_reward_hist ? d_reward_hist + t * n : nullptr, d_reason_hist ? d_reason_hist + t * n : nullptr,
-                                         h->stream));
-    }
-    return BSK_OK;
-}
-
-int bsk_population_create(const bsk_policy_spec* spec, int n_members, const float* params, int device_id, bsk_population** out) {
-    if (!out) return fail(BSK_EINVAL, "out is NULL");
-    *out = nullptr;
-    bsk::PolicyLayout lay;
-    int rc = policy_spec_layout(spec, lay);
-    if (rc) return rc;
-    if (n_members < 1 || n_members > (1 << 22)) return fail(BSK_EINVAL, "n_members must be in 1..2^22");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(BSK_ENODEV, "no HIP device visible: libbskgpu has no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return fail(BSK_ENODEV, "device_id out of range");
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device_id));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(BSK_ENODEV, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
-    DeviceGuard guard(device_id);
-    bsk_population* p = new bsk_population();
-    p->lay = lay;
-    p->device = device_id;
-    p->n_members = n_members;
-    const unsigned long long rng0[2] = {0ull, 0ull};
-    auto init = [&]() -> int {
-        const size_t bytes = (size_t)n_members * (size_t)lay.n_device * sizeof(float);
-        HIP_TRY(hipMalloc(&p->d_params, bytes));
-        HIP_TRY(hipMalloc(&p->d_rng, sizeof rng0));
-        HIP_COPY(hipMemcpy(p->d_rng, rng0, sizeof rng0, hipMemcpyHostToDevice));
-        if (params) return bsk_population_set_params(p, params);
-        HIP_TRY(hipMemset(p->d_params, 0, bytes));        // (all-zero members pack to all-zero device blocks)
-        HIP_SYNC(hipDeviceSynchronize());
-        return BSK_OK;
-    };
-    rc = init();
-    if (rc) { bsk_population_destroy(p); return rc; }
-    *out = p;
-    return BSK_OK;
-}
-
-void bsk_population_destroy(bsk_population* p) {
-    if (!p) return;
-    DeviceGuard guard(p->device);
-    if (p->d_params || p->d_rng || p->d_scratch) (void)hipDeviceSynchronize();
-    if (p->d_params) (void)hipFree(p->d_params);
-    if (p->d_rng) (void)hipFree(p->d_rng);
-    if (p->d_scratch) (void)hipFree(p->d_scratch);
-    delete p;
-}
-
-int bsk_population_set_params(bsk_population* p, const float* params) {
-    if (!p || !params) return fail(BSK_EINVAL, "population/params is NULL");
-    DeviceGuard guard(p->device);
-    const size_t nd = (size_t)p->lay.n_device;
-    std::vector<float> all((size_t)p->n_members * nd), one;
-    for (int m = 0; m < p->n_members; ++m) {
-        bsk::policy_pack(p->lay, params + (size_t)m * (size_t)p->lay.n_params, one);
-        std::memcpy(all.data() + (size_t)m * nd, one.data(), nd * sizeof(float));
-    }
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old parameters)
-    HIP_COPY(hipMemcpy(p->d_params, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
-    return BSK_OK;
-}
-
-int bsk_population_set_params_device(bsk_population* p, const float* d_params, int first, int count, void* stream) {
-    if (!p || !d_params) return fail(BSK_EINVAL, "population/d_params is NULL");
-    if (first < 0 || count < 1 || first > p->n_members - count)
-        return fail(BSK_EINVAL, "first / count must name members inside the population (first >= 0, count >= 1, first + count <= n_members)");
-    DeviceGuard guard(p->device);
-    HIP_TRY(bsk::launch_policy_pack(p->lay, d_params, p->d_params + (size_t)first * (size_t)p->lay.n_device, count, (hipStream_t)stream));
-    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
-}
-
-int bsk_population_get_member(bsk_population* p, int member, float* params) {
-    if (!p || !params) return fail(BSK_EINVAL, "population/params is NULL");
-    if (member < 0 || member >= p->n_members) return fail(BSK_EINVAL, "member must be in 0..n_members-1");
-    DeviceGuard guard(p->device);
-    std::vector<float> dev((size_t)p->lay.n_device);
-    HIP_SYNC(hipDeviceSynchronize());
-    HIP_COPY(hipMemcpy(dev.data(), p->d_params + (size_t)member * dev.size(), dev.size() * sizeof(float), hipMemcpyDeviceToHost));
-    bsk::policy_unpack(p->lay, dev.data(), params);
-    return BSK_OK;
-}
-
-int bsk_population_set_rng(bsk_population* p, uint64_t seed, uint64_t draw) {
-    if (!p) return fail(BSK_EINVAL, "population is NULL");
-    DeviceGuard guard(p->device);
-    const unsigned long long w[2] = {seed, draw};
-    HIP_SYNC(hipDeviceSynchronize());
-    HIP_COPY(hipMemcpy(p->d_rng, w, sizeof w, hipMemcpyHostToDevice));
-    return BSK_OK;
-}
-
-int bsk_population_get_rng(bsk_population* p, uint64_t* seed, uint64_t* draw) {
-    if (!p) return fail(BSK_EINVAL, "population is NULL");
-    DeviceGuard guard(p->device);
-    unsigned long long w[2];
-    HIP_SYNC(hipDeviceSynchronize());
-    HIP_COPY(hipMemcpy(w, p->d_rng, sizeof w, hipMemcpyDeviceToHost));
-    if (seed) *seed = w[0];
-    if (draw) *draw = w[1];
-    return BSK_OK;
-}
-
-int bsk_population_act(bsk_population* p, const double* d_obs, int64_t obs_stride, int n, int envs_per_member, int64_t env_base, int mode,
-                       int32_t* d_action, float* d_logp, float* d_value, float* d_logits, int64_t out_stride, void* stream) {
-    int rc = population_check_act(p, d_obs, obs_stride, n, envs_per_member, env_base, mode, d_action, d_value, d_logits, out_stride);
-    if (rc) return rc;
-    DeviceGuard guard(p->device);
-    return population_launch(p, d_obs, obs_stride, n, envs_per_member, env_base, mode, d_action, d_logp, d_value, d_logits, out_stride,
-                             (hipStream_t)stream);
-}
-
-int bsk_population_rollout(bsk_population* p, bsk_handle* h, int mode, int substeps, int n_steps, double gamma,
-                           double* d_obs_hist, double* d_reward_hist, uint8_t* d_reason_hist,
-                           int32_t* d_action_hist, float* d_logp_hist, float* d_value_hist,
-                           double* d_env_value, int32_t* d_env_len, double* d_fitness, double* d_mean_len) {
-    if (!p || !h) return fail(BSK_EINVAL, "population/handle is NULL");
-    if (substeps < 1 || n_steps < 1) return fail(BSK_EINVAL, "substeps and n_steps must be >= 1");
-    if (!std::isfinite(gamma)) return fail(BSK_EINVAL, "gamma must be finite");
-    if (p->device != h->device) return fail(BSK_EINVAL, "bsk_population_rollout: the population and the handle live on different devices");
-    if (h->n % p->n_members != 0)
-        return fail(BSK_EINVAL, "bsk_population_rollout: the handle's n_envs must be n_members * envs_per_member");
-    const int E = h->n / p->n_members;
-    int rc = population_check_act(p, h->d_obs, h->ostride, h->n, E, (int64_t)h->env_base, mode, h->d_act, d_value_hist, nullptr, 0);
-    if (rc) return rc;
-    if (h->cfg.gravity_model == BSK_GRAV_SH && !h->sp.sh_tab)
-        return fail(BSK_EINVAL, "BSK_GRAV_SH: call bsk_set_gravity_sh before stepping");
-    if ((h->cfg.flags & BSK_FLAG_AUTO_RESET) && h->n_pool == 0)
-        return fail(BSK_EINVAL, "BSK_FLAG_AUTO_RESET: call bsk_set_ic_pool before stepping");
-    DeviceGuard guard(h->device);
-    if (p->scratch_cap < h->n) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        HIP_TRY(hipStreamIsCapturing(h->stream, &cap));
-        if (cap != hipStreamCaptureStatusNone)
-            return fail(BSK_EINVAL, "bsk_population_rollout: the first rollout of a size allocates the population's scratch rows and "
-                                    "cannot be captured; make one such call outside the capture first");
-        if (p->d_scratch) {
-            HIP_SYNC(hipDeviceSynchronize());                   // (a queued rollout may still use the smaller rows)
-            (void)hipFree(p->d_scratch);
-            p->d_scratch = nullptr;
-            p->scratch_cap = 0;
-        }
-        const size_t n = (size_t)h->n;                          // (a multiple of 64: every row below starts 8-byte aligned)
-        HIP_TRY(hipMalloc(&p->d_scratch, n * (8 + 8 + 4 + 4 + 1)));
-        char* at = (char*)p->d_scratch;
-        p->acc.v = (double*)at; at += n * 8;
-        p->acc.g = (double*)at; at += n * 8;
-        p->acc.len = (int*)at; at += n * 4;
-        p->d_act = (int*)at; at += n * 4;
-        p->acc.alive = (unsigned char*)at;
-        p->scratch_cap = h->n;
-    }
-    const size_t n = (size_t)h->n;
-    const bool want_fitness = d_env_value || d_env_len || d_fitness || d_mean_len;
-    for (int t = 0; t < n_steps; ++t) {
-        int32_t* act = d_action_hist ? d_action_hist + t * n : p->d_act;
-        rc = population_launch(p, h->d_obs, h->ostride, h->n, E, (int64_t)h->env_base, mode, act, d_logp_hist ? d_logp_hist + t * n : nullptr,
-                               d_value_hist ? d_value_hist + t * n : nullptr, nullptr, 0, h->stream);
-        if (rc) return rc;
-        if ((rc = do_step(h, act, substeps, 1))) return rc;
-        double* obs_row = d_obs_hist ? d_obs_hist + t * 5 * n : nullptr;
-        double* reward_row = d_reward_hist ? d_reward_hist + t * n : nullptr;
-        uint8_t* reason_row = d_reason_hist ? d_reason_hist + t * n : nullptr;
-        // the history rows and the value rule in ONE launch; with no fitness output asked for, the rows alone (or nothing)
-        if (want_fitness)
-            HIP_TRY(bsk::launch_fitness_row(h->d_obs, h->d_reward, h->d_reason, h->ostride, h->n, obs_row, reward_row, reason_row, p->acc,
-                                            gamma, t == 0, h->stream));
-        else
-            HIP_TRY(bsk::launch_hist_row(h->d_obs, h->d_reward, h->d_reason, h->ostride, h->n, obs_row, reward_row, reason_row, h->stream));
-    }
-    HIP_TRY(bsk::launch_fitness_join(p->acc, p->n_members, E, d_env_value, d_env_len, d_fitness, d_mean_len, h->stream));
-    return BSK_OK;
-}
-
-int bsk_es_create(const bsk_policy_spec* spec, int n_members, const float* theta, double sigma, double lr, int frozen, uint64_t seed,
-                  int device_id, bsk_es** out) {
-    if (!out) return fail(BSK_EINVAL, "out is NULL");
-    *out = nullptr;
-    bsk::PolicyLayout lay;
-    int rc = policy_spec_layout(spec, lay);
-    if (rc) return rc;
-    if (n_members < 2 || n_members > 65536 || n_members % 2 != 0)
-        return fail(BSK_EINVAL, "bsk_es_create: n_members must be even and in 2..65536 (the ranking compares every pair of members)");
-    if (!std::isfinite(sigma) || !(sigma > 0.0)) return fail(BSK_EINVAL, "bsk_es_create: sigma must be finite and positive");
-    if (!std::isfinite(lr)) return fail(BSK_EINVAL, "bsk_es_create: lr must be finite");
-    if (frozen < 0 || frozen > lay.n_params) return fail(BSK_EINVAL, "bsk_es_create: frozen must be in 0..n_params");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(BSK_ENODEV, "no HIP device visible: libbskgpu has no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return fail(BSK_ENODEV, "device_id out of range");
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device_id));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(BSK_ENODEV, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
-    DeviceGuard guard(device_id);
-    bsk_es* es = new bsk_es();
-    es->lay = lay;
-    es->device = device_id;
-    es->n_members = n_members;
-    es->sigma = sigma;
-    es->lr = lr;
-    es->frozen = frozen;
-    const unsigned long long state0[2] = {seed, 0ull};
-    std::vector<double> theta0((size_t)lay.n_params, 0.0);
-    if (theta)
-        for (int j = 0; j < lay.n_params; ++j) theta0[(size_t)j] = (double)theta[j];
-    auto init = [&]() -> int {
-        HIP_TRY(hipMalloc(&es->d_state, sizeof state0));
-        HIP_TRY(hipMalloc(&es->d_theta, theta0.size() * sizeof(double)));
-        HIP_TRY(hipMalloc(&es->d_w, (size_t)(n_members / 2) * sizeof(double)));
-        HIP_COPY(hipMemcpy(es->d_state, state0, sizeof state0, hipMemcpyHostToDevice));
-        HIP_COPY(hipMemcpy(es->d_theta, theta0.data(), theta0.size() * sizeof(double), hipMemcpyHostToDevice));
-        return BSK_OK;
-    };
-    rc = init();
-    if (rc) { bsk_es_destroy(es); return rc; }
-    *out = es;
-    return BSK_OK;
-}
-
-void bsk_es_destroy(bsk_es* es) {
-    if (!es) return;
-    DeviceGuard guard(es->device);
-    if (es->d_state || es->d_theta || es->d_w || es->d_adam) (void)hipDeviceSynchronize();
-    if (es->d_state) (void)hipFree(es->d_state);
-    if (es->d_theta) (void)hipFree(es->d_theta);
-    if (es->d_w) (void)hipFree(es->d_w);
-    if (es->d_adam) (void)hipFree(es->d_adam);
-    delete es;
-}
-
-static bsk::EsArgs es_args(const bsk_es* es) {
-    bsk::EsArgs a;
-    a.state = es->d_state;
-    a.theta = es->d_theta;
-    a.sigma = es->sigma;
-    a.frozen = es->frozen;
-    a.pairs = es->n_members / 2;
-    return a;
-}
-
-int bsk_es_ask(bsk_es* es, bsk_population* pop, void* stream) {
-    if (!es || !pop) return fail(BSK_EINVAL, "es/population is NULL");
-    if (pop->n_members != es->n_members) return fail(BSK_EINVAL, "bsk_es_ask: the population's n_members differs from the optimiser's");
-    if (std::memcmp(&pop->lay, &es->lay, sizeof(bsk::PolicyLayout)) != 0)      // (all-int, value-initialised: policy_layout)
-        return fail(BSK_EINVAL, "bsk_es_ask: the population's spec differs from the optimiser's");
-    if (pop->device != es->device) return fail(BSK_EINVAL, "bsk_es_ask: the optimiser and the population live on different devices");
-    DeviceGuard guard(es->device);
-    HIP_TRY(bsk::launch_es_ask(es->lay, es_args(es), pop->d_params, (hipStream_t)stream));
-    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
-}
-
-int bsk_es_tell(bsk_es* es, const double* d_fitness, void* stream) {
-    if (!es || !d_fitness) return fail(BSK_EINVAL, "es/d_fitness is NULL");
-    DeviceGuard guard(es->device);
-    HIP_TRY(bsk::launch_es_rank(d_fitness, es->n_members, es->d_w, (hipStream_t)stream));
-    if (es->optimizer == BSK_ES_ADAM) {
-        const size_t np = (size_t)es->lay.n_params;
-        bsk::EsAdam ad;
-        ad.m = es->d_adam;
-        ad.v = es->d_adam + np;
-        ad.beta_pow = es->d_adam + 2 * np;
-        ad.beta1 = es->beta1; ad.beta2 = es->beta2;
-        ad.a1 = 1.0 - es->beta1; ad.a2 = 1.0 - es->beta2;
-        ad.eps = es->eps; ad.weight_decay = es->weight_decay;
-        ad.cg = 1.0 / ((double)es->n_members * es->sigma);
-        ad.lr = es->lr;
-        HIP_TRY(bsk::launch_es_tell_adam(es_args(es), es->lay.n_params, es->d_w, ad, (hipStream_t)stream));
-        HIP_TRY(bsk::launch_es_advance_adam(es->d_state, es->d_adam + 2 * np, es->beta1, es->beta2, (hipStream_t)stream));
-        return BSK_OK;
-    }
-    const double c = es->lr / ((double)es->n_members * es->sigma);
-    HIP_TRY(bsk::launch_es_tell(es_args(es), es->lay.n_params, es->d_w, c, (hipStream_t)stream));
-    HIP_TRY(bsk::launch_es_advance(es->d_state, (hipStream_t)stream));
-    return BSK_OK;
-}
-
-int bsk_es_get_state(bsk_es* es, double* theta, uint64_t* generation) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    DeviceGuard guard(es->device);
-    HIP_SYNC(hipDeviceSynchronize());
-    if (theta) HIP_COPY(hipMemcpy(theta, es->d_theta, (size_t)es->lay.n_params * sizeof(double), hipMemcpyDeviceToHost));
-    if (generation) {
-        unsigned long long w[2];
-        HIP_COPY(hipMemcpy(w, es->d_state, sizeof w, hipMemcpyDeviceToHost));
-        *generation = w[1];
-    }
-    return BSK_OK;
-}
-
-int bsk_es_set_state(bsk_es* es, const double* theta, uint64_t generation) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    DeviceGuard guard(es->device);
-    const unsigned long long g = generation;
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old state)
-    if (theta) HIP_COPY(hipMemcpy(es->d_theta, theta, (size_t)es->lay.n_params * sizeof(double), hipMemcpyHostToDevice));
-    HIP_COPY(hipMemcpy(es->d_state + 1, &g, sizeof g, hipMemcpyHostToDevice));
-    return BSK_OK;
-}
-
-int bsk_es_generation_device(bsk_es* es, const uint64_t** d_generation) {
-    if (!es || !d_generation) return fail(BSK_EINVAL, "es/d_generation is NULL");
-    *d_generation = (const uint64_t*)(es->d_state + 1);
-    return BSK_OK;
-}
-
-int bsk_es_set_optimizer(bsk_es* es, int kind, double beta1, double beta2, double eps, double weight_decay) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (kind != BSK_ES_SGD && kind != BSK_ES_ADAM) return fail(BSK_EINVAL, "bsk_es_set_optimizer: kind must be BSK_ES_SGD or BSK_ES_ADAM");
-    if (kind == BSK_ES_ADAM) {
-        if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
-            return fail(BSK_EINVAL, "bsk_es_set_optimizer: beta1 and beta2 must be in [0, 1)");
-        if (!std::isfinite(eps) || !(eps > 0.0)) return fail(BSK_EINVAL, "bsk_es_set_optimizer: eps must be finite and positive");
-        if (!std::isfinite(weight_decay) || weight_decay < 0.0)
-            return fail(BSK_EINVAL, "bsk_es_set_optimizer: weight_decay must be finite and not negative");
-    }
-    DeviceGuard guard(es->device);
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued tells still use the old rule and the old moments)
-    if (kind == BSK_ES_SGD) {
-        es->optimizer = BSK_ES_SGD;
-        return BSK_OK;
-    }
-    const size_t np = (size_t)es->lay.n_params;
-    if (!es->d_adam) HIP_TRY(hipMalloc(&es->d_adam, (2 * np + 2) * sizeof(double)));
-    const double one[2] = {1.0, 1.0};
-    HIP_TRY(hipMemset(es->d_adam, 0, 2 * np * sizeof(double)));
-    HIP_COPY(hipMemcpy(es->d_adam + 2 * np, one, sizeof one, hipMemcpyHostToDevice));
-    es->optimizer = BSK_ES_ADAM;
-    es->beta1 = beta1; es->beta2 = beta2; es->eps = eps; es->weight_decay = weight_decay;
-    return BSK_OK;
-}
-
-int bsk_es_get_moments(bsk_es* es, double* m, double* v, double* beta_pow) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (es->optimizer != BSK_ES_ADAM) return fail(BSK_EINVAL, "bsk_es_get_moments: the optimiser is BSK_ES_SGD, it has no moments");
-    DeviceGuard guard(es->device);
-    const size_t np = (size_t)es->lay.n_params;
-    HIP_SYNC(hipDeviceSynchronize());
-    if (m) HIP_COPY(hipMemcpy(m, es->d_adam, np * sizeof(double), hipMemcpyDeviceToHost));
-    if (v) HIP_COPY(hipMemcpy(v, es->d_adam + np, np * sizeof(double), hipMemcpyDeviceToHost));
-    if (beta_pow) HIP_COPY(hipMemcpy(beta_pow, es->d_adam + 2 * np, 2 * sizeof(double), hipMemcpyDeviceToHost));
-    return BSK_OK;
-}
-
-int bsk_es_set_moments(bsk_es* es, const double* m, const double* v, const double* beta_pow) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (es->optimizer != BSK_ES_ADAM) return fail(BSK_EINVAL, "bsk_es_set_moments: the optimiser is BSK_ES_SGD, it has no moments");
-    DeviceGuard guard(es->device);
-    const size_t np = (size_t)es->lay.n_params;
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old moments)
-    if (m) HIP_COPY(hipMemcpy(es->d_adam, m, np * sizeof(double), hipMemcpyHostToDevice));
-    if (v) HIP_COPY(hipMemcpy(es->d_adam + np, v, np * sizeof(double), hipMemcpyHostToDevice));
-    if (beta_pow) HIP_COPY(hipMemcpy(es->d_adam + 2 * np, beta_pow, 2 * sizeof(double), hipMemcpyHostToDevice));
-    return BSK_OK;
-}
-
 int bsk_set_env_base(bsk_handle* h, int64_t env_base) {
     if (!h) return fail(BSK_EINVAL, "handle is NULL");
     if (env_base < 0 || env_base > 0xFFFFFFFFll) return fail(BSK_EINVAL, "env_base must be in 0..2^32-1");

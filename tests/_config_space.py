@@ -2,7 +2,7 @@
 
 ``bsk_default_config`` is symmetric exactly where an indexing mistake would show (all ``js`` equal, all ``facet_cd`` 2.2, the
 +/- facet pairs of equal area, two zero components in ``sigma_R0N`` and in ``panel_normal``, identity ``ctrl_axes``,
-``failure_penalty = 1``), and ``build_params`` (csrc/bsk_capi.hip) hands the kernels several derived copies of most constants.
+``failure_penalty = 1``), and ``build_params`` (csrc/bsk_config.hip) hands the kernels several derived copies of most constants.
 This module says, for EVERY field of ``_lib.BskConfig._fields_``:
 
 * its kind - ``abi`` (bookkeeping of the C-ABI), ``structure`` (schedules, switches and geometry that select a kernel form or a
@@ -227,7 +227,7 @@ def _one_storage(cfg, rng, ctx):
 
 
 # ---------------------------------------------------------------------------------------------------------------- forms
-# the kernel forms that read a copy of a field at each level (csrc/bsk_capi.hip: build_params; csrc/bsk_device.hpp)
+# the kernel forms that read a copy of a field at each level (csrc/bsk_config.hip: build_params; csrc/bsk_device.hpp)
 FORMS = {
     "bare": ("single", "fullhub", "ldss", "rollout"),
     "power": ("single", "fullhub", "pair"),

@@ -626,7 +626,7 @@ def main():
     def full_inertia_edit(cfg):
         """a GENERAL hub - symmetric positive-definite inertia matrix with products of inertia, one wheel axis tilted by nine
         degrees - in the full scenario minus desaturation: the case that pins the step kernels' general-inertia family
-        (3 x 3 back-substitution, full W = sum Js g g^T; csrc/bsk_capi.hip picks it whenever an off-diagonal is non-zero)"""
+        (3 x 3 back-substitution, full W = sum Js g g^T; csrc/bsk_config.hip picks it whenever an off-diagonal is non-zero)"""
         scenario_edit(cfg)
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from helpers import general_hub       # (an edit of the INPUT constants, shared with the tests that rebuild the config)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate tests/golden/sh70_field.json: degree-70 spherical-harmonic gravity by a method independent of Pines.
 
-The oracle (oracle/bsk_oracle.c), the kernels' table builders (csrc/bsk_capi.hip) and the golden trajectories
+The oracle (oracle/bsk_oracle.c), the kernels' table builders (csrc/bsk_config.hip) and the golden trajectories
 (make_golden.py) all evaluate Pines' recursion with the same N1 constants, so an error common to them passes every
 comparison between them.  This script shares none of it: the potential is summed in spherical coordinates from
 unnormalised associated Legendre functions P_lm(sin phi) of the integer-coefficient upward recursion (no Condon-Shortley

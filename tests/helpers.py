@@ -51,7 +51,7 @@ def cfg_for_case(case):
 
 
 def general_hub(cfg, rng=None, inertia=True, tilt=True):
-    """Edit ``cfg`` so that the step kernels with a GENERAL inertia matrix run (``DIAG = false``: csrc/bsk_capi.hip selects
+    """Edit ``cfg`` so that the step kernels with a GENERAL inertia matrix run (``DIAG = false``: csrc/bsk_config.hip selects
     them whenever an off-diagonal of I_sc or of I_sc - sum Js g g^T is non-zero).  ``inertia``: a symmetric positive-definite
     I_sc with products of inertia of 1 - 20 % of the smallest diagonal entry (the reference's hub is the diagonal cuboid of
     leoPowerAttitudeSimulator.py:244-249: this is surface beyond it that the ABI accepts).  ``tilt``: one wheel's spin axis
@@ -137,3 +137,30 @@ def load_sh70_fixture():
     doc["v"] = np.array([s["v"] for s in sc]).T.copy()
     doc["after"] = {int(k): np.array([[float(v) for v in s["after_ticks"][k]] for s in sc]).T.copy() for k in ("1", "10")}
     return doc
+
+
+def create_each(device_id, hidden=(16,), n_members=2, n_envs=64):
+    """``bsk_create``, ``bsk_policy_create``, ``bsk_population_create`` and ``bsk_es_create`` with valid arguments on ``device_id``
+    -> [(name, return code, *out, bsk_last_error's text)], *out = None where the call left NULL (it goes in as a non-NULL value).
+    ``hidden``: (16,) is the smallest network with a hidden layer that the library admits (16 ... 128 units, in multiples of 16) - with
+    a narrower one the spec is refused, BSK_EINVAL, before the device is looked at."""
+    import ctypes as C
+
+    from basilisk_env_amd import _lib
+    from basilisk_env_amd import policy as P
+    from basilisk_env_amd.simulators.dynamics import default_config
+    lib = _lib.load()
+    cfg = default_config(4, _lib.GRAV_PM_J2)
+    spec = P.check_spec(hidden)
+    cs = P.c_spec(spec)
+    params = np.zeros((n_members, P.n_params(spec)), np.float32)
+    calls = (("bsk_create", lambda h: lib.bsk_create(C.byref(cfg), n_envs, device_id, None, C.byref(h))),
+             ("bsk_policy_create", lambda h: lib.bsk_policy_create(C.byref(cs), params[0].ctypes.data, device_id, C.byref(h))),
+             ("bsk_population_create", lambda h: lib.bsk_population_create(C.byref(cs), n_members, params.ctypes.data, device_id, C.byref(h))),
+             ("bsk_es_create", lambda h: lib.bsk_es_create(C.byref(cs), n_members, params[0].ctypes.data, 0.1, 0.05, 10, 0, device_id, C.byref(h))))
+    out = []
+    for name, call in calls:
+        h = C.c_void_p(0xDEAD)
+        rc = call(h)
+        out.append((name, rc, h.value, lib.bsk_last_error().decode()))
+    return out

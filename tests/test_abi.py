@@ -129,13 +129,18 @@ def test_product_library_reads_no_measurement_overrides():
     if os.path.exists(tun):
         got = set(m.decode() for m in re.findall(rb"BSKGPU_[A-Z_]+", open(tun, "rb").read()))
         assert {"BSKGPU_STRIDE_PAD", "BSKGPU_OSTRIDE_PAD", "BSKGPU_BLOCK", "BSKGPU_PAIR_SHIFT"} <= got
-    src = open(os.path.join(root, "basilisk_env_amd", "csrc", "bsk_capi.hip")).read()
-    outside, depth = [], 0
-    for line in src.splitlines():
-        if line.startswith("#if BSK_TUNABLES"):
-            depth += 1
-        elif line.startswith("#endif") and depth:
-            depth -= 1
-        elif "getenv" in line and not depth:
-            outside.append(line.strip())
+    import glob
+    csrc = os.path.join(root, "basilisk_env_amd", "csrc")
+    units = sorted(glob.glob(os.path.join(csrc, "bsk_capi*.hip"))) + [os.path.join(csrc, "bsk_config.hip")]
+    assert len(units) >= 3, units
+    outside = []
+    for unit in units:             # every translation unit of the C-ABI: three over all of them
+        depth = 0
+        for line in open(unit).read().splitlines():
+            if line.startswith("#if BSK_TUNABLES"):
+                depth += 1
+            elif line.startswith("#endif") and depth:
+                depth -= 1
+            elif "getenv" in line and not depth:
+                outside.append(line.strip())
     assert len(outside) == 3, outside

@@ -39,7 +39,7 @@ def test_every_config_field_is_classified():
 @pytest.mark.parametrize("n_rw", [0, 3, 4])
 def test_draws_are_asymmetric_and_land_in_their_family(n_rw, hub):
     """What the default hides: per-wheel js, unequal facet pairs, full vectors, a general map - and the hub kind build_params
-    will see (csrc/bsk_capi.hip: every off-diagonal of I and of I - sum js g g^T exactly zero, or not)."""
+    will see (csrc/bsk_config.hip: every off-diagonal of I and of I - sum js g g^T exactly zero, or not)."""
     d = default_config(n_rw, GRAV_PM_J2)
     for seed in range(20):
         c = CS.draw_config(np.random.default_rng(seed), n_rw, GRAV_PM_J2, "full", hub)

@@ -1,6 +1,6 @@
 """GPU: every physical constant of ``bsk_config`` away from its default, in every kernel form, against the CPU oracle.
 
-``build_params`` (csrc/bsk_capi.hip) hands the kernels several derived copies of most constants (``js`` alone lives in
+``build_params`` (csrc/bsk_config.hip) hands the kernels several derived copies of most constants (``js`` alone lives in
 ``StepParams.js``, ``ColdCfg.js`` and four rows of the broadcast table), different kernel forms read different copies, and
 ``bsk_default_config`` is symmetric exactly where an indexing mistake would show.  tests/_config_space.py classifies every field
 and says how to draw it asymmetrically; tests/test_config_space_host.py shows that the oracle agrees with the 50-digit model over

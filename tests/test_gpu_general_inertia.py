@@ -1,6 +1,6 @@
 """GPU: the step kernels with a GENERAL hub (``DIAG = false``) through the C-ABI against the CPU oracle and a 50-digit golden.
 
-csrc/bsk_capi.hip selects the ``DIAG = false`` instantiations whenever an off-diagonal of I_sc or of I_sc - sum Js g g^T is
+csrc/bsk_config.hip selects the ``DIAG = false`` instantiations whenever an off-diagonal of I_sc or of I_sc - sum Js g g^T is
 non-zero (3 x 3 back-substitution, full W = sum Js g g^T, nine-entry matrices in the kernel arguments): half of the compiled
 step kernels.  The reference's own hub is the diagonal cuboid of leoPowerAttitudeSimulator.py:244-249, so every other GPU test
 runs the diagonal family; this file puts the general one under the oracle at every feature level (bare, LDS-scratch, power,

@@ -603,3 +603,63 @@ def test_c_consumer_closes_the_loop_like_the_python_binding(tmp_path):
     assert float(got[7]) == sum(prop.get_obs()[0].ravel().tolist())
     prop.close()
     pol.close()
+
+
+def test_every_create_refuses_a_device_id_past_the_last_alike():
+    """The admission of a device is written once (csrc/bsk_capi.hip: open_device) behind bsk_create, bsk_policy_create,
+    bsk_population_create and bsk_es_create: BSK_ENODEV, *out left NULL and one text for all four.  Nothing is launched."""
+    from helpers import create_each
+    got = create_each(_hip.device_count(), hidden=(16,), n_members=2, n_envs=64)
+    assert len(got) == 4
+    for name, rc, out, text in got:
+        assert rc == -2 and out is None and text == "device_id out of range", (name, rc, out, text)
+
+
+def test_population_and_policy_rollouts_enqueue_the_same_loop():
+    """The two rollouts share one per-step loop (csrc/bsk_capi_policy.hip: rollout_steps): a population of two members that both hold
+    one policy's parameters leaves what that policy leaves on the same handle from the same reset, bit for bit - history rows and
+    final handle state - with every history output given (the population's rows then come out of the fitness launch, the policy's out
+    of the history launch) and with none given, no fitness output either (no third launch at all); and neither call copies or
+    synchronises once a first one has allocated its scratch.  (tests/test_gpu_population.py holds a population of distinct members
+    to separate policy rollouts on handles of E envs, all outputs given, and its rollout's host traffic in that configuration; the
+    configuration without outputs, and the policy's side of the counters at this shape, are held here.)"""
+    n, T, k = 128, 3, 2
+    spec, params = _loop_policy((16,), (16,), 77)            # (the narrowest hidden layer there is)
+    pol = P.DevicePolicy(spec, params)
+    pop = P.PolicyPopulation(spec, np.stack([params, params]))
+    prop = BatchedPropagator(default_config(4, GRAV_PM_J2), n)
+    ic = sample_ic_batch(n, 4, seed=21)
+    rows = (("obs", 40, np.float64, 5), ("reward", 8, np.float64, 1), ("reason", 1, np.uint8, 1), ("action", 4, np.int32, 1),
+            ("logp", 4, np.float32, 1), ("value", 4, np.float32, 1))
+    bufs = {key: _hip.DeviceBuffer(T * n * size, 0) for key, size, _, _ in rows}
+    fit = {"d_env_value": _hip.DeviceBuffer(8 * n, 0), "d_env_len": _hip.DeviceBuffer(4 * n, 0), "d_fitness": _hip.DeviceBuffer(16, 0),
+           "d_mean_len": _hip.DeviceBuffer(16, 0)}
+    prop.reset(ic)
+    pol.rollout_device(prop, 1, k, "greedy")               # (the first calls allocate the scratch rows)
+    pop.rollout_device(prop, 1, k, "greedy")
+    for given in (True, False):
+        left = []
+        for who in (pop, pol):
+            prop.reset(ic)
+            args = [bufs[key].ptr for key, _, _, _ in rows] if given else []
+            kw = {key: b.ptr for key, b in fit.items()} if given and who is pop else {}
+            c0 = BatchedPropagator.debug_counters()
+            if who is pop:
+                who.rollout_device(prop, T, k, "greedy", 0.97, *args, **kw)
+            else:
+                who.rollout_device(prop, T, k, "greedy", *args)
+            assert BatchedPropagator.debug_counters() == c0, (given, who)       # no copy, no synchronisation
+            prop.sync()
+            hist = {key: _download(bufs[key].ptr, dt, T * n * m) for key, _, dt, m in rows} if given else {}
+            left.append((hist, _envs(prop)))
+        for part in (0, 1):
+            assert set(left[0][part]) == set(left[1][part])
+            for key in left[0][part]:
+                a, b = left[0][part][key], left[1][part][key]
+                assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (given, key)
+        if given:
+            assert len(set(left[0][0]["action"].tolist())) > 1              # (not a loop under one constant action)
+    for x in list(bufs.values()) + list(fit.values()):
+        x.free()
+    for x in (prop, pol, pop):
+        x.close()
