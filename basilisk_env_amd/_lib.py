@@ -91,6 +91,57 @@ EXPORTS = [
     "bsk_profile_begin", "bsk_profile_set_stride", "bsk_profile_end", "bsk_profile_end_samples", "bsk_calibrate_fp64", "bsk_kernel_info", "bsk_last_error", "bsk_version",
 ]
 
+
+def _signatures():
+    """Every export of include/bskgpu.h -> (argtypes, restype); ``rc`` is the status that all return but the two strings and the
+    four destroys."""
+    P, vp, rc, i, i64, u64, f64 = C.POINTER, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_uint64, C.c_double
+    spec = P(BskPolicySpec)
+    return {
+        "bsk_last_error": ([], C.c_char_p), "bsk_version": ([], C.c_char_p),
+        "bsk_default_config": ([P(BskConfig), i, i], rc), "bsk_create": ([P(BskConfig), i, i, vp, P(vp)], rc),
+        "bsk_destroy": ([vp], None), "bsk_set_gravity_sh": ([vp, i, vp, vp], rc), "bsk_reset": ([vp, vp, vp], rc),
+        "bsk_step": ([vp, vp, i], rc), "bsk_step_device": ([vp, vp, i], rc), "bsk_step_device_i64": ([vp, vp, i], rc),
+        "bsk_step_n": ([vp, vp, C.c_int32, i, i, vp, vp, vp], rc),
+        "bsk_get_episode_device": ([vp, P(vp), P(vp), P(vp), P(vp), P(vp)], rc), "bsk_get_batch_stats_device": ([vp, P(vp)], rc),
+        "bsk_set_step_stats": ([vp, i], rc), "bsk_reset_from_pool_device": ([vp, vp], rc),
+        "bsk_debug_counters": ([P(i64), P(i64)], rc), "bsk_debug_words": ([vp, vp], rc),
+        "bsk_get_obs": ([vp, vp, vp, vp, vp], rc), "bsk_get_obs_rowmajor": ([vp, vp, vp, vp], rc),
+        "bsk_get_obs_device": ([vp, P(vp), P(vp), P(vp), P(vp), P(i64)], rc), "bsk_get_obs_state": ([vp, vp, vp, vp, vp], rc),
+        "bsk_get_stream": ([vp, P(vp)], rc), "bsk_get_terminal_obs_device": ([vp, P(vp), P(vp)], rc),
+        "bsk_get_state_device": ([vp, P(vp), P(i64)], rc), "bsk_get_batch_stats": ([vp, P(f64), P(i64)], rc),
+        "bsk_n_fields": ([vp], rc), "bsk_get_state": ([vp, vp], rc), "bsk_set_state": ([vp, vp], rc),
+        "bsk_get_counters": ([vp, vp, vp], rc), "bsk_set_counters": ([vp, vp, vp], rc), "bsk_set_ic_pool": ([vp, i, vp], rc),
+        "bsk_sample_ic_pool": ([vp, i, u64], rc), "bsk_reset_from_pool": ([vp, vp], rc),
+        "bsk_reset_from_pool_shared": ([vp, i, vp, vp], rc), "bsk_get_ic_pool": ([vp, vp], rc),
+        "bsk_get_terminal_obs": ([vp, vp, vp], rc), "bsk_set_env_base": ([vp, i64], rc), "bsk_set_sim_time": ([vp, f64], rc),
+        "bsk_sync": ([vp], rc),
+        "bsk_fork_device": ([vp, vp, vp], rc), "bsk_fork": ([vp, vp, vp], rc),
+        "bsk_select_branches": ([vp, vp, vp, i, i, i, f64, vp, vp, vp, vp], rc),
+        "bsk_beam_select": ([vp, vp, i, i, i, f64, vp, vp, vp, vp, vp, vp], rc),
+        "bsk_policy_n_params": ([spec], rc), "bsk_policy_create": ([spec, vp, i, P(vp)], rc), "bsk_policy_set_params": ([vp, vp], rc),
+        "bsk_policy_destroy": ([vp], None), "bsk_policy_set_rng": ([vp, u64, u64], rc), "bsk_policy_get_rng": ([vp, P(u64), P(u64)], rc),
+        "bsk_policy_act": ([vp, vp, i64, i, i64, i, vp, vp, vp, vp, i64, vp], rc),
+        "bsk_policy_rollout": ([vp, vp, i, i, i, vp, vp, vp, vp, vp, vp], rc),
+        "bsk_population_create": ([spec, i, vp, i, P(vp)], rc), "bsk_population_destroy": ([vp], None),
+        "bsk_population_set_rng": ([vp, u64, u64], rc), "bsk_population_get_rng": ([vp, P(u64), P(u64)], rc),
+        "bsk_population_set_params": ([vp, vp], rc), "bsk_population_set_params_device": ([vp, vp, i, i, vp], rc),
+        "bsk_population_get_member": ([vp, i, vp], rc),
+        "bsk_population_act": ([vp, vp, i64, i, i, i64, i, vp, vp, vp, vp, i64, vp], rc),
+        "bsk_population_rollout": ([vp, vp, i, i, i, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], rc),
+        "bsk_es_create": ([spec, i, vp, f64, f64, i, u64, i, P(vp)], rc), "bsk_es_destroy": ([vp], None),
+        "bsk_es_ask": ([vp, vp, vp], rc), "bsk_es_tell": ([vp, vp, vp], rc), "bsk_es_get_state": ([vp, vp, P(u64)], rc),
+        "bsk_es_set_state": ([vp, vp, u64], rc), "bsk_es_generation_device": ([vp, P(vp)], rc),
+        "bsk_es_set_optimizer": ([vp, i, f64, f64, f64, f64], rc), "bsk_es_get_moments": ([vp, vp, vp, vp], rc),
+        "bsk_es_set_moments": ([vp, vp, vp, vp], rc),
+        "bsk_profile_begin": ([vp, i], rc), "bsk_profile_set_stride": ([vp, i], rc), "bsk_profile_end": ([vp, P(f64), P(i)], rc),
+        "bsk_profile_end_samples": ([vp, P(f64), P(i), vp, i], rc), "bsk_calibrate_fp64": ([i, i, i, P(f64), P(f64)], rc),
+        "bsk_kernel_info": ([vp, C.c_char_p, i, P(i), P(i), P(i), P(i)], rc),
+    }
+
+
+SIGNATURES = _signatures()
+
 _LIB = None
 
 
@@ -135,78 +186,11 @@ def load():
         lib = C.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the host
         raise BskGpuUnavailable("cannot load %s: %s" % (path, e)) from e
-    P = C.POINTER
-    vp = C.c_void_p
-    lib.bsk_last_error.restype = C.c_char_p
-    lib.bsk_version.restype = C.c_char_p
-    lib.bsk_default_config.argtypes = [P(BskConfig), C.c_int, C.c_int]
-    lib.bsk_create.argtypes = [P(BskConfig), C.c_int, C.c_int, vp, P(vp)]
-    lib.bsk_destroy.argtypes = [vp]
-    lib.bsk_destroy.restype = None
-    lib.bsk_set_gravity_sh.argtypes = [vp, C.c_int, vp, vp]
-    lib.bsk_reset.argtypes = [vp, vp, vp]
-    lib.bsk_step.argtypes = [vp, vp, C.c_int]
-    lib.bsk_step_device.argtypes = [vp, vp, C.c_int]
-    for name, args in (("bsk_step_device_i64", [vp, vp, C.c_int]), ("bsk_get_episode_device", [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]),
-                       ("bsk_get_batch_stats_device", [vp, P(vp)]), ("bsk_set_step_stats", [vp, C.c_int]), ("bsk_get_obs_rowmajor", [vp, vp, vp, vp]), ("bsk_reset_from_pool_device", [vp, vp]),
-                       ("bsk_debug_counters", [P(C.c_int64), P(C.c_int64)]), ("bsk_debug_words", [vp, vp]),
-                       ("bsk_step_n", [vp, vp, C.c_int32, C.c_int, C.c_int, vp, vp, vp]),
-                       ("bsk_fork_device", [vp, vp, vp]), ("bsk_fork", [vp, vp, vp]),
-                       ("bsk_select_branches", [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp]),
-                       ("bsk_beam_select", [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp]),
-                       ("bsk_policy_n_params", [P(BskPolicySpec)]), ("bsk_policy_create", [P(BskPolicySpec), vp, C.c_int, P(vp)]),
-                       ("bsk_policy_set_params", [vp, vp]), ("bsk_policy_destroy", [vp]), ("bsk_policy_set_rng", [vp, C.c_uint64, C.c_uint64]),
-                       ("bsk_policy_get_rng", [vp, P(C.c_uint64), P(C.c_uint64)]),
-                       ("bsk_policy_act", [vp, vp, C.c_int64, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, C.c_int64, vp]),
-                       ("bsk_policy_rollout", [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
-                       ("bsk_population_create", [P(BskPolicySpec), C.c_int, vp, C.c_int, P(vp)]), ("bsk_population_destroy", [vp]),
-                       ("bsk_population_set_rng", [vp, C.c_uint64, C.c_uint64]),
-                       ("bsk_population_get_rng", [vp, P(C.c_uint64), P(C.c_uint64)]), ("bsk_population_set_params", [vp, vp]),
-                       ("bsk_population_set_params_device", [vp, vp, C.c_int, C.c_int, vp]),
-                       ("bsk_population_get_member", [vp, C.c_int, vp]),
-                       ("bsk_population_act", [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp, C.c_int64, vp]),
-                       ("bsk_population_rollout", [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-                       ("bsk_es_create", [P(BskPolicySpec), C.c_int, vp, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_int, P(vp)]),
-                       ("bsk_es_destroy", [vp]), ("bsk_es_ask", [vp, vp, vp]), ("bsk_es_tell", [vp, vp, vp]),
-                       ("bsk_es_get_state", [vp, vp, P(C.c_uint64)]), ("bsk_es_set_state", [vp, vp, C.c_uint64]),
-                       ("bsk_reset_from_pool_shared", [vp, C.c_int, vp, vp]), ("bsk_es_generation_device", [vp, P(vp)]),
-                       ("bsk_es_set_optimizer", [vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]),
-                       ("bsk_es_get_moments", [vp, vp, vp, vp]), ("bsk_es_set_moments", [vp, vp, vp, vp])):
-        # (a BSKGPU_LIB variant built from an older tree - kernel A/B against a previous round - may predate these)
+    for name, (argtypes, restype) in SIGNATURES.items():
+        # (a BSKGPU_LIB variant built from an older tree - kernel A/B against a previous round - may predate an export)
         if hasattr(lib, name) or not os.environ.get("BSKGPU_LIB"):
-            getattr(lib, name).argtypes = args
-    if hasattr(lib, "bsk_policy_destroy"):
-        lib.bsk_policy_destroy.restype = None
-    if hasattr(lib, "bsk_population_destroy"):
-        lib.bsk_population_destroy.restype = None
-    if hasattr(lib, "bsk_es_destroy"):
-        lib.bsk_es_destroy.restype = None
-    lib.bsk_get_obs.argtypes = [vp, vp, vp, vp, vp]
-    lib.bsk_get_obs_device.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(C.c_int64)]
-    lib.bsk_get_obs_state.argtypes = [vp, vp, vp, vp, vp]
-    lib.bsk_get_stream.argtypes = [vp, P(vp)]
-    lib.bsk_get_terminal_obs_device.argtypes = [vp, P(vp), P(vp)]
-    lib.bsk_get_state_device.argtypes = [vp, P(vp), P(C.c_int64)]
-    lib.bsk_get_batch_stats.argtypes = [vp, P(C.c_double), P(C.c_int64)]
-    lib.bsk_n_fields.argtypes = [vp]
-    lib.bsk_get_state.argtypes = [vp, vp]
-    lib.bsk_set_state.argtypes = [vp, vp]
-    lib.bsk_get_counters.argtypes = [vp, vp, vp]
-    lib.bsk_set_counters.argtypes = [vp, vp, vp]
-    lib.bsk_set_ic_pool.argtypes = [vp, C.c_int, vp]
-    lib.bsk_get_terminal_obs.argtypes = [vp, vp, vp]
-    lib.bsk_sample_ic_pool.argtypes = [vp, C.c_int, C.c_uint64]
-    lib.bsk_reset_from_pool.argtypes = [vp, vp]
-    lib.bsk_get_ic_pool.argtypes = [vp, vp]
-    lib.bsk_set_sim_time.argtypes = [vp, C.c_double]
-    lib.bsk_set_env_base.argtypes = [vp, C.c_int64]
-    lib.bsk_sync.argtypes = [vp]
-    lib.bsk_profile_begin.argtypes = [vp, C.c_int]
-    lib.bsk_profile_set_stride.argtypes = [vp, C.c_int]
-    lib.bsk_profile_end.argtypes = [vp, P(C.c_double), P(C.c_int)]
-    lib.bsk_profile_end_samples.argtypes = [vp, P(C.c_double), P(C.c_int), vp, C.c_int]
-    lib.bsk_calibrate_fp64.argtypes = [C.c_int, C.c_int, C.c_int, P(C.c_double), P(C.c_double)]
-    lib.bsk_kernel_info.argtypes = [vp, C.c_char_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int)]
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = argtypes, restype
     _LIB = lib
     return lib
 

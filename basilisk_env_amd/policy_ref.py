@@ -1,0 +1,410 @@
+"""The numpy restatements the policy, population and evolution-strategy kernels are held to, bit for bit: the oracle of this subsystem.
+
+Each function repeats, operation by operation and in the kernel's order, what include/bskgpu.h defines: the networks (``mlp_ref``: every
+layer output one k-ordered chain of ``fma32`` from the bias), the action choice (``act_ref``, ``softmax_ref``, the Philox draw of
+``sample_uniform``), the per-member fitness of a rollout (``population_fitness_ref``), and the evolution strategy - its noise
+(``es_noise_ref``: Philox, then Wichura's AS 241 with a series logarithm), members (``es_ask_ref``), ranking (``centred_ranks``) and the
+SGD and Adam updates (``es_tell_ref``, ``es_tell_adam_ref``) - with ``shared_slot_ref`` for the shared-episode reset.
+``EvolutionStrategy`` is the host-side search the device one was modelled on.  Needs numpy and ``policy_spec`` only: no device, no
+library.  The tests compare these with the device for equality, so the order of operations and the ``np.errstate`` scopes are part
+of what they state.
+"""
+import numpy as np
+
+from .policy_spec import MODES, _as_spec, unpack_params
+
+def fma32(a, b, c):
+    """float32 arrays (broadcast against each other) -> float32: a * b + c rounded ONCE, what ``fmaf`` / ``v_fma_f32`` / one step
+    of an f32 MFMA accumulator give.  The product of two float32 is exact in float64 (48 bits); TwoSum gives the exact residual of
+    the float64 addition; the float64 sum is rounded to odd with it, and rounding that to float32 equals rounding the exact sum."""
+    p = np.asarray(a, np.float32).astype(np.float64) * np.asarray(b, np.float32).astype(np.float64)
+    c = np.asarray(c, np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = p + c
+        t = s - p
+        err = (p - (s - t)) + (c - t)                                        # TwoSum: s + err == p + c exactly
+    s = np.ascontiguousarray(s)
+    bits = s.view(np.int64)
+    fix = (err != 0) & ((bits & 1) == 0) & np.isfinite(s) & (s != 0)
+    bits = np.where(fix, bits + np.where((err > 0) == (s > 0), 1, -1), bits)  # round to odd in 53 bits
+    return np.where((s == 0) & (err != 0), err, bits.view(np.float64)).astype(np.float32)
+
+
+def _forward32(layers, activation, x, chunk=2048):
+    """the definition's chain, units x spacecraft; ``chunk`` spacecraft at a time (the working set stays in cache), the chunks
+    spread over a few threads (numpy's array operations release the interpreter lock)"""
+    n = x.shape[1]
+    out = np.empty((layers[-1][0].shape[0], n), np.float32)
+
+    def run(lo):
+        h = x[:, lo:lo + chunk]
+        for li, (W, b) in enumerate(layers):
+            z = np.broadcast_to(b[:, None], (W.shape[0], h.shape[1])).astype(np.float32)
+            for k in range(W.shape[1]):
+                z = fma32(W[:, k:k + 1], h[k:k + 1, :], z)
+            if li + 1 < len(layers):
+                with np.errstate(invalid="ignore"):
+                    z = np.tanh(z) if activation == "tanh" else np.where(z > 0, z, np.float32(0))
+            h = z.astype(np.float32)
+        out[:, lo:lo + chunk] = h
+    starts = range(0, n, chunk)
+    if len(starts) < 4:
+        for lo in starts:
+            run(lo)
+    else:
+        import os
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max(1, min(8, os.cpu_count() or 1))) as pool:
+            list(pool.map(run, starts))
+    return out
+
+
+def _forward64(layers, activation, x):
+    h = x
+    for li, (W, b) in enumerate(layers):
+        h = W.astype(np.float64) @ h + b.astype(np.float64)[:, None]
+        if li + 1 < len(layers):
+            h = np.tanh(h) if activation == "tanh" else np.maximum(h, 0.0)
+    return h
+
+
+def mlp_ref(spec, params, obs, fp64=False):
+    """numpy restatement of the policy's networks (include/bskgpu.h).  ``obs``: (5, n) float64 -> logits (3, n), value (n,) or None.
+    Default: the definition itself - float32, every layer output one k-ordered ``fma32`` chain from the bias: bit for bit the
+    kernel's logits and value for ``relu`` networks (``tanh`` is the host's here and the device library's there).
+    ``fp64=True``: the same float32 parameters and float32-converted inputs carried through in float64 (what error bounds are
+    derived against)."""
+    spec = _as_spec(spec)
+    scale, shift, a, v = unpack_params(spec, params)
+    o32 = np.asarray(obs, np.float64).reshape(5, -1).astype(np.float32)
+    if fp64:
+        x = o32.astype(np.float64) * scale.astype(np.float64)[:, None] + shift.astype(np.float64)[:, None]
+        return _forward64(a, spec.activation, x), (None if v is None else _forward64(v, spec.value_activation, x)[0])
+    x = fma32(o32, scale[:, None], shift[:, None])
+    return _forward32(a, spec.activation, x), (None if v is None else _forward32(v, spec.value_activation, x)[0])
+
+
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+_MASK32, _SH32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al. 2011) on uint64 arrays that hold 32-bit words -> the four output words (csrc/bsk_philox.hpp)."""
+    c0, c1, c2, c3, k0, k1 = (np.asarray(w, np.uint64) for w in (c0, c1, c2, c3, k0, k1))
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
+        c0, c1, c2, c3 = ((p1 >> _SH32) ^ c1 ^ k0) & _MASK32, p1 & _MASK32, ((p0 >> _SH32) ^ c3 ^ k1) & _MASK32, p0 & _MASK32
+        k0, k1 = (k0 + _PHILOX_W0) & _MASK32, (k1 + _PHILOX_W1) & _MASK32
+    return c0, c1, c2, c3
+
+
+def sample_uniform(n, seed=0, draw=0, env_base=0):
+    """u of sample mode for spacecraft env_base .. env_base + n - 1: (w0 >> 8) * 2**-24 with w0 the first Philox word of counter
+    (env_lo, env_hi, draw_lo, draw_hi) under key (seed_lo, seed_hi) -> float32 (n,)."""
+    env = np.uint64(int(env_base)) + np.arange(int(n), dtype=np.uint64)
+    seed, draw = np.uint64(int(seed)), np.uint64(int(draw))
+    w0 = philox4x32_10(env & _MASK32, env >> _SH32, draw & _MASK32, draw >> _SH32, seed & _MASK32, seed >> _SH32)[0]
+    return (w0 >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+
+
+def softmax_ref(logits):
+    """-> m, e (3, n), s of include/bskgpu.h step 5, float32 operations in the kernel's order (``exp`` is the host's)."""
+    l = np.asarray(logits, np.float32).reshape(3, -1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        m = np.fmax(np.fmax(l[0], l[1]), l[2])
+        e = np.exp(l - m)
+        s = (e[0] + e[1]) + e[2]
+    return m, e, s
+
+
+def act_ref(logits, mode="greedy", seed=0, draw=0, env_base=0):
+    """numpy restatement of the action choice.  ``logits`` (3, n) float32 -> action int32 (n,), logp float32 (n,).
+    greedy: the greatest logit, ties to the lowest index, a NaN loses to every number (three NaNs pick 0).
+    sample: p_i = e_i / s, action = 0 if u < p_0, else 1 if u < p_0 + p_1, else 2 (``sample_uniform``)."""
+    if mode not in MODES:
+        raise ValueError("mode must be 'greedy' or 'sample'")
+    l = np.asarray(logits, np.float32).reshape(3, -1)
+    m, e, s = softmax_ref(l)
+    if mode == "sample":
+        u = sample_uniform(l.shape[1], seed, draw, env_base)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            c0 = e[0] / s
+            c1 = c0 + e[1] / s
+        a = np.where(u < c0, 0, np.where(u < c1, 1, 2)).astype(np.int32)
+    else:
+        a = np.zeros(l.shape[1], np.int32)
+        best = l[0].copy()
+        for i in (1, 2):
+            na, nb = np.isnan(l[i]), np.isnan(best)
+            with np.errstate(invalid="ignore"):
+                win = np.where(na != nb, nb, ~na & (l[i] > best))
+            a[win] = i
+            best[win] = l[i][win]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        logp = (np.take_along_axis(l, a[None, :].astype(np.int64), axis=0)[0] - m) - np.log(s)
+    return a, logp.astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Populations (bsk_population_*): the per-member fitness of a rollout, the ranking, and the host-side search around them
+
+def population_fitness_ref(reward_hist, reason_hist, gamma, n_members):
+    """numpy restatement of the device fitness (include/bskgpu.h).  ``reward_hist`` (T, n) float64, ``reason_hist`` (T, n): the
+    rows a rollout records; n = n_members * E, E a multiple of 64.  -> dict: ``env_value`` (n,) float64 and ``env_len`` (n,) int32 -
+    per env v = v + g * reward, len += 1, g = g * gamma while alive, alive until the first step with reason != 0 (included) - and
+    ``fitness`` / ``mean_len`` (n_members,) float64: per member, lane l adds its elements l, l + 64, ... ascending from the first,
+    then s[l] = s[l] + s[l + stride] for stride 32 ... 1, then s[0] / E.  Every operation rounds on its own, in the kernel's order:
+    the results are equal bit for bit."""
+    r = np.asarray(reward_hist, np.float64)
+    q = np.asarray(reason_hist)
+    if r.ndim != 2 or q.shape != r.shape:
+        raise ValueError("reward_hist and reason_hist: (n_steps, n) each")
+    n, P = r.shape[1], int(n_members)
+    if P < 1 or n % P or (n // P) % 64 or n == 0:
+        raise ValueError("n must be n_members * envs_per_member, envs_per_member a positive multiple of 64")
+    E = n // P
+    gamma = np.float64(gamma)
+    v, g = np.zeros(n, np.float64), np.ones(n, np.float64)
+    length, alive = np.zeros(n, np.int32), np.ones(n, bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for t in range(r.shape[0]):
+            p = g * r[t]
+            v = np.where(alive, v + p, v)
+            g = np.where(alive, g * gamma, g)
+            length += alive
+            alive &= q[t] == 0
+
+        def mean(x):
+            x = x.reshape(P, E // 64, 64)
+            s = x[:, 0, :].copy()
+            for i in range(1, E // 64):
+                s = s + x[:, i, :]
+            for stride in (32, 16, 8, 4, 2, 1):
+                s[:, :stride] = s[:, :stride] + s[:, stride:2 * stride]
+            return s[:, 0] / np.float64(E)
+        return {"env_value": v, "env_len": length, "fitness": mean(v), "mean_len": mean(length.astype(np.float64))}
+
+
+def centred_ranks(fitness):
+    """(P,) fitness -> (P,) float64 utilities 0.5 (best) ... -0.5 (worst), evenly spaced.  The order is the library's ``beats`` rule
+    (bsk_select_branches): the greater value first, a NaN below every number, equal values (and NaNs) to the lower index."""
+    f = np.asarray(fitness, np.float64).reshape(-1)
+    nan = np.isnan(f)
+    order = np.lexsort((-np.where(nan, 0.0, f), nan))          # (stable: ties keep ascending index)
+    u = np.empty(f.size, np.float64)
+    u[order] = 0.5 - np.arange(f.size) / max(f.size - 1, 1)
+    return u
+
+
+class EvolutionStrategy(object):
+    """A small antithetic evolution strategy with centred-rank utilities (Salimans et al. 2017, "Evolution Strategies as a Scalable
+    Alternative to Reinforcement Learning"), host-side numpy: the piece that turns ``PolicyPopulation.evaluate`` into a search.
+    ``ask()`` -> (P, n) float32 members theta + sigma * eps_i (even rows) and theta - sigma * eps_i (odd rows), P even;
+    ``tell(fitness)`` moves theta by lr / (P * sigma) * sum_k u_k * (+-eps_k), u the ``centred_ranks`` of the fitness (greater is
+    better).  The first ``frozen`` floats - a policy block's in_scale and in_shift - are never perturbed nor moved.  Seeded: the
+    same seed asks the same members."""
+
+    def __init__(self, theta, population, sigma=0.1, lr=0.05, seed=0, frozen=10):
+        self.theta = np.array(theta, dtype=np.float64).reshape(-1)
+        self.population, self.sigma, self.lr, self.frozen = int(population), float(sigma), float(lr), int(frozen)
+        if self.population < 2 or self.population % 2:
+            raise ValueError("population must be even and >= 2")
+        if not (self.sigma > 0.0) or not (0 <= self.frozen <= self.theta.size):
+            raise ValueError("sigma must be positive and frozen within the parameter block")
+        self._rng = np.random.default_rng(seed)
+        self._eps = None
+
+    def ask(self):
+        eps = self._rng.standard_normal((self.population // 2, self.theta.size))
+        eps[:, :self.frozen] = 0.0
+        self._eps = eps
+        members = np.empty((self.population, self.theta.size), np.float64)
+        members[0::2] = self.theta + self.sigma * eps
+        members[1::2] = self.theta - self.sigma * eps
+        return members.astype(np.float32)
+
+    def tell(self, fitness):
+        if self._eps is None:
+            raise RuntimeError("tell() follows ask()")
+        u = centred_ranks(fitness)
+        if u.size != self.population:
+            raise ValueError("expected %d fitness values, got %d" % (self.population, u.size))
+        step = (u[0::2] - u[1::2]) @ self._eps
+        self.theta = self.theta + self.lr / (self.population * self.sigma) * step
+        self._eps = None
+        return self.theta.astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The evolution strategy on the device (bsk_es_*; definition in include/bskgpu.h, kernels in csrc/bsk_es.hip), restated
+
+# Wichura's AS 241 (PPND16), coefficients lowest first
+_PPND_A = (3.3871328727963666080, 1.3314166789178437745e2, 1.9715909503065514427e3, 1.3731693765509461125e4,
+           4.5921953931549871457e4, 6.7265770927008700853e4, 3.3430575583588128105e4, 2.5090809287301226727e3)
+_PPND_B = (1.0, 4.2313330701600911252e1, 6.8718700749205790830e2, 5.3941960214247511077e3,
+           2.1213794301586595867e4, 3.9307895800092710610e4, 2.8729085735721942674e4, 5.2264952788528545610e3)
+_PPND_C = (1.42343711074968357734, 4.63033784615654529590, 5.76949722146069140550, 3.64784832476320460504,
+           1.27045825245236838258, 2.41780725177450611770e-1, 2.27238449892691845833e-2, 7.74545014278341407640e-4)
+_PPND_D = (1.0, 2.05319162663775882187, 1.67638483018380384940, 6.89767334985100004550e-1,
+           1.48103976427480074590e-1, 1.51986665636164571966e-2, 5.47593808499534494600e-4, 1.05075007164441684324e-9)
+_PPND_E = (6.65790464350110377720, 5.46378491116411436990, 1.78482653991729133580, 2.96560571828504891230e-1,
+           2.65321895265761230930e-2, 1.24266094738807843860e-3, 2.71155556874348757815e-5, 2.01033439929228813265e-7)
+_PPND_F = (1.0, 5.99832206555887937690e-1, 1.36929880922735805310e-1, 1.48753612908506148525e-2,
+           7.86869131145613259100e-4, 1.84631831751005468180e-5, 1.42151175831644588870e-7, 2.04426310338993978564e-15)
+
+
+def _horner(coef, x):
+    y = np.full_like(x, coef[-1])
+    for c in coef[-2::-1]:
+        y = y * x + c
+    return y
+
+
+def _series_log(p):
+    """ln(p) of include/bskgpu.h for p in (0, 0.5): frexp, then the atanh series in (m - 1) / (m + 1) - no library logarithm"""
+    m, e = np.frexp(p)
+    low = m < 0.7071067811865476
+    m = np.where(low, m + m, m)
+    e = np.where(low, e - 1, e).astype(np.float64)
+    s = (m - 1.0) / (m + 1.0)
+    s2 = s * s
+    t = np.full_like(s, 1.0 / 23.0)
+    for k in range(10, -1, -1):
+        t = t * s2 + 1.0 / (2 * k + 1)
+    return e * 0.6931471805599453 + (2.0 * s) * t
+
+
+def es_uniform_ref(k):
+    """52-bit integers k -> u = (k + 0.5) * 2**-52, exact and inside (0, 1)"""
+    return (np.asarray(k, np.uint64).astype(np.float64) + 0.5) * 2.0 ** -52
+
+
+def es_inverse_normal_ref(u):
+    """The inverse normal CDF of include/bskgpu.h on float64 u in (0, 1): AS 241 with a series logarithm, every operation one of
+    f64 + - * /, sqrt or an integer operation, each rounded on its own - the device's bits."""
+    u = np.asarray(u, np.float64)
+    q = u - 0.5
+    centre = np.abs(q) <= 0.425
+    r = 0.180625 - q * q
+    z = q * _horner(_PPND_A, r) / _horner(_PPND_B, r)
+    if not centre.all():
+        tail = ~centre
+        p = np.where(q[tail] < 0, u[tail], 1.0 - u[tail])
+        r = np.sqrt(-_series_log(p))
+        x, y = r - 1.6, r - 5.0
+        t = np.where(r <= 5.0, _horner(_PPND_C, x) / _horner(_PPND_D, x), _horner(_PPND_E, y) / _horner(_PPND_F, y))
+        z[tail] = np.where(q[tail] < 0, -t, t)
+    return z
+
+
+def es_noise_ref(seed, generation, pairs, n_params):
+    """z(g, i, j) of include/bskgpu.h -> float64 (pairs, n_params): Philox4x32-10 under key (seed lo, seed hi) at counter
+    (j, i, g lo, g hi); k = (w0 >> 6) * 2**26 + (w1 >> 6); u = (k + 0.5) * 2**-52; z = the inverse normal CDF of u."""
+    seed, g = np.uint64(int(seed)), np.uint64(int(generation))
+    j = np.broadcast_to(np.arange(int(n_params), dtype=np.uint64)[None, :], (int(pairs), int(n_params)))
+    i = np.broadcast_to(np.arange(int(pairs), dtype=np.uint64)[:, None], j.shape)
+    w0, w1, _, _ = philox4x32_10(j, i, g & _MASK32, g >> _SH32, seed & _MASK32, seed >> _SH32)
+    k = ((w0 >> np.uint64(6)) << np.uint64(26)) + (w1 >> np.uint64(6))
+    return es_inverse_normal_ref(es_uniform_ref(k))
+
+
+def es_ask_ref(theta, sigma, frozen, P, seed, generation):
+    """The members ``bsk_es_ask`` writes -> float32 (P, n_params): rows 2i / 2i + 1 are theta +- sigma * z(g, i, :), product and
+    sum each rounded in float64, then rounded to float32; the first ``frozen`` columns are (float)theta."""
+    theta = np.asarray(theta, np.float64).reshape(-1)
+    P, frozen = int(P), int(frozen)
+    step = np.float64(sigma) * es_noise_ref(seed, generation, P // 2, theta.size)
+    step[:, :frozen] = 0.0
+    members = np.empty((P, theta.size), np.float64)
+    members[0::2] = theta + step
+    members[1::2] = theta - step
+    members[:, :frozen] = theta[:frozen]
+    return members.astype(np.float32)
+
+
+def es_tell_ref(theta, fitness, sigma, lr, frozen, seed, generation):
+    """The theta ``bsk_es_tell`` leaves -> float64 (n_params,): w_i = u_2i - u_2i+1 of the ``centred_ranks``; per parameter
+    j >= frozen lane l = 0 .. 63 sums w_i * z(g, i, j) over its pairs i = l, l + 64, ... ascending from the first (+0.0 with no
+    pair), the lanes join as the fitness tree does (stride 32 ... 1), and theta_j = theta_j + lr / (P * sigma) * s[0]."""
+    theta = np.array(theta, dtype=np.float64).reshape(-1)
+    frozen = int(frozen)
+    s0, P = _es_pair_sum(fitness, theta.size, seed, generation)
+    with np.errstate(invalid="ignore", over="ignore"):
+        c = float(lr) / (float(P) * float(sigma))
+        theta[frozen:] = theta[frozen:] + c * s0[frozen:]
+    return theta
+
+
+def _es_pair_sum(fitness, n_params, seed, generation):
+    """Steps 1 - 3 of ``bsk_es_tell`` up to s[0] -> (float64 (n_params,), P): the one sum behind ``es_tell_ref`` and
+    ``es_tell_adam_ref``, as ``ES_PAIR_SUM`` (csrc/bsk_es.hip) is behind the two update kernels."""
+    u = centred_ranks(fitness)
+    P = u.size
+    if P < 2 or P % 2:
+        raise ValueError("expected an even number of fitness values, at least 2")
+    w = u[0::2] - u[1::2]
+    with np.errstate(invalid="ignore", over="ignore"):
+        terms = w[:, None] * es_noise_ref(seed, generation, P // 2, n_params)
+        s = np.zeros((64, int(n_params)), np.float64)
+        s[:min(64, P // 2)] = terms[:64]
+        for at in range(64, P // 2, 64):
+            chunk = terms[at:at + 64]
+            s[:len(chunk)] = s[:len(chunk)] + chunk
+        for stride in (32, 16, 8, 4, 2, 1):
+            s[:stride] = s[:stride] + s[stride:2 * stride]
+    return s[0].copy(), P
+
+
+def check_adam(beta1, beta2, eps, weight_decay):
+    """The argument rules of ``bsk_es_set_optimizer(BSK_ES_ADAM, ...)`` -> the four as floats; ValueError where it returns
+    BSK_EINVAL.  Needs no device."""
+    beta1, beta2, eps, weight_decay = float(beta1), float(beta2), float(eps), float(weight_decay)
+    if not (0.0 <= beta1 < 1.0) or not (0.0 <= beta2 < 1.0):
+        raise ValueError("beta1 and beta2 must be in [0, 1)")
+    if not np.isfinite(eps) or not (eps > 0.0):
+        raise ValueError("eps must be finite and positive")
+    if not np.isfinite(weight_decay) or weight_decay < 0.0:
+        raise ValueError("weight_decay must be finite and not negative")
+    return beta1, beta2, eps, weight_decay
+
+
+def es_tell_adam_ref(theta, m, v, beta_pow, fitness, sigma, lr, frozen, seed, generation, beta1, beta2, eps, weight_decay):
+    """What ``bsk_es_tell`` leaves under ``BSK_ES_ADAM`` -> (theta, m, v, beta_pow), float64: s[0] of ``es_tell_ref``'s sum, then
+    per parameter j >= frozen, every operation rounded on its own (include/bskgpu.h), cg = 1 / (P * sigma):
+    g = cg * s[0] - weight_decay * theta_j; m_j = beta1 * m_j + (1 - beta1) * g; v_j = beta2 * v_j + ((1 - beta2) * g) * g;
+    theta_j = theta_j + (lr * (m_j / (1 - p1))) / (sqrt(v_j / (1 - p2)) + eps) with p = beta_pow * beta, the beta_pow returned."""
+    theta = np.array(theta, dtype=np.float64).reshape(-1)
+    m, v = np.array(m, dtype=np.float64).reshape(-1), np.array(v, dtype=np.float64).reshape(-1)
+    bp = np.array(beta_pow, dtype=np.float64).reshape(2)
+    frozen = int(frozen)
+    if m.size != theta.size or v.size != theta.size:
+        raise ValueError("m and v have theta's size")
+    b1, b2, eps, wd = (np.float64(x) for x in check_adam(beta1, beta2, eps, weight_decay))
+    s0, P = _es_pair_sum(fitness, theta.size, seed, generation)
+    lr = np.float64(lr)
+    cg = np.float64(1.0) / (np.float64(P) * np.float64(sigma))
+    a1, a2 = np.float64(1.0) - b1, np.float64(1.0) - b2
+    p1, p2 = bp[0] * b1, bp[1] * b2
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        t = theta[frozen:]
+        g = cg * s0[frozen:] - wd * t
+        mj = b1 * m[frozen:] + a1 * g
+        vj = b2 * v[frozen:] + (a2 * g) * g
+        m[frozen:], v[frozen:] = mj, vj
+        theta[frozen:] = t + (lr * (mj / (np.float64(1.0) - p1))) / (np.sqrt(vj / (np.float64(1.0) - p2)) + eps)
+    return theta, m, v, np.array([p1, p2], np.float64)
+
+
+def shared_slot_ref(n, envs_per_member, epoch, n_pool, env_base=0):
+    """The IC-pool slots ``bsk_reset_from_pool_shared`` restarts envs 0 .. n - 1 from -> uint32 (n,): g = (env_base + env) mod 2^32,
+    q = g mod envs_per_member, e = epoch mod 2^32, slot = (q * 2654435761 + e * 40503 + 12345) mod 2^32 mod n_pool.  Envs with equal
+    q share a slot.  Needs no device."""
+    n, E, n_pool = int(n), int(envs_per_member), int(n_pool)
+    if E < 1 or n_pool < 1:
+        raise ValueError("envs_per_member and n_pool must be >= 1")
+    mask = np.uint64(0xFFFFFFFF)
+    g = (np.arange(n, dtype=np.uint64) + np.uint64(int(env_base) & 0xFFFFFFFF)) & mask
+    q = g % np.uint64(E)
+    e = np.uint64(int(epoch) & 0xFFFFFFFF)
+    return (((q * np.uint64(2654435761) + e * np.uint64(40503) + np.uint64(12345)) & mask) % np.uint64(n_pool)).astype(np.uint32)

@@ -27,6 +27,7 @@ def test_every_declared_symbol_is_exported():
     missing = [f for f in decl if not hasattr(lib, f)]
     assert not missing, missing
     assert sorted(_lib.EXPORTS) == decl          # the Python binding tracks the header exactly
+    assert sorted(_lib.SIGNATURES) == decl       # ... and declares the arguments of every one of them
 
 
 def test_no_torch_or_oracle_linkage():

@@ -663,3 +663,64 @@ def test_population_and_policy_rollouts_enqueue_the_same_loop():
         x.free()
     for x in (prop, pol, pop):
         x.close()
+
+
+def test_one_lifecycle_and_one_host_path_behind_the_three_bindings():
+    """DevicePolicy, PolicyPopulation and DeviceEvolutionStrategy close through one base (basilisk_env_amd/policy.py: _DeviceObject):
+    a second close is silent and a use after it is refused by name.  ``rollout`` and ``evaluate`` bring their results to the host
+    through one helper (_ParamStore._host_rollout): what it returns equals what ``rollout_device`` leaves in buffers the caller owns,
+    from the same state and the same seed.  The smallest shapes there are: one hidden layer of 16, 64 envs per member, two env steps
+    of one substep."""
+    T, k, E, members = 2, 1, 64, 2
+    spec, params = _loop_policy((16,), (16,), 77)
+    _, other = seeded_policy((16,), "relu", (16,), seed=78)
+    pol = P.DevicePolicy(spec, params)
+    pop = P.PolicyPopulation(spec, np.stack([params, other]))
+    es = P.DeviceEvolutionStrategy(spec, params, members)
+    # the policy: host rows against caller-owned device rows
+    a, b = (_stepped_propagator(E, steps=1, k=k, seed=23) for _ in range(2))
+    rows = (("obs", np.float64, 5), ("reward", np.float64, 1), ("reason", np.uint8, 1), ("action", np.int32, 1), ("logp", np.float32, 1),
+            ("value", np.float32, 1))
+    bufs = {key: _hip.DeviceBuffer(T * E * m * np.dtype(dt).itemsize, 0) for key, dt, m in rows}
+    pol.set_rng(7, 3)
+    host = pol.rollout(a, T, k, "sample")
+    pol.set_rng(7, 3)
+    pol.rollout_device(b, T, k, "sample", *(bufs[key].ptr for key, _, _ in rows))
+    b.sync()
+    assert list(host) == [key for key, _, _ in rows]
+    for key, dt, m in rows:
+        mine = _download(bufs[key].ptr, dt, T * E * m).reshape(host[key].shape)
+        assert host[key].dtype == dt and host[key].tobytes() == mine.tobytes(), key
+    assert pol.get_rng() == (7, 3 + T)
+    # the population: host fitness against caller-owned device fitness
+    n = members * E
+    c, d = (_stepped_propagator(n, steps=1, k=k, seed=29) for _ in range(2))
+    fit = (("env_value", np.float64, n), ("env_len", np.int32, n), ("fitness", np.float64, members), ("mean_len", np.float64, members))
+    fbufs = {key: _hip.DeviceBuffer(count * np.dtype(dt).itemsize, 0) for key, dt, count in fit}
+    pop.set_rng(9, 1)
+    host = pop.evaluate(c, T, k, "sample", 0.97)
+    pop.set_rng(9, 1)
+    pop.rollout_device(d, T, k, "sample", 0.97, **{"d_" + key: fbufs[key].ptr for key, _, _ in fit})
+    d.sync()
+    assert list(host) == [key for key, _, _ in fit]
+    for key, dt, count in fit:
+        mine = _download(fbufs[key].ptr, dt, count)
+        assert host[key].dtype == dt and host[key].shape == (count,) and host[key].tobytes() == mine.tobytes(), key
+    assert np.all((host["env_len"] >= 1) & (host["env_len"] <= T)) and pop.get_rng() == (9, 1 + T)
+    # the strategy: one launch into the population, then the wait all three inherit
+    es.ask(pop)
+    es.sync()
+    assert np.array_equal(pop.member(0)[:10], params[:10]) and es.generation == 0
+    for obj, what, use in ((pol, "policy", lambda: pol.get_rng()), (pop, "population", lambda: pop.member(0)),
+                           (es, "evolution strategy", lambda: es.generation)):
+        obj.close()
+        obj.close()
+        with pytest.raises(RuntimeError) as e:
+            use()
+        assert e.value.args == ("%s is closed" % what,)
+        with pytest.raises(RuntimeError):
+            obj._handle()
+    for x in list(bufs.values()) + list(fbufs.values()):
+        x.free()
+    for x in (a, b, c, d):
+        x.close()
