@@ -7,6 +7,7 @@
 //                           basilisk_env/simulators/leoPowerAttitudeSimulator.py:119-193, leo_orbit.py:25-40, sc_attitudes.py:3-13)
 //   reset_from_pool_kernel / init_outputs_kernel    device-side (re)start from the staged pool, first observations
 #include "bsk_device.hpp"
+#include "bsk_envstep.hpp"
 #include "bsk_aux.hpp"
 #include "bsk_philox.hpp"
 
@@ -271,12 +272,11 @@ __device__ __forceinline__ void init_outputs(const ResetOut& ro, const double* _
         const double v = st[(int64_t)(BSK_NF_BASE + k) * stride + i];
         om2 = fma(v, v, om2);
     }
-    const double o[5] = {sqrt_nr(dot(sg, sg)), sqrt_nr(dot(w, w)), sqrt_nr(om2) * ro.inv_wheel_limit,
-                         st[(int64_t)(BSK_NF_BASE + ro.n_rw + BSK_T_CHARGE) * stride + i] * ro.charge_scale, 1.0};
+    const Obs5 f0 = first_observation(sg, w, om2, st[(int64_t)(BSK_NF_BASE + ro.n_rw + BSK_T_CHARGE) * stride + i], ro.inv_wheel_limit, ro.charge_scale);
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        ro.obs[(int64_t)k * ro.ostride + i] = o[k];
-        if (ro.obs_rm) ro.obs_rm[(int64_t)i * 5 + k] = o[k];
+        ro.obs[(int64_t)k * ro.ostride + i] = f0.o[k];
+        if (ro.obs_rm) ro.obs_rm[(int64_t)i * 5 + k] = f0.o[k];
     }
     ro.reward[i] = 0.0;
     ro.reason[i] = 0;
@@ -292,7 +292,7 @@ __global__ void reset_from_pool_kernel(double* __restrict__ st, int64_t stride, 
     if (i >= n || (mask && !mask[i])) return;
     const int ep = episodes[i];
     episodes[i] = ep + 1;
-    const unsigned slot = (((unsigned)i + env_base) * 2654435761u + (unsigned)ep * 40503u + 12345u) % (unsigned)n_pool;
+    const unsigned slot = pool_slot((unsigned)i + env_base, (unsigned)ep, (unsigned)n_pool);
     for (int f = 0; f < nf; ++f) st[f * stride + i] = pool[(int64_t)f * n_pool + slot];
     cnt[i] = make_int2(0, 0);
     init_outputs(ro, st, stride, i);
@@ -311,7 +311,7 @@ __global__ void reset_from_pool_shared_kernel(double* __restrict__ st, int64_t s
     episodes[i] = episodes[i] + 1;
     const unsigned e = epoch ? (unsigned)*epoch : 0u;
     const unsigned q = ((unsigned)i + env_base) % envs_per_member;
-    const unsigned slot = (q * 2654435761u + e * 40503u + 12345u) % (unsigned)n_pool;
+    const unsigned slot = pool_slot(q, e, (unsigned)n_pool);
     for (int f = 0; f < nf; ++f) st[f * stride + i] = pool[(int64_t)f * n_pool + slot];
     cnt[i] = make_int2(0, 0);
     init_outputs(ro, st, stride, i);

@@ -127,7 +127,7 @@ struct HotCfg {
     double js[NRW > 0 ? NRW : 1], ijs[NRW > 0 ? NRW : 1];
     double fc;
     int32_t fsw_every, sh_degree;
-    // harmonics walk (bsk_capi.hip: bsk_set_gravity_sh): first column of the second half; bodies of the
+    // harmonics walk (bsk_config.hip: build_sh_table_dpp's layout, set by bsk_set_gravity_sh): first column of the second half; bodies of the
     // whole padded stream; bodies of each half and first chunk of the second half (two-wave form)
     int32_t sh_split, sh_bodies;
     int32_t sh_bodies0, sh_bodies1, sh_chunk1, pad_;
@@ -919,7 +919,7 @@ struct State {
 // Pines' normalised spherical-harmonic field (SURVEY.md §8 note N1), degree d, position in the
 // planet-fixed frame.  All lanes walk the same (l, m) sequence, so the coefficient stream is
 // wave-uniform and is read with SCALAR loads: the host fuses Cbar/Sbar/n1/n2/nq1/nq2 into one
-// stream in iteration order (bsk_capi.hip: build_sh_table), 8 doubles = one s_load_dwordx16 per
+// stream in iteration order (bsk_config.hip: build_sh_table), 8 doubles = one s_load_dwordx16 per
 // step, and the VALU takes them as SGPR operands.  Columns M = 1..d+1 of the derived Legendre
 // function A[L][M], L = M..d+1, are generated by the three-term recursion on B = w_L A[L][M]
 // (w_L = mu/(r Re) (Re/r)^(L+1) folded into the recursion), and each column's six coefficient
@@ -948,7 +948,7 @@ __device__ __forceinline__ double fmac_bc(double acc, double tab, double b) {
 // chunks in flight = chunks per loop body (the host pads the stream to whole bodies + slack)
 constexpr int SH_RING = 8;
 
-// Forms 4 / 5 of the harmonics evaluation.  The fused stream (bsk_capi.hip: build_sh_table_dpp) holds 8
+// Forms 4 / 5 of the harmonics evaluation.  The fused stream (bsk_config.hip: build_sh_table_dpp) holds 8
 // doubles per (L, M) entry in iteration order, every column padded to an even number of entries, so a
 // 128-byte chunk = 2 entries = the 16 doubles one 16-lane row holds in ONE VGPR pair: lane l of every
 // row loads double (l & 15) of the chunk (a single global_load_dwordx2, one cache line per wave), and

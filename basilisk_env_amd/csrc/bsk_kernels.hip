@@ -15,6 +15,7 @@
 //   reference basilisk_env/simulators/leoPowerAttitudeSimulator.py:535-644
 //   reference basilisk_env/envs/leoPowerAttitudeEnvironment.py:98-127,161-170
 #include "bsk_device.hpp"
+#include "bsk_envstep.hpp"
 #include "bsk_launch.hpp"
 
 #include <atomic>
@@ -945,7 +946,7 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
         stf(tob + 4 * SO, bo, o4);
         const int ep = ta.episodes[i];
         ta.episodes[i] = ep + 1;
-        const unsigned slot = (((unsigned)i + ta.env_base) * 2654435761u + (unsigned)ep * 40503u + 12345u) % (unsigned)n_pool;
+        const unsigned slot = pool_slot((unsigned)i + ta.env_base, (unsigned)ep, (unsigned)n_pool);
         const double* __restrict__ pool = ta.pool;
         const int nf = ta.n_fields;
         for (int f = 0; f < nf; ++f) stf(FLD(f), bo, pool[(int64_t)f * n_pool + slot]);
@@ -959,13 +960,13 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
             const double v = pool[(int64_t)(BSK_NF_BASE + k) * n_pool + slot];
             pom2 = fma(v, v, pom2);
         }
-        const double n0 = sqrt_nr(dot(ps, ps)), n1 = sqrt_nr(dot(pw, pw)), n2 = sqrt_nr(pom2) * ta.obs_cfg.inv_wheel_limit;
-        const double n3 = pool[(int64_t)(TAIL + BSK_T_CHARGE) * n_pool + slot] * ta.obs_cfg.charge_scale;
-        stf(ob + 0 * SO, bo, n0); stf(ob + 1 * SO, bo, n1); stf(ob + 2 * SO, bo, n2); stf(ob + 3 * SO, bo, n3);
-        stf(ob + 4 * SO, bo, 1.0);
+        const Obs5 f0 = first_observation(ps, pw, pom2, pool[(int64_t)(TAIL + BSK_T_CHARGE) * n_pool + slot], ta.obs_cfg.inv_wheel_limit,
+                                          ta.obs_cfg.charge_scale);
+        stf(ob + 0 * SO, bo, f0.o[0]); stf(ob + 1 * SO, bo, f0.o[1]); stf(ob + 2 * SO, bo, f0.o[2]); stf(ob + 3 * SO, bo, f0.o[3]);
+        stf(ob + 4 * SO, bo, f0.o[4]);
         if (ta.obs_rm) {
             double* __restrict__ rm = ta.obs_rm + (int64_t)i * 5;
-            rm[0] = n0; rm[1] = n1; rm[2] = n2; rm[3] = n3; rm[4] = 1.0;
+            rm[0] = f0.o[0]; rm[1] = f0.o[1]; rm[2] = f0.o[2]; rm[3] = f0.o[3]; rm[4] = f0.o[4];
         }
         *(gptr<unsigned long long>)((gptr<char>)uniform_ptr(ta.cnt) + bo) = 0ull;
       }

@@ -11,11 +11,14 @@
 //
 // What one env step does is what step_kernel does at the bare level (mode switch -> FSW chain when due, the reference's task
 // order and priorities -> RK4 sub-steps -> observation, reward, done; device-side restart from the staged pool) with the same
-// device functions (bsk_device.hpp) in the same order per value: T steps of this kernel leave every buffer of the handle - slab,
-// counters, observation / reward / reason / done mask, terminal observations, episode counts and statistics - bit for bit as
-// T launches of step_kernel do, and the history rows are what bsk_get_obs would have returned after each of them
-// (tests/test_gpu_rollout.py).  Built for the bare propagator (point mass / J2, every wheel set, diagonal and general hub).
+// device functions (bsk_device.hpp; the restart's slot rule and first observation: bsk_envstep.hpp) in the same order per value.
+// The step's outcome, statistics and FSW timing are written out here as in step_kernel and kept equal by hand.
+// T steps of this kernel leave every buffer of the handle - slab, counters, observation / reward / reason / done mask, terminal
+// observations, episode counts and statistics - bit for bit as T launches of step_kernel do, and the history rows are what
+// bsk_get_obs would have returned after each of them (tests/test_gpu_rollout.py).  Built for the bare propagator (point mass /
+// J2, every wheel set, diagonal and general hub).
 #include "bsk_device.hpp"
+#include "bsk_envstep.hpp"
 #include "bsk_launch.hpp"
 #include "bsk_rollout.hpp"
 
@@ -229,12 +232,12 @@ __global__ __launch_bounds__(256, 2) void rollout_kernel(const RolloutArgs<NRW, 
         was_reset = false;
         if (n_pool > 0 && why != 0) {
             // device-side restart (rare, divergent): the finished episode's observation is kept as terminal observation, the env
-            // continues from pool slot ((env_base + env) 2654435761 + episode 40503 + 12345) mod 2^32 mod n_pool - in the slab (every
-            // field, as step_kernel writes it) AND in this lane's registers
+            // continues from its pool slot (bsk_envstep.hpp: pool_slot) - in the slab (every field, as step_kernel writes it) AND in
+            // this lane's registers
             // (shadow lanes of the tail follow env n-1 in registers only: every global store of the restart is its own lane's)
             gptr<double> tob = uniform_ptr(ta.term_obs);
             if (valid) { stf(tob + 0 * SO, bo, o0); stf(tob + 1 * SO, bo, o1); stf(tob + 2 * SO, bo, o2); stf(tob + 3 * SO, bo, o3); stf(tob + 4 * SO, bo, o4); }
-            const unsigned slot = (((unsigned)i + ta.env_base) * 2654435761u + (unsigned)ep * 40503u + 12345u) % (unsigned)n_pool;
+            const unsigned slot = pool_slot((unsigned)i + ta.env_base, (unsigned)ep, (unsigned)n_pool);
             ep += 1;
             if (valid) ta.episodes[i] = ep;
             const double* __restrict__ pool = ta.pool;
@@ -259,8 +262,8 @@ __global__ __launch_bounds__(256, 2) void rollout_kernel(const RolloutArgs<NRW, 
             charge = pl(TAIL + BSK_T_CHARGE);
             sbr = pl(TAIL + BSK_T_SBR);
             // what the step reports as observation: the NEW episode's first one (the vec env's convention)
-            o0 = sqrt_nr(dot(x.s, x.s)); o1 = sqrt_nr(dot(x.w, x.w)); o2 = sqrt_nr(pom2) * ta.obs_cfg.inv_wheel_limit;
-            o3 = charge * ta.obs_cfg.charge_scale; o4 = 1.0;
+            const Obs5 f0 = first_observation(x.s, x.w, pom2, charge, ta.obs_cfg.inv_wheel_limit, ta.obs_cfg.charge_scale);
+            o0 = f0.o[0]; o1 = f0.o[1]; o2 = f0.o[2]; o3 = f0.o[3]; o4 = f0.o[4];
             steps0 = 0; phase = 0; tick = 0;
             was_reset = true;
         } else {
