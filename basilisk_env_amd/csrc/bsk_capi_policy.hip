@@ -1,16 +1,27 @@
 // bsk_capi_policy.hip — C-ABI of what drives an environment handle from the device: the fused MLP policy (bsk_policy_*), the
-// population of policies (bsk_population_*) and the evolution strategy (bsk_es_*).  Host side only, as bsk_capi.hip; kernels and
-// launch wrappers: bsk_policy.hip, bsk_population.hip, bsk_es.hip.
+// population of policies (bsk_population_*), the evolution strategy (bsk_es_*) and the running observation statistics that give a
+// policy its input normalisation (bsk_obs_stats_*).  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_policy.hip,
+// bsk_population.hip, bsk_es.hip, bsk_obsstats.hip.
 #include <cmath>
 #include <cstring>
 #include <initializer_list>
 
 #include "bsk_capi.hpp"
 #include "bsk_es.hpp"
+#include "bsk_obsstats.hpp"
 #include "bsk_policy.hpp"
 #include "bsk_population.hpp"
 
 using namespace bsk::capi;
+
+// bsk_obs_stats_*: sums, sums of squares and counts of the observation rows (kernels: bsk_obsstats.hip)
+struct bsk_obs_stats {
+    int device = 0;
+    int n_cap = 0;
+    void* d_block = nullptr;               // ONE allocation of 8-byte words: [part | cnt | tot | tot_n]
+    bsk::ObsStats st = {};
+    size_t words() const { return (size_t)st.waves * 11 + 11; }
+};
 
 namespace {
 
@@ -22,6 +33,7 @@ struct ParamStore {
     int n_members = 1;
     float* d_params = nullptr;             // [n_members][lay.n_device]: one device layout of the parameters (bsk_policy.hpp) per member
     unsigned long long* d_rng = nullptr;   // {seed, draw}: read by sample-mode launches, draw advanced behind each of them
+    bsk_obs_stats* stats = nullptr;        // bsk_*_set_obs_stats: what the rollouts accumulate into; not owned
 };
 
 }  // namespace
@@ -202,11 +214,15 @@ struct RolloutHist {
 // The closed loop of both rollouts, enqueued on the handle's stream with no host visit in between.  Per env step: the actions of the
 // current observations (into row t of the action history, or into d_act where none is kept), the step on them, and row t of the
 // other histories - with one step of the value rule in the SAME launch where `acc` is given, alone otherwise (no launch for no row).
+// With a statistics object attached, the observations each launch of the policy reads are accumulated in front of it - under `acc`
+// those of the envs still alive, as the previous step's launch of the value rule left them - and joined once behind the last step.
 int rollout_steps(ParamStore* p, int envs_per_member, bsk_handle* h, int mode, int substeps, int n_steps, const RolloutHist& hist,
                   int32_t* d_act, const bsk::FitnessAcc* acc, double gamma) {
     const size_t n = (size_t)h->n;
     for (int t = 0; t < n_steps; ++t) {
         int32_t* act = hist.action ? hist.action + t * n : d_act;
+        if (p->stats)
+            HIP_TRY(bsk::launch_obs_stats(h->d_obs, h->ostride, h->n, acc && t > 0 ? acc->alive : nullptr, p->stats->st, h->stream));
         int rc = launch_act(p, envs_per_member, h->d_obs, h->ostride, h->n, (int64_t)h->env_base, mode, act,
                             hist.logp ? hist.logp + t * n : nullptr, hist.value ? hist.value + t * n : nullptr, nullptr, 0, h->stream);
         if (rc) return rc;
@@ -220,6 +236,21 @@ int rollout_steps(ParamStore* p, int envs_per_member, bsk_handle* h, int mode, i
         else
             HIP_TRY(bsk::launch_hist_row(h->d_obs, h->d_reward, h->d_reason, h->ostride, h->n, obs_row, reward_row, reason_row, h->stream));
     }
+    if (p->stats) HIP_TRY(bsk::launch_obs_stats_join(p->stats->st, h->stream));
+    return BSK_OK;
+}
+
+// what a rollout refuses of an attached statistics object before anything is enqueued
+int check_stats(const ParamStore* p, const bsk_handle* h) {
+    if (!p->stats) return BSK_OK;
+    if (p->stats->device != h->device) return fail(BSK_EINVAL, "the attached observation statistics and the handle live on different devices");
+    if (h->n > p->stats->n_cap) return fail(BSK_EINVAL, "the handle's n_envs exceeds the capacity of the attached observation statistics");
+    return BSK_OK;
+}
+
+int attach_stats(ParamStore* p, const char* null_msg, bsk_obs_stats* stats) {
+    if (!p) return fail(BSK_EINVAL, null_msg);
+    p->stats = stats;
     return BSK_OK;
 }
 
@@ -257,6 +288,7 @@ void bsk_policy_destroy(bsk_policy* p) {
     delete p;
 }
 
+int bsk_policy_set_obs_stats(bsk_policy* p, bsk_obs_stats* stats) { return attach_stats(p, "policy is NULL", stats); }
 int bsk_policy_set_rng(bsk_policy* p, uint64_t seed, uint64_t draw) { return set_rng(p, "policy is NULL", seed, draw); }
 int bsk_policy_get_rng(bsk_policy* p, uint64_t* seed, uint64_t* draw) { return get_rng(p, "policy is NULL", seed, draw); }
 
@@ -277,6 +309,7 @@ int bsk_policy_rollout(bsk_policy* p, bsk_handle* h, int mode, int substeps, int
     int rc = check_act(p, "policy", 0, h->d_obs, h->ostride, h->n, (int64_t)h->env_base, mode, h->d_act, d_value_hist, nullptr, 0);
     if (rc) return rc;
     if ((rc = check_steppable(h))) return rc;
+    if ((rc = check_stats(p, h))) return rc;
     DeviceGuard guard(h->device);
     if (!d_action_hist && p->act_cap < h->n) {
         rc = grow_scratch((void**)&p->d_act, &p->act_cap, (size_t)h->ostride * sizeof(int), h->stream,
@@ -337,6 +370,7 @@ int bsk_population_get_member(bsk_population* p, int member, float* params) {
     bsk::policy_unpack(p->lay, dev.data(), params);
     return BSK_OK;
 }
+int bsk_population_set_obs_stats(bsk_population* p, bsk_obs_stats* stats) { return attach_stats(p, "population is NULL", stats); }
 int bsk_population_set_rng(bsk_population* p, uint64_t seed, uint64_t draw) { return set_rng(p, "population is NULL", seed, draw); }
 int bsk_population_get_rng(bsk_population* p, uint64_t* seed, uint64_t* draw) { return get_rng(p, "population is NULL", seed, draw); }
 
@@ -364,6 +398,7 @@ int bsk_population_rollout(bsk_population* p, bsk_handle* h, int mode, int subst
     int rc = check_act(p, "population", E, h->d_obs, h->ostride, h->n, (int64_t)h->env_base, mode, h->d_act, d_value_hist, nullptr, 0);
     if (rc) return rc;
     if ((rc = check_steppable(h))) return rc;
+    if ((rc = check_stats(p, h))) return rc;
     DeviceGuard guard(h->device);
     if (p->scratch_cap < h->n) {
         const size_t n = (size_t)h->n;                          // (a multiple of 64: every row below starts 8-byte aligned)
@@ -545,5 +580,115 @@ int bsk_es_set_moments(bsk_es* es, const double* m, const double* v, const doubl
     if (v) HIP_COPY(hipMemcpy(es->d_adam + np, v, np * sizeof(double), hipMemcpyHostToDevice));
     if (beta_pow) HIP_COPY(hipMemcpy(es->d_adam + 2 * np, beta_pow, 2 * sizeof(double), hipMemcpyHostToDevice));
     return BSK_OK;
+}
+int bsk_obs_stats_create(int n_cap, int device_id, bsk_obs_stats** out) {
+    if (!out) return fail(BSK_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (n_cap < 1 || n_cap > (1 << 28)) return fail(BSK_EINVAL, "bsk_obs_stats_create: n_cap must be in 1..2^28");
+    int rc = open_device(device_id);
+    if (rc) return rc;
+    DeviceGuard guard(device_id);
+    bsk_obs_stats* s = new bsk_obs_stats();
+    s->device = device_id;
+    s->n_cap = n_cap;
+    s->st.waves = (n_cap + 63) / 64;
+    const hipError_t e = hipMalloc(&s->d_block, s->words() * 8);
+    if (e != hipSuccess) {
+        delete s;
+        return fail(e == hipErrorOutOfMemory ? BSK_ENOMEM : BSK_EHIP, std::string("bsk_obs_stats_create: ") + hipGetErrorString(e));
+    }
+    unsigned long long* at = (unsigned long long*)s->d_block;
+    s->st.part = (double*)at; at += (size_t)s->st.waves * 10;
+    s->st.cnt = at; at += (size_t)s->st.waves;
+    s->st.tot = (double*)at; at += 10;
+    s->st.tot_n = at;
+    if ((rc = bsk_obs_stats_reset(s, nullptr)) == BSK_OK) {
+        g_n_syncs.fetch_add(1, std::memory_order_relaxed);
+        const hipError_t e2 = hipDeviceSynchronize();
+        if (e2 != hipSuccess) rc = fail(BSK_EHIP, std::string("bsk_obs_stats_create: ") + hipGetErrorString(e2));
+    }
+    if (rc) { bsk_obs_stats_destroy(s); return rc; }
+    *out = s;
+    return BSK_OK;
+}
+
+void bsk_obs_stats_destroy(bsk_obs_stats* s) {
+    if (!s) return;
+    DeviceGuard guard(s->device);
+    free_all({s->d_block});
+    delete s;
+}
+
+int bsk_obs_stats_reset(bsk_obs_stats* s, void* stream) {
+    if (!s) return fail(BSK_EINVAL, "stats is NULL");
+    DeviceGuard guard(s->device);
+    HIP_TRY(hipMemsetAsync(s->d_block, 0, s->words() * 8, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
+}
+
+int bsk_obs_stats_accumulate(bsk_obs_stats* s, const double* d_obs, int64_t obs_stride, int n, const uint8_t* d_alive, void* stream) {
+    if (!s || !d_obs) return fail(BSK_EINVAL, "stats/d_obs is NULL");
+    if (n < 1 || n > s->n_cap) return fail(BSK_EINVAL, "bsk_obs_stats_accumulate: n must be in 1..n_cap");
+    if (obs_stride < n) return fail(BSK_EINVAL, "obs_stride must be >= n");
+    DeviceGuard guard(s->device);
+    HIP_TRY(bsk::launch_obs_stats(d_obs, obs_stride, n, d_alive, s->st, (hipStream_t)stream));
+    HIP_TRY(bsk::launch_obs_stats_join(s->st, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
+}
+
+int bsk_obs_stats_get(bsk_obs_stats* s, uint64_t* count, double* mean5, double* var5) {
+    if (!s) return fail(BSK_EINVAL, "stats is NULL");
+    DeviceGuard guard(s->device);
+    unsigned long long w[11];                              // tot[10] | tot_n: neighbours in the block
+    HIP_SYNC(hipDeviceSynchronize());
+    HIP_COPY(hipMemcpy(w, s->st.tot, sizeof w, hipMemcpyDeviceToHost));
+    if (count) *count = w[10];
+    for (int k = 0; k < 5; ++k) {
+        double sum, sum_sq, mean = 0.0, var = 0.0;
+        std::memcpy(&sum, &w[k], 8);
+        std::memcpy(&sum_sq, &w[5 + k], 8);
+        if (w[10] != 0ull) bsk::obs_moments_host(sum, sum_sq, w[10], &mean, &var);
+        if (mean5) mean5[k] = mean;
+        if (var5) var5[k] = var;
+    }
+    return BSK_OK;
+}
+
+int bsk_obs_stats_totals_device(bsk_obs_stats* s, const double** d_tot10, const uint64_t** d_count) {
+    if (!s || !d_tot10 || !d_count) return fail(BSK_EINVAL, "stats/d_tot10/d_count is NULL");
+    *d_tot10 = s->st.tot;
+    *d_count = (const uint64_t*)s->st.tot_n;
+    return BSK_OK;
+}
+
+int bsk_obs_stats_get_state(bsk_obs_stats* s, double* part, uint64_t* cnt) {
+    if (!s) return fail(BSK_EINVAL, "stats is NULL");
+    DeviceGuard guard(s->device);
+    HIP_SYNC(hipDeviceSynchronize());
+    if (part) HIP_COPY(hipMemcpy(part, s->st.part, (size_t)s->st.waves * 10 * 8, hipMemcpyDeviceToHost));
+    if (cnt) HIP_COPY(hipMemcpy(cnt, s->st.cnt, (size_t)s->st.waves * 8, hipMemcpyDeviceToHost));
+    return BSK_OK;
+}
+
+int bsk_obs_stats_set_state(bsk_obs_stats* s, const double* part, const uint64_t* cnt) {
+    if (!s || !part || !cnt) return fail(BSK_EINVAL, "stats/part/cnt is NULL");
+    DeviceGuard guard(s->device);
+    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read and write the old state)
+    HIP_COPY(hipMemcpy(s->st.part, part, (size_t)s->st.waves * 10 * 8, hipMemcpyHostToDevice));
+    HIP_COPY(hipMemcpy(s->st.cnt, cnt, (size_t)s->st.waves * 8, hipMemcpyHostToDevice));
+    HIP_TRY(bsk::launch_obs_stats_join(s->st, nullptr));  // the totals are a function of the partial rows: formed again
+    HIP_SYNC(hipDeviceSynchronize());
+    return BSK_OK;
+}
+
+int bsk_es_apply_obs_norm(bsk_es* es, bsk_obs_stats* s, double std_min, void* stream) {
+    if (!es || !s) return fail(BSK_EINVAL, "es/stats is NULL");
+    if (es->frozen < 10)
+        return fail(BSK_EINVAL, "bsk_es_apply_obs_norm: frozen must be >= 10 (in_scale and in_shift would be perturbed and moved by the search)");
+    if (!std::isfinite(std_min) || !(std_min > 0.0)) return fail(BSK_EINVAL, "bsk_es_apply_obs_norm: std_min must be finite and positive");
+    if (es->device != s->device) return fail(BSK_EINVAL, "bsk_es_apply_obs_norm: the optimiser and the statistics live on different devices");
+    DeviceGuard guard(es->device);
+    HIP_TRY(bsk::launch_es_obs_norm(s->st.tot, s->st.tot_n, std_min, es->d_theta, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
 }
 }  // extern "C"

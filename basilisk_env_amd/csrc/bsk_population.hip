@@ -5,6 +5,8 @@
 // Compiled with -ffp-contract=off (Makefile), as bsk_fork.hip is: the additions and products are the ones a numpy restatement makes.
 #include "bsk_population.hpp"
 
+#include "bsk_tree.hpp"
+
 namespace bsk {
 
 // The per-env rule is bsk_select_branches' (bsk_fork.hip: select_kernel), one step per launch: while alive
@@ -48,17 +50,8 @@ hipError_t launch_fitness_row(const double* obs, const double* reward, const uns
 
 // Member m is the envs m * E .. m * E + E - 1 (E a multiple of 64).  Lane l adds its elements l, l + 64, l + 128, ... in ascending
 // order, starting FROM the first (not from zero: -0.0 stays -0.0); then s[l] = s[l] + s[l + stride] for l < stride, stride = 32, 16,
-// ..., 1; the mean is s[0] / E.  No atomics, no dependence on the launch shape: numpy repeats it (policy.py: population_fitness_ref).
-__device__ __forceinline__ double fitness_tree(double s, int lane) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_down(s, off, 64);
-        if (lane < off) s = s + o;
-    }
-    return s;
-}
-
+// ..., 1 (fitness_tree, bsk_tree.hpp); the mean is s[0] / E.  No atomics, no dependence on the launch shape: numpy repeats it
+// (policy_ref.py: population_fitness_ref).
 __global__ __launch_bounds__(256) void fitness_join_kernel(const FitnessAcc acc, int n_members, int E, double* __restrict__ env_value,
                                                            int* __restrict__ env_len, double* __restrict__ fitness,
                                                            double* __restrict__ mean_len) {

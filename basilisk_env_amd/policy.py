@@ -10,9 +10,11 @@ stable-baselines, outside the env.
 ``PolicyPopulation`` holds P parameter sets of one spec (``bsk_population_*``): member m drives envs [m * E, (m + 1) * E) of one
 propagator, one launch per env step serves all members, and the per-member fitness of a rollout is formed on the device.
 ``DeviceEvolutionStrategy`` (``bsk_es_*``) keeps theta on the device and asks, ranks and updates there, its noise regenerated from
-a counter instead of stored.
+a counter instead of stored.  ``ObsStats`` (``bsk_obs_stats_*``) keeps running sums of the observation rows on the device: attached to
+a population or a policy it is fed by their rollouts, and ``DeviceEvolutionStrategy.apply_obs_norm`` turns it into theta's in_scale
+and in_shift.
 
-The three are handles of the library and share what such a handle needs (``_DeviceObject``: create, close, the closed-handle
+The four are handles of the library and share what such a handle needs (``_DeviceObject``: create, close, the closed-handle
 refusal, ``sync``); the policy and the population are also both parameter stores that act (``_ParamStore``: the draw counter, the
 output buffers and views of ``act``, rollouts with host results) - as ``ParamStore`` is behind the two in csrc/bsk_capi_policy.hip.
 
@@ -20,7 +22,7 @@ What needs no device lives beside this module and is re-exported here under the 
 layout of the parameter block in ``policy_spec`` (``check_spec``, ``pack_params``, ...), and in ``policy_ref`` the numpy
 restatements the kernels are held to bit for bit (``mlp_ref`` / ``act_ref``: every layer output one k-ordered chain of f32 fused
 multiply-adds from the bias; ``population_fitness_ref``; ``es_noise_ref`` / ``es_ask_ref`` / ``es_tell_ref`` /
-``es_tell_adam_ref``) with ``EvolutionStrategy``, the host-side loop the device one was modelled on.
+``es_tell_adam_ref``; ``obs_stats_accumulate_ref`` / ``obs_stats_totals_ref`` / ``obs_norm_ref``) with ``EvolutionStrategy``, the host-side loop the device one was modelled on.
 """
 import ctypes as C
 import sys
@@ -31,7 +33,8 @@ from . import _hip, _lib
 from ._lib import check
 from .policy_ref import (EvolutionStrategy, _es_pair_sum, _series_log, act_ref, centred_ranks, check_adam,  # noqa: F401
                          es_ask_ref, es_inverse_normal_ref, es_noise_ref, es_tell_adam_ref, es_tell_ref, es_uniform_ref, fma32,
-                         mlp_ref, philox4x32_10, population_fitness_ref, sample_uniform, shared_slot_ref, softmax_ref)
+                         mlp_ref, obs_moments_ref, obs_norm_ref, obs_stats_accumulate_ref, obs_stats_totals_ref,
+                         obs_stats_zero_state, philox4x32_10, population_fitness_ref, sample_uniform, shared_slot_ref, softmax_ref)
 from .policy_spec import (ACTIVATIONS, MAX_HIDDEN_LAYERS, MODES, POLICY_GREEDY, POLICY_RELU, POLICY_SAMPLE,  # noqa: F401
                           POLICY_TANH, BskPolicySpec, Spec, _as_spec, c_spec, check_spec, layer_shapes, n_params, pack_params,
                           torch_layers, unpack_params)
@@ -91,9 +94,11 @@ def _host_block(values, n, dtype=np.float32, rows=0, what="parameters"):
 
 
 class _DeviceObject(object):
-    """A handle of the library on one GPU, made by ``bsk_<_kind>_create(spec, ..., device, &handle)``.  ``_out`` holds the
-    ``_hip.DeviceBuffer``s the object owns, by name (None: none yet), ``_source`` the device array a queued launch still reads."""
-    _kind = None              # policy / population / es: the C functions are bsk_<_kind>_*
+    """A handle of the library on one GPU, made by ``bsk_<_kind>_create(spec, ..., device, &handle)`` (an object without a
+    ``spec``: without that argument).  ``_out`` holds the
+    ``_hip.DeviceBuffer``s the object owns, by name (None: none yet), ``_source`` the device array a queued launch still reads,
+    ``_stats`` the ``ObsStats`` attached to it."""
+    _kind = None              # policy / population / es / obs_stats: the C functions are bsk_<_kind>_*
     _what = None              # what the object is called in a message
 
     def _c(self, name):
@@ -102,9 +107,11 @@ class _DeviceObject(object):
     def _create(self, device, *args):
         self._lib = _lib.load()
         self.device = int(device)
-        self._cs = c_spec(self.spec)
         h = C.c_void_p()
-        check(self._c("create")(C.byref(self._cs), *args, self.device, C.byref(h)))
+        if getattr(self, "spec", None) is not None:
+            self._cs = c_spec(self.spec)
+            args = (C.byref(self._cs),) + args
+        check(self._c("create")(*args, self.device, C.byref(h)))
         self._p = h
         self._out = self._source = None
 
@@ -114,7 +121,7 @@ class _DeviceObject(object):
             self._p = None
         for b in (getattr(self, "_out", None) or {}).values():
             b.free()
-        self._out = self._source = None
+        self._out = self._source = self._stats = None
 
     def __del__(self):
         try:
@@ -220,6 +227,96 @@ class _ParamStore(_DeviceObject):
             for b in bufs.values():
                 b.free()
         return host
+
+
+    def set_obs_stats(self, stats):
+        """Attaches an ``ObsStats`` (None detaches): from then on the rollouts accumulate, in front of every launch of the policy,
+        the observation the action is chosen from - one more launch per env step - and join once behind the last step.  Under a
+        population rollout that forms fitness only the episode that counts towards it is counted.  The object is kept alive, not
+        owned: close it after detaching."""
+        check(self._c("set_obs_stats")(self._handle(), None if stats is None else stats._handle()))
+        self._stats = stats
+
+
+class ObsStats(_DeviceObject):
+    """Running sums, sums of squares and counts of the five observation rows for up to ``n_envs`` spacecraft, on the device
+    (``bsk_obs_stats_*``): fed by ``accumulate`` or by the rollouts of what it is attached to (``set_obs_stats``), in a fixed
+    order and without atomics, so that ``obs_stats_accumulate_ref`` / ``obs_stats_totals_ref`` repeat it bit for bit.  Not
+    thread-safe, one stream at a time."""
+    _kind, _what = "obs_stats", "observation statistics"
+
+    def __init__(self, n_envs, device=0):
+        self.n_envs = int(n_envs)
+        self.waves = (self.n_envs + 63) // 64
+        self._create(device, self.n_envs)
+
+    def accumulate(self, obs, n=None, stride=None, alive=None, stream=0):
+        """``obs``: a device array (5, n) float64 with contiguous rows (``__cuda_array_interface__``), or a raw pointer to
+        f64[5][stride] with ``n`` (``stride`` defaults to n); ``alive``: a raw device pointer to n bytes, an array of them, or None
+        (every spacecraft counts).  Two launches on ``stream``: no copy, no synchronisation, capturable."""
+        cai = getattr(obs, "__cuda_array_interface__", None)
+        if cai is not None:
+            shape, strides = tuple(cai["shape"]), cai.get("strides")
+            if cai["typestr"] != "<f8" or len(shape) != 2 or shape[0] != 5 or shape[1] < 1:
+                raise ValueError("observations: a float64 device array of shape (5, n), got %r %r" % (cai["typestr"], shape))
+            strides = (shape[1] * 8, 8) if strides is None else tuple(strides)
+            if strides[1] != 8 or strides[0] % 8 or strides[0] < shape[1] * 8:
+                raise ValueError("observations: rows must be contiguous and at least n elements apart")
+            self._source, obs, n, stride = obs, int(cai["data"][0]), shape[1], strides[0] // 8
+        elif n is None:
+            raise ValueError("a raw observation pointer needs n")
+        stride = int(n) if stride is None else int(stride)
+        a = getattr(alive, "__cuda_array_interface__", None)
+        if a is not None:
+            if a["typestr"] not in ("|u1", "|b1") or int(np.prod(a["shape"])) != int(n):
+                raise ValueError("alive: %d bytes, got %r %r" % (n, a["typestr"], a["shape"]))
+            self._alive, alive = alive, int(a["data"][0])
+        check(self._lib.bsk_obs_stats_accumulate(self._handle(), C.c_void_p(int(obs)) if obs else None, stride, int(n),
+                                                 C.c_void_p(int(alive)) if alive else None, C.c_void_p(int(stream or 0))))
+
+    def _get(self):
+        n, mean, var = C.c_uint64(), np.empty(5, np.float64), np.empty(5, np.float64)
+        check(self._lib.bsk_obs_stats_get(self._handle(), C.byref(n), mean.ctypes.data, var.ctypes.data))
+        return n.value, mean, var
+
+    @property
+    def count(self):
+        """The number of observations counted; synchronises."""
+        return self._get()[0]
+
+    @property
+    def mean(self):
+        """float64 (5,), zeros while nothing is counted; synchronises."""
+        return self._get()[1]
+
+    @property
+    def var(self):
+        """float64 (5,), E[x^2] - mean^2 clamped at zero (``obs_moments_ref``); synchronises."""
+        return self._get()[2]
+
+    @property
+    def state(self):
+        """(part float64 (W, 10), cnt uint64 (W,)), W = ceil(n_envs / 64): what a checkpoint keeps; synchronises."""
+        part, cnt = np.empty((self.waves, 10), np.float64), np.empty(self.waves, np.uint64)
+        check(self._lib.bsk_obs_stats_get_state(self._handle(), part.ctypes.data, cnt.ctypes.data))
+        return part, cnt
+
+    def set_state(self, part, cnt):
+        """The partial rows back (``state``'s shapes); the totals are formed again.  Synchronises."""
+        part = _host_block(part, 10, np.float64, rows=self.waves, what="partial sums")
+        cnt = _host_block(cnt, self.waves, np.uint64, what="counts")
+        check(self._lib.bsk_obs_stats_set_state(self._handle(), part.ctypes.data, cnt.ctypes.data))
+
+    def reset(self, stream=0):
+        """Everything back to zero: one memset on ``stream``."""
+        check(self._lib.bsk_obs_stats_reset(self._handle(), C.c_void_p(int(stream or 0))))
+
+    def totals_ptr(self):
+        """-> (pointer to tot float64[10], pointer to the count uint64): DEVICE words, valid until ``close``, as fresh as the last
+        join."""
+        t, n = C.c_void_p(), C.c_void_p()
+        check(self._lib.bsk_obs_stats_totals_device(self._handle(), C.byref(t), C.byref(n)))
+        return t.value, n.value
 
 
 class DevicePolicy(_ParamStore):
@@ -487,14 +584,24 @@ class DeviceEvolutionStrategy(_DeviceObject):
             self._out = {"fitness": _hip.DeviceBuffer(8 * self.population, self.device)}
         return self._out["fitness"]
 
-    def run_generation(self, prop, pop, n_steps, substeps, mode="greedy", gamma=1.0, reset=True, shared_episodes=False):
+    def apply_obs_norm(self, stats, std_min=1e-6, stream=0):
+        """theta[0:5] = in_scale, theta[5:10] = in_shift out of ``stats``' totals (``obs_norm_ref``): one launch on ``stream``, no
+        copy, no synchronisation.  A row whose standard deviation is below ``std_min`` gets scale 0; nothing is written while
+        nothing has been counted.  Needs ``frozen >= 10``; the next ``ask`` carries the ten floats into every member."""
+        check(self._lib.bsk_es_apply_obs_norm(self._handle(), stats._handle(), float(std_min), C.c_void_p(int(stream or 0))))
+
+    def run_generation(self, prop, pop, n_steps, substeps, mode="greedy", gamma=1.0, reset=True, shared_episodes=False, obs_stats=None,
+                       std_min=1e-6):
         """One generation on the propagator's stream: every env restarted from the propagator's IC pool (``reset``; needs an
         auto-reset pool), ``ask``, ``pop.rollout_device`` with the fitness into ``fitness_buffer()``, ``tell``.  Nothing else is
         issued - no copy, no synchronisation - so after one warming call (it allocates the buffer and the population's scratch
         rows) a call can be captured into a graph and replayed generation after generation.  ``shared_episodes``: the reset is
         ``reset_from_pool_shared`` with E = n_envs // population and the generation word as the epoch, so that all members of a
         generation are scored on the same E initial conditions and every generation draws new ones; nothing else in the stream
-        changes.  That is exact for ``greedy``: sample mode still draws its uniform per global env index."""
+        changes.  That is exact for ``greedy``: sample mode still draws its uniform per global env index.
+        ``obs_stats``: an ``ObsStats`` the rollout accumulates into (attached to ``pop`` for the rollout, which is left with what it
+        had attached before), and ``apply_obs_norm(obs_stats, std_min)`` behind ``tell``: generation g runs with the statistics of
+        the generations before it."""
         prop = getattr(prop, "propagator", prop)
         fit = self.fitness_buffer()
         stream = prop.stream_ptr()
@@ -503,5 +610,15 @@ class DeviceEvolutionStrategy(_DeviceObject):
         elif reset:
             prop.reset_from_pool_device(None)
         self.ask(pop, stream)
-        pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr)
+        if obs_stats is None:
+            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr)
+            self.tell(fit.ptr, stream)
+            return
+        before = getattr(pop, "_stats", None)
+        pop.set_obs_stats(obs_stats)
+        try:
+            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr)
+        finally:
+            pop.set_obs_stats(before)
         self.tell(fit.ptr, stream)
+        self.apply_obs_norm(obs_stats, std_min, stream)

@@ -4,7 +4,9 @@ Each function repeats, operation by operation and in the kernel's order, what in
 layer output one k-ordered chain of ``fma32`` from the bias), the action choice (``act_ref``, ``softmax_ref``, the Philox draw of
 ``sample_uniform``), the per-member fitness of a rollout (``population_fitness_ref``), and the evolution strategy - its noise
 (``es_noise_ref``: Philox, then Wichura's AS 241 with a series logarithm), members (``es_ask_ref``), ranking (``centred_ranks``) and the
-SGD and Adam updates (``es_tell_ref``, ``es_tell_adam_ref``) - with ``shared_slot_ref`` for the shared-episode reset.
+SGD and Adam updates (``es_tell_ref``, ``es_tell_adam_ref``) - with ``shared_slot_ref`` for the shared-episode reset, and the running
+observation statistics with the input normalisation out of them (``obs_stats_accumulate_ref``, ``obs_stats_totals_ref``,
+``obs_norm_ref``).
 ``EvolutionStrategy`` is the host-side search the device one was modelled on.  Needs numpy and ``policy_spec`` only: no device, no
 library.  The tests compare these with the device for equality, so the order of operations and the ``np.errstate`` scopes are part
 of what they state.
@@ -408,3 +410,88 @@ def shared_slot_ref(n, envs_per_member, epoch, n_pool, env_base=0):
     q = g % np.uint64(E)
     e = np.uint64(int(epoch) & 0xFFFFFFFF)
     return (((q * np.uint64(2654435761) + e * np.uint64(40503) + np.uint64(12345)) & mask) % np.uint64(n_pool)).astype(np.uint32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Running observation statistics (bsk_obs_stats_*; definition in include/bskgpu.h, kernels in csrc/bsk_obsstats.hip), restated
+
+_TREE = (32, 16, 8, 4, 2, 1)
+
+
+def obs_stats_zero_state(n_cap):
+    """The state of a new statistics object of capacity ``n_cap`` -> (part float64 (W, 10), cnt uint64 (W,)), W = ceil(n_cap / 64)."""
+    W = (int(n_cap) + 63) // 64
+    if W < 1:
+        raise ValueError("n_cap must be >= 1")
+    return np.zeros((W, 10), np.float64), np.zeros(W, np.uint64)
+
+
+def obs_stats_accumulate_ref(state, obs5n, alive=None):
+    """One ``bsk_obs_stats_accumulate`` -> the new (part, cnt); ``state`` is not changed.  ``obs5n`` (5, n) float64, ``alive`` (n,) or
+    None (every spacecraft counts).  Wave w is the spacecraft 64 w .. 64 w + 63; a lane that does not count brings +0.0; x and
+    x * x each go through the fitness tree (stride 32 ... 1) and the wave's ten sums are added to part[w], the number of counting
+    lanes to cnt[w]; a wave in which no lane counts is left alone."""
+    part, cnt = np.array(state[0], dtype=np.float64), np.array(state[1], dtype=np.uint64)
+    obs = np.asarray(obs5n, np.float64)
+    if part.ndim != 2 or part.shape[1] != 10 or cnt.shape != (part.shape[0],):
+        raise ValueError("state: part (W, 10) and cnt (W,)")
+    if obs.ndim != 2 or obs.shape[0] != 5 or not (1 <= obs.shape[1] <= 64 * part.shape[0]):
+        raise ValueError("observations: (5, n) with 1 <= n <= 64 * W")
+    n = obs.shape[1]
+    counts = np.ones(n, bool) if alive is None else np.asarray(alive).reshape(-1) != 0
+    if counts.size != n:
+        raise ValueError("alive: one byte per spacecraft")
+    nw = (n + 63) // 64
+    x = np.zeros((5, nw * 64), np.float64)
+    x[:, :n] = np.where(counts, obs, 0.0)
+    lanes = np.zeros(nw * 64, bool)
+    lanes[:n] = counts
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        s = np.concatenate([x, x * x]).reshape(10, nw, 64)
+        for stride in _TREE:
+            s[:, :, :stride] = s[:, :, :stride] + s[:, :, stride:2 * stride]
+        live = lanes.reshape(nw, 64).sum(axis=1)
+        stores = np.flatnonzero(live > 0)
+        part[stores] = part[stores] + s[:, stores, 0].T
+    cnt[:nw] = cnt[:nw] + live.astype(np.uint64)
+    return part, cnt
+
+
+def obs_stats_totals_ref(state):
+    """The join -> (tot float64 (10,), count int): per column lane l adds part[w] for w = l, l + 64, ... ascending from the first
+    (+0.0 with no element), the lanes join in the fitness tree; count is the sum of cnt."""
+    part, cnt = np.asarray(state[0], np.float64), np.asarray(state[1], np.uint64)
+    W = part.shape[0]
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = np.zeros((64, 10), np.float64)
+        s[:min(64, W)] = part[:64]
+        for at in range(64, W, 64):
+            chunk = part[at:at + 64]
+            s[:len(chunk)] = s[:len(chunk)] + chunk
+        for stride in _TREE:
+            s[:stride] = s[:stride] + s[stride:2 * stride]
+    return s[0].copy(), sum(int(c) for c in cnt)
+
+
+def obs_moments_ref(tot, count):
+    """-> (mean, var) float64 (5,) each of count > 0 observations: mean = tot[k] / N, var = max(tot[5 + k] / N - mean * mean, 0)."""
+    tot = np.asarray(tot, np.float64).reshape(10)
+    N = np.float64(int(count))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        mean = tot[:5] / N
+        var = tot[5:] / N - mean * mean
+    return mean, np.where(var > 0, var, 0.0)
+
+
+def obs_norm_ref(tot, count, std_min):
+    """What ``bsk_es_apply_obs_norm`` writes -> (in_scale, in_shift) float64 (5,) each, or None while count == 0 (nothing is
+    written): sd = sqrt(var), scale = 1 / sd where sd >= std_min and 0 elsewhere - a row that has not varied is switched off, the
+    rule of ARS - and shift = 0 - mean * scale."""
+    if int(count) == 0:
+        return None
+    mean, var = obs_moments_ref(tot, count)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        sd = np.sqrt(var)
+        scale = np.where(sd >= np.float64(std_min), np.float64(1.0) / sd, 0.0)
+        shift = np.float64(0.0) - mean * scale
+    return scale, shift

@@ -670,6 +670,77 @@ int bsk_es_set_optimizer(bsk_es* es, int kind, double beta1, double beta2, doubl
 int bsk_es_get_moments(bsk_es* es, double* m, double* v, double* beta_pow);
 int bsk_es_set_moments(bsk_es* es, const double* m, const double* v, const double* beta_pow);
 
+/* Running statistics of the five observation rows, formed on the device: what gives a policy its in_scale / in_shift.  Salimans et
+ * al. 2017 and ARS V2 (Mania et al. 2018) normalise the observations by the mean and standard deviation of everything the search
+ * has seen so far; the sums behind them are a reduction over data that already lies in the handle's observation rows when the
+ * policy launch reads them, so they are formed there, in the stream and in a fixed order, like the fitness.  Opt-in: with no
+ * statistics object attached every entry point issues the launches it issued before and leaves the same bits.
+ * All arithmetic is f64 with plain + - * / and sqrt, each operation rounded on its own (no FMA); no atomics, and no result depends
+ * on the launch shape (basilisk_env_amd/policy_ref.py repeats it bit for bit: obs_stats_accumulate_ref, obs_stats_totals_ref,
+ * obs_norm_ref).
+ * An object of capacity n_cap spacecraft owns, with W = ceil(n_cap / 64), in device memory and all zero after creation:
+ *     part[w][0..9] f64, w = 0 .. W - 1: per wave of 64 spacecraft, entries 0..4 the sums and entries 5..9 the sums of squares of
+ *                   the observation rows k = 0 .. 4;   cnt[w] uint64: the number of observations behind them;
+ *     tot[0..9] f64 and tot_n uint64: their totals.
+ * accumulate, given d_obs f64[5][obs_stride], n and d_alive uint8[n] or NULL - ONE launch, one lane per spacecraft, wave w the
+ * spacecraft 64 w .. 64 w + 63:
+ *     lane l of wave w has i = 64 w + l and COUNTS when i < n and (d_alive is NULL or d_alive[i] != 0);
+ *     per row k:  x = counts ? obs[k][i] : +0.0;   q = x * x;   s1[l] = x, s2[l] = q;
+ *     each of the ten values through the fitness tree: for stride = 32, 16, 8, 4, 2, 1:  s[l] = s[l] + s[l + stride] for l < stride;
+ *     part[w][k] = part[w][k] + s1[0];   part[w][5 + k] = part[w][5 + k] + s2[0];   cnt[w] = cnt[w] + the number of lanes that count;
+ *     a wave in which no lane counts stores nothing.
+ *   join, a second launch behind it (behind the LAST step where a rollout accumulates), for each of the ten columns c:
+ *     s[l] = part[l][c], or +0.0 when l >= W;  s[l] = s[l] + part[l + 64 m][c] for m = 1, 2, ... ascending while l + 64 m < W
+ *     the tree again;  tot[c] = s[0];   tot_n = the sum of cnt[0 .. W - 1] (integer).
+ * The normalisation out of the totals (bsk_es_apply_obs_norm), per row k; nothing is written while tot_n == 0:
+ *     N = (double)tot_n;   mean = tot[k] / N;   e2 = tot[5 + k] / N;   var = e2 - mean * mean;   var = var > 0 ? var : 0;
+ *     sd = sqrt(var);   scale = sd >= std_min ? 1.0 / sd : 0.0;   shift = 0.0 - mean * scale;
+ *     theta[k] = scale (in_scale_k);   theta[5 + k] = shift (in_shift_k).
+ *   A row that has not varied - the fifth at the start of training - is switched off (scale = 0) and never multiplied by 1 / tiny:
+ *   the rule of ARS.  There is no clip: the policy's definition has none.
+ * A statistics object belongs to one device, is not thread-safe and serves ONE stream at a time. */
+typedef struct bsk_obs_stats bsk_obs_stats;
+/* BSK_EINVAL for a NULL `out` and n_cap outside 1..2^28; then the device (BSK_ENODEV when no gfx950 device is usable).
+ * Synchronises the device. */
+int bsk_obs_stats_create(int n_cap, int device_id, bsk_obs_stats** out);
+/* The object is not owned by what it is attached to: destroying one that is still attached to a policy or a population (detach
+ * with NULL first) is the caller's error.  Waits for the device first, like every destroy. */
+void bsk_obs_stats_destroy(bsk_obs_stats* stats);
+/* The two launches above on `stream` (a hipStream_t, NULL = the null stream) of the object's device: raw DEVICE pointers, no copy,
+ * no synchronisation, capturable.  d_obs in the layout of bsk_get_obs_device.  BSK_EINVAL before anything is launched: a NULL
+ * stats or d_obs, n < 1, n > n_cap, obs_stride < n. */
+int bsk_obs_stats_accumulate(bsk_obs_stats* stats, const double* d_obs, int64_t obs_stride, int n, const uint8_t* d_alive, void* stream);
+/* tot_n and, per row, mean and var as defined above (var after the clamp), formed on the host from the totals with the operations
+ * of the kernel; all three +0 while nothing has been counted.  Each pointer may be NULL.  Ordered after everything queued on the
+ * object's device; synchronises it. */
+int bsk_obs_stats_get(bsk_obs_stats* stats, uint64_t* count, double* mean5, double* var5);
+/* tot[10] and tot_n as DEVICE words (read-only for the caller; valid for the object's lifetime and as fresh as the last join).  No
+ * launch, no copy, no synchronisation.  BSK_EINVAL for NULL pointers. */
+int bsk_obs_stats_totals_device(bsk_obs_stats* stats, const double** d_tot10, const uint64_t** d_count);
+/* The partial rows to / from host memory, part f64[W][10] and cnt uint64[W]: what a checkpoint needs to resume bit for bit (the
+ * totals are a function of them, and set forms them again).  get: either may be NULL; set: BSK_EINVAL for a NULL one.  Both
+ * synchronise the device. */
+int bsk_obs_stats_get_state(bsk_obs_stats* stats, double* part, uint64_t* cnt);
+int bsk_obs_stats_set_state(bsk_obs_stats* stats, const double* part, const uint64_t* cnt);
+/* Everything back to zero: one memset on `stream`, no copy, no synchronisation. */
+int bsk_obs_stats_reset(bsk_obs_stats* stats, void* stream);
+/* Attach `stats` to a population / a policy (NULL detaches).  From then on bsk_population_rollout / bsk_policy_rollout accumulate,
+ * on the handle's stream and in front of every launch of the policy, the observation the action is chosen FROM, and join once
+ * behind the last step: one more launch per env step, one more per rollout.  A population rollout that forms fitness (any of its
+ * four fitness outputs given) counts with d_alive = NULL at step 0 and with the alive bytes of its value rule afterwards - as the
+ * previous step left them - so exactly the observations of the episode that counts towards the fitness are counted, and tot_n
+ * grows by the sum of d_env_len; every other rollout counts every env at every step.  The rollout returns BSK_EINVAL before
+ * anything is launched when the handle's n_envs exceeds the capacity of the attached object or the two live on different devices.
+ * BSK_EINVAL for a NULL population / policy. */
+int bsk_population_set_obs_stats(bsk_population* pop, bsk_obs_stats* stats);
+int bsk_policy_set_obs_stats(bsk_policy* p, bsk_obs_stats* stats);
+/* The normalisation above, straight into the optimiser's device theta[0..9]: ONE launch of five threads on `stream`, no copy, no
+ * synchronisation, capturable.  bsk_es_ask writes (float)theta_j of frozen parameters into every member, so the next generation
+ * runs normalised with no further call.  BSK_EINVAL before anything is launched: NULL pointers, an optimiser with frozen < 10
+ * (the search would perturb and move what this call sets), std_min not finite or not positive, optimiser and statistics on
+ * different devices. */
+int bsk_es_apply_obs_norm(bsk_es* es, bsk_obs_stats* stats, double std_min, void* stream);
+
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the
  * three-wave form's barrier-free exchange gives up after 2^20 polls instead of hanging, and says so here. */

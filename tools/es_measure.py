@@ -11,14 +11,16 @@
         rollout reset from the pool and `rollout_device` alone: what the device loop is expected to approach
         adam    `run_generation` of an optimiser created with optimizer="adam"
         shared  `run_generation(..., shared_episodes=True)`: the reset that gives all members the same episodes
-  python tools/es_measure.py kernel [adam]
+        obsnorm `run_generation(..., obs_stats=...)`: one obs_stats_kernel launch in front of every policy launch, the join and
+                the normalisation behind the generation
+  python tools/es_measure.py kernel [adam | obs]
       per P one warming and three measured generations of `run_generation` (`adam`: of an optimizer="adam" optimiser on shared
-      episodes).  Run it under the profiler in a run of its own:
+      episodes; `obs`: with an `ObsStats` given).  Run it under the profiler in a run of its own:
       rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o es -- python tools/es_measure.py kernel
   python tools/es_measure.py stats DIR/.../es_kernel_trace.csv
       per measured generation of that run the times of es_ask_kernel, es_rank_kernel and es_tell_kernel (or es_tell_adam_kernel)
       and the sum over every other kernel of the generation (the generations are recognised by the es_advance_kernel or
-      es_advance_adam_kernel that ends each)
+      es_advance_adam_kernel that ends each); of a `kernel obs` run also obs_stats_kernel, per generation and per launch
 """
 import csv
 import os
@@ -60,6 +62,8 @@ def loop():
             rep = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
             adam = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1, optimizer="adam")
             shared = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
+            normed = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
+            obs_stats = P.ObsStats(N)
             fit = torch.zeros(m, dtype=torch.float64, device="cuda")
 
             def host_gen(steps, pop=pop, host=host):
@@ -80,6 +84,9 @@ def loop():
             def shared_gen(steps, pop=pop, shared=shared):
                 shared.run_generation(prop, pop, steps, 1, "greedy", GAMMA, shared_episodes=True)
 
+            def obsnorm_gen(steps, pop=pop, normed=normed, obs_stats=obs_stats):
+                normed.run_generation(prop, pop, steps, 1, "greedy", GAMMA, obs_stats=obs_stats)
+
             rep.run_generation(prop, pop, WARM_T, 1, "greedy", GAMMA)
             prop.sync()
             graph = torch.cuda.CUDAGraph()
@@ -91,7 +98,8 @@ def loop():
                     graph.replay()
 
             variants += [("host   P = %d" % m, host_gen), ("device P = %d" % m, device_gen), ("graph  P = %d" % m, graph_gen),
-                         ("rollout P = %d" % m, rollout_gen), ("adam   P = %d" % m, adam_gen), ("shared P = %d" % m, shared_gen)]
+                         ("rollout P = %d" % m, rollout_gen), ("adam   P = %d" % m, adam_gen), ("shared P = %d" % m, shared_gen),
+                         ("obsnorm P = %d" % m, obsnorm_gen)]
         res = {name: [] for name, _ in variants}
         for _ in range(ROUNDS):
             for name, run in variants:
@@ -106,15 +114,16 @@ def loop():
     env.close()
 
 
-def kernel(adam=False):
+def kernel(adam=False, obs=False):
     torch, P, side, env, prop, spec, theta = _setup()
     with torch.cuda.stream(side):
         for m in MEMBERS:
             pop = P.PolicyPopulation(spec, n_members=m)
             dev = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1, optimizer="adam" if adam else "sgd")
-            dev.run_generation(prop, pop, WARM_T, 1, "greedy", GAMMA, shared_episodes=adam)
+            obs_stats = P.ObsStats(N) if obs else None
+            dev.run_generation(prop, pop, WARM_T, 1, "greedy", GAMMA, shared_episodes=adam, obs_stats=obs_stats)
             for _ in range(ROUNDS):
-                dev.run_generation(prop, pop, T, 1, "greedy", GAMMA, shared_episodes=adam)
+                dev.run_generation(prop, pop, T, 1, "greedy", GAMMA, shared_episodes=adam, obs_stats=obs_stats)
             prop.sync()
     print("per P in %r: one warming generation of %d steps, then %d of %d steps" % (MEMBERS, WARM_T, ROUNDS, T))
     env.close()
@@ -128,7 +137,8 @@ def stats(path):
     rows.sort()
     gens, cur, seen = [], {}, False
     for _, d, name in rows:
-        key = next((k for k in ("es_ask_kernel", "es_rank_kernel", "es_tell_kernel", "es_advance_kernel") if k in name.replace("_adam", "")), "rest")
+        key = next((k for k in ("es_ask_kernel", "es_rank_kernel", "es_tell_kernel", "es_advance_kernel", "obs_stats_kernel")
+                    if k in name.replace("_adam", "")), "rest")
         seen = seen or key == "es_ask_kernel"
         if not seen:
             continue                           # (the set-up's launches, before the first generation)
@@ -142,6 +152,9 @@ def stats(path):
             # (tell: es_tell_kernel, or es_tell_adam_kernel in a `kernel adam` run)
             print("P = %-5d ask %8.1f us, rank %7.1f us, tell %8.1f us, every other kernel of the generation %9.1f us" %
                   (m, g["es_ask_kernel"] / 1e3, g["es_rank_kernel"] / 1e3, g["es_tell_kernel"] / 1e3, g["rest"] / 1e3))
+            if "obs_stats_kernel" in g:        # (a `kernel obs` run: T launches per generation, one in front of every policy launch)
+                print("          obs_stats_kernel %8.1f us per generation, %.2f us per launch" %
+                      (g["obs_stats_kernel"] / 1e3, g["obs_stats_kernel"] / 1e3 / T))
 
 
 if __name__ == "__main__":
@@ -150,7 +163,7 @@ if __name__ == "__main__":
     if what == "loop":
         loop()
     elif what == "kernel":
-        kernel(adam=len(sys.argv) > 2 and sys.argv[2] == "adam")
+        kernel(adam=sys.argv[2:3] == ["adam"], obs=sys.argv[2:3] == ["obs"])
     elif what == "stats":
         stats(sys.argv[2])
     else:
