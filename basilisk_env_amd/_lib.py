@@ -66,6 +66,7 @@ class BskConfig(C.Structure):
 POLICY_RELU, POLICY_TANH = 0, 1
 POLICY_GREEDY, POLICY_SAMPLE = 0, 1
 ES_SGD, ES_ADAM = 0, 1
+ES_SIGMA_FIXED, ES_SIGMA_PGPE = 0, 1
 
 
 class BskPolicySpec(C.Structure):
@@ -88,6 +89,7 @@ EXPORTS = [
     "bsk_population_set_params_device", "bsk_population_get_member", "bsk_population_act", "bsk_population_rollout",
     "bsk_es_create", "bsk_es_destroy", "bsk_es_ask", "bsk_es_tell", "bsk_es_get_state", "bsk_es_set_state",
     "bsk_es_generation_device", "bsk_es_set_optimizer", "bsk_es_get_moments", "bsk_es_set_moments",
+    "bsk_es_set_sigma_adaptation", "bsk_es_get_sigma", "bsk_es_set_sigma",
     "bsk_obs_stats_create", "bsk_obs_stats_destroy", "bsk_obs_stats_accumulate", "bsk_obs_stats_get", "bsk_obs_stats_totals_device",
     "bsk_obs_stats_get_state", "bsk_obs_stats_set_state", "bsk_obs_stats_reset", "bsk_population_set_obs_stats",
     "bsk_policy_set_obs_stats", "bsk_es_apply_obs_norm",
@@ -137,6 +139,8 @@ def _signatures():
         "bsk_es_set_state": ([vp, vp, u64], rc), "bsk_es_generation_device": ([vp, P(vp)], rc),
         "bsk_es_set_optimizer": ([vp, i, f64, f64, f64, f64], rc), "bsk_es_get_moments": ([vp, vp, vp, vp], rc),
         "bsk_es_set_moments": ([vp, vp, vp, vp], rc),
+        "bsk_es_set_sigma_adaptation": ([vp, i, f64, f64, f64, f64], rc), "bsk_es_get_sigma": ([vp, vp], rc),
+        "bsk_es_set_sigma": ([vp, vp], rc),
         "bsk_obs_stats_create": ([i, i, P(vp)], rc), "bsk_obs_stats_destroy": ([vp], None),
         "bsk_obs_stats_accumulate": ([vp, vp, i64, i, vp, vp], rc), "bsk_obs_stats_get": ([vp, P(u64), vp, vp], rc),
         "bsk_obs_stats_totals_device": ([vp, P(vp), P(vp)], rc), "bsk_obs_stats_get_state": ([vp, vp, vp], rc),

@@ -64,11 +64,16 @@ struct bsk_es {
     int frozen = 0;
     unsigned long long* d_state = nullptr; // {seed, generation}: generation advanced behind every tell
     double* d_theta = nullptr;             // [lay.n_params]
-    double* d_w = nullptr;                 // [n_members / 2]: bsk_es_tell's scratch, the utility difference of every pair
+    double* d_w = nullptr;                 // [w | q], n_members / 2 each: bsk_es_tell's scratch, the difference (and, under
+                                           // BSK_ES_SIGMA_PGPE, the sum) of every pair's two utilities
     // bsk_es_set_optimizer: BSK_ES_SGD until Adam is selected; then ONE allocation [m | v | beta_pow] of 2 * n_params + 2 doubles
     int optimizer = BSK_ES_SGD;
     double beta1 = 0.0, beta2 = 0.0, eps = 0.0, weight_decay = 0.0;
     double* d_adam = nullptr;
+    // bsk_es_set_sigma_adaptation: BSK_ES_SIGMA_FIXED until PGPE is selected; then sigma_vec [n_params]
+    int sigma_kind = BSK_ES_SIGMA_FIXED;
+    double lr_sigma = 0.0, max_change = 0.0, sigma_min = 0.0, sigma_max = 0.0;
+    double* d_sigma = nullptr;
 };
 
 namespace {
@@ -443,7 +448,7 @@ int bsk_es_create(const bsk_policy_spec* spec, int n_members, const float* theta
             for (int j = 0; j < lay.n_params; ++j) theta0[(size_t)j] = (double)theta[j];
         HIP_TRY(hipMalloc(&es->d_state, sizeof state0));
         HIP_TRY(hipMalloc(&es->d_theta, theta0.size() * sizeof(double)));
-        HIP_TRY(hipMalloc(&es->d_w, (size_t)(n_members / 2) * sizeof(double)));
+        HIP_TRY(hipMalloc(&es->d_w, (size_t)n_members * sizeof(double)));
         HIP_COPY(hipMemcpy(es->d_state, state0, sizeof state0, hipMemcpyHostToDevice));
         HIP_COPY(hipMemcpy(es->d_theta, theta0.data(), theta0.size() * sizeof(double), hipMemcpyHostToDevice));
         return BSK_OK;
@@ -453,7 +458,7 @@ int bsk_es_create(const bsk_policy_spec* spec, int n_members, const float* theta
 void bsk_es_destroy(bsk_es* es) {
     if (!es) return;
     DeviceGuard guard(es->device);
-    free_all({es->d_state, es->d_theta, es->d_w, es->d_adam});
+    free_all({es->d_state, es->d_theta, es->d_w, es->d_adam, es->d_sigma});
     delete es;
 }
 
@@ -467,6 +472,17 @@ static bsk::EsArgs es_args(const bsk_es* es) {
     return a;
 }
 
+static bsk::EsSigma es_sigma(const bsk_es* es) {
+    bsk::EsSigma sv;
+    sv.sigma_vec = es->d_sigma;
+    sv.pd = (double)es->n_members;
+    sv.cs = es->lr_sigma / sv.pd;
+    sv.max_change = es->max_change;
+    sv.sigma_min = es->sigma_min;
+    sv.sigma_max = es->sigma_max;
+    return sv;
+}
+
 int bsk_es_ask(bsk_es* es, bsk_population* pop, void* stream) {
     if (!es || !pop) return fail(BSK_EINVAL, "es/population is NULL");
     if (pop->n_members != es->n_members) return fail(BSK_EINVAL, "bsk_es_ask: the population's n_members differs from the optimiser's");
@@ -474,14 +490,22 @@ int bsk_es_ask(bsk_es* es, bsk_population* pop, void* stream) {
         return fail(BSK_EINVAL, "bsk_es_ask: the population's spec differs from the optimiser's");
     if (pop->device != es->device) return fail(BSK_EINVAL, "bsk_es_ask: the optimiser and the population live on different devices");
     DeviceGuard guard(es->device);
-    HIP_TRY(bsk::launch_es_ask(es->lay, es_args(es), pop->d_params, (hipStream_t)stream));
+    if (es->sigma_kind == BSK_ES_SIGMA_PGPE)
+        HIP_TRY(bsk::launch_es_ask_sigma(es->lay, es_args(es), es->d_sigma, pop->d_params, (hipStream_t)stream));
+    else
+        HIP_TRY(bsk::launch_es_ask(es->lay, es_args(es), pop->d_params, (hipStream_t)stream));
     return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
 }
 
 int bsk_es_tell(bsk_es* es, const double* d_fitness, void* stream) {
     if (!es || !d_fitness) return fail(BSK_EINVAL, "es/d_fitness is NULL");
     DeviceGuard guard(es->device);
-    HIP_TRY(bsk::launch_es_rank(d_fitness, es->n_members, es->d_w, (hipStream_t)stream));
+    const bool pgpe = es->sigma_kind == BSK_ES_SIGMA_PGPE;
+    double* d_q = es->d_w + es->n_members / 2;
+    if (pgpe)
+        HIP_TRY(bsk::launch_es_rank_q(d_fitness, es->n_members, es->d_w, d_q, (hipStream_t)stream));
+    else
+        HIP_TRY(bsk::launch_es_rank(d_fitness, es->n_members, es->d_w, (hipStream_t)stream));
     if (es->optimizer == BSK_ES_ADAM) {
         const size_t np = (size_t)es->lay.n_params;
         bsk::EsAdam ad;
@@ -493,12 +517,19 @@ int bsk_es_tell(bsk_es* es, const double* d_fitness, void* stream) {
         ad.eps = es->eps; ad.weight_decay = es->weight_decay;
         ad.cg = 1.0 / ((double)es->n_members * es->sigma);
         ad.lr = es->lr;
-        HIP_TRY(bsk::launch_es_tell_adam(es_args(es), es->lay.n_params, es->d_w, ad, (hipStream_t)stream));
+        if (pgpe)
+            HIP_TRY(bsk::launch_es_tell_adam_sigma(es_args(es), es->lay.n_params, es->d_w, d_q, ad, es_sigma(es), (hipStream_t)stream));
+        else
+            HIP_TRY(bsk::launch_es_tell_adam(es_args(es), es->lay.n_params, es->d_w, ad, (hipStream_t)stream));
         HIP_TRY(bsk::launch_es_advance_adam(es->d_state, es->d_adam + 2 * np, es->beta1, es->beta2, (hipStream_t)stream));
         return BSK_OK;
     }
-    const double c = es->lr / ((double)es->n_members * es->sigma);
-    HIP_TRY(bsk::launch_es_tell(es_args(es), es->lay.n_params, es->d_w, c, (hipStream_t)stream));
+    if (pgpe) {
+        HIP_TRY(bsk::launch_es_tell_sigma(es_args(es), es->lay.n_params, es->d_w, d_q, es->lr, es_sigma(es), (hipStream_t)stream));
+    } else {
+        const double c = es->lr / ((double)es->n_members * es->sigma);
+        HIP_TRY(bsk::launch_es_tell(es_args(es), es->lay.n_params, es->d_w, c, (hipStream_t)stream));
+    }
     HIP_TRY(bsk::launch_es_advance(es->d_state, (hipStream_t)stream));
     return BSK_OK;
 }
@@ -581,6 +612,57 @@ int bsk_es_set_moments(bsk_es* es, const double* m, const double* v, const doubl
     if (beta_pow) HIP_COPY(hipMemcpy(es->d_adam + 2 * np, beta_pow, 2 * sizeof(double), hipMemcpyHostToDevice));
     return BSK_OK;
 }
+
+int bsk_es_set_sigma_adaptation(bsk_es* es, int kind, double lr_sigma, double max_change, double sigma_min, double sigma_max) {
+    const char* const fn = "bsk_es_set_sigma_adaptation: ";
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    if (kind != BSK_ES_SIGMA_FIXED && kind != BSK_ES_SIGMA_PGPE)
+        return fail(BSK_EINVAL, std::string(fn) + "kind must be BSK_ES_SIGMA_FIXED or BSK_ES_SIGMA_PGPE");
+    if (kind == BSK_ES_SIGMA_PGPE) {
+        if (!std::isfinite(lr_sigma) || lr_sigma < 0.0) return fail(BSK_EINVAL, std::string(fn) + "lr_sigma must be finite and not negative");
+        if (!std::isfinite(max_change) || !(max_change > 0.0 && max_change < 1.0))
+            return fail(BSK_EINVAL, std::string(fn) + "max_change must be inside (0, 1)");
+        if (!std::isfinite(sigma_min) || !(sigma_min > 0.0)) return fail(BSK_EINVAL, std::string(fn) + "sigma_min must be finite and positive");
+        if (!std::isfinite(sigma_max) || sigma_max < sigma_min)
+            return fail(BSK_EINVAL, std::string(fn) + "sigma_max must be finite and not below sigma_min");
+        if (es->sigma < sigma_min || es->sigma > sigma_max)
+            return fail(BSK_EINVAL, std::string(fn) + "the sigma of bsk_es_create must be inside [sigma_min, sigma_max]");
+    }
+    DeviceGuard guard(es->device);
+    HIP_SYNC(hipDeviceSynchronize());                     // (queued asks and tells still use the old rule and the old vector)
+    if (kind == BSK_ES_SIGMA_FIXED) {
+        es->sigma_kind = BSK_ES_SIGMA_FIXED;
+        return BSK_OK;
+    }
+    const size_t np = (size_t)es->lay.n_params;
+    if (!es->d_sigma) HIP_TRY(hipMalloc(&es->d_sigma, np * sizeof(double)));
+    const std::vector<double> fill(np, es->sigma);
+    HIP_COPY(hipMemcpy(es->d_sigma, fill.data(), np * sizeof(double), hipMemcpyHostToDevice));
+    es->sigma_kind = BSK_ES_SIGMA_PGPE;
+    es->lr_sigma = lr_sigma; es->max_change = max_change; es->sigma_min = sigma_min; es->sigma_max = sigma_max;
+    return BSK_OK;
+}
+
+int bsk_es_get_sigma(bsk_es* es, double* sigma) {
+    if (!es || !sigma) return fail(BSK_EINVAL, "es/sigma is NULL");
+    if (es->sigma_kind != BSK_ES_SIGMA_PGPE) return fail(BSK_EINVAL, "bsk_es_get_sigma: the kind is BSK_ES_SIGMA_FIXED, there is no vector");
+    DeviceGuard guard(es->device);
+    HIP_SYNC(hipDeviceSynchronize());
+    HIP_COPY(hipMemcpy(sigma, es->d_sigma, (size_t)es->lay.n_params * sizeof(double), hipMemcpyDeviceToHost));
+    return BSK_OK;
+}
+
+int bsk_es_set_sigma(bsk_es* es, const double* sigma) {
+    if (!es || !sigma) return fail(BSK_EINVAL, "es/sigma is NULL");
+    if (es->sigma_kind != BSK_ES_SIGMA_PGPE) return fail(BSK_EINVAL, "bsk_es_set_sigma: the kind is BSK_ES_SIGMA_FIXED, there is no vector");
+    for (int j = 0; j < es->lay.n_params; ++j)
+        if (!std::isfinite(sigma[j]) || !(sigma[j] > 0.0)) return fail(BSK_EINVAL, "bsk_es_set_sigma: every entry must be finite and positive");
+    DeviceGuard guard(es->device);
+    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old vector)
+    HIP_COPY(hipMemcpy(es->d_sigma, sigma, (size_t)es->lay.n_params * sizeof(double), hipMemcpyHostToDevice));
+    return BSK_OK;
+}
+
 int bsk_obs_stats_create(int n_cap, int device_id, bsk_obs_stats** out) {
     if (!out) return fail(BSK_EINVAL, "out is NULL");
     *out = nullptr;

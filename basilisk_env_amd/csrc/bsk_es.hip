@@ -5,9 +5,12 @@
 //   es_tell_kernel     one wave per parameter: the utilities contracted with the regenerated noise in a fixed order
 //   es_tell_adam_kernel     the same contraction driven through Adam with an L2 penalty
 //   es_advance_kernel  the generation counter += 1 (es_advance_adam_kernel: and Adam's two running powers)
+//   es_ask_sigma_kernel, es_rank_q_kernel, es_tell_sigma_kernel, es_tell_adam_sigma_kernel     the same four under
+//                      BSK_ES_SIGMA_PGPE: a step size per parameter in device memory, moved by lane 0 behind a second sum
 // The noise is never stored: z(g, i, j) is one Philox4x32-10 call and an inverse normal CDF made of f64 + - * /, sqrt and integer
 // operations.  Compiled with -ffp-contract=off (Makefile), as bsk_population.hip is: every operation rounds on its own, and numpy
-// repeats all of it bit for bit (policy.py: es_noise_ref, es_ask_ref, es_tell_ref, es_tell_adam_ref).
+// repeats all of it bit for bit (policy_ref.py: es_noise_ref, es_ask_ref, es_tell_ref, es_tell_adam_ref, es_ask_sigma_ref,
+// es_tell_pgpe_ref).
 #include "bsk_es.hpp"
 
 #include "bsk_philox.hpp"
@@ -84,7 +87,9 @@ __device__ __forceinline__ double es_noise(unsigned long long seed, unsigned lon
 
 // Pair blockIdx.x, float d of the device layout: policy_pack_kernel's gather with theta +- sigma * z in place of a source block.
 // Both members of the pair from ONE evaluation of z; every float of both device blocks is written by exactly one thread.
-__global__ __launch_bounds__(256) void es_ask_kernel(const EsArgs es, float* __restrict__ dst, const PolicyPackMap map) {
+// sigma_vec == nullptr (a constant where es_ask_kernel inlines this): the optimiser's one sigma; otherwise sigma_vec[j].
+__device__ __forceinline__ void es_ask_pair(const EsArgs& es, const double* __restrict__ sigma_vec, float* __restrict__ dst,
+                                            const PolicyPackMap& map) {
 #pragma clang fp contract(off)
     const int d = (int)(blockIdx.y * blockDim.x + threadIdx.x);
     if (d >= map.n_device) return;
@@ -95,7 +100,7 @@ __global__ __launch_bounds__(256) void es_ask_kernel(const EsArgs es, float* __r
         if (j < es.frozen) {
             plus = minus = (float)t;
         } else {
-            const double step = es.sigma * es_noise(es.state[0], es.state[1], blockIdx.x, (unsigned)j);
+            const double step = (sigma_vec ? sigma_vec[j] : es.sigma) * es_noise(es.state[0], es.state[1], blockIdx.x, (unsigned)j);
             plus = (float)(t + step);
             minus = (float)(t - step);
         }
@@ -103,6 +108,16 @@ __global__ __launch_bounds__(256) void es_ask_kernel(const EsArgs es, float* __r
     float* at = dst + (size_t)(2u * blockIdx.x) * (size_t)map.n_device + d;
     at[0] = plus;
     at[map.n_device] = minus;
+}
+
+__global__ __launch_bounds__(256) void es_ask_kernel(const EsArgs es, float* __restrict__ dst, const PolicyPackMap map) {
+    es_ask_pair(es, nullptr, dst, map);
+}
+
+// BSK_ES_SIGMA_PGPE: one more f64 load, sigma_vec[j], beside theta[j] (frozen entries are never read)
+__global__ __launch_bounds__(256) void es_ask_sigma_kernel(const EsArgs es, const double* __restrict__ sigma_vec, float* __restrict__ dst,
+                                                           const PolicyPackMap map) {
+    es_ask_pair(es, sigma_vec, dst, map);
 }
 
 // a (index ia) comes before b (index ib): bsk_fork.hip's beats() - the greater value, a NaN below every number, ties to the lower index
@@ -134,6 +149,34 @@ __global__ __launch_bounds__(256) void es_rank_kernel(const double* __restrict__
     const double u = 0.5 - (double)rank / (double)(P - 1 > 1 ? P - 1 : 1);
     const double odd = __shfl_down(u, 1, 64);       // (P is even: members 2i and 2i + 1 are neighbours in one wave)
     if (live && (k & 1) == 0) w[k >> 1] = u - odd;
+}
+
+// BSK_ES_SIGMA_PGPE: the same ranking, the even thread also writing q_i = u_2i + u_2i+1 - what the pair says about the step SIZE.
+// The text a second time and not one body behind both: inlined from a shared function es_rank_kernel came out with other scalar
+// instructions around its inner loop (as the comment on ES_PAIR_SUM reports of the update kernels), and it keeps the ones it had.
+__global__ __launch_bounds__(256) void es_rank_q_kernel(const double* __restrict__ fitness, int P, double* __restrict__ w,
+                                                        double* __restrict__ q) {
+#pragma clang fp contract(off)
+    __shared__ double tile[256];
+    const int k = (int)(blockIdx.x * 256u + threadIdx.x);
+    const bool live = k < P;
+    const double f = live ? fitness[k] : 0.0;
+    int rank = 0;
+    for (int base = 0; base < P; base += 256) {
+        const int m = base + (int)threadIdx.x;
+        __syncthreads();                   // (the previous tile's last reads)
+        tile[threadIdx.x] = m < P ? fitness[m] : 0.0;
+        __syncthreads();
+        const int count = P - base < 256 ? P - base : 256;
+        if (live)
+            for (int t = 0; t < count; ++t) rank += es_beats(tile[t], base + t, f, k) ? 1 : 0;
+    }
+    const double u = 0.5 - (double)rank / (double)(P - 1 > 1 ? P - 1 : 1);
+    const double odd = __shfl_down(u, 1, 64);
+    if (live && (k & 1) == 0) {
+        w[k >> 1] = u - odd;
+        q[k >> 1] = u + odd;
+    }
 }
 
 // the fitness tree (bsk_population.hip): s[l] = s[l] + s[l + stride] for l < stride, stride = 32 ... 1
@@ -191,6 +234,70 @@ __global__ __launch_bounds__(256) void es_tell_adam_kernel(const EsArgs es, int 
     }
 }
 
+// BSK_ES_SIGMA_PGPE (include/bskgpu.h): ES_PAIR_SUM with a second accumulator in the same loop, r over q_i * (z * z - 1.0) from the
+// SAME evaluation of z, and a second tree.  Its own text, so that the fixed-sigma kernels above keep theirs (the comment on
+// ES_PAIR_SUM); the order of s is that macro's, term by term.
+#define ES_PAIR_SUM_SIGMA(es, w, q, j, lane, s, r)                                    \
+    const unsigned long long seed = es.state[0], g = es.state[1];                     \
+    double s = 0.0, r = 0.0;                                                          \
+    for (int i = lane; i < es.pairs; i += 64) {                                       \
+        const double z = es_noise(seed, g, (unsigned)i, (unsigned)j);                 \
+        const double t = w[i] * z;                                                    \
+        const double t2 = q[i] * (z * z - 1.0);                                       \
+        s = i == lane ? t : s + t;                                                    \
+        r = i == lane ? t2 : r + t2;                                                  \
+    }                                                                                 \
+    s = es_tree(s, lane);                                                             \
+    r = es_tree(r, lane)
+
+// lane 0: sigma_vec[j] out of r[0] and sg, the value it had before this tell - a relative change of at most max_change, then the bounds
+__device__ __forceinline__ void es_sigma_step(const EsSigma& sv, int j, double sg, double r) {
+#pragma clang fp contract(off)
+    double d = (sv.cs * r) * sg;
+    const double lim = sv.max_change * sg;
+    d = d > lim ? lim : (d < -lim ? -lim : d);
+    double n = sg + d;
+    n = n < sv.sigma_min ? sv.sigma_min : n;
+    n = n > sv.sigma_max ? sv.sigma_max : n;
+    sv.sigma_vec[j] = n;
+}
+
+__global__ __launch_bounds__(256) void es_tell_sigma_kernel(const EsArgs es, int n_params, const double* __restrict__ w,
+                                                            const double* __restrict__ q, double lr, const EsSigma sv) {
+#pragma clang fp contract(off)
+    const int j = es.frozen + (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));     // (wave-uniform)
+    const int lane = (int)(threadIdx.x & 63u);
+    if (j >= n_params) return;
+    ES_PAIR_SUM_SIGMA(es, w, q, j, lane, s, r);
+    if (lane == 0) {
+        const double sg = sv.sigma_vec[j];
+        es.theta[j] = es.theta[j] + (lr / (sv.pd * sg)) * s;
+        es_sigma_step(sv, j, sg, r);
+    }
+}
+
+__global__ __launch_bounds__(256) void es_tell_adam_sigma_kernel(const EsArgs es, int n_params, const double* __restrict__ w,
+                                                                 const double* __restrict__ q, const EsAdam ad, const EsSigma sv) {
+#pragma clang fp contract(off)
+    const int j = es.frozen + (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));     // (wave-uniform)
+    const int lane = (int)(threadIdx.x & 63u);
+    if (j >= n_params) return;
+    ES_PAIR_SUM_SIGMA(es, w, q, j, lane, s, r);
+    if (lane == 0) {
+        const double sg = sv.sigma_vec[j];
+        const double cg = 1.0 / (sv.pd * sg);                                                  // (ad.cg is the fixed mode's)
+        const double p1 = ad.beta_pow[0] * ad.beta1, p2 = ad.beta_pow[1] * ad.beta2;
+        const double t = es.theta[j];
+        const double grad = cg * s - ad.weight_decay * t;
+        const double m = ad.beta1 * ad.m[j] + ad.a1 * grad;
+        const double v = ad.beta2 * ad.v[j] + (ad.a2 * grad) * grad;
+        ad.m[j] = m;
+        ad.v[j] = v;
+        es.theta[j] = t + (ad.lr * (m / (1.0 - p1))) / (sqrt(v / (1.0 - p2)) + ad.eps);
+        es_sigma_step(sv, j, sg, r);
+    }
+}
+
 __global__ void es_advance_kernel(unsigned long long* state) { state[1] += 1ull; }
 
 __global__ void es_advance_adam_kernel(unsigned long long* state, double* beta_pow, double beta1, double beta2) {
@@ -222,6 +329,33 @@ hipError_t launch_es_tell_adam(const EsArgs& es, int n_params, const double* w, 
     const int moving = n_params - es.frozen;
     if (moving < 1) return hipSuccess;
     hipLaunchKernelGGL(es_tell_adam_kernel, dim3((unsigned)((moving + 3) / 4)), dim3(256), 0, s, es, n_params, w, ad);
+    return hipGetLastError();
+}
+
+hipError_t launch_es_ask_sigma(const PolicyLayout& lay, const EsArgs& es, const double* sigma_vec, float* d_params, hipStream_t s) {
+    const PolicyPackMap map = policy_pack_map(lay);
+    hipLaunchKernelGGL(es_ask_sigma_kernel, dim3((unsigned)es.pairs, (unsigned)((lay.n_device + 255) / 256)), dim3(256), 0, s, es, sigma_vec,
+                       d_params, map);
+    return hipGetLastError();
+}
+
+hipError_t launch_es_rank_q(const double* fitness, int n_members, double* w, double* q, hipStream_t s) {
+    hipLaunchKernelGGL(es_rank_q_kernel, dim3((unsigned)((n_members + 255) / 256)), dim3(256), 0, s, fitness, n_members, w, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_es_tell_sigma(const EsArgs& es, int n_params, const double* w, const double* q, double lr, const EsSigma& sv, hipStream_t s) {
+    const int moving = n_params - es.frozen;
+    if (moving < 1) return hipSuccess;
+    hipLaunchKernelGGL(es_tell_sigma_kernel, dim3((unsigned)((moving + 3) / 4)), dim3(256), 0, s, es, n_params, w, q, lr, sv);
+    return hipGetLastError();
+}
+
+hipError_t launch_es_tell_adam_sigma(const EsArgs& es, int n_params, const double* w, const double* q, const EsAdam& ad, const EsSigma& sv,
+                                     hipStream_t s) {
+    const int moving = n_params - es.frozen;
+    if (moving < 1) return hipSuccess;
+    hipLaunchKernelGGL(es_tell_adam_sigma_kernel, dim3((unsigned)((moving + 3) / 4)), dim3(256), 0, s, es, n_params, w, q, ad, sv);
     return hipGetLastError();
 }
 

@@ -25,6 +25,14 @@ struct EsAdam {
     double cg, lr;                     // cg = 1 / ((double)P * sigma)
 };
 
+// bsk_es_set_sigma_adaptation(BSK_ES_SIGMA_PGPE): the step size of every parameter and the constants of its update
+struct EsSigma {
+    double* sigma_vec;                 // [n_params]; entries below `frozen` are carried, never read by a kernel and never moved
+    double pd;                         // (double)P
+    double cs;                         // lr_sigma / pd, formed once on the host
+    double max_change, sigma_min, sigma_max;
+};
+
 // The members of this generation into d_params ([2 * pairs][lay.n_device], a population's device layout): one launch, every
 // float written exactly once.
 hipError_t launch_es_ask(const PolicyLayout& lay, const EsArgs& es, float* d_params, hipStream_t s);
@@ -34,6 +42,14 @@ hipError_t launch_es_rank(const double* fitness, int n_members, double* w, hipSt
 hipError_t launch_es_tell(const EsArgs& es, int n_params, const double* w, double c, hipStream_t s);
 // the same sum through Adam: g = cg * s[0] - weight_decay * theta_j, the moments, the bias-corrected step (include/bskgpu.h)
 hipError_t launch_es_tell_adam(const EsArgs& es, int n_params, const double* w, const EsAdam& ad, hipStream_t s);
+// BSK_ES_SIGMA_PGPE, the same four with sigma_vec[j] in the place of sigma (include/bskgpu.h): ask; the ranking that also writes
+// q f64[n_members / 2], the SUM of each pair's utilities; the two updates, which leave sigma_vec moved as well (es.sigma and
+// ad.cg are not read)
+hipError_t launch_es_ask_sigma(const PolicyLayout& lay, const EsArgs& es, const double* sigma_vec, float* d_params, hipStream_t s);
+hipError_t launch_es_rank_q(const double* fitness, int n_members, double* w, double* q, hipStream_t s);
+hipError_t launch_es_tell_sigma(const EsArgs& es, int n_params, const double* w, const double* q, double lr, const EsSigma& sv, hipStream_t s);
+hipError_t launch_es_tell_adam_sigma(const EsArgs& es, int n_params, const double* w, const double* q, const EsAdam& ad, const EsSigma& sv,
+                                     hipStream_t s);
 // generation += 1 and beta_pow *= {beta1, beta2}, one thread, behind launch_es_tell_adam on the same stream
 hipError_t launch_es_advance_adam(unsigned long long* state, double* beta_pow, double beta1, double beta2, hipStream_t s);
 // generation += 1, one thread, behind a tell on the same stream (a replayed graph moves on to the next generation)

@@ -22,7 +22,7 @@ What needs no device lives beside this module and is re-exported here under the 
 layout of the parameter block in ``policy_spec`` (``check_spec``, ``pack_params``, ...), and in ``policy_ref`` the numpy
 restatements the kernels are held to bit for bit (``mlp_ref`` / ``act_ref``: every layer output one k-ordered chain of f32 fused
 multiply-adds from the bias; ``population_fitness_ref``; ``es_noise_ref`` / ``es_ask_ref`` / ``es_tell_ref`` /
-``es_tell_adam_ref``; ``obs_stats_accumulate_ref`` / ``obs_stats_totals_ref`` / ``obs_norm_ref``) with ``EvolutionStrategy``, the host-side loop the device one was modelled on.
+``es_tell_adam_ref`` / ``es_ask_sigma_ref`` / ``es_tell_pgpe_ref``; ``obs_stats_accumulate_ref`` / ``obs_stats_totals_ref`` / ``obs_norm_ref``) with ``EvolutionStrategy``, the host-side loop the device one was modelled on.
 """
 import ctypes as C
 import sys
@@ -31,12 +31,14 @@ import numpy as np
 
 from . import _hip, _lib
 from ._lib import check
-from .policy_ref import (EvolutionStrategy, _es_pair_sum, _series_log, act_ref, centred_ranks, check_adam,  # noqa: F401
-                         es_ask_ref, es_inverse_normal_ref, es_noise_ref, es_tell_adam_ref, es_tell_ref, es_uniform_ref, fma32,
+from .policy_ref import (EvolutionStrategy, _es_pair_sum, _es_pair_sums, _series_log, act_ref, centred_ranks, check_adam,  # noqa: F401
+                         es_ask_ref, es_ask_sigma_ref, es_inverse_normal_ref, es_noise_ref, es_tell_adam_ref, es_tell_pgpe_ref,
+                         es_tell_ref, es_uniform_ref, fma32,
                          mlp_ref, obs_moments_ref, obs_norm_ref, obs_stats_accumulate_ref, obs_stats_totals_ref,
                          obs_stats_zero_state, philox4x32_10, population_fitness_ref, sample_uniform, shared_slot_ref, softmax_ref)
 from .policy_spec import (ACTIVATIONS, MAX_HIDDEN_LAYERS, MODES, POLICY_GREEDY, POLICY_RELU, POLICY_SAMPLE,  # noqa: F401
-                          POLICY_TANH, BskPolicySpec, Spec, _as_spec, c_spec, check_spec, layer_shapes, n_params, pack_params,
+                          POLICY_TANH, BskPolicySpec, Spec, _as_spec, c_spec, check_sigma_adaptation, check_spec, layer_shapes,
+                          n_params, pack_params,
                           torch_layers, unpack_params)
 
 
@@ -494,16 +496,28 @@ class DeviceEvolutionStrategy(_DeviceObject):
     pair, parameter) instead of stored.  ``theta``: the float32 parameter block the search starts from (None: zeros).  Equal bit
     for bit to ``es_ask_ref`` / ``es_tell_ref``.  ``optimizer="adam"`` drives the same estimate through Adam with the L2 penalty
     ``weight_decay`` (``bsk_es_set_optimizer``; ``es_tell_adam_ref``); ``"sgd"``, the default, ignores the four Adam arguments.
-    Not thread-safe, one stream at a time."""
+    ``sigma_adapt="pgpe"`` gives every parameter a step size of its own in device memory, started at ``sigma`` and adapted by
+    every ``tell`` from the same pairs that move theta (``bsk_es_set_sigma_adaptation``; ``es_ask_sigma_ref``,
+    ``es_tell_pgpe_ref``): by ``lr_sigma``, at most ``sigma_max_change`` of itself per generation, inside
+    [``sigma_min``, ``sigma_max``] (None: ``sigma`` / 100 and 10 ``sigma``).  None, the default, keeps the one ``sigma`` and never
+    calls that entry point.  Not thread-safe, one stream at a time."""
     _kind, _what = "es", "evolution strategy"
 
     def __init__(self, spec, theta, population, sigma=0.1, lr=0.05, seed=0, frozen=10, device=0, optimizer="sgd", beta1=0.9,
-                 beta2=0.999, eps=1e-8, weight_decay=0.0):
+                 beta2=0.999, eps=1e-8, weight_decay=0.0, sigma_adapt=None, lr_sigma=0.1, sigma_max_change=0.2, sigma_min=None,
+                 sigma_max=None):
         if optimizer not in ("sgd", "adam"):
             raise ValueError("optimizer must be 'sgd' or 'adam', got %r" % (optimizer,))
         if optimizer == "adam":
             beta1, beta2, eps, weight_decay = check_adam(beta1, beta2, eps, weight_decay)
         self.optimizer, self.adam = optimizer, (beta1, beta2, eps, weight_decay)
+        if sigma_adapt not in (None, "pgpe"):
+            raise ValueError("sigma_adapt must be None or 'pgpe', got %r" % (sigma_adapt,))
+        if sigma_adapt is not None:
+            sigma_min = 0.01 * float(sigma) if sigma_min is None else sigma_min
+            sigma_max = 10.0 * float(sigma) if sigma_max is None else sigma_max
+            check_sigma_adaptation(lr_sigma, sigma_max_change, sigma_min, sigma_max, sigma)
+        self.sigma_adapt, self.sigma_adaptation = None, None
         self.spec = _as_spec(spec)
         self.n_params = n_params(self.spec)
         self.population, self.sigma, self.lr, self.frozen = int(population), float(sigma), float(lr), int(frozen)
@@ -512,6 +526,8 @@ class DeviceEvolutionStrategy(_DeviceObject):
         self._create(device, self.population, None if t is None else t.ctypes.data, self.sigma, self.lr, self.frozen, self.seed)
         if optimizer == "adam":
             self.set_optimizer("adam", beta1, beta2, eps, weight_decay)
+        if sigma_adapt is not None:
+            self.set_sigma_adaptation(sigma_adapt, lr_sigma, sigma_max_change, sigma_min, sigma_max)
 
     # ------------------------------------------------------------------ state
     @property
@@ -562,6 +578,34 @@ class DeviceEvolutionStrategy(_DeviceObject):
         arrs = [None if a is None else _host_block(a, size, np.float64, what="values")
                 for a, size in ((m, self.n_params), (v, self.n_params), (beta_pow, 2))]
         check(self._lib.bsk_es_set_moments(self._handle(), *[None if a is None else a.ctypes.data for a in arrs]))
+
+    def set_sigma_adaptation(self, sigma_adapt, lr_sigma=0.1, sigma_max_change=0.2, sigma_min=None, sigma_max=None):
+        """``"pgpe"``: a step size per parameter, every entry started at ``sigma`` (every selection fills the vector again);
+        None: the one ``sigma`` again.  Theta, the generation and Adam's state stay; synchronises."""
+        if sigma_adapt not in (None, "pgpe"):
+            raise ValueError("sigma_adapt must be None or 'pgpe', got %r" % (sigma_adapt,))
+        if sigma_adapt is None:
+            check(self._lib.bsk_es_set_sigma_adaptation(self._handle(), _lib.ES_SIGMA_FIXED, 0.0, 0.0, 0.0, 0.0))
+            self.sigma_adapt, self.sigma_adaptation = None, None
+            return
+        sigma_min = 0.01 * self.sigma if sigma_min is None else sigma_min
+        sigma_max = 10.0 * self.sigma if sigma_max is None else sigma_max
+        args = check_sigma_adaptation(lr_sigma, sigma_max_change, sigma_min, sigma_max, self.sigma)
+        check(self._lib.bsk_es_set_sigma_adaptation(self._handle(), _lib.ES_SIGMA_PGPE, *args))
+        self.sigma_adapt, self.sigma_adaptation = sigma_adapt, args
+
+    @property
+    def sigma_vector(self):
+        """The step size of every parameter, float64 (n_params,); synchronises.  An error while ``sigma_adapt`` is None."""
+        out = np.empty(self.n_params, np.float64)
+        check(self._lib.bsk_es_get_sigma(self._handle(), out.ctypes.data))
+        return out
+
+    def set_sigma(self, sigma_vec):
+        """New step sizes (float64 (n_params,), every entry finite and positive; the first ``frozen`` are carried, not used);
+        synchronises.  An error while ``sigma_adapt`` is None."""
+        s = _host_block(sigma_vec, self.n_params, np.float64, what="values")
+        check(self._lib.bsk_es_set_sigma(self._handle(), s.ctypes.data))
 
     # ------------------------------------------------------------------ the search
     def ask(self, pop, stream=0):

@@ -4,7 +4,8 @@ Each function repeats, operation by operation and in the kernel's order, what in
 layer output one k-ordered chain of ``fma32`` from the bias), the action choice (``act_ref``, ``softmax_ref``, the Philox draw of
 ``sample_uniform``), the per-member fitness of a rollout (``population_fitness_ref``), and the evolution strategy - its noise
 (``es_noise_ref``: Philox, then Wichura's AS 241 with a series logarithm), members (``es_ask_ref``), ranking (``centred_ranks``) and the
-SGD and Adam updates (``es_tell_ref``, ``es_tell_adam_ref``) - with ``shared_slot_ref`` for the shared-episode reset, and the running
+SGD and Adam updates (``es_tell_ref``, ``es_tell_adam_ref``) and the same with a step size per parameter that adapts
+(``es_ask_sigma_ref``, ``es_tell_pgpe_ref``) - with ``shared_slot_ref`` for the shared-episode reset, and the running
 observation statistics with the input normalisation out of them (``obs_stats_accumulate_ref``, ``obs_stats_totals_ref``,
 ``obs_norm_ref``).
 ``EvolutionStrategy`` is the host-side search the device one was modelled on.  Needs numpy and ``policy_spec`` only: no device, no
@@ -13,7 +14,7 @@ of what they state.
 """
 import numpy as np
 
-from .policy_spec import MODES, _as_spec, unpack_params
+from .policy_spec import MODES, _as_spec, check_sigma_adaptation, unpack_params
 
 def fma32(a, b, c):
     """float32 arrays (broadcast against each other) -> float32: a * b + c rounded ONCE, what ``fmaf`` / ``v_fma_f32`` / one step
@@ -338,16 +339,18 @@ def es_tell_ref(theta, fitness, sigma, lr, frozen, seed, generation):
     return theta
 
 
-def _es_pair_sum(fitness, n_params, seed, generation):
-    """Steps 1 - 3 of ``bsk_es_tell`` up to s[0] -> (float64 (n_params,), P): the one sum behind ``es_tell_ref`` and
-    ``es_tell_adam_ref``, as ``ES_PAIR_SUM`` (csrc/bsk_es.hip) is behind the two update kernels."""
+def _es_pair_sums(fitness, n_params, seed, generation, with_r=False):
+    """Steps 1 - 3 of ``bsk_es_tell`` up to the sums -> (s0, r0, P), float64 (n_params,) each: the ONE helper behind every tell
+    restatement.  s0 is over w_i * z, w_i = u_2i - u_2i+1; r0 (``with_r``; None otherwise) is over q_i * (z * z - 1.0),
+    q_i = u_2i + u_2i+1, from the same z.  Each sum in the one order: lane l = 0 .. 63 takes its pairs l, l + 64, ... ascending from
+    the first (+0.0 with none), then the lanes join in the tree with strides 32 ... 1."""
     u = centred_ranks(fitness)
     P = u.size
     if P < 2 or P % 2:
         raise ValueError("expected an even number of fitness values, at least 2")
-    w = u[0::2] - u[1::2]
-    with np.errstate(invalid="ignore", over="ignore"):
-        terms = w[:, None] * es_noise_ref(seed, generation, P // 2, n_params)
+    z = es_noise_ref(seed, generation, P // 2, n_params)
+
+    def lanes_then_tree(terms):
         s = np.zeros((64, int(n_params)), np.float64)
         s[:min(64, P // 2)] = terms[:64]
         for at in range(64, P // 2, 64):
@@ -355,7 +358,18 @@ def _es_pair_sum(fitness, n_params, seed, generation):
             s[:len(chunk)] = s[:len(chunk)] + chunk
         for stride in (32, 16, 8, 4, 2, 1):
             s[:stride] = s[:stride] + s[stride:2 * stride]
-    return s[0].copy(), P
+        return s[0].copy()
+    with np.errstate(invalid="ignore", over="ignore"):
+        s0 = lanes_then_tree((u[0::2] - u[1::2])[:, None] * z)
+        r0 = lanes_then_tree((u[0::2] + u[1::2])[:, None] * (z * z - 1.0)) if with_r else None
+    return s0, r0, P
+
+
+def _es_pair_sum(fitness, n_params, seed, generation):
+    """-> (s0, P) of ``_es_pair_sums``: the sum behind ``es_tell_ref`` and ``es_tell_adam_ref``, as ``ES_PAIR_SUM`` (csrc/bsk_es.hip)
+    is behind the two update kernels."""
+    s0, _, P = _es_pair_sums(fitness, n_params, seed, generation)
+    return s0, P
 
 
 def check_adam(beta1, beta2, eps, weight_decay):
@@ -396,6 +410,72 @@ def es_tell_adam_ref(theta, m, v, beta_pow, fitness, sigma, lr, frozen, seed, ge
         m[frozen:], v[frozen:] = mj, vj
         theta[frozen:] = t + (lr * (mj / (np.float64(1.0) - p1))) / (np.sqrt(vj / (np.float64(1.0) - p2)) + eps)
     return theta, m, v, np.array([p1, p2], np.float64)
+
+
+def es_ask_sigma_ref(theta, sigma_vec, frozen, P, seed, generation):
+    """The members ``bsk_es_ask`` writes under ``BSK_ES_SIGMA_PGPE`` -> float32 (P, n_params): ``es_ask_ref`` with sigma_vec[j] in
+    the place of sigma.  The first ``frozen`` entries of ``sigma_vec`` are not read."""
+    theta = np.asarray(theta, np.float64).reshape(-1)
+    sv = np.asarray(sigma_vec, np.float64).reshape(-1)
+    if sv.size != theta.size:
+        raise ValueError("sigma_vec has theta's size")
+    P, frozen = int(P), int(frozen)
+    step = sv[None, :] * es_noise_ref(seed, generation, P // 2, theta.size)
+    step[:, :frozen] = 0.0
+    members = np.empty((P, theta.size), np.float64)
+    members[0::2] = theta + step
+    members[1::2] = theta - step
+    members[:, :frozen] = theta[:frozen]
+    return members.astype(np.float32)
+
+
+def es_tell_pgpe_ref(theta, sigma_vec, fitness, lr, frozen, seed, generation, lr_sigma, max_change, sigma_min, sigma_max, adam=None):
+    """What ``bsk_es_tell`` leaves under ``BSK_ES_SIGMA_PGPE`` (include/bskgpu.h), float64 -> (theta, sigma_vec), or with
+    ``adam=(m, v, beta_pow, beta1, beta2, eps, weight_decay)`` -> (theta, sigma_vec, m, v, beta_pow).  Both sums from
+    ``_es_pair_sums``; per parameter j >= frozen with sg = sigma_vec[j] as given and Pd = float(P), every operation rounded on its
+    own: SGD theta_j = theta_j + (lr / (Pd * sg)) * s[0]; Adam ``es_tell_adam_ref``'s rule with cg = 1 / (Pd * sg);
+    d = (cs * r[0]) * sg with cs = lr_sigma / Pd, clamped to +- max_change * sg; sigma_vec[j] = sg + d clamped to
+    [sigma_min, sigma_max].  ``sigma_vec`` need not lie inside the bounds (``bsk_es_set_sigma`` takes any positive vector)."""
+    theta = np.array(theta, dtype=np.float64).reshape(-1)
+    sv = np.array(sigma_vec, dtype=np.float64).reshape(-1)
+    frozen = int(frozen)
+    if sv.size != theta.size:
+        raise ValueError("sigma_vec has theta's size")
+    if not (np.isfinite(sv).all() and (sv > 0.0).all()):
+        raise ValueError("every entry of sigma_vec must be finite and positive")
+    lr_sigma, max_change, sigma_min, sigma_max = (np.float64(x) for x in check_sigma_adaptation(lr_sigma, max_change, sigma_min, sigma_max))
+    s0, r0, P = _es_pair_sums(fitness, theta.size, seed, generation, with_r=True)
+    pd, lr = np.float64(P), np.float64(lr)
+    cs = lr_sigma / pd
+    sg, t = sv[frozen:], theta[frozen:]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        if adam is None:
+            theta[frozen:] = t + (lr / (pd * sg)) * s0[frozen:]
+        else:
+            m, v, beta_pow, beta1, beta2, eps, weight_decay = adam
+            m, v = np.array(m, dtype=np.float64).reshape(-1), np.array(v, dtype=np.float64).reshape(-1)
+            bp = np.array(beta_pow, dtype=np.float64).reshape(2)
+            if m.size != theta.size or v.size != theta.size:
+                raise ValueError("m and v have theta's size")
+            b1, b2, eps, wd = (np.float64(x) for x in check_adam(beta1, beta2, eps, weight_decay))
+            cg = np.float64(1.0) / (pd * sg)
+            a1, a2 = np.float64(1.0) - b1, np.float64(1.0) - b2
+            p1, p2 = bp[0] * b1, bp[1] * b2
+            g = cg * s0[frozen:] - wd * t
+            mj = b1 * m[frozen:] + a1 * g
+            vj = b2 * v[frozen:] + (a2 * g) * g
+            m[frozen:], v[frozen:] = mj, vj
+            theta[frozen:] = t + (lr * (mj / (np.float64(1.0) - p1))) / (np.sqrt(vj / (np.float64(1.0) - p2)) + eps)
+        d = (cs * r0[frozen:]) * sg
+        lim = max_change * sg
+        d = np.where(d > lim, lim, np.where(d < -lim, -lim, d))
+        n = sg + d
+        n = np.where(n < sigma_min, sigma_min, n)
+        n = np.where(n > sigma_max, sigma_max, n)
+        sv[frozen:] = n
+    if adam is None:
+        return theta, sv
+    return theta, sv, m, v, np.array([p1, p2], np.float64)
 
 
 def shared_slot_ref(n, envs_per_member, epoch, n_pool, env_base=0):

@@ -2,10 +2,12 @@
 
 ``check_spec`` turns hidden widths and activations into a ``Spec`` or says what is wrong with them; ``layer_shapes``, ``n_params``,
 ``pack_params`` and ``unpack_params`` lay the block out - ``in_scale[5]``, ``in_shift[5]``, then ``W[out][in]`` and ``b[out]`` per layer,
-the action network first - and ``torch_layers`` reads one network out of an ``nn.Sequential``.  Nothing here needs a device or the
-library: only its constants and the mirror of the C struct are imported.
+the action network first - and ``torch_layers`` reads one network out of an ``nn.Sequential``.  ``check_sigma_adaptation`` holds the
+argument rules of the evolution strategy's per-parameter step size.  Nothing here needs a device or the library: only its constants
+and the mirror of the C struct are imported.
 """
 import ctypes as C
+import math
 from collections import namedtuple
 
 import numpy as np
@@ -61,6 +63,23 @@ def c_spec(spec):
         for k, w in enumerate(spec.value_hidden):
             c.v_hidden[k] = w
     return c
+
+
+def check_sigma_adaptation(lr_sigma, max_change, sigma_min, sigma_max, sigma=None):
+    """The argument rules of ``bsk_es_set_sigma_adaptation(BSK_ES_SIGMA_PGPE, ...)`` -> the four as floats; ValueError where it
+    returns BSK_EINVAL.  ``sigma``: the sigma the optimiser was created with (None: that rule is not checked).  Needs no device."""
+    lr_sigma, max_change, sigma_min, sigma_max = (float(x) for x in (lr_sigma, max_change, sigma_min, sigma_max))
+    if not math.isfinite(lr_sigma) or lr_sigma < 0.0:
+        raise ValueError("lr_sigma must be finite and not negative")
+    if not math.isfinite(max_change) or not (0.0 < max_change < 1.0):
+        raise ValueError("max_change must be inside (0, 1)")
+    if not math.isfinite(sigma_min) or not (sigma_min > 0.0):
+        raise ValueError("sigma_min must be finite and positive")
+    if not math.isfinite(sigma_max) or sigma_max < sigma_min:
+        raise ValueError("sigma_max must be finite and not below sigma_min")
+    if sigma is not None and not (sigma_min <= float(sigma) <= sigma_max):
+        raise ValueError("the optimiser's sigma must be inside [sigma_min, sigma_max]")
+    return lr_sigma, max_change, sigma_min, sigma_max
 
 
 def layer_shapes(spec):

@@ -670,6 +670,50 @@ int bsk_es_set_optimizer(bsk_es* es, int kind, double beta1, double beta2, doubl
 int bsk_es_get_moments(bsk_es* es, double* m, double* v, double* beta_pow);
 int bsk_es_set_moments(bsk_es* es, const double* m, const double* v, const double* beta_pow);
 
+/* A step size per parameter, adapted on the device: PGPE's symmetric-sampling rule (Sehnke et al. 2010) on the centred-rank
+ * utilities, from the same pairs that move theta.  Off by default (BSK_ES_SIGMA_FIXED): an optimiser that never selects
+ * BSK_ES_SIGMA_PGPE launches the kernels of the definition above with the arguments it passed before.  Under either update rule;
+ * + - * / only, every operation rounded on its own in f64 with plain /, no FMA (basilisk_env_amd/policy_ref.py: es_ask_sigma_ref
+ * and es_tell_pgpe_ref repeat it bit for bit).
+ * State: sigma_vec f64[n_params] in device memory, allocated at the first selection of BSK_ES_SIGMA_PGPE and on EVERY selection
+ * filled with the sigma of bsk_es_create (as Adam's moments are zeroed on every selection).  Entries j < frozen are carried, but
+ * never read by a kernel and never moved.  Being device state, sigma_vec moves on by itself under a replayed graph.
+ * ask: member 2i is (float)(theta_j + sigma_vec[j] * z(g,i,j)), member 2i + 1 the same with -; product and sum each round in f64;
+ *   j < frozen as above.
+ * tell, steps 1 and 2: rank_k and u_k as above; w_i = u_2i - u_2i+1 as above and in addition q_i = u_2i + u_2i+1.
+ * tell, step 3, for every j >= frozen, z = z(g,i,j) from ONE evaluation, two sums, each in the order of step 3 above (lane l takes
+ *   its pairs l, l + 64, ... ascending from the first, +0.0 with none; then the tree with strides 32 ... 1):
+ *        s[0] over w_i * z                       r[0] over q_i * (z * z - 1.0)
+ *   With sg = sigma_vec[j] as it was before this tell and Pd = (double)P:
+ *        BSK_ES_SGD:   theta_j = theta_j + (lr / (Pd * sg)) * s[0]
+ *        BSK_ES_ADAM:  the rule of bsk_es_set_optimizer with cg = 1.0 / (Pd * sg), formed per parameter
+ *        sigma:        d = (cs * r[0]) * sg,  cs = lr_sigma / Pd formed once on the host
+ *                      lim = max_change * sg
+ *                      d = d > lim ? lim : (d < -lim ? -lim : d)
+ *                      n = sg + d
+ *                      n = n < sigma_min ? sigma_min : n
+ *                      n = n > sigma_max ? sigma_max : n
+ *                      sigma_vec[j] = n
+ *   r[0] is finite by construction: the utilities and z are finite.
+ * Step 4 is unchanged; tell stays three launches, no copy, no synchronisation, capturable.
+ * Consequences.  A uniform sigma_vec with lr_sigma = 0 gives the optimiser of BSK_ES_SIGMA_FIXED bit for bit under both update
+ * rules (d = +-0, sg + d = sg).  At P = 2, q_0 = 0 always: sigma never moves.  Under a fitness that is linear in the parameters
+ * and has no ties the two members of a pair mirror each other in the ranking (rank_2i + rank_2i+1 = P - 1), every q_i is exactly 0
+ * and sigma keeps its bits; two pairs whose fitness differs by less than the rounding of the members to float count as tied here.
+ * |d| <= max_change * sg before the bounds apply, so max_change < 1 keeps sigma positive.
+ * bsk_es_set_sigma_adaptation synchronises the device.  BSK_ES_SIGMA_FIXED ignores the other arguments and restores the one sigma
+ * of bsk_es_create (the vector stays allocated, unused).  Theta, the generation and the Adam state are left alone; bsk_es_set_optimizer
+ * and bsk_es_set_state leave sigma_vec alone.  BSK_EINVAL before anything is launched: a NULL optimiser, an unknown kind; for PGPE
+ * lr_sigma not finite or < 0, max_change not finite or outside (0, 1), sigma_min not finite or <= 0, sigma_max not finite or
+ * < sigma_min, the sigma of bsk_es_create outside [sigma_min, sigma_max]. */
+#define BSK_ES_SIGMA_FIXED 0
+#define BSK_ES_SIGMA_PGPE 1
+int bsk_es_set_sigma_adaptation(bsk_es* es, int kind, double lr_sigma, double max_change, double sigma_min, double sigma_max);
+/* sigma_vec to / from host memory, f64[n_params] (for checkpoints).  Synchronise the device.  BSK_EINVAL for NULL pointers and while
+ * the kind is BSK_ES_SIGMA_FIXED; set also for any entry that is not finite and positive (nothing is written then). */
+int bsk_es_get_sigma(bsk_es* es, double* sigma);
+int bsk_es_set_sigma(bsk_es* es, const double* sigma);
+
 /* Running statistics of the five observation rows, formed on the device: what gives a policy its in_scale / in_shift.  Salimans et
  * al. 2017 and ARS V2 (Mania et al. 2018) normalise the observations by the mean and standard deviation of everything the search
  * has seen so far; the sums behind them are a reduction over data that already lies in the handle's observation rows when the

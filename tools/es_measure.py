@@ -13,12 +13,15 @@
         shared  `run_generation(..., shared_episodes=True)`: the reset that gives all members the same episodes
         obsnorm `run_generation(..., obs_stats=...)`: one obs_stats_kernel launch in front of every policy launch, the join and
                 the normalisation behind the generation
-  python tools/es_measure.py kernel [adam | obs]
+        sigma   `run_generation` of an optimiser created with sigma_adapt="pgpe": a step size per parameter, moved by tell
+  python tools/es_measure.py kernel [adam | obs | sigma]
       per P one warming and three measured generations of `run_generation` (`adam`: of an optimizer="adam" optimiser on shared
-      episodes; `obs`: with an `ObsStats` given).  Run it under the profiler in a run of its own:
+      episodes; `obs`: with an `ObsStats` given; `sigma`: of a sigma_adapt="pgpe" optimiser).  Run it under the profiler in a run
+      of its own:
       rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o es -- python tools/es_measure.py kernel
   python tools/es_measure.py stats DIR/.../es_kernel_trace.csv
-      per measured generation of that run the times of es_ask_kernel, es_rank_kernel and es_tell_kernel (or es_tell_adam_kernel)
+      per measured generation of that run the times of es_ask_kernel, es_rank_kernel and es_tell_kernel (or es_tell_adam_kernel;
+      of a `kernel sigma` run es_ask_sigma_kernel, es_rank_q_kernel and es_tell_sigma_kernel)
       and the sum over every other kernel of the generation (the generations are recognised by the es_advance_kernel or
       es_advance_adam_kernel that ends each); of a `kernel obs` run also obs_stats_kernel, per generation and per launch
 """
@@ -63,6 +66,7 @@ def loop():
             adam = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1, optimizer="adam")
             shared = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
             normed = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
+            sig = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1, sigma_adapt="pgpe")
             obs_stats = P.ObsStats(N)
             fit = torch.zeros(m, dtype=torch.float64, device="cuda")
 
@@ -87,6 +91,9 @@ def loop():
             def obsnorm_gen(steps, pop=pop, normed=normed, obs_stats=obs_stats):
                 normed.run_generation(prop, pop, steps, 1, "greedy", GAMMA, obs_stats=obs_stats)
 
+            def sigma_gen(steps, pop=pop, sig=sig):
+                sig.run_generation(prop, pop, steps, 1, "greedy", GAMMA)
+
             rep.run_generation(prop, pop, WARM_T, 1, "greedy", GAMMA)
             prop.sync()
             graph = torch.cuda.CUDAGraph()
@@ -99,7 +106,7 @@ def loop():
 
             variants += [("host   P = %d" % m, host_gen), ("device P = %d" % m, device_gen), ("graph  P = %d" % m, graph_gen),
                          ("rollout P = %d" % m, rollout_gen), ("adam   P = %d" % m, adam_gen), ("shared P = %d" % m, shared_gen),
-                         ("obsnorm P = %d" % m, obsnorm_gen)]
+                         ("obsnorm P = %d" % m, obsnorm_gen), ("sigma  P = %d" % m, sigma_gen)]
         res = {name: [] for name, _ in variants}
         for _ in range(ROUNDS):
             for name, run in variants:
@@ -114,12 +121,13 @@ def loop():
     env.close()
 
 
-def kernel(adam=False, obs=False):
+def kernel(adam=False, obs=False, sigma=False):
     torch, P, side, env, prop, spec, theta = _setup()
     with torch.cuda.stream(side):
         for m in MEMBERS:
             pop = P.PolicyPopulation(spec, n_members=m)
-            dev = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1, optimizer="adam" if adam else "sgd")
+            dev = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1, optimizer="adam" if adam else "sgd",
+                                            sigma_adapt="pgpe" if sigma else None)
             obs_stats = P.ObsStats(N) if obs else None
             dev.run_generation(prop, pop, WARM_T, 1, "greedy", GAMMA, shared_episodes=adam, obs_stats=obs_stats)
             for _ in range(ROUNDS):
@@ -138,7 +146,7 @@ def stats(path):
     gens, cur, seen = [], {}, False
     for _, d, name in rows:
         key = next((k for k in ("es_ask_kernel", "es_rank_kernel", "es_tell_kernel", "es_advance_kernel", "obs_stats_kernel")
-                    if k in name.replace("_adam", "")), "rest")
+                    if k in name.replace("_adam", "").replace("_sigma", "").replace("es_rank_q", "es_rank")), "rest")
         seen = seen or key == "es_ask_kernel"
         if not seen:
             continue                           # (the set-up's launches, before the first generation)
@@ -149,7 +157,8 @@ def stats(path):
     assert len(gens) == len(MEMBERS) * (1 + ROUNDS), len(gens)
     for b, m in enumerate(MEMBERS):
         for g in gens[b * (1 + ROUNDS) + 1:(b + 1) * (1 + ROUNDS)]:
-            # (tell: es_tell_kernel, or es_tell_adam_kernel in a `kernel adam` run)
+            # (tell: es_tell_kernel, or es_tell_adam_kernel in a `kernel adam` run; the *_sigma kernels and es_rank_q_kernel in a
+            # `kernel sigma` run)
             print("P = %-5d ask %8.1f us, rank %7.1f us, tell %8.1f us, every other kernel of the generation %9.1f us" %
                   (m, g["es_ask_kernel"] / 1e3, g["es_rank_kernel"] / 1e3, g["es_tell_kernel"] / 1e3, g["rest"] / 1e3))
             if "obs_stats_kernel" in g:        # (a `kernel obs` run: T launches per generation, one in front of every policy launch)
@@ -163,7 +172,7 @@ if __name__ == "__main__":
     if what == "loop":
         loop()
     elif what == "kernel":
-        kernel(adam=sys.argv[2:3] == ["adam"], obs=sys.argv[2:3] == ["obs"])
+        kernel(adam=sys.argv[2:3] == ["adam"], obs=sys.argv[2:3] == ["obs"], sigma=sys.argv[2:3] == ["sigma"])
     elif what == "stats":
         stats(sys.argv[2])
     else:
