@@ -74,6 +74,12 @@ struct bsk_es {
     int sigma_kind = BSK_ES_SIGMA_FIXED;
     double lr_sigma = 0.0, max_change = 0.0, sigma_min = 0.0, sigma_max = 0.0;
     double* d_sigma = nullptr;
+    // bsk_es_set_log: off until a capacity is given; then ONE allocation of 8-byte words
+    // [log_gen C | log_row 8 C | best_fitness | best_generation | best_member, - | take, b | best_params ceil(n_params / 2)]
+    int log_capacity = 0;
+    unsigned long long* d_log = nullptr;
+    const double* d_mean_len = nullptr;    // the caller's, bound by bsk_es_set_log; may be NULL
+    hipStream_t last_stream = nullptr;     // of the last ask / tell / apply_obs_norm: what bsk_es_set_log asks about a capture
 };
 
 namespace {
@@ -458,7 +464,7 @@ int bsk_es_create(const bsk_policy_spec* spec, int n_members, const float* theta
 void bsk_es_destroy(bsk_es* es) {
     if (!es) return;
     DeviceGuard guard(es->device);
-    free_all({es->d_state, es->d_theta, es->d_w, es->d_adam, es->d_sigma});
+    free_all({es->d_state, es->d_theta, es->d_w, es->d_adam, es->d_sigma, es->d_log});
     delete es;
 }
 
@@ -483,6 +489,25 @@ static bsk::EsSigma es_sigma(const bsk_es* es) {
     return sv;
 }
 
+// the words of the log's allocation and the views of them the kernels take
+static size_t es_log_words(const bsk_es* es, int capacity) { return 9 * (size_t)capacity + 4 + ((size_t)es->lay.n_params + 1) / 2; }
+
+static bsk::EsLog es_log(const bsk_es* es) {
+    const size_t C = (size_t)es->log_capacity;
+    unsigned long long* tail = es->d_log + 9 * C;
+    bsk::EsLog lg;
+    lg.gen = es->d_log;
+    lg.row = (double*)(es->d_log + C);
+    lg.best_fitness = (double*)tail;
+    lg.best_generation = tail + 1;
+    lg.best_member = (int*)(tail + 2);
+    lg.cand = (int*)(tail + 3);
+    lg.best_params = (float*)(tail + 4);
+    lg.mean_len = es->d_mean_len;
+    lg.capacity = es->log_capacity;
+    return lg;
+}
+
 int bsk_es_ask(bsk_es* es, bsk_population* pop, void* stream) {
     if (!es || !pop) return fail(BSK_EINVAL, "es/population is NULL");
     if (pop->n_members != es->n_members) return fail(BSK_EINVAL, "bsk_es_ask: the population's n_members differs from the optimiser's");
@@ -490,6 +515,7 @@ int bsk_es_ask(bsk_es* es, bsk_population* pop, void* stream) {
         return fail(BSK_EINVAL, "bsk_es_ask: the population's spec differs from the optimiser's");
     if (pop->device != es->device) return fail(BSK_EINVAL, "bsk_es_ask: the optimiser and the population live on different devices");
     DeviceGuard guard(es->device);
+    es->last_stream = (hipStream_t)stream;
     if (es->sigma_kind == BSK_ES_SIGMA_PGPE)
         HIP_TRY(bsk::launch_es_ask_sigma(es->lay, es_args(es), es->d_sigma, pop->d_params, (hipStream_t)stream));
     else
@@ -502,6 +528,9 @@ int bsk_es_tell(bsk_es* es, const double* d_fitness, void* stream) {
     DeviceGuard guard(es->device);
     const bool pgpe = es->sigma_kind == BSK_ES_SIGMA_PGPE;
     double* d_q = es->d_w + es->n_members / 2;
+    es->last_stream = (hipStream_t)stream;
+    if (es->log_capacity > 0)                             // in front of the update: theta, sigma_vec and the generation as ask read them
+        HIP_TRY(bsk::launch_es_log(es_args(es), pgpe ? es->d_sigma : nullptr, es->lay.n_params, d_fitness, es_log(es), (hipStream_t)stream));
     if (pgpe)
         HIP_TRY(bsk::launch_es_rank_q(d_fitness, es->n_members, es->d_w, d_q, (hipStream_t)stream));
     else
@@ -663,6 +692,82 @@ int bsk_es_set_sigma(bsk_es* es, const double* sigma) {
     return BSK_OK;
 }
 
+int bsk_es_set_log(bsk_es* es, int capacity, const double* d_mean_len) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    if (capacity < 0) return fail(BSK_EINVAL, "bsk_es_set_log: capacity must not be negative");
+    DeviceGuard guard(es->device);
+    // (the optimiser serves one stream at a time: the stream of its last launch is the one a capture of its loop records)
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (es->last_stream && hipStreamIsCapturing(es->last_stream, &st) != hipSuccess) {
+        (void)hipGetLastError();                          // (a stream that has been destroyed since captures nothing)
+        st = hipStreamCaptureStatusNone;
+        es->last_stream = nullptr;
+    }
+    if (st != hipStreamCaptureStatusNone)
+        return fail(BSK_EINVAL, "bsk_es_set_log: the optimiser's stream is being captured; it allocates and synchronises and cannot be captured");
+    HIP_SYNC(hipDeviceSynchronize());                     // (queued tells still write the old log)
+    if (es->d_log) {
+        (void)hipFree(es->d_log);
+        es->d_log = nullptr;
+    }
+    es->log_capacity = 0;
+    es->d_mean_len = nullptr;
+    if (capacity == 0) return BSK_OK;
+    const size_t C = (size_t)capacity, words = es_log_words(es, capacity);
+    HIP_TRY(hipMalloc(&es->d_log, words * 8));
+    HIP_TRY(hipMemset(es->d_log, 0xff, C * 8));                                    // log_gen: all ones
+    HIP_TRY(hipMemset(es->d_log + C, 0, (words - C) * 8));                           // log_row, best_params, the candidate words
+    const unsigned long long tail[3] = {0x7ff8000000000000ull, ~0ull, 0xffffffffull};   // a NaN, all ones, member -1
+    HIP_COPY(hipMemcpy(es->d_log + 9 * C, tail, sizeof tail, hipMemcpyHostToDevice));
+    es->log_capacity = capacity;
+    es->d_mean_len = d_mean_len;
+    return BSK_OK;
+}
+
+int bsk_es_get_log(bsk_es* es, uint64_t* gen, double* rows) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    if (es->log_capacity < 1) return fail(BSK_EINVAL, "bsk_es_get_log: the optimiser has no log (bsk_es_set_log)");
+    DeviceGuard guard(es->device);
+    const size_t C = (size_t)es->log_capacity;
+    HIP_SYNC(hipDeviceSynchronize());
+    if (gen) HIP_COPY(hipMemcpy(gen, es->d_log, C * 8, hipMemcpyDeviceToHost));
+    if (rows) HIP_COPY(hipMemcpy(rows, es->d_log + C, 8 * C * 8, hipMemcpyDeviceToHost));
+    return BSK_OK;
+}
+
+int bsk_es_get_best(bsk_es* es, float* params, double* fitness, uint64_t* generation, int32_t* member) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    if (es->log_capacity < 1) return fail(BSK_EINVAL, "bsk_es_get_best: the optimiser has no log (bsk_es_set_log)");
+    DeviceGuard guard(es->device);
+    const bsk::EsLog lg = es_log(es);
+    HIP_SYNC(hipDeviceSynchronize());
+    if (params) HIP_COPY(hipMemcpy(params, lg.best_params, (size_t)es->lay.n_params * sizeof(float), hipMemcpyDeviceToHost));
+    if (fitness) HIP_COPY(hipMemcpy(fitness, lg.best_fitness, 8, hipMemcpyDeviceToHost));
+    if (generation) HIP_COPY(hipMemcpy(generation, lg.best_generation, 8, hipMemcpyDeviceToHost));
+    if (member) HIP_COPY(hipMemcpy(member, lg.best_member, 4, hipMemcpyDeviceToHost));
+    return BSK_OK;
+}
+
+int bsk_es_set_best(bsk_es* es, const float* params, const double* fitness, const uint64_t* generation, const int32_t* member) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    if (es->log_capacity < 1) return fail(BSK_EINVAL, "bsk_es_set_best: the optimiser has no log (bsk_es_set_log)");
+    DeviceGuard guard(es->device);
+    const bsk::EsLog lg = es_log(es);
+    HIP_SYNC(hipDeviceSynchronize());                     // (queued tells still read and write the old champion)
+    if (params) HIP_COPY(hipMemcpy(lg.best_params, params, (size_t)es->lay.n_params * sizeof(float), hipMemcpyHostToDevice));
+    if (fitness) HIP_COPY(hipMemcpy(lg.best_fitness, fitness, 8, hipMemcpyHostToDevice));
+    if (generation) HIP_COPY(hipMemcpy(lg.best_generation, generation, 8, hipMemcpyHostToDevice));
+    if (member) HIP_COPY(hipMemcpy(lg.best_member, member, 4, hipMemcpyHostToDevice));
+    return BSK_OK;
+}
+
+int bsk_es_best_device(bsk_es* es, const float** d_params) {
+    if (!es || !d_params) return fail(BSK_EINVAL, "es/d_params is NULL");
+    if (es->log_capacity < 1) return fail(BSK_EINVAL, "bsk_es_best_device: the optimiser has no log (bsk_es_set_log)");
+    *d_params = es_log(es).best_params;
+    return BSK_OK;
+}
+
 int bsk_obs_stats_create(int n_cap, int device_id, bsk_obs_stats** out) {
     if (!out) return fail(BSK_EINVAL, "out is NULL");
     *out = nullptr;
@@ -770,6 +875,7 @@ int bsk_es_apply_obs_norm(bsk_es* es, bsk_obs_stats* s, double std_min, void* st
     if (!std::isfinite(std_min) || !(std_min > 0.0)) return fail(BSK_EINVAL, "bsk_es_apply_obs_norm: std_min must be finite and positive");
     if (es->device != s->device) return fail(BSK_EINVAL, "bsk_es_apply_obs_norm: the optimiser and the statistics live on different devices");
     DeviceGuard guard(es->device);
+    es->last_stream = (hipStream_t)stream;
     HIP_TRY(bsk::launch_es_obs_norm(s->st.tot, s->st.tot_n, std_min, es->d_theta, (hipStream_t)stream));
     return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
 }

@@ -7,6 +7,8 @@
 //   es_advance_kernel  the generation counter += 1 (es_advance_adam_kernel: and Adam's two running powers)
 //   es_ask_sigma_kernel, es_rank_q_kernel, es_tell_sigma_kernel, es_tell_adam_sigma_kernel     the same four under
 //                      BSK_ES_SIGMA_PGPE: a step size per parameter in device memory, moved by lane 0 behind a second sum
+//   es_log_kernel, es_best_kernel     bsk_es_set_log: one wave for the generation's row and the champion rule, then one thread per
+//                      parameter for the champion's floats - in front of the update, from what ask read
 // The noise is never stored: z(g, i, j) is one Philox4x32-10 call and an inverse normal CDF made of f64 + - * /, sqrt and integer
 // operations.  Compiled with -ffp-contract=off (Makefile), as bsk_population.hip is: every operation rounds on its own, and numpy
 // repeats all of it bit for bit (policy_ref.py: es_noise_ref, es_ask_ref, es_tell_ref, es_tell_adam_ref, es_ask_sigma_ref,
@@ -14,6 +16,7 @@
 #include "bsk_es.hpp"
 
 #include "bsk_philox.hpp"
+#include "bsk_tree.hpp"
 
 namespace bsk {
 
@@ -85,6 +88,22 @@ __device__ __forceinline__ double es_noise(unsigned long long seed, unsigned lon
     return es_inverse_normal(((double)k + 0.5) * 0x1p-52);
 }
 
+// The two floats of parameter j in pair `pair` (include/bskgpu.h, ask): theta_j +- s_j * z(g, pair, j), s_j the one sigma or
+// sigma_vec[j]; (float)theta_j for a frozen j.  ONE text behind ask and the champion of the training log (es_best_kernel), so
+// that the two cannot diverge.  A macro and not a device function for the reason ES_PAIR_SUM gives: behind a call es_ask_kernel
+// came out with other registers and another order of its two stores, and it keeps the instruction stream it had.
+#define ES_PAIR_VALUES(es, sigma_vec, pair, j, plus, minus)                                                                     \
+    {                                                                                                                           \
+        const double t = es.theta[j];                                                                                           \
+        if (j < es.frozen) {                                                                                                    \
+            plus = minus = (float)t;                                                                                            \
+        } else {                                                                                                                \
+            const double step = (sigma_vec ? sigma_vec[j] : es.sigma) * es_noise(es.state[0], es.state[1], pair, (unsigned)j);  \
+            plus = (float)(t + step);                                                                                           \
+            minus = (float)(t - step);                                                                                          \
+        }                                                                                                                       \
+    }
+
 // Pair blockIdx.x, float d of the device layout: policy_pack_kernel's gather with theta +- sigma * z in place of a source block.
 // Both members of the pair from ONE evaluation of z; every float of both device blocks is written by exactly one thread.
 // sigma_vec == nullptr (a constant where es_ask_kernel inlines this): the optimiser's one sigma; otherwise sigma_vec[j].
@@ -95,16 +114,7 @@ __device__ __forceinline__ void es_ask_pair(const EsArgs& es, const double* __re
     if (d >= map.n_device) return;
     const int j = policy_pack_source(map, d);
     float plus = 0.0f, minus = 0.0f;
-    if (j >= 0) {
-        const double t = es.theta[j];
-        if (j < es.frozen) {
-            plus = minus = (float)t;
-        } else {
-            const double step = (sigma_vec ? sigma_vec[j] : es.sigma) * es_noise(es.state[0], es.state[1], blockIdx.x, (unsigned)j);
-            plus = (float)(t + step);
-            minus = (float)(t - step);
-        }
-    }
+    if (j >= 0) ES_PAIR_VALUES(es, sigma_vec, blockIdx.x, j, plus, minus)
     float* at = dst + (size_t)(2u * blockIdx.x) * (size_t)map.n_device + d;
     at[0] = plus;
     at[map.n_device] = minus;
@@ -305,6 +315,91 @@ __global__ void es_advance_adam_kernel(unsigned long long* state, double* beta_p
     beta_pow[0] = beta_pow[0] * beta1;
     beta_pow[1] = beta_pow[1] * beta2;
     state[1] += 1ull;
+}
+
+// The training log (include/bskgpu.h, bsk_es_set_log): ONE wave in front of the update.  Lane l walks members l, l + 64, ...
+// ascending: its running best and worst under es_beats (the worst among the non-NaN members only), the sums of x, x * x and
+// mean_len in the library's one order (from the first element, +0.0 with none), the number of non-NaN members.  The lanes join with
+// __shfl_down: best and worst under the same predicate - es_beats with its index tiebreak is a strict total order, so the join's
+// order does not matter - the sums in the fitness tree.  Lane 0 writes row g mod capacity and applies the champion rule; the
+// candidate words {take, b} are for es_best_kernel behind this launch.  (__shfl_down past the wave's end returns the lane's own
+// value: a member never beats itself, and a lane at or above the stride adds nothing.)
+__global__ __launch_bounds__(64) void es_log_kernel(const unsigned long long* __restrict__ state, const double* __restrict__ fitness, int P,
+                                                    const EsLog lg) {
+#pragma clang fp contract(off)
+    const int lane = (int)threadIdx.x;
+    double bf = 0.0, wf = 0.0;
+    int bi = -1, wi = -1, cnt = 0;
+    double s1 = 0.0, s2 = 0.0, l1 = 0.0;
+    for (int k = lane; k < P; k += 64) {
+        const double f = fitness[k];
+        const bool isn = f != f;
+        const double x = isn ? 0.0 : f;
+        const double q = x * x;
+        s1 = k == lane ? x : s1 + x;
+        s2 = k == lane ? q : s2 + q;
+        if (lg.mean_len) {
+            const double m = lg.mean_len[k];
+            l1 = k == lane ? m : l1 + m;
+        }
+        cnt += isn ? 0 : 1;
+        if (bi < 0 || es_beats(f, k, bf, bi)) { bf = f; bi = k; }
+        if (!isn && (wi < 0 || es_beats(wf, wi, f, k))) { wf = f; wi = k; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double obf = __shfl_down(bf, off, 64), owf = __shfl_down(wf, off, 64);
+        const int obi = __shfl_down(bi, off, 64), owi = __shfl_down(wi, off, 64), ocnt = __shfl_down(cnt, off, 64);
+        if (obi >= 0 && (bi < 0 || es_beats(obf, obi, bf, bi))) { bf = obf; bi = obi; }
+        if (owi >= 0 && (wi < 0 || es_beats(wf, wi, owf, owi))) { wf = owf; wi = owi; }
+        if (lane < off) cnt += ocnt;
+    }
+    s1 = fitness_tree(s1, lane);
+    s2 = fitness_tree(s2, lane);
+    l1 = fitness_tree(l1, lane);
+    if (lane != 0) return;
+    const unsigned long long g = state[1];
+    const unsigned long long slot = g % (unsigned long long)lg.capacity;
+    double* row = lg.row + 8 * slot;
+    row[0] = bf;
+    row[1] = wi >= 0 ? wf : __longlong_as_double(0x7ff8000000000000ll);
+    row[2] = s1;
+    row[3] = s2;
+    row[4] = (double)cnt;
+    row[5] = (double)bi;
+    row[6] = l1;
+    row[7] = lg.mean_len ? lg.mean_len[bi] : 0.0;
+    lg.gen[slot] = g;
+    const double champion = *lg.best_fitness;
+    const bool take = bf == bf && (champion != champion || bf > champion);
+    if (take) {
+        *lg.best_fitness = bf;
+        *lg.best_generation = g;
+        lg.best_member[0] = bi;
+    }
+    lg.cand[0] = take ? 1 : 0;
+    lg.cand[1] = bi;
+}
+
+// One thread per parameter j, behind es_log_kernel on the same stream (the kernel boundary orders the candidate words: no atomics,
+// no fence) and in front of the update: while `take`, best_params[j] = the float ask writes for member b of this generation -
+// ES_PAIR_VALUES, the text of es_ask_pair, with theta, sigma_vec and the generation word as ask read them.
+__global__ __launch_bounds__(256) void es_best_kernel(const EsArgs es, const double* __restrict__ sigma_vec, int n_params, const EsLog lg) {
+#pragma clang fp contract(off)
+    const int j = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (j >= n_params || lg.cand[0] == 0) return;
+    const int b = lg.cand[1];
+    float plus, minus;
+    ES_PAIR_VALUES(es, sigma_vec, (unsigned)(b >> 1), j, plus, minus)
+    lg.best_params[j] = (b & 1) ? minus : plus;
+}
+
+hipError_t launch_es_log(const EsArgs& es, const double* sigma_vec, int n_params, const double* fitness, const EsLog& lg, hipStream_t s) {
+    hipLaunchKernelGGL(es_log_kernel, dim3(1), dim3(64), 0, s, es.state, fitness, 2 * es.pairs, lg);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(es_best_kernel, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, s, es, sigma_vec, n_params, lg);
+    return hipGetLastError();
 }
 
 hipError_t launch_es_ask(const PolicyLayout& lay, const EsArgs& es, float* d_params, hipStream_t s) {

@@ -33,6 +33,19 @@ struct EsSigma {
     double max_change, sigma_min, sigma_max;
 };
 
+// bsk_es_set_log: the ring of per-generation rows and the champion, all device memory (one allocation of the optimiser's)
+struct EsLog {
+    unsigned long long* gen;           // [capacity], the generation each row belongs to (all ones: never written)
+    double* row;                       // [capacity][8]
+    double* best_fitness;              // the champion: a NaN while there is none
+    unsigned long long* best_generation;
+    int* best_member;
+    int* cand;                         // {take, b}: es_log_kernel's words for es_best_kernel
+    float* best_params;                // [n_params], the C-ABI parameter layout
+    const double* mean_len;            // [n_members] or nullptr: the caller's, bound by bsk_es_set_log
+    int capacity;
+};
+
 // The members of this generation into d_params ([2 * pairs][lay.n_device], a population's device layout): one launch, every
 // float written exactly once.
 hipError_t launch_es_ask(const PolicyLayout& lay, const EsArgs& es, float* d_params, hipStream_t s);
@@ -50,6 +63,9 @@ hipError_t launch_es_rank_q(const double* fitness, int n_members, double* w, dou
 hipError_t launch_es_tell_sigma(const EsArgs& es, int n_params, const double* w, const double* q, double lr, const EsSigma& sv, hipStream_t s);
 hipError_t launch_es_tell_adam_sigma(const EsArgs& es, int n_params, const double* w, const double* q, const EsAdam& ad, const EsSigma& sv,
                                      hipStream_t s);
+// The two launches of the training log, in front of the update (theta, sigma_vec and the generation word as ask read them):
+// the row of this generation and the champion rule, then the champion's floats.  sigma_vec: nullptr under BSK_ES_SIGMA_FIXED.
+hipError_t launch_es_log(const EsArgs& es, const double* sigma_vec, int n_params, const double* fitness, const EsLog& lg, hipStream_t s);
 // generation += 1 and beta_pow *= {beta1, beta2}, one thread, behind launch_es_tell_adam on the same stream
 hipError_t launch_es_advance_adam(unsigned long long* state, double* beta_pow, double beta1, double beta2, hipStream_t s);
 // generation += 1, one thread, behind a tell on the same stream (a replayed graph moves on to the next generation)

@@ -22,7 +22,7 @@ What needs no device lives beside this module and is re-exported here under the 
 layout of the parameter block in ``policy_spec`` (``check_spec``, ``pack_params``, ...), and in ``policy_ref`` the numpy
 restatements the kernels are held to bit for bit (``mlp_ref`` / ``act_ref``: every layer output one k-ordered chain of f32 fused
 multiply-adds from the bias; ``population_fitness_ref``; ``es_noise_ref`` / ``es_ask_ref`` / ``es_tell_ref`` /
-``es_tell_adam_ref`` / ``es_ask_sigma_ref`` / ``es_tell_pgpe_ref``; ``obs_stats_accumulate_ref`` / ``obs_stats_totals_ref`` / ``obs_norm_ref``) with ``EvolutionStrategy``, the host-side loop the device one was modelled on.
+``es_tell_adam_ref`` / ``es_ask_sigma_ref`` / ``es_tell_pgpe_ref`` / ``es_log_row_ref`` / ``es_best_ref``; ``obs_stats_accumulate_ref`` / ``obs_stats_totals_ref`` / ``obs_norm_ref``) with ``EvolutionStrategy``, the host-side loop the device one was modelled on.
 """
 import ctypes as C
 import sys
@@ -31,8 +31,10 @@ import numpy as np
 
 from . import _hip, _lib
 from ._lib import check
-from .policy_ref import (EvolutionStrategy, _es_pair_sum, _es_pair_sums, _series_log, act_ref, centred_ranks, check_adam,  # noqa: F401
-                         es_ask_ref, es_ask_sigma_ref, es_inverse_normal_ref, es_noise_ref, es_tell_adam_ref, es_tell_pgpe_ref,
+from .policy_ref import (ES_LOG_COLUMNS, ES_LOG_EMPTY, EvolutionStrategy, _es_pair_sum, _es_pair_sums, _series_log, act_ref,  # noqa: F401
+                         centred_ranks, check_adam, check_log,
+                         es_ask_ref, es_ask_sigma_ref, es_best_ref, es_champion_empty, es_inverse_normal_ref, es_log_order_ref,
+                         es_log_row_ref, es_log_slot_ref, es_log_table_ref, es_noise_ref, es_tell_adam_ref, es_tell_pgpe_ref,
                          es_tell_ref, es_uniform_ref, fma32,
                          mlp_ref, obs_moments_ref, obs_norm_ref, obs_stats_accumulate_ref, obs_stats_totals_ref,
                          obs_stats_zero_state, philox4x32_10, population_fitness_ref, sample_uniform, shared_slot_ref, softmax_ref)
@@ -500,12 +502,15 @@ class DeviceEvolutionStrategy(_DeviceObject):
     every ``tell`` from the same pairs that move theta (``bsk_es_set_sigma_adaptation``; ``es_ask_sigma_ref``,
     ``es_tell_pgpe_ref``): by ``lr_sigma``, at most ``sigma_max_change`` of itself per generation, inside
     [``sigma_min``, ``sigma_max``] (None: ``sigma`` / 100 and 10 ``sigma``).  None, the default, keeps the one ``sigma`` and never
-    calls that entry point.  Not thread-safe, one stream at a time."""
+    calls that entry point.  ``log_capacity`` > 0 keeps a training log of that many generations and the best member so far on
+    the device (``set_log``; ``training_log``, ``best``); 0, the default, never calls that entry point either.  Not thread-safe,
+    one stream at a time."""
     _kind, _what = "es", "evolution strategy"
 
     def __init__(self, spec, theta, population, sigma=0.1, lr=0.05, seed=0, frozen=10, device=0, optimizer="sgd", beta1=0.9,
                  beta2=0.999, eps=1e-8, weight_decay=0.0, sigma_adapt=None, lr_sigma=0.1, sigma_max_change=0.2, sigma_min=None,
-                 sigma_max=None):
+                 sigma_max=None, log_capacity=0):
+        log_capacity = check_log(log_capacity)
         if optimizer not in ("sgd", "adam"):
             raise ValueError("optimizer must be 'sgd' or 'adam', got %r" % (optimizer,))
         if optimizer == "adam":
@@ -518,6 +523,7 @@ class DeviceEvolutionStrategy(_DeviceObject):
             sigma_max = 10.0 * float(sigma) if sigma_max is None else sigma_max
             check_sigma_adaptation(lr_sigma, sigma_max_change, sigma_min, sigma_max, sigma)
         self.sigma_adapt, self.sigma_adaptation = None, None
+        self.log_capacity, self._log_len, self._log_source = 0, None, None
         self.spec = _as_spec(spec)
         self.n_params = n_params(self.spec)
         self.population, self.sigma, self.lr, self.frozen = int(population), float(sigma), float(lr), int(frozen)
@@ -528,6 +534,8 @@ class DeviceEvolutionStrategy(_DeviceObject):
             self.set_optimizer("adam", beta1, beta2, eps, weight_decay)
         if sigma_adapt is not None:
             self.set_sigma_adaptation(sigma_adapt, lr_sigma, sigma_max_change, sigma_min, sigma_max)
+        if log_capacity:
+            self.set_log(log_capacity)
 
     # ------------------------------------------------------------------ state
     @property
@@ -607,6 +615,73 @@ class DeviceEvolutionStrategy(_DeviceObject):
         s = _host_block(sigma_vec, self.n_params, np.float64, what="values")
         check(self._lib.bsk_es_set_sigma(self._handle(), s.ctypes.data))
 
+    # ------------------------------------------------------------------ the training log and the champion
+    def set_log(self, capacity, mean_len=None):
+        """A ring of ``capacity`` generations and the best member so far, on the device (``bsk_es_set_log``): from now on every
+        ``tell`` writes the generation's row and applies the champion rule in front of its update (``es_log_row_ref``,
+        ``es_best_ref``).  Every call with ``capacity`` > 0 starts from an empty log and no champion; 0 turns both off.
+        ``mean_len``: P float64 in DEVICE memory the length columns are read from - a raw pointer or anything with
+        ``__cuda_array_interface__``, the caller's to keep alive; None: a buffer of the optimiser's own, zeros (so the two columns
+        are +0.0, as with nothing bound) until ``run_generation`` has the rollout write the members' mean episode lengths there.
+        Theta, the generation, Adam's state and the step sizes stay; synchronises, and cannot be captured."""
+        def refuse(typestr, shape, size, dense):
+            if typestr != "<f8" or size != self.population or (len(shape) == 1 and not dense):
+                return "mean_len: %d contiguous float64, got %r %r" % (self.population, typestr, shape)
+        capacity = check_log(capacity)
+        queued, ptr = self._source, None
+        if capacity and mean_len is not None:
+            ptr, _ = self._device_pointer(mean_len, 8, refuse)
+            self._source = queued                          # (a queued tell still reads its fitness)
+        # off first: the refusal under capture comes from the library, before anything is allocated or written here
+        check(self._lib.bsk_es_set_log(self._handle(), 0, None))
+        self.log_capacity, self._log_len, self._log_source = 0, None, None
+        if not capacity:
+            return
+        if mean_len is None:
+            if self._out is None:
+                self._out = {}
+            if "mean_len" not in self._out:
+                self._out["mean_len"] = _hip.DeviceBuffer(8 * self.population, self.device)
+            ptr = self._out["mean_len"].ptr
+            with _hip.device_guard(self.device):
+                _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(ptr), 0, 8 * self.population, None), "hipMemsetAsync")
+        check(self._lib.bsk_es_set_log(self._handle(), capacity, C.c_void_p(int(ptr)) if ptr else None))
+        self.log_capacity, self._log_len, self._log_source = capacity, int(ptr or 0) or None, mean_len      # (every later tell reads it)
+
+    def training_log(self):
+        """The log as a dict of numpy arrays over the generations it holds, sorted by generation (``es_log_table_ref``):
+        ``generation``, ``best``, ``worst``, ``sum``, ``sum_sq``, ``count``, ``best_member``, ``len_sum``, ``best_len`` as the
+        device stored them, and ``mean`` / ``std`` of the non-NaN members derived here (NaN where ``count`` is 0).  Synchronises.
+        An error with no log."""
+        gen = np.empty(max(self.log_capacity, 1), np.uint64)
+        rows = np.empty((gen.size, 8), np.float64)
+        check(self._lib.bsk_es_get_log(self._handle(), gen.ctypes.data, rows.ctypes.data))
+        return es_log_table_ref(gen, rows)
+
+    @property
+    def best(self):
+        """The champion -> (params float32 (n_params,), fitness, generation, member); (zeros, NaN, ``ES_LOG_EMPTY``, -1) while no
+        generation has taken.  Synchronises.  An error with no log."""
+        params, f, g, m = np.empty(self.n_params, np.float32), C.c_double(), C.c_uint64(), C.c_int32()
+        check(self._lib.bsk_es_get_best(self._handle(), params.ctypes.data, C.addressof(f), C.addressof(g), C.addressof(m)))
+        return params, f.value, g.value, m.value
+
+    def set_best(self, params=None, fitness=None, generation=None, member=None):
+        """A new champion, for a checkpoint that resumes bit for bit; None keeps; synchronises.  An error with no log."""
+        p = None if params is None else _host_block(params, self.n_params)
+        f = None if fitness is None else C.c_double(float(fitness))
+        g = None if generation is None else C.c_uint64(int(generation))
+        m = None if member is None else C.c_int32(int(member))
+        check(self._lib.bsk_es_set_best(self._handle(), None if p is None else p.ctypes.data,
+                                        *[None if x is None else C.addressof(x) for x in (f, g, m)]))
+
+    def best_params_ptr(self):
+        """The champion's parameter block as a DEVICE pointer to n_params float32, valid until the next ``set_log`` or ``close``:
+        ``pop.set_params_device(es.best_params_ptr(), m, 1)`` loads it into a member with no host in between."""
+        p = C.c_void_p()
+        check(self._lib.bsk_es_best_device(self._handle(), C.byref(p)))
+        return p.value
+
     # ------------------------------------------------------------------ the search
     def ask(self, pop, stream=0):
         """This generation's members into every member of ``pop`` (a ``PolicyPopulation`` of the same spec and size): one launch
@@ -615,7 +690,8 @@ class DeviceEvolutionStrategy(_DeviceObject):
 
     def tell(self, d_fitness, stream=0):
         """``d_fitness``: P float64 in DEVICE memory (greater is better) - a raw pointer or anything with
-        ``__cuda_array_interface__``.  Ranks them, moves theta and advances the generation: three launches on ``stream``."""
+        ``__cuda_array_interface__``.  Ranks them, moves theta and advances the generation: three launches on ``stream``, and with
+        a log on two more in front of the update."""
         def refuse(typestr, shape, size, dense):
             if typestr != "<f8" or size != self.population or (len(shape) == 1 and not dense):       # (a 1-D array's stride only)
                 return "device fitness: %d contiguous float64, got %r %r" % (self.population, typestr, shape)
@@ -625,7 +701,9 @@ class DeviceEvolutionStrategy(_DeviceObject):
     def fitness_buffer(self):
         """The device buffer of P float64 ``run_generation`` has the rollout write the fitness to (``_hip.DeviceBuffer``)."""
         if self._out is None:
-            self._out = {"fitness": _hip.DeviceBuffer(8 * self.population, self.device)}
+            self._out = {}
+        if "fitness" not in self._out:
+            self._out["fitness"] = _hip.DeviceBuffer(8 * self.population, self.device)
         return self._out["fitness"]
 
     def apply_obs_norm(self, stats, std_min=1e-6, stream=0):
@@ -645,23 +723,25 @@ class DeviceEvolutionStrategy(_DeviceObject):
         changes.  That is exact for ``greedy``: sample mode still draws its uniform per global env index.
         ``obs_stats``: an ``ObsStats`` the rollout accumulates into (attached to ``pop`` for the rollout, which is left with what it
         had attached before), and ``apply_obs_norm(obs_stats, std_min)`` behind ``tell``: generation g runs with the statistics of
-        the generations before it."""
+        the generations before it.  With a log on the rollout also writes the members' mean episode lengths into the buffer
+        ``set_log`` bound, for the row's length columns; with it off the rollout is passed what it was passed before."""
         prop = getattr(prop, "propagator", prop)
         fit = self.fitness_buffer()
         stream = prop.stream_ptr()
+        lengths = {"d_mean_len": self._log_len} if self.log_capacity else {}
         if reset and shared_episodes:
             prop.reset_from_pool_shared(prop.n_envs // self.population, self.generation_ptr())
         elif reset:
             prop.reset_from_pool_device(None)
         self.ask(pop, stream)
         if obs_stats is None:
-            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr)
+            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr, **lengths)
             self.tell(fit.ptr, stream)
             return
         before = getattr(pop, "_stats", None)
         pop.set_obs_stats(obs_stats)
         try:
-            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr)
+            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr, **lengths)
         finally:
             pop.set_obs_stats(before)
         self.tell(fit.ptr, stream)

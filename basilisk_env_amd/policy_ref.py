@@ -478,6 +478,123 @@ def es_tell_pgpe_ref(theta, sigma_vec, fitness, lr, frozen, seed, generation, lr
     return theta, sv, m, v, np.array([p1, p2], np.float64)
 
 
+# The training log and the champion (bsk_es_set_log; kernels es_log_kernel / es_best_kernel), restated
+
+ES_LOG_COLUMNS = ("best", "worst", "sum", "sum_sq", "count", "best_member", "len_sum", "best_len")
+ES_LOG_EMPTY = 2 ** 64 - 1                     # log_gen of a slot that has never been written, best_generation of no champion
+
+
+def _lanes_then_tree(x):
+    """The library's one order on a 1-D float64 array -> s[0]: lane l = 0 .. 63 adds its elements l, l + 64, ... ascending from the
+    first (+0.0 with none), then s[l] = s[l] + s[l + stride] for stride 32 ... 1."""
+    x = np.asarray(x, np.float64).reshape(-1)
+    s = np.zeros(64, np.float64)
+    s[:min(64, x.size)] = x[:64]
+    with np.errstate(invalid="ignore", over="ignore"):
+        for at in range(64, x.size, 64):
+            chunk = x[at:at + 64]
+            s[:chunk.size] = s[:chunk.size] + chunk
+        for stride in _TREE:
+            s[:stride] = s[:stride] + s[stride:2 * stride]
+    return s[0]
+
+
+def es_log_order_ref(fitness):
+    """-> (b, wst) of include/bskgpu.h under the order of ``centred_ranks``: b the member nobody beats; wst, among the members
+    that are not NaN, the one that beats no other of them (-1 when all are NaN)."""
+    f = np.asarray(fitness, np.float64).reshape(-1)
+    nan = np.isnan(f)
+    order = np.lexsort((-np.where(nan, 0.0, f), nan))          # (centred_ranks' order: the best first, NaNs last)
+    cnt = int(f.size - nan.sum())
+    return int(order[0]), (int(order[cnt - 1]) if cnt else -1)
+
+
+def es_log_row_ref(fitness, mean_len=None):
+    """The eight words ``bsk_es_tell`` writes into its log row -> float64 (8,), ``ES_LOG_COLUMNS``: f[b], f[wst] (NaN when every
+    member is NaN), S1 over x_k = f_k (+0.0 for a NaN), S2 over x_k * x_k, the number of non-NaN members, b, and with ``mean_len``
+    (P,) L1 over it and mean_len[b] (+0.0 both without) - each sum in the library's one order, every operation rounded on its own."""
+    f = np.asarray(fitness, np.float64).reshape(-1)
+    if f.size < 1:
+        raise ValueError("expected at least one fitness value")
+    b, wst = es_log_order_ref(f)
+    nan = np.isnan(f)
+    x = np.where(nan, 0.0, f)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = x * x
+    row = np.zeros(8, np.float64)
+    row[0] = f[b]
+    row[1] = f[wst] if wst >= 0 else np.nan
+    row[2], row[3] = _lanes_then_tree(x), _lanes_then_tree(q)
+    row[4], row[5] = float(f.size - nan.sum()), float(b)
+    if mean_len is not None:
+        ml = np.asarray(mean_len, np.float64).reshape(-1)
+        if ml.size != f.size:
+            raise ValueError("mean_len has one value per member")
+        row[6], row[7] = _lanes_then_tree(ml), ml[b]
+    return row
+
+
+def es_log_slot_ref(generation, capacity):
+    """The ring slot of a generation: the whole 64-bit word mod the capacity."""
+    if int(capacity) < 1:
+        raise ValueError("capacity must be >= 1")
+    return (int(generation) & (2 ** 64 - 1)) % int(capacity)
+
+
+def es_champion_empty(n_params):
+    """The champion after ``bsk_es_set_log`` -> (params float32 zeros, fitness NaN, generation all ones, member -1)."""
+    return np.zeros(int(n_params), np.float32), float("nan"), ES_LOG_EMPTY, -1
+
+
+def es_best_ref(champion, fitness, generation, members_row_fn):
+    """The champion rule of ``bsk_es_tell`` -> the new (params, fitness, generation, member).  ``champion``: the old four;
+    ``members_row_fn(b)`` -> member b of this generation as ask writes it, float32 (n_params,) - a row of ``es_ask_ref`` /
+    ``es_ask_sigma_ref`` on theta and sigma as they are BEFORE this tell (there is no second noise formula here); called only when
+    the generation's best member takes: it is not NaN and the champion is NaN or strictly lower.  A tie keeps the older one."""
+    params, best, gen, member = champion
+    f = np.asarray(fitness, np.float64).reshape(-1)
+    b, _ = es_log_order_ref(f)
+    fb = float(f[b])
+    if np.isnan(fb) or not (np.isnan(best) or fb > best):
+        return np.array(params, np.float32), float(best), int(gen), int(member)
+    return np.array(members_row_fn(b), dtype=np.float32).reshape(-1), fb, int(generation) & (2 ** 64 - 1), b
+
+
+def es_log_table_ref(gen, rows):
+    """The ring as ``bsk_es_get_log`` returns it -> ``training_log``'s dict of numpy arrays over the slots that have been written,
+    sorted by generation: ``generation`` uint64, ``ES_LOG_COLUMNS`` (float64; ``count`` and ``best_member`` int64), and derived on
+    the host ``mean`` = sum / count and ``std`` = sqrt(max(sum_sq / count - mean * mean, 0)), NaN where count == 0."""
+    gen = np.asarray(gen, np.uint64).reshape(-1)
+    rows = np.asarray(rows, np.float64).reshape(gen.size, 8)
+    valid = np.flatnonzero(gen != np.uint64(ES_LOG_EMPTY))
+    valid = valid[np.argsort(gen[valid], kind="stable")]
+    out = {"generation": gen[valid].copy()}
+    for c, name in enumerate(ES_LOG_COLUMNS):
+        col = rows[valid, c].copy()
+        out[name] = col.astype(np.int64) if name in ("count", "best_member") else col
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        n = np.where(out["count"] > 0, out["count"], 1).astype(np.float64)
+        mean = out["sum"] / n
+        var = out["sum_sq"] / n - mean * mean
+        std = np.sqrt(np.where(var > 0, var, 0.0))
+    out["mean"] = np.where(out["count"] > 0, mean, np.nan)
+    out["std"] = np.where(out["count"] > 0, std, np.nan)
+    return out
+
+
+def check_log(capacity, population=None, mean_len_size=None):
+    """The argument rules of ``set_log`` that need no device -> the capacity as an int; ValueError where ``bsk_es_set_log`` returns
+    BSK_EINVAL or the bound array does not have one float64 per member."""
+    if isinstance(capacity, bool) or int(capacity) != capacity:
+        raise ValueError("log capacity must be an integer, got %r" % (capacity,))
+    capacity = int(capacity)
+    if capacity < 0 or capacity > 2 ** 31 - 1:
+        raise ValueError("log capacity must be in 0..2^31-1, got %d" % capacity)
+    if mean_len_size is not None and population is not None and int(mean_len_size) != int(population):
+        raise ValueError("mean_len: %d contiguous float64, got %d" % (int(population), int(mean_len_size)))
+    return capacity
+
+
 def shared_slot_ref(n, envs_per_member, epoch, n_pool, env_base=0):
     """The IC-pool slots ``bsk_reset_from_pool_shared`` restarts envs 0 .. n - 1 from -> uint32 (n,): g = (env_base + env) mod 2^32,
     q = g mod envs_per_member, e = epoch mod 2^32, slot = (q * 2654435761 + e * 40503 + 12345) mod 2^32 mod n_pool.  Envs with equal

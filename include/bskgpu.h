@@ -631,7 +631,8 @@ void bsk_es_destroy(bsk_es* es);
  * a different device. */
 int bsk_es_ask(bsk_es* es, bsk_population* pop, void* stream);
 /* Ranks d_fitness (DEVICE memory, f64[n_members]: what bsk_population_rollout's d_fitness holds), moves theta and advances the
- * generation: three launches on `stream`, no copy, no synchronisation; capturable.  BSK_EINVAL for NULL pointers. */
+ * generation: three launches on `stream` (five with a log, bsk_es_set_log), no copy, no synchronisation; capturable.  BSK_EINVAL
+ * for NULL pointers. */
 int bsk_es_tell(bsk_es* es, const double* d_fitness, void* stream);
 /* theta (host pointer, f64[n_params], or NULL) and the generation counter (or NULL).  Ordered after everything queued on the
  * optimiser's device; synchronises it. */
@@ -713,6 +714,65 @@ int bsk_es_set_sigma_adaptation(bsk_es* es, int kind, double lr_sigma, double ma
  * the kind is BSK_ES_SIGMA_FIXED; set also for any entry that is not finite and positive (nothing is written then). */
 int bsk_es_get_sigma(bsk_es* es, double* sigma);
 int bsk_es_set_sigma(bsk_es* es, const double* sigma);
+
+/* A training log and the best member so far, kept on the device: what a replayed graph of reset, ask, rollout and tell leaves for
+ * the user besides theta - how every generation scored, and the candidate that scored best.  Both are small reductions over what
+ * lies in device memory when tell runs: the P fitness values, and theta, sigma and the generation word, from which ask's members
+ * are regenerated exactly.  Off by default: an optimiser that never calls bsk_es_set_log launches the kernels of the definitions
+ * above with the arguments it passed before.  f64 + and * only, every operation rounded on its own, no FMA, no atomics
+ * (basilisk_env_amd/policy_ref.py: es_log_row_ref and es_best_ref repeat it bit for bit).
+ * State of a log of capacity C >= 1, all in device memory:
+ *     log_gen uint64[C], all ones after enabling;   log_row f64[C][8], zeros after enabling;
+ *     the champion: best_params f32[n_params] in the C-ABI parameter layout (zeros), best_fitness f64 (the NaN 0x7FF8000000000000),
+ *                   best_generation uint64 (all ones), best_member int32 (-1);
+ *     two candidate words {take, b} that the two kernels below use between them.
+ * With a log on, bsk_es_tell issues two more launches IN FRONT of the update, so that theta, sigma_vec and the
+ * generation word are still the ones ask used: five launches, still no copy, no synchronisation, capturable.
+ * The first launch is one wave.  g = the generation word as read, slot = g mod C (of the whole 64-bit word), f = the P values:
+ *   order: the rule of step 1 above - the greater value wins, a NaN is below every number, ties (and NaNs) go to the lower index; with
+ *     the index it is a strict total order, so -0.0 against +0.0 is decided by the index and no result depends on the order in
+ *     which the lanes join.  b = the member that nobody beats;  wst = among the members that are not NaN the one that beats no
+ *     other of them, -1 when every member is NaN.
+ *   sums, each in the library's one order: x_k = f_k, or +0.0 where f_k is NaN;
+ *        s[l] = x_l, or +0.0 when l >= P                                              (l = 0 .. 63)
+ *        s[l] = s[l] + x_(l+64m) for m = 1, 2, ... ascending while l + 64m < P
+ *        for stride = 32, 16, 8, 4, 2, 1:  s[l] = s[l] + s[l + stride] for l < stride
+ *     S1 = s[0] over x_k;  S2 the same over x_k * x_k;  cnt = the number of members that are not NaN (an integer);
+ *     L1 the same over mean_len[k] when d_mean_len is bound, +0.0 otherwise.  (+inf and -inf among the values make S1 a NaN: which
+ *     NaN is not defined.)
+ *   row:  log_row[slot] = {f[b], wst >= 0 ? f[wst] : the NaN 0x7FF8000000000000, S1, S2, (double)cnt, (double)b, L1,
+ *                          bound ? mean_len[b] : 0.0};   log_gen[slot] = g.
+ *     Means and variances are the reader's division: the device stores sums.
+ *   champion:  take = f[b] is not NaN and (best_fitness is NaN or f[b] > best_fitness) - a tie keeps the older champion, a
+ *     generation of NaNs never takes;  when take: best_fitness = f[b], best_generation = g, best_member = b;  always: the
+ *     candidate words = {take, b}.
+ * The second launch has one thread per parameter j and does nothing unless take; otherwise best_params[j] is exactly the float ask
+ * writes for member b of generation g: (float)theta_j for j < frozen, else (float)(theta_j + s_j * z(g, b >> 1, j)) for an even
+ * b and (float)(theta_j - s_j * z(g, b >> 1, j)) for an odd one, s_j = sigma, or sigma_vec[j] under BSK_ES_SIGMA_PGPE; product and
+ * sum each round in f64 (one text behind this kernel and ask).  The kernel boundary orders the two launches: no atomics, no fence,
+ * as the policy's draw counter is ordered.
+ * The champion is "what ask would write now": it is the member that was evaluated as long as the caller moves neither theta nor
+ * sigma between ask and tell.  A loop of reset, ask, rollout, tell and bsk_es_apply_obs_norm does not: the normalisation is written
+ * BEHIND tell.
+ * bsk_es_set_log: capacity > 0 allocates (or frees and allocates again) and sets everything above to its initial value;
+ * d_mean_len is DEVICE memory, f64[n_members], or NULL - what bsk_population_rollout's d_mean_len writes; it stays bound and is
+ * the caller's to keep alive.  capacity == 0 turns the log off and frees it.  Synchronises the device.  Theta, the generation,
+ * Adam's state and sigma_vec are left alone; bsk_es_set_state, bsk_es_set_optimizer and bsk_es_set_sigma_adaptation leave the log
+ * and the champion alone.  BSK_EINVAL: a NULL optimiser, a negative capacity, and while the stream of the optimiser's last ask /
+ * tell / bsk_es_apply_obs_norm is being captured (nothing is changed then, and the capture stays valid). */
+int bsk_es_set_log(bsk_es* es, int capacity, const double* d_mean_len);
+/* The whole ring to host memory: gen uint64[C], rows f64[C][8] (either may be NULL); a slot whose log_gen is all ones has never
+ * been written.  Synchronises the device.  BSK_EINVAL for a NULL optimiser and with no log. */
+int bsk_es_get_log(bsk_es* es, uint64_t* gen, double* rows);
+/* The champion to / from host memory: params f32[n_params], fitness, generation, member; each may be NULL (get: not asked for;
+ * set: keep).  For a checkpoint that resumes bit for bit, like bsk_es_get_moments.  Synchronise the device.  BSK_EINVAL for a NULL
+ * optimiser and with no log. */
+int bsk_es_get_best(bsk_es* es, float* params, double* fitness, uint64_t* generation, int32_t* member);
+int bsk_es_set_best(bsk_es* es, const float* params, const double* fitness, const uint64_t* generation, const int32_t* member);
+/* best_params as a DEVICE pointer (read-only for the caller; valid until the next bsk_es_set_log or bsk_es_destroy): what
+ * bsk_population_set_params_device takes, so the champion is loaded into a policy's member with no host in between.  No launch, no
+ * copy, no synchronisation.  BSK_EINVAL for NULL pointers and with no log. */
+int bsk_es_best_device(bsk_es* es, const float** d_params);
 
 /* Running statistics of the five observation rows, formed on the device: what gives a policy its in_scale / in_shift.  Salimans et
  * al. 2017 and ARS V2 (Mania et al. 2018) normalise the observations by the mean and standard deviation of everything the search

@@ -1,0 +1,426 @@
+"""GPU: the training log and the champion of the device evolution strategy (bsk_es_set_log / _get_log / _get_best / _set_best /
+_best_device; es_log_kernel and es_best_kernel in csrc/bsk_es.hip; contract in include/bskgpu.h).
+
+Every check is an EQUALITY of bits against the numpy restatements (policy.es_log_row_ref / es_best_ref with the members of
+es_ask_ref / es_ask_sigma_ref, which tests/test_es_log_host.py holds to an operation-by-operation restatement) or against an
+optimiser with no log - no tolerance anywhere.  One exception the definition makes itself: which NaN a SUM becomes when +inf and
+-inf are both among its terms is not defined, so the three sum columns compare as "the same bits, or a NaN in both".
+Shapes as in tests/test_gpu_es.py: P = 2 is one pair with 63 empty lanes of the one-wave reduction, P = 130 gives two lanes
+three terms and the others two, P = 256 gives every lane four; generation 2^32 + 3 and seed 2^33 + 5 catch a dropped high word
+(2^32 + 3 and 3 fall into different slots of every capacity used here).
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+from _policy_bounds import seeded_policy
+from basilisk_env_amd import _hip, _lib
+from basilisk_env_amd import policy as P
+from basilisk_env_amd._lib import FLAG_AUTO_RESET, GRAV_PM_J2
+from basilisk_env_amd.simulators.dynamics import BatchedPropagator, default_config
+from basilisk_env_amd.simulators.initial_conditions.batch import sample_ic_batch
+
+pytestmark = pytest.mark.gpu
+
+SEED, LATE = 2 ** 33 + 5, 2 ** 32 + 3
+SPECS = {"relu16": ((16,), "relu", None), "tanh16x32v16": ((16, 32), "tanh", (16,))}
+BETA1, BETA2, EPS, WD = 0.9, 0.999, 1e-8, 1e-2
+PGPE = dict(sigma_adapt="pgpe", lr_sigma=4.0, sigma_max_change=0.2, sigma_min=0.05, sigma_max=0.2)
+ADAM = dict(optimizer="adam", beta1=BETA1, beta2=BETA2, eps=EPS, weight_decay=WD)
+NAN = float("nan")
+SUMS = (2, 3, 6)
+N_POOL = 41
+
+
+def _download(ptr, dtype, count):
+    out = np.empty(count, dtype=dtype)
+    _hip.check(_hip.runtime().hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), out.nbytes, _hip.hipMemcpyDeviceToHost), "hipMemcpy")
+    return out
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
+
+
+def _same(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
+
+
+def _same_rows(got, want):
+    """(..., 8) rows: bit for bit, the sum columns also where both are NaN"""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    if got.shape != want.shape or got.shape[-1] != 8:
+        return False
+    ok = _bits(got) == _bits(want)
+    for c in SUMS:
+        ok[..., c] |= np.isnan(got[..., c]) & np.isnan(want[..., c])
+    return bool(ok.all())
+
+
+def _same_champion(got, want):
+    return (_same(got[0], want[0]) and _same(np.float64(got[1]), np.float64(want[1])) and int(got[2]) == int(want[2])
+            and int(got[3]) == int(want[3]))
+
+
+def _raw_log(es, capacity):
+    gen, rows = np.empty(capacity, np.uint64), np.empty((capacity, 8), np.float64)
+    _lib.check(es._lib.bsk_es_get_log(es._handle(), gen.ctypes.data, rows.ctypes.data))
+    return gen, rows
+
+
+def _fitness_cases(n_members, rng):
+    """the kind tests/test_gpu_es.py builds - a tie, NaN pairs, +-inf - plus an all-NaN and a +-0.0 vector"""
+    if n_members == 2:
+        cases = [[1.0, 1.0], [NAN, NAN], [-np.inf, np.inf], [0.25, -3.0], [NAN, 0.0], [-0.0, 0.0], [0.0, -0.0]]
+        return [np.array(f) for f in cases]
+    f = rng.normal(size=n_members)
+    f[7] = f[3]                                # a tie
+    f[10] = f[11] = np.nan                     # a NaN pair
+    f[20], f[21], f[40], f[41 + 64] = np.inf, -np.inf, np.inf, np.nan
+    g = rng.normal(size=n_members)
+    g[5] = g[77] = g.max() + 1.0               # the best twice: the lower index; the worst twice: the higher one
+    g[9] = g[100] = g.min() - 1.0
+    zeros = np.zeros(n_members)
+    zeros[1::2] = -0.0
+    return [f, g, np.full(n_members, np.nan), zeros, -zeros, rng.normal(size=n_members)]
+
+
+def _make(spec, theta0, n_members, frozen, rule, seed=SEED, **kw):
+    args = dict(ADAM, **PGPE) if rule == "adam-pgpe" else {}
+    args.update(kw)
+    return P.DeviceEvolutionStrategy(spec, theta0, n_members, sigma=0.1, lr=0.05, seed=seed, frozen=frozen, **args)
+
+
+def _members_fn(es_state, frozen, n_members, seed, generation):
+    """member b as ask writes it from (theta, sigma_vec or None) as they are BEFORE the tell"""
+    theta, sv = es_state
+    if sv is None:
+        return lambda b: P.es_ask_ref(theta, 0.1, frozen, n_members, seed, generation)[b]
+    return lambda b: P.es_ask_sigma_ref(theta, sv, frozen, n_members, seed, generation)[b]
+
+
+def _before(es, rule):
+    return es.theta, (es.sigma_vector if rule == "adam-pgpe" else None)
+
+
+@pytest.mark.parametrize("bound", ["null", "own", "array"])
+@pytest.mark.parametrize("n_members", [2, 130, 256])
+def test_every_tell_writes_the_row_of_the_definition_and_changes_nothing_else(n_members, bound):
+    import torch
+    spec, theta0 = seeded_policy((16,), "relu", None, seed=9)
+    frozen, C, rule = 10, 4, "adam-pgpe"
+    es, plain = _make(spec, theta0, n_members, frozen, rule), _make(spec, theta0, n_members, frozen, rule)
+    rng = np.random.default_rng(n_members)
+    ml = d_ml = None
+    if bound == "null":
+        assert es._lib.bsk_es_set_log(es._handle(), C, None) == 0          # (the binding's None binds a zeroed buffer of its own)
+    elif bound == "own":
+        es.set_log(C)
+    else:
+        ml = rng.integers(1, 7, size=n_members) + rng.integers(0, 64, size=n_members) / 64.0
+        d_ml = torch.from_numpy(ml).cuda()
+        torch.cuda.synchronize()
+        es.set_log(C, d_ml)
+    gen, rows = _raw_log(es, C)
+    assert (gen == np.uint64(P.ES_LOG_EMPTY)).all() and _same(rows, np.zeros((C, 8)))
+    want_gen, want_rows = gen.copy(), rows.copy()
+    champion = P.es_champion_empty(theta0.size)
+    assert _same_champion(es.best, champion)
+    generation, takes = 0, 0
+    for round_, f in enumerate(_fitness_cases(n_members, rng)):
+        if round_ == 1:
+            generation = LATE
+            for opt in (es, plain):
+                opt.set_state(None, generation)
+            assert _same_champion(es.best, champion) and _same_rows(_raw_log(es, C)[1], want_rows)      # set_state leaves both alone
+        state = _before(es, rule)
+        d_f = torch.from_numpy(f).cuda()
+        torch.cuda.synchronize()
+        c0 = BatchedPropagator.debug_counters()
+        es.tell(d_f)
+        plain.tell(d_f)
+        assert BatchedPropagator.debug_counters() == c0            # five launches: no copy, no synchronisation
+        slot = P.es_log_slot_ref(generation, C)
+        want_gen[slot], want_rows[slot] = generation, P.es_log_row_ref(f, ml)
+        gen, rows = _raw_log(es, C)
+        assert np.array_equal(gen, want_gen) and _same_rows(rows, want_rows), (round_, rows[slot], want_rows[slot])
+        new = P.es_best_ref(champion, f, generation, _members_fn(state, frozen, n_members, SEED, generation))
+        takes += new[2] != champion[2]
+        champion = new
+        assert _same_champion(es.best, champion), round_
+        # the log changes nothing: theta, the step sizes and Adam's moments are those of the optimiser without one
+        for got, want, name in zip((es.theta, es.sigma_vector) + es.moments, (plain.theta, plain.sigma_vector) + plain.moments,
+                                   ("theta", "sigma", "m", "v", "beta_pow")):
+            assert _same(got, want), (round_, name)
+        generation += 1
+        assert es.generation == plain.generation == generation
+    assert takes >= 1 and not np.isnan(champion[1])
+    for x in (es, plain):
+        x.close()
+
+
+@pytest.mark.parametrize("rule", ["sgd-fixed", "adam-pgpe"])
+@pytest.mark.parametrize("which,frozen", [("relu16", 10), ("relu16", 0), ("tanh16x32v16", 10), ("tanh16x32v16", 0)])
+def test_the_champion_is_the_member_ask_wrote_before_the_update(which, frozen, rule):
+    import torch
+    hidden, activation, value_hidden = SPECS[which]
+    spec, theta0 = seeded_policy(hidden, activation, value_hidden, seed=7)
+    n_members = 130
+    es = _make(spec, theta0, n_members, frozen, rule, log_capacity=8)
+    if rule == "adam-pgpe":
+        es.set_sigma(np.random.default_rng(77).uniform(0.06, 0.18, size=theta0.size))
+    es.set_state(None, LATE)
+    base = np.random.default_rng(3).uniform(-1.0, 1.0, size=n_members)
+    # take (an even member); lower: keep; an exact tie: keep; higher on an odd member - the second term of lane 13: take
+    script = [(6, 2.0, True), (40, 1.5, False), (12, 2.0, False), (77, 3.0, True)]
+    champion = P.es_champion_empty(theta0.size)
+    for round_, (b, top, takes) in enumerate(script):
+        generation = LATE + round_
+        f = base.copy()
+        f[b] = top
+        state = _before(es, rule)
+        d_f = torch.from_numpy(f).cuda()
+        torch.cuda.synchronize()
+        es.tell(d_f)
+        member = _members_fn(state, frozen, n_members, SEED, generation)
+        new = P.es_best_ref(champion, f, generation, member)
+        assert (new[2] == generation) == takes and (not takes or new[3] == b)
+        champion = new
+        got = es.best
+        assert _same_champion(got, champion), (round_, got[1:], champion[1:])
+        if takes:
+            # ... and not the plus member of the pair, nor the member of the theta the update left, nor of the low word alone
+            after = _members_fn(_before(es, rule), frozen, n_members, SEED, generation)(b)
+            low = _members_fn(state, frozen, n_members, SEED, generation & 0xFFFFFFFF)(b)
+            assert not _same(got[0], member(b ^ 1)) and not _same(got[0], after) and not _same(got[0], low)
+            assert _same(got[0][:frozen], state[0][:frozen].astype(np.float32))
+    assert champion[1:] == (3.0, LATE + 3, 77)
+    log = es.training_log()
+    assert log["generation"].tolist() == [LATE + r for r in range(4)] and log["best_member"].tolist() == [6, 40, 12, 77]
+    assert log["best"].tolist() == [2.0, 1.5, 2.0, 3.0] and (log["count"] == n_members).all()
+    es.close()
+
+
+def test_the_ring_holds_the_last_generations_in_their_slots():
+    import torch
+    spec, theta0 = seeded_policy((16,), "relu", None, seed=9)
+    n_members, C = 4, 3
+    es = _make(spec, theta0, n_members, 10, "sgd-fixed", log_capacity=C)
+    es.set_state(None, LATE)
+    rng = np.random.default_rng(1)
+    fs = [rng.normal(size=n_members) for _ in range(5)]
+    fs[3][2] = np.nan
+    for round_, f in enumerate(fs):
+        es.tell(torch.from_numpy(f).cuda())
+        held = list(range(max(0, round_ + 1 - C), round_ + 1))
+        gen, rows = _raw_log(es, C)
+        for r in held:
+            slot = (LATE + r) % C
+            assert gen[slot] == LATE + r and _same_rows(rows[slot], P.es_log_row_ref(fs[r])), (round_, r)
+        assert (gen != np.uint64(P.ES_LOG_EMPTY)).sum() == len(held)
+        log = es.training_log()
+        assert log["generation"].tolist() == [LATE + r for r in held]
+        want = np.stack([P.es_log_row_ref(fs[r]) for r in held])
+        assert _same_rows(np.stack([log[c].astype(np.float64) for c in P.ES_LOG_COLUMNS], axis=1), want)
+    assert (LATE % C, 3 % C) == (1, 0) and log["count"].tolist() == [4, 3, 4]
+    with np.errstate(invalid="ignore"):
+        assert _same(log["mean"], log["sum"] / log["count"])
+    es.close()
+
+
+def _propagator(n, ic, pool, stream=None):
+    cfg = default_config(4, GRAV_PM_J2)
+    cfg.flags |= FLAG_AUTO_RESET
+    cfg.max_length = 6
+    p = BatchedPropagator(cfg, n, stream=stream)
+    p.set_ic_pool(pool)
+    p.reset(ic)
+    p.step(np.zeros(n, np.int32), 1)
+    return p
+
+
+def test_a_replayed_graph_keeps_the_log_and_the_champion_of_the_eager_loop():
+    import torch
+    n_members, E, T, k, gamma, C = 4, 64, 3, 1, 0.99, 8
+    n = n_members * E
+    spec, theta0 = seeded_policy((16,), "tanh", None, seed=5)
+    ic, pool = sample_ic_batch(n, 4, seed=29), sample_ic_batch(N_POOL, 4, seed=15)
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        def make():
+            prop = _propagator(n, ic, pool, side.cuda_stream)
+            pop = P.PolicyPopulation(spec, n_members=n_members)
+            return prop, pop, _make(spec, theta0, n_members, 10, "adam-pgpe", seed=3, log_capacity=C)
+
+        # eagerly, four generations; each row against the fitness and the mean lengths the rollout left in device memory
+        prop, pop, es = make()
+        champion = P.es_champion_empty(theta0.size)
+        for g in range(4):
+            state = _before(es, "adam-pgpe")
+            c0 = BatchedPropagator.debug_counters()
+            es.run_generation(prop, pop, T, k, "greedy", gamma, shared_episodes=True)
+            if g:
+                assert BatchedPropagator.debug_counters() == c0      # no copy, no synchronisation
+            prop.sync()
+            fitness = _download(es.fitness_buffer().ptr, np.float64, n_members)
+            mean_len = _download(es._out["mean_len"].ptr, np.float64, n_members)
+            assert np.isfinite(fitness).all() and (mean_len >= 1.0).all() and (mean_len <= T).all()
+            gen, rows = _raw_log(es, C)
+            assert gen[g] == g and _same_rows(rows[g], P.es_log_row_ref(fitness, mean_len)), g
+            assert rows[g][6] == mean_len.sum() and rows[g][7] == mean_len[int(rows[g][5])]
+            champion = P.es_best_ref(champion, fitness, g, _members_fn(state, 10, n_members, 3, g))
+            assert _same_champion(es.best, champion), g
+        want_log, want_best, want_theta = es.training_log(), es.best, es.theta
+        assert want_log["generation"].tolist() == [0, 1, 2, 3] and want_best[2] < 4
+        for x in (prop, pop, es):
+            x.close()
+
+        # captured once behind a warming call, replayed three times
+        prop, pop, es = make()
+        es.run_generation(prop, pop, T, k, "greedy", gamma, shared_episodes=True)
+        prop.sync()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            es.run_generation(prop, pop, T, k, "greedy", gamma, shared_episodes=True)
+        c0 = BatchedPropagator.debug_counters()
+        for _ in range(3):
+            graph.replay()
+        torch.cuda.synchronize()
+        assert BatchedPropagator.debug_counters() == c0
+        got_log = es.training_log()
+        assert sorted(got_log) == sorted(want_log)
+        for key in want_log:
+            assert _same(got_log[key], want_log[key]), key
+        assert _same_champion(es.best, want_best) and _same(es.theta, want_theta) and es.generation == 4
+        for x in (prop, pop, es):
+            x.close()
+
+
+def test_the_champion_is_handed_to_a_population_without_the_host():
+    import torch
+    hidden, activation, value_hidden = SPECS["tanh16x32v16"]
+    spec, theta0 = seeded_policy(hidden, activation, value_hidden, seed=7)
+    n_members = 4
+    es = _make(spec, theta0, n_members, 10, "sgd-fixed", log_capacity=2)
+    es.tell(torch.tensor([0.0, 3.0, 1.0, -1.0], dtype=torch.float64, device="cuda"))
+    best = es.best
+    assert best[1:] == (3.0, 0, 1) and _same(best[0], P.es_ask_ref(theta0, 0.1, 10, n_members, SEED, 0)[1])
+    sentinel = np.full((3, theta0.size), 3.0, np.float32)
+    pop = P.PolicyPopulation(spec, sentinel)
+    c0 = BatchedPropagator.debug_counters()
+    pop.set_params_device(es.best_params_ptr(), 1, 1)
+    assert BatchedPropagator.debug_counters() == c0
+    assert _same(pop.member(1), best[0]) and (pop.member(0) == 3.0).all() and (pop.member(2) == 3.0).all()
+    one = P.PolicyPopulation(spec, n_members=1)
+    one.set_params_device(es.best_params_ptr(), 0, 1)
+    assert _same(one.member(0), best[0])
+    for x in (es, pop, one):
+        x.close()
+
+
+def test_a_checkpoint_resumes_with_the_same_rows_and_champion():
+    import torch
+    spec, theta0 = seeded_policy((16,), "relu", None, seed=9)
+    n_members, C = 130, 4
+    rng = np.random.default_rng(8)
+    fs = [rng.normal(size=n_members) for _ in range(4)]
+    fs[2] = fs[2] * 0.1                              # a generation that does not take ...
+    fs[3][51] = 9.0                                  # ... and one that does, on an odd member
+    es = _make(spec, theta0, n_members, 10, "adam-pgpe", log_capacity=C)
+    es.set_state(None, LATE)
+    for f in fs[:2]:
+        es.tell(torch.from_numpy(f).cuda())
+    best = es.best
+    saved = dict(theta=es.theta, generation=es.generation, moments=es.moments, sigma=es.sigma_vector, best=best, log=_raw_log(es, C))
+    assert not np.isnan(best[1]) and saved["generation"] == LATE + 2
+    # round trips: the champion through set_best, whole and one word at a time
+    es.set_best(np.zeros(theta0.size, np.float32), -1.0, 7, 3)
+    assert _same_champion(es.best, (np.zeros(theta0.size, np.float32), -1.0, 7, 3))
+    es.set_best(fitness=NAN)
+    assert np.isnan(es.best[1]) and es.best[2:] == (7, 3)
+    es.set_best(*best)
+    assert _same_champion(es.best, best)
+    gen, rows = _raw_log(es, C)
+    assert np.array_equal(gen, saved["log"][0]) and _same_rows(rows, saved["log"][1])          # (set_best leaves the ring alone)
+
+    resumed = _make(spec, theta0, n_members, 10, "adam-pgpe", log_capacity=C)
+    resumed.set_state(saved["theta"], saved["generation"])
+    resumed.set_moments(*saved["moments"])
+    resumed.set_sigma(saved["sigma"])
+    resumed.set_best(*saved["best"])
+    for f in fs[2:]:
+        for opt in (es, resumed):
+            opt.tell(torch.from_numpy(f).cuda())
+    assert _same_champion(resumed.best, es.best) and es.best[1:] == (9.0, LATE + 3, 51) and _same(resumed.theta, es.theta)
+    a, b = es.training_log(), resumed.training_log()
+    assert a["generation"].tolist() == [LATE + r for r in range(4)] and b["generation"].tolist() == [LATE + 2, LATE + 3]
+    for key in a:
+        assert _same(a[key][2:], b[key]), key
+    for x in (es, resumed):
+        x.close()
+
+
+def test_without_a_log_nothing_of_it_exists_and_a_capture_refuses_to_make_one():
+    import torch
+    lib = _lib.load()
+    spec, theta0 = seeded_policy((16,), "relu", None, seed=21)
+    n_members = 4
+    es, plain = _make(spec, theta0, n_members, 10, "sgd-fixed"), _make(spec, theta0, n_members, 10, "sgd-fixed")
+    ptr = ctypes.c_void_p()
+
+    def is_off():
+        for call in (es.training_log, lambda: es.best, es.best_params_ptr, lambda: es.set_best(fitness=1.0)):
+            with pytest.raises(_lib.BskError) as e:
+                call()
+            assert e.value.code == -1 and "no log" in str(e.value)
+        assert lib.bsk_es_best_device(es._handle(), ctypes.byref(ptr)) == -1 and lib.bsk_es_get_log(es._handle(), None, None) == -1
+
+    is_off()
+    assert lib.bsk_es_set_log(None, 4, None) == -1 and lib.bsk_es_set_log(es._handle(), -1, None) == -1
+    assert lib.bsk_es_best_device(None, ctypes.byref(ptr)) == -1 and lib.bsk_es_get_best(None, None, None, None, None) == -1
+    with pytest.raises(ValueError):
+        es.set_log(-1)
+    with pytest.raises(ValueError):
+        es.set_log(4, torch.zeros(n_members + 1, dtype=torch.float64, device="cuda"))
+    with pytest.raises(ValueError):
+        es.set_log(4, torch.zeros(n_members, dtype=torch.float32, device="cuda"))
+    is_off()
+
+    side = torch.cuda.Stream()
+    fs = [np.array(f) for f in ([0.0, 1.0, 2.0, 3.0], [5.0, 1.0, NAN, 3.0], [0.5, 0.25, 4.0, 1.0])]
+    with torch.cuda.stream(side):
+        d_fs = [torch.from_numpy(f).cuda() for f in fs]
+        torch.cuda.synchronize()
+        es.set_log(4)
+        for opt in (es, plain):
+            opt.tell(d_fs[0], side.cuda_stream)
+        torch.cuda.synchronize()
+        log = es.training_log()
+        assert log["generation"].tolist() == [0] and es.best[1:] == (3.0, 0, 3)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            for capacity in (8, 0):
+                with pytest.raises(_lib.BskError) as e:
+                    es.set_log(capacity)
+                assert e.value.code == -1 and "captured" in str(e.value)
+        # the refusal changed nothing: the log goes on where it was
+        assert es.log_capacity == 4
+        for opt in (es, plain):
+            opt.tell(d_fs[1], side.cuda_stream)
+        torch.cuda.synchronize()
+        assert es.training_log()["generation"].tolist() == [0, 1] and es.best[1:] == (5.0, 1, 0)
+        # off again: the entry points refuse as before, and tell is the three launches of the optimiser that never had a log
+        es.set_log(0)
+        is_off()
+        for opt in (es, plain):
+            opt.tell(d_fs[2], side.cuda_stream)
+        torch.cuda.synchronize()
+        assert _same(es.theta, plain.theta) and es.generation == plain.generation == 3
+        # on again: empty, whatever was there before
+        es.set_log(2)
+        assert es.training_log()["generation"].size == 0 and _same_champion(es.best, P.es_champion_empty(theta0.size))
+    for x in (es, plain):
+        x.close()

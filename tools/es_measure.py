@@ -14,16 +14,19 @@
         obsnorm `run_generation(..., obs_stats=...)`: one obs_stats_kernel launch in front of every policy launch, the join and
                 the normalisation behind the generation
         sigma   `run_generation` of an optimiser created with sigma_adapt="pgpe": a step size per parameter, moved by tell
-  python tools/es_measure.py kernel [adam | obs | sigma]
+        log     `run_generation` of an optimiser created with log_capacity=256: two more launches in front of the update, and the
+                rollout also writes the members' mean episode lengths
+  python tools/es_measure.py kernel [adam | obs | sigma | log]
       per P one warming and three measured generations of `run_generation` (`adam`: of an optimizer="adam" optimiser on shared
-      episodes; `obs`: with an `ObsStats` given; `sigma`: of a sigma_adapt="pgpe" optimiser).  Run it under the profiler in a run
-      of its own:
+      episodes; `obs`: with an `ObsStats` given; `sigma`: of a sigma_adapt="pgpe" optimiser; `log`: of a log_capacity=256
+      optimiser).  Run it under the profiler in a run of its own:
       rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o es -- python tools/es_measure.py kernel
   python tools/es_measure.py stats DIR/.../es_kernel_trace.csv
       per measured generation of that run the times of es_ask_kernel, es_rank_kernel and es_tell_kernel (or es_tell_adam_kernel;
       of a `kernel sigma` run es_ask_sigma_kernel, es_rank_q_kernel and es_tell_sigma_kernel)
       and the sum over every other kernel of the generation (the generations are recognised by the es_advance_kernel or
-      es_advance_adam_kernel that ends each); of a `kernel obs` run also obs_stats_kernel, per generation and per launch
+      es_advance_adam_kernel that ends each); of a `kernel obs` run also obs_stats_kernel, per generation and per launch; of a
+      `kernel log` run also es_log_kernel and es_best_kernel
 """
 import csv
 import os
@@ -67,6 +70,7 @@ def loop():
             shared = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
             normed = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1)
             sig = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1, sigma_adapt="pgpe")
+            logged = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1, log_capacity=256)
             obs_stats = P.ObsStats(N)
             fit = torch.zeros(m, dtype=torch.float64, device="cuda")
 
@@ -94,6 +98,9 @@ def loop():
             def sigma_gen(steps, pop=pop, sig=sig):
                 sig.run_generation(prop, pop, steps, 1, "greedy", GAMMA)
 
+            def log_gen(steps, pop=pop, logged=logged):
+                logged.run_generation(prop, pop, steps, 1, "greedy", GAMMA)
+
             rep.run_generation(prop, pop, WARM_T, 1, "greedy", GAMMA)
             prop.sync()
             graph = torch.cuda.CUDAGraph()
@@ -106,7 +113,7 @@ def loop():
 
             variants += [("host   P = %d" % m, host_gen), ("device P = %d" % m, device_gen), ("graph  P = %d" % m, graph_gen),
                          ("rollout P = %d" % m, rollout_gen), ("adam   P = %d" % m, adam_gen), ("shared P = %d" % m, shared_gen),
-                         ("obsnorm P = %d" % m, obsnorm_gen), ("sigma  P = %d" % m, sigma_gen)]
+                         ("obsnorm P = %d" % m, obsnorm_gen), ("sigma  P = %d" % m, sigma_gen), ("log    P = %d" % m, log_gen)]
         res = {name: [] for name, _ in variants}
         for _ in range(ROUNDS):
             for name, run in variants:
@@ -121,13 +128,13 @@ def loop():
     env.close()
 
 
-def kernel(adam=False, obs=False, sigma=False):
+def kernel(adam=False, obs=False, sigma=False, log=False):
     torch, P, side, env, prop, spec, theta = _setup()
     with torch.cuda.stream(side):
         for m in MEMBERS:
             pop = P.PolicyPopulation(spec, n_members=m)
             dev = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1, optimizer="adam" if adam else "sgd",
-                                            sigma_adapt="pgpe" if sigma else None)
+                                            sigma_adapt="pgpe" if sigma else None, log_capacity=256 if log else 0)
             obs_stats = P.ObsStats(N) if obs else None
             dev.run_generation(prop, pop, WARM_T, 1, "greedy", GAMMA, shared_episodes=adam, obs_stats=obs_stats)
             for _ in range(ROUNDS):
@@ -145,7 +152,8 @@ def stats(path):
     rows.sort()
     gens, cur, seen = [], {}, False
     for _, d, name in rows:
-        key = next((k for k in ("es_ask_kernel", "es_rank_kernel", "es_tell_kernel", "es_advance_kernel", "obs_stats_kernel")
+        key = next((k for k in ("es_ask_kernel", "es_rank_kernel", "es_tell_kernel", "es_advance_kernel", "obs_stats_kernel", "es_log_kernel",
+                                "es_best_kernel")
                     if k in name.replace("_adam", "").replace("_sigma", "").replace("es_rank_q", "es_rank")), "rest")
         seen = seen or key == "es_ask_kernel"
         if not seen:
@@ -164,6 +172,8 @@ def stats(path):
             if "obs_stats_kernel" in g:        # (a `kernel obs` run: T launches per generation, one in front of every policy launch)
                 print("          obs_stats_kernel %8.1f us per generation, %.2f us per launch" %
                       (g["obs_stats_kernel"] / 1e3, g["obs_stats_kernel"] / 1e3 / T))
+            if "es_log_kernel" in g:           # (a `kernel log` run: one launch of each per generation, in front of the update)
+                print("          es_log_kernel %6.1f us, es_best_kernel %6.1f us" % (g["es_log_kernel"] / 1e3, g["es_best_kernel"] / 1e3))
 
 
 if __name__ == "__main__":
@@ -172,7 +182,8 @@ if __name__ == "__main__":
     if what == "loop":
         loop()
     elif what == "kernel":
-        kernel(adam=sys.argv[2:3] == ["adam"], obs=sys.argv[2:3] == ["obs"], sigma=sys.argv[2:3] == ["sigma"])
+        kernel(adam=sys.argv[2:3] == ["adam"], obs=sys.argv[2:3] == ["obs"], sigma=sys.argv[2:3] == ["sigma"],
+               log=sys.argv[2:3] == ["log"])
     elif what == "stats":
         stats(sys.argv[2])
     else:
