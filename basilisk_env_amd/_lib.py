@@ -91,6 +91,8 @@ EXPORTS = [
     "bsk_es_generation_device", "bsk_es_set_optimizer", "bsk_es_get_moments", "bsk_es_set_moments",
     "bsk_es_set_sigma_adaptation", "bsk_es_get_sigma", "bsk_es_set_sigma",
     "bsk_es_set_log", "bsk_es_get_log", "bsk_es_get_best", "bsk_es_set_best", "bsk_es_best_device",
+    "bsk_es_set_validation", "bsk_es_get_validation_log", "bsk_es_get_validated_best", "bsk_es_set_validated_best",
+    "bsk_es_validated_best_device", "bsk_es_validation_epochs_device", "bsk_population_set_obs_stats_members",
     "bsk_obs_stats_create", "bsk_obs_stats_destroy", "bsk_obs_stats_accumulate", "bsk_obs_stats_get", "bsk_obs_stats_totals_device",
     "bsk_obs_stats_get_state", "bsk_obs_stats_set_state", "bsk_obs_stats_reset", "bsk_population_set_obs_stats",
     "bsk_policy_set_obs_stats", "bsk_es_apply_obs_norm",
@@ -144,6 +146,10 @@ def _signatures():
         "bsk_es_set_sigma": ([vp, vp], rc),
         "bsk_es_set_log": ([vp, i, vp], rc), "bsk_es_get_log": ([vp, vp, vp], rc), "bsk_es_get_best": ([vp, vp, vp, vp, vp], rc),
         "bsk_es_set_best": ([vp, vp, vp, vp, vp], rc), "bsk_es_best_device": ([vp, P(vp)], rc),
+        "bsk_es_set_validation": ([vp, i, i, u64, vp], rc), "bsk_es_get_validation_log": ([vp, vp, vp], rc),
+        "bsk_es_get_validated_best": ([vp, vp, vp, vp], rc), "bsk_es_set_validated_best": ([vp, vp, vp, vp], rc),
+        "bsk_es_validated_best_device": ([vp, P(vp)], rc), "bsk_es_validation_epochs_device": ([vp, P(vp)], rc),
+        "bsk_population_set_obs_stats_members": ([vp, i], rc),
         "bsk_obs_stats_create": ([i, i, P(vp)], rc), "bsk_obs_stats_destroy": ([vp], None),
         "bsk_obs_stats_accumulate": ([vp, vp, i64, i, vp, vp], rc), "bsk_obs_stats_get": ([vp, P(u64), vp, vp], rc),
         "bsk_obs_stats_totals_device": ([vp, P(vp), P(vp)], rc), "bsk_obs_stats_get_state": ([vp, vp, vp], rc),

@@ -34,6 +34,7 @@ struct ParamStore {
     float* d_params = nullptr;             // [n_members][lay.n_device]: one device layout of the parameters (bsk_policy.hpp) per member
     unsigned long long* d_rng = nullptr;   // {seed, draw}: read by sample-mode launches, draw advanced behind each of them
     bsk_obs_stats* stats = nullptr;        // bsk_*_set_obs_stats: what the rollouts accumulate into; not owned
+    int n_counted = 0;                     // bsk_population_set_obs_stats_members: the envs of the first n_counted members feed `stats`; 0: all
 };
 
 }  // namespace
@@ -80,6 +81,11 @@ struct bsk_es {
     unsigned long long* d_log = nullptr;
     const double* d_mean_len = nullptr;    // the caller's, bound by bsk_es_set_log; may be NULL
     hipStream_t last_stream = nullptr;     // of the last ask / tell / apply_obs_norm: what bsk_es_set_log asks about a capture
+    // bsk_es_set_validation: off until n_val > 0; then ONE allocation of 8-byte words
+    // [val_epoch V | val_gen C | val_row 4 C | val_best_fitness | val_best_generation | take, - | val_best_params ceil(n_params / 2)]
+    int n_val = 0, val_capacity = 0;
+    unsigned long long* d_val = nullptr;
+    const double* d_val_len = nullptr;     // the caller's, f64[n_members + n_val], bound by bsk_es_set_validation; may be NULL
 };
 
 namespace {
@@ -230,10 +236,11 @@ struct RolloutHist {
 int rollout_steps(ParamStore* p, int envs_per_member, bsk_handle* h, int mode, int substeps, int n_steps, const RolloutHist& hist,
                   int32_t* d_act, const bsk::FitnessAcc* acc, double gamma) {
     const size_t n = (size_t)h->n;
+    const int n_stats = envs_per_member > 0 && p->n_counted > 0 ? p->n_counted * envs_per_member : h->n;     // (<= h->n: n_counted <= n_members)
     for (int t = 0; t < n_steps; ++t) {
         int32_t* act = hist.action ? hist.action + t * n : d_act;
         if (p->stats)
-            HIP_TRY(bsk::launch_obs_stats(h->d_obs, h->ostride, h->n, acc && t > 0 ? acc->alive : nullptr, p->stats->st, h->stream));
+            HIP_TRY(bsk::launch_obs_stats(h->d_obs, h->ostride, n_stats, acc && t > 0 ? acc->alive : nullptr, p->stats->st, h->stream));
         int rc = launch_act(p, envs_per_member, h->d_obs, h->ostride, h->n, (int64_t)h->env_base, mode, act,
                             hist.logp ? hist.logp + t * n : nullptr, hist.value ? hist.value + t * n : nullptr, nullptr, 0, h->stream);
         if (rc) return rc;
@@ -255,7 +262,9 @@ int rollout_steps(ParamStore* p, int envs_per_member, bsk_handle* h, int mode, i
 int check_stats(const ParamStore* p, const bsk_handle* h) {
     if (!p->stats) return BSK_OK;
     if (p->stats->device != h->device) return fail(BSK_EINVAL, "the attached observation statistics and the handle live on different devices");
-    if (h->n > p->stats->n_cap) return fail(BSK_EINVAL, "the handle's n_envs exceeds the capacity of the attached observation statistics");
+    // (a population that counts its first n_counted members only: their envs; the caller has checked that n_members divides h->n)
+    const int64_t n = p->n_counted > 0 ? (int64_t)p->n_counted * (h->n / p->n_members) : (int64_t)h->n;
+    if (n > p->stats->n_cap) return fail(BSK_EINVAL, "the handle's n_envs exceeds the capacity of the attached observation statistics");
     return BSK_OK;
 }
 
@@ -382,6 +391,12 @@ int bsk_population_get_member(bsk_population* p, int member, float* params) {
     return BSK_OK;
 }
 int bsk_population_set_obs_stats(bsk_population* p, bsk_obs_stats* stats) { return attach_stats(p, "population is NULL", stats); }
+int bsk_population_set_obs_stats_members(bsk_population* p, int n_counted) {
+    if (!p) return fail(BSK_EINVAL, "population is NULL");
+    if (n_counted < 1 || n_counted > p->n_members) return fail(BSK_EINVAL, "bsk_population_set_obs_stats_members: n_counted must be in 1..n_members");
+    p->n_counted = n_counted;
+    return BSK_OK;
+}
 int bsk_population_set_rng(bsk_population* p, uint64_t seed, uint64_t draw) { return set_rng(p, "population is NULL", seed, draw); }
 int bsk_population_get_rng(bsk_population* p, uint64_t* seed, uint64_t* draw) { return get_rng(p, "population is NULL", seed, draw); }
 
@@ -464,7 +479,7 @@ int bsk_es_create(const bsk_policy_spec* spec, int n_members, const float* theta
 void bsk_es_destroy(bsk_es* es) {
     if (!es) return;
     DeviceGuard guard(es->device);
-    free_all({es->d_state, es->d_theta, es->d_w, es->d_adam, es->d_sigma, es->d_log});
+    free_all({es->d_state, es->d_theta, es->d_w, es->d_adam, es->d_sigma, es->d_log, es->d_val});
     delete es;
 }
 
@@ -508,9 +523,44 @@ static bsk::EsLog es_log(const bsk_es* es) {
     return lg;
 }
 
+// the words of the validation's allocation and the views of them the kernels take
+static size_t es_val_words(const bsk_es* es, int n_val, int capacity) {
+    return (size_t)n_val + 5 * (size_t)capacity + 3 + ((size_t)es->lay.n_params + 1) / 2;
+}
+
+static bsk::EsVal es_val(const bsk_es* es) {
+    const size_t C = (size_t)es->val_capacity;
+    unsigned long long* ring = es->d_val + (size_t)es->n_val;
+    unsigned long long* tail = ring + 5 * C;
+    bsk::EsVal vl;
+    vl.gen = ring;
+    vl.row = (double*)(ring + C);
+    vl.best_fitness = (double*)tail;
+    vl.best_generation = tail + 1;
+    vl.cand = (int*)(tail + 2);
+    vl.best_params = (float*)(tail + 3);
+    vl.mean_len = es->d_val_len;
+    vl.capacity = es->val_capacity;
+    vl.n_val = es->n_val;
+    return vl;
+}
+
+// (the optimiser serves one stream at a time: the stream of its last launch is the one a capture of its loop records)
+static bool es_stream_capturing(bsk_es* es) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (es->last_stream && hipStreamIsCapturing(es->last_stream, &st) != hipSuccess) {
+        (void)hipGetLastError();                          // (a stream that has been destroyed since captures nothing)
+        st = hipStreamCaptureStatusNone;
+        es->last_stream = nullptr;
+    }
+    return st != hipStreamCaptureStatusNone;
+}
+
 int bsk_es_ask(bsk_es* es, bsk_population* pop, void* stream) {
     if (!es || !pop) return fail(BSK_EINVAL, "es/population is NULL");
-    if (pop->n_members != es->n_members) return fail(BSK_EINVAL, "bsk_es_ask: the population's n_members differs from the optimiser's");
+    if (pop->n_members != es->n_members + es->n_val)
+        return fail(BSK_EINVAL, es->n_val > 0 ? "bsk_es_ask: the population's n_members differs from the optimiser's n_members + n_val (bsk_es_set_validation)"
+                                              : "bsk_es_ask: the population's n_members differs from the optimiser's");
     if (std::memcmp(&pop->lay, &es->lay, sizeof(bsk::PolicyLayout)) != 0)      // (all-int, value-initialised: policy_layout)
         return fail(BSK_EINVAL, "bsk_es_ask: the population's spec differs from the optimiser's");
     if (pop->device != es->device) return fail(BSK_EINVAL, "bsk_es_ask: the optimiser and the population live on different devices");
@@ -520,6 +570,9 @@ int bsk_es_ask(bsk_es* es, bsk_population* pop, void* stream) {
         HIP_TRY(bsk::launch_es_ask_sigma(es->lay, es_args(es), es->d_sigma, pop->d_params, (hipStream_t)stream));
     else
         HIP_TRY(bsk::launch_es_ask(es->lay, es_args(es), pop->d_params, (hipStream_t)stream));
+    if (es->n_val > 0)                                    // the centre into the members behind ask's: member-major, so the launch above is the one it was
+        HIP_TRY(bsk::launch_es_center(es->lay, es->d_theta, pop->d_params + (size_t)es->n_members * (size_t)es->lay.n_device, es->n_val,
+                                      (hipStream_t)stream));
     return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
 }
 
@@ -531,6 +584,8 @@ int bsk_es_tell(bsk_es* es, const double* d_fitness, void* stream) {
     es->last_stream = (hipStream_t)stream;
     if (es->log_capacity > 0)                             // in front of the update: theta, sigma_vec and the generation as ask read them
         HIP_TRY(bsk::launch_es_log(es_args(es), pgpe ? es->d_sigma : nullptr, es->lay.n_params, d_fitness, es_log(es), (hipStream_t)stream));
+    if (es->n_val > 0)                                    // behind the log's two, in front of the update too: f[P .. P + V - 1]
+        HIP_TRY(bsk::launch_es_validate(es_args(es), es->lay.n_params, d_fitness, es_val(es), (hipStream_t)stream));
     if (pgpe)
         HIP_TRY(bsk::launch_es_rank_q(d_fitness, es->n_members, es->d_w, d_q, (hipStream_t)stream));
     else
@@ -696,14 +751,7 @@ int bsk_es_set_log(bsk_es* es, int capacity, const double* d_mean_len) {
     if (!es) return fail(BSK_EINVAL, "es is NULL");
     if (capacity < 0) return fail(BSK_EINVAL, "bsk_es_set_log: capacity must not be negative");
     DeviceGuard guard(es->device);
-    // (the optimiser serves one stream at a time: the stream of its last launch is the one a capture of its loop records)
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (es->last_stream && hipStreamIsCapturing(es->last_stream, &st) != hipSuccess) {
-        (void)hipGetLastError();                          // (a stream that has been destroyed since captures nothing)
-        st = hipStreamCaptureStatusNone;
-        es->last_stream = nullptr;
-    }
-    if (st != hipStreamCaptureStatusNone)
+    if (es_stream_capturing(es))
         return fail(BSK_EINVAL, "bsk_es_set_log: the optimiser's stream is being captured; it allocates and synchronises and cannot be captured");
     HIP_SYNC(hipDeviceSynchronize());                     // (queued tells still write the old log)
     if (es->d_log) {
@@ -765,6 +813,87 @@ int bsk_es_best_device(bsk_es* es, const float** d_params) {
     if (!es || !d_params) return fail(BSK_EINVAL, "es/d_params is NULL");
     if (es->log_capacity < 1) return fail(BSK_EINVAL, "bsk_es_best_device: the optimiser has no log (bsk_es_set_log)");
     *d_params = es_log(es).best_params;
+    return BSK_OK;
+}
+
+int bsk_es_set_validation(bsk_es* es, int n_val, int capacity, uint64_t epoch0, const double* d_mean_len) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    if (n_val < 0 || n_val > 16) return fail(BSK_EINVAL, "bsk_es_set_validation: n_val must be in 0..16");
+    if (n_val > 0 && capacity < 1) return fail(BSK_EINVAL, "bsk_es_set_validation: capacity must be >= 1");
+    DeviceGuard guard(es->device);
+    if (es_stream_capturing(es))
+        return fail(BSK_EINVAL, "bsk_es_set_validation: the optimiser's stream is being captured; it allocates and synchronises and cannot be captured");
+    HIP_SYNC(hipDeviceSynchronize());                     // (queued asks and tells still use the old state)
+    if (es->d_val) {
+        (void)hipFree(es->d_val);
+        es->d_val = nullptr;
+    }
+    es->n_val = es->val_capacity = 0;
+    es->d_val_len = nullptr;
+    if (n_val == 0) return BSK_OK;
+    const size_t V = (size_t)n_val, C = (size_t)capacity, words = es_val_words(es, n_val, capacity);
+    std::vector<unsigned long long> head(V);
+    for (size_t v = 0; v < V; ++v) head[v] = epoch0 + v;
+    HIP_TRY(hipMalloc(&es->d_val, words * 8));
+    HIP_COPY(hipMemcpy(es->d_val, head.data(), V * 8, hipMemcpyHostToDevice));          // val_epoch
+    HIP_TRY(hipMemset(es->d_val + V, 0xff, C * 8));                                      // val_gen: all ones
+    HIP_TRY(hipMemset(es->d_val + V + C, 0, (words - V - C) * 8));                       // val_row, val_best_params, the candidate word
+    const unsigned long long tail[2] = {0x7ff8000000000000ull, ~0ull};                   // a NaN, all ones
+    HIP_COPY(hipMemcpy(es->d_val + V + 5 * C, tail, sizeof tail, hipMemcpyHostToDevice));
+    HIP_SYNC(hipDeviceSynchronize());
+    es->n_val = n_val;
+    es->val_capacity = capacity;
+    es->d_val_len = d_mean_len;
+    return BSK_OK;
+}
+
+int bsk_es_get_validation_log(bsk_es* es, uint64_t* gen, double* rows) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    if (es->n_val < 1) return fail(BSK_EINVAL, "bsk_es_get_validation_log: validation is off (bsk_es_set_validation)");
+    DeviceGuard guard(es->device);
+    const bsk::EsVal vl = es_val(es);
+    const size_t C = (size_t)es->val_capacity;
+    HIP_SYNC(hipDeviceSynchronize());
+    if (gen) HIP_COPY(hipMemcpy(gen, vl.gen, C * 8, hipMemcpyDeviceToHost));
+    if (rows) HIP_COPY(hipMemcpy(rows, vl.row, 4 * C * 8, hipMemcpyDeviceToHost));
+    return BSK_OK;
+}
+
+int bsk_es_get_validated_best(bsk_es* es, float* params, double* fitness, uint64_t* generation) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    if (es->n_val < 1) return fail(BSK_EINVAL, "bsk_es_get_validated_best: validation is off (bsk_es_set_validation)");
+    DeviceGuard guard(es->device);
+    const bsk::EsVal vl = es_val(es);
+    HIP_SYNC(hipDeviceSynchronize());
+    if (params) HIP_COPY(hipMemcpy(params, vl.best_params, (size_t)es->lay.n_params * sizeof(float), hipMemcpyDeviceToHost));
+    if (fitness) HIP_COPY(hipMemcpy(fitness, vl.best_fitness, 8, hipMemcpyDeviceToHost));
+    if (generation) HIP_COPY(hipMemcpy(generation, vl.best_generation, 8, hipMemcpyDeviceToHost));
+    return BSK_OK;
+}
+
+int bsk_es_set_validated_best(bsk_es* es, const float* params, const double* fitness, const uint64_t* generation) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    if (es->n_val < 1) return fail(BSK_EINVAL, "bsk_es_set_validated_best: validation is off (bsk_es_set_validation)");
+    DeviceGuard guard(es->device);
+    const bsk::EsVal vl = es_val(es);
+    HIP_SYNC(hipDeviceSynchronize());                     // (queued tells still read and write the old champion)
+    if (params) HIP_COPY(hipMemcpy(vl.best_params, params, (size_t)es->lay.n_params * sizeof(float), hipMemcpyHostToDevice));
+    if (fitness) HIP_COPY(hipMemcpy(vl.best_fitness, fitness, 8, hipMemcpyHostToDevice));
+    if (generation) HIP_COPY(hipMemcpy(vl.best_generation, generation, 8, hipMemcpyHostToDevice));
+    return BSK_OK;
+}
+
+int bsk_es_validated_best_device(bsk_es* es, const float** d_params) {
+    if (!es || !d_params) return fail(BSK_EINVAL, "es/d_params is NULL");
+    if (es->n_val < 1) return fail(BSK_EINVAL, "bsk_es_validated_best_device: validation is off (bsk_es_set_validation)");
+    *d_params = es_val(es).best_params;
+    return BSK_OK;
+}
+
+int bsk_es_validation_epochs_device(bsk_es* es, const uint64_t** d_epochs) {
+    if (!es || !d_epochs) return fail(BSK_EINVAL, "es/d_epochs is NULL");
+    if (es->n_val < 1) return fail(BSK_EINVAL, "bsk_es_validation_epochs_device: validation is off (bsk_es_set_validation)");
+    *d_epochs = (const uint64_t*)es->d_val;
     return BSK_OK;
 }
 

@@ -9,6 +9,9 @@
 //                      BSK_ES_SIGMA_PGPE: a step size per parameter in device memory, moved by lane 0 behind a second sum
 //   es_log_kernel, es_best_kernel     bsk_es_set_log: one wave for the generation's row and the champion rule, then one thread per
 //                      parameter for the champion's floats - in front of the update, from what ask read
+//   es_center_kernel, es_validate_kernel, es_val_best_kernel     bsk_es_set_validation: the centre into the V members behind
+//                      ask's, then one thread for the centre's row and the validated champion's rule and one thread per parameter
+//                      for its floats - in front of the update too
 // The noise is never stored: z(g, i, j) is one Philox4x32-10 call and an inverse normal CDF made of f64 + - * /, sqrt and integer
 // operations.  Compiled with -ffp-contract=off (Makefile), as bsk_population.hip is: every operation rounds on its own, and numpy
 // repeats all of it bit for bit (policy_ref.py: es_noise_ref, es_ask_ref, es_tell_ref, es_tell_adam_ref, es_ask_sigma_ref,
@@ -399,6 +402,70 @@ hipError_t launch_es_log(const EsArgs& es, const double* sigma_vec, int n_params
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(es_best_kernel, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, s, es, sigma_vec, n_params, lg);
+    return hipGetLastError();
+}
+
+// Validation on fixed episodes (include/bskgpu.h, bsk_es_set_validation).  Validation member blockIdx.x, float d of its device
+// block: ask's gather (policy_pack_source) with the plain (float)theta_j in place of theta +- sigma * z - for every j, frozen or
+// not, and with no sum in between, so that a -0.0 in theta stays -0.0; the padding is zero.  dst is the block of member P: every
+// float of the V blocks is written by exactly one thread.
+__global__ __launch_bounds__(256) void es_center_kernel(const double* __restrict__ theta, float* __restrict__ dst, const PolicyPackMap map) {
+#pragma clang fp contract(off)
+    const int d = (int)(blockIdx.y * blockDim.x + threadIdx.x);
+    if (d >= map.n_device) return;
+    const int j = policy_pack_source(map, d);
+    dst[(size_t)blockIdx.x * (size_t)map.n_device + d] = j >= 0 ? (float)theta[j] : 0.0f;
+}
+
+// ONE thread, in front of the update and behind the log's two launches: the centre's score f_c = (f[P] + f[P + 1] + ...) / V, the
+// sum ascending from the first value, and L_c the same over mean_len; row g mod capacity; the champion rule of es_log_kernel on
+// f_c.  The candidate word is for es_val_best_kernel behind this launch.
+__global__ void es_validate_kernel(const unsigned long long* __restrict__ state, const double* __restrict__ fitness, int P, const EsVal vl) {
+#pragma clang fp contract(off)
+    const unsigned long long g = state[1];
+    const unsigned long long slot = g % (unsigned long long)vl.capacity;
+    double s = fitness[P], l = vl.mean_len ? vl.mean_len[P] : 0.0;
+    for (int v = 1; v < vl.n_val; ++v) {
+        s = s + fitness[P + v];
+        if (vl.mean_len) l = l + vl.mean_len[P + v];
+    }
+    const double fc = s / (double)vl.n_val;
+    const double lc = vl.mean_len ? l / (double)vl.n_val : 0.0;
+    const double champion = *vl.best_fitness;
+    const bool take = fc == fc && (champion != champion || fc > champion);
+    if (take) {
+        *vl.best_fitness = fc;
+        *vl.best_generation = g;
+    }
+    double* row = vl.row + 4 * slot;
+    row[0] = fc;
+    row[1] = lc;
+    row[2] = take ? 1.0 : 0.0;
+    row[3] = (double)vl.n_val;
+    vl.gen[slot] = g;
+    vl.cand[0] = take ? 1 : 0;
+}
+
+// One thread per parameter j, behind es_validate_kernel on the same stream (the kernel boundary orders the candidate word: no
+// atomics, no fence) and in front of the update: while `take`, val_best_params[j] = (float)theta_j - the float es_center_kernel wrote.
+__global__ __launch_bounds__(256) void es_val_best_kernel(const double* __restrict__ theta, int n_params, const EsVal vl) {
+#pragma clang fp contract(off)
+    const int j = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (j >= n_params || vl.cand[0] == 0) return;
+    vl.best_params[j] = (float)theta[j];
+}
+
+hipError_t launch_es_center(const PolicyLayout& lay, const double* theta, float* d_block, int n_val, hipStream_t s) {
+    const PolicyPackMap map = policy_pack_map(lay);
+    hipLaunchKernelGGL(es_center_kernel, dim3((unsigned)n_val, (unsigned)((lay.n_device + 255) / 256)), dim3(256), 0, s, theta, d_block, map);
+    return hipGetLastError();
+}
+
+hipError_t launch_es_validate(const EsArgs& es, int n_params, const double* fitness, const EsVal& vl, hipStream_t s) {
+    hipLaunchKernelGGL(es_validate_kernel, dim3(1), dim3(1), 0, s, es.state, fitness, 2 * es.pairs, vl);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(es_val_best_kernel, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, s, es.theta, n_params, vl);
     return hipGetLastError();
 }
 

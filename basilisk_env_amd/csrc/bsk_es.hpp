@@ -46,6 +46,20 @@ struct EsLog {
     int capacity;
 };
 
+// bsk_es_set_validation: the ring of the centre's rows and the validated champion, all device memory (one allocation of the
+// optimiser's; the V epoch words in front of it are the caller's to read, no kernel of the optimiser does)
+struct EsVal {
+    unsigned long long* gen;           // [capacity], the generation each row belongs to (all ones: never written)
+    double* row;                       // [capacity][4]: f_c, L_c, take, V
+    double* best_fitness;              // the validated champion: a NaN while there is none
+    unsigned long long* best_generation;
+    int* cand;                         // {take}: es_validate_kernel's word for es_val_best_kernel
+    float* best_params;                // [n_params], the C-ABI parameter layout
+    const double* mean_len;            // [n_members + n_val] or nullptr: the caller's, bound by bsk_es_set_validation
+    int capacity;
+    int n_val;
+};
+
 // The members of this generation into d_params ([2 * pairs][lay.n_device], a population's device layout): one launch, every
 // float written exactly once.
 hipError_t launch_es_ask(const PolicyLayout& lay, const EsArgs& es, float* d_params, hipStream_t s);
@@ -66,6 +80,11 @@ hipError_t launch_es_tell_adam_sigma(const EsArgs& es, int n_params, const doubl
 // The two launches of the training log, in front of the update (theta, sigma_vec and the generation word as ask read them):
 // the row of this generation and the champion rule, then the champion's floats.  sigma_vec: nullptr under BSK_ES_SIGMA_FIXED.
 hipError_t launch_es_log(const EsArgs& es, const double* sigma_vec, int n_params, const double* fitness, const EsLog& lg, hipStream_t s);
+// Validation: (float)theta into the n_val device blocks from d_block on (the block of member n_members), one launch behind ask's ...
+hipError_t launch_es_center(const PolicyLayout& lay, const double* theta, float* d_block, int n_val, hipStream_t s);
+// ... and the two launches in front of the update, behind the log's: fitness f64[n_members + n_val], the centre's row and the
+// champion rule on one thread, then the validated champion's floats
+hipError_t launch_es_validate(const EsArgs& es, int n_params, const double* fitness, const EsVal& vl, hipStream_t s);
 // generation += 1 and beta_pow *= {beta1, beta2}, one thread, behind launch_es_tell_adam on the same stream
 hipError_t launch_es_advance_adam(unsigned long long* state, double* beta_pow, double beta1, double beta2, hipStream_t s);
 // generation += 1, one thread, behind a tell on the same stream (a replayed graph moves on to the next generation)

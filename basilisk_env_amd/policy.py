@@ -22,7 +22,7 @@ What needs no device lives beside this module and is re-exported here under the 
 layout of the parameter block in ``policy_spec`` (``check_spec``, ``pack_params``, ...), and in ``policy_ref`` the numpy
 restatements the kernels are held to bit for bit (``mlp_ref`` / ``act_ref``: every layer output one k-ordered chain of f32 fused
 multiply-adds from the bias; ``population_fitness_ref``; ``es_noise_ref`` / ``es_ask_ref`` / ``es_tell_ref`` /
-``es_tell_adam_ref`` / ``es_ask_sigma_ref`` / ``es_tell_pgpe_ref`` / ``es_log_row_ref`` / ``es_best_ref``; ``obs_stats_accumulate_ref`` / ``obs_stats_totals_ref`` / ``obs_norm_ref``) with ``EvolutionStrategy``, the host-side loop the device one was modelled on.
+``es_tell_adam_ref`` / ``es_ask_sigma_ref`` / ``es_tell_pgpe_ref`` / ``es_log_row_ref`` / ``es_best_ref`` / ``es_center_ref`` / ``es_validate_ref``; ``obs_stats_accumulate_ref`` / ``obs_stats_totals_ref`` / ``obs_norm_ref``) with ``EvolutionStrategy``, the host-side loop the device one was modelled on.
 """
 import ctypes as C
 import sys
@@ -31,11 +31,12 @@ import numpy as np
 
 from . import _hip, _lib
 from ._lib import check
-from .policy_ref import (ES_LOG_COLUMNS, ES_LOG_EMPTY, EvolutionStrategy, _es_pair_sum, _es_pair_sums, _series_log, act_ref,  # noqa: F401
-                         centred_ranks, check_adam, check_log,
-                         es_ask_ref, es_ask_sigma_ref, es_best_ref, es_champion_empty, es_inverse_normal_ref, es_log_order_ref,
+from .policy_ref import (ES_LOG_COLUMNS, ES_LOG_EMPTY, ES_VAL_COLUMNS, ES_VAL_MAX_MEMBERS, EvolutionStrategy, _es_pair_sum,  # noqa: F401
+                         _es_pair_sums, _series_log, act_ref,
+                         centred_ranks, check_adam, check_log, check_validation,
+                         es_ask_ref, es_ask_sigma_ref, es_best_ref, es_center_ref, es_champion_empty, es_inverse_normal_ref, es_log_order_ref,
                          es_log_row_ref, es_log_slot_ref, es_log_table_ref, es_noise_ref, es_tell_adam_ref, es_tell_pgpe_ref,
-                         es_tell_ref, es_uniform_ref, fma32,
+                         es_tell_ref, es_uniform_ref, es_validate_ref, es_validation_state, es_validation_table_ref, fma32,
                          mlp_ref, obs_moments_ref, obs_norm_ref, obs_stats_accumulate_ref, obs_stats_totals_ref,
                          obs_stats_zero_state, philox4x32_10, population_fitness_ref, sample_uniform, shared_slot_ref, softmax_ref)
 from .policy_spec import (ACTIVATIONS, MAX_HIDDEN_LAYERS, MODES, POLICY_GREEDY, POLICY_RELU, POLICY_SAMPLE,  # noqa: F401
@@ -445,6 +446,11 @@ class PolicyPopulation(_ParamStore):
         check(self._lib.bsk_population_set_params_device(self._handle(), C.c_void_p(int(src)) if src else None, int(first), int(count),
                                                          C.c_void_p(int(stream or 0))))
 
+    def set_obs_stats_members(self, n_counted=None):
+        """Only the envs of the first ``n_counted`` members feed an attached ``ObsStats`` (None: all of them, the default):
+        ``bsk_population_set_obs_stats_members``.  No launch; the next rollout's accumulate launches cover n_counted * E envs."""
+        check(self._lib.bsk_population_set_obs_stats_members(self._handle(), self.n_members if n_counted is None else int(n_counted)))
+
     def member(self, m):
         """Member ``m``'s parameter block (n_params,) float32 - what ``DevicePolicy(spec, block)`` takes.  Synchronises."""
         out = np.empty(self.n_params, np.float32)
@@ -503,14 +509,18 @@ class DeviceEvolutionStrategy(_DeviceObject):
     ``es_tell_pgpe_ref``): by ``lr_sigma``, at most ``sigma_max_change`` of itself per generation, inside
     [``sigma_min``, ``sigma_max``] (None: ``sigma`` / 100 and 10 ``sigma``).  None, the default, keeps the one ``sigma`` and never
     calls that entry point.  ``log_capacity`` > 0 keeps a training log of that many generations and the best member so far on
-    the device (``set_log``; ``training_log``, ``best``); 0, the default, never calls that entry point either.  Not thread-safe,
-    one stream at a time."""
+    the device (``set_log``; ``training_log``, ``best``); 0, the default, never calls that entry point either.
+    ``validation_members`` = V > 0 scores the centre theta on fixed episodes inside every generation (``set_validation``;
+    ``validation_log``, ``validated_best``): ``ask`` then takes a population of ``members_total`` = P + V members, the last V
+    holding the centre, and ``tell`` P + V fitness values, of which ranking, log, champion and update read the first P; 0, the
+    default, never calls that entry point either.  Not thread-safe, one stream at a time."""
     _kind, _what = "es", "evolution strategy"
 
     def __init__(self, spec, theta, population, sigma=0.1, lr=0.05, seed=0, frozen=10, device=0, optimizer="sgd", beta1=0.9,
                  beta2=0.999, eps=1e-8, weight_decay=0.0, sigma_adapt=None, lr_sigma=0.1, sigma_max_change=0.2, sigma_min=None,
-                 sigma_max=None, log_capacity=0):
+                 sigma_max=None, log_capacity=0, validation_members=0, validation_capacity=None, validation_epoch=0xFFFFFFFF):
         log_capacity = check_log(log_capacity)
+        check_validation(validation_members, validation_capacity, validation_epoch, log_capacity)
         if optimizer not in ("sgd", "adam"):
             raise ValueError("optimizer must be 'sgd' or 'adam', got %r" % (optimizer,))
         if optimizer == "adam":
@@ -524,6 +534,8 @@ class DeviceEvolutionStrategy(_DeviceObject):
             check_sigma_adaptation(lr_sigma, sigma_max_change, sigma_min, sigma_max, sigma)
         self.sigma_adapt, self.sigma_adaptation = None, None
         self.log_capacity, self._log_len, self._log_source = 0, None, None
+        self.validation_members, self.validation_capacity, self.validation_epoch = 0, 0, 0
+        self._val_len, self._val_source, self._val_masks = None, None, {}
         self.spec = _as_spec(spec)
         self.n_params = n_params(self.spec)
         self.population, self.sigma, self.lr, self.frozen = int(population), float(sigma), float(lr), int(frozen)
@@ -536,6 +548,14 @@ class DeviceEvolutionStrategy(_DeviceObject):
             self.set_sigma_adaptation(sigma_adapt, lr_sigma, sigma_max_change, sigma_min, sigma_max)
         if log_capacity:
             self.set_log(log_capacity)
+        if validation_members:
+            self.set_validation(validation_members, validation_capacity, validation_epoch)
+
+    def close(self):
+        for b in (getattr(self, "_val_masks", None) or {}).values():
+            b.free()
+        self._val_masks = {}
+        super(DeviceEvolutionStrategy, self).close()
 
     # ------------------------------------------------------------------ state
     @property
@@ -625,28 +645,39 @@ class DeviceEvolutionStrategy(_DeviceObject):
         are +0.0, as with nothing bound) until ``run_generation`` has the rollout write the members' mean episode lengths there.
         Theta, the generation, Adam's state and the step sizes stay; synchronises, and cannot be captured."""
         def refuse(typestr, shape, size, dense):
-            if typestr != "<f8" or size != self.population or (len(shape) == 1 and not dense):
-                return "mean_len: %d contiguous float64, got %r %r" % (self.population, typestr, shape)
+            if typestr != "<f8" or size != self.members_total or (len(shape) == 1 and not dense):
+                return "mean_len: %d contiguous float64, got %r %r" % (self.members_total, typestr, shape)
         capacity = check_log(capacity)
         queued, ptr = self._source, None
         if capacity and mean_len is not None:
             ptr, _ = self._device_pointer(mean_len, 8, refuse)
             self._source = queued                          # (a queued tell still reads its fitness)
+            if self.validation_members and int(ptr or 0) != self._val_len:
+                raise ValueError("mean_len: while validation is on the log reads the length buffer set_validation bound (the rollout writes one)")
+        if capacity and mean_len is None and self.validation_members and self._val_source is not None:
+            ptr = self._val_len                            # (the array the caller bound there: the rollout writes P + V values into it)
         # off first: the refusal under capture comes from the library, before anything is allocated or written here
         check(self._lib.bsk_es_set_log(self._handle(), 0, None))
         self.log_capacity, self._log_len, self._log_source = 0, None, None
         if not capacity:
             return
-        if mean_len is None:
-            if self._out is None:
-                self._out = {}
-            if "mean_len" not in self._out:
-                self._out["mean_len"] = _hip.DeviceBuffer(8 * self.population, self.device)
-            ptr = self._out["mean_len"].ptr
-            with _hip.device_guard(self.device):
-                _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(ptr), 0, 8 * self.population, None), "hipMemsetAsync")
+        if ptr is None:
+            ptr = self._own_lengths()
         check(self._lib.bsk_es_set_log(self._handle(), capacity, C.c_void_p(int(ptr)) if ptr else None))
         self.log_capacity, self._log_len, self._log_source = capacity, int(ptr or 0) or None, mean_len      # (every later tell reads it)
+
+    def _own_lengths(self):
+        """The optimiser's own length buffer, zeroed -> its pointer: P + ``ES_VAL_MAX_MEMBERS`` float64, so that the log and the
+        validation read ONE buffer - the rollout writes one - whichever is turned on first and however many members validate."""
+        nbytes = 8 * (self.population + ES_VAL_MAX_MEMBERS)
+        if self._out is None:
+            self._out = {}
+        if "mean_len" not in self._out:
+            self._out["mean_len"] = _hip.DeviceBuffer(nbytes, self.device)
+        ptr = self._out["mean_len"].ptr
+        with _hip.device_guard(self.device):
+            _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(ptr), 0, nbytes, None), "hipMemsetAsync")
+        return ptr
 
     def training_log(self):
         """The log as a dict of numpy arrays over the generations it holds, sorted by generation (``es_log_table_ref``):
@@ -682,28 +713,143 @@ class DeviceEvolutionStrategy(_DeviceObject):
         check(self._lib.bsk_es_best_device(self._handle(), C.byref(p)))
         return p.value
 
+    # ------------------------------------------------------------------ validation on fixed episodes
+    @property
+    def members_total(self):
+        """P + V: the members of the population ``ask`` takes and the fitness values ``tell`` takes."""
+        return self.population + self.validation_members
+
+    def set_validation(self, members, capacity=None, epoch=0xFFFFFFFF, mean_len=None):
+        """``members`` = V in 1..16 validation members holding the centre theta, a ring of ``capacity`` rows (None: the log's
+        capacity, or 64) and the validated champion, on the device (``bsk_es_set_validation``; ``es_center_ref``,
+        ``es_validate_ref``); 0 turns it off.  Every call with V > 0 starts from an empty ring and no champion.  Member P + v
+        restarts its envs under the epoch word ``epoch`` + v, constant from here on; the default keeps member P's slots away from the
+        low generation words ``shared_episodes`` uses (the slot rule reads the low 32 bits of the word: with V > 1 member P + v
+        then uses the words v - 1).  ``mean_len``: P + V float64 in DEVICE memory, as ``set_log`` takes; None:
+        the buffer the log reads (the rollout writes one), the optimiser's own unless an array was bound there.
+        What is exact: under ``greedy`` the centre's validation score is a deterministic function of theta - the same bits for the
+        same theta in every generation; ``sample`` still draws per global env index and draw counter.  A validation env that
+        finishes restarts by the per-env rule; its later episodes do not count, as everywhere.  Training is untouched bit for bit:
+        the validation envs restart under their own mask, their observations do not enter ``obs_stats``, and ranking, log, champion
+        and update never read their fitness.  Theta, the generation, Adam's state, the step sizes, the log and its champion stay;
+        synchronises, and cannot be captured.  ``run_generation`` builds its device masks in the first call after this one."""
+        members, capacity, epoch = check_validation(members, capacity, epoch, self.log_capacity)
+        total = self.population + members
+
+        def refuse(typestr, shape, size, dense):
+            if typestr != "<f8" or size != total or (len(shape) == 1 and not dense):
+                return "mean_len: %d contiguous float64, got %r %r" % (total, typestr, shape)
+        queued, ptr = self._source, None
+        if members and mean_len is not None:
+            ptr, _ = self._device_pointer(mean_len, 8, refuse)
+            self._source = queued                          # (a queued tell still reads its fitness)
+            if self.log_capacity and int(ptr or 0) != self._log_len:
+                raise ValueError("mean_len: while a log is on the validation reads the length buffer set_log bound (the rollout writes one)")
+        elif members and self.log_capacity and self._log_source is not None:
+            raise ValueError("the log reads an array of P lengths the caller bound, and the rollout will write P + V: turn the log off, "
+                             "give set_validation a mean_len of P + V values, then set_log the same array")
+        # off first: the refusal under capture comes from the library, before anything is allocated or written here
+        check(self._lib.bsk_es_set_validation(self._handle(), 0, 0, 0, None))
+        for b in self._val_masks.values():
+            b.free()
+        self.validation_members, self.validation_capacity, self.validation_epoch = 0, 0, 0
+        self._val_len, self._val_source, self._val_masks = None, None, {}
+        if not members:
+            return
+        if ptr is None:
+            ptr = self._log_len if self.log_capacity else self._own_lengths()
+        check(self._lib.bsk_es_set_validation(self._handle(), members, capacity, epoch, C.c_void_p(int(ptr)) if ptr else None))
+        self.validation_members, self.validation_capacity, self.validation_epoch = members, capacity, epoch
+        self._val_len, self._val_source = int(ptr or 0) or None, mean_len
+
+    def validation_log(self):
+        """The validation ring as a dict of numpy arrays over the generations it holds, sorted by generation
+        (``es_validation_table_ref``): ``generation``, ``fitness`` (f_c, the centre's mean over its V members), ``mean_len``,
+        ``take``, ``members``.  Synchronises.  An error with validation off."""
+        gen = np.empty(max(self.validation_capacity, 1), np.uint64)
+        rows = np.empty((gen.size, 4), np.float64)
+        check(self._lib.bsk_es_get_validation_log(self._handle(), gen.ctypes.data, rows.ctypes.data))
+        return es_validation_table_ref(gen, rows)
+
+    @property
+    def validated_best(self):
+        """The validated champion -> (params float32 (n_params,), fitness, generation): the centre with the best validation score so
+        far; (zeros, NaN, ``ES_LOG_EMPTY``) while no generation has taken.  Synchronises.  An error with validation off."""
+        params, f, g = np.empty(self.n_params, np.float32), C.c_double(), C.c_uint64()
+        check(self._lib.bsk_es_get_validated_best(self._handle(), params.ctypes.data, C.addressof(f), C.addressof(g)))
+        return params, f.value, g.value
+
+    def set_validated_best(self, params=None, fitness=None, generation=None):
+        """A new validated champion, for a checkpoint that resumes bit for bit; None keeps; synchronises."""
+        p = None if params is None else _host_block(params, self.n_params)
+        f = None if fitness is None else C.c_double(float(fitness))
+        g = None if generation is None else C.c_uint64(int(generation))
+        check(self._lib.bsk_es_set_validated_best(self._handle(), None if p is None else p.ctypes.data,
+                                                  *[None if x is None else C.addressof(x) for x in (f, g)]))
+
+    def validated_best_params_ptr(self):
+        """The validated champion's parameter block as a DEVICE pointer to n_params float32, valid until the next ``set_validation``
+        or ``close``: what ``pop.set_params_device`` takes."""
+        p = C.c_void_p()
+        check(self._lib.bsk_es_validated_best_device(self._handle(), C.byref(p)))
+        return p.value
+
+    def validation_epochs_ptr(self):
+        """The V epoch words as a DEVICE pointer to uint64[V], valid until the next ``set_validation`` or ``close``: member P + v's
+        ``reset_from_pool_shared`` takes this pointer + 8 v."""
+        p = C.c_void_p()
+        check(self._lib.bsk_es_validation_epochs_device(self._handle(), C.byref(p)))
+        return p.value
+
+    def _validation_masks(self, n_envs):
+        """The device masks of ``run_generation`` for a handle of ``n_envs`` -> pointer to uint8[1 + V][n_envs]: row 0 the envs of
+        the P training members, row 1 + v those of validation member v.  Built and uploaded once per size (it allocates and
+        synchronises: the warming call), so that a later call stays capturable."""
+        buf = self._val_masks.get(n_envs)
+        if buf is None:
+            P, V = self.population, self.validation_members
+            E = n_envs // (P + V)
+            if E < 1 or E * (P + V) != n_envs:
+                raise ValueError("the propagator's n_envs (%d) must be a multiple of population + validation_members (%d)" % (n_envs, P + V))
+            host = np.zeros((1 + V, n_envs), np.uint8)
+            host[0, :P * E] = 1
+            for v in range(V):
+                host[1 + v, (P + v) * E:(P + v + 1) * E] = 1
+            buf = _hip.DeviceBuffer(host.nbytes, self.device)
+            with _hip.device_guard(self.device):
+                _hip.check(_hip.runtime().hipMemcpyAsync(C.c_void_p(buf.ptr), C.c_void_p(host.ctypes.data), host.nbytes,
+                                                         _hip.hipMemcpyHostToDevice, None), "hipMemcpyAsync")
+            self.sync()                                    # (the copy reads `host`)
+            self._val_masks[n_envs] = buf
+        return buf.ptr
+
     # ------------------------------------------------------------------ the search
     def ask(self, pop, stream=0):
-        """This generation's members into every member of ``pop`` (a ``PolicyPopulation`` of the same spec and size): one launch
-        on ``stream``, no copy, no synchronisation."""
+        """This generation's members into every member of ``pop`` (a ``PolicyPopulation`` of the same spec and ``members_total``
+        members): one launch on ``stream`` - and one more for the V validation members - no copy, no synchronisation."""
         check(self._lib.bsk_es_ask(self._handle(), pop._handle(), C.c_void_p(int(stream or 0))))
 
     def tell(self, d_fitness, stream=0):
-        """``d_fitness``: P float64 in DEVICE memory (greater is better) - a raw pointer or anything with
-        ``__cuda_array_interface__``.  Ranks them, moves theta and advances the generation: three launches on ``stream``, and with
-        a log on two more in front of the update."""
+        """``d_fitness``: P float64 in DEVICE memory (greater is better; P + V while validation is on) - a raw pointer or anything
+        with ``__cuda_array_interface__``.  Ranks the first P, moves theta and advances the generation: three launches on
+        ``stream``, with a log on two more in front of the update, and with validation on two more behind those."""
         def refuse(typestr, shape, size, dense):
-            if typestr != "<f8" or size != self.population or (len(shape) == 1 and not dense):       # (a 1-D array's stride only)
-                return "device fitness: %d contiguous float64, got %r %r" % (self.population, typestr, shape)
+            if typestr != "<f8" or size != self.members_total or (len(shape) == 1 and not dense):       # (a 1-D array's stride only)
+                return "device fitness: %d contiguous float64, got %r %r" % (self.members_total, typestr, shape)
         d_fitness, _ = self._device_pointer(d_fitness, 8, refuse)
         check(self._lib.bsk_es_tell(self._handle(), C.c_void_p(int(d_fitness)) if d_fitness else None, C.c_void_p(int(stream or 0))))
 
     def fitness_buffer(self):
-        """The device buffer of P float64 ``run_generation`` has the rollout write the fitness to (``_hip.DeviceBuffer``)."""
+        """The device buffer of P float64 (P + V while validation is on) ``run_generation`` has the rollout write the fitness to
+        (``_hip.DeviceBuffer``)."""
         if self._out is None:
             self._out = {}
+        want = 8 * self.members_total
+        if "fitness" in self._out and self._out["fitness"].nbytes < want:
+            self.sync()                                    # (a queued tell still reads the smaller one)
+            self._out.pop("fitness").free()
         if "fitness" not in self._out:
-            self._out["fitness"] = _hip.DeviceBuffer(8 * self.population, self.device)
+            self._out["fitness"] = _hip.DeviceBuffer(want, self.device)
         return self._out["fitness"]
 
     def apply_obs_norm(self, stats, std_min=1e-6, stream=0):
@@ -724,12 +870,30 @@ class DeviceEvolutionStrategy(_DeviceObject):
         ``obs_stats``: an ``ObsStats`` the rollout accumulates into (attached to ``pop`` for the rollout, which is left with what it
         had attached before), and ``apply_obs_norm(obs_stats, std_min)`` behind ``tell``: generation g runs with the statistics of
         the generations before it.  With a log on the rollout also writes the members' mean episode lengths into the buffer
-        ``set_log`` bound, for the row's length columns; with it off the rollout is passed what it was passed before."""
+        ``set_log`` bound, for the row's length columns; with it off the rollout is passed what it was passed before.
+        With validation on (``set_validation``) ``pop`` has P + V members and E = n_envs // (P + V): the training envs restart as
+        above, but under a device mask of the first P * E envs; then validation member v's E envs restart by
+        ``reset_from_pool_shared`` under its own mask and its own constant epoch word - one launch each.  The masks are built in
+        the first call for a handle's size (the warming call).  ``obs_stats`` counts the first P members only
+        (``pop.set_obs_stats_members``; the population is left counting all), and the rollout writes P + V fitness values and
+        lengths."""
         prop = getattr(prop, "propagator", prop)
         fit = self.fitness_buffer()
         stream = prop.stream_ptr()
-        lengths = {"d_mean_len": self._log_len} if self.log_capacity else {}
-        if reset and shared_episodes:
+        V = self.validation_members
+        lengths = {"d_mean_len": self._val_len if V else self._log_len} if self.log_capacity or V else {}
+        if V:
+            E = prop.n_envs // self.members_total
+            masks = self._validation_masks(prop.n_envs)
+            if reset and shared_episodes:
+                prop.reset_from_pool_shared(E, self.generation_ptr(), masks)
+            elif reset:
+                prop.reset_from_pool_device(masks)
+            if reset:
+                epochs = self.validation_epochs_ptr()
+                for v in range(V):
+                    prop.reset_from_pool_shared(E, epochs + 8 * v, masks + (1 + v) * prop.n_envs)
+        elif reset and shared_episodes:
             prop.reset_from_pool_shared(prop.n_envs // self.population, self.generation_ptr())
         elif reset:
             prop.reset_from_pool_device(None)
@@ -740,9 +904,13 @@ class DeviceEvolutionStrategy(_DeviceObject):
             return
         before = getattr(pop, "_stats", None)
         pop.set_obs_stats(obs_stats)
+        if V:
+            pop.set_obs_stats_members(self.population)
         try:
             pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr, **lengths)
         finally:
+            if V:
+                pop.set_obs_stats_members(None)
             pop.set_obs_stats(before)
         self.tell(fit.ptr, stream)
         self.apply_obs_norm(obs_stats, std_min, stream)

@@ -595,6 +595,98 @@ def check_log(capacity, population=None, mean_len_size=None):
     return capacity
 
 
+# Validation on fixed episodes (bsk_es_set_validation; kernels es_center_kernel / es_validate_kernel / es_val_best_kernel), restated
+
+ES_VAL_COLUMNS = ("fitness", "mean_len", "take", "members")
+ES_VAL_MAX_MEMBERS = 16
+
+
+def check_validation(members, capacity=None, epoch=0, log_capacity=0):
+    """The argument rules of ``set_validation`` that need no device -> (members, capacity, epoch) as ints; ValueError where
+    ``bsk_es_set_validation`` returns BSK_EINVAL.  ``capacity`` None: the log's capacity, or 64 with no log."""
+    for what, x in (("validation members", members), ("validation epoch", epoch)) + ((("validation capacity", capacity),) if capacity is not None else ()):
+        if isinstance(x, bool) or int(x) != x:
+            raise ValueError("%s must be an integer, got %r" % (what, x))
+    members, epoch = int(members), int(epoch)
+    if members < 0 or members > ES_VAL_MAX_MEMBERS:
+        raise ValueError("validation members must be in 0..%d, got %d" % (ES_VAL_MAX_MEMBERS, members))
+    capacity = (int(log_capacity) or 64) if capacity is None else int(capacity)
+    if members and (capacity < 1 or capacity > 2 ** 31 - 1):
+        raise ValueError("validation capacity must be in 1..2^31-1, got %d" % capacity)
+    if epoch < 0 or epoch > 2 ** 64 - 1 - ES_VAL_MAX_MEMBERS:
+        raise ValueError("validation epoch must be in 0..2^64-17, got %d" % epoch)
+    return members, capacity, epoch
+
+
+def es_center_ref(theta):
+    """What ``bsk_es_ask`` writes into every validation member -> float32 (n_params,), the C-ABI parameter block: the plain
+    (float)theta_j of every j, frozen or not - no ``+ sigma * 0``, so a -0.0 in theta stays -0.0."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.asarray(theta, np.float64).reshape(-1).astype(np.float32)
+
+
+def es_validation_state(members, capacity, n_params, epoch=0):
+    """The validation state after ``bsk_es_set_validation`` -> dict: ``epochs`` uint64 (V,) = epoch + v, ``gen`` uint64 (C,) all
+    ones, ``rows`` float64 (C, 4) zeros, ``best_params`` float32 zeros, ``best_fitness`` NaN, ``best_generation`` all ones,
+    ``take`` 0."""
+    V, C = int(members), int(capacity)
+    if V < 1 or V > ES_VAL_MAX_MEMBERS or C < 1:
+        raise ValueError("members in 1..%d and capacity >= 1" % ES_VAL_MAX_MEMBERS)
+    return {"epochs": np.array([(int(epoch) + v) & (2 ** 64 - 1) for v in range(V)], np.uint64),
+            "gen": np.full(C, ES_LOG_EMPTY, np.uint64), "rows": np.zeros((C, 4), np.float64),
+            "best_params": np.zeros(int(n_params), np.float32), "best_fitness": float("nan"), "best_generation": ES_LOG_EMPTY, "take": 0}
+
+
+def es_validate_ref(state, fitness, mean_len, generation, theta):
+    """The two validation launches of ``bsk_es_tell`` -> the new state (``es_validation_state``'s dict; the old one is not touched).
+    ``fitness``: float64 (P + V,) - its LAST V = len(state["epochs"]) values are the validation members'; ``mean_len``: the same
+    shape or None (nothing bound: L_c = +0.0); ``theta``: float64 (n_params,) as ask read it.  s = f[P], then + f[P + v] for v
+    ascending, f_c = s / V, L_c likewise; the champion rule on f_c - not NaN, and the champion NaN or strictly lower: a tie keeps
+    the older one; row g mod C = {f_c, L_c, take, V}; with take the champion's floats are ``es_center_ref(theta)``."""
+    V, C = len(state["epochs"]), len(state["gen"])
+    f = np.asarray(fitness, np.float64).reshape(-1)
+    if f.size < V:
+        raise ValueError("expected at least %d fitness values" % V)
+    g = int(generation) & (2 ** 64 - 1)
+
+    def centre(x):
+        x = np.asarray(x, np.float64).reshape(-1)
+        if x.size != f.size:
+            raise ValueError("mean_len has one value per member")
+        with np.errstate(invalid="ignore", over="ignore"):
+            s = np.float64(x[x.size - V])
+            for v in range(1, V):
+                s = np.float64(s + x[x.size - V + v])
+            return np.float64(s / np.float64(V))
+    fc = centre(f)
+    lc = np.float64(0.0) if mean_len is None else centre(mean_len)
+    best = state["best_fitness"]
+    take = (not np.isnan(fc)) and (np.isnan(best) or fc > best)
+    out = {"epochs": state["epochs"].copy(), "gen": state["gen"].copy(), "rows": state["rows"].copy(),
+           "best_params": state["best_params"].copy(), "best_fitness": best, "best_generation": state["best_generation"],
+           "take": 1 if take else 0}
+    slot = g % C
+    out["rows"][slot] = (fc, lc, 1.0 if take else 0.0, float(V))
+    out["gen"][slot] = np.uint64(g)
+    if take:
+        out["best_fitness"], out["best_generation"], out["best_params"] = float(fc), g, es_center_ref(theta)
+    return out
+
+
+def es_validation_table_ref(gen, rows):
+    """The ring as ``bsk_es_get_validation_log`` returns it -> ``validation_log``'s dict of numpy arrays over the slots that have
+    been written, sorted by generation: ``generation`` uint64 and ``ES_VAL_COLUMNS`` (float64; ``take`` and ``members`` int64)."""
+    gen = np.asarray(gen, np.uint64).reshape(-1)
+    rows = np.asarray(rows, np.float64).reshape(gen.size, 4)
+    valid = np.flatnonzero(gen != np.uint64(ES_LOG_EMPTY))
+    valid = valid[np.argsort(gen[valid], kind="stable")]
+    out = {"generation": gen[valid].copy()}
+    for c, name in enumerate(ES_VAL_COLUMNS):
+        col = rows[valid, c].copy()
+        out[name] = col.astype(np.int64) if name in ("take", "members") else col
+    return out
+
+
 def shared_slot_ref(n, envs_per_member, epoch, n_pool, env_base=0):
     """The IC-pool slots ``bsk_reset_from_pool_shared`` restarts envs 0 .. n - 1 from -> uint32 (n,): g = (env_base + env) mod 2^32,
     q = g mod envs_per_member, e = epoch mod 2^32, slot = (q * 2654435761 + e * 40503 + 12345) mod 2^32 mod n_pool.  Envs with equal

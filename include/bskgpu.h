@@ -631,8 +631,8 @@ void bsk_es_destroy(bsk_es* es);
  * a different device. */
 int bsk_es_ask(bsk_es* es, bsk_population* pop, void* stream);
 /* Ranks d_fitness (DEVICE memory, f64[n_members]: what bsk_population_rollout's d_fitness holds), moves theta and advances the
- * generation: three launches on `stream` (five with a log, bsk_es_set_log), no copy, no synchronisation; capturable.  BSK_EINVAL
- * for NULL pointers. */
+ * generation: three launches on `stream` (two more with a log, bsk_es_set_log, and two more under bsk_es_set_validation), no copy,
+ * no synchronisation; capturable.  BSK_EINVAL for NULL pointers. */
 int bsk_es_tell(bsk_es* es, const double* d_fitness, void* stream);
 /* theta (host pointer, f64[n_params], or NULL) and the generation counter (or NULL).  Ordered after everything queued on the
  * optimiser's device; synchronises it. */
@@ -774,6 +774,64 @@ int bsk_es_set_best(bsk_es* es, const float* params, const double* fitness, cons
  * copy, no synchronisation.  BSK_EINVAL for NULL pointers and with no log. */
 int bsk_es_best_device(bsk_es* es, const float** d_params);
 
+/* Validation on fixed episodes, inside each generation: how good the CENTRE theta is - what the method deploys - on episodes that
+ * do not change from one generation to the next.  A log row describes the perturbed members on that generation's own episodes,
+ * and the champion above is the maximum of a noisy score over members and generations; neither is a learning curve.  Here the
+ * population gets V more members, P .. P + V - 1, that hold the centre; the handle gets V * E more envs, which the caller restarts
+ * from fixed pool slots (bsk_reset_from_pool_shared with the epoch words below, under a mask); the rollout scores them in the
+ * launches it issues anyway; the ranking, the log, the champion and the update never see them.  Off by default: an optimiser that
+ * never calls bsk_es_set_validation launches the kernels of the definitions above with the arguments it passed before.  f64 + and /
+ * only, every operation rounded on its own, no atomics (basilisk_env_amd/policy_ref.py: es_center_ref and es_validate_ref repeat
+ * it bit for bit).
+ * State with V = n_val members and a ring of C = capacity rows, all in device memory:
+ *     val_epoch uint64[V] = epoch0 + v (mod 2^64), constant until the next bsk_es_set_validation: member P + v's epoch word;
+ *     val_gen uint64[C], all ones;   val_row f64[C][4], zeros;
+ *     the validated champion: val_best_params f32[n_params] in the C-ABI parameter layout (zeros), val_best_fitness f64 (the NaN
+ *                   0x7FF8000000000000), val_best_generation uint64 (all ones);
+ *     one candidate word `take` that the two kernels of tell use between them.
+ * With validation on:
+ * bsk_es_ask takes a population of P + V members of the optimiser's spec (one of P members is BSK_EINVAL; with validation off one
+ *   of P + V is).  The ask kernel of the definitions above writes members 0 .. P - 1 exactly as before - the device layout is
+ *   member-major, it is the same launch on the same pointer - and ONE more launch writes every float of the device blocks of
+ *   members P .. P + V - 1: the plain (float)theta_j of its source element under the gather ask uses, for every j, frozen or not,
+ *   and zero for the padding.  No sigma * 0 is added: a -0.0 in theta stays -0.0.
+ * bsk_es_tell takes d_fitness f64[P + V].  Ranking, log, champion and update read the first P values with the kernels and the
+ *   arguments they have.  Two more launches run IN FRONT of the update, behind the log's two when both are on, so theta and the
+ *   generation word are still the ones ask used.  The first is one thread: g = the generation word, slot = g mod C (of the whole
+ *   64-bit word);
+ *        s = f[P];  for v = 1 .. V - 1 ascending: s = s + f[P + v];  f_c = s / (double)V;
+ *        L_c the same over mean_len[P + v] when d_mean_len is bound, +0.0 otherwise;
+ *        take = f_c is not NaN and (val_best_fitness is NaN or f_c > val_best_fitness) - a tie keeps the older champion, a NaN among
+ *          the V values makes f_c a NaN, which never takes;  when take: val_best_fitness = f_c, val_best_generation = g;
+ *        always: val_row[slot] = {f_c, L_c, take ? 1.0 : 0.0, (double)V}, val_gen[slot] = g, the candidate word = take.
+ *   The second has one thread per parameter j and does nothing unless take; then val_best_params[j] = (float)theta_j, the float the
+ *   members P .. P + V - 1 held.  The kernel boundary orders the two launches, as it does for the log: no atomics, no fence.
+ * The validation members' observations must not enter an attached normalisation (bsk_population_set_obs_stats_members), and their
+ * envs restart under their own mask; a run with validation on then trains bit for bit as the same run with it off.  Under
+ * BSK_POLICY_GREEDY f_c is a deterministic function of theta; BSK_POLICY_SAMPLE still draws per global env index and draw counter.
+ * A validation env that finishes restarts by the per-env rule; its later episodes do not count, as everywhere.
+ * bsk_es_set_validation: n_val in 1..16 with capacity >= 1 allocates (or frees and allocates again) and sets everything above to
+ * its initial value; d_mean_len is DEVICE memory, f64[P + V], or NULL - what bsk_population_rollout's d_mean_len writes; it stays
+ * bound and is the caller's to keep alive.  n_val == 0 turns validation off and frees it.  Synchronises the device.  Theta, the
+ * generation, Adam's state, sigma_vec, the log and the champion are left alone.  BSK_EINVAL before anything else: a NULL
+ * optimiser, n_val outside 0..16, capacity < 1 with n_val > 0; then, as bsk_es_set_log, while the stream of the optimiser's last
+ * ask / tell / bsk_es_apply_obs_norm is being captured (nothing is changed then, and the capture stays valid). */
+int bsk_es_set_validation(bsk_es* es, int n_val, int capacity, uint64_t epoch0, const double* d_mean_len);
+/* The whole ring to host memory: gen uint64[C], rows f64[C][4] (either may be NULL); a slot whose val_gen is all ones has never
+ * been written.  Synchronises the device.  BSK_EINVAL for a NULL optimiser and with validation off. */
+int bsk_es_get_validation_log(bsk_es* es, uint64_t* gen, double* rows);
+/* The validated champion to / from host memory: params f32[n_params], fitness, generation; each may be NULL (get: not asked for;
+ * set: keep).  For a checkpoint that resumes bit for bit.  Synchronise the device.  BSK_EINVAL for a NULL optimiser and with
+ * validation off. */
+int bsk_es_get_validated_best(bsk_es* es, float* params, double* fitness, uint64_t* generation);
+int bsk_es_set_validated_best(bsk_es* es, const float* params, const double* fitness, const uint64_t* generation);
+/* val_best_params as a DEVICE pointer - what bsk_population_set_params_device takes - and the V epoch words as DEVICE words - what
+ * bsk_reset_from_pool_shared takes as d_epoch, d_epochs + v for member P + v.  Read-only for the caller; valid until the next
+ * bsk_es_set_validation or bsk_es_destroy.  No launch, no copy, no synchronisation.  BSK_EINVAL for NULL pointers and with
+ * validation off. */
+int bsk_es_validated_best_device(bsk_es* es, const float** d_params);
+int bsk_es_validation_epochs_device(bsk_es* es, const uint64_t** d_epochs);
+
 /* Running statistics of the five observation rows, formed on the device: what gives a policy its in_scale / in_shift.  Salimans et
  * al. 2017 and ARS V2 (Mania et al. 2018) normalise the observations by the mean and standard deviation of everything the search
  * has seen so far; the sums behind them are a reduction over data that already lies in the handle's observation rows when the
@@ -838,6 +896,11 @@ int bsk_obs_stats_reset(bsk_obs_stats* stats, void* stream);
  * BSK_EINVAL for a NULL population / policy. */
 int bsk_population_set_obs_stats(bsk_population* pop, bsk_obs_stats* stats);
 int bsk_policy_set_obs_stats(bsk_policy* p, bsk_obs_stats* stats);
+/* Only the envs of the first n_counted members of `pop` feed an attached object (default: all n_members): the accumulate launch of
+ * bsk_population_rollout gets n = n_counted * envs_per_member in place of the handle's n_envs, and that is what the capacity is
+ * checked against; the kernels are the same.  With n_counted = P under bsk_es_set_validation the validation members' observations
+ * never enter the normalisation.  BSK_EINVAL for a NULL population and n_counted outside 1..n_members. */
+int bsk_population_set_obs_stats_members(bsk_population* pop, int n_counted);
 /* The normalisation above, straight into the optimiser's device theta[0..9]: ONE launch of five threads on `stream`, no copy, no
  * synchronisation, capturable.  bsk_es_ask writes (float)theta_j of frozen parameters into every member, so the next generation
  * runs normalised with no further call.  BSK_EINVAL before anything is launched: NULL pointers, an optimiser with frozen < 10

@@ -16,6 +16,9 @@
         sigma   `run_generation` of an optimiser created with sigma_adapt="pgpe": a step size per parameter, moved by tell
         log     `run_generation` of an optimiser created with log_capacity=256: two more launches in front of the update, and the
                 rollout also writes the members' mean episode lengths
+        validate `run_generation` of an optimiser created with validation_members=1, on a handle of its own with the envs of one
+                more member (N + N / P spacecraft): V + 1 masked resets in the place of one, the centre's launch behind ask's, two
+                more launches in front of the update
   python tools/es_measure.py kernel [adam | obs | sigma | log]
       per P one warming and three measured generations of `run_generation` (`adam`: of an optimizer="adam" optimiser on shared
       episodes; `obs`: with an `ObsStats` given; `sigma`: of a sigma_adapt="pgpe" optimiser; `log`: of a log_capacity=256
@@ -40,15 +43,20 @@ MEMBERS = (64, 1024)
 GAMMA = 0.99
 
 
+def _env(n, side):
+    from basilisk_env_amd.envs.leoPowerAttitudeVecEnv import LeoPowerAttVecEnv
+    env = LeoPowerAttVecEnv(n, device_reset_pool=4096, device_sampler=True, stream=side.cuda_stream)
+    env.reset_tensors()
+    env.propagator.step(np.zeros(n, np.int32), 1)
+    return env
+
+
 def _setup():
     import torch
     from basilisk_env_amd import policy as P
-    from basilisk_env_amd.envs.leoPowerAttitudeVecEnv import LeoPowerAttVecEnv
     side = torch.cuda.Stream()
-    env = LeoPowerAttVecEnv(N, device_reset_pool=4096, device_sampler=True, stream=side.cuda_stream)
-    env.reset_tensors()
+    env = _env(N, side)
     prop = env.propagator
-    prop.step(np.zeros(N, np.int32), 1)
     spec = P.check_spec((64, 64), "tanh")
     rng = np.random.default_rng(7)
     a, _ = P.layer_shapes(spec)
@@ -60,7 +68,7 @@ def _setup():
 def loop():
     torch, P, side, env, prop, spec, theta = _setup()
     with torch.cuda.stream(side):
-        variants = []
+        variants, val_envs = [], []
         for m in MEMBERS:
             pop = P.PolicyPopulation(spec, n_members=m)
             host = P.EvolutionStrategy(theta, m, sigma=0.1, lr=0.05, seed=1)
@@ -73,6 +81,10 @@ def loop():
             logged = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1, log_capacity=256)
             obs_stats = P.ObsStats(N)
             fit = torch.zeros(m, dtype=torch.float64, device="cuda")
+            # one validation member: the same P and the same envs per member, so one member's envs more on a handle of its own
+            val = P.DeviceEvolutionStrategy(spec, theta, m, sigma=0.1, lr=0.05, seed=1, validation_members=1)
+            val_pop = P.PolicyPopulation(spec, n_members=m + 1)
+            val_envs.append(_env(N + N // m, side))
 
             def host_gen(steps, pop=pop, host=host):
                 pop.set_params(host.ask())
@@ -101,6 +113,9 @@ def loop():
             def log_gen(steps, pop=pop, logged=logged):
                 logged.run_generation(prop, pop, steps, 1, "greedy", GAMMA)
 
+            def validate_gen(steps, val=val, val_pop=val_pop, val_prop=val_envs[-1].propagator):
+                val.run_generation(val_prop, val_pop, steps, 1, "greedy", GAMMA)
+
             rep.run_generation(prop, pop, WARM_T, 1, "greedy", GAMMA)
             prop.sync()
             graph = torch.cuda.CUDAGraph()
@@ -113,7 +128,8 @@ def loop():
 
             variants += [("host   P = %d" % m, host_gen), ("device P = %d" % m, device_gen), ("graph  P = %d" % m, graph_gen),
                          ("rollout P = %d" % m, rollout_gen), ("adam   P = %d" % m, adam_gen), ("shared P = %d" % m, shared_gen),
-                         ("obsnorm P = %d" % m, obsnorm_gen), ("sigma  P = %d" % m, sigma_gen), ("log    P = %d" % m, log_gen)]
+                         ("obsnorm P = %d" % m, obsnorm_gen), ("sigma  P = %d" % m, sigma_gen), ("log    P = %d" % m, log_gen),
+                         ("validate P = %d" % m, validate_gen)]
         res = {name: [] for name, _ in variants}
         for _ in range(ROUNDS):
             for name, run in variants:
@@ -125,6 +141,8 @@ def loop():
                 res[name].append((time.perf_counter() - t0) * 1e6)
         for name, _ in variants:
             print("%-18s us per %d-step generation: %s" % (name, T, ", ".join("%.0f" % x for x in res[name])))
+    for e in val_envs:
+        e.close()
     env.close()
 
 
