@@ -2,7 +2,7 @@
 // interfaces each entry point replaces): the environment handle.  Host side only: handle management, HBM allocation,
 // uploads/downloads, launch geometry.  No CPU compute path exists here by design: without a
 // gfx950 device bsk_create fails with BSK_ENODEV.  (bsk_config.hip: the configuration arithmetic; bsk_capi_policy.hip: policy,
-// population and evolution strategy; bsk_capi.hpp: what the three share.)
+// population and observation statistics; bsk_capi_es.hip: evolution strategy; bsk_capi.hpp: what they share.)
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>

@@ -1,6 +1,7 @@
 // bsk_capi.hpp — what the translation units of the C-ABI share (bsk_capi.hip: the environment handle; bsk_capi_policy.hip: policy,
-// population, evolution strategy; bsk_config.hip: the configuration arithmetic).  Internal: not installed, nothing here is exported -
-// everything that crosses a translation unit lives in bsk::capi, a namespace of hidden visibility.
+// population, observation statistics; bsk_capi_es.hip: evolution strategy - what those two share beyond this: bsk_capi_policy.hpp;
+// bsk_config.hip: the configuration arithmetic).  Internal: not installed, nothing here is exported - everything that crosses a
+// translation unit lives in bsk::capi, a namespace of hidden visibility.
 #pragma once
 #include <hip/hip_runtime.h>
 

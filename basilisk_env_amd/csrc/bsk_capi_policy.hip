@@ -1,94 +1,15 @@
 // bsk_capi_policy.hip — C-ABI of what drives an environment handle from the device: the fused MLP policy (bsk_policy_*), the
-// population of policies (bsk_population_*), the evolution strategy (bsk_es_*) and the running observation statistics that give a
-// policy its input normalisation (bsk_obs_stats_*).  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_policy.hip,
-// bsk_population.hip, bsk_es.hip, bsk_obsstats.hip.
+// population of policies (bsk_population_*) and the running observation statistics that give a policy its input normalisation
+// (bsk_obs_stats_*); the evolution strategy over them (bsk_es_*) is bsk_capi_es.hip, and what the two share bsk_capi_policy.hpp.
+// Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_policy.hip, bsk_population.hip, bsk_obsstats.hip.
 #include <cmath>
 #include <cstring>
-#include <initializer_list>
 
-#include "bsk_capi.hpp"
-#include "bsk_es.hpp"
-#include "bsk_obsstats.hpp"
-#include "bsk_policy.hpp"
-#include "bsk_population.hpp"
+#include "bsk_capi_policy.hpp"
 
 using namespace bsk::capi;
 
-// bsk_obs_stats_*: sums, sums of squares and counts of the observation rows (kernels: bsk_obsstats.hip)
-struct bsk_obs_stats {
-    int device = 0;
-    int n_cap = 0;
-    void* d_block = nullptr;               // ONE allocation of 8-byte words: [part | cnt | tot | tot_n]
-    bsk::ObsStats st = {};
-    size_t words() const { return (size_t)st.waves * 11 + 11; }
-};
-
-namespace {
-
-// What a policy and a population are alike in: n_members parameter blocks of one spec on one device (a policy: one block) and
-// one draw counter for all of them
-struct ParamStore {
-    bsk::PolicyLayout lay;
-    int device = 0;
-    int n_members = 1;
-    float* d_params = nullptr;             // [n_members][lay.n_device]: one device layout of the parameters (bsk_policy.hpp) per member
-    unsigned long long* d_rng = nullptr;   // {seed, draw}: read by sample-mode launches, draw advanced behind each of them
-    bsk_obs_stats* stats = nullptr;        // bsk_*_set_obs_stats: what the rollouts accumulate into; not owned
-    int n_counted = 0;                     // bsk_population_set_obs_stats_members: the envs of the first n_counted members feed `stats`; 0: all
-};
-
-}  // namespace
-
-// bsk_policy_*: the fused MLP policy (kernel and layout: bsk_policy.hip)
-struct bsk_policy : ParamStore {
-    int* d_act = nullptr;                  // bsk_policy_rollout's scratch row of actions (d_action_hist == NULL)
-    int act_cap = 0;
-};
-
-// bsk_population_*: n_members parameter blocks of one spec, member m driving envs [m * E, (m + 1) * E) (bsk_policy.hip,
-// bsk_population.hip)
-struct bsk_population : ParamStore {
-    // bsk_population_rollout's scratch, one allocation sized for the largest handle seen: the running value of every env and a
-    // row of actions (d_action_hist == NULL)
-    void* d_scratch = nullptr;
-    bsk::FitnessAcc acc = {};
-    int* d_act = nullptr;
-    int scratch_cap = 0;
-};
-
-// bsk_es_*: the evolution strategy whose candidates never leave the device (bsk_es.hip)
-struct bsk_es {
-    bsk::PolicyLayout lay;
-    int device = 0;
-    int n_members = 0;
-    double sigma = 0.0, lr = 0.0;
-    int frozen = 0;
-    unsigned long long* d_state = nullptr; // {seed, generation}: generation advanced behind every tell
-    double* d_theta = nullptr;             // [lay.n_params]
-    double* d_w = nullptr;                 // [w | q], n_members / 2 each: bsk_es_tell's scratch, the difference (and, under
-                                           // BSK_ES_SIGMA_PGPE, the sum) of every pair's two utilities
-    // bsk_es_set_optimizer: BSK_ES_SGD until Adam is selected; then ONE allocation [m | v | beta_pow] of 2 * n_params + 2 doubles
-    int optimizer = BSK_ES_SGD;
-    double beta1 = 0.0, beta2 = 0.0, eps = 0.0, weight_decay = 0.0;
-    double* d_adam = nullptr;
-    // bsk_es_set_sigma_adaptation: BSK_ES_SIGMA_FIXED until PGPE is selected; then sigma_vec [n_params]
-    int sigma_kind = BSK_ES_SIGMA_FIXED;
-    double lr_sigma = 0.0, max_change = 0.0, sigma_min = 0.0, sigma_max = 0.0;
-    double* d_sigma = nullptr;
-    // bsk_es_set_log: off until a capacity is given; then ONE allocation of 8-byte words
-    // [log_gen C | log_row 8 C | best_fitness | best_generation | best_member, - | take, b | best_params ceil(n_params / 2)]
-    int log_capacity = 0;
-    unsigned long long* d_log = nullptr;
-    const double* d_mean_len = nullptr;    // the caller's, bound by bsk_es_set_log; may be NULL
-    hipStream_t last_stream = nullptr;     // of the last ask / tell / apply_obs_norm: what bsk_es_set_log asks about a capture
-    // bsk_es_set_validation: off until n_val > 0; then ONE allocation of 8-byte words
-    // [val_epoch V | val_gen C | val_row 4 C | val_best_fitness | val_best_generation | take, - | val_best_params ceil(n_params / 2)]
-    int n_val = 0, val_capacity = 0;
-    unsigned long long* d_val = nullptr;
-    const double* d_val_len = nullptr;     // the caller's, f64[n_members + n_val], bound by bsk_es_set_validation; may be NULL
-};
-
-namespace {
+namespace bsk { namespace capi {
 
 int policy_spec_layout(const bsk_policy_spec* spec, bsk::PolicyLayout& lay) {
     if (!spec) return fail(BSK_EINVAL, "spec is NULL");
@@ -98,29 +19,6 @@ int policy_spec_layout(const bsk_policy_spec* spec, bsk::PolicyLayout& lay) {
     return BSK_OK;
 }
 
-// The create skeleton of the three objects.  Its head: *out = NULL, then the spec's layout ...
-template <class T>
-int create_begin(const bsk_policy_spec* spec, T** out, bsk::PolicyLayout& lay) {
-    if (!out) return fail(BSK_EINVAL, "out is NULL");
-    *out = nullptr;
-    return policy_spec_layout(spec, lay);
-}
-
-// ... and, behind the caller's own argument checks, its tail: admit the device, allocate through `init`, destroy what a failure leaves
-template <class T, class Init>
-int create_on_device(const bsk::PolicyLayout& lay, int device_id, T** out, void (*destroy)(T*), Init init) {
-    int rc = open_device(device_id);
-    if (rc) return rc;
-    DeviceGuard guard(device_id);
-    T* obj = new T();
-    obj->lay = lay;
-    obj->device = device_id;
-    if ((rc = init(obj))) { destroy(obj); return rc; }
-    *out = obj;
-    return BSK_OK;
-}
-
-// The destroy rule: what is queued on the device may still use the buffers - wait for it once if there is any, then free them
 void free_all(std::initializer_list<void*> bufs) {
     bool any = false;
     for (void* b : bufs) any = any || b;
@@ -128,6 +26,19 @@ void free_all(std::initializer_list<void*> bufs) {
     for (void* b : bufs)
         if (b) (void)hipFree(b);
 }
+
+int transfer(int device, hipMemcpyKind dir, std::initializer_list<Field> fields) {
+    DeviceGuard guard(device);
+    const bool get = dir == hipMemcpyDeviceToHost;
+    HIP_SYNC(hipDeviceSynchronize());
+    for (const Field& f : fields)
+        if (f.host) HIP_COPY(hipMemcpy((void*)(get ? f.host : f.dev), get ? f.dev : f.host, f.bytes, dir));
+    return BSK_OK;
+}
+
+} }  // namespace bsk::capi
+
+namespace {
 
 // the parameter blocks (left as allocated) and the draw counter {0, 0}
 int store_alloc(ParamStore* p) {
@@ -186,19 +97,14 @@ int store_upload(ParamStore* p, const float* params) {
 
 int set_rng(ParamStore* p, const char* null_msg, uint64_t seed, uint64_t draw) {
     if (!p) return fail(BSK_EINVAL, null_msg);
-    DeviceGuard guard(p->device);
     const unsigned long long w[2] = {seed, draw};
-    HIP_SYNC(hipDeviceSynchronize());
-    HIP_COPY(hipMemcpy(p->d_rng, w, sizeof w, hipMemcpyHostToDevice));
-    return BSK_OK;
+    return transfer(p->device, hipMemcpyHostToDevice, {{w, p->d_rng, sizeof w}});
 }
 
 int get_rng(ParamStore* p, const char* null_msg, uint64_t* seed, uint64_t* draw) {
     if (!p) return fail(BSK_EINVAL, null_msg);
-    DeviceGuard guard(p->device);
     unsigned long long w[2];
-    HIP_SYNC(hipDeviceSynchronize());
-    HIP_COPY(hipMemcpy(w, p->d_rng, sizeof w, hipMemcpyDeviceToHost));
+    if (int rc = transfer(p->device, hipMemcpyDeviceToHost, {{w, p->d_rng, sizeof w}})) return rc;
     if (seed) *seed = w[0];
     if (draw) *draw = w[1];
     return BSK_OK;
@@ -448,455 +354,6 @@ int bsk_population_rollout(bsk_population* p, bsk_handle* h, int mode, int subst
     return BSK_OK;
 }
 
-int bsk_es_create(const bsk_policy_spec* spec, int n_members, const float* theta, double sigma, double lr, int frozen, uint64_t seed,
-                  int device_id, bsk_es** out) {
-    bsk::PolicyLayout lay;
-    int rc = create_begin(spec, out, lay);
-    if (rc) return rc;
-    if (n_members < 2 || n_members > 65536 || n_members % 2 != 0)
-        return fail(BSK_EINVAL, "bsk_es_create: n_members must be even and in 2..65536 (the ranking compares every pair of members)");
-    if (!std::isfinite(sigma) || !(sigma > 0.0)) return fail(BSK_EINVAL, "bsk_es_create: sigma must be finite and positive");
-    if (!std::isfinite(lr)) return fail(BSK_EINVAL, "bsk_es_create: lr must be finite");
-    if (frozen < 0 || frozen > lay.n_params) return fail(BSK_EINVAL, "bsk_es_create: frozen must be in 0..n_params");
-    return create_on_device(lay, device_id, out, bsk_es_destroy, [&](bsk_es* es) -> int {
-        es->n_members = n_members;
-        es->sigma = sigma;
-        es->lr = lr;
-        es->frozen = frozen;
-        const unsigned long long state0[2] = {seed, 0ull};
-        std::vector<double> theta0((size_t)lay.n_params, 0.0);
-        if (theta)
-            for (int j = 0; j < lay.n_params; ++j) theta0[(size_t)j] = (double)theta[j];
-        HIP_TRY(hipMalloc(&es->d_state, sizeof state0));
-        HIP_TRY(hipMalloc(&es->d_theta, theta0.size() * sizeof(double)));
-        HIP_TRY(hipMalloc(&es->d_w, (size_t)n_members * sizeof(double)));
-        HIP_COPY(hipMemcpy(es->d_state, state0, sizeof state0, hipMemcpyHostToDevice));
-        HIP_COPY(hipMemcpy(es->d_theta, theta0.data(), theta0.size() * sizeof(double), hipMemcpyHostToDevice));
-        return BSK_OK;
-    });
-}
-
-void bsk_es_destroy(bsk_es* es) {
-    if (!es) return;
-    DeviceGuard guard(es->device);
-    free_all({es->d_state, es->d_theta, es->d_w, es->d_adam, es->d_sigma, es->d_log, es->d_val});
-    delete es;
-}
-
-static bsk::EsArgs es_args(const bsk_es* es) {
-    bsk::EsArgs a;
-    a.state = es->d_state;
-    a.theta = es->d_theta;
-    a.sigma = es->sigma;
-    a.frozen = es->frozen;
-    a.pairs = es->n_members / 2;
-    return a;
-}
-
-static bsk::EsSigma es_sigma(const bsk_es* es) {
-    bsk::EsSigma sv;
-    sv.sigma_vec = es->d_sigma;
-    sv.pd = (double)es->n_members;
-    sv.cs = es->lr_sigma / sv.pd;
-    sv.max_change = es->max_change;
-    sv.sigma_min = es->sigma_min;
-    sv.sigma_max = es->sigma_max;
-    return sv;
-}
-
-// the words of the log's allocation and the views of them the kernels take
-static size_t es_log_words(const bsk_es* es, int capacity) { return 9 * (size_t)capacity + 4 + ((size_t)es->lay.n_params + 1) / 2; }
-
-static bsk::EsLog es_log(const bsk_es* es) {
-    const size_t C = (size_t)es->log_capacity;
-    unsigned long long* tail = es->d_log + 9 * C;
-    bsk::EsLog lg;
-    lg.gen = es->d_log;
-    lg.row = (double*)(es->d_log + C);
-    lg.best_fitness = (double*)tail;
-    lg.best_generation = tail + 1;
-    lg.best_member = (int*)(tail + 2);
-    lg.cand = (int*)(tail + 3);
-    lg.best_params = (float*)(tail + 4);
-    lg.mean_len = es->d_mean_len;
-    lg.capacity = es->log_capacity;
-    return lg;
-}
-
-// the words of the validation's allocation and the views of them the kernels take
-static size_t es_val_words(const bsk_es* es, int n_val, int capacity) {
-    return (size_t)n_val + 5 * (size_t)capacity + 3 + ((size_t)es->lay.n_params + 1) / 2;
-}
-
-static bsk::EsVal es_val(const bsk_es* es) {
-    const size_t C = (size_t)es->val_capacity;
-    unsigned long long* ring = es->d_val + (size_t)es->n_val;
-    unsigned long long* tail = ring + 5 * C;
-    bsk::EsVal vl;
-    vl.gen = ring;
-    vl.row = (double*)(ring + C);
-    vl.best_fitness = (double*)tail;
-    vl.best_generation = tail + 1;
-    vl.cand = (int*)(tail + 2);
-    vl.best_params = (float*)(tail + 3);
-    vl.mean_len = es->d_val_len;
-    vl.capacity = es->val_capacity;
-    vl.n_val = es->n_val;
-    return vl;
-}
-
-// (the optimiser serves one stream at a time: the stream of its last launch is the one a capture of its loop records)
-static bool es_stream_capturing(bsk_es* es) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (es->last_stream && hipStreamIsCapturing(es->last_stream, &st) != hipSuccess) {
-        (void)hipGetLastError();                          // (a stream that has been destroyed since captures nothing)
-        st = hipStreamCaptureStatusNone;
-        es->last_stream = nullptr;
-    }
-    return st != hipStreamCaptureStatusNone;
-}
-
-int bsk_es_ask(bsk_es* es, bsk_population* pop, void* stream) {
-    if (!es || !pop) return fail(BSK_EINVAL, "es/population is NULL");
-    if (pop->n_members != es->n_members + es->n_val)
-        return fail(BSK_EINVAL, es->n_val > 0 ? "bsk_es_ask: the population's n_members differs from the optimiser's n_members + n_val (bsk_es_set_validation)"
-                                              : "bsk_es_ask: the population's n_members differs from the optimiser's");
-    if (std::memcmp(&pop->lay, &es->lay, sizeof(bsk::PolicyLayout)) != 0)      // (all-int, value-initialised: policy_layout)
-        return fail(BSK_EINVAL, "bsk_es_ask: the population's spec differs from the optimiser's");
-    if (pop->device != es->device) return fail(BSK_EINVAL, "bsk_es_ask: the optimiser and the population live on different devices");
-    DeviceGuard guard(es->device);
-    es->last_stream = (hipStream_t)stream;
-    if (es->sigma_kind == BSK_ES_SIGMA_PGPE)
-        HIP_TRY(bsk::launch_es_ask_sigma(es->lay, es_args(es), es->d_sigma, pop->d_params, (hipStream_t)stream));
-    else
-        HIP_TRY(bsk::launch_es_ask(es->lay, es_args(es), pop->d_params, (hipStream_t)stream));
-    if (es->n_val > 0)                                    // the centre into the members behind ask's: member-major, so the launch above is the one it was
-        HIP_TRY(bsk::launch_es_center(es->lay, es->d_theta, pop->d_params + (size_t)es->n_members * (size_t)es->lay.n_device, es->n_val,
-                                      (hipStream_t)stream));
-    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
-}
-
-int bsk_es_tell(bsk_es* es, const double* d_fitness, void* stream) {
-    if (!es || !d_fitness) return fail(BSK_EINVAL, "es/d_fitness is NULL");
-    DeviceGuard guard(es->device);
-    const bool pgpe = es->sigma_kind == BSK_ES_SIGMA_PGPE;
-    double* d_q = es->d_w + es->n_members / 2;
-    es->last_stream = (hipStream_t)stream;
-    if (es->log_capacity > 0)                             // in front of the update: theta, sigma_vec and the generation as ask read them
-        HIP_TRY(bsk::launch_es_log(es_args(es), pgpe ? es->d_sigma : nullptr, es->lay.n_params, d_fitness, es_log(es), (hipStream_t)stream));
-    if (es->n_val > 0)                                    // behind the log's two, in front of the update too: f[P .. P + V - 1]
-        HIP_TRY(bsk::launch_es_validate(es_args(es), es->lay.n_params, d_fitness, es_val(es), (hipStream_t)stream));
-    if (pgpe)
-        HIP_TRY(bsk::launch_es_rank_q(d_fitness, es->n_members, es->d_w, d_q, (hipStream_t)stream));
-    else
-        HIP_TRY(bsk::launch_es_rank(d_fitness, es->n_members, es->d_w, (hipStream_t)stream));
-    if (es->optimizer == BSK_ES_ADAM) {
-        const size_t np = (size_t)es->lay.n_params;
-        bsk::EsAdam ad;
-        ad.m = es->d_adam;
-        ad.v = es->d_adam + np;
-        ad.beta_pow = es->d_adam + 2 * np;
-        ad.beta1 = es->beta1; ad.beta2 = es->beta2;
-        ad.a1 = 1.0 - es->beta1; ad.a2 = 1.0 - es->beta2;
-        ad.eps = es->eps; ad.weight_decay = es->weight_decay;
-        ad.cg = 1.0 / ((double)es->n_members * es->sigma);
-        ad.lr = es->lr;
-        if (pgpe)
-            HIP_TRY(bsk::launch_es_tell_adam_sigma(es_args(es), es->lay.n_params, es->d_w, d_q, ad, es_sigma(es), (hipStream_t)stream));
-        else
-            HIP_TRY(bsk::launch_es_tell_adam(es_args(es), es->lay.n_params, es->d_w, ad, (hipStream_t)stream));
-        HIP_TRY(bsk::launch_es_advance_adam(es->d_state, es->d_adam + 2 * np, es->beta1, es->beta2, (hipStream_t)stream));
-        return BSK_OK;
-    }
-    if (pgpe) {
-        HIP_TRY(bsk::launch_es_tell_sigma(es_args(es), es->lay.n_params, es->d_w, d_q, es->lr, es_sigma(es), (hipStream_t)stream));
-    } else {
-        const double c = es->lr / ((double)es->n_members * es->sigma);
-        HIP_TRY(bsk::launch_es_tell(es_args(es), es->lay.n_params, es->d_w, c, (hipStream_t)stream));
-    }
-    HIP_TRY(bsk::launch_es_advance(es->d_state, (hipStream_t)stream));
-    return BSK_OK;
-}
-
-int bsk_es_get_state(bsk_es* es, double* theta, uint64_t* generation) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    DeviceGuard guard(es->device);
-    HIP_SYNC(hipDeviceSynchronize());
-    if (theta) HIP_COPY(hipMemcpy(theta, es->d_theta, (size_t)es->lay.n_params * sizeof(double), hipMemcpyDeviceToHost));
-    if (generation) {
-        unsigned long long w[2];
-        HIP_COPY(hipMemcpy(w, es->d_state, sizeof w, hipMemcpyDeviceToHost));
-        *generation = w[1];
-    }
-    return BSK_OK;
-}
-
-int bsk_es_set_state(bsk_es* es, const double* theta, uint64_t generation) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    DeviceGuard guard(es->device);
-    const unsigned long long g = generation;
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old state)
-    if (theta) HIP_COPY(hipMemcpy(es->d_theta, theta, (size_t)es->lay.n_params * sizeof(double), hipMemcpyHostToDevice));
-    HIP_COPY(hipMemcpy(es->d_state + 1, &g, sizeof g, hipMemcpyHostToDevice));
-    return BSK_OK;
-}
-
-int bsk_es_generation_device(bsk_es* es, const uint64_t** d_generation) {
-    if (!es || !d_generation) return fail(BSK_EINVAL, "es/d_generation is NULL");
-    *d_generation = (const uint64_t*)(es->d_state + 1);
-    return BSK_OK;
-}
-
-int bsk_es_set_optimizer(bsk_es* es, int kind, double beta1, double beta2, double eps, double weight_decay) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (kind != BSK_ES_SGD && kind != BSK_ES_ADAM) return fail(BSK_EINVAL, "bsk_es_set_optimizer: kind must be BSK_ES_SGD or BSK_ES_ADAM");
-    if (kind == BSK_ES_ADAM) {
-        if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
-            return fail(BSK_EINVAL, "bsk_es_set_optimizer: beta1 and beta2 must be in [0, 1)");
-        if (!std::isfinite(eps) || !(eps > 0.0)) return fail(BSK_EINVAL, "bsk_es_set_optimizer: eps must be finite and positive");
-        if (!std::isfinite(weight_decay) || weight_decay < 0.0)
-            return fail(BSK_EINVAL, "bsk_es_set_optimizer: weight_decay must be finite and not negative");
-    }
-    DeviceGuard guard(es->device);
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued tells still use the old rule and the old moments)
-    if (kind == BSK_ES_SGD) {
-        es->optimizer = BSK_ES_SGD;
-        return BSK_OK;
-    }
-    const size_t np = (size_t)es->lay.n_params;
-    if (!es->d_adam) HIP_TRY(hipMalloc(&es->d_adam, (2 * np + 2) * sizeof(double)));
-    const double one[2] = {1.0, 1.0};
-    HIP_TRY(hipMemset(es->d_adam, 0, 2 * np * sizeof(double)));
-    HIP_COPY(hipMemcpy(es->d_adam + 2 * np, one, sizeof one, hipMemcpyHostToDevice));
-    es->optimizer = BSK_ES_ADAM;
-    es->beta1 = beta1; es->beta2 = beta2; es->eps = eps; es->weight_decay = weight_decay;
-    return BSK_OK;
-}
-
-int bsk_es_get_moments(bsk_es* es, double* m, double* v, double* beta_pow) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (es->optimizer != BSK_ES_ADAM) return fail(BSK_EINVAL, "bsk_es_get_moments: the optimiser is BSK_ES_SGD, it has no moments");
-    DeviceGuard guard(es->device);
-    const size_t np = (size_t)es->lay.n_params;
-    HIP_SYNC(hipDeviceSynchronize());
-    if (m) HIP_COPY(hipMemcpy(m, es->d_adam, np * sizeof(double), hipMemcpyDeviceToHost));
-    if (v) HIP_COPY(hipMemcpy(v, es->d_adam + np, np * sizeof(double), hipMemcpyDeviceToHost));
-    if (beta_pow) HIP_COPY(hipMemcpy(beta_pow, es->d_adam + 2 * np, 2 * sizeof(double), hipMemcpyDeviceToHost));
-    return BSK_OK;
-}
-
-int bsk_es_set_moments(bsk_es* es, const double* m, const double* v, const double* beta_pow) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (es->optimizer != BSK_ES_ADAM) return fail(BSK_EINVAL, "bsk_es_set_moments: the optimiser is BSK_ES_SGD, it has no moments");
-    DeviceGuard guard(es->device);
-    const size_t np = (size_t)es->lay.n_params;
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old moments)
-    if (m) HIP_COPY(hipMemcpy(es->d_adam, m, np * sizeof(double), hipMemcpyHostToDevice));
-    if (v) HIP_COPY(hipMemcpy(es->d_adam + np, v, np * sizeof(double), hipMemcpyHostToDevice));
-    if (beta_pow) HIP_COPY(hipMemcpy(es->d_adam + 2 * np, beta_pow, 2 * sizeof(double), hipMemcpyHostToDevice));
-    return BSK_OK;
-}
-
-int bsk_es_set_sigma_adaptation(bsk_es* es, int kind, double lr_sigma, double max_change, double sigma_min, double sigma_max) {
-    const char* const fn = "bsk_es_set_sigma_adaptation: ";
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (kind != BSK_ES_SIGMA_FIXED && kind != BSK_ES_SIGMA_PGPE)
-        return fail(BSK_EINVAL, std::string(fn) + "kind must be BSK_ES_SIGMA_FIXED or BSK_ES_SIGMA_PGPE");
-    if (kind == BSK_ES_SIGMA_PGPE) {
-        if (!std::isfinite(lr_sigma) || lr_sigma < 0.0) return fail(BSK_EINVAL, std::string(fn) + "lr_sigma must be finite and not negative");
-        if (!std::isfinite(max_change) || !(max_change > 0.0 && max_change < 1.0))
-            return fail(BSK_EINVAL, std::string(fn) + "max_change must be inside (0, 1)");
-        if (!std::isfinite(sigma_min) || !(sigma_min > 0.0)) return fail(BSK_EINVAL, std::string(fn) + "sigma_min must be finite and positive");
-        if (!std::isfinite(sigma_max) || sigma_max < sigma_min)
-            return fail(BSK_EINVAL, std::string(fn) + "sigma_max must be finite and not below sigma_min");
-        if (es->sigma < sigma_min || es->sigma > sigma_max)
-            return fail(BSK_EINVAL, std::string(fn) + "the sigma of bsk_es_create must be inside [sigma_min, sigma_max]");
-    }
-    DeviceGuard guard(es->device);
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued asks and tells still use the old rule and the old vector)
-    if (kind == BSK_ES_SIGMA_FIXED) {
-        es->sigma_kind = BSK_ES_SIGMA_FIXED;
-        return BSK_OK;
-    }
-    const size_t np = (size_t)es->lay.n_params;
-    if (!es->d_sigma) HIP_TRY(hipMalloc(&es->d_sigma, np * sizeof(double)));
-    const std::vector<double> fill(np, es->sigma);
-    HIP_COPY(hipMemcpy(es->d_sigma, fill.data(), np * sizeof(double), hipMemcpyHostToDevice));
-    es->sigma_kind = BSK_ES_SIGMA_PGPE;
-    es->lr_sigma = lr_sigma; es->max_change = max_change; es->sigma_min = sigma_min; es->sigma_max = sigma_max;
-    return BSK_OK;
-}
-
-int bsk_es_get_sigma(bsk_es* es, double* sigma) {
-    if (!es || !sigma) return fail(BSK_EINVAL, "es/sigma is NULL");
-    if (es->sigma_kind != BSK_ES_SIGMA_PGPE) return fail(BSK_EINVAL, "bsk_es_get_sigma: the kind is BSK_ES_SIGMA_FIXED, there is no vector");
-    DeviceGuard guard(es->device);
-    HIP_SYNC(hipDeviceSynchronize());
-    HIP_COPY(hipMemcpy(sigma, es->d_sigma, (size_t)es->lay.n_params * sizeof(double), hipMemcpyDeviceToHost));
-    return BSK_OK;
-}
-
-int bsk_es_set_sigma(bsk_es* es, const double* sigma) {
-    if (!es || !sigma) return fail(BSK_EINVAL, "es/sigma is NULL");
-    if (es->sigma_kind != BSK_ES_SIGMA_PGPE) return fail(BSK_EINVAL, "bsk_es_set_sigma: the kind is BSK_ES_SIGMA_FIXED, there is no vector");
-    for (int j = 0; j < es->lay.n_params; ++j)
-        if (!std::isfinite(sigma[j]) || !(sigma[j] > 0.0)) return fail(BSK_EINVAL, "bsk_es_set_sigma: every entry must be finite and positive");
-    DeviceGuard guard(es->device);
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read the old vector)
-    HIP_COPY(hipMemcpy(es->d_sigma, sigma, (size_t)es->lay.n_params * sizeof(double), hipMemcpyHostToDevice));
-    return BSK_OK;
-}
-
-int bsk_es_set_log(bsk_es* es, int capacity, const double* d_mean_len) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (capacity < 0) return fail(BSK_EINVAL, "bsk_es_set_log: capacity must not be negative");
-    DeviceGuard guard(es->device);
-    if (es_stream_capturing(es))
-        return fail(BSK_EINVAL, "bsk_es_set_log: the optimiser's stream is being captured; it allocates and synchronises and cannot be captured");
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued tells still write the old log)
-    if (es->d_log) {
-        (void)hipFree(es->d_log);
-        es->d_log = nullptr;
-    }
-    es->log_capacity = 0;
-    es->d_mean_len = nullptr;
-    if (capacity == 0) return BSK_OK;
-    const size_t C = (size_t)capacity, words = es_log_words(es, capacity);
-    HIP_TRY(hipMalloc(&es->d_log, words * 8));
-    HIP_TRY(hipMemset(es->d_log, 0xff, C * 8));                                    // log_gen: all ones
-    HIP_TRY(hipMemset(es->d_log + C, 0, (words - C) * 8));                           // log_row, best_params, the candidate words
-    const unsigned long long tail[3] = {0x7ff8000000000000ull, ~0ull, 0xffffffffull};   // a NaN, all ones, member -1
-    HIP_COPY(hipMemcpy(es->d_log + 9 * C, tail, sizeof tail, hipMemcpyHostToDevice));
-    es->log_capacity = capacity;
-    es->d_mean_len = d_mean_len;
-    return BSK_OK;
-}
-
-int bsk_es_get_log(bsk_es* es, uint64_t* gen, double* rows) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (es->log_capacity < 1) return fail(BSK_EINVAL, "bsk_es_get_log: the optimiser has no log (bsk_es_set_log)");
-    DeviceGuard guard(es->device);
-    const size_t C = (size_t)es->log_capacity;
-    HIP_SYNC(hipDeviceSynchronize());
-    if (gen) HIP_COPY(hipMemcpy(gen, es->d_log, C * 8, hipMemcpyDeviceToHost));
-    if (rows) HIP_COPY(hipMemcpy(rows, es->d_log + C, 8 * C * 8, hipMemcpyDeviceToHost));
-    return BSK_OK;
-}
-
-int bsk_es_get_best(bsk_es* es, float* params, double* fitness, uint64_t* generation, int32_t* member) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (es->log_capacity < 1) return fail(BSK_EINVAL, "bsk_es_get_best: the optimiser has no log (bsk_es_set_log)");
-    DeviceGuard guard(es->device);
-    const bsk::EsLog lg = es_log(es);
-    HIP_SYNC(hipDeviceSynchronize());
-    if (params) HIP_COPY(hipMemcpy(params, lg.best_params, (size_t)es->lay.n_params * sizeof(float), hipMemcpyDeviceToHost));
-    if (fitness) HIP_COPY(hipMemcpy(fitness, lg.best_fitness, 8, hipMemcpyDeviceToHost));
-    if (generation) HIP_COPY(hipMemcpy(generation, lg.best_generation, 8, hipMemcpyDeviceToHost));
-    if (member) HIP_COPY(hipMemcpy(member, lg.best_member, 4, hipMemcpyDeviceToHost));
-    return BSK_OK;
-}
-
-int bsk_es_set_best(bsk_es* es, const float* params, const double* fitness, const uint64_t* generation, const int32_t* member) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (es->log_capacity < 1) return fail(BSK_EINVAL, "bsk_es_set_best: the optimiser has no log (bsk_es_set_log)");
-    DeviceGuard guard(es->device);
-    const bsk::EsLog lg = es_log(es);
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued tells still read and write the old champion)
-    if (params) HIP_COPY(hipMemcpy(lg.best_params, params, (size_t)es->lay.n_params * sizeof(float), hipMemcpyHostToDevice));
-    if (fitness) HIP_COPY(hipMemcpy(lg.best_fitness, fitness, 8, hipMemcpyHostToDevice));
-    if (generation) HIP_COPY(hipMemcpy(lg.best_generation, generation, 8, hipMemcpyHostToDevice));
-    if (member) HIP_COPY(hipMemcpy(lg.best_member, member, 4, hipMemcpyHostToDevice));
-    return BSK_OK;
-}
-
-int bsk_es_best_device(bsk_es* es, const float** d_params) {
-    if (!es || !d_params) return fail(BSK_EINVAL, "es/d_params is NULL");
-    if (es->log_capacity < 1) return fail(BSK_EINVAL, "bsk_es_best_device: the optimiser has no log (bsk_es_set_log)");
-    *d_params = es_log(es).best_params;
-    return BSK_OK;
-}
-
-int bsk_es_set_validation(bsk_es* es, int n_val, int capacity, uint64_t epoch0, const double* d_mean_len) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (n_val < 0 || n_val > 16) return fail(BSK_EINVAL, "bsk_es_set_validation: n_val must be in 0..16");
-    if (n_val > 0 && capacity < 1) return fail(BSK_EINVAL, "bsk_es_set_validation: capacity must be >= 1");
-    DeviceGuard guard(es->device);
-    if (es_stream_capturing(es))
-        return fail(BSK_EINVAL, "bsk_es_set_validation: the optimiser's stream is being captured; it allocates and synchronises and cannot be captured");
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued asks and tells still use the old state)
-    if (es->d_val) {
-        (void)hipFree(es->d_val);
-        es->d_val = nullptr;
-    }
-    es->n_val = es->val_capacity = 0;
-    es->d_val_len = nullptr;
-    if (n_val == 0) return BSK_OK;
-    const size_t V = (size_t)n_val, C = (size_t)capacity, words = es_val_words(es, n_val, capacity);
-    std::vector<unsigned long long> head(V);
-    for (size_t v = 0; v < V; ++v) head[v] = epoch0 + v;
-    HIP_TRY(hipMalloc(&es->d_val, words * 8));
-    HIP_COPY(hipMemcpy(es->d_val, head.data(), V * 8, hipMemcpyHostToDevice));          // val_epoch
-    HIP_TRY(hipMemset(es->d_val + V, 0xff, C * 8));                                      // val_gen: all ones
-    HIP_TRY(hipMemset(es->d_val + V + C, 0, (words - V - C) * 8));                       // val_row, val_best_params, the candidate word
-    const unsigned long long tail[2] = {0x7ff8000000000000ull, ~0ull};                   // a NaN, all ones
-    HIP_COPY(hipMemcpy(es->d_val + V + 5 * C, tail, sizeof tail, hipMemcpyHostToDevice));
-    HIP_SYNC(hipDeviceSynchronize());
-    es->n_val = n_val;
-    es->val_capacity = capacity;
-    es->d_val_len = d_mean_len;
-    return BSK_OK;
-}
-
-int bsk_es_get_validation_log(bsk_es* es, uint64_t* gen, double* rows) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (es->n_val < 1) return fail(BSK_EINVAL, "bsk_es_get_validation_log: validation is off (bsk_es_set_validation)");
-    DeviceGuard guard(es->device);
-    const bsk::EsVal vl = es_val(es);
-    const size_t C = (size_t)es->val_capacity;
-    HIP_SYNC(hipDeviceSynchronize());
-    if (gen) HIP_COPY(hipMemcpy(gen, vl.gen, C * 8, hipMemcpyDeviceToHost));
-    if (rows) HIP_COPY(hipMemcpy(rows, vl.row, 4 * C * 8, hipMemcpyDeviceToHost));
-    return BSK_OK;
-}
-
-int bsk_es_get_validated_best(bsk_es* es, float* params, double* fitness, uint64_t* generation) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (es->n_val < 1) return fail(BSK_EINVAL, "bsk_es_get_validated_best: validation is off (bsk_es_set_validation)");
-    DeviceGuard guard(es->device);
-    const bsk::EsVal vl = es_val(es);
-    HIP_SYNC(hipDeviceSynchronize());
-    if (params) HIP_COPY(hipMemcpy(params, vl.best_params, (size_t)es->lay.n_params * sizeof(float), hipMemcpyDeviceToHost));
-    if (fitness) HIP_COPY(hipMemcpy(fitness, vl.best_fitness, 8, hipMemcpyDeviceToHost));
-    if (generation) HIP_COPY(hipMemcpy(generation, vl.best_generation, 8, hipMemcpyDeviceToHost));
-    return BSK_OK;
-}
-
-int bsk_es_set_validated_best(bsk_es* es, const float* params, const double* fitness, const uint64_t* generation) {
-    if (!es) return fail(BSK_EINVAL, "es is NULL");
-    if (es->n_val < 1) return fail(BSK_EINVAL, "bsk_es_set_validated_best: validation is off (bsk_es_set_validation)");
-    DeviceGuard guard(es->device);
-    const bsk::EsVal vl = es_val(es);
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued tells still read and write the old champion)
-    if (params) HIP_COPY(hipMemcpy(vl.best_params, params, (size_t)es->lay.n_params * sizeof(float), hipMemcpyHostToDevice));
-    if (fitness) HIP_COPY(hipMemcpy(vl.best_fitness, fitness, 8, hipMemcpyHostToDevice));
-    if (generation) HIP_COPY(hipMemcpy(vl.best_generation, generation, 8, hipMemcpyHostToDevice));
-    return BSK_OK;
-}
-
-int bsk_es_validated_best_device(bsk_es* es, const float** d_params) {
-    if (!es || !d_params) return fail(BSK_EINVAL, "es/d_params is NULL");
-    if (es->n_val < 1) return fail(BSK_EINVAL, "bsk_es_validated_best_device: validation is off (bsk_es_set_validation)");
-    *d_params = es_val(es).best_params;
-    return BSK_OK;
-}
-
-int bsk_es_validation_epochs_device(bsk_es* es, const uint64_t** d_epochs) {
-    if (!es || !d_epochs) return fail(BSK_EINVAL, "es/d_epochs is NULL");
-    if (es->n_val < 1) return fail(BSK_EINVAL, "bsk_es_validation_epochs_device: validation is off (bsk_es_set_validation)");
-    *d_epochs = (const uint64_t*)es->d_val;
-    return BSK_OK;
-}
-
 int bsk_obs_stats_create(int n_cap, int device_id, bsk_obs_stats** out) {
     if (!out) return fail(BSK_EINVAL, "out is NULL");
     *out = nullptr;
@@ -979,33 +436,18 @@ int bsk_obs_stats_totals_device(bsk_obs_stats* s, const double** d_tot10, const 
 
 int bsk_obs_stats_get_state(bsk_obs_stats* s, double* part, uint64_t* cnt) {
     if (!s) return fail(BSK_EINVAL, "stats is NULL");
-    DeviceGuard guard(s->device);
-    HIP_SYNC(hipDeviceSynchronize());
-    if (part) HIP_COPY(hipMemcpy(part, s->st.part, (size_t)s->st.waves * 10 * 8, hipMemcpyDeviceToHost));
-    if (cnt) HIP_COPY(hipMemcpy(cnt, s->st.cnt, (size_t)s->st.waves * 8, hipMemcpyDeviceToHost));
-    return BSK_OK;
+    const size_t W = (size_t)s->st.waves;
+    return transfer(s->device, hipMemcpyDeviceToHost, {{part, s->st.part, W * 10 * 8}, {cnt, s->st.cnt, W * 8}});
 }
 
 int bsk_obs_stats_set_state(bsk_obs_stats* s, const double* part, const uint64_t* cnt) {
     if (!s || !part || !cnt) return fail(BSK_EINVAL, "stats/part/cnt is NULL");
     DeviceGuard guard(s->device);
-    HIP_SYNC(hipDeviceSynchronize());                     // (queued launches still read and write the old state)
-    HIP_COPY(hipMemcpy(s->st.part, part, (size_t)s->st.waves * 10 * 8, hipMemcpyHostToDevice));
-    HIP_COPY(hipMemcpy(s->st.cnt, cnt, (size_t)s->st.waves * 8, hipMemcpyHostToDevice));
+    const size_t W = (size_t)s->st.waves;
+    int rc = transfer(s->device, hipMemcpyHostToDevice, {{part, s->st.part, W * 10 * 8}, {cnt, s->st.cnt, W * 8}});
+    if (rc) return rc;
     HIP_TRY(bsk::launch_obs_stats_join(s->st, nullptr));  // the totals are a function of the partial rows: formed again
     HIP_SYNC(hipDeviceSynchronize());
     return BSK_OK;
-}
-
-int bsk_es_apply_obs_norm(bsk_es* es, bsk_obs_stats* s, double std_min, void* stream) {
-    if (!es || !s) return fail(BSK_EINVAL, "es/stats is NULL");
-    if (es->frozen < 10)
-        return fail(BSK_EINVAL, "bsk_es_apply_obs_norm: frozen must be >= 10 (in_scale and in_shift would be perturbed and moved by the search)");
-    if (!std::isfinite(std_min) || !(std_min > 0.0)) return fail(BSK_EINVAL, "bsk_es_apply_obs_norm: std_min must be finite and positive");
-    if (es->device != s->device) return fail(BSK_EINVAL, "bsk_es_apply_obs_norm: the optimiser and the statistics live on different devices");
-    DeviceGuard guard(es->device);
-    es->last_stream = (hipStream_t)stream;
-    HIP_TRY(bsk::launch_es_obs_norm(s->st.tot, s->st.tot_n, std_min, es->d_theta, (hipStream_t)stream));
-    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
 }
 }  // extern "C"

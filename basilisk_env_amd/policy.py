@@ -16,7 +16,8 @@ and in_shift.
 
 The four are handles of the library and share what such a handle needs (``_DeviceObject``: create, close, the closed-handle
 refusal, ``sync``); the policy and the population are also both parameter stores that act (``_ParamStore``: the draw counter, the
-output buffers and views of ``act``, rollouts with host results) - as ``ParamStore`` is behind the two in csrc/bsk_capi_policy.hip.
+output buffers and views of ``act``, rollouts with host results) - as ``ParamStore`` is behind the two in csrc/bsk_capi_policy.hip;
+``bsk_es_*`` is csrc/bsk_capi_es.hip.
 
 What needs no device lives beside this module and is re-exported here under the names it always had: the argument rules and the
 layout of the parameter block in ``policy_spec`` (``check_spec``, ``pack_params``, ...), and in ``policy_ref`` the numpy
@@ -497,6 +498,14 @@ class PolicyPopulation(_ParamStore):
                                                                             **{"d_" + k: p for k, p in d.items()}))
 
 
+def _refuse_unless_f64(noun, count):
+    """``_device_pointer``'s ``refuse`` for what must be ``count`` contiguous float64; ``noun`` names it in the message."""
+    def refuse(typestr, shape, size, dense):
+        if typestr != "<f8" or size != count or (len(shape) == 1 and not dense):       # (a 1-D array's stride only)
+            return "%s: %d contiguous float64, got %r %r" % (noun, count, typestr, shape)
+    return refuse
+
+
 class DeviceEvolutionStrategy(_DeviceObject):
     """``EvolutionStrategy``'s search with theta, the ranking and the update on the device (``bsk_es_*``): ``ask`` writes the
     ``population`` = P members straight into a ``PolicyPopulation``'s device layout, ``tell`` reads the P float64 fitness values
@@ -519,23 +528,14 @@ class DeviceEvolutionStrategy(_DeviceObject):
     def __init__(self, spec, theta, population, sigma=0.1, lr=0.05, seed=0, frozen=10, device=0, optimizer="sgd", beta1=0.9,
                  beta2=0.999, eps=1e-8, weight_decay=0.0, sigma_adapt=None, lr_sigma=0.1, sigma_max_change=0.2, sigma_min=None,
                  sigma_max=None, log_capacity=0, validation_members=0, validation_capacity=None, validation_epoch=0xFFFFFFFF):
+        # every argument is checked before the handle exists: a bad one leaves none behind
         log_capacity = check_log(log_capacity)
         check_validation(validation_members, validation_capacity, validation_epoch, log_capacity)
-        if optimizer not in ("sgd", "adam"):
-            raise ValueError("optimizer must be 'sgd' or 'adam', got %r" % (optimizer,))
-        if optimizer == "adam":
-            beta1, beta2, eps, weight_decay = check_adam(beta1, beta2, eps, weight_decay)
-        self.optimizer, self.adam = optimizer, (beta1, beta2, eps, weight_decay)
-        if sigma_adapt not in (None, "pgpe"):
-            raise ValueError("sigma_adapt must be None or 'pgpe', got %r" % (sigma_adapt,))
-        if sigma_adapt is not None:
-            sigma_min = 0.01 * float(sigma) if sigma_min is None else sigma_min
-            sigma_max = 10.0 * float(sigma) if sigma_max is None else sigma_max
-            check_sigma_adaptation(lr_sigma, sigma_max_change, sigma_min, sigma_max, sigma)
+        self.optimizer, self.adam = optimizer, self._check_optimizer(optimizer, beta1, beta2, eps, weight_decay)
+        self._check_sigma_adapt(sigma_adapt, lr_sigma, sigma_max_change, sigma_min, sigma_max, sigma)
         self.sigma_adapt, self.sigma_adaptation = None, None
-        self.log_capacity, self._log_len, self._log_source = 0, None, None
-        self.validation_members, self.validation_capacity, self.validation_epoch = 0, 0, 0
-        self._val_len, self._val_source, self._val_masks = None, None, {}
+        self.log_capacity, self.validation_members, self.validation_capacity, self.validation_epoch = 0, 0, 0, 0
+        self._len_ptr, self._len_bound, self._val_masks = None, {}, {}
         self.spec = _as_spec(spec)
         self.n_params = n_params(self.spec)
         self.population, self.sigma, self.lr, self.frozen = int(population), float(sigma), float(lr), int(frozen)
@@ -543,7 +543,7 @@ class DeviceEvolutionStrategy(_DeviceObject):
         t = None if theta is None else _host_block(theta, self.n_params)
         self._create(device, self.population, None if t is None else t.ctypes.data, self.sigma, self.lr, self.frozen, self.seed)
         if optimizer == "adam":
-            self.set_optimizer("adam", beta1, beta2, eps, weight_decay)
+            self.set_optimizer("adam", *self.adam)
         if sigma_adapt is not None:
             self.set_sigma_adaptation(sigma_adapt, lr_sigma, sigma_max_change, sigma_min, sigma_max)
         if log_capacity:
@@ -554,8 +554,14 @@ class DeviceEvolutionStrategy(_DeviceObject):
     def close(self):
         for b in (getattr(self, "_val_masks", None) or {}).values():
             b.free()
-        self._val_masks = {}
+        self._val_masks, self._len_bound = {}, {}
         super(DeviceEvolutionStrategy, self).close()
+
+    def _device_word(self, name):
+        """``bsk_es_<name>_device`` -> a DEVICE pointer into the optimiser's own memory: no launch, no copy, no synchronisation"""
+        p = C.c_void_p()
+        check(self._c(name + "_device")(self._handle(), C.byref(p)))
+        return p.value
 
     # ------------------------------------------------------------------ state
     @property
@@ -579,20 +585,21 @@ class DeviceEvolutionStrategy(_DeviceObject):
 
     def generation_ptr(self):
         """The generation counter as a DEVICE uint64 word, valid until ``close``: the epoch of ``reset_from_pool_shared``."""
-        p = C.c_void_p()
-        check(self._lib.bsk_es_generation_device(self._handle(), C.byref(p)))
-        return p.value
+        return self._device_word("generation")
+
+    @staticmethod
+    def _check_optimizer(optimizer, beta1, beta2, eps, weight_decay):
+        """-> Adam's four arguments: as floats and by ``check_adam``'s rules under ``"adam"``, as they came under ``"sgd"``"""
+        if optimizer not in ("sgd", "adam"):
+            raise ValueError("optimizer must be 'sgd' or 'adam', got %r" % (optimizer,))
+        return check_adam(beta1, beta2, eps, weight_decay) if optimizer == "adam" else (beta1, beta2, eps, weight_decay)
 
     def set_optimizer(self, optimizer, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0):
         """``"adam"``: Adam with an L2 penalty from zero moments (every selection zeroes them); ``"sgd"``: the plain step.  Theta and
         the generation stay; synchronises."""
-        if optimizer not in ("sgd", "adam"):
-            raise ValueError("optimizer must be 'sgd' or 'adam', got %r" % (optimizer,))
-        if optimizer == "adam":
-            beta1, beta2, eps, weight_decay = check_adam(beta1, beta2, eps, weight_decay)
-        check(self._lib.bsk_es_set_optimizer(self._handle(), _lib.ES_ADAM if optimizer == "adam" else _lib.ES_SGD, float(beta1), float(beta2),
-                                             float(eps), float(weight_decay)))
-        self.optimizer, self.adam = optimizer, (float(beta1), float(beta2), float(eps), float(weight_decay))
+        adam = tuple(float(x) for x in self._check_optimizer(optimizer, beta1, beta2, eps, weight_decay))
+        check(self._lib.bsk_es_set_optimizer(self._handle(), _lib.ES_ADAM if optimizer == "adam" else _lib.ES_SGD, *adam))
+        self.optimizer, self.adam = optimizer, adam
 
     @property
     def moments(self):
@@ -607,19 +614,24 @@ class DeviceEvolutionStrategy(_DeviceObject):
                 for a, size in ((m, self.n_params), (v, self.n_params), (beta_pow, 2))]
         check(self._lib.bsk_es_set_moments(self._handle(), *[None if a is None else a.ctypes.data for a in arrs]))
 
-    def set_sigma_adaptation(self, sigma_adapt, lr_sigma=0.1, sigma_max_change=0.2, sigma_min=None, sigma_max=None):
-        """``"pgpe"``: a step size per parameter, every entry started at ``sigma`` (every selection fills the vector again);
-        None: the one ``sigma`` again.  Theta, the generation and Adam's state stay; synchronises."""
+    @staticmethod
+    def _check_sigma_adapt(sigma_adapt, lr_sigma, sigma_max_change, sigma_min, sigma_max, sigma):
+        """-> None, or under ``"pgpe"`` the four arguments of ``bsk_es_set_sigma_adaptation`` by ``check_sigma_adaptation``'s rules,
+        the bounds defaulting to ``sigma`` / 100 and 10 ``sigma``"""
         if sigma_adapt not in (None, "pgpe"):
             raise ValueError("sigma_adapt must be None or 'pgpe', got %r" % (sigma_adapt,))
         if sigma_adapt is None:
-            check(self._lib.bsk_es_set_sigma_adaptation(self._handle(), _lib.ES_SIGMA_FIXED, 0.0, 0.0, 0.0, 0.0))
-            self.sigma_adapt, self.sigma_adaptation = None, None
-            return
-        sigma_min = 0.01 * self.sigma if sigma_min is None else sigma_min
-        sigma_max = 10.0 * self.sigma if sigma_max is None else sigma_max
-        args = check_sigma_adaptation(lr_sigma, sigma_max_change, sigma_min, sigma_max, self.sigma)
-        check(self._lib.bsk_es_set_sigma_adaptation(self._handle(), _lib.ES_SIGMA_PGPE, *args))
+            return None
+        sigma_min = 0.01 * float(sigma) if sigma_min is None else sigma_min
+        sigma_max = 10.0 * float(sigma) if sigma_max is None else sigma_max
+        return check_sigma_adaptation(lr_sigma, sigma_max_change, sigma_min, sigma_max, sigma)
+
+    def set_sigma_adaptation(self, sigma_adapt, lr_sigma=0.1, sigma_max_change=0.2, sigma_min=None, sigma_max=None):
+        """``"pgpe"``: a step size per parameter, every entry started at ``sigma`` (every selection fills the vector again);
+        None: the one ``sigma`` again.  Theta, the generation and Adam's state stay; synchronises."""
+        args = self._check_sigma_adapt(sigma_adapt, lr_sigma, sigma_max_change, sigma_min, sigma_max, self.sigma)
+        kind = _lib.ES_SIGMA_FIXED if args is None else _lib.ES_SIGMA_PGPE
+        check(self._lib.bsk_es_set_sigma_adaptation(self._handle(), kind, *(args or (0.0, 0.0, 0.0, 0.0))))
         self.sigma_adapt, self.sigma_adaptation = sigma_adapt, args
 
     @property
@@ -635,36 +647,48 @@ class DeviceEvolutionStrategy(_DeviceObject):
         s = _host_block(sigma_vec, self.n_params, np.float64, what="values")
         check(self._lib.bsk_es_set_sigma(self._handle(), s.ctypes.data))
 
-    # ------------------------------------------------------------------ the training log and the champion
-    def set_log(self, capacity, mean_len=None):
-        """A ring of ``capacity`` generations and the best member so far, on the device (``bsk_es_set_log``): from now on every
-        ``tell`` writes the generation's row and applies the champion rule in front of its update (``es_log_row_ref``,
-        ``es_best_ref``).  Every call with ``capacity`` > 0 starts from an empty log and no champion; 0 turns both off.
-        ``mean_len``: P float64 in DEVICE memory the length columns are read from - a raw pointer or anything with
-        ``__cuda_array_interface__``, the caller's to keep alive; None: a buffer of the optimiser's own, zeros (so the two columns
-        are +0.0, as with nothing bound) until ``run_generation`` has the rollout write the members' mean episode lengths there.
-        Theta, the generation, Adam's state and the step sizes stay; synchronises, and cannot be captured."""
-        def refuse(typestr, shape, size, dense):
-            if typestr != "<f8" or size != self.members_total or (len(shape) == 1 and not dense):
-                return "mean_len: %d contiguous float64, got %r %r" % (self.members_total, typestr, shape)
-        capacity = check_log(capacity)
-        queued, ptr = self._source, None
-        if capacity and mean_len is not None:
-            ptr, _ = self._device_pointer(mean_len, 8, refuse)
+    # ------------------------------------------------------------------ the one length buffer
+    def _lengths(self, who=None, count=0, mean_len=None, turn_off=None):
+        """The device pointer the length columns read.  There is ONE for the log and the validation, ``_len_ptr``, because the
+        rollout of ``run_generation`` writes one array of mean episode lengths: the optimiser's own buffer (``_own_lengths``), or an
+        array a caller bound - ``_len_bound`` says through which of ``set_log`` / ``set_validation``, and keeps it alive.
+        No argument -> that pointer, None while both are off.  Otherwise ``who`` ("log" | "validation") is being set to read
+        ``count`` lengths (0: off) from ``mean_len`` (None: wherever they are), by these rules: an array given while the other of
+        the two is on must be the one that one reads; validation does not come on beside a log reading a caller's array of P
+        lengths; with nothing given ``who`` reads what the other reads, and with that off the optimiser's own buffer, zeroed (as it
+        is whenever the log comes on reading it).  ``turn_off()``, the caller's call of the library with ``who`` off, runs behind
+        these refusals and before anything is allocated or written here: the refusal under capture comes from the library.
+        -> the pointer ``who`` reads from now on, None: off"""
+        if who is None:
+            return self._len_ptr if self.log_capacity or self.validation_members else None
+        other, other_on = ("validation", self.validation_members) if who == "log" else ("log", self.log_capacity)
+        ptr = None
+        if count and mean_len is not None:
+            queued = self._source
+            ptr, _ = self._device_pointer(mean_len, 8, _refuse_unless_f64("mean_len", count))
             self._source = queued                          # (a queued tell still reads its fitness)
-            if self.validation_members and int(ptr or 0) != self._val_len:
-                raise ValueError("mean_len: while validation is on the log reads the length buffer set_validation bound (the rollout writes one)")
-        if capacity and mean_len is None and self.validation_members and self._val_source is not None:
-            ptr = self._val_len                            # (the array the caller bound there: the rollout writes P + V values into it)
-        # off first: the refusal under capture comes from the library, before anything is allocated or written here
-        check(self._lib.bsk_es_set_log(self._handle(), 0, None))
-        self.log_capacity, self._log_len, self._log_source = 0, None, None
-        if not capacity:
-            return
-        if ptr is None:
+            if other_on and int(ptr or 0) != self._len_ptr:
+                raise ValueError("mean_len: while %s is on the %s reads the length buffer set_%s bound (the rollout writes one)"
+                                 % ("a log" if other == "log" else other, who, other))
+        elif count and who == "validation" and other_on and "log" in self._len_bound:
+            raise ValueError("the log reads an array of P lengths the caller bound, and the rollout will write P + V: turn the log off, "
+                             "give set_validation a mean_len of P + V values, then set_log the same array")
+        turn_off()
+        self._len_bound.pop(who, None)
+        if not count:
+            return None
+        if mean_len is not None:
+            self._len_bound[who] = mean_len                # (every later tell reads it)
+        elif other_on:
+            ptr = self._len_ptr
+        own = (self._out or {}).get("mean_len")
+        if ptr is None or (who == "log" and own is not None and ptr == own.ptr):
             ptr = self._own_lengths()
-        check(self._lib.bsk_es_set_log(self._handle(), capacity, C.c_void_p(int(ptr)) if ptr else None))
-        self.log_capacity, self._log_len, self._log_source = capacity, int(ptr or 0) or None, mean_len      # (every later tell reads it)
+        self._len_ptr = int(ptr or 0) or None
+        return self._len_ptr
+
+    _log_len = property(lambda self: self._len_ptr if self.log_capacity else None)
+    _val_len = property(lambda self: self._len_ptr if self.validation_members else None)
 
     def _own_lengths(self):
         """The optimiser's own length buffer, zeroed -> its pointer: P + ``ES_VAL_MAX_MEMBERS`` float64, so that the log and the
@@ -678,6 +702,39 @@ class DeviceEvolutionStrategy(_DeviceObject):
         with _hip.device_guard(self.device):
             _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(ptr), 0, nbytes, None), "hipMemsetAsync")
         return ptr
+
+    # ------------------------------------------------------------------ the two records: rows and a champion each
+    def _champion(self, name, n_words):
+        """``bsk_es_get_<name>`` -> (params float32 (n_params,), fitness, generation[, member])"""
+        params, words = np.empty(self.n_params, np.float32), (C.c_double(), C.c_uint64(), C.c_int32())[:n_words]
+        check(self._c("get_" + name)(self._handle(), params.ctypes.data, *[C.addressof(x) for x in words]))
+        return (params,) + tuple(x.value for x in words)
+
+    def _set_champion(self, name, params, *words):
+        """``bsk_es_set_<name>``: ``words`` = fitness, generation[, member]; None keeps"""
+        p = None if params is None else _host_block(params, self.n_params)
+        kinds = ((C.c_double, float), (C.c_uint64, int), (C.c_int32, int))
+        words = [None if x is None else ctype(conv(x)) for x, (ctype, conv) in zip(words, kinds)]
+        check(self._c("set_" + name)(self._handle(), None if p is None else p.ctypes.data,
+                                     *[None if x is None else C.addressof(x) for x in words]))
+
+    def set_log(self, capacity, mean_len=None):
+        """A ring of ``capacity`` generations and the best member so far, on the device (``bsk_es_set_log``): from now on every
+        ``tell`` writes the generation's row and applies the champion rule in front of its update (``es_log_row_ref``,
+        ``es_best_ref``).  Every call with ``capacity`` > 0 starts from an empty log and no champion; 0 turns both off.
+        ``mean_len``: P float64 in DEVICE memory the length columns are read from - a raw pointer or anything with
+        ``__cuda_array_interface__``, the caller's to keep alive; None: a buffer of the optimiser's own, zeros (so the two columns
+        are +0.0, as with nothing bound) until ``run_generation`` has the rollout write the members' mean episode lengths there.
+        Theta, the generation, Adam's state and the step sizes stay; synchronises, and cannot be captured."""
+        capacity = check_log(capacity)
+
+        def turn_off():
+            check(self._lib.bsk_es_set_log(self._handle(), 0, None))
+            self.log_capacity = 0
+        ptr = self._lengths("log", self.members_total if capacity else 0, mean_len, turn_off)
+        if capacity:
+            check(self._lib.bsk_es_set_log(self._handle(), capacity, C.c_void_p(ptr) if ptr else None))
+            self.log_capacity = capacity
 
     def training_log(self):
         """The log as a dict of numpy arrays over the generations it holds, sorted by generation (``es_log_table_ref``):
@@ -693,25 +750,16 @@ class DeviceEvolutionStrategy(_DeviceObject):
     def best(self):
         """The champion -> (params float32 (n_params,), fitness, generation, member); (zeros, NaN, ``ES_LOG_EMPTY``, -1) while no
         generation has taken.  Synchronises.  An error with no log."""
-        params, f, g, m = np.empty(self.n_params, np.float32), C.c_double(), C.c_uint64(), C.c_int32()
-        check(self._lib.bsk_es_get_best(self._handle(), params.ctypes.data, C.addressof(f), C.addressof(g), C.addressof(m)))
-        return params, f.value, g.value, m.value
+        return self._champion("best", 3)
 
     def set_best(self, params=None, fitness=None, generation=None, member=None):
         """A new champion, for a checkpoint that resumes bit for bit; None keeps; synchronises.  An error with no log."""
-        p = None if params is None else _host_block(params, self.n_params)
-        f = None if fitness is None else C.c_double(float(fitness))
-        g = None if generation is None else C.c_uint64(int(generation))
-        m = None if member is None else C.c_int32(int(member))
-        check(self._lib.bsk_es_set_best(self._handle(), None if p is None else p.ctypes.data,
-                                        *[None if x is None else C.addressof(x) for x in (f, g, m)]))
+        self._set_champion("best", params, fitness, generation, member)
 
     def best_params_ptr(self):
         """The champion's parameter block as a DEVICE pointer to n_params float32, valid until the next ``set_log`` or ``close``:
         ``pop.set_params_device(es.best_params_ptr(), m, 1)`` loads it into a member with no host in between."""
-        p = C.c_void_p()
-        check(self._lib.bsk_es_best_device(self._handle(), C.byref(p)))
-        return p.value
+        return self._device_word("best")
 
     # ------------------------------------------------------------------ validation on fixed episodes
     @property
@@ -734,33 +782,16 @@ class DeviceEvolutionStrategy(_DeviceObject):
         and update never read their fitness.  Theta, the generation, Adam's state, the step sizes, the log and its champion stay;
         synchronises, and cannot be captured.  ``run_generation`` builds its device masks in the first call after this one."""
         members, capacity, epoch = check_validation(members, capacity, epoch, self.log_capacity)
-        total = self.population + members
 
-        def refuse(typestr, shape, size, dense):
-            if typestr != "<f8" or size != total or (len(shape) == 1 and not dense):
-                return "mean_len: %d contiguous float64, got %r %r" % (total, typestr, shape)
-        queued, ptr = self._source, None
-        if members and mean_len is not None:
-            ptr, _ = self._device_pointer(mean_len, 8, refuse)
-            self._source = queued                          # (a queued tell still reads its fitness)
-            if self.log_capacity and int(ptr or 0) != self._log_len:
-                raise ValueError("mean_len: while a log is on the validation reads the length buffer set_log bound (the rollout writes one)")
-        elif members and self.log_capacity and self._log_source is not None:
-            raise ValueError("the log reads an array of P lengths the caller bound, and the rollout will write P + V: turn the log off, "
-                             "give set_validation a mean_len of P + V values, then set_log the same array")
-        # off first: the refusal under capture comes from the library, before anything is allocated or written here
-        check(self._lib.bsk_es_set_validation(self._handle(), 0, 0, 0, None))
-        for b in self._val_masks.values():
-            b.free()
-        self.validation_members, self.validation_capacity, self.validation_epoch = 0, 0, 0
-        self._val_len, self._val_source, self._val_masks = None, None, {}
-        if not members:
-            return
-        if ptr is None:
-            ptr = self._log_len if self.log_capacity else self._own_lengths()
-        check(self._lib.bsk_es_set_validation(self._handle(), members, capacity, epoch, C.c_void_p(int(ptr)) if ptr else None))
-        self.validation_members, self.validation_capacity, self.validation_epoch = members, capacity, epoch
-        self._val_len, self._val_source = int(ptr or 0) or None, mean_len
+        def turn_off():
+            check(self._lib.bsk_es_set_validation(self._handle(), 0, 0, 0, None))
+            for b in self._val_masks.values():
+                b.free()
+            self.validation_members, self.validation_capacity, self.validation_epoch, self._val_masks = 0, 0, 0, {}
+        ptr = self._lengths("validation", self.population + members if members else 0, mean_len, turn_off)
+        if members:
+            check(self._lib.bsk_es_set_validation(self._handle(), members, capacity, epoch, C.c_void_p(ptr) if ptr else None))
+            self.validation_members, self.validation_capacity, self.validation_epoch = members, capacity, epoch
 
     def validation_log(self):
         """The validation ring as a dict of numpy arrays over the generations it holds, sorted by generation
@@ -775,31 +806,21 @@ class DeviceEvolutionStrategy(_DeviceObject):
     def validated_best(self):
         """The validated champion -> (params float32 (n_params,), fitness, generation): the centre with the best validation score so
         far; (zeros, NaN, ``ES_LOG_EMPTY``) while no generation has taken.  Synchronises.  An error with validation off."""
-        params, f, g = np.empty(self.n_params, np.float32), C.c_double(), C.c_uint64()
-        check(self._lib.bsk_es_get_validated_best(self._handle(), params.ctypes.data, C.addressof(f), C.addressof(g)))
-        return params, f.value, g.value
+        return self._champion("validated_best", 2)
 
     def set_validated_best(self, params=None, fitness=None, generation=None):
         """A new validated champion, for a checkpoint that resumes bit for bit; None keeps; synchronises."""
-        p = None if params is None else _host_block(params, self.n_params)
-        f = None if fitness is None else C.c_double(float(fitness))
-        g = None if generation is None else C.c_uint64(int(generation))
-        check(self._lib.bsk_es_set_validated_best(self._handle(), None if p is None else p.ctypes.data,
-                                                  *[None if x is None else C.addressof(x) for x in (f, g)]))
+        self._set_champion("validated_best", params, fitness, generation)
 
     def validated_best_params_ptr(self):
         """The validated champion's parameter block as a DEVICE pointer to n_params float32, valid until the next ``set_validation``
         or ``close``: what ``pop.set_params_device`` takes."""
-        p = C.c_void_p()
-        check(self._lib.bsk_es_validated_best_device(self._handle(), C.byref(p)))
-        return p.value
+        return self._device_word("validated_best")
 
     def validation_epochs_ptr(self):
         """The V epoch words as a DEVICE pointer to uint64[V], valid until the next ``set_validation`` or ``close``: member P + v's
         ``reset_from_pool_shared`` takes this pointer + 8 v."""
-        p = C.c_void_p()
-        check(self._lib.bsk_es_validation_epochs_device(self._handle(), C.byref(p)))
-        return p.value
+        return self._device_word("validation_epochs")
 
     def _validation_masks(self, n_envs):
         """The device masks of ``run_generation`` for a handle of ``n_envs`` -> pointer to uint8[1 + V][n_envs]: row 0 the envs of
@@ -833,10 +854,7 @@ class DeviceEvolutionStrategy(_DeviceObject):
         """``d_fitness``: P float64 in DEVICE memory (greater is better; P + V while validation is on) - a raw pointer or anything
         with ``__cuda_array_interface__``.  Ranks the first P, moves theta and advances the generation: three launches on
         ``stream``, with a log on two more in front of the update, and with validation on two more behind those."""
-        def refuse(typestr, shape, size, dense):
-            if typestr != "<f8" or size != self.members_total or (len(shape) == 1 and not dense):       # (a 1-D array's stride only)
-                return "device fitness: %d contiguous float64, got %r %r" % (self.members_total, typestr, shape)
-        d_fitness, _ = self._device_pointer(d_fitness, 8, refuse)
+        d_fitness, _ = self._device_pointer(d_fitness, 8, _refuse_unless_f64("device fitness", self.members_total))
         check(self._lib.bsk_es_tell(self._handle(), C.c_void_p(int(d_fitness)) if d_fitness else None, C.c_void_p(int(stream or 0))))
 
     def fitness_buffer(self):
@@ -881,7 +899,7 @@ class DeviceEvolutionStrategy(_DeviceObject):
         fit = self.fitness_buffer()
         stream = prop.stream_ptr()
         V = self.validation_members
-        lengths = {"d_mean_len": self._val_len if V else self._log_len} if self.log_capacity or V else {}
+        lengths = self._lengths()                          # (None with neither the log nor validation on: as not passed)
         if V:
             E = prop.n_envs // self.members_total
             masks = self._validation_masks(prop.n_envs)
@@ -899,7 +917,7 @@ class DeviceEvolutionStrategy(_DeviceObject):
             prop.reset_from_pool_device(None)
         self.ask(pop, stream)
         if obs_stats is None:
-            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr, **lengths)
+            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr, d_mean_len=lengths)
             self.tell(fit.ptr, stream)
             return
         before = getattr(pop, "_stats", None)
@@ -907,7 +925,7 @@ class DeviceEvolutionStrategy(_DeviceObject):
         if V:
             pop.set_obs_stats_members(self.population)
         try:
-            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr, **lengths)
+            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr, d_mean_len=lengths)
         finally:
             if V:
                 pop.set_obs_stats_members(None)

@@ -7,12 +7,12 @@ thread past the members), P = 256 gives every lane two terms; the tanh spec has 
 in the device layout; generation 2^32 + 3 and seed 2^33 + 5 catch a dropped high word.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from _device_bits import build_c_consumer, download as _download, same as _same
 from _policy_bounds import observation_like, seeded_policy
 from basilisk_env_amd import _hip, _lib
 from basilisk_env_amd import policy as P
@@ -24,22 +24,6 @@ pytestmark = pytest.mark.gpu
 
 SEED, LATE = 2 ** 33 + 5, 2 ** 32 + 3
 SPECS = {"relu16": ((16,), "relu", None), "tanh16x32v16": ((16, 32), "tanh", (16,))}
-
-
-def _download(ptr, dtype, count):
-    out = np.empty(count, dtype=dtype)
-    _hip.check(_hip.runtime().hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), out.nbytes, _hip.hipMemcpyDeviceToHost), "hipMemcpy")
-    return out
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 def _members(pop):
@@ -316,13 +300,7 @@ def test_refusals_come_before_any_launch():
 def test_c_consumer_prints_the_python_bindings_theta(tmp_path):
     """tests/c_abi/c_abi_es.c: bsk_es_create / _ask / _tell / _get_state from plain C99 around bsk_population_rollout, two
     generations; its printout equals the Python binding's"""
-    root_dir = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "c_abi_es"
-    libdir = os.path.dirname(_lib.lib_path())
-    rocm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
-    subprocess.check_call(["gcc", "-std=c99", "-O1", "-Wall", "-Werror", "-I", os.path.join(root_dir, "include"),
-                           os.path.join(root_dir, "tests", "c_abi", "c_abi_es.c"), "-L", libdir, "-lbskgpu", "-L", rocm,
-                           "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath," + rocm, "-o", str(exe)])
+    exe = build_c_consumer(tmp_path, "c_abi_es")
     n_members, E = 4, 64
     n = n_members * E
     ic = sample_ic_batch(n, 4, seed=53)

@@ -6,12 +6,12 @@ operation restatement) or against code that already ships - no tolerance anywher
 pair (63 empty lanes), P = 130 has one lane with two terms and a ranking thread past the members, P = 256 gives every lane two.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from _device_bits import build_c_consumer, download as _download, same as _same
 from _policy_bounds import seeded_policy
 from basilisk_env_amd import _hip, _lib
 from basilisk_env_amd import policy as P
@@ -24,22 +24,6 @@ pytestmark = pytest.mark.gpu
 SEED, LATE = 2 ** 33 + 5, 2 ** 32 + 3
 BETA1, BETA2, EPS = 0.9, 0.999, 1e-8
 N_POOL = 41
-
-
-def _download(ptr, dtype, count):
-    out = np.empty(count, dtype=dtype)
-    _hip.check(_hip.runtime().hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), out.nbytes, _hip.hipMemcpyDeviceToHost), "hipMemcpy")
-    return out
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 def _fitness_cases(n_members, rng):
@@ -264,13 +248,7 @@ def test_refusals_come_before_any_launch():
 def test_c_consumer_prints_the_python_bindings_adam_state(tmp_path):
     """tests/c_abi/c_abi_es_adam.c: bsk_es_set_optimizer / bsk_es_generation_device / bsk_reset_from_pool_shared / bsk_es_get_moments
     from plain C99, two generations on a 128-env handle; its hex-float printout equals the Python binding's"""
-    root_dir = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "c_abi_es_adam"
-    libdir = os.path.dirname(_lib.lib_path())
-    rocm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
-    subprocess.check_call(["gcc", "-std=c99", "-O1", "-Wall", "-Werror", "-I", os.path.join(root_dir, "include"),
-                           os.path.join(root_dir, "tests", "c_abi", "c_abi_es_adam.c"), "-L", libdir, "-lbskgpu", "-L", rocm,
-                           "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath," + rocm, "-o", str(exe)])
+    exe = build_c_consumer(tmp_path, "c_abi_es_adam")
     n_members, n = 2, 128                                   # (a member drives a multiple of 64 envs)
     E = n // n_members
     pool = sample_ic_batch(N_POOL, 4, seed=53)

@@ -14,8 +14,9 @@ import ctypes
 import numpy as np
 import pytest
 
+from _device_bits import bits as _bits, download as _download, same as _same
 from _policy_bounds import seeded_policy
-from basilisk_env_amd import _hip, _lib
+from basilisk_env_amd import _lib
 from basilisk_env_amd import policy as P
 from basilisk_env_amd._lib import FLAG_AUTO_RESET, GRAV_PM_J2
 from basilisk_env_amd.simulators.dynamics import BatchedPropagator, default_config
@@ -31,22 +32,6 @@ ADAM = dict(optimizer="adam", beta1=BETA1, beta2=BETA2, eps=EPS, weight_decay=WD
 NAN = float("nan")
 SUMS = (2, 3, 6)
 N_POOL = 41
-
-
-def _download(ptr, dtype, count):
-    out = np.empty(count, dtype=dtype)
-    _hip.check(_hip.runtime().hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), out.nbytes, _hip.hipMemcpyDeviceToHost), "hipMemcpy")
-    return out
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 def _same_rows(got, want):

@@ -13,12 +13,12 @@ ranking and one validation member, P = 130 with V = 3 gives the one-wave reducti
 v more than one term; seed 2^33 + 5 and generation 2^32 + 3 catch a dropped high word.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from _device_bits import bits as _bits, build_c_consumer, download as _download, same as _same
 from _policy_bounds import seeded_policy
 from basilisk_env_amd import _hip, _lib
 from basilisk_env_amd import policy as P
@@ -39,22 +39,6 @@ ADAM = dict(optimizer="adam", beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-
 RULES = {"sgd-fixed": {}, "adam-fixed": ADAM, "sgd-pgpe": PGPE, "adam-pgpe": dict(ADAM, **PGPE)}
 NAN, INF = float("nan"), float("inf")
 N_POOL, E, T, K, GAMMA = 41, 64, 6, 2, 0.97
-
-
-def _download(ptr, dtype, count):
-    out = np.empty(count, dtype=dtype)
-    _hip.check(_hip.runtime().hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), out.nbytes, _hip.hipMemcpyDeviceToHost), "hipMemcpy")
-    return out
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 def _same_or_nan(a, b):
@@ -109,10 +93,10 @@ def _assert_validation_is(es, ref, where=""):
     assert generation == ref["best_generation"], where
 
 
-def _propagator(n, ic, pool, stream=None):
+def _propagator(n, ic, pool, stream=None, max_length=4):
     cfg = default_config(4, GRAV_PM_J2)
     cfg.flags |= FLAG_AUTO_RESET
-    cfg.max_length = 4
+    cfg.max_length = max_length
     p = BatchedPropagator(cfg, n, stream=stream)
     p.set_ic_pool(pool)
     p.reset(np.ascontiguousarray(ic[:, :n]))
@@ -507,16 +491,135 @@ def test_what_is_refused_leaves_everything_as_it_was():
         x.close()
 
 
+def _small_world(members):
+    """P = 2 training members and ``members`` - 2 validation members of relu16, E = 64 envs each, episodes at most 6 long
+    -> (spec, theta0, propagator, population)"""
+    spec, theta0 = seeded_policy((16,), "relu", None, seed=POLICY_SEED["relu16"])
+    pool, ic = sample_ic_batch(N_POOL, 4, seed=15), sample_ic_batch(members * E, 4, seed=29)
+    return spec, theta0, _propagator(members * E, ic, pool, max_length=6), P.PolicyPopulation(spec, n_members=members)
+
+
+def _records(es):
+    """everything the two records hold -> dict of arrays"""
+    out = {"theta": es.theta}
+    out.update(("log." + k, v) for k, v in es.training_log().items())
+    out.update(("val." + k, v) for k, v in es.validation_log().items())
+    out.update(zip(("best.params", "best.fitness", "best.generation", "best.member"), (np.asarray(x) for x in es.best)))
+    out.update(zip(("vbest.params", "vbest.fitness", "vbest.generation"), (np.asarray(x) for x in es.validated_best)))
+    return out
+
+
+def test_log_and_validation_bind_one_length_buffer_in_either_order():
+    """The log's length columns and the validation's read ONE device buffer - the rollout writes one - whichever of the two is
+    turned on first, and whether the buffer is the optimiser's own or an array the caller bound; and the two call sequences that
+    would leave them on two buffers are refused, with the optimiser left as it was."""
+    import torch
+    n_members, n_val, T_, K_ = 2, 1, 4, 1
+    arr = torch.zeros(n_members + n_val, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    orders = {"log-val": lambda es: (es.set_log(4), es.set_validation(1)),
+              "val-log": lambda es: (es.set_validation(1), es.set_log(4)),
+              "val(arr)-log": lambda es: (es.set_validation(1, mean_len=arr), es.set_log(4))}
+    worlds, got = {}, {}
+    for name, turn_on in orders.items():
+        spec, theta0, prop, pop = _small_world(n_members + n_val)
+        es = _make(spec, theta0, n_members, "sgd-fixed")
+        turn_on(es)
+        assert es.log_capacity == 4 and es.validation_members == n_val and es.validation_capacity == (4 if name == "log-val" else 64)
+        for _ in range(2):
+            es.run_generation(prop, pop, T_, K_, "greedy", GAMMA, shared_episodes=True)
+        prop.sync()
+        worlds[name], got[name] = (prop, pop, es), _records(es)
+    want = got["log-val"]
+    assert want["log.generation"].tolist() == [0, 1] and want["val.generation"].tolist() == [0, 1]
+    assert np.isfinite(want["log.best"]).all() and np.isfinite(want["val.fitness"]).all() and (want["log.len_sum"] >= n_members).all()
+    for name in ("val-log", "val(arr)-log"):
+        assert sorted(got[name]) == sorted(want)
+        for key in want:
+            assert _same(got[name][key], want[key]), (name, key)
+    # the caller's array holds the lengths of the last generation: what the log's row summed and what the centre's row holds
+    es = worlds["val(arr)-log"][2]
+    lens = arr.cpu().numpy()
+    fit = _download(es.fitness_buffer().ptr, np.float64, n_members + n_val)
+    row = P.es_log_row_ref(fit[:n_members], lens[:n_members])
+    assert (lens >= 1.0).all() and (lens <= T_).all()
+    assert _same(row[6], want["log.len_sum"][1]) and _same(row[7], want["log.best_len"][1]) and _same(lens[n_members], want["val.mean_len"][1])
+    # refused: another array for the log while validation is on; everything stays, and the next generation runs
+    prop, pop, es = worlds["log-val"]
+    other = torch.zeros(n_members + n_val, dtype=torch.float64, device="cuda")
+    with pytest.raises(ValueError) as e:
+        es.set_log(4, mean_len=other)
+    assert str(e.value) == "mean_len: while validation is on the log reads the length buffer set_validation bound (the rollout writes one)"
+    _assert_same_training(_records(es), want, "refused set_log")
+    es.run_generation(prop, pop, T_, K_, "greedy", GAMMA, shared_episodes=True)
+    prop.sync()
+    assert es.generation == 3 and es.training_log()["generation"].tolist() == [0, 1, 2] and es.validation_log()["generation"].tolist() == [0, 1, 2]
+    # refused: validation beside a log that reads a caller's array of P lengths; the log goes on as it was
+    spec, theta0, prop2, pop2 = _small_world(n_members)
+    es2 = _make(spec, theta0, n_members, "sgd-fixed")
+    arr_p = torch.zeros(n_members, dtype=torch.float64, device="cuda")
+    es2.set_log(4, mean_len=arr_p)
+    with pytest.raises(ValueError) as e:
+        es2.set_validation(1)
+    assert str(e.value) == ("the log reads an array of P lengths the caller bound, and the rollout will write P + V: turn the log off, "
+                            "give set_validation a mean_len of P + V values, then set_log the same array")
+    assert es2.log_capacity == 4 and es2.validation_members == 0 and es2.members_total == n_members
+    es2.run_generation(prop2, pop2, T_, K_, "greedy", GAMMA, shared_episodes=True)
+    prop2.sync()
+    lens_p = arr_p.cpu().numpy()
+    table = es2.training_log()
+    assert es2.generation == 1 and table["generation"].tolist() == [0] and (lens_p >= 1.0).all()
+    assert _same(np.float64(lens_p[0] + lens_p[1]), table["len_sum"][0])
+    for world in list(worlds.values()) + [(prop2, pop2, es2)]:
+        _close(*world)
+
+
+def test_the_two_records_move_through_their_accessors_alike():
+    """get -> a fresh optimiser -> set -> get, for the log's champion and the validated one: every field's bits come back; the
+    device pointers into the optimiser are four different words; and every accessor of a record that is off says so by its own
+    name, before anything is copied or waited for."""
+    n_members, n_val = 2, 1
+    spec, theta0, prop, pop = _small_world(n_members + n_val)
+    es = _make(spec, theta0, n_members, "sgd-fixed", log_capacity=4, validation_members=n_val)
+    fresh = _make(spec, theta0, n_members, "sgd-fixed", log_capacity=4, validation_members=n_val)
+    es.run_generation(prop, pop, 4, 1, "greedy", GAMMA, shared_episodes=True)
+    prop.sync()
+    for get, put, empty in ((lambda o: o.best, lambda o, x: o.set_best(*x), P.es_champion_empty(theta0.size)),
+                            (lambda o: o.validated_best, lambda o, x: o.set_validated_best(*x), P.es_champion_empty(theta0.size)[:3])):
+        champion, before = get(es), get(fresh)
+        assert len(champion) == len(before) == len(empty)
+        for x, y in zip(before, empty):
+            assert _same_or_nan(np.asarray(x), np.asarray(y))
+        assert champion[0].any() and np.isfinite(champion[1]) and champion[2] == 0 and (len(champion) == 3 or champion[3] in (0, 1))
+        put(fresh, champion)
+        for x, y in zip(get(fresh), champion):
+            assert type(x) is type(y) and _same(np.asarray(x), np.asarray(y))
+    # (the rows stay where they were: a champion is no row)
+    assert fresh.training_log()["generation"].size == 0 and fresh.validation_log()["generation"].size == 0
+    ptrs = [es.best_params_ptr(), es.validated_best_params_ptr(), es.validation_epochs_ptr(), es.generation_ptr()]
+    assert all(ptrs) and len(set(ptrs)) == 4
+    assert _same(_download(ptrs[0], np.float32, theta0.size), es.best[0]) and _same(_download(ptrs[1], np.float32, theta0.size), es.validated_best[0])
+    off = _make(spec, theta0, n_members, "sgd-fixed")
+    no_log, no_val = "the optimiser has no log (bsk_es_set_log)", "validation is off (bsk_es_set_validation)"
+    refusals = [(off.training_log, "bsk_es_get_log", no_log), (lambda: off.best, "bsk_es_get_best", no_log),
+                (lambda: off.set_best(fitness=1.0), "bsk_es_set_best", no_log), (off.best_params_ptr, "bsk_es_best_device", no_log),
+                (off.validation_log, "bsk_es_get_validation_log", no_val), (lambda: off.validated_best, "bsk_es_get_validated_best", no_val),
+                (lambda: off.set_validated_best(fitness=1.0), "bsk_es_set_validated_best", no_val),
+                (off.validated_best_params_ptr, "bsk_es_validated_best_device", no_val),
+                (off.validation_epochs_ptr, "bsk_es_validation_epochs_device", no_val)]
+    c0 = BatchedPropagator.debug_counters()
+    for call, fn, why in refusals:
+        with pytest.raises(_lib.BskError) as e:
+            call()
+        assert e.value.code == -1 and str(e.value) == "libbskgpu error -1: %s: %s" % (fn, why)
+    assert BatchedPropagator.debug_counters() == c0
+    _close(prop, pop, es, fresh, off)
+
+
 def test_c_consumer_prints_the_python_bindings_validation(tmp_path):
     """tests/c_abi/c_abi_es_validation.c: bsk_es_set_validation and its accessors from plain C99, two generations with one
     validation member beside two training members; its hex-float printout equals the Python binding's"""
-    root_dir = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "c_abi_es_validation"
-    libdir = os.path.dirname(_lib.lib_path())
-    rocm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
-    subprocess.check_call(["gcc", "-std=c99", "-O1", "-Wall", "-Werror", "-I", os.path.join(root_dir, "include"),
-                           os.path.join(root_dir, "tests", "c_abi", "c_abi_es_validation.c"), "-L", libdir, "-lbskgpu", "-L", rocm,
-                           "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath," + rocm, "-o", str(exe)])
+    exe = build_c_consumer(tmp_path, "c_abi_es_validation")
     n_members, n_val = 2, 1
     n = (n_members + n_val) * E
     pool = sample_ic_batch(N_POOL, 4, seed=53)

@@ -12,6 +12,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from _device_bits import download as _download, same as _same
 from _policy_bounds import seeded_policy
 from basilisk_env_amd import _hip, _lib
 from basilisk_env_amd import policy as P
@@ -22,26 +23,10 @@ from basilisk_env_amd.simulators.initial_conditions.batch import sample_ic_batch
 pytestmark = pytest.mark.gpu
 
 
-def _download(ptr, dtype, count):
-    out = np.empty(count, dtype=dtype)
-    _hip.check(_hip.runtime().hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), out.nbytes, _hip.hipMemcpyDeviceToHost), "hipMemcpy")
-    return out
-
-
 def _upload(buf, arr):
     arr = np.ascontiguousarray(arr)
     assert arr.nbytes <= buf.nbytes
     _hip.check(_hip.runtime().hipMemcpy(ctypes.c_void_p(buf.ptr), ctypes.c_void_p(arr.ctypes.data), arr.nbytes, _hip.hipMemcpyHostToDevice), "hipMemcpy")
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 def _block(rng, n):

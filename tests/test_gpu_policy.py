@@ -8,11 +8,11 @@ such a bound (two logits closer than twice the bound, u within delta of a CDF bo
 0.1 % of the spacecraft; the shares are printed.  Closed loops (bsk_policy_rollout, LeoPowerAttVecEnv.step_policy) are compared with
 a host-driven loop that reads the observation back, chooses with act_ref and steps with those actions.
 """
-import ctypes
 
 import numpy as np
 import pytest
 
+from _device_bits import download as _download
 from _policy_bounds import centred, mlp_bound, observation_like, reset_observations, seeded_policy, softmax_bound
 from basilisk_env_amd import _hip, _lib
 from basilisk_env_amd import policy as P
@@ -25,12 +25,6 @@ pytestmark = pytest.mark.gpu
 FULL = FLAG_POWER | FLAG_SUN_THIRD_BODY | FLAG_DRAG | FLAG_DESAT
 SIZES = (1, 63, 64, 65, 777, 65536 + 77)
 CAP = 1e-3            # at most 0.1 % of the spacecraft may fall inside a bound's either-way zone
-
-
-def _download(ptr, dtype, count):
-    out = np.empty(count, dtype=dtype)
-    _hip.check(_hip.runtime().hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), out.nbytes, _hip.hipMemcpyDeviceToHost), "hipMemcpy")
-    return out
 
 
 def _host(view, sync):

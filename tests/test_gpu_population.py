@@ -11,12 +11,12 @@ P = 3 / E = 64 (one workgroup per member), P = 2 / E = 128 (two) and P = 5 / E =
 random parameters, so a wrong block cannot pass.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from _device_bits import build_c_consumer, download as _download, same as _same
 from _policy_bounds import centred, observation_like, reset_observations, seeded_policy
 from basilisk_env_amd import _hip, _lib
 from basilisk_env_amd import policy as P
@@ -29,23 +29,6 @@ pytestmark = pytest.mark.gpu
 FULL = FLAG_POWER | FLAG_SUN_THIRD_BODY | FLAG_DRAG | FLAG_DESAT
 HIST = (("obs", 40, np.float64, 5), ("reward", 8, np.float64, 1), ("reason", 1, np.uint8, 1), ("action", 4, np.int32, 1),
         ("logp", 4, np.float32, 1), ("value", 4, np.float32, 1))
-
-
-def _download(ptr, dtype, count):
-    out = np.empty(count, dtype=dtype)
-    _hip.check(_hip.runtime().hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), out.nbytes, _hip.hipMemcpyDeviceToHost), "hipMemcpy")
-    return out
-
-
-def _bits(a):
-    """a float array as integers: equality of bits, NaN payloads and signed zeros included"""
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 def _members(n_members, hidden, activation, value_hidden, seed, centre=False):
@@ -551,13 +534,7 @@ def test_two_evolution_strategy_generations_are_reproducible():
 def test_c_consumer_prints_the_python_bindings_fitness(tmp_path):
     """tests/c_abi/c_abi_population.c: bsk_population_create / _rollout / _set_params_device from plain C99; its printout equals the
     Python binding's"""
-    root_dir = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "c_abi_population"
-    libdir = os.path.dirname(_lib.lib_path())
-    rocm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
-    subprocess.check_call(["gcc", "-std=c99", "-O1", "-Wall", "-Werror", "-I", os.path.join(root_dir, "include"),
-                           os.path.join(root_dir, "tests", "c_abi", "c_abi_population.c"), "-L", libdir, "-lbskgpu", "-L", rocm,
-                           "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath," + rocm, "-o", str(exe)])
+    exe = build_c_consumer(tmp_path, "c_abi_population")
     n_members, E = 3, 64
     n = n_members * E
     ic = sample_ic_batch(n, 4, seed=53)
