@@ -67,6 +67,7 @@ POLICY_RELU, POLICY_TANH = 0, 1
 POLICY_GREEDY, POLICY_SAMPLE = 0, 1
 ES_SGD, ES_ADAM = 0, 1
 ES_SIGMA_FIXED, ES_SIGMA_PGPE = 0, 1
+BSK_OUTCOME_COLS = 11         # doubles per member row of bsk_population_set_outcomes (tests/test_outcomes_host.py reads the header)
 
 
 class BskPolicySpec(C.Structure):
@@ -87,6 +88,7 @@ EXPORTS = [
     "bsk_policy_act", "bsk_policy_rollout",
     "bsk_population_create", "bsk_population_destroy", "bsk_population_set_rng", "bsk_population_get_rng", "bsk_population_set_params",
     "bsk_population_set_params_device", "bsk_population_get_member", "bsk_population_act", "bsk_population_rollout",
+    "bsk_population_set_outcomes", "bsk_es_set_outcome_log", "bsk_es_get_outcome_log",
     "bsk_es_create", "bsk_es_destroy", "bsk_es_ask", "bsk_es_tell", "bsk_es_get_state", "bsk_es_set_state",
     "bsk_es_generation_device", "bsk_es_set_optimizer", "bsk_es_get_moments", "bsk_es_set_moments",
     "bsk_es_set_sigma_adaptation", "bsk_es_get_sigma", "bsk_es_set_sigma",
@@ -150,6 +152,8 @@ def _signatures():
         "bsk_es_get_validated_best": ([vp, vp, vp, vp], rc), "bsk_es_set_validated_best": ([vp, vp, vp, vp], rc),
         "bsk_es_validated_best_device": ([vp, P(vp)], rc), "bsk_es_validation_epochs_device": ([vp, P(vp)], rc),
         "bsk_population_set_obs_stats_members": ([vp, i], rc),
+        "bsk_population_set_outcomes": ([vp, vp], rc), "bsk_es_set_outcome_log": ([vp, i, vp], rc),
+        "bsk_es_get_outcome_log": ([vp, vp, vp], rc),
         "bsk_obs_stats_create": ([i, i, P(vp)], rc), "bsk_obs_stats_destroy": ([vp], None),
         "bsk_obs_stats_accumulate": ([vp, vp, i64, i, vp, vp], rc), "bsk_obs_stats_get": ([vp, P(u64), vp, vp], rc),
         "bsk_obs_stats_totals_device": ([vp, P(vp), P(vp)], rc), "bsk_obs_stats_get_state": ([vp, vp, vp], rc),

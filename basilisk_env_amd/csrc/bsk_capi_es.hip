@@ -1,6 +1,6 @@
 // bsk_capi_es.hip — C-ABI of the evolution strategy whose candidates never leave the device (bsk_es_*): ask into a population's
-// parameter blocks, tell from a rollout's fitness, the optimiser and step-size rules, and the two records a tell keeps - the
-// training log and the validation of the centre.  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_es.hip.
+// parameter blocks, tell from a rollout's fitness, the optimiser and step-size rules, and the three records a tell keeps - the
+// training log, the validation of the centre and the ring of episode outcomes.  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_es.hip.
 // The population and the observation statistics it reads through their handles: bsk_capi_policy.hpp.
 #include <cmath>
 #include <cstring>
@@ -12,30 +12,34 @@ using namespace bsk::capi;
 
 namespace {
 
-// The training log (bsk_es_set_log) and the validation (bsk_es_set_validation) are one shape, a ring of per-generation rows
-// and a champion in ONE allocation of 8-byte words:
+// The training log (bsk_es_set_log), the validation (bsk_es_set_validation) and the outcome ring (bsk_es_set_outcome_log) are one
+// shape, a ring of per-generation rows and - the first two - a champion behind it, in ONE allocation of 8-byte words:
 //   [head | gen C | row width * C | best_fitness | best_generation | best_member, - (log only) | cand | best_params ceil(n_params / 2)]
-// head: the validation's V epoch words, none for the log; cand: the two ints the first launch of a record leaves for its
-// second.  What is empty says so by the same sentinels in both: generation words all ones, a NaN fitness, zeroed parameters.
+// head: the validation's V epoch words, none for the others; cand: the two ints the first launch of a record leaves for its
+// second.  What is empty says so by the same sentinels in all: generation words all ones, a NaN fitness, zeroed parameters.
 struct EsRecord {
-    const int width;                       // doubles per row: 8 of the log, 4 of the validation
-    const bool member;                     // the champion has a member word (started at -1)
+    const int width;                       // doubles per row: 8 of the log, 4 of the validation, 3 * BSK_OUTCOME_COLS of the outcomes
+    const int champion;                    // 8-byte words of the champion in front of its parameters: 4 with a member word
+                                           // (started at -1; the log), 3 without (the validation), 0: the ring alone
     const char* const off;                 // what an accessor of a record that is off answers, behind its own name
     int head = 0, capacity = 0;            // capacity 0: off, and nothing below is there
     unsigned long long* d = nullptr;
-    const double* d_len = nullptr;         // the caller's, bound by the setter: what the length columns read; may be NULL
+    const double* d_src = nullptr;         // the caller's, bound by the setter: what the record's kernel reads beside the fitness -
+                                           // the mean lengths (may be NULL), the outcome ring's member rows
 
+    // the ring is the base shape of all three; the champion is a tail behind it whose length is formed here and nowhere else
+    size_t tail_words(int n_params) const { return champion ? (size_t)champion + ((size_t)n_params + 1) / 2 : 0; }
     size_t words(int head_, int capacity_, int n_params) const {
-        return (size_t)head_ + (size_t)(1 + width) * (size_t)capacity_ + (member ? 4 : 3) + ((size_t)n_params + 1) / 2;
+        return (size_t)head_ + (size_t)(1 + width) * (size_t)capacity_ + tail_words(n_params);
     }
     unsigned long long* gen() const { return d + head; }
     double* row() const { return (double*)(gen() + capacity); }
     unsigned long long* tail() const { return gen() + (size_t)(1 + width) * (size_t)capacity; }
     double* best_fitness() const { return (double*)tail(); }
     unsigned long long* best_generation() const { return tail() + 1; }
-    int* best_member() const { return (int*)(tail() + 2); }                   // (member only)
-    int* cand() const { return (int*)(tail() + (member ? 3 : 2)); }
-    float* best_params() const { return (float*)(tail() + (member ? 4 : 3)); }
+    int* best_member() const { return (int*)(tail() + 2); }                   // (champion == 4 only)
+    int* cand() const { return (int*)(tail() + champion - 1); }
+    float* best_params() const { return (float*)(tail() + champion); }
 };
 
 }  // namespace
@@ -61,13 +65,16 @@ struct bsk_es {
     double* d_sigma = nullptr;
     // bsk_es_set_log: off until a capacity is given; then ONE allocation of 8-byte words
     // [log_gen C | log_row 8 C | best_fitness | best_generation | best_member, - | take, b | best_params ceil(n_params / 2)]
-    EsRecord log = {8, true, ": the optimiser has no log (bsk_es_set_log)"};
+    EsRecord log = {8, 4, ": the optimiser has no log (bsk_es_set_log)"};
     hipStream_t last_stream = nullptr;     // of the last ask / tell / apply_obs_norm: what bsk_es_set_log asks about a capture
     // bsk_es_set_validation: off until n_val > 0; then ONE allocation of 8-byte words
     // [val_epoch V | val_gen C | val_row 4 C | val_best_fitness | val_best_generation | take, - | val_best_params ceil(n_params / 2)]
-    // and d_len the caller's f64[n_members + n_val]
-    EsRecord val = {4, false, ": validation is off (bsk_es_set_validation)"};
+    // and d_src the caller's f64[n_members + n_val]
+    EsRecord val = {4, 3, ": validation is off (bsk_es_set_validation)"};
     int n_val() const { return val.head; } // (the V epoch words are what stands in front of the validation's ring)
+    // bsk_es_set_outcome_log: off until a capacity is given; then ONE allocation of 8-byte words [out_gen C | out_row 33 C], and
+    // d_src the caller's member rows f64[n_members + n_val][BSK_OUTCOME_COLS]
+    EsRecord outcome = {3 * BSK_OUTCOME_COLS, 0, ": the outcome ring is off (bsk_es_set_outcome_log)"};
 };
 
 namespace {
@@ -117,7 +124,7 @@ View record_view(const EsRecord& r) {
     v.best_generation = r.best_generation();
     v.cand = r.cand();
     v.best_params = r.best_params();
-    v.mean_len = r.d_len;
+    v.mean_len = r.d_src;
     v.capacity = r.capacity;
     return v;
 }
@@ -132,6 +139,16 @@ bsk::EsVal es_val(const bsk_es* es) {
     bsk::EsVal vl = record_view<bsk::EsVal>(es->val);
     vl.n_val = es->val.head;
     return vl;
+}
+
+bsk::EsOutcome es_outcome(const bsk_es* es) {
+    bsk::EsOutcome oc;
+    oc.gen = es->outcome.gen();
+    oc.row = es->outcome.row();
+    oc.rows = es->outcome.d_src;
+    oc.capacity = es->outcome.capacity;
+    oc.n_val = es->n_val();
+    return oc;
 }
 
 // (the optimiser serves one stream at a time: the stream of its last launch is the one a capture of its loop records)
@@ -156,20 +173,20 @@ int record_off(bsk_es* es, EsRecord& r, const char* fn) {
         r.d = nullptr;
     }
     r.head = r.capacity = 0;
-    r.d_len = nullptr;
+    r.d_src = nullptr;
     return BSK_OK;
 }
 
 // ... and then, for a capacity: the allocation in its empty state - generation words all ones, rows, parameters and candidate
-// words zero, the champion a NaN of generation all ones (and member -1).  The head words are left to the caller, and so is
-// turning the record on (head, capacity, d_len) once everything has succeeded.
+// words zero, the champion (where the record has one) a NaN of generation all ones (and member -1).  The head words are left to the caller, and so is
+// turning the record on (head, capacity, d_src) once everything has succeeded.
 int record_alloc(EsRecord& r, int head, int capacity, int n_params) {
     const size_t H = (size_t)head, C = (size_t)capacity, words = r.words(head, capacity, n_params);
     HIP_TRY(hipMalloc(&r.d, words * 8));
     HIP_TRY(hipMemset(r.d + H, 0xff, C * 8));
     HIP_TRY(hipMemset(r.d + H + C, 0, (words - H - C) * 8));
     const unsigned long long tail[3] = {0x7ff8000000000000ull, ~0ull, 0xffffffffull};
-    HIP_COPY(hipMemcpy(r.d + H + (size_t)(1 + r.width) * C, tail, (r.member ? 3 : 2) * 8, hipMemcpyHostToDevice));
+    if (r.champion) HIP_COPY(hipMemcpy(r.d + H + (size_t)(1 + r.width) * C, tail, (size_t)(r.champion - 1) * 8, hipMemcpyHostToDevice));
     return BSK_OK;
 }
 
@@ -240,7 +257,7 @@ int bsk_es_create(const bsk_policy_spec* spec, int n_members, const float* theta
 void bsk_es_destroy(bsk_es* es) {
     if (!es) return;
     DeviceGuard guard(es->device);
-    free_all({es->d_state, es->d_theta, es->d_w, es->d_adam, es->d_sigma, es->log.d, es->val.d});
+    free_all({es->d_state, es->d_theta, es->d_w, es->d_adam, es->d_sigma, es->log.d, es->val.d, es->outcome.d});
     delete es;
 }
 
@@ -277,6 +294,8 @@ int bsk_es_tell(bsk_es* es, const double* d_fitness, void* stream) {
     if (es->log.capacity > 0) HIP_TRY(bsk::launch_es_log(a, pgpe ? es->d_sigma : nullptr, np, d_fitness, es_log(es), s));
     // the validation, behind the log's two launches and in front of the update too: f[P .. P + V - 1]
     if (es->n_val() > 0) HIP_TRY(bsk::launch_es_validate(a, np, d_fitness, es_val(es), s));
+    // the outcome ring, in front of the update too: its own launch, reading the member rows the rollout left
+    if (es->outcome.capacity > 0) HIP_TRY(bsk::launch_es_outcome(a, d_fitness, es_outcome(es), s));
     // the ranking of the first P; a step size per parameter wants the sum of every pair's utilities beside their difference
     if (pgpe) HIP_TRY(bsk::launch_es_rank_q(d_fitness, P, d_w, d_q, s));
     else      HIP_TRY(bsk::launch_es_rank(d_fitness, P, d_w, s));
@@ -409,7 +428,7 @@ int bsk_es_set_log(bsk_es* es, int capacity, const double* d_mean_len) {
     if (rc || capacity == 0) return rc;
     if ((rc = record_alloc(es->log, 0, capacity, es->lay.n_params))) return rc;
     es->log.capacity = capacity;
-    es->log.d_len = d_mean_len;
+    es->log.d_src = d_mean_len;
     return BSK_OK;
 }
 
@@ -427,10 +446,26 @@ int bsk_es_set_validation(bsk_es* es, int n_val, int capacity, uint64_t epoch0, 
     HIP_SYNC(hipDeviceSynchronize());                     // (its own too: the caller's next reset reads the epoch words from any stream)
     es->val.head = n_val;
     es->val.capacity = capacity;
-    es->val.d_len = d_mean_len;
+    es->val.d_src = d_mean_len;
     return BSK_OK;
 }
 
+int bsk_es_set_outcome_log(bsk_es* es, int capacity, const double* d_rows) {
+    if (!es) return fail(BSK_EINVAL, "es is NULL");
+    if (capacity < 0) return fail(BSK_EINVAL, "bsk_es_set_outcome_log: capacity must not be negative");
+    if (capacity > 0 && !d_rows) return fail(BSK_EINVAL, "bsk_es_set_outcome_log: d_rows is NULL");
+    DeviceGuard guard(es->device);
+    int rc = record_off(es, es->outcome, "bsk_es_set_outcome_log");
+    if (rc || capacity == 0) return rc;
+    if ((rc = record_alloc(es->outcome, 0, capacity, 0))) return rc;        // (no champion: no parameters to hold)
+    es->outcome.capacity = capacity;
+    es->outcome.d_src = d_rows;
+    return BSK_OK;
+}
+
+int bsk_es_get_outcome_log(bsk_es* es, uint64_t* gen, double* rows) {
+    return record_get_rows(es, &bsk_es::outcome, "bsk_es_get_outcome_log", gen, rows);
+}
 int bsk_es_get_log(bsk_es* es, uint64_t* gen, double* rows) { return record_get_rows(es, &bsk_es::log, "bsk_es_get_log", gen, rows); }
 int bsk_es_get_validation_log(bsk_es* es, uint64_t* gen, double* rows) {
     return record_get_rows(es, &bsk_es::val, "bsk_es_get_validation_log", gen, rows);

@@ -137,10 +137,11 @@ struct RolloutHist {
 // The closed loop of both rollouts, enqueued on the handle's stream with no host visit in between.  Per env step: the actions of the
 // current observations (into row t of the action history, or into d_act where none is kept), the step on them, and row t of the
 // other histories - with one step of the value rule in the SAME launch where `acc` is given, alone otherwise (no launch for no row).
+// `out` (with `acc` only): the outcome rule in that launch too, on the action row of this step.
 // With a statistics object attached, the observations each launch of the policy reads are accumulated in front of it - under `acc`
 // those of the envs still alive, as the previous step's launch of the value rule left them - and joined once behind the last step.
 int rollout_steps(ParamStore* p, int envs_per_member, bsk_handle* h, int mode, int substeps, int n_steps, const RolloutHist& hist,
-                  int32_t* d_act, const bsk::FitnessAcc* acc, double gamma) {
+                  int32_t* d_act, const bsk::FitnessAcc* acc, double gamma, const bsk::OutcomeAcc* out = nullptr) {
     const size_t n = (size_t)h->n;
     const int n_stats = envs_per_member > 0 && p->n_counted > 0 ? p->n_counted * envs_per_member : h->n;     // (<= h->n: n_counted <= n_members)
     for (int t = 0; t < n_steps; ++t) {
@@ -154,7 +155,10 @@ int rollout_steps(ParamStore* p, int envs_per_member, bsk_handle* h, int mode, i
         double* obs_row = hist.obs ? hist.obs + t * 5 * n : nullptr;
         double* reward_row = hist.reward ? hist.reward + t * n : nullptr;
         uint8_t* reason_row = hist.reason ? hist.reason + t * n : nullptr;
-        if (acc)
+        if (acc && out)
+            HIP_TRY(bsk::launch_outcome_row(h->d_obs, h->d_reward, h->d_reason, act, h->ostride, h->n, obs_row, reward_row, reason_row, *acc,
+                                            *out, gamma, t == 0, h->stream));
+        else if (acc)
             HIP_TRY(bsk::launch_fitness_row(h->d_obs, h->d_reward, h->d_reason, h->ostride, h->n, obs_row, reward_row, reason_row, *acc,
                                             gamma, t == 0, h->stream));
         else
@@ -267,7 +271,7 @@ int bsk_population_create(const bsk_policy_spec* spec, int n_members, const floa
 void bsk_population_destroy(bsk_population* p) {
     if (!p) return;
     DeviceGuard guard(p->device);
-    free_all({p->d_params, p->d_rng, p->d_scratch});
+    free_all({p->d_params, p->d_rng, p->d_scratch, p->d_out_scratch});
     delete p;
 }
 
@@ -297,6 +301,11 @@ int bsk_population_get_member(bsk_population* p, int member, float* params) {
     return BSK_OK;
 }
 int bsk_population_set_obs_stats(bsk_population* p, bsk_obs_stats* stats) { return attach_stats(p, "population is NULL", stats); }
+int bsk_population_set_outcomes(bsk_population* p, double* d_rows) {
+    if (!p) return fail(BSK_EINVAL, "population is NULL");
+    p->d_outcomes = d_rows;
+    return BSK_OK;
+}
 int bsk_population_set_obs_stats_members(bsk_population* p, int n_counted) {
     if (!p) return fail(BSK_EINVAL, "population is NULL");
     if (n_counted < 1 || n_counted > p->n_members) return fail(BSK_EINVAL, "bsk_population_set_obs_stats_members: n_counted must be in 1..n_members");
@@ -346,11 +355,26 @@ int bsk_population_rollout(bsk_population* p, bsk_handle* h, int mode, int subst
         p->acc.alive = (unsigned char*)at;
         p->scratch_cap = h->n;
     }
-    // the history rows and the value rule in ONE launch; with no fitness output asked for, the rows alone (or nothing)
+    const bool outcomes = p->d_outcomes != nullptr;
+    if (outcomes && p->out_cap < h->n) {
+        const size_t n = (size_t)h->n;
+        rc = grow_scratch(&p->d_out_scratch, &p->out_cap, n * (3 * 4 + 1), h->stream,
+                          "bsk_population_rollout: the first rollout of a size with outcome rows attached allocates their accumulators "
+                          "and cannot be captured; make one such call outside the capture first");
+        if (rc) return rc;
+        p->out.act_n = (int*)p->d_out_scratch;
+        p->out.end_reason = (unsigned char*)p->d_out_scratch + n * 3 * 4;
+        p->out_cap = h->n;
+    }
+    // the history rows and the value rule in ONE launch; with no fitness output asked for and no outcome rows attached, the rows
+    // alone (or nothing)
     const bool want_fitness = d_env_value || d_env_len || d_fitness || d_mean_len;
     const RolloutHist hist = {d_obs_hist, d_reward_hist, d_reason_hist, d_action_hist, d_logp_hist, d_value_hist};
-    if ((rc = rollout_steps(p, E, h, mode, substeps, n_steps, hist, p->d_act, want_fitness ? &p->acc : nullptr, gamma))) return rc;
+    rc = rollout_steps(p, E, h, mode, substeps, n_steps, hist, p->d_act, want_fitness || outcomes ? &p->acc : nullptr, gamma,
+                       outcomes ? &p->out : nullptr);
+    if (rc) return rc;
     HIP_TRY(bsk::launch_fitness_join(p->acc, p->n_members, E, d_env_value, d_env_len, d_fitness, d_mean_len, h->stream));
+    if (outcomes) HIP_TRY(bsk::launch_outcome_join(p->acc, p->out, p->n_members, E, p->d_outcomes, h->stream));
     return BSK_OK;
 }
 

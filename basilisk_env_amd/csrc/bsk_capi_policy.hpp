@@ -88,4 +88,10 @@ struct bsk_population : bsk::capi::ParamStore {
     bsk::FitnessAcc acc = {};
     int* d_act = nullptr;
     int scratch_cap = 0;
+    // bsk_population_set_outcomes: the caller's rows (NULL: off), and the second accumulator set - its own allocation, made by the
+    // first rollout of a size that has rows attached
+    double* d_outcomes = nullptr;
+    void* d_out_scratch = nullptr;
+    bsk::OutcomeAcc out = {};
+    int out_cap = 0;
 };

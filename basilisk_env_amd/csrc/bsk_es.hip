@@ -9,6 +9,7 @@
 //                      BSK_ES_SIGMA_PGPE: a step size per parameter in device memory, moved by lane 0 behind a second sum
 //   es_log_kernel, es_best_kernel     bsk_es_set_log: one wave for the generation's row and the champion rule, then one thread per
 //                      parameter for the champion's floats - in front of the update, from what ask read
+//   es_outcome_kernel  bsk_es_set_outcome_log: one wave for the generation's row of episode outcomes - in front of the update too
 //   es_center_kernel, es_validate_kernel, es_val_best_kernel     bsk_es_set_validation: the centre into the V members behind
 //                      ask's, then one thread for the centre's row and the validated champion's rule and one thread per parameter
 //                      for its floats - in front of the update too
@@ -18,6 +19,7 @@
 // es_tell_pgpe_ref).
 #include "bsk_es.hpp"
 
+#include "../../include/bskgpu.h"
 #include "bsk_philox.hpp"
 #include "bsk_tree.hpp"
 
@@ -402,6 +404,74 @@ hipError_t launch_es_log(const EsArgs& es, const double* sigma_vec, int n_params
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(es_best_kernel, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, s, es, sigma_vec, n_params, lg);
+    return hipGetLastError();
+}
+
+// One block of the outcome row (include/bskgpu.h, bsk_es_set_outcome_log): the totals over the `count` member rows from R on.  Lane l
+// walks rows l, l + 64, ... ascending: the eight counts as integers, column 8 in the library's one order (from the first element,
+// +0.0 with none), columns 9 and 10 under extreme_pick from the NaN that stands for "no member".  With count == 0 (validation off;
+// wave-uniform) every entry is +0.0.
+__device__ __forceinline__ void es_outcome_totals(const double* __restrict__ R, int count, int lane, double* __restrict__ dst) {
+#pragma clang fp contract(off)
+    if (count < 1) {
+        if (lane < BSK_OUTCOME_COLS) dst[lane] = 0.0;
+        return;
+    }
+    long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double sq = 0.0, lo = __longlong_as_double(0x7ff8000000000000ll), hi = lo;
+    for (int k = lane; k < count; k += 64) {
+        const double* r = R + (size_t)k * BSK_OUTCOME_COLS;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) cnt[c] += (long long)r[c];
+        sq = k == lane ? r[8] : sq + r[8];
+        lo = extreme_pick<false>(lo, r[9]);
+        hi = extreme_pick<true>(hi, r[10]);
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) cnt[c] = count_tree(cnt[c], lane);
+    sq = fitness_tree(sq, lane);
+    lo = extreme_tree<false>(lo, lane);
+    hi = extreme_tree<true>(hi, lane);
+    if (lane != 0) return;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) dst[c] = (double)cnt[c];
+    dst[8] = sq;
+    dst[9] = lo;
+    dst[10] = hi;
+}
+
+// The outcome ring: ONE wave in front of the update.  Block A the totals over the P ranked members, block B the row of the member
+// nobody beats under es_beats - found here from the fitness, as es_log_kernel finds it, and not read from the log's candidate words:
+// the two records do not know each other - block C the totals over the V validation members.  It writes row g mod capacity of its
+// own ring and nothing else.
+__global__ __launch_bounds__(64) void es_outcome_kernel(const unsigned long long* __restrict__ state, const double* __restrict__ fitness,
+                                                        int P, const EsOutcome oc) {
+#pragma clang fp contract(off)
+    const int lane = (int)threadIdx.x;
+    const unsigned long long g = state[1];
+    const unsigned long long slot = g % (unsigned long long)oc.capacity;
+    double* row = oc.row + (size_t)(3 * BSK_OUTCOME_COLS) * slot;
+    es_outcome_totals(oc.rows, P, lane, row);
+    es_outcome_totals(oc.rows + (size_t)P * BSK_OUTCOME_COLS, oc.n_val, lane, row + 2 * BSK_OUTCOME_COLS);
+    double bf = 0.0;
+    int bi = -1;
+    for (int k = lane; k < P; k += 64) {
+        const double f = fitness[k];
+        if (bi < 0 || es_beats(f, k, bf, bi)) { bf = f; bi = k; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double obf = __shfl_down(bf, off, 64);
+        const int obi = __shfl_down(bi, off, 64);
+        if (obi >= 0 && (bi < 0 || es_beats(obf, obi, bf, bi))) { bf = obf; bi = obi; }
+    }
+    const int b = __shfl(bi, 0, 64);
+    if (lane < BSK_OUTCOME_COLS) row[BSK_OUTCOME_COLS + lane] = oc.rows[(size_t)b * BSK_OUTCOME_COLS + lane];
+    if (lane == 0) oc.gen[slot] = g;
+}
+
+hipError_t launch_es_outcome(const EsArgs& es, const double* fitness, const EsOutcome& oc, hipStream_t s) {
+    hipLaunchKernelGGL(es_outcome_kernel, dim3(1), dim3(64), 0, s, es.state, fitness, 2 * es.pairs, oc);
     return hipGetLastError();
 }
 

@@ -60,6 +60,15 @@ struct EsVal {
     int n_val;
 };
 
+// bsk_es_set_outcome_log: the ring of what the members did (one allocation of the optimiser's) and the member rows it is formed from
+struct EsOutcome {
+    unsigned long long* gen;           // [capacity], the generation each row belongs to (all ones: never written)
+    double* row;                       // [capacity][3 * BSK_OUTCOME_COLS]: the P ranked members' totals | the first-ranked member's row | the V validation members' totals
+    const double* rows;                // [n_members + n_val][BSK_OUTCOME_COLS]: the caller's, bound by bsk_es_set_outcome_log
+    int capacity;
+    int n_val;
+};
+
 // The members of this generation into d_params ([2 * pairs][lay.n_device], a population's device layout): one launch, every
 // float written exactly once.
 hipError_t launch_es_ask(const PolicyLayout& lay, const EsArgs& es, float* d_params, hipStream_t s);
@@ -85,6 +94,9 @@ hipError_t launch_es_center(const PolicyLayout& lay, const double* theta, float*
 // ... and the two launches in front of the update, behind the log's: fitness f64[n_members + n_val], the centre's row and the
 // champion rule on one thread, then the validated champion's floats
 hipError_t launch_es_validate(const EsArgs& es, int n_params, const double* fitness, const EsVal& vl, hipStream_t s);
+// The outcome ring: ONE wave in front of the update, beside the log's launches - it reads the generation word, fitness f64[n_members]
+// and the member rows, and writes its own ring only
+hipError_t launch_es_outcome(const EsArgs& es, const double* fitness, const EsOutcome& oc, hipStream_t s);
 // generation += 1 and beta_pow *= {beta1, beta2}, one thread, behind launch_es_tell_adam on the same stream
 hipError_t launch_es_advance_adam(unsigned long long* state, double* beta_pow, double beta1, double beta2, hipStream_t s);
 // generation += 1, one thread, behind a tell on the same stream (a replayed graph moves on to the next generation)

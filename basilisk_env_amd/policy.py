@@ -23,7 +23,8 @@ What needs no device lives beside this module and is re-exported here under the 
 layout of the parameter block in ``policy_spec`` (``check_spec``, ``pack_params``, ...), and in ``policy_ref`` the numpy
 restatements the kernels are held to bit for bit (``mlp_ref`` / ``act_ref``: every layer output one k-ordered chain of f32 fused
 multiply-adds from the bias; ``population_fitness_ref``; ``es_noise_ref`` / ``es_ask_ref`` / ``es_tell_ref`` /
-``es_tell_adam_ref`` / ``es_ask_sigma_ref`` / ``es_tell_pgpe_ref`` / ``es_log_row_ref`` / ``es_best_ref`` / ``es_center_ref`` / ``es_validate_ref``; ``obs_stats_accumulate_ref`` / ``obs_stats_totals_ref`` / ``obs_norm_ref``) with ``EvolutionStrategy``, the host-side loop the device one was modelled on.
+``es_tell_adam_ref`` / ``es_ask_sigma_ref`` / ``es_tell_pgpe_ref`` / ``es_log_row_ref`` / ``es_best_ref`` / ``es_center_ref`` / ``es_validate_ref``;
+``population_outcomes_ref`` / ``es_outcome_row_ref``; ``obs_stats_accumulate_ref`` / ``obs_stats_totals_ref`` / ``obs_norm_ref``) with ``EvolutionStrategy``, the host-side loop the device one was modelled on.
 """
 import ctypes as C
 import sys
@@ -36,12 +37,15 @@ from .policy_ref import (ES_LOG_COLUMNS, ES_LOG_EMPTY, ES_VAL_COLUMNS, ES_VAL_MA
                          _es_pair_sums, _series_log, act_ref,
                          centred_ranks, check_adam, check_log, check_validation,
                          es_ask_ref, es_ask_sigma_ref, es_best_ref, es_center_ref, es_champion_empty, es_inverse_normal_ref, es_log_order_ref,
-                         es_log_row_ref, es_log_slot_ref, es_log_table_ref, es_noise_ref, es_tell_adam_ref, es_tell_pgpe_ref,
+                         es_log_row_ref, es_log_slot_ref, es_log_table_ref, es_noise_ref, es_outcome_row_ref, es_outcome_table_ref,
+                         es_tell_adam_ref, es_tell_pgpe_ref,
                          es_tell_ref, es_uniform_ref, es_validate_ref, es_validation_state, es_validation_table_ref, fma32,
                          mlp_ref, obs_moments_ref, obs_norm_ref, obs_stats_accumulate_ref, obs_stats_totals_ref,
-                         obs_stats_zero_state, philox4x32_10, population_fitness_ref, sample_uniform, shared_slot_ref, softmax_ref)
-from .policy_spec import (ACTIVATIONS, MAX_HIDDEN_LAYERS, MODES, POLICY_GREEDY, POLICY_RELU, POLICY_SAMPLE,  # noqa: F401
-                          POLICY_TANH, BskPolicySpec, Spec, _as_spec, c_spec, check_sigma_adaptation, check_spec, layer_shapes,
+                         obs_stats_zero_state, outcome_table_ref, philox4x32_10, population_fitness_ref, population_outcomes_ref, sample_uniform,
+                         shared_slot_ref, softmax_ref)
+from .policy_spec import (ACTIVATIONS, MAX_HIDDEN_LAYERS, MODES, OUTCOME_COLS, OUTCOME_COLUMNS, POLICY_GREEDY, POLICY_RELU,  # noqa: F401
+                          POLICY_SAMPLE, POLICY_TANH, BskPolicySpec, Spec, _as_spec, c_spec, check_outcome_log,
+                          check_sigma_adaptation, check_spec, layer_shapes,
                           n_params, pack_params,
                           torch_layers, unpack_params)
 
@@ -127,7 +131,7 @@ class _DeviceObject(object):
             self._p = None
         for b in (getattr(self, "_out", None) or {}).values():
             b.free()
-        self._out = self._source = self._stats = None
+        self._out = self._source = self._stats = self._outcomes = None
 
     def __del__(self):
         try:
@@ -452,6 +456,20 @@ class PolicyPopulation(_ParamStore):
         ``bsk_population_set_obs_stats_members``.  No launch; the next rollout's accumulate launches cover n_counted * E envs."""
         check(self._lib.bsk_population_set_obs_stats_members(self._handle(), self.n_members if n_counted is None else int(n_counted)))
 
+    def set_outcomes(self, rows):
+        """Attaches episode-outcome rows (None detaches): ``rows`` is DEVICE memory, float64 (P, 11) - a raw pointer or anything
+        with ``__cuda_array_interface__``, the caller's to keep alive.  From then on every rollout also says, per member, how the
+        episodes that count ended and which actions they used (``bsk_population_set_outcomes``; ``OUTCOME_COLUMNS``,
+        ``population_outcomes_ref``): the value rule's launch at every env step carries the rule, one more small launch follows the
+        last step.  The first such rollout of a size allocates and cannot be captured.  No launch, no copy, no synchronisation."""
+        ptr = None
+        if rows is not None:
+            queued = self._source
+            ptr, _ = self._device_pointer(rows, 8, _refuse_unless_f64("outcome rows", self.n_members * OUTCOME_COLS))
+            self._source = queued                          # (a queued launch still reads its own source)
+        check(self._lib.bsk_population_set_outcomes(self._handle(), C.c_void_p(int(ptr)) if ptr else None))
+        self._outcomes = rows if ptr else None
+
     def member(self, m):
         """Member ``m``'s parameter block (n_params,) float32 - what ``DevicePolicy(spec, block)`` takes.  Synchronises."""
         out = np.empty(self.n_params, np.float32)
@@ -473,29 +491,48 @@ class PolicyPopulation(_ParamStore):
 
     def rollout_device(self, prop, n_steps, substeps, mode="greedy", gamma=1.0, d_obs_hist=None, d_reward_hist=None, d_reason_hist=None,
                        d_action_hist=None, d_logp_hist=None, d_value_hist=None, d_env_value=None, d_env_len=None, d_fitness=None,
-                       d_mean_len=None):
+                       d_mean_len=None, d_outcomes=None):
         """``bsk_population_rollout`` with device pointers (or None): one generation on the propagator's stream - per env step the
         policy launch for every member, the step, and one launch for the history rows and the running values; then the fitness
         (``d_env_value`` f64[n], ``d_env_len`` i32[n], ``d_fitness`` f64[P], ``d_mean_len`` f64[P]).  No copy, no synchronisation;
-        capturable after a first rollout of the size has allocated the population's scratch rows."""
+        capturable after a first rollout of the size has allocated the population's scratch rows.  ``d_outcomes``: f64[P][11] the
+        episode-outcome rows are written to - attached for this call (``set_outcomes``), which leaves the population with what it
+        had attached before; None: the rollout is passed what it was passed before."""
         if mode not in MODES:
             raise ValueError("mode must be 'greedy' or 'sample'")
         prop = getattr(prop, "propagator", prop)
         vp = lambda p: C.c_void_p(int(p)) if p else None      # noqa: E731
-        check(self._lib.bsk_population_rollout(self._handle(), prop._handle(), MODES[mode], int(substeps), int(n_steps), float(gamma),
-                                               vp(d_obs_hist), vp(d_reward_hist), vp(d_reason_hist), vp(d_action_hist), vp(d_logp_hist),
-                                               vp(d_value_hist), vp(d_env_value), vp(d_env_len), vp(d_fitness), vp(d_mean_len)))
 
-    def evaluate(self, prop, n_steps, substeps, mode="greedy", gamma=1.0):
+        def launch():
+            check(self._lib.bsk_population_rollout(self._handle(), prop._handle(), MODES[mode], int(substeps), int(n_steps), float(gamma),
+                                                   vp(d_obs_hist), vp(d_reward_hist), vp(d_reason_hist), vp(d_action_hist),
+                                                   vp(d_logp_hist), vp(d_value_hist), vp(d_env_value), vp(d_env_len), vp(d_fitness),
+                                                   vp(d_mean_len)))
+        if d_outcomes is None:
+            return launch()
+        before = getattr(self, "_outcomes", None)
+        self.set_outcomes(d_outcomes)
+        try:
+            launch()
+        finally:
+            self.set_outcomes(before)
+
+    def evaluate(self, prop, n_steps, substeps, mode="greedy", gamma=1.0, outcomes=False):
         """One generation with host results: -> dict ``fitness`` (P,), ``mean_len`` (P,), ``env_value`` (n,) float64 and ``env_len``
-        (n,) int32.  Allocates device scratch per call and synchronises: the convenience form; a search loop that keeps its
-        candidates on the device hands ``rollout_device`` its own buffers."""
+        (n,) int32; with ``outcomes`` also ``outcomes``, the members' episode-outcome rows as a dict of (P,) arrays by
+        ``OUTCOME_COLUMNS`` (``outcome_table_ref``).  Allocates device scratch per call and synchronises: the convenience form; a
+        search loop that keeps its candidates on the device hands ``rollout_device`` its own buffers."""
         prop = getattr(prop, "propagator", prop)
         n, P = prop.n_envs, self.n_members
         host = {"env_value": np.empty(n, np.float64), "env_len": np.empty(n, np.int32), "fitness": np.empty(P, np.float64),
                 "mean_len": np.empty(P, np.float64)}
-        return self._host_rollout(prop, host, lambda d: self.rollout_device(prop, n_steps, substeps, mode, gamma,
-                                                                            **{"d_" + k: p for k, p in d.items()}))
+        if outcomes:
+            host["outcomes"] = np.empty((P, OUTCOME_COLS), np.float64)
+        res = self._host_rollout(prop, host, lambda d: self.rollout_device(prop, n_steps, substeps, mode, gamma,
+                                                                           **{"d_" + k: p for k, p in d.items()}))
+        if outcomes:
+            res["outcomes"] = outcome_table_ref(res["outcomes"])
+        return res
 
 
 def _refuse_unless_f64(noun, count):
@@ -522,7 +559,8 @@ class DeviceEvolutionStrategy(_DeviceObject):
     ``validation_members`` = V > 0 scores the centre theta on fixed episodes inside every generation (``set_validation``;
     ``validation_log``, ``validated_best``): ``ask`` then takes a population of ``members_total`` = P + V members, the last V
     holding the centre, and ``tell`` P + V fitness values, of which ranking, log, champion and update read the first P; 0, the
-    default, never calls that entry point either.  Not thread-safe, one stream at a time."""
+    default, never calls that entry point either.  ``set_outcome_log`` adds a third ring, of what the members' episodes did
+    (``outcome_log``).  Not thread-safe, one stream at a time."""
     _kind, _what = "es", "evolution strategy"
 
     def __init__(self, spec, theta, population, sigma=0.1, lr=0.05, seed=0, frozen=10, device=0, optimizer="sgd", beta1=0.9,
@@ -531,6 +569,7 @@ class DeviceEvolutionStrategy(_DeviceObject):
         # every argument is checked before the handle exists: a bad one leaves none behind
         log_capacity = check_log(log_capacity)
         check_validation(validation_members, validation_capacity, validation_epoch, log_capacity)
+        self.outcome_capacity = 0
         self.optimizer, self.adam = optimizer, self._check_optimizer(optimizer, beta1, beta2, eps, weight_decay)
         self._check_sigma_adapt(sigma_adapt, lr_sigma, sigma_max_change, sigma_min, sigma_max, sigma)
         self.sigma_adapt, self.sigma_adaptation = None, None
@@ -844,6 +883,47 @@ class DeviceEvolutionStrategy(_DeviceObject):
             self._val_masks[n_envs] = buf
         return buf.ptr
 
+    # ------------------------------------------------------------------ episode outcomes
+    def set_outcome_log(self, capacity):
+        """A ring of ``capacity`` generations of episode outcomes on the device (``bsk_es_set_outcome_log``): from now on
+        ``run_generation`` has the rollout write every member's outcome row into a buffer of the optimiser's own
+        (``outcomes_ptr``: P + ``ES_VAL_MAX_MEMBERS`` rows, whatever validation is set to later) and every ``tell`` writes, in one
+        more launch in front of its update, the totals over the P ranked members, the row of the member the ranking puts first
+        and the totals over the validation members (``es_outcome_row_ref``).  Every call with ``capacity`` > 0 starts from an
+        empty ring; 0 turns it off.  Everything else of the optimiser stays; synchronises, and cannot be captured."""
+        capacity = check_outcome_log(capacity)
+        # Off first, as ``_lengths`` turns its record off first: under a capture the library refuses here, BEFORE the allocation and
+        # the null-stream memset below, either of which would invalidate the capture.  It costs a second synchronisation, at set-up.
+        check(self._lib.bsk_es_set_outcome_log(self._handle(), 0, None))
+        self.outcome_capacity = 0
+        if not capacity:
+            return
+        nbytes = 8 * OUTCOME_COLS * (self.population + ES_VAL_MAX_MEMBERS)
+        if self._out is None:
+            self._out = {}
+        if "outcomes" not in self._out:
+            self._out["outcomes"] = _hip.DeviceBuffer(nbytes, self.device)
+        ptr = self._out["outcomes"].ptr
+        with _hip.device_guard(self.device):
+            _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(ptr), 0, nbytes, None), "hipMemsetAsync")
+        check(self._lib.bsk_es_set_outcome_log(self._handle(), capacity, C.c_void_p(ptr)))
+        self.outcome_capacity = capacity
+
+    def outcomes_ptr(self):
+        """The members' outcome rows as a DEVICE pointer to float64 (P + V, 11), valid until ``close``: what ``run_generation``
+        hands the rollout as ``d_outcomes`` and ``tell`` reads.  None while the ring is off."""
+        return self._out["outcomes"].ptr if self.outcome_capacity else None
+
+    def outcome_log(self):
+        """The ring as a dict over the generations it holds, sorted by generation (``es_outcome_table_ref``): ``generation``, and
+        ``members`` (totals over the P ranked members), ``best`` (the first-ranked member's row), ``validation`` (totals over the
+        validation members; zeros with validation off) - each a dict of arrays by ``OUTCOME_COLUMNS``.  Synchronises.  An error
+        with the ring off."""
+        gen = np.empty(max(self.outcome_capacity, 1), np.uint64)
+        rows = np.empty((gen.size, 3 * OUTCOME_COLS), np.float64)
+        check(self._lib.bsk_es_get_outcome_log(self._handle(), gen.ctypes.data, rows.ctypes.data))
+        return es_outcome_table_ref(gen, rows)
+
     # ------------------------------------------------------------------ the search
     def ask(self, pop, stream=0):
         """This generation's members into every member of ``pop`` (a ``PolicyPopulation`` of the same spec and ``members_total``
@@ -853,7 +933,8 @@ class DeviceEvolutionStrategy(_DeviceObject):
     def tell(self, d_fitness, stream=0):
         """``d_fitness``: P float64 in DEVICE memory (greater is better; P + V while validation is on) - a raw pointer or anything
         with ``__cuda_array_interface__``.  Ranks the first P, moves theta and advances the generation: three launches on
-        ``stream``, with a log on two more in front of the update, and with validation on two more behind those."""
+        ``stream``, with a log on two more in front of the update, with validation on two more behind those, and with the
+        outcome ring on one more behind those."""
         d_fitness, _ = self._device_pointer(d_fitness, 8, _refuse_unless_f64("device fitness", self.members_total))
         check(self._lib.bsk_es_tell(self._handle(), C.c_void_p(int(d_fitness)) if d_fitness else None, C.c_void_p(int(stream or 0))))
 
@@ -894,12 +975,15 @@ class DeviceEvolutionStrategy(_DeviceObject):
         ``reset_from_pool_shared`` under its own mask and its own constant epoch word - one launch each.  The masks are built in
         the first call for a handle's size (the warming call).  ``obs_stats`` counts the first P members only
         (``pop.set_obs_stats_members``; the population is left counting all), and the rollout writes P + V fitness values and
-        lengths."""
+        lengths.  With the outcome ring on (``set_outcome_log``) the rollout also writes the members' outcome rows into
+        ``outcomes_ptr()`` (attached to ``pop`` for the rollout, which is left with what it had attached before); with it off the
+        rollout is passed what it was passed before."""
         prop = getattr(prop, "propagator", prop)
         fit = self.fitness_buffer()
         stream = prop.stream_ptr()
         V = self.validation_members
         lengths = self._lengths()                          # (None with neither the log nor validation on: as not passed)
+        rows = self.outcomes_ptr()                         # (None with the outcome ring off: as not passed)
         if V:
             E = prop.n_envs // self.members_total
             masks = self._validation_masks(prop.n_envs)
@@ -917,7 +1001,7 @@ class DeviceEvolutionStrategy(_DeviceObject):
             prop.reset_from_pool_device(None)
         self.ask(pop, stream)
         if obs_stats is None:
-            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr, d_mean_len=lengths)
+            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr, d_mean_len=lengths, d_outcomes=rows)
             self.tell(fit.ptr, stream)
             return
         before = getattr(pop, "_stats", None)
@@ -925,7 +1009,7 @@ class DeviceEvolutionStrategy(_DeviceObject):
         if V:
             pop.set_obs_stats_members(self.population)
         try:
-            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr, d_mean_len=lengths)
+            pop.rollout_device(prop, n_steps, substeps, mode, gamma, d_fitness=fit.ptr, d_mean_len=lengths, d_outcomes=rows)
         finally:
             if V:
                 pop.set_obs_stats_members(None)

@@ -14,7 +14,7 @@ of what they state.
 """
 import numpy as np
 
-from .policy_spec import MODES, _as_spec, check_sigma_adaptation, unpack_params
+from .policy_spec import MODES, OUTCOME_COLS, OUTCOME_COLUMNS, _as_spec, check_sigma_adaptation, unpack_params
 
 def fma32(a, b, c):
     """float32 arrays (broadcast against each other) -> float32: a * b + c rounded ONCE, what ``fmaf`` / ``v_fma_f32`` / one step
@@ -187,6 +187,80 @@ def population_fitness_ref(reward_hist, reason_hist, gamma, n_members):
                 s[:, :stride] = s[:, :stride] + s[:, stride:2 * stride]
             return s[:, 0] / np.float64(E)
         return {"env_value": v, "env_len": length, "fitness": mean(v), "mean_len": mean(length.astype(np.float64))}
+
+
+def _extreme_pick(m, x, greatest):
+    """The rule of the outcome rows' minimum (``greatest``: maximum), elementwise: candidate x replaces incumbent m when it is
+    smaller (greater) or the incumbent is a NaN.  The bits of whichever is kept are kept."""
+    with np.errstate(invalid="ignore"):
+        return np.where(((x > m) if greatest else (x < m)) | np.isnan(m), x, m)
+
+
+def _extreme_lanes_then_tree(x, greatest):
+    """That rule in the library's one order over the last axis of ``x`` (..., k): lane l = 0 .. 63 starts from the NaN that stands
+    for "nothing yet" and takes its elements l, l + 64, ... ascending; then, for stride 32 ... 1, lane l + stride is the candidate
+    against the incumbent in lane l.  -> (...,): lane 0."""
+    x = np.asarray(x, np.float64)
+    m = np.full(x.shape[:-1] + (64,), np.nan, np.float64)
+    for at in range(0, x.shape[-1], 64):
+        chunk = x[..., at:at + 64]
+        m[..., :chunk.shape[-1]] = _extreme_pick(m[..., :chunk.shape[-1]], chunk, greatest)
+    for stride in (32, 16, 8, 4, 2, 1):
+        m[..., :stride] = _extreme_pick(m[..., :stride], m[..., stride:2 * stride], greatest)
+    return m[..., 0]
+
+
+def population_outcomes_ref(reward_hist, reason_hist, action_hist, gamma, E):
+    """numpy restatement of the episode-outcome rows (include/bskgpu.h, bsk_population_set_outcomes) from the histories a rollout
+    records: ``reward_hist`` (T, n) float64, ``reason_hist`` (T, n) and ``action_hist`` (T, n) integers, n = P * ``E``, E a multiple
+    of 64.  -> float64 (P, 11), ``OUTCOME_COLUMNS``.  Per env, while alive before step t (``population_fitness_ref``'s rule):
+    act_n[a_t] += 1 (an action outside 0..2 is counted nowhere), and end_reason = the reason byte of the step that ends the episode
+    (0: never ended).  Per member: the envs whose end_reason has each of the four bits, the envs with end_reason 0, the three step
+    counts - integers, converted once - then the sum of v * v (each product rounded on its own), the minimum and the maximum of v
+    in the fitness's order: lanes ascending from the first element, then strides 32 ... 1.  Equal to the device bit for bit."""
+    q = np.asarray(reason_hist)
+    a = np.asarray(action_hist)
+    E = int(E)
+    if q.ndim != 2 or a.shape != q.shape:
+        raise ValueError("reason_hist and action_hist: (n_steps, n) each")
+    n = q.shape[1]
+    if E < 64 or E % 64 or n == 0 or n % E:
+        raise ValueError("n must be n_members * E, E a positive multiple of 64")
+    P = n // E
+    v = population_fitness_ref(reward_hist, q, gamma, P)["env_value"]
+    act_n, end = np.zeros((3, n), np.int64), np.zeros(n, np.int64)
+    alive = np.ones(n, bool)
+    for t in range(q.shape[0]):
+        for k in range(3):
+            act_n[k] += alive & (a[t] == k)
+        end = np.where(alive & (q[t] != 0), q[t].astype(np.int64), end)
+        alive &= q[t] == 0
+    rows = np.empty((P, OUTCOME_COLS), np.float64)
+    for c, bit in enumerate((1, 2, 4, 8)):
+        rows[:, c] = ((end & bit) != 0).reshape(P, E).sum(axis=1)
+    rows[:, 4] = (end == 0).reshape(P, E).sum(axis=1)
+    for k in range(3):
+        rows[:, 5 + k] = act_n[k].reshape(P, E).sum(axis=1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        x = (v * v).reshape(P, E // 64, 64)
+        s = x[:, 0, :].copy()
+        for i in range(1, E // 64):
+            s = s + x[:, i, :]
+        for stride in (32, 16, 8, 4, 2, 1):
+            s[:, :stride] = s[:, :stride] + s[:, stride:2 * stride]
+    rows[:, 8] = s[:, 0]
+    rows[:, 9] = _extreme_lanes_then_tree(v.reshape(P, E), False)
+    rows[:, 10] = _extreme_lanes_then_tree(v.reshape(P, E), True)
+    return rows
+
+
+def outcome_table_ref(rows):
+    """Member rows float64 (..., 11) -> dict of arrays by ``OUTCOME_COLUMNS``: the eight counts as int64, the three value columns
+    float64 as stored."""
+    rows = np.asarray(rows, np.float64)
+    if rows.shape[-1] != OUTCOME_COLS:
+        raise ValueError("outcome rows have %d columns, got %r" % (OUTCOME_COLS, rows.shape))
+    return {name: (rows[..., c].astype(np.int64) if c < 8 else rows[..., c].copy()) for c, name in enumerate(OUTCOME_COLUMNS)}
 
 
 def centred_ranks(fitness):
@@ -579,6 +653,49 @@ def es_log_table_ref(gen, rows):
         std = np.sqrt(np.where(var > 0, var, 0.0))
     out["mean"] = np.where(out["count"] > 0, mean, np.nan)
     out["std"] = np.where(out["count"] > 0, std, np.nan)
+    return out
+
+
+# The outcome ring (bsk_es_set_outcome_log; kernel es_outcome_kernel), restated
+
+def _outcome_totals(rows):
+    """Block A / C of an outcome row over member rows (k, 11) -> float64 (11,): the counts summed as integers, column 8 in the
+    library's one order, columns 9 and 10 under the rows' own rule in that order; +0.0 everywhere with no member."""
+    out = np.zeros(OUTCOME_COLS, np.float64)
+    if rows.shape[0] == 0:
+        return out
+    with np.errstate(invalid="ignore"):
+        out[:8] = rows[:, :8].astype(np.int64).sum(axis=0)
+    out[8] = _lanes_then_tree(rows[:, 8])
+    out[9] = _extreme_lanes_then_tree(rows[:, 9], False)
+    out[10] = _extreme_lanes_then_tree(rows[:, 10], True)
+    return out
+
+
+def es_outcome_row_ref(member_rows, fitness, P, V):
+    """The 33 words ``bsk_es_tell`` writes into its outcome ring -> float64 (33,): the totals over the P ranked members' rows, the
+    row of the member the ranking puts first (``es_log_order_ref``'s b), the totals over the V validation members' rows (+0.0 with
+    V = 0).  ``member_rows``: (P + V, 11) as the rollout wrote them; ``fitness``: at least P values, of which the first P rank."""
+    P, V = int(P), int(V)
+    rows = np.asarray(member_rows, np.float64)
+    f = np.asarray(fitness, np.float64).reshape(-1)
+    if P < 1 or V < 0 or rows.shape != (P + V, OUTCOME_COLS) or f.size < P:
+        raise ValueError("member_rows: (P + V, %d) and at least P fitness values" % OUTCOME_COLS)
+    b, _ = es_log_order_ref(f[:P])
+    return np.concatenate([_outcome_totals(rows[:P]), rows[b], _outcome_totals(rows[P:])])
+
+
+def es_outcome_table_ref(gen, rows):
+    """The ring as ``bsk_es_get_outcome_log`` returns it -> ``outcome_log``'s dict over the slots that have been written, sorted by
+    generation: ``generation`` uint64, and ``members`` / ``best`` / ``validation``, each an ``outcome_table_ref`` dict of arrays
+    over those generations."""
+    gen = np.asarray(gen, np.uint64).reshape(-1)
+    rows = np.asarray(rows, np.float64).reshape(gen.size, 3, OUTCOME_COLS)
+    valid = np.flatnonzero(gen != np.uint64(ES_LOG_EMPTY))
+    valid = valid[np.argsort(gen[valid], kind="stable")]
+    out = {"generation": gen[valid].copy()}
+    for k, name in enumerate(("members", "best", "validation")):
+        out[name] = outcome_table_ref(rows[valid, k])
     return out
 
 

@@ -3,7 +3,8 @@
 ``check_spec`` turns hidden widths and activations into a ``Spec`` or says what is wrong with them; ``layer_shapes``, ``n_params``,
 ``pack_params`` and ``unpack_params`` lay the block out - ``in_scale[5]``, ``in_shift[5]``, then ``W[out][in]`` and ``b[out]`` per layer,
 the action network first - and ``torch_layers`` reads one network out of an ``nn.Sequential``.  ``check_sigma_adaptation`` holds the
-argument rules of the evolution strategy's per-parameter step size.  Nothing here needs a device or the library: only its constants
+argument rules of the evolution strategy's per-parameter step size, ``OUTCOME_COLUMNS`` names the columns of an episode-outcome
+row and ``check_outcome_log`` holds the argument rule of the ring that keeps them.  Nothing here needs a device or the library: only its constants
 and the mirror of the C struct are imported.
 """
 import ctypes as C
@@ -12,7 +13,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._lib import BSK_ABI_VERSION, POLICY_GREEDY, POLICY_RELU, POLICY_SAMPLE, POLICY_TANH, BskPolicySpec
+from ._lib import BSK_ABI_VERSION, BSK_OUTCOME_COLS, POLICY_GREEDY, POLICY_RELU, POLICY_SAMPLE, POLICY_TANH, BskPolicySpec
 
 MAX_HIDDEN_LAYERS = 3
 ACTIVATIONS = {"relu": POLICY_RELU, "tanh": POLICY_TANH}
@@ -80,6 +81,23 @@ def check_sigma_adaptation(lr_sigma, max_change, sigma_min, sigma_max, sigma=Non
     if sigma is not None and not (sigma_min <= float(sigma) <= sigma_max):
         raise ValueError("the optimiser's sigma must be inside [sigma_min, sigma_max]")
     return lr_sigma, max_change, sigma_min, sigma_max
+
+
+#: the columns of one member's episode-outcome row (``BSK_OUTCOME_COLS`` doubles; include/bskgpu.h, bsk_population_set_outcomes)
+OUTCOME_COLUMNS = ("end_length", "end_wheels", "end_battery", "end_orbit", "unfinished", "steps_action0", "steps_action1",
+                   "steps_action2", "value_sum_sq", "value_min", "value_max")
+OUTCOME_COLS = BSK_OUTCOME_COLS
+assert len(OUTCOME_COLUMNS) == OUTCOME_COLS                  # (one name per column of the header's row)
+
+
+def check_outcome_log(capacity):
+    """The argument rule of ``set_outcome_log`` -> the capacity as an int; ValueError where ``bsk_es_set_outcome_log`` returns
+    BSK_EINVAL (0 turns the ring off).  Needs no device."""
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)):
+        raise ValueError("outcome log capacity must be an integer, got %r" % (capacity,))
+    if capacity < 0 or capacity > 2 ** 31 - 1:
+        raise ValueError("outcome log capacity must be in 0..2^31-1, got %d" % capacity)
+    return int(capacity)
 
 
 def layer_shapes(spec):

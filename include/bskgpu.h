@@ -569,6 +569,43 @@ int bsk_population_rollout(bsk_population* pop, bsk_handle* h, int mode, int sub
                            int32_t* d_action_hist, float* d_logp_hist, float* d_value_hist,
                            double* d_env_value, int32_t* d_env_len, double* d_fitness, double* d_mean_len);
 
+/* Episode outcomes: how the episodes that count towards the fitness ended and which actions they used, per member - what a fitness
+ * value cannot say ("the batteries run flat" against "every episode reaches the length limit").  The reason byte and the action row
+ * of an env step exist for one launch; the summary is formed where the fitness is formed, with no [n_steps][n_envs] history and no
+ * host.  Off by default: a population that never calls bsk_population_set_outcomes launches the kernels of the definition above
+ * with the arguments it passed before.  With rows attached every later bsk_population_rollout
+ *   - takes the launch with the value rule at every env step, whether a fitness output was asked for or not (an attached
+ *     bsk_obs_stats object then counts by the alive bytes, as under a rollout that forms fitness), and in that same launch, for
+ *     every env that is alive BEFORE step t (its first episode has not ended: the `alive` of the value rule), with a_t the action
+ *     the policy launch of step t wrote (0, 1 or 2) and q_t the step's reason byte:
+ *         act_n[a_t] = act_n[a_t] + 1;      if q_t != 0: end_reason = q_t
+ *     act_n int32[3] and end_reason uint8 per env, both zero at step 0.  An env still alive behind the last step keeps
+ *     end_reason == 0; under BSK_FLAG_AUTO_RESET later episodes are not counted, exactly as in the fitness;
+ *   - behind the last step, next to the launch that writes the fitness, issues one launch of one wave per member that writes
+ *     d_rows[m][0 .. BSK_OUTCOME_COLS - 1] over member m's envs e = 0 .. E - 1 (v_e = the env's value, what d_env_value holds):
+ *         col 0 .. 3   the number of envs whose end_reason has BSK_DONE_LENGTH, _WHEELS, _BATTERY, _ORBIT set (a byte with two bits
+ *                      set counts in both)
+ *         col 4        the number of envs with end_reason == 0: unfinished when the rollout ended
+ *         col 5 .. 7   the sum of act_n[0], act_n[1], act_n[2]: steps taken under each action while alive; 5 + 6 + 7 is the
+ *                      member's sum of d_env_len
+ *         col 8        the sum of x_e = v_e * v_e, each product rounded on its own, in the order of the fitness:
+ *                        s[l] = x_l;  s[l] = s[l] + x_(l+64c) for c = 1, 2, ... ascending while l + 64c < E        (l = 0 .. 63)
+ *                        for stride = 32, 16, 8, 4, 2, 1:  s[l] = s[l] + s[l + stride] for l < stride;   col 8 = s[0]
+ *         col 9, 10    the minimum and the maximum of v_e in the same order, under the rule "candidate x replaces incumbent m when
+ *                      x < m (max: x > m) or m is a NaN":  m[l] = v_l;  then x = v_(l+64c) ascending;  then for stride = 32 ... 1
+ *                      and l < stride the candidate m[l + stride] against the incumbent m[l];  the result is m[0].  All-NaN
+ *                      gives a NaN; -0.0 and +0.0 compare equal, so which of the two is reported follows from the order.
+ *     Counts are summed as integers and converted to f64 once: exact and independent of any order.  f64 * and + only, no FMA, no
+ *     atomics, no dependence on the launch shape (basilisk_env_amd/policy_ref.py: population_outcomes_ref repeats it bit for bit).
+ * The accumulators are allocated like the population's scratch rows: by the first rollout of a size that has rows attached, which
+ * returns BSK_EINVAL under capture.  Fitness, histories and every buffer of the handle are what the same rollout leaves without
+ * rows attached, bit for bit.
+ * bsk_population_set_outcomes: d_rows is DEVICE memory, f64[n_members][BSK_OUTCOME_COLS], on the population's device (the rollout
+ * checks the handle against that device, like everything else, before anything is launched); it stays attached and is the caller's
+ * to keep alive.  NULL detaches.  No launch, no copy, no synchronisation.  BSK_EINVAL for a NULL population. */
+#define BSK_OUTCOME_COLS 11
+int bsk_population_set_outcomes(bsk_population* pop, double* d_rows);
+
 /* An evolution strategy on the device: antithetic Gaussian perturbations with centred-rank utilities (Salimans et al. 2017), the
  * optimiser a population was given bsk_population_set_params_device for - its candidates never leave the device and its noise is
  * never stored: ask and tell regenerate it from (seed, generation, pair, parameter).  Reset, ask, rollout and tell are one stream
@@ -831,6 +868,36 @@ int bsk_es_set_validated_best(bsk_es* es, const float* params, const double* fit
  * validation off. */
 int bsk_es_validated_best_device(bsk_es* es, const float** d_params);
 int bsk_es_validation_epochs_device(bsk_es* es, const uint64_t** d_epochs);
+
+/* The outcome ring: a third record beside the training log and the validation log - what the members of every generation DID, from
+ * the rows bsk_population_set_outcomes has the generation's rollout write.  Off by default: an optimiser that never calls
+ * bsk_es_set_outcome_log launches the kernels of the definitions above with the arguments it passed before.
+ * State of a ring of capacity C >= 1, all in device memory: out_gen uint64[C], all ones after enabling; out_row
+ * f64[C][3 * BSK_OUTCOME_COLS], zeros after enabling.  With the ring on bsk_es_tell issues ONE more launch of one wave IN FRONT of
+ * the update (behind the log's and the validation's launches where those are on).  It reads the generation word, the first P
+ * fitness values and d_rows, and writes only its own ring: ranking, log, champion, update and validation neither read what it
+ * writes nor are read by it.  g = the generation word, slot = g mod C (of the whole 64-bit word), R = d_rows:
+ *   block A, out_row[slot][0 .. 10], totals over the P ranked members:
+ *        col 0 .. 7   the sum over m < P of R[m][col], each converted to an integer, summed as integers, converted to f64 once
+ *        col 8        the sum of R[m][8] in the library's one order:  s[l] = R[l][8], or +0.0 when l >= P;  s[l] = s[l] + R[l + 64c][8]
+ *                     for c = 1, 2, ... ascending while l + 64c < P;  the tree of strides 32 ... 1;  s[0]
+ *        col 9, 10    R[m][9] and R[m][10] combined in the same order by the rule of the member rows (the candidate replaces when it
+ *                     is smaller - col 10: greater - or the incumbent is a NaN);  a lane with no member holds the NaN
+ *                     0x7FF8000000000000, which every number replaces and which replaces no number
+ *   block B, out_row[slot][11 .. 21]:  R[b], the row of the member tell's ranking puts first (rank 0: the member nobody beats under
+ *        the order of step 1 above), copied
+ *   block C, out_row[slot][22 .. 32]:  block A's rule over the validation members m = P .. P + V - 1 (bsk_es_set_validation), l
+ *        counting from member P; with validation off every entry is +0.0
+ *   out_gen[slot] = g.   (basilisk_env_amd/policy_ref.py: es_outcome_row_ref repeats the row bit for bit.)
+ * bsk_es_set_outcome_log: capacity > 0 allocates (or frees and allocates again) an empty ring; d_rows is DEVICE memory,
+ * f64[P + V][BSK_OUTCOME_COLS] - the rows attached to the population the optimiser asks into - it stays bound and is the caller's to
+ * keep alive.  capacity == 0 turns the ring off and frees it.  Synchronises the device; everything else of the optimiser is left
+ * alone.  BSK_EINVAL: a NULL optimiser, a negative capacity, a NULL d_rows with capacity > 0, and, as bsk_es_set_log, while the
+ * stream of the optimiser's last ask / tell / bsk_es_apply_obs_norm is being captured. */
+int bsk_es_set_outcome_log(bsk_es* es, int capacity, const double* d_rows);
+/* The whole ring to host memory: gen uint64[C], rows f64[C][3 * BSK_OUTCOME_COLS] (either may be NULL); a slot whose out_gen is all
+ * ones has never been written.  Synchronises the device.  BSK_EINVAL for a NULL optimiser and with the ring off. */
+int bsk_es_get_outcome_log(bsk_es* es, uint64_t* gen, double* rows);
 
 /* Running statistics of the five observation rows, formed on the device: what gives a policy its in_scale / in_shift.  Salimans et
  * al. 2017 and ARS V2 (Mania et al. 2018) normalise the observations by the mean and standard deviation of everything the search
