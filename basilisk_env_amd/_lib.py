@@ -81,7 +81,7 @@ class BskPolicySpec(C.Structure):
 
 EXPORTS = [
     "bsk_default_config", "bsk_create", "bsk_destroy", "bsk_set_gravity_sh", "bsk_reset", "bsk_step",
-    "bsk_step_device", "bsk_step_device_i64", "bsk_step_n", "bsk_get_episode_device", "bsk_get_batch_stats_device", "bsk_set_step_stats", "bsk_reset_from_pool_device", "bsk_debug_counters", "bsk_debug_words", "bsk_get_obs", "bsk_get_obs_rowmajor", "bsk_get_obs_device", "bsk_get_obs_state", "bsk_get_stream", "bsk_get_terminal_obs_device", "bsk_get_state_device", "bsk_get_batch_stats", "bsk_n_fields",
+    "bsk_step_device", "bsk_step_device_i64", "bsk_step_n", "bsk_get_episode_device", "bsk_get_batch_stats_device", "bsk_set_step_stats", "bsk_set_halves_form", "bsk_reset_from_pool_device", "bsk_debug_counters", "bsk_debug_words", "bsk_get_obs", "bsk_get_obs_rowmajor", "bsk_get_obs_device", "bsk_get_obs_state", "bsk_get_stream", "bsk_get_terminal_obs_device", "bsk_get_state_device", "bsk_get_batch_stats", "bsk_n_fields",
     "bsk_get_state", "bsk_set_state", "bsk_get_counters", "bsk_set_counters", "bsk_set_ic_pool", "bsk_sample_ic_pool", "bsk_reset_from_pool", "bsk_reset_from_pool_shared", "bsk_get_ic_pool", "bsk_get_terminal_obs", "bsk_set_env_base", "bsk_set_sim_time", "bsk_sync",
     "bsk_fork_device", "bsk_fork", "bsk_select_branches", "bsk_beam_select",
     "bsk_policy_n_params", "bsk_policy_create", "bsk_policy_set_params", "bsk_policy_destroy", "bsk_policy_set_rng", "bsk_policy_get_rng",
@@ -114,7 +114,7 @@ def _signatures():
         "bsk_step": ([vp, vp, i], rc), "bsk_step_device": ([vp, vp, i], rc), "bsk_step_device_i64": ([vp, vp, i], rc),
         "bsk_step_n": ([vp, vp, C.c_int32, i, i, vp, vp, vp], rc),
         "bsk_get_episode_device": ([vp, P(vp), P(vp), P(vp), P(vp), P(vp)], rc), "bsk_get_batch_stats_device": ([vp, P(vp)], rc),
-        "bsk_set_step_stats": ([vp, i], rc), "bsk_reset_from_pool_device": ([vp, vp], rc),
+        "bsk_set_step_stats": ([vp, i], rc), "bsk_set_halves_form": ([vp, i], rc), "bsk_reset_from_pool_device": ([vp, vp], rc),
         "bsk_debug_counters": ([P(i64), P(i64)], rc), "bsk_debug_words": ([vp, vp], rc),
         "bsk_get_obs": ([vp, vp, vp, vp, vp], rc), "bsk_get_obs_rowmajor": ([vp, vp, vp, vp], rc),
         "bsk_get_obs_device": ([vp, P(vp), P(vp), P(vp), P(vp), P(i64)], rc), "bsk_get_obs_state": ([vp, vp, vp, vp, vp], rc),

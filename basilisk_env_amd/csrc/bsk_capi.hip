@@ -149,6 +149,9 @@ int choose_form(const bsk_handle* h, int substeps) {
     const auto& f = h->policy;
     if (f.tri_ok && substeps >= f.tri_min_substeps && h->n <= f.tri_max_envs) return bsk::FORM_TRI;
     if (f.pair_ok && substeps >= f.pair_min_substeps && h->n <= f.pair_max_envs) return bsk::FORM_PAIR;
+    // (an IC pool may be staged at any time, and its restarts rewrite r, v rows from the wave that does not hold them)
+    if (f.halves_ok && f.halves_mode != 0 && substeps == 1 && h->n_pool == 0 &&
+        (f.halves_mode > 0 || (h->n >= f.halves_min_envs && h->n <= f.halves_max_envs))) return bsk::FORM_HALVES;
     return h->cfg.gravity_model == BSK_GRAV_SH ? f.sh_form : bsk::FORM_SINGLE;
 }
 
@@ -351,6 +354,14 @@ int bsk_create(const bsk_config* cfg, int n_envs, int device_id, void* stream, b
     // both wave-split forms pay while every workgroup has a CU (and its LDS) to itself: 64 spacecraft per CU of THIS device
     // (256 CUs on a whole MI355X; fewer in a partitioned mode)
     if (prop.multiProcessorCount > 0) h->policy.pair_max_envs = h->policy.tri_max_envs = 64 * prop.multiProcessorCount;
+    // the halves form doubles the waves of a launch and its kernel leaves room for two waves per SIMD: it pays while one round
+    // places them all, up to 256 spacecraft per CU (65 536 on a whole MI355X: +7.7 %; 131 072 forced into the form: -18 %).
+    // Measured faster from 128 per CU up (32 768: +7 %); below, 16 384 read -7 % and +4 % in two runs and stays as it was
+    // (profiles/halves_k1/README.md)
+    if (prop.multiProcessorCount > 0) {
+        h->policy.halves_min_envs = 128 * prop.multiProcessorCount;
+        h->policy.halves_max_envs = 256 * prop.multiProcessorCount;
+    }
     h->policy.pair_ok = bsk::form_built(cfg->gravity_model, h->diag, h->sp.feat, bsk::FORM_PAIR);
     h->policy.tri_ok = bsk::form_built(cfg->gravity_model, h->diag, h->sp.feat, bsk::FORM_TRI);
     h->sp.pair_shift = 31;     // no swap: the hardware already places one wave 0 and one wave 1 of different workgroups on a SIMD (tools/micro/placement.hip)
@@ -367,6 +378,9 @@ int bsk_create(const bsk_config* cfg, int n_envs, int device_id, void* stream, b
         if (v == 0) h->policy.tri_ok = false;
         else { h->policy.tri_min_substeps = 1; h->policy.tri_max_envs = 1 << 28; }     // every launch (measurement / tests)
     }
+    // the halves form is complete where the FSW chain runs on the state of one integrator step earlier (nav_lag): with nav_lag = 0
+    // the observation needs the end-of-step r, v in the rotational wave on every launch
+    h->policy.halves_ok = bsk::form_built(cfg->gravity_model, h->diag, h->sp.feat, bsk::FORM_HALVES, cfg->n_rw) && h->sp.nav_lag != 0;
     h->last.form = choose_form(h, 0);
     if (stream) { h->stream = (hipStream_t)stream; h->own_stream = false; }
     else {
@@ -824,6 +838,13 @@ int bsk_get_episode_device(bsk_handle* h, double** d_ep_return, double** d_term_
     return BSK_OK;
 }
 
+int bsk_set_halves_form(bsk_handle* h, int mode) {
+    if (!h) return fail(BSK_EINVAL, "handle is NULL");
+    if (mode < -1 || mode > 1) return fail(BSK_EINVAL, "bsk_set_halves_form: mode must be -1 (size window), 0 (never) or 1 (every launch the form is complete for)");
+    h->policy.halves_mode = mode;
+    return BSK_OK;
+}
+
 int bsk_set_step_stats(bsk_handle* h, int on) {
     if (!h) return fail(BSK_EINVAL, "handle is NULL");
     h->step_stats = on != 0;
@@ -995,7 +1016,7 @@ int bsk_kernel_info(bsk_handle* h, char* name, int name_cap, int* vgprs, int* ld
     static const char* const GRAV[] = {"PM", "PM_J2"};                                              // BSK_GRAV_PM, _PM_J2
     static const char* const SH_FORM[] = {"", "SH/scalar", "", "", "SH/dpp", "SH/dpp2"};            // BSK_GRAV_SH, by form
     static const char* const LEVEL[] = {",lds-scratch", "", ",power", ",scenario", ",scenario/generic-facets"};  // FEAT_LDSS ..
-    static const char* const SPLIT[] = {"", "", ",pair", ",tri", "", ""};                          // by form
+    static const char* const SPLIT[] = {"", "", ",pair", ",tri", "", "", ",halves"};               // by form
     const char* hub = h->diag ? "diag" : "full";
     if (name && name_cap > 0 && h->last.rollout)
         std::snprintf(name, name_cap, "rollout_kernel<%s,%d,%s,%s>", GRAV[g], h->cfg.n_rw, hub, h->last.act ? "actions" : "constant");

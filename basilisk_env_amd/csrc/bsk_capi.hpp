@@ -135,11 +135,17 @@ struct bsk_handle {
     // single-wave form up to three pairs per CU, 7 % slower at four (65 536).  Three-wave form (bsk_device.hpp: TriX): the pair form
     // with the dynamics wave cut into a translational and a rotational wave; full-scenario level only, preferred over the pair form
     // where both apply (profiles/r03/tri_form.txt: -16 % against the pair form up to one workgroup per CU, twice the time above).
+    // Halves form (bsk_device.hpp: HalvesLds): one-sub-step launches of the bare point-mass / J2 kernels with wheels, nav_lag and no
+    // IC pool, for batches of halves_min_envs..halves_max_envs spacecraft.
+    // bsk_set_halves_form (halves_mode): -1 that window, 0 never, 1 every launch the form is complete for, at any size.
     // BSKGPU_PAIR / BSKGPU_TRI = 0 | 1 force a form off / on for every launch (bsk_create).  Harmonics run sh_form (bsk_set_gravity_sh).
     struct {
         bool pair_ok = false, tri_ok = false;
         int pair_min_substeps = 16, pair_max_envs = 16384;
         int tri_min_substeps = 16, tri_max_envs = 16384;
+        bool halves_ok = false;
+        int halves_min_envs = 1, halves_max_envs = 0;       // (bsk_create: 128 - 256 spacecraft per CU of the device)
+        int halves_mode = -1;
         int sh_form = bsk::FORM_SH_DPP;
     } policy;
     // what the last launch ran (bsk_kernel_info): the step kernel in `form`, or bsk_step_n's rollout kernel (with per-step actions)

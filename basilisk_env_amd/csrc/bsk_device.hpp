@@ -468,6 +468,18 @@ struct TriLds {
 typedef TriX __attribute__((address_space(3))) * TriXP;
 typedef TriLds __attribute__((address_space(3))) * TriP;
 
+// Halves form (SPLIT == 6): the bare one-sub-step launch as a rotational wave (wave 0: attitude, wheels, FSW chain, observation,
+// reward, every store but r, v) and a translational wave (wave 1: r, v) of the SAME 64 spacecraft.  At the bare level nothing
+// couples the two inside the RK4 step (gravity reads r only), so they meet through this block at barriers alone: the loaded
+// (r, v) on launches with an FSW tick (the chain's navigation input: the translational wave overwrites the rows early), and the
+// "below r_min" ballot of the end-of-step position.
+struct HalvesLds {
+    double rv[6][64];                         // translational -> rotational: the loaded r, v (launches with an FSW tick only)
+    unsigned long long orbit;                 // translational -> rotational: ballot of |r|^2 < r_min2 at the end of the step
+    unsigned long long pad_;
+};
+typedef HalvesLds __attribute__((address_space(3))) * HalvesP;
+
 // The exchange's LDS accesses are RELAXED ATOMICS of workgroup scope: the compiler neither merges nor drops them, and - unlike
 // volatile accesses, each of which it follows with a wait for its completion - it leaves a batch of reads in flight until
 // the first use of a result.  What relaxed atomics do NOT promise is their order against each other (different addresses), and
@@ -1473,16 +1485,21 @@ __device__ __forceinline__ void acc_load(AccP A, int lane, Core& a) {
 // shadow-set switch once per completed step.  Motor torque and Coulomb friction are evaluated
 // from the wheel speeds at the start of the step and held through its four stages (the RW
 // effector updates both once per dyn tick, outside the equations of motion).
-template <int GRAV, int NRW, bool DIAG, int FEAT, int SPLIT, bool THR = false, int DRAGM = 0, class WV>
+// PART (halves form, bare levels): PART_ROT / PART_TRA integrate sigma, omega and the wheels / r and v only, each with the
+// operations the whole step performs on those components (`u`, `lext`, `wv` are not read by PART_TRA).
+template <int GRAV, int NRW, bool DIAG, int FEAT, int SPLIT, bool THR = false, int DRAGM = 0, int PART = PART_ALL, class WV>
 __device__ __forceinline__ void rk4_step(const HotCfg<NRW, DIAG>& c, const WV& wv, State<NRW>& x,
                                          const double* u, V3 lext, double t0, const Env& ev, AccP acc_lds = nullptr,
                                          const Pre* pre = nullptr, double* q2_out = nullptr) {
+    static_assert(PART == PART_ALL || (!is_full<FEAT>() && FEAT != FEAT_LDSS), "the halves of a step exist where nothing couples them");
+    constexpr bool ROTP = PART != PART_TRA;                      // this wave integrates the rotational components
     Core y, k, yt, acc;
     y.r = x.r; y.v = x.v; y.s = x.s; y.w = x.w;
     y.p = mk(0, 0, 0);
-    if constexpr (NRW > 0) y.p = mv3<DIAG>(c.W, y.w);      // W w0: the wheels' momentum goes on top (wv.head)
+    if constexpr (NRW > 0 && ROTP) y.p = mv3<DIAG>(c.W, y.w);      // W w0: the wheels' momentum goes on top (wv.head)
     V3 T = mk(0, 0, 0);
     double tqj[NRW > 0 ? NRW : 1], tq[NRW > 0 ? NRW : 1];
+    if constexpr (ROTP) {
 #pragma unroll
     for (int i = 0; i < NRW; ++i) {
         // Coulomb friction -fc sign(Om), 0 at rest, as three fp64 instructions: fc sign(Om) = clamp(2^1000 Om, -fc, fc)
@@ -1492,41 +1509,44 @@ __device__ __forceinline__ void rk4_step(const HotCfg<NRW, DIAG>& c, const WV& w
         tq[i] = u[i] - fs;
     }
     if constexpr (NRW > 0) wv.head(tq, x.Om, T, y.p, tqj);      // y.p = c_1 = p_0 + W w_0
+    }
     const V3 rhs0 = lext - T;
     V3 c2 = y.p, c4 = y.p;                                       // c_2 = c_3 = c_1 + h/2 T,  c_4 = c_1 + h T
-    if constexpr (NRW > 0) { c2 = axpy(c.h2, T, y.p); c4 = axpy(c.h, T, y.p); }
+    if constexpr (NRW > 0 && ROTP) { c2 = axpy(c.h2, T, y.p); c4 = axpy(c.h, T, y.p); }
     V3 a3 = mk(0, 0, 0);
     if constexpr (is_full<FEAT>()) a3 = third_body_step(ev.s3, y.r, y.v, c.h2);
     constexpr bool LDSACC = FEAT == FEAT_LDSS;
     AccP A = nullptr;
     int lane = 0;
     if constexpr (LDSACC) { A = acc_lds; lane = (int)(threadIdx.x & 63u); }
-    eom<GRAV, NRW, DIAG, FEAT, SPLIT, THR, DRAGM>(c, y, rhs0, a3, t0, ev, 0, k, pre);
-    core_axpy<NRW>(c.h6, k, y, acc);
+    eom<GRAV, NRW, DIAG, FEAT, SPLIT, THR, DRAGM, PART>(c, y, rhs0, a3, t0, ev, 0, k, pre);
+    core_axpy<NRW, PART>(c.h6, k, y, acc);
     if constexpr (LDSACC) acc_store<NRW>(A, lane, acc);
-    core_axpy<NRW>(c.h2, k, y, yt);
+    core_axpy<NRW, PART>(c.h2, k, y, yt);
     yt.p = c2;
-    eom<GRAV, NRW, DIAG, FEAT, SPLIT, THR, DRAGM>(c, yt, rhs0, a3, t0 + c.h2, ev, 1, k);
+    eom<GRAV, NRW, DIAG, FEAT, SPLIT, THR, DRAGM, PART>(c, yt, rhs0, a3, t0 + c.h2, ev, 1, k);
     if constexpr (LDSACC) acc_load<NRW>(A, lane, acc);
-    core_axpy<NRW>(c.h3, k, acc, acc);
+    core_axpy<NRW, PART>(c.h3, k, acc, acc);
     if constexpr (LDSACC) acc_store<NRW>(A, lane, acc);
-    core_axpy<NRW>(c.h2, k, y, yt);
-    eom<GRAV, NRW, DIAG, FEAT, SPLIT, THR, DRAGM>(c, yt, rhs0, a3, t0 + c.h2, ev, 1, k);
+    core_axpy<NRW, PART>(c.h2, k, y, yt);
+    eom<GRAV, NRW, DIAG, FEAT, SPLIT, THR, DRAGM, PART>(c, yt, rhs0, a3, t0 + c.h2, ev, 1, k);
     if constexpr (LDSACC) acc_load<NRW>(A, lane, acc);
-    core_axpy<NRW>(c.h3, k, acc, acc);
+    core_axpy<NRW, PART>(c.h3, k, acc, acc);
     if constexpr (LDSACC) acc_store<NRW>(A, lane, acc);
-    core_axpy<NRW>(c.h, k, y, yt);
+    core_axpy<NRW, PART>(c.h, k, y, yt);
     yt.p = c4;
-    eom<GRAV, NRW, DIAG, FEAT, SPLIT, THR, DRAGM>(c, yt, rhs0, a3, t0 + c.h, ev, 2, k);
+    eom<GRAV, NRW, DIAG, FEAT, SPLIT, THR, DRAGM, PART>(c, yt, rhs0, a3, t0 + c.h, ev, 2, k);
     if constexpr (LDSACC) acc_load<NRW>(A, lane, acc);
-    core_axpy<NRW>(c.h6, k, acc, yt);
+    core_axpy<NRW, PART>(c.h6, k, acc, yt);
+    if constexpr (PART != PART_ROT) { x.r = yt.r; x.v = yt.v; }
+    if constexpr (!ROTP) return;
     const V3 dw = yt.w - y.w;
     double base[NRW > 0 ? NRW : 1];
     if constexpr (NRW > 0) {
         wv.bases(c.h, tq, tqj, x.Om, base);
         wv.tail(dw, base, x.Om);
     }
-    x.r = yt.r; x.v = yt.v; x.s = yt.s; x.w = yt.w;
+    x.s = yt.s; x.w = yt.w;
     double s2 = dot(x.s, x.s);
     if (BSK_UNLIKELY(s2 > 1.0)) {
         x.s = (-rcp_nr(s2)) * x.s;

@@ -42,6 +42,13 @@ __device__ __forceinline__ int uni_any(bool lane_cond) {
     return r;
 }
 
+// Halves form: does some lane of the wave run its FSW chain at the head of this one-sub-step launch, on the loaded state?  Both
+// waves of a workgroup evaluate this on the same counter words, and every barrier decision of the form is this value alone.
+// (the chain of t = 0 runs on messages nobody has written: zeros, no state)
+__device__ __forceinline__ int halves_fsw_due(int cnt_x, int nav_lag, int fsw_every) {
+    return uni_any((cnt_x >> 20) == (nav_lag != 0 ? fsw_every - 1 : 0));
+}
+
 __device__ __forceinline__ int wave_min_uniform(int v) {
     // every lane holds the same value unless a masked reset staggered the FSW phases inside this wave: one ballot
     // settles the common case, the shuffle tree (six trips through the LDS crossbar) only runs when lanes differ
@@ -58,7 +65,7 @@ constexpr int LDSS_WAVES = 3;   // waves per SIMD the LDS-scratch level is built
 // sums through LDS: twice the waves per SIMD at the same batch size, so one wave's loads and scalar
 // instructions overlap with the other's FMAs.  Only wave 0 stores.
 template <int GRAV, int NRW, bool DIAG, int FEAT, int SPLIT>
-__global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPLIT == 3) ? 2 : (FEAT == FEAT_LDSS ? LDSS_WAVES : 1)) void step_kernel(const StepArgs<NRW, DIAG> a) {
+__global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPLIT == 3 || SPLIT == 6) ? 2 : (FEAT == FEAT_LDSS ? LDSS_WAVES : 1)) void step_kernel(const StepArgs<NRW, DIAG> a) {
     const HotCfg<NRW, DIAG>& c = a.hot;
     const ColdCfg* __restrict__ cold = a.cold;
     const probe::Stamp t_kernel = probe::stamp<probe::PAIR_TIME>();
@@ -69,8 +76,11 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     // wave and the translational wave of the same 64 spacecraft
     constexpr bool TRI = SPLIT == 3;
     constexpr bool PAIR = SPLIT == 2 || TRI;
+    // SPLIT == 6 (halves form, bsk_device.hpp: HalvesLds): a 128-thread workgroup = the rotational wave (this function's single-wave
+    // path without r, v) and the translational wave (the block below) of the same 64 spacecraft
+    constexpr bool HALVES = SPLIT == 6;
     const int gid = (SPLIT == 5) ? (int)(blockIdx.x * 128 + (threadIdx.x >> 7) * 64 + (threadIdx.x & 63))
-                  : PAIR ? (int)(blockIdx.x * 64 + (threadIdx.x & 63))
+                  : (PAIR || HALVES) ? (int)(blockIdx.x * 64 + (threadIdx.x & 63))
                          : (int)(blockIdx.x * blockDim.x + threadIdx.x);
     const bool valid = gid < a.n;
     const int i = valid ? gid : a.n - 1;  // tail lanes shadow the last env; their stores are masked
@@ -79,10 +89,47 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     const uint32_t bo = (uint32_t)i * 8u;   // per-lane byte offset inside every field row (n < 2^28)
 #define FLD(f) (st + (int64_t)(f) * S)
 
+    extern __shared__ __align__(16) unsigned char lds_dyn[];
+    if constexpr (HALVES) {
+        static_assert(form_built(GRAV, DIAG, FEAT, SPLIT, NRW), "the halves form: bare level, point mass or J2, with wheels (bsk_launch.hpp: form_built)");
+        // ---- translational wave: r, v of the launch's one RK4 step (bsk_capi.hip, choose_form: substeps == 1, nav_lag != 0, no
+        // IC pool), stored as soon as they are final; it meets the rotational wave at barriers only
+        if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0) {
+            const HalvesP HL = (HalvesP)lds_dyn;
+            const int hl = (int)(threadIdx.x & 63u);
+            State<NRW> xt;
+            xt.r = mk(ldf(FLD(BSK_F_R + 0), bo), ldf(FLD(BSK_F_R + 1), bo), ldf(FLD(BSK_F_R + 2), bo));
+            xt.v = mk(ldf(FLD(BSK_F_V + 0), bo), ldf(FLD(BSK_F_V + 1), bo), ldf(FLD(BSK_F_V + 2), bo));
+            const int2 cnt_t = *reinterpret_cast<const int2*>(reinterpret_cast<const char*>(a.cnt) + bo);
+            asm volatile("" ::"s"(c.h), "s"(c.h2), "s"(c.h3), "s"(c.h6), "s"(c.nmu), "s"(c.j2k));
+            if (halves_fsw_due(cnt_t.x, a.nav_lag, c.fsw_every)) {
+                // the FSW chain of the other wave navigates on the LOADED r, v (nav_lag): handed over before the rows are overwritten
+                HL->rv[0][hl] = xt.r.x; HL->rv[1][hl] = xt.r.y; HL->rv[2][hl] = xt.r.z;
+                HL->rv[3][hl] = xt.v.x; HL->rv[4][hl] = xt.v.y; HL->rv[5][hl] = xt.v.z;
+                __syncthreads();
+            }
+            const Env ev_t{};
+            const WheelV<NRW> wv_t{};
+            rk4_step<GRAV, NRW, DIAG, FEAT, SPLIT, false, 0, PART_TRA>(c, wv_t, xt, nullptr, mk(0, 0, 0), (double)cnt_t.y * c.h, ev_t);
+            const gptr<double> so_t = uniform_ptr(a.tail.st);
+            stf(so_t + (int64_t)(BSK_F_R + 0) * S, bo, xt.r.x); stf(so_t + (int64_t)(BSK_F_R + 1) * S, bo, xt.r.y);
+            stf(so_t + (int64_t)(BSK_F_R + 2) * S, bo, xt.r.z);
+            stf(so_t + (int64_t)(BSK_F_V + 0) * S, bo, xt.v.x); stf(so_t + (int64_t)(BSK_F_V + 1) * S, bo, xt.v.y);
+            stf(so_t + (int64_t)(BSK_F_V + 2) * S, bo, xt.v.z);
+            const unsigned long long below = __builtin_amdgcn_ballot_w64(dot(xt.r, xt.r) < a.tail.obs_cfg.r_min2);
+            if (hl == 0) HL->orbit = below;
+            __syncthreads();
+            return;
+        }
+    }
     // every load of the launch is issued here, before any use
     State<NRW> x;
+    if constexpr (HALVES) {       // (the other wave's; the loaded values arrive through LDS on launches with an FSW tick)
+        x.r = mk(0, 0, 0); x.v = mk(0, 0, 0);
+    } else {
     x.r = mk(ldf(FLD(BSK_F_R + 0), bo), ldf(FLD(BSK_F_R + 1), bo), ldf(FLD(BSK_F_R + 2), bo));
     x.v = mk(ldf(FLD(BSK_F_V + 0), bo), ldf(FLD(BSK_F_V + 1), bo), ldf(FLD(BSK_F_V + 2), bo));
+    }
     x.s = mk(ldf(FLD(BSK_F_SIGMA + 0), bo), ldf(FLD(BSK_F_SIGMA + 1), bo), ldf(FLD(BSK_F_SIGMA + 2), bo));
     x.w = mk(ldf(FLD(BSK_F_OMEGA + 0), bo), ldf(FLD(BSK_F_OMEGA + 1), bo), ldf(FLD(BSK_F_OMEGA + 2), bo));
 #pragma unroll
@@ -138,7 +185,6 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     double shadow = 1.0;
     SunGeom sg;
     constexpr bool POWER = FEAT >= FEAT_POWER;
-    extern __shared__ __align__(16) unsigned char lds_dyn[];
     LdsP L = nullptr;
     const int lane = (int)(threadIdx.x & 63u);
     if constexpr (POWER) {
@@ -660,6 +706,15 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
             return;                                        // the dynamics wave writes the launch's results
         }
     } else {
+    if constexpr (HALVES) {
+        // launches with an FSW tick in some lane: the chain's navigation input is the translational wave's loaded r, v
+        if (halves_fsw_due(cnt.x, a.nav_lag, fsw_every)) {
+            const HalvesP HL = (HalvesP)lds_dyn;
+            __syncthreads();
+            x.r = mk(HL->rv[0][lane], HL->rv[1][lane], HL->rv[2][lane]);
+            x.v = mk(HL->rv[3][lane], HL->rv[4][lane], HL->rv[5][lane]);
+        }
+    }
     int np = 0;   // power system: ticks recorded since the last flush (per lane)
     PowerCfg pc_loop_cfg;   // power level (panel constants as scalar operands): the four the tick reads, as scalars of their own
     if constexpr (POWER && !FULL) {
@@ -757,7 +812,7 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
                 thr_masks(ev);
             }
             if constexpr (FULL) rk4_step<GRAV, NRW, DIAG, FEAT, SPLIT, THR, DM>(c, wv, x, u, lext, (double)tick * c.h, ev, accp, &pre, &q2);
-            else rk4_step<GRAV, NRW, DIAG, FEAT, SPLIT, false>(c, wv, x, u, lext, (double)tick * c.h, ev, accp);
+            else rk4_step<GRAV, NRW, DIAG, FEAT, SPLIT, false, 0, HALVES ? PART_ROT : PART_ALL>(c, wv, x, u, lext, (double)tick * c.h, ev, accp);
             if constexpr (POWER) power_tick<FULL>(FULL ? a.power : pc_loop_cfg, sg, x.r, x.s, L, np + t, lane, kt.c, FULL ? &pre : nullptr, FULL ? &q2 : nullptr);
             ++t;
             ++tick;
@@ -884,7 +939,7 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     // obs[0] is the logged att_guidance message: with nav_lag the one the last FSW tick wrote (held in `sbr`),
     // otherwise the tracking error of the end-of-step state under the step's mode
     double o0 = sbr;
-    if (!(NRW > 0 && ta.nav_lag != 0)) {
+    if (!HALVES && !(NRW > 0 && ta.nav_lag != 0)) {
         double sR0N[3] = {ta.obs_cfg.sigma_R0N[0], ta.obs_cfg.sigma_R0N[1], ta.obs_cfg.sigma_R0N[2]};
         const Guid g = guidance<NRW>(sR0N, x, action);
         o0 = sqrt_nr(dot(g.sigma_BR, g.sigma_BR));
@@ -904,7 +959,12 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     if (steps0 >= ta.obs_cfg.max_length) why |= BSK_DONE_LENGTH;
     if (o2 > 1.0) { why |= BSK_DONE_WHEELS; rew -= ta.obs_cfg.failure_penalty; }
     if (!static_o3 && o3 == 0.0) { why |= BSK_DONE_BATTERY; rew -= ta.obs_cfg.failure_penalty; }
-    if (dot(x.r, x.r) < ta.obs_cfg.r_min2) why |= BSK_DONE_ORBIT;
+    if constexpr (HALVES) {       // the translational wave's ballot of the end-of-step position
+        __syncthreads();
+        if ((((HalvesP)lds_dyn)->orbit >> lane) & 1ull) why |= BSK_DONE_ORBIT;
+    } else {
+        if (dot(x.r, x.r) < ta.obs_cfg.r_min2) why |= BSK_DONE_ORBIT;
+    }
 
     if constexpr (SPLIT == 5) {
         if (threadIdx.x & 64) return;    // the second wave of each pair only helped with the harmonics
@@ -935,7 +995,7 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     gptr<double> so = uniform_ptr(ta.st);
     gptr<double> ob = uniform_ptr(ta.obs);
 #define FLD(f) (so + (int64_t)(f) * S2)
-    const int n_pool = ta.n_pool;
+    const int n_pool = HALVES ? 0 : ta.n_pool;      // (the halves form runs on handles without an IC pool)
     if (n_pool > 0 && why != 0) {
       if (valid2) {   // tail lanes shadow env n-1: its own lane performs the reset, they must not repeat it
         // Device-side auto-reset (rare, divergent): reload this env from the staged IC pool, keep the
@@ -971,8 +1031,10 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
         *(gptr<unsigned long long>)((gptr<char>)uniform_ptr(ta.cnt) + bo) = 0ull;
       }
     } else {
+        if constexpr (!HALVES) {   // (the translational wave has stored them)
         stf(FLD(BSK_F_R + 0), bo, x.r.x); stf(FLD(BSK_F_R + 1), bo, x.r.y); stf(FLD(BSK_F_R + 2), bo, x.r.z);
         stf(FLD(BSK_F_V + 0), bo, x.v.x); stf(FLD(BSK_F_V + 1), bo, x.v.y); stf(FLD(BSK_F_V + 2), bo, x.v.z);
+        }
         stf(FLD(BSK_F_SIGMA + 0), bo, x.s.x); stf(FLD(BSK_F_SIGMA + 1), bo, x.s.y); stf(FLD(BSK_F_SIGMA + 2), bo, x.s.z);
         stf(FLD(BSK_F_OMEGA + 0), bo, x.w.x); stf(FLD(BSK_F_OMEGA + 1), bo, x.w.y); stf(FLD(BSK_F_OMEGA + 2), bo, x.w.z);
 #pragma unroll
@@ -1112,7 +1174,7 @@ static hipError_t launch_t(const StepLaunch& go, const LaunchShape& sh) {
 
 template <int G, int R, bool D, int P, int S>
 static hipError_t step_form(int block, int n, const StepLaunch* go, KernelDesc* d) {
-    if constexpr (form_built(G, D, P, S)) {
+    if constexpr (form_built(G, D, P, S, R)) {
         d->fn = (const void*)&step_kernel<G, R, D, P, S>;
         d->shape = launch_shape(S, P, block, n);
         return go ? launch_t<G, R, D, P, S>(*go, d->shape) : hipSuccess;
@@ -1130,6 +1192,10 @@ hipError_t BSK_STEP_UNIT(int grav, int nrw, bool diag, int feat, int form, int b
 #define ONE_WAVE_FORMS(G, R, D, P) CASE(G, R, D, P, FORM_SH_DPP) CASE(G, R, D, P, FORM_SH_DPP2) CASE(G, R, D, P, FORM_SINGLE)
     BSK_VARIANTS(SPLIT_FORMS)
     BSK_VARIANTS(ONE_WAVE_FORMS)
+    // (the halves form last: the kernels before it keep their places in the code object)
+#define HALVES_FORM(G, R, D, P) CASE(G, R, D, P, FORM_HALVES)
+    BSK_VARIANTS(HALVES_FORM)
+#undef HALVES_FORM
 #undef ONE_WAVE_FORMS
 #undef SPLIT_FORMS
 #undef CASE

@@ -134,16 +134,19 @@ enum Form : int {
     FORM_TRI = 3,       // rotational, FSW / environment and translational wave of the same 64 spacecraft (TriLds)
     FORM_SH_DPP = 4,    // harmonics: DPP broadcast stream
     FORM_SH_DPP2 = 5,   // harmonics: DPP broadcast stream, the walk split over two cooperating waves
+    FORM_HALVES = 6,    // bare level, one sub-step: rotational wave + translational wave of the same 64 spacecraft (HalvesLds)
 };
 
 // The forms built for a cell (gravity model, hub kind, feature level).  The wave-split forms exist for the power (pair) and
-// full-scenario (pair, three-wave) levels of the point-mass and J2 kernels with a diagonal hub; the DPP forms for harmonics.
-constexpr bool form_built(int grav, bool diag, int feat, int form) {
+// full-scenario (pair, three-wave) levels of the point-mass and J2 kernels with a diagonal hub; the DPP forms for harmonics; the
+// halves form for the bare level of the point-mass and J2 kernels with wheels (either hub kind).
+constexpr bool form_built(int grav, bool diag, int feat, int form, int nrw = BSK_MAX_RW) {
     switch (form) {
     case FORM_SINGLE: return true;
     case FORM_PAIR: return diag && grav != BSK_GRAV_SH && (feat == FEAT_POWER || feat == FEAT_FULL);
     case FORM_TRI: return diag && grav != BSK_GRAV_SH && feat == FEAT_FULL;
     case FORM_SH_DPP: case FORM_SH_DPP2: return grav == BSK_GRAV_SH;
+    case FORM_HALVES: return grav != BSK_GRAV_SH && feat == FEAT_BARE && nrw > 0;
     default: return false;
     }
 }
@@ -154,6 +157,7 @@ struct LaunchShape { int block, grid; size_t lds; };     // lds: dynamic LDS byt
 constexpr LaunchShape launch_shape(int form, int feat, int block, int n) {
     if (form == FORM_PAIR) return {128, (n + 63) / 64, sizeof(PairLds)};
     if (form == FORM_TRI) return {192, (n + 63) / 64, sizeof(TriLds)};
+    if (form == FORM_HALVES) return {128, (n + 63) / 64, sizeof(HalvesLds)};
     // the two-wave harmonics form: 256-thread workgroups of 2 x 64 spacecraft x 2 halves of the walk
     if (form == FORM_SH_DPP2) block = 256;
     const int grid = form == FORM_SH_DPP2 ? (n + 127) / 128 : (n + block - 1) / block;

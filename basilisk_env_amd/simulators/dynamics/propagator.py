@@ -416,6 +416,11 @@ class BatchedPropagator(object):
         behind it cost one small launch instead of two (same bits).  For loops that ask after every step; default off."""
         check(self._lib.bsk_set_step_stats(self._handle(), 1 if on else 0))
 
+    def set_halves_form(self, mode):
+        """The halves form of the one-sub-step launch: ``None`` the handle's size window (default), ``False`` never, ``True`` every
+        launch the form is complete for, at any batch size (same bits either way; ``kernel_info`` names the form that ran)."""
+        check(self._lib.bsk_set_halves_form(self._handle(), -1 if mode is None else 1 if mode else 0))
+
     def get_terminal_obs(self):
         """-> terminal observations (5, N) (valid where the last step reported done), finished-episode
         counts (N,) int32."""

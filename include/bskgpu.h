@@ -299,6 +299,10 @@ int bsk_get_batch_stats_device(bsk_handle* h, double** d_stats2);
  * two-level form, which is as fast there).  Same bits either way.  Default off: a step that nobody asks about pays nothing.  (Takes effect with the next launch; a handle whose launches have been captured into a HIP graph keeps
  * the two-level form - replays step without the host's knowledge.) */
 int bsk_set_step_stats(bsk_handle* h, int on);
+/* The halves form of the one-sub-step launch (bsk_kernel_info): mode -1 (default) the handle's size window,
+ * 0 never, 1 every launch the form is complete for, at any batch size (measurement and tests: the results are the same bits in
+ * either form).  Takes effect with the next launch. */
+int bsk_set_halves_form(bsk_handle* h, int mode);
 
 /* Full state read-back / injection, host SoA [n_fields][n_envs] (parity tests, reset_init). */
 int bsk_n_fields(const bsk_handle* h);
@@ -1012,7 +1016,10 @@ int bsk_calibrate_fp64(int device_id, int waves_per_simd, int repeats, double* t
  * sub-steps in a wave-split form of the same arithmetic (bit-identical results: "...,pair" at the power level - a dynamics and
  * an FSW + environment wave per 64 spacecraft, 128-thread workgroups - and "...,tri" at the full-scenario level - a
  * translational, a rotational and the FSW + environment wave, 192-thread workgroups), everything else the
- * single-wave form.  BSKGPU_PAIR / BSKGPU_TRI = 0 | 1 in the environment of bsk_create switch a form off / on for every launch.
+ * single-wave form - except one-sub-step launches of the bare level (point mass or J2, with wheels, nav_lag != 0, no IC pool) for
+ * batches of 128 to 256 spacecraft per CU of the device (32 768 - 65 536 on a whole MI355X), which run "...,halves": a rotational and
+ * a translational wave per 64 spacecraft, 128-thread workgroups, bit-identical results (bsk_set_halves_form: off / on at any size).
+ * BSKGPU_PAIR / BSKGPU_TRI = 0 | 1 in the environment of bsk_create switch a form off / on for every launch.
  * Before the first launch: the single-wave form of the config (harmonics: the form of the last bsk_set_gravity_sh, the one-wave
  * DPP form before any). */
 int bsk_kernel_info(bsk_handle* h, char* name, int name_cap, int* vgprs, int* lds_bytes,
