@@ -392,8 +392,10 @@ __device__ __forceinline__ double percent_shadow(const PowerCfg& pc, V3 r_HB, V3
 // alone on its SIMD - and with 64 spacecraft per wave some lane is in the penumbra during most 10-tick windows, so
 // practically every flush paid it (0.4 ms of the power level's 2.3 ms at K = 1800).  One pass serves up to 64 queue entries
 // for the same latency, so the record now spans PEN_SLOTS = 30 ticks (a third of the passes); the queue holds PEN_QCAP
-// entries and a tick that finds it full evaluates its factor on the spot (never in LEO: 192 entries are three spacecraft in
-// the penumbra for the whole record), so the worst case costs time, not correctness.
+// entries and a tick that finds it full evaluates its factor on the spot.  192 entries are 6.4 spacecraft in the penumbra for
+// the whole record: independent spacecraft in LEO never get there, a forked batch (bsk_fork_device, the planners) does so
+// routinely - the 64 clones of a wave cross the band together and from the 4th tick of every record each lane evaluates in
+// place.  That route costs time, not correctness (tests/test_gpu_penumbra_crowd.py holds both to the oracle).
 constexpr int PEN_CHUNK = 10;                 // RK4 ticks per trip of the inner loop at most (third-body anchor)
 constexpr int PEN_SLOTS = 30;                 // ticks recorded between two flushes
 constexpr int PEN_QCAP = 192;                 // penumbra queue entries per record

@@ -557,7 +557,11 @@ static double shadow_factor(const bsk_config* c, const double r[3], const double
     double f1 = safe_asin((REQ_SUN + c->req) / nhp), f2 = safe_asin((REQ_SUN - c->req) / nhp);
     double s = v3norm(r), s0 = -v3dot(r, sun) / nhp;
     double c1 = s0 + c->req / sin(f1), c2 = s0 - c->req / sin(f2);
-    double l = sqrt(s * s - s0 * s0), l1 = c1 * tan(f1), l2 = c2 * tan(f2);
+    /* On the shadow axis s^2 - s0^2 rounds to either side of zero, and the square root of a negative value is a NaN that fails
+       both cone tests: "sunlit" in the middle of the umbra.  The reference engine's eclipse module takes the same square root
+       and has the same hole [BSK-recall]; that is not something to reproduce (the kernels and the 50-digit model classify the axis
+       correctly), so the difference is clamped: a departure from the reference, like the conditioned lens area above. */
+    double l = sqrt(fmax(s * s - s0 * s0, 0.0)), l1 = c1 * tan(f1), l2 = c2 * tan(f2);
     if (fabs(l) < fabs(l2) || fabs(l) < fabs(l1))
         return g_penumbra_form ? percent_shadow_as_written(c->req, r_HB, r) : percent_shadow(c->req, r_HB, r);
     return 1.0;
