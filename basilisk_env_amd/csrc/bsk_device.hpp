@@ -652,7 +652,8 @@ __device__ __forceinline__ double atmosphere_exp(const KTab& kt, double x) {    
 // Taylor polynomial of e^d (truncation d^7 / 5040 < 5e-17 for |d| <= 2^-6, i.e. 125 m of radial motion per tick) - ten
 // instructions instead of the thirty-five of the full evaluation.  The exponents telescope exactly (x' - x of neighbouring
 // doubles is exact), so what accumulates is the rounding of one polynomial and one product per tick (2e-16 each); every
-// chunk of <= PEN_CHUNK ticks starts from a full evaluation (anchor), and a lane whose exponent jumps by more than 2^-6
+// <= PEN_CHUNK ticks a lane starts again from a full evaluation (anchor: at the chunk heads that are its OWN boundaries -
+// bsk_kernels.hip: `since` - not at those other lanes' FSW phases cut), and a lane whose exponent jumps by more than 2^-6
 // takes the full evaluation for that tick (per lane: the others keep their increments, so a lane's result does not depend
 // on its neighbours in the wave).  The conditioning of the exponential itself - an ulp of |r| is 1e-13 of rho - is three
 // orders above either.  All three forms of the scenario kernel anchor at the same ticks and advance with the same
@@ -1171,7 +1172,7 @@ __device__ __forceinline__ V3 gravity_sh(const Hot& c, V3 p) {
 // gravity: point mass (+ closed-form J2): 15 / 22 fp64 ops; spherical harmonics above.
 // tsim is only used by the harmonics (planet rotation about the inertial z axis).
 // third-body perturbation relative to the central body: a3(r) = mu_s [ (s - r)/|s - r|^3 - s/|s|^3 ].
-// Evaluated exactly once per chunk of <= PEN_SLOTS ticks, at the chunk's first position r_c, and carried through
+// Evaluated exactly once per chunk of <= PEN_CHUNK ticks (of the lane's own: bsk_kernels.hip, `since`), at the chunk's first position r_c, and carried through
 // the RK4 stages by its gradient, the tidal tensor G = k (3 s^ s^T - 1), k = mu_s/|s|^3 (per launch, about the
 // planet's centre):  a3(r) ~ a3(r_c) + G (r - r_c) = A0 + G r.  What is dropped: the second-order term,
 // ~3 mu_s |r - r_c|^2 / |s|^4 = 5e-17 m/s^2 for the 7.6 km a chunk covers, and G's change between the planet's

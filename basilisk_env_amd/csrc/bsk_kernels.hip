@@ -325,6 +325,16 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     // of the loop (wave-uniform: the other lanes of the wave wait), so that the FSW chain is instantiated once.
     bool z0 = false;
     if constexpr (NRW > 0) z0 = navlag && tick == 0 && substeps_eff > 0;
+    // Full-scenario levels: the third body and the density are ANCHORED at the head of a chunk of ticks (bsk_device.hpp: Sun3, Atmo)
+    // and carried by increments inside it, so a spacecraft's low bits depend on where its anchors fall - and the chunks are
+    // wave-uniform, cut at the FSW ticks of EVERY lane of the wave.  A lane therefore anchors only at its OWN boundaries - the
+    // launch's first tick, its own FSW ticks, PEN_CHUNK ticks after its last anchor: a function of its own counters - and passes
+    // the chunk heads that other lanes' FSW phases cause with its increments running.  Its own boundaries enter the wave's
+    // trip count below, so each of them is a chunk head.  `since`: ticks since this lane's anchor.  The anchors themselves run
+    // for every lane at every head, as they always did; a lane that passes a head gets its previous values back behind them
+    // (a wave of one FSW phase - nearly all - skips that on one ballot).  tests/test_gpu_lane_independence.py holds it.
+    int since = 0;
+    bool own = true;
     unsigned long long dbg_waitA = 0, dbg_waitB = 0, dbg_chain = 0, dbg_bar = 0;      // (probe builds only: bsk_probes.hpp)
     if constexpr (PAIR) {
         static_assert(form_built(GRAV, DIAG, FEAT, SPLIT), "a wave-split form this cell is not built in (bsk_launch.hpp: form_built)");
@@ -420,7 +430,7 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
         };
         // One chunk's control decisions: a function of (phase, z0, tick, j) only - both waves evaluate it on identical
         // inputs, so their barrier sequences agree.
-        struct Chunk { int m; bool cond, fsw_any, anyz, zlane, needB, needB0; int t_latch; };
+        struct Chunk { int m; bool cond, fsw_any, anyz, zlane, needB, needB0; int t_latch; bool own, own_next; int own_all, next_all; };
         auto next_chunk = [&]() {
             Chunk q;
             q.m = substeps_eff - j;
@@ -438,11 +448,23 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
                 if (q.anyz) dist = 0;                      // t = 0 tick: latched without a step in between
                 z0 = false;
                 q.m = min(q.m, dist);
+                if constexpr (FULL) {                      // this lane's own anchor boundaries (see `since` above)
+                    own = since == 0 || q.cond || since >= PAIR_CHUNK;
+                    if (own) since = 0;
+                    q.m = min(q.m, PAIR_CHUNK - since);
+                }
             }
             q.m = wave_min_uniform(min(q.m, PAIR_CHUNK));
+            q.own = own; q.own_next = true; q.own_all = 1; q.next_all = 1;
             if constexpr (NRW > 0) {
                 phase += q.m;
                 if (phase >= fsw_every) phase -= fsw_every;
+                if constexpr (FULL) {
+                    since += q.m;
+                    q.own_next = phase == (navlag ? fsw_every - 1 : 0) || since >= PAIR_CHUNK;   // ... and whether the next head is one
+                    q.own_all = uni_any(!q.own) == 0;
+                    q.next_all = uni_any(!q.own_next) == 0;
+                }
             }
             j += q.m;
             q.needB0 = q.fsw_any && !navlag;               // same-tick chain: commands before the chunk's first step
@@ -472,14 +494,22 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
                 // exponentialAtmosphere at a position (the arithmetic of the single-wave tick loop), 0 below the skip density
                 // (anchored where the single-wave loop anchors: the launch's first tick, every chunk's first tick - whose
                 // density the last step of the chunk before it asks for)
-                bool atm_anchor = true;
+                bool atm_anchor = true, anchor_own = true;
+                int anchor_all = 1;
                 auto density = [&](V3 r) __attribute__((always_inline)) {
                     double rho = 0.0;
                     if (drag_cfg) {
                         const double r2 = dot(r, r);
                         const double rm = r2 * rsqrt_nr(r2);
-                        if (atm_anchor) rho = atm.anchor(kt, rm);
-                        else rho = atm.advance(kt, rm);
+                        if (atm_anchor) {                  // the next chunk's first density: a full evaluation for the lanes that anchor there
+                            if (BSK_LIKELY(anchor_all)) rho = atm.anchor(kt, rm);
+                            else {
+                                Atmo an = atm;
+                                const double ra = an.anchor(kt, rm), rb = atm.advance(kt, rm);
+                                if (anchor_own) atm = an;
+                                rho = anchor_own ? ra : rb;
+                            }
+                        } else rho = atm.advance(kt, rm);
                     }
                     return rho;
                 };
@@ -506,7 +536,12 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
                         read_cmd();
                     }
                     if constexpr (!ROT) {
+                        const V3 a0_kept = ev.s3.A0;
                         if (ev.sun_on) third_body_anchor(ev.s3, mk(PL->sun[0][lane], PL->sun[1][lane], PL->sun[2][lane]), a.extra.mu_sun, x.r);
+                        if (BSK_UNLIKELY(!q.own_all)) {    // lanes of other FSW phases pass this head with what they had
+                            if (!q.own) ev.s3.A0 = a0_kept;
+                        }
+                        anchor_own = q.own_next; anchor_all = q.next_all;
                     }
                     for (int t = 0; t < m; ++t, ++tick) {
                         V3 v1 = mk(0, 0, 0), Tw = mk(0, 0, 0), pw = mk(0, 0, 0);
@@ -601,10 +636,13 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
                     read_cmd();
                 }
                 if constexpr (FULL) {
+                    const V3 a0_kept = ev.s3.A0;
+                    const Atmo atm_kept = atm;
                     if (ev.sun_on) third_body_anchor(ev.s3, mk(PL->sun[0][lane], PL->sun[1][lane], PL->sun[2][lane]), a.extra.mu_sun, x.r);
-                }
-                if constexpr (FULL) {
                     if (drag_cfg) { const double r2 = dot(x.r, x.r); atm.anchor(kt, r2 * rsqrt_nr(r2)); }
+                    if (BSK_UNLIKELY(!q.own_all)) {        // lanes of other FSW phases pass this head with what they had
+                        if (!q.own) { ev.s3.A0 = a0_kept; atm = atm_kept; }
+                    }
                 }
                 for (int t = 0; t < m; ++t, ++tick) {
                     const V3 lx = mk(PL->lext[0][lane], PL->lext[1][lane], PL->lext[2][lane]);   // (parked in LDS)
@@ -753,6 +791,11 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
             z0 = false;
             m = min(m, dist);
             if constexpr (POWER) m = min(m, PEN_CHUNK);
+            if constexpr (FULL) {                      // this lane's own anchor boundaries (see `since` above)
+                own = since == 0 || fsw_here || since >= PEN_CHUNK;
+                if (own) since = 0;
+                m = min(m, PEN_CHUNK - since);
+            }
             // The DPP-broadcast harmonics need every lane active inside the RK4 loop, so the trip count is
             // made wave-uniform: envs of one wave that sit at different FSW phases (after a masked reset)
             // advance together to the nearest FSW tick of any of them.
@@ -779,8 +822,14 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
         j += m;
         if constexpr (FULL) {
             const probe::Stamp pc_anchor = probe::stamp<probe::CHUNK == 5>();
+            const V3 a0_kept = ev.s3.A0;
+            const Atmo atm_kept = atm;
             if (ev.sun_on) third_body_anchor(ev.s3, sg.sun, a.extra.mu_sun, x.r);   // exact at the chunk's first position
             if (drag_cfg_u) atm.anchor(kt, pre.r2 * rsqrt_nr(pre.r2));             // ... and the density's full evaluation
+            if (BSK_UNLIKELY(uni_any(!own) != 0)) {     // lanes of other FSW phases pass this head with what they had
+                if (!own) { ev.s3.A0 = a0_kept; atm = atm_kept; }
+            }
+            if constexpr (NRW > 0) since += m;
             probe::since<probe::CHUNK == 5>(dbg_chain, pc_anchor);
         }
         // ---- the chunk's ticks.  A tick = head (what decides which instantiation of the step runs: the atmosphere's density,
