@@ -470,14 +470,17 @@ struct TriLds {
 typedef TriX __attribute__((address_space(3))) * TriXP;
 typedef TriLds __attribute__((address_space(3))) * TriP;
 
-// Halves form (SPLIT == 6): the bare one-sub-step launch as a rotational wave (wave 0: attitude, wheels, FSW chain, observation,
-// reward, every store but r, v) and a translational wave (wave 1: r, v) of the SAME 64 spacecraft.  At the bare level nothing
-// couples the two inside the RK4 step (gravity reads r only), so they meet through this block at barriers alone: the loaded
-// (r, v) on launches with an FSW tick (the chain's navigation input: the translational wave overwrites the rows early), and the
-// "below r_min" ballot of the end-of-step position.
+// Halves form (SPLIT == 6): the bare one-sub-step launch as a rotational wave (wave 0: attitude, wheels, FSW chain, the stores of
+// its own state rows) and a translational wave (wave 1: r, v, and the launch's epilogue - observation, reward, reason, done mask,
+// counters, episode statistics, wave sum) of the SAME 64 spacecraft.  At the bare level nothing couples the two inside the RK4 step
+// (gravity reads r only), so they meet through this block at barriers alone: the loaded (r, v) on launches with an FSW tick (the
+// chain's navigation input: the translational wave overwrites the rows early), and - on every launch - the three values the
+// epilogue needs of the rotational result.  The rotational wave is the late one: the translational wave, long done with r and v,
+// has the epilogue's arguments, addresses and counter arithmetic ready when those three arrive.
 struct HalvesLds {
     double rv[6][64];                         // translational -> rotational: the loaded r, v (launches with an FSW tick only)
-    unsigned long long orbit;                 // translational -> rotational: ballot of |r|^2 < r_min2 at the end of the step
+    double hand[3][64];                       // rotational -> translational: |omega|^2, sum Omega_k^2, |sigma_BR| (held or fresh)
+    unsigned long long dbg;                   // rotational -> translational, probe builds only: the wave's debug word (bsk_probes.hpp)
     unsigned long long pad_;
 };
 typedef HalvesLds __attribute__((address_space(3))) * HalvesP;

@@ -49,6 +49,43 @@ __device__ __forceinline__ int halves_fsw_due(int cnt_x, int nav_lag, int fsw_ev
     return uni_any((cnt_x >> 20) == (nav_lag != 0 ? fsw_every - 1 : 0));
 }
 
+// Halves form: the FSW phase a launch of ONE sub-step leaves in the counter word.  The tick loop advances the phase by the ticks of
+// each chunk and wraps it at fsw_every; a launch of one sub-step is one chunk of one tick whatever opened it (the t = 0 chain's
+// chunk of zero ticks moves nothing; nav_lag only decides at which phase the chain runs), so the rule needs no loop.  The wave
+// that writes the counters back (the translational one) has no loop to take it from.
+__device__ __forceinline__ int halves_phase_after(int cnt_x, int fsw_every) {
+    const int phase = (cnt_x >> 20) + 1;
+    return phase >= fsw_every ? phase - fsw_every : phase;
+}
+
+// Reward and termination of an env step from its observation (reference envs/leoPowerAttitudeEnvironment.py:98-127): declares
+// `int why; double rew;`.  One statement for the epilogue of every form and the halves form's own (its translational wave).
+// `static_o3`: obs[3] is a reset-time constant and no battery is empty (StepArgs::static_charge); `r2`: |r|^2 at the end of the step.
+// (A macro: as an inlined function the same lines moved the instruction selection of every single-wave kernel - compare
+// polarities, operand orders - and the forms a change to one epilogue does not concern keep their instruction streams.)
+#define BSK_STEP_OUTCOME(oc, action, steps0, o0, o2, o3, static_o3, r2)                                   \
+    int why = 0;                                                                                          \
+    double rew = ((action) == 0) ? (oc).reward_mult * rcp_nr(fma((o0), (o0), 1.0)) : 0.0;                 \
+    if ((steps0) >= (oc).max_length) why |= BSK_DONE_LENGTH;                                              \
+    if ((o2) > 1.0) { why |= BSK_DONE_WHEELS; rew -= (oc).failure_penalty; }                              \
+    if (!(static_o3) && (o3) == 0.0) { why |= BSK_DONE_BATTERY; rew -= (oc).failure_penalty; }            \
+    if ((r2) < (oc).r_min2) why |= BSK_DONE_ORBIT
+
+// The post-loop arguments, re-read from the kernarg segment through an opaque pointer: the compiler cannot hoist these scalar
+// loads above the point of the call, so they cost the code before it no SGPRs.
+// ... and in ONE batch: fetched field by field where they are used, the ~11 scalar loads of the epilogue were
+// eleven dependent round trips on the critical path of a K = 1 launch (a wave alone on its SIMD waits each out)
+template <int NRW, bool DIAG>
+__device__ __forceinline__ TailArgs load_tail() {
+    typedef const TailArgs __attribute__((address_space(4))) * TailPtr;
+    TailPtr tp = (TailPtr)((const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() +
+                           offsetof(StepArgs<NRW __COMMA__ DIAG>, tail));
+    asm volatile("" : "+s"(tp));
+    TailArgs ta;
+    __builtin_memcpy(&ta, (const TailArgs*)tp, sizeof(TailArgs));
+    return ta;
+}
+
 __device__ __forceinline__ int wave_min_uniform(int v) {
     // every lane holds the same value unless a masked reset staggered the FSW phases inside this wave: one ballot
     // settles the common case, the shuffle tree (six trips through the LDS crossbar) only runs when lanes differ
@@ -77,7 +114,8 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     constexpr bool TRI = SPLIT == 3;
     constexpr bool PAIR = SPLIT == 2 || TRI;
     // SPLIT == 6 (halves form, bsk_device.hpp: HalvesLds): a 128-thread workgroup = the rotational wave (this function's single-wave
-    // path without r, v) and the translational wave (the block below) of the same 64 spacecraft
+    // path without r, v, up to the end of the tick loop) and the translational wave (the block below: r, v and the launch's
+    // epilogue) of the same 64 spacecraft
     constexpr bool HALVES = SPLIT == 6;
     const int gid = (SPLIT == 5) ? (int)(blockIdx.x * 128 + (threadIdx.x >> 7) * 64 + (threadIdx.x & 63))
                   : (PAIR || HALVES) ? (int)(blockIdx.x * 64 + (threadIdx.x & 63))
@@ -93,7 +131,8 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     if constexpr (HALVES) {
         static_assert(form_built(GRAV, DIAG, FEAT, SPLIT, NRW), "the halves form: bare level, point mass or J2, with wheels (bsk_launch.hpp: form_built)");
         // ---- translational wave: r, v of the launch's one RK4 step (bsk_capi.hip, choose_form: substeps == 1, nav_lag != 0, no
-        // IC pool), stored as soon as they are final; it meets the rotational wave at barriers only
+        // IC pool), stored as soon as they are final, and then the launch's epilogue (bsk_device.hpp: HalvesLds); it meets the
+        // rotational wave at barriers only
         if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0) {
             const HalvesP HL = (HalvesP)lds_dyn;
             const int hl = (int)(threadIdx.x & 63u);
@@ -101,6 +140,13 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
             xt.r = mk(ldf(FLD(BSK_F_R + 0), bo), ldf(FLD(BSK_F_R + 1), bo), ldf(FLD(BSK_F_R + 2), bo));
             xt.v = mk(ldf(FLD(BSK_F_V + 0), bo), ldf(FLD(BSK_F_V + 1), bo), ldf(FLD(BSK_F_V + 2), bo));
             const int2 cnt_t = *reinterpret_cast<const int2*>(reinterpret_cast<const char*>(a.cnt) + bo);
+            // what the epilogue reads beside the state: the action, the battery charge where obs[3] is not static, the running return
+            const int action_t = *reinterpret_cast<const int*>(reinterpret_cast<const char*>(a.act) + (bo >> a.act_shift));
+            double charge_t = 1.0;
+            if (BSK_UNLIKELY(a.static_charge == 0)) charge_t = ldf(FLD(BSK_NF_BASE + NRW + BSK_T_CHARGE), bo);
+            double ep_ret_t = 0.0;
+            if (BSK_UNLIKELY(a.ep_return != nullptr)) ep_ret_t = ldf(a.ep_return, bo);
+            const TailArgs ta = load_tail<NRW, DIAG>();
             asm volatile("" ::"s"(c.h), "s"(c.h2), "s"(c.h3), "s"(c.h6), "s"(c.nmu), "s"(c.j2k));
             if (halves_fsw_due(cnt_t.x, a.nav_lag, c.fsw_every)) {
                 // the FSW chain of the other wave navigates on the LOADED r, v (nav_lag): handed over before the rows are overwritten
@@ -111,14 +157,63 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
             const Env ev_t{};
             const WheelV<NRW> wv_t{};
             rk4_step<GRAV, NRW, DIAG, FEAT, SPLIT, false, 0, PART_TRA>(c, wv_t, xt, nullptr, mk(0, 0, 0), (double)cnt_t.y * c.h, ev_t);
-            const gptr<double> so_t = uniform_ptr(a.tail.st);
+            const gptr<double> so_t = uniform_ptr(ta.st);
             stf(so_t + (int64_t)(BSK_F_R + 0) * S, bo, xt.r.x); stf(so_t + (int64_t)(BSK_F_R + 1) * S, bo, xt.r.y);
             stf(so_t + (int64_t)(BSK_F_R + 2) * S, bo, xt.r.z);
             stf(so_t + (int64_t)(BSK_F_V + 0) * S, bo, xt.v.x); stf(so_t + (int64_t)(BSK_F_V + 1) * S, bo, xt.v.y);
             stf(so_t + (int64_t)(BSK_F_V + 2) * S, bo, xt.v.z);
-            const unsigned long long below = __builtin_amdgcn_ballot_w64(dot(xt.r, xt.r) < a.tail.obs_cfg.r_min2);
-            if (hl == 0) HL->orbit = below;
+            // ---- the launch's epilogue (the single-wave form's, below, for the bare level without an IC pool: same operations in
+            // the same order, tests/test_gpu_halves*.py hold the two bit for bit).  First what needs no rotational result, while
+            // the rotational wave is still integrating ...
+            const double r2_t = dot(xt.r, xt.r);       // ("below r_min" is this wave's own: nothing travels for it any more)
+            const int64_t SO = uniform64(ta.ostride);
+            const int steps0 = cnt_t.x & 0xFFFFF;
+            const unsigned long long packed = (unsigned long long)(unsigned)(min(steps0 + 1, 0xFFFFF) | (halves_phase_after(cnt_t.x, c.fsw_every) << 20)) |
+                                              ((unsigned long long)(unsigned)(cnt_t.y + ta.substeps) << 32);
+            const bool static_o3 = ta.static_charge != 0;
+            const double o3 = charge_t * ta.obs_cfg.charge_scale;
+            const gptr<double> ob = uniform_ptr(ta.obs), ob1 = ob + SO, ob2 = ob + 2 * SO, ob3 = ob + 3 * SO, ob4 = ob + 4 * SO;
+            // (left to the compiler all of this sinks behind the barrier, to where it is used: the empty asm holds it in front)
+            asm volatile("" ::"v"(r2_t), "v"(packed), "v"(o3), "v"(steps0), "s"(ob1), "s"(ob2), "s"(ob3), "s"(ob4));
+            // ... then, behind the form's last barrier, the three values that do: |omega|^2, sum Omega_k^2, |sigma_BR|
             __syncthreads();
+            const double o0 = HL->hand[2][hl];
+            const double o1 = sqrt_nr(HL->hand[0][hl]);
+            const double o2 = sqrt_nr(HL->hand[1][hl]) * ta.obs_cfg.inv_wheel_limit;
+            const double o4 = 1.0;                       // (no power system: the shadow factor never moves)
+            BSK_STEP_OUTCOME(ta.obs_cfg, action_t, steps0, o0, o2, o3, static_o3, r2_t);
+            const unsigned long long dmask = __ballot(valid && why != 0);
+            if (hl == 0) {
+                if constexpr (probe::CHUNK != 0) {       // probe builds: the rotational wave's word, never in the done mask
+                    if (ta.dbg) ta.dbg[gid >> 6] = HL->dbg;
+                }
+                ta.done_mask[gid >> 6] = dmask;
+            }
+            // (tail lanes shadow env n-1: same address, same value, no mask)
+            *(gptr<unsigned long long>)((gptr<char>)uniform_ptr(ta.cnt) + bo) = packed;
+            stf(ob, bo, o0); stf(ob1, bo, o1); stf(ob2, bo, o2);
+            if (!static_o3) stf(ob3, bo, o3);
+            stf(ob4, bo, o4);
+            if (ta.obs_rm) {       // optional row-major copy (N, 5)
+                double* __restrict__ rm = ta.obs_rm + (int64_t)i * 5;
+                rm[0] = o0; rm[1] = o1; rm[2] = o2; rm[4] = o4;
+                if (!static_o3) rm[3] = o3;
+            }
+            stf(uniform_ptr(ta.reward), bo, rew);
+            ta.reason[i] = (unsigned char)why;
+            if (ta.ep_return) {    // episode statistics: 'r' includes this step's reward, 'l' = env steps taken before this one
+                ep_ret_t += rew;
+                if (why != 0) {
+                    stf(uniform_ptr(ta.term_return), bo, ep_ret_t);
+                    ta.term_len[i] = steps0;
+                }
+                stf(uniform_ptr(ta.ep_return), bo, ep_ret_t);
+                ta.done[i] = why != 0 ? 1 : 0;
+            }
+            if (BSK_UNLIKELY(ta.wave_sum != nullptr)) {
+                const double ws = wave_sum(valid ? rew : 0.0);
+                if (hl == 0) ta.wave_sum[gid >> 6] = ws;
+            }
             return;
         }
     }
@@ -138,7 +233,10 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     const V3 lext = mk(ldf(FLD(TAIL + BSK_T_LEXT + 0), bo), ldf(FLD(TAIL + BSK_T_LEXT + 1), bo),
                        ldf(FLD(TAIL + BSK_T_LEXT + 2), bo));
     double charge = 1.0;     // (bare levels with StepArgs::static_charge: never read - any non-zero value)
+    // (halves form: the charge and the running return are the epilogue's, loaded by the wave that runs it)
+    if constexpr (!HALVES) {
     if (FEAT >= FEAT_POWER || BSK_UNLIKELY(a.static_charge == 0)) charge = ldf(FLD(TAIL + BSK_T_CHARGE), bo);
+    }
     const int2 cnt = *reinterpret_cast<const int2*>(reinterpret_cast<const char*>(a.cnt) + bo);  // {steps | phase << 20, ticks}
     // (int32 actions, or the low words of int64 ones - torch's argmax output - read in place: a.act_shift)
     const int action = *reinterpret_cast<const int*>(reinterpret_cast<const char*>(a.act) + (bo >> a.act_shift));
@@ -154,7 +252,9 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
 #undef FLD
     // device-resident episode statistics (BSK_FLAG_EPISODE_STATS): the running return travels with the state's loads
     double ep_ret = 0.0;
+    if constexpr (!HALVES) {
     if (BSK_UNLIKELY(a.ep_return != nullptr)) ep_ret = ldf(a.ep_return, bo);
+    }
     // The loop's first scalar constants, fetched while the state's loads are in flight: left to the compiler their
     // scalar loads sit behind the wait for the state - one more round trip on a K = 1 launch's critical path.
     asm volatile("" ::"s"(c.fsw_every), "s"(c.h), "s"(c.h2), "s"(c.h3), "s"(c.h6), "s"(c.nmu), "s"(c.j2k), "s"(c.Dm[0]), "s"(c.Dm[1]));
@@ -961,16 +1061,42 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     if constexpr (probe::CHUNK != 0) dbg_waitA = probe::elapsed(pc_loop);
     }   // !PAIR
 
-    // Re-read the post-loop arguments from the kernarg segment through an opaque pointer: the
-    // compiler cannot hoist these scalar loads above the loop, so they cost it no SGPRs.
-    typedef const TailArgs __attribute__((address_space(4))) * TailPtr;
-    TailPtr tp = (TailPtr)((const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() +
-                           offsetof(StepArgs<NRW __COMMA__ DIAG>, tail));
-    asm volatile("" : "+s"(tp));
-    // ... and in ONE batch: fetched field by field where they are used, the ~11 scalar loads of the epilogue were
-    // eleven dependent round trips on the critical path of a K = 1 launch (a wave alone on its SIMD waits each out)
-    TailArgs ta;
-    __builtin_memcpy(&ta, (const TailArgs*)tp, sizeof(TailArgs));
+    if constexpr (HALVES) {
+        // ---- rotational wave: the epilogue runs in the translational wave, which has been waiting for exactly these three values
+        // (the operands of obs[1], obs[2] and obs[0] as the single-wave form forms them: same operations, same order).  |sigma_BR|
+        // travels on every launch - held or fresh, the t = 0 chain's included - so no launch needs a decision about it.
+        const HalvesP HL = (HalvesP)lds_dyn;
+        HL->hand[0][lane] = dot(x.w, x.w);
+        double om2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < NRW; ++k) om2 = fma(x.Om[k], x.Om[k], om2);
+        HL->hand[1][lane] = om2;
+        HL->hand[2][lane] = sbr;
+        if constexpr (probe::CHUNK != 0) {      // (the word of the single-wave form's probe, below)
+            if (lane == 0) HL->dbg = ((dbg_chain >> 4) & 0xFFFFFFFFull) | (((dbg_waitA >> 4) & 0xFFFFFFFFull) << 32);
+        }
+        __syncthreads();
+        // ... and this wave stores its own rows and ends, with what it has held since its loads: a.st, a.stride, a.fsw_lag
+        const gptr<double> so = uniform_ptr(const_cast<double*>(st));
+        stf(so + (int64_t)(BSK_F_SIGMA + 0) * S, bo, x.s.x); stf(so + (int64_t)(BSK_F_SIGMA + 1) * S, bo, x.s.y);
+        stf(so + (int64_t)(BSK_F_SIGMA + 2) * S, bo, x.s.z);
+        stf(so + (int64_t)(BSK_F_OMEGA + 0) * S, bo, x.w.x); stf(so + (int64_t)(BSK_F_OMEGA + 1) * S, bo, x.w.y);
+        stf(so + (int64_t)(BSK_F_OMEGA + 2) * S, bo, x.w.z);
+#pragma unroll
+        for (int k = 0; k < NRW; ++k) stf(so + (int64_t)(BSK_NF_BASE + k) * S, bo, x.Om[k]);
+        if (fsw_ran) {
+#pragma unroll
+            for (int k = 0; k < NRW; ++k) stf(so + (int64_t)(TAIL + BSK_T_UCMD + k) * S, bo, u[k]);
+            if (a.fsw_lag) {
+#pragma unroll
+                for (int k = 0; k < NRW; ++k) stf(so + (int64_t)(TAIL + BSK_T_UPEND + k) * S, bo, up[k]);
+            }
+            stf(so + (int64_t)(TAIL + BSK_T_SBR) * S, bo, sbr);
+        }
+        return;
+    }
+    // (every other form: the epilogue, in the wave that integrated)
+    const TailArgs ta = load_tail<NRW, DIAG>();
     const int64_t S2 = uniform64(ta.stride);
     const int64_t SO = uniform64(ta.ostride);      // observation rows: unpadded (the slab's rows are: bsk_capi.hip, bsk_create)
     const int n2 = ta.n;
@@ -988,7 +1114,7 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     // obs[0] is the logged att_guidance message: with nav_lag the one the last FSW tick wrote (held in `sbr`),
     // otherwise the tracking error of the end-of-step state under the step's mode
     double o0 = sbr;
-    if (!HALVES && !(NRW > 0 && ta.nav_lag != 0)) {
+    if (!(NRW > 0 && ta.nav_lag != 0)) {
         double sR0N[3] = {ta.obs_cfg.sigma_R0N[0], ta.obs_cfg.sigma_R0N[1], ta.obs_cfg.sigma_R0N[2]};
         const Guid g = guidance<NRW>(sR0N, x, action);
         o0 = sqrt_nr(dot(g.sigma_BR, g.sigma_BR));
@@ -1003,17 +1129,7 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     const double o4 = shadow;
 
     // reward and termination
-    int why = 0;
-    double rew = (action == 0) ? ta.obs_cfg.reward_mult * rcp_nr(fma(o0, o0, 1.0)) : 0.0;
-    if (steps0 >= ta.obs_cfg.max_length) why |= BSK_DONE_LENGTH;
-    if (o2 > 1.0) { why |= BSK_DONE_WHEELS; rew -= ta.obs_cfg.failure_penalty; }
-    if (!static_o3 && o3 == 0.0) { why |= BSK_DONE_BATTERY; rew -= ta.obs_cfg.failure_penalty; }
-    if constexpr (HALVES) {       // the translational wave's ballot of the end-of-step position
-        __syncthreads();
-        if ((((HalvesP)lds_dyn)->orbit >> lane) & 1ull) why |= BSK_DONE_ORBIT;
-    } else {
-        if (dot(x.r, x.r) < ta.obs_cfg.r_min2) why |= BSK_DONE_ORBIT;
-    }
+    BSK_STEP_OUTCOME(ta.obs_cfg, action, steps0, o0, o2, o3, static_o3, dot(x.r, x.r));
 
     if constexpr (SPLIT == 5) {
         if (threadIdx.x & 64) return;    // the second wave of each pair only helped with the harmonics
@@ -1044,7 +1160,7 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     gptr<double> so = uniform_ptr(ta.st);
     gptr<double> ob = uniform_ptr(ta.obs);
 #define FLD(f) (so + (int64_t)(f) * S2)
-    const int n_pool = HALVES ? 0 : ta.n_pool;      // (the halves form runs on handles without an IC pool)
+    const int n_pool = ta.n_pool;
     if (n_pool > 0 && why != 0) {
       if (valid2) {   // tail lanes shadow env n-1: its own lane performs the reset, they must not repeat it
         // Device-side auto-reset (rare, divergent): reload this env from the staged IC pool, keep the
@@ -1080,10 +1196,8 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
         *(gptr<unsigned long long>)((gptr<char>)uniform_ptr(ta.cnt) + bo) = 0ull;
       }
     } else {
-        if constexpr (!HALVES) {   // (the translational wave has stored them)
         stf(FLD(BSK_F_R + 0), bo, x.r.x); stf(FLD(BSK_F_R + 1), bo, x.r.y); stf(FLD(BSK_F_R + 2), bo, x.r.z);
         stf(FLD(BSK_F_V + 0), bo, x.v.x); stf(FLD(BSK_F_V + 1), bo, x.v.y); stf(FLD(BSK_F_V + 2), bo, x.v.z);
-        }
         stf(FLD(BSK_F_SIGMA + 0), bo, x.s.x); stf(FLD(BSK_F_SIGMA + 1), bo, x.s.y); stf(FLD(BSK_F_SIGMA + 2), bo, x.s.z);
         stf(FLD(BSK_F_OMEGA + 0), bo, x.w.x); stf(FLD(BSK_F_OMEGA + 1), bo, x.w.y); stf(FLD(BSK_F_OMEGA + 2), bo, x.w.z);
 #pragma unroll
