@@ -98,13 +98,15 @@ EXPORTS = [
     "bsk_obs_stats_create", "bsk_obs_stats_destroy", "bsk_obs_stats_accumulate", "bsk_obs_stats_get", "bsk_obs_stats_totals_device",
     "bsk_obs_stats_get_state", "bsk_obs_stats_set_state", "bsk_obs_stats_reset", "bsk_population_set_obs_stats",
     "bsk_policy_set_obs_stats", "bsk_es_apply_obs_norm",
+    "bsk_fit_create", "bsk_fit_destroy", "bsk_fit_accumulate", "bsk_fit_step", "bsk_fit_stats_device", "bsk_fit_get_state",
+    "bsk_fit_set_state", "bsk_fit_set_lr", "bsk_fit_alive_mask",
     "bsk_profile_begin", "bsk_profile_set_stride", "bsk_profile_end", "bsk_profile_end_samples", "bsk_calibrate_fp64", "bsk_kernel_info", "bsk_last_error", "bsk_version",
 ]
 
 
 def _signatures():
     """Every export of include/bskgpu.h -> (argtypes, restype); ``rc`` is the status that all return but the two strings and the
-    five destroys."""
+    six destroys."""
     P, vp, rc, i, i64, u64, f64 = C.POINTER, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_uint64, C.c_double
     spec = P(BskPolicySpec)
     return {
@@ -160,6 +162,11 @@ def _signatures():
         "bsk_obs_stats_set_state": ([vp, vp, vp], rc), "bsk_obs_stats_reset": ([vp, vp], rc),
         "bsk_population_set_obs_stats": ([vp, vp], rc), "bsk_policy_set_obs_stats": ([vp, vp], rc),
         "bsk_es_apply_obs_norm": ([vp, vp, f64, vp], rc),
+        "bsk_fit_create": ([vp, f64, f64, f64, f64, f64, f64, P(vp)], rc), "bsk_fit_destroy": ([vp], None),
+        "bsk_fit_accumulate": ([vp, vp, i64, i, vp, vp, vp, vp, i64, vp], rc), "bsk_fit_step": ([vp, vp], rc),
+        "bsk_fit_stats_device": ([vp, P(vp)], rc), "bsk_fit_get_state": ([vp, vp, vp, vp, vp, P(u64)], rc),
+        "bsk_fit_set_state": ([vp, vp, vp, vp, vp, u64], rc), "bsk_fit_set_lr": ([vp, f64], rc),
+        "bsk_fit_alive_mask": ([vp, i, i, vp, vp], rc),
         "bsk_profile_begin": ([vp, i], rc), "bsk_profile_set_stride": ([vp, i], rc), "bsk_profile_end": ([vp, P(f64), P(i)], rc),
         "bsk_profile_end_samples": ([vp, P(f64), P(i), vp, i], rc), "bsk_calibrate_fp64": ([i, i, i, P(f64), P(f64)], rc),
         "bsk_kernel_info": ([vp, C.c_char_p, i, P(i), P(i), P(i), P(i)], rc),

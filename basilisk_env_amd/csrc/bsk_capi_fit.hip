@@ -1,0 +1,196 @@
+// bsk_capi_fit.hip — C-ABI of the supervised fit of a policy to labelled observations (bsk_fit_*): accumulate block gradients of a
+// cross-entropy (and, optionally, a squared value error) from device buffers, then one Adam step into the attached policy's own
+// parameters.  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_fit.hip.  The policy it reads and writes through
+// its handle: bsk_capi_policy.hpp.
+#include <cmath>
+
+#include "bsk_capi_policy.hpp"
+#include "bsk_fit.hpp"
+
+using namespace bsk::capi;
+
+// bsk_fit_*: ONE allocation of 8-byte words [theta np | m np | v np | beta_pow 2 | A np | row 4 | count | steps] and, from the first
+// accumulate on, the scratch of the block gradients: [G n_blocks * np floats | diag n_blocks * 4 doubles]
+struct bsk_fit {
+    bsk_policy* policy = nullptr;          // not owned: what accumulate reads and step writes
+    int device = 0;
+    double lr = 0.0, beta1 = 0.0, beta2 = 0.0, eps = 0.0, weight_decay = 0.0;
+    float value_coef = 0.0f;
+    double* d_state = nullptr;
+    void* d_scratch = nullptr;
+    int blocks_cap = 0;
+    bool value_seen = false;               // some accumulate since the last step carried value targets: the step moves the value network
+
+    size_t np() const { return (size_t)policy->lay.n_params; }
+    double* theta() const { return d_state; }
+    double* m() const { return d_state + np(); }
+    double* v() const { return d_state + 2 * np(); }
+    double* beta_pow() const { return d_state + 3 * np(); }
+    double* A() const { return d_state + 3 * np() + 2; }
+    double* row() const { return d_state + 4 * np() + 2; }
+    unsigned long long* count() const { return (unsigned long long*)(d_state + 4 * np() + 6); }
+    unsigned long long* steps() const { return count() + 1; }
+    size_t words() const { return 4 * np() + 8; }
+    // where the action network's parameters end in the C-ABI block: all a fit without value targets folds and moves
+    int action_end() const {
+        const bsk::PolicyLayout& lay = policy->lay;
+        return lay.v.n_layers > 0 ? bsk::policy_pack_map(lay).layer[lay.a.n_layers].src : lay.n_params;
+    }
+};
+
+namespace {
+
+bool finite_nonneg(double x) { return std::isfinite(x) && x >= 0.0; }
+
+// (float)theta into the policy's device layout: the gather of bsk_es_set_validation's centre members
+int write_policy(bsk_fit* f, hipStream_t s) {
+    HIP_TRY(bsk::launch_es_center(f->policy->lay, f->theta(), f->policy->d_params, 1, s));
+    return BSK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bsk_fit_create(bsk_policy* p, double lr, double beta1, double beta2, double eps, double weight_decay, double value_coef, bsk_fit** out) {
+    if (!out) return fail(BSK_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (!p) return fail(BSK_EINVAL, "policy is NULL");
+    if (!finite_nonneg(lr)) return fail(BSK_EINVAL, "bsk_fit_create: lr must be finite and not negative");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(BSK_EINVAL, "bsk_fit_create: beta1 and beta2 must be in [0, 1)");
+    if (!std::isfinite(eps) || !(eps > 0.0)) return fail(BSK_EINVAL, "bsk_fit_create: eps must be finite and positive");
+    if (!finite_nonneg(weight_decay)) return fail(BSK_EINVAL, "bsk_fit_create: weight_decay must be finite and not negative");
+    if (!finite_nonneg(value_coef)) return fail(BSK_EINVAL, "bsk_fit_create: value_coef must be finite and not negative");
+    DeviceGuard guard(p->device);
+    bsk_fit* f = new bsk_fit();
+    f->policy = p;
+    f->device = p->device;
+    f->lr = lr; f->beta1 = beta1; f->beta2 = beta2; f->eps = eps; f->weight_decay = weight_decay;
+    f->value_coef = (float)value_coef;
+    // theta := the policy's current parameters, widened; m = v = A = 0, beta_pow = {1, 1}, count = steps = 0
+    const bsk::PolicyLayout& lay = p->lay;
+    std::vector<float> dev((size_t)lay.n_device), params((size_t)lay.n_params);
+    std::vector<double> state(f->words(), 0.0);
+    int rc = transfer(p->device, hipMemcpyDeviceToHost, {{dev.data(), p->d_params, dev.size() * sizeof(float)}});
+    if (rc) { delete f; return rc; }
+    bsk::policy_unpack(lay, dev.data(), params.data());
+    for (size_t j = 0; j < params.size(); ++j) state[j] = (double)params[j];
+    state[3 * f->np()] = state[3 * f->np() + 1] = 1.0;
+    auto upload = [&]() -> int {
+        HIP_TRY(hipMalloc(&f->d_state, state.size() * 8));
+        HIP_COPY(hipMemcpy(f->d_state, state.data(), state.size() * 8, hipMemcpyHostToDevice));
+        return BSK_OK;
+    };
+    if ((rc = upload())) { bsk_fit_destroy(f); return rc; }
+    *out = f;
+    return BSK_OK;
+}
+
+void bsk_fit_destroy(bsk_fit* f) {
+    if (!f) return;
+    DeviceGuard guard(f->device);
+    free_all({f->d_state, f->d_scratch});
+    delete f;
+}
+
+int bsk_fit_accumulate(bsk_fit* f, const double* d_obs, int64_t obs_stride, int n, const int32_t* d_label, const double* d_value_target,
+                       const uint8_t* d_alive, float* d_dlogits, int64_t out_stride, void* stream) {
+    if (!f || !d_obs || !d_label) return fail(BSK_EINVAL, "fit/d_obs/d_label is NULL");
+    if (n < 1 || n > (1 << 28)) return fail(BSK_EINVAL, "bsk_fit_accumulate: n must be in 1..2^28");
+    if (obs_stride < n) return fail(BSK_EINVAL, "bsk_fit_accumulate: obs_stride must be >= n");
+    if (d_dlogits && out_stride < n) return fail(BSK_EINVAL, "bsk_fit_accumulate: out_stride must be >= n");
+    const bsk::PolicyLayout& lay = f->policy->lay;
+    if (d_value_target && lay.v.n_layers == 0) return fail(BSK_EINVAL, "bsk_fit_accumulate: d_value_target given, but the policy has no value network");
+    DeviceGuard guard(f->device);
+    const hipStream_t s = (hipStream_t)stream;
+    const int n_blocks = (n + bsk::FIT_BLOCK_SAMPLES - 1) / bsk::FIT_BLOCK_SAMPLES;
+    const size_t np = f->np();
+    if (f->blocks_cap < n_blocks) {
+        const size_t g_bytes = ((size_t)n_blocks * np * sizeof(float) + 15) / 16 * 16;
+        int rc = grow_scratch(&f->d_scratch, &f->blocks_cap, g_bytes + (size_t)n_blocks * 4 * sizeof(double), s,
+                              "bsk_fit_accumulate: the first accumulate of a size allocates the scratch of the block gradients and cannot be "
+                              "captured; make one such call outside the capture first");
+        if (rc) return rc;
+        f->blocks_cap = n_blocks;
+    }
+    const size_t g_bytes = ((size_t)f->blocks_cap * np * sizeof(float) + 15) / 16 * 16;
+    const bsk::PolicyPackMap map = bsk::policy_pack_map(lay);
+    bsk::FitArgs a = {};
+    a.params = f->policy->d_params;
+    a.a = bsk::fit_net(map, 0, lay.a);
+    if (d_value_target) a.v = bsk::fit_net(map, lay.a.n_layers, lay.v);
+    a.obs = d_obs; a.obs_stride = obs_stride; a.n = n;
+    a.label = d_label; a.target = d_value_target; a.alive = d_alive;
+    a.value_coef = f->value_coef;
+    a.dlogits = d_dlogits; a.out_stride = out_stride;
+    a.G = (float*)f->d_scratch;
+    a.diag = (double*)((char*)f->d_scratch + g_bytes);
+    a.n_params = lay.n_params;
+    a.rows = bsk::fit_lds_rows(lay);
+    HIP_TRY(bsk::launch_fit_blocks(a, s));
+    HIP_TRY(bsk::launch_fit_fold(a.G, a.diag, n_blocks, lay.n_params, d_value_target ? lay.n_params : f->action_end(), f->A(), f->row(),
+                                 f->count(), s));
+    if (d_value_target) f->value_seen = true;
+    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
+}
+
+int bsk_fit_step(bsk_fit* f, void* stream) {
+    if (!f) return fail(BSK_EINVAL, "fit is NULL");
+    DeviceGuard guard(f->device);
+    const hipStream_t s = (hipStream_t)stream;
+    bsk::EsAdam ad = {};
+    ad.m = f->m(); ad.v = f->v(); ad.beta_pow = f->beta_pow();
+    ad.beta1 = f->beta1; ad.beta2 = f->beta2;
+    ad.a1 = 1.0 - f->beta1; ad.a2 = 1.0 - f->beta2;
+    ad.eps = f->eps; ad.weight_decay = f->weight_decay;
+    ad.lr = f->lr;
+    HIP_TRY(bsk::launch_fit_step(f->theta(), f->A(), f->count(), f->steps(), f->value_seen ? f->policy->lay.n_params : f->action_end(), ad, s));
+    f->value_seen = false;
+    return write_policy(f, s);        // asynchronous on `stream`: no copy, no synchronisation
+}
+
+int bsk_fit_stats_device(bsk_fit* f, const double** d_row4) {
+    if (!f || !d_row4) return fail(BSK_EINVAL, "fit/d_row4 is NULL");
+    *d_row4 = f->row();
+    return BSK_OK;
+}
+
+int bsk_fit_get_state(bsk_fit* f, double* theta, double* m, double* v, double* beta_pow, uint64_t* steps) {
+    if (!f) return fail(BSK_EINVAL, "fit is NULL");
+    const size_t bytes = f->np() * sizeof(double);
+    return transfer(f->device, hipMemcpyDeviceToHost, {{theta, f->theta(), bytes}, {m, f->m(), bytes}, {v, f->v(), bytes},
+                                                       {beta_pow, f->beta_pow(), 2 * sizeof(double)}, {steps, f->steps(), 8}});
+}
+
+int bsk_fit_set_state(bsk_fit* f, const double* theta, const double* m, const double* v, const double* beta_pow, uint64_t steps) {
+    if (!f) return fail(BSK_EINVAL, "fit is NULL");
+    const size_t bytes = f->np() * sizeof(double);
+    const unsigned long long st = steps;
+    int rc = transfer(f->device, hipMemcpyHostToDevice, {{theta, f->theta(), bytes}, {m, f->m(), bytes}, {v, f->v(), bytes},
+                                                         {beta_pow, f->beta_pow(), 2 * sizeof(double)}, {&st, f->steps(), 8}});
+    if (rc) return rc;
+    DeviceGuard guard(f->device);
+    // what has been accumulated since the last step belongs to the state that is replaced: A, the count and the diagnostics row
+    // (contiguous words) start from zero, as behind a step
+    HIP_TRY(hipMemset(f->A(), 0, (f->np() + 5) * sizeof(double)));
+    f->value_seen = false;
+    if (theta && (rc = write_policy(f, nullptr))) return rc;          // a new theta is the policy's too: (float)theta
+    HIP_SYNC(hipDeviceSynchronize());
+    return BSK_OK;
+}
+
+int bsk_fit_set_lr(bsk_fit* f, double lr) {
+    if (!f) return fail(BSK_EINVAL, "fit is NULL");
+    if (!finite_nonneg(lr)) return fail(BSK_EINVAL, "bsk_fit_set_lr: lr must be finite and not negative");
+    f->lr = lr;
+    return BSK_OK;
+}
+
+int bsk_fit_alive_mask(const uint8_t* d_reason, int n, int first, uint8_t* d_alive, void* stream) {
+    if (!d_reason || !d_alive) return fail(BSK_EINVAL, "d_reason/d_alive is NULL");
+    if (n < 1) return fail(BSK_EINVAL, "bsk_fit_alive_mask: n must be >= 1");
+    HIP_TRY(bsk::launch_fit_alive(d_reason, n, first != 0, d_alive, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
+}
+
+}  // extern "C"

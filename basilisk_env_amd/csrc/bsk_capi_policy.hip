@@ -36,6 +36,22 @@ int transfer(int device, hipMemcpyKind dir, std::initializer_list<Field> fields)
     return BSK_OK;
 }
 
+// A rollout's scratch buffer is replaced by one of `bytes`: refused while `stream` is being captured; a queued rollout may still use
+// the smaller buffer, so the device is waited for before that is freed.  The caller decides when, and records the new capacity.
+int grow_scratch(void** d_buf, int* cap, size_t bytes, hipStream_t stream, const char* capture_msg) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(stream, &st));
+    if (st != hipStreamCaptureStatusNone) return fail(BSK_EINVAL, capture_msg);
+    if (*d_buf) {
+        HIP_SYNC(hipDeviceSynchronize());
+        (void)hipFree(*d_buf);
+        *d_buf = nullptr;
+        *cap = 0;
+    }
+    HIP_TRY(hipMalloc(d_buf, bytes));
+    return BSK_OK;
+}
+
 } }  // namespace bsk::capi
 
 namespace {
@@ -107,22 +123,6 @@ int get_rng(ParamStore* p, const char* null_msg, uint64_t* seed, uint64_t* draw)
     if (int rc = transfer(p->device, hipMemcpyDeviceToHost, {{w, p->d_rng, sizeof w}})) return rc;
     if (seed) *seed = w[0];
     if (draw) *draw = w[1];
-    return BSK_OK;
-}
-
-// A rollout's scratch buffer is replaced by one of `bytes`: refused while `stream` is being captured; a queued rollout may still use
-// the smaller buffer, so the device is waited for before that is freed.  The caller decides when, and records the new capacity.
-int grow_scratch(void** d_buf, int* cap, size_t bytes, hipStream_t stream, const char* capture_msg) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(stream, &st));
-    if (st != hipStreamCaptureStatusNone) return fail(BSK_EINVAL, capture_msg);
-    if (*d_buf) {
-        HIP_SYNC(hipDeviceSynchronize());
-        (void)hipFree(*d_buf);
-        *d_buf = nullptr;
-        *cap = 0;
-    }
-    HIP_TRY(hipMalloc(d_buf, bytes));
     return BSK_OK;
 }
 

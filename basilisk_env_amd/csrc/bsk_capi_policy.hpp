@@ -71,6 +71,11 @@ struct Field {
 // queued has written what a get reads, and has read what a set replaces - then one counted copy per field whose host is not NULL
 int transfer(int device, hipMemcpyKind dir, std::initializer_list<Field> fields);
 
+// A scratch buffer an enqueue-only entry point owns is replaced by one of `bytes`: refused with BSK_EINVAL and `capture_msg` while
+// `stream` is being captured; a queued launch may still use the smaller buffer, so the device is waited for before that is freed.
+// The caller decides when, and records the new capacity.
+int grow_scratch(void** d_buf, int* cap, size_t bytes, hipStream_t stream, const char* capture_msg);
+
 } }  // namespace bsk::capi
 
 // bsk_policy_*: the fused MLP policy (kernel and layout: bsk_policy.hip)

@@ -238,14 +238,8 @@ __global__ __launch_bounds__(256) void es_tell_adam_kernel(const EsArgs es, int 
     if (j >= n_params) return;
     ES_PAIR_SUM(es, w, j, lane, s);
     if (lane == 0) {
-        const double p1 = ad.beta_pow[0] * ad.beta1, p2 = ad.beta_pow[1] * ad.beta2;
         const double t = es.theta[j];
-        const double grad = ad.cg * s - ad.weight_decay * t;
-        const double m = ad.beta1 * ad.m[j] + ad.a1 * grad;
-        const double v = ad.beta2 * ad.v[j] + (ad.a2 * grad) * grad;
-        ad.m[j] = m;
-        ad.v[j] = v;
-        es.theta[j] = t + (ad.lr * (m / (1.0 - p1))) / (sqrt(v / (1.0 - p2)) + ad.eps);
+        es.theta[j] = t + adam_step(ad, j, ad.cg * s - ad.weight_decay * t);
     }
 }
 
@@ -301,14 +295,8 @@ __global__ __launch_bounds__(256) void es_tell_adam_sigma_kernel(const EsArgs es
     if (lane == 0) {
         const double sg = sv.sigma_vec[j];
         const double cg = 1.0 / (sv.pd * sg);                                                  // (ad.cg is the fixed mode's)
-        const double p1 = ad.beta_pow[0] * ad.beta1, p2 = ad.beta_pow[1] * ad.beta2;
         const double t = es.theta[j];
-        const double grad = cg * s - ad.weight_decay * t;
-        const double m = ad.beta1 * ad.m[j] + ad.a1 * grad;
-        const double v = ad.beta2 * ad.v[j] + (ad.a2 * grad) * grad;
-        ad.m[j] = m;
-        ad.v[j] = v;
-        es.theta[j] = t + (ad.lr * (m / (1.0 - p1))) / (sqrt(v / (1.0 - p2)) + ad.eps);
+        es.theta[j] = t + adam_step(ad, j, cg * s - ad.weight_decay * t);
         es_sigma_step(sv, j, sg, r);
     }
 }

@@ -25,6 +25,20 @@ struct EsAdam {
     double cg, lr;                     // cg = 1 / ((double)P * sigma)
 };
 
+// Adam's update of parameter j under the gradient `grad` (include/bskgpu.h, bsk_es_set_optimizer): the two moments are moved and
+// stored, and the bias-corrected step is returned - (lr * (m / (1 - p1))) / (sqrt(v / (1 - p2)) + eps), every operation rounded on
+// its own.  ONE text behind the evolution strategy, which ascends (theta + step), and the policy fit of bsk_fit.hip, which descends
+// (theta - step); beta_pow is read here and moved on by a one-thread launch behind the update.
+__device__ __forceinline__ double adam_step(const EsAdam& ad, int j, double grad) {
+#pragma clang fp contract(off)
+    const double p1 = ad.beta_pow[0] * ad.beta1, p2 = ad.beta_pow[1] * ad.beta2;
+    const double m = ad.beta1 * ad.m[j] + ad.a1 * grad;
+    const double v = ad.beta2 * ad.v[j] + (ad.a2 * grad) * grad;
+    ad.m[j] = m;
+    ad.v[j] = v;
+    return (ad.lr * (m / (1.0 - p1))) / (sqrt(v / (1.0 - p2)) + ad.eps);
+}
+
 // bsk_es_set_sigma_adaptation(BSK_ES_SIGMA_PGPE): the step size of every parameter and the constants of its update
 struct EsSigma {
     double* sigma_vec;                 // [n_params]; entries below `frozen` are carried, never read by a kernel and never moved

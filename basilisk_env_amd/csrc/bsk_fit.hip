@@ -1,0 +1,368 @@
+// bsk_fit.hip — a supervised fit of the MLP policy to labelled observations, on the device (bsk_fit_*; definition in
+// include/bskgpu.h): cross-entropy on the action, an optional squared error on the value, Adam.
+//   fit_block_kernel    one workgroup per block of 64 samples: the policy's forward pass with every layer kept, the output deltas,
+//                       the backward sweep and the block's gradient G_b in the C-ABI parameter order, plus its diagnostics terms
+//   fit_fold_kernel     one thread per parameter: A += (double)G_b, b ascending; four threads more for the diagnostics row
+//   fit_adam_kernel     one thread per parameter: the mean gradient through Adam (adam_step, bsk_es.hpp: the text of the
+//                       evolution strategy's update), a descent
+//   fit_advance_kernel  one thread: beta_pow and the step counter move on, the count back to zero
+//   fit_alive_kernel    bsk_fit_alive_mask: which envs of a collection loop are still in their first episode
+// The forward pass IS policy_kernel's: policy_hidden / policy_output of bsk_policy.hpp.  Every fused multiply-add is an explicit
+// fmaf and every chain has one owner that walks it in the definition's order, so neither the launch shape nor the hardware's
+// scheduling enters a bit: no atomics, no cross-lane reduction.  Compiled with -ffp-contract=off (Makefile) for the f64 parts.
+#include "bsk_fit.hpp"
+
+#include "../../include/bskgpu.h"
+
+// Measurement builds only (make fit-stamps -> variants/fit_stamps.so; tools/fit_measure.py stamps): thread 0 of every workgroup
+// counts the clock ticks of the weight-gradient walks, a barrier behind each, and of the whole kernel, and the block's diagnostics
+// terms [0] and [1] carry the two counts in place of the losses.  The product never compiles this in.
+#ifndef BSK_FIT_STAMPS
+#define BSK_FIT_STAMPS 0
+#endif
+
+namespace bsk {
+
+// LDS: rows of 64 floats, [unit][lane] as in policy_kernel.  Row 0 - 7: the network input x (five used); then every hidden layer of
+// the network in turn; then POLICY_OB rows of output deltas.  The backward sweep needs no rows of its own: the deltas of a hidden
+// layer replace its activations IN PLACE once the layer above has taken its weight gradient from them.
+constexpr int FIT_X_ROWS = 8;
+constexpr int FIT_FOLD_BATCH = 32;     // block gradients the fold has in flight per thread
+constexpr int FIT_DIAG_ROWS = 5;       // behind the rows: two doubles and an int per sample, the terms of the block's diagnostics
+
+__device__ __forceinline__ int fit_row(const FitNet& net, int l) {      // the first row of layer l's INPUT; l = n_layers: the output deltas
+    int r = l == 0 ? 0 : FIT_X_ROWS;
+    for (int i = 1; i < l; ++i) r += net.layer[i - 1].N;
+    return r;
+}
+
+// d_h[k] of the layer below, k split between the waves four at a time, for this lane's sample: the j-ascending chain
+// acc = fmaf(W[j][k], d_z[j], acc) from +0.0f; then through the activation's derivative at h[k], in place.
+__device__ __forceinline__ void fit_input_delta(const float* __restrict__ wt, int N, int fan_out, int K, int act, const float* dz, float* h,
+                                                int lane, int wave) {
+    constexpr int KB = 4;              // (K is a hidden width here: a multiple of 16)
+    for (int k0 = wave * KB; k0 < K; k0 += POLICY_WAVES * KB) {
+        float acc[KB];
+#pragma unroll
+        for (int kk = 0; kk < KB; ++kk) acc[kk] = 0.0f;
+#pragma unroll 4
+        for (int j = 0; j < fan_out; ++j) {
+            const float d = dz[j * POLICY_LANES + lane];
+#pragma unroll
+            for (int kk = 0; kk < KB; ++kk) acc[kk] = __builtin_fmaf(wt[(k0 + kk) * N + j], d, acc[kk]);
+        }
+#pragma unroll
+        for (int kk = 0; kk < KB; ++kk) {
+            float* at = h + (k0 + kk) * POLICY_LANES + lane;
+            const float hk = *at;
+            *at = act == BSK_POLICY_TANH ? acc[kk] * __builtin_fmaf(-hk, hk, 1.0f) : (hk > 0.0f ? acc[kk] : 0.0f);
+        }
+    }
+}
+
+// The weight gradients of one layer: GW[j][k] = the sample-ascending chain acc = fmaf(d_z[j][s], h[k][s], acc) from +0.0f.  The
+// ownership is turned round from the sweeps: a lane owns one row of the wider side - its 64 samples in registers, read from the
+// LDS once - and walks the rows of the other side, which its whole half-wave reads at one address (a broadcast).  The waves split
+// those rows; a side of 32 rows or fewer leaves the upper half-wave to a second one.  DZ_LANES: the lanes own d_z rows (j), else h rows (k).
+template <bool DZ_LANES>
+__device__ __forceinline__ void fit_weight_grad(const float* dz, int fan_out, const float* h, int K, float* __restrict__ gw, int lane, int wave) {
+    const float* A = DZ_LANES ? dz : h;
+    const float* B = DZ_LANES ? h : dz;
+    const int n_a = DZ_LANES ? fan_out : K, n_b = DZ_LANES ? K : fan_out;
+    const int span = n_a <= 32 ? 32 : 64, subs = 64 / span;
+    const int sub = lane / span, al = lane % span;
+    for (int a0 = 0; a0 < n_a; a0 += span) {
+        const int a = a0 + al;
+        const bool valid = a < n_a;
+        const float4* row = (const float4*)(A + (valid ? a : 0) * POLICY_LANES);
+        float4 r[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) r[i] = row[i];
+        for (int b = wave * subs + sub; b < n_b; b += POLICY_WAVES * subs) {
+            const float4* col = (const float4*)(B + b * POLICY_LANES);
+            float acc = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float4 q = col[i];
+                if (DZ_LANES) {
+                    acc = __builtin_fmaf(r[i].x, q.x, acc); acc = __builtin_fmaf(r[i].y, q.y, acc);
+                    acc = __builtin_fmaf(r[i].z, q.z, acc); acc = __builtin_fmaf(r[i].w, q.w, acc);
+                } else {
+                    acc = __builtin_fmaf(q.x, r[i].x, acc); acc = __builtin_fmaf(q.y, r[i].y, acc);
+                    acc = __builtin_fmaf(q.z, r[i].z, acc); acc = __builtin_fmaf(q.w, r[i].w, acc);
+                }
+            }
+            if (valid) gw[DZ_LANES ? a * K + b : b * K + a] = acc;
+        }
+    }
+}
+
+// Gb[j]: the sample-ascending chain of plain additions of d_z[j][s] from +0.0f, one thread per unit
+__device__ __forceinline__ void fit_bias_grad(const float* dz, int fan_out, float* __restrict__ gb) {
+    for (int j = (int)threadIdx.x; j < fan_out; j += POLICY_BLOCK) {
+        const float4* row = (const float4*)(dz + j * POLICY_LANES);
+        float acc = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float4 q = row[i];
+            acc = acc + q.x; acc = acc + q.y; acc = acc + q.z; acc = acc + q.w;
+        }
+        gb[j] = acc;
+    }
+}
+
+// The forward pass of one network from the x rows, every layer kept.  -> out (wave 0): the output layer, as policy_net leaves it
+__device__ __forceinline__ void fit_forward(const float* __restrict__ params, const FitNet& net, float* lds, int lane, int wave, float* out) {
+    const int last = net.n_layers - 1;
+    int row = 0;
+    for (int l = 0; l < last; ++l) {
+        const PolicyPackMap::Layer& y = net.layer[l];
+        const int next = l == 0 ? FIT_X_ROWS : row + net.layer[l - 1].N;
+        policy_hidden(params + y.w, params + y.b, y.K, y.N, net.act, lds + row * POLICY_LANES, lds + next * POLICY_LANES, lane, wave);
+        __syncthreads();                   // (layer l + 1 reads what every wave wrote)
+        row = next;
+    }
+    if (wave == 0) policy_output(params + net.layer[last].w, params + net.layer[last].b, net.layer[last].K, lds + row * POLICY_LANES, lane, out);
+}
+
+// The backward sweep from the output deltas (written, and a barrier passed): per layer from the last the weight and bias gradients
+// into the block's row g (C-ABI order), then - a barrier on either side - the deltas of the layer below in place of its activations.
+__device__ __forceinline__ void fit_backward(const float* __restrict__ params, const FitNet& net, float* lds, float* __restrict__ g, int lane,
+                                             int wave, long long* walk_ticks) {
+    const float* dz = lds + fit_row(net, net.n_layers) * POLICY_LANES;
+    for (int l = net.n_layers - 1; l >= 0; --l) {
+        const PolicyPackMap::Layer& y = net.layer[l];
+        float* h = lds + fit_row(net, l) * POLICY_LANES;
+#if BSK_FIT_STAMPS
+        const long long t0 = clock64();
+#endif
+        if (y.fan_out >= y.K) fit_weight_grad<true>(dz, y.fan_out, h, y.K, g + y.src, lane, wave);
+        else                  fit_weight_grad<false>(dz, y.fan_out, h, y.K, g + y.src, lane, wave);
+#if BSK_FIT_STAMPS
+        __syncthreads();
+        *walk_ticks += clock64() - t0;
+#endif
+        fit_bias_grad(dz, y.fan_out, g + y.src + y.fan_out * y.K);
+        if (l == 0) break;
+        __syncthreads();                   // (the gradients have read h; it turns into the deltas below)
+        fit_input_delta(params + y.w, y.N, y.fan_out, y.K, net.act, dz, h, lane, wave);
+        __syncthreads();
+        dz = h;
+    }
+}
+
+__global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p) {
+    // (everything in the dynamic region and every carve a multiple of 16 bytes: a static array in front would shift its base)
+    extern __shared__ __attribute__((aligned(16))) float fit_lds[];
+    double* s_nll = (double*)(fit_lds + p.rows * POLICY_LANES);
+    double* s_vl = s_nll + POLICY_LANES;
+    int* s_flag = (int*)(s_vl + POLICY_LANES);     // bit 0: the sample contributes; bit 1: the greedy action is its label
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t j = (int64_t)blockIdx.x * POLICY_LANES + lane;
+    const bool live = j < p.n;
+    float* g = p.G + (size_t)blockIdx.x * (size_t)p.n_params;
+    long long walk_ticks = 0;              // (BSK_FIT_STAMPS builds only; otherwise never touched)
+#if BSK_FIT_STAMPS
+    const long long t_start = clock64();
+#endif
+
+    int label = -1;
+    bool on = false;
+    if (wave == 0) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const double o = live ? p.obs[(int64_t)i * p.obs_stride + j] : 0.0;       // (tail lanes read nothing)
+            fit_lds[i * POLICY_LANES + lane] = __builtin_fmaf((float)o, p.params[i], p.params[5 + i]);
+        }
+        if (live) label = p.label[j];
+        on = live && label >= 0 && label <= 2 && (!p.alive || p.alive[j] != 0);
+    }
+    __syncthreads();
+
+    // the action network: cross-entropy against the label
+    float out[POLICY_OB] = {0.0f, 0.0f, 0.0f, 0.0f};
+    fit_forward(p.params, p.a, fit_lds, lane, wave, out);
+    float* delta = fit_lds + fit_row(p.a, p.a.n_layers) * POLICY_LANES;
+    if (wave == 0) {
+        const float m = fmaxf(fmaxf(out[0], out[1]), out[2]);
+        const float e0 = expf(out[0] - m), e1 = expf(out[1] - m), e2 = expf(out[2] - m);
+        const float s = (e0 + e1) + e2;
+        int a = 0;
+        float best = out[0];
+        if (policy_beats(out[1], best)) { best = out[1]; a = 1; }
+        if (policy_beats(out[2], best)) { best = out[2]; a = 2; }
+        const float logp = ((label == 0 ? out[0] : (label == 1 ? out[1] : out[2])) - m) - logf(s);
+        float gl[3] = {0.0f, 0.0f, 0.0f};
+        if (on) {
+            gl[0] = e0 / s - (label == 0 ? 1.0f : 0.0f);
+            gl[1] = e1 / s - (label == 1 ? 1.0f : 0.0f);
+            gl[2] = e2 / s - (label == 2 ? 1.0f : 0.0f);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            delta[i * POLICY_LANES + lane] = gl[i];
+            if (p.dlogits && live) p.dlogits[(int64_t)i * p.out_stride + j] = gl[i];
+        }
+        s_nll[lane] = on ? -(double)logp : 0.0;
+        s_vl[lane] = 0.0;
+        s_flag[lane] = (on ? 1 : 0) | (on && a == label ? 2 : 0);
+    }
+    __syncthreads();
+    fit_backward(p.params, p.a, fit_lds, g, lane, wave, &walk_ticks);
+
+    // the value network: squared error against the target
+    if (p.v.n_layers > 0) {                // (workgroup-uniform)
+        __syncthreads();                   // (the action network's last reads of the rows)
+        float val[POLICY_OB] = {0.0f, 0.0f, 0.0f, 0.0f};
+        fit_forward(p.params, p.v, fit_lds, lane, wave, val);
+        delta = fit_lds + fit_row(p.v, p.v.n_layers) * POLICY_LANES;
+        if (wave == 0) {
+            const float d = on ? val[0] - (float)p.target[j] : 0.0f;
+            delta[lane] = on ? p.value_coef * d : 0.0f;
+            s_vl[lane] = (((double)d) * ((double)d)) * 0.5;
+        }
+        __syncthreads();
+        fit_backward(p.params, p.v, fit_lds, g, lane, wave, &walk_ticks);
+    }
+
+    __syncthreads();
+    if (threadIdx.x == 0) {                // the block's terms, sample-ascending from +0.0
+        double nll = 0.0, vl = 0.0;
+        int count = 0, correct = 0;
+        for (int s = 0; s < POLICY_LANES; ++s) {
+            nll = nll + s_nll[s];
+            vl = vl + s_vl[s];
+            count += s_flag[s] & 1;
+            correct += (s_flag[s] >> 1) & 1;
+        }
+        double* row = p.diag + 4 * (size_t)blockIdx.x;
+        row[0] = nll;
+        row[1] = vl;
+#if BSK_FIT_STAMPS
+        row[0] = (double)walk_ticks;
+        row[1] = (double)(clock64() - t_start);
+#endif
+        row[2] = (double)correct;
+        row[3] = (double)count;
+    }
+}
+
+__global__ __launch_bounds__(256) void fit_fold_kernel(const float* __restrict__ G, const double* __restrict__ diag, int n_blocks, int n_params,
+                                                       int n_fold, double* __restrict__ A, double* __restrict__ row,
+                                                       unsigned long long* __restrict__ count) {
+    const int t = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (t < 4) {                           // the diagnostics row: its four sums, block-ascending from +0.0
+        double s = 0.0;
+        int b = 0;
+        for (; b + FIT_FOLD_BATCH <= n_blocks; b += FIT_FOLD_BATCH) {      // (fetched side by side, added in order: as below)
+            double d[FIT_FOLD_BATCH];
+#pragma unroll
+            for (int i = 0; i < FIT_FOLD_BATCH; ++i) d[i] = diag[4 * (size_t)(b + i) + t];
+#pragma unroll
+            for (int i = 0; i < FIT_FOLD_BATCH; ++i) s = s + d[i];
+        }
+        for (; b < n_blocks; ++b) s = s + diag[4 * (size_t)b + t];
+        row[t] = s;
+        if (t == 3) *count += (unsigned long long)s;
+    }
+    const int p = 10 + t;
+    if (p >= n_fold) return;
+    // The chain is serial by definition; the loads are not.  FIT_FOLD_BATCH block values are fetched side by side and then added in
+    // order: with one load per addition in flight the kernel was 1 024 dependent memory round trips long (469 us at 65 536 samples).
+    const float* __restrict__ at = G + p;
+    double acc = A[p];
+    int b = 0;
+    for (; b + FIT_FOLD_BATCH <= n_blocks; b += FIT_FOLD_BATCH) {
+        float g[FIT_FOLD_BATCH];
+#pragma unroll
+        for (int i = 0; i < FIT_FOLD_BATCH; ++i) g[i] = at[(size_t)(b + i) * (size_t)n_params];
+#pragma unroll
+        for (int i = 0; i < FIT_FOLD_BATCH; ++i) acc = acc + (double)g[i];
+    }
+    for (; b < n_blocks; ++b) acc = acc + (double)at[(size_t)b * (size_t)n_params];
+    A[p] = acc;
+}
+
+__global__ __launch_bounds__(256) void fit_adam_kernel(double* __restrict__ theta, double* __restrict__ A,
+                                                       const unsigned long long* __restrict__ count, int n_upd, const EsAdam ad) {
+    const int p = 10 + (int)(blockIdx.x * 256u + threadIdx.x);
+    if (p >= n_upd) return;
+    const unsigned long long cnt = *count;
+    if (cnt != 0ull) {
+        const double t = theta[p];
+        theta[p] = t - adam_step(ad, p, A[p] / (double)cnt + ad.weight_decay * t);
+    }
+    A[p] = 0.0;
+}
+
+__global__ void fit_advance_kernel(unsigned long long* count, unsigned long long* steps, double* beta_pow, double beta1, double beta2) {
+    if (*count != 0ull) {
+        beta_pow[0] = beta_pow[0] * beta1;
+        beta_pow[1] = beta_pow[1] * beta2;
+        *steps += 1ull;
+    }
+    *count = 0ull;
+}
+
+// the alive bytes of a collection loop: one thread per env
+__global__ __launch_bounds__(256) void fit_alive_kernel(const uint8_t* __restrict__ reason, int n, int first, uint8_t* __restrict__ alive) {
+    const int j = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (j < n) alive[j] = first || (alive[j] != 0 && reason[j] == 0) ? 1 : 0;        // (first: neither array is read)
+}
+
+hipError_t launch_fit_alive(const uint8_t* reason, int n, int first, uint8_t* alive, hipStream_t s) {
+    hipLaunchKernelGGL(fit_alive_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reason, n, first, alive);
+    return hipGetLastError();
+}
+
+int fit_lds_rows(const PolicyLayout& lay) {
+    const PolicyNet* nets[2] = {&lay.a, &lay.v};
+    int most = 0;
+    for (const PolicyNet* net : nets) {
+        int hidden = 0;
+        for (int l = 0; l + 1 < net->n_layers; ++l) hidden += net->N[l];
+        if (hidden > most) most = hidden;
+    }
+    return FIT_X_ROWS + most + POLICY_OB;
+}
+
+FitNet fit_net(const PolicyPackMap& map, int first, const PolicyNet& net) {
+    FitNet f = {};
+    f.n_layers = net.n_layers;
+    f.act = net.act;
+    for (int l = 0; l < net.n_layers; ++l) f.layer[l] = map.layer[first + l];
+    return f;
+}
+
+hipError_t launch_fit_blocks(const FitArgs& args, hipStream_t s) {
+    const size_t lds = (size_t)(args.rows + FIT_DIAG_ROWS) * POLICY_LANES * sizeof(float);
+    if (lds > 48 * 1024) {                 // (idempotent, and cheap beside the launch: no per-device record to keep)
+        hipError_t e = hipFuncSetAttribute((const void*)&fit_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const unsigned n_blocks = (unsigned)((args.n + FIT_BLOCK_SAMPLES - 1) / FIT_BLOCK_SAMPLES);
+    hipLaunchKernelGGL(fit_block_kernel, dim3(n_blocks), dim3(POLICY_BLOCK), lds, s, args);
+    return hipGetLastError();
+}
+
+hipError_t launch_fit_fold(const float* G, const double* diag, int n_blocks, int n_params, int n_fold, double* A, double* row,
+                           unsigned long long* count, hipStream_t s) {
+    const int threads = n_fold - 10 > 4 ? n_fold - 10 : 4;
+    hipLaunchKernelGGL(fit_fold_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, G, diag, n_blocks, n_params, n_fold, A, row,
+                       count);
+    return hipGetLastError();
+}
+
+hipError_t launch_fit_step(double* theta, double* A, unsigned long long* count, unsigned long long* steps, int n_upd, const EsAdam& ad,
+                           hipStream_t s) {
+    if (n_upd > 10) {
+        hipLaunchKernelGGL(fit_adam_kernel, dim3((unsigned)((n_upd - 10 + 255) / 256)), dim3(256), 0, s, theta, A, count, n_upd, ad);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(fit_advance_kernel, dim3(1), dim3(1), 0, s, count, steps, const_cast<double*>(ad.beta_pow), ad.beta1, ad.beta2);
+    return hipGetLastError();
+}
+
+}  // namespace bsk

@@ -1,0 +1,56 @@
+// bsk_fit.hpp — a supervised fit of the MLP policy on the device (bsk_fit.hip; internal): what bsk_fit_accumulate / bsk_fit_step
+// launch.  The arithmetic is the definition in include/bskgpu.h (bsk_fit_*).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "bsk_es.hpp"
+#include "bsk_policy.hpp"
+
+namespace bsk {
+
+constexpr int FIT_BLOCK_SAMPLES = POLICY_LANES;     // samples of one gradient block: one workgroup, one lane each
+
+// One network as the fit kernel walks it: the layers of the pack map (where Wt / b lie in the device block, where W / b start in
+// the C-ABI block, which is the order of the gradient) and the hidden activation.
+struct FitNet {
+    int n_layers;                  // 0: the network is not fitted by this launch (none, or no targets)
+    int act;
+    PolicyPackMap::Layer layer[POLICY_MAX_LAYERS];
+};
+
+struct FitArgs {
+    const float* params;           // the policy's device layout
+    FitNet a, v;
+    const double* obs;             // [5][obs_stride]
+    int64_t obs_stride;
+    int n;
+    const int32_t* label;          // [n]
+    const double* target;          // [n] or NULL
+    const uint8_t* alive;          // [n] or NULL
+    float value_coef;
+    float* dlogits;                // [3][out_stride] or NULL
+    int64_t out_stride;
+    float* G;                      // [n_blocks][n_params]: the block gradients, C-ABI parameter order
+    double* diag;                  // [n_blocks][4]: the block's terms of the diagnostics row
+    int n_params;
+    int rows;                      // fit_lds_rows
+};
+
+// LDS rows of 64 floats the block kernel needs for this layout: the input, every hidden layer of the larger network, the output deltas
+int fit_lds_rows(const PolicyLayout& lay);
+FitNet fit_net(const PolicyPackMap& map, int first, const PolicyNet& net);
+
+// One workgroup per 64 samples: forward, output deltas, backward, the block's gradient and diagnostics terms
+hipError_t launch_fit_blocks(const FitArgs& args, hipStream_t s);
+// A[p] += (double)G[b][p] for b ascending, p in 10 .. n_fold - 1; the diagnostics row out of the block terms; count += row[3]
+hipError_t launch_fit_fold(const float* G, const double* diag, int n_blocks, int n_params, int n_fold, double* A, double* row,
+                           unsigned long long* count, hipStream_t s);
+// Adam on g = A / count + weight_decay * theta for p in 10 .. n_upd - 1 (descent; nothing while count == 0), A zeroed; then one
+// thread: beta_pow and the step counter move on, count = 0
+hipError_t launch_fit_step(double* theta, double* A, unsigned long long* count, unsigned long long* steps, int n_upd, const EsAdam& ad,
+                           hipStream_t s);
+// alive[j] = first || (alive[j] && reason[j] == 0), as bytes 1 / 0
+hipError_t launch_fit_alive(const uint8_t* reason, int n, int first, uint8_t* alive, hipStream_t s);
+
+}  // namespace bsk

@@ -5,7 +5,7 @@
 
 #include <vector>
 
-struct bsk_policy_spec;            // (include/bskgpu.h)
+#include "../../include/bskgpu.h"
 
 namespace bsk {
 
@@ -77,6 +77,65 @@ __device__ __forceinline__ int policy_pack_source(const PolicyPackMap& map, int 
         }
     }
     return j;
+}
+
+// One lane per spacecraft and POLICY_WAVES waves per 64 spacecraft: the waves of a workgroup share the spacecraft and split each hidden
+// layer's units between them, 16 at a time.  65 536 spacecraft are only 1 024 wave-columns, one per SIMD: with one wave each, a launch
+// is as long as one wave's whole chain with nothing to hide its load latencies behind (measured: 31.8 us for relu [64, 64]); four
+// waves cut the chain into four and give every SIMD four waves to switch between.  The weights are wave-uniform: a lane's 16
+// neighbouring units share the input h_k, so per k a wave makes one LDS read (h_k of its 64 spacecraft), one scalar load (16
+// consecutive weights of Wt[k][j0 .. j0+16), SGPR operands) and 8 independent v_pk_fma_f32 - no weight ever enters a VGPR or the
+// LDS.  Activations go from layer to layer through LDS columns [unit][lane]: conflict-free, one barrier per layer.  Every unit's
+// chain is evaluated by exactly one wave in the definition's order, so the split changes no bit.  (A v_mfma_f32_32x32x2_f32 form of
+// the hidden layers was measured level with this one at [64, 64]: docs/KERNEL_NOTES.md.)
+constexpr int POLICY_LANES = 64;
+constexpr int POLICY_WAVES = 4;
+constexpr int POLICY_BLOCK = POLICY_LANES * POLICY_WAVES;
+
+__device__ __forceinline__ float policy_act(float z, int act) {
+    return act == BSK_POLICY_TANH ? tanhf(z) : (z > 0.0f ? z : 0.0f);
+}
+
+// a hidden layer: hout[j] = act(b[j] + sum_k Wt[k][j] * hin[k]), k ascending; wave w takes the blocks of POLICY_JB units w, w + 4, ...
+__device__ __forceinline__ void policy_hidden(const float* __restrict__ wt, const float* __restrict__ bias, int K, int N, int act,
+                                              const float* hin, float* hout, int lane, int wave) {
+    for (int j0 = wave * POLICY_JB; j0 < N; j0 += POLICY_WAVES * POLICY_JB) {
+        float z[POLICY_JB];
+#pragma unroll
+        for (int jj = 0; jj < POLICY_JB; ++jj) z[jj] = bias[j0 + jj];
+#pragma unroll 4
+        for (int k = 0; k < K; ++k) {
+            const float h = hin[k * POLICY_LANES + lane];
+            const float* __restrict__ w = wt + k * N + j0;
+#pragma unroll
+            for (int jj = 0; jj < POLICY_JB; ++jj) z[jj] = __builtin_fmaf(w[jj], h, z[jj]);
+        }
+#pragma unroll
+        for (int jj = 0; jj < POLICY_JB; ++jj) hout[(j0 + jj) * POLICY_LANES + lane] = policy_act(z[jj], act);
+    }
+}
+
+// the output layer (linear): POLICY_OB rows, the ones beyond the fan-out are zero rows of the device layout.  Wave 0 alone evaluates
+// it: it is the wave that reads the observations and stores the results.
+__device__ __forceinline__ void policy_output(const float* __restrict__ wt, const float* __restrict__ bias, int K, const float* hin,
+                                              int lane, float* out) {
+#pragma unroll
+    for (int jj = 0; jj < POLICY_OB; ++jj) out[jj] = bias[jj];
+#pragma unroll 4
+    for (int k = 0; k < K; ++k) {
+        const float h = hin[k * POLICY_LANES + lane];
+        const float* __restrict__ w = wt + k * POLICY_OB;
+#pragma unroll
+        for (int jj = 0; jj < POLICY_OB; ++jj) out[jj] = __builtin_fmaf(w[jj], h, out[jj]);
+    }
+}
+
+// (value, index) order of the greedy choice: the greater logit wins, equal logits go to the lower index, a NaN loses to every
+// number (bsk_fork.hip: beats() - the rule of bsk_select_branches)
+__device__ __forceinline__ bool policy_beats(float a, float b) {      // a (the later index) displaces b (the earlier one)
+    const bool na = a != a, nb = b != b;
+    if (na != nb) return nb;
+    return !na && a > b;
 }
 
 hipError_t launch_policy(const PolicyArgs& args, hipStream_t s);

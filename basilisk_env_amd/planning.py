@@ -374,6 +374,73 @@ class BeamPlanner(_BranchPlanner):
         return seq.reshape(self.n_roots, self.width, self.horizon)
 
 
+def check_distill_args(n_steps, collect):
+    """Argument rules of ``distill`` (no device needed) -> n_steps as an int."""
+    if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or n_steps < 1:
+        raise ValueError("n_steps must be an integer >= 1, got %r" % (n_steps,))
+    if collect not in ("expert", "policy"):
+        raise ValueError("collect must be 'expert' or 'policy', got %r" % (collect,))
+    return int(n_steps)
+
+
+def distill(planner, policy, fit, env, n_steps, collect="expert", value_targets=False):
+    """Planner distillation (behaviour cloning) with no host in the loop: ``n_steps`` env steps of ``env`` - the
+    ``BatchedPropagator`` (or an env over one) that is ``planner``'s root - and at each of them
+      1. ``planner.plan()``, which leaves its labels in ``d_best_action`` and its values in ``d_best_value`` on the device;
+      2. ``fit.accumulate`` on the root's own observation rows with those labels (and, with ``value_targets``, those values as the
+         value network's targets) under the root's alive bytes (``bsk_fit_alive_mask``): every root counts at the first step - the
+         observation it holds is labelled whatever its last step before the call left in the reason bytes, so reset a root whose
+         episode is over before calling - and a root whose episode ends inside the loop contributes no more from the next step
+         on, also when ``FLAG_AUTO_RESET`` starts it again;
+      3. the root's step: on the planner's actions (``collect="expert"``), or on ``policy``'s own greedy actions for the same rows
+         (``"policy"``: DAgger's collection rule - the states are the learner's, the labels the expert's);
+      4. ``fit.step()``.
+    ``fit`` is a ``PolicyFit`` attached to ``policy``.  Everything is enqueued on the root's stream: no copy to or from the host and
+    no synchronisation until the loop has ended.  -> float64 (n_steps, 4), the diagnostics row of every step's accumulate
+    (``policy_ref.FIT_STATS_COLUMNS``), read once at the end."""
+    from . import _hip
+    n_steps = check_distill_args(n_steps, collect)
+    prop = getattr(env, "propagator", env)
+    if planner.root is not prop:
+        raise ValueError("the planner's root is not this env's propagator")
+    if fit.policy is not policy:
+        raise ValueError("the fit is attached to another policy")
+    if value_targets and policy.spec.value_hidden is None:
+        raise ValueError("value_targets: the policy has no value network")
+    if policy.device != prop.device:
+        raise ValueError("the policy lives on device %d, the propagator on device %d" % (policy.device, prop.device))
+    lib, rt, vp = _lib.load(), _hip.runtime(), C.c_void_p
+    n, stream = prop.n_envs, prop.stream_ptr()
+    views = prop.device_views()
+    obs, stride = views["obs"].__cuda_array_interface__["data"][0], views["stride"]
+    reason = views["reason"].__cuda_array_interface__["data"][0]
+    alive, rows = _hip.DeviceBuffer(n, prop.device), _hip.DeviceBuffer(32 * n_steps, prop.device)
+    if collect == "policy":
+        policy._buffers(n)                                 # (grown here, where a wait for the device is no wait inside the loop)
+    try:
+        with _hip.device_guard(prop.device):
+            for t in range(n_steps):
+                check(lib.bsk_fit_alive_mask(vp(reason), n, int(t == 0), vp(alive.ptr), vp(stream)))
+                planner.plan()
+                fit.accumulate(obs, planner.d_best_action.ptr, planner.d_best_value.ptr if value_targets else None, alive.ptr,
+                               n=n, stride=stride, stream=stream)
+                _hip.check(rt.hipMemcpyAsync(vp(rows.ptr + 32 * t), vp(fit.stats_ptr()), 32, _hip.hipMemcpyDeviceToDevice, vp(stream)),
+                           "hipMemcpyAsync")
+                actions = planner.d_best_action.ptr
+                if collect == "policy":
+                    actions = policy.enqueue(obs, stride, n, "greedy", (), getattr(prop, "env_base", 0), stream)["action"].ptr
+                prop.step_device(actions, planner.substeps)
+                fit.step(stream)
+            out = np.empty((n_steps, 4), np.float64)
+            _hip.check(rt.hipMemcpyAsync(vp(out.ctypes.data), vp(rows.ptr), out.nbytes, _hip.hipMemcpyDeviceToHost, vp(stream)),
+                       "hipMemcpyAsync")
+    finally:
+        prop.sync()                                        # (the one wait: the rows are on the host, nothing queued reads the two buffers)
+        alive.free()
+        rows.free()
+    return out
+
+
 def demo(n=64, steps=40, depth=2, substeps=600, seed=0, beam=None):
     """A small batch of the full scenario (power system, Sun, drag, desaturation) run for ``steps`` env steps of ``substeps`` RK4
     steps under the planner and under each constant action, from the same initial conditions; prints the mean return per env

@@ -12,9 +12,10 @@ propagator, one launch per env step serves all members, and the per-member fitne
 ``DeviceEvolutionStrategy`` (``bsk_es_*``) keeps theta on the device and asks, ranks and updates there, its noise regenerated from
 a counter instead of stored.  ``ObsStats`` (``bsk_obs_stats_*``) keeps running sums of the observation rows on the device: attached to
 a population or a policy it is fed by their rollouts, and ``DeviceEvolutionStrategy.apply_obs_norm`` turns it into theta's in_scale
-and in_shift.
+and in_shift.  ``PolicyFit`` (``bsk_fit_*``; its binding lives in ``policy_fit`` and is re-exported here) is the gradient side: a
+supervised fit of a ``DevicePolicy`` to labels that are already on the device, such as a planner's.
 
-The four are handles of the library and share what such a handle needs (``_DeviceObject``: create, close, the closed-handle
+They are handles of the library and share what such a handle needs (``policy_base._DeviceObject``: create, close, the closed-handle
 refusal, ``sync``); the policy and the population are also both parameter stores that act (``_ParamStore``: the draw counter, the
 output buffers and views of ``act``, rollouts with host results) - as ``ParamStore`` is behind the two in csrc/bsk_capi_policy.hip;
 ``bsk_es_*`` is csrc/bsk_capi_es.hip.
@@ -27,12 +28,15 @@ multiply-adds from the bias; ``population_fitness_ref``; ``es_noise_ref`` / ``es
 ``population_outcomes_ref`` / ``es_outcome_row_ref``; ``obs_stats_accumulate_ref`` / ``obs_stats_totals_ref`` / ``obs_norm_ref``) with ``EvolutionStrategy``, the host-side loop the device one was modelled on.
 """
 import ctypes as C
-import sys
 
 import numpy as np
 
 from . import _hip, _lib
 from ._lib import check
+from .policy_base import _DeviceObject, _host_block  # noqa: F401
+from .policy_fit import PolicyFit  # noqa: F401
+from .policy_ref import (FIT_BLOCK, FIT_STATS_COLUMNS, check_fit, check_fit_batch, fit_accumulate_ref, fit_backward_ref,  # noqa: F401
+                         fit_dlogits32_ref, fit_dlogits_ref, fit_loss_ref, fit_stats_ref, fit_step_ref)
 from .policy_ref import (ES_LOG_COLUMNS, ES_LOG_EMPTY, ES_VAL_COLUMNS, ES_VAL_MAX_MEMBERS, EvolutionStrategy, _es_pair_sum,  # noqa: F401
                          _es_pair_sums, _series_log, act_ref,
                          centred_ranks, check_adam, check_log, check_validation,
@@ -88,87 +92,6 @@ def _observation_source(pol, source, env_base, stream):
         owner = pol
         pol._source = source                   # (the launch reads it after this call returns)
     return ptr, stride, n, int(stream or 0), int(env_base or 0), owner
-
-
-def _host_block(values, n, dtype=np.float32, rows=0, what="parameters"):
-    """Host values -> a contiguous ``dtype`` array: ``n`` elements flattened (``rows=0``), or blocks of ``n`` as the rows of a 2-D
-    array - exactly ``rows`` of them, any number from one on with ``rows=None``.  Anything else is a ``ValueError``."""
-    p = np.ascontiguousarray(values, dtype=dtype)
-    if rows == 0:
-        p = p.reshape(-1)
-        if p.size != n:
-            raise ValueError("expected %d %s, got %d" % (n, what, p.size))
-    elif p.ndim != 2 or p.shape[1] != n or p.shape[0] < 1 or (rows is not None and p.shape[0] != rows):
-        raise ValueError("expected %s of shape (%s, %d), got %r" % (what, "P" if rows is None else rows, n, p.shape))
-    return p
-
-
-class _DeviceObject(object):
-    """A handle of the library on one GPU, made by ``bsk_<_kind>_create(spec, ..., device, &handle)`` (an object without a
-    ``spec``: without that argument).  ``_out`` holds the
-    ``_hip.DeviceBuffer``s the object owns, by name (None: none yet), ``_source`` the device array a queued launch still reads,
-    ``_stats`` the ``ObsStats`` attached to it."""
-    _kind = None              # policy / population / es / obs_stats: the C functions are bsk_<_kind>_*
-    _what = None              # what the object is called in a message
-
-    def _c(self, name):
-        return getattr(self._lib, "bsk_%s_%s" % (self._kind, name))
-
-    def _create(self, device, *args):
-        self._lib = _lib.load()
-        self.device = int(device)
-        h = C.c_void_p()
-        if getattr(self, "spec", None) is not None:
-            self._cs = c_spec(self.spec)
-            args = (C.byref(self._cs),) + args
-        check(self._c("create")(*args, self.device, C.byref(h)))
-        self._p = h
-        self._out = self._source = None
-
-    def close(self):
-        if getattr(self, "_p", None):
-            self._c("destroy")(self._p)
-            self._p = None
-        for b in (getattr(self, "_out", None) or {}).values():
-            b.free()
-        self._out = self._source = self._stats = self._outcomes = None
-
-    def __del__(self):
-        try:
-            if sys.is_finalizing():
-                return
-            self.close()
-        except Exception:
-            pass
-
-    def _handle(self):
-        if not self._p:
-            raise RuntimeError("%s is closed" % self._what)
-        return self._p
-
-    def sync(self):
-        """Waits for everything queued on the object's device (it keeps no stream of its own)."""
-        with _hip.device_guard(self.device):
-            _hip.check(_hip.runtime().hipDeviceSynchronize(), "hipDeviceSynchronize")
-
-    def _device_pointer(self, src, itemsize, refuse):
-        """``src``: a raw device pointer - returned as it is, with no element count - or anything with
-        ``__cuda_array_interface__``, read into typestr, shape, element count and whether its strides (where it gives any) are those
-        of a dense array of ``itemsize``-byte elements.  ``refuse(typestr, shape, size, dense)`` -> the text of the ``ValueError`` or
-        None; an array it lets pass is kept alive in ``_source``, for the launch reads it after the call has returned.
-        -> (pointer, element count or None)"""
-        cai = getattr(src, "__cuda_array_interface__", None)
-        if cai is None:
-            return src, None
-        shape, strides = tuple(cai["shape"]), cai.get("strides")
-        size = int(np.prod(shape)) if len(shape) else 1
-        dense = tuple(itemsize * int(np.prod(shape[k + 1:], dtype=np.int64)) for k in range(len(shape)))
-        dense = strides is None or tuple(strides) == dense
-        why = refuse(cai["typestr"], cai["shape"], size, dense)
-        if why:
-            raise ValueError(why)
-        self._source = src
-        return cai["data"][0], size
 
 
 class _ParamStore(_DeviceObject):

@@ -459,6 +459,19 @@ def check_adam(beta1, beta2, eps, weight_decay):
     return beta1, beta2, eps, weight_decay
 
 
+def _adam_step_ref(m, v, beta_pow, g, lr, b1, b2, eps):
+    """Adam's lines of include/bskgpu.h (csrc/bsk_es.hpp: adam_step) on float64 arrays, every operation rounded on its own
+    -> (m, v, step, beta_pow moved on): m = b1 m + (1 - b1) g; v = b2 v + ((1 - b2) g) g;
+    step = (lr * (m / (1 - p1))) / (sqrt(v / (1 - p2)) + eps) with p = beta_pow * beta.  The evolution strategy adds the step to
+    theta, the policy fit subtracts it.  The caller holds the ``np.errstate`` scope."""
+    one = np.float64(1.0)
+    a1, a2 = one - b1, one - b2
+    p1, p2 = beta_pow[0] * b1, beta_pow[1] * b2
+    mj = b1 * m + a1 * g
+    vj = b2 * v + (a2 * g) * g
+    return mj, vj, (lr * (mj / (one - p1))) / (np.sqrt(vj / (one - p2)) + eps), np.array([p1, p2], np.float64)
+
+
 def es_tell_adam_ref(theta, m, v, beta_pow, fitness, sigma, lr, frozen, seed, generation, beta1, beta2, eps, weight_decay):
     """What ``bsk_es_tell`` leaves under ``BSK_ES_ADAM`` -> (theta, m, v, beta_pow), float64: s[0] of ``es_tell_ref``'s sum, then
     per parameter j >= frozen, every operation rounded on its own (include/bskgpu.h), cg = 1 / (P * sigma):
@@ -474,16 +487,11 @@ def es_tell_adam_ref(theta, m, v, beta_pow, fitness, sigma, lr, frozen, seed, ge
     s0, P = _es_pair_sum(fitness, theta.size, seed, generation)
     lr = np.float64(lr)
     cg = np.float64(1.0) / (np.float64(P) * np.float64(sigma))
-    a1, a2 = np.float64(1.0) - b1, np.float64(1.0) - b2
-    p1, p2 = bp[0] * b1, bp[1] * b2
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         t = theta[frozen:]
-        g = cg * s0[frozen:] - wd * t
-        mj = b1 * m[frozen:] + a1 * g
-        vj = b2 * v[frozen:] + (a2 * g) * g
-        m[frozen:], v[frozen:] = mj, vj
-        theta[frozen:] = t + (lr * (mj / (np.float64(1.0) - p1))) / (np.sqrt(vj / (np.float64(1.0) - p2)) + eps)
-    return theta, m, v, np.array([p1, p2], np.float64)
+        m[frozen:], v[frozen:], step, bp = _adam_step_ref(m[frozen:], v[frozen:], bp, cg * s0[frozen:] - wd * t, lr, b1, b2, eps)
+        theta[frozen:] = t + step
+    return theta, m, v, bp
 
 
 def es_ask_sigma_ref(theta, sigma_vec, frozen, P, seed, generation):
@@ -533,13 +541,8 @@ def es_tell_pgpe_ref(theta, sigma_vec, fitness, lr, frozen, seed, generation, lr
                 raise ValueError("m and v have theta's size")
             b1, b2, eps, wd = (np.float64(x) for x in check_adam(beta1, beta2, eps, weight_decay))
             cg = np.float64(1.0) / (pd * sg)
-            a1, a2 = np.float64(1.0) - b1, np.float64(1.0) - b2
-            p1, p2 = bp[0] * b1, bp[1] * b2
-            g = cg * s0[frozen:] - wd * t
-            mj = b1 * m[frozen:] + a1 * g
-            vj = b2 * v[frozen:] + (a2 * g) * g
-            m[frozen:], v[frozen:] = mj, vj
-            theta[frozen:] = t + (lr * (mj / (np.float64(1.0) - p1))) / (np.sqrt(vj / (np.float64(1.0) - p2)) + eps)
+            m[frozen:], v[frozen:], step, bp = _adam_step_ref(m[frozen:], v[frozen:], bp, cg * s0[frozen:] - wd * t, lr, b1, b2, eps)
+            theta[frozen:] = t + step
         d = (cs * r0[frozen:]) * sg
         lim = max_change * sg
         d = np.where(d > lim, lim, np.where(d < -lim, -lim, d))
@@ -549,7 +552,7 @@ def es_tell_pgpe_ref(theta, sigma_vec, fitness, lr, frozen, seed, generation, lr
         sv[frozen:] = n
     if adam is None:
         return theta, sv
-    return theta, sv, m, v, np.array([p1, p2], np.float64)
+    return theta, sv, m, v, bp
 
 
 # The training log and the champion (bsk_es_set_log; kernels es_log_kernel / es_best_kernel), restated
@@ -901,3 +904,284 @@ def obs_norm_ref(tot, count, std_min):
         scale = np.where(sd >= np.float64(std_min), np.float64(1.0) / sd, 0.0)
         shift = np.float64(0.0) - mean * scale
     return scale, shift
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Fitting the policy to labelled observations (bsk_fit_*; definition in include/bskgpu.h, kernels in csrc/bsk_fit.hip), restated
+
+FIT_BLOCK = 64                                 # samples of one gradient block
+FIT_STATS_COLUMNS = ("nll_sum", "value_loss_sum", "correct", "count")
+
+
+def check_fit(lr, beta1, beta2, eps, weight_decay, value_coef):
+    """The argument rules of ``bsk_fit_create`` -> the six as floats; ValueError where it returns BSK_EINVAL.  Needs no device."""
+    lr, value_coef = float(lr), float(value_coef)
+    if not np.isfinite(lr) or lr < 0.0:
+        raise ValueError("lr must be finite and not negative")
+    beta1, beta2, eps, weight_decay = check_adam(beta1, beta2, eps, weight_decay)
+    if not np.isfinite(value_coef) or value_coef < 0.0:
+        raise ValueError("value_coef must be finite and not negative")
+    return lr, beta1, beta2, eps, weight_decay, value_coef
+
+
+def check_fit_batch(spec, n, labels_size=None, targets_size=None, alive_size=None):
+    """The argument rules of ``bsk_fit_accumulate`` that need no device: n >= 1, value targets only with a value network, and
+    every array given as long as n."""
+    spec = _as_spec(spec)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1 or n > 2 ** 28:
+        raise ValueError("n must be in 1..2^28, got %r" % (n,))
+    if targets_size is not None and spec.value_hidden is None:
+        raise ValueError("value targets given, but the policy has no value network")
+    for what, size in (("labels", labels_size), ("value targets", targets_size), ("alive", alive_size)):
+        if size is not None and int(size) != int(n):
+            raise ValueError("%s: %d elements, got %d" % (what, n, size))
+    return int(n)
+
+
+def _fit_mask(n, labels, alive):
+    """-> (labels int64 (n,), the samples that contribute: alive and a label in 0..2)"""
+    labels = np.asarray(labels).reshape(-1).astype(np.int64)
+    if labels.size != n:
+        raise ValueError("labels: one per sample")
+    on = (labels >= 0) & (labels <= 2)
+    if alive is not None:
+        alive = np.asarray(alive).reshape(-1)
+        if alive.size != n:
+            raise ValueError("alive: one byte per sample")
+        on &= alive != 0
+    return labels, on
+
+
+def _fit_nets(spec, params, fp64):
+    """-> in_scale, in_shift, the action network's [(W, b), ...], the value network's or None; float64 arrays under ``fp64`` - from
+    ``params`` as it is, so that a float64 block is not rounded - float32 otherwise"""
+    spec = _as_spec(spec)
+    if not fp64:
+        return unpack_params(spec, params)
+    p = np.asarray(params, np.float64).reshape(-1)
+    like = unpack_params(spec, np.zeros(p.size, np.float32))
+    at, nets = 10, []
+    for net in like[2:]:
+        if net is None:
+            nets.append(None)
+            continue
+        layers = []
+        for W, b in net:
+            layers.append((p[at:at + W.size].reshape(W.shape), p[at + W.size:at + W.size + b.size]))
+            at += W.size + b.size
+        nets.append(layers)
+    return p[:5], p[5:10], nets[0], nets[1]
+
+
+def _fit_forward(layers, activation, x, fp64):
+    """One network with every layer kept -> [x, h_1, ..., output]: ``_forward32``'s chain, or float64 products under ``fp64``"""
+    hs = [x]
+    for li, (W, b) in enumerate(layers):
+        h = hs[-1]
+        if fp64:
+            z = W @ h + b[:, None]
+        else:
+            z = np.broadcast_to(b[:, None], (W.shape[0], h.shape[1])).astype(np.float32)
+            for k in range(W.shape[1]):
+                z = fma32(W[:, k:k + 1], h[k:k + 1, :], z)
+        if li + 1 < len(layers):
+            with np.errstate(invalid="ignore"):
+                z = np.tanh(z) if activation == "tanh" else np.where(z > 0, z, z.dtype.type(0))
+        hs.append(z.astype(np.float64 if fp64 else np.float32))
+    return hs
+
+
+def _fit_inputs(scale, shift, obs, fp64):
+    """(5, n) float64 observations -> x (5, n padded to whole blocks): a sample of the padding is an all-zero observation"""
+    o = np.asarray(obs, np.float64).reshape(5, -1)
+    n = o.shape[1]
+    o32 = np.zeros((5, -(-n // FIT_BLOCK) * FIT_BLOCK), np.float32)
+    o32[:, :n] = o.astype(np.float32)
+    if fp64:
+        return o32.astype(np.float64) * scale[:, None] + shift[:, None], n
+    return fma32(o32, scale[:, None], shift[:, None]), n
+
+
+def fit_dlogits_ref(spec, params, obs, labels, alive=None, value_targets=None, value_coef=0.0):
+    """The output deltas in float64 from float64 logits (``mlp_ref(fp64=True)``'s, on ``params`` as given - a float64 block is not
+    rounded) -> (dlogits (3, n), dvalue (n,) or None): p - onehot(label) and value_coef * (v - target), zeros where the sample does
+    not contribute (alive == 0, or a label outside 0..2)."""
+    spec = _as_spec(spec)
+    scale, shift, a, v = _fit_nets(spec, params, True)
+    x, n = _fit_inputs(scale, shift, obs, True)
+    labels, on = _fit_mask(n, labels, alive)
+    l = _fit_forward(a, spec.activation, x, True)[-1][:, :n]
+    e = np.exp(l - l.max(axis=0))
+    g = e / e.sum(axis=0)
+    g[np.clip(labels, 0, 2), np.arange(n)] -= 1.0
+    g = np.where(on, g, 0.0)
+    if value_targets is None:
+        return g, None
+    if v is None:
+        raise ValueError("value targets given, but the policy has no value network")
+    val = _fit_forward(v, spec.value_activation, x, True)[-1][0, :n]
+    return g, np.where(on, np.float64(value_coef) * (val - np.asarray(value_targets, np.float64).reshape(-1)), 0.0)
+
+
+def fit_dlogits32_ref(spec, params, obs, labels, alive=None, value_targets=None, value_coef=0.0):
+    """The output deltas as the kernel forms them, float32 -> (dlogits (3, n), dvalue (n,) or None): ``mlp_ref``'s logits and value,
+    ``softmax_ref``'s m, e and s, p_i = e_i / s, g_i = p_i - (i == label); dvalue = float32(value_coef) * (v - float32(target));
+    +0.0 where the sample does not contribute.  ``exp`` is the host's here and the device library's there, so these are the
+    device's deltas to a bound, not bit for bit; everything behind them is (``fit_backward_ref``)."""
+    spec = _as_spec(spec)
+    o = np.asarray(obs, np.float64).reshape(5, -1)
+    n = o.shape[1]
+    labels, on = _fit_mask(n, labels, alive)
+    l, val = mlp_ref(spec, params, o)
+    _, e, s = softmax_ref(l)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        g = (e / s).astype(np.float32) - (np.arange(3)[:, None] == labels[None, :]).astype(np.float32)
+    g = np.where(on, g, np.float32(0)).astype(np.float32)
+    if value_targets is None:
+        return g, None
+    if val is None:
+        raise ValueError("value targets given, but the policy has no value network")
+    d = val - np.asarray(value_targets, np.float64).reshape(-1).astype(np.float32)
+    return g, np.where(on, np.float32(value_coef) * d, np.float32(0)).astype(np.float32)
+
+
+def fit_loss_ref(spec, params, obs, labels, alive=None, value_targets=None, value_coef=0.0):
+    """The loss whose gradient the fit accumulates, float64 and on ``params`` as given: the SUM over the contributing samples of
+    -log softmax(logits)[label] + value_coef * 0.5 * (v - target)**2.  For finite differences."""
+    spec = _as_spec(spec)
+    scale, shift, a, v = _fit_nets(spec, params, True)
+    x, n = _fit_inputs(scale, shift, obs, True)
+    labels, on = _fit_mask(n, labels, alive)
+    l = _fit_forward(a, spec.activation, x, True)[-1][:, :n]
+    d = l - l.max(axis=0)
+    logp = d - np.log(np.exp(d).sum(axis=0))
+    loss = -np.where(on, logp[np.clip(labels, 0, 2), np.arange(n)], 0.0).sum()
+    if value_targets is not None:
+        val = _fit_forward(v, spec.value_activation, x, True)[-1][0, :n]
+        loss += np.float64(value_coef) * 0.5 * np.where(on, (val - np.asarray(value_targets, np.float64).reshape(-1)) ** 2, 0.0).sum()
+    return float(loss)
+
+
+def _fit_net_backward(layers, activation, hs, dz, fp64, out):
+    """The backward sweep of one network from its output deltas ``dz`` (fan_out, n padded): per layer from the last the block
+    gradients - GW[j][k] the sample-ascending ``fma32`` chain of d_z[j][s] * h[k][s] from +0.0, Gb[j] the sample-ascending sum of
+    d_z[j][s] - appended to ``out`` as (W part, b part) per layer, LAST LAYER FIRST; then d_h[k] the j-ascending ``fma32`` chain of
+    W[j][k] * d_z[j] from +0.0 and d_z of the layer below through the activation's derivative at h."""
+    dt = np.float64 if fp64 else np.float32
+    B = dz.shape[1] // FIT_BLOCK
+    for li in range(len(layers) - 1, -1, -1):
+        W, _ = layers[li]
+        h = hs[li]
+        dzb, hb = dz.reshape(dz.shape[0], B, FIT_BLOCK), h.reshape(h.shape[0], B, FIT_BLOCK)
+        if fp64:
+            gw = np.einsum("jbs,kbs->bjk", dzb, hb)
+            gb = dzb.sum(axis=2).T
+        else:
+            gw = np.zeros((B, dz.shape[0], h.shape[0]), np.float32)
+            gb = np.zeros((B, dz.shape[0]), np.float32)
+            for s in range(FIT_BLOCK):
+                gw = fma32(dzb[:, :, s].T[:, :, None], hb[:, :, s].T[:, None, :], gw)
+                gb = gb + dzb[:, :, s].T
+        out.append((gw.reshape(B, -1), gb))
+        if li == 0:
+            break
+        if fp64:
+            dh = W.T @ dz
+        else:
+            dh = np.zeros(h.shape, np.float32)
+            for j in range(W.shape[0]):
+                dh = fma32(W[j][:, None], dz[j][None, :], dh)
+        if activation == "tanh":
+            dz = (dh * (1.0 - h * h if fp64 else fma32(-h, h, np.float32(1.0)))).astype(dt)
+        else:
+            dz = np.where(h > 0, dh, dt(0))
+
+
+def fit_backward_ref(spec, params, obs, dlogits, dvalue=None, fp64=False):
+    """The block gradients of ``bsk_fit_accumulate`` from GIVEN output deltas -> G (n_blocks, n_params) in the C-ABI parameter
+    order, the first ten columns zero; block b is the samples 64 b .. 64 b + 63, the last one filled with all-zero observations and
+    zero deltas.  ``dlogits`` (3, n) float32 - the device's own ``d_dlogits``, taken as exact - and ``dvalue`` (n,) float32 or None
+    (then the value network's columns are zero).  Default: the definition in float32, bit for bit the device's block gradients for
+    ``relu`` networks (``tanh`` is the host's here).  ``fp64=True``: float64 throughout, on ``params`` and deltas as given."""
+    spec = _as_spec(spec)
+    dt = np.float64 if fp64 else np.float32
+    scale, shift, a, v = _fit_nets(spec, params, fp64)
+    x, n = _fit_inputs(scale, shift, obs, fp64)
+    B = x.shape[1] // FIT_BLOCK
+    cols = [np.zeros((B, 10), dt)]
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        for layers, act, delta, rows in ((a, spec.activation, dlogits, 3), (v, spec.value_activation, dvalue, 1)):
+            if layers is None:
+                continue
+            if delta is None:
+                cols.append(np.zeros((B, sum(W.size + b.size for W, b in layers)), dt))
+                continue
+            dz = np.zeros((rows, x.shape[1]), dt)
+            dz[:, :n] = np.asarray(delta, dt).reshape(rows, n)
+            out = []
+            _fit_net_backward(layers, act, _fit_forward(layers, act, x, fp64), dz, fp64, out)
+            for gw, gb in reversed(out):
+                cols += [gw, gb]
+    return np.concatenate(cols, axis=1)
+
+
+def fit_accumulate_ref(A, count, G, contributing):
+    """One ``bsk_fit_accumulate`` on the accumulators -> (A float64 (n_params,), count int): A_p = A_p + float64(G[b][p]) for b
+    ascending, count + the contributing samples of the call.  ``A`` is not changed."""
+    A = np.array(A, dtype=np.float64).reshape(-1)
+    G = np.asarray(G)
+    if G.ndim != 2 or G.shape[1] != A.size:
+        raise ValueError("G: (n_blocks, n_params)")
+    with np.errstate(invalid="ignore", over="ignore"):
+        for b in range(G.shape[0]):
+            A = A + G[b].astype(np.float64)
+    return A, int(count) + int(contributing)
+
+
+def fit_stats_ref(spec, params, obs, labels, alive=None, value_targets=None):
+    """The diagnostics row of one accumulate -> float64 (4,), ``FIT_STATS_COLUMNS``: float32 logits, log-probability and value
+    difference as the kernel forms them (``exp`` / ``log`` are the host's), widened and summed sample-ascending within a block, then
+    block-ascending."""
+    spec = _as_spec(spec)
+    o = np.asarray(obs, np.float64).reshape(5, -1)
+    n = o.shape[1]
+    labels, on = _fit_mask(n, labels, alive)
+    l, val = mlp_ref(spec, params, o)
+    m, e, s = softmax_ref(l)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        logp = (l[np.clip(labels, 0, 2), np.arange(n)] - m) - np.log(s)
+    greedy, _ = act_ref(l)
+    pad = -(-n // FIT_BLOCK) * FIT_BLOCK
+    terms = np.zeros((2, pad), np.float64)
+    terms[0, :n] = np.where(on, -logp.astype(np.float64), 0.0)
+    if value_targets is not None:
+        d = np.where(on, val - np.asarray(value_targets, np.float64).reshape(-1).astype(np.float32), np.float32(0)).astype(np.float64)
+        terms[1, :n] = (d * d) * 0.5
+    blocks = np.zeros((2, pad // FIT_BLOCK), np.float64)
+    for s_ in range(FIT_BLOCK):
+        blocks = blocks + terms[:, s_::FIT_BLOCK]
+    row = np.zeros(2, np.float64)
+    for b in range(blocks.shape[1]):
+        row = row + blocks[:, b]
+    return np.array([row[0], row[1], float((on & (greedy == labels)).sum()), float(on.sum())], np.float64)
+
+
+def fit_step_ref(theta, m, v, beta_pow, steps, A, count, lr, beta1, beta2, eps, weight_decay, n_update=None):
+    """What ``bsk_fit_step`` leaves -> (theta, m, v, beta_pow, steps, A, count), float64: nothing moves while count == 0; otherwise
+    for p in 10 .. n_update - 1 (default: all; the action network's end when no accumulate since the last step carried value
+    targets) g = A_p / count + weight_decay * theta_p, Adam's lines (``_adam_step_ref``, the evolution strategy's) and
+    theta_p = theta_p - step: a descent.  beta_pow and steps move on; A and the count come back zero."""
+    theta = np.array(theta, dtype=np.float64).reshape(-1)
+    m, v = np.array(m, dtype=np.float64).reshape(-1), np.array(v, dtype=np.float64).reshape(-1)
+    bp = np.array(beta_pow, dtype=np.float64).reshape(2)
+    A = np.array(A, dtype=np.float64).reshape(-1)
+    lr, b1, b2, eps, wd, _ = (np.float64(x) for x in check_fit(lr, beta1, beta2, eps, weight_decay, 0.0))
+    hi = theta.size if n_update is None else int(n_update)
+    if int(count) == 0:
+        return theta, m, v, bp, int(steps), np.zeros_like(A), 0
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        t = theta[10:hi]
+        g = A[10:hi] / np.float64(int(count)) + wd * t
+        m[10:hi], v[10:hi], step, bp = _adam_step_ref(m[10:hi], v[10:hi], bp, g, lr, b1, b2, eps)
+        theta[10:hi] = t - step
+    return theta, m, v, bp, int(steps) + 1, np.zeros_like(A), 0

@@ -511,7 +511,7 @@ int bsk_policy_rollout(bsk_policy* p, bsk_handle* h, int mode, int substeps, int
 
 /* A population of policies: n_members parameter sets of ONE spec on the device, evaluated side by side - what forks were made for
  * ("population training"): evolution strategies, CEM, population-based training.  The library has no autograd; gradient-free
- * search over the parameters is how a policy is trained on it.
+ * search over the parameters is one of the two ways a policy is trained on it (the other: a supervised fit, bsk_fit_* below).
  * Member <-> env rule: with envs_per_member = E, spacecraft j belongs to member j / E - member m drives the envs [m * E, (m + 1) * E)
  * of one handle (or the columns of one observation block).  E is a multiple of 64 and n = n_members * E exactly: a group of 64
  * spacecraft never straddles two members.
@@ -978,6 +978,85 @@ int bsk_population_set_obs_stats_members(bsk_population* pop, int n_counted);
  * (the search would perturb and move what this call sets), std_min not finite or not positive, optimiser and statistics on
  * different devices. */
 int bsk_es_apply_obs_norm(bsk_es* es, bsk_obs_stats* stats, double std_min, void* stream);
+
+/* Fitting a policy to labelled observations on the device: cross-entropy of the action network against int32 labels and,
+ * optionally, value_coef * squared error of the value network against f64 targets, by Adam on an f64 master copy of the
+ * parameters - planner distillation (behaviour cloning) when the labels are a planner's d_best_action, and the backward pass any
+ * other gradient method would stand on.  A fit is attached to ONE policy, reads its device parameters and writes them at every
+ * step; policy_kernel, its arguments and its outputs are what they are without a fit.
+ * The arithmetic is the definition; f32 unless it says f64, every fmaf one rounding, every other operation rounded on its own.
+ *  Forward, per sample: the policy's definition above (x_i, then per unit one k-ascending fmaf chain from the bias), every layer's
+ *   activations h_l kept.
+ *  Output deltas, action network: m, e_i = expf(l_i - m), s = (e_0 + e_1) + e_2 as in steps 5 / 6 above; p_i = e_i / s;
+ *   g_i = p_i - (i == label ? 1.0f : 0.0f).  A sample CONTRIBUTES when its index is below n, its alive byte is non-zero (NULL: all
+ *   are) and its label is 0, 1 or 2; for every other sample each g_i is +0.0f, and it is not counted.
+ *  Output delta, value network (with targets only): vc = (float)value_coef; d = v - (float)target; g_v = vc * d; +0.0f where the
+ *   sample does not contribute.  Without targets the value network is not evaluated, gets no gradient, and the step leaves its
+ *   parameters, m and v alone.
+ *  Backward through a layer with weights W[j][k], pre-activation deltas d_z[j] and inputs h[k]:
+ *   d_h[k] = the j-ascending chain acc = fmaf(W[j][k], d_z[j], acc) from +0.0f;
+ *   RELU: d_z_prev[k] = h[k] > 0 ? d_h[k] : +0.0f;   TANH: d_z_prev[k] = d_h[k] * fmaf(-h[k], h[k], 1.0f).
+ *   in_scale and in_shift (the first 10 floats) get no gradient and never move.
+ *  Block gradients: samples are taken in blocks of 64 consecutive indices 64 b .. 64 b + 63, the last block filled with samples
+ *   that do not contribute.  GW_b[j][k] = the sample-ascending chain acc = fmaf(d_z[j][s], h[k][s], acc) from +0.0f;
+ *   Gb_b[j] = the sample-ascending chain acc = acc + d_z[j][s] from +0.0f.
+ *  Across blocks and calls, f64: A_p = A_p + (double)G_b,p for b ascending, one accumulator per parameter that every accumulate
+ *   before the next step continues; a uint64 count of the contributing samples beside it.
+ *  Diagnostics, one row of four f64 per accumulate, each a sum over the samples of a block ascending from +0.0 and then over the
+ *   blocks ascending from +0.0:  [0] -(double)logp of the label, logp = (l_label - m) - logf(s) of step 6, contributing samples
+ *   (others add +0.0);  [1] ((double)d * (double)d) * 0.5 (+0.0 without targets);  [2] the contributing samples whose greedy
+ *   action (step 4) is the label;  [3] the contributing samples.
+ *  Step: nothing moves while count == 0.  Otherwise for every parameter p >= 10 (of the action network alone when no accumulate
+ *   since the last step carried targets), f64 and no FMA:  g = A_p / (double)count + weight_decay * theta_p;  m_p, v_p and the
+ *   step term exactly as under bsk_es_set_optimizer;  theta_p = theta_p - (lr * (m_p / (1.0 - p1))) / (sqrt(v_p / (1.0 - p2)) + eps)
+ *   - a descent, where the evolution strategy ascends.  A one-thread launch behind it moves beta_pow and the step counter on and
+ *   zeroes the count (A_p is zeroed by the update); a last launch writes (float)theta into the policy's device layout.
+ * RELU networks: gradients, A, count and the step are reproducible bit for bit from the device's own output deltas
+ * (basilisk_env_amd/policy_ref.py: fit_backward_ref, fit_accumulate_ref, fit_step_ref).  expf, logf and tanhf are the device
+ * library's: the output deltas, the diagnostics' first column and everything behind a TANH layer are reproducible to a bound.
+ * A fit belongs to its policy's device, is not thread-safe and serves ONE stream at a time, like a population.  The policy must
+ * outlive it.  bsk_policy_set_params on the attached policy does NOT update theta - the next step would overwrite the policy with
+ * the old theta's successor: give the fit the same parameters through bsk_fit_set_state. */
+typedef struct bsk_fit bsk_fit;
+/* theta := the policy's current parameters (synchronises the device, copies).  BSK_EINVAL: NULL pointers; lr or value_coef not
+ * finite or negative; beta1 or beta2 outside [0, 1), eps not finite or <= 0, weight_decay not finite or < 0. */
+int bsk_fit_create(bsk_policy* p, double lr, double beta1, double beta2, double eps, double weight_decay, double value_coef,
+                   bsk_fit** out);
+void bsk_fit_destroy(bsk_fit* f);
+/* Two launches on `stream` (a hipStream_t, NULL = the null stream): raw DEVICE pointers, no copy, no synchronisation; capturable
+ * once an accumulate of at least this n has allocated the scratch of the block gradients (a call that must allocate returns
+ * BSK_EINVAL under capture).
+ *   d_obs           f64[5][obs_stride], obs_stride >= n: the layout of bsk_get_obs_device
+ *   d_label         int32[n]: what bsk_select_branches / bsk_beam_select leave in d_best_action
+ *   d_value_target  f64[n] or NULL (non-NULL with a policy that has no value network: BSK_EINVAL)
+ *   d_alive         uint8[n] or NULL
+ *   d_dlogits       f32[3][out_stride] or NULL: the g_i of every sample (out_stride >= n)
+ * BSK_EINVAL before anything is launched: NULL fit / d_obs / d_label, n < 1 or above 2^28, a stride below n. */
+int bsk_fit_accumulate(bsk_fit* f, const double* d_obs, int64_t obs_stride, int n, const int32_t* d_label,
+                       const double* d_value_target, const uint8_t* d_alive, float* d_dlogits, int64_t out_stride, void* stream);
+/* The step above: three launches on `stream`, no copy, no synchronisation, capturable.  The learning rate is an argument of the
+ * launch: a captured graph keeps the one it was captured with. */
+int bsk_fit_step(bsk_fit* f, void* stream);
+/* The diagnostics row of the last accumulate as DEVICE words, f64[4] (read-only for the caller; valid for the fit's lifetime).  No
+ * launch, no copy, no synchronisation. */
+int bsk_fit_stats_device(bsk_fit* f, const double** d_row4);
+/* theta, m, v f64[n_params], beta_pow f64[2] and the number of steps that moved something; each may be NULL.  Synchronises.  The
+ * accumulators A and the count are not part of it: a checkpoint is taken behind a step, where they are zero. */
+int bsk_fit_get_state(bsk_fit* f, double* theta, double* m, double* v, double* beta_pow, uint64_t* steps);
+/* The same back (NULL: keep; steps always): for a checkpoint that resumes bit for bit, and for new parameters of the policy - a
+ * theta given here is also written to the attached policy as (float)theta.  Whatever has been accumulated since the last step is
+ * discarded: A, the count and the diagnostics row are zeroed, as behind a step.  Synchronises. */
+int bsk_fit_set_state(bsk_fit* f, const double* theta, const double* m, const double* v, const double* beta_pow, uint64_t steps);
+/* A new learning rate for the steps enqueued from now on.  BSK_EINVAL when not finite or negative. */
+int bsk_fit_set_lr(bsk_fit* f, double lr);
+/* The alive bytes of a loop that collects samples from a handle while it steps it (d_alive of bsk_fit_accumulate), by the rule of the
+ * population's fitness - an env stops being alive after the first step with reason != 0, and stays out when BSK_FLAG_AUTO_RESET
+ * starts its next episode.  first != 0, in front of the loop's first step: d_alive[j] = 1 for every env, and d_reason is not read -
+ * the observation every env holds then counts, whatever its last step before the loop left in the reason bytes (an env whose
+ * episode is over and that has not been reset is the caller's to reset or to mask).  first == 0, behind each step, with the reason
+ * bytes of bsk_get_obs_device:  d_alive[j] = d_alive[j] != 0 && d_reason[j] == 0.  Bytes 1 / 0.  One launch on `stream` of the current
+ * device, no copy, no synchronisation, capturable.  BSK_EINVAL for NULL pointers and n < 1. */
+int bsk_fit_alive_mask(const uint8_t* d_reason, int n, int first, uint8_t* d_alive, void* stream);
 
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the

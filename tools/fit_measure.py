@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Cost of one step of the policy fit ("Fitting the policy"): 65 536 labelled observations, `relu [64, 64]`,
+one `PolicyFit.accumulate` + `step` on an otherwise idle stream, against the same loss and an Adam step in torch f32 autograd on the
+same card.
+
+  python tools/fit_measure.py time
+      device events around the pair, 30 warming and 200 timed iterations one by one, the median and the 10th / 90th percentile; the
+      same around `accumulate` alone and `step` alone; then torch: `F.cross_entropy(model(x * scale + shift), labels)`,
+      `backward()` and `torch.optim.Adam.step()` on float32 inputs that are already on the device, timed the same way.
+  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o fit -- python tools/fit_measure.py kernel
+      (a run of its own) 60 pairs on the null stream: DIR/.../fit_kernel_stats.csv holds the mean time of
+      fit_block_kernel, fit_fold_kernel, fit_adam_kernel, fit_advance_kernel and es_center_kernel apart.
+  BSKGPU_LIB=basilisk_env_amd/variants/fit_stamps.so python tools/fit_measure.py stamps
+      (after `make -C basilisk_env_amd/csrc fit-stamps`) the share of fit_block_kernel's clock ticks, summed over its workgroups,
+      that thread 0 spends in the weight-gradient walks - the library is a measurement build whose diagnostics row carries ticks.
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+N, HIDDEN, WARM, ITERS = 65536, (64, 64), 30, 200
+
+
+def _setup():
+    import torch
+    from _policy_bounds import observation_like, seeded_policy
+    from basilisk_env_amd import policy as P
+    spec, params = seeded_policy(HIDDEN, "relu", seed=1)
+    obs = observation_like(N, 3)
+    labels = np.where(obs[3] < 0.4, 1, np.where(obs[2] > 0.7, 2, 0)).astype(np.int32)
+    pol = P.DevicePolicy(spec, params)
+    fit = P.PolicyFit(pol, lr=1e-3)
+    return torch, P, spec, params, obs, labels, pol, fit
+
+
+def _timed(torch, stream, fn):
+    """-> microseconds per call: (median, p10, p90) of ITERS calls, each between two events on ``stream``"""
+    for _ in range(WARM):
+        fn()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(ITERS)]
+    for a, b in ev:
+        a.record(stream)
+        fn()
+        b.record(stream)
+    torch.cuda.synchronize()
+    t = np.array([a.elapsed_time(b) for a, b in ev]) * 1e3
+    return float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))
+
+
+def time_():
+    torch, P, spec, params, obs, labels, pol, fit = _setup()
+    side = torch.cuda.Stream()
+    d_obs, d_lab = torch.from_numpy(obs).cuda(), torch.from_numpy(labels).cuda()
+    torch.cuda.synchronize()
+    s = side.cuda_stream
+    with torch.cuda.stream(side):
+        def pair():
+            fit.accumulate(d_obs, d_lab, stream=s)
+            fit.step(s)
+        for name, fn in (("accumulate + step", pair), ("accumulate alone", lambda: fit.accumulate(d_obs, d_lab, stream=s)),
+                         ("step alone", lambda: fit.step(s))):
+            print("device  %-18s %8.1f us  (p10 %.1f, p90 %.1f)" % ((name,) + _timed(torch, side, fn)))
+        row = fit.stats()
+        print("device  last row: mean cross-entropy %.4f, correct %d of %d" % (row["nll_sum"] / row["count"], row["correct"], row["count"]))
+
+        scale, shift, layers, _ = P.unpack_params(spec, params)
+        mods = []
+        for k, (W, b) in enumerate(layers):
+            lin = torch.nn.Linear(W.shape[1], W.shape[0])
+            with torch.no_grad():
+                lin.weight.copy_(torch.from_numpy(W.copy()))
+                lin.bias.copy_(torch.from_numpy(b.copy()))
+            mods += [lin] + ([torch.nn.ReLU()] if k + 1 < len(layers) else [])
+        model = torch.nn.Sequential(*mods).cuda()
+        opt = torch.optim.Adam(model.parameters(), lr=1e-3)
+        x = torch.from_numpy(obs.T.astype(np.float32).copy()).cuda()
+        sc, sh = torch.from_numpy(scale.copy()).cuda(), torch.from_numpy(shift.copy()).cuda()
+        y = d_lab.long()
+
+        def torch_step():
+            opt.zero_grad(set_to_none=True)
+            loss = torch.nn.functional.cross_entropy(model(x * sc + sh), y)
+            loss.backward()
+            opt.step()
+        print("torch   %-18s %8.1f us  (p10 %.1f, p90 %.1f)" % (("f32 autograd + Adam",) + _timed(torch, side, torch_step)))
+    fit.close()
+    pol.close()
+
+
+def kernel():
+    torch, P, spec, params, obs, labels, pol, fit = _setup()
+    d_obs, d_lab = torch.from_numpy(obs).cuda(), torch.from_numpy(labels).cuda()
+    torch.cuda.synchronize()
+    for _ in range(60):
+        fit.accumulate(d_obs, d_lab)
+        fit.step()
+    torch.cuda.synchronize()
+    fit.close()
+    pol.close()
+
+
+def stamps():
+    if "fit_stamps" not in os.environ.get("BSKGPU_LIB", ""):
+        sys.exit("run with BSKGPU_LIB=<...>/variants/fit_stamps.so (make -C basilisk_env_amd/csrc fit-stamps)")
+    torch, P, spec, params, obs, labels, pol, fit = _setup()
+    d_obs, d_lab = torch.from_numpy(obs).cuda(), torch.from_numpy(labels).cuda()
+    torch.cuda.synchronize()
+    for _ in range(3):
+        fit.accumulate(d_obs, d_lab)
+    row = fit.stats()
+    walk, whole = row["nll_sum"], row["value_loss_sum"]
+    print("stamps  fit_block_kernel, %d workgroups: weight-gradient walks %.0f of %.0f ticks of thread 0 = %.1f %%"
+          % ((N + 63) // 64, walk, whole, 100.0 * walk / whole))
+    fit.close()
+    pol.close()
+
+
+if __name__ == "__main__":
+    {"time": time_, "kernel": kernel, "stamps": stamps}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
