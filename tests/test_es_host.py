@@ -10,6 +10,7 @@ import mpmath as mp
 import numpy as np
 import pytest
 
+from _es_cases import TAIL_K_FAR, beyond_one_tile, tail_rows
 from basilisk_env_amd import policy as P
 
 # The greatest errors measured over the sample of _sample_k() (they are printed by the test): 4.1e-15 absolute, 7.1e-16 relative.
@@ -73,6 +74,30 @@ def test_inverse_normal_is_antisymmetric_to_the_bit(sample):
     mirrored = P.es_inverse_normal_ref(P.es_uniform_ref(np.uint64(2 ** 52 - 1) - k))
     assert np.array_equal(_bits(mirrored), _bits(-z))
     assert np.array_equal(P.es_uniform_ref(np.uint64(2 ** 52 - 1) - k), 1.0 - P.es_uniform_ref(k))      # 1 - u is exact
+
+
+def test_the_recorded_seeds_draw_from_the_far_tail():
+    """The far branch of the inverse normal CDF (r > 5, the E / F rationals) through the whole chain seed -> Philox -> k -> u -> z:
+    tests/test_gpu_es.py asks the device for the z recorded here, so the record is held to the restatement's bits, to the branch
+    (|z| above the E polynomial's value at r = 5, which the r <= 5 branch never exceeds) and to mpmath."""
+    rows, k_far = tail_rows(), TAIL_K_FAR
+    assert len(rows) >= 3 and any(seed >= 2 ** 32 for seed, _, _, _ in rows)         # (the key's high word)
+    assert any(z > 0 for _, _, _, z in rows) and any(z < 0 for _, _, _, z in rows)
+    mp.mp.dps = 40
+    for seed, j, k, z in rows:
+        got = P.es_noise_ref(seed, 0, 1, j + 1)[0, j]
+        assert np.array_equal(_bits(got), _bits(z)), (seed, j, float(got).hex())
+        # the k of the definition, and on the far side of the switch test_inverse_normal_against_mpmath's sample finds by bisection
+        w0, w1, _, _ = P.philox4x32_10(j, 0, 0, 0, seed & 0xFFFFFFFF, seed >> 32)
+        assert (int(w0) >> 6) * 2 ** 26 + (int(w1) >> 6) == k and min(k, 2 ** 52 - 1 - k) <= k_far
+        assert _bits(P.es_inverse_normal_ref(_u(k)))[0] == _bits(z)[0]
+        assert float(np.sqrt(-P._series_log(_u(min(k, 2 ** 52 - 1 - k))))[0]) > 5.0
+        assert abs(z) > 6.6579046435 and (z < 0) == (k < 2 ** 51)
+        u = (mp.mpf(k) + mp.mpf("0.5")) * mp.mpf(2) ** -52
+        want = mp.sqrt(2) * mp.erfinv(2 * u - 1)
+        d = abs(mp.mpf(z) - want)
+        print("seed %d, j %d: z %s, |z - mpmath| %.3g" % (seed, j, float(z).hex(), float(d)))
+        assert float(d) <= BOUND_ABS and float(d / abs(want)) <= BOUND_REL
 
 
 def test_moments_of_two_million_draws():
@@ -156,6 +181,23 @@ def test_ties_nan_and_infinities_rank_as_centred_ranks(fitness):
     z = P.es_noise_ref(1, 0, f.size // 2, 14)
     want = theta + 0.05 / (f.size * 0.1) * ((u[0::2] - u[1::2]) @ z)
     assert np.isfinite(got).all() and np.array_equal(got[:3], theta[:3]) and np.allclose(got, np.where(np.arange(14) < 3, theta, want), rtol=0, atol=1e-13)
+
+
+def test_the_vectors_beyond_one_tile_rank_as_the_counting_rule_says():
+    """tests/_es_cases.py: what the GPU tests feed the ranking kernels at 258 members, against the counting rule restated above"""
+    cases = beyond_one_tile(258, np.random.default_rng(258))
+    assert len(cases) == 4 and beyond_one_tile(256, np.random.default_rng(0)) == []
+    a, b, c, d = cases
+    assert a[257] == a[5] and np.isnan(a[256]) and np.isnan(b[[11, 256, 257]]).all() and c[256] == c[257] == c.max()
+    assert d[256] == np.inf and d[257] == -np.inf
+    ranks = []
+    for f in cases:
+        u = P.centred_ranks(f)
+        assert np.array_equal(_bits(_ranks_by_counting(f)), _bits(u))
+        ranks.append(np.rint((0.5 - u) * 257).astype(int))
+    assert ranks[0][257] == ranks[0][5] + 1 and ranks[0][256] == 257      # the tie goes to the lower index; the one NaN is last
+    assert ranks[1][[11, 256, 257]].tolist() == [255, 256, 257]           # the three NaNs at the bottom, by index
+    assert ranks[2][[256, 257]].tolist() == [0, 1] and ranks[3][[40, 256, 257]].tolist() == [0, 1, 257]
 
 
 def test_tell_refuses_odd_and_empty_populations():

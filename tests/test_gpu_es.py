@@ -3,8 +3,15 @@
 Every check is an EQUALITY of bits against the numpy restatement (policy.es_ask_ref / es_tell_ref, which tests/test_es_host.py
 holds to mpmath, to the plain matrix product and to EvolutionStrategy) or against code that already ships - no tolerance anywhere.
 Shapes: P = 2 is one pair (63 empty lanes in tell's sum), P = 130 is 65 pairs (one lane with two terms, and a ranking with one
-thread past the members), P = 256 gives every lane two terms; the tanh spec has a value network, whose fan-outs 3 and 1 are padded
-in the device layout; generation 2^32 + 3 and seed 2^33 + 5 catch a dropped high word.
+thread past the members), P = 256 gives every lane two terms; P = 258 and 600 take the ranking past one tile of 256 values and one
+workgroup (258: a second workgroup and a second tile of exactly one pair; 600: three tiles, a partial third workgroup, and 300
+pairs, so lanes with five and with four terms), with ties, NaNs and infinities on the far side of the boundaries
+(tests/_es_cases.py); the tanh spec has a value network, whose fan-outs 3 and 1 are padded in the device layout; generation
+2^32 + 3 and seed 2^33 + 5 catch a dropped high word.
+
+The far tail of the inverse normal CDF (r > 5: p < e^-25, 2.8e-11 per draw) is reached by choosing the key: the seeds of
+tests/golden/es_tail_seeds.json (found by tools/es_tail_seeds.c; tests/test_es_host.py holds the restatement there to mpmath) make
+the first draw of one parameter a |z| of about 6.8.
 """
 import ctypes
 import subprocess
@@ -13,6 +20,7 @@ import numpy as np
 import pytest
 
 from _device_bits import build_c_consumer, download as _download, same as _same
+from _es_cases import beyond_one_tile, tail_rows
 from _policy_bounds import observation_like, seeded_policy
 from basilisk_env_amd import _hip, _lib
 from basilisk_env_amd import policy as P
@@ -32,7 +40,7 @@ def _members(pop):
 
 @pytest.mark.parametrize("frozen", [10, 0])
 @pytest.mark.parametrize("which", sorted(SPECS))
-@pytest.mark.parametrize("n_members", [2, 130])
+@pytest.mark.parametrize("n_members", [2, 130, 258, 600])
 def test_ask_writes_the_members_of_the_definition(n_members, which, frozen):
     import torch
     hidden, activation, value_hidden = SPECS[which]
@@ -83,10 +91,10 @@ def _fitness_cases(n_members, rng):
     f[7] = f[3]                                # a tie
     f[10] = f[11] = np.nan                     # a NaN pair
     f[20], f[21], f[40], f[41 + 64] = np.inf, -np.inf, np.inf, np.nan
-    return [f, rng.normal(size=n_members), np.zeros(n_members)]
+    return [f, rng.normal(size=n_members), np.zeros(n_members)] + beyond_one_tile(n_members, rng)
 
 
-@pytest.mark.parametrize("n_members", [2, 130, 256])
+@pytest.mark.parametrize("n_members", [2, 130, 256, 258, 600])
 def test_tell_moves_theta_as_the_definition_does(n_members):
     import torch
     spec, theta0 = seeded_policy((16,), "relu", None, seed=9)
@@ -123,6 +131,88 @@ def test_tell_moves_theta_as_the_definition_does(n_members):
         es.tell(torch.zeros(n_members + 2, dtype=torch.float64, device="cuda"))
     with pytest.raises(ValueError):
         es.tell(torch.zeros(n_members, dtype=torch.float32, device="cuda"))
+    es.close()
+
+
+TAIL_IDS = ["seed%d-j%d" % row[:2] for row in tail_rows()]
+
+
+def _tail_strategy(row, n_members=2, **kw):
+    """spec (16,) relu, theta = 0 behind the ten input entries, sigma = 1 and lr = P, so that c = lr / (P * sigma) = 1"""
+    import torch
+    spec, theta0 = seeded_policy((16,), "relu", None, seed=23)
+    theta0[10:] = 0.0
+    es = P.DeviceEvolutionStrategy(spec, theta0, n_members, sigma=1.0, lr=float(n_members), seed=row[0], frozen=10, **kw)
+    fitness = np.linspace(1.0, 0.0, n_members)                 # descending: member 0, the + z one of pair 0, is the best
+    d_f = torch.from_numpy(fitness).cuda()
+    torch.cuda.synchronize()
+    return spec, theta0.astype(np.float64), es, fitness, d_f
+
+
+@pytest.mark.parametrize("row", tail_rows(), ids=TAIL_IDS)
+def test_the_far_tail_of_the_inverse_normal_reaches_ask_and_tell(row):
+    """z(0, 0, j) of the row's seed comes from the r > 5 branch of es_inverse_normal, which no test reaches by chance.  ask: the
+    two members are the restatement's, column j the float of +-z.  tell with fitness [1, 0]: w_0 = 1, c = 1 and the tree adds
+    +0.0 alone, so theta_j IS the recorded z - with no restatement in between."""
+    seed, j, _, z = row
+    spec, theta0, es, fitness, d_f = _tail_strategy(row)
+    pop = P.PolicyPopulation(spec, n_members=2)
+    es.ask(pop)
+    got = _members(pop)
+    assert _same(got, P.es_ask_ref(theta0, 1.0, 10, 2, seed, 0))
+    assert _same(got[:, j], np.array([z, -z]).astype(np.float32)) and abs(z) > 6.6579046435
+    es.tell(d_f)
+    theta = es.theta
+    assert _same(theta, P.es_tell_ref(theta0, fitness, 1.0, 2.0, 10, seed, 0))
+    assert _same(theta[j], np.float64(z)), (float(theta[j]).hex(), float(z).hex())
+    assert np.abs(np.delete(theta, j)[10:]).max() < 6.0 and es.generation == 1     # (the one wild draw is the recorded one)
+    assert _same(theta[:10], theta0[:10])
+    es.close()
+    pop.close()
+
+
+@pytest.mark.parametrize("n_members", [2, 4])
+@pytest.mark.parametrize("optimizer", ["sgd", "adam"])
+@pytest.mark.parametrize("row", tail_rows(), ids=TAIL_IDS)
+def test_the_far_tail_goes_through_the_step_size_rule_and_adam(row, optimizer, n_members):
+    """The same draw under BSK_ES_SIGMA_PGPE (es_tell_sigma_kernel / es_tell_adam_sigma_kernel).  Two members have
+    q_0 = u_0 + u_1 = 0 and the vector cannot move; FOUR have q_0 = 2 / 3, and there z * z - 1, about 45, is the largest term the
+    rule ever sees: parameter j runs into the max_change clamp and then into sigma_max."""
+    seed, j, _, z = row
+    adam = dict(optimizer="adam", beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2) if optimizer == "adam" else {}
+    rule = (4.0, 0.2, 0.5, 1.1)
+    spec, theta0, es, fitness, d_f = _tail_strategy(row, n_members, sigma_adapt="pgpe", lr_sigma=rule[0], sigma_max_change=rule[1],
+                                                    sigma_min=rule[2], sigma_max=rule[3], **adam)
+    n = theta0.size
+    state = (np.zeros(n), np.zeros(n), np.ones(2), 0.9, 0.999, 1e-8, 1e-2) if optimizer == "adam" else None
+    es.tell(d_f)
+    want = P.es_tell_pgpe_ref(theta0, np.ones(n), fitness, float(n_members), 10, seed, 0, *rule, adam=state)
+    got = (es.theta, es.sigma_vector) + (es.moments if optimizer == "adam" else ())
+    for g, w, name in zip(got, want, ("theta", "sigma", "m", "v", "beta_pow")):
+        assert _same(g, w), name
+    assert np.isfinite(got[0]).all() and got[0][j] != 0.0
+    if n_members == 2:
+        assert _same(got[1], np.ones(n))
+        if optimizer == "sgd":
+            assert _same(got[0][j], np.float64(z))             # lr / (Pd * sg) = 1
+    else:
+        # (elsewhere r is 2 / 3 of z_0 ** 2 - z_1 ** 2 of two ordinary draws: some entries stop at the lower clamp, some move freely)
+        assert got[1][j] == 1.1 and (got[1][10:] == 0.8).any() and ((got[1][10:] > 0.8) & (got[1][10:] < 1.1)).any()
+    es.close()
+
+
+@pytest.mark.parametrize("row", tail_rows(), ids=TAIL_IDS)
+def test_the_far_tail_goes_through_adam(row):
+    """... and under Adam with the one sigma (es_tell_adam_kernel): g_j = z / 2 - weight_decay * 0 is the first gradient Adam sees"""
+    seed, j, _, z = row
+    _, theta0, es, fitness, d_f = _tail_strategy(row, optimizer="adam", beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2)
+    n = theta0.size
+    es.tell(d_f)
+    want = P.es_tell_adam_ref(theta0, np.zeros(n), np.zeros(n), np.ones(2), fitness, 1.0, 2.0, 10, seed, 0, 0.9, 0.999, 1e-8, 1e-2)
+    got = (es.theta,) + es.moments
+    for g, w, name in zip(got, want, ("theta", "m", "v", "beta_pow")):
+        assert _same(g, w), name
+    assert np.isfinite(got[0]).all() and _same(got[1][j], (1.0 - 0.9) * (0.5 * np.float64(z)))
     es.close()
 
 

@@ -3,7 +3,8 @@ csrc/bsk_es.hip; contract in include/bskgpu.h), alone and in whole generations o
 
 Every check is an EQUALITY of bits against policy.es_tell_adam_ref (which tests/test_es_adam_host.py holds to an operation-by-
 operation restatement) or against code that already ships - no tolerance anywhere.  Shapes as in tests/test_gpu_es.py: P = 2 is one
-pair (63 empty lanes), P = 130 has one lane with two terms and a ranking thread past the members, P = 256 gives every lane two.
+pair (63 empty lanes), P = 130 has one lane with two terms and a ranking thread past the members, P = 256 gives every lane two,
+P = 258 and 600 rank over two and three tiles and workgroups with the awkward values beyond the first (tests/_es_cases.py).
 """
 import ctypes
 import subprocess
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 
 from _device_bits import build_c_consumer, download as _download, same as _same
+from _es_cases import beyond_one_tile
 from _policy_bounds import seeded_policy
 from basilisk_env_amd import _hip, _lib
 from basilisk_env_amd import policy as P
@@ -34,12 +36,12 @@ def _fitness_cases(n_members, rng):
     f[7] = f[3]                                # a tie
     f[10] = f[11] = np.nan                     # a NaN pair
     f[20], f[21], f[40], f[41 + 64] = np.inf, -np.inf, np.inf, np.nan
-    return [f, np.roll(f, 1), np.zeros(n_members)]
+    return [f, np.roll(f, 1), np.zeros(n_members)] + beyond_one_tile(n_members, rng)
 
 
 @pytest.mark.parametrize("weight_decay", [0.0, 1e-2])
 @pytest.mark.parametrize("frozen", [0, 10])
-@pytest.mark.parametrize("n_members", [2, 130, 256])
+@pytest.mark.parametrize("n_members", [2, 130, 256, 258, 600])
 def test_adam_tell_is_the_definition(n_members, frozen, weight_decay):
     import torch
     spec, theta0 = seeded_policy((16,), "relu", None, seed=9)

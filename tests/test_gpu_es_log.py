@@ -6,7 +6,8 @@ es_ask_ref / es_ask_sigma_ref, which tests/test_es_log_host.py holds to an opera
 optimiser with no log - no tolerance anywhere.  One exception the definition makes itself: which NaN a SUM becomes when +inf and
 -inf are both among its terms is not defined, so the three sum columns compare as "the same bits, or a NaN in both".
 Shapes as in tests/test_gpu_es.py: P = 2 is one pair with 63 empty lanes of the one-wave reduction, P = 130 gives two lanes
-three terms and the others two, P = 256 gives every lane four; generation 2^32 + 3 and seed 2^33 + 5 catch a dropped high word
+three terms and the others two, P = 256 gives every lane four, P = 258 and 600 put the ranking behind the update past one tile
+(tests/_es_cases.py) and give the log's lanes unequal walks; generation 2^32 + 3 and seed 2^33 + 5 catch a dropped high word
 (2^32 + 3 and 3 fall into different slots of every capacity used here).
 """
 import ctypes
@@ -15,6 +16,7 @@ import numpy as np
 import pytest
 
 from _device_bits import bits as _bits, download as _download, same as _same
+from _es_cases import beyond_one_tile
 from _policy_bounds import seeded_policy
 from basilisk_env_amd import _lib
 from basilisk_env_amd import policy as P
@@ -70,7 +72,7 @@ def _fitness_cases(n_members, rng):
     g[9] = g[100] = g.min() - 1.0
     zeros = np.zeros(n_members)
     zeros[1::2] = -0.0
-    return [f, g, np.full(n_members, np.nan), zeros, -zeros, rng.normal(size=n_members)]
+    return [f, g, np.full(n_members, np.nan), zeros, -zeros, rng.normal(size=n_members)] + beyond_one_tile(n_members, rng)
 
 
 def _make(spec, theta0, n_members, frozen, rule, seed=SEED, **kw):
@@ -92,7 +94,7 @@ def _before(es, rule):
 
 
 @pytest.mark.parametrize("bound", ["null", "own", "array"])
-@pytest.mark.parametrize("n_members", [2, 130, 256])
+@pytest.mark.parametrize("n_members", [2, 130, 256, 258, 600])
 def test_every_tell_writes_the_row_of_the_definition_and_changes_nothing_else(n_members, bound):
     import torch
     spec, theta0 = seeded_policy((16,), "relu", None, seed=9)

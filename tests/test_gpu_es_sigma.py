@@ -4,7 +4,8 @@ kernels and es_rank_q_kernel in csrc/bsk_es.hip; contract in include/bskgpu.h), 
 Every check is an EQUALITY of bits against policy.es_ask_sigma_ref / policy.es_tell_pgpe_ref (which tests/test_es_sigma_host.py
 holds to an operation-by-operation restatement) or against code that already ships - no tolerance anywhere.  Shapes as in
 tests/test_gpu_es_adam.py: P = 2 is one pair (63 empty lanes, and q_0 = 0: sigma cannot move), P = 130 has one lane with two terms
-and a ranking thread past the members, P = 256 gives every lane two.
+and a ranking thread past the members, P = 256 gives every lane two, P = 258 and 600 take es_rank_q_kernel over two and three
+tiles and workgroups with the awkward values beyond the first (tests/_es_cases.py).
 """
 import subprocess
 
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 
 from _device_bits import build_c_consumer, download as _download, same as _same
+from _es_cases import beyond_one_tile
 from _policy_bounds import seeded_policy
 from basilisk_env_amd import _hip, _lib
 from basilisk_env_amd import policy as P
@@ -40,7 +42,7 @@ def _fitness_cases(n_members, rng):
     f[7] = f[3]                                # a tie
     f[10] = f[11] = np.nan                     # a NaN pair
     f[20], f[21], f[40], f[41 + 64] = np.inf, -np.inf, np.inf, np.nan
-    return [f, np.roll(f, 1), np.zeros(n_members)]
+    return [f, np.roll(f, 1), np.zeros(n_members)] + beyond_one_tile(n_members, rng)
 
 
 def _sigma0(n):
@@ -69,7 +71,7 @@ def _branches(sv, fitness, frozen, generation):
 
 @pytest.mark.parametrize("optimizer", ["sgd", "adam"])
 @pytest.mark.parametrize("frozen", [0, 10])
-@pytest.mark.parametrize("n_members", [2, 130, 256])
+@pytest.mark.parametrize("n_members", [2, 130, 256, 258, 600])
 def test_tell_is_the_definition(n_members, frozen, optimizer):
     import torch
     spec, theta0 = seeded_policy((16,), "relu", None, seed=9)
@@ -114,7 +116,7 @@ def test_tell_is_the_definition(n_members, frozen, optimizer):
 
 
 @pytest.mark.parametrize("frozen", [0, 10])
-@pytest.mark.parametrize("n_members", [2, 130, 256])
+@pytest.mark.parametrize("n_members", [2, 130, 256, 258, 600])
 def test_ask_is_the_definition(n_members, frozen):
     spec, theta0 = seeded_policy((16,), "relu", None, seed=9)
     n = theta0.size
@@ -137,7 +139,7 @@ def test_ask_is_the_definition(n_members, frozen):
 
 
 @pytest.mark.parametrize("optimizer", ["sgd", "adam"])
-@pytest.mark.parametrize("n_members", [2, 130, 256])
+@pytest.mark.parametrize("n_members", [2, 130, 256, 258, 600])
 def test_a_uniform_vector_with_lr_sigma_zero_is_the_optimiser_that_never_selected_the_mode(n_members, optimizer):
     import torch
     frozen = 10

@@ -5,8 +5,17 @@ Output deltas go through the device library's expf and are held to the bound of 
 them is an EQUALITY of bits for relu networks: the device's own deltas are handed to policy.fit_backward_ref / fit_accumulate_ref /
 fit_step_ref as exact f32 numbers.  The accumulators A are read as Adam's first moment after one step with beta1 = 0, weight_decay = 0
 and lr = 0: m = 0 * m + (1 - 0) * g = g = A / count exactly, and theta stays where it was.  tanh networks carry the derived bound.
-Shapes are small: n = 65 is two blocks with one nearly empty, 200 is four with a tail, (80, 48) splits unevenly over the four waves,
-(128, 128, 128) is the widest network there is.
+Shapes are small: n = 65 is two blocks with one nearly empty, 200 is four with a tail, (128, 128, 128) is the widest network there
+is.  The bit-for-bit cases go past every loop's first trip.  The fold (fit_fold_kernel) adds 32 blocks at a time and the rest one by
+one: 2048 samples are one batch and no rest, 2049 one batch and a block of a single sample (a second time with one value target of
+1e12, without which the f64 sum of f32 block gradients is exact in any order), 4400 + 100 two batches and five blocks
+and then a second call onto a non-zero A - with a value network, so that the diagnostics row's value loss goes through the batched
+loop too.  The weight gradients (fit_weight_grad) walk the wider side 64 rows at a time: (80, 48) and (112, 48) give a second trip
+with 16 and 48 of its 64 lanes valid, in either orientation (the first layers, 80 and 112 over K = 5, own d_z rows; the second ones,
+48 over K = 80 and K = 112, own h rows), a (96,) value network puts 96 rows over K = 5, (16, 128) puts 128 rows over K = 16 (two full
+trips, 16 rows for the waves to split), (48, 112, 16) stacks three unequal hidden layers on the row offsets and the in-place deltas.
+The two networks of a fit carry their own activations: both orders of tanh and relu are checked, each slice by the means its
+activation allows.
 """
 import subprocess
 
@@ -119,10 +128,18 @@ def _reference_moment(spec, params, calls, value_coef):
     return P.fit_step_ref(params.astype(np.float64), z, z, np.ones(2), 0, A, count, 0.0, 0.0, 0.999, 1e-8, 0.0)[1], count
 
 
-@pytest.mark.parametrize("case", ["relu16", "relu128x3", "value", "two_calls"])
+BIT_CASES = {"relu16": ((16,), None, [200]), "relu128x3": ((128, 128, 128), None, [65]), "value": ((32, 16), (16,), [130]),
+             "two_calls": ((16,), None, [100, 29]),
+             # the fold past its batch of 32 blocks; the weight gradients past one trip of 64 rows (the module's docstring)
+             "fold32": ((16,), None, [2048]), "fold33": ((16,), (16,), [2049]), "fold33_wide": ((16,), (16,), [2049]),
+             "fold69_two_calls": ((16,), (16,), [4400, 100]),
+             "w80_48": ((80, 48), None, [130]), "w112_48_v96": ((112, 48), (96,), [130]), "w16_128": ((16, 128), None, [130]),
+             "w48_112_16": ((48, 112, 16), None, [65])}
+
+
+@pytest.mark.parametrize("case", list(BIT_CASES))
 def test_backward_and_accumulators_equal_the_restatement_bit_for_bit(case):
-    hidden, vh, sizes = {"relu16": ((16,), None, [200]), "relu128x3": ((128, 128, 128), None, [65]),
-                         "value": ((32, 16), (16,), [130]), "two_calls": ((16,), None, [100, 29])}[case]
+    hidden, vh, sizes = BIT_CASES[case]
     spec, params = seeded_policy(hidden, "relu", vh, seed=11)
     value_coef = 0.5
     f = _Fit(spec, params, lr=0.0, beta1=0.0, weight_decay=0.0, value_coef=value_coef)
@@ -130,6 +147,10 @@ def test_backward_and_accumulators_equal_the_restatement_bit_for_bit(case):
     for k, n in enumerate(sizes):
         obs, labels, alive, targets = _batch(n, 20 + k)
         targets = targets if vh else None
+        if case == "fold33_wide":
+            # The f64 sum of a few dozen f32 block gradients of one magnitude is exact, whatever its order.  One target of 1e12
+            # spreads the value network's block gradients over more than 53 bits: there the sum rounds, and the order shows.
+            targets[n // 3] = 1e12
         dl = f.accumulate(obs, labels, alive, targets)
         calls.append((obs, labels, alive, targets, dl))
         _check_stats(f.fit.stats(), spec, params, obs, labels, alive, targets)
@@ -156,6 +177,49 @@ def test_tanh_backward_lies_within_the_derived_bound():
     err, tol = np.abs(m * count - G64.sum(axis=0)), bound.sum(axis=0) * (1.0 + 2.0 ** -20) + 2.0 ** -52 * np.abs(G64.sum(axis=0))
     print("tanh (32,): max |A - fp64| %.3e, max bound %.3e, max ratio %.3f" % (err.max(), tol.max(), (err / np.maximum(tol, 1e-300)).max()))
     assert count == 126 and (err <= tol).all() and not m[:10].any()
+    f.close()
+
+
+@pytest.mark.parametrize("activation,value_activation", [("tanh", "relu"), ("relu", "tanh")])
+def test_each_network_of_a_fit_runs_its_own_activation(activation, value_activation):
+    """(32, 16) with a (48,) value network at n = 130, the two activations different.  The relu network's slice of A is the
+    restatement's bit for bit whichever of the two it is; a tanh action network lies within ``backward_bound``; a tanh value network
+    has no bound yet and is asked to be finite and NOT what the relu / relu restatement of the same floats gives.  Swapping the two
+    activations changes both slices of the restatement, so a kernel that ran one network under the other's activation fails one
+    of the two cases."""
+    spec, params = seeded_policy((32, 16), activation, (48,), seed=19, value_activation=value_activation)
+    relu_relu = P.check_spec((32, 16), "relu", (48,), "relu")
+    value_coef = 0.5
+    a_end = 10 + sum(o * i + o for o, i in P.layer_shapes(spec)[0])
+    obs, labels, alive, targets = _batch(130, 33)
+    f = _Fit(spec, params, lr=0.0, beta1=0.0, weight_decay=0.0, value_coef=value_coef)
+    dl = f.accumulate(obs, labels, alive, targets)
+    row = f.fit.stats()
+    f.fit.step()
+    st = f.fit.state()
+    m = st["m"]
+    calls = [(obs, labels, alive, targets, dl)]
+    want, count = _reference_moment(spec, params, calls, value_coef)
+    plain, _ = _reference_moment(relu_relu, params, calls, value_coef)
+    swapped, _ = _reference_moment(P.check_spec((32, 16), value_activation, (48,), activation), params, calls, value_coef)
+    assert row["count"] == count == 126 and st["steps"] == 1 and not m[:10].any() and 10 < a_end < m.size
+    for lo, hi in ((10, a_end), (a_end, m.size)):
+        assert np.count_nonzero(want[lo:hi]) > (hi - lo) // 10 and not _same(want[lo:hi], swapped[lo:hi])
+    if activation == "relu":
+        assert _same(m[10:a_end], want[10:a_end])
+        assert np.isfinite(m[a_end:]).all() and np.count_nonzero(m[a_end:]) > (m.size - a_end) // 10
+        assert not _same(m[a_end:], plain[a_end:])
+    else:
+        assert _same(m[a_end:], want[a_end:])
+        assert _same(np.float64(row["value_loss_sum"]), np.float64(P.fit_stats_ref(spec, params, obs, labels, alive, targets)[1]))
+        G64, bound = backward_bound(spec, params, obs, dl)
+        G64, bound = G64.sum(axis=0)[10:a_end], bound.sum(axis=0)[10:a_end]
+        # (m * count is A up to the division's and the product's rounding: 2**-52 of |A| covers both)
+        err, tol = np.abs(m[10:a_end] * count - G64), bound * (1.0 + 2.0 ** -20) + 2.0 ** -52 * np.abs(G64)
+        print("tanh (32, 16) over a relu value network: max |A - fp64| %.3e, max bound %.3e, max ratio %.3f"
+              % (err.max(), tol.max(), (err / np.maximum(tol, 1e-300)).max()))
+        assert (err <= tol).all()
+    assert _same(st["theta"], params.astype(np.float64))             # lr = 0: nothing moved
     f.close()
 
 
