@@ -476,7 +476,8 @@ typedef TriLds __attribute__((address_space(3))) * TriP;
 // (gravity reads r only), so they meet through this block at barriers alone: the loaded (r, v) on launches with an FSW tick (the
 // chain's navigation input: the translational wave overwrites the rows early), and - on every launch - the three values the
 // epilogue needs of the rotational result.  The rotational wave is the late one: the translational wave, long done with r and v,
-// has the epilogue's arguments, addresses and counter arithmetic ready when those three arrive.
+// has the epilogue's arguments, addresses and counter arithmetic ready when those three arrive.  None of the three reads the
+// step's attitude: the rotational wave integrates it behind the hand-over (rk4_rot_omega / rk4_rot_sigma).
 struct HalvesLds {
     double rv[6][64];                         // translational -> rotational: the loaded r, v (launches with an FSW tick only)
     double hand[3][64];                       // rotational -> translational: |omega|^2, sum Omega_k^2, |sigma_BR| (held or fresh)
@@ -1559,6 +1560,85 @@ __device__ __forceinline__ void rk4_step(const HotCfg<NRW, DIAG>& c, const WV& w
         if (q2_out) s2 = dot(x.s, x.s);
     }
     if (q2_out) *q2_out = s2;        // |sigma|^2 of the step's attitude, for whoever rotates with it next (EnvTask)
+}
+
+// ---- halves form (SPLIT == 6): rk4_step<..., PART_ROT> in two parts.  At the bare level the attitude is a passenger of the step:
+// w' = Di (rhs0 - w x (Dm w + c_i)) does not read sigma, the wheels follow w, and sigma' reads sigma and the stage's w only.  What the
+// other wave waits for (HalvesLds::hand) needs w and the wheel speeds, so the rotational wave integrates those first, keeps the four
+// stage rates, and integrates sigma from them behind the hand-over.  Each value is produced by the operations of rk4_step on the
+// same operands in its order per value (the eom phases of the three-wave form: 2 = w' only, 1 = sigma' only); only WHEN differs.
+struct RotKept {
+    V3 w[4];       // the angular velocity each stage was evaluated at (w[0]: the loaded one)
+};
+// w and the wheels: x.w, x.Om are the step's; x.s stays the loaded attitude until rk4_rot_sigma
+template <int GRAV, int NRW, bool DIAG, int FEAT, int SPLIT, class WV>
+__device__ __forceinline__ void rk4_rot_omega(const HotCfg<NRW, DIAG>& c, const WV& wv, State<NRW>& x, const double* u, V3 lext,
+                                              double t0, const Env& ev, RotKept& kept) {
+    static_assert(!is_full<FEAT>() && FEAT != FEAT_LDSS && NRW > 0, "the halves of a step exist where nothing couples them");
+#define BSK_EOM_W(Z, TS, DE) eom<GRAV, NRW, DIAG, FEAT, SPLIT, false, 0, PART_ROT, 2>(c, Z, rhs0, a3, TS, ev, DE, k)
+    Core y, k, yt, acc;
+    y.w = x.w;
+    y.p = mv3<DIAG>(c.W, y.w);
+    V3 T = mk(0, 0, 0);
+    double tqj[NRW], tq[NRW];
+#pragma unroll
+    for (int i = 0; i < NRW; ++i) {
+        const double fs = fmin(fmax(x.Om[i] * 0x1p1000, -c.fc), c.fc);      // (rk4_step: Coulomb friction)
+        tq[i] = u[i] - fs;
+    }
+    wv.head(tq, x.Om, T, y.p, tqj);
+    const V3 rhs0 = lext - T;
+    const V3 c2 = axpy(c.h2, T, y.p), c4 = axpy(c.h, T, y.p);
+    const V3 a3 = mk(0, 0, 0);
+    BSK_EOM_W(y, t0, 0);
+    acc.w = axpy(c.h6, k.w, y.w);
+    yt.w = axpy(c.h2, k.w, y.w);
+    yt.p = c2;
+    kept.w[1] = yt.w;
+    BSK_EOM_W(yt, t0 + c.h2, 1);
+    acc.w = axpy(c.h3, k.w, acc.w);
+    yt.w = axpy(c.h2, k.w, y.w);
+    kept.w[2] = yt.w;
+    BSK_EOM_W(yt, t0 + c.h2, 1);
+    acc.w = axpy(c.h3, k.w, acc.w);
+    yt.w = axpy(c.h, k.w, y.w);
+    yt.p = c4;
+    kept.w[3] = yt.w;
+    BSK_EOM_W(yt, t0 + c.h, 2);
+    yt.w = axpy(c.h6, k.w, acc.w);
+#undef BSK_EOM_W
+    const V3 dw = yt.w - y.w;
+    double base[NRW];
+    wv.bases(c.h, tq, tqj, x.Om, base);
+    wv.tail(dw, base, x.Om);
+    kept.w[0] = y.w;
+    x.w = yt.w;
+}
+// sigma, from the loaded attitude (x.s on entry) and the stage rates: x.s is the step's, switched to the inner MRP set where needed
+template <int GRAV, int NRW, bool DIAG, int FEAT, int SPLIT>
+__device__ __forceinline__ void rk4_rot_sigma(const HotCfg<NRW, DIAG>& c, const RotKept& kept, State<NRW>& x) {
+    const Env ev{};
+    const V3 none = mk(0, 0, 0);
+#define BSK_EOM_S(Z) eom<GRAV, NRW, DIAG, FEAT, SPLIT, false, 0, PART_ROT, 1>(c, Z, none, none, 0.0, ev, 0, k)
+    Core y, k, yt, acc;
+    y.s = x.s; y.w = kept.w[0];
+    BSK_EOM_S(y);
+    acc.s = axpy(c.h6, k.s, y.s);
+    yt.s = axpy(c.h2, k.s, y.s);
+    yt.w = kept.w[1];
+    BSK_EOM_S(yt);
+    acc.s = axpy(c.h3, k.s, acc.s);
+    yt.s = axpy(c.h2, k.s, y.s);
+    yt.w = kept.w[2];
+    BSK_EOM_S(yt);
+    acc.s = axpy(c.h3, k.s, acc.s);
+    yt.s = axpy(c.h, k.s, y.s);
+    yt.w = kept.w[3];
+    BSK_EOM_S(yt);
+    x.s = axpy(c.h6, k.s, acc.s);
+#undef BSK_EOM_S
+    const double s2 = dot(x.s, x.s);
+    if (BSK_UNLIKELY(s2 > 1.0)) x.s = (-rcp_nr(s2)) * x.s;
 }
 
 // ---- three-wave form (SPLIT == 3): the RK4 step of one half of the spacecraft (exchange protocol: TriX).

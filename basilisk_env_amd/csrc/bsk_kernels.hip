@@ -106,6 +106,7 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
     const HotCfg<NRW, DIAG>& c = a.hot;
     const ColdCfg* __restrict__ cold = a.cold;
     const probe::Stamp t_kernel = probe::stamp<probe::PAIR_TIME>();
+    const probe::Stamp halves_t0 = probe::stamp<probe::HALVES_ROLE == 1>();    // (halves form: the rotational wave's start)
     // SPLIT == 5: waves 0/1 of the workgroup carry spacecraft group 0 (halves 0/1 of the walk), waves 2/3 group 1
     // SPLIT == 2 (pair form, bsk_device.hpp: PairLds): a 128-thread workgroup = the dynamics wave and the FSW + environment
     // wave of the SAME 64 spacecraft
@@ -176,7 +177,9 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
             // (left to the compiler all of this sinks behind the barrier, to where it is used: the empty asm holds it in front)
             asm volatile("" ::"v"(r2_t), "v"(packed), "v"(o3), "v"(steps0), "s"(ob1), "s"(ob2), "s"(ob3), "s"(ob4));
             // ... then, behind the form's last barrier, the three values that do: |omega|^2, sum Omega_k^2, |sigma_BR|
+            const probe::Stamp role_b0 = probe::stamp<probe::HALVES_ROLE == 2>();
             __syncthreads();
+            const probe::Stamp role_b1 = probe::stamp<probe::HALVES_ROLE == 2>();
             const double o0 = HL->hand[2][hl];
             const double o1 = sqrt_nr(HL->hand[0][hl]);
             const double o2 = sqrt_nr(HL->hand[1][hl]) * ta.obs_cfg.inv_wheel_limit;
@@ -214,11 +217,15 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
                 const double ws = wave_sum(valid ? rew : 0.0);
                 if (hl == 0) ta.wave_sum[gid >> 6] = ws;
             }
+            if constexpr (probe::HALVES_ROLE == 2) {     // probe builds: cycles at the barrier | from the barrier to here
+                if (hl == 0 && ta.dbg) ta.dbg[gid >> 6] = probe::pack2(role_b1 - role_b0, probe::elapsed(role_b1));
+            }
             return;
         }
     }
     // every load of the launch is issued here, before any use
     State<NRW> x;
+    RotKept rot_kept;             // (halves form only: what the step's attitude is integrated from, behind the hand-over)
     if constexpr (HALVES) {       // (the other wave's; the loaded values arrive through LDS on launches with an FSW tick)
         x.r = mk(0, 0, 0); x.v = mk(0, 0, 0);
     } else {
@@ -961,7 +968,9 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
                 thr_masks(ev);
             }
             if constexpr (FULL) rk4_step<GRAV, NRW, DIAG, FEAT, SPLIT, THR, DM>(c, wv, x, u, lext, (double)tick * c.h, ev, accp, &pre, &q2);
-            else rk4_step<GRAV, NRW, DIAG, FEAT, SPLIT, false, 0, HALVES ? PART_ROT : PART_ALL>(c, wv, x, u, lext, (double)tick * c.h, ev, accp);
+            // (halves form: the launch's one step; omega and the wheels here, sigma behind the hand-over - the block behind the loop)
+            else if constexpr (HALVES) rk4_rot_omega<GRAV, NRW, DIAG, FEAT, SPLIT>(c, wv, x, u, lext, (double)tick * c.h, ev, rot_kept);
+            else rk4_step<GRAV, NRW, DIAG, FEAT, SPLIT, false, 0, PART_ALL>(c, wv, x, u, lext, (double)tick * c.h, ev, accp);
             if constexpr (POWER) power_tick<FULL>(FULL ? a.power : pc_loop_cfg, sg, x.r, x.s, L, np + t, lane, kt.c, FULL ? &pre : nullptr, FULL ? &q2 : nullptr);
             ++t;
             ++tick;
@@ -985,6 +994,13 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
         };
         burst_any = burst_pending();
         probe::since<probe::CHUNK == 1>(dbg_chain, pc_head);
+        if constexpr (HALVES) {
+            // The kept stage rates are the launch's ONE step's (choose_form: substeps == 1), and that step is in the loop's last
+            // trip: whatever they held before a trip's ticks is never read.  Said to the compiler with an empty asm that defines them
+            // - left unsaid they are live around the loop and across the FSW chain at its head, 24 registers the chain does not have.
+            asm volatile("" : "=v"(rot_kept.w[0].x), "=v"(rot_kept.w[0].y), "=v"(rot_kept.w[0].z), "=v"(rot_kept.w[1].x), "=v"(rot_kept.w[1].y), "=v"(rot_kept.w[1].z));
+            asm volatile("" : "=v"(rot_kept.w[2].x), "=v"(rot_kept.w[2].y), "=v"(rot_kept.w[2].z), "=v"(rot_kept.w[3].x), "=v"(rot_kept.w[3].y), "=v"(rot_kept.w[3].z));
+        }
         const probe::Stamp pc_first = probe::stamp<probe::CHUNK == 2>();
         // The chunk's first tick runs alone when an FSW tick opened the chunk under the reference's task priorities: after it
         // the dynamics task's effectors latch the new commands (idempotent moves, a no-op for lanes without a new message).
@@ -1065,6 +1081,8 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
         // ---- rotational wave: the epilogue runs in the translational wave, which has been waiting for exactly these three values
         // (the operands of obs[1], obs[2] and obs[0] as the single-wave form forms them: same operations, same order).  |sigma_BR|
         // travels on every launch - held or fresh, the t = 0 chain's included - so no launch needs a decision about it.
+        // None of the three reads the step's attitude, so this wave arrives here with omega and the wheels integrated and sigma
+        // not yet (rk4_rot_omega in the tick loop): the attitude's four stages run behind the barrier, below.
         const HalvesP HL = (HalvesP)lds_dyn;
         HL->hand[0][lane] = dot(x.w, x.w);
         double om2 = 0.0;
@@ -1075,11 +1093,10 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
         if constexpr (probe::CHUNK != 0) {      // (the word of the single-wave form's probe, below)
             if (lane == 0) HL->dbg = ((dbg_chain >> 4) & 0xFFFFFFFFull) | (((dbg_waitA >> 4) & 0xFFFFFFFFull) << 32);
         }
+        const probe::Stamp role_hand = probe::stamp<probe::HALVES_ROLE == 1>();
         __syncthreads();
         // ... and this wave stores its own rows and ends, with what it has held since its loads: a.st, a.stride, a.fsw_lag
         const gptr<double> so = uniform_ptr(const_cast<double*>(st));
-        stf(so + (int64_t)(BSK_F_SIGMA + 0) * S, bo, x.s.x); stf(so + (int64_t)(BSK_F_SIGMA + 1) * S, bo, x.s.y);
-        stf(so + (int64_t)(BSK_F_SIGMA + 2) * S, bo, x.s.z);
         stf(so + (int64_t)(BSK_F_OMEGA + 0) * S, bo, x.w.x); stf(so + (int64_t)(BSK_F_OMEGA + 1) * S, bo, x.w.y);
         stf(so + (int64_t)(BSK_F_OMEGA + 2) * S, bo, x.w.z);
 #pragma unroll
@@ -1092,6 +1109,18 @@ __global__ __launch_bounds__(256, (SPLIT == 5 || SPLIT == 4 || SPLIT == 2 || SPL
                 for (int k = 0; k < NRW; ++k) stf(so + (int64_t)(TAIL + BSK_T_UPEND + k) * S, bo, up[k]);
             }
             stf(so + (int64_t)(TAIL + BSK_T_SBR) * S, bo, sbr);
+        }
+        // The step's attitude: nothing between the step and these stores reads it (the FSW chain at the launch's head read the
+        // loaded one), so its four stages run here, beside the other wave's epilogue and this wave's stores in flight.  The kept
+        // values pass through an empty asm: left alone the compiler schedules the sigma chain back in front of the hand-over.
+        asm volatile("" : "+v"(x.s.x), "+v"(x.s.y), "+v"(x.s.z), "+v"(rot_kept.w[0].x), "+v"(rot_kept.w[0].y), "+v"(rot_kept.w[0].z));
+        asm volatile("" : "+v"(rot_kept.w[1].x), "+v"(rot_kept.w[1].y), "+v"(rot_kept.w[1].z), "+v"(rot_kept.w[2].x), "+v"(rot_kept.w[2].y), "+v"(rot_kept.w[2].z),
+                          "+v"(rot_kept.w[3].x), "+v"(rot_kept.w[3].y), "+v"(rot_kept.w[3].z));
+        rk4_rot_sigma<GRAV, NRW, DIAG, FEAT, SPLIT>(c, rot_kept, x);
+        stf(so + (int64_t)(BSK_F_SIGMA + 0) * S, bo, x.s.x); stf(so + (int64_t)(BSK_F_SIGMA + 1) * S, bo, x.s.y);
+        stf(so + (int64_t)(BSK_F_SIGMA + 2) * S, bo, x.s.z);
+        if constexpr (probe::HALVES_ROLE == 1) {     // probe builds: cycles from the wave's start to the hand-over | from there to here
+            if (lane == 0 && a.tail.dbg) a.tail.dbg[blockIdx.x] = probe::pack2(role_hand - halves_t0, probe::elapsed(role_hand));
         }
         return;
     }

@@ -14,6 +14,10 @@
 //     BSK_PROBE_TRI_ROLE=1|2|3  three-wave form, ONE role per library (1 rotational, 2 FSW + environment, 3 translational wave): cycles in
 //                             its tick loop, cycles of them at the workgroup barriers, cycles re-reading the exchange (dynamics halves) or
 //                             in the FSW chain (environment wave); the workgroup's word of the debug buffer (tools/tri_roles.py)
+//     BSK_PROBE_HALVES_ROLE=1|2  halves form, ONE role per library.  1, rotational wave: cycles from the wave's start to the hand-over (its
+//                             arrival at the form's last barrier) and from there to its last instruction.  2, translational wave: cycles
+//                             waiting at that barrier and from the barrier to its last instruction.  Each wave writes its workgroup's word
+//                             of the debug buffer itself, as its last instruction (tools/halves_roles.py)
 //     BSK_PROBE_TRI_NOPUBLISH fault injection: the translational wave never publishes, so that its partner's poll times out
 //                             (tests/test_gpu_tri.py: the handle's error word -> BSK_EHIP)
 // A probe writes ONE 64-bit word per wave into the handle's debug buffer (bsk_debug_words), never into a result buffer.
@@ -23,7 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #if !defined(BSK_PROBES) || !BSK_PROBES
-#if defined(BSK_PROBE_PAIR_WAIT) || defined(BSK_PROBE_PAIR_TIME) || defined(BSK_PROBE_PAIR_HWID) || defined(BSK_PROBE_TRI_XCHG) || defined(BSK_PROBE_TRI_NOPUBLISH) || defined(BSK_PROBE_CHUNK) || defined(BSK_PROBE_TRI_ROLE)
+#if defined(BSK_PROBE_PAIR_WAIT) || defined(BSK_PROBE_PAIR_TIME) || defined(BSK_PROBE_PAIR_HWID) || defined(BSK_PROBE_TRI_XCHG) || defined(BSK_PROBE_TRI_NOPUBLISH) || defined(BSK_PROBE_CHUNK) || defined(BSK_PROBE_TRI_ROLE) || defined(BSK_PROBE_HALVES_ROLE)
 #error "a BSK_PROBE_* selector without -DBSK_PROBES=1: probes never ride along in a product build"
 #endif
 #endif
@@ -70,17 +74,26 @@ static_assert(TRI_ROLE_WAVE >= 0 && TRI_ROLE_WAVE <= 2, "BSK_PROBE_TRI_ROLE=1|2|
 constexpr bool TRI_ROLE = false;
 constexpr int TRI_ROLE_WAVE = -1;
 #endif
+#ifdef BSK_PROBE_HALVES_ROLE
+constexpr int HALVES_ROLE = BSK_PROBE_HALVES_ROLE;          // the wave whose word is kept: 1 rotational, 2 translational
+static_assert(HALVES_ROLE == 1 || HALVES_ROLE == 2, "BSK_PROBE_HALVES_ROLE=1|2");
+#else
+constexpr int HALVES_ROLE = 0;
+#endif
 #else
 constexpr bool PAIR_WAIT = false, PAIR_TIME = false, PAIR_HWID = false, TRI_NOPUBLISH = false, TRI_ROLE = false;
-constexpr int TRI_XCHG = 0, CHUNK = 0, TRI_ROLE_WAVE = -1;
+constexpr int TRI_XCHG = 0, CHUNK = 0, TRI_ROLE_WAVE = -1, HALVES_ROLE = 0;
 #endif
-constexpr bool ANY = PAIR_WAIT || PAIR_TIME || PAIR_HWID || TRI_XCHG != 0 || CHUNK != 0 || TRI_ROLE;     // probes that emit a word per wave
+constexpr bool ANY = PAIR_WAIT || PAIR_TIME || PAIR_HWID || TRI_XCHG != 0 || CHUNK != 0 || TRI_ROLE || HALVES_ROLE != 0;     // probes that emit a word per wave
 constexpr bool XCH_STATS = TRI_XCHG != 0 || TRI_ROLE;      // the exchange keeps its miss / re-read / cycle counts
-static_assert((int)PAIR_WAIT + (int)PAIR_TIME + (int)PAIR_HWID + (int)(TRI_XCHG != 0) + (int)TRI_NOPUBLISH + (int)(CHUNK != 0) + (int)TRI_ROLE <= 1, "one probe per library");
+static_assert((int)PAIR_WAIT + (int)PAIR_TIME + (int)PAIR_HWID + (int)(TRI_XCHG != 0) + (int)TRI_NOPUBLISH + (int)(CHUNK != 0) + (int)TRI_ROLE + (int)(HALVES_ROLE != 0) <= 1, "one probe per library");
 // three 20-bit fields of cycles / 64
 __device__ __forceinline__ unsigned long long pack3(unsigned long long a, unsigned long long b, unsigned long long c) {
     return ((a >> 6) & 0xFFFFFull) | (((b >> 6) & 0xFFFFFull) << 20) | (((c >> 6) & 0xFFFFFull) << 40);
 }
+
+// two 32-bit fields of cycles
+__device__ __forceinline__ unsigned long long pack2(unsigned long long a, unsigned long long b) { return (a & 0xFFFFFFFFull) | ((b & 0xFFFFFFFFull) << 32); }
 
 typedef unsigned long long Stamp;
 // the cycle counter when probe ON is built in, 0 (and no instruction) otherwise
