@@ -83,9 +83,9 @@ EXPORTS = [
     "bsk_default_config", "bsk_create", "bsk_destroy", "bsk_set_gravity_sh", "bsk_reset", "bsk_step",
     "bsk_step_device", "bsk_step_device_i64", "bsk_step_n", "bsk_get_episode_device", "bsk_get_batch_stats_device", "bsk_set_step_stats", "bsk_set_halves_form", "bsk_reset_from_pool_device", "bsk_debug_counters", "bsk_debug_words", "bsk_get_obs", "bsk_get_obs_rowmajor", "bsk_get_obs_device", "bsk_get_obs_state", "bsk_get_stream", "bsk_get_terminal_obs_device", "bsk_get_state_device", "bsk_get_batch_stats", "bsk_n_fields",
     "bsk_get_state", "bsk_set_state", "bsk_get_counters", "bsk_set_counters", "bsk_set_ic_pool", "bsk_sample_ic_pool", "bsk_reset_from_pool", "bsk_reset_from_pool_shared", "bsk_get_ic_pool", "bsk_get_terminal_obs", "bsk_set_env_base", "bsk_set_sim_time", "bsk_sync",
-    "bsk_fork_device", "bsk_fork", "bsk_select_branches", "bsk_beam_select",
+    "bsk_fork_device", "bsk_fork", "bsk_select_branches", "bsk_beam_select", "bsk_select_branches_boot", "bsk_beam_select_boot",
     "bsk_policy_n_params", "bsk_policy_create", "bsk_policy_set_params", "bsk_policy_destroy", "bsk_policy_set_rng", "bsk_policy_get_rng",
-    "bsk_policy_act", "bsk_policy_rollout",
+    "bsk_policy_act", "bsk_policy_value", "bsk_policy_rollout",
     "bsk_population_create", "bsk_population_destroy", "bsk_population_set_rng", "bsk_population_get_rng", "bsk_population_set_params",
     "bsk_population_set_params_device", "bsk_population_get_member", "bsk_population_act", "bsk_population_rollout",
     "bsk_population_set_outcomes", "bsk_es_set_outcome_log", "bsk_es_get_outcome_log",
@@ -131,9 +131,12 @@ def _signatures():
         "bsk_fork_device": ([vp, vp, vp], rc), "bsk_fork": ([vp, vp, vp], rc),
         "bsk_select_branches": ([vp, vp, vp, i, i, i, f64, vp, vp, vp, vp], rc),
         "bsk_beam_select": ([vp, vp, i, i, i, f64, vp, vp, vp, vp, vp, vp], rc),
+        "bsk_select_branches_boot": ([vp, vp, vp, i, i, i, f64, vp, vp, vp, vp, vp], rc),
+        "bsk_beam_select_boot": ([vp, vp, i, i, i, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp], rc),
         "bsk_policy_n_params": ([spec], rc), "bsk_policy_create": ([spec, vp, i, P(vp)], rc), "bsk_policy_set_params": ([vp, vp], rc),
         "bsk_policy_destroy": ([vp], None), "bsk_policy_set_rng": ([vp, u64, u64], rc), "bsk_policy_get_rng": ([vp, P(u64), P(u64)], rc),
         "bsk_policy_act": ([vp, vp, i64, i, i64, i, vp, vp, vp, vp, i64, vp], rc),
+        "bsk_policy_value": ([vp, vp, i64, i, vp, vp], rc),
         "bsk_policy_rollout": ([vp, vp, i, i, i, vp, vp, vp, vp, vp, vp], rc),
         "bsk_population_create": ([spec, i, vp, i, P(vp)], rc), "bsk_population_destroy": ([vp], None),
         "bsk_population_set_rng": ([vp, u64, u64], rc), "bsk_population_get_rng": ([vp, P(u64), P(u64)], rc),

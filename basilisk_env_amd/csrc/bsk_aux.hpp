@@ -76,12 +76,16 @@ struct ForkSide {
 // other than -1 (NULL: not raised).  seal_word: the destination's StatsSeal::word, whose seal the fork lifts (NULL: none).
 hipError_t launch_fork(const ForkSide& src, const ForkSide& dst, int nf, const int* map, bool identity, int* err,
                        unsigned long long* seal_word, hipStream_t s);
-// one action per group of `group` consecutive branches from their rollout histories (bsk_select_branches)
+// one action per group of `group` consecutive branches from their rollout histories (bsk_select_branches); with leaf (f32[n_branch])
+// the branches no step ended also take g * leaf[b] (bsk_select_branches_boot), with NULL the kernel without that term
 hipError_t launch_select(const double* reward_hist, const unsigned char* reason_hist, const int* first_action, int n_steps, int n_branch,
-                         int group, double gamma, double* values, double* best_value, int* best_action, hipStream_t s);
-// one level of a beam search: the `width` best of every root's 3 * width candidates (bsk_beam_select)
+                         int group, double gamma, const float* leaf, double* values, double* best_value, int* best_action, hipStream_t s);
+// one level of a beam search: the `width` best of every root's 3 * width candidates (bsk_beam_select); with leaf
+// (f32[3 * width * n_roots]) ranked by value + boot_weight * leaf[c] of the live candidates, the keys of the kept ones into key
+// (f64[n_roots * width] or NULL) (bsk_beam_select_boot), with NULL the kernel without that term
 hipError_t launch_beam(const double* reward, const unsigned char* reason, int n_roots, int width, int level, double weight,
-                       const bsk_beam_slot* in, bsk_beam_slot* out, int* map, double* best_value, int* best_action, hipStream_t s);
+                       double boot_weight, const float* leaf, const bsk_beam_slot* in, bsk_beam_slot* out, int* map, double* key,
+                       double* best_value, int* best_action, hipStream_t s);
 
 // first-level workgroups of stats_kernel at most = entries of the `done_part` scratch
 int stats_done_parts();

@@ -921,20 +921,38 @@ int bsk_fork(bsk_handle* dst, bsk_handle* src, const int32_t* map) {
     return BSK_OK;
 }
 
-int bsk_select_branches(const double* d_reward_hist, const uint8_t* d_reason_hist, const int32_t* d_first_action, int n_steps, int n_branch,
-                        int group, double gamma, double* d_values, double* d_best_value, int32_t* d_best_action, void* stream) {
+// what bsk_select_branches and bsk_select_branches_boot refuse alike, before any launch
+static int check_select(const double* d_reward_hist, const uint8_t* d_reason_hist, const int32_t* d_first_action, int n_steps, int n_branch,
+                        int group, const int32_t* d_best_action) {
     if (!d_reward_hist || !d_reason_hist || !d_first_action || !d_best_action)
         return fail(BSK_EINVAL, "reward_hist/reason_hist/first_action/best_action is NULL");
     if (n_steps < 1 || n_branch < 1 || group < 1) return fail(BSK_EINVAL, "n_steps, n_branch and group must be >= 1");
     if (n_branch % group != 0) return fail(BSK_EINVAL, "n_branch must be a multiple of group");
-    HIP_TRY(bsk::launch_select(d_reward_hist, d_reason_hist, d_first_action, n_steps, n_branch, group, gamma, d_values, d_best_value,
+    return BSK_OK;
+}
+
+int bsk_select_branches(const double* d_reward_hist, const uint8_t* d_reason_hist, const int32_t* d_first_action, int n_steps, int n_branch,
+                        int group, double gamma, double* d_values, double* d_best_value, int32_t* d_best_action, void* stream) {
+    if (int rc = check_select(d_reward_hist, d_reason_hist, d_first_action, n_steps, n_branch, group, d_best_action)) return rc;
+    HIP_TRY(bsk::launch_select(d_reward_hist, d_reason_hist, d_first_action, n_steps, n_branch, group, gamma, nullptr, d_values, d_best_value,
                                d_best_action, (hipStream_t)stream));
     return BSK_OK;
 }
 
-int bsk_beam_select(const double* d_reward, const uint8_t* d_reason, int n_roots, int width, int level, double weight,
-                    const bsk_beam_slot* d_in, bsk_beam_slot* d_out, int32_t* d_map, double* d_best_value, int32_t* d_best_action,
-                    void* stream) {
+int bsk_select_branches_boot(const double* d_reward_hist, const uint8_t* d_reason_hist, const int32_t* d_first_action, int n_steps,
+                             int n_branch, int group, double gamma, const float* d_leaf_value, double* d_values, double* d_best_value,
+                             int32_t* d_best_action, void* stream) {
+    if (int rc = check_select(d_reward_hist, d_reason_hist, d_first_action, n_steps, n_branch, group, d_best_action)) return rc;
+    if (!d_leaf_value) return fail(BSK_EINVAL, "leaf_value is NULL");
+    HIP_TRY(bsk::launch_select(d_reward_hist, d_reason_hist, d_first_action, n_steps, n_branch, group, gamma, d_leaf_value, d_values,
+                               d_best_value, d_best_action, (hipStream_t)stream));
+    return BSK_OK;
+}
+
+// what bsk_beam_select and bsk_beam_select_boot refuse alike, before any launch
+static int check_beam(const double* d_reward, const uint8_t* d_reason, int n_roots, int width, int level, double weight,
+                      const bsk_beam_slot* d_in, const bsk_beam_slot* d_out, const int32_t* d_map, const double* d_best_value,
+                      const int32_t* d_best_action) {
     if (!d_reward || !d_reason || !d_out || !d_map || !d_best_value || !d_best_action || (!d_in && level != 0))
         return fail(BSK_EINVAL, "reward/reason/out/map/best_value/best_action is NULL, or in is NULL at a level above 0");
     if (width < 1 || width > BSK_BEAM_MAX_WIDTH) return fail(BSK_EINVAL, "width must be in 1..81");
@@ -942,8 +960,26 @@ int bsk_beam_select(const double* d_reward, const uint8_t* d_reason, int n_roots
     if ((int64_t)3 * width * n_roots >= ((int64_t)1 << 31)) return fail(BSK_EINVAL, "3 * width * n_roots candidates must stay below 2^31");
     if (!std::isfinite(weight)) return fail(BSK_EINVAL, "weight must be finite");
     if (d_in == d_out) return fail(BSK_EINVAL, "in and out must be distinct slot buffers");
-    HIP_TRY(bsk::launch_beam(d_reward, d_reason, n_roots, width, level, weight, d_in, d_out, d_map, d_best_value, d_best_action,
-                             (hipStream_t)stream));
+    return BSK_OK;
+}
+
+int bsk_beam_select(const double* d_reward, const uint8_t* d_reason, int n_roots, int width, int level, double weight,
+                    const bsk_beam_slot* d_in, bsk_beam_slot* d_out, int32_t* d_map, double* d_best_value, int32_t* d_best_action,
+                    void* stream) {
+    if (int rc = check_beam(d_reward, d_reason, n_roots, width, level, weight, d_in, d_out, d_map, d_best_value, d_best_action)) return rc;
+    HIP_TRY(bsk::launch_beam(d_reward, d_reason, n_roots, width, level, weight, 0.0, nullptr, d_in, d_out, d_map, nullptr, d_best_value,
+                             d_best_action, (hipStream_t)stream));
+    return BSK_OK;
+}
+
+int bsk_beam_select_boot(const double* d_reward, const uint8_t* d_reason, int n_roots, int width, int level, double weight,
+                         double boot_weight, const float* d_leaf_value, const bsk_beam_slot* d_in, bsk_beam_slot* d_out, int32_t* d_map,
+                         double* d_key, double* d_best_value, int32_t* d_best_action, void* stream) {
+    if (int rc = check_beam(d_reward, d_reason, n_roots, width, level, weight, d_in, d_out, d_map, d_best_value, d_best_action)) return rc;
+    if (!d_leaf_value) return fail(BSK_EINVAL, "leaf_value is NULL");
+    if (!std::isfinite(boot_weight)) return fail(BSK_EINVAL, "boot_weight must be finite");
+    HIP_TRY(bsk::launch_beam(d_reward, d_reason, n_roots, width, level, weight, boot_weight, d_leaf_value, d_in, d_out, d_map, d_key,
+                             d_best_value, d_best_action, (hipStream_t)stream));
     return BSK_OK;
 }
 int bsk_set_env_base(bsk_handle* h, int64_t env_base) {

@@ -230,6 +230,18 @@ int bsk_policy_act(bsk_policy* p, const double* d_obs, int64_t obs_stride, int n
     return launch_act(p, 0, d_obs, obs_stride, n, env_base, mode, d_action, d_logp, d_value, d_logits, out_stride, (hipStream_t)stream);
 }
 
+int bsk_policy_value(bsk_policy* p, const double* d_obs, int64_t obs_stride, int n, float* d_value, void* stream) {
+    if (!p || !d_obs || !d_value) return fail(BSK_EINVAL, "policy/d_obs/d_value is NULL");
+    if (n < 1 || n > (1 << 28)) return fail(BSK_EINVAL, "n must be in 1..2^28");
+    if (obs_stride < n) return fail(BSK_EINVAL, "obs_stride must be >= n");
+    if (p->lay.v.n_layers == 0) return fail(BSK_EINVAL, "bsk_policy_value: the policy has no value network");
+    DeviceGuard guard(p->device);
+    bsk::PolicyValueArgs a;
+    a.params = p->d_params; a.v = p->lay.v; a.obs = d_obs; a.obs_stride = obs_stride; a.n = n; a.value = d_value; a.width = p->lay.width;
+    HIP_TRY(bsk::launch_policy_value(a, (hipStream_t)stream));
+    return BSK_OK;
+}
+
 int bsk_policy_rollout(bsk_policy* p, bsk_handle* h, int mode, int substeps, int n_steps,
                        double* d_obs_hist, double* d_reward_hist, uint8_t* d_reason_hist,
                        int32_t* d_action_hist, float* d_logp_hist, float* d_value_hist) {

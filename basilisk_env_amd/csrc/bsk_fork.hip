@@ -2,8 +2,10 @@
 // bsk_aux.hip; neither touches the step or rollout kernels):
 //   fork_kernel     env j of one handle becomes an exact copy of env map[j] of another (or the same) handle: every buffer that
 //                   decides an env's future or reports its present (bsk_fork_device, include/bskgpu.h)
-//   select_kernel   discounted value of every branch of a rollout history, best branch per group of `group` (bsk_select_branches)
-//   beam_kernel     one level of a beam search: the `width` best of every root's 3 * width candidates (bsk_beam_select)
+//   select_kernel   discounted value of every branch of a rollout history, best branch per group of `group` (bsk_select_branches);
+//                   <true>: plus a discounted leaf value for the branches no step ended (bsk_select_branches_boot)
+//   beam_kernel     one level of a beam search: the `width` best of every root's 3 * width candidates (bsk_beam_select);
+//                   <true>: ranked by value + discounted leaf value of the live candidates (bsk_beam_select_boot)
 // Compiled with -ffp-contract=off (Makefile): select_kernel's and beam_kernel's additions and products are the ones a numpy
 // restatement makes.
 #include "bsk_device.hpp"
@@ -93,10 +95,14 @@ __device__ __forceinline__ bool beats(double a, int ia, double b, int ib) {
 // (that step's reward included), every operation rounded on its own - no contraction into FMAs - so that numpy's evaluation of the
 // same expression gives the same bits.  The lanes' best (value, index) pairs are joined by a butterfly under the total order of
 // beats(): any joining order gives the same winner.
+// BOOT (bsk_select_branches_boot): a branch that no step ended also takes  v = v + g * (double)leaf[b]  with the g the loop left
+// (T multiplications), product and sum each rounded on their own; a branch that ended - at the last step too - takes nothing.
+// One text serves both entry points: without BOOT `leaf` is not read and the instantiation is the kernel as it was.
+template <bool BOOT>
 __global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ rh, const unsigned char* __restrict__ qh,
                                                       const int* __restrict__ first_action, int T, int n_branch, int group, int n_groups,
-                                                      double gamma, double* __restrict__ values, double* __restrict__ best_value,
-                                                      int* __restrict__ best_action) {
+                                                      double gamma, const float* __restrict__ leaf, double* __restrict__ values,
+                                                      double* __restrict__ best_value, int* __restrict__ best_action) {
 #pragma clang fp contract(off)
     const int g = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));     // (wave-uniform)
     const int lane = (int)(threadIdx.x & 63u);
@@ -109,12 +115,19 @@ __global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ 
         if (i >= group) continue;
         const int64_t b = b0 + i;
         double v = 0.0, w = 1.0;
+        bool ended = false;
         for (int t = 0; t < T; ++t) {
             const int64_t at = (int64_t)t * n_branch + b;
             const double p = w * rh[at];
             v = v + p;
             w = w * gamma;
-            if (qh[at] != 0) break;
+            if (qh[at] != 0) { ended = true; break; }
+        }
+        if constexpr (BOOT) {
+            if (!ended) {
+                const double p = w * (double)leaf[b];
+                v = v + p;
+            }
         }
         if (values) values[b] = v;
         if (beats(v, i, bv, bi)) { bv = v; bi = i; }
@@ -131,11 +144,16 @@ __global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ 
     }
 }
 
+// leaf: f32[n_branch] (bsk_select_branches_boot), or NULL for the kernel without the leaf term (bsk_select_branches)
 hipError_t launch_select(const double* reward_hist, const unsigned char* reason_hist, const int* first_action, int n_steps, int n_branch,
-                         int group, double gamma, double* values, double* best_value, int* best_action, hipStream_t s) {
+                         int group, double gamma, const float* leaf, double* values, double* best_value, int* best_action, hipStream_t s) {
     const int n_groups = n_branch / group;
-    hipLaunchKernelGGL(select_kernel, dim3((n_groups + 3) / 4), dim3(256), 0, s, reward_hist, reason_hist, first_action, n_steps, n_branch,
-                       group, n_groups, gamma, values, best_value, best_action);
+    if (leaf)
+        hipLaunchKernelGGL(select_kernel<true>, dim3((n_groups + 3) / 4), dim3(256), 0, s, reward_hist, reason_hist, first_action, n_steps,
+                           n_branch, group, n_groups, gamma, leaf, values, best_value, best_action);
+    else
+        hipLaunchKernelGGL(select_kernel<false>, dim3((n_groups + 3) / 4), dim3(256), 0, s, reward_hist, reason_hist, first_action, n_steps,
+                           n_branch, group, n_groups, gamma, leaf, values, best_value, best_action);
     return hipGetLastError();
 }
 
@@ -144,12 +162,18 @@ hipError_t launch_select(const double* reward_hist, const unsigned char* reason_
 // from the parent slot, puts (value, valid) in LDS and counts the candidates of its root that come before it; the order is total,
 // so that count is its rank and no two candidates share one.  The threads of rank < width write their slot: plain stores, one
 // barrier, no atomics.  Nothing outside the 3 * width * n_roots candidates and the width * n_roots parent slots is read.
+// BOOT (bsk_beam_select_boot): the candidates are ranked by a key - value + boot_weight * (double)leaf[c] for a valid candidate that
+// is live after this step (product, then sum), the value itself otherwise - which takes the value's place in s_value; the slot keeps
+// the value v, so the next level continues the true return.  Without BOOT key and value are one and the instantiation is the kernel
+// as it was.
 constexpr int BEAM_BLOCK = 256;
+template <bool BOOT>
 __global__ __launch_bounds__(BEAM_BLOCK) void beam_kernel(const double* __restrict__ reward, const unsigned char* __restrict__ reason,
-                                                           int n_roots, int width, int level, double weight,
+                                                           int n_roots, int width, int level, double weight, double boot_weight,
+                                                           const float* __restrict__ leaf,
                                                            const bsk_beam_slot* __restrict__ in, bsk_beam_slot* __restrict__ out,
-                                                           int* __restrict__ map, double* __restrict__ best_value,
-                                                           int* __restrict__ best_action) {
+                                                           int* __restrict__ map, double* __restrict__ key_out,
+                                                           double* __restrict__ best_value, int* __restrict__ best_action) {
 #pragma clang fp contract(off)
     __shared__ double s_value[BEAM_BLOCK];
     __shared__ unsigned char s_valid[BEAM_BLOCK];
@@ -187,7 +211,14 @@ __global__ __launch_bounds__(BEAM_BLOCK) void beam_kernel(const double* __restri
         }
     }
     const bool ok = flags != 0u;
-    s_value[t] = v;
+    double key = v;                                            // what the candidate is ranked by (an invalid one: NaN)
+    if constexpr (BOOT) {
+        if ((flags & BSK_BEAM_LIVE) != 0u) {                   // (live implies valid; c < 3 * width * n_roots, the leaf's length)
+            const double p = boot_weight * (double)leaf[c];
+            key = v + p;
+        }
+    }
+    s_value[t] = key;
     s_valid[t] = ok ? 1 : 0;
     __syncthreads();
     if (!active) return;
@@ -195,7 +226,7 @@ __global__ __launch_bounds__(BEAM_BLOCK) void beam_kernel(const double* __restri
     int rank = 0;
     for (int j = 0; j < nc; ++j) {                             // candidates of this root that come before candidate i
         const bool okj = s_valid[base + j] != 0;
-        const bool before = okj != ok ? okj : (ok ? beats(s_value[base + j], j, v, i) : j < i);
+        const bool before = okj != ok ? okj : (ok ? beats(s_value[base + j], j, key, i) : j < i);
         rank += before ? 1 : 0;
     }
     if (rank < width) {
@@ -206,18 +237,28 @@ __global__ __launch_bounds__(BEAM_BLOCK) void beam_kernel(const double* __restri
         o.flags = flags;
         out[s] = o;
         map[s] = ok ? c : -1;
+        if constexpr (BOOT) {
+            if (key_out) key_out[s] = key;
+        }
         if (rank == 0) {
-            best_value[root] = v;
+            best_value[root] = key;
             best_action[root] = first;
         }
     }
 }
 
+// leaf: f32[3 * width * n_roots] with boot_weight and key (f64[n_roots * width] or NULL) (bsk_beam_select_boot), or NULL for the
+// kernel without the leaf term (bsk_beam_select)
 hipError_t launch_beam(const double* reward, const unsigned char* reason, int n_roots, int width, int level, double weight,
-                       const bsk_beam_slot* in, bsk_beam_slot* out, int* map, double* best_value, int* best_action, hipStream_t s) {
+                       double boot_weight, const float* leaf, const bsk_beam_slot* in, bsk_beam_slot* out, int* map, double* key,
+                       double* best_value, int* best_action, hipStream_t s) {
     const int per = BEAM_BLOCK / (3 * width);
-    hipLaunchKernelGGL(beam_kernel, dim3((n_roots + per - 1) / per), dim3(BEAM_BLOCK), 0, s, reward, reason, n_roots, width, level, weight,
-                       in, out, map, best_value, best_action);
+    if (leaf)
+        hipLaunchKernelGGL(beam_kernel<true>, dim3((n_roots + per - 1) / per), dim3(BEAM_BLOCK), 0, s, reward, reason, n_roots, width, level,
+                           weight, boot_weight, leaf, in, out, map, key, best_value, best_action);
+    else
+        hipLaunchKernelGGL(beam_kernel<false>, dim3((n_roots + per - 1) / per), dim3(BEAM_BLOCK), 0, s, reward, reason, n_roots, width, level,
+                           weight, boot_weight, leaf, in, out, map, key, best_value, best_action);
     return hipGetLastError();
 }
 

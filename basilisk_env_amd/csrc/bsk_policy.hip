@@ -2,7 +2,9 @@
 // step nor the rollout kernels):
 //   policy_kernel           action network (5 -> hidden... -> 3 logits) and optional value network (5 -> hidden... -> 1) for n
 //                           spacecraft in one launch: greedy or sampled action, log-probability, value, logits (bsk_policy_act)
-//   policy_population_kernel  the same for a population: every envs_per_member spacecraft under a parameter block of their own
+//   policy_value_kernel     the value network alone for n spacecraft: no action network, no draw counter, no action row
+//                           (bsk_policy_value); it shares every device function with policy_kernel
+//   policy_population_kernel  policy_kernel for a population: every envs_per_member spacecraft under a parameter block of their own
 //                           (bsk_population_act); it shares every device function with policy_kernel
 //   policy_pack_kernel      C-ABI parameter blocks in device memory -> the device layout (bsk_population_set_params_device)
 //   policy_advance_kernel   the policy's draw counter += 1, behind a sample-mode launch
@@ -85,6 +87,27 @@ __global__ __launch_bounds__(POLICY_BLOCK) void policy_kernel(const PolicyArgs p
     policy_eval(p, p.params, policy_lds);
 }
 
+// The value network alone (bsk_policy_value): policy_eval's geometry - one lane per spacecraft, POLICY_WAVES waves per 64 columns,
+// activations through the LDS columns [unit][lane], the block address workgroup-uniform so that the weight loads stay scalar - and
+// its device functions, so the value is the one policy_kernel writes, bit for bit.  No action network is walked, the draw counter
+// is not read and no action row is written: nothing of the policy's single-stream state is touched.
+__global__ __launch_bounds__(POLICY_BLOCK) void policy_value_kernel(const PolicyValueArgs p) {
+    extern __shared__ float policy_lds[];
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));       // (wave-uniform: weight addresses stay scalar)
+    const int64_t j = (int64_t)blockIdx.x * POLICY_LANES + lane;
+    const bool live = j < p.n;
+    float x[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {                          // (step 1 of the definition, as policy_eval writes it)
+        const double o = live && wave == 0 ? p.obs[(int64_t)i * p.obs_stride + j] : 0.0;       // (tail lanes read nothing)
+        x[i] = __builtin_fmaf((float)o, p.params[i], p.params[5 + i]);
+    }
+    float val[POLICY_OB] = {0.0f, 0.0f, 0.0f, 0.0f};
+    policy_net(p.params, p.v, x, policy_lds, policy_lds + p.width * POLICY_LANES, lane, wave, val);
+    if (wave == 0 && live) p.value[j] = val[0];            // (tail lanes write nothing)
+}
+
 // The population form (bsk_population_act): workgroup b serves the same 64 spacecraft and takes the parameter block of member
 // b / wg_per_member, wg_per_member = envs_per_member / 64.  The block address depends on blockIdx alone, so it is as scalar as
 // p.params is above and policy_hidden's weight loads stay one scalar load of 16 consecutive floats: nothing else differs.
@@ -110,6 +133,12 @@ __global__ void policy_advance_kernel(unsigned long long* rng) { rng[1] += 1ull;
 hipError_t launch_policy(const PolicyArgs& args, hipStream_t s) {
     const size_t lds = (size_t)2 * args.width * POLICY_LANES * sizeof(float);
     hipLaunchKernelGGL(policy_kernel, dim3((unsigned)((args.n + POLICY_LANES - 1) / POLICY_LANES)), dim3(POLICY_BLOCK), lds, s, args);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_value(const PolicyValueArgs& args, hipStream_t s) {
+    const size_t lds = (size_t)2 * args.width * POLICY_LANES * sizeof(float);
+    hipLaunchKernelGGL(policy_value_kernel, dim3((unsigned)((args.n + POLICY_LANES - 1) / POLICY_LANES)), dim3(POLICY_BLOCK), lds, s, args);
     return hipGetLastError();
 }
 

@@ -41,6 +41,17 @@ struct PolicyArgs {
     int width;                     // LDS floats per lane and buffer: the widest layer input (>= 5)
 };
 
+// what policy_value_kernel takes: the value network alone (bsk_policy_value)
+struct PolicyValueArgs {
+    const float* params;           // device layout (PolicyLayout)
+    PolicyNet v;                   // n_layers >= 1
+    const double* obs;             // [5][obs_stride]
+    int64_t obs_stride;
+    int n;
+    float* value;                  // [n]
+    int width;                     // the layout's width (both networks'), as PolicyArgs::width
+};
+
 // Host side of the layout: checks a spec, counts its C-ABI parameters, and repacks them for the device.
 struct PolicyLayout {
     PolicyNet a, v;
@@ -139,6 +150,8 @@ __device__ __forceinline__ bool policy_beats(float a, float b) {      // a (the 
 }
 
 hipError_t launch_policy(const PolicyArgs& args, hipStream_t s);
+// the value network alone, policy_kernel's value bit for bit: reads the parameters and the observations, writes value[0 .. n)
+hipError_t launch_policy_value(const PolicyValueArgs& args, hipStream_t s);
 // The population form: args.params holds one device block of n_device floats per member, spacecraft j runs member
 // j / envs_per_member; envs_per_member is a multiple of 64 and args.n a multiple of envs_per_member.
 hipError_t launch_policy_population(const PolicyArgs& args, int envs_per_member, int n_device, hipStream_t s);

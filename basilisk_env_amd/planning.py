@@ -10,6 +10,12 @@ captured into one HIP graph.  An extra beside the reference surface (INTEGRATION
 ``BeamPlanner`` looks further ahead than 3**depth branches allow: per root it keeps the ``width`` best action sequences, and every
 level forks them into their 3 children (``bsk_fork_device``), steps the children once (``bsk_step_device``), keeps the ``width``
 best children (``bsk_beam_select``) and forks them back, so its cost grows linearly with the ``horizon``.
+
+Both cut every sequence off at their horizon and score the rest of the episode as zero - unless they are given a ``value_policy``,
+a ``DevicePolicy`` with a value network: one more launch (``bsk_policy_value``) then evaluates it on the observations the sequences
+end in, and the choice adds its discounted estimate to every sequence whose episode has not ended (``bsk_select_branches_boot``,
+``bsk_beam_select_boot``): n-step lookahead with a learned value at the leaf.  ``distill(..., value_targets=True)`` on such a planner
+fits the value network to n-step targets formed through the planner's own max, which makes distillation an iteration.
 """
 import ctypes as C
 
@@ -69,6 +75,23 @@ def branch_values(reward_hist, reason_hist, gamma):
         g = g * gamma
         live &= q[t] == 0
     return v
+
+
+def branch_values_boot(reward_hist, reason_hist, gamma, leaf):
+    """numpy restatement of bsk_select_branches_boot's branch value (include/bskgpu.h), same operations in the same order:
+    ``branch_values``' loop, then v = v + g * leaf for the branches no step ended (g after ``n_steps`` multiplications; product,
+    then sum); a branch that ended - at the last step too - keeps its value."""
+    r = np.asarray(reward_hist, dtype=np.float64)
+    q = np.asarray(reason_hist)
+    v = np.zeros(r.shape[1])
+    g = np.ones(r.shape[1])
+    live = np.ones(r.shape[1], dtype=bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for t in range(r.shape[0]):
+            v = np.where(live, v + g * r[t], v)
+            g = g * gamma
+            live &= q[t] == 0
+        return np.where(live, v + g * np.asarray(leaf, dtype=np.float32).astype(np.float64), v)
 
 
 def select_best(values, group):
@@ -160,6 +183,52 @@ def beam_select_ref(reward, reason, n_roots, width, level, weight, slots_in=None
     out = cand[keep]
     fmap = np.where((out["flags"] & BEAM_VALID) != 0, keep, -1).astype(np.int32)
     return out, fmap, out["value"][::int(width)].copy(), out["first"][::int(width)].copy()
+
+
+def beam_keys(cand, leaf, boot_weight):
+    """What bsk_beam_select_boot ranks the candidates ``cand`` (``beam_candidates``) by -> f64[]: value + boot_weight * leaf
+    (product, then sum) for a valid candidate that is live after this step, its value for a valid one that is not, NaN for an
+    invalid one."""
+    live = (cand["flags"] & BEAM_LIVE) != 0
+    lf = np.asarray(leaf, dtype=np.float32)[:len(cand)].astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.where(live, cand["value"] + np.float64(boot_weight) * lf, cand["value"])
+
+
+def beam_select_boot_ref(reward, reason, leaf, n_roots, width, level, weight, boot_weight, slots_in=None):
+    """numpy restatement of one ``bsk_beam_select_boot`` level (include/bskgpu.h), bit for bit -> (slots_out BEAM_SLOT[n_roots *
+    width] with the UN-bootstrapped values, map int32[n_roots * width], keys f64[n_roots * width], best_value f64[n_roots] - the
+    key of rank 0 -, best_action int32[n_roots])."""
+    cand = beam_candidates(reward, reason, n_roots, width, level, weight, slots_in)
+    keys = beam_keys(cand, leaf, boot_weight)
+    ranked = cand.copy()
+    ranked["value"] = keys                                 # (beam_order's rule with the key in place of the value)
+    keep = beam_order(ranked, n_roots)[:, :int(width)].ravel()
+    out = cand[keep]
+    fmap = np.where((out["flags"] & BEAM_VALID) != 0, keep, -1).astype(np.int32)
+    return out, fmap, keys[keep], keys[keep][::int(width)].copy(), out["first"][::int(width)].copy()
+
+
+def check_bootstrap(bootstrap):
+    """Argument rule of ``BeamPlanner(bootstrap=...)`` (no device needed)."""
+    if bootstrap not in ("every", "last"):
+        raise ValueError("bootstrap must be 'every' or 'last', got %r" % (bootstrap,))
+    return bootstrap
+
+
+def check_value_policy(value_policy, device=None):
+    """Argument rules of a planner's ``value_policy`` (no device needed): None, or a ``DevicePolicy`` with a value network - on
+    ``device`` where one is given."""
+    if value_policy is None:
+        return None
+    spec = getattr(value_policy, "spec", None)
+    if spec is None or not hasattr(value_policy, "value_enqueue"):
+        raise TypeError("value_policy must be a DevicePolicy, got %r" % type(value_policy))
+    if spec.value_hidden is None:
+        raise ValueError("value_policy: the policy has no value network")
+    if device is not None and value_policy.device != device:
+        raise ValueError("value_policy lives on device %d, the root on device %d" % (value_policy.device, device))
+    return value_policy
 
 
 class _BranchPlanner(object):
@@ -259,11 +328,19 @@ class LookaheadPlanner(_BranchPlanner):
     The planner owns a branch propagator of ``n_roots * 3**depth`` envs on the root's device and stream with the root's config
     minus ``BRANCH_CLEARED_FLAGS``, the root's sim time and spherical-harmonic field, and device buffers built once: the fork map,
     the action table, the histories and the outputs.  A later ``set_sim_time`` / ``set_gravity_sh`` on the root needs a new planner
-    (the fork refuses partners that differ)."""
+    (the fork refuses partners that differ).
+
+    ``value_policy``: a ``DevicePolicy`` with a value network on the root's device (None: the plain planner, launch for launch).
+    Every branch no step ended then adds ``gamma**n_steps`` times the value network's estimate of its last observation
+    (``branch_values_boot``): ``last_values()``, ``last_branch_values()`` and ``d_best_value`` carry bootstrapped estimates.  The
+    policy is read, not owned; its parameters may change between plans (``PolicyFit``), which is what makes ``distill`` on such a
+    planner an iteration."""
     _handle_names = ("branch",)
 
-    def __init__(self, root, depth=2, tail_steps=0, tail_action=0, gamma=1.0, substeps=None):
+    def __init__(self, root, depth=2, tail_steps=0, tail_action=0, gamma=1.0, substeps=None, value_policy=None):
+        check_value_policy(value_policy)
         self._attach(root, substeps)
+        self.value_policy = check_value_policy(value_policy, self.root.device)
         self.n_branch = check_args(self.n_roots, depth, tail_steps, tail_action, gamma)
         self.depth, self.tail_steps, self.tail_action, self.gamma = int(depth), int(tail_steps), int(tail_action), float(gamma)
         self.group = 3 ** self.depth
@@ -281,14 +358,28 @@ class LookaheadPlanner(_BranchPlanner):
         self.d_values = self._dev(8 * nb)
         self.d_best_value = self._dev(8 * self.n_roots)
         self.d_best_action = self._dev(4 * self.n_roots)
+        if self.value_policy is not None:
+            views = self.branch.device_views()
+            self._d_obs, self._obs_stride = views["obs"].__cuda_array_interface__["data"][0], views["stride"]
+            self.d_leaf = self._dev(4 * nb)                                  # f32[n_branch]: the value network at every leaf
 
     def plan(self):
         """fork -> ``depth + tail_steps`` env steps of every branch -> per-root choice, all enqueued on the root's stream (no copy,
-        no synchronisation).  -> int32 (n_roots,) device view of the chosen actions (``__cuda_array_interface__`` / DLPack):
+        no synchronisation).  With a ``value_policy``: its value network on the branches' last observations (``bsk_policy_value``)
+        in front of the choice, which then adds the discounted leaf value to every branch no step ended
+        (``bsk_select_branches_boot``).  -> int32 (n_roots,) device view of the chosen actions (``__cuda_array_interface__`` / DLPack):
         ``root.step_device(view.__cuda_array_interface__["data"][0], ...)`` and ``torch.from_dlpack(view)`` take it as it is."""
         self.branch.fork_from(self.root, self.d_map.ptr)
         self.branch.step_n(self.n_steps, self.substeps, self.d_actions.ptr, d_reward_hist=self.d_reward_hist.ptr,
                            d_reason_hist=self.d_reason_hist.ptr)
+        if self.value_policy is not None:
+            self.value_policy.value_enqueue(self._d_obs, self._obs_stride, self.n_branch, self.d_leaf.ptr, self.stream)
+            check(_lib.load().bsk_select_branches_boot(C.c_void_p(self.d_reward_hist.ptr), C.c_void_p(self.d_reason_hist.ptr),
+                                                       C.c_void_p(self.d_first_action.ptr), self.n_steps, self.n_branch, self.group,
+                                                       self.gamma, C.c_void_p(self.d_leaf.ptr), C.c_void_p(self.d_values.ptr),
+                                                       C.c_void_p(self.d_best_value.ptr), C.c_void_p(self.d_best_action.ptr),
+                                                       C.c_void_p(self.stream)))
+            return self._actions_view()
         check(_lib.load().bsk_select_branches(C.c_void_p(self.d_reward_hist.ptr), C.c_void_p(self.d_reason_hist.ptr),
                                               C.c_void_p(self.d_first_action.ptr), self.n_steps, self.n_branch, self.group, self.gamma,
                                               C.c_void_p(self.d_values.ptr), C.c_void_p(self.d_best_value.ptr),
@@ -310,11 +401,22 @@ class BeamPlanner(_BranchPlanner):
     root and forks them back into the slots (not after the last level): 4 * horizon launches, capturable into one HIP graph.
     A sequence whose episode has ended continues with action 0 alone and keeps its value.  With ``width >= 3**horizon`` the
     best value equals ``LookaheadPlanner(depth=horizon)``'s bit for bit; ``width == 1`` is a greedy one-step lookahead.  Without
-    ``FLAG_DESAT`` actions 1 and 2 command the same thing: their children tie exactly and both take a slot."""
+    ``FLAG_DESAT`` actions 1 and 2 command the same thing: their children tie exactly and both take a slot.
+
+    ``value_policy``: a ``DevicePolicy`` with a value network on the root's device (None: the plain planner, launch for launch).
+    A level then runs the value network on the children's observations (``bsk_policy_value``, a fifth launch) and ranks them by
+    "return so far + ``w_{t+1}`` times the value of where they stand" (``bsk_beam_select_boot``; an ended sequence by its return
+    alone); the slots keep the un-bootstrapped return, so ``last_beam_values()`` stays the true returns while ``last_values()``
+    and ``d_best_value`` carry the bootstrapped estimate of the best sequence and ``last_beam_keys()`` those of all kept ones.
+    ``bootstrap="every"`` does so at every level, ``"last"`` at the last level only (the levels before it run as without a
+    policy).  With ``width >= 3**horizon`` either equals the bootstrapped ``LookaheadPlanner(depth=horizon)`` bit for bit."""
     _handle_names = ("beam", "children")
 
-    def __init__(self, root, width=9, horizon=32, gamma=1.0, substeps=None):
+    def __init__(self, root, width=9, horizon=32, gamma=1.0, substeps=None, value_policy=None, bootstrap="every"):
+        self.bootstrap = check_bootstrap(bootstrap)
+        check_value_policy(value_policy)
         self._attach(root, substeps)
+        self.value_policy = check_value_policy(value_policy, self.root.device)
         self.weights = check_beam_args(self.n_roots, width, horizon, gamma)
         self.width, self.horizon, self.gamma = int(width), int(horizon), float(gamma)
         self.n_slots = self.n_roots * self.width
@@ -333,6 +435,14 @@ class BeamPlanner(_BranchPlanner):
         views = self.children.device_views()
         self._d_reward = views["reward"].__cuda_array_interface__["data"][0]
         self._d_reason = views["reason"].__cuda_array_interface__["data"][0]
+        if self.value_policy is not None:
+            self._d_obs, self._obs_stride = views["obs"].__cuda_array_interface__["data"][0], views["stride"]
+            self.d_leaf = self._dev(4 * nc)                                  # f32[n_children]: the value network at every child
+            self.d_keys = self._dev(8 * ns)                                  # f64[n_slots]: what the last bootstrapped level ranked by
+            boot = self.weights[-1] * self.gamma                             # w_H, the factor of the step after the last level
+            if not np.isfinite(boot):
+                raise ValueError("gamma**t overflows within the horizon")
+            self.boot_weights = np.append(self.weights[1:], boot)            # level t's leaf counts with w_{t+1} = w_t * gamma
 
     def plan(self):
         """root -> every slot, then ``horizon`` levels of fork -> step -> select -> fork back, all enqueued on the root's stream
@@ -345,9 +455,16 @@ class BeamPlanner(_BranchPlanner):
             self.children.step_device(self.d_actions.ptr, self.substeps)
             d_map = self.d_maps.ptr + 4 * self.n_slots * t
             d_in = vp(self.d_slots[(t + 1) % 2].ptr) if t else None
-            check(lib.bsk_beam_select(vp(self._d_reward), vp(self._d_reason), self.n_roots, self.width, t, float(self.weights[t]),
-                                      d_in, vp(self.d_slots[t % 2].ptr), vp(d_map), vp(self.d_best_value.ptr),
-                                      vp(self.d_best_action.ptr), vp(self.stream)))
+            if self.value_policy is not None and (self.bootstrap == "every" or t + 1 == self.horizon):
+                self.value_policy.value_enqueue(self._d_obs, self._obs_stride, self.n_children, self.d_leaf.ptr, self.stream)
+                check(lib.bsk_beam_select_boot(vp(self._d_reward), vp(self._d_reason), self.n_roots, self.width, t,
+                                               float(self.weights[t]), float(self.boot_weights[t]), vp(self.d_leaf.ptr), d_in,
+                                               vp(self.d_slots[t % 2].ptr), vp(d_map), vp(self.d_keys.ptr), vp(self.d_best_value.ptr),
+                                               vp(self.d_best_action.ptr), vp(self.stream)))
+            else:
+                    check(lib.bsk_beam_select(vp(self._d_reward), vp(self._d_reason), self.n_roots, self.width, t, float(self.weights[t]),
+                                          d_in, vp(self.d_slots[t % 2].ptr), vp(d_map), vp(self.d_best_value.ptr),
+                                          vp(self.d_best_action.ptr), vp(self.stream)))
             if t + 1 < self.horizon:
                 self.beam.fork_from(self.children, d_map)
         return self._actions_view()
@@ -358,6 +475,13 @@ class BeamPlanner(_BranchPlanner):
     def last_beam_values(self):
         """discounted value of every kept sequence of the last plan, f64 (n_roots, width) in rank order (NaN: no sequence)"""
         return self._last_slots()["value"].reshape(self.n_roots, self.width)
+
+    def last_beam_keys(self):
+        """what the last level of the last plan ranked the kept sequences by, f64 (n_roots, width) in rank order: the value plus
+        the discounted leaf value of the sequences still live (NaN: no sequence); needs a ``value_policy``"""
+        if self.value_policy is None:
+            raise ValueError("last_beam_keys: the planner has no value_policy")
+        return self._read(self.d_keys, np.float64, self.n_slots).reshape(self.n_roots, self.width)
 
     def last_sequences(self):
         """the kept action sequences of the last plan, int32 (n_roots, width, horizon) in rank order, rebuilt from the level maps

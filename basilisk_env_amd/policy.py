@@ -290,6 +290,14 @@ class DevicePolicy(_ParamStore):
                                        *outputs, int(n), C.c_void_p(int(stream))))
         return out
 
+    def value_enqueue(self, obs_ptr, obs_stride, n, out_ptr, stream=0):
+        """``bsk_policy_value`` on raw arguments: the value network alone for observations f64[5][obs_stride] at ``obs_ptr``, one
+        launch on ``stream`` that writes f32[n] at ``out_ptr`` - bit for bit what ``enqueue(..., want=("value",))`` leaves in
+        ``value``.  No action network, no draw counter, no output buffer of the policy: it allocates nothing and is capturable from
+        the first call (what the planners read at their leaves, ``planning.LookaheadPlanner(value_policy=...)``)."""
+        check(self._lib.bsk_policy_value(self._handle(), C.c_void_p(int(obs_ptr)) if obs_ptr else None, int(obs_stride), int(n),
+                                         C.c_void_p(int(out_ptr)) if out_ptr else None, C.c_void_p(int(stream or 0))))
+
     def act(self, source, mode="greedy", want=("logp", "value", "logits"), env_base=None, stream=None):
         """One launch: actions (and what ``want`` names) for every spacecraft of ``source`` - a ``BatchedPropagator`` (or an env
         with a ``propagator``): its own observation buffers, stream and env_base - or any device array of shape (5, n) float64 with
