@@ -5,7 +5,9 @@ Every check is an EQUALITY of bits: against the staged pool at the slots policy.
 in Python integers by tests/test_es_adam_host.py), against a host reset from those same initial conditions on a second handle, and
 between envs that share a slot.  Shapes: (256, 64, 0) is whole members in one 256-thread workgroup; (200, 48, 70) has members that
 straddle waves, an n that E does not divide, a last workgroup that is not full and a shard offset that is no multiple of E;
-(256, 64, 128) a shard that starts at a member boundary.  Epoch 2^32 + 3 catches a read of the high word.
+(256, 64, 128) a shard that starts at a member boundary; (700, 192, 5) is three workgroups, the last one partial, with an E that is no
+power of two, and (700, 192, 2^32 - 300) puts the wrap of the 32-bit global index env_base + env inside the batch: envs 300 .. 699
+count on from 0, and 2^32 is no multiple of 192.  Epoch 2^32 + 3 catches a read of the high word.
 """
 import ctypes
 
@@ -72,7 +74,7 @@ def _stepped(cfg, n, env_base, pool, ic):
     return p
 
 
-@pytest.mark.parametrize("n,E,env_base", [(256, 64, 0), (200, 48, 70), (256, 64, 128)])
+@pytest.mark.parametrize("n,E,env_base", [(256, 64, 0), (200, 48, 70), (256, 64, 128), (700, 192, 5), (700, 192, 2 ** 32 - 300)])
 def test_the_shared_reset_is_the_definition(n, E, env_base, pool):
     import torch
     cfg = _config()
@@ -104,7 +106,7 @@ def test_the_shared_reset_is_the_definition(n, E, env_base, pool):
             assert _same(after[key], host[key]), (epoch, key)
         assert not after["rew"].any() and not after["why"].any() and not after["done"].any() and not after["episode_return"].any()
         # equal q, equal initial condition - and one member's envs are not all alike
-        q = (np.arange(n) + env_base) % E
+        q = (np.arange(n) + env_base) % 2 ** 32 % E
         first = np.array([np.flatnonzero(q == x)[0] for x in q])
         assert _same(after["state"], after["state"][:, first]) and _same(after["obs"], after["obs"][:, first])
         assert len({after["state"][0, j] for j in range(E)}) > 20

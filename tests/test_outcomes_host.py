@@ -93,7 +93,7 @@ def _histories(seed, T, P, E):
     return reward, reason, action
 
 
-@pytest.mark.parametrize("P,E,gamma", [(3, 64, 0.97), (2, 128, 1.0), (1, 192, 0.5)])
+@pytest.mark.parametrize("P,E,gamma", [(3, 64, 0.97), (2, 128, 1.0), (1, 192, 0.5), (2, 320, 0.97), (2, 1024, 1.0)])
 def test_member_rows_equal_the_plain_loop(P, E, gamma):
     reward, reason, action = _histories(100 * P + E, 9, P, E)
     got = R.population_outcomes_ref(reward, reason, action, gamma, E)
@@ -114,6 +114,40 @@ def test_member_rows_equal_the_plain_loop(P, E, gamma):
     stray = np.array([sum(int(action[t, i]) == 7 for t in range(length[i])) for i in range(P * E)]).reshape(P, E).sum(axis=1)
     assert stray.sum() > 0
     assert np.array_equal(got[:, 5] + got[:, 6] + got[:, 7], fit["env_len"].reshape(P, E).sum(axis=1) - stray)
+
+
+@pytest.mark.parametrize("E", [64, 192, 320, 1024])
+def test_member_rows_carry_non_finite_values_as_the_plain_loop_does(E):
+    """What the non-finite runs of tests/test_gpu_population_shapes.py lean on: members whose values hold +inf, -inf, both, a NaN in
+    a lane's first element (the incumbent that must be replaced), a NaN in a later one (the candidate that must not win), a NaN
+    in front of an infinity - and rewards of -0.0 in a lane's first env, whose value is +0.0 by the rule (v starts from +0.0)"""
+    P, T, gamma = 7, 5, 0.97
+    rng = np.random.default_rng(E)
+    n = P * E
+    reward = rng.normal(size=(T, n))
+    reason = np.where(rng.random((T, n)) < 0.15, rng.choice([1, 2, 4, 8], size=(T, n)), 0).astype(np.uint8)
+    reason[:2] = 0
+    action = rng.integers(0, 3, size=(T, n)).astype(np.int32)
+    last = E - 1                                                # (with E = 64 every element is a lane's first)
+    reward[1, 0 * E + 7] = np.inf
+    reward[1, 1 * E + last] = -np.inf
+    reward[0, 2 * E + 3], reward[1, 2 * E + last] = np.inf, -np.inf
+    reward[1, 3 * E + 5] = NAN                                  # lane 5: a NaN first
+    reward[0, 4 * E + last] = NAN                               # lane 63: a NaN last
+    reward[0, 5 * E + 9], reward[1, 5 * E + 9] = np.inf, -np.inf                # inf - inf inside one env's value
+    reward[0, 5 * E + 10], reward[0, 5 * E + last - 1] = -np.inf, np.inf
+    reward[:, 6 * E + 0] = -0.0
+    reason[:, 6 * E + 0] = 0
+    got = R.population_outcomes_ref(reward, reason, action, gamma, E)
+    want, _ = _loop_member_rows(reward, reason, action, gamma, E)
+    same = (_bits(got) == _bits(want)) | (np.isnan(got) & np.isnan(want))           # (which NaN a sum makes of inf - inf is the host's)
+    assert same.all(), (got[:, 8:], want[:, 8:])
+    assert np.array_equal(_bits(got[:, 9:]), _bits(want[:, 9:]))                    # the extremes are picked, not computed: every bit
+    assert got[0, 10] == np.inf and got[1, 9] == -np.inf and got[2, 9] == -np.inf and got[2, 10] == np.inf
+    assert np.isnan(got[3:6, 8]).all() and not np.isnan(got[:, 9:]).any()
+    assert got[5, 9] == -np.inf and got[5, 10] == np.inf
+    v = R.population_fitness_ref(reward, reason, gamma, P)["env_value"]
+    assert np.isfinite(got[6]).all() and v[6 * E] == 0.0 and not np.signbit(v[6 * E])
 
 
 def test_steps_by_action_sum_to_the_fitness_lengths():
