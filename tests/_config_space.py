@@ -1,4 +1,5 @@
-"""The space of ``bsk_config`` constants, for tests (tests/test_config_space_host.py, tests/test_gpu_config_space.py).
+"""The space of ``bsk_config`` constants, for tests (tests/test_config_space_host.py, tests/test_gpu_config_space.py, and for the
+halves form of the one-sub-step launch tests/test_halves_config_host.py, tests/test_gpu_halves_config.py).
 
 ``bsk_default_config`` is symmetric exactly where an indexing mistake would show (all ``js`` equal, all ``facet_cd`` 2.2, the
 +/- facet pairs of equal area, two zero components in ``sigma_R0N`` and in ``panel_normal``, identity ``ctrl_axes``,
@@ -68,7 +69,7 @@ def kernel_name(cfg, hub, level, form="single", sh_form=None, rollout=None):
     if rollout:
         return "rollout_kernel<%s,%d,%s,%s>" % (g, cfg.n_rw, hub, rollout)
     lvl = {"bare": "", "ldss": ",lds-scratch", "power": ",power", "full": ",scenario", "fullg": ",scenario/generic-facets"}[level]
-    return "step_kernel<%s,%d,%s%s%s>" % (g, cfg.n_rw, hub, lvl, {"single": "", "pair": ",pair", "tri": ",tri"}[form])
+    return "step_kernel<%s,%d,%s%s%s>" % (g, cfg.n_rw, hub, lvl, {"single": "", "pair": ",pair", "tri": ",tri", "halves": ",halves"}[form])
 
 
 # ---------------------------------------------------------------------------------------------------------------- draws
@@ -324,6 +325,36 @@ def run_oracle(cfg, ic, schedule, sim_time0=0.0, sh=(None, None), ticks0=0, omp=
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------- halves form
+ODD_ACTIONS = (3, 7, 15, 16, 255, -1)      # raw integers outside {0, 1, 2}: to the oracle's guidance, as to the kernels, "not 0"
+
+
+def halves_schedule(n, seed, launches=48, odd_actions=False):
+    """[(actions int32[n], 1)] * launches: what the halves form of the step kernel runs (one sub-step per launch), past several FSW
+    ticks of every period ``draw_halves_structure`` draws.  ``odd_actions``: a quarter of the actions come from ``ODD_ACTIONS``."""
+    rng = np.random.default_rng(8000 + seed)
+    out = []
+    for _ in range(launches):
+        act = rng.integers(0, 3, n).astype(np.int32)
+        if odd_actions:
+            odd = rng.random(n) < 0.25
+            act[odd] = rng.choice(np.array(ODD_ACTIONS, dtype=np.int32), size=int(odd.sum()))
+        out.append((act, 1))
+    return out
+
+
+def draw_halves_structure(cfg, rng):
+    """The structure fields the halves form duplicates code for (its own phase rule, tick test and integrator constants): an FSW
+    period on which every launch / every other launch / an odd share of the launches carries the hand-over, another integrator
+    step, either task order, and an episode shorter than ``halves_schedule``.  ``nav_lag`` stays 1: the form needs it."""
+    cfg.fsw_every = int(rng.choice([1, 2, 3, 7, 13]))
+    cfg.dt = float(rng.choice([0.05, 0.1, 0.25]))
+    cfg.fsw_lag = int(rng.integers(0, 2))
+    cfg.nav_lag = 1
+    cfg.max_length = int(rng.integers(20, 40))
+    return cfg
+
+
 def change(a, b, n_rw):
     """How far two runs of ``run_oracle`` are apart, in the units of the GPU tests' tolerances: the largest relative change of a
     state field group (helpers.max_group_err, GPU tolerance 1e-11), of the battery charge [W s] relative to 1e4 (GPU: 1e-7 W s),
@@ -370,14 +401,15 @@ FIELDS = {
     "abi_version": _abi("checked by validate()"),
     "struct_size": _abi("checked by validate()"),
     "pad0_": _abi("padding"),
-    "dt": _structure("integrator step: varied by the parity, fuzz and rollout tests; every Scenario here keeps 0.1 s"),
-    "fsw_every": _structure("FSW period: fuzz tests"),
+    "dt": _structure("integrator step: varied by the parity, fuzz and rollout tests, and in the halves form by "
+                     "tests/test_gpu_halves_config.py (draw_halves_structure); every Scenario here keeps 0.1 s"),
+    "fsw_every": _structure("FSW period: fuzz tests; in the halves form tests/test_gpu_halves_config.py (1, 2, 3, 7, 10, 13)"),
     "gravity_model": _structure("selects the kernel: every test"),
     "sh_degree": _structure("harmonics tests"),
     "n_rw": _structure("selects the kernel: every test"),
     "flags": _structure("feature level and output forms: every test"),
     "max_length": _structure("episode length: rollout and auto-reset tests"),
-    "fsw_lag": _structure("task order: fuzz tests"),
+    "fsw_lag": _structure("task order: fuzz tests; in the halves form tests/test_gpu_halves_config.py"),
     "nav_lag": _structure("task priorities: fuzz tests"),
     "gs": _structure("wheel spin axes: a tilted axis is the general-hub family (helpers.general_hub; hub='full' here)"),
     "n_facets": _structure("facet count: tests/test_gpu_forces.py"),
