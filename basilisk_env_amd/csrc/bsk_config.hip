@@ -365,6 +365,12 @@ int validate(const bsk_config& c) {
         return fail(BSK_EINVAL, "BSK_FLAG_SUN_THIRD_BODY / BSK_FLAG_DRAG / BSK_FLAG_DESAT are built in the full-scenario kernel: set BSK_FLAG_POWER too");
     if ((c.flags & BSK_FLAG_DESAT) && (c.n_thr < 3 || c.n_thr > BSK_MAX_THR || c.n_rw == 0 || !(c.thr_max_thrust > 0.0) || !(c.mass > 0.0)))
         return fail(BSK_EINVAL, "BSK_FLAG_DESAT needs 3..8 thrusters, wheels, thr_max_thrust > 0 and mass > 0");
+    if ((c.flags & BSK_FLAG_DESAT) && !(std::isfinite(c.thr_min_on_time) && c.thr_min_on_time >= 0.0 && std::isfinite(c.thr_min_fire_time) && c.thr_min_fire_time >= 0.0))
+        return fail(BSK_EINVAL, "BSK_FLAG_DESAT needs thr_min_on_time and thr_min_fire_time finite and not negative");
+    // a burst limit is kept in 16 bits (bsk_device.hpp: desat_tick packs two per register): a stretched pulse must fit
+    if ((c.flags & BSK_FLAG_DESAT) && !(std::floor(c.thr_min_on_time * (2.0 / c.dt)) <= 65535.0))
+        return fail(BSK_EINVAL, "BSK_FLAG_DESAT: floor(thr_min_on_time * 2 / dt) must be at most 65535 (the burst limit of a pulse that passes "
+                                "thr_min_fire_time and is stretched to thr_min_on_time, in half steps of dt, is kept in 16 bits)");
     if ((c.flags & BSK_FLAG_DRAG) && (c.n_facets < 0 || c.n_facets > 8 || !(c.scale_height > 0.0) || !(c.mass > 0.0)))
         return fail(BSK_EINVAL, "BSK_FLAG_DRAG needs 0..8 facets, scale_height > 0 and mass > 0");
     if ((c.flags & BSK_FLAG_LDS_SCRATCH) && ((c.flags & BSK_FLAG_POWER) || c.gravity_model == BSK_GRAV_SH))

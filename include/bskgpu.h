@@ -163,6 +163,8 @@ typedef struct bsk_config {
     double thr_max_thrust;     /* N   (MOOG Monarc-1: 0.9)                                   */
     double thr_min_fire_time;  /* s   thrMomentumDumping.thrMinFireTime (…Simulator.py:190)   */
     double thr_min_on_time;    /* s   thruster MinOnTime (MOOG Monarc-1: 0.02)               */
+                               /*     with BSK_FLAG_DESAT both times are finite and >= 0, and floor(thr_min_on_time * 2 / dt)
+                                      <= 65535: a burst limit is kept in 16 bits (bsk_create refuses the config otherwise) */
     double hs_min;             /* N m s  thrMomentumManagement.hs_min (…Simulator.py:183)     */
 
     /* drag (…Simulator.py:147-148, 272-281) */

@@ -28,6 +28,39 @@
 
 #include "../include/bskgpu.h"
 
+/* Branch masks (tests/_actuators.py; built with -DORC_BRANCH_MASK by tests/test_actuators_host.py only - the default build has none
+ * of this: every MARK() below expands to nothing).  One uint32 per spacecraft that ORs a bit for every data-dependent branch of the
+ * actuator chain taken during the last orc_step; orc_branch_mask() copies them out. */
+#ifdef ORC_BRANCH_MASK
+enum {
+    ORC_B_REQ_ABOVE = 1u << 0,      /* desat request: wheel momentum above hs_min                                   */
+    ORC_B_REQ_BELOW = 1u << 1,      /*                at or below hs_min (nothing to dump)                           */
+    ORC_B_TICK_FIRE = 1u << 2,      /* desat tick: fires a burst                                                     */
+    ORC_B_TICK_COUNT = 1u << 3,     /*             counts down                                                       */
+    ORC_B_PULSE_DROP_OWED = 1u << 4,/* pulse below thr_min_fire_time dropped although on-time > 0 was owed           */
+    ORC_B_PULSE_DROP_ZERO = 1u << 5,/* pulse of on-time 0 dropped                                                    */
+    ORC_B_PULSE_FULL = 1u << 6,     /* pulse of a full control period                                                */
+    ORC_B_PULSE_STRETCH = 1u << 7,  /* partial pulse stretched to thr_min_on_time                                    */
+    ORC_B_PULSE_PARTIAL = 1u << 8,  /* partial pulse, not stretched                                                  */
+    ORC_B_CMD_CLAMP = 1u << 9,      /* wheel command clamped at +-u_max                                              */
+    ORC_B_CMD_DEAD = 1u << 10,      /* non-zero command inside the dead-band                                         */
+    ORC_B_CMD_ZERO = 1u << 11,      /* command exactly zero before the dead-band                                     */
+    ORC_B_CMD_PASS = 1u << 12,      /* command passed through                                                        */
+    ORC_B_OM_POS = 1u << 13,        /* a wheel speed at the start of a tick: positive                                */
+    ORC_B_OM_NEG = 1u << 14,        /*                                       negative                                */
+    ORC_B_OM_ZERO = 1u << 15,       /*                                       exactly zero                            */
+    ORC_B_THR_STAGE = 1u << 16,     /* some thruster active in an RK4 stage                                          */
+    ORC_B_THR_END = 1u << 17,       /* a step whose first stage is inside a burst and whose last stage is outside it */
+    ORC_B_OM_CROSS = 1u << 18       /* a wheel whose speed ends a tick with the other sign than it began it with    */
+};
+static _Thread_local uint32_t t_mask;
+static uint32_t* g_masks = 0;
+static int g_masks_n = 0;
+#define MARK(b) (t_mask |= (uint32_t)(b))
+#else
+#define MARK(b) ((void)0)
+#endif
+
 /* ---------------------------------------------------------------- small algebra */
 static void v3set(double a, double b, double c, double o[3]) { o[0] = a; o[1] = b; o[2] = c; }
 static void v3copy(const double a[3], double o[3]) { o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; }
@@ -315,6 +348,7 @@ static void eom(orc_ctx* ctx, const double x[NX], const double tq[BSK_MAX_RW], c
         double F_B[3] = {0, 0, 0}, bn[9];
         for (int i = 0; i < c->n_thr; ++i)
             if (th->lim[i] > 0.0 && (double)th->e2 <= th->lim[i]) {
+                MARK(ORC_B_THR_STAGE);
                 v3add(F_B, ctx->thr_f[i], F_B);
                 v3add(lext, ctx->thr_l[i], lext);
             }
@@ -351,6 +385,21 @@ static void rk4_step(orc_ctx* ctx, double x[NX], const double ucmd[BSK_MAX_RW], 
     if (ctx->c->flags & BSK_FLAG_DRAG) rho = ctx->c->base_density * exp(-(v3norm(x) - ctx->c->req) / ctx->c->scale_height);
     wheel_torque(ctx, x, ucmd, u); /* motor + friction torque, held over the step */
     const int e2 = th ? th->e2 : 0;
+#ifdef ORC_BRANCH_MASK
+    double om0[BSK_MAX_RW];
+    for (int i = 0; i < ctx->c->n_rw; ++i) {
+        om0[i] = x[12 + i];
+        MARK(om0[i] > 0.0 ? ORC_B_OM_POS : om0[i] < 0.0 ? ORC_B_OM_NEG : ORC_B_OM_ZERO);
+    }
+    if (th && th->active) {
+        int first = 0, last = 0;
+        for (int i = 0; i < ctx->c->n_thr; ++i) {
+            if (th->lim[i] > 0.0 && (double)e2 <= th->lim[i]) first = 1;
+            if (th->lim[i] > 0.0 && (double)(e2 + 2) <= th->lim[i]) last = 1;
+        }
+        if (first && !last) MARK(ORC_B_THR_END);
+    }
+#endif
     eom(ctx, x, u, lext, t, sun, rho, th, k);
     for (int i = 0; i < NX; ++i) { acc[i] = x[i] + h / 6.0 * k[i]; xt[i] = x[i] + 0.5 * h * k[i]; }
     if (th) th->e2 = e2 + 1;
@@ -364,6 +413,10 @@ static void rk4_step(orc_ctx* ctx, double x[NX], const double ucmd[BSK_MAX_RW], 
     if (g_friction_per_stage) wheel_torque(ctx, xt, ucmd, u);
     eom(ctx, xt, u, lext, t + h, sun, rho, th, k);
     for (int i = 0; i < NX; ++i) x[i] = acc[i] + h / 6.0 * k[i];
+#ifdef ORC_BRANCH_MASK
+    for (int i = 0; i < ctx->c->n_rw; ++i)
+        if ((om0[i] > 0.0 && x[12 + i] < 0.0) || (om0[i] < 0.0 && x[12 + i] > 0.0)) MARK(ORC_B_OM_CROSS);
+#endif
     double s2 = v3dot(x + 6, x + 6);
     if (s2 > 1.0) v3scale(-1.0 / s2, x + 6, x + 6);
 }
@@ -428,6 +481,7 @@ static void control(orc_ctx* ctx, const att_guid* g, double u[BSK_MAX_RW]) {
        wheel's own saturation and dead-band (reactionWheelStateEffector, HR16 preset) */
     for (int i = 0; i < c->n_rw; ++i) {
         double us = -v3dot(ctx->map[i], Lr);
+        MARK(c->u_max > 0.0 && fabs(us) > c->u_max ? ORC_B_CMD_CLAMP : us == 0.0 ? ORC_B_CMD_ZERO : fabs(us) < c->u_min ? ORC_B_CMD_DEAD : ORC_B_CMD_PASS);
         if (c->u_max > 0.0) { if (us > c->u_max) us = c->u_max; else if (us < -c->u_max) us = -c->u_max; }
         if (fabs(us) < c->u_min) us = 0.0;
         u[i] = us;
@@ -580,11 +634,19 @@ int orc_step(const bsk_config* c, int n, double* state, int32_t* steps, int32_t*
     if (ctx_init(&ctx, c, cbar, sbar)) return -1;
     const int nrw = c->n_rw, tail = BSK_NF_BASE + nrw;
 #define S(f, i) state[(size_t)(f) * n + (i)]
+#ifdef ORC_BRANCH_MASK
+    free(g_masks);
+    g_masks = calloc((size_t)(n > 0 ? n : 1), sizeof(uint32_t));
+    g_masks_n = g_masks ? n : 0;
+#endif
 #ifdef ORC_OMP
 #pragma omp parallel for schedule(static)
 #endif
     for (int e = 0; e < n; ++e) {
         double x[NX] = {0}, u[BSK_MAX_RW], lext[3];
+#ifdef ORC_BRANCH_MASK
+        t_mask = 0;
+#endif
         for (int f = 0; f < 12 + nrw; ++f) x[f] = S(f, e);
         for (int k = 0; k < 3; ++k) lext[k] = S(tail + BSK_T_LEXT + k, e);
         for (int i = 0; i < BSK_MAX_RW; ++i) u[i] = S(tail + BSK_T_UCMD + i, e);
@@ -635,6 +697,7 @@ int orc_step(const bsk_config* c, int n, double* state, int32_t* steps, int32_t*
                         for (int k = 0; k < 3; ++k) hs[k] += c->js[i] * (NAV)[12 + i] * c->gs[i][k];                     \
                     double hm = v3norm(hs), dH[3] = {0, 0, 0};                                                           \
                     if (hm > c->hs_min) v3scale(-(hm - c->hs_min) / hm, hs, dH);                                         \
+                    MARK(hm > c->hs_min ? ORC_B_REQ_ABOVE : ORC_B_REQ_BELOW);                                            \
                     /* thrForceMapping, on-pulsing (thrForceSign +1, :186): minimum-norm impulses                        \
                        F = D^T (D D^T)^-1 dH, then subtract the smallest so that all are >= 0 */                         \
                     double F[BSK_MAX_THR], fmin = 0.0;                                                                   \
@@ -643,12 +706,15 @@ int orc_step(const bsk_config* c, int n, double* state, int32_t* steps, int32_t*
                     for (int i = 0; i < c->n_thr; ++i) thr_rem[i] = (F[i] - fmin) / c->thr_max_thrust;                   \
                     thr_cnt = 0;                                                                                         \
                 }                                                                                                        \
+                MARK(thr_cnt <= 0 ? ORC_B_TICK_FIRE : ORC_B_TICK_COUNT);                                                 \
                 if (thr_cnt <= 0) {                                                                                      \
                     /* fire: each thruster for min(remaining, control period); pulses shorter than thrMinFireTime       \
                        (:190) are dropped; the thruster stretches a pulse to its MinOnTime */                           \
                     for (int i = 0; i < BSK_MAX_THR; ++i) lim_msg[i] = thr_lim[i];                                       \
                     for (int i = 0; i < c->n_thr; ++i) {                                                                 \
                         double on = thr_rem[i] < Tc ? thr_rem[i] : Tc;                                                   \
+                        MARK(on < c->thr_min_fire_time ? (on > 0.0 ? ORC_B_PULSE_DROP_OWED : ORC_B_PULSE_DROP_ZERO)              \
+                             : on >= Tc ? ORC_B_PULSE_FULL : on < c->thr_min_on_time ? ORC_B_PULSE_STRETCH : ORC_B_PULSE_PARTIAL); \
                         if (on < c->thr_min_fire_time) { on = 0.0; thr_rem[i] = 0.0; lim_msg[i] = 0.0; continue; }       \
                         thr_rem[i] -= on;                                                                                \
                         if (on >= Tc) lim_msg[i] = 2.0 * c->fsw_every;                                                   \
@@ -752,6 +818,9 @@ int orc_step(const bsk_config* c, int n, double* state, int32_t* steps, int32_t*
         }
         steps[e] += 1;
         ticks[e] = tick;
+#ifdef ORC_BRANCH_MASK
+        if (e < g_masks_n) g_masks[e] = t_mask;
+#endif
     }
 #undef S
 #undef FSW_TICK
@@ -759,6 +828,15 @@ int orc_step(const bsk_config* c, int n, double* state, int32_t* steps, int32_t*
     ctx_free(&ctx);
     return 0;
 }
+
+#ifdef ORC_BRANCH_MASK
+/* the branch masks of the last orc_step, one per spacecraft -> the number copied (at most n) */
+int orc_branch_mask(uint32_t* out, int n) {
+    int k = n < g_masks_n ? n : g_masks_n;
+    for (int i = 0; i < k; ++i) out[i] = g_masks[i];
+    return k;
+}
+#endif
 
 #ifdef ORC_OMP
 #include <omp.h>

@@ -29,7 +29,54 @@ def load(omp=False):
         path = override
     elif not os.path.exists(path):
         build()
-    lib = C.CDLL(path)
+    lib = _bind(C.CDLL(path))
+    _LIBS[name] = lib
+    return lib
+
+
+def load_path(path):
+    """A second build of the same source, loaded from ``path`` (tests/test_actuators_host.py: the build with -DORC_BRANCH_MASK, made
+    by ``build_branch_mask``).  The default library is untouched; pass the result as ``lib=`` to ``step``."""
+    path = os.path.abspath(path)
+    if path not in _LIBS:
+        lib = _bind(C.CDLL(path))
+        if hasattr(lib, "orc_branch_mask"):
+            lib.orc_branch_mask.argtypes = [C.c_void_p, C.c_int]
+        _LIBS[path] = lib
+    return _LIBS[path]
+
+
+def makefile_flags():
+    """(compiler, flags) of oracle/Makefile's default build"""
+    cc, flags = "gcc", None
+    with open(os.path.join(_HERE, "Makefile")) as fh:
+        for line in fh:
+            if line.startswith("CC ?="):
+                cc = line.split("=", 1)[1].strip()
+            if line.startswith("CFLAGS ?="):
+                flags = line.split("=", 1)[1].split()
+    assert flags, "oracle/Makefile: no CFLAGS"
+    return os.environ.get("CC", cc), flags
+
+
+def build_branch_mask(out_dir):
+    """Compile oracle/bsk_oracle.c with the Makefile's flags plus -DORC_BRANCH_MASK into ``out_dir`` -> the loaded library"""
+    cc, flags = makefile_flags()
+    out = os.path.join(str(out_dir), "liboracle_branch_mask.so")
+    if not os.path.exists(out):
+        subprocess.check_call([cc] + flags + ["-DORC_BRANCH_MASK", "-shared", "-o", out, os.path.join(_HERE, "bsk_oracle.c"), "-lm"])
+    return load_path(out)
+
+
+def branch_masks(lib, n):
+    """The branch masks (oracle/bsk_oracle.c: ORC_B_*) of the last ``step(..., lib=lib)``, uint32 (n,)"""
+    out = np.zeros(n, np.uint32)
+    got = lib.orc_branch_mask(out.ctypes.data, n)
+    assert got == n, (got, n)
+    return out
+
+
+def _bind(lib):
     P, vp = C.POINTER, C.c_void_p
     lib.orc_n_fields.argtypes = [P(BskConfig)]
     lib.orc_step.argtypes = [P(BskConfig), C.c_int, vp, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp]
@@ -41,7 +88,6 @@ def load(omp=False):
     lib.orc_submrp.argtypes = [vp, vp, vp]
     lib.orc_shadow.argtypes = [P(BskConfig), vp, vp]
     lib.orc_shadow.restype = C.c_double
-    _LIBS[name] = lib
     return lib
 
 
@@ -68,10 +114,11 @@ def _p(a):
     return a.ctypes.data if a is not None else None
 
 
-def step(cfg, state, steps, ticks, actions, substeps, sim_time0=0.0, cbar=None, sbar=None, omp=False):
+def step(cfg, state, steps, ticks, actions, substeps, sim_time0=0.0, cbar=None, sbar=None, omp=False, lib=None):
     """One env step for every column of ``state`` ([n_fields, N], modified in place together with
-    ``steps``/``ticks`` int32[N]).  -> obs (5,N), reward (N,), done (N,) bool, reason (N,) uint8."""
-    lib = load(omp)
+    ``steps``/``ticks`` int32[N]).  -> obs (5,N), reward (N,), done (N,) bool, reason (N,) uint8.
+    ``lib``: another build of the oracle (``load_path``) instead of the default one."""
+    lib = load(omp) if lib is None else lib
     n = state.shape[1]
     assert state.dtype == np.float64 and state.flags.c_contiguous and state.shape[0] == n_fields(cfg.n_rw)
     assert steps.dtype == np.int32 and ticks.dtype == np.int32

@@ -94,6 +94,45 @@ def test_abi_rejects_bad_config():
     assert lib.bsk_version().startswith(b"bskgpu")
 
 
+def _desat_config():
+    c = default_config(3, _lib.GRAV_PM)
+    c.flags |= _lib.FLAG_POWER | _lib.FLAG_DESAT
+    return c
+
+
+def test_abi_rejects_desat_times_that_do_not_fit_a_burst_limit():
+    """A burst limit is kept in 16 bits (csrc/bsk_device.hpp: desat_tick packs two per register; the oracle keeps doubles): with
+    BSK_FLAG_DESAT the two thruster times are finite and not negative, and floor(thr_min_on_time * 2 / dt), the limit of a stretched
+    pulse, is at most 65535.  One below the limit is accepted (tests/test_gpu_actuators.py runs it against the oracle)."""
+    lib = _lib.load()
+    h = ctypes.c_void_p()
+    for field in ("thr_min_on_time", "thr_min_fire_time"):
+        for bad in (-1e-3, float("nan"), float("inf"), -float("inf")):
+            c = _desat_config()
+            setattr(c, field, bad)
+            assert lib.bsk_create(ctypes.byref(c), 4, 0, None, ctypes.byref(h)) == -1, (field, bad)
+            assert b"thr_min_on_time" in lib.bsk_last_error() and b"thr_min_fire_time" in lib.bsk_last_error()
+            c.flags &= ~_lib.FLAG_DESAT                              # without the flag nothing reads them
+            rc = lib.bsk_create(ctypes.byref(c), 4, 0, None, ctypes.byref(h))
+            assert rc != -1, (field, bad, lib.bsk_last_error())
+            if rc == 0:
+                lib.bsk_destroy(h)
+    for dt, on, accepted in ((0.1, 3276.775, True), (0.1, 3276.8, False), (0.1, 3276.85, False), (1.0, 32767.9, True), (1.0, 32768.0, False),
+                             (0.001, 32.76775, True), (0.001, 32.7685, False), (0.1, 0.0, True)):
+        c = _desat_config()
+        c.dt, c.thr_min_on_time = dt, on
+        assert (np.floor(on * (2.0 / dt)) <= 65535) == accepted
+        rc = lib.bsk_create(ctypes.byref(c), 4, 0, None, ctypes.byref(h))
+        if accepted:
+            assert rc != -1, (dt, on, lib.bsk_last_error())
+            if rc == 0:
+                lib.bsk_destroy(h)
+        else:
+            assert rc == -1, (dt, on)
+            msg = lib.bsk_last_error()
+            assert b"thr_min_on_time" in msg and b"thr_min_fire_time" in msg and b"dt" in msg and b"65535" in msg, msg
+
+
 def test_header_is_valid_c99():
     """include/bskgpu.h compiles as C (not only as C++): it is the contract a cgo/JNI/ctypes binding reads."""
     import subprocess
