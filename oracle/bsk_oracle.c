@@ -28,9 +28,10 @@
 
 #include "../include/bskgpu.h"
 
-/* Branch masks (tests/_actuators.py; built with -DORC_BRANCH_MASK by tests/test_actuators_host.py only - the default build has none
- * of this: every MARK() below expands to nothing).  One uint32 per spacecraft that ORs a bit for every data-dependent branch of the
- * actuator chain taken during the last orc_step; orc_branch_mask() copies them out. */
+/* Branch masks (tests/_actuators.py, tests/_guidance.py; built with -DORC_BRANCH_MASK by tests/test_actuators_host.py and
+ * tests/test_guidance_host.py only - the default build has none of this: every MARK() below expands to nothing).  One uint32 per
+ * spacecraft that ORs a bit for every data-dependent branch of the actuator chain and of the attitude guidance chain taken during the
+ * last orc_step; orc_branch_mask() copies them out. */
 #ifdef ORC_BRANCH_MASK
 enum {
     ORC_B_REQ_ABOVE = 1u << 0,      /* desat request: wheel momentum above hs_min                                   */
@@ -51,7 +52,16 @@ enum {
     ORC_B_OM_ZERO = 1u << 15,       /*                                       exactly zero                            */
     ORC_B_THR_STAGE = 1u << 16,     /* some thruster active in an RK4 stage                                          */
     ORC_B_THR_END = 1u << 17,       /* a step whose first stage is inside a burst and whose last stage is outside it */
-    ORC_B_OM_CROSS = 1u << 18       /* a wheel whose speed ends a tick with the other sign than it began it with    */
+    ORC_B_OM_CROSS = 1u << 18,      /* a wheel whose speed ends a tick with the other sign than it began it with    */
+    /* the attitude guidance chain (tests/_guidance.py) */
+    ORC_B_GUID_ZNAV = 1u << 19,     /* reference: hillPoint on a navigation message nobody has written (zero)        */
+    ORC_B_GUID_HILL = 1u << 20,     /*            the Hill frame                                                     */
+    ORC_B_GUID_INERTIAL = 1u << 21, /*            sigma_R0N                                                          */
+    ORC_B_C2MRP_0 = 1u << 22,       /* Sheppard case 0 .. 3 (bits 22 .. 25)                                          */
+    ORC_B_C2MRP_FLIP = 1u << 26,    /* b0 < 0 in case 1 .. 3: the Euler parameters change sign                       */
+    ORC_B_SUBMRP_GUARD = 1u << 27,  /* |den| < 0.1: the relative MRP from the shadow of the first                    */
+    ORC_B_SUBMRP_INNER = 1u << 28,  /* |q|^2 > 1: the result mapped to the inner set                                 */
+    ORC_B_MRP_SWITCH = 1u << 29     /* the shadow-set switch after an RK4 step                                       */
 };
 static _Thread_local uint32_t t_mask;
 static uint32_t* g_masks = 0;
@@ -124,6 +134,7 @@ static void c2mrp(const double c[9], double q[3]) {
     int i = 0;
     for (int j = 1; j < 4; ++j) if (b2[j] > b2[i]) i = j;
     double b[4];
+    MARK(ORC_B_C2MRP_0 << i);
     switch (i) {
     case 0:
         b[0] = sqrt(b2[0]);
@@ -132,19 +143,19 @@ static void c2mrp(const double c[9], double q[3]) {
     case 1:
         b[1] = sqrt(b2[1]);
         b[0] = (c[5] - c[7]) / 4. / b[1];
-        if (b[0] < 0) { b[1] = -b[1]; b[0] = -b[0]; }
+        if (b[0] < 0) { b[1] = -b[1]; b[0] = -b[0]; MARK(ORC_B_C2MRP_FLIP); }
         b[2] = (c[1] + c[3]) / 4. / b[1]; b[3] = (c[6] + c[2]) / 4. / b[1];
         break;
     case 2:
         b[2] = sqrt(b2[2]);
         b[0] = (c[6] - c[2]) / 4. / b[2];
-        if (b[0] < 0) { b[2] = -b[2]; b[0] = -b[0]; }
+        if (b[0] < 0) { b[2] = -b[2]; b[0] = -b[0]; MARK(ORC_B_C2MRP_FLIP); }
         b[1] = (c[1] + c[3]) / 4. / b[2]; b[3] = (c[5] + c[7]) / 4. / b[2];
         break;
     default:
         b[3] = sqrt(b2[3]);
         b[0] = (c[1] - c[3]) / 4. / b[3];
-        if (b[0] < 0) { b[3] = -b[3]; b[0] = -b[0]; }
+        if (b[0] < 0) { b[3] = -b[3]; b[0] = -b[0]; MARK(ORC_B_C2MRP_FLIP); }
         b[1] = (c[6] + c[2]) / 4. / b[3]; b[2] = (c[5] + c[7]) / 4. / b[3];
         break;
     }
@@ -159,6 +170,7 @@ static void submrp(const double q1in[3], const double q2[3], double q[3]) {
     double d1 = v3dot(s1, s1), d2 = v3dot(q2, q2);
     double den = 1.0 + d1 * d2 + 2.0 * v3dot(s1, q2);
     if (fabs(den) < 0.1) {
+        MARK(ORC_B_SUBMRP_GUARD);
         v3scale(-1.0 / d1, s1, s1);
         d1 = v3dot(s1, s1);
         den = 1.0 + d1 * d2 + 2.0 * v3dot(s1, q2);
@@ -166,7 +178,7 @@ static void submrp(const double q1in[3], const double q2[3], double q[3]) {
     v3cross(s1, q2, t);
     for (int k = 0; k < 3; ++k) q[k] = ((1.0 - d2) * s1[k] - (1.0 - d1) * q2[k] + 2.0 * t[k]) / den;
     double m = v3dot(q, q);
-    if (m > 1.0) v3scale(-1.0 / m, q, q);
+    if (m > 1.0) { MARK(ORC_B_SUBMRP_INNER); v3scale(-1.0 / m, q, q); }
 }
 
 /* ---------------------------------------------------------------- derived constants */
@@ -418,7 +430,7 @@ static void rk4_step(orc_ctx* ctx, double x[NX], const double ucmd[BSK_MAX_RW], 
         if ((om0[i] > 0.0 && x[12 + i] < 0.0) || (om0[i] < 0.0 && x[12 + i] > 0.0)) MARK(ORC_B_OM_CROSS);
 #endif
     double s2 = v3dot(x + 6, x + 6);
-    if (s2 > 1.0) v3scale(-1.0 / s2, x + 6, x + 6);
+    if (s2 > 1.0) { MARK(ORC_B_MRP_SWITCH); v3scale(-1.0 / s2, x + 6, x + 6); }
 }
 
 /* ---------------------------------------------------------------- FSW chain (1 Hz)
@@ -433,11 +445,13 @@ static void guidance(orc_ctx* ctx, const double x[NX], int action, att_guid* g) 
         /* hillPoint on a navigation message nobody has written yet (all zeros; the FSW tasks' first tick, see
            orc_step): its unit vectors normalise to zero, the DCM of zeros maps to the zero MRP and the module's
            radius guard zeroes the rates [BSK-recall] */
+        MARK(ORC_B_GUID_ZNAV);
         v3set(0, 0, 0, sigma_RN); v3set(0, 0, 0, omega_RN_N); v3set(0, 0, 0, domega_RN_N);
     } else if (action == 0) {
         /* hillPoint (…Simulator.py:414-419): Hill frame {i_r, i_theta, i_h} */
         const double *r = x, *v = x + 3;
         double rm = v3norm(r), h[3], dcm[9];
+        MARK(ORC_B_GUID_HILL);
         v3cross(r, v, h);
         double hm = v3norm(h);
         v3scale(1.0 / rm, r, dcm);
@@ -450,6 +464,7 @@ static void guidance(orc_ctx* ctx, const double x[NX], int action, att_guid* g) 
     } else {
         /* inertial3D (…Simulator.py:407-411, sigma_R0N :170) — also the attitude target of the
            desat mode (action 2, :574-588) */
+        MARK(ORC_B_GUID_INERTIAL);
         v3copy(c->sigma_R0N, sigma_RN);
         v3set(0, 0, 0, omega_RN_N); v3set(0, 0, 0, domega_RN_N);
     }
@@ -788,7 +803,13 @@ int orc_step(const bsk_config* c, int n, double* state, int32_t* steps, int32_t*
         /* obs[0] is the logged att_guidance message (…Simulator.py:605,611): with nav_lag the one the last FSW tick
            wrote; otherwise the tracking error of the end-of-step state under the step's mode */
         att_guid g;
+#ifdef ORC_BRANCH_MASK
+        const uint32_t mask_fsw = t_mask;
+#endif
         guidance(&ctx, x, act, &g);
+#ifdef ORC_BRANCH_MASK
+        if (navlag) t_mask = mask_fsw;   /* this evaluation goes unused under nav_lag: what it takes is no branch of the step */
+#endif
         double o0 = navlag ? sbr : v3norm(g.sigma_BR), o1 = v3norm(x + 9), o2 = 0;
         for (int i = 0; i < nrw; ++i) o2 += x[12 + i] * x[12 + i];
         o2 = sqrt(o2) / c->wheel_limit;

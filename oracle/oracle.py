@@ -69,7 +69,8 @@ def build_branch_mask(out_dir):
 
 
 def branch_masks(lib, n):
-    """The branch masks (oracle/bsk_oracle.c: ORC_B_*) of the last ``step(..., lib=lib)``, uint32 (n,)"""
+    """The branch masks (oracle/bsk_oracle.c: ORC_B_*) of the last ``step(..., lib=lib)``, uint32 (n,): bits 0 .. 18 the actuator
+    chain (tests/_actuators.py: BITS), bits 19 .. 29 the attitude guidance chain (tests/_guidance.py: BITS)"""
     out = np.zeros(n, np.uint32)
     got = lib.orc_branch_mask(out.ctypes.data, n)
     assert got == n, (got, n)

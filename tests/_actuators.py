@@ -186,7 +186,7 @@ class Cast(object):
     # ------------------------------------------------------------------------------------------------------------ layouts
     def layouts(self):
         """-> {name: index (n,) int: the character in each env, -1 filler}"""
-        first = [s for s in self.slots if s in WHOLE_WAVE] + [s for s in self.slots if s not in WHOLE_WAVE]
+        first = [s for s in self.slots if self.count[s] == WAVE] + [s for s in self.slots if self.count[s] != WAVE]
         srt = np.concatenate([self.where(s) for s in first])
         frac = np.concatenate([(np.arange(self.count[s]) + 0.5) / self.count[s] for s in self.slots])
         mixed = np.lexsort((np.arange(self.M), frac))
@@ -247,7 +247,7 @@ def column_errors(a, b, n_rw):
     return worst
 
 
-def kept(cast, ref=None, report=None):
+def kept(cast, ref=None, report=None, sbr=False, lib=None, bits=0):
     """The either-way rule: the dead-band, the drop threshold, floor() and the friction sign are discontinuous, so a character
     whose ORACLE answer changes side under a relative 1e-13 change of its initial state decides nothing about a kernel.  The oracle
     runs again with the initial state scaled by 1 + 1e-13 and by 1 - 1e-13.  -> (M,) bool: False where, after any launch, either
@@ -261,19 +261,28 @@ def kept(cast, ref=None, report=None):
     f(+) + f(-) - 2 f(0): second order (1e-26 x curvature) for a smooth response, the full jump if either run crossed an edge.  That
     is held to a tenth of the bounds.  The plain difference is reported (``report``: a dict that receives the worst of both, in
     units of the bounds): it is the casts' conditioning - a few bounds at most, that is a gain below 100 on a relative 1e-13, under
-    which the kernels' own rounding (1e-16) stays four orders below the bounds."""
+    which the kernels' own rounding (1e-16) stays four orders below the bounds.
+
+    tests/_guidance.py adds: ``sbr`` - the att_guidance message's |sigma_BR| (BSK_T_SBR) under the state bound as well; ``lib`` (a
+    branch-mask build) and ``bits`` - the three runs go through it (``ref`` carries ``mask``) and a kept character takes the same
+    branches among ``bits`` in all of them, launch by launch."""
     n_rw = cast.n_rw
     tail = _lib.NF_BASE + n_rw
-    ref = cast.run_oracle() if ref is None else ref
+    ref = (cast.run_oracle() if lib is None else cast.run_oracle(lib=lib)) if ref is None else ref
     ok = np.ones(cast.M, bool)
     ints = slice(tail + _lib.T_THR_LIM, tail + _lib.T_THR_CNT + 1)
     rem = slice(tail + _lib.T_THR_REM, tail + _lib.T_THR_REM + 8)
     cmds = [slice(tail + f, tail + f + 4) for f in (_lib.T_UCMD, _lib.T_UPEND)]
-    plus, minus = cast.run_oracle(scale=1.0 + 1e-13), cast.run_oracle(scale=1.0 - 1e-13)
+    if sbr:
+        cmds = cmds + [slice(tail + _lib.T_SBR, tail + _lib.T_SBR + 1)]         # (CMD_BOUND is the state bound)
+    kw = {} if lib is None else {"lib": lib}
+    plus, minus = cast.run_oracle(scale=1.0 + 1e-13, **kw), cast.run_oracle(scale=1.0 - 1e-13, **kw)
     worst = {"plain": 0.0, "symmetric": 0.0}
     for p, m, b in zip(plus, minus, ref):
         for a in (p, m):
             ok &= (a["reason"] == b["reason"]) & (a["state"][ints] == b["state"][ints]).all(axis=0)
+            if lib is not None:
+                ok &= (a["mask"] & np.uint32(bits)) == (b["mask"] & np.uint32(bits))
         for get, bound in ([lambda x, y: column_errors(x, y, n_rw)], STATE_BOUND), ([lambda x, y: np.abs(x[rem] - y[rem]).max(axis=0)], REM_BOUND), \
                 ([lambda x, y, c=c: np.abs(x[c] - y[c]).max(axis=0) for c in cmds], CMD_BOUND):
             for fn in get:
@@ -286,11 +295,15 @@ def kept(cast, ref=None, report=None):
     return ok
 
 
-def check_cap(cast, ok):
-    """At most 2 % left out, every slot keeps 12 of 16 (48 of 64) -> the share left out"""
-    share = 1.0 - ok.mean()
+def check_cap(cast, ok, exempt=()):
+    """At most 2 % left out, every slot keeps 12 of 16 (48 of 64) -> the share left out.  ``exempt``: slots of edge characters by
+    construction (tests/_guidance.py: ``tie``), which count in neither."""
+    counted = ~np.isin(cast.slot, exempt)
+    share = 1.0 - ok[counted].mean()
     assert share <= 0.02, (cast.kind, share)
     for s in cast.slots:
+        if s in exempt:
+            continue
         w = cast.where(s)
         assert ok[w].sum() >= 0.75 * w.size, (cast.kind, s, int(ok[w].sum()), w.size)
     return share
@@ -388,25 +401,27 @@ WHEEL_FORMS, DESAT_FORMS = _forms()
 _CASTS = {}
 
 
-def cast_for(kind, form):
-    """(cfg, Cast, row) of one entry of WHEEL_FORMS / DESAT_FORMS; built once per session (casts of equal configs are shared)"""
+def cast_for(kind, form, forms=None, edit=None, make=None):
+    """(cfg, Cast, row) of one entry of WHEEL_FORMS / DESAT_FORMS; built once per session (casts of equal configs are shared).
+    tests/_guidance.py passes its own table of ``forms``, config ``edit`` and cast class ``make``."""
     import test_gpu_kernel_info as KI
     from basilisk_env_amd._lib import GRAV_SH
     from helpers import visible_sh_coefficients
-    row = (WHEEL_FORMS if kind == "wheel" else DESAT_FORMS)[form]
+    row = (forms if forms is not None else WHEEL_FORMS if kind == "wheel" else DESAT_FORMS)[form]
+    edit = (desat_config if kind == "desat" else None) if edit is None else edit
     grav, n_rw, level, diag, _, _, _, nav, _ = row
     key = (kind, grav, n_rw, "bare" if level == "ldss" else level, diag, nav)
     cfg = KI.config(grav, n_rw, level, diag)
     cfg.nav_lag = nav
-    if kind == "desat":
-        desat_config(cfg)
+    if edit is not None:
+        edit(cfg)
     if key not in _CASTS:
         ref_cfg = KI.config(grav, n_rw, "bare" if level == "ldss" else level, diag)       # (the LDS-scratch flag changes no arithmetic)
         ref_cfg.nav_lag = nav
-        if kind == "desat":
-            desat_config(ref_cfg)
+        if edit is not None:
+            edit(ref_cfg)
         sh = visible_sh_coefficients(ref_cfg.sh_degree, seed=3) if grav == GRAV_SH else (None, None)
-        _CASTS[key] = Cast(ref_cfg, kind, sh)
+        _CASTS[key] = (Cast if make is None else make)(ref_cfg, kind, sh)
     return cfg, _CASTS[key], row
 
 
