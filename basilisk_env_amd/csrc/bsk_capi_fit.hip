@@ -1,6 +1,7 @@
 // bsk_capi_fit.hip — C-ABI of the supervised fit of a policy to labelled observations (bsk_fit_*): accumulate block gradients of a
 // cross-entropy (and, optionally, a squared value error) from device buffers, then one Adam step into the attached policy's own
-// parameters.  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_fit.hip.  The policy it reads and writes through
+// parameters; the same with a clipped policy-gradient loss in the cross-entropy's place (bsk_fit_accumulate_pg), and the advantage
+// estimator that feeds it from rollout histories (bsk_gae).  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_fit.hip.  The policy it reads and writes through
 // its handle: bsk_capi_policy.hpp.
 #include <cmath>
 
@@ -9,8 +10,9 @@
 
 using namespace bsk::capi;
 
-// bsk_fit_*: ONE allocation of 8-byte words [theta np | m np | v np | beta_pow 2 | A np | row 4 | count | steps] and, from the first
-// accumulate on, the scratch of the block gradients: [G n_blocks * np floats | diag n_blocks * 4 doubles]
+// bsk_fit_*: ONE allocation of 8-byte words [theta np | m np | v np | beta_pow 2 | A np | row 4 | count | steps | pg_row 4] and, from
+// the first accumulate on, the scratch of the block gradients: [G n_blocks * np floats | diag n_blocks * 8 doubles | lp 3 * 64
+// n_blocks floats] (a supervised launch uses the first 4 n_blocks of diag and no lp)
 struct bsk_fit {
     bsk_policy* policy = nullptr;          // not owned: what accumulate reads and step writes
     int device = 0;
@@ -30,7 +32,8 @@ struct bsk_fit {
     double* row() const { return d_state + 4 * np() + 2; }
     unsigned long long* count() const { return (unsigned long long*)(d_state + 4 * np() + 6); }
     unsigned long long* steps() const { return count() + 1; }
-    size_t words() const { return 4 * np() + 8; }
+    double* pg_row() const { return d_state + 4 * np() + 8; }
+    size_t words() const { return 4 * np() + 12; }
     // where the action network's parameters end in the C-ABI block: all a fit without value targets folds and moves
     int action_end() const {
         const bsk::PolicyLayout& lay = policy->lay;
@@ -46,6 +49,68 @@ bool finite_nonneg(double x) { return std::isfinite(x) && x >= 0.0; }
 int write_policy(bsk_fit* f, hipStream_t s) {
     HIP_TRY(bsk::launch_es_center(f->policy->lay, f->theta(), f->policy->d_params, 1, s));
     return BSK_OK;
+}
+
+// the policy-gradient arguments of an accumulate (bsk_fit_accumulate_pg), already checked
+struct PgLoss {
+    const float* adv;
+    const float* logp_old;
+    float hi, lo, ec;
+};
+
+// bsk_fit_accumulate (pg == nullptr) and bsk_fit_accumulate_pg: the block launch in either form, then the fold
+int accumulate(bsk_fit* f, const double* d_obs, int64_t obs_stride, int n, const int32_t* d_label, const double* d_value_target,
+               const uint8_t* d_alive, float* d_dlogits, int64_t out_stride, const PgLoss* pg, void* stream) {
+    if (n < 1 || n > (1 << 28)) return fail(BSK_EINVAL, "bsk_fit_accumulate: n must be in 1..2^28");
+    if (obs_stride < n) return fail(BSK_EINVAL, "bsk_fit_accumulate: obs_stride must be >= n");
+    if (d_dlogits && out_stride < n) return fail(BSK_EINVAL, "bsk_fit_accumulate: out_stride must be >= n");
+    const bsk::PolicyLayout& lay = f->policy->lay;
+    if (d_value_target && lay.v.n_layers == 0) return fail(BSK_EINVAL, "bsk_fit_accumulate: d_value_target given, but the policy has no value network");
+    DeviceGuard guard(f->device);
+    const hipStream_t s = (hipStream_t)stream;
+    const int n_blocks = (n + bsk::FIT_BLOCK_SAMPLES - 1) / bsk::FIT_BLOCK_SAMPLES;
+    const size_t np = f->np();
+    if (f->blocks_cap < n_blocks) {
+        const size_t g_bytes = ((size_t)n_blocks * np * sizeof(float) + 15) / 16 * 16;
+        int rc = grow_scratch(&f->d_scratch, &f->blocks_cap, g_bytes + (size_t)n_blocks * (8 * sizeof(double) + 3 * bsk::FIT_BLOCK_SAMPLES * sizeof(float)), s,
+                              "bsk_fit_accumulate: the first accumulate of a size allocates the scratch of the block gradients and cannot be "
+                              "captured; make one such call outside the capture first");
+        if (rc) return rc;
+        f->blocks_cap = n_blocks;
+    }
+    const size_t g_bytes = ((size_t)f->blocks_cap * np * sizeof(float) + 15) / 16 * 16;
+    const bsk::PolicyPackMap map = bsk::policy_pack_map(lay);
+    bsk::FitArgs a = {};
+    a.params = f->policy->d_params;
+    a.a = bsk::fit_net(map, 0, lay.a);
+    if (d_value_target) a.v = bsk::fit_net(map, lay.a.n_layers, lay.v);
+    a.obs = d_obs; a.obs_stride = obs_stride; a.n = n;
+    a.label = d_label; a.target = d_value_target; a.alive = d_alive;
+    a.value_coef = f->value_coef;
+    a.dlogits = d_dlogits; a.out_stride = out_stride;
+    a.G = (float*)f->d_scratch;
+    a.diag = (double*)((char*)f->d_scratch + g_bytes);
+    a.n_params = lay.n_params;
+    a.rows = bsk::fit_lds_rows(lay);
+    const int n_fold = d_value_target ? lay.n_params : f->action_end();
+    if (pg) {
+        a.adv = pg->adv; a.logp_old = pg->logp_old;
+        a.clip_hi = pg->hi; a.clip_lo = pg->lo; a.ent_coef = pg->ec;
+        // the log-probabilities of the three actions, formed where policy_kernel forms its logp: one launch in front
+        float* lp = (float*)((char*)f->d_scratch + g_bytes + (size_t)f->blocks_cap * 8 * sizeof(double));
+        bsk::PolicyLogpArgs la = {};
+        la.params = f->policy->d_params; la.a = lay.a; la.obs = d_obs; la.obs_stride = obs_stride; la.n = n; la.lp = lp;
+        la.width = lay.width;
+        HIP_TRY(bsk::launch_policy_logp(la, s));
+        a.lp = lp;
+        HIP_TRY(bsk::launch_fit_blocks_pg(a, s));
+        HIP_TRY(bsk::launch_fit_fold_pg(a.G, a.diag, n_blocks, lay.n_params, n_fold, f->A(), f->row(), f->pg_row(), f->count(), s));
+    } else {
+        HIP_TRY(bsk::launch_fit_blocks(a, s));
+        HIP_TRY(bsk::launch_fit_fold(a.G, a.diag, n_blocks, lay.n_params, n_fold, f->A(), f->row(), f->count(), s));
+    }
+    if (d_value_target) f->value_seen = true;
+    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
 }
 
 }  // namespace
@@ -96,42 +161,34 @@ void bsk_fit_destroy(bsk_fit* f) {
 int bsk_fit_accumulate(bsk_fit* f, const double* d_obs, int64_t obs_stride, int n, const int32_t* d_label, const double* d_value_target,
                        const uint8_t* d_alive, float* d_dlogits, int64_t out_stride, void* stream) {
     if (!f || !d_obs || !d_label) return fail(BSK_EINVAL, "fit/d_obs/d_label is NULL");
-    if (n < 1 || n > (1 << 28)) return fail(BSK_EINVAL, "bsk_fit_accumulate: n must be in 1..2^28");
-    if (obs_stride < n) return fail(BSK_EINVAL, "bsk_fit_accumulate: obs_stride must be >= n");
-    if (d_dlogits && out_stride < n) return fail(BSK_EINVAL, "bsk_fit_accumulate: out_stride must be >= n");
-    const bsk::PolicyLayout& lay = f->policy->lay;
-    if (d_value_target && lay.v.n_layers == 0) return fail(BSK_EINVAL, "bsk_fit_accumulate: d_value_target given, but the policy has no value network");
-    DeviceGuard guard(f->device);
-    const hipStream_t s = (hipStream_t)stream;
-    const int n_blocks = (n + bsk::FIT_BLOCK_SAMPLES - 1) / bsk::FIT_BLOCK_SAMPLES;
-    const size_t np = f->np();
-    if (f->blocks_cap < n_blocks) {
-        const size_t g_bytes = ((size_t)n_blocks * np * sizeof(float) + 15) / 16 * 16;
-        int rc = grow_scratch(&f->d_scratch, &f->blocks_cap, g_bytes + (size_t)n_blocks * 4 * sizeof(double), s,
-                              "bsk_fit_accumulate: the first accumulate of a size allocates the scratch of the block gradients and cannot be "
-                              "captured; make one such call outside the capture first");
-        if (rc) return rc;
-        f->blocks_cap = n_blocks;
-    }
-    const size_t g_bytes = ((size_t)f->blocks_cap * np * sizeof(float) + 15) / 16 * 16;
-    const bsk::PolicyPackMap map = bsk::policy_pack_map(lay);
-    bsk::FitArgs a = {};
-    a.params = f->policy->d_params;
-    a.a = bsk::fit_net(map, 0, lay.a);
-    if (d_value_target) a.v = bsk::fit_net(map, lay.a.n_layers, lay.v);
-    a.obs = d_obs; a.obs_stride = obs_stride; a.n = n;
-    a.label = d_label; a.target = d_value_target; a.alive = d_alive;
-    a.value_coef = f->value_coef;
-    a.dlogits = d_dlogits; a.out_stride = out_stride;
-    a.G = (float*)f->d_scratch;
-    a.diag = (double*)((char*)f->d_scratch + g_bytes);
-    a.n_params = lay.n_params;
-    a.rows = bsk::fit_lds_rows(lay);
-    HIP_TRY(bsk::launch_fit_blocks(a, s));
-    HIP_TRY(bsk::launch_fit_fold(a.G, a.diag, n_blocks, lay.n_params, d_value_target ? lay.n_params : f->action_end(), f->A(), f->row(),
-                                 f->count(), s));
-    if (d_value_target) f->value_seen = true;
-    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation
+    return accumulate(f, d_obs, obs_stride, n, d_label, d_value_target, d_alive, d_dlogits, out_stride, nullptr, stream);
+}
+
+int bsk_fit_accumulate_pg(bsk_fit* f, const double* d_obs, int64_t obs_stride, int n, const int32_t* d_action, const float* d_adv,
+                          const float* d_logp_old, double clip, double ent_coef, const double* d_value_target, const uint8_t* d_alive,
+                          float* d_dlogits, int64_t out_stride, void* stream) {
+    if (!f || !d_obs || !d_action || !d_adv) return fail(BSK_EINVAL, "fit/d_obs/d_action/d_adv is NULL");
+    if (d_logp_old && !(std::isfinite(clip) && clip > 0.0 && clip < 1.0))
+        return fail(BSK_EINVAL, "bsk_fit_accumulate_pg: clip must be in (0, 1) when d_logp_old is given");
+    if (!finite_nonneg(ent_coef)) return fail(BSK_EINVAL, "bsk_fit_accumulate_pg: ent_coef must be finite and not negative");
+    const PgLoss pg = {d_adv, d_logp_old, 1.0f + (float)clip, 1.0f - (float)clip, (float)ent_coef};
+    return accumulate(f, d_obs, obs_stride, n, d_action, d_value_target, d_alive, d_dlogits, out_stride, &pg, stream);
+}
+
+int bsk_fit_pg_stats_device(bsk_fit* f, const double** d_row4) {
+    if (!f || !d_row4) return fail(BSK_EINVAL, "fit/d_row4 is NULL");
+    *d_row4 = f->pg_row();
+    return BSK_OK;
+}
+
+int bsk_gae(const double* d_reward_hist, const uint8_t* d_reason_hist, const float* d_value_hist, const float* d_last_value, int n_steps,
+            int n_envs, int64_t stride, double gamma, double lambda, float* d_adv, double* d_ret, void* stream) {
+    if (!d_reward_hist || !d_reason_hist || !d_value_hist || !d_adv) return fail(BSK_EINVAL, "bsk_gae: a history or d_adv is NULL");
+    if (n_steps < 1 || n_envs < 1 || stride < n_envs) return fail(BSK_EINVAL, "bsk_gae: n_steps and n_envs must be >= 1, stride >= n_envs");
+    if (!(gamma >= 0.0 && gamma <= 1.0) || !(lambda >= 0.0 && lambda <= 1.0)) return fail(BSK_EINVAL, "bsk_gae: gamma and lambda must be in [0, 1]");
+    HIP_TRY(bsk::launch_gae(d_reward_hist, d_reason_hist, d_value_hist, d_last_value, n_steps, n_envs, stride, gamma, gamma * lambda, d_adv,
+                            d_ret, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream` of the current device: no copy, no synchronisation, no allocation
 }
 
 int bsk_fit_step(bsk_fit* f, void* stream) {
@@ -173,6 +230,7 @@ int bsk_fit_set_state(bsk_fit* f, const double* theta, const double* m, const do
     // what has been accumulated since the last step belongs to the state that is replaced: A, the count and the diagnostics row
     // (contiguous words) start from zero, as behind a step
     HIP_TRY(hipMemset(f->A(), 0, (f->np() + 5) * sizeof(double)));
+    HIP_TRY(hipMemset(f->pg_row(), 0, 4 * sizeof(double)));
     f->value_seen = false;
     if (theta && (rc = write_policy(f, nullptr))) return rc;          // a new theta is the policy's too: (float)theta
     HIP_SYNC(hipDeviceSynchronize());

@@ -2,7 +2,11 @@
 // include/bskgpu.h): cross-entropy on the action, an optional squared error on the value, Adam.
 //   fit_block_kernel    one workgroup per block of 64 samples: the policy's forward pass with every layer kept, the output deltas,
 //                       the backward sweep and the block's gradient G_b in the C-ABI parameter order, plus its diagnostics terms
+//                       <PG = true> (bsk_fit_accumulate_pg): the output deltas of the clipped policy-gradient loss with its
+//                       entropy bonus in the cross-entropy's place, and four more diagnostics terms; <false> is the supervised kernel
 //   fit_fold_kernel     one thread per parameter: A += (double)G_b, b ascending; four threads more for the diagnostics row
+//                       (<8>: eight, the policy-gradient row behind the first)
+//   gae_kernel          bsk_gae: one thread per env walks its column of the rollout histories from the last step to the first
 //   fit_adam_kernel     one thread per parameter: the mean gradient through Adam (adam_step, bsk_es.hpp: the text of the
 //                       evolution strategy's update), a descent
 //   fit_advance_kernel  one thread: beta_pow and the step counter move on, the count back to zero
@@ -29,6 +33,7 @@ namespace bsk {
 constexpr int FIT_X_ROWS = 8;
 constexpr int FIT_FOLD_BATCH = 32;     // block gradients the fold has in flight per thread
 constexpr int FIT_DIAG_ROWS = 5;       // behind the rows: two doubles and an int per sample, the terms of the block's diagnostics
+constexpr int FIT_PG_DIAG_ROWS = 8;    // behind those, policy-gradient launches only: four doubles more per sample
 
 __device__ __forceinline__ int fit_row(const FitNet& net, int l) {      // the first row of layer l's INPUT; l = n_layers: the output deltas
     int r = l == 0 ? 0 : FIT_X_ROWS;
@@ -151,12 +156,14 @@ __device__ __forceinline__ void fit_backward(const float* __restrict__ params, c
     }
 }
 
+template <bool PG>
 __global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p) {
     // (everything in the dynamic region and every carve a multiple of 16 bytes: a static array in front would shift its base)
     extern __shared__ __attribute__((aligned(16))) float fit_lds[];
     double* s_nll = (double*)(fit_lds + p.rows * POLICY_LANES);
     double* s_vl = s_nll + POLICY_LANES;
     int* s_flag = (int*)(s_vl + POLICY_LANES);     // bit 0: the sample contributes; bit 1: the greedy action is its label
+    double* s_pg = (double*)(s_flag + POLICY_LANES);        // (PG launches only) [4][lane]: -d, H, clipped, A * r
     const int lane = (int)(threadIdx.x & 63u);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t j = (int64_t)blockIdx.x * POLICY_LANES + lane;
@@ -192,12 +199,46 @@ __global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p
         float best = out[0];
         if (policy_beats(out[1], best)) { best = out[1]; a = 1; }
         if (policy_beats(out[2], best)) { best = out[2]; a = 2; }
-        const float logp = ((label == 0 ? out[0] : (label == 1 ? out[1] : out[2])) - m) - logf(s);
+        float logp;
         float gl[3] = {0.0f, 0.0f, 0.0f};
-        if (on) {
-            gl[0] = e0 / s - (label == 0 ? 1.0f : 0.0f);
-            gl[1] = e1 / s - (label == 1 ? 1.0f : 0.0f);
-            gl[2] = e2 / s - (label == 2 ? 1.0f : 0.0f);
+        if constexpr (PG) {
+            // the clipped surrogate's deltas (include/bskgpu.h, bsk_fit_accumulate_pg): `label` is the action taken.  p_i is the
+            // supervised kernel's, from this unit's e_i and s; lp_i is READ - policy_logp_kernel's, from the launch in front, which
+            // forms it in policy_kernel's own unit (bsk_policy.hpp, policy_softmax: this unit's expf and logf are not that one's)
+            const float pr[3] = {e0 / s, e1 / s, e2 / s};
+            float lp[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) lp[i] = live ? p.lp[(int64_t)i * p.n + j] : 0.0f;
+            logp = label == 0 ? lp[0] : (label == 1 ? lp[1] : lp[2]);
+            const float H = -((pr[0] * lp[0] + pr[1] * lp[1]) + pr[2] * lp[2]);
+            const float A = on ? p.adv[j] : 0.0f;
+            float d = 0.0f, r = 1.0f;
+            bool clipped = false;
+            if (p.logp_old) {                  // (workgroup-uniform)
+                d = logp - (on ? p.logp_old[j] : 0.0f);
+                r = expf(d);
+                clipped = (A > 0.0f && r > p.clip_hi) || (A < 0.0f && r < p.clip_lo);
+            }
+            const bool flat = clipped || A == 0.0f;          // c = +0.0f: the deltas are +0.0f, never the product's -0.0f
+            const float c = A * r;
+            if (on) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const float gp = flat ? 0.0f : c * (pr[i] - (label == i ? 1.0f : 0.0f));
+                    gl[i] = p.ent_coef == 0.0f ? gp : __builtin_fmaf(p.ent_coef, pr[i] * (lp[i] + H), gp);
+                }
+            }
+            s_pg[lane] = on ? -(double)d : 0.0;
+            s_pg[POLICY_LANES + lane] = on ? (double)H : 0.0;
+            s_pg[2 * POLICY_LANES + lane] = on && clipped ? 1.0 : 0.0;
+            s_pg[3 * POLICY_LANES + lane] = on ? (double)A * (double)r : 0.0;
+        } else {
+            logp = ((label == 0 ? out[0] : (label == 1 ? out[1] : out[2])) - m) - logf(s);
+            if (on) {
+                gl[0] = e0 / s - (label == 0 ? 1.0f : 0.0f);
+                gl[1] = e1 / s - (label == 1 ? 1.0f : 0.0f);
+                gl[2] = e2 / s - (label == 2 ? 1.0f : 0.0f);
+            }
         }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -236,7 +277,7 @@ __global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p
             count += s_flag[s] & 1;
             correct += (s_flag[s] >> 1) & 1;
         }
-        double* row = p.diag + 4 * (size_t)blockIdx.x;
+        double* row = p.diag + (PG ? 8 : 4) * (size_t)blockIdx.x;
         row[0] = nll;
         row[1] = vl;
 #if BSK_FIT_STAMPS
@@ -245,25 +286,35 @@ __global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p
 #endif
         row[2] = (double)correct;
         row[3] = (double)count;
+        if constexpr (PG) {                // the policy-gradient row's terms, in the same order
+            for (int k = 0; k < 4; ++k) {
+                double acc = 0.0;
+                for (int s = 0; s < POLICY_LANES; ++s) acc = acc + s_pg[k * POLICY_LANES + s];
+                row[4 + k] = acc;
+            }
+        }
     }
 }
 
+// W: the doubles of a block's diagnostics terms - 4, or 8 behind a policy-gradient launch, whose last four sums are pg_row's
+template <int W>
 __global__ __launch_bounds__(256) void fit_fold_kernel(const float* __restrict__ G, const double* __restrict__ diag, int n_blocks, int n_params,
                                                        int n_fold, double* __restrict__ A, double* __restrict__ row,
-                                                       unsigned long long* __restrict__ count) {
+                                                       unsigned long long* __restrict__ count, double* __restrict__ pg_row) {
     const int t = (int)(blockIdx.x * 256u + threadIdx.x);
-    if (t < 4) {                           // the diagnostics row: its four sums, block-ascending from +0.0
+    if (t < W) {                           // the diagnostics row: its four sums, block-ascending from +0.0
         double s = 0.0;
         int b = 0;
         for (; b + FIT_FOLD_BATCH <= n_blocks; b += FIT_FOLD_BATCH) {      // (fetched side by side, added in order: as below)
             double d[FIT_FOLD_BATCH];
 #pragma unroll
-            for (int i = 0; i < FIT_FOLD_BATCH; ++i) d[i] = diag[4 * (size_t)(b + i) + t];
+            for (int i = 0; i < FIT_FOLD_BATCH; ++i) d[i] = diag[W * (size_t)(b + i) + t];
 #pragma unroll
             for (int i = 0; i < FIT_FOLD_BATCH; ++i) s = s + d[i];
         }
-        for (; b < n_blocks; ++b) s = s + diag[4 * (size_t)b + t];
-        row[t] = s;
+        for (; b < n_blocks; ++b) s = s + diag[W * (size_t)b + t];
+        if (W == 4 || t < 4) row[t] = s;
+        else pg_row[t - 4] = s;
         if (t == 3) *count += (unsigned long long)s;
     }
     const int p = 10 + t;
@@ -311,6 +362,41 @@ __global__ __launch_bounds__(256) void fit_alive_kernel(const uint8_t* __restric
     if (j < n) alive[j] = first || (alive[j] != 0 && reason[j] == 0) ? 1 : 0;        // (first: neither array is read)
 }
 
+// bsk_gae: env j's column of the histories from the last step to the first, f64, every operation rounded on its own (no FMA: the
+// file's -ffp-contract=off).  A lane owns its env, so every load and store of a step is one coalesced row segment; no lane reads
+// what another wrote.
+__global__ __launch_bounds__(256) void gae_kernel(const double* __restrict__ reward, const uint8_t* __restrict__ reason,
+                                                  const float* __restrict__ value, const float* __restrict__ last_value, int n_steps,
+                                                  int n_envs, int64_t stride, double gamma, double gl, float* __restrict__ adv,
+                                                  double* __restrict__ ret) {
+    const int j = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (j >= n_envs) return;
+    double carry = 0.0;
+    double next_v = last_value ? (double)last_value[j] : 0.0;
+#pragma unroll 4
+    for (int t = n_steps - 1; t >= 0; --t) {
+        const int64_t at = (int64_t)t * stride + j;
+        const double v = (double)value[at];
+        const double rew = reward[at];
+        if (reason[at] == 0) {
+            const double delta = (rew + gamma * next_v) - v;
+            carry = delta + gl * carry;
+        } else {
+            carry = rew - v;
+        }
+        adv[at] = (float)carry;
+        if (ret) ret[at] = carry + v;
+        next_v = v;
+    }
+}
+
+hipError_t launch_gae(const double* reward, const uint8_t* reason, const float* value, const float* last_value, int n_steps, int n_envs,
+                      int64_t stride, double gamma, double gl, float* adv, double* ret, hipStream_t s) {
+    hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, s, reward, reason, value, last_value, n_steps,
+                       n_envs, stride, gamma, gl, adv, ret);
+    return hipGetLastError();
+}
+
 hipError_t launch_fit_alive(const uint8_t* reason, int n, int first, uint8_t* alive, hipStream_t s) {
     hipLaunchKernelGGL(fit_alive_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reason, n, first, alive);
     return hipGetLastError();
@@ -335,22 +421,34 @@ FitNet fit_net(const PolicyPackMap& map, int first, const PolicyNet& net) {
     return f;
 }
 
-hipError_t launch_fit_blocks(const FitArgs& args, hipStream_t s) {
-    const size_t lds = (size_t)(args.rows + FIT_DIAG_ROWS) * POLICY_LANES * sizeof(float);
+template <bool PG>
+static hipError_t launch_fit_blocks_as(const FitArgs& args, hipStream_t s) {
+    const size_t lds = (size_t)(args.rows + FIT_DIAG_ROWS + (PG ? FIT_PG_DIAG_ROWS : 0)) * POLICY_LANES * sizeof(float);
     if (lds > 48 * 1024) {                 // (idempotent, and cheap beside the launch: no per-device record to keep)
-        hipError_t e = hipFuncSetAttribute((const void*)&fit_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)&fit_block_kernel<PG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     const unsigned n_blocks = (unsigned)((args.n + FIT_BLOCK_SAMPLES - 1) / FIT_BLOCK_SAMPLES);
-    hipLaunchKernelGGL(fit_block_kernel, dim3(n_blocks), dim3(POLICY_BLOCK), lds, s, args);
+    hipLaunchKernelGGL(fit_block_kernel<PG>, dim3(n_blocks), dim3(POLICY_BLOCK), lds, s, args);
     return hipGetLastError();
 }
+
+hipError_t launch_fit_blocks(const FitArgs& args, hipStream_t s) { return launch_fit_blocks_as<false>(args, s); }
+hipError_t launch_fit_blocks_pg(const FitArgs& args, hipStream_t s) { return launch_fit_blocks_as<true>(args, s); }
 
 hipError_t launch_fit_fold(const float* G, const double* diag, int n_blocks, int n_params, int n_fold, double* A, double* row,
                            unsigned long long* count, hipStream_t s) {
     const int threads = n_fold - 10 > 4 ? n_fold - 10 : 4;
-    hipLaunchKernelGGL(fit_fold_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, G, diag, n_blocks, n_params, n_fold, A, row,
-                       count);
+    hipLaunchKernelGGL(fit_fold_kernel<4>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, G, diag, n_blocks, n_params, n_fold, A,
+                       row, count, (double*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_fit_fold_pg(const float* G, const double* diag, int n_blocks, int n_params, int n_fold, double* A, double* row,
+                              double* pg_row, unsigned long long* count, hipStream_t s) {
+    const int threads = n_fold - 10 > 8 ? n_fold - 10 : 8;
+    hipLaunchKernelGGL(fit_fold_kernel<8>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, G, diag, n_blocks, n_params, n_fold, A,
+                       row, count, pg_row);
     return hipGetLastError();
 }
 

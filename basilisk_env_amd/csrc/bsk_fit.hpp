@@ -1,5 +1,6 @@
 // bsk_fit.hpp — a supervised fit of the MLP policy on the device (bsk_fit.hip; internal): what bsk_fit_accumulate / bsk_fit_step
-// launch.  The arithmetic is the definition in include/bskgpu.h (bsk_fit_*).
+// launch, the policy-gradient form of the block kernel (bsk_fit_accumulate_pg) and the advantage estimator in front of it (bsk_gae).
+// The arithmetic is the definition in include/bskgpu.h (bsk_fit_*, bsk_gae).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,6 +36,11 @@ struct FitArgs {
     double* diag;                  // [n_blocks][4]: the block's terms of the diagnostics row
     int n_params;
     int rows;                      // fit_lds_rows
+    // the policy-gradient launch alone (launch_fit_blocks_pg; `label` is then the action taken, `diag` [n_blocks][8])
+    const float* adv;              // [n]
+    const float* logp_old;         // [n] or NULL: no ratio, no clipping
+    const float* lp;               // [3][n]: the log-probabilities of the three actions, policy_logp_kernel's
+    float clip_hi, clip_lo, ent_coef;      // 1.0f + (float)clip, 1.0f - (float)clip, (float)ent_coef
 };
 
 // LDS rows of 64 floats the block kernel needs for this layout: the input, every hidden layer of the larger network, the output deltas
@@ -43,9 +49,17 @@ FitNet fit_net(const PolicyPackMap& map, int first, const PolicyNet& net);
 
 // One workgroup per 64 samples: forward, output deltas, backward, the block's gradient and diagnostics terms
 hipError_t launch_fit_blocks(const FitArgs& args, hipStream_t s);
+// The same with the policy-gradient output deltas in the cross-entropy's place, and eight diagnostics terms per block
+hipError_t launch_fit_blocks_pg(const FitArgs& args, hipStream_t s);
 // A[p] += (double)G[b][p] for b ascending, p in 10 .. n_fold - 1; the diagnostics row out of the block terms; count += row[3]
 hipError_t launch_fit_fold(const float* G, const double* diag, int n_blocks, int n_params, int n_fold, double* A, double* row,
                            unsigned long long* count, hipStream_t s);
+// The same over block terms of eight: the first four into `row` as above, the last four into `pg_row`
+hipError_t launch_fit_fold_pg(const float* G, const double* diag, int n_blocks, int n_params, int n_fold, double* A, double* row,
+                              double* pg_row, unsigned long long* count, hipStream_t s);
+// Generalised advantage estimation over rollout histories [n_steps][stride]: one thread per env, t descending
+hipError_t launch_gae(const double* reward, const uint8_t* reason, const float* value, const float* last_value, int n_steps, int n_envs,
+                      int64_t stride, double gamma, double gl, float* adv, double* ret, hipStream_t s);
 // Adam on g = A / count + weight_decay * theta for p in 10 .. n_upd - 1 (descent; nothing while count == 0), A zeroed; then one
 // thread: beta_pow and the step counter move on, count = 0
 hipError_t launch_fit_step(double* theta, double* A, unsigned long long* count, unsigned long long* steps, int n_upd, const EsAdam& ad,

@@ -57,8 +57,9 @@ __device__ __forceinline__ void policy_eval(const PolicyArgs& p, const float* __
     if (wave != 0) return;                 // (no barrier from here on)
 
     const float m = fmaxf(fmaxf(l[0], l[1]), l[2]);
-    const float e0 = expf(l[0] - m), e1 = expf(l[1] - m), e2 = expf(l[2] - m);
-    const float s = (e0 + e1) + e2;
+    float e[3];
+    const float s = policy_softmax(l, m, e);
+    const float e0 = e[0], e1 = e[1], e2 = e[2];
     int a = 0;
     if (p.mode == BSK_POLICY_SAMPLE) {
         const unsigned long long seed = p.rng[0], draw = p.rng[1], env = p.env_base + (unsigned long long)j;
@@ -74,7 +75,7 @@ __device__ __forceinline__ void policy_eval(const PolicyArgs& p, const float* __
     }
     if (!live) return;
     p.action[j] = a;
-    if (p.logp) p.logp[j] = ((a == 0 ? l[0] : (a == 1 ? l[1] : l[2])) - m) - logf(s);
+    if (p.logp) p.logp[j] = policy_logp(a == 0 ? l[0] : (a == 1 ? l[1] : l[2]), m, s);
     if (p.value) p.value[j] = val[0];
     if (p.logits) {
 #pragma unroll
@@ -108,6 +109,32 @@ __global__ __launch_bounds__(POLICY_BLOCK) void policy_value_kernel(const Policy
     if (wave == 0 && live) p.value[j] = val[0];            // (tail lanes write nothing)
 }
 
+// The log-probabilities of all three actions (bsk_fit_accumulate_pg reads those of the actions taken): policy_eval's geometry and
+// its device functions once more - the action network, then steps 5 and 6 in policy_eval's own text and this unit's own arithmetic
+// mode - so that lp[a][j] is, bit for bit, the logp policy_kernel writes when it chooses a.  Touches nothing of the policy's
+// single-stream state.
+__global__ __launch_bounds__(POLICY_BLOCK) void policy_logp_kernel(const PolicyLogpArgs p) {
+    extern __shared__ float policy_lds[];
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));       // (wave-uniform: weight addresses stay scalar)
+    const int64_t j = (int64_t)blockIdx.x * POLICY_LANES + lane;
+    const bool live = j < p.n;
+    float x[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {                          // (step 1 of the definition, as policy_eval writes it)
+        const double o = live && wave == 0 ? p.obs[(int64_t)i * p.obs_stride + j] : 0.0;       // (tail lanes read nothing)
+        x[i] = __builtin_fmaf((float)o, p.params[i], p.params[5 + i]);
+    }
+    float l[POLICY_OB] = {0.0f, 0.0f, 0.0f, 0.0f};
+    policy_net(p.params, p.a, x, policy_lds, policy_lds + p.width * POLICY_LANES, lane, wave, l);
+    if (wave != 0 || !live) return;                        // (no barrier from here on; tail lanes write nothing)
+    const float m = fmaxf(fmaxf(l[0], l[1]), l[2]);
+    float e[3];
+    const float s = policy_softmax(l, m, e);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p.lp[(int64_t)i * p.n + j] = policy_logp(l[i], m, s);
+}
+
 // The population form (bsk_population_act): workgroup b serves the same 64 spacecraft and takes the parameter block of member
 // b / wg_per_member, wg_per_member = envs_per_member / 64.  The block address depends on blockIdx alone, so it is as scalar as
 // p.params is above and policy_hidden's weight loads stay one scalar load of 16 consecutive floats: nothing else differs.
@@ -139,6 +166,12 @@ hipError_t launch_policy(const PolicyArgs& args, hipStream_t s) {
 hipError_t launch_policy_value(const PolicyValueArgs& args, hipStream_t s) {
     const size_t lds = (size_t)2 * args.width * POLICY_LANES * sizeof(float);
     hipLaunchKernelGGL(policy_value_kernel, dim3((unsigned)((args.n + POLICY_LANES - 1) / POLICY_LANES)), dim3(POLICY_BLOCK), lds, s, args);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_logp(const PolicyLogpArgs& args, hipStream_t s) {
+    const size_t lds = (size_t)2 * args.width * POLICY_LANES * sizeof(float);
+    hipLaunchKernelGGL(policy_logp_kernel, dim3((unsigned)((args.n + POLICY_LANES - 1) / POLICY_LANES)), dim3(POLICY_BLOCK), lds, s, args);
     return hipGetLastError();
 }
 

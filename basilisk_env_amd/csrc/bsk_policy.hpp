@@ -52,6 +52,17 @@ struct PolicyValueArgs {
     int width;                     // the layout's width (both networks'), as PolicyArgs::width
 };
 
+// What policy_logp_kernel takes: the action network alone, and where the three log-probabilities of every spacecraft go
+struct PolicyLogpArgs {
+    const float* params;           // device layout (PolicyLayout)
+    PolicyNet a;
+    const double* obs;             // [5][obs_stride]
+    int64_t obs_stride;
+    int n;
+    float* lp;                     // [3][n]
+    int width;                     // the layout's width, as PolicyArgs::width
+};
+
 // Host side of the layout: checks a spec, counts its C-ABI parameters, and repacks them for the device.
 struct PolicyLayout {
     PolicyNet a, v;
@@ -149,9 +160,24 @@ __device__ __forceinline__ bool policy_beats(float a, float b) {      // a (the 
     return !na && a > b;
 }
 
+// Steps 5 and 6 of the definition: e_i = expf(l_i - m), s = (e_0 + e_1) + e_2 -> s, and the log-probability (l_i - m) - logf(s).
+// One text for policy_kernel and policy_logp_kernel.  It must also be compiled in ONE unit: the compiler expands expf and logf into
+// compensated products whose last subtraction / addition it fuses or not with the unit's contraction mode, which moves s and logp
+// in their last bit - so bsk_fit.hip, built without contraction, reads these log-probabilities from policy_logp_kernel instead of
+// forming them itself.
+__device__ __forceinline__ float policy_softmax(const float* l, float m, float* e) {
+    e[0] = expf(l[0] - m);
+    e[1] = expf(l[1] - m);
+    e[2] = expf(l[2] - m);
+    return (e[0] + e[1]) + e[2];
+}
+__device__ __forceinline__ float policy_logp(float l_i, float m, float s) { return (l_i - m) - logf(s); }
+
 hipError_t launch_policy(const PolicyArgs& args, hipStream_t s);
 // the value network alone, policy_kernel's value bit for bit: reads the parameters and the observations, writes value[0 .. n)
 hipError_t launch_policy_value(const PolicyValueArgs& args, hipStream_t s);
+// lp[i][j] = (l_i - m) - logf(s) of spacecraft j, i = 0 .. 2: for ANY action what policy_kernel writes as the logp of its own, bit for bit
+hipError_t launch_policy_logp(const PolicyLogpArgs& args, hipStream_t s);
 // The population form: args.params holds one device block of n_device floats per member, spacecraft j runs member
 // j / envs_per_member; envs_per_member is a multiple of 64 and args.n a multiple of envs_per_member.
 hipError_t launch_policy_population(const PolicyArgs& args, int envs_per_member, int n_device, hipStream_t s);

@@ -6,7 +6,13 @@ Adam update of a float64 master copy of the parameters, written back into the po
 two is enqueued on one stream with no copy and no synchronisation, so a planner's ``d_best_action`` can be the labels with no host
 in between (``planning.distill``) and the pair can be captured into a HIP graph.  The arithmetic is a fixed order of float32 fused
 multiply-adds and float64 sums; ``policy_ref`` restates it (``fit_backward_ref``, ``fit_accumulate_ref``, ``fit_step_ref``).
-Reached as ``basilisk_env_amd.policy.PolicyFit``."""
+Reached as ``basilisk_env_amd.policy.PolicyFit``.
+
+``accumulate_pg`` is the same launches - and one in front, in which the policy's own code forms the log-probabilities - with the
+output deltas of a clipped policy-gradient loss (PPO; A2C without old log-probabilities) and an entropy bonus in the
+cross-entropy's place (``bsk_fit_accumulate_pg``), ``gae`` the advantage estimator
+over a rollout's histories (``bsk_gae``), and ``PolicyGradient`` the training loop made of them - rollout, advantages, epochs of
+minibatch steps - with no host in it.  Reached as ``basilisk_env_amd.policy.gae`` / ``.PolicyGradient``."""
 import ctypes as C
 
 import numpy as np
@@ -14,7 +20,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .policy_base import _DeviceObject, _host_block
-from .policy_ref import FIT_STATS_COLUMNS, check_fit, check_fit_batch
+from .policy_ref import FIT_STATS_COLUMNS, PG_STATS_COLUMNS, check_fit, check_fit_batch, check_gae, check_pg, check_pg_loop
 from .policy_spec import n_params
 
 
@@ -66,6 +72,15 @@ class PolicyFit(_DeviceObject):
         ``alive``: n bytes or None, a zero byte takes the sample out, as a label outside 0..2 does; ``dlogits``: float32 (3, n)
         the output deltas are also written to, or None.  Each a raw device pointer or anything with
         ``__cuda_array_interface__``; arrays are kept alive until the next call."""
+        obs_ptr, stride, n, lab, tgt, liv, dl = self._batch(obs, labels, value_targets, alive, dlogits, n, stride, "labels")
+        vp = lambda p: C.c_void_p(p) if p else None      # noqa: E731
+        handle = self._handle()
+        self._kept = (obs, labels, value_targets, alive, dlogits)          # (the launches read them after this call returns)
+        check(self._lib.bsk_fit_accumulate(handle, vp(obs_ptr), stride, n, vp(lab), vp(tgt), vp(liv), vp(dl), n,
+                                           C.c_void_p(int(stream or 0))))
+
+    def _batch(self, obs, labels, value_targets, alive, dlogits, n, stride, noun):
+        """The pointer and array rules of ``accumulate`` -> (obs pointer, stride, n, labels, targets, alive, dlogits pointers)"""
         cai = getattr(obs, "__cuda_array_interface__", None)
         if cai is not None:
             shape, strides = tuple(cai["shape"]), cai.get("strides")
@@ -80,20 +95,37 @@ class PolicyFit(_DeviceObject):
         else:
             obs_ptr = int(obs)
         stride = int(n) if stride is None else int(stride)
-        lab, lab_n, _ = _pointer(labels, ("<i4",), "labels")
+        lab, lab_n, _ = _pointer(labels, ("<i4",), noun)
         tgt, tgt_n, _ = _pointer(value_targets, ("<f8",), "value targets")
         liv, liv_n, _ = _pointer(alive, ("|u1", "|b1"), "alive")
         dl, _, dl_shape = _pointer(dlogits, ("<f4",), "dlogits")
         n = check_fit_batch(self.policy.spec, n, lab_n, tgt_n if tgt_n is not None else (n if tgt else None), liv_n)
         if lab is None:
-            raise ValueError("labels are required")
+            raise ValueError("%s are required" % noun)
         if dl_shape is not None and dl_shape != (3, n):
             raise ValueError("dlogits: a float32 device array of shape (3, %d), got %r" % (n, dl_shape))
+        return obs_ptr, stride, n, lab, tgt, liv, dl
+
+    def accumulate_pg(self, obs, actions, advantages, logp_old=None, clip=0.2, ent_coef=0.0, value_targets=None, alive=None,
+                      dlogits=None, n=None, stride=None, stream=0):
+        """``accumulate`` with the policy-gradient output deltas (``bsk_fit_accumulate_pg``; three launches): ``actions`` int32 (n,) - the actions
+        taken, in the labels' place -, ``advantages`` float32 (n,) and ``logp_old`` float32 (n,), the log-probabilities the actions
+        were taken with, or None (A2C: no ratio, no clipping; ``clip`` is then not read).  ``ent_coef``: the weight of the entropy
+        bonus.  Everything else, the pointer and array rules included, is ``accumulate``'s; ``pg_stats`` has the row it adds."""
+        obs_ptr, stride, n, act, tgt, liv, dl = self._batch(obs, actions, value_targets, alive, dlogits, n, stride, "actions")
+        adv, adv_n, _ = _pointer(advantages, ("<f4",), "advantages")
+        old, old_n, _ = _pointer(logp_old, ("<f4",), "old log-probabilities")
+        if adv is None:
+            raise ValueError("advantages are required")
+        for what, size in (("advantages", adv_n), ("old log-probabilities", old_n)):
+            if size is not None and size != n:
+                raise ValueError("%s: %d elements, got %d" % (what, n, size))
+        clip, ent_coef = check_pg(clip, ent_coef, old is not None)
         vp = lambda p: C.c_void_p(p) if p else None      # noqa: E731
         handle = self._handle()
-        self._kept = (obs, labels, value_targets, alive, dlogits)          # (the launches read them after this call returns)
-        check(self._lib.bsk_fit_accumulate(handle, vp(obs_ptr), stride, n, vp(lab), vp(tgt), vp(liv), vp(dl), n,
-                                           C.c_void_p(int(stream or 0))))
+        self._kept = (obs, actions, advantages, logp_old, value_targets, alive, dlogits)
+        check(self._lib.bsk_fit_accumulate_pg(handle, vp(obs_ptr), stride, n, vp(act), vp(adv), vp(old), clip, ent_coef, vp(tgt), vp(liv),
+                                              vp(dl), n, C.c_void_p(int(stream or 0))))
 
     def step(self, stream=0):
         """One Adam step of the mean gradient since the last one, then float32(theta) into the policy: three launches on
@@ -107,17 +139,35 @@ class PolicyFit(_DeviceObject):
         check(self._lib.bsk_fit_stats_device(self._handle(), C.byref(p)))
         return p.value
 
-    def stats(self):
-        """The last ``accumulate``'s row -> dict by ``FIT_STATS_COLUMNS``: ``nll_sum`` (the summed cross-entropy), ``value_loss_sum``
-        (the summed 0.5 (v - target)^2), ``correct`` (samples whose greedy action is the label) and ``count`` (samples that
-        contributed).  A host read: synchronises."""
+    def pg_stats_ptr(self):
+        """The policy-gradient row of the last ``accumulate_pg`` as a DEVICE pointer to 4 float64, valid until ``close``."""
+        p = C.c_void_p()
+        check(self._lib.bsk_fit_pg_stats_device(self._handle(), C.byref(p)))
+        return p.value
+
+    def _row(self, ptr):
         from . import _hip
         row = np.empty(4, np.float64)
         self.sync()                                # (everything queued has written the row)
         with _hip.device_guard(self.device):
-            _hip.check(_hip.runtime().hipMemcpyAsync(C.c_void_p(row.ctypes.data), C.c_void_p(self.stats_ptr()), row.nbytes,
+            _hip.check(_hip.runtime().hipMemcpyAsync(C.c_void_p(row.ctypes.data), C.c_void_p(ptr), row.nbytes,
                                                      _hip.hipMemcpyDeviceToHost, None), "hipMemcpyAsync")
         self.sync()
+        return row
+
+    def pg_stats(self):
+        """The last ``accumulate_pg``'s row -> dict by ``PG_STATS_COLUMNS``: ``kl_sum`` (the summed old minus new log-probability of
+        the actions taken, an estimate of the KL divergence from the old policy; 0 without ``logp_old``), ``entropy_sum``,
+        ``clipped`` (samples whose ratio left the clip range on the side that zeroes their gradient) and ``surrogate_sum`` (the
+        summed advantage times ratio).  A host read: synchronises."""
+        row = self._row(self.pg_stats_ptr())
+        return dict(zip(PG_STATS_COLUMNS, (row[0], row[1], int(row[2]), row[3])))
+
+    def stats(self):
+        """The last ``accumulate``'s row -> dict by ``FIT_STATS_COLUMNS``: ``nll_sum`` (the summed cross-entropy), ``value_loss_sum``
+        (the summed 0.5 (v - target)^2), ``correct`` (samples whose greedy action is the label) and ``count`` (samples that
+        contributed).  A host read: synchronises."""
+        row = self._row(self.stats_ptr())
         return dict(zip(FIT_STATS_COLUMNS, (row[0], row[1], int(row[2]), int(row[3]))))
 
     def state(self):
@@ -147,3 +197,136 @@ class PolicyFit(_DeviceObject):
         value = check_fit(value, *self.adam, self.value_coef)[0]
         check(self._lib.bsk_fit_set_lr(self._handle(), value))
         self._lr = value
+
+
+def gae(reward_hist, reason_hist, value_hist, last_value, n_steps, n_envs, adv, ret=None, gamma=0.99, lam=0.95, stride=None, stream=0):
+    """``bsk_gae``: generalised advantage estimation over the histories of a rollout, one launch on ``stream`` of the current device,
+    no copy, no synchronisation, no allocation.  Each array a raw device pointer or anything with ``__cuda_array_interface__``:
+    ``reward_hist`` float64, ``reason_hist`` uint8 and ``value_hist`` float32 [n_steps][stride] (``stride`` defaults to
+    ``n_envs``), ``last_value`` float32 [n_envs] or None (= 0), ``adv`` float32 and ``ret`` float64 (or None) [n_steps][stride].
+    Every non-zero reason byte - the time limit included - ends the episode for the estimator (``policy_ref.gae_ref``)."""
+    n_steps, n_envs, stride, gamma, lam = check_gae(n_steps, n_envs, n_envs if stride is None else stride, gamma, lam)
+    ptrs = []
+    for x, types, what, need in ((reward_hist, ("<f8",), "reward history", n_steps * stride), (reason_hist, ("|u1", "|b1"), "reason history", n_steps * stride),
+                                 (value_hist, ("<f4",), "value history", n_steps * stride), (last_value, ("<f4",), "last value", n_envs),
+                                 (adv, ("<f4",), "advantages", n_steps * stride), (ret, ("<f8",), "returns", n_steps * stride)):
+        ptr, size, _ = _pointer(x, types, what)
+        if size is not None and size < need:
+            raise ValueError("%s: at least %d elements, got %d" % (what, need, size))
+        ptrs.append(C.c_void_p(ptr) if ptr else None)
+    check(_lib.load().bsk_gae(ptrs[0], ptrs[1], ptrs[2], ptrs[3], n_steps, n_envs, stride, gamma, lam, ptrs[4], ptrs[5],
+                              C.c_void_p(int(stream or 0))))
+
+
+class PolicyGradient(object):
+    """On-device policy-gradient training (PPO; the clipped surrogate of ``bsk_fit_accumulate_pg`` on advantages from ``bsk_gae``):
+    ``env`` - a ``BatchedPropagator`` (or an env over one) created with ``FLAG_AUTO_RESET`` -, ``policy`` - a ``DevicePolicy`` with a
+    value network - and ``fit``, the ``PolicyFit`` attached to it.  ``iterate()`` is ``collect()`` - ``n_steps`` env steps of
+    ``substeps`` under the sampled policy, then values and advantages - and ``update()`` - ``epochs`` passes over ``minibatches``
+    groups of consecutive time rows, one ``accumulate_pg`` per row and one Adam step per group.  Everything is enqueued on the
+    env's stream from buffers allocated here: neither allocates, copies to or from the host or synchronises; ``iterate`` waits
+    once, at its end, for the log.  ``close()`` frees the buffers (not the env, the policy or the fit)."""
+
+    def __init__(self, env, policy, fit, n_steps, gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, epochs=4, minibatches=4, substeps=1):
+        from . import _hip
+        from ._lib import FLAG_AUTO_RESET
+        (self.n_steps, self.gamma, self.lam, self.clip, self.ent_coef, self.epochs, self.minibatches,
+         self.substeps) = check_pg_loop(n_steps, gamma, lam, clip, ent_coef, epochs, minibatches, substeps)
+        prop = getattr(env, "propagator", env)
+        if not (prop.cfg.flags & FLAG_AUTO_RESET):
+            raise ValueError("the env must be created with FLAG_AUTO_RESET: episodes restart inside the rollout")
+        if policy.spec.value_hidden is None:
+            raise ValueError("the policy has no value network")
+        if fit.policy is not policy:
+            raise ValueError("the fit is attached to another policy")
+        if policy.device != prop.device:
+            raise ValueError("the policy lives on device %d, the propagator on device %d" % (policy.device, prop.device))
+        self.prop, self.policy, self.fit = prop, policy, fit
+        T, n = self.n_steps, prop.n_envs
+        self.n_envs = n
+        sizes = {"obs": 8 * (T + 1) * 5 * n, "reward": 8 * T * n, "reason": T * n, "action": 4 * T * n, "logp": 4 * T * n,
+                 "value": 4 * T * n, "last_value": 4 * n, "adv": 4 * T * n, "ret": 8 * T * n, "log": 64 * self.epochs * T}
+        self._buf = {k: _hip.DeviceBuffer(b, prop.device) for k, b in sizes.items()}
+        # Whatever a first launch would allocate, here: the fit's scratch of block gradients for n samples, by an accumulate of zeros in
+        # which no sample is alive - it adds +0.0 to every accumulator and nothing to the count.
+        b, stream = self._buf, prop.stream_ptr()
+        with _hip.device_guard(prop.device):
+            for k in ("obs", "action", "adv", "reason"):
+                _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(b[k].ptr), 0, sizes[k], C.c_void_p(stream)), "hipMemsetAsync")
+            fit.accumulate_pg(b["obs"].ptr, b["action"].ptr, b["adv"].ptr, None, self.clip, 0.0, None, b["reason"].ptr, n=n, stride=n,
+                              stream=stream)
+
+    def close(self):
+        if getattr(self, "_buf", None):
+            self.prop.sync()
+            for b in self._buf.values():
+                b.free()
+            self._buf = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def buffers(self):
+        """-> the device pointers of the loop's buffers by name: ``obs`` f64[n_steps + 1][5][n] (row t: what the action of step t
+        was chosen from), ``reward`` f64, ``reason`` u8, ``action`` i32, ``logp`` f32, ``value`` f32, ``adv`` f32, ``ret`` f64
+        [n_steps][n], ``last_value`` f32[n], ``log`` f64[epochs][n_steps][8] (the two diagnostics rows of every accumulate)"""
+        return {k: b.ptr for k, b in self._buf.items()}
+
+    def collect(self):
+        """The handle's observation into row 0, a sampled rollout of ``n_steps`` that fills the histories (observations from row 1),
+        the value of the observation the handle holds afterwards, and ``bsk_gae``: all enqueued on the env's stream."""
+        from . import _hip
+        prop, b, T, n = self.prop, self._buf, self.n_steps, self.n_envs
+        stream = prop.stream_ptr()
+        views = prop.device_views()
+        obs, stride = views["obs"].__cuda_array_interface__["data"][0], views["stride"]
+        with _hip.device_guard(prop.device):
+            _hip.memcpy2d_async(b["obs"].ptr, 8 * n, obs, 8 * stride, 8 * n, 5, _hip.hipMemcpyDeviceToDevice, stream)
+            self.policy.rollout_device(prop, T, self.substeps, "sample", b["obs"].ptr + 8 * 5 * n, b["reward"].ptr, b["reason"].ptr,
+                                       b["action"].ptr, b["logp"].ptr, b["value"].ptr)
+            self.policy.value_enqueue(obs, stride, n, b["last_value"].ptr, stream)
+            gae(b["reward"].ptr, b["reason"].ptr, b["value"].ptr, b["last_value"].ptr, T, n, b["adv"].ptr, b["ret"].ptr, self.gamma,
+                self.lam, stream=stream)
+
+    def update(self):
+        """``epochs`` passes of ``minibatches`` groups of consecutive time rows: per row one ``accumulate_pg`` of the n envs and its
+        two diagnostics rows into the log, device to device (a row is one accumulate's: ``iterate`` adds a group's on the host,
+        behind its wait); per group one ``fit.step()``."""
+        from . import _hip
+        prop, b, n, fit = self.prop, self._buf, self.n_envs, self.fit
+        stream, rows = prop.stream_ptr(), self.n_steps // self.minibatches
+        rt, vp = _hip.runtime(), C.c_void_p
+        pg_row, fit_row = fit.pg_stats_ptr(), fit.stats_ptr()
+        with _hip.device_guard(prop.device):
+            slot = 0
+            for _ in range(self.epochs):
+                for g in range(self.minibatches):
+                    for t in range(g * rows, (g + 1) * rows):
+                        fit.accumulate_pg(b["obs"].ptr + 8 * 5 * n * t, b["action"].ptr + 4 * n * t, b["adv"].ptr + 4 * n * t,
+                                          b["logp"].ptr + 4 * n * t, self.clip, self.ent_coef, b["ret"].ptr + 8 * n * t, None,
+                                          n=n, stride=n, stream=stream)
+                        for k, src in enumerate((pg_row, fit_row)):
+                            _hip.check(rt.hipMemcpyAsync(vp(b["log"].ptr + 64 * slot + 32 * k), vp(src), 32,
+                                                         _hip.hipMemcpyDeviceToDevice, vp(stream)), "hipMemcpyAsync")
+                        slot += 1
+                    fit.step(stream)
+
+    def iterate(self):
+        """``collect()`` then ``update()`` -> float64 (epochs * minibatches, 8): per minibatch ``PG_STATS_COLUMNS`` then
+        ``FIT_STATS_COLUMNS``, each the sum over the minibatch's rows in their order, formed after the one wait at the end."""
+        from . import _hip
+        out = np.empty((self.epochs * self.minibatches, self.n_steps // self.minibatches, 8), np.float64)
+        self.collect()
+        self.update()
+        with _hip.device_guard(self.prop.device):
+            _hip.check(_hip.runtime().hipMemcpyAsync(C.c_void_p(out.ctypes.data), C.c_void_p(self._buf["log"].ptr), out.nbytes,
+                                                     _hip.hipMemcpyDeviceToHost, C.c_void_p(self.prop.stream_ptr())), "hipMemcpyAsync")
+        self.prop.sync()
+        log = np.zeros((out.shape[0], 8), np.float64)
+        for k in range(out.shape[1]):
+            log = log + out[:, k]
+        return log

@@ -1185,3 +1185,194 @@ def fit_step_ref(theta, m, v, beta_pow, steps, A, count, lr, beta1, beta2, eps, 
         m[10:hi], v[10:hi], step, bp = _adam_step_ref(m[10:hi], v[10:hi], bp, g, lr, b1, b2, eps)
         theta[10:hi] = t - step
     return theta, m, v, bp, int(steps) + 1, np.zeros_like(A), 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Policy-gradient training on the fit (bsk_gae, bsk_fit_accumulate_pg; definition in include/bskgpu.h), restated
+
+PG_STATS_COLUMNS = ("kl_sum", "entropy_sum", "clipped", "surrogate_sum")
+
+
+def check_gae(n_steps, n_envs, stride, gamma, lam):
+    """The argument rules of ``bsk_gae`` that need no device -> (n_steps, n_envs, stride, gamma, lam); ValueError where it returns
+    BSK_EINVAL."""
+    for what, x in (("n_steps", n_steps), ("n_envs", n_envs), ("stride", stride)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
+            raise ValueError("%s must be an integer >= 1, got %r" % (what, x))
+    if stride < n_envs:
+        raise ValueError("stride must be >= n_envs")
+    gamma, lam = float(gamma), float(lam)
+    if not (0.0 <= gamma <= 1.0) or not (0.0 <= lam <= 1.0):
+        raise ValueError("gamma and lam must be in [0, 1]")
+    return int(n_steps), int(n_envs), int(stride), gamma, lam
+
+
+def check_pg(clip, ent_coef, with_logp_old=True):
+    """The argument rules ``bsk_fit_accumulate_pg`` adds to ``bsk_fit_accumulate``'s -> (clip, ent_coef) as floats; ValueError where
+    it returns BSK_EINVAL: ``clip`` finite and inside (0, 1) when old log-probabilities are given (otherwise it is not read),
+    ``ent_coef`` finite and not negative.  Needs no device."""
+    clip, ent_coef = float(clip), float(ent_coef)
+    if with_logp_old and not (np.isfinite(clip) and 0.0 < clip < 1.0):
+        raise ValueError("clip must be inside (0, 1) when old log-probabilities are given")
+    if not np.isfinite(ent_coef) or ent_coef < 0.0:
+        raise ValueError("ent_coef must be finite and not negative")
+    return clip, ent_coef
+
+
+def check_pg_loop(n_steps, gamma, lam, clip, ent_coef, epochs, minibatches, substeps):
+    """The argument rules of ``policy_fit.PolicyGradient`` that need neither env nor device -> the eight, checked."""
+    for what, x in (("n_steps", n_steps), ("epochs", epochs), ("minibatches", minibatches), ("substeps", substeps)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
+            raise ValueError("%s must be an integer >= 1, got %r" % (what, x))
+    if n_steps % minibatches:
+        raise ValueError("n_steps (%d) must be divisible by minibatches (%d)" % (n_steps, minibatches))
+    _, _, _, gamma, lam = check_gae(n_steps, 1, 1, gamma, lam)
+    clip, ent_coef = check_pg(clip, ent_coef)
+    return int(n_steps), gamma, lam, clip, ent_coef, int(epochs), int(minibatches), int(substeps)
+
+
+def gae_ref(reward, reason, value, last_value=None, gamma=0.99, lam=0.95):
+    """``bsk_gae`` restated: ``reward`` float64, ``reason`` uint8 and ``value`` float32, each (T, N); ``last_value`` float32 (N,) or
+    None (= 0) -> (adv float32 (T, N), ret float64 (T, N)).  Per env, float64, t descending, every operation rounded on its own:
+    where reason == 0, carry = ((reward + gamma * next_v) - v) + (gamma * lam) * carry; elsewhere - EVERY reason, the time limit
+    included - carry = reward - v; adv = float32(carry), ret = carry + v, next_v = v.  Bit for bit the device's."""
+    reward = np.asarray(reward, np.float64)
+    T, N = reward.shape
+    reason = np.asarray(reason).reshape(T, N)
+    value = np.asarray(value, np.float32).reshape(T, N)
+    g = np.float64(gamma)
+    gl = g * np.float64(lam)
+    carry = np.zeros(N, np.float64)
+    next_v = np.zeros(N, np.float64) if last_value is None else np.asarray(last_value, np.float32).reshape(N).astype(np.float64)
+    adv, ret = np.empty((T, N), np.float32), np.empty((T, N), np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for t in range(T - 1, -1, -1):
+            v = value[t].astype(np.float64)
+            carry = np.where(reason[t] == 0, ((reward[t] + g * next_v) - v) + gl * carry, reward[t] - v)
+            adv[t] = carry.astype(np.float32)
+            ret[t] = carry + v
+            next_v = v
+    return adv, ret
+
+
+def pg_clip_edges(clip):
+    """-> (lo, hi) float32: 1.0f - (float)clip and 1.0f + (float)clip, as the host forms them once"""
+    c = np.float32(clip)
+    return np.float32(1.0) - c, np.float32(1.0) + c
+
+
+def fit_pg_terms_ref(logits, actions, adv, logp_old=None, clip=0.2, ent_coef=0.0, on=None, fp64=False):
+    """The policy-gradient output deltas and the per-sample terms of their diagnostics from GIVEN logits (3, n) -> dict ``g``
+    (3, n), ``d``, ``r``, ``H``, ``clipped`` (bool), ``surrogate`` = A r, each (n,).  Default: float32 in the kernel's order
+    (``softmax_ref``'s m, e and s; p_i = e_i / s; lp_i = (l_i - m) - log(s); ``fma32`` for the entropy term; ``exp`` and ``log`` are
+    the host's).  ``fp64=True``: the same formulas in float64 on the logits as given, with the float32 clip edges widened.  Samples
+    outside ``on`` (bool (n,), default all) get zero deltas; their other terms are still formed."""
+    dt = np.float64 if fp64 else np.float32
+    l = np.asarray(logits, dt).reshape(3, -1)
+    n = l.shape[1]
+    a = np.clip(np.asarray(actions).reshape(-1).astype(np.int64), 0, 2)
+    A = np.asarray(adv, np.float32).reshape(-1).astype(dt)
+    on = np.ones(n, bool) if on is None else np.asarray(on, bool).reshape(-1)
+    lo, hi = (dt(x) for x in pg_clip_edges(clip))
+    ec = dt(np.float32(ent_coef))
+    pick = (a, np.arange(n))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore", under="ignore"):
+        if fp64:
+            z = l - l.max(axis=0)
+            e = np.exp(z)
+            s = e.sum(axis=0)
+            p, lp = e / s, z - np.log(s)
+        else:
+            m, e, s = softmax_ref(l)
+            p, lp = (e / s).astype(dt), ((l - m) - np.log(s)).astype(dt)
+        H = -((p[0] * lp[0] + p[1] * lp[1]) + p[2] * lp[2])
+        if logp_old is None:
+            d, r, clipped = np.zeros(n, dt), np.ones(n, dt), np.zeros(n, bool)
+        else:
+            d = lp[pick] - np.asarray(logp_old, np.float32).reshape(-1).astype(dt)
+            r = np.exp(d).astype(dt)
+            clipped = ((A > 0) & (r > hi)) | ((A < 0) & (r < lo))
+        onehot = (np.arange(3)[:, None] == a[None, :]).astype(dt)
+        g = np.where(clipped | (A == 0), dt(0), (A * r) * (p - onehot)).astype(dt)
+        if ec != 0:
+            q = p * (lp + H)
+            g = (g + ec * q) if fp64 else fma32(ec, q, g)
+        g = np.where(on, g, dt(0)).astype(dt)
+    return {"g": g, "d": d, "r": r, "H": H, "clipped": clipped, "surrogate": A * r if fp64 else A.astype(np.float64) * r.astype(np.float64)}
+
+
+def fit_pg_dlogits32_ref(spec, params, obs, actions, adv, logp_old=None, clip=0.2, ent_coef=0.0, alive=None):
+    """The policy-gradient output deltas as the kernel forms them, float32 (3, n): ``mlp_ref``'s logits through
+    ``fit_pg_terms_ref``; +0.0 where the sample does not contribute (``_fit_mask`` with the action in the label's place).  With
+    ``logp_old=None``, unit advantages and ``ent_coef=0`` these are ``fit_dlogits32_ref``'s bits for labels = actions."""
+    spec = _as_spec(spec)
+    o = np.asarray(obs, np.float64).reshape(5, -1)
+    actions, on = _fit_mask(o.shape[1], actions, alive)
+    return fit_pg_terms_ref(mlp_ref(spec, params, o)[0], actions, adv, logp_old, clip, ent_coef, on)["g"]
+
+
+def fit_pg_dlogits_ref(spec, params, obs, actions, adv, logp_old=None, clip=0.2, ent_coef=0.0, alive=None, fp64=True):
+    """The policy-gradient output deltas (3, n).  ``fp64=True``: float64 from float64 logits on ``params`` as given (a float64 block
+    is not rounded), what ``fit_backward_ref(fp64=True)`` turns into the gradient of ``fit_pg_loss_ref``;  ``fp64=False``:
+    ``fit_pg_dlogits32_ref``."""
+    if not fp64:
+        return fit_pg_dlogits32_ref(spec, params, obs, actions, adv, logp_old, clip, ent_coef, alive)
+    spec = _as_spec(spec)
+    scale, shift, a, _ = _fit_nets(spec, params, True)
+    x, n = _fit_inputs(scale, shift, obs, True)
+    actions, on = _fit_mask(n, actions, alive)
+    l = _fit_forward(a, spec.activation, x, True)[-1][:, :n]
+    return fit_pg_terms_ref(l, actions, adv, logp_old, clip, ent_coef, on, fp64=True)["g"]
+
+
+def fit_pg_loss_ref(spec, params, obs, actions, adv, logp_old=None, clip=0.2, ent_coef=0.0, alive=None, value_targets=None,
+                    value_coef=0.0):
+    """The loss whose gradient ``bsk_fit_accumulate_pg`` accumulates, float64 and on ``params`` as given: the SUM over the
+    contributing samples of -min(r A, clamp(r, lo, hi) A) - ent_coef H + value_coef * 0.5 * (v - target)**2, with
+    r = exp(lp_a - logp_old); without ``logp_old`` the first term is -A lp_a, whose gradient is that of -r A at r = 1.  For finite
+    differences: it has a kink where r crosses lo (A < 0) or hi (A > 0)."""
+    spec = _as_spec(spec)
+    scale, shift, a, v = _fit_nets(spec, params, True)
+    x, n = _fit_inputs(scale, shift, obs, True)
+    actions, on = _fit_mask(n, actions, alive)
+    l = _fit_forward(a, spec.activation, x, True)[-1][:, :n]
+    z = l - l.max(axis=0)
+    lp = z - np.log(np.exp(z).sum(axis=0))
+    lpa = lp[np.clip(actions, 0, 2), np.arange(n)]
+    A = np.asarray(adv, np.float32).reshape(-1).astype(np.float64)
+    if logp_old is None:
+        per = -A * lpa
+    else:
+        lo, hi = (np.float64(e) for e in pg_clip_edges(clip))
+        r = np.exp(lpa - np.asarray(logp_old, np.float32).reshape(-1).astype(np.float64))
+        per = -np.minimum(r * A, np.clip(r, lo, hi) * A)
+    H = -(np.exp(lp) * lp).sum(axis=0)
+    loss = np.where(on, per - np.float64(np.float32(ent_coef)) * H, 0.0).sum()
+    if value_targets is not None:
+        val = _fit_forward(v, spec.value_activation, x, True)[-1][0, :n]
+        loss += np.float64(value_coef) * 0.5 * np.where(on, (val - np.asarray(value_targets, np.float64).reshape(-1)) ** 2, 0.0).sum()
+    return float(loss)
+
+
+def fit_pg_stats_ref(spec, params, obs, actions, adv, logp_old=None, clip=0.2, alive=None):
+    """The policy-gradient row of one ``bsk_fit_accumulate_pg`` -> float64 (4,), ``PG_STATS_COLUMNS``: the float32 terms of
+    ``fit_pg_terms_ref`` on ``mlp_ref``'s logits, widened and summed sample-ascending within a block, then block-ascending;
+    contributing samples only."""
+    spec = _as_spec(spec)
+    o = np.asarray(obs, np.float64).reshape(5, -1)
+    n = o.shape[1]
+    actions, on = _fit_mask(n, actions, alive)
+    t = fit_pg_terms_ref(mlp_ref(spec, params, o)[0], actions, adv, logp_old, clip, 0.0, on)
+    pad = -(-n // FIT_BLOCK) * FIT_BLOCK
+    terms = np.zeros((4, pad), np.float64)
+    terms[0, :n] = np.where(on, -t["d"].astype(np.float64), 0.0)
+    terms[1, :n] = np.where(on, t["H"].astype(np.float64), 0.0)
+    terms[2, :n] = np.where(on & t["clipped"], 1.0, 0.0)
+    terms[3, :n] = np.where(on, t["surrogate"], 0.0)
+    blocks = np.zeros((4, pad // FIT_BLOCK), np.float64)
+    for s_ in range(FIT_BLOCK):
+        blocks = blocks + terms[:, s_::FIT_BLOCK]
+    row = np.zeros(4, np.float64)
+    for b in range(blocks.shape[1]):
+        row = row + blocks[:, b]
+    return row

@@ -1103,6 +1103,72 @@ int bsk_fit_set_lr(bsk_fit* f, double lr);
  * device, no copy, no synchronisation, capturable.  BSK_EINVAL for NULL pointers and n < 1. */
 int bsk_fit_alive_mask(const uint8_t* d_reason, int n, int first, uint8_t* d_alive, void* stream);
 
+/* Policy-gradient training on top of the fit: an advantage estimator over the histories of bsk_policy_rollout, and the output
+ * deltas of a clipped surrogate (PPO; without old log-probabilities plain A2C / REINFORCE) with an entropy bonus in the place of the
+ * cross-entropy's.  Everything behind the output deltas is bsk_fit_accumulate's, unchanged.
+ *
+ * Generalised advantage estimation (Schulman et al. 2016), ONE launch.  Layouts are bsk_policy_rollout's: histories
+ * [n_steps][stride], stride >= n_envs.
+ *   d_last_value  f32[n_envs] or NULL (= 0): the value of the observation the handle holds after the rollout (bsk_policy_value on
+ *                 the handle's observation buffers)
+ *   d_adv         f32[n_steps][stride];   d_ret  f64[n_steps][stride] or NULL (f64: it is d_value_target of the fit)
+ * Per env j, all f64, no FMA, every operation rounded on its own; gl = gamma * lambda formed once on the host:
+ *   carry = 0;  next_v = d_last_value ? (double)last_value[j] : 0
+ *   for t = n_steps - 1 .. 0:   v = (double)value[t][j]
+ *     reason[t][j] == 0:  delta = (reward[t][j] + gamma * next_v) - v;  carry = delta + gl * carry
+ *     otherwise:          delta = reward[t][j] - v;                     carry = delta
+ *     adv[t][j] = (float)carry;  ret[t][j] = carry + v;  next_v = v
+ * EVERY reason != 0 cuts the bootstrap, the time limit (BSK_DONE_LENGTH) included: the rule of stable-baselines' PPO2, under
+ * which the reference's agent was trained - and the only correct one under BSK_FLAG_AUTO_RESET, where value[t + 1] already belongs
+ * to the first observation of the next episode.
+ * One thread per env walks t downwards; every load and store is coalesced along j; no atomics and no cross-lane traffic, so the
+ * launch shape enters no bit (basilisk_env_amd/policy_ref.py: gae_ref, equal bit for bit).  Enqueued on `stream` of the current
+ * device: no copy, no synchronisation, no allocation; capturable from the first call.  Columns j >= n_envs are neither read nor
+ * written.  BSK_EINVAL before any launch: a NULL history or d_adv; n_steps < 1, n_envs < 1, stride < n_envs; gamma or lambda outside
+ * [0, 1] or not finite. */
+int bsk_gae(const double* d_reward_hist, const uint8_t* d_reason_hist, const float* d_value_hist, const float* d_last_value,
+            int n_steps, int n_envs, int64_t stride, double gamma, double lambda, float* d_adv, double* d_ret, void* stream);
+/* bsk_fit_accumulate in everything - scratch rule and capturability, which samples contribute (index below n, alive byte non-zero,
+ * d_action in 0..2), the value network's term, block gradients, fold, count, bsk_fit_step, the diagnostics row of
+ * bsk_fit_stats_device with d_action in the label's place - but the output deltas of the action network, one more row of
+ * diagnostics and one more launch in front (three in all): lp_i below is formed by the policy's own evaluation code for all three
+ * actions and read by the fit's kernel, so that it is the logp of bsk_policy_act to the bit; its 3 n floats are part of the scratch.
+ *   d_action    int32[n]: the action taken (d_action_hist of the rollout);  d_adv  f32[n]: its advantage (bsk_gae)
+ *   d_logp_old  f32[n]: the log-probability the action was taken with (d_logp_hist), or NULL: no ratio, no clipping
+ * The loss per sample is  L = -min(r A, clamp(r, lo, hi) A) - ent_coef H,  r = exp(lp_a - logp_old),  H = -sum_i p_i lp_i.
+ * With d lp_a / d l_i = (i == a) - p_i:  d(-r A) / d l_i = A r (p_i - (i == a)), and the min takes the clamped branch - whose
+ * gradient is zero - exactly where A > 0 and r > hi or A < 0 and r < lo;  d(-H) / d l_i = p_i (lp_i + H).
+ * Per sample, all f32, every operation rounded on its own unless written fmaf;  hi = 1.0f + (float)clip, lo = 1.0f - (float)clip
+ * and ec = (float)ent_coef formed once on the host:
+ *   m, e_i, s as in steps 5 / 6 of the policy's definition;  p_i = e_i / s;  ls = logf(s);  lp_i = (l_i - m) - ls
+ *   (expf and logf are the device library's as the compiler expands them: p_i is the p_i of bsk_fit_accumulate, bit for bit, and
+ *   lp_i the logp of policy_kernel, bit for bit - in their last bit the two need not stem from one s)
+ *   A = d_adv[j];  a = d_action[j]
+ *   d_logp_old == NULL:  r = 1.0f, clipped = false
+ *   otherwise:           d = lp_a - d_logp_old[j];  r = expf(d);  clipped = (A > 0 && r > hi) || (A < 0 && r < lo)
+ *   clipped || A == 0:   gp_i = +0.0f   (the product with c = +0.0f, its sign dropped)
+ *   otherwise:           c = A * r;  gp_i = c * (p_i - (i == a ? 1.0f : 0.0f))
+ *   ec == 0:  g_i = gp_i
+ *   else:     H = -((p_0 * lp_0 + p_1 * lp_1) + p_2 * lp_2);  q_i = p_i * (lp_i + H);  g_i = fmaf(ec, q_i, gp_i)
+ * A sample that does not contribute gets +0.0f for each g_i and is not counted.  Non-finite advantages and old log-probabilities
+ * are outside the numerical contract, as non-finite observations are.  It follows that (1) with d_logp_old == NULL, A = 1 and
+ * ent_coef = 0 the deltas, A_p and the count are bsk_fit_accumulate's for label = action, bit for bit; (2) lp_a is formed as
+ * policy_kernel forms logp, so with unchanged parameters and d_logp_old from bsk_policy_act or the rollout d is +0.0f, r is 1.0f
+ * and nothing is clipped; (3) a sample with A == 0 and ec == 0 contributes +0.0f deltas and is still counted.
+ * The policy-gradient row, f64[4] behind bsk_fit_pg_stats_device, written by every bsk_fit_accumulate_pg in the order of the first
+ * row (sample-ascending inside a block from +0.0, then block-ascending from +0.0; contributing samples only):
+ *   [0] the sum of -(double)d, an estimate of the KL divergence from the old policy (+0.0 without d_logp_old)
+ *   [1] the sum of (double)H (computed for this row also when ec == 0)     [2] the clipped samples
+ *   [3] the sum of (double)A * (double)r
+ * BSK_EINVAL before any launch, beyond bsk_fit_accumulate's rules: NULL d_action or d_adv; clip not finite or outside (0, 1) when
+ * d_logp_old is given; ent_coef not finite or negative. */
+int bsk_fit_accumulate_pg(bsk_fit* f, const double* d_obs, int64_t obs_stride, int n, const int32_t* d_action, const float* d_adv,
+                          const float* d_logp_old, double clip, double ent_coef, const double* d_value_target,
+                          const uint8_t* d_alive, float* d_dlogits, int64_t out_stride, void* stream);
+/* The policy-gradient row of the last bsk_fit_accumulate_pg as DEVICE words, f64[4] (read-only for the caller; valid for the fit's
+ * lifetime; zero before the first).  No launch, no copy, no synchronisation. */
+int bsk_fit_pg_stats_device(bsk_fit* f, const double** d_row4);
+
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the
  * three-wave form's barrier-free exchange gives up after 2^20 polls instead of hanging, and says so here. */

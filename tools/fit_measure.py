@@ -13,6 +13,15 @@ same card.
   BSKGPU_LIB=basilisk_env_amd/variants/fit_stamps.so python tools/fit_measure.py stamps
       (after `make -C basilisk_env_amd/csrc fit-stamps`) the share of fit_block_kernel's clock ticks, summed over its workgroups,
       that thread 0 spends in the weight-gradient walks - the library is a measurement build whose diagnostics row carries ticks.
+  python tools/fit_measure.py pg
+      the policy-gradient form ("Policy gradient") with a `[64]` value network and value targets, timed as under
+      `time`: `accumulate` + `step` and `accumulate` alone (the supervised pair: with BSKGPU_LIB naming a library built from the
+      parent commit this is all that runs - the parent's band, re-measured in the same session), then `accumulate_pg` + `step` and
+      `accumulate_pg` alone in PPO mode with the entropy bonus on, then `bsk_gae` at 32 steps of 65 536 envs against its 52 MB of
+      traffic.
+  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o pg -- python tools/fit_measure.py pg-kernel
+      (a run of its own) 60 `accumulate_pg` + `step` pairs of that set-up on the null stream: the mean time of policy_logp_kernel,
+      fit_block_kernel<true>, fit_fold_kernel<8> and the step's three kernels apart.
 """
 import os
 import sys
@@ -121,5 +130,65 @@ def stamps():
     pol.close()
 
 
+def pg(trace=False):
+    import torch
+    from _policy_bounds import observation_like, seeded_policy
+    from basilisk_env_amd import _lib
+    from basilisk_env_amd import policy as P
+    spec, params = seeded_policy(HIDDEN, "relu", (64,), seed=1)
+    obs = observation_like(N, 3)
+    rng = np.random.default_rng(5)
+    labels = np.where(obs[3] < 0.4, 1, np.where(obs[2] > 0.7, 2, 0)).astype(np.int32)
+    pol = P.DevicePolicy(spec, params)
+    fit = P.PolicyFit(pol, lr=1e-3)
+    side = torch.cuda.Stream()
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()      # noqa: E731
+    d_obs, d_lab, d_tgt = dev(obs), dev(labels), dev(rng.normal(size=N))
+    s = side.cuda_stream
+    if trace:
+        d_adv, d_old = dev(rng.normal(size=N).astype(np.float32)), dev((-1.1 + rng.normal(0.0, 0.3, N)).astype(np.float32))
+        torch.cuda.synchronize()
+        for _ in range(60):
+            fit.accumulate_pg(d_obs, d_lab, d_adv, d_old, 0.2, 0.01, d_tgt)
+            fit.step()
+        torch.cuda.synchronize()
+        fit.close()
+        pol.close()
+        return
+    with torch.cuda.stream(side):
+        def pair():
+            fit.accumulate(d_obs, d_lab, d_tgt, stream=s)
+            fit.step(s)
+        for name, fn in (("accumulate + step", pair), ("accumulate alone", lambda: fit.accumulate(d_obs, d_lab, d_tgt, stream=s))):
+            print("device  %-22s %8.1f us  (p10 %.1f, p90 %.1f)" % ((name,) + _timed(torch, side, fn)))
+        if hasattr(_lib.load(), "bsk_fit_accumulate_pg"):
+            # old log-probabilities 0.3 away from the policy's own, as in tests/test_gpu_pg.py: a good share of the samples is clipped
+            res = pol.act(d_obs, "greedy", want=("logits",), stream=s)
+            torch.cuda.synchronize()
+            from _device_bits import download
+            l = download(res["logits"].__cuda_array_interface__["data"][0], np.float32, 3 * N).reshape(3, N).astype(np.float64)
+            z = l - l.max(axis=0)
+            lpa = (z - np.log(np.exp(z).sum(axis=0)))[labels, np.arange(N)]
+            d_adv, d_old = dev(rng.normal(size=N).astype(np.float32)), dev((lpa + rng.normal(0.0, 0.3, N)).astype(np.float32))
+
+            def pg_pair():
+                fit.accumulate_pg(d_obs, d_lab, d_adv, d_old, 0.2, 0.01, d_tgt, stream=s)
+                fit.step(s)
+            for name, fn in (("accumulate_pg + step", pg_pair),
+                             ("accumulate_pg alone", lambda: fit.accumulate_pg(d_obs, d_lab, d_adv, d_old, 0.2, 0.01, d_tgt, stream=s))):
+                print("device  %-22s %8.1f us  (p10 %.1f, p90 %.1f)" % ((name,) + _timed(torch, side, fn)))
+            row = fit.pg_stats()
+            print("device  last row: clipped %d of %d" % (row["clipped"], fit.stats()["count"]))
+            T = 32
+            d_rew, d_val = dev(rng.normal(size=(T, N))), dev(rng.normal(size=(T, N)).astype(np.float32))
+            d_why = dev((rng.uniform(size=(T, N)) < 0.02).astype(np.uint8))
+            d_a, d_r = torch.empty((T, N), dtype=torch.float32, device="cuda"), torch.empty((T, N), dtype=torch.float64, device="cuda")
+            med, p10, p90 = _timed(torch, side, lambda: P.gae(d_rew, d_why, d_val, None, T, N, d_a, d_r, stream=s))
+            print("device  %-22s %8.1f us  (p10 %.1f, p90 %.1f): %.0f GB/s of its %.1f MB" % ("bsk_gae 32 x 65536", med, p10, p90,
+                                                                                          25.0 * T * N / med * 1e-3, 25.0 * T * N * 1e-6))
+    fit.close()
+    pol.close()
+
+
 if __name__ == "__main__":
-    {"time": time_, "kernel": kernel, "stamps": stamps}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
+    {"time": time_, "kernel": kernel, "stamps": stamps, "pg": pg, "pg-kernel": lambda: pg(trace=True)}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
