@@ -10,7 +10,8 @@
 
 using namespace bsk::capi;
 
-// bsk_fit_*: ONE allocation of 8-byte words [theta np | m np | v np | beta_pow 2 | A np | row 4 | count | steps | pg_row 4] and, from
+// bsk_fit_*: ONE allocation of 8-byte words [theta np | m np | v np | beta_pow 2 | A np | row 4 | count | steps | pg_row 4 | gnorm_row 2]
+// and, from
 // the first accumulate on, the scratch of the block gradients: [G n_blocks * np floats | diag n_blocks * 8 doubles | lp 3 * 64
 // n_blocks floats] (a supervised launch uses the first 4 n_blocks of diag and no lp)
 struct bsk_fit {
@@ -18,6 +19,7 @@ struct bsk_fit {
     int device = 0;
     double lr = 0.0, beta1 = 0.0, beta2 = 0.0, eps = 0.0, weight_decay = 0.0;
     float value_coef = 0.0f;
+    double max_grad_norm = 0.0;            // bsk_fit_set_max_grad_norm: 0 = no clip, and the step's launches without it
     double* d_state = nullptr;
     void* d_scratch = nullptr;
     int blocks_cap = 0;
@@ -33,7 +35,8 @@ struct bsk_fit {
     unsigned long long* count() const { return (unsigned long long*)(d_state + 4 * np() + 6); }
     unsigned long long* steps() const { return count() + 1; }
     double* pg_row() const { return d_state + 4 * np() + 8; }
-    size_t words() const { return 4 * np() + 12; }
+    double* gnorm_row() const { return d_state + 4 * np() + 12; }          // {norm, scale} of the last clipped step
+    size_t words() const { return 4 * np() + 14; }
     // where the action network's parameters end in the C-ABI block: all a fit without value targets folds and moves
     int action_end() const {
         const bsk::PolicyLayout& lay = policy->lay;
@@ -141,6 +144,7 @@ int bsk_fit_create(bsk_policy* p, double lr, double beta1, double beta2, double 
     bsk::policy_unpack(lay, dev.data(), params.data());
     for (size_t j = 0; j < params.size(); ++j) state[j] = (double)params[j];
     state[3 * f->np()] = state[3 * f->np() + 1] = 1.0;
+    state[4 * f->np() + 13] = 1.0;         // (the clip's row before the first clipped step: {+0.0, 1.0})
     auto upload = [&]() -> int {
         HIP_TRY(hipMalloc(&f->d_state, state.size() * 8));
         HIP_COPY(hipMemcpy(f->d_state, state.data(), state.size() * 8, hipMemcpyHostToDevice));
@@ -201,7 +205,8 @@ int bsk_fit_step(bsk_fit* f, void* stream) {
     ad.a1 = 1.0 - f->beta1; ad.a2 = 1.0 - f->beta2;
     ad.eps = f->eps; ad.weight_decay = f->weight_decay;
     ad.lr = f->lr;
-    HIP_TRY(bsk::launch_fit_step(f->theta(), f->A(), f->count(), f->steps(), f->value_seen ? f->policy->lay.n_params : f->action_end(), ad, s));
+    HIP_TRY(bsk::launch_fit_step(f->theta(), f->A(), f->count(), f->steps(), f->value_seen ? f->policy->lay.n_params : f->action_end(), ad,
+                               f->max_grad_norm, f->gnorm_row(), s));
     f->value_seen = false;
     return write_policy(f, s);        // asynchronous on `stream`: no copy, no synchronisation
 }
@@ -242,6 +247,40 @@ int bsk_fit_set_lr(bsk_fit* f, double lr) {
     if (!finite_nonneg(lr)) return fail(BSK_EINVAL, "bsk_fit_set_lr: lr must be finite and not negative");
     f->lr = lr;
     return BSK_OK;
+}
+
+int bsk_fit_set_max_grad_norm(bsk_fit* f, double max_norm) {
+    if (!f) return fail(BSK_EINVAL, "fit is NULL");
+    if (!finite_nonneg(max_norm)) return fail(BSK_EINVAL, "bsk_fit_set_max_grad_norm: max_norm must be 0 (off) or finite and positive");
+    f->max_grad_norm = max_norm;
+    return BSK_OK;
+}
+
+int bsk_fit_grad_norm_device(bsk_fit* f, const double** d_row2) {
+    if (!f || !d_row2) return fail(BSK_EINVAL, "fit/d_row2 is NULL");
+    *d_row2 = f->gnorm_row();
+    return BSK_OK;
+}
+
+int bsk_fit_apply_obs_norm(bsk_fit* f, bsk_obs_stats* s, double std_min, void* stream) {
+    if (!f || !s) return fail(BSK_EINVAL, "fit/stats is NULL");
+    if (!std::isfinite(std_min) || !(std_min > 0.0)) return fail(BSK_EINVAL, "bsk_fit_apply_obs_norm: std_min must be finite and positive");
+    if (f->device != s->device) return fail(BSK_EINVAL, "bsk_fit_apply_obs_norm: the fit and the statistics live on different devices");
+    DeviceGuard guard(f->device);
+    HIP_TRY(bsk::launch_es_obs_norm(s->st.tot, s->st.tot_n, std_min, f->theta(), (hipStream_t)stream));
+    return write_policy(f, (hipStream_t)stream);        // asynchronous on `stream`: no copy, no synchronisation
+}
+
+int64_t bsk_adv_normalize_work_bytes(int n) { return n < 1 ? 0 : 8 * (4 + 3 * (((int64_t)n + 63) / 64)); }
+
+int bsk_adv_normalize(const float* d_adv, const uint8_t* d_alive, int rows, int n, int64_t stride, double eps, float* d_out, void* d_work,
+                      void* stream) {
+    if (!d_adv || !d_out || !d_work) return fail(BSK_EINVAL, "bsk_adv_normalize: d_adv, d_out or d_work is NULL");
+    if (rows < 1 || n < 1 || stride < n) return fail(BSK_EINVAL, "bsk_adv_normalize: rows and n must be >= 1, stride >= n");
+    if ((int64_t)rows > ((int64_t)1 << 31) / stride) return fail(BSK_EINVAL, "bsk_adv_normalize: rows * stride must not exceed 2^31");
+    if (!std::isfinite(eps) || !(eps > 0.0)) return fail(BSK_EINVAL, "bsk_adv_normalize: eps must be finite and positive");
+    HIP_TRY(bsk::launch_adv_normalize(d_adv, d_alive, rows, n, stride, eps, d_out, (double*)d_work, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream` of the current device: no copy, no synchronisation, no allocation
 }
 
 int bsk_fit_alive_mask(const uint8_t* d_reason, int n, int first, uint8_t* d_alive, void* stream) {

@@ -7,16 +7,22 @@
 //   fit_fold_kernel     one thread per parameter: A += (double)G_b, b ascending; four threads more for the diagnostics row
 //                       (<8>: eight, the policy-gradient row behind the first)
 //   gae_kernel          bsk_gae: one thread per env walks its column of the rollout histories from the last step to the first
+//   adv_partial_kernel, adv_join_kernel, adv_apply_kernel    bsk_adv_normalize: the mean and standard deviation of an advantage
+//                       block in the fixed order of the observation statistics (bsk_tree.hpp), and (x - mean) / (sd + eps)
+//   fit_gnorm_kernel    bsk_fit_set_max_grad_norm: one workgroup, the global norm of the mean gradient and the clip's scale
 //   fit_adam_kernel     one thread per parameter: the mean gradient through Adam (adam_step, bsk_es.hpp: the text of the
-//                       evolution strategy's update), a descent
+//                       evolution strategy's update), a descent; <true>: the gradient times the clip's scale first
 //   fit_advance_kernel  one thread: beta_pow and the step counter move on, the count back to zero
 //   fit_alive_kernel    bsk_fit_alive_mask: which envs of a collection loop are still in their first episode
 // The forward pass IS policy_kernel's: policy_hidden / policy_output of bsk_policy.hpp.  Every fused multiply-add is an explicit
 // fmaf and every chain has one owner that walks it in the definition's order, so neither the launch shape nor the hardware's
-// scheduling enters a bit: no atomics, no cross-lane reduction.  Compiled with -ffp-contract=off (Makefile) for the f64 parts.
+// scheduling enters a bit: no atomics, and no cross-lane reduction but the fixed tree of bsk_tree.hpp under the two reductions of
+// the policy-gradient loop (adv_*, fit_gnorm_kernel).  Compiled with -ffp-contract=off (Makefile) for the f64 parts.
 #include "bsk_fit.hpp"
 
 #include "../../include/bskgpu.h"
+#include "bsk_obsstats.hpp"
+#include "bsk_tree.hpp"
 
 // Measurement builds only (make fit-stamps -> variants/fit_stamps.so; tools/fit_measure.py stamps): thread 0 of every workgroup
 // counts the clock ticks of the weight-gradient walks, a barrier behind each, and of the whole kernel, and the block's diagnostics
@@ -34,6 +40,9 @@ constexpr int FIT_X_ROWS = 8;
 constexpr int FIT_FOLD_BATCH = 32;     // block gradients the fold has in flight per thread
 constexpr int FIT_DIAG_ROWS = 5;       // behind the rows: two doubles and an int per sample, the terms of the block's diagnostics
 constexpr int FIT_PG_DIAG_ROWS = 8;    // behind those, policy-gradient launches only: four doubles more per sample
+constexpr int FIT_GNORM_BLOCK = 1024;  // fit_gnorm_kernel's one workgroup: sixteen waves
+constexpr int ADV_BATCH = 8;           // rows of an advantage block the partial sums have in flight per lane
+constexpr int ADV_APPLY_ROWS = 1024;   // rows of the apply launch's grid; a block strides over the rest
 
 __device__ __forceinline__ int fit_row(const FitNet& net, int l) {      // the first row of layer l's INPUT; l = n_layers: the output deltas
     int r = l == 0 ? 0 : FIT_X_ROWS;
@@ -335,14 +344,56 @@ __global__ __launch_bounds__(256) void fit_fold_kernel(const float* __restrict__
     A[p] = acc;
 }
 
+// bsk_fit_set_max_grad_norm: the global norm of the mean gradient over the parameters the step moves, and the factor that brings it
+// down to max_norm (TensorFlow's clip_by_global_norm, PPO2's rule) - ONE workgroup, so that the order of the sum is the kernel's
+// own.  Thread i adds g_q * g_q for q = i, i + 1024, ... ascending FROM the first (+0.0 with none); every wave joins its 64 in the
+// fitness tree; thread 0 adds the sixteen wave sums ascending.  row = {norm, scale}: scale is exactly 1.0 while norm <= max_norm.
+__global__ __launch_bounds__(FIT_GNORM_BLOCK) void fit_gnorm_kernel(const double* __restrict__ A, const unsigned long long* __restrict__ count,
+                                                                    int n_upd, double max_norm, double* __restrict__ row) {
+#pragma clang fp contract(off)
+    __shared__ double s_wave[FIT_GNORM_BLOCK / 64];
+    const int i = (int)threadIdx.x, lane = i & 63;
+    const unsigned long long cnt = *count;
+    if (cnt == 0ull) {                     // (workgroup-uniform: nothing moves, nothing is scaled)
+        if (i == 0) { row[0] = 0.0; row[1] = 1.0; }
+        return;
+    }
+    const int n = n_upd - 10;
+    double s = 0.0;
+    for (int q = i; q < n; q += FIT_GNORM_BLOCK) {
+        const double g = A[10 + q] / (double)cnt;
+        const double gg = g * g;
+        s = q == i ? gg : s + gg;
+    }
+    s = fitness_tree(s, lane);
+    if (lane == 0) s_wave[i >> 6] = s;
+    __syncthreads();
+    if (i == 0) {
+        double S = s_wave[0];
+        for (int w = 1; w < FIT_GNORM_BLOCK / 64; ++w) S = S + s_wave[w];
+        const double norm = sqrt(S);
+        row[0] = norm;
+        row[1] = max_norm / (norm > max_norm ? norm : max_norm);
+    }
+}
+
+// CLIP: the mean gradient times the scale fit_gnorm_kernel left, the L2 term added behind it.  <false> is the step without a clip,
+// with the arguments it has always had: the row is an argument of <true, const double*> alone.
+template <bool CLIP, typename... Row>
 __global__ __launch_bounds__(256) void fit_adam_kernel(double* __restrict__ theta, double* __restrict__ A,
-                                                       const unsigned long long* __restrict__ count, int n_upd, const EsAdam ad) {
+                                                       const unsigned long long* __restrict__ count, int n_upd, const EsAdam ad,
+                                                       const Row... gnorm_row) {
     const int p = 10 + (int)(blockIdx.x * 256u + threadIdx.x);
     if (p >= n_upd) return;
     const unsigned long long cnt = *count;
     if (cnt != 0ull) {
         const double t = theta[p];
-        theta[p] = t - adam_step(ad, p, A[p] / (double)cnt + ad.weight_decay * t);
+        if constexpr (CLIP) {
+            const double* const row[] = {gnorm_row...};
+            theta[p] = t - adam_step(ad, p, (A[p] / (double)cnt) * row[0][1] + ad.weight_decay * t);
+        } else {
+            theta[p] = t - adam_step(ad, p, A[p] / (double)cnt + ad.weight_decay * t);
+        }
     }
     A[p] = 0.0;
 }
@@ -388,6 +439,130 @@ __global__ __launch_bounds__(256) void gae_kernel(const double* __restrict__ rew
         if (ret) ret[at] = carry + v;
         next_v = v;
     }
+}
+
+// bsk_adv_normalize, first launch.  Wave w is the columns 64 w .. 64 w + 63 of the block, a lane its column: it walks the rows
+// ascending, a1 = a1 + xd and a2 = a2 + xd * xd from +0.0 (xd = +0.0 where the sample does not count), then the wave joins in the
+// fitness tree and lane 0 WRITES its partial sums and its count.  The chain is serial by definition; the loads are not:
+// ADV_BATCH rows are fetched side by side and added in order, as in fit_fold_kernel.  Every load is one coalesced row segment.
+__global__ __launch_bounds__(256) void adv_partial_kernel(const float* __restrict__ adv, const uint8_t* __restrict__ alive, int rows, int n,
+                                                          int64_t stride, int waves, double* __restrict__ part,
+                                                          unsigned long long* __restrict__ cnt) {
+#pragma clang fp contract(off)
+    const int w = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));     // (wave-uniform)
+    const int lane = (int)(threadIdx.x & 63u);
+    if (w >= waves) return;
+    const int c = w * 64 + lane;
+    const bool in = c < n;
+    const float* __restrict__ x = adv + (in ? c : 0);
+    const uint8_t* __restrict__ live = alive ? alive + (in ? c : 0) : nullptr;
+    double a1 = 0.0, a2 = 0.0;
+    long long k = 0;
+    int t = 0;
+    for (; t + ADV_BATCH <= rows; t += ADV_BATCH) {
+        float v[ADV_BATCH];
+        bool on[ADV_BATCH];
+#pragma unroll
+        for (int i = 0; i < ADV_BATCH; ++i) {
+            const int64_t at = (int64_t)(t + i) * stride;
+            on[i] = in && (!live || live[at] != 0);
+            v[i] = in ? x[at] : 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < ADV_BATCH; ++i) {
+            const double xd = on[i] ? (double)v[i] : 0.0;
+            a1 = a1 + xd;
+            a2 = a2 + xd * xd;
+            k += on[i] ? 1 : 0;
+        }
+    }
+    for (; t < rows; ++t) {
+        const int64_t at = (int64_t)t * stride;
+        const bool on = in && (!live || live[at] != 0);
+        const double xd = on ? (double)x[at] : 0.0;
+        a1 = a1 + xd;
+        a2 = a2 + xd * xd;
+        k += on ? 1 : 0;
+    }
+    a1 = fitness_tree(a1, lane);
+    a2 = fitness_tree(a2, lane);
+    k = count_tree(k, lane);
+    if (lane == 0) {
+        part[2 * (size_t)w] = a1;
+        part[2 * (size_t)w + 1] = a2;
+        cnt[w] = (unsigned long long)k;
+    }
+}
+
+// Second launch, three waves: obs_stats_join_kernel's rule on the two columns of the partial sums and on the counts - lane l adds
+// the entries w = l, l + 64, ... ascending FROM the first (+0.0 with none), then the tree - and one thread forms the four words
+// {mean, sd, inv, (double)N} out of the totals; four +0.0 when nothing counts.
+__global__ __launch_bounds__(192) void adv_join_kernel(const double* __restrict__ part, const unsigned long long* __restrict__ cnt, int waves,
+                                                       double eps, double* __restrict__ mom) {
+#pragma clang fp contract(off)
+    __shared__ double s_tot[2];
+    __shared__ unsigned long long s_n;
+    const int c = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = (int)(threadIdx.x & 63u);
+    if (c < 2) {
+        double s = 0.0;
+        for (int w = lane; w < waves; w += 64) {
+            const double v = part[2 * (size_t)w + c];
+            s = w == lane ? v : s + v;
+        }
+        s = fitness_tree(s, lane);
+        if (lane == 0) s_tot[c] = s;
+    } else {
+        long long s = 0;
+        for (int w = lane; w < waves; w += 64) s += (long long)cnt[w];
+        s = count_tree(s, lane);
+        if (lane == 0) s_n = (unsigned long long)s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long N = s_n;
+        if (N == 0ull) {
+            mom[0] = mom[1] = mom[2] = mom[3] = 0.0;
+        } else {
+            double mean, var;
+            obs_moments(s_tot[0], s_tot[1], N, mean, var);
+            const double sd = sqrt(var);
+            mom[0] = mean;
+            mom[1] = sd;
+            mom[2] = 1.0 / (sd + eps);
+            mom[3] = (double)N;
+        }
+    }
+}
+
+// Third launch, elementwise over the columns below n: a counting sample becomes (float)(((double)x - mean) * inv), any other +0.0f;
+// nothing is written while N == 0.  A thread reads and writes its own element alone, so out may be adv.
+__global__ __launch_bounds__(256) void adv_apply_kernel(const float* adv, const uint8_t* __restrict__ alive, int rows, int n, int64_t stride,
+                                                        const double* __restrict__ mom, float* out) {
+#pragma clang fp contract(off)
+    const int c = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (c >= n || mom[3] == 0.0) return;
+    const double mean = mom[0], inv = mom[2];
+    for (int t = (int)blockIdx.y; t < rows; t += (int)gridDim.y) {
+        const int64_t at = (int64_t)t * stride + c;
+        const bool on = !alive || alive[at] != 0;
+        out[at] = on ? (float)(((double)adv[at] - mean) * inv) : 0.0f;
+    }
+}
+
+hipError_t launch_adv_normalize(const float* adv, const uint8_t* alive, int rows, int n, int64_t stride, double eps, float* out, double* work,
+                                hipStream_t s) {
+    const int waves = (n + 63) / 64;
+    double* part = work + 4;
+    unsigned long long* cnt = (unsigned long long*)(part + 2 * (size_t)waves);
+    hipLaunchKernelGGL(adv_partial_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, adv, alive, rows, n, stride, waves, part, cnt);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(adv_join_kernel, dim3(1), dim3(192), 0, s, (const double*)part, (const unsigned long long*)cnt, waves, eps, work);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(adv_apply_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)(rows < ADV_APPLY_ROWS ? rows : ADV_APPLY_ROWS)), dim3(256), 0,
+                       s, adv, alive, rows, n, stride, (const double*)work, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_gae(const double* reward, const uint8_t* reason, const float* value, const float* last_value, int n_steps, int n_envs,
@@ -453,9 +628,19 @@ hipError_t launch_fit_fold_pg(const float* G, const double* diag, int n_blocks, 
 }
 
 hipError_t launch_fit_step(double* theta, double* A, unsigned long long* count, unsigned long long* steps, int n_upd, const EsAdam& ad,
-                           hipStream_t s) {
+                           double max_norm, double* gnorm_row, hipStream_t s) {
     if (n_upd > 10) {
-        hipLaunchKernelGGL(fit_adam_kernel, dim3((unsigned)((n_upd - 10 + 255) / 256)), dim3(256), 0, s, theta, A, count, n_upd, ad);
+        const dim3 grid((unsigned)((n_upd - 10 + 255) / 256));
+        if (max_norm > 0.0) {              // one launch in front, over the range the step moves
+            hipLaunchKernelGGL(fit_gnorm_kernel, dim3(1), dim3(FIT_GNORM_BLOCK), 0, s, (const double*)A, (const unsigned long long*)count, n_upd,
+                               max_norm, gnorm_row);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(fit_adam_kernel<true, const double*>), grid, dim3(256), 0, s, theta, A, count, n_upd, ad,
+                               (const double*)gnorm_row);
+        } else {
+            hipLaunchKernelGGL(fit_adam_kernel<false>, grid, dim3(256), 0, s, theta, A, count, n_upd, ad);
+        }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -60,10 +60,15 @@ hipError_t launch_fit_fold_pg(const float* G, const double* diag, int n_blocks, 
 // Generalised advantage estimation over rollout histories [n_steps][stride]: one thread per env, t descending
 hipError_t launch_gae(const double* reward, const uint8_t* reason, const float* value, const float* last_value, int n_steps, int n_envs,
                       int64_t stride, double gamma, double gl, float* adv, double* ret, hipStream_t s);
+// bsk_adv_normalize over adv f32[rows][stride], columns below n: the partial sums of every wave of 64 columns, their join and the
+// four words {mean, sd, inv, N}, then out = (float)((x - mean) * inv).  work: 4 + 3 * ceil(n / 64) words of 8 bytes
+hipError_t launch_adv_normalize(const float* adv, const uint8_t* alive, int rows, int n, int64_t stride, double eps, float* out, double* work,
+                                hipStream_t s);
 // Adam on g = A / count + weight_decay * theta for p in 10 .. n_upd - 1 (descent; nothing while count == 0), A zeroed; then one
-// thread: beta_pow and the step counter move on, count = 0
+// thread: beta_pow and the step counter move on, count = 0.  max_norm > 0: one workgroup in front leaves {norm, scale} of the mean
+// gradient in gnorm_row, and g = (A / count) * scale + weight_decay * theta; max_norm == 0: the launches and arguments without it
 hipError_t launch_fit_step(double* theta, double* A, unsigned long long* count, unsigned long long* steps, int n_upd, const EsAdam& ad,
-                           hipStream_t s);
+                           double max_norm, double* gnorm_row, hipStream_t s);
 // alive[j] = first || (alive[j] && reason[j] == 0), as bytes 1 / 0
 hipError_t launch_fit_alive(const uint8_t* reason, int n, int first, uint8_t* alive, hipStream_t s);
 

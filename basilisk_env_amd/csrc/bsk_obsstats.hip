@@ -70,16 +70,6 @@ __global__ __launch_bounds__(64) void obs_stats_join_kernel(const ObsStats st) {
     }
 }
 
-// mean and variance of one row: var = E[x^2] - mean^2, clamped at zero (the difference of two rounded numbers can fall below it)
-__host__ __device__ __forceinline__ void obs_moments(double sum, double sum_sq, unsigned long long count, double& mean, double& var) {
-#pragma clang fp contract(off)
-    const double N = (double)count;
-    mean = sum / N;
-    const double e2 = sum_sq / N;
-    const double v = e2 - mean * mean;
-    var = v > 0.0 ? v : 0.0;
-}
-
 // Thread k < 5 is row k.  scale = 1 / sd, or 0 where the row has not varied (sd < std_min): such a row - the fifth at the start of
 // training - is switched off instead of being multiplied by 1 / tiny; shift = 0 - mean * scale moves the mean to zero.
 __global__ void es_obs_norm_kernel(const double* __restrict__ tot, const unsigned long long* __restrict__ tot_n, double std_min,

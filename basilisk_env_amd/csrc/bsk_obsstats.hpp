@@ -27,6 +27,17 @@ hipError_t launch_obs_stats_join(const ObsStats& st, hipStream_t s);
 // standard deviation is below std_min is switched off (scale 0), never multiplied by 1 / tiny: the rule of ARS (Mania et al. 2018).
 hipError_t launch_es_obs_norm(const double* tot, const unsigned long long* tot_n, double std_min, double* theta, hipStream_t s);
 
+// mean and variance of one row: var = E[x^2] - mean^2, clamped at zero (the difference of two rounded numbers can fall below it).
+// One text for the observation rows (es_obs_norm_kernel) and the advantages of a minibatch (bsk_fit.hip: adv_join_kernel).
+__host__ __device__ __forceinline__ void obs_moments(double sum, double sum_sq, unsigned long long count, double& mean, double& var) {
+#pragma clang fp contract(off)
+    const double N = (double)count;
+    mean = sum / N;
+    const double e2 = sum_sq / N;
+    const double v = e2 - mean * mean;
+    var = v > 0.0 ? v : 0.0;
+}
+
 // es_obs_norm_kernel's arithmetic on the host, compiled from the same text: mean = sum / N, var = max(sum_sq / N - mean * mean, 0)
 // of one row out of its two totals and the count N > 0 (bsk_obs_stats_get)
 void obs_moments_host(double sum, double sum_sq, unsigned long long count, double* mean, double* var);

@@ -14,7 +14,9 @@ a counter instead of stored.  ``ObsStats`` (``bsk_obs_stats_*``) keeps running s
 a population or a policy it is fed by their rollouts, and ``DeviceEvolutionStrategy.apply_obs_norm`` turns it into theta's in_scale
 and in_shift.  ``PolicyFit`` (``bsk_fit_*``; its binding lives in ``policy_fit`` and is re-exported here) is the gradient side: a
 supervised fit of a ``DevicePolicy`` to labels that are already on the device, such as a planner's - and, with ``gae``
-(``bsk_gae``), ``PolicyFit.accumulate_pg`` and the loop ``PolicyGradient`` over them, training by the reward itself (PPO / A2C).
+(``bsk_gae``), ``PolicyFit.accumulate_pg`` and the loop ``PolicyGradient`` over them, training by the reward itself (PPO / A2C),
+conditioned as PPO2 conditions it by ``normalize_advantages`` (``bsk_adv_normalize``), ``PolicyFit.max_grad_norm`` and
+``PolicyFit.apply_obs_norm``.
 
 They are handles of the library and share what such a handle needs (``policy_base._DeviceObject``: create, close, the closed-handle
 refusal, ``sync``); the policy and the population are also both parameter stores that act (``_ParamStore``: the draw counter, the
@@ -35,11 +37,13 @@ import numpy as np
 from . import _hip, _lib
 from ._lib import check
 from .policy_base import _DeviceObject, _host_block  # noqa: F401
-from .policy_fit import PolicyFit, PolicyGradient, gae  # noqa: F401
+from .policy_fit import PolicyFit, PolicyGradient, gae, normalize_advantages  # noqa: F401
 from .policy_ref import (FIT_BLOCK, FIT_STATS_COLUMNS, check_fit, check_fit_batch, fit_accumulate_ref, fit_backward_ref,  # noqa: F401
                          fit_dlogits32_ref, fit_dlogits_ref, fit_loss_ref, fit_stats_ref, fit_step_ref)
 from .policy_ref import (PG_STATS_COLUMNS, check_gae, check_pg, check_pg_loop, fit_pg_dlogits32_ref, fit_pg_dlogits_ref,  # noqa: F401
                          fit_pg_loss_ref, fit_pg_stats_ref, fit_pg_terms_ref, gae_ref, pg_clip_edges)
+from .policy_ref import (adv_normalize_ref, adv_normalize_work_bytes, check_adv_normalize, check_max_grad_norm,  # noqa: F401
+                         fit_grad_norm_ref)
 from .policy_ref import (ES_LOG_COLUMNS, ES_LOG_EMPTY, ES_VAL_COLUMNS, ES_VAL_MAX_MEMBERS, EvolutionStrategy, _es_pair_sum,  # noqa: F401
                          _es_pair_sums, _series_log, act_ref,
                          centred_ranks, check_adam, check_log, check_validation,

@@ -12,7 +12,11 @@ Reached as ``basilisk_env_amd.policy.PolicyFit``.
 output deltas of a clipped policy-gradient loss (PPO; A2C without old log-probabilities) and an entropy bonus in the
 cross-entropy's place (``bsk_fit_accumulate_pg``), ``gae`` the advantage estimator
 over a rollout's histories (``bsk_gae``), and ``PolicyGradient`` the training loop made of them - rollout, advantages, epochs of
-minibatch steps - with no host in it.  Reached as ``basilisk_env_amd.policy.gae`` / ``.PolicyGradient``."""
+minibatch steps - with no host in it.  Reached as ``basilisk_env_amd.policy.gae`` / ``.PolicyGradient``.
+
+What stable-baselines' PPO2 does to every minibatch beyond that is here too, each off by default: ``normalize_advantages``
+(``bsk_adv_normalize``), ``PolicyFit.max_grad_norm`` (the clip of the gradient's global norm inside ``step``) and
+``PolicyFit.apply_obs_norm`` (an ``ObsStats`` into the policy's in_scale / in_shift); ``PolicyGradient`` takes all three."""
 import ctypes as C
 
 import numpy as np
@@ -20,7 +24,8 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .policy_base import _DeviceObject, _host_block
-from .policy_ref import FIT_STATS_COLUMNS, PG_STATS_COLUMNS, check_fit, check_fit_batch, check_gae, check_pg, check_pg_loop
+from .policy_ref import (FIT_STATS_COLUMNS, PG_STATS_COLUMNS, adv_normalize_work_bytes, check_adv_normalize, check_fit, check_fit_batch,
+                         check_gae, check_max_grad_norm, check_pg, check_pg_loop)
 from .policy_spec import n_params
 
 
@@ -40,14 +45,16 @@ def _pointer(x, typestrs, what):
 
 class PolicyFit(_DeviceObject):
     """A supervised fit of ``policy`` (a ``DevicePolicy``) on its GPU: ``lr`` and Adam's ``beta1``, ``beta2``, ``eps`` with the L2
-    penalty ``weight_decay`` (``check_adam``'s rules), and ``value_coef``, the weight of the value network's squared error.  The
+    penalty ``weight_decay`` (``check_adam``'s rules), ``value_coef``, the weight of the value network's squared error, and
+    ``max_grad_norm``, the bound every ``step`` holds the global norm of the mean gradient to (0, the default: none).  The
     master copy theta starts as the policy's parameters; every ``step`` writes float32(theta) back into the policy, whose ``act``
     and rollouts then run the fitted network with no further call.  ``policy.set_params`` does NOT reach theta: follow it with
     ``set_state(theta=...)``.  The policy must stay open while the fit is.  Not thread-safe, one stream at a time."""
     _kind, _what = "fit", "policy fit"
 
-    def __init__(self, policy, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, value_coef=0.5):
+    def __init__(self, policy, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, value_coef=0.5, max_grad_norm=0.0):
         args = check_fit(lr, beta1, beta2, eps, weight_decay, value_coef)          # (before the handle exists: a bad one leaves none)
+        max_grad_norm = check_max_grad_norm(max_grad_norm)
         self.policy = policy
         self.n_params = n_params(policy.spec)
         self._lr, self.adam, self.value_coef = args[0], args[1:5], args[5]
@@ -58,6 +65,9 @@ class PolicyFit(_DeviceObject):
         self._p = h
         self._out = self._source = None
         self._kept = ()
+        self._max_grad_norm = 0.0
+        if max_grad_norm:
+            self.max_grad_norm = max_grad_norm
 
     def close(self):
         super(PolicyFit, self).close()
@@ -129,8 +139,15 @@ class PolicyFit(_DeviceObject):
 
     def step(self, stream=0):
         """One Adam step of the mean gradient since the last one, then float32(theta) into the policy: three launches on
-        ``stream``, no copy, no synchronisation, capturable.  Nothing moves when no sample has contributed."""
+        ``stream`` - four with ``max_grad_norm`` set, the gradient's global norm in front -, no copy, no synchronisation,
+        capturable.  Nothing moves when no sample has contributed."""
         check(self._lib.bsk_fit_step(self._handle(), C.c_void_p(int(stream or 0))))
+
+    def apply_obs_norm(self, stats, std_min=1e-6, stream=0):
+        """in_scale / in_shift out of an ``ObsStats`` (``obs_norm_ref``) into theta[0:10] - which no step moves - and float32(theta)
+        into the policy (``bsk_fit_apply_obs_norm``): two launches on ``stream``, no copy, no synchronisation, capturable.  While
+        nothing has been counted theta keeps what it has; theta[10:], m and v are never touched."""
+        check(self._lib.bsk_fit_apply_obs_norm(self._handle(), stats._handle(), float(std_min), C.c_void_p(int(stream or 0))))
 
     # ------------------------------------------------------------------ what it holds
     def stats_ptr(self):
@@ -145,9 +162,23 @@ class PolicyFit(_DeviceObject):
         check(self._lib.bsk_fit_pg_stats_device(self._handle(), C.byref(p)))
         return p.value
 
-    def _row(self, ptr):
+    def grad_norm_ptr(self):
+        """{norm, scale} of the last ``step`` taken with ``max_grad_norm`` set as a DEVICE pointer to 2 float64, valid until
+        ``close``."""
+        p = C.c_void_p()
+        check(self._lib.bsk_fit_grad_norm_device(self._handle(), C.byref(p)))
+        return p.value
+
+    def grad_norm(self):
+        """-> dict ``norm`` (the global norm of the last clipped step's mean gradient, before clipping) and ``scale`` (what the
+        step multiplied it by: exactly 1.0 while the norm was within ``max_grad_norm``); (0.0, 1.0) before the first.  A host read:
+        synchronises."""
+        row = self._row(self.grad_norm_ptr(), 2)
+        return {"norm": float(row[0]), "scale": float(row[1])}
+
+    def _row(self, ptr, words=4):
         from . import _hip
-        row = np.empty(4, np.float64)
+        row = np.empty(words, np.float64)
         self.sync()                                # (everything queued has written the row)
         with _hip.device_guard(self.device):
             _hip.check(_hip.runtime().hipMemcpyAsync(C.c_void_p(row.ctypes.data), C.c_void_p(ptr), row.nbytes,
@@ -198,6 +229,18 @@ class PolicyFit(_DeviceObject):
         check(self._lib.bsk_fit_set_lr(self._handle(), value))
         self._lr = value
 
+    @property
+    def max_grad_norm(self):
+        """The bound on the global norm of the mean gradient a ``step`` enforces (``bsk_fit_set_max_grad_norm``; PPO2: 0.5), or 0:
+        no clip, and ``step`` launches what it launches without one."""
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        value = check_max_grad_norm(value)
+        check(self._lib.bsk_fit_set_max_grad_norm(self._handle(), value))
+        self._max_grad_norm = value
+
 
 def gae(reward_hist, reason_hist, value_hist, last_value, n_steps, n_envs, adv, ret=None, gamma=0.99, lam=0.95, stride=None, stream=0):
     """``bsk_gae``: generalised advantage estimation over the histories of a rollout, one launch on ``stream`` of the current device,
@@ -218,6 +261,29 @@ def gae(reward_hist, reason_hist, value_hist, last_value, n_steps, n_envs, adv, 
                               C.c_void_p(int(stream or 0))))
 
 
+def normalize_advantages(adv, rows, n, out=None, alive=None, eps=1e-8, stride=None, work=None, stream=0):
+    """``bsk_adv_normalize``: (A - mean) / (sd + eps) over the block ``adv`` float32 [rows][stride] (``stride`` defaults to ``n``)
+    - the rows of one minibatch - into ``out`` (None: in place); ``alive`` uint8 [rows][stride] or None (every sample counts;
+    a sample that does not count becomes 0).  ``work``: a device buffer of ``adv_normalize_work_bytes(n)`` bytes, whose first four
+    float64 are afterwards mean, sd, 1 / (sd + eps) and the number of samples.  Each a raw device pointer or anything with
+    ``__cuda_array_interface__``.  Three launches on ``stream`` of the current device, no copy, no synchronisation, no allocation
+    (``policy_ref.adv_normalize_ref``, equal bit for bit)."""
+    rows, n, stride, eps = check_adv_normalize(rows, n, n if stride is None else stride, eps)
+    if work is None:
+        raise ValueError("work: a device buffer of adv_normalize_work_bytes(n) bytes is required")
+    ptrs = []
+    for x, types, what, need in ((adv, ("<f4",), "advantages", rows * stride), (alive, ("|u1", "|b1"), "alive", rows * stride),
+                                 (adv if out is None else out, ("<f4",), "out", rows * stride),
+                                 (work, ("<f8", "|u1", "<u8"), "work", None)):
+        ptr, size, _ = _pointer(x, types, what)
+        if need is None and size is not None:
+            size, need = size * int(x.__cuda_array_interface__["typestr"][2:]), adv_normalize_work_bytes(n)
+        if size is not None and size < need:
+            raise ValueError("%s: at least %d elements, got %d" % (what, need, size))
+        ptrs.append(C.c_void_p(ptr) if ptr else None)
+    check(_lib.load().bsk_adv_normalize(ptrs[0], ptrs[1], rows, n, stride, eps, ptrs[2], ptrs[3], C.c_void_p(int(stream or 0))))
+
+
 class PolicyGradient(object):
     """On-device policy-gradient training (PPO; the clipped surrogate of ``bsk_fit_accumulate_pg`` on advantages from ``bsk_gae``):
     ``env`` - a ``BatchedPropagator`` (or an env over one) created with ``FLAG_AUTO_RESET`` -, ``policy`` - a ``DevicePolicy`` with a
@@ -225,13 +291,28 @@ class PolicyGradient(object):
     ``substeps`` under the sampled policy, then values and advantages - and ``update()`` - ``epochs`` passes over ``minibatches``
     groups of consecutive time rows, one ``accumulate_pg`` per row and one Adam step per group.  Everything is enqueued on the
     env's stream from buffers allocated here: neither allocates, copies to or from the host or synchronises; ``iterate`` waits
-    once, at its end, for the log.  ``close()`` frees the buffers (not the env, the policy or the fit)."""
+    once, at its end, for the log.  ``close()`` frees the buffers (not the env, the policy or the fit).
 
-    def __init__(self, env, policy, fit, n_steps, gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, epochs=4, minibatches=4, substeps=1):
+    PPO2's conditioning of the update, each off by default and leaving the launches above as they are when off:
+    ``normalize_advantages`` - behind ``bsk_gae`` every minibatch's group of rows is normalised on its own (``bsk_adv_normalize``)
+    into a second buffer ``adv_norm``, which ``update()`` then reads (``adv`` keeps the raw estimate; the groups are the same in every
+    epoch); ``obs_stats`` - an ``ObsStats`` attached to the policy here and detached by ``close()``, fed by the rollouts, and turned
+    into the policy's in_scale / in_shift (``fit.apply_obs_norm(obs_stats, std_min)``) at the START of ``collect()``, never between a
+    rollout and its update, so that the first minibatch still sees ratio 1; and, when ``fit.max_grad_norm`` is set at the time of
+    ``update()``, the {norm, scale} row of every step in ``grad_norms``, float64 (epochs * minibatches, 2), after ``iterate()``
+    (None otherwise)."""
+
+    def __init__(self, env, policy, fit, n_steps, gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, epochs=4, minibatches=4, substeps=1,
+                 normalize_advantages=False, obs_stats=None, std_min=1e-6):
         from . import _hip
         from ._lib import FLAG_AUTO_RESET
         (self.n_steps, self.gamma, self.lam, self.clip, self.ent_coef, self.epochs, self.minibatches,
          self.substeps) = check_pg_loop(n_steps, gamma, lam, clip, ent_coef, epochs, minibatches, substeps)
+        self.normalize_advantages, self.obs_stats, self.std_min = bool(normalize_advantages), obs_stats, float(std_min)
+        if not np.isfinite(self.std_min) or not (self.std_min > 0.0):
+            raise ValueError("std_min must be finite and positive")
+        self.grad_norms = None
+        self._clipped = False
         prop = getattr(env, "propagator", env)
         if not (prop.cfg.flags & FLAG_AUTO_RESET):
             raise ValueError("the env must be created with FLAG_AUTO_RESET: episodes restart inside the rollout")
@@ -245,7 +326,14 @@ class PolicyGradient(object):
         T, n = self.n_steps, prop.n_envs
         self.n_envs = n
         sizes = {"obs": 8 * (T + 1) * 5 * n, "reward": 8 * T * n, "reason": T * n, "action": 4 * T * n, "logp": 4 * T * n,
-                 "value": 4 * T * n, "last_value": 4 * n, "adv": 4 * T * n, "ret": 8 * T * n, "log": 64 * self.epochs * T}
+                 "value": 4 * T * n, "last_value": 4 * n, "adv": 4 * T * n, "ret": 8 * T * n, "log": 64 * self.epochs * T,
+                 "grad_norm_log": 16 * self.epochs * self.minibatches}
+        if self.normalize_advantages:
+            sizes.update(adv_norm=4 * T * n, adv_work=adv_normalize_work_bytes(n))
+        if obs_stats is not None:
+            if obs_stats.n_envs < n or obs_stats.device != prop.device:
+                raise ValueError("obs_stats: a statistics object of at least %d envs on device %d" % (n, prop.device))
+            policy.set_obs_stats(obs_stats)                # (the rollouts of collect() feed it from now on)
         self._buf = {k: _hip.DeviceBuffer(b, prop.device) for k, b in sizes.items()}
         # Whatever a first launch would allocate, here: the fit's scratch of block gradients for n samples, by an accumulate of zeros in
         # which no sample is alive - it adds +0.0 to every accumulator and nothing to the count.
@@ -262,6 +350,8 @@ class PolicyGradient(object):
             for b in self._buf.values():
                 b.free()
             self._buf = None
+            if self.obs_stats is not None:
+                self.policy.set_obs_stats(None)
 
     def __enter__(self):
         return self
@@ -273,15 +363,22 @@ class PolicyGradient(object):
     def buffers(self):
         """-> the device pointers of the loop's buffers by name: ``obs`` f64[n_steps + 1][5][n] (row t: what the action of step t
         was chosen from), ``reward`` f64, ``reason`` u8, ``action`` i32, ``logp`` f32, ``value`` f32, ``adv`` f32, ``ret`` f64
-        [n_steps][n], ``last_value`` f32[n], ``log`` f64[epochs][n_steps][8] (the two diagnostics rows of every accumulate)"""
+        [n_steps][n], ``last_value`` f32[n], ``log`` f64[epochs][n_steps][8] (the two diagnostics rows of every accumulate),
+        ``grad_norm_log`` f64[epochs * minibatches][2] (written under ``fit.max_grad_norm`` only) and, with
+        ``normalize_advantages``, ``adv_norm`` f32[n_steps][n] - every minibatch's rows normalised on their own, what ``update()``
+        reads - and ``adv_work``, the scratch of ``bsk_adv_normalize``"""
         return {k: b.ptr for k, b in self._buf.items()}
 
     def collect(self):
         """The handle's observation into row 0, a sampled rollout of ``n_steps`` that fills the histories (observations from row 1),
-        the value of the observation the handle holds afterwards, and ``bsk_gae``: all enqueued on the env's stream."""
+        the value of the observation the handle holds afterwards, and ``bsk_gae``: all enqueued on the env's stream.  In front of
+        all of it, with ``obs_stats``: the statistics so far into the policy's input normalisation; behind all of it, with
+        ``normalize_advantages``: every minibatch's rows of ``adv`` normalised into ``adv_norm``."""
         from . import _hip
         prop, b, T, n = self.prop, self._buf, self.n_steps, self.n_envs
         stream = prop.stream_ptr()
+        if self.obs_stats is not None:
+            self.fit.apply_obs_norm(self.obs_stats, self.std_min, stream)
         views = prop.device_views()
         obs, stride = views["obs"].__cuda_array_interface__["data"][0], views["stride"]
         with _hip.device_guard(prop.device):
@@ -291,13 +388,22 @@ class PolicyGradient(object):
             self.policy.value_enqueue(obs, stride, n, b["last_value"].ptr, stream)
             gae(b["reward"].ptr, b["reason"].ptr, b["value"].ptr, b["last_value"].ptr, T, n, b["adv"].ptr, b["ret"].ptr, self.gamma,
                 self.lam, stream=stream)
+            if self.normalize_advantages:
+                rows = T // self.minibatches
+                for g in range(self.minibatches):
+                    normalize_advantages(b["adv"].ptr + 4 * n * rows * g, rows, n, b["adv_norm"].ptr + 4 * n * rows * g,
+                                         work=b["adv_work"].ptr, stream=stream)
 
     def update(self):
         """``epochs`` passes of ``minibatches`` groups of consecutive time rows: per row one ``accumulate_pg`` of the n envs and its
         two diagnostics rows into the log, device to device (a row is one accumulate's: ``iterate`` adds a group's on the host,
-        behind its wait); per group one ``fit.step()``."""
+        behind its wait); per group one ``fit.step()`` and, under ``fit.max_grad_norm``, its {norm, scale} row into a log of its
+        own."""
         from . import _hip
         prop, b, n, fit = self.prop, self._buf, self.n_envs, self.fit
+        adv = b["adv_norm" if self.normalize_advantages else "adv"].ptr
+        self._clipped = fit.max_grad_norm > 0.0
+        gn_row = fit.grad_norm_ptr() if self._clipped else None
         stream, rows = prop.stream_ptr(), self.n_steps // self.minibatches
         rt, vp = _hip.runtime(), C.c_void_p
         pg_row, fit_row = fit.pg_stats_ptr(), fit.stats_ptr()
@@ -306,7 +412,7 @@ class PolicyGradient(object):
             for _ in range(self.epochs):
                 for g in range(self.minibatches):
                     for t in range(g * rows, (g + 1) * rows):
-                        fit.accumulate_pg(b["obs"].ptr + 8 * 5 * n * t, b["action"].ptr + 4 * n * t, b["adv"].ptr + 4 * n * t,
+                        fit.accumulate_pg(b["obs"].ptr + 8 * 5 * n * t, b["action"].ptr + 4 * n * t, adv + 4 * n * t,
                                           b["logp"].ptr + 4 * n * t, self.clip, self.ent_coef, b["ret"].ptr + 8 * n * t, None,
                                           n=n, stride=n, stream=stream)
                         for k, src in enumerate((pg_row, fit_row)):
@@ -314,18 +420,28 @@ class PolicyGradient(object):
                                                          _hip.hipMemcpyDeviceToDevice, vp(stream)), "hipMemcpyAsync")
                         slot += 1
                     fit.step(stream)
+                    if self._clipped:
+                        _hip.check(rt.hipMemcpyAsync(vp(b["grad_norm_log"].ptr + 16 * (slot // rows - 1)), vp(gn_row), 16,
+                                                     _hip.hipMemcpyDeviceToDevice, vp(stream)), "hipMemcpyAsync")
 
     def iterate(self):
         """``collect()`` then ``update()`` -> float64 (epochs * minibatches, 8): per minibatch ``PG_STATS_COLUMNS`` then
-        ``FIT_STATS_COLUMNS``, each the sum over the minibatch's rows in their order, formed after the one wait at the end."""
+        ``FIT_STATS_COLUMNS``, each the sum over the minibatch's rows in their order, formed after the one wait at the end.
+        ``grad_norms`` is afterwards the {norm, scale} row of every step, float64 (epochs * minibatches, 2), or None without
+        ``fit.max_grad_norm``."""
         from . import _hip
         out = np.empty((self.epochs * self.minibatches, self.n_steps // self.minibatches, 8), np.float64)
         self.collect()
         self.update()
+        norms = np.empty((self.epochs * self.minibatches, 2), np.float64) if self._clipped else None
         with _hip.device_guard(self.prop.device):
+            if norms is not None:
+                _hip.check(_hip.runtime().hipMemcpyAsync(C.c_void_p(norms.ctypes.data), C.c_void_p(self._buf["grad_norm_log"].ptr), norms.nbytes,
+                                                         _hip.hipMemcpyDeviceToHost, C.c_void_p(self.prop.stream_ptr())), "hipMemcpyAsync")
             _hip.check(_hip.runtime().hipMemcpyAsync(C.c_void_p(out.ctypes.data), C.c_void_p(self._buf["log"].ptr), out.nbytes,
                                                      _hip.hipMemcpyDeviceToHost, C.c_void_p(self.prop.stream_ptr())), "hipMemcpyAsync")
         self.prop.sync()
+        self.grad_norms = norms
         log = np.zeros((out.shape[0], 8), np.float64)
         for k in range(out.shape[1]):
             log = log + out[:, k]

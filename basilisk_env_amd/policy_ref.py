@@ -1166,22 +1166,69 @@ def fit_stats_ref(spec, params, obs, labels, alive=None, value_targets=None):
     return np.array([row[0], row[1], float((on & (greedy == labels)).sum()), float(on.sum())], np.float64)
 
 
-def fit_step_ref(theta, m, v, beta_pow, steps, A, count, lr, beta1, beta2, eps, weight_decay, n_update=None):
+FIT_GNORM_BLOCK = 1024                         # threads of the one workgroup under the gradient's global norm
+
+
+def check_max_grad_norm(max_grad_norm):
+    """The argument rule of ``bsk_fit_set_max_grad_norm`` -> the float: 0 (off) or finite and positive; ValueError where it returns
+    BSK_EINVAL.  Needs no device."""
+    max_grad_norm = float(max_grad_norm)
+    if not np.isfinite(max_grad_norm) or max_grad_norm < 0.0:
+        raise ValueError("max_grad_norm must be 0 (off) or finite and positive")
+    return max_grad_norm
+
+
+def fit_grad_norm_ref(A, count, n_update, max_norm):
+    """The row ``bsk_fit_step`` leaves behind ``bsk_fit_grad_norm_device`` under ``bsk_fit_set_max_grad_norm(max_norm)`` ->
+    (norm, scale) float64: g_q = A[10 + q] / count for q = 0 .. n_update - 11; thread i of 1 024 adds g_q * g_q for q = i, i + 1024,
+    ... ascending from the first (+0.0 with none); each of the 16 waves joins its 64 in the fitness tree; the wave sums are added
+    ascending; norm = sqrt(S), scale = max_norm / (norm if norm > max_norm else max_norm).  count == 0: (+0.0, 1.0)."""
+    max_norm = np.float64(check_max_grad_norm(max_norm))
+    if not max_norm > 0.0:
+        raise ValueError("max_norm must be positive: with 0 the step forms no norm")
+    if int(count) == 0:
+        return np.float64(0.0), np.float64(1.0)
+    A = np.asarray(A, np.float64).reshape(-1)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore", under="ignore"):
+        g = A[10:int(n_update)] / np.float64(int(count))
+        gg = g * g
+        s = np.zeros(FIT_GNORM_BLOCK, np.float64)
+        s[:min(FIT_GNORM_BLOCK, gg.size)] = gg[:FIT_GNORM_BLOCK]
+        for at in range(FIT_GNORM_BLOCK, gg.size, FIT_GNORM_BLOCK):
+            chunk = gg[at:at + FIT_GNORM_BLOCK]
+            s[:chunk.size] = s[:chunk.size] + chunk
+        s = s.reshape(FIT_GNORM_BLOCK // 64, 64)
+        for stride in _TREE:
+            s[:, :stride] = s[:, :stride] + s[:, stride:2 * stride]
+        S = s[0, 0]
+        for w in range(1, s.shape[0]):
+            S = S + s[w, 0]
+        norm = np.sqrt(S)
+        scale = max_norm / (norm if norm > max_norm else max_norm)
+    return np.float64(norm), np.float64(scale)
+
+
+def fit_step_ref(theta, m, v, beta_pow, steps, A, count, lr, beta1, beta2, eps, weight_decay, n_update=None, max_grad_norm=0.0):
     """What ``bsk_fit_step`` leaves -> (theta, m, v, beta_pow, steps, A, count), float64: nothing moves while count == 0; otherwise
     for p in 10 .. n_update - 1 (default: all; the action network's end when no accumulate since the last step carried value
     targets) g = A_p / count + weight_decay * theta_p, Adam's lines (``_adam_step_ref``, the evolution strategy's) and
-    theta_p = theta_p - step: a descent.  beta_pow and steps move on; A and the count come back zero."""
+    theta_p = theta_p - step: a descent.  beta_pow and steps move on; A and the count come back zero.  ``max_grad_norm`` > 0
+    (``bsk_fit_set_max_grad_norm``): g = (A_p / count) * scale + weight_decay * theta_p with ``fit_grad_norm_ref``'s scale."""
     theta = np.array(theta, dtype=np.float64).reshape(-1)
     m, v = np.array(m, dtype=np.float64).reshape(-1), np.array(v, dtype=np.float64).reshape(-1)
     bp = np.array(beta_pow, dtype=np.float64).reshape(2)
     A = np.array(A, dtype=np.float64).reshape(-1)
     lr, b1, b2, eps, wd, _ = (np.float64(x) for x in check_fit(lr, beta1, beta2, eps, weight_decay, 0.0))
+    max_grad_norm = check_max_grad_norm(max_grad_norm)
     hi = theta.size if n_update is None else int(n_update)
     if int(count) == 0:
         return theta, m, v, bp, int(steps), np.zeros_like(A), 0
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         t = theta[10:hi]
-        g = A[10:hi] / np.float64(int(count)) + wd * t
+        if max_grad_norm > 0.0:
+            g = (A[10:hi] / np.float64(int(count))) * fit_grad_norm_ref(A, count, hi, max_grad_norm)[1] + wd * t
+        else:
+            g = A[10:hi] / np.float64(int(count)) + wd * t
         m[10:hi], v[10:hi], step, bp = _adam_step_ref(m[10:hi], v[10:hi], bp, g, lr, b1, b2, eps)
         theta[10:hi] = t - step
     return theta, m, v, bp, int(steps) + 1, np.zeros_like(A), 0
@@ -1253,6 +1300,66 @@ def gae_ref(reward, reason, value, last_value=None, gamma=0.99, lam=0.95):
             ret[t] = carry + v
             next_v = v
     return adv, ret
+
+
+def adv_normalize_work_bytes(n):
+    """``bsk_adv_normalize_work_bytes``: 8 * (4 + 3 * ceil(n / 64)), the device bytes ``bsk_adv_normalize`` needs for n columns."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError("n must be an integer >= 1, got %r" % (n,))
+    return 8 * (4 + 3 * ((int(n) + 63) // 64))
+
+
+def check_adv_normalize(rows, n, stride, eps):
+    """The argument rules of ``bsk_adv_normalize`` that need no device -> (rows, n, stride, eps); ValueError where it returns
+    BSK_EINVAL."""
+    for what, x in (("rows", rows), ("n", n), ("stride", stride)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
+            raise ValueError("%s must be an integer >= 1, got %r" % (what, x))
+    if stride < n:
+        raise ValueError("stride must be >= n")
+    if int(rows) * int(stride) > 2 ** 31:
+        raise ValueError("rows * stride must not exceed 2^31")
+    eps = float(eps)
+    if not np.isfinite(eps) or not (eps > 0.0):
+        raise ValueError("eps must be finite and positive")
+    return int(rows), int(n), int(stride), eps
+
+
+def adv_normalize_ref(adv, alive=None, eps=1e-8):
+    """``bsk_adv_normalize`` restated: ``adv`` float32 (rows, n), ``alive`` (rows, n) or None (every sample counts) ->
+    (out float32 (rows, n), moments float64 (4,) = mean, sd, inv, N).  Float64, every operation rounded on its own: per column the
+    rows ascending, a1 = a1 + x and a2 = a2 + x * x from +0.0 with +0.0 for a sample that does not count; per wave of 64 columns
+    the fitness tree; the waves joined by ``obs_stats_totals_ref``'s rule; ``obs_moments_ref``'s mean and var; sd = sqrt(var),
+    inv = 1 / (sd + eps); out = float32((x - mean) * inv), +0.0 where the sample does not count.  With N == 0 the moments are four
+    +0.0 and ``out`` is ``adv`` as it was (the device writes nothing).  Bit for bit the device's."""
+    adv = np.asarray(adv, np.float32)
+    if adv.ndim != 2:
+        raise ValueError("advantages: (rows, n)")
+    rows, n = adv.shape
+    rows, n, _, eps = check_adv_normalize(rows, n, n, eps)
+    counts = np.ones((rows, n), bool) if alive is None else np.asarray(alive).reshape(rows, n) != 0
+    W = (n + 63) // 64
+    xd = np.zeros((rows, W * 64), np.float64)
+    xd[:, :n] = np.where(counts, adv.astype(np.float64), 0.0)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore", divide="ignore"):
+        a = np.zeros((2, W * 64), np.float64)
+        for t in range(rows):
+            a[0] = a[0] + xd[t]
+            a[1] = a[1] + xd[t] * xd[t]
+        s = a.reshape(2, W, 64)
+        for stride in _TREE:
+            s[:, :, :stride] = s[:, :, :stride] + s[:, :, stride:2 * stride]
+        part = np.zeros((W, 10), np.float64)
+        part[:, 0], part[:, 5] = s[0, :, 0], s[1, :, 0]
+        tot, _ = obs_stats_totals_ref((part, np.zeros(W, np.uint64)))
+        N = int(counts.sum())
+        if N == 0:
+            return adv.copy(), np.zeros(4, np.float64)
+        mean, var = (x[0] for x in obs_moments_ref(tot, N))
+        sd = np.sqrt(var)
+        inv = np.float64(1.0) / (sd + np.float64(eps))
+        out = np.where(counts, ((adv.astype(np.float64) - mean) * inv).astype(np.float32), np.float32(0.0))
+    return out.astype(np.float32), np.array([mean, sd, inv, np.float64(N)], np.float64)
 
 
 def pg_clip_edges(clip):

@@ -1169,6 +1169,57 @@ int bsk_fit_accumulate_pg(bsk_fit* f, const double* d_obs, int64_t obs_stride, i
  * lifetime; zero before the first).  No launch, no copy, no synchronisation. */
 int bsk_fit_pg_stats_device(bsk_fit* f, const double** d_row4);
 
+/* The two things stable-baselines' PPO2 does to every minibatch beyond the clipped surrogate, and the observation normalisation of
+ * the evolution strategy for the fit.  All three are off until asked for; without them every entry point above issues the launches,
+ * with the arguments, it issued before.  Both reductions are f64 in a fixed order, every operation rounded on its own (no FMA), no
+ * atomics: basilisk_env_amd/policy_ref.py repeats them bit for bit (adv_normalize_ref, fit_grad_norm_ref, fit_step_ref).
+ *
+ * Advantage normalisation, (A - mean) / (sd + eps) over a block d_adv f32[rows][stride] of which the columns below n are used - the
+ * rows of one minibatch out of bsk_gae.  d_alive uint8[rows][stride] or NULL; a sample COUNTS when its column is below n and its alive
+ * byte is non-zero (NULL: all are).  d_out f32[rows][stride] may be d_adv.  THREE launches, W = ceil(n / 64):
+ *  partial sums - wave w is the columns 64 w .. 64 w + 63, lane l the column c = 64 w + l; from a1 = a2 = +0.0 and k = 0 the lane walks
+ *   t = 0 .. rows - 1 ascending:  xd = counts ? (double)adv[t][c] : +0.0;  a1 = a1 + xd;  a2 = a2 + xd * xd (the product of two
+ *   widened floats is exact);  k = k + (counts ? 1 : 0).  a1 and a2 each through the fitness tree of the observation statistics
+ *   above (stride 32 ... 1), k through its integer twin;  part[w] = (a1[0], a2[0]), cnt[w] = k[0] - WRITTEN, not added to: nothing
+ *   is carried from call to call.
+ *  join - for each of the two columns of part: s[l] = part[l], or +0.0 when l >= W;  s[l] = s[l] + part[l + 64 m] for m = 1, 2, ...
+ *   ascending while l + 64 m < W;  the tree;  S1, S2 = s[0].  N = the integer sum of cnt.  With N == 0 the four words below become
+ *   +0.0 and d_out is NOT written.  Otherwise, as for an observation row:  mean = S1 / (double)N;  e2 = S2 / (double)N;
+ *   var = e2 - mean * mean;  var = var > 0 ? var : 0;  sd = sqrt(var);  inv = 1.0 / (sd + eps).
+ *  apply - a sample that counts:  out[t][c] = (float)(((double)adv[t][c] - mean) * inv);  any other with c < n:  +0.0f.  Columns at
+ *   and above n are neither read nor written.
+ * d_work: bsk_adv_normalize_work_bytes(n) = 8 * (4 + 3 W) bytes of device memory, 8-byte aligned, the caller's; after the call its
+ * first four f64 words are {mean, sd, inv, (double)N} and the rest is scratch (part, cnt).  Enqueued on `stream` of the current
+ * device: no copy, no synchronisation, no allocation; capturable from the first call.  All samples equal give sd = 0 and outputs
+ * of +-0 (or (x - mean) / eps where the mean's rounding leaves a difference): eps keeps them finite, as in PPO2.
+ * BSK_EINVAL before any launch: a NULL d_adv, d_out or d_work; rows < 1, n < 1, stride < n; rows * stride > 2^31; eps not finite or
+ * not positive.  bsk_adv_normalize_work_bytes returns 0 for n < 1. */
+int64_t bsk_adv_normalize_work_bytes(int n);
+int bsk_adv_normalize(const float* d_adv, const uint8_t* d_alive, int rows, int n, int64_t stride, double eps, float* d_out, void* d_work,
+                      void* stream);
+/* Clipping of the gradient's global norm inside bsk_fit_step (TensorFlow's clip_by_global_norm, PPO2's max_grad_norm).  max_norm = 0
+ * (the default) is off: bsk_fit_step is the three launches above.  Otherwise ONE launch goes in front of them, one workgroup of
+ * 1 024 threads over the parameters p = 10 .. n_upd - 1 the step moves (the action network's alone when no accumulate since the last
+ * step carried targets), f64, no FMA:
+ *   g_q = A[10 + q] / (double)count, the division of the step;  thread i:  s = g_i * g_i, or +0.0 when there is no q = i;
+ *   s = s + g_q * g_q for q = i + 1024, i + 2048, ... ascending;  each of the sixteen waves joins its 64 lanes in the fitness tree;
+ *   S = ((w_0 + w_1) + w_2) + ... + w_15;  norm = sqrt(S);  scale = max_norm / (norm > max_norm ? norm : max_norm)
+ *   - exactly 1.0 while norm <= max_norm (and for a NaN norm);  count == 0:  {norm, scale} = {+0.0, 1.0}.
+ * and the step uses  g = (A_p / (double)count) * scale + weight_decay * theta_p:  the L2 term is added behind the clip.  It follows
+ * that (1) with max_norm above the norm theta, m, v, beta_pow and the step counter are the unclipped step's bit for bit, since
+ * x * 1.0 is x; (2) the norm reported is the norm before clipping.
+ * BSK_EINVAL: a NULL fit; max_norm negative or not finite.  No launch; it holds for the steps enqueued from now on, and a captured
+ * graph keeps what it was captured with. */
+int bsk_fit_set_max_grad_norm(bsk_fit* f, double max_norm);
+/* {norm, scale} of the last step taken with clipping on, as DEVICE words f64[2] ({+0.0, 1.0} before the first; read-only for the
+ * caller; valid for the fit's lifetime).  No launch, no copy, no synchronisation. */
+int bsk_fit_grad_norm_device(bsk_fit* f, const double** d_row2);
+/* bsk_es_apply_obs_norm for the fit: the normalisation out of the totals of `stats` into the fit's f64 theta[0..9] - which no step
+ * moves - and (float)theta into the attached policy's device layout.  TWO launches on `stream`, no copy, no synchronisation,
+ * capturable.  While nothing has been counted theta is not written.  theta[10..], m and v are never touched.  BSK_EINVAL before
+ * anything is launched: NULL pointers, std_min not finite or not positive, fit and statistics on different devices. */
+int bsk_fit_apply_obs_norm(bsk_fit* f, bsk_obs_stats* stats, double std_min, void* stream);
+
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the
  * three-wave form's barrier-free exchange gives up after 2^20 polls instead of hanging, and says so here. */

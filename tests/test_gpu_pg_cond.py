@@ -1,0 +1,400 @@
+"""GPU: what conditions the policy-gradient update as PPO2 does - bsk_adv_normalize, the clip of the gradient's global norm inside
+bsk_fit_step (bsk_fit_set_max_grad_norm), bsk_fit_apply_obs_norm (csrc/bsk_fit.hip: adv_partial_kernel, adv_join_kernel,
+adv_apply_kernel, fit_gnorm_kernel, fit_adam_kernel<true>; definition in include/bskgpu.h) and ``policy.PolicyGradient`` with all
+three on.
+
+Both reductions are f64 additions, products, divisions and square roots in a fixed order: EQUAL to ``adv_normalize_ref`` /
+``fit_grad_norm_ref`` / ``fit_step_ref`` in every bit, for relu networks from the device's own output deltas as in
+tests/test_gpu_fit.py.  Shapes are the smallest at which each loop goes past its first trip: n = 65 is two waves of the partial
+sums, 4 097 sixty-five - the join's lanes in their second lap; rows = 7 leaves a tail behind no full batch of the row walk and
+rows = 9 (the in-place case of n = 300) one behind a full batch; 18 moved parameters are less than one lap of the norm's 1 024
+threads, 17 790 more than seventeen.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from _device_bits import download as _download, same as _same
+from _pg_cond_bounds import adv_case
+from _policy_bounds import observation_like, seeded_policy
+from basilisk_env_amd import _lib
+from basilisk_env_amd import policy as P
+from basilisk_env_amd._lib import FLAG_AUTO_RESET, GRAV_PM_J2
+from basilisk_env_amd.simulators.dynamics import BatchedPropagator, default_config
+from basilisk_env_amd.simulators.initial_conditions.batch import sample_ic_batch
+from test_gpu_fit import _batch, _dev, _Fit, _host
+from test_gpu_pg import _PG, _lp_of
+
+pytestmark = pytest.mark.gpu
+
+EINVAL = -1
+GUARD = 5                                      # words behind the work buffer that nobody may write
+
+
+def _work(n):
+    import torch
+    words = P.adv_normalize_work_bytes(n) // 8
+    assert words == 4 + 3 * ((n + 63) // 64)
+    return torch.full((words + GUARD,), -3.0, dtype=torch.float64, device="cuda")
+
+
+def _masks(rows, n, alive):
+    """the masks of a case by name: none, the random one, one that kills a whole wave (the first 64 columns; with one wave, all
+    columns but the last), one that kills everything"""
+    wave = np.ones((rows, n), np.uint8)
+    wave[:, :64 if n > 64 else n - 1] = 0
+    return {"none": None, "random": alive, "wave": wave, "all": np.zeros((rows, n), np.uint8)}
+
+
+# ------------------------------------------------------------------------------------------------------------------ bsk_adv_normalize
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 300, 4097])
+@pytest.mark.parametrize("rows", [1, 2, 7])
+def test_adv_normalize_equals_the_restatement_bit_for_bit(rows, n):
+    import torch
+    stride, eps = n + 3, 1e-8
+    for scale in (1e-3, 1e4):
+        adv, alive = adv_case(rows, n, rows * 10 + n, scale, masked=True)
+        for name, mask in _masks(rows, n, alive).items():
+            for in_place in (False, True):
+                padded = np.full((rows, stride), 9.0, np.float32)
+                padded[:, :n] = adv
+                d_adv, work = _dev(padded), _work(n)
+                d_out = d_adv if in_place else torch.full((rows, stride), -7.0, dtype=torch.float32, device="cuda")
+                d_alive = None
+                if mask is not None:
+                    full = np.ones((rows, stride), np.uint8)
+                    full[:, :n] = mask
+                    d_alive = _dev(full)
+                torch.cuda.synchronize()
+                P.normalize_advantages(d_adv, rows, n, None if in_place else d_out, d_alive, eps, stride, work)
+                torch.cuda.synchronize()
+                want, mom = P.adv_normalize_ref(adv, mask, eps)
+                got, w = d_out.cpu().numpy(), work.cpu().numpy()
+                where = (rows, n, scale, name, in_place)
+                assert _same(w[:4], mom), (where, w[:4], mom)
+                assert (w[-GUARD:] == -3.0).all(), where
+                if name == "all":                       # nothing counts: the moments are zero and out is untouched
+                    assert _same(mom, np.zeros(4)) and _same(got[:, :n], adv if in_place else np.full((rows, n), -7.0, np.float32)), where
+                else:
+                    assert mom[3] == (rows * n if mask is None else int((mask != 0).sum())) and _same(got[:, :n], want), where
+                assert (got[:, n:] == (9.0 if in_place else -7.0)).all(), where          # the padding is nobody's
+                if not in_place:
+                    assert _same(d_adv.cpu().numpy(), padded), where                     # the raw estimate stays
+    assert n < 65 or not _same(*[P.adv_normalize_ref(adv, m)[1] for m in (None, _masks(rows, n, alive)["wave"])])
+
+
+def test_adv_normalize_walks_past_a_full_batch_of_rows_in_place_on_a_raw_pointer():
+    """nine rows: one batch of eight loads side by side and a tail of one; raw pointers in place of arrays"""
+    import torch
+    rows, n = 9, 300
+    adv, alive = adv_case(rows, n, 77, masked=True)
+    d_adv, d_alive, work = _dev(adv), _dev(alive), _work(n)
+    torch.cuda.synchronize()
+    P.normalize_advantages(d_adv.data_ptr(), rows, n, alive=d_alive.data_ptr(), work=work.data_ptr())
+    torch.cuda.synchronize()
+    want, mom = P.adv_normalize_ref(adv, alive)
+    assert _same(d_adv.cpu().numpy(), want) and _same(work.cpu().numpy()[:4], mom) and mom[3] == (alive != 0).sum()
+
+
+def test_adv_normalize_refuses_bad_arguments_before_any_launch():
+    import torch
+    rows, n = 2, 70
+    lib = _lib.load()
+    adv, alive = adv_case(rows, n, 3, masked=True)
+    d_adv, d_alive, work = _dev(adv), _dev(alive), _work(n)
+    out = torch.full((rows, n), -7.0, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
+    good = [vp(d_adv), vp(d_alive), rows, n, n, 1e-8, vp(out), vp(work), None]
+    nan, inf = float("nan"), float("inf")
+    for at, bad in ((0, None), (6, None), (7, None), (2, 0), (2, -1), (3, 0), (4, n - 1), (5, 0.0), (5, -1e-8), (5, nan), (5, inf)):
+        args = list(good)
+        args[at] = bad
+        assert lib.bsk_adv_normalize(*args) == EINVAL, (at, bad)
+    # rows * stride above 2^31: refused on its arguments alone (2^31 itself is a valid size)
+    args = list(good)
+    args[2], args[3], args[4] = 2 ** 15, n, 2 ** 16 + 1
+    assert lib.bsk_adv_normalize(*args) == EINVAL and b"2^31" in lib.bsk_last_error()
+    torch.cuda.synchronize()
+    assert (out.cpu().numpy() == -7.0).all() and (work.cpu().numpy() == -3.0).all()
+    assert lib.bsk_adv_normalize(*good) == 0
+    torch.cuda.synchronize()
+    want, mom = P.adv_normalize_ref(adv, alive)
+    assert _same(out.cpu().numpy(), want) and _same(work.cpu().numpy()[:4], mom)
+    with pytest.raises(ValueError):
+        P.normalize_advantages(d_adv, rows, n, out, work=work, eps=0.0)
+    with pytest.raises(ValueError):
+        P.normalize_advantages(d_adv, rows, n, out, work=work[:5])
+    with pytest.raises(ValueError):
+        P.normalize_advantages(d_adv, rows + 1, n, out, work=work)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the clip
+KW = dict(lr=1e-2, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-3)
+CLIP_CASES = {"no_hidden": ((), None, False), "relu64": ((64,), None, False), "relu128x2_action": ((128, 128), (16,), False),
+              "relu128x2_value": ((128, 128), (16,), True)}
+
+
+def _accumulate(f, spec, now, k, with_targets, n=130):
+    """one accumulate on the device and the accumulators it leaves, by the restatement from the device's own output deltas"""
+    obs, labels, alive, targets = _batch(n, 80 + k)
+    targets = targets if with_targets else None
+    dl = f.accumulate(obs, labels, alive, targets)
+    dv = None if targets is None else P.fit_dlogits32_ref(spec, now, obs, labels, alive, targets, 0.5)[1]
+    on = (labels >= 0) & (labels <= 2) & (alive != 0)
+    return P.fit_accumulate_ref(np.zeros(now.size), 0, P.fit_backward_ref(spec, now, obs, dl, dv), on.sum())
+
+
+@pytest.mark.parametrize("case", list(CLIP_CASES))
+def test_a_clipped_step_equals_the_restatement_bit_for_bit(case):
+    """Three fits from one start: a bound a quarter of each step's norm, one four times it, and none.  Row and state of the first
+    two are the restatement's; the second's state is the third's (x * 1.0 is x), and the norm it reports is the norm of the
+    gradient as it was."""
+    hidden, vh, with_targets = CLIP_CASES[case]
+    spec, params = seeded_policy(hidden, "relu", vh, seed=31)
+    a_end = 10 + sum(o * i + o for o, i in P.layer_shapes(spec)[0])
+    n_upd = params.size if with_targets else a_end
+    assert n_upd - 10 == {"no_hidden": 18, "relu64": 579, "relu128x2_action": 17667, "relu128x2_value": 17780}[case]
+    fits = {factor: _Fit(spec, params, value_coef=0.5, **KW) for factor in (0.25, 4.0, None)}
+    states = {factor: (params.astype(np.float64), np.zeros(params.size), np.zeros(params.size), np.ones(2), 0) for factor in fits}
+    for k in range(2):
+        rows = {}
+        for factor, f in fits.items():
+            A, count = _accumulate(f, spec, states[factor][0].astype(np.float32), k, with_targets)
+            norm = P.fit_grad_norm_ref(A, count, n_upd, 1.0)[0]
+            assert norm > 0
+            max_norm = 0.0 if factor is None else float(norm) * factor
+            f.fit.max_grad_norm = max_norm
+            assert f.fit.max_grad_norm == max_norm
+            f.fit.step()
+            states[factor] = P.fit_step_ref(*states[factor], A, count, KW["lr"], KW["beta1"], KW["beta2"], KW["eps"], KW["weight_decay"],
+                                            n_update=n_upd, max_grad_norm=max_norm)[:5]
+            got = f.fit.state()
+            for i, name in enumerate(("theta", "m", "v", "beta_pow")):
+                assert _same(got[name], states[factor][i]), (case, k, factor, name)
+            assert got["steps"] == k + 1
+            if with_targets:
+                assert not np.array_equal(got["theta"][a_end:], params[a_end:].astype(np.float64))
+            else:
+                assert _same(got["theta"][a_end:], params[a_end:].astype(np.float64)) and not got["m"][a_end:].any()
+            if factor is not None:
+                row = f.fit.grad_norm()
+                want = P.fit_grad_norm_ref(A, count, n_upd, max_norm)
+                assert _same(np.float64(row["norm"]), want[0]) and _same(np.float64(row["scale"]), want[1]), (case, k, factor, row, want)
+                assert (row["scale"] == 1.0) == (factor > 1) and _same(np.float64(row["norm"]), norm)
+                rows[factor] = row
+        # the same start and the same batch: the norm before clipping is one number, whatever the bound (k = 0; afterwards the
+        # clipped fit has moved elsewhere)
+        if k == 0:
+            assert rows[0.25]["norm"] == rows[4.0]["norm"] and rows[0.25]["scale"] < 0.2500001
+        a, b = fits[4.0].fit.state(), fits[None].fit.state()
+        assert all(_same(a[name], b[name]) for name in ("theta", "m", "v", "beta_pow")) and a["steps"] == b["steps"]
+        assert not np.array_equal(fits[0.25].fit.state()["theta"], b["theta"])
+    # the row of a fit that never clipped: as created
+    assert fits[None].fit.grad_norm() == {"norm": 0.0, "scale": 1.0}
+    for f in fits.values():
+        f.close()
+
+
+def test_a_clipped_step_with_nothing_accumulated_leaves_zero_and_one_and_moves_nothing():
+    spec, params = seeded_policy((16,), "relu", (16,), seed=32)
+    f = _Fit(spec, params, max_grad_norm=1e-3, **KW)
+    assert f.fit.max_grad_norm == 1e-3
+    f.accumulate(*_batch(70, 90)[:3])
+    f.fit.step()
+    row, before = f.fit.grad_norm(), f.fit.state()
+    assert row["norm"] > 1e-3 and 0 < row["scale"] < 1 and before["steps"] == 1
+    f.fit.step()
+    row, after = f.fit.grad_norm(), f.fit.state()
+    assert _same(np.array([row["norm"], row["scale"]]), np.array([0.0, 1.0]))
+    assert all(_same(before[k], after[k]) for k in ("theta", "m", "v", "beta_pow")) and after["steps"] == 1
+    lib = _lib.load()
+    for bad in (-0.5, float("nan"), float("inf")):
+        assert lib.bsk_fit_set_max_grad_norm(f.fit._handle(), bad) == EINVAL, bad
+        with pytest.raises(ValueError):
+            f.fit.max_grad_norm = bad
+        with pytest.raises(ValueError):
+            P.PolicyFit(f.policy, max_grad_norm=bad)
+    assert f.fit.max_grad_norm == 1e-3 and lib.bsk_fit_grad_norm_device(f.fit._handle(), None) == EINVAL
+    f.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------ apply_obs_norm
+def test_fit_apply_obs_norm_writes_the_definition_into_theta_and_the_policy():
+    import torch
+    n = 1000
+    spec, params = seeded_policy((16,), "relu", (16,), seed=33)
+    f = _Fit(spec, params, **KW)
+    f.accumulate(*_batch(70, 91)[:3])
+    f.fit.step()                                             # (m and v hold something)
+    before = f.fit.state()
+    probe = observation_like(70, 9)
+    stats = P.ObsStats(n)
+
+    def runs(theta):
+        res = f.policy.act(_dev(probe), want=("logits", "value"))
+        torch.cuda.synchronize()
+        l, v = P.mlp_ref(spec, theta.astype(np.float32), probe)
+        return _same(_host(res["logits"]), l) and _same(_host(res["value"]), v)
+    # nothing counted yet: nothing changes
+    f.fit.apply_obs_norm(stats)
+    got = f.fit.state()
+    assert all(_same(before[k], got[k]) for k in ("theta", "m", "v", "beta_pow")) and runs(before["theta"])
+    rng = np.random.default_rng(12)
+    obs = observation_like(n, 5) + np.array([0.0, 5.0, -300.0, 1e-3, 0.0])[:, None]
+    obs[4] = 0.625                                           # a row that has not varied - and one that barely has
+    obs[3] = 1e-8 * (rng.random(n) - 0.5)
+    d_obs = _dev(obs)
+    torch.cuda.synchronize()
+    stats.accumulate(d_obs)
+    c0 = BatchedPropagator.debug_counters()
+    f.fit.apply_obs_norm(stats, std_min=1e-6)
+    assert BatchedPropagator.debug_counters() == c0          # no copy, no synchronisation
+    tot, count = P.obs_stats_totals_ref(P.obs_stats_accumulate_ref(P.obs_stats_zero_state(n), obs, None))
+    scale, shift = P.obs_norm_ref(tot, count, 1e-6)
+    got = f.fit.state()
+    assert count == n and _same(got["theta"][:10], np.r_[scale, shift]) and (scale[:3] > 0).all() and not scale[3:].any()
+    assert _same(got["theta"][10:], before["theta"][10:]) and all(_same(before[k], got[k]) for k in ("m", "v", "beta_pow"))
+    assert got["steps"] == before["steps"] and not _same(got["theta"][:10], before["theta"][:10])
+    assert runs(got["theta"]) and not runs(before["theta"])             # the policy's float32 block holds the rounded values
+    # the threshold is an argument; and the next step leaves the ten words alone
+    f.fit.apply_obs_norm(stats, std_min=1e-12)
+    s2, h2 = P.obs_norm_ref(tot, count, 1e-12)
+    assert s2[3] > 1e6 and _same(f.fit.state()["theta"][:10], np.r_[s2, h2])
+    f.fit.apply_obs_norm(stats, std_min=1e-6)
+    f.accumulate(*_batch(70, 92)[:3])
+    f.fit.step()
+    after = f.fit.state()
+    assert _same(after["theta"][:10], np.r_[scale, shift]) and after["steps"] == 2 and runs(after["theta"])
+    lib = _lib.load()
+    for args in ((None, stats._handle(), 1e-6), (f.fit._handle(), None, 1e-6), (f.fit._handle(), stats._handle(), 0.0),
+                 (f.fit._handle(), stats._handle(), float("nan")), (f.fit._handle(), stats._handle(), float("inf"))):
+        assert lib.bsk_fit_apply_obs_norm(*args, None) == EINVAL, args
+    assert _same(f.fit.state()["theta"], after["theta"])
+    f.close()
+    stats.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------ capture
+def test_normalize_accumulate_pg_and_a_clipped_step_replay_from_a_hip_graph():
+    import torch
+    T, n = 2, 130
+    spec, params = seeded_policy((32,), "relu", (16,), seed=15)
+    obs, actions, alive, targets = _batch(n, 60)
+    actions = np.clip(actions, 0, 2)
+    adv, adv_alive = adv_case(T, n, 61, masked=True)
+    old = (_lp_of(P.mlp_ref(spec, params, obs)[0], actions) + np.random.default_rng(61).normal(0.0, 0.3, n)).astype(np.float32)
+    side = torch.cuda.Stream()
+    d = {k: _dev(v) for k, v in dict(obs=obs, actions=actions, alive=alive, targets=targets, adv=adv, adv_alive=adv_alive, old=old).items()}
+    with torch.cuda.stream(side):
+        eager, replayed = (_PG(spec, params, lr=1e-2, weight_decay=1e-3, max_grad_norm=1e-3) for _ in range(2))
+        bufs = [(torch.zeros((T, n), dtype=torch.float32, device="cuda"), _work(n)) for _ in range(2)]
+
+        def launches(x, advn, work):
+            P.normalize_advantages(d["adv"], T, n, advn, d["adv_alive"], work=work, stream=side.cuda_stream)
+            x.fit.accumulate_pg(d["obs"], d["actions"], advn[1], d["old"], 0.2, 0.01, d["targets"], d["alive"], stream=side.cuda_stream)
+            x.fit.step(side.cuda_stream)
+        for _ in range(3):
+            launches(eager, *bufs[0])
+        launches(replayed, *bufs[1])                       # (warming: the first accumulate allocates the scratch)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        c0 = BatchedPropagator.debug_counters()
+        with torch.cuda.graph(graph, stream=side):
+            launches(replayed, *bufs[1])
+        for _ in range(2):
+            graph.replay()
+        torch.cuda.synchronize()
+        assert BatchedPropagator.debug_counters() == c0                # no copy, no synchronisation
+        a, b = eager.fit.state(), replayed.fit.state()
+        assert all(_same(a[k], b[k]) for k in ("theta", "m", "v", "beta_pow")) and a["steps"] == b["steps"] == 3
+        assert not np.array_equal(a["theta"], params.astype(np.float64))
+        assert eager.fit.stats() == replayed.fit.stats() and eager.fit.pg_stats() == replayed.fit.pg_stats()
+        row = eager.fit.grad_norm()
+        assert row == replayed.fit.grad_norm() and row["norm"] > 1e-3 and 0 < row["scale"] < 1
+        assert all(_same(x.cpu().numpy(), y.cpu().numpy()) for x, y in zip(*bufs))
+        want, mom = P.adv_normalize_ref(adv, adv_alive)
+        assert _same(bufs[1][0].cpu().numpy(), want) and _same(bufs[1][1].cpu().numpy()[:4], mom)
+        del graph
+        eager.close()
+        replayed.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------ the loop
+def test_policy_gradient_runs_conditioned_on_the_device_end_to_end():
+    """tests/test_gpu_pg.py's loop with everything on: normalised advantages, a clip at 0.5, observation statistics."""
+    import torch
+    n, T, std_min = 256, 8, 1e-6
+    spec, params = seeded_policy((16,), "relu", (16,), seed=16)
+    cfg = default_config(4, GRAV_PM_J2)
+    cfg.flags |= FLAG_AUTO_RESET
+    cfg.max_length = 5                                      # (episodes end, and start again, inside every rollout)
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        root = BatchedPropagator(cfg, n, stream=side.cuda_stream)
+        root.set_ic_pool(sample_ic_batch(23, 4, seed=73))
+        root.reset(sample_ic_batch(n, 4, seed=72))
+        root.step(np.zeros(n, np.int32), 1)                 # (the observation buffers hold a step's output)
+        steps, ticks = root.get_counters()
+        root.set_counters(steps + np.arange(n, dtype=np.int32) % 4, ticks)          # episodes end at different steps
+        f = _PG(spec, params, lr=1e-2)
+        f.fit.max_grad_norm = 0.5
+        stats = P.ObsStats(n)
+        with pytest.raises(ValueError):
+            small = P.ObsStats(n - 1)
+            try:
+                P.PolicyGradient(root, f.policy, f.fit, T, obs_stats=small)
+            finally:
+                small.close()
+        pg = P.PolicyGradient(root, f.policy, f.fit, T, gamma=0.97, lam=0.9, clip=0.2, ent_coef=0.01, epochs=2, minibatches=2, substeps=1,
+                              normalize_advantages=True, obs_stats=stats, std_min=std_min)
+        assert pg.grad_norms is None
+        f.policy.set_rng(3, 0)
+        torch.cuda.synchronize()
+        bufs = pg.buffers()
+        rows = T // 2
+        want_norm = params[:10].astype(np.float64)           # nothing counted before the first rollout: theta[0:10] stays
+        for it in range(2):
+            seen, wait = [], root.sync
+            root.sync = lambda: (seen.append(BatchedPropagator.debug_counters()), wait())[1]
+            c0 = BatchedPropagator.debug_counters()
+            log = pg.iterate()
+            root.sync = wait
+            assert seen and seen[0] == c0                   # up to the one wait behind the loop: no copy, no synchronisation
+            assert log.shape == (4, 8) and np.isfinite(log).all()
+            assert (log[:, 7] == rows * n).all()
+            assert _same(np.float64(log[0, 0]), np.float64(0.0)) and log[0, 2] == 0, (it, log[0])
+            assert (log[1:, 0] != 0).all(), (it, log[:, 0])
+            hist = {k: _download(bufs[k], dt, cnt) for k, dt, cnt in (("reward", np.float64, T * n), ("reason", np.uint8, T * n), ("value", np.float32, T * n),
+                                                                      ("last_value", np.float32, n), ("adv", np.float32, T * n),
+                                                                      ("adv_norm", np.float32, T * n))}
+            want_adv, _ = P.gae_ref(hist["reward"].reshape(T, n), hist["reason"].reshape(T, n), hist["value"].reshape(T, n),
+                                    hist["last_value"], 0.97, 0.9)
+            raw, normed = hist["adv"].reshape(T, n), hist["adv_norm"].reshape(T, n)
+            assert _same(raw, want_adv)                      # the raw estimate stays
+            for g in range(2):
+                want, mom = P.adv_normalize_ref(raw[g * rows:(g + 1) * rows])
+                assert mom[3] == rows * n and mom[1] > 0 and _same(normed[g * rows:(g + 1) * rows], want), (it, g)
+            assert (hist["reason"] != 0).any()
+            norms = pg.grad_norms
+            assert norms.shape == (4, 2) and norms.dtype == np.float64 and np.isfinite(norms).all() and (norms[:, 0] > 0).all()
+            assert (norms[:, 1] <= 1.0).all() and ((norms[:, 1] == 1.0) == (norms[:, 0] <= 0.5)).all(), norms
+            assert _same(norms[-1], np.array([f.fit.grad_norm()[k] for k in ("norm", "scale")]))
+            # collect() began with the statistics as they stood when it started
+            theta = f.fit.state()["theta"]
+            assert _same(theta[:10], want_norm), (it, theta[:10], want_norm)
+            tot, count = P.obs_stats_totals_ref(stats.state)
+            assert count == (it + 1) * T * n
+            want_norm = np.r_[P.obs_norm_ref(tot, count, std_min)]
+        assert not _same(want_norm, params[:10].astype(np.float64)) and not _same(theta[:10], params[:10].astype(np.float64))
+        st = f.fit.state()
+        assert st["steps"] == 8 and not np.array_equal(st["theta"][10:], params[10:].astype(np.float64))
+        # everything off: no second advantage buffer, no norms
+        plain = P.PolicyGradient(root, f.policy, f.fit, T)
+        assert plain.grad_norms is None and "adv_norm" not in plain.buffers() and "adv_work" not in plain.buffers()
+        plain.close()
+        pg.close()
+        f.close()
+        stats.close()
+        root.close()

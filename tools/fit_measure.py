@@ -22,6 +22,12 @@ same card.
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o pg -- python tools/fit_measure.py pg-kernel
       (a run of its own) 60 `accumulate_pg` + `step` pairs of that set-up on the null stream: the mean time of policy_logp_kernel,
       fit_block_kernel<true>, fit_fold_kernel<8> and the step's three kernels apart.
+  python tools/fit_measure.py cond
+      what conditions the update as PPO2 does ("Conditioning the update"), timed as under `time` on the `pg`
+      set-up: `accumulate_pg` alone, `accumulate_pg` + `step` and a `step` with nothing accumulated (with BSKGPU_LIB naming a
+      library built from the parent commit this is all that runs - the parent's bands, re-measured in the same session), then the
+      pair and the empty step with `max_grad_norm = 0.5`, then `bsk_adv_normalize` at 8 and at 32 rows of 65 536 against the 12 bytes
+      per sample it moves (4 read twice, 4 written).
 """
 import os
 import sys
@@ -190,5 +196,49 @@ def pg(trace=False):
     pol.close()
 
 
+def cond():
+    import torch
+    from _policy_bounds import observation_like, seeded_policy
+    from basilisk_env_amd import _lib
+    from basilisk_env_amd import policy as P
+    spec, params = seeded_policy(HIDDEN, "relu", (64,), seed=1)
+    obs = observation_like(N, 3)
+    rng = np.random.default_rng(5)
+    labels = np.where(obs[3] < 0.4, 1, np.where(obs[2] > 0.7, 2, 0)).astype(np.int32)
+    pol = P.DevicePolicy(spec, params)
+    fit = P.PolicyFit(pol, lr=1e-3)
+    side = torch.cuda.Stream()
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()      # noqa: E731
+    d_obs, d_lab, d_tgt = dev(obs), dev(labels), dev(rng.normal(size=N))
+    d_adv, d_old = dev(rng.normal(size=N).astype(np.float32)), dev((-1.1 + rng.normal(0.0, 0.3, N)).astype(np.float32))
+    s = side.cuda_stream
+    new = hasattr(_lib.load(), "bsk_adv_normalize")
+    with torch.cuda.stream(side):
+        def acc():
+            fit.accumulate_pg(d_obs, d_lab, d_adv, d_old, 0.2, 0.01, d_tgt, stream=s)
+
+        def step():                        # (a step moves something only behind an accumulate: the pair, minus the accumulate alone)
+            acc()
+            fit.step(s)
+        print("device  %-26s %8.1f us  (p10 %.1f, p90 %.1f)" % (("accumulate_pg alone",) + _timed(torch, side, acc)))
+        print("device  %-26s %8.1f us  (p10 %.1f, p90 %.1f)" % (("accumulate_pg + step",) + _timed(torch, side, step)))
+        print("device  %-26s %8.1f us  (p10 %.1f, p90 %.1f)" % (("step alone (count == 0)",) + _timed(torch, side, lambda: fit.step(s))))
+        if new:
+            fit.max_grad_norm = 0.5
+            print("device  %-26s %8.1f us  (p10 %.1f, p90 %.1f)" % (("accumulate_pg + clipped step",) + _timed(torch, side, step)))
+            print("device  %-26s %8.1f us  (p10 %.1f, p90 %.1f)" % (("clipped step alone (count == 0)",) + _timed(torch, side, lambda: fit.step(s))))
+            print("device  last clipped step: %r" % (fit.grad_norm(),))
+            for T in (8, 32):
+                d_a = dev(rng.normal(size=(T, N)).astype(np.float32))
+                d_o = torch.empty((T, N), dtype=torch.float32, device="cuda")
+                work = torch.empty(P.adv_normalize_work_bytes(N) // 8, dtype=torch.float64, device="cuda")
+                med, p10, p90 = _timed(torch, side, lambda: P.normalize_advantages(d_a, T, N, d_o, work=work, stream=s))
+                print("device  %-26s %8.1f us  (p10 %.1f, p90 %.1f): %.0f GB/s of its %.1f MB" % ("bsk_adv_normalize %d x 65536" % T, med, p10, p90,
+                                                                                              12.0 * T * N / med * 1e-3, 12.0 * T * N * 1e-6))
+    fit.close()
+    pol.close()
+
+
 if __name__ == "__main__":
-    {"time": time_, "kernel": kernel, "stamps": stamps, "pg": pg, "pg-kernel": lambda: pg(trace=True)}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
+    {"time": time_, "kernel": kernel, "stamps": stamps, "pg": pg, "pg-kernel": lambda: pg(trace=True),
+     "cond": cond}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
