@@ -102,6 +102,7 @@ EXPORTS = [
     "bsk_fit_set_state", "bsk_fit_set_lr", "bsk_fit_alive_mask",
     "bsk_gae", "bsk_fit_accumulate_pg", "bsk_fit_pg_stats_device",
     "bsk_adv_normalize_work_bytes", "bsk_adv_normalize", "bsk_fit_set_max_grad_norm", "bsk_fit_grad_norm_device", "bsk_fit_apply_obs_norm",
+    "bsk_pg_gather", "bsk_pg_shuffle_advance", "bsk_fit_accumulate_ppo", "bsk_fit_vclip_stats_device",
     "bsk_profile_begin", "bsk_profile_set_stride", "bsk_profile_end", "bsk_profile_end_samples", "bsk_calibrate_fp64", "bsk_kernel_info", "bsk_last_error", "bsk_version",
 ]
 
@@ -178,6 +179,10 @@ def _signatures():
         "bsk_adv_normalize_work_bytes": ([i], i64), "bsk_adv_normalize": ([vp, vp, i, i, i64, f64, vp, vp, vp], rc),
         "bsk_fit_set_max_grad_norm": ([vp, f64], rc), "bsk_fit_grad_norm_device": ([vp, P(vp)], rc),
         "bsk_fit_apply_obs_norm": ([vp, vp, f64, vp], rc),
+        "bsk_pg_gather": ([vp, i, i, i64, i64, i, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp], rc),
+        "bsk_pg_shuffle_advance": ([vp, vp], rc),
+        "bsk_fit_accumulate_ppo": ([vp, vp, i64, i, vp, vp, vp, f64, f64, vp, vp, f64, vp, vp, i64, vp, vp], rc),
+        "bsk_fit_vclip_stats_device": ([vp, P(vp)], rc),
         "bsk_profile_begin": ([vp, i], rc), "bsk_profile_set_stride": ([vp, i], rc), "bsk_profile_end": ([vp, P(f64), P(i)], rc),
         "bsk_profile_end_samples": ([vp, P(f64), P(i), vp, i], rc), "bsk_calibrate_fp64": ([i, i, i, P(f64), P(f64)], rc),
         "bsk_kernel_info": ([vp, C.c_char_p, i, P(i), P(i), P(i), P(i)], rc),

@@ -1,19 +1,22 @@
 // bsk_capi_fit.hip — C-ABI of the supervised fit of a policy to labelled observations (bsk_fit_*): accumulate block gradients of a
 // cross-entropy (and, optionally, a squared value error) from device buffers, then one Adam step into the attached policy's own
 // parameters; the same with a clipped policy-gradient loss in the cross-entropy's place (bsk_fit_accumulate_pg), and the advantage
-// estimator that feeds it from rollout histories (bsk_gae).  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_fit.hip.  The policy it reads and writes through
+// estimator that feeds it from rollout histories (bsk_gae); PPO2's clipped value loss on top of that (bsk_fit_accumulate_ppo) and the
+// shuffled minibatches it is fed (bsk_pg_gather, bsk_pg_shuffle_advance; kernels: bsk_shuffle.hip).  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_fit.hip.  The policy it reads and writes through
 // its handle: bsk_capi_policy.hpp.
 #include <cmath>
 
 #include "bsk_capi_policy.hpp"
 #include "bsk_fit.hpp"
+#include "bsk_shuffle.hpp"
 
 using namespace bsk::capi;
 
-// bsk_fit_*: ONE allocation of 8-byte words [theta np | m np | v np | beta_pow 2 | A np | row 4 | count | steps | pg_row 4 | gnorm_row 2]
-// and, from
-// the first accumulate on, the scratch of the block gradients: [G n_blocks * np floats | diag n_blocks * 8 doubles | lp 3 * 64
-// n_blocks floats] (a supervised launch uses the first 4 n_blocks of diag and no lp)
+// bsk_fit_*: ONE allocation of 8-byte words [theta np | m np | v np | beta_pow 2 | A np | row 4 | count | steps | pg_row 4 | gnorm_row 2 |
+// vclip_row 2] and, from
+// the first accumulate on, the scratch of the block gradients: [G n_blocks * np floats | diag n_blocks * 10 doubles | lp 3 * 64
+// n_blocks floats] (a supervised launch uses the first 4 n_blocks of diag and no lp, a policy-gradient launch without the value
+// clip the first 8 n_blocks)
 struct bsk_fit {
     bsk_policy* policy = nullptr;          // not owned: what accumulate reads and step writes
     int device = 0;
@@ -36,7 +39,8 @@ struct bsk_fit {
     unsigned long long* steps() const { return count() + 1; }
     double* pg_row() const { return d_state + 4 * np() + 8; }
     double* gnorm_row() const { return d_state + 4 * np() + 12; }          // {norm, scale} of the last clipped step
-    size_t words() const { return 4 * np() + 14; }
+    double* vclip_row() const { return d_state + 4 * np() + 14; }          // {value-clipped samples, sum of the unclipped d d / 2}
+    size_t words() const { return 4 * np() + 16; }
     // where the action network's parameters end in the C-ABI block: all a fit without value targets folds and moves
     int action_end() const {
         const bsk::PolicyLayout& lay = policy->lay;
@@ -59,7 +63,13 @@ struct PgLoss {
     const float* adv;
     const float* logp_old;
     float hi, lo, ec;
+    // bsk_fit_accumulate_ppo's three: with neither pointer the launches are bsk_fit_accumulate_pg's
+    const float* value_old;
+    float clip_vf;
+    float* dvalue;
 };
+
+constexpr size_t FIT_DIAG_WORDS = 10;      // doubles of diagnostics terms the scratch holds per block: the widest launch's
 
 // bsk_fit_accumulate (pg == nullptr) and bsk_fit_accumulate_pg: the block launch in either form, then the fold
 int accumulate(bsk_fit* f, const double* d_obs, int64_t obs_stride, int n, const int32_t* d_label, const double* d_value_target,
@@ -75,7 +85,7 @@ int accumulate(bsk_fit* f, const double* d_obs, int64_t obs_stride, int n, const
     const size_t np = f->np();
     if (f->blocks_cap < n_blocks) {
         const size_t g_bytes = ((size_t)n_blocks * np * sizeof(float) + 15) / 16 * 16;
-        int rc = grow_scratch(&f->d_scratch, &f->blocks_cap, g_bytes + (size_t)n_blocks * (8 * sizeof(double) + 3 * bsk::FIT_BLOCK_SAMPLES * sizeof(float)), s,
+        int rc = grow_scratch(&f->d_scratch, &f->blocks_cap, g_bytes + (size_t)n_blocks * (FIT_DIAG_WORDS * sizeof(double) + 3 * bsk::FIT_BLOCK_SAMPLES * sizeof(float)), s,
                               "bsk_fit_accumulate: the first accumulate of a size allocates the scratch of the block gradients and cannot be "
                               "captured; make one such call outside the capture first");
         if (rc) return rc;
@@ -100,14 +110,21 @@ int accumulate(bsk_fit* f, const double* d_obs, int64_t obs_stride, int n, const
         a.adv = pg->adv; a.logp_old = pg->logp_old;
         a.clip_hi = pg->hi; a.clip_lo = pg->lo; a.ent_coef = pg->ec;
         // the log-probabilities of the three actions, formed where policy_kernel forms its logp: one launch in front
-        float* lp = (float*)((char*)f->d_scratch + g_bytes + (size_t)f->blocks_cap * 8 * sizeof(double));
+        float* lp = (float*)((char*)f->d_scratch + g_bytes + (size_t)f->blocks_cap * FIT_DIAG_WORDS * sizeof(double));
         bsk::PolicyLogpArgs la = {};
         la.params = f->policy->d_params; la.a = lay.a; la.obs = d_obs; la.obs_stride = obs_stride; la.n = n; la.lp = lp;
         la.width = lay.width;
         HIP_TRY(bsk::launch_policy_logp(la, s));
         a.lp = lp;
-        HIP_TRY(bsk::launch_fit_blocks_pg(a, s));
-        HIP_TRY(bsk::launch_fit_fold_pg(a.G, a.diag, n_blocks, lay.n_params, n_fold, f->A(), f->row(), f->pg_row(), f->count(), s));
+        if (pg->value_old || pg->dvalue) {
+            const bsk::FitVclip vc = {pg->value_old, pg->clip_vf, pg->dvalue};
+            HIP_TRY(bsk::launch_fit_blocks_ppo(a, vc, s));
+            HIP_TRY(bsk::launch_fit_fold_ppo(a.G, a.diag, n_blocks, lay.n_params, n_fold, f->A(), f->row(), f->pg_row(),
+                                             pg->value_old ? f->vclip_row() : nullptr, f->count(), s));
+        } else {
+            HIP_TRY(bsk::launch_fit_blocks_pg(a, s));
+            HIP_TRY(bsk::launch_fit_fold_pg(a.G, a.diag, n_blocks, lay.n_params, n_fold, f->A(), f->row(), f->pg_row(), f->count(), s));
+        }
     } else {
         HIP_TRY(bsk::launch_fit_blocks(a, s));
         HIP_TRY(bsk::launch_fit_fold(a.G, a.diag, n_blocks, lay.n_params, n_fold, f->A(), f->row(), f->count(), s));
@@ -171,12 +188,62 @@ int bsk_fit_accumulate(bsk_fit* f, const double* d_obs, int64_t obs_stride, int 
 int bsk_fit_accumulate_pg(bsk_fit* f, const double* d_obs, int64_t obs_stride, int n, const int32_t* d_action, const float* d_adv,
                           const float* d_logp_old, double clip, double ent_coef, const double* d_value_target, const uint8_t* d_alive,
                           float* d_dlogits, int64_t out_stride, void* stream) {
+    return bsk_fit_accumulate_ppo(f, d_obs, obs_stride, n, d_action, d_adv, d_logp_old, clip, ent_coef, d_value_target, nullptr, 0.0, d_alive,
+                                  d_dlogits, out_stride, nullptr, stream);
+}
+
+int bsk_fit_accumulate_ppo(bsk_fit* f, const double* d_obs, int64_t obs_stride, int n, const int32_t* d_action, const float* d_adv,
+                           const float* d_logp_old, double clip, double ent_coef, const double* d_value_target, const float* d_value_old,
+                           double clip_vf, const uint8_t* d_alive, float* d_dlogits, int64_t out_stride, float* d_dvalue, void* stream) {
     if (!f || !d_obs || !d_action || !d_adv) return fail(BSK_EINVAL, "fit/d_obs/d_action/d_adv is NULL");
     if (d_logp_old && !(std::isfinite(clip) && clip > 0.0 && clip < 1.0))
         return fail(BSK_EINVAL, "bsk_fit_accumulate_pg: clip must be in (0, 1) when d_logp_old is given");
     if (!finite_nonneg(ent_coef)) return fail(BSK_EINVAL, "bsk_fit_accumulate_pg: ent_coef must be finite and not negative");
-    const PgLoss pg = {d_adv, d_logp_old, 1.0f + (float)clip, 1.0f - (float)clip, (float)ent_coef};
+    if ((d_value_old || d_dvalue) && !d_value_target)
+        return fail(BSK_EINVAL, "bsk_fit_accumulate_ppo: d_value_old and d_dvalue need d_value_target");
+    if (d_value_old && !(std::isfinite(clip_vf) && clip_vf > 0.0))
+        return fail(BSK_EINVAL, "bsk_fit_accumulate_ppo: clip_vf must be finite and positive when d_value_old is given");
+    const PgLoss pg = {d_adv, d_logp_old, 1.0f + (float)clip, 1.0f - (float)clip, (float)ent_coef, d_value_old, (float)clip_vf, d_dvalue};
     return accumulate(f, d_obs, obs_stride, n, d_action, d_value_target, d_alive, d_dlogits, out_stride, &pg, stream);
+}
+
+int bsk_fit_vclip_stats_device(bsk_fit* f, const double** d_row2) {
+    if (!f || !d_row2) return fail(BSK_EINVAL, "fit/d_row2 is NULL");
+    *d_row2 = f->vclip_row();
+    return BSK_OK;
+}
+
+int bsk_pg_gather(const uint64_t* d_state, int n_steps, int n_envs, int64_t stride, int64_t q0, int m, const double* d_obs_hist,
+                  const int32_t* d_action_hist, const float* d_adv, const float* d_logp_hist, const double* d_ret, const float* d_value_hist,
+                  double* d_obs_out, int64_t out_stride, int32_t* d_action_out, float* d_adv_out, float* d_logp_out, double* d_ret_out,
+                  float* d_value_out, int32_t* d_index_out, void* stream) {
+    if (n_steps < 1 || n_envs < 1 || stride < n_envs) return fail(BSK_EINVAL, "bsk_pg_gather: n_steps and n_envs must be >= 1, stride >= n_envs");
+    const int64_t N = (int64_t)n_steps * (int64_t)n_envs;
+    if (N >= ((int64_t)1 << 31)) return fail(BSK_EINVAL, "bsk_pg_gather: n_steps * n_envs must be below 2^31");
+    if (q0 < 0 || m < 1 || q0 > N - (int64_t)m) return fail(BSK_EINVAL, "bsk_pg_gather: the window q0 .. q0 + m - 1 must lie inside 0 .. n_steps * n_envs - 1");
+    const void* const from[6] = {d_obs_hist, d_action_hist, d_adv, d_logp_hist, d_ret, d_value_hist};
+    const void* const to[6] = {d_obs_out, d_action_out, d_adv_out, d_logp_out, d_ret_out, d_value_out};
+    bool any = d_index_out != nullptr;
+    for (int k = 0; k < 6; ++k) {
+        if ((from[k] == nullptr) != (to[k] == nullptr)) return fail(BSK_EINVAL, "bsk_pg_gather: a history and its output are given together or not at all");
+        any = any || from[k];
+    }
+    if (!any) return fail(BSK_EINVAL, "bsk_pg_gather: nothing to write");
+    if (d_obs_hist && out_stride < m) return fail(BSK_EINVAL, "bsk_pg_gather: out_stride must be >= m");
+    bsk::PgGatherArgs a = {};
+    a.state = (const unsigned long long*)d_state;
+    a.n_envs = n_envs; a.N = (uint32_t)N; a.stride = stride; a.q0 = q0; a.m = m; a.out_stride = out_stride;
+    a.obs = d_obs_hist; a.action = d_action_hist; a.adv = d_adv; a.logp = d_logp_hist; a.ret = d_ret; a.value = d_value_hist;
+    a.obs_out = d_obs_out; a.action_out = d_action_out; a.adv_out = d_adv_out; a.logp_out = d_logp_out; a.ret_out = d_ret_out;
+    a.value_out = d_value_out; a.index_out = d_index_out;
+    HIP_TRY(bsk::launch_pg_gather(a, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream` of the current device: no copy, no synchronisation, no allocation
+}
+
+int bsk_pg_shuffle_advance(uint64_t* d_state, void* stream) {
+    if (!d_state) return fail(BSK_EINVAL, "bsk_pg_shuffle_advance: d_state is NULL");
+    HIP_TRY(bsk::launch_pg_shuffle_advance((unsigned long long*)d_state, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream` of the current device: no copy, no synchronisation, no allocation
 }
 
 int bsk_fit_pg_stats_device(bsk_fit* f, const double** d_row4) {
@@ -236,6 +303,7 @@ int bsk_fit_set_state(bsk_fit* f, const double* theta, const double* m, const do
     // (contiguous words) start from zero, as behind a step
     HIP_TRY(hipMemset(f->A(), 0, (f->np() + 5) * sizeof(double)));
     HIP_TRY(hipMemset(f->pg_row(), 0, 4 * sizeof(double)));
+    HIP_TRY(hipMemset(f->vclip_row(), 0, 2 * sizeof(double)));
     f->value_seen = false;
     if (theta && (rc = write_policy(f, nullptr))) return rc;          // a new theta is the policy's too: (float)theta
     HIP_SYNC(hipDeviceSynchronize());

@@ -4,8 +4,10 @@
 //                       the backward sweep and the block's gradient G_b in the C-ABI parameter order, plus its diagnostics terms
 //                       <PG = true> (bsk_fit_accumulate_pg): the output deltas of the clipped policy-gradient loss with its
 //                       entropy bonus in the cross-entropy's place, and four more diagnostics terms; <false> is the supervised kernel
+//                       <true, FitVclip> (bsk_fit_accumulate_ppo with d_value_old or d_dvalue): the same with PPO2's clipped value
+//                       loss in the squared error's place, the value deltas written out, and two diagnostics terms more
 //   fit_fold_kernel     one thread per parameter: A += (double)G_b, b ascending; four threads more for the diagnostics row
-//                       (<8>: eight, the policy-gradient row behind the first)
+//                       (<8>: eight, the policy-gradient row behind the first; <10, double*>: ten, the value-clip row behind that)
 //   gae_kernel          bsk_gae: one thread per env walks its column of the rollout histories from the last step to the first
 //   adv_partial_kernel, adv_join_kernel, adv_apply_kernel    bsk_adv_normalize: the mean and standard deviation of an advantage
 //                       block in the fixed order of the observation statistics (bsk_tree.hpp), and (x - mean) / (sd + eps)
@@ -40,6 +42,7 @@ constexpr int FIT_X_ROWS = 8;
 constexpr int FIT_FOLD_BATCH = 32;     // block gradients the fold has in flight per thread
 constexpr int FIT_DIAG_ROWS = 5;       // behind the rows: two doubles and an int per sample, the terms of the block's diagnostics
 constexpr int FIT_PG_DIAG_ROWS = 8;    // behind those, policy-gradient launches only: four doubles more per sample
+constexpr int FIT_VC_DIAG_ROWS = 4;    // behind those, launches with a FitVclip only: two doubles more per sample
 constexpr int FIT_GNORM_BLOCK = 1024;  // fit_gnorm_kernel's one workgroup: sixteen waves
 constexpr int ADV_BATCH = 8;           // rows of an advantage block the partial sums have in flight per lane
 constexpr int ADV_APPLY_ROWS = 1024;   // rows of the apply launch's grid; a block strides over the rest
@@ -165,14 +168,19 @@ __device__ __forceinline__ void fit_backward(const float* __restrict__ params, c
     }
 }
 
-template <bool PG>
-__global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p) {
+// Vc: nothing, or one FitVclip behind a policy-gradient launch.  The two instantiations without one keep the argument they have
+// always had; the clipped value loss is code of <true, FitVclip> alone.
+template <bool PG, typename... Vc>
+__global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p, const Vc... vclip) {
+    constexpr bool VC = sizeof...(Vc) > 0;
+    static_assert(PG || !VC, "the value clip rides on the policy-gradient launch");
     // (everything in the dynamic region and every carve a multiple of 16 bytes: a static array in front would shift its base)
     extern __shared__ __attribute__((aligned(16))) float fit_lds[];
     double* s_nll = (double*)(fit_lds + p.rows * POLICY_LANES);
     double* s_vl = s_nll + POLICY_LANES;
     int* s_flag = (int*)(s_vl + POLICY_LANES);     // bit 0: the sample contributes; bit 1: the greedy action is its label
     double* s_pg = (double*)(s_flag + POLICY_LANES);        // (PG launches only) [4][lane]: -d, H, clipped, A * r
+    double* s_vc = s_pg + 4 * POLICY_LANES;                 // (VC launches only) [2][lane]: value-clipped, the unclipped d d / 2
     const int lane = (int)(threadIdx.x & 63u);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t j = (int64_t)blockIdx.x * POLICY_LANES + lane;
@@ -268,9 +276,40 @@ __global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p
         fit_forward(p.params, p.v, fit_lds, lane, wave, val);
         delta = fit_lds + fit_row(p.v, p.v.n_layers) * POLICY_LANES;
         if (wave == 0) {
-            const float d = on ? val[0] - (float)p.target[j] : 0.0f;
-            delta[lane] = on ? p.value_coef * d : 0.0f;
-            s_vl[lane] = (((double)d) * ((double)d)) * 0.5;
+            if constexpr (VC) {
+                const float R = on ? (float)p.target[j] : 0.0f;
+                const float d = on ? val[0] - R : 0.0f;
+                // PPO2's max((v - R)^2, (v_old + clamp(v - v_old, +-cv) - R)^2) (include/bskgpu.h, bsk_fit_accumulate_ppo): where
+                // the clipped branch holds the max its gradient is zero; a tie is the unclipped branch's
+                const FitVclip x[] = {vclip...};
+                float dl = on ? p.value_coef * d : 0.0f;
+                const double plain = (((double)d) * ((double)d)) * 0.5;
+                double term = plain;
+                bool vclipped = false;
+                if (x[0].value_old && on) {        // (the pointer: workgroup-uniform)
+                    const float cv = x[0].clip_vf;
+                    const float vo = x[0].value_old[j];
+                    const float dv = val[0] - vo;
+                    if (!(-cv <= dv && dv <= cv)) {
+                        const float vc = vo + (dv > 0.0f ? cv : -cv);
+                        const float d2 = vc - R;
+                        if (d2 * d2 > d * d) {
+                            dl = 0.0f;
+                            term = (((double)d2) * ((double)d2)) * 0.5;
+                            vclipped = true;
+                        }
+                    }
+                }
+                delta[lane] = dl;
+                s_vl[lane] = term;
+                s_vc[lane] = vclipped ? 1.0 : 0.0;
+                s_vc[POLICY_LANES + lane] = plain;
+                if (x[0].dvalue && live) x[0].dvalue[j] = dl;
+            } else {
+                const float d = on ? val[0] - (float)p.target[j] : 0.0f;
+                delta[lane] = on ? p.value_coef * d : 0.0f;
+                s_vl[lane] = (((double)d) * ((double)d)) * 0.5;
+            }
         }
         __syncthreads();
         fit_backward(p.params, p.v, fit_lds, g, lane, wave, &walk_ticks);
@@ -286,7 +325,7 @@ __global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p
             count += s_flag[s] & 1;
             correct += (s_flag[s] >> 1) & 1;
         }
-        double* row = p.diag + (PG ? 8 : 4) * (size_t)blockIdx.x;
+        double* row = p.diag + (VC ? 10 : (PG ? 8 : 4)) * (size_t)blockIdx.x;
         row[0] = nll;
         row[1] = vl;
 #if BSK_FIT_STAMPS
@@ -302,14 +341,23 @@ __global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p
                 row[4 + k] = acc;
             }
         }
+        if constexpr (VC) {                // the value-clip row's terms, in the same order
+            for (int k = 0; k < 2; ++k) {
+                double acc = 0.0;
+                for (int s = 0; s < POLICY_LANES; ++s) acc = acc + s_vc[k * POLICY_LANES + s];
+                row[8 + k] = acc;
+            }
+        }
     }
 }
 
-// W: the doubles of a block's diagnostics terms - 4, or 8 behind a policy-gradient launch, whose last four sums are pg_row's
-template <int W>
+// W: the doubles of a block's diagnostics terms - 4, or 8 behind a policy-gradient launch, whose last four sums are pg_row's, or 10
+// behind one with a FitVclip, whose last two are vclip_row's: an argument of <10, double*> alone (NULL: those two go nowhere)
+template <int W, typename... Row>
 __global__ __launch_bounds__(256) void fit_fold_kernel(const float* __restrict__ G, const double* __restrict__ diag, int n_blocks, int n_params,
                                                        int n_fold, double* __restrict__ A, double* __restrict__ row,
-                                                       unsigned long long* __restrict__ count, double* __restrict__ pg_row) {
+                                                       unsigned long long* __restrict__ count, double* __restrict__ pg_row,
+                                                       const Row... vclip_row) {
     const int t = (int)(blockIdx.x * 256u + threadIdx.x);
     if (t < W) {                           // the diagnostics row: its four sums, block-ascending from +0.0
         double s = 0.0;
@@ -323,7 +371,11 @@ __global__ __launch_bounds__(256) void fit_fold_kernel(const float* __restrict__
         }
         for (; b < n_blocks; ++b) s = s + diag[W * (size_t)b + t];
         if (W == 4 || t < 4) row[t] = s;
-        else pg_row[t - 4] = s;
+        else if (W == 8 || t < 8) pg_row[t - 4] = s;
+        else if constexpr (W == 10) {
+            double* const vrow[] = {vclip_row...};
+            if (vrow[0]) vrow[0][t - 8] = s;
+        }
         if (t == 3) *count += (unsigned long long)s;
     }
     const int p = 10 + t;
@@ -596,20 +648,22 @@ FitNet fit_net(const PolicyPackMap& map, int first, const PolicyNet& net) {
     return f;
 }
 
-template <bool PG>
-static hipError_t launch_fit_blocks_as(const FitArgs& args, hipStream_t s) {
-    const size_t lds = (size_t)(args.rows + FIT_DIAG_ROWS + (PG ? FIT_PG_DIAG_ROWS : 0)) * POLICY_LANES * sizeof(float);
+template <bool PG, typename... Vc>
+static hipError_t launch_fit_blocks_as(const FitArgs& args, hipStream_t s, const Vc&... vclip) {
+    const size_t lds = (size_t)(args.rows + FIT_DIAG_ROWS + (PG ? FIT_PG_DIAG_ROWS : 0) + (sizeof...(Vc) ? FIT_VC_DIAG_ROWS : 0)) *
+                       POLICY_LANES * sizeof(float);
     if (lds > 48 * 1024) {                 // (idempotent, and cheap beside the launch: no per-device record to keep)
-        hipError_t e = hipFuncSetAttribute((const void*)&fit_block_kernel<PG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)&fit_block_kernel<PG, Vc...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     const unsigned n_blocks = (unsigned)((args.n + FIT_BLOCK_SAMPLES - 1) / FIT_BLOCK_SAMPLES);
-    hipLaunchKernelGGL(fit_block_kernel<PG>, dim3(n_blocks), dim3(POLICY_BLOCK), lds, s, args);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(fit_block_kernel<PG, Vc...>), dim3(n_blocks), dim3(POLICY_BLOCK), lds, s, args, vclip...);
     return hipGetLastError();
 }
 
 hipError_t launch_fit_blocks(const FitArgs& args, hipStream_t s) { return launch_fit_blocks_as<false>(args, s); }
 hipError_t launch_fit_blocks_pg(const FitArgs& args, hipStream_t s) { return launch_fit_blocks_as<true>(args, s); }
+hipError_t launch_fit_blocks_ppo(const FitArgs& args, const FitVclip& vc, hipStream_t s) { return launch_fit_blocks_as<true>(args, s, vc); }
 
 hipError_t launch_fit_fold(const float* G, const double* diag, int n_blocks, int n_params, int n_fold, double* A, double* row,
                            unsigned long long* count, hipStream_t s) {
@@ -624,6 +678,14 @@ hipError_t launch_fit_fold_pg(const float* G, const double* diag, int n_blocks, 
     const int threads = n_fold - 10 > 8 ? n_fold - 10 : 8;
     hipLaunchKernelGGL(fit_fold_kernel<8>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, G, diag, n_blocks, n_params, n_fold, A,
                        row, count, pg_row);
+    return hipGetLastError();
+}
+
+hipError_t launch_fit_fold_ppo(const float* G, const double* diag, int n_blocks, int n_params, int n_fold, double* A, double* row,
+                               double* pg_row, double* vclip_row, unsigned long long* count, hipStream_t s) {
+    const int threads = n_fold - 10 > 10 ? n_fold - 10 : 10;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(fit_fold_kernel<10, double*>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, G, diag, n_blocks,
+                       n_params, n_fold, A, row, count, pg_row, vclip_row);
     return hipGetLastError();
 }
 

@@ -43,6 +43,14 @@ struct FitArgs {
     float clip_hi, clip_lo, ent_coef;      // 1.0f + (float)clip, 1.0f - (float)clip, (float)ent_coef
 };
 
+// What bsk_fit_accumulate_ppo adds to a policy-gradient launch (launch_fit_blocks_ppo: a third instantiation of the block kernel, which
+// takes this beside FitArgs; `diag` is then [n_blocks][10])
+struct FitVclip {
+    const float* value_old;        // [n] or NULL: the plain squared error
+    float clip_vf;                 // (float)clip_vf
+    float* dvalue;                 // [n] or NULL: the value network's output delta of every sample
+};
+
 // LDS rows of 64 floats the block kernel needs for this layout: the input, every hidden layer of the larger network, the output deltas
 int fit_lds_rows(const PolicyLayout& lay);
 FitNet fit_net(const PolicyPackMap& map, int first, const PolicyNet& net);
@@ -51,12 +59,17 @@ FitNet fit_net(const PolicyPackMap& map, int first, const PolicyNet& net);
 hipError_t launch_fit_blocks(const FitArgs& args, hipStream_t s);
 // The same with the policy-gradient output deltas in the cross-entropy's place, and eight diagnostics terms per block
 hipError_t launch_fit_blocks_pg(const FitArgs& args, hipStream_t s);
+// The same with the clipped value loss (value_old) and / or the value deltas written out (dvalue), and ten diagnostics terms per block
+hipError_t launch_fit_blocks_ppo(const FitArgs& args, const FitVclip& vc, hipStream_t s);
 // A[p] += (double)G[b][p] for b ascending, p in 10 .. n_fold - 1; the diagnostics row out of the block terms; count += row[3]
 hipError_t launch_fit_fold(const float* G, const double* diag, int n_blocks, int n_params, int n_fold, double* A, double* row,
                            unsigned long long* count, hipStream_t s);
 // The same over block terms of eight: the first four into `row` as above, the last four into `pg_row`
 hipError_t launch_fit_fold_pg(const float* G, const double* diag, int n_blocks, int n_params, int n_fold, double* A, double* row,
                               double* pg_row, unsigned long long* count, hipStream_t s);
+// The same over block terms of ten: the last two into `vclip_row`, or nowhere while it is NULL
+hipError_t launch_fit_fold_ppo(const float* G, const double* diag, int n_blocks, int n_params, int n_fold, double* A, double* row,
+                               double* pg_row, double* vclip_row, unsigned long long* count, hipStream_t s);
 // Generalised advantage estimation over rollout histories [n_steps][stride]: one thread per env, t descending
 hipError_t launch_gae(const double* reward, const uint8_t* reason, const float* value, const float* last_value, int n_steps, int n_envs,
                       int64_t stride, double gamma, double gl, float* adv, double* ret, hipStream_t s);

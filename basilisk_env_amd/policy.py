@@ -16,7 +16,8 @@ and in_shift.  ``PolicyFit`` (``bsk_fit_*``; its binding lives in ``policy_fit``
 supervised fit of a ``DevicePolicy`` to labels that are already on the device, such as a planner's - and, with ``gae``
 (``bsk_gae``), ``PolicyFit.accumulate_pg`` and the loop ``PolicyGradient`` over them, training by the reward itself (PPO / A2C),
 conditioned as PPO2 conditions it by ``normalize_advantages`` (``bsk_adv_normalize``), ``PolicyFit.max_grad_norm`` and
-``PolicyFit.apply_obs_norm``.
+``PolicyFit.apply_obs_norm``, fed shuffled minibatches by ``pg_gather`` (``bsk_pg_gather``; ``pg_perm_ref``) and given PPO2's
+clipped value loss by ``PolicyFit.accumulate_ppo`` (``fit_value_delta_ref``).
 
 They are handles of the library and share what such a handle needs (``policy_base._DeviceObject``: create, close, the closed-handle
 refusal, ``sync``); the policy and the population are also both parameter stores that act (``_ParamStore``: the draw counter, the
@@ -37,7 +38,9 @@ import numpy as np
 from . import _hip, _lib
 from ._lib import check
 from .policy_base import _DeviceObject, _host_block  # noqa: F401
-from .policy_fit import PolicyFit, PolicyGradient, gae, normalize_advantages  # noqa: F401
+from .policy_fit import PolicyFit, PolicyGradient, gae, normalize_advantages, pg_gather, pg_shuffle_advance  # noqa: F401
+from .policy_ref import (VCLIP_STATS_COLUMNS, check_pg_gather, check_pg_shuffle, fit_value_delta_ref, pg_gather_ref,  # noqa: F401
+                         pg_perm_keys_ref, pg_perm_ref, pg_shuffle_keys_ref)
 from .policy_ref import (FIT_BLOCK, FIT_STATS_COLUMNS, check_fit, check_fit_batch, fit_accumulate_ref, fit_backward_ref,  # noqa: F401
                          fit_dlogits32_ref, fit_dlogits_ref, fit_loss_ref, fit_stats_ref, fit_step_ref)
 from .policy_ref import (PG_STATS_COLUMNS, check_gae, check_pg, check_pg_loop, fit_pg_dlogits32_ref, fit_pg_dlogits_ref,  # noqa: F401

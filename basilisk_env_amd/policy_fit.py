@@ -16,7 +16,12 @@ minibatch steps - with no host in it.  Reached as ``basilisk_env_amd.policy.gae`
 
 What stable-baselines' PPO2 does to every minibatch beyond that is here too, each off by default: ``normalize_advantages``
 (``bsk_adv_normalize``), ``PolicyFit.max_grad_norm`` (the clip of the gradient's global norm inside ``step``) and
-``PolicyFit.apply_obs_norm`` (an ``ObsStats`` into the policy's in_scale / in_shift); ``PolicyGradient`` takes all three."""
+``PolicyFit.apply_obs_norm`` (an ``ObsStats`` into the policy's in_scale / in_shift); ``PolicyGradient`` takes all three.
+
+The last two pieces of PPO2's update are here as well, off by default: minibatches drawn from a new permutation of all samples in
+every epoch - ``pg_gather`` (``bsk_pg_gather``) by a permutation that is never stored, a function of two device words
+``{seed, epoch}`` that ``policy_ref.pg_perm_ref`` repeats bit for bit - and the clipped value loss, ``PolicyFit.accumulate_ppo``
+(``bsk_fit_accumulate_ppo``); ``PolicyGradient(shuffle=True, cliprange_vf=...)`` runs both."""
 import ctypes as C
 
 import numpy as np
@@ -24,8 +29,9 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .policy_base import _DeviceObject, _host_block
-from .policy_ref import (FIT_STATS_COLUMNS, PG_STATS_COLUMNS, adv_normalize_work_bytes, check_adv_normalize, check_fit, check_fit_batch,
-                         check_gae, check_max_grad_norm, check_pg, check_pg_loop)
+from .policy_ref import (FIT_STATS_COLUMNS, PG_STATS_COLUMNS, VCLIP_STATS_COLUMNS, adv_normalize_work_bytes, check_adv_normalize,
+                         check_fit, check_fit_batch, check_gae, check_max_grad_norm, check_pg, check_pg_gather, check_pg_loop,
+                         check_pg_shuffle)
 from .policy_spec import n_params
 
 
@@ -137,6 +143,38 @@ class PolicyFit(_DeviceObject):
         check(self._lib.bsk_fit_accumulate_pg(handle, vp(obs_ptr), stride, n, vp(act), vp(adv), vp(old), clip, ent_coef, vp(tgt), vp(liv),
                                               vp(dl), n, C.c_void_p(int(stream or 0))))
 
+    def accumulate_ppo(self, obs, actions, advantages, logp_old=None, clip=0.2, ent_coef=0.0, value_targets=None, value_old=None,
+                       clip_vf=None, alive=None, dlogits=None, dvalue=None, n=None, stride=None, stream=0):
+        """``accumulate_pg`` with PPO2's clipped value loss (``bsk_fit_accumulate_ppo``): ``value_old`` float32 (n,) - the values
+        the rollout recorded - with ``clip_vf`` finite and positive, or None (the plain squared error; ``clip_vf`` is then not
+        read), and ``dvalue`` float32 (n,) or None, which receives the value network's output delta of every sample, the counterpart
+        of ``dlogits``.  Either needs ``value_targets``.  With neither the launches are ``accumulate_pg``'s; ``vclip_stats`` has the
+        row ``value_old`` adds.  Everything else, the pointer and array rules included, is ``accumulate_pg``'s."""
+        obs_ptr, stride, n, act, tgt, liv, dl = self._batch(obs, actions, value_targets, alive, dlogits, n, stride, "actions")
+        adv, adv_n, _ = _pointer(advantages, ("<f4",), "advantages")
+        old, old_n, _ = _pointer(logp_old, ("<f4",), "old log-probabilities")
+        vold, vold_n, _ = _pointer(value_old, ("<f4",), "old values")
+        dv, dv_n, _ = _pointer(dvalue, ("<f4",), "dvalue")
+        if adv is None:
+            raise ValueError("advantages are required")
+        for what, size in (("advantages", adv_n), ("old log-probabilities", old_n), ("old values", vold_n), ("dvalue", dv_n)):
+            if size is not None and size != n:
+                raise ValueError("%s: %d elements, got %d" % (what, n, size))
+        clip, ent_coef = check_pg(clip, ent_coef, old is not None)
+        if (vold is not None or dv is not None) and tgt is None:
+            raise ValueError("old values and dvalue need value targets")
+        if vold is None:
+            clip_vf = 0.0                          # (not read)
+        elif clip_vf is None:
+            raise ValueError("clip_vf is required with old values")
+        else:
+            clip_vf = check_pg_shuffle(cliprange_vf=clip_vf)[2]
+        vp = lambda p: C.c_void_p(p) if p else None      # noqa: E731
+        handle = self._handle()
+        self._kept = (obs, actions, advantages, logp_old, value_targets, value_old, alive, dlogits, dvalue)
+        check(self._lib.bsk_fit_accumulate_ppo(handle, vp(obs_ptr), stride, n, vp(act), vp(adv), vp(old), clip, ent_coef, vp(tgt), vp(vold),
+                                               clip_vf, vp(liv), vp(dl), n, vp(dv), C.c_void_p(int(stream or 0))))
+
     def step(self, stream=0):
         """One Adam step of the mean gradient since the last one, then float32(theta) into the policy: three launches on
         ``stream`` - four with ``max_grad_norm`` set, the gradient's global norm in front -, no copy, no synchronisation,
@@ -161,6 +199,20 @@ class PolicyFit(_DeviceObject):
         p = C.c_void_p()
         check(self._lib.bsk_fit_pg_stats_device(self._handle(), C.byref(p)))
         return p.value
+
+    def vclip_stats_ptr(self):
+        """The value-clip row of the last ``accumulate_ppo`` with ``value_old`` as a DEVICE pointer to 2 float64, valid until
+        ``close``."""
+        p = C.c_void_p()
+        check(self._lib.bsk_fit_vclip_stats_device(self._handle(), C.byref(p)))
+        return p.value
+
+    def vclip_stats(self):
+        """The last ``accumulate_ppo`` with ``value_old``'s row -> dict by ``VCLIP_STATS_COLUMNS``: ``value_clipped`` (samples whose
+        clipped branch held the max, and whose value gradient is therefore zero) and ``value_loss_unclipped_sum`` (the summed
+        0.5 (v - target)^2, whatever the branch).  A host read: synchronises."""
+        row = self._row(self.vclip_stats_ptr(), 2)
+        return dict(zip(VCLIP_STATS_COLUMNS, (int(row[0]), row[1])))
 
     def grad_norm_ptr(self):
         """{norm, scale} of the last ``step`` taken with ``max_grad_norm`` set as a DEVICE pointer to 2 float64, valid until
@@ -284,6 +336,53 @@ def normalize_advantages(adv, rows, n, out=None, alive=None, eps=1e-8, stride=No
     check(_lib.load().bsk_adv_normalize(ptrs[0], ptrs[1], rows, n, stride, eps, ptrs[2], ptrs[3], C.c_void_p(int(stream or 0))))
 
 
+def pg_gather(state, n_steps, n_envs, q0, m, obs_hist=None, action_hist=None, adv=None, logp_hist=None, ret=None, value_hist=None,
+              obs_out=None, action_out=None, adv_out=None, logp_out=None, ret_out=None, value_out=None, index_out=None, stride=None,
+              out_stride=None, stream=0):
+    """``bsk_pg_gather``: one minibatch out of a rollout's histories into contiguous buffers, one launch on ``stream`` of the
+    current device, no copy, no synchronisation, no allocation.  Output position i in [0, m) takes sample
+    s = perm(q0 + i) of the n_steps * n_envs - the permutation of the two device words ``state`` = {seed, epoch}
+    (``policy_ref.pg_perm_ref``) - or s = q0 + i with ``state`` None.  ``obs_hist`` float64 [n_steps][5][stride] -> ``obs_out``
+    float64 [5][out_stride] (``out_stride`` defaults to m); ``action_hist`` int32, ``adv``, ``logp_hist``, ``value_hist`` float32 and
+    ``ret`` float64 [n_steps][stride] (``stride`` defaults to ``n_envs``) -> their ``_out`` [m]; ``index_out`` int32 [m] receives s.
+    A history and its output go together; each a raw device pointer or anything with ``__cuda_array_interface__``."""
+    n_steps, n_envs, stride, q0, m, out_stride = check_pg_gather(n_steps, n_envs, n_envs if stride is None else stride, q0, m,
+                                                                 m if out_stride is None else out_stride)
+    N = n_steps * stride
+    pairs = (("observations", obs_hist, obs_out, ("<f8",), 5 * N, 4 * out_stride + m), ("actions", action_hist, action_out, ("<i4",), N, m),
+             ("advantages", adv, adv_out, ("<f4",), N, m), ("log-probabilities", logp_hist, logp_out, ("<f4",), N, m),
+             ("returns", ret, ret_out, ("<f8",), N, m), ("values", value_hist, value_out, ("<f4",), N, m))
+    src, dst = [], []
+    for what, a, b, types, need_a, need_b in pairs:
+        if (a is None) != (b is None):
+            raise ValueError("%s: a history and its output are given together or not at all" % what)
+        for x, need, to in ((a, need_a, src), (b, need_b, dst)):
+            ptr, size, _ = _pointer(x, types, what)
+            if size is not None and size < need:
+                raise ValueError("%s: at least %d elements, got %d" % (what, need, size))
+            to.append(C.c_void_p(ptr) if ptr else None)
+    idx, idx_n, _ = _pointer(index_out, ("<i4",), "index_out")
+    if idx_n is not None and idx_n < m:
+        raise ValueError("index_out: at least %d elements, got %d" % (m, idx_n))
+    if not idx and not any(src):
+        raise ValueError("nothing to write")
+    st, st_n, _ = _pointer(state, ("<u8", "<i8"), "state")
+    if st_n is not None and st_n < 2:
+        raise ValueError("state: two 64-bit words {seed, epoch}")
+    vp = lambda p: C.c_void_p(p) if p else None      # noqa: E731
+    check(_lib.load().bsk_pg_gather(vp(st), n_steps, n_envs, stride, q0, m, *src, dst[0], out_stride, *dst[1:], vp(idx),
+                                    C.c_void_p(int(stream or 0))))
+
+
+def pg_shuffle_advance(state, stream=0):
+    """``bsk_pg_shuffle_advance``: epoch += 1 in the two device words ``state``, one launch on ``stream``, no copy, no
+    synchronisation."""
+    st, st_n, _ = _pointer(state, ("<u8", "<i8"), "state")
+    if not st or (st_n is not None and st_n < 2):
+        raise ValueError("state: two 64-bit device words {seed, epoch}")
+    check(_lib.load().bsk_pg_shuffle_advance(C.c_void_p(st), C.c_void_p(int(stream or 0))))
+
+
 class PolicyGradient(object):
     """On-device policy-gradient training (PPO; the clipped surrogate of ``bsk_fit_accumulate_pg`` on advantages from ``bsk_gae``):
     ``env`` - a ``BatchedPropagator`` (or an env over one) created with ``FLAG_AUTO_RESET`` -, ``policy`` - a ``DevicePolicy`` with a
@@ -300,14 +399,25 @@ class PolicyGradient(object):
     into the policy's in_scale / in_shift (``fit.apply_obs_norm(obs_stats, std_min)``) at the START of ``collect()``, never between a
     rollout and its update, so that the first minibatch still sees ratio 1; and, when ``fit.max_grad_norm`` is set at the time of
     ``update()``, the {norm, scale} row of every step in ``grad_norms``, float64 (epochs * minibatches, 2), after ``iterate()``
-    (None otherwise)."""
+    (None otherwise).
+
+    And the rest of PPO2's update, off by default likewise.  ``shuffle`` - a minibatch is no longer a group of rows but
+    M = (n_steps // minibatches) * n_envs samples of a permutation of ALL n_steps * n_envs, a new one in every epoch: per
+    minibatch one ``pg_gather`` into contiguous buffers ``mb_*``, then the accumulates over chunks of ``n_envs`` of them, and
+    behind every epoch ``pg_shuffle_advance``.  The permutation is a function of the two device words ``{seed, epoch}``
+    (``shuffle_state`` / ``set_shuffle_state``; ``policy_ref.pg_perm_ref``), so a captured epoch draws a new one at every replay.
+    ``normalize_advantages`` then normalises every gathered minibatch in place - PPO2's rule, over the random subset - and
+    ``collect()`` normalises nothing.  ``cliprange_vf`` - the clipped value loss of ``PolicyFit.accumulate_ppo`` against the
+    rollout's recorded values, with or without ``shuffle``.  ``PolicyGradient(shuffle=True, normalize_advantages=True,
+    cliprange_vf=0.2)`` with ``fit.max_grad_norm = 0.5`` is PPO2's update."""
 
     def __init__(self, env, policy, fit, n_steps, gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, epochs=4, minibatches=4, substeps=1,
-                 normalize_advantages=False, obs_stats=None, std_min=1e-6):
+                 normalize_advantages=False, obs_stats=None, std_min=1e-6, shuffle=False, seed=0, cliprange_vf=None):
         from . import _hip
         from ._lib import FLAG_AUTO_RESET
         (self.n_steps, self.gamma, self.lam, self.clip, self.ent_coef, self.epochs, self.minibatches,
          self.substeps) = check_pg_loop(n_steps, gamma, lam, clip, ent_coef, epochs, minibatches, substeps)
+        self.shuffle, seed, self.cliprange_vf = check_pg_shuffle(shuffle, seed, cliprange_vf, self.n_steps, self.minibatches)
         self.normalize_advantages, self.obs_stats, self.std_min = bool(normalize_advantages), obs_stats, float(std_min)
         if not np.isfinite(self.std_min) or not (self.std_min > 0.0):
             raise ValueError("std_min must be finite and positive")
@@ -328,7 +438,13 @@ class PolicyGradient(object):
         sizes = {"obs": 8 * (T + 1) * 5 * n, "reward": 8 * T * n, "reason": T * n, "action": 4 * T * n, "logp": 4 * T * n,
                  "value": 4 * T * n, "last_value": 4 * n, "adv": 4 * T * n, "ret": 8 * T * n, "log": 64 * self.epochs * T,
                  "grad_norm_log": 16 * self.epochs * self.minibatches}
-        if self.normalize_advantages:
+        if self.shuffle:
+            check_pg_shuffle(True, seed, cliprange_vf, T, self.minibatches, n)          # (the gather's bound on n_steps * n_envs)
+            M = (T // self.minibatches) * n
+            sizes.update(shuffle_state=16, mb_obs=8 * 5 * M, mb_action=4 * M, mb_adv=4 * M, mb_logp=4 * M, mb_ret=8 * M, mb_value=4 * M)
+            if self.normalize_advantages:
+                sizes.update(adv_work=adv_normalize_work_bytes(n))
+        elif self.normalize_advantages:
             sizes.update(adv_norm=4 * T * n, adv_work=adv_normalize_work_bytes(n))
         if obs_stats is not None:
             if obs_stats.n_envs < n or obs_stats.device != prop.device:
@@ -343,6 +459,34 @@ class PolicyGradient(object):
                 _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(b[k].ptr), 0, sizes[k], C.c_void_p(stream)), "hipMemsetAsync")
             fit.accumulate_pg(b["obs"].ptr, b["action"].ptr, b["adv"].ptr, None, self.clip, 0.0, None, b["reason"].ptr, n=n, stride=n,
                               stream=stream)
+        if self.shuffle:
+            self.set_shuffle_state(seed, 0)
+
+    def shuffle_state(self):
+        """-> (seed, epoch), the two device words of the permutation (``shuffle=True`` only); epoch is the number of epochs run
+        since ``set_shuffle_state``.  For checkpoints; synchronises."""
+        return tuple(int(w) for w in self._shuffle_words(None))
+
+    def set_shuffle_state(self, seed, epoch=0):
+        """The two words back: with them, and the fit's state, an update resumes bit for bit.  Synchronises."""
+        seed = check_pg_shuffle(True, seed)[1]
+        if isinstance(epoch, bool) or not isinstance(epoch, (int, np.integer)) or not 0 <= int(epoch) < 2 ** 64:
+            raise ValueError("epoch must be an integer in 0 .. 2^64 - 1, got %r" % (epoch,))
+        self._shuffle_words(np.array([seed, int(epoch)], np.uint64))
+
+    def _shuffle_words(self, new):
+        from . import _hip
+        if not self.shuffle:
+            raise ValueError("the loop was created without shuffle")
+        words = np.empty(2, np.uint64) if new is None else new
+        self.prop.sync()
+        with _hip.device_guard(self.prop.device):
+            ptr, host = C.c_void_p(self._buf["shuffle_state"].ptr), C.c_void_p(words.ctypes.data)
+            if new is None:
+                _hip.check(_hip.runtime().hipMemcpy(host, ptr, 16, _hip.hipMemcpyDeviceToHost), "hipMemcpy")
+            else:
+                _hip.check(_hip.runtime().hipMemcpy(ptr, host, 16, _hip.hipMemcpyHostToDevice), "hipMemcpy")
+        return words
 
     def close(self):
         if getattr(self, "_buf", None):
@@ -366,14 +510,18 @@ class PolicyGradient(object):
         [n_steps][n], ``last_value`` f32[n], ``log`` f64[epochs][n_steps][8] (the two diagnostics rows of every accumulate),
         ``grad_norm_log`` f64[epochs * minibatches][2] (written under ``fit.max_grad_norm`` only) and, with
         ``normalize_advantages``, ``adv_norm`` f32[n_steps][n] - every minibatch's rows normalised on their own, what ``update()``
-        reads - and ``adv_work``, the scratch of ``bsk_adv_normalize``"""
+        reads - and ``adv_work``, the scratch of ``bsk_adv_normalize``.  With ``shuffle``: ``shuffle_state`` u64[2] = {seed, epoch}
+        and the gathered minibatch of M = (n_steps // minibatches) * n samples, ``mb_obs`` f64[5][M], ``mb_action`` i32,
+        ``mb_adv`` f32 (normalised in place under ``normalize_advantages``; there is then no ``adv_norm``), ``mb_logp`` f32,
+        ``mb_ret`` f64 and ``mb_value`` f32 [M] (written under ``cliprange_vf`` only)"""
         return {k: b.ptr for k, b in self._buf.items()}
 
     def collect(self):
         """The handle's observation into row 0, a sampled rollout of ``n_steps`` that fills the histories (observations from row 1),
         the value of the observation the handle holds afterwards, and ``bsk_gae``: all enqueued on the env's stream.  In front of
         all of it, with ``obs_stats``: the statistics so far into the policy's input normalisation; behind all of it, with
-        ``normalize_advantages``: every minibatch's rows of ``adv`` normalised into ``adv_norm``."""
+        ``normalize_advantages`` and without ``shuffle``: every minibatch's rows of ``adv`` normalised into ``adv_norm`` (with
+        ``shuffle`` the minibatches do not exist yet: ``update()`` normalises each behind its gather)."""
         from . import _hip
         prop, b, T, n = self.prop, self._buf, self.n_steps, self.n_envs
         stream = prop.stream_ptr()
@@ -388,7 +536,7 @@ class PolicyGradient(object):
             self.policy.value_enqueue(obs, stride, n, b["last_value"].ptr, stream)
             gae(b["reward"].ptr, b["reason"].ptr, b["value"].ptr, b["last_value"].ptr, T, n, b["adv"].ptr, b["ret"].ptr, self.gamma,
                 self.lam, stream=stream)
-            if self.normalize_advantages:
+            if self.normalize_advantages and not self.shuffle:
                 rows = T // self.minibatches
                 for g in range(self.minibatches):
                     normalize_advantages(b["adv"].ptr + 4 * n * rows * g, rows, n, b["adv_norm"].ptr + 4 * n * rows * g,
@@ -398,31 +546,62 @@ class PolicyGradient(object):
         """``epochs`` passes of ``minibatches`` groups of consecutive time rows: per row one ``accumulate_pg`` of the n envs and its
         two diagnostics rows into the log, device to device (a row is one accumulate's: ``iterate`` adds a group's on the host,
         behind its wait); per group one ``fit.step()`` and, under ``fit.max_grad_norm``, its {norm, scale} row into a log of its
-        own."""
+        own.  With ``shuffle`` a group is a gathered minibatch and a row a chunk of n of its samples (``epoch``)."""
+        self._clipped = self.fit.max_grad_norm > 0.0
+        for e in range(self.epochs):
+            self.epoch(e)
+
+    def epoch(self, e=0):
+        """One pass of ``update()`` over the minibatches, enqueued on the env's stream: its diagnostics rows go to the log's rows of
+        pass ``e``.  Without ``shuffle``: the groups of consecutive time rows, one accumulate per row.  With it, per minibatch g:
+        one ``pg_gather`` of the M samples perm(g M) .. perm(g M + M - 1) into ``mb_*``, under ``normalize_advantages`` their
+        normalisation in place, then one accumulate per chunk of n of them; and behind the pass ``pg_shuffle_advance``, so that
+        the next pass - or the next replay of this one from a graph - draws another permutation.  Under ``cliprange_vf`` the
+        accumulates are ``accumulate_ppo`` against the recorded values."""
         from . import _hip
         prop, b, n, fit = self.prop, self._buf, self.n_envs, self.fit
-        adv = b["adv_norm" if self.normalize_advantages else "adv"].ptr
-        self._clipped = fit.max_grad_norm > 0.0
-        gn_row = fit.grad_norm_ptr() if self._clipped else None
+        adv = b["adv_norm" if self.normalize_advantages and not self.shuffle else "adv"].ptr
+        clipped = fit.max_grad_norm > 0.0
+        gn_row = fit.grad_norm_ptr() if clipped else None
         stream, rows = prop.stream_ptr(), self.n_steps // self.minibatches
         rt, vp = _hip.runtime(), C.c_void_p
         pg_row, fit_row = fit.pg_stats_ptr(), fit.stats_ptr()
+        M, cv = rows * n, self.cliprange_vf
         with _hip.device_guard(prop.device):
-            slot = 0
-            for _ in range(self.epochs):
-                for g in range(self.minibatches):
-                    for t in range(g * rows, (g + 1) * rows):
-                        fit.accumulate_pg(b["obs"].ptr + 8 * 5 * n * t, b["action"].ptr + 4 * n * t, adv + 4 * n * t,
-                                          b["logp"].ptr + 4 * n * t, self.clip, self.ent_coef, b["ret"].ptr + 8 * n * t, None,
-                                          n=n, stride=n, stream=stream)
-                        for k, src in enumerate((pg_row, fit_row)):
-                            _hip.check(rt.hipMemcpyAsync(vp(b["log"].ptr + 64 * slot + 32 * k), vp(src), 32,
-                                                         _hip.hipMemcpyDeviceToDevice, vp(stream)), "hipMemcpyAsync")
-                        slot += 1
-                    fit.step(stream)
-                    if self._clipped:
-                        _hip.check(rt.hipMemcpyAsync(vp(b["grad_norm_log"].ptr + 16 * (slot // rows - 1)), vp(gn_row), 16,
+            slot = int(e) * self.n_steps
+            for g in range(self.minibatches):
+                if self.shuffle:
+                    old = (b["value"].ptr, b["mb_value"].ptr) if cv is not None else (None, None)
+                    pg_gather(b["shuffle_state"].ptr, self.n_steps, n, g * M, M, b["obs"].ptr, b["action"].ptr, adv, b["logp"].ptr,
+                              b["ret"].ptr, old[0], b["mb_obs"].ptr, b["mb_action"].ptr, b["mb_adv"].ptr, b["mb_logp"].ptr,
+                              b["mb_ret"].ptr, old[1], stream=stream)
+                    if self.normalize_advantages:
+                        normalize_advantages(b["mb_adv"].ptr, rows, n, work=b["adv_work"].ptr, stream=stream)
+                for c in range(rows):
+                    if self.shuffle:
+                        at, stride = c * n, M
+                        src = (b["mb_obs"].ptr + 8 * at, b["mb_action"].ptr + 4 * at, b["mb_adv"].ptr + 4 * at, b["mb_logp"].ptr + 4 * at,
+                               b["mb_ret"].ptr + 8 * at, b["mb_value"].ptr + 4 * at)
+                    else:
+                        t, stride = g * rows + c, n
+                        src = (b["obs"].ptr + 8 * 5 * n * t, b["action"].ptr + 4 * n * t, adv + 4 * n * t, b["logp"].ptr + 4 * n * t,
+                               b["ret"].ptr + 8 * n * t, b["value"].ptr + 4 * n * t)
+                    if cv is None:
+                        fit.accumulate_pg(src[0], src[1], src[2], src[3], self.clip, self.ent_coef, src[4], None, n=n, stride=stride,
+                                          stream=stream)
+                    else:
+                        fit.accumulate_ppo(src[0], src[1], src[2], src[3], self.clip, self.ent_coef, src[4], src[5], cv, None, n=n,
+                                           stride=stride, stream=stream)
+                    for k, row in enumerate((pg_row, fit_row)):
+                        _hip.check(rt.hipMemcpyAsync(vp(b["log"].ptr + 64 * slot + 32 * k), vp(row), 32,
                                                      _hip.hipMemcpyDeviceToDevice, vp(stream)), "hipMemcpyAsync")
+                    slot += 1
+                fit.step(stream)
+                if clipped:
+                    _hip.check(rt.hipMemcpyAsync(vp(b["grad_norm_log"].ptr + 16 * (slot // rows - 1)), vp(gn_row), 16,
+                                                 _hip.hipMemcpyDeviceToDevice, vp(stream)), "hipMemcpyAsync")
+            if self.shuffle:
+                pg_shuffle_advance(b["shuffle_state"].ptr, stream)
 
     def iterate(self):
         """``collect()`` then ``update()`` -> float64 (epochs * minibatches, 8): per minibatch ``PG_STATS_COLUMNS`` then

@@ -1483,3 +1483,164 @@ def fit_pg_stats_ref(spec, params, obs, actions, adv, logp_old=None, clip=0.2, a
     for b in range(blocks.shape[1]):
         row = row + blocks[:, b]
     return row
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Shuffled minibatches and the clipped value loss (bsk_pg_gather, bsk_fit_accumulate_ppo; definition in include/bskgpu.h), restated
+
+PG_SHUFFLE_ROUNDS = 8
+PG_SHUFFLE_TAG = 0x50475348                    # "PGSH": the third counter word of the key draws
+VCLIP_STATS_COLUMNS = ("value_clipped", "value_loss_unclipped_sum")
+
+
+def pg_shuffle_keys_ref(seed, epoch):
+    """The eight round keys of the permutation of ``{seed, epoch}`` -> uint64 (8,) holding 32-bit words: two draws of
+    ``philox4x32_10`` with counter (epoch_lo, epoch_hi, PG_SHUFFLE_TAG, i) under key (seed_lo, seed_hi), i = 0, 1.  ``epoch`` may be
+    an array of E epochs: -> (8, E), a column per epoch."""
+    seed = np.uint64(int(seed) & (2 ** 64 - 1))
+    scalar = np.ndim(epoch) == 0
+    epoch = np.array([int(e) & (2 ** 64 - 1) for e in np.atleast_1d(epoch)], np.uint64)
+    i = np.arange(2, dtype=np.uint64)[:, None]
+    w = philox4x32_10(epoch & _MASK32, epoch >> _SH32, np.uint64(PG_SHUFFLE_TAG), i, seed & _MASK32, seed >> _SH32)
+    keys = np.stack([np.broadcast_to(x, (2, epoch.size)) for x in w], axis=1).reshape(8, epoch.size).astype(np.uint64)
+    return keys[:, 0] if scalar else keys
+
+
+def _pg_fmix(h):
+    """murmur3's finaliser on uint64 arrays that hold 32-bit words"""
+    h = h ^ (h >> np.uint64(16))
+    h = (h * np.uint64(0x85EBCA6B)) & _MASK32
+    h = h ^ (h >> np.uint64(13))
+    h = (h * np.uint64(0xC2B2AE35)) & _MASK32
+    return h ^ (h >> np.uint64(16))
+
+
+def pg_perm_keys_ref(keys, N, q):
+    """perm(q) under GIVEN round keys (8 words): the unbalanced Feistel network over 2^b values, b = max(2, bit_length(N - 1)),
+    walked until it lands below N - every element for as many trips as IT needs, no cap -> int64, the shape of ``q``.  ``keys``
+    (8, E) with ``q`` (E, ...): row e of ``q`` under column e of the keys."""
+    N = int(N)
+    if not 1 <= N < 2 ** 31:
+        raise ValueError("N must be in 1 .. 2^31 - 1, got %r" % (N,))
+    q = np.asarray(q, np.int64)
+    if q.size and (q.min() < 0 or q.max() >= N):
+        raise ValueError("q must lie in 0 .. N - 1")
+    k = np.asarray(keys, np.uint64) & _MASK32
+    if k.ndim == 1:
+        k = np.broadcast_to(k.reshape(PG_SHUFFLE_ROUNDS, 1), (PG_SHUFFLE_ROUNDS, q.size))
+    else:
+        if q.ndim < 1 or k.shape != (PG_SHUFFLE_ROUNDS, q.shape[0]):
+            raise ValueError("keys (8, E) need q (E, ...)")
+        k = np.repeat(k, q.size // max(q.shape[0], 1), axis=1)
+    b = max(2, (N - 1).bit_length())
+    a = b >> 1
+    c = b - a
+    mask = {a: np.uint64((1 << a) - 1), c: np.uint64((1 << c) - 1)}
+    x = q.reshape(-1).astype(np.uint64)
+    todo = np.arange(x.size)
+    while todo.size:
+        v, kr = x[todo], k[:, todo]
+        L, R = v >> np.uint64(c), v & mask[c]
+        wl, wr = a, c
+        for r in range(PG_SHUFFLE_ROUNDS):
+            F = _pg_fmix(R ^ kr[r]) & mask[wl]
+            L, R = R, L ^ F
+            wl, wr = wr, wl
+        v = (L << np.uint64(wr)) | R
+        x[todo] = v
+        todo = todo[v >= np.uint64(N)]
+    return x.astype(np.int64).reshape(q.shape)
+
+
+def pg_perm_ref(seed, epoch, N, q):
+    """``bsk_pg_gather``'s permutation of [0, N) under the state words ``{seed, epoch}`` at the positions ``q`` -> int64, the shape
+    of ``q``.  Integer arithmetic alone: bit for bit the device's (csrc/bsk_shuffle.hpp)."""
+    return pg_perm_keys_ref(pg_shuffle_keys_ref(seed, epoch), N, q)
+
+
+def pg_gather_ref(state, n_envs, q0, m, obs=None, **hist):
+    """``bsk_pg_gather`` restated: a ``take`` by ``pg_perm_ref``.  ``state``: (seed, epoch) or None (the identity); ``obs``
+    (n_steps, 5, n_envs) or None; every other history (n_steps, n_envs) by keyword -> dict: ``index`` int64 (m,), ``obs`` (5, m)
+    and each history given (m,), in its own dtype."""
+    arrays = {k: np.asarray(v) for k, v in hist.items() if v is not None}
+    obs = None if obs is None else np.asarray(obs)
+    first = obs if obs is not None else next(iter(arrays.values()))
+    N = first.shape[0] * int(n_envs)
+    q = int(q0) + np.arange(int(m), dtype=np.int64)
+    if q0 < 0 or m < 1 or q0 + m > N:
+        raise ValueError("the window q0 .. q0 + m - 1 must lie inside 0 .. N - 1")
+    s = q if state is None else pg_perm_ref(state[0], state[1], N, q)
+    t, j = s // int(n_envs), s % int(n_envs)
+    out = {"index": s}
+    if obs is not None:
+        out["obs"] = np.ascontiguousarray(obs[t, :, j].T)
+    for k, v in arrays.items():
+        out[k] = v[t, j]
+    return out
+
+
+def fit_value_delta_ref(v, R, value_old=None, clip_vf=None, value_coef=0.5):
+    """The value network's output delta and loss term of ``bsk_fit_accumulate_ppo`` per contributing sample -> (delta float32,
+    term float64, clipped bool), each (n,).  ``v`` the network's float32 outputs, ``R`` the targets (rounded to float32 here, as
+    the kernel rounds them), ``value_old`` float32 or None.  Float32, every operation rounded on its own: d = v - R; without
+    ``value_old``, or with -cv <= v - value_old <= cv: delta = value_coef * d, term = d d / 2 (the product and the half in
+    float64); else vc = value_old +- cv, d2 = vc - R, and where d2 d2 > d d: delta = +0.0, term = d2 d2 / 2, clipped.  A tie is
+    the unclipped branch's.  Bit for bit the device's."""
+    v = np.asarray(v, np.float32).reshape(-1)
+    R = np.asarray(R).reshape(-1).astype(np.float32)
+    vc32 = np.float32(value_coef)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        d = (v - R).astype(np.float32)
+        delta = (vc32 * d).astype(np.float32)
+        term = (d.astype(np.float64) * d.astype(np.float64)) * 0.5
+        clipped = np.zeros(v.size, bool)
+        if value_old is not None:
+            cv = np.float32(clip_vf)
+            vo = np.asarray(value_old, np.float32).reshape(-1)
+            dv = (v - vo).astype(np.float32)
+            outside = ~((-cv <= dv) & (dv <= cv))
+            vcl = (vo + np.where(dv > 0, cv, -cv).astype(np.float32)).astype(np.float32)
+            d2 = (vcl - R).astype(np.float32)
+            clipped = outside & ((d2 * d2).astype(np.float32) > (d * d).astype(np.float32))
+            delta = np.where(clipped, np.float32(0.0), delta).astype(np.float32)
+            term = np.where(clipped, (d2.astype(np.float64) * d2.astype(np.float64)) * 0.5, term)
+    return delta, term, clipped
+
+
+def check_pg_shuffle(shuffle=False, seed=0, cliprange_vf=None, n_steps=1, minibatches=1, n_envs=1):
+    """The argument rules ``PolicyGradient`` adds for shuffled minibatches and the clipped value loss, beside ``check_pg_loop``'s
+    -> (shuffle, seed, cliprange_vf): ``shuffle`` a bool, ``seed`` an integer in 0 .. 2^64 - 1, ``cliprange_vf`` None (the plain
+    squared error) or finite and positive - where ``bsk_fit_accumulate_ppo`` returns BSK_EINVAL otherwise -, and with ``shuffle``
+    n_steps * n_envs below 2^31, ``bsk_pg_gather``'s bound.  Needs no device."""
+    if not isinstance(shuffle, (bool, np.bool_)):
+        raise ValueError("shuffle must be a bool, got %r" % (shuffle,))
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("seed must be an integer in 0 .. 2^64 - 1, got %r" % (seed,))
+    if cliprange_vf is not None:
+        if isinstance(cliprange_vf, bool):
+            raise ValueError("cliprange_vf must be None or a positive number")
+        cliprange_vf = float(cliprange_vf)
+        if not np.isfinite(cliprange_vf) or not (cliprange_vf > 0.0):
+            raise ValueError("cliprange_vf must be None or finite and positive")
+    for what, x in (("n_steps", n_steps), ("minibatches", minibatches), ("n_envs", n_envs)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
+            raise ValueError("%s must be an integer >= 1, got %r" % (what, x))
+    if shuffle and int(n_steps) * int(n_envs) >= 2 ** 31:
+        raise ValueError("shuffle: n_steps * n_envs must be below 2^31")
+    return bool(shuffle), int(seed), cliprange_vf
+
+
+def check_pg_gather(n_steps, n_envs, stride, q0, m, out_stride):
+    """The argument rules of ``bsk_pg_gather`` that need no device -> the six as ints; ValueError where it returns BSK_EINVAL."""
+    for what, x, least in (("n_steps", n_steps, 1), ("n_envs", n_envs, 1), ("stride", stride, 1), ("q0", q0, 0), ("m", m, 1),
+                           ("out_stride", out_stride, 0)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < least:
+            raise ValueError("%s must be an integer >= %d, got %r" % (what, least, x))
+    n_steps, n_envs, stride, q0, m, out_stride = (int(x) for x in (n_steps, n_envs, stride, q0, m, out_stride))
+    if n_steps * n_envs >= 2 ** 31:
+        raise ValueError("n_steps * n_envs must be below 2^31")
+    if stride < n_envs:
+        raise ValueError("stride must be >= n_envs")
+    if q0 + m > n_steps * n_envs:
+        raise ValueError("the window q0 .. q0 + m - 1 must lie inside 0 .. n_steps * n_envs - 1")
+    return n_steps, n_envs, stride, q0, m, out_stride

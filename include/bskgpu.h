@@ -1220,6 +1220,70 @@ int bsk_fit_grad_norm_device(bsk_fit* f, const double** d_row2);
  * anything is launched: NULL pointers, std_min not finite or not positive, fit and statistics on different devices. */
 int bsk_fit_apply_obs_norm(bsk_fit* f, bsk_obs_stats* stats, double std_min, void* stream);
 
+/* The last two pieces of PPO2's update: minibatches drawn from a new permutation of all n_steps * n_envs samples in every epoch,
+ * and the clipped value loss (cliprange_vf).  Both are off until asked for; without them every entry point above issues the
+ * launches, with the arguments, it issued before.
+ *
+ * The permutation of [0, N), 1 <= N < 2^31, is never stored: it is a function of two uint64 DEVICE words {seed, epoch}, the
+ * caller's, as the policy's {seed, draw} are.  All arithmetic is uint32 unless stated (policy_ref.py: pg_perm_ref, equal bit for
+ * bit; csrc/bsk_shuffle.hpp):
+ *   b = max(2, bit_length(N - 1));  a = b >> 1;  c = b - a    - an unbalanced Feistel network over 2^b < 2 N values
+ *   the eight round keys  k[4 i .. 4 i + 3] = philox4x32_10(c0 = epoch_lo, c1 = epoch_hi, c2 = 0x50475348, c3 = i;
+ *                                                            key = seed_lo, seed_hi)  for i = 0, 1
+ *   fmix(h):  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16
+ *   perm(q):  x = q;  repeat
+ *               L = x >> c;  R = x & (2^c - 1);  wl = a;  wr = c
+ *               for r = 0 .. 7:  F = fmix(R ^ k[r]) & (2^wl - 1);  (L, R) = (R, L ^ F);  swap(wl, wr)
+ *               x = (L << wr) | R
+ *             until x < N   (cycle walking)
+ * The walk always ends - the cycle of q under the permutation of 2^b values returns to q < N - and has NO cap: a cap would break
+ * the bijection.  Its mean length is below two trips.
+ *
+ * bsk_pg_gather: one minibatch out of the rollout histories into contiguous buffers, ONE launch, one thread per output position.
+ * N = n_steps * n_envs;  output position i in [0, m) takes sample s = perm(q0 + i), or s = q0 + i with d_state == NULL;
+ * t = s / n_envs, j = s % n_envs.  The histories are [n_steps][stride] (d_action_hist int32, d_adv, d_logp_hist and d_value_hist
+ * f32, d_ret f64) and d_obs_hist f64[n_steps][5][stride], word r of the sample at [t][r][j];  d_obs_out is f64[5][out_stride] - a
+ * chunk of it is bsk_fit_accumulate_pg's d_obs as it is -, the other outputs [m], and d_index_out int32[m] receives s.  Each
+ * history and its output are both NULL or both given; d_index_out may be given alone.  Columns j >= n_envs of the histories are not
+ * read, and nothing but positions 0 .. m - 1 of an output (of each of the five rows of d_obs_out) is written.  Enqueued on
+ * `stream` of the current device: no copy, no synchronisation, no allocation; capturable from the first call, and a replayed
+ * graph reads the state words as they are THEN.  The stores are coalesced, the loads scattered by construction.
+ * BSK_EINVAL before any launch: n_steps < 1, n_envs < 1, N >= 2^31, stride < n_envs; q0 < 0, m < 1, q0 + m > N; out_stride < m
+ * with d_obs_hist; a history without its output or the reverse; nothing to write.
+ * bsk_pg_shuffle_advance: epoch += 1, ONE launch of one thread, under the same terms.  BSK_EINVAL: d_state NULL. */
+int bsk_pg_gather(const uint64_t* d_state, int n_steps, int n_envs, int64_t stride, int64_t q0, int m, const double* d_obs_hist,
+                  const int32_t* d_action_hist, const float* d_adv, const float* d_logp_hist, const double* d_ret,
+                  const float* d_value_hist, double* d_obs_out, int64_t out_stride, int32_t* d_action_out, float* d_adv_out,
+                  float* d_logp_out, double* d_ret_out, float* d_value_out, int32_t* d_index_out, void* stream);
+int bsk_pg_shuffle_advance(uint64_t* d_state, void* stream);
+/* bsk_fit_accumulate_pg - which is this call with d_value_old = NULL, clip_vf = 0, d_dvalue = NULL - with PPO2's value loss
+ * max((v - R)^2, (v_old + clamp(v - v_old, -clip_vf, clip_vf) - R)^2) / 2 in the squared error's place.  d_value_old f32[n]: the
+ * values the rollout recorded (d_value_hist);  d_dvalue f32[n] or NULL: receives the value network's output delta of every sample
+ * below n, +0.0f where the sample does not contribute - the counterpart of d_dlogits.  With either pointer the block launch is a
+ * third instantiation of the kernel and the fold one over ten terms per block; with neither, the launches of bsk_fit_accumulate_pg.
+ * Per contributing sample, f32, every operation rounded on its own;  cv = (float)clip_vf:
+ *   v = the value network's output;  R = (float)d_value_target[j];  d = v - R
+ *   d_value_old == NULL:  delta = value_coef * d, the term (double)d * (double)d / 2    (bsk_fit_accumulate's text)
+ *   otherwise  vo = d_value_old[j];  dv = v - vo
+ *     -cv <= dv && dv <= cv:  as above
+ *     else  vc = vo + (dv > 0 ? cv : -cv);  d2 = vc - R
+ *       d2 * d2 > d * d:  the clipped branch holds the max and its gradient is zero:  delta = +0.0f, the term is
+ *                         (double)d2 * (double)d2 / 2, and the sample is VALUE-CLIPPED
+ *       otherwise:        as above (a tie is the unclipped branch's)
+ * Column [1] of the first diagnostics row sums the term above.  A third row, f64[2] behind bsk_fit_vclip_stats_device, is written
+ * in the first row's order by launches with d_value_old ONLY: [0] the value-clipped samples, [1] the sum of the unclipped
+ * (double)d * (double)d / 2.  It follows that with clip_vf above every |dv| the accumulators and the first two rows are
+ * bsk_fit_accumulate_pg's bit for bit.
+ * BSK_EINVAL before any launch, beyond bsk_fit_accumulate_pg's rules: d_value_old or d_dvalue without d_value_target (and so
+ * without a value network); clip_vf not finite or <= 0 when d_value_old is given. */
+int bsk_fit_accumulate_ppo(bsk_fit* f, const double* d_obs, int64_t obs_stride, int n, const int32_t* d_action, const float* d_adv,
+                           const float* d_logp_old, double clip, double ent_coef, const double* d_value_target,
+                           const float* d_value_old, double clip_vf, const uint8_t* d_alive, float* d_dlogits, int64_t out_stride,
+                           float* d_dvalue, void* stream);
+/* The value-clip row as DEVICE words, f64[2] (read-only for the caller; valid for the fit's lifetime; zero before the first launch
+ * with d_value_old).  No launch, no copy, no synchronisation. */
+int bsk_fit_vclip_stats_device(bsk_fit* f, const double** d_row2);
+
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the
  * three-wave form's barrier-free exchange gives up after 2^20 polls instead of hanging, and says so here. */

@@ -1,0 +1,488 @@
+"""GPU: shuffled minibatches and the clipped value loss of the policy-gradient loop - bsk_pg_gather / bsk_pg_shuffle_advance
+(csrc/bsk_shuffle.hip: pg_gather_kernel), bsk_fit_accumulate_ppo (csrc/bsk_fit.hip: fit_block_kernel<true, FitVclip>,
+fit_fold_kernel<10, double*>; definition in include/bskgpu.h) and ``policy.PolicyGradient(shuffle=, seed=, cliprange_vf=)``.
+
+Everything here is an equality of bits.  The permutation is integer arithmetic (``pg_perm_ref``; the device function itself is
+held to it on the host by tests/test_pg_shuffle_host.py before this file runs it), the gather a copy, and the value loss a handful
+of f32 operations with no library function, taken from the device's OWN value outputs: the test reads v of every sample through
+d_dvalue of a launch with value_coef = 1 and targets 0, then places old values and targets around it so that every sample lands in a
+chosen branch at least 2^-10 relative from every edge (in fact by 0.15 or more, at values of order 1) - no sample needs to be, and
+none is, left out.  Shapes are the smallest at which each path is taken: N = 1; N = 2^8 with no cycle walk; 195 and 140 with a tail,
+walks and a stride above n_envs; 4097, just above a power of two, with the longest walks; 65 samples are two blocks of the fit."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from _device_bits import download as _download, same as _same
+from _policy_bounds import observation_like, seeded_policy
+from basilisk_env_amd import _lib
+from basilisk_env_amd import policy as P
+from basilisk_env_amd._lib import FLAG_AUTO_RESET, GRAV_PM_J2
+from basilisk_env_amd.simulators.dynamics import BatchedPropagator, default_config
+from basilisk_env_amd.simulators.initial_conditions.batch import sample_ic_batch
+from test_gpu_fit import _dev
+from test_gpu_pg import _PG, _block_sum, _lp_of
+
+pytestmark = pytest.mark.gpu
+
+EINVAL = -1
+SENTINEL = -7
+NAMES = ("obs", "action", "adv", "logp", "ret", "value")
+DTYPES = dict(obs=np.float64, action=np.int32, adv=np.float32, logp=np.float32, ret=np.float64, value=np.float32)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the gather
+def _histories(T, n, stride, seed):
+    """-> (the histories as the loop holds them, [T][stride] and obs [T][5][stride] with 9s in the padding columns; the same
+    without the padding)"""
+    rng = np.random.default_rng(500 + seed)
+    plain = dict(obs=rng.normal(size=(T, 5, n)), action=rng.integers(0, 3, (T, n)).astype(np.int32),
+                 adv=rng.normal(size=(T, n)).astype(np.float32), logp=-rng.random((T, n)).astype(np.float32),
+                 ret=rng.normal(size=(T, n)), value=rng.normal(size=(T, n)).astype(np.float32))
+    padded = {}
+    for k, a in plain.items():
+        full = np.full(a.shape[:-1] + (stride,), 9, a.dtype)
+        full[..., :n] = a
+        padded[k] = full
+    return padded, plain
+
+
+def _state(seed, epoch):
+    return _dev(np.array([seed, epoch], np.uint64).view(np.int64))
+
+
+def _outputs(m, pad=3):
+    import torch
+    out = {k: torch.full((5, m + pad) if k == "obs" else (m + pad,), SENTINEL, dtype=getattr(torch, np.dtype(DTYPES[k]).name), device="cuda")
+           for k in NAMES}
+    out["index"] = torch.full((m + pad,), SENTINEL, dtype=torch.int32, device="cuda")
+    return out
+
+
+def _gather(state, T, n, stride, q0, m, d_hist, pad=3):
+    """one bsk_pg_gather of all six pairs and the index into sentinel-filled outputs with ``pad`` elements (columns) to spare -> the
+    outputs on the host"""
+    import torch
+    out = _outputs(m, pad)
+    torch.cuda.synchronize()
+    P.pg_gather(state, T, n, q0, m, d_hist["obs"], d_hist["action"], d_hist["adv"], d_hist["logp"], d_hist["ret"], d_hist["value"],
+                out["obs"], out["action"], out["adv"], out["logp"], out["ret"], out["value"], out["index"], stride=stride,
+                out_stride=m + pad)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def _check_gather(got, want, m):
+    assert np.array_equal(got["index"][:m].astype(np.int64), want["index"]) and (got["index"][m:] == SENTINEL).all()
+    for k in NAMES:
+        assert got[k].dtype == want[k].dtype == DTYPES[k]
+        assert _same(got[k][..., :m], want[k]), k
+        assert (got[k][..., m:] == SENTINEL).all(), k          # what lies behind position m - 1 is nobody's
+
+
+SHAPES = [(1, 1, 1), (4, 64, 64), (3, 65, 65), (2, 70, 96), (1, 4097, 4097)]
+
+
+@pytest.mark.parametrize("T,n,stride", SHAPES)
+def test_the_gather_equals_the_restatement_bit_for_bit(T, n, stride):
+    import torch
+    N, seed, epoch = T * n, 11 + n, 5
+    padded, plain = _histories(T, n, stride, n)
+    d_hist = {k: _dev(v) for k, v in padded.items()}
+    got = _gather(_state(seed, epoch), T, n, stride, 0, N, d_hist)
+    want = P.pg_gather_ref((seed, epoch), n, 0, N, **plain)
+    assert np.array_equal(want["index"], P.pg_perm_ref(seed, epoch, N, np.arange(N)))
+    assert np.array_equal(np.sort(got["index"][:N]), np.arange(N))
+    _check_gather(got, want, N)
+    torch.cuda.synchronize()
+    for k, v in padded.items():                                # the histories, padding columns included, are read only
+        assert _same(d_hist[k].cpu().numpy(), v), k
+
+
+def test_a_window_that_starts_and_ends_inside_a_wave():
+    T, n, stride, q0, m = 3, 65, 65, 37, 101
+    padded, plain = _histories(T, n, stride, 1)
+    got = _gather(_state(3, 2 ** 33 + 1), T, n, stride, q0, m, {k: _dev(v) for k, v in padded.items()})
+    want = P.pg_gather_ref((3, 2 ** 33 + 1), n, q0, m, **plain)
+    assert np.array_equal(want["index"], P.pg_perm_ref(3, 2 ** 33 + 1, T * n, np.arange(T * n))[q0:q0 + m])
+    _check_gather(got, want, m)
+
+
+def test_without_state_words_the_gather_reproduces_a_row():
+    T, n, stride = 2, 70, 96
+    padded, plain = _histories(T, n, stride, 2)
+    d_hist = {k: _dev(v) for k, v in padded.items()}
+    for t in range(T):
+        got = _gather(None, T, n, stride, t * n, n, d_hist)
+        assert np.array_equal(got["index"][:n], t * n + np.arange(n))
+        for k in NAMES:
+            assert _same(got[k][..., :n], plain[k][t]), (t, k)
+            assert (got[k][..., n:] == SENTINEL).all()
+
+
+def test_a_gather_behind_an_advance_is_the_next_epoch():
+    import torch
+    T, n, stride, seed = 3, 65, 65, 2 ** 40 + 7
+    padded, plain = _histories(T, n, stride, 3)
+    d_hist = {k: _dev(v) for k, v in padded.items()}
+    state = _state(seed, 2 ** 32 - 1)                         # (the advance carries into the epoch's upper word)
+    first = _gather(state, T, n, stride, 0, T * n, d_hist)
+    P.pg_shuffle_advance(state)
+    second = _gather(state, T, n, stride, 0, T * n, d_hist)
+    torch.cuda.synchronize()
+    assert list(state.cpu().numpy().view(np.uint64)) == [seed, 2 ** 32]
+    _check_gather(first, P.pg_gather_ref((seed, 2 ** 32 - 1), n, 0, T * n, **plain), T * n)
+    _check_gather(second, P.pg_gather_ref((seed, 2 ** 32), n, 0, T * n, **plain), T * n)
+    assert not np.array_equal(first["index"], second["index"])
+
+
+def test_the_gather_refuses_bad_arguments_before_any_launch():
+    import torch
+    T, n, stride, m = 2, 5, 6, 7
+    padded, plain = _histories(T, n, stride, 4)
+    d_hist = {k: _dev(v) for k, v in padded.items()}
+    out = _outputs(m)
+    state = _state(1, 0)
+    torch.cuda.synchronize()
+    lib = _lib.load()
+    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
+    src, dst = [vp(d_hist[k]) for k in NAMES], [vp(out[k]) for k in NAMES]
+    #       0          1  2  3       4  5  6 ... 11   12       13     14 ... 18    19                20
+    good = [vp(state), T, n, stride, 1, m] + src + [dst[0], m + 3] + dst[1:] + [vp(out["index"]), None]
+    assert len(good) == 21
+    bads = [(1, 0), (2, 0), (1, -1), (3, n - 1), (4, -1), (5, 0), (4, T * n - m + 1), (4, 2 ** 40), (13, m - 1)]
+    bads += [(at, None) for at in range(6, 13)] + [(at, None) for at in range(14, 19)]           # a half-given pair, each way
+    for at, bad in bads:
+        args = list(good)
+        args[at] = bad
+        assert lib.bsk_pg_gather(*args) == EINVAL, (at, bad)
+    # N = 2^31 and beyond (nothing is read: refused before the launch)
+    args = list(good)
+    args[1], args[2], args[3] = 2 ** 16, 2 ** 15, 2 ** 15
+    assert lib.bsk_pg_gather(*args) == EINVAL
+    # nothing to write; the state may be NULL, the index alone is enough
+    nothing = [vp(state), T, n, stride, 1, m] + [None] * 6 + [None, 0] + [None] * 5 + [None, None]
+    assert lib.bsk_pg_gather(*nothing) == EINVAL
+    assert lib.bsk_pg_shuffle_advance(None, None) == EINVAL
+    torch.cuda.synchronize()
+    for k, t in out.items():
+        assert (t.cpu().numpy() == SENTINEL).all(), k
+    assert list(state.cpu().numpy()) == [1, 0]
+    alone = list(nothing)
+    alone[19] = vp(out["index"])
+    assert lib.bsk_pg_gather(*alone) == 0 and lib.bsk_pg_gather(*good) == 0
+    torch.cuda.synchronize()
+    _check_gather({k: t.cpu().numpy() for k, t in out.items()}, P.pg_gather_ref((1, 0), n, 1, m, **plain), m)
+    # the binding refuses the same with a ValueError, before the library is asked
+    for kw in (dict(q0=T * n), dict(m=0), dict(stride=n - 1), dict(n_envs=0)):
+        a = dict(n_steps=T, n_envs=n, q0=1, m=m, stride=stride)
+        a.update(kw)
+        with pytest.raises(ValueError):
+            P.pg_gather(state, a["n_steps"], a["n_envs"], a["q0"], a["m"], index_out=out["index"], stride=a["stride"])
+    with pytest.raises(ValueError):
+        P.pg_gather(state, T, n, 1, m, obs_hist=d_hist["obs"], stride=stride)
+    with pytest.raises(ValueError):
+        P.pg_gather(state, T, n, 1, m, stride=stride)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the value loss
+CV = 0.25
+KINDS = ("inside", "above_clipped", "above_unclipped", "below_clipped", "below_unclipped")
+
+
+def _place(v, kinds):
+    """old values and targets around the device's own v that put sample j into branch kinds[j]: dv = +-0.1 inside the range of
+    0.25 and +-1.0 outside it; squared errors 1 against 3.06 where the clipped branch holds the max, 4 against 1.56 where not"""
+    vo, R = np.empty(v.size, np.float32), np.empty(v.size, np.float64)
+    for j, kind in enumerate(kinds):
+        side = -1.0 if kind.startswith("below") else 1.0
+        vo[j] = v[j] - np.float32(side * (0.1 if kind == "inside" else 1.0))
+        R[j] = float(v[j]) + side * (-2.0 if kind.endswith("unclipped") else 1.0)
+    return vo, R
+
+
+def _ppo_case(n, seed):
+    spec, params = seeded_policy((16,), "relu", (16,), seed=seed)
+    obs = observation_like(n, seed)
+    rng = np.random.default_rng(700 + seed)
+    actions = rng.integers(0, 3, n).astype(np.int32)
+    adv = rng.normal(size=n).astype(np.float32)
+    old = (_lp_of(P.mlp_ref(spec, params, obs)[0], actions) + rng.normal(0.0, 0.3, n)).astype(np.float32)
+    return spec, params, obs, actions, adv, old
+
+
+@pytest.mark.parametrize("n", [1, 65])
+def test_the_clipped_value_loss_equals_the_restatement_in_every_branch(n):
+    """Every sample contributes and every sample is checked: no case is skipped."""
+    import torch
+    spec, params, obs, actions, adv, old = _ppo_case(n, 40 + n)
+    reader, f = _PG(spec, params, value_coef=1.0), _PG(spec, params, value_coef=0.5)
+    d = {k: _dev(a) for k, a in dict(obs=obs, actions=actions, adv=adv, old=old, zero=np.zeros(n)).items()}
+    dvalue = torch.full((n + 2,), float(SENTINEL), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    # the device's own v: value_coef = 1, targets 0, no old values - delta = 1.0f * (v - 0.0f)
+    reader.fit.accumulate_ppo(d["obs"], d["actions"], d["adv"], d["old"], 0.2, 0.01, d["zero"], dvalue=dvalue[:n])
+    torch.cuda.synchronize()
+    v = dvalue.cpu().numpy()[:n].copy()
+    assert _same(v, P.mlp_ref(spec, params, obs)[1].reshape(-1)) and (dvalue.cpu().numpy()[n:] == SENTINEL).all()
+    assert reader.fit.vclip_stats() == dict(zip(P.VCLIP_STATS_COLUMNS, (0, 0.0)))         # written with old values only
+    seen = set()
+    for shift in range(len(KINDS)):
+        kinds = [KINDS[(j + shift) % len(KINDS)] for j in range(n)]
+        vo, R = _place(v, kinds)
+        want_delta, want_term, want_clipped = P.fit_value_delta_ref(v, R, vo, CV, 0.5)
+        assert [k.endswith("_clipped") for k in kinds] == list(want_clipped)              # (the branches are the intended ones)
+        dv = (v - vo).astype(np.float64)
+        assert (np.abs(np.abs(dv) - CV) > 2.0 ** -10 * CV).all()
+        d_vo, d_R = _dev(vo), _dev(R)
+        dvalue.fill_(float(SENTINEL))
+        torch.cuda.synchronize()
+        f.fit.accumulate_ppo(d["obs"], d["actions"], d["adv"], d["old"], 0.2, 0.01, d_R, d_vo, CV, dvalue=dvalue[:n])
+        torch.cuda.synchronize()
+        got = dvalue.cpu().numpy()
+        assert _same(got[:n], want_delta) and (got[n:] == SENTINEL).all(), shift
+        row, vrow = f.fit.stats(), f.fit.vclip_stats()
+        assert _same(np.float64(row["value_loss_sum"]), np.float64(_block_sum(want_term))) and row["count"] == n, shift
+        plain = P.fit_value_delta_ref(v, R, None, None, 0.5)[1]
+        assert vrow["value_clipped"] == int(want_clipped.sum()), shift
+        assert _same(np.float64(vrow["value_loss_unclipped_sum"]), np.float64(_block_sum(plain))), shift
+        seen.update(kinds)
+        f.fit.step()                                           # (the count returns to zero; lr moves theta, so v is re-read below)
+        f.fit.set_state(theta=params.astype(np.float64), m=np.zeros(params.size), v=np.zeros(params.size), beta_pow=np.ones(2))
+    assert seen == set(KINDS)
+    reader.close()
+    f.close()
+
+
+def test_a_value_clip_that_never_binds_and_no_old_values_leave_the_state_of_accumulate_pg():
+    import torch
+    n = 65
+    spec, params, obs, actions, adv, old = _ppo_case(n, 50)
+    rng = np.random.default_rng(51)
+    targets = rng.normal(size=n)
+    vo = rng.normal(size=n).astype(np.float32)
+    d = [_dev(a) for a in (obs, actions, adv, old, targets, vo)]
+    fits = {k: _PG(spec, params, lr=1e-2, weight_decay=1e-3, value_coef=0.5) for k in ("pg", "wide", "null")}
+    dvalue = torch.zeros(n, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    for _ in range(2):
+        fits["pg"].fit.accumulate_pg(d[0], d[1], d[2], d[3], 0.2, 0.01, d[4])
+        fits["wide"].fit.accumulate_ppo(d[0], d[1], d[2], d[3], 0.2, 0.01, d[4], d[5], 1e6)          # above every |dv|
+        fits["null"].fit.accumulate_ppo(d[0], d[1], d[2], d[3], 0.2, 0.01, d[4], dvalue=dvalue)      # the third kernel, no old values
+        rows = {k: (x.fit.stats(), x.fit.pg_stats()) for k, x in fits.items()}
+        assert rows["pg"] == rows["wide"] == rows["null"]
+        assert fits["wide"].fit.vclip_stats()["value_clipped"] == 0
+        assert fits["wide"].fit.vclip_stats()["value_loss_unclipped_sum"] == rows["pg"][0]["value_loss_sum"]
+        for x in fits.values():
+            x.fit.step()
+    a = fits["pg"].fit.state()
+    assert a["steps"] == 2 and not np.array_equal(a["theta"], params.astype(np.float64))
+    for k in ("wide", "null"):
+        b = fits[k].fit.state()
+        assert all(_same(a[name], b[name]) for name in ("theta", "m", "v", "beta_pow")) and b["steps"] == 2, k
+    # ... and a range that does bind moves the value network elsewhere
+    fits["wide"].fit.accumulate_ppo(d[0], d[1], d[2], d[3], 0.2, 0.01, d[4], d[5], 1e-3)
+    fits["pg"].fit.accumulate_pg(d[0], d[1], d[2], d[3], 0.2, 0.01, d[4])
+    assert fits["wide"].fit.vclip_stats()["value_clipped"] > 0
+    for k in ("wide", "pg"):
+        fits[k].fit.step()
+    assert not np.array_equal(fits["wide"].fit.state()["theta"], fits["pg"].fit.state()["theta"])
+    for x in fits.values():
+        x.close()
+
+
+def test_ppo_argument_rules_on_the_device():
+    import torch
+    n = 70
+    spec, params, obs, actions, adv, old = _ppo_case(n, 52)
+    f = _PG(spec, params)
+    bare_spec, bare_params = seeded_policy((16,), "relu", seed=52)
+    bare = _PG(bare_spec, bare_params)                         # no value network
+    t = [_dev(a) for a in (obs, actions, adv, old, np.zeros(n), np.zeros(n, np.float32))]
+    dvalue = torch.full((n,), float(SENTINEL), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    lib = _lib.load()
+    vp = lambda x: None if x is None else C.c_void_p(x.data_ptr())      # noqa: E731
+    #       0                1          2  3  4          5          6          7    8     9          10         11  12    13    14 15          16
+    good = [f.fit._handle(), vp(t[0]), n, n, vp(t[1]), vp(t[2]), vp(t[3]), 0.2, 0.01, vp(t[4]), vp(t[5]), CV, None, None, n, vp(dvalue), None]
+    nan, inf = float("nan"), float("inf")
+    for at, bad in ((9, None), (11, 0.0), (11, -CV), (11, nan), (11, inf), (0, bare.fit._handle()), (0, None), (5, None), (7, 1.0)):
+        args = list(good)
+        args[at] = bad
+        assert lib.bsk_fit_accumulate_ppo(*args) == EINVAL, (at, bad)
+    args = list(good)                                          # d_dvalue alone needs targets too
+    args[9], args[10] = None, None
+    assert lib.bsk_fit_accumulate_ppo(*args) == EINVAL
+    assert lib.bsk_fit_vclip_stats_device(f.fit._handle(), None) == EINVAL and lib.bsk_fit_vclip_stats_device(None, None) == EINVAL
+    torch.cuda.synchronize()
+    assert (dvalue.cpu().numpy() == SENTINEL).all() and f.fit.stats()["count"] == 0
+    args = list(good)                                          # clip_vf is not read without old values
+    args[10], args[11] = None, nan
+    assert lib.bsk_fit_accumulate_ppo(*args) == 0 and lib.bsk_fit_accumulate_ppo(*good) == 0
+    torch.cuda.synchronize()
+    assert f.fit.stats()["count"] == n and (dvalue.cpu().numpy() != SENTINEL).all()
+    for kw in (dict(value_old=t[5]), dict(value_old=t[5], clip_vf=0.0), dict(value_old=t[5][:5], clip_vf=CV), dict(dvalue=dvalue[:5])):
+        with pytest.raises(ValueError):
+            f.fit.accumulate_ppo(t[0], t[1], t[2], t[3], 0.2, 0.01, t[4], **kw)
+    with pytest.raises(ValueError):
+        f.fit.accumulate_ppo(t[0], t[1], t[2], t[3], 0.2, 0.01, None, t[5], CV)
+    f.close()
+    bare.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------ the loop
+T, MB, EPOCHS, SEED = 4, 2, 2, 9
+KW = dict(lr=1e-2, weight_decay=1e-3)
+
+
+def _root(n, stream):
+    cfg = default_config(4, GRAV_PM_J2)
+    cfg.flags |= FLAG_AUTO_RESET
+    cfg.max_length = 3                                          # (episodes end, and start again, inside the rollout)
+    root = BatchedPropagator(cfg, n, stream=stream)
+    root.set_ic_pool(sample_ic_batch(23, 4, seed=73))
+    root.reset(sample_ic_batch(n, 4, seed=72))
+    root.step(np.zeros(n, np.int32), 1)                         # (the observation buffers hold a step's output)
+    steps, ticks = root.get_counters()
+    root.set_counters(steps + np.arange(n, dtype=np.int32) % 3, ticks)
+    return root
+
+
+def _log(pg):
+    return _download(pg.buffers()["log"], np.float64, EPOCHS * T * 8).reshape(EPOCHS, T, 8)
+
+
+def _same_state(a, b):
+    return all(_same(a[k], b[k]) for k in ("theta", "m", "v", "beta_pow")) and a["steps"] == b["steps"]
+
+
+@pytest.mark.parametrize("n", [8, 65])
+def test_update_equals_a_drive_of_the_primitives_by_hand(n):
+    import torch
+    spec, params = seeded_policy((16,), "relu", (16,), seed=17)
+    rows, M = T // MB, (T // MB) * n
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        root = _root(n, side.cuda_stream)
+        f, hand = _PG(spec, params, **KW), _PG(spec, params, **KW)
+        with pytest.raises(ValueError):
+            P.PolicyGradient(root, f.policy, f.fit, T, minibatches=MB, shuffle=True, seed=-1)
+        with pytest.raises(ValueError):
+            P.PolicyGradient(root, f.policy, f.fit, T, minibatches=MB, cliprange_vf=0.0)
+        pg = P.PolicyGradient(root, f.policy, f.fit, T, gamma=0.97, lam=0.9, clip=0.2, ent_coef=0.01, epochs=EPOCHS, minibatches=MB,
+                              shuffle=True, seed=SEED, cliprange_vf=0.2)
+        bufs = pg.buffers()
+        assert {"shuffle_state", "mb_obs", "mb_action", "mb_adv", "mb_logp", "mb_ret", "mb_value"} <= set(bufs) and "adv_norm" not in bufs
+        assert pg.shuffle_state() == (SEED, 0)
+        f.policy.set_rng(3, 0)
+        pg.collect()
+        torch.cuda.synchronize()
+        assert _same_state(f.fit.state(), hand.fit.state())    # (collect() does not touch the fit)
+        hist = {k: _download(bufs[k], DTYPES[k], T * n).reshape(T, n) for k in NAMES[1:]}
+        hist["obs"] = _download(bufs["obs"], np.float64, T * 5 * n).reshape(T, 5, n)
+        assert (_download(bufs["reason"], np.uint8, T * n) != 0).any()
+        c0 = BatchedPropagator.debug_counters()
+        pg.update()
+        assert BatchedPropagator.debug_counters() == c0         # no copy, no synchronisation
+        torch.cuda.synchronize()
+        assert pg.shuffle_state() == (SEED, EPOCHS)
+        log, index_sets = _log(pg), []
+        # by hand: a numpy gather by pg_perm_ref, an upload into contiguous buffers, accumulate_ppo per chunk, step; epoch + 1
+        for e in range(EPOCHS):
+            index_sets.append([])
+            for g in range(MB):
+                mb = P.pg_gather_ref((SEED, e), n, g * M, M, **hist)
+                index_sets[e].append(np.sort(mb["index"]))
+                d = {k: _dev(mb[k]) for k in NAMES}
+                torch.cuda.synchronize()
+                for c in range(rows):
+                    cut = slice(c * n, (c + 1) * n)
+                    hand.fit.accumulate_ppo(d["obs"][:, cut], d["action"][cut], d["adv"][cut], d["logp"][cut], 0.2, 0.01, d["ret"][cut],
+                                            d["value"][cut], 0.2)
+                    pg_row, fit_row = hand.fit.pg_stats(), hand.fit.stats()
+                    want = np.array([pg_row[k] for k in P.PG_STATS_COLUMNS] + [fit_row[k] for k in P.FIT_STATS_COLUMNS], np.float64)
+                    assert _same(log[e, g * rows + c], want), (e, g, c)
+                hand.fit.step()
+            assert np.array_equal(np.sort(np.concatenate(index_sets[e])), np.arange(T * n))
+        assert _same_state(f.fit.state(), hand.fit.state())
+        assert f.fit.state()["steps"] == EPOCHS * MB and not np.array_equal(f.fit.state()["theta"], params.astype(np.float64))
+        assert (log[:, :, 7].sum(axis=1) == T * n).all()        # every sample once per epoch
+        assert not np.array_equal(index_sets[0][0], index_sets[1][0])          # the epochs cut the samples differently
+        # the device's own indices say the same: the first minibatch under the words {SEED, 0} and behind one advance
+        idx = torch.zeros(M, dtype=torch.int32, device="cuda")
+        pg.set_shuffle_state(SEED, 0)
+        for e in range(EPOCHS):
+            P.pg_gather(bufs["shuffle_state"], T, n, 0, M, index_out=idx, stream=side.cuda_stream)
+            torch.cuda.synchronize()
+            assert np.array_equal(np.sort(idx.cpu().numpy()), index_sets[e][0]), e
+            P.pg_shuffle_advance(bufs["shuffle_state"], side.cuda_stream)
+        pg.close()
+        f.close()
+        hand.close()
+        root.close()
+
+
+def test_a_captured_epoch_draws_a_new_permutation_at_every_replay():
+    import torch
+    n = 65
+    spec, params = seeded_policy((16,), "relu", (16,), seed=18)
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        root = _root(n, side.cuda_stream)
+        f = _PG(spec, params, max_grad_norm=0.5, **KW)
+        pg = P.PolicyGradient(root, f.policy, f.fit, T, gamma=0.97, lam=0.9, epochs=EPOCHS, minibatches=MB, normalize_advantages=True,
+                              shuffle=True, seed=SEED, cliprange_vf=0.2)
+        assert "adv_work" in pg.buffers() and "adv_norm" not in pg.buffers()
+        f.policy.set_rng(4, 0)
+        pg.collect()
+        torch.cuda.synchronize()
+        start = f.fit.state()
+        adv = _download(pg.buffers()["adv"], np.float32, T * n)
+        pg.update()                                             # two eager epochs (and the warming of every launch)
+        torch.cuda.synchronize()
+        eager, eager_log = f.fit.state(), _log(pg)
+        assert eager["steps"] == EPOCHS * MB and pg.shuffle_state() == (SEED, EPOCHS)
+        assert _same(_download(pg.buffers()["adv"], np.float32, T * n), adv)           # the raw estimate stays: mb_adv is normalised
+        assert (eager_log[:, :, 7].sum(axis=1) == T * n).all() and f.fit.vclip_stats()["value_loss_unclipped_sum"] > 0
+        f.fit.set_state(**{k: start[k] for k in ("theta", "m", "v", "beta_pow", "steps")})
+        pg.set_shuffle_state(SEED, 0)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        c0 = BatchedPropagator.debug_counters()
+        with torch.cuda.graph(graph, stream=side):
+            pg.epoch(0)
+        for _ in range(EPOCHS):
+            graph.replay()
+        torch.cuda.synchronize()
+        assert BatchedPropagator.debug_counters() == c0         # no copy, no synchronisation
+        assert _same_state(f.fit.state(), eager) and pg.shuffle_state() == (SEED, EPOCHS)
+        assert _same(_log(pg)[0], eager_log[1])                 # the second replay wrote the second epoch's rows, into slot 0
+        del graph
+        pg.close()
+        f.close()
+        root.close()
+
+
+def test_with_everything_off_the_loop_is_the_loop_it_was():
+    import torch
+    n = 8
+    spec, params = seeded_policy((16,), "relu", (16,), seed=19)
+    side = torch.cuda.Stream()
+    out = []
+    with torch.cuda.stream(side):
+        for kw in ({}, dict(shuffle=False, seed=0, cliprange_vf=None)):
+            root = _root(n, side.cuda_stream)
+            f = _PG(spec, params, **KW)
+            pg = P.PolicyGradient(root, f.policy, f.fit, T, gamma=0.97, lam=0.9, epochs=EPOCHS, minibatches=MB, normalize_advantages=True, **kw)
+            assert not set(pg.buffers()) & {"shuffle_state", "mb_obs", "mb_value"} and "adv_norm" in pg.buffers()
+            with pytest.raises(ValueError):
+                pg.shuffle_state()
+            f.policy.set_rng(5, 0)
+            torch.cuda.synchronize()
+            out.append((pg.iterate(), f.fit.state()))
+            pg.close()
+            f.close()
+            root.close()
+    assert _same(out[0][0], out[1][0]) and _same_state(out[0][1], out[1][1]) and out[0][1]["steps"] == EPOCHS * MB
+    assert (out[0][0][:, 7] == (T // MB) * n).all()

@@ -28,6 +28,14 @@ same card.
       library built from the parent commit this is all that runs - the parent's bands, re-measured in the same session), then the
       pair and the empty step with `max_grad_norm = 0.5`, then `bsk_adv_normalize` at 8 and at 32 rows of 65 536 against the 12 bytes
       per sample it moves (4 read twice, 4 written).
+  python tools/fit_measure.py shuffle
+      shuffled minibatches and the clipped value loss ("Shuffled minibatches and the clipped value loss"),
+      timed as under `time` on the `pg` set-up: `accumulate_pg` alone and `accumulate_pg` + `step` (with BSKGPU_LIB naming a library
+      built from the parent commit this is all that runs - the parent's bands, re-measured in the same session), then
+      `accumulate_ppo` with old values and a range of 0.2, alone and with the step, then `bsk_pg_gather` of 8 x 65 536 samples out
+      of histories of 32 x 65 536, all six pairs, against the 128 bytes per sample it moves (64 read, 64 written) and the 8 TB/s of
+      the HBM - once by the permutation (scattered reads) and once by the identity (the same bytes, coalesced), so that the
+      difference is the cost of the scatter.
 """
 import os
 import sys
@@ -239,6 +247,68 @@ def cond():
     pol.close()
 
 
+def shuffle():
+    import torch
+    from _policy_bounds import observation_like, seeded_policy
+    from basilisk_env_amd import _lib
+    from basilisk_env_amd import policy as P
+    spec, params = seeded_policy(HIDDEN, "relu", (64,), seed=1)
+    obs = observation_like(N, 3)
+    rng = np.random.default_rng(5)
+    labels = np.where(obs[3] < 0.4, 1, np.where(obs[2] > 0.7, 2, 0)).astype(np.int32)
+    pol = P.DevicePolicy(spec, params)
+    fit = P.PolicyFit(pol, lr=1e-3)
+    side = torch.cuda.Stream()
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()      # noqa: E731
+    tgt = rng.normal(size=N)
+    d_obs, d_lab, d_tgt = dev(obs), dev(labels), dev(tgt)
+    d_adv, d_old = dev(rng.normal(size=N).astype(np.float32)), dev((-1.1 + rng.normal(0.0, 0.3, N)).astype(np.float32))
+    s = side.cuda_stream
+    new = hasattr(_lib.load(), "bsk_pg_gather")
+    line = "device  %-30s %8.1f us  (p10 %.1f, p90 %.1f)"
+    with torch.cuda.stream(side):
+        def acc():
+            fit.accumulate_pg(d_obs, d_lab, d_adv, d_old, 0.2, 0.01, d_tgt, stream=s)
+
+        def step():
+            acc()
+            fit.step(s)
+        print(line % (("accumulate_pg alone",) + _timed(torch, side, acc)))
+        print(line % (("accumulate_pg + step",) + _timed(torch, side, step)))
+        if new:
+            # old values 0.3 away from the targets' scale: a good share of the samples leaves the range of 0.2
+            d_vold = dev(rng.normal(0.0, 0.3, N).astype(np.float32))
+
+            def ppo():
+                fit.accumulate_ppo(d_obs, d_lab, d_adv, d_old, 0.2, 0.01, d_tgt, d_vold, 0.2, stream=s)
+
+            def ppo_step():
+                ppo()
+                fit.step(s)
+            print(line % (("accumulate_ppo alone",) + _timed(torch, side, ppo)))
+            print(line % (("accumulate_ppo + step",) + _timed(torch, side, ppo_step)))
+            ppo()
+            print("device  last row: value-clipped %d of %d" % (fit.vclip_stats()["value_clipped"], fit.stats()["count"]))
+            T, rows = 32, 8
+            m = rows * N
+            hist = dict(obs=dev(rng.normal(size=(T, 5, N))), action=dev(rng.integers(0, 3, (T, N)).astype(np.int32)),
+                        adv=dev(rng.normal(size=(T, N)).astype(np.float32)), logp=dev(rng.normal(size=(T, N)).astype(np.float32)),
+                        ret=dev(rng.normal(size=(T, N))), value=dev(rng.normal(size=(T, N)).astype(np.float32)))
+            out = dict(obs=torch.empty((5, m), dtype=torch.float64, device="cuda"), action=torch.empty(m, dtype=torch.int32, device="cuda"),
+                       adv=torch.empty(m, dtype=torch.float32, device="cuda"), logp=torch.empty(m, dtype=torch.float32, device="cuda"),
+                       ret=torch.empty(m, dtype=torch.float64, device="cuda"), value=torch.empty(m, dtype=torch.float32, device="cuda"))
+            state = dev(np.array([1, 0], np.int64))
+            names = ("obs", "action", "adv", "logp", "ret", "value")
+            print("device  histories %.0f MB, one minibatch %.0f MB" % (64.0 * T * N * 1e-6, 64.0 * m * 1e-6))
+            for what, st in (("bsk_pg_gather 8 of 32 x 65536", state), ("the same by the identity", None)):
+                med, p10, p90 = _timed(torch, side, lambda: P.pg_gather(st, T, N, m, m, *[hist[k] for k in names],
+                                                                        *[out[k] for k in names], stream=s))
+                print((line + ": %.0f GB/s of its %.1f MB, %.1f %% of 8 TB/s") % (what, med, p10, p90, 128.0 * m / med * 1e-3, 128.0 * m * 1e-6,
+                                                                              100.0 * 128.0 * m / med * 1e-3 / 8000.0))
+    fit.close()
+    pol.close()
+
+
 if __name__ == "__main__":
     {"time": time_, "kernel": kernel, "stamps": stamps, "pg": pg, "pg-kernel": lambda: pg(trace=True),
-     "cond": cond}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
+     "cond": cond, "shuffle": shuffle}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
