@@ -2,12 +2,14 @@
 // cross-entropy (and, optionally, a squared value error) from device buffers, then one Adam step into the attached policy's own
 // parameters; the same with a clipped policy-gradient loss in the cross-entropy's place (bsk_fit_accumulate_pg), and the advantage
 // estimator that feeds it from rollout histories (bsk_gae); PPO2's clipped value loss on top of that (bsk_fit_accumulate_ppo) and the
-// shuffled minibatches it is fed (bsk_pg_gather, bsk_pg_shuffle_advance; kernels: bsk_shuffle.hip).  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_fit.hip.  The policy it reads and writes through
+// shuffled minibatches it is fed (bsk_pg_gather, bsk_pg_shuffle_advance; kernels: bsk_shuffle.hip); the training log of the loop over
+// them (bsk_pg_episodes, bsk_pg_log_update, bsk_pg_log_advance; kernels: bsk_pglog.hip).  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_fit.hip.  The policy it reads and writes through
 // its handle: bsk_capi_policy.hpp.
 #include <cmath>
 
 #include "bsk_capi_policy.hpp"
 #include "bsk_fit.hpp"
+#include "bsk_pglog.hpp"
 #include "bsk_shuffle.hpp"
 
 using namespace bsk::capi;
@@ -243,6 +245,45 @@ int bsk_pg_gather(const uint64_t* d_state, int n_steps, int n_envs, int64_t stri
 int bsk_pg_shuffle_advance(uint64_t* d_state, void* stream) {
     if (!d_state) return fail(BSK_EINVAL, "bsk_pg_shuffle_advance: d_state is NULL");
     HIP_TRY(bsk::launch_pg_shuffle_advance((unsigned long long*)d_state, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream` of the current device: no copy, no synchronisation, no allocation
+}
+
+size_t bsk_pg_episodes_work_bytes(int n_envs) {
+    return n_envs < 1 ? 0 : 8 * (size_t)bsk::PG_EP_WORDS * (size_t)(((int64_t)n_envs + 63) / 64);
+}
+
+int bsk_pg_episodes(const double* d_reward_hist, const uint8_t* d_reason_hist, const int32_t* d_action_hist, const float* d_value_hist,
+                    const double* d_ret, int n_steps, int n_envs, int64_t stride, double* d_ep_return, int32_t* d_ep_len, void* d_work,
+                    double* d_ring, int capacity, const uint64_t* d_counter, void* stream) {
+    if (!d_reward_hist || !d_reason_hist) return fail(BSK_EINVAL, "bsk_pg_episodes: the reward or the reason history is NULL");
+    if (!d_ep_return || !d_ep_len || !d_work || !d_ring) return fail(BSK_EINVAL, "bsk_pg_episodes: d_ep_return, d_ep_len, d_work or d_ring is NULL");
+    if ((d_value_hist == nullptr) != (d_ret == nullptr)) return fail(BSK_EINVAL, "bsk_pg_episodes: d_value_hist and d_ret are given together or not at all");
+    if (n_steps < 1 || n_envs < 1 || stride < n_envs) return fail(BSK_EINVAL, "bsk_pg_episodes: n_steps and n_envs must be >= 1, stride >= n_envs");
+    if (capacity < 1) return fail(BSK_EINVAL, "bsk_pg_episodes: capacity must be >= 1");
+    if ((int64_t)n_steps > ((int64_t)1 << 31) / stride) return fail(BSK_EINVAL, "bsk_pg_episodes: n_steps * stride must not exceed 2^31");
+    bsk::PgEpisodesArgs a = {};
+    a.reward = d_reward_hist; a.reason = d_reason_hist; a.action = d_action_hist; a.value = d_value_hist; a.ret = d_ret;
+    a.n_steps = n_steps; a.n_envs = n_envs; a.stride = stride;
+    a.ep_return = d_ep_return; a.ep_len = d_ep_len; a.work = (double*)d_work;
+    a.ring = d_ring; a.capacity = capacity; a.counter = (const unsigned long long*)d_counter;
+    HIP_TRY(bsk::launch_pg_episodes(a, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream` of the current device: no copy, no synchronisation, no allocation
+}
+
+int bsk_pg_log_update(const double* d_diag, int n_rows, const double* d_norms, int n_norms, double* d_ring, int capacity,
+                      const uint64_t* d_counter, void* stream) {
+    if (!d_diag || !d_ring) return fail(BSK_EINVAL, "bsk_pg_log_update: d_diag or d_ring is NULL");
+    if (n_rows < 1 || capacity < 1) return fail(BSK_EINVAL, "bsk_pg_log_update: n_rows and capacity must be >= 1");
+    if (d_norms && n_norms < 1) return fail(BSK_EINVAL, "bsk_pg_log_update: n_norms must be >= 1 when d_norms is given");
+    HIP_TRY(bsk::launch_pg_log_update(d_diag, n_rows, d_norms, n_norms, d_ring, capacity, (const unsigned long long*)d_counter,
+                                      (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream` of the current device: no copy, no synchronisation, no allocation
+}
+
+int bsk_pg_log_advance(uint64_t* d_gen, int capacity, uint64_t* d_counter, void* stream) {
+    if (!d_gen || !d_counter) return fail(BSK_EINVAL, "bsk_pg_log_advance: d_gen or d_counter is NULL");
+    if (capacity < 1) return fail(BSK_EINVAL, "bsk_pg_log_advance: capacity must be >= 1");
+    HIP_TRY(bsk::launch_pg_log_advance((unsigned long long*)d_gen, capacity, (unsigned long long*)d_counter, (hipStream_t)stream));
     return BSK_OK;        // asynchronous on `stream` of the current device: no copy, no synchronisation, no allocation
 }
 

@@ -21,7 +21,12 @@ What stable-baselines' PPO2 does to every minibatch beyond that is here too, eac
 The last two pieces of PPO2's update are here as well, off by default: minibatches drawn from a new permutation of all samples in
 every epoch - ``pg_gather`` (``bsk_pg_gather``) by a permutation that is never stored, a function of two device words
 ``{seed, epoch}`` that ``policy_ref.pg_perm_ref`` repeats bit for bit - and the clipped value loss, ``PolicyFit.accumulate_ppo``
-(``bsk_fit_accumulate_ppo``); ``PolicyGradient(shuffle=True, cliprange_vf=...)`` runs both."""
+(``bsk_fit_accumulate_ppo``); ``PolicyGradient(shuffle=True, cliprange_vf=...)`` runs both.
+
+And what tells whether the agent is getting better: ``pg_episodes`` / ``pg_log_update`` / ``pg_log_advance`` (``bsk_pg_episodes``,
+...) form one row per iteration in a ring on the device - episode returns, lengths and end reasons followed across rollouts,
+PPO2's explained variance, the update's diagnostics - which ``policy_ref.pg_episodes_ref`` / ``pg_log_update_ref`` repeat bit for
+bit; ``PolicyGradient(log_capacity=...)`` keeps it and ``training_log()`` reads it."""
 import ctypes as C
 
 import numpy as np
@@ -30,8 +35,9 @@ from . import _lib
 from ._lib import check
 from .policy_base import _DeviceObject, _host_block
 from .policy_ref import (FIT_STATS_COLUMNS, PG_STATS_COLUMNS, VCLIP_STATS_COLUMNS, adv_normalize_work_bytes, check_adv_normalize,
-                         check_fit, check_fit_batch, check_gae, check_max_grad_norm, check_pg, check_pg_gather, check_pg_loop,
-                         check_pg_shuffle)
+                         check_fit, check_fit_batch, check_gae, check_max_grad_norm, check_pg, check_pg_episodes, check_pg_gather,
+                         check_pg_log, check_pg_loop, check_pg_shuffle, PG_LOG_COLS, pg_episodes_work_bytes,
+                         pg_log_table_ref)
 from .policy_spec import n_params
 
 
@@ -383,6 +389,70 @@ def pg_shuffle_advance(state, stream=0):
     check(_lib.load().bsk_pg_shuffle_advance(C.c_void_p(st), C.c_void_p(int(stream or 0))))
 
 
+def pg_episodes(reward_hist, reason_hist, n_steps, n_envs, ep_return, ep_len, work, ring, capacity, counter=None, action_hist=None,
+                value_hist=None, ret=None, stride=None, stream=0):
+    """``bsk_pg_episodes``: columns 0 .. 15 of a training-log row (``PG_LOG_COLUMNS``) out of one rollout's histories, two launches
+    on ``stream`` of the current device, no copy, no synchronisation, no allocation.  ``reward_hist`` float64 and ``reason_hist``
+    uint8 [n_steps][stride] (``stride`` defaults to ``n_envs``); ``action_hist`` int32 or None; ``value_hist`` float32 and ``ret``
+    float64, both or neither (without them the explained variance is NaN).  ``ep_return`` float64 [n_envs] and ``ep_len`` int32
+    [n_envs] carry every env's running episode from call to call (zeros: fresh envs); ``work``: ``pg_episodes_work_bytes(n_envs)``
+    bytes; ``ring`` float64 [capacity][26], of which slot ``counter`` % capacity is written - ``counter`` one uint64 device word, or
+    None: slot 0.  Each a raw device pointer or anything with ``__cuda_array_interface__`` (``policy_ref.pg_episodes_ref``, equal bit
+    for bit)."""
+    n_steps, n_envs, stride, capacity = check_pg_episodes(n_steps, n_envs, n_envs if stride is None else stride, capacity,
+                                                          value_hist is not None, ret is not None)
+    N = n_steps * stride
+    ptrs = []
+    for x, types, what, need, must in ((reward_hist, ("<f8",), "reward history", N, True), (reason_hist, ("|u1", "|b1"), "reason history", N, True),
+                                       (action_hist, ("<i4",), "action history", N, False), (value_hist, ("<f4",), "value history", N, False),
+                                       (ret, ("<f8",), "returns", N, False), (ep_return, ("<f8",), "ep_return", n_envs, True),
+                                       (ep_len, ("<i4",), "ep_len", n_envs, True), (work, ("<f8", "|u1", "<u8", "<i8"), "work", None, True),
+                                       (ring, ("<f8",), "ring", capacity * PG_LOG_COLS, True), (counter, ("<u8", "<i8"), "counter", 1, False)):
+        ptr, size, _ = _pointer(x, types, what)
+        if must and not ptr:
+            raise ValueError("%s: a device buffer is required" % what)
+        if need is None and size is not None:
+            size, need = size * int(x.__cuda_array_interface__["typestr"][2:]), pg_episodes_work_bytes(n_envs)
+        if size is not None and size < need:
+            raise ValueError("%s: at least %d elements, got %d" % (what, need, size))
+        ptrs.append(C.c_void_p(ptr) if ptr else None)
+    check(_lib.load().bsk_pg_episodes(ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], n_steps, n_envs, stride, ptrs[5], ptrs[6], ptrs[7],
+                                      ptrs[8], capacity, ptrs[9], C.c_void_p(int(stream or 0))))
+
+
+def pg_log_update(diag, n_rows, ring, capacity, counter=None, norms=None, n_norms=None, stream=0):
+    """``bsk_pg_log_update``: columns 16 .. 25 of slot ``counter`` % capacity of ``ring`` (slot 0 with ``counter`` None) - the sum of
+    the ``n_rows`` rows of ``diag`` float64 [n_rows][8], and of the ``n_norms`` {norm, scale} rows of ``norms`` float64 [n_norms][2]
+    (or None) the sum of the norms and the number of rows with scale < 1.  One launch on ``stream``, no copy, no synchronisation
+    (``policy_ref.pg_log_update_ref``)."""
+    if norms is not None and n_norms is None:
+        raise ValueError("n_norms: the number of {norm, scale} rows is required with norms")
+    n_rows, capacity, n_norms = check_pg_log(n_rows, capacity, None if norms is None else n_norms)
+    ptrs = []
+    for x, types, what, need, must in ((diag, ("<f8",), "diag", 8 * n_rows, True), (norms, ("<f8",), "norms", 2 * (n_norms or 0), False),
+                                       (ring, ("<f8",), "ring", capacity * PG_LOG_COLS, True), (counter, ("<u8", "<i8"), "counter", 1, False)):
+        ptr, size, _ = _pointer(x, types, what)
+        if must and not ptr:
+            raise ValueError("%s: a device buffer is required" % what)
+        if size is not None and size < need:
+            raise ValueError("%s: at least %d elements, got %d" % (what, need, size))
+        ptrs.append(C.c_void_p(ptr) if ptr else None)
+    check(_lib.load().bsk_pg_log_update(ptrs[0], n_rows, ptrs[1], n_norms or 0, ptrs[2], capacity, ptrs[3], C.c_void_p(int(stream or 0))))
+
+
+def pg_log_advance(gen, capacity, counter, stream=0):
+    """``bsk_pg_log_advance``: gen[counter % capacity] = counter, counter += 1 - ``gen`` uint64 [capacity], ``counter`` one uint64
+    device word.  One launch on ``stream``, no copy, no synchronisation."""
+    _, capacity, _ = check_pg_log(1, capacity)
+    ptrs = []
+    for x, what, need in ((gen, "gen", capacity), (counter, "counter", 1)):
+        ptr, size, _ = _pointer(x, ("<u8", "<i8"), what)
+        if not ptr or (size is not None and size < need):
+            raise ValueError("%s: %d 64-bit device words" % (what, need))
+        ptrs.append(C.c_void_p(ptr))
+    check(_lib.load().bsk_pg_log_advance(ptrs[0], capacity, ptrs[1], C.c_void_p(int(stream or 0))))
+
+
 class PolicyGradient(object):
     """On-device policy-gradient training (PPO; the clipped surrogate of ``bsk_fit_accumulate_pg`` on advantages from ``bsk_gae``):
     ``env`` - a ``BatchedPropagator`` (or an env over one) created with ``FLAG_AUTO_RESET`` -, ``policy`` - a ``DevicePolicy`` with a
@@ -409,15 +479,27 @@ class PolicyGradient(object):
     ``normalize_advantages`` then normalises every gathered minibatch in place - PPO2's rule, over the random subset - and
     ``collect()`` normalises nothing.  ``cliprange_vf`` - the clipped value loss of ``PolicyFit.accumulate_ppo`` against the
     rollout's recorded values, with or without ``shuffle``.  ``PolicyGradient(shuffle=True, normalize_advantages=True,
-    cliprange_vf=0.2)`` with ``fit.max_grad_norm = 0.5`` is PPO2's update."""
+    cliprange_vf=0.2)`` with ``fit.max_grad_norm = 0.5`` is PPO2's update.
+
+    ``log_capacity`` > 0 keeps a training log of that many iterations on the device, as ``DeviceEvolutionStrategy`` does: a ring of
+    rows of ``PG_LOG_COLUMNS`` - how many episodes ended in the rollout, their returns and lengths, how they ended, which actions
+    were taken, PPO2's explained variance, and the update's diagnostics summed over the iteration.  ``collect()`` then ends with
+    ``pg_episodes`` over its histories - the return and the length of every env's running episode are carried from rollout to
+    rollout in ``ep_return`` / ``ep_len`` - and ``update()`` with ``pg_log_update`` and ``pg_log_advance``; ``training_log()`` reads
+    the ring.  The rows survive the replay of a captured iteration, which overwrites ``log``.  Nothing in it writes what training
+    reads: theta, m, v and the histories are the same bit for bit with the log on.  0, the default, allocates and enqueues what
+    the loop always did."""
 
     def __init__(self, env, policy, fit, n_steps, gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, epochs=4, minibatches=4, substeps=1,
-                 normalize_advantages=False, obs_stats=None, std_min=1e-6, shuffle=False, seed=0, cliprange_vf=None):
+                 normalize_advantages=False, obs_stats=None, std_min=1e-6, shuffle=False, seed=0, cliprange_vf=None, log_capacity=0):
         from . import _hip
         from ._lib import FLAG_AUTO_RESET
         (self.n_steps, self.gamma, self.lam, self.clip, self.ent_coef, self.epochs, self.minibatches,
          self.substeps) = check_pg_loop(n_steps, gamma, lam, clip, ent_coef, epochs, minibatches, substeps)
         self.shuffle, seed, self.cliprange_vf = check_pg_shuffle(shuffle, seed, cliprange_vf, self.n_steps, self.minibatches)
+        if isinstance(log_capacity, bool) or not isinstance(log_capacity, (int, np.integer)) or not 0 <= log_capacity < 2 ** 31:
+            raise ValueError("log_capacity must be an integer in 0 .. 2^31 - 1, got %r" % (log_capacity,))
+        self.log_capacity = int(log_capacity)
         self.normalize_advantages, self.obs_stats, self.std_min = bool(normalize_advantages), obs_stats, float(std_min)
         if not np.isfinite(self.std_min) or not (self.std_min > 0.0):
             raise ValueError("std_min must be finite and positive")
@@ -446,6 +528,10 @@ class PolicyGradient(object):
                 sizes.update(adv_work=adv_normalize_work_bytes(n))
         elif self.normalize_advantages:
             sizes.update(adv_norm=4 * T * n, adv_work=adv_normalize_work_bytes(n))
+        if self.log_capacity:
+            check_pg_episodes(T, n, n, self.log_capacity)
+            sizes.update(ep_return=8 * n, ep_len=4 * n, ep_work=pg_episodes_work_bytes(n), log_ring=8 * PG_LOG_COLS * self.log_capacity,
+                         log_gen=8 * self.log_capacity, log_counter=8)
         if obs_stats is not None:
             if obs_stats.n_envs < n or obs_stats.device != prop.device:
                 raise ValueError("obs_stats: a statistics object of at least %d envs on device %d" % (n, prop.device))
@@ -457,6 +543,9 @@ class PolicyGradient(object):
         with _hip.device_guard(prop.device):
             for k in ("obs", "action", "adv", "reason"):
                 _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(b[k].ptr), 0, sizes[k], C.c_void_p(stream)), "hipMemsetAsync")
+            if self.log_capacity:          # every slot "never written" (all ones), everything else zero: fresh envs, iteration 0
+                for k, byte in (("ep_return", 0), ("ep_len", 0), ("ep_work", 0), ("log_ring", 0), ("log_counter", 0), ("log_gen", 0xFF)):
+                    _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(b[k].ptr), byte, sizes[k], C.c_void_p(stream)), "hipMemsetAsync")
             fit.accumulate_pg(b["obs"].ptr, b["action"].ptr, b["adv"].ptr, None, self.clip, 0.0, None, b["reason"].ptr, n=n, stride=n,
                               stream=stream)
         if self.shuffle:
@@ -488,6 +577,47 @@ class PolicyGradient(object):
                 _hip.check(_hip.runtime().hipMemcpy(ptr, host, 16, _hip.hipMemcpyHostToDevice), "hipMemcpy")
         return words
 
+    def training_log(self):
+        """-> (iterations uint64 (k,), rows float64 (k, 26)): the slots of the ring that have been written, oldest first - one row of
+        ``PG_LOG_COLUMNS`` per ``collect()`` + ``update()``, the last ``log_capacity`` of them.  Synchronises."""
+        if not self.log_capacity:
+            raise ValueError("the loop was created without log_capacity")
+        gen, rows = np.empty(self.log_capacity, np.uint64), np.empty((self.log_capacity, PG_LOG_COLS), np.float64)
+        self._log_copy(((gen, "log_gen"), (rows, "log_ring")), False)
+        return pg_log_table_ref(gen, rows)
+
+    def episode_state(self):
+        """-> (ep_return float64 (n,), ep_len int32 (n,), counter): the return and the length of every env's running episode and the
+        number of the iteration being written.  For checkpoints; synchronises."""
+        if not self.log_capacity:
+            raise ValueError("the loop was created without log_capacity")
+        R, L, c = np.empty(self.n_envs, np.float64), np.empty(self.n_envs, np.int32), np.empty(1, np.uint64)
+        self._log_copy(((R, "ep_return"), (L, "ep_len"), (c, "log_counter")), False)
+        return R, L, int(c[0])
+
+    def set_episode_state(self, ep_return, ep_len, counter=0):
+        """The three back: with them - and the env's own state - the log goes on as if it had not been interrupted (the ring's rows
+        are not part of it).  Synchronises."""
+        if not self.log_capacity:
+            raise ValueError("the loop was created without log_capacity")
+        R, L = np.ascontiguousarray(ep_return, np.float64).reshape(-1), np.ascontiguousarray(ep_len, np.int32).reshape(-1)
+        if R.size != self.n_envs or L.size != self.n_envs:
+            raise ValueError("ep_return and ep_len: one value per env (%d)" % self.n_envs)
+        if isinstance(counter, bool) or not isinstance(counter, (int, np.integer)) or not 0 <= int(counter) < 2 ** 64:
+            raise ValueError("counter must be an integer in 0 .. 2^64 - 1, got %r" % (counter,))
+        self._log_copy(((R, "ep_return"), (L, "ep_len"), (np.array([int(counter)], np.uint64), "log_counter")), True)
+
+    def _log_copy(self, pairs, upload):
+        from . import _hip
+        self.prop.sync()
+        with _hip.device_guard(self.prop.device):
+            for host, name in pairs:
+                h, d = C.c_void_p(host.ctypes.data), C.c_void_p(self._buf[name].ptr)
+                if upload:
+                    _hip.check(_hip.runtime().hipMemcpy(d, h, host.nbytes, _hip.hipMemcpyHostToDevice), "hipMemcpy")
+                else:
+                    _hip.check(_hip.runtime().hipMemcpy(h, d, host.nbytes, _hip.hipMemcpyDeviceToHost), "hipMemcpy")
+
     def close(self):
         if getattr(self, "_buf", None):
             self.prop.sync()
@@ -513,7 +643,10 @@ class PolicyGradient(object):
         reads - and ``adv_work``, the scratch of ``bsk_adv_normalize``.  With ``shuffle``: ``shuffle_state`` u64[2] = {seed, epoch}
         and the gathered minibatch of M = (n_steps // minibatches) * n samples, ``mb_obs`` f64[5][M], ``mb_action`` i32,
         ``mb_adv`` f32 (normalised in place under ``normalize_advantages``; there is then no ``adv_norm``), ``mb_logp`` f32,
-        ``mb_ret`` f64 and ``mb_value`` f32 [M] (written under ``cliprange_vf`` only)"""
+        ``mb_ret`` f64 and ``mb_value`` f32 [M] (written under ``cliprange_vf`` only).  With ``log_capacity``: ``ep_return`` f64[n]
+        and ``ep_len`` i32[n] (every env's running episode), ``ep_work`` (the scratch of ``bsk_pg_episodes``), ``log_ring``
+        f64[log_capacity][26], ``log_gen`` u64[log_capacity] (the iteration each slot holds; all ones: never written) and
+        ``log_counter`` u64 (the iteration being written)"""
         return {k: b.ptr for k, b in self._buf.items()}
 
     def collect(self):
@@ -541,6 +674,9 @@ class PolicyGradient(object):
                 for g in range(self.minibatches):
                     normalize_advantages(b["adv"].ptr + 4 * n * rows * g, rows, n, b["adv_norm"].ptr + 4 * n * rows * g,
                                          work=b["adv_work"].ptr, stream=stream)
+            if self.log_capacity:
+                pg_episodes(b["reward"].ptr, b["reason"].ptr, T, n, b["ep_return"].ptr, b["ep_len"].ptr, b["ep_work"].ptr, b["log_ring"].ptr,
+                            self.log_capacity, b["log_counter"].ptr, b["action"].ptr, b["value"].ptr, b["ret"].ptr, stream=stream)
 
     def update(self):
         """``epochs`` passes of ``minibatches`` groups of consecutive time rows: per row one ``accumulate_pg`` of the n envs and its
@@ -550,6 +686,13 @@ class PolicyGradient(object):
         self._clipped = self.fit.max_grad_norm > 0.0
         for e in range(self.epochs):
             self.epoch(e)
+        if self.log_capacity:
+            from . import _hip
+            b, stream = self._buf, self.prop.stream_ptr()
+            with _hip.device_guard(self.prop.device):
+                pg_log_update(b["log"].ptr, self.epochs * self.n_steps, b["log_ring"].ptr, self.log_capacity, b["log_counter"].ptr,
+                              b["grad_norm_log"].ptr if self._clipped else None, self.epochs * self.minibatches, stream=stream)
+                pg_log_advance(b["log_gen"].ptr, self.log_capacity, b["log_counter"].ptr, stream)
 
     def epoch(self, e=0):
         """One pass of ``update()`` over the minibatches, enqueued on the env's stream: its diagnostics rows go to the log's rows of

@@ -1644,3 +1644,180 @@ def check_pg_gather(n_steps, n_envs, stride, q0, m, out_stride):
     if q0 + m > n_steps * n_envs:
         raise ValueError("the window q0 .. q0 + m - 1 must lie inside 0 .. n_steps * n_envs - 1")
     return n_steps, n_envs, stride, q0, m, out_stride
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# A training log for the policy-gradient loop (bsk_pg_episodes, bsk_pg_log_update, bsk_pg_log_advance; definition in
+# include/bskgpu.h, kernels in csrc/bsk_pglog.hip), restated
+
+PG_LOG_COLUMNS = ("episodes", "return_sum", "return_sum_sq", "return_min", "return_max", "len_sum",
+                  "end_length", "end_wheels", "end_battery", "end_orbit", "act_0", "act_1", "act_2", "reward_sum",
+                  "explained_variance", "value_err_sum_sq") + PG_STATS_COLUMNS + FIT_STATS_COLUMNS + ("grad_norm_sum", "grad_clipped")
+PG_LOG_COLS = len(PG_LOG_COLUMNS)              # BSK_PG_LOG_COLS
+PG_EP_WORDS = 19                               # words of one wave's partial row: 7 sums, 2 extremes, 10 counts
+PG_EP_SUMS = ("s_R", "s_R2", "s_rew", "s_y", "s_y2", "s_e", "s_e2")
+PG_EP_COUNTS = ("n_ep", "len_sum", "end_length", "end_wheels", "end_battery", "end_orbit", "act_0", "act_1", "act_2", "samples")
+
+
+def pg_episodes_work_bytes(n_envs):
+    """``bsk_pg_episodes_work_bytes``: 8 * 19 * ceil(n_envs / 64), the device bytes ``bsk_pg_episodes`` needs for its partial rows."""
+    if isinstance(n_envs, bool) or not isinstance(n_envs, (int, np.integer)) or n_envs < 1:
+        raise ValueError("n_envs must be an integer >= 1, got %r" % (n_envs,))
+    return 8 * PG_EP_WORDS * ((int(n_envs) + 63) // 64)
+
+
+def check_pg_episodes(n_steps, n_envs, stride, capacity, with_value=False, with_ret=False):
+    """The argument rules of ``bsk_pg_episodes`` that need no device -> (n_steps, n_envs, stride, capacity); ValueError where it
+    returns BSK_EINVAL: each an integer >= 1, stride >= n_envs, n_steps * stride <= 2^31, value and return histories both or
+    neither."""
+    for what, x in (("n_steps", n_steps), ("n_envs", n_envs), ("stride", stride), ("capacity", capacity)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
+            raise ValueError("%s must be an integer >= 1, got %r" % (what, x))
+    if stride < n_envs:
+        raise ValueError("stride must be >= n_envs")
+    if int(n_steps) * int(stride) > 2 ** 31:
+        raise ValueError("n_steps * stride must not exceed 2^31")
+    if bool(with_value) != bool(with_ret):
+        raise ValueError("the value and the return histories are given together or not at all")
+    return int(n_steps), int(n_envs), int(stride), int(capacity)
+
+
+def check_pg_log(n_rows, capacity, n_norms=None):
+    """The argument rules of ``bsk_pg_log_update`` (and, with n_rows = 1, of ``bsk_pg_log_advance``) that need no device ->
+    (n_rows, capacity, n_norms): n_rows and capacity integers >= 1; ``n_norms`` None (no norms) or an integer >= 1."""
+    for what, x in (("n_rows", n_rows), ("capacity", capacity)) + ((("n_norms", n_norms),) if n_norms is not None else ()):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
+            raise ValueError("%s must be an integer >= 1, got %r" % (what, x))
+    return int(n_rows), int(capacity), None if n_norms is None else int(n_norms)
+
+
+def _pg_episode_state(state, n):
+    if state is None:
+        return np.zeros(n, np.float64), np.zeros(n, np.int32)
+    R, L = np.array(state[0], dtype=np.float64).reshape(-1), np.array(state[1], dtype=np.int32).reshape(-1)
+    if R.shape != (n,) or L.shape != (n,):
+        raise ValueError("state: (ep_return float64 (%d,), ep_len int32 (%d,))" % (n, n))
+    return R, L
+
+
+def pg_episodes_walk_ref(reward, reason, action=None, value=None, ret=None, state=None):
+    """The per-column walk of ``bsk_pg_episodes`` (csrc/bsk_pglog.hpp: pg_episode_walk), every column at once -> (sums float64
+    (7, N) in ``PG_EP_SUMS``' order, mn float64 (N,), mx float64 (N,), counts int64 (10, N) in ``PG_EP_COUNTS``' order,
+    (ep_return float64 (N,), ep_len int32 (N,))): what each lane holds in front of the trees, and the state it writes back.
+    ``reward`` float64, ``reason`` uint8, ``action`` int32 or None, ``value`` float32 and ``ret`` float64 (both or neither), each
+    (T, N); ``state``: the carried (ep_return, ep_len) or None (zeros: fresh envs).  Rows ascending, every operation rounded on its
+    own."""
+    reward = np.asarray(reward, np.float64)
+    if reward.ndim != 2 or reward.shape[0] < 1 or reward.shape[1] < 1:
+        raise ValueError("reward: (n_steps, n_envs)")
+    T, N = reward.shape
+    check_pg_episodes(T, N, N, 1, value is not None, ret is not None)
+    reason = np.asarray(reason).reshape(T, N).astype(np.uint8)
+    action = None if action is None else np.asarray(action, np.int32).reshape(T, N)
+    if value is not None:
+        value, ret = np.asarray(value, np.float32).reshape(T, N), np.asarray(ret, np.float64).reshape(T, N)
+    R, L = _pg_episode_state(state, N)
+    L = L.astype(np.int64)
+    s = np.zeros((7, N), np.float64)
+    mn, mx = np.full(N, np.nan, np.float64), np.full(N, np.nan, np.float64)
+    k = np.zeros((10, N), np.int64)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        for t in range(T):
+            R = R + reward[t]
+            L = L + 1
+            s[2] = s[2] + reward[t]
+            k[9] += 1
+            if action is not None:
+                for a in range(3):
+                    k[6 + a] += action[t] == a
+            if value is not None:
+                y = ret[t]
+                e = y - value[t].astype(np.float64)
+                s[3] = s[3] + y
+                s[4] = s[4] + y * y
+                s[5] = s[5] + e
+                s[6] = s[6] + e * e
+            q = reason[t] != 0
+            s[0] = np.where(q, s[0] + R, s[0])
+            s[1] = np.where(q, s[1] + R * R, s[1])
+            mn = np.where(q, _extreme_pick(mn, R, False), mn)
+            mx = np.where(q, _extreme_pick(mx, R, True), mx)
+            k[0] += q
+            k[1] += np.where(q, L, 0)
+            for b in range(4):
+                k[2 + b] += q & ((reason[t] & (1 << b)) != 0)
+            R = np.where(q, np.float64(0.0), R)
+            L = np.where(q, 0, L)
+    return s, mn, mx, k, (R, L.astype(np.int32))
+
+
+def pg_episodes_ref(reward, reason, action=None, value=None, ret=None, state=None):
+    """``bsk_pg_episodes`` restated -> (row float64 (16,): columns 0 .. 15 of ``PG_LOG_COLUMNS``, (ep_return float64 (N,), ep_len
+    int32 (N,)): the new state).  ``pg_episodes_walk_ref`` per column; per wave of 64 columns (lanes at and above N bring +0.0, NaN
+    and 0) the seven sums through the fitness tree and the two extremes through it under their own rule; the waves joined by
+    ``obs_stats_totals_ref``'s rule - lane l the partials l, l + 64, ... ascending from the first, then the tree; the counts as
+    integers, converted once; the explained variance 1 - var_e / var_y out of ``obs_moments_ref`` on (S_y, S_y2, N) and (S_e, S_e2, N),
+    NaN when var_y == 0 or without ``value`` / ``ret``.  Bit for bit the device's."""
+    s, mn, mx, k, new_state = pg_episodes_walk_ref(reward, reason, action, value, ret, state)
+    N = s.shape[1]
+    W = (N + 63) // 64
+    lanes = np.zeros((7, W * 64), np.float64)
+    lanes[:, :N] = s
+    ext = np.full((2, W * 64), np.nan, np.float64)
+    ext[0, :N], ext[1, :N] = mn, mx
+    with np.errstate(invalid="ignore", over="ignore", under="ignore", divide="ignore"):
+        tree = lanes.reshape(7, W, 64)
+        for stride in _TREE:
+            tree[:, :, :stride] = tree[:, :, :stride] + tree[:, :, stride:2 * stride]
+        part = np.zeros((W, 10), np.float64)
+        part[:, :7] = tree[:, :, 0].T
+        tot, _ = obs_stats_totals_ref((part, np.zeros(W, np.uint64)))
+        lo = _extreme_lanes_then_tree(_extreme_lanes_then_tree(ext[0].reshape(W, 64), False), False)
+        hi = _extreme_lanes_then_tree(_extreme_lanes_then_tree(ext[1].reshape(W, 64), True), True)
+        n = k.sum(axis=1)
+        row = np.zeros(16, np.float64)
+        row[0], row[1], row[2], row[3], row[4], row[5] = np.float64(n[0]), tot[0], tot[1], lo, hi, np.float64(n[1])
+        row[6:13] = n[2:9].astype(np.float64)
+        row[13] = tot[2]
+        row[14] = np.nan
+        if value is not None:
+            _, var = obs_moments_ref(np.array([tot[3], tot[5], 0, 0, 0, tot[4], tot[6], 0, 0, 0], np.float64), int(n[9]))
+            if var[0] != 0.0:
+                row[14] = np.float64(1.0) - var[1] / var[0]
+        row[15] = tot[6]
+    return row, new_state
+
+
+def pg_log_update_ref(diag, norms=None):
+    """``bsk_pg_log_update`` restated -> float64 (10,): columns 16 .. 25 of ``PG_LOG_COLUMNS``.  ``diag`` float64 (n_rows, 8): each
+    column summed, rows ascending FROM the first; ``norms`` float64 (n_norms, 2) = {norm, scale} rows or None: the norms summed the
+    same way and the rows with scale < 1.0 counted; +0.0 and 0 without."""
+    diag = np.asarray(diag, np.float64)
+    if diag.ndim != 2 or diag.shape[1] != 8:
+        raise ValueError("diag: (n_rows, 8)")
+    check_pg_log(diag.shape[0], 1, None if norms is None else np.asarray(norms).shape[0])
+    out = np.zeros(10, np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = diag[0].copy()
+        for r in range(1, diag.shape[0]):
+            s = s + diag[r]
+        out[:8] = s
+        if norms is not None:
+            norms = np.asarray(norms, np.float64)
+            if norms.ndim != 2 or norms.shape[1] != 2:
+                raise ValueError("norms: (n_norms, 2)")
+            t = norms[0, 0]
+            for r in range(1, norms.shape[0]):
+                t = t + norms[r, 0]
+            out[8], out[9] = t, np.float64(int((norms[:, 1] < 1.0).sum()))
+    return out
+
+
+def pg_log_table_ref(gen, rows):
+    """The ring as the device holds it -> ``training_log``'s (iterations uint64 (k,), rows float64 (k, 26)) over the slots that have
+    been written (``gen`` is not all ones), oldest first."""
+    gen = np.asarray(gen, np.uint64).reshape(-1)
+    rows = np.asarray(rows, np.float64).reshape(gen.size, PG_LOG_COLS)
+    valid = np.flatnonzero(gen != np.uint64(ES_LOG_EMPTY))
+    valid = valid[np.argsort(gen[valid], kind="stable")]
+    return gen[valid].copy(), rows[valid].copy()

@@ -19,6 +19,7 @@
 #ifndef BSKGPU_H
 #define BSKGPU_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -1283,6 +1284,63 @@ int bsk_fit_accumulate_ppo(bsk_fit* f, const double* d_obs, int64_t obs_stride, 
 /* The value-clip row as DEVICE words, f64[2] (read-only for the caller; valid for the fit's lifetime; zero before the first launch
  * with d_value_old).  No launch, no copy, no synchronisation. */
 int bsk_fit_vclip_stats_device(bsk_fit* f, const double** d_row2);
+
+/* A training log for the policy-gradient loop: a ring of rows f64[capacity][BSK_PG_LOG_COLS] in DEVICE memory, the caller's, one row
+ * per iteration, formed by small launches behind bsk_gae and behind the last bsk_fit_step - so that a loop replayed from a graph,
+ * with no host in it, still says how the episodes went.  Free functions of the current device; none allocates, copies or
+ * synchronises, all are capturable from the first call.  Nothing here writes a buffer that training reads.  All f64, every
+ * operation rounded on its own (no FMA), no atomics, a fixed order: basilisk_env_amd/policy_ref.py repeats it bit for bit
+ * (pg_episodes_ref, pg_log_update_ref).  The row (PG_LOG_COLUMNS in Python); counts are integers converted to f64 once:
+ *   [0] episodes ended in this rollout      [1], [2] the sum and the sum of squares of their undiscounted returns
+ *   [3], [4] the least and the greatest of those returns (NaN with none)      [5] the sum of their lengths in steps
+ *   [6 .. 9] ends by BSK_DONE_LENGTH, _WHEELS, _BATTERY, _ORBIT (a reason byte with two bits set counts in both, the outcome rows'
+ *   rule)      [10 .. 12] steps under action 0, 1, 2 (any other value is counted nowhere)      [13] the sum of all rewards
+ *   [14] the explained variance 1 - var(ret - value) / var(ret), PPO2's explained_variance      [15] the sum of (ret - value)^2
+ *   [16 .. 19] the policy-gradient diagnostics row (bsk_fit_pg_stats_device) summed over every accumulate of the iteration
+ *   [20 .. 23] the same sum of the fit's row (bsk_fit_stats_device)
+ *   [24] the sum of the gradient norms of the iteration's steps      [25] the steps whose gradient was clipped (scale < 1.0)
+ *
+ * bsk_pg_episodes: columns 0 .. 15 from the histories of one rollout, [n_steps][stride] in bsk_policy_rollout's layout, TWO
+ * launches.  d_action_hist may be NULL (columns 10 .. 12 are then 0); d_value_hist and d_ret (bsk_gae's) both or neither.  The
+ * return and the length of every env's RUNNING episode are carried from call to call in d_ep_return f64[n_envs] and d_ep_len
+ * int32[n_envs], the caller's: zero bytes mean a fresh env, and an episode that began before the state was zeroed reports only what
+ * was seen of it.  Per env j, from R = d_ep_return[j], L = d_ep_len[j], rows t = 0 .. n_steps - 1 ASCENDING, sums from +0.0, the
+ * extremes from NaN, counts from 0:
+ *   R = R + reward[t][j];  L = L + 1;  s_rew = s_rew + reward[t][j];  act_n[action[t][j]] += 1
+ *   y = ret[t][j];  v = (double)value[t][j];  e = y - v;  s_y = s_y + y;  s_y2 = s_y2 + y * y;  s_e = s_e + e;  s_e2 = s_e2 + e * e
+ *   reason[t][j] != 0:  s_R = s_R + R;  s_R2 = s_R2 + R * R;  mn, mx take R under the rule of the outcome rows (the candidate
+ *     replaces the incumbent when it is smaller / greater or the incumbent is a NaN);  n_ep += 1;  len_sum += L;  one count per set
+ *     bit of the four;  then R = +0.0, L = 0
+ * and R, L are written back.  Wave w is the envs 64 w .. 64 w + 63 (a lane at or above n_envs brings +0.0, NaN and 0): the seven
+ * sums {s_R, s_R2, s_rew, s_y, s_y2, s_e, s_e2} each through the fitness tree of the observation statistics (stride 32 ... 1), the
+ * two extremes through the same tree under their rule (lane l the incumbent, lane l + stride the candidate), the ten counts {n_ep,
+ * len_sum, the four ends, the three actions, the samples walked} as integers; lane 0 WRITES the 19 words of wave w into d_work - no
+ * state is carried there.  The join is bsk_adv_normalize's per column: s[l] = the entries w = l, l + 64, ... ascending from the
+ * first (+0.0, or NaN, with none), then the tree.  With N the samples walked, as for an observation row:
+ *   mean_y = S_y / N;  var_y = max(S_y2 / N - mean_y * mean_y, 0);  likewise var_e;  [14] = 1.0 - var_e / var_y,
+ * NaN when var_y == 0 (PPO2's rule) or without the value and return histories ([15] is then +0.0).
+ * The row goes to slot *d_counter % capacity of d_ring, slot 0 with d_counter NULL; columns 16 .. 25 are left as they are.
+ * d_work: bsk_pg_episodes_work_bytes(n_envs) = 8 * 19 * ceil(n_envs / 64) bytes, 8-byte aligned (0 for n_envs < 1).  Columns at or
+ * above n_envs of a strided history are neither read nor written.  One env per lane: latency-bound at 65 536 envs, as bsk_gae is.
+ * BSK_EINVAL before any launch: NULL reward, reason, state, work or ring pointers; exactly one of d_value_hist and d_ret;
+ * n_steps < 1, n_envs < 1, stride < n_envs, capacity < 1; n_steps * stride > 2^31.
+ *
+ * bsk_pg_log_update: columns 16 .. 25 of the slot, ONE launch of one wave.  d_diag f64[n_rows][8]: [16 + c] = the sum of column c,
+ * rows ascending from the first.  d_norms f64[n_norms][2] = {norm, scale} rows (bsk_fit_grad_norm_device) or NULL: [24] = the sum
+ * of the norms ascending from the first, [25] = the rows with scale < 1.0; with NULL +0.0 and 0.  Columns 0 .. 15 are left as they
+ * are.  BSK_EINVAL: NULL d_diag or d_ring; n_rows < 1; capacity < 1; d_norms given with n_norms < 1.
+ *
+ * bsk_pg_log_advance: d_gen[*d_counter % capacity] = *d_counter;  *d_counter += 1 - ONE launch of one thread.  d_gen
+ * uint64[capacity] names the iteration every slot holds (the caller fills it with all ones: never written).  BSK_EINVAL: NULL d_gen
+ * or d_counter; capacity < 1. */
+#define BSK_PG_LOG_COLS 26
+size_t bsk_pg_episodes_work_bytes(int n_envs);
+int bsk_pg_episodes(const double* d_reward_hist, const uint8_t* d_reason_hist, const int32_t* d_action_hist, const float* d_value_hist,
+                    const double* d_ret, int n_steps, int n_envs, int64_t stride, double* d_ep_return, int32_t* d_ep_len, void* d_work,
+                    double* d_ring, int capacity, const uint64_t* d_counter, void* stream);
+int bsk_pg_log_update(const double* d_diag, int n_rows, const double* d_norms, int n_norms, double* d_ring, int capacity,
+                      const uint64_t* d_counter, void* stream);
+int bsk_pg_log_advance(uint64_t* d_gen, int capacity, uint64_t* d_counter, void* stream);
 
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the

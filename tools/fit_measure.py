@@ -36,6 +36,12 @@ same card.
       of histories of 32 x 65 536, all six pairs, against the 128 bytes per sample it moves (64 read, 64 written) and the 8 TB/s of
       the HBM - once by the permutation (scattered reads) and once by the identity (the same bytes, coalesced), so that the
       difference is the cost of the scatter.
+  python tools/fit_measure.py pglog
+      the training log of the gradient loop ("A training log for the gradient loop"), timed as under `time` on
+      the `pg` set-up: `accumulate_pg` alone, `accumulate_pg` + `step`, `bsk_gae` at 32 x 65 536 and `bsk_pg_gather` of 8 x 65 536
+      (with BSKGPU_LIB naming a library built from the parent commit this is all that runs - the parent's bands, re-measured in the
+      same session), then `bsk_pg_episodes` at 32 x 65 536 with all histories against the 25 bytes per sample it reads, beside
+      `bsk_gae` at the same shape, and `bsk_pg_log_update` + `bsk_pg_log_advance` over 128 diagnostics rows and 16 norms.
 """
 import os
 import sys
@@ -309,6 +315,77 @@ def shuffle():
     pol.close()
 
 
+def pglog():
+    import torch
+    from _policy_bounds import observation_like, seeded_policy
+    from basilisk_env_amd import _lib
+    from basilisk_env_amd import policy as P
+    spec, params = seeded_policy(HIDDEN, "relu", (64,), seed=1)
+    obs = observation_like(N, 3)
+    rng = np.random.default_rng(5)
+    labels = np.where(obs[3] < 0.4, 1, np.where(obs[2] > 0.7, 2, 0)).astype(np.int32)
+    pol = P.DevicePolicy(spec, params)
+    fit = P.PolicyFit(pol, lr=1e-3)
+    side = torch.cuda.Stream()
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()      # noqa: E731
+    d_obs, d_lab, d_tgt = dev(obs), dev(labels), dev(rng.normal(size=N))
+    d_adv, d_old = dev(rng.normal(size=N).astype(np.float32)), dev((-1.1 + rng.normal(0.0, 0.3, N)).astype(np.float32))
+    s = side.cuda_stream
+    new = hasattr(_lib.load(), "bsk_pg_episodes")
+    line = "device  %-34s %8.1f us  (p10 %.1f, p90 %.1f)"
+    with torch.cuda.stream(side):
+        def acc():
+            fit.accumulate_pg(d_obs, d_lab, d_adv, d_old, 0.2, 0.01, d_tgt, stream=s)
+
+        def step():
+            acc()
+            fit.step(s)
+        print(line % (("accumulate_pg alone",) + _timed(torch, side, acc)))
+        print(line % (("accumulate_pg + step",) + _timed(torch, side, step)))
+        T, rows = 32, 8
+        m = rows * N
+        hist = dict(obs=dev(rng.normal(size=(T, 5, N))), action=dev(rng.integers(0, 3, (T, N)).astype(np.int32)),
+                    adv=torch.empty((T, N), dtype=torch.float32, device="cuda"), logp=dev(rng.normal(size=(T, N)).astype(np.float32)),
+                    ret=torch.empty((T, N), dtype=torch.float64, device="cuda"), value=dev(rng.normal(size=(T, N)).astype(np.float32)))
+        d_rew = dev(rng.normal(size=(T, N)))
+        d_why = dev(((rng.uniform(size=(T, N)) < 0.02) * rng.choice([1, 2, 4, 8], (T, N))).astype(np.uint8))
+        gae_t = _timed(torch, side, lambda: P.gae(d_rew, d_why, hist["value"], None, T, N, hist["adv"], hist["ret"], stream=s))
+        print((line + ": %.0f GB/s of its %.1f MB") % (("bsk_gae 32 x 65536",) + gae_t + (25.0 * T * N / gae_t[0] * 1e-3, 25.0 * T * N * 1e-6)))
+        out = dict(obs=torch.empty((5, m), dtype=torch.float64, device="cuda"), action=torch.empty(m, dtype=torch.int32, device="cuda"),
+                   adv=torch.empty(m, dtype=torch.float32, device="cuda"), logp=torch.empty(m, dtype=torch.float32, device="cuda"),
+                   ret=torch.empty(m, dtype=torch.float64, device="cuda"), value=torch.empty(m, dtype=torch.float32, device="cuda"))
+        state = dev(np.array([1, 0], np.int64))
+        names = ("obs", "action", "adv", "logp", "ret", "value")
+        print(line % (("bsk_pg_gather 8 of 32 x 65536",) + _timed(torch, side, lambda: P.pg_gather(state, T, N, m, m, *[hist[k] for k in names],
+                                                                                                  *[out[k] for k in names], stream=s))))
+        if new:
+            cap = 64
+            ep_R, ep_L = torch.zeros(N, dtype=torch.float64, device="cuda"), torch.zeros(N, dtype=torch.int32, device="cuda")
+            work = torch.zeros(P.pg_episodes_work_bytes(N) // 8, dtype=torch.float64, device="cuda")
+            ring = torch.zeros(cap * P.PG_LOG_COLS, dtype=torch.float64, device="cuda")
+            gen, counter = dev(np.full(cap, -1, np.int64)), dev(np.zeros(1, np.int64))
+            ep_t = _timed(torch, side, lambda: P.pg_episodes(d_rew, d_why, T, N, ep_R, ep_L, work, ring, cap, counter, hist["action"],
+                                                             hist["value"], hist["ret"], stream=s))
+            print((line + ": %.0f GB/s of its %.1f MB") % (("bsk_pg_episodes 32 x 65536",) + ep_t + (25.0 * T * N / ep_t[0] * 1e-3, 25.0 * T * N * 1e-6)))
+            gae_again = _timed(torch, side, lambda: P.gae(d_rew, d_why, hist["value"], None, T, N, hist["adv"], hist["ret"], stream=s))
+            print(line % (("bsk_gae 32 x 65536 again",) + gae_again))
+            print("device  bsk_pg_episodes / bsk_gae: %.2f (medians; against the second bsk_gae %.2f)" % (ep_t[0] / gae_t[0], ep_t[0] / gae_again[0]))
+            d_diag, d_norms = dev(rng.normal(size=(128, 8))), dev(np.stack([rng.uniform(0.1, 1.0, 16), rng.uniform(0.5, 1.0, 16)], axis=1))
+
+            def tail():
+                P.pg_log_update(d_diag, 128, ring, cap, counter, d_norms, 16, stream=s)
+                P.pg_log_advance(gen, cap, counter, s)
+            print(line % (("pg_log_update + pg_log_advance",) + _timed(torch, side, tail)))
+            P.pg_episodes(d_rew, d_why, T, N, ep_R, ep_L, work, ring, cap, counter, hist["action"], hist["value"], hist["ret"], stream=s)
+            tail()                                             # (one whole row behind the timed ones, which wrote their halves apart)
+            torch.cuda.synchronize()
+            it, table = P.pg_log_table_ref(gen.cpu().numpy().view(np.uint64), ring.cpu().numpy())
+            print("device  ring: %d of %d slots written, iterations %d .. %d; last row: %d episodes of mean length %.1f, explained variance %.4f"
+                  % (it.size, cap, it[0], it[-1], table[-1, 0], table[-1, 5] / max(table[-1, 0], 1.0), table[-1, 14]))
+    fit.close()
+    pol.close()
+
+
 if __name__ == "__main__":
     {"time": time_, "kernel": kernel, "stamps": stamps, "pg": pg, "pg-kernel": lambda: pg(trace=True),
-     "cond": cond, "shuffle": shuffle}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
+     "cond": cond, "shuffle": shuffle, "pglog": pglog}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
