@@ -104,6 +104,7 @@ EXPORTS = [
     "bsk_adv_normalize_work_bytes", "bsk_adv_normalize", "bsk_fit_set_max_grad_norm", "bsk_fit_grad_norm_device", "bsk_fit_apply_obs_norm",
     "bsk_pg_gather", "bsk_pg_shuffle_advance", "bsk_fit_accumulate_ppo", "bsk_fit_vclip_stats_device",
     "bsk_pg_episodes_work_bytes", "bsk_pg_episodes", "bsk_pg_log_update", "bsk_pg_log_advance",
+    "bsk_reward_norm_work_bytes", "bsk_reward_norm",
     "bsk_profile_begin", "bsk_profile_set_stride", "bsk_profile_end", "bsk_profile_end_samples", "bsk_calibrate_fp64", "bsk_kernel_info", "bsk_last_error", "bsk_version",
 ]
 
@@ -187,6 +188,8 @@ def _signatures():
         "bsk_pg_episodes_work_bytes": ([i], C.c_size_t),
         "bsk_pg_episodes": ([vp, vp, vp, vp, vp, i, i, i64, vp, vp, vp, vp, i, vp, vp], rc),
         "bsk_pg_log_update": ([vp, i, vp, i, vp, i, vp, vp], rc), "bsk_pg_log_advance": ([vp, i, vp, vp], rc),
+        "bsk_reward_norm_work_bytes": ([i], i64),
+        "bsk_reward_norm": ([vp, vp, i, i, i64, f64, f64, f64, i, vp, vp, vp, vp, vp], rc),
         "bsk_profile_begin": ([vp, i], rc), "bsk_profile_set_stride": ([vp, i], rc), "bsk_profile_end": ([vp, P(f64), P(i)], rc),
         "bsk_profile_end_samples": ([vp, P(f64), P(i), vp, i], rc), "bsk_calibrate_fp64": ([i, i, i, P(f64), P(f64)], rc),
         "bsk_kernel_info": ([vp, C.c_char_p, i, P(i), P(i), P(i), P(i)], rc),

@@ -3,13 +3,15 @@
 // parameters; the same with a clipped policy-gradient loss in the cross-entropy's place (bsk_fit_accumulate_pg), and the advantage
 // estimator that feeds it from rollout histories (bsk_gae); PPO2's clipped value loss on top of that (bsk_fit_accumulate_ppo) and the
 // shuffled minibatches it is fed (bsk_pg_gather, bsk_pg_shuffle_advance; kernels: bsk_shuffle.hip); the training log of the loop over
-// them (bsk_pg_episodes, bsk_pg_log_update, bsk_pg_log_advance; kernels: bsk_pglog.hip).  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_fit.hip.  The policy it reads and writes through
+// them (bsk_pg_episodes, bsk_pg_log_update, bsk_pg_log_advance; kernels: bsk_pglog.hip); the rewards of a rollout scaled by the
+// running deviation of the discounted return (bsk_reward_norm; kernels: bsk_rewnorm.hip).  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_fit.hip.  The policy it reads and writes through
 // its handle: bsk_capi_policy.hpp.
 #include <cmath>
 
 #include "bsk_capi_policy.hpp"
 #include "bsk_fit.hpp"
 #include "bsk_pglog.hpp"
+#include "bsk_rewnorm.hpp"
 #include "bsk_shuffle.hpp"
 
 using namespace bsk::capi;
@@ -284,6 +286,27 @@ int bsk_pg_log_advance(uint64_t* d_gen, int capacity, uint64_t* d_counter, void*
     if (!d_gen || !d_counter) return fail(BSK_EINVAL, "bsk_pg_log_advance: d_gen or d_counter is NULL");
     if (capacity < 1) return fail(BSK_EINVAL, "bsk_pg_log_advance: capacity must be >= 1");
     HIP_TRY(bsk::launch_pg_log_advance((unsigned long long*)d_gen, capacity, (unsigned long long*)d_counter, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream` of the current device: no copy, no synchronisation, no allocation
+}
+
+int64_t bsk_reward_norm_work_bytes(int n) { return n < 1 ? 0 : 8 * (int64_t)bsk::REWARD_NORM_WORK_WORDS * (((int64_t)n + 63) / 64); }
+
+int bsk_reward_norm(const double* d_reward_hist, const uint8_t* d_reason_hist, int n_steps, int n_envs, int64_t stride, double gamma,
+                    double eps, double clip, int update, double* d_ret_run, void* d_state, void* d_work, double* d_out, void* stream) {
+    if (!d_reward_hist || !d_reason_hist || !d_state || !d_out)
+        return fail(BSK_EINVAL, "bsk_reward_norm: the reward or the reason history, d_state or d_out is NULL");
+    if (update && (!d_ret_run || !d_work)) return fail(BSK_EINVAL, "bsk_reward_norm: d_ret_run and d_work are required with update");
+    if (n_steps < 1 || n_envs < 1 || stride < n_envs) return fail(BSK_EINVAL, "bsk_reward_norm: n_steps and n_envs must be >= 1, stride >= n_envs");
+    if ((int64_t)n_steps > ((int64_t)1 << 31) / stride) return fail(BSK_EINVAL, "bsk_reward_norm: n_steps * stride must not exceed 2^31");
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(BSK_EINVAL, "bsk_reward_norm: gamma must be in [0, 1]");
+    if (!finite_nonneg(eps)) return fail(BSK_EINVAL, "bsk_reward_norm: eps must be finite and not negative");
+    if (!(clip > 0.0)) return fail(BSK_EINVAL, "bsk_reward_norm: clip must be greater than 0 (+inf: nothing is clipped)");
+    bsk::RewardNormArgs a = {};
+    a.reward = d_reward_hist; a.reason = d_reason_hist;
+    a.n_steps = n_steps; a.n_envs = n_envs; a.stride = stride;
+    a.gamma = gamma; a.eps = eps; a.clip = clip; a.update = update != 0;
+    a.ret_run = d_ret_run; a.state = (double*)d_state; a.work = (double*)d_work; a.out = d_out;
+    HIP_TRY(bsk::launch_reward_norm(a, (hipStream_t)stream));
     return BSK_OK;        // asynchronous on `stream` of the current device: no copy, no synchronisation, no allocation
 }
 

@@ -26,7 +26,12 @@ every epoch - ``pg_gather`` (``bsk_pg_gather``) by a permutation that is never s
 And what tells whether the agent is getting better: ``pg_episodes`` / ``pg_log_update`` / ``pg_log_advance`` (``bsk_pg_episodes``,
 ...) form one row per iteration in a ring on the device - episode returns, lengths and end reasons followed across rollouts,
 PPO2's explained variance, the update's diagnostics - which ``policy_ref.pg_episodes_ref`` / ``pg_log_update_ref`` repeat bit for
-bit; ``PolicyGradient(log_capacity=...)`` keeps it and ``training_log()`` reads it."""
+bit; ``PolicyGradient(log_capacity=...)`` keeps it and ``training_log()`` reads it.
+
+And the piece of the PPO2 recipe that lives outside its update, stable-baselines' ``VecNormalize(norm_reward=True)``:
+``reward_normalize`` (``bsk_reward_norm``) divides a rollout's rewards by the running standard deviation of the discounted return -
+carried across rollouts in device memory - and clips them; ``policy_ref.reward_norm_ref`` repeats it bit for bit and
+``PolicyGradient(normalize_rewards=True)`` puts it between the rollout and ``bsk_gae``."""
 import ctypes as C
 
 import numpy as np
@@ -36,8 +41,9 @@ from ._lib import check
 from .policy_base import _DeviceObject, _host_block
 from .policy_ref import (FIT_STATS_COLUMNS, PG_STATS_COLUMNS, VCLIP_STATS_COLUMNS, adv_normalize_work_bytes, check_adv_normalize,
                          check_fit, check_fit_batch, check_gae, check_max_grad_norm, check_pg, check_pg_episodes, check_pg_gather,
-                         check_pg_log, check_pg_loop, check_pg_shuffle, PG_LOG_COLS, pg_episodes_work_bytes,
-                         pg_log_table_ref)
+                         check_pg_log, check_pg_loop, check_pg_shuffle, check_reward_norm, PG_LOG_COLS, pg_episodes_work_bytes,
+                         pg_log_table_ref, REWARD_NORM_STATE_WORDS, reward_norm_divisor, reward_norm_state_words,
+                         reward_norm_work_bytes)
 from .policy_spec import n_params
 
 
@@ -342,6 +348,39 @@ def normalize_advantages(adv, rows, n, out=None, alive=None, eps=1e-8, stride=No
     check(_lib.load().bsk_adv_normalize(ptrs[0], ptrs[1], rows, n, stride, eps, ptrs[2], ptrs[3], C.c_void_p(int(stream or 0))))
 
 
+def reward_normalize(reward_hist, reason_hist, n_steps, n_envs, state, out=None, ret_run=None, work=None, gamma=0.99, eps=1e-8,
+                     clip=10.0, update=True, stride=None, stream=0):
+    """``bsk_reward_norm``: the rewards ``reward_hist`` float64 [n_steps][stride] (``stride`` defaults to ``n_envs``) divided by the
+    running standard deviation of the discounted return and clipped to [-clip, clip], into ``out`` (None: in place) -
+    VecNormalize(norm_reward=True) for a whole rollout.  ``state``: ``REWARD_NORM_STATE_WORDS`` = 8 device words of 8 bytes, all
+    zero when fresh, carried from call to call; ``ret_run`` float64 [n_envs]: every env's running discounted return, carried
+    likewise; ``reason_hist`` uint8 [n_steps][stride]: a non-zero byte ends the env's return; ``work``:
+    ``reward_norm_work_bytes(n_envs)`` bytes.  With ``update`` the statistics take in the WHOLE rollout first (two launches) and
+    then the whole rollout is divided by the deviation that holds it (one launch); without it the statistics are frozen, only the
+    last launch is made, and ``ret_run`` and ``work`` may be None.  Each a raw device pointer or anything with
+    ``__cuda_array_interface__``.  On ``stream`` of the current device, no copy, no synchronisation, no allocation
+    (``policy_ref.reward_norm_ref``, equal bit for bit)."""
+    n_steps, n_envs, stride, gamma, eps, clip = check_reward_norm(n_steps, n_envs, n_envs if stride is None else stride, gamma, eps, clip)
+    update = bool(update)
+    N = n_steps * stride
+    words = ("<f8", "|u1", "<u8", "<i8")
+    ptrs = []
+    for x, types, what, need, must in ((reward_hist, ("<f8",), "reward history", N, True), (reason_hist, ("|u1", "|b1"), "reason history", N, True),
+                                       (ret_run, ("<f8",), "ret_run", n_envs, update), (state, words, "state", 8 * REWARD_NORM_STATE_WORDS, True),
+                                       (work, words, "work", reward_norm_work_bytes(n_envs), update),
+                                       (reward_hist if out is None else out, ("<f8",), "out", N, True)):
+        ptr, size, _ = _pointer(x, types, what)
+        if must and not ptr:
+            raise ValueError("%s: a device buffer is required" % what)
+        if size is not None and what in ("state", "work"):
+            size *= int(x.__cuda_array_interface__["typestr"][2:])
+        if size is not None and size < need:
+            raise ValueError("%s: at least %d elements, got %d" % (what, need, size))
+        ptrs.append(C.c_void_p(ptr) if ptr else None)
+    check(_lib.load().bsk_reward_norm(ptrs[0], ptrs[1], n_steps, n_envs, stride, gamma, eps, clip, int(update), ptrs[2], ptrs[3], ptrs[4],
+                                      ptrs[5], C.c_void_p(int(stream or 0))))
+
+
 def pg_gather(state, n_steps, n_envs, q0, m, obs_hist=None, action_hist=None, adv=None, logp_hist=None, ret=None, value_hist=None,
               obs_out=None, action_out=None, adv_out=None, logp_out=None, ret_out=None, value_out=None, index_out=None, stride=None,
               out_stride=None, stream=0):
@@ -488,10 +527,25 @@ class PolicyGradient(object):
     rollout in ``ep_return`` / ``ep_len`` - and ``update()`` with ``pg_log_update`` and ``pg_log_advance``; ``training_log()`` reads
     the ring.  The rows survive the replay of a captured iteration, which overwrites ``log``.  Nothing in it writes what training
     reads: theta, m, v and the histories are the same bit for bit with the log on.  0, the default, allocates and enqueues what
-    the loop always did."""
+    the loop always did.
+
+    ``normalize_rewards`` - VecNormalize(norm_reward=True), off by default: between the value launch and ``bsk_gae``, ``collect()``
+    enqueues ``reward_normalize`` (``bsk_reward_norm``) with the loop's ``gamma``, ``reward_eps`` and ``reward_clip``, out of
+    ``reward`` into a second history ``reward_norm``, which ``bsk_gae`` then reads.  The statistics - eight device words
+    ``reward_state`` - and every env's running discounted return ``ret_run`` are carried from rollout to rollout on the device, so
+    a replayed graph keeps accumulating them.  Unlike VecNormalize, which updates step by step, the statistics take in the whole
+    rollout first and the whole rollout is then divided by one number: the scale is defined in the first rollout.  ``reward``
+    keeps the raw rewards and ``pg_episodes`` still reads those, so the training log reports true returns.
+    ``update_reward_stats`` (an attribute, True) is read when ``collect()`` enqueues: set it to False to freeze the statistics, as
+    for evaluation; a captured graph bakes in the value it was captured with.  ``reward_norm_state()`` /
+    ``set_reward_norm_state()`` are for checkpoints and ``reward_scale()`` is the current divisor.  A value network trained this
+    way is in units of reward / sd: the planners' ``bootstrap=`` adds its output to RAW rewards, so a caller that bootstraps from it
+    must multiply the values by ``reward_scale()`` - nothing in the planners does.  Off, the loop allocates and enqueues what it
+    always did: the same launches, the same arguments, the same buffers."""
 
     def __init__(self, env, policy, fit, n_steps, gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, epochs=4, minibatches=4, substeps=1,
-                 normalize_advantages=False, obs_stats=None, std_min=1e-6, shuffle=False, seed=0, cliprange_vf=None, log_capacity=0):
+                 normalize_advantages=False, obs_stats=None, std_min=1e-6, shuffle=False, seed=0, cliprange_vf=None, log_capacity=0,
+                 normalize_rewards=False, reward_clip=10.0, reward_eps=1e-8):
         from . import _hip
         from ._lib import FLAG_AUTO_RESET
         (self.n_steps, self.gamma, self.lam, self.clip, self.ent_coef, self.epochs, self.minibatches,
@@ -505,6 +559,8 @@ class PolicyGradient(object):
             raise ValueError("std_min must be finite and positive")
         self.grad_norms = None
         self._clipped = False
+        self.normalize_rewards, self.update_reward_stats = bool(normalize_rewards), True
+        _, _, _, _, self.reward_eps, self.reward_clip = check_reward_norm(self.n_steps, 1, 1, self.gamma, reward_eps, reward_clip)
         prop = getattr(env, "propagator", env)
         if not (prop.cfg.flags & FLAG_AUTO_RESET):
             raise ValueError("the env must be created with FLAG_AUTO_RESET: episodes restart inside the rollout")
@@ -532,6 +588,9 @@ class PolicyGradient(object):
             check_pg_episodes(T, n, n, self.log_capacity)
             sizes.update(ep_return=8 * n, ep_len=4 * n, ep_work=pg_episodes_work_bytes(n), log_ring=8 * PG_LOG_COLS * self.log_capacity,
                          log_gen=8 * self.log_capacity, log_counter=8)
+        if self.normalize_rewards:
+            check_reward_norm(T, n, n, self.gamma, self.reward_eps, self.reward_clip)
+            sizes.update(reward_norm=8 * T * n, ret_run=8 * n, reward_state=8 * REWARD_NORM_STATE_WORDS, reward_work=reward_norm_work_bytes(n))
         if obs_stats is not None:
             if obs_stats.n_envs < n or obs_stats.device != prop.device:
                 raise ValueError("obs_stats: a statistics object of at least %d envs on device %d" % (n, prop.device))
@@ -546,6 +605,9 @@ class PolicyGradient(object):
             if self.log_capacity:          # every slot "never written" (all ones), everything else zero: fresh envs, iteration 0
                 for k, byte in (("ep_return", 0), ("ep_len", 0), ("ep_work", 0), ("log_ring", 0), ("log_counter", 0), ("log_gen", 0xFF)):
                     _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(b[k].ptr), byte, sizes[k], C.c_void_p(stream)), "hipMemsetAsync")
+            if self.normalize_rewards:     # a fresh state, fresh envs
+                for k in ("reward_norm", "ret_run", "reward_state", "reward_work"):
+                    _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(b[k].ptr), 0, sizes[k], C.c_void_p(stream)), "hipMemsetAsync")
             fit.accumulate_pg(b["obs"].ptr, b["action"].ptr, b["adv"].ptr, None, self.clip, 0.0, None, b["reason"].ptr, n=n, stride=n,
                               stream=stream)
         if self.shuffle:
@@ -607,6 +669,33 @@ class PolicyGradient(object):
             raise ValueError("counter must be an integer in 0 .. 2^64 - 1, got %r" % (counter,))
         self._log_copy(((R, "ep_return"), (L, "ep_len"), (np.array([int(counter)], np.uint64), "log_counter")), True)
 
+    def reward_norm_state(self):
+        """-> (state uint64 (8,), ret_run float64 (n,)): the words of the reward statistics as the device holds them
+        (``policy_ref.REWARD_NORM_STATE_FIELDS``) and every env's running discounted return (``normalize_rewards=True`` only).  For
+        checkpoints; synchronises."""
+        if not self.normalize_rewards:
+            raise ValueError("the loop was created without normalize_rewards")
+        words, R = np.empty(REWARD_NORM_STATE_WORDS, np.uint64), np.empty(self.n_envs, np.float64)
+        self._log_copy(((words, "reward_state"), (R, "ret_run")), False)
+        return words, R
+
+    def set_reward_norm_state(self, state, ret_run):
+        """The two back: with them - and the env's own state - the scaling goes on as if it had not been interrupted.
+        Synchronises."""
+        if not self.normalize_rewards:
+            raise ValueError("the loop was created without normalize_rewards")
+        words = reward_norm_state_words(np.ascontiguousarray(state))
+        R = np.ascontiguousarray(ret_run, np.float64).reshape(-1)
+        if R.size != self.n_envs:
+            raise ValueError("ret_run: one value per env (%d)" % self.n_envs)
+        self._log_copy(((words, "reward_state"), (R, "ret_run")), True)
+
+    def reward_scale(self):
+        """-> float: what ``collect()`` divides the rewards by as the statistics stand - the running standard deviation of the
+        discounted return, 1.0 before the first rollout.  A value of the value network times this is in the reward's own unit.
+        Synchronises."""
+        return float(reward_norm_divisor(self.reward_norm_state()[0]))
+
     def _log_copy(self, pairs, upload):
         from . import _hip
         self.prop.sync()
@@ -646,13 +735,17 @@ class PolicyGradient(object):
         ``mb_ret`` f64 and ``mb_value`` f32 [M] (written under ``cliprange_vf`` only).  With ``log_capacity``: ``ep_return`` f64[n]
         and ``ep_len`` i32[n] (every env's running episode), ``ep_work`` (the scratch of ``bsk_pg_episodes``), ``log_ring``
         f64[log_capacity][26], ``log_gen`` u64[log_capacity] (the iteration each slot holds; all ones: never written) and
-        ``log_counter`` u64 (the iteration being written)"""
+        ``log_counter`` u64 (the iteration being written).  With ``normalize_rewards``: ``reward_norm`` f64[n_steps][n] (the scaled
+        and clipped rewards, what ``bsk_gae`` reads; ``reward`` keeps the raw ones), ``ret_run`` f64[n] (every env's running
+        discounted return), ``reward_state`` u64[8] (the statistics) and ``reward_work`` (the scratch of ``bsk_reward_norm``)"""
         return {k: b.ptr for k, b in self._buf.items()}
 
     def collect(self):
         """The handle's observation into row 0, a sampled rollout of ``n_steps`` that fills the histories (observations from row 1),
         the value of the observation the handle holds afterwards, and ``bsk_gae``: all enqueued on the env's stream.  In front of
-        all of it, with ``obs_stats``: the statistics so far into the policy's input normalisation; behind all of it, with
+        all of it, with ``obs_stats``: the statistics so far into the policy's input normalisation; between the value and
+        ``bsk_gae``, with ``normalize_rewards``: ``reward`` scaled into ``reward_norm``, which ``bsk_gae`` then reads, the
+        statistics updated first unless ``update_reward_stats`` is False at this moment; behind all of it, with
         ``normalize_advantages`` and without ``shuffle``: every minibatch's rows of ``adv`` normalised into ``adv_norm`` (with
         ``shuffle`` the minibatches do not exist yet: ``update()`` normalises each behind its gather)."""
         from . import _hip
@@ -667,7 +760,12 @@ class PolicyGradient(object):
             self.policy.rollout_device(prop, T, self.substeps, "sample", b["obs"].ptr + 8 * 5 * n, b["reward"].ptr, b["reason"].ptr,
                                        b["action"].ptr, b["logp"].ptr, b["value"].ptr)
             self.policy.value_enqueue(obs, stride, n, b["last_value"].ptr, stream)
-            gae(b["reward"].ptr, b["reason"].ptr, b["value"].ptr, b["last_value"].ptr, T, n, b["adv"].ptr, b["ret"].ptr, self.gamma,
+            reward = b["reward"].ptr
+            if self.normalize_rewards:
+                reward = b["reward_norm"].ptr
+                reward_normalize(b["reward"].ptr, b["reason"].ptr, T, n, b["reward_state"].ptr, reward, b["ret_run"].ptr, b["reward_work"].ptr,
+                                 self.gamma, self.reward_eps, self.reward_clip, self.update_reward_stats, stream=stream)
+            gae(reward, b["reason"].ptr, b["value"].ptr, b["last_value"].ptr, T, n, b["adv"].ptr, b["ret"].ptr, self.gamma,
                 self.lam, stream=stream)
             if self.normalize_advantages and not self.shuffle:
                 rows = T // self.minibatches

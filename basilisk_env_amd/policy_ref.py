@@ -1821,3 +1821,127 @@ def pg_log_table_ref(gen, rows):
     valid = np.flatnonzero(gen != np.uint64(ES_LOG_EMPTY))
     valid = valid[np.argsort(gen[valid], kind="stable")]
     return gen[valid].copy(), rows[valid].copy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Rewards scaled by the running deviation of the discounted return (bsk_reward_norm; definition in include/bskgpu.h, kernels in
+# csrc/bsk_rewnorm.hip), restated
+
+REWARD_NORM_STATE_WORDS = 8                    # BSK_REWARD_NORM_STATE_WORDS
+REWARD_NORM_STATE_FIELDS = ("sum", "sum_sq", "count", "mean", "var", "sd", "calls", "zero")
+
+
+def reward_norm_work_bytes(n):
+    """``bsk_reward_norm_work_bytes``: 8 * 3 * ceil(n / 64), the device bytes ``bsk_reward_norm`` needs for its partial rows."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError("n must be an integer >= 1, got %r" % (n,))
+    return 8 * 3 * ((int(n) + 63) // 64)
+
+
+def check_reward_norm(n_steps, n_envs, stride, gamma, eps, clip):
+    """The argument rules of ``bsk_reward_norm`` that need no device -> (n_steps, n_envs, stride, gamma, eps, clip); ValueError
+    where it returns BSK_EINVAL: the size rules of ``check_pg_episodes``; gamma in [0, 1]; eps finite and not negative; clip
+    greater than 0 (+inf is allowed: nothing is then clipped) and not a NaN."""
+    n_steps, n_envs, stride, _ = check_pg_episodes(n_steps, n_envs, stride, 1)
+    gamma, eps, clip = float(gamma), float(eps), float(clip)
+    if not (0.0 <= gamma <= 1.0):
+        raise ValueError("gamma must be in [0, 1]")
+    if not np.isfinite(eps) or eps < 0.0:
+        raise ValueError("eps must be finite and not negative")
+    if not (clip > 0.0):
+        raise ValueError("clip must be greater than 0")
+    return n_steps, n_envs, stride, gamma, eps, clip
+
+
+def reward_norm_state_words(state=None):
+    """The eight state words as uint64 (8,), a copy: None -> all zero, a fresh state.  Words 0, 1, 3, 4 and 5 are the bits of float64
+    numbers (``.view(numpy.float64)``), words 2 and 6 integers (``REWARD_NORM_STATE_FIELDS``)."""
+    if state is None:
+        return np.zeros(REWARD_NORM_STATE_WORDS, np.uint64)
+    words = np.array(state, copy=True)
+    if words.dtype != np.uint64 or words.shape != (REWARD_NORM_STATE_WORDS,):
+        raise ValueError("state: uint64 (%d,), the words as the device holds them" % REWARD_NORM_STATE_WORDS)
+    return words
+
+
+def reward_norm_divisor(state):
+    """What the apply divides by: sd when something has been counted, 1.0 on a fresh state."""
+    words = reward_norm_state_words(state)
+    return np.float64(words.view(np.float64)[5]) if int(words[2]) != 0 else np.float64(1.0)
+
+
+def reward_norm_walk_ref(reward, reason, gamma, ret_run=None):
+    """The per-column walk of ``bsk_reward_norm`` (csrc/bsk_rewnorm.hpp: reward_norm_walk), every column at once -> (a1 float64 (N,),
+    a2 float64 (N,), k int64 (N,), ret_run float64 (N,)): what each lane holds in front of the trees, and the running return it
+    writes back.  ``reward`` float64 and ``reason`` uint8, each (T, N); ``ret_run``: the carried returns or None (zeros: fresh
+    envs).  Rows ascending, every operation rounded on its own: R = gamma * R + reward; a1 = a1 + R; a2 = a2 + R * R; k += 1; then
+    R = +0.0 where the reason byte is not zero."""
+    reward = np.asarray(reward, np.float64)
+    if reward.ndim != 2 or reward.shape[0] < 1 or reward.shape[1] < 1:
+        raise ValueError("reward: (n_steps, n_envs)")
+    T, N = reward.shape
+    _, _, _, gamma, _, _ = check_reward_norm(T, N, N, gamma, 0.0, 1.0)
+    reason = np.asarray(reason).reshape(T, N).astype(np.uint8)
+    R = np.zeros(N, np.float64) if ret_run is None else np.array(ret_run, dtype=np.float64).reshape(-1)
+    if R.shape != (N,):
+        raise ValueError("ret_run: float64 (%d,)" % N)
+    g = np.float64(gamma)
+    a1, a2, k = np.zeros(N, np.float64), np.zeros(N, np.float64), np.zeros(N, np.int64)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        for t in range(T):
+            R = g * R + reward[t]
+            a1 = a1 + R
+            a2 = a2 + R * R
+            k += 1
+            R = np.where(reason[t] != 0, np.float64(0.0), R)
+    return a1, a2, k, R
+
+
+def reward_norm_ref(reward, reason, gamma, eps, clip, update, state=None, ret_run=None, with_work=False):
+    """``bsk_reward_norm`` restated -> (out float64 (T, N), state uint64 (8,), ret_run float64 (N,)) and, ``with_work``, the partial
+    rows uint64 (W, 3) as the device leaves them (None without ``update``).  ``state``: the eight words carried in
+    (``reward_norm_state_words``; None: fresh) and ``ret_run`` the running returns (None: zeros); neither is changed.  With
+    ``update``: ``reward_norm_walk_ref`` per column; per wave of 64 columns (lanes at and above N bring +0.0 and 0) the two sums
+    through the fitness tree; the waves joined by ``obs_stats_totals_ref``'s rule; sum, sum_sq and count added to, calls += 1;
+    ``obs_moments_ref``'s mean and var; sd = sqrt(var + eps).  Always: d = sd where count != 0 and 1.0 otherwise - behind the
+    update, so the WHOLE rollout is divided by the deviation that already holds it -, y = reward / d, clipped to [-clip, clip], a NaN
+    passing through.  Bit for bit the device's."""
+    reward = np.asarray(reward, np.float64)
+    if reward.ndim != 2 or reward.shape[0] < 1 or reward.shape[1] < 1:
+        raise ValueError("reward: (n_steps, n_envs)")
+    T, N = reward.shape
+    _, _, _, gamma, eps, clip = check_reward_norm(T, N, N, gamma, eps, clip)
+    words = reward_norm_state_words(state)
+    R = np.zeros(N, np.float64) if ret_run is None else np.array(ret_run, dtype=np.float64).reshape(-1)
+    if R.shape != (N,):
+        raise ValueError("ret_run: float64 (%d,)" % N)
+    work = None
+    with np.errstate(invalid="ignore", over="ignore", under="ignore", divide="ignore"):
+        if update:
+            a1, a2, k, R = reward_norm_walk_ref(reward, reason, gamma, R)
+            W = (N + 63) // 64
+            lanes = np.zeros((2, W * 64), np.float64)
+            lanes[0, :N], lanes[1, :N] = a1, a2
+            tree = lanes.reshape(2, W, 64)
+            for stride in _TREE:
+                tree[:, :, :stride] = tree[:, :, :stride] + tree[:, :, stride:2 * stride]
+            counts = np.zeros(W * 64, np.int64)
+            counts[:N] = k
+            counts = counts.reshape(W, 64).sum(axis=1)
+            work = np.empty((W, 3), np.uint64)
+            work[:, 0], work[:, 1] = tree[0, :, 0].view(np.uint64), tree[1, :, 0].view(np.uint64)
+            work[:, 2] = counts.astype(np.uint64)
+            part = np.zeros((W, 10), np.float64)
+            part[:, 0], part[:, 5] = tree[0, :, 0], tree[1, :, 0]
+            tot, _ = obs_stats_totals_ref((part, np.zeros(W, np.uint64)))
+            f = words.view(np.float64)
+            total = np.array([f[0] + tot[0], 0, 0, 0, 0, f[1] + tot[5], 0, 0, 0, 0], np.float64)
+            count = (int(words[2]) + int(counts.sum())) % 2 ** 64
+            mean, var = (x[0] for x in obs_moments_ref(total, count))
+            f[0], f[1], f[3], f[4], f[5] = total[0], total[5], mean, var, np.sqrt(var + np.float64(eps))
+            words[2], words[6], words[7] = count, (int(words[6]) + 1) % 2 ** 64, 0
+        d = reward_norm_divisor(words)
+        y = reward / d
+        c = np.float64(clip)
+        out = np.where(y > c, c, np.where(y < -c, -c, y))
+    return (out, words, R, work) if with_work else (out, words, R)

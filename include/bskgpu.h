@@ -1342,6 +1342,52 @@ int bsk_pg_log_update(const double* d_diag, int n_rows, const double* d_norms, i
                       const uint64_t* d_counter, void* stream);
 int bsk_pg_log_advance(uint64_t* d_gen, int capacity, uint64_t* d_counter, void* stream);
 
+/* Reward scaling for the policy-gradient loop: the rewards of a rollout divided by the running standard deviation of the discounted
+ * return and clipped - what stable-baselines' VecNormalize(norm_reward=True) does to every PPO2 run -, so that the value network
+ * regresses targets of order one whatever the reward's unit.  A free function of the current device; it does not allocate, copy or
+ * synchronise and is capturable from the first call.  All f64, every operation rounded on its own (no FMA), no atomics, a fixed
+ * order: basilisk_env_amd/policy_ref.py repeats it bit for bit (reward_norm_ref).
+ *
+ * d_state: BSK_REWARD_NORM_STATE_WORDS = 8 words of 8 bytes in DEVICE memory, the caller's; all zero means fresh:
+ *   [0] sum of the running returns seen      [1] sum of their squares      [2] their number (uint64)
+ *   [3] mean      [4] var      [5] sd      [6] the number of updating calls (uint64)      [7] 0
+ * d_ret_run f64[n_envs], the caller's: the running discounted return of every env, carried from call to call (zeros: fresh envs).
+ * The histories are [n_steps][stride] in bsk_policy_rollout's layout; W = ceil(n_envs / 64).
+ *
+ * With update != 0, TWO launches in front of the apply:
+ *  walk - wave w is the envs 64 w .. 64 w + 63, lane l the env j = 64 w + l; from R = d_ret_run[j], a1 = a2 = +0.0 and k = 0 the lane
+ *   walks t = 0 .. n_steps - 1 ASCENDING:
+ *     R = gamma * R + reward[t][j]  (the product rounded, then the sum);  a1 = a1 + R;  a2 = a2 + R * R;  k = k + 1;
+ *     reason[t][j] != 0:  R = +0.0  - AFTER it was counted, VecNormalize's order
+ *   and d_ret_run[j] = R.  a1 and a2 each through the fitness tree of the observation statistics above (stride 32 ... 1; a lane at
+ *   or above n_envs brings +0.0 and 0), k through its integer twin;  work[w] = (a1[0], a2[0], k[0]) - WRITTEN, not added to: the
+ *   partial rows hold no state from call to call.
+ *  join - bsk_adv_normalize's rule per column of work: s[l] = work[l], or +0.0 when l >= W;  s[l] = s[l] + work[l + 64 m] for
+ *   m = 1, 2, ... ascending while l + 64 m < W;  the tree;  S1, S2 = s[0];  K = the integer sum of the counts.  Then one thread:
+ *     sum = sum + S1;  sum_sq = sum_sq + S2;  count += K;  calls += 1;
+ *     mean = sum / (double)count;  var = max(sum_sq / (double)count - mean * mean, 0)  (as for an observation row);
+ *     sd = sqrt(var + eps);  word [7] = 0.
+ * Always, ONE launch:
+ *  apply - d = (count != 0) ? sd : 1.0, read from the state as it is behind the join;  for every t and every j < n_envs
+ *     y = reward[t][j] / d;  out[t][j] = y > clip ? clip : (y < -clip ? -clip : y)      - a NaN passes through.
+ *   Elementwise, each thread its own element: d_out may be d_reward_hist.
+ * So the statistics take in the WHOLE rollout first and then the whole rollout is scaled by one number.  This deviates from
+ * VecNormalize on purpose: it updates its statistics step by step, so the steps of one rollout are divided by n_steps different
+ * numbers and the very first by the deviation of a single step's returns.  Here the scale is defined in the first rollout, and a
+ * rollout costs three launches instead of n_steps.  As there, the mean is not subtracted, and the returns are discounted forward in
+ * time from the past, which is not the return the value network regresses.
+ * With update == 0 only the apply is launched: the statistics are frozen and d_ret_run and d_work are neither read nor written (they
+ * may be NULL), as for evaluation.  On a fresh state that is the identity under the clip.
+ * d_work: bsk_reward_norm_work_bytes(n_envs) = 8 * 3 * W bytes, 8-byte aligned (0 for n < 1).  Columns at or above n_envs of a
+ * strided history are neither read nor written.  The walk is one env per lane: latency-bound at 65 536 envs, as bsk_gae is.
+ * BSK_EINVAL before any launch: a NULL history, d_state or d_out; update != 0 with a NULL d_ret_run or d_work; n_steps < 1,
+ * n_envs < 1, stride < n_envs; n_steps * stride > 2^31; gamma outside [0, 1] or not finite; eps negative or not finite; clip not
+ * greater than 0, or NaN (+inf is allowed: nothing is then clipped). */
+#define BSK_REWARD_NORM_STATE_WORDS 8
+int64_t bsk_reward_norm_work_bytes(int n);
+int bsk_reward_norm(const double* d_reward_hist, const uint8_t* d_reason_hist, int n_steps, int n_envs, int64_t stride, double gamma,
+                    double eps, double clip, int update, double* d_ret_run, void* d_state, void* d_work, double* d_out, void* stream);
+
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the
  * three-wave form's barrier-free exchange gives up after 2^20 polls instead of hanging, and says so here. */

@@ -42,6 +42,12 @@ same card.
       (with BSKGPU_LIB naming a library built from the parent commit this is all that runs - the parent's bands, re-measured in the
       same session), then `bsk_pg_episodes` at 32 x 65 536 with all histories against the 25 bytes per sample it reads, beside
       `bsk_gae` at the same shape, and `bsk_pg_log_update` + `bsk_pg_log_advance` over 128 diagnostics rows and 16 norms.
+  python tools/fit_measure.py rewnorm
+      the reward scaling of the gradient loop ("Scaling the rewards"), timed as under `time` on the `pg`
+      set-up: `accumulate_pg` + `step`, `bsk_gae` and `bsk_pg_episodes` at 32 x 65 536 (with BSKGPU_LIB naming a library built from
+      the parent commit this is all that runs - the parent's bands, re-measured in the same session), then `bsk_reward_norm` at
+      that shape with `update = 1` (three launches: 9 bytes per sample read by the walk, 16 moved by the apply) and with
+      `update = 0` (the apply alone, against its 16 bytes per sample), out of place and in place.
 """
 import os
 import sys
@@ -386,6 +392,71 @@ def pglog():
     pol.close()
 
 
+def rewnorm():
+    import torch
+    from _policy_bounds import observation_like, seeded_policy
+    from basilisk_env_amd import _lib
+    from basilisk_env_amd import policy as P
+    spec, params = seeded_policy(HIDDEN, "relu", (64,), seed=1)
+    obs = observation_like(N, 3)
+    rng = np.random.default_rng(5)
+    labels = np.where(obs[3] < 0.4, 1, np.where(obs[2] > 0.7, 2, 0)).astype(np.int32)
+    pol = P.DevicePolicy(spec, params)
+    fit = P.PolicyFit(pol, lr=1e-3)
+    side = torch.cuda.Stream()
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()      # noqa: E731
+    d_obs, d_lab, d_tgt = dev(obs), dev(labels), dev(rng.normal(size=N))
+    d_adv, d_old = dev(rng.normal(size=N).astype(np.float32)), dev((-1.1 + rng.normal(0.0, 0.3, N)).astype(np.float32))
+    s = side.cuda_stream
+    new = hasattr(_lib.load(), "bsk_reward_norm")
+    line = "device  %-34s %8.1f us  (p10 %.1f, p90 %.1f)"
+    with torch.cuda.stream(side):
+        def step():
+            fit.accumulate_pg(d_obs, d_lab, d_adv, d_old, 0.2, 0.01, d_tgt, stream=s)
+            fit.step(s)
+        print(line % (("accumulate_pg + step",) + _timed(torch, side, step)))
+        T = 32
+        d_act, d_val = dev(rng.integers(0, 3, (T, N)).astype(np.int32)), dev(rng.normal(size=(T, N)).astype(np.float32))
+        d_gae, d_ret = torch.empty((T, N), dtype=torch.float32, device="cuda"), torch.empty((T, N), dtype=torch.float64, device="cuda")
+        d_rew = dev(rng.normal(size=(T, N)))
+        d_why = dev(((rng.uniform(size=(T, N)) < 0.02) * rng.choice([1, 2, 4, 8], (T, N))).astype(np.uint8))
+        gae_t = _timed(torch, side, lambda: P.gae(d_rew, d_why, d_val, None, T, N, d_gae, d_ret, stream=s))
+        print((line + ": %.0f GB/s of its %.1f MB") % (("bsk_gae 32 x 65536",) + gae_t + (25.0 * T * N / gae_t[0] * 1e-3, 25.0 * T * N * 1e-6)))
+        cap = 64
+        ep_R, ep_L = torch.zeros(N, dtype=torch.float64, device="cuda"), torch.zeros(N, dtype=torch.int32, device="cuda")
+        ep_work = torch.zeros(P.pg_episodes_work_bytes(N) // 8, dtype=torch.float64, device="cuda")
+        ring, counter = torch.zeros(cap * P.PG_LOG_COLS, dtype=torch.float64, device="cuda"), dev(np.zeros(1, np.int64))
+        ep_t = _timed(torch, side, lambda: P.pg_episodes(d_rew, d_why, T, N, ep_R, ep_L, ep_work, ring, cap, counter, d_act, d_val, d_ret,
+                                                         stream=s))
+        print((line + ": %.0f GB/s of its %.1f MB") % (("bsk_pg_episodes 32 x 65536",) + ep_t + (25.0 * T * N / ep_t[0] * 1e-3, 25.0 * T * N * 1e-6)))
+        if new:
+            state = torch.zeros(P.REWARD_NORM_STATE_WORDS, dtype=torch.int64, device="cuda")
+            ret_run = torch.zeros(N, dtype=torch.float64, device="cuda")
+            work = torch.zeros(P.reward_norm_work_bytes(N) // 8, dtype=torch.float64, device="cuda")
+            d_out = torch.empty((T, N), dtype=torch.float64, device="cuda")
+            d_inplace = d_rew.clone()
+            print("device  buffers: rewards %.1f MB, reasons %.1f MB, output %.1f MB - all inside the 256 MB last-level cache"
+                  % (8.0 * T * N * 1e-6, 1.0 * T * N * 1e-6, 8.0 * T * N * 1e-6))
+            up = _timed(torch, side, lambda: P.reward_normalize(d_rew, d_why, T, N, state, d_out, ret_run, work, 0.99, 1e-8, 10.0, True, stream=s))
+            print((line + ": the walk reads %.1f MB, the apply moves %.1f MB") % (("bsk_reward_norm update = 1",) + up + (9.0 * T * N * 1e-6, 16.0 * T * N * 1e-6)))
+            frozen = {}
+            for what, out in (("bsk_reward_norm update = 0", d_out), ("the same in place", d_inplace)):
+                ap = frozen[what] = _timed(torch, side, lambda: P.reward_normalize(d_rew if out is d_out else d_inplace, d_why, T, N, state, out if out is d_out else None,
+                                                                    None, None, 0.99, 1e-8, 10.0, False, stream=s))
+                print((line + ": %.0f GB/s of its %.1f MB, %.1f %% of 8 TB/s") % ((what,) + ap + (16.0 * T * N / ap[0] * 1e-3, 16.0 * T * N * 1e-6,
+                                                                                      100.0 * 16.0 * T * N / ap[0] * 1e-3 / 8000.0)))
+            ep_again = _timed(torch, side, lambda: P.pg_episodes(d_rew, d_why, T, N, ep_R, ep_L, ep_work, ring, cap, counter, d_act, d_val, d_ret,
+                                                                 stream=s))
+            print(line % (("bsk_pg_episodes 32 x 65536 again",) + ep_again))
+            print("device  bsk_reward_norm (update = 1) / bsk_pg_episodes: %.2f; walk + join = update 1 - update 0: %.1f us"
+                  % (up[0] / ep_again[0], up[0] - frozen["bsk_reward_norm update = 0"][0]))
+            torch.cuda.synchronize()
+            words = state.cpu().numpy().view(np.uint64)
+            print("device  state: %d updating calls, %d returns, sd %.4f" % (words[6], words[2], words.view(np.float64)[5]))
+    fit.close()
+    pol.close()
+
+
 if __name__ == "__main__":
     {"time": time_, "kernel": kernel, "stamps": stamps, "pg": pg, "pg-kernel": lambda: pg(trace=True),
-     "cond": cond, "shuffle": shuffle, "pglog": pglog}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
+     "cond": cond, "shuffle": shuffle, "pglog": pglog, "rewnorm": rewnorm}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
