@@ -1151,8 +1151,10 @@ int bsk_gae(const double* d_reward_hist, const uint8_t* d_reason_hist, const flo
  *   otherwise:           c = A * r;  gp_i = c * (p_i - (i == a ? 1.0f : 0.0f))
  *   ec == 0:  g_i = gp_i
  *   else:     H = -((p_0 * lp_0 + p_1 * lp_1) + p_2 * lp_2);  q_i = p_i * (lp_i + H);  g_i = fmaf(ec, q_i, gp_i)
- * A sample that does not contribute gets +0.0f for each g_i and is not counted.  Non-finite advantages and old log-probabilities
- * are outside the numerical contract, as non-finite observations are.  It follows that (1) with d_logp_old == NULL, A = 1 and
+ * A sample that does not contribute gets +0.0f for each g_i and is not counted, and its d_adv, d_logp_old and d_value_target words
+ * (and its d_value_old word in bsk_fit_accumulate_ppo) are NOT READ: they may hold anything, NaN included - an env past its first
+ * episode keeps stale history words.  Its observation is read, and must be finite.  Non-finite advantages and old log-probabilities
+ * of a contributing sample are outside the numerical contract, as non-finite observations are.  It follows that (1) with d_logp_old == NULL, A = 1 and
  * ent_coef = 0 the deltas, A_p and the count are bsk_fit_accumulate's for label = action, bit for bit; (2) lp_a is formed as
  * policy_kernel forms logp, so with unchanged parameters and d_logp_old from bsk_policy_act or the rollout d is +0.0f, r is 1.0f
  * and nothing is clipped; (3) a sample with A == 0 and ec == 0 contributes +0.0f deltas and is still counted.

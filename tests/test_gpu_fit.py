@@ -117,10 +117,16 @@ def _check_stats(row, spec, params, obs, labels, alive, targets):
 
 
 def _reference_moment(spec, params, calls, value_coef):
-    """A / count of the given accumulate calls [(obs, labels, alive, targets, device dlogits)], by the numpy restatements"""
+    """A / count of the given accumulate calls [(obs, labels, alive, targets, device dlogits)], by the numpy restatements.  A sixth
+    item is the d_dvalue the launch wrote (bsk_fit_accumulate_ppo): the device's own value deltas, taken as exact as dlogits is, in
+    the place of the squared error's."""
     A, count = np.zeros(params.size), 0
-    for obs, labels, alive, targets, dl in calls:
-        dv = None if targets is None else P.fit_dlogits32_ref(spec, params, obs, labels, alive, targets, value_coef)[1]
+    for call in calls:
+        obs, labels, alive, targets, dl = call[:5]
+        if len(call) > 5:
+            dv = call[5]
+        else:
+            dv = None if targets is None else P.fit_dlogits32_ref(spec, params, obs, labels, alive, targets, value_coef)[1]
         G = P.fit_backward_ref(spec, params, obs, dl, dv)
         on = (labels >= 0) & (labels <= 2) & (alive != 0)
         A, count = P.fit_accumulate_ref(A, count, G, on.sum())

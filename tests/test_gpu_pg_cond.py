@@ -7,8 +7,8 @@ Both reductions are f64 additions, products, divisions and square roots in a fix
 ``fit_grad_norm_ref`` / ``fit_step_ref`` in every bit, for relu networks from the device's own output deltas as in
 tests/test_gpu_fit.py.  Shapes are the smallest at which each loop goes past its first trip: n = 65 is two waves of the partial
 sums, 4 097 sixty-five - the join's lanes in their second lap; rows = 7 leaves a tail behind no full batch of the row walk and
-rows = 9 (the in-place case of n = 300) one behind a full batch; 18 moved parameters are less than one lap of the norm's 1 024
-threads, 17 790 more than seventeen.
+rows = 9 (the in-place case of n = 300) one behind a full batch, rows = 1 030 a tail behind 128 of them and the apply launch's
+row stride in its second trip; 18 moved parameters are less than one lap of the norm's 1 024 threads, 17 790 more than seventeen.
 """
 import ctypes as C
 
@@ -95,6 +95,35 @@ def test_adv_normalize_walks_past_a_full_batch_of_rows_in_place_on_a_raw_pointer
     torch.cuda.synchronize()
     want, mom = P.adv_normalize_ref(adv, alive)
     assert _same(d_adv.cpu().numpy(), want) and _same(work.cpu().numpy()[:4], mom) and mom[3] == (alive != 0).sum()
+
+
+@pytest.mark.parametrize("n", [3, 70])
+def test_adv_normalize_past_the_apply_launchs_grid_of_rows(n):
+    """rows = 1 030: adv_apply_kernel's grid has ADV_APPLY_ROWS = 1 024 rows and a block strides over the rest - one trip for every
+    row of the grid and a second for the first six -, and adv_partial_kernel walks 128 full batches of ADV_BATCH = 8 and a tail of
+    six.  Masked alive bytes, stride = n + 3, in place and out of place; the padding is nobody's."""
+    import torch
+    rows, stride, eps = 1030, n + 3, 1e-8
+    adv, alive = adv_case(rows, n, 1030 + n, masked=True)
+    want, mom = P.adv_normalize_ref(adv, alive, eps)
+    assert mom[3] == (alive != 0).sum() and 0 < mom[3] < rows * n and (alive[1024:] != 0).any() and (alive[1024:] == 0).any()
+    padded, full = np.full((rows, stride), 9.0, np.float32), np.ones((rows, stride), np.uint8)
+    padded[:, :n], full[:, :n] = adv, alive
+    d_alive = _dev(full)
+    for in_place in (False, True):
+        d_adv, work = _dev(padded), _work(n)
+        d_out = d_adv if in_place else torch.full((rows, stride), -7.0, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        P.normalize_advantages(d_adv, rows, n, None if in_place else d_out, d_alive, eps, stride, work)
+        torch.cuda.synchronize()
+        got, w = d_out.cpu().numpy(), work.cpu().numpy()
+        assert _same(w[:4], mom) and (w[-GUARD:] == -3.0).all(), (in_place, w[:4], mom)
+        assert _same(got[:, :n], want), (in_place, np.argwhere(got[:, :n] != want)[:4])
+        assert (got[:, n:] == (9.0 if in_place else -7.0)).all(), in_place          # the padding is nobody's
+        if not in_place:
+            assert _same(d_adv.cpu().numpy(), padded)                               # the raw estimate stays
+    # (a row the stride's second trip reaches holds what the restatement gives, not what it held)
+    assert not _same(want[1024:], adv[1024:])
 
 
 def test_adv_normalize_refuses_bad_arguments_before_any_launch():

@@ -16,6 +16,7 @@ import pytest
 
 from _device_bits import download as _download, same as _same
 from _policy_bounds import observation_like, seeded_policy
+from _ppo_cases import CV, KINDS, place as _place
 from basilisk_env_amd import _lib
 from basilisk_env_amd import policy as P
 from basilisk_env_amd._lib import FLAG_AUTO_RESET, GRAV_PM_J2
@@ -187,21 +188,6 @@ def test_the_gather_refuses_bad_arguments_before_any_launch():
 
 
 # ------------------------------------------------------------------------------------------------------------------ the value loss
-CV = 0.25
-KINDS = ("inside", "above_clipped", "above_unclipped", "below_clipped", "below_unclipped")
-
-
-def _place(v, kinds):
-    """old values and targets around the device's own v that put sample j into branch kinds[j]: dv = +-0.1 inside the range of
-    0.25 and +-1.0 outside it; squared errors 1 against 3.06 where the clipped branch holds the max, 4 against 1.56 where not"""
-    vo, R = np.empty(v.size, np.float32), np.empty(v.size, np.float64)
-    for j, kind in enumerate(kinds):
-        side = -1.0 if kind.startswith("below") else 1.0
-        vo[j] = v[j] - np.float32(side * (0.1 if kind == "inside" else 1.0))
-        R[j] = float(v[j]) + side * (-2.0 if kind.endswith("unclipped") else 1.0)
-    return vo, R
-
-
 def _ppo_case(n, seed):
     spec, params = seeded_policy((16,), "relu", (16,), seed=seed)
     obs = observation_like(n, seed)

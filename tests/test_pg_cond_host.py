@@ -14,7 +14,7 @@ from basilisk_env_amd import policy as P
 # ------------------------------------------------------------------------------------------------------------------ advantages
 @pytest.mark.parametrize("scale", [1e-3, 1.0, 1e4])
 @pytest.mark.parametrize("masked", [False, True])
-@pytest.mark.parametrize("rows,n", [(1, 1), (1, 63), (2, 64), (7, 65), (2, 300), (3, 4097)])
+@pytest.mark.parametrize("rows,n", [(1, 1), (1, 63), (2, 64), (7, 65), (2, 300), (3, 4097), (1030, 3), (1030, 70)])
 def test_adv_normalize_ref_is_numpys_mean_and_std_within_the_derived_bound(rows, n, masked, scale):
     eps = 1e-8
     adv, alive = adv_case(rows, n, rows * 10 + n, scale, masked and rows * n > 8)
