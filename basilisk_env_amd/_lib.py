@@ -79,6 +79,12 @@ class BskPolicySpec(C.Structure):
     ]
 
 
+class BskFitSchedule(C.Structure):
+    """Mirror of ``struct bsk_fit_schedule`` (include/bskgpu.h): every pair is {a, b}."""
+    _fields_ = [("lr", C.c_double * 2), ("clip", C.c_double * 2), ("clip_vf", C.c_double * 2), ("ent_coef", C.c_double * 2),
+                ("total", C.c_uint64), ("kl_stop", C.c_double)]
+
+
 EXPORTS = [
     "bsk_default_config", "bsk_create", "bsk_destroy", "bsk_set_gravity_sh", "bsk_reset", "bsk_step",
     "bsk_step_device", "bsk_step_device_i64", "bsk_step_n", "bsk_get_episode_device", "bsk_get_batch_stats_device", "bsk_set_step_stats", "bsk_set_halves_form", "bsk_reset_from_pool_device", "bsk_debug_counters", "bsk_debug_words", "bsk_get_obs", "bsk_get_obs_rowmajor", "bsk_get_obs_device", "bsk_get_obs_state", "bsk_get_stream", "bsk_get_terminal_obs_device", "bsk_get_state_device", "bsk_get_batch_stats", "bsk_n_fields",
@@ -105,6 +111,8 @@ EXPORTS = [
     "bsk_pg_gather", "bsk_pg_shuffle_advance", "bsk_fit_accumulate_ppo", "bsk_fit_vclip_stats_device",
     "bsk_pg_episodes_work_bytes", "bsk_pg_episodes", "bsk_pg_log_update", "bsk_pg_log_advance",
     "bsk_reward_norm_work_bytes", "bsk_reward_norm",
+    "bsk_fit_set_schedule", "bsk_fit_schedule_begin", "bsk_fit_kl_gate", "bsk_fit_schedule_end", "bsk_fit_schedule_device",
+    "bsk_fit_get_schedule_state", "bsk_fit_set_schedule_state",
     "bsk_profile_begin", "bsk_profile_set_stride", "bsk_profile_end", "bsk_profile_end_samples", "bsk_calibrate_fp64", "bsk_kernel_info", "bsk_last_error", "bsk_version",
 ]
 
@@ -190,6 +198,10 @@ def _signatures():
         "bsk_pg_log_update": ([vp, i, vp, i, vp, i, vp, vp], rc), "bsk_pg_log_advance": ([vp, i, vp, vp], rc),
         "bsk_reward_norm_work_bytes": ([i], i64),
         "bsk_reward_norm": ([vp, vp, i, i, i64, f64, f64, f64, i, vp, vp, vp, vp, vp], rc),
+        "bsk_fit_set_schedule": ([vp, P(BskFitSchedule)], rc), "bsk_fit_schedule_begin": ([vp, vp], rc),
+        "bsk_fit_kl_gate": ([vp, vp, i, vp], rc), "bsk_fit_schedule_end": ([vp, vp, i, vp], rc),
+        "bsk_fit_schedule_device": ([vp, P(vp)], rc), "bsk_fit_get_schedule_state": ([vp, vp], rc),
+        "bsk_fit_set_schedule_state": ([vp, u64], rc),
         "bsk_profile_begin": ([vp, i], rc), "bsk_profile_set_stride": ([vp, i], rc), "bsk_profile_end": ([vp, P(f64), P(i)], rc),
         "bsk_profile_end_samples": ([vp, P(f64), P(i), vp, i], rc), "bsk_calibrate_fp64": ([i, i, i, P(f64), P(f64)], rc),
         "bsk_kernel_info": ([vp, C.c_char_p, i, P(i), P(i), P(i), P(i)], rc),

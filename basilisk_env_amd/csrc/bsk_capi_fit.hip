@@ -4,20 +4,24 @@
 // estimator that feeds it from rollout histories (bsk_gae); PPO2's clipped value loss on top of that (bsk_fit_accumulate_ppo) and the
 // shuffled minibatches it is fed (bsk_pg_gather, bsk_pg_shuffle_advance; kernels: bsk_shuffle.hip); the training log of the loop over
 // them (bsk_pg_episodes, bsk_pg_log_update, bsk_pg_log_advance; kernels: bsk_pglog.hip); the rewards of a rollout scaled by the
-// running deviation of the discounted return (bsk_reward_norm; kernels: bsk_rewnorm.hip).  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_fit.hip.  The policy it reads and writes through
+// running deviation of the discounted return (bsk_reward_norm; kernels: bsk_rewnorm.hip); schedules of lr, clip, clip_vf and ent_coef
+// and a KL stop per update, carried in eight device words of the fit (bsk_fit_set_schedule, bsk_fit_schedule_begin, bsk_fit_kl_gate,
+// bsk_fit_schedule_end; kernels: bsk_pgsched.hip, and the scheduled instantiations in bsk_fit.hip).  Host side only, as bsk_capi.hip; kernels and launch wrappers: bsk_fit.hip.  The policy it reads and writes through
 // its handle: bsk_capi_policy.hpp.
 #include <cmath>
+#include <cstring>
 
 #include "bsk_capi_policy.hpp"
 #include "bsk_fit.hpp"
 #include "bsk_pglog.hpp"
+#include "bsk_pgsched.hpp"
 #include "bsk_rewnorm.hpp"
 #include "bsk_shuffle.hpp"
 
 using namespace bsk::capi;
 
 // bsk_fit_*: ONE allocation of 8-byte words [theta np | m np | v np | beta_pow 2 | A np | row 4 | count | steps | pg_row 4 | gnorm_row 2 |
-// vclip_row 2] and, from
+// vclip_row 2 | sched 8] and, from
 // the first accumulate on, the scratch of the block gradients: [G n_blocks * np floats | diag n_blocks * 10 doubles | lp 3 * 64
 // n_blocks floats] (a supervised launch uses the first 4 n_blocks of diag and no lp, a policy-gradient launch without the value
 // clip the first 8 n_blocks)
@@ -31,6 +35,9 @@ struct bsk_fit {
     void* d_scratch = nullptr;
     int blocks_cap = 0;
     bool value_seen = false;               // some accumulate since the last step carried value targets: the step moves the value network
+    bool scheduled = false;                // bsk_fit_set_schedule: the policy-gradient accumulates and the step read the schedule words
+    bsk::PgSchedPairs pairs = {};          // ... formed from these by bsk_fit_schedule_begin
+    double kl_stop = 0.0;                  // ... and bsk_fit_kl_gate closes against this (0: no gate)
 
     size_t np() const { return (size_t)policy->lay.n_params; }
     double* theta() const { return d_state; }
@@ -44,7 +51,9 @@ struct bsk_fit {
     double* pg_row() const { return d_state + 4 * np() + 8; }
     double* gnorm_row() const { return d_state + 4 * np() + 12; }          // {norm, scale} of the last clipped step
     double* vclip_row() const { return d_state + 4 * np() + 14; }          // {value-clipped samples, sum of the unclipped d d / 2}
-    size_t words() const { return 4 * np() + 16; }
+    // the schedule block (bsk_pgsched.hpp): {lr, clip, clip_vf, ent_coef} now, iteration, gate, steps skipped, the KL that closed it
+    unsigned long long* sched() const { return (unsigned long long*)(d_state + 4 * np() + 16); }
+    size_t words() const { return 4 * np() + 16 + bsk::PG_SCHED_WORDS; }
     // where the action network's parameters end in the C-ABI block: all a fit without value targets folds and moves
     int action_end() const {
         const bsk::PolicyLayout& lay = policy->lay;
@@ -120,13 +129,16 @@ int accumulate(bsk_fit* f, const double* d_obs, int64_t obs_stride, int n, const
         la.width = lay.width;
         HIP_TRY(bsk::launch_policy_logp(la, s));
         a.lp = lp;
+        const double* sched = f->scheduled ? (const double*)f->sched() : nullptr;      // (then a.clip_hi .. and vc.clip_vf are not read)
         if (pg->value_old || pg->dvalue) {
             const bsk::FitVclip vc = {pg->value_old, pg->clip_vf, pg->dvalue};
-            HIP_TRY(bsk::launch_fit_blocks_ppo(a, vc, s));
+            if (sched) HIP_TRY(bsk::launch_fit_blocks_ppo_sched(a, vc, sched, s));
+            else HIP_TRY(bsk::launch_fit_blocks_ppo(a, vc, s));
             HIP_TRY(bsk::launch_fit_fold_ppo(a.G, a.diag, n_blocks, lay.n_params, n_fold, f->A(), f->row(), f->pg_row(),
                                              pg->value_old ? f->vclip_row() : nullptr, f->count(), s));
         } else {
-            HIP_TRY(bsk::launch_fit_blocks_pg(a, s));
+            if (sched) HIP_TRY(bsk::launch_fit_blocks_pg_sched(a, sched, s));
+            else HIP_TRY(bsk::launch_fit_blocks_pg(a, s));
             HIP_TRY(bsk::launch_fit_fold_pg(a.G, a.diag, n_blocks, lay.n_params, n_fold, f->A(), f->row(), f->pg_row(), f->count(), s));
         }
     } else {
@@ -337,7 +349,7 @@ int bsk_fit_step(bsk_fit* f, void* stream) {
     ad.eps = f->eps; ad.weight_decay = f->weight_decay;
     ad.lr = f->lr;
     HIP_TRY(bsk::launch_fit_step(f->theta(), f->A(), f->count(), f->steps(), f->value_seen ? f->policy->lay.n_params : f->action_end(), ad,
-                               f->max_grad_norm, f->gnorm_row(), s));
+                               f->max_grad_norm, f->gnorm_row(), s, f->scheduled ? (const double*)f->sched() : nullptr));
     f->value_seen = false;
     return write_policy(f, s);        // asynchronous on `stream`: no copy, no synchronisation
 }
@@ -379,6 +391,83 @@ int bsk_fit_set_lr(bsk_fit* f, double lr) {
     if (!finite_nonneg(lr)) return fail(BSK_EINVAL, "bsk_fit_set_lr: lr must be finite and not negative");
     f->lr = lr;
     return BSK_OK;
+}
+
+// the eight words of iteration `it` with the gate open: what bsk_fit_schedule_begin leaves, formed with its own text
+static void schedule_words(const bsk_fit* f, uint64_t it, uint64_t* words) {
+    for (int k = 0; k < 4; ++k) {
+        const double x = bsk::pg_sched_value(it, f->pairs.total, f->pairs.a[k], f->pairs.b[k]);
+        std::memcpy(&words[k], &x, 8);
+    }
+    words[bsk::PG_SCHED_ITERATION] = it;
+    words[bsk::PG_SCHED_GATE] = words[bsk::PG_SCHED_SKIPPED] = words[bsk::PG_SCHED_KL] = 0;
+}
+
+int bsk_fit_set_schedule(bsk_fit* f, const bsk_fit_schedule* sc) {
+    if (!f) return fail(BSK_EINVAL, "fit is NULL");
+    if (!sc) {
+        f->scheduled = false;
+        return BSK_OK;
+    }
+    for (int e = 0; e < 2; ++e) {
+        if (!finite_nonneg(sc->lr[e])) return fail(BSK_EINVAL, "bsk_fit_set_schedule: lr must be finite and not negative");
+        if (!(std::isfinite(sc->clip[e]) && sc->clip[e] > 0.0 && sc->clip[e] < 1.0)) return fail(BSK_EINVAL, "bsk_fit_set_schedule: clip must be in (0, 1)");
+        if (!(std::isfinite(sc->clip_vf[e]) && sc->clip_vf[e] > 0.0)) return fail(BSK_EINVAL, "bsk_fit_set_schedule: clip_vf must be finite and positive");
+        if (!finite_nonneg(sc->ent_coef[e])) return fail(BSK_EINVAL, "bsk_fit_set_schedule: ent_coef must be finite and not negative");
+    }
+    if (sc->total >= ((uint64_t)1 << 53)) return fail(BSK_EINVAL, "bsk_fit_set_schedule: total must be below 2^53");
+    if (!finite_nonneg(sc->kl_stop)) return fail(BSK_EINVAL, "bsk_fit_set_schedule: kl_stop must be 0 (no stop) or finite and positive");
+    const double* const from[4] = {sc->lr, sc->clip, sc->clip_vf, sc->ent_coef};          // (the words' order)
+    for (int k = 0; k < 4; ++k) { f->pairs.a[k] = from[k][0]; f->pairs.b[k] = from[k][1]; }
+    f->pairs.total = sc->total;
+    f->kl_stop = sc->kl_stop;
+    f->scheduled = true;
+    return bsk_fit_set_schedule_state(f, 0);
+}
+
+int bsk_fit_set_schedule_state(bsk_fit* f, uint64_t iteration) {
+    if (!f) return fail(BSK_EINVAL, "fit is NULL");
+    if (!f->scheduled) return fail(BSK_EINVAL, "bsk_fit_set_schedule_state: no schedule is attached");
+    uint64_t words[bsk::PG_SCHED_WORDS];
+    schedule_words(f, iteration, words);
+    return transfer(f->device, hipMemcpyHostToDevice, {{words, f->sched(), sizeof(words)}});
+}
+
+int bsk_fit_get_schedule_state(bsk_fit* f, uint64_t* words8) {
+    if (!f || !words8) return fail(BSK_EINVAL, "fit/words8 is NULL");
+    return transfer(f->device, hipMemcpyDeviceToHost, {{words8, f->sched(), 8 * bsk::PG_SCHED_WORDS}});
+}
+
+int bsk_fit_schedule_device(bsk_fit* f, const uint64_t** d_words8) {
+    if (!f || !d_words8) return fail(BSK_EINVAL, "fit/d_words8 is NULL");
+    *d_words8 = (const uint64_t*)f->sched();
+    return BSK_OK;
+}
+
+int bsk_fit_schedule_begin(bsk_fit* f, void* stream) {
+    if (!f) return fail(BSK_EINVAL, "fit is NULL");
+    if (!f->scheduled) return fail(BSK_EINVAL, "bsk_fit_schedule_begin: no schedule is attached");
+    DeviceGuard guard(f->device);
+    HIP_TRY(bsk::launch_pg_sched_begin(f->sched(), f->pairs, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation, no allocation
+}
+
+int bsk_fit_kl_gate(bsk_fit* f, const double* d_diag, int n_rows, void* stream) {
+    if (!f || !d_diag) return fail(BSK_EINVAL, "fit/d_diag is NULL");
+    if (!f->scheduled || !(f->kl_stop > 0.0)) return fail(BSK_EINVAL, "bsk_fit_kl_gate: no schedule with kl_stop > 0 is attached");
+    if (n_rows < 1) return fail(BSK_EINVAL, "bsk_fit_kl_gate: n_rows must be >= 1");
+    DeviceGuard guard(f->device);
+    HIP_TRY(bsk::launch_fit_kl_gate(d_diag, n_rows, f->kl_stop, f->sched(), f->count(), (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation, no allocation
+}
+
+int bsk_fit_schedule_end(bsk_fit* f, double* d_ring, int capacity, void* stream) {
+    if (!f) return fail(BSK_EINVAL, "fit is NULL");
+    if (!f->scheduled) return fail(BSK_EINVAL, "bsk_fit_schedule_end: no schedule is attached");
+    if (d_ring && capacity < 1) return fail(BSK_EINVAL, "bsk_fit_schedule_end: capacity must be >= 1 when d_ring is given");
+    DeviceGuard guard(f->device);
+    HIP_TRY(bsk::launch_pg_sched_end(f->sched(), d_ring, capacity, (hipStream_t)stream));
+    return BSK_OK;        // asynchronous on `stream`: no copy, no synchronisation, no allocation
 }
 
 int bsk_fit_set_max_grad_norm(bsk_fit* f, double max_norm) {

@@ -6,6 +6,8 @@
 //                       entropy bonus in the cross-entropy's place, and four more diagnostics terms; <false> is the supervised kernel
 //                       <true, FitVclip> (bsk_fit_accumulate_ppo with d_value_old or d_dvalue): the same with PPO2's clipped value
 //                       loss in the squared error's place, the value deltas written out, and two diagnostics terms more
+//                       <true, [FitVclip,] FitSched> (a schedule attached, bsk_fit_set_schedule): clip, ent_coef and clip_vf from the
+//                       fit's schedule words (bsk_pgsched.hpp) in the place of the arguments - uniform loads, the host's roundings
 //   fit_fold_kernel     one thread per parameter: A += (double)G_b, b ascending; four threads more for the diagnostics row
 //                       (<8>: eight, the policy-gradient row behind the first; <10, double*>: ten, the value-clip row behind that)
 //   gae_kernel          bsk_gae: one thread per env walks its column of the rollout histories from the last step to the first
@@ -14,6 +16,7 @@
 //   fit_gnorm_kernel    bsk_fit_set_max_grad_norm: one workgroup, the global norm of the mean gradient and the clip's scale
 //   fit_adam_kernel     one thread per parameter: the mean gradient through Adam (adam_step, bsk_es.hpp: the text of the
 //                       evolution strategy's update), a descent; <true>: the gradient times the clip's scale first
+//                       <..., FitSched>: lr from the schedule words, in a copy of the EsAdam that goes through the same adam_step
 //   fit_advance_kernel  one thread: beta_pow and the step counter move on, the count back to zero
 //   fit_alive_kernel    bsk_fit_alive_mask: which envs of a collection loop are still in their first episode
 // The forward pass IS policy_kernel's: policy_hidden / policy_output of bsk_policy.hpp.  Every fused multiply-add is an explicit
@@ -22,8 +25,12 @@
 // the policy-gradient loop (adv_*, fit_gnorm_kernel).  Compiled with -ffp-contract=off (Makefile) for the f64 parts.
 #include "bsk_fit.hpp"
 
+#include <tuple>
+#include <type_traits>
+
 #include "../../include/bskgpu.h"
 #include "bsk_obsstats.hpp"
+#include "bsk_pgsched.hpp"
 #include "bsk_tree.hpp"
 
 // Measurement builds only (make fit-stamps -> variants/fit_stamps.so; tools/fit_measure.py stamps): thread 0 of every workgroup
@@ -168,12 +175,25 @@ __device__ __forceinline__ void fit_backward(const float* __restrict__ params, c
     }
 }
 
-// Vc: nothing, or one FitVclip behind a policy-gradient launch.  The two instantiations without one keep the argument they have
-// always had; the clipped value loss is code of <true, FitVclip> alone.
+// Vc: nothing, one FitVclip behind a policy-gradient launch, and / or - last - one FitSched: the fit's schedule words
+// (bsk_pgsched.hpp), from which a scheduled launch takes clip, ent_coef and clip_vf in the place of its arguments, with the
+// roundings the host applies to those (bsk_fit_accumulate_ppo).  Every lane reads the same words: uniform loads of a kernel
+// argument that is const and __restrict__, never through the LDS.  The instantiations without a row keep the arguments they have
+// always had; the clipped value loss is code of the instantiations with a FitVclip alone.
 template <bool PG, typename... Vc>
 __global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p, const Vc... vclip) {
-    constexpr bool VC = sizeof...(Vc) > 0;
-    static_assert(PG || !VC, "the value clip rides on the policy-gradient launch");
+    constexpr bool VC = (std::is_same_v<Vc, FitVclip> || ... || false);
+    constexpr bool SCHED = (std::is_same_v<Vc, FitSched> || ... || false);
+    static_assert(PG || !(VC || SCHED), "the value clip and the schedule ride on the policy-gradient launch");
+    static_assert(sizeof...(Vc) == (VC ? 1 : 0) + (SCHED ? 1 : 0), "a FitVclip first, a FitSched last, nothing else");
+    float sched_hi = 0.0f, sched_lo = 0.0f, sched_ec = 0.0f, sched_cv = 0.0f;       // (SCHED alone; the others read `p` where they did)
+    if constexpr (SCHED) {                 // (in front of every store of the kernel: nothing can have written the words)
+        const double* __restrict__ sched = std::get<sizeof...(Vc) - 1>(std::forward_as_tuple(vclip...)).row;
+        sched_hi = 1.0f + (float)sched[PG_SCHED_CLIP];
+        sched_lo = 1.0f - (float)sched[PG_SCHED_CLIP];
+        sched_ec = (float)sched[PG_SCHED_ENT_COEF];
+        sched_cv = (float)sched[PG_SCHED_CLIP_VF];
+    }
     // (everything in the dynamic region and every carve a multiple of 16 bytes: a static array in front would shift its base)
     extern __shared__ __attribute__((aligned(16))) float fit_lds[];
     double* s_nll = (double*)(fit_lds + p.rows * POLICY_LANES);
@@ -234,15 +254,16 @@ __global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p
             if (p.logp_old) {                  // (workgroup-uniform)
                 d = logp - (on ? p.logp_old[j] : 0.0f);
                 r = expf(d);
-                clipped = (A > 0.0f && r > p.clip_hi) || (A < 0.0f && r < p.clip_lo);
+                clipped = (A > 0.0f && r > (SCHED ? sched_hi : p.clip_hi)) || (A < 0.0f && r < (SCHED ? sched_lo : p.clip_lo));
             }
+            const float ent_coef = SCHED ? sched_ec : p.ent_coef;
             const bool flat = clipped || A == 0.0f;          // c = +0.0f: the deltas are +0.0f, never the product's -0.0f
             const float c = A * r;
             if (on) {
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
                     const float gp = flat ? 0.0f : c * (pr[i] - (label == i ? 1.0f : 0.0f));
-                    gl[i] = p.ent_coef == 0.0f ? gp : __builtin_fmaf(p.ent_coef, pr[i] * (lp[i] + H), gp);
+                    gl[i] = ent_coef == 0.0f ? gp : __builtin_fmaf(ent_coef, pr[i] * (lp[i] + H), gp);
                 }
             }
             s_pg[lane] = on ? -(double)d : 0.0;
@@ -281,14 +302,14 @@ __global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p
                 const float d = on ? val[0] - R : 0.0f;
                 // PPO2's max((v - R)^2, (v_old + clamp(v - v_old, +-cv) - R)^2) (include/bskgpu.h, bsk_fit_accumulate_ppo): where
                 // the clipped branch holds the max its gradient is zero; a tie is the unclipped branch's
-                const FitVclip x[] = {vclip...};
+                const FitVclip& x = std::get<0>(std::forward_as_tuple(vclip...));
                 float dl = on ? p.value_coef * d : 0.0f;
                 const double plain = (((double)d) * ((double)d)) * 0.5;
                 double term = plain;
                 bool vclipped = false;
-                if (x[0].value_old && on) {        // (the pointer: workgroup-uniform)
-                    const float cv = x[0].clip_vf;
-                    const float vo = x[0].value_old[j];
+                if (x.value_old && on) {           // (the pointer: workgroup-uniform)
+                    const float cv = SCHED ? sched_cv : x.clip_vf;
+                    const float vo = x.value_old[j];
                     const float dv = val[0] - vo;
                     if (!(-cv <= dv && dv <= cv)) {
                         const float vc = vo + (dv > 0.0f ? cv : -cv);
@@ -304,7 +325,7 @@ __global__ __launch_bounds__(POLICY_BLOCK) void fit_block_kernel(const FitArgs p
                 s_vl[lane] = term;
                 s_vc[lane] = vclipped ? 1.0 : 0.0;
                 s_vc[POLICY_LANES + lane] = plain;
-                if (x[0].dvalue && live) x[0].dvalue[j] = dl;
+                if (x.dvalue && live) x.dvalue[j] = dl;
             } else {
                 const float d = on ? val[0] - (float)p.target[j] : 0.0f;
                 delta[lane] = on ? p.value_coef * d : 0.0f;
@@ -429,25 +450,43 @@ __global__ __launch_bounds__(FIT_GNORM_BLOCK) void fit_gnorm_kernel(const double
     }
 }
 
-// CLIP: the mean gradient times the scale fit_gnorm_kernel left, the L2 term added behind it.  <false> is the step without a clip,
-// with the arguments it has always had: the row is an argument of <true, const double*> alone.
-template <bool CLIP, typename... Row>
-__global__ __launch_bounds__(256) void fit_adam_kernel(double* __restrict__ theta, double* __restrict__ A,
-                                                       const unsigned long long* __restrict__ count, int n_upd, const EsAdam ad,
-                                                       const Row... gnorm_row) {
-    const int p = 10 + (int)(blockIdx.x * 256u + threadIdx.x);
-    if (p >= n_upd) return;
+// one parameter of the step: what every instantiation of fit_adam_kernel does with the EsAdam it ends up with
+template <bool CLIP>
+__device__ __forceinline__ void fit_adam_thread(double* __restrict__ theta, double* __restrict__ A, const unsigned long long* __restrict__ count,
+                                                int p, const EsAdam& ad, const double* scale_row) {
     const unsigned long long cnt = *count;
     if (cnt != 0ull) {
         const double t = theta[p];
         if constexpr (CLIP) {
-            const double* const row[] = {gnorm_row...};
-            theta[p] = t - adam_step(ad, p, (A[p] / (double)cnt) * row[0][1] + ad.weight_decay * t);
+            theta[p] = t - adam_step(ad, p, (A[p] / (double)cnt) * scale_row[1] + ad.weight_decay * t);
         } else {
             theta[p] = t - adam_step(ad, p, A[p] / (double)cnt + ad.weight_decay * t);
         }
     }
     A[p] = 0.0;
+}
+
+// CLIP: the mean gradient times the scale fit_gnorm_kernel left, the L2 term added behind it.  <false> is the step without a clip,
+// with the arguments it has always had: the clip's row is an argument of <true, const double*, ...> alone.  A FitSched - last -
+// makes a scheduled step: a copy of `ad` takes its lr from the fit's schedule words (one uniform load) and goes through the same
+// adam_step.
+template <bool CLIP, typename... Row>
+__global__ __launch_bounds__(256) void fit_adam_kernel(double* __restrict__ theta, double* __restrict__ A,
+                                                       const unsigned long long* __restrict__ count, int n_upd, const EsAdam ad_in,
+                                                       const Row... gnorm_row) {
+    constexpr bool SCHED = (std::is_same_v<Row, FitSched> || ... || false);
+    static_assert(sizeof...(Row) == (CLIP ? 1 : 0) + (SCHED ? 1 : 0), "the clip's row first, a FitSched last, nothing else");
+    const int p = 10 + (int)(blockIdx.x * 256u + threadIdx.x);
+    if (p >= n_upd) return;
+    const double* scale_row = nullptr;
+    if constexpr (CLIP) scale_row = std::get<0>(std::forward_as_tuple(gnorm_row...));
+    if constexpr (SCHED) {
+        EsAdam ad = ad_in;
+        ad.lr = std::get<sizeof...(Row) - 1>(std::forward_as_tuple(gnorm_row...)).row[PG_SCHED_LR];
+        fit_adam_thread<CLIP>(theta, A, count, p, ad, scale_row);
+    } else {
+        fit_adam_thread<CLIP>(theta, A, count, p, ad_in, scale_row);
+    }
 }
 
 __global__ void fit_advance_kernel(unsigned long long* count, unsigned long long* steps, double* beta_pow, double beta1, double beta2) {
@@ -650,7 +689,8 @@ FitNet fit_net(const PolicyPackMap& map, int first, const PolicyNet& net) {
 
 template <bool PG, typename... Vc>
 static hipError_t launch_fit_blocks_as(const FitArgs& args, hipStream_t s, const Vc&... vclip) {
-    const size_t lds = (size_t)(args.rows + FIT_DIAG_ROWS + (PG ? FIT_PG_DIAG_ROWS : 0) + (sizeof...(Vc) ? FIT_VC_DIAG_ROWS : 0)) *
+    constexpr bool VC = (std::is_same_v<Vc, FitVclip> || ... || false);
+    const size_t lds = (size_t)(args.rows + FIT_DIAG_ROWS + (PG ? FIT_PG_DIAG_ROWS : 0) + (VC ? FIT_VC_DIAG_ROWS : 0)) *
                        POLICY_LANES * sizeof(float);
     if (lds > 48 * 1024) {                 // (idempotent, and cheap beside the launch: no per-device record to keep)
         hipError_t e = hipFuncSetAttribute((const void*)&fit_block_kernel<PG, Vc...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -664,6 +704,12 @@ static hipError_t launch_fit_blocks_as(const FitArgs& args, hipStream_t s, const
 hipError_t launch_fit_blocks(const FitArgs& args, hipStream_t s) { return launch_fit_blocks_as<false>(args, s); }
 hipError_t launch_fit_blocks_pg(const FitArgs& args, hipStream_t s) { return launch_fit_blocks_as<true>(args, s); }
 hipError_t launch_fit_blocks_ppo(const FitArgs& args, const FitVclip& vc, hipStream_t s) { return launch_fit_blocks_as<true>(args, s, vc); }
+hipError_t launch_fit_blocks_pg_sched(const FitArgs& args, const double* sched, hipStream_t s) {
+    return launch_fit_blocks_as<true>(args, s, FitSched{sched});
+}
+hipError_t launch_fit_blocks_ppo_sched(const FitArgs& args, const FitVclip& vc, const double* sched, hipStream_t s) {
+    return launch_fit_blocks_as<true>(args, s, vc, FitSched{sched});
+}
 
 hipError_t launch_fit_fold(const float* G, const double* diag, int n_blocks, int n_params, int n_fold, double* A, double* row,
                            unsigned long long* count, hipStream_t s) {
@@ -690,7 +736,7 @@ hipError_t launch_fit_fold_ppo(const float* G, const double* diag, int n_blocks,
 }
 
 hipError_t launch_fit_step(double* theta, double* A, unsigned long long* count, unsigned long long* steps, int n_upd, const EsAdam& ad,
-                           double max_norm, double* gnorm_row, hipStream_t s) {
+                           double max_norm, double* gnorm_row, hipStream_t s, const double* sched) {
     if (n_upd > 10) {
         const dim3 grid((unsigned)((n_upd - 10 + 255) / 256));
         if (max_norm > 0.0) {              // one launch in front, over the range the step moves
@@ -698,8 +744,15 @@ hipError_t launch_fit_step(double* theta, double* A, unsigned long long* count, 
                                max_norm, gnorm_row);
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(fit_adam_kernel<true, const double*>), grid, dim3(256), 0, s, theta, A, count, n_upd, ad,
-                               (const double*)gnorm_row);
+            if (sched)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(fit_adam_kernel<true, const double*, FitSched>), grid, dim3(256), 0, s, theta, A, count,
+                                   n_upd, ad, (const double*)gnorm_row, FitSched{sched});
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(fit_adam_kernel<true, const double*>), grid, dim3(256), 0, s, theta, A, count, n_upd, ad,
+                                   (const double*)gnorm_row);
+        } else if (sched) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(fit_adam_kernel<false, FitSched>), grid, dim3(256), 0, s, theta, A, count, n_upd, ad,
+                               FitSched{sched});
         } else {
             hipLaunchKernelGGL(fit_adam_kernel<false>, grid, dim3(256), 0, s, theta, A, count, n_upd, ad);
         }

@@ -51,6 +51,12 @@ struct FitVclip {
     float* dvalue;                 // [n] or NULL: the value network's output delta of every sample
 };
 
+// The fit's schedule words (bsk_pgsched.hpp) as a scheduled launch takes them: a further element of the kernels' variadic packs, a
+// type of its own beside the clip's row (const double*).  Every lane reads the same words of it: uniform loads
+struct FitSched {
+    const double* __restrict__ row;        // [PG_SCHED_WORDS]: lr, clip, clip_vf, ent_coef now, ...
+};
+
 // LDS rows of 64 floats the block kernel needs for this layout: the input, every hidden layer of the larger network, the output deltas
 int fit_lds_rows(const PolicyLayout& lay);
 FitNet fit_net(const PolicyPackMap& map, int first, const PolicyNet& net);
@@ -61,6 +67,10 @@ hipError_t launch_fit_blocks(const FitArgs& args, hipStream_t s);
 hipError_t launch_fit_blocks_pg(const FitArgs& args, hipStream_t s);
 // The same with the clipped value loss (value_old) and / or the value deltas written out (dvalue), and ten diagnostics terms per block
 hipError_t launch_fit_blocks_ppo(const FitArgs& args, const FitVclip& vc, hipStream_t s);
+// The two above as scheduled launches: clip_hi, clip_lo and ent_coef of `args` and clip_vf of `vc` are not read - the words at
+// `sched` are, rounded as the host rounds the arguments
+hipError_t launch_fit_blocks_pg_sched(const FitArgs& args, const double* sched, hipStream_t s);
+hipError_t launch_fit_blocks_ppo_sched(const FitArgs& args, const FitVclip& vc, const double* sched, hipStream_t s);
 // A[p] += (double)G[b][p] for b ascending, p in 10 .. n_fold - 1; the diagnostics row out of the block terms; count += row[3]
 hipError_t launch_fit_fold(const float* G, const double* diag, int n_blocks, int n_params, int n_fold, double* A, double* row,
                            unsigned long long* count, hipStream_t s);
@@ -79,9 +89,10 @@ hipError_t launch_adv_normalize(const float* adv, const uint8_t* alive, int rows
                                 hipStream_t s);
 // Adam on g = A / count + weight_decay * theta for p in 10 .. n_upd - 1 (descent; nothing while count == 0), A zeroed; then one
 // thread: beta_pow and the step counter move on, count = 0.  max_norm > 0: one workgroup in front leaves {norm, scale} of the mean
-// gradient in gnorm_row, and g = (A / count) * scale + weight_decay * theta; max_norm == 0: the launches and arguments without it
+// gradient in gnorm_row, and g = (A / count) * scale + weight_decay * theta; max_norm == 0: the launches and arguments without it.
+// sched (the fit's schedule words, or NULL: the launches and arguments without it): ad.lr is not read, word 0 is
 hipError_t launch_fit_step(double* theta, double* A, unsigned long long* count, unsigned long long* steps, int n_upd, const EsAdam& ad,
-                           double max_norm, double* gnorm_row, hipStream_t s);
+                           double max_norm, double* gnorm_row, hipStream_t s, const double* sched = nullptr);
 // alive[j] = first || (alive[j] && reason[j] == 0), as bytes 1 / 0
 hipError_t launch_fit_alive(const uint8_t* reason, int n, int first, uint8_t* alive, hipStream_t s);
 

@@ -20,7 +20,9 @@ conditioned as PPO2 conditions it by ``normalize_advantages`` (``bsk_adv_normali
 clipped value loss by ``PolicyFit.accumulate_ppo`` (``fit_value_delta_ref``); ``PolicyGradient(log_capacity=)`` keeps a per-iteration
 training log on the device (``pg_episodes`` / ``pg_log_update`` / ``pg_log_advance``; ``pg_episodes_ref``, ``PG_LOG_COLUMNS``) and
 ``PolicyGradient(normalize_rewards=True)`` divides the rewards by the running deviation of the discounted return
-(``reward_normalize``, ``bsk_reward_norm``; ``reward_norm_ref``).
+(``reward_normalize``, ``bsk_reward_norm``; ``reward_norm_ref``); ``PolicyFit.set_schedule`` keeps lr, clip, clip_vf and ent_coef
+in device words the fit's kernels read, annealed per iteration, with a KL stop per update (``bsk_fit_set_schedule``, ...;
+``pg_schedule_ref``, ``fit_kl_gate_ref``) - ``PolicyGradient(total_iterations=, lr_end=, clip_end=, kl_stop=)``.
 
 They are handles of the library and share what such a handle needs (``policy_base._DeviceObject``: create, close, the closed-handle
 refusal, ``sync``); the policy and the population are also both parameter stores that act (``_ParamStore``: the draw counter, the
@@ -46,6 +48,8 @@ from .policy_fit import pg_episodes, pg_log_advance, pg_log_update  # noqa: F401
 from .policy_fit import reward_normalize  # noqa: F401
 from .policy_ref import (REWARD_NORM_STATE_FIELDS, REWARD_NORM_STATE_WORDS, check_reward_norm, reward_norm_divisor,  # noqa: F401
                          reward_norm_ref, reward_norm_state_words, reward_norm_walk_ref, reward_norm_work_bytes)
+from .policy_ref import (SCHED_LOG_COLUMNS, SCHED_STATE_FIELDS, SCHED_WORDS, check_pg_schedule, fit_kl_gate_ref,  # noqa: F401
+                         pg_schedule_ref, sched_log_table_ref, sched_words_ref)
 from .policy_ref import (PG_LOG_COLS, PG_LOG_COLUMNS, check_pg_episodes, check_pg_log, pg_episodes_ref, pg_episodes_walk_ref,  # noqa: F401
                          pg_episodes_work_bytes, pg_log_table_ref, pg_log_update_ref)
 from .policy_ref import (VCLIP_STATS_COLUMNS, check_pg_gather, check_pg_shuffle, fit_value_delta_ref, pg_gather_ref,  # noqa: F401

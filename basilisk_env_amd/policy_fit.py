@@ -31,7 +31,14 @@ bit; ``PolicyGradient(log_capacity=...)`` keeps it and ``training_log()`` reads 
 And the piece of the PPO2 recipe that lives outside its update, stable-baselines' ``VecNormalize(norm_reward=True)``:
 ``reward_normalize`` (``bsk_reward_norm``) divides a rollout's rewards by the running standard deviation of the discounted return -
 carried across rollouts in device memory - and clips them; ``policy_ref.reward_norm_ref`` repeats it bit for bit and
-``PolicyGradient(normalize_rewards=True)`` puts it between the rollout and ``bsk_gae``."""
+``PolicyGradient(normalize_rewards=True)`` puts it between the rollout and ``bsk_gae``.
+
+And what PPO2 changes WHILE it trains: ``PolicyFit.set_schedule`` (``bsk_fit_set_schedule``) keeps lr, clip, clip_vf and ent_coef
+in eight device words of the fit, which scheduled instantiations of the fit's kernels read in the place of their arguments, so that
+a replayed graph anneals them; ``schedule_begin`` forms them from the iteration word by ``policy_ref.pg_schedule_ref``'s rule,
+``kl_gate`` drops the steps of an update once a minibatch's mean KL exceeds ``kl_stop`` (``policy_ref.fit_kl_gate_ref``) and
+``schedule_end`` logs the iteration and moves on.  ``PolicyGradient(total_iterations=, lr_end=, clip_end=, cliprange_vf_end=,
+ent_coef_end=, kl_stop=)`` enqueues them; all off by default."""
 import ctypes as C
 
 import numpy as np
@@ -43,7 +50,8 @@ from .policy_ref import (FIT_STATS_COLUMNS, PG_STATS_COLUMNS, VCLIP_STATS_COLUMN
                          check_fit, check_fit_batch, check_gae, check_max_grad_norm, check_pg, check_pg_episodes, check_pg_gather,
                          check_pg_log, check_pg_loop, check_pg_shuffle, check_reward_norm, PG_LOG_COLS, pg_episodes_work_bytes,
                          pg_log_table_ref, REWARD_NORM_STATE_WORDS, reward_norm_divisor, reward_norm_state_words,
-                         reward_norm_work_bytes)
+                         reward_norm_work_bytes, check_pg_schedule, SCHED_LOG_COLUMNS, SCHED_STATE_FIELDS, SCHED_WORDS,
+                         sched_log_table_ref)
 from .policy_spec import n_params
 
 
@@ -84,6 +92,7 @@ class PolicyFit(_DeviceObject):
         self._out = self._source = None
         self._kept = ()
         self._max_grad_norm = 0.0
+        self._schedule = None
         if max_grad_norm:
             self.max_grad_norm = max_grad_norm
 
@@ -282,6 +291,85 @@ class PolicyFit(_DeviceObject):
         arrs = [None if a is None else _host_block(a, size, np.float64, what="values")
                 for a, size in ((theta, self.n_params), (m, self.n_params), (v, self.n_params), (beta_pow, 2))]
         check(self._lib.bsk_fit_set_state(self._handle(), *[None if a is None else a.ctypes.data for a in arrs], int(steps)))
+
+    # ------------------------------------------------------------------ schedules and the KL stop
+    def set_schedule(self, total, lr, clip, clip_vf, ent_coef, kl_stop=0.0):
+        """Attaches a schedule (``bsk_fit_set_schedule``): each of ``lr``, ``clip``, ``clip_vf`` and ``ent_coef`` a pair (a, b) - a at
+        iteration 0, b from iteration ``total`` on, a line between (``policy_ref.pg_schedule_ref``; ``total`` = 0: a for ever) -
+        and ``kl_stop``, 0 (none) or the mean KL of a minibatch above which ``kl_gate`` drops the rest of an update.  From here on
+        ``accumulate_pg`` / ``accumulate_ppo`` and ``step`` read the values from eight device words of the fit and not from their
+        arguments (which are still checked) or ``lr``, so a captured graph trains at what the words hold at each replay.  The words
+        start at iteration 0.  Synchronises."""
+        total, lr, clip, clip_vf, ent_coef, kl_stop = check_pg_schedule(total, lr, clip, clip_vf, ent_coef, kl_stop)
+        sc = _lib.BskFitSchedule((C.c_double * 2)(*lr), (C.c_double * 2)(*clip), (C.c_double * 2)(*clip_vf), (C.c_double * 2)(*ent_coef),
+                                 total, kl_stop)
+        check(self._lib.bsk_fit_set_schedule(self._handle(), C.byref(sc)))
+        self._schedule = (total, lr, clip, clip_vf, ent_coef, kl_stop)
+
+    def clear_schedule(self):
+        """Detaches the schedule: the launches and arguments of a fit that never had one."""
+        check(self._lib.bsk_fit_set_schedule(self._handle(), None))
+        self._schedule = None
+
+    @property
+    def schedule(self):
+        """(total, lr, clip, clip_vf, ent_coef, kl_stop) as attached, the four as pairs, or None."""
+        return self._schedule
+
+    def schedule_begin(self, stream=0):
+        """``bsk_fit_schedule_begin``: lr, clip, clip_vf and ent_coef of the iteration the words hold, the gate open - one launch on
+        ``stream``, no copy, no synchronisation, capturable."""
+        check(self._lib.bsk_fit_schedule_begin(self._handle(), C.c_void_p(int(stream or 0))))
+
+    def kl_gate(self, diag, n_rows, stream=0):
+        """``bsk_fit_kl_gate`` over ``diag`` float64 [n_rows][8] - the loop's ``log`` rows of the accumulates since the last step -,
+        in front of ``step``: once their mean KL is not <= ``kl_stop`` (or the gate is closed already) what has been accumulated is
+        dropped, and ``step`` moves nothing.  One launch on ``stream``, no copy, no synchronisation, capturable
+        (``policy_ref.fit_kl_gate_ref``)."""
+        ptr, size, _ = _pointer(diag, ("<f8",), "diag")
+        if isinstance(n_rows, bool) or not isinstance(n_rows, (int, np.integer)) or n_rows < 1:
+            raise ValueError("n_rows must be an integer >= 1, got %r" % (n_rows,))
+        if not ptr or (size is not None and size < 8 * n_rows):
+            raise ValueError("diag: a device buffer of at least %d float64" % (8 * n_rows))
+        check(self._lib.bsk_fit_kl_gate(self._handle(), C.c_void_p(ptr), int(n_rows), C.c_void_p(int(stream or 0))))
+
+    def schedule_end(self, ring=None, capacity=0, stream=0):
+        """``bsk_fit_schedule_end``: with ``ring`` float64 [capacity][8] the iteration's row of ``SCHED_LOG_COLUMNS`` into slot
+        iteration % capacity; then iteration += 1.  One launch on ``stream``, no copy, no synchronisation, capturable."""
+        ptr, size, _ = _pointer(ring, ("<f8",), "ring")
+        if ptr:
+            if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity < 2 ** 31:
+                raise ValueError("capacity must be an integer in 1 .. 2^31 - 1 with a ring, got %r" % (capacity,))
+            if size is not None and size < len(SCHED_LOG_COLUMNS) * capacity:
+                raise ValueError("ring: at least %d float64" % (len(SCHED_LOG_COLUMNS) * capacity))
+        check(self._lib.bsk_fit_schedule_end(self._handle(), C.c_void_p(ptr) if ptr else None, int(capacity) if ptr else 0,
+                                             C.c_void_p(int(stream or 0))))
+
+    def schedule_ptr(self):
+        """The eight schedule words (``SCHED_STATE_FIELDS``) as a DEVICE pointer, valid until ``close``."""
+        p = C.c_void_p()
+        check(self._lib.bsk_fit_schedule_device(self._handle(), C.byref(p)))
+        return p.value
+
+    def schedule_words(self):
+        """The eight words as the device holds them -> uint64 (8,).  Synchronises."""
+        words = np.empty(SCHED_WORDS, np.uint64)
+        check(self._lib.bsk_fit_get_schedule_state(self._handle(), C.c_void_p(words.ctypes.data)))
+        return words
+
+    def schedule_state(self):
+        """The eight words decoded -> dict by ``SCHED_STATE_FIELDS``: ``lr``, ``clip``, ``clip_vf``, ``ent_coef`` and ``kl_at_stop``
+        floats, ``iteration``, ``gate`` and ``steps_skipped`` ints.  Synchronises."""
+        words = self.schedule_words()
+        f = words.view(np.float64)
+        return {name: (float(f[k]) if k < 4 or k == 7 else int(words[k])) for k, name in enumerate(SCHED_STATE_FIELDS)}
+
+    def set_schedule_state(self, iteration):
+        """The iteration back, for checkpoints: the words of that iteration with the gate open, as ``schedule_begin`` would leave
+        them.  Synchronises."""
+        if isinstance(iteration, bool) or not isinstance(iteration, (int, np.integer)) or not 0 <= int(iteration) < 2 ** 64:
+            raise ValueError("iteration must be an integer in 0 .. 2^64 - 1, got %r" % (iteration,))
+        check(self._lib.bsk_fit_set_schedule_state(self._handle(), int(iteration)))
 
     @property
     def lr(self):
@@ -541,11 +629,24 @@ class PolicyGradient(object):
     ``set_reward_norm_state()`` are for checkpoints and ``reward_scale()`` is the current divisor.  A value network trained this
     way is in units of reward / sd: the planners' ``bootstrap=`` adds its output to RAW rewards, so a caller that bootstraps from it
     must multiply the values by ``reward_scale()`` - nothing in the planners does.  Off, the loop allocates and enqueues what it
-    always did: the same launches, the same arguments, the same buffers."""
+    always did: the same launches, the same arguments, the same buffers.
+
+    Schedules and a KL stop, off by default: ``total_iterations`` with ``lr_end``, ``clip_end``, ``cliprange_vf_end`` and
+    ``ent_coef_end`` (None: constant) anneals ``fit.lr``, ``clip``, ``cliprange_vf`` and ``ent_coef`` - as they are when the loop is
+    created - linearly to their ends over that many ``update()`` calls (``policy_ref.pg_schedule_ref``; PPO2's annealing is an end of
+    0 for lr), and ``kl_stop`` > 0 drops the remaining steps of an update once a minibatch's mean KL, the loop's estimator
+    mean(logp_old - logp), is above it (``policy_ref.fit_kl_gate_ref``); ``kl_stop`` alone attaches a constant schedule.  The loop
+    then attaches a schedule to the fit (``PolicyFit.set_schedule``; ``close()`` clears it) and ``update()`` enqueues
+    ``schedule_begin`` in front, ``kl_gate`` over every minibatch's rows of ``log`` in front of its step, and ``schedule_end``
+    behind the last epoch, into ``sched_ring`` (allocated beside the training log under ``log_capacity``; ``schedule_log()`` reads
+    it).  All of it is state in device words, so a captured iteration anneals and stops at every replay.  Accumulates behind a
+    closed gate still run and are discarded - the launch sequence is static -, and the training log's diagnostics columns still sum
+    their rows.  With ``total_iterations`` None and ``kl_stop`` 0 the loop is what it always was."""
 
     def __init__(self, env, policy, fit, n_steps, gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, epochs=4, minibatches=4, substeps=1,
                  normalize_advantages=False, obs_stats=None, std_min=1e-6, shuffle=False, seed=0, cliprange_vf=None, log_capacity=0,
-                 normalize_rewards=False, reward_clip=10.0, reward_eps=1e-8):
+                 normalize_rewards=False, reward_clip=10.0, reward_eps=1e-8, total_iterations=None, lr_end=None, clip_end=None,
+                 cliprange_vf_end=None, ent_coef_end=None, kl_stop=0.0):
         from . import _hip
         from ._lib import FLAG_AUTO_RESET
         (self.n_steps, self.gamma, self.lam, self.clip, self.ent_coef, self.epochs, self.minibatches,
@@ -561,6 +662,18 @@ class PolicyGradient(object):
         self._clipped = False
         self.normalize_rewards, self.update_reward_stats = bool(normalize_rewards), True
         _, _, _, _, self.reward_eps, self.reward_clip = check_reward_norm(self.n_steps, 1, 1, self.gamma, reward_eps, reward_clip)
+        self.scheduled = total_iterations is not None or kl_stop != 0
+        schedule = None
+        if self.scheduled:
+            ends = lambda a, b: (a, a if b is None else b)      # noqa: E731
+            cv = 1.0 if self.cliprange_vf is None else self.cliprange_vf          # (never read without old values)
+            if self.cliprange_vf is None and cliprange_vf_end is not None:
+                raise ValueError("cliprange_vf_end needs cliprange_vf")
+            schedule = check_pg_schedule(0 if total_iterations is None else total_iterations, ends(fit.lr, lr_end), ends(self.clip, clip_end),
+                                         ends(cv, cliprange_vf_end), ends(self.ent_coef, ent_coef_end), kl_stop)
+        elif any(x is not None for x in (lr_end, clip_end, cliprange_vf_end, ent_coef_end)):
+            raise ValueError("lr_end, clip_end, cliprange_vf_end and ent_coef_end need total_iterations")
+        self.kl_stop = schedule[5] if schedule else 0.0
         prop = getattr(env, "propagator", env)
         if not (prop.cfg.flags & FLAG_AUTO_RESET):
             raise ValueError("the env must be created with FLAG_AUTO_RESET: episodes restart inside the rollout")
@@ -588,6 +701,8 @@ class PolicyGradient(object):
             check_pg_episodes(T, n, n, self.log_capacity)
             sizes.update(ep_return=8 * n, ep_len=4 * n, ep_work=pg_episodes_work_bytes(n), log_ring=8 * PG_LOG_COLS * self.log_capacity,
                          log_gen=8 * self.log_capacity, log_counter=8)
+            if self.scheduled:
+                sizes.update(sched_ring=8 * len(SCHED_LOG_COLUMNS) * self.log_capacity)
         if self.normalize_rewards:
             check_reward_norm(T, n, n, self.gamma, self.reward_eps, self.reward_clip)
             sizes.update(reward_norm=8 * T * n, ret_run=8 * n, reward_state=8 * REWARD_NORM_STATE_WORDS, reward_work=reward_norm_work_bytes(n))
@@ -603,7 +718,8 @@ class PolicyGradient(object):
             for k in ("obs", "action", "adv", "reason"):
                 _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(b[k].ptr), 0, sizes[k], C.c_void_p(stream)), "hipMemsetAsync")
             if self.log_capacity:          # every slot "never written" (all ones), everything else zero: fresh envs, iteration 0
-                for k, byte in (("ep_return", 0), ("ep_len", 0), ("ep_work", 0), ("log_ring", 0), ("log_counter", 0), ("log_gen", 0xFF)):
+                for k, byte in ((("ep_return", 0), ("ep_len", 0), ("ep_work", 0), ("log_ring", 0), ("log_counter", 0), ("log_gen", 0xFF)) +
+                                ((("sched_ring", 0xFF),) if self.scheduled else ())):
                     _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(b[k].ptr), byte, sizes[k], C.c_void_p(stream)), "hipMemsetAsync")
             if self.normalize_rewards:     # a fresh state, fresh envs
                 for k in ("reward_norm", "ret_run", "reward_state", "reward_work"):
@@ -612,6 +728,17 @@ class PolicyGradient(object):
                               stream=stream)
         if self.shuffle:
             self.set_shuffle_state(seed, 0)
+        if schedule:                       # (behind the accumulate of zeros above, which is an unscheduled launch like any before)
+            fit.set_schedule(*schedule)
+
+    def schedule_log(self):
+        """-> float64 (k, 8): the rows of ``SCHED_LOG_COLUMNS`` the schedule's ring holds, oldest first - one per ``update()``, the
+        last ``log_capacity`` of them.  Synchronises."""
+        if not (self.scheduled and self.log_capacity):
+            raise ValueError("the loop was created without a schedule or without log_capacity")
+        rows = np.empty((self.log_capacity, len(SCHED_LOG_COLUMNS)), np.float64)
+        self._log_copy(((rows, "sched_ring"),), False)
+        return sched_log_table_ref(rows)
 
     def shuffle_state(self):
         """-> (seed, epoch), the two device words of the permutation (``shuffle=True`` only); epoch is the number of epochs run
@@ -713,6 +840,8 @@ class PolicyGradient(object):
             for b in self._buf.values():
                 b.free()
             self._buf = None
+            if self.scheduled and self.fit._p:         # (a fit closed before the loop has no schedule left to clear)
+                self.fit.clear_schedule()
             if self.obs_stats is not None:
                 self.policy.set_obs_stats(None)
 
@@ -735,7 +864,8 @@ class PolicyGradient(object):
         ``mb_ret`` f64 and ``mb_value`` f32 [M] (written under ``cliprange_vf`` only).  With ``log_capacity``: ``ep_return`` f64[n]
         and ``ep_len`` i32[n] (every env's running episode), ``ep_work`` (the scratch of ``bsk_pg_episodes``), ``log_ring``
         f64[log_capacity][26], ``log_gen`` u64[log_capacity] (the iteration each slot holds; all ones: never written) and
-        ``log_counter`` u64 (the iteration being written).  With ``normalize_rewards``: ``reward_norm`` f64[n_steps][n] (the scaled
+        ``log_counter`` u64 (the iteration being written) and, with a schedule, ``sched_ring`` f64[log_capacity][8] (rows of
+        ``SCHED_LOG_COLUMNS``; a NaN iteration: never written).  With ``normalize_rewards``: ``reward_norm`` f64[n_steps][n] (the scaled
         and clipped rewards, what ``bsk_gae`` reads; ``reward`` keeps the raw ones), ``ret_run`` f64[n] (every env's running
         discounted return), ``reward_state`` u64[8] (the statistics) and ``reward_work`` (the scratch of ``bsk_reward_norm``)"""
         return {k: b.ptr for k, b in self._buf.items()}
@@ -782,8 +912,13 @@ class PolicyGradient(object):
         behind its wait); per group one ``fit.step()`` and, under ``fit.max_grad_norm``, its {norm, scale} row into a log of its
         own.  With ``shuffle`` a group is a gathered minibatch and a row a chunk of n of its samples (``epoch``)."""
         self._clipped = self.fit.max_grad_norm > 0.0
+        if self.scheduled:
+            self.fit.schedule_begin(self.prop.stream_ptr())
         for e in range(self.epochs):
             self.epoch(e)
+        if self.scheduled:
+            ring = self._buf["sched_ring"].ptr if self.log_capacity else None
+            self.fit.schedule_end(ring, self.log_capacity, self.prop.stream_ptr())
         if self.log_capacity:
             from . import _hip
             b, stream = self._buf, self.prop.stream_ptr()
@@ -837,6 +972,8 @@ class PolicyGradient(object):
                         _hip.check(rt.hipMemcpyAsync(vp(b["log"].ptr + 64 * slot + 32 * k), vp(row), 32,
                                                      _hip.hipMemcpyDeviceToDevice, vp(stream)), "hipMemcpyAsync")
                     slot += 1
+                if self.kl_stop > 0.0:     # (over this minibatch's rows of the log, which the copies above have just written)
+                    fit.kl_gate(b["log"].ptr + 64 * (slot - rows), rows, stream)
                 fit.step(stream)
                 if clipped:
                     _hip.check(rt.hipMemcpyAsync(vp(b["grad_norm_log"].ptr + 16 * (slot // rows - 1)), vp(gn_row), 16,

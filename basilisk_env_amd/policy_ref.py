@@ -1945,3 +1945,107 @@ def reward_norm_ref(reward, reason, gamma, eps, clip, update, state=None, ret_ru
         c = np.float64(clip)
         out = np.where(y > c, c, np.where(y < -c, -c, y))
     return (out, words, R, work) if with_work else (out, words, R)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Schedules of lr, clip, clip_vf and ent_coef and a KL stop per update (bsk_fit_set_schedule, bsk_fit_schedule_begin,
+# bsk_fit_kl_gate, bsk_fit_schedule_end; definition in include/bskgpu.h, kernels in csrc/bsk_pgsched.hip), restated
+
+SCHED_WORDS = 8                                # BSK_FIT_SCHEDULE_WORDS
+SCHED_STATE_FIELDS = ("lr", "clip", "clip_vf", "ent_coef", "iteration", "gate", "steps_skipped", "kl_at_stop")
+SCHED_LOG_COLUMNS = ("iteration", "lr", "clip", "clip_vf", "ent_coef", "steps_skipped", "kl_at_stop", "stopped")
+
+
+def _sched_pair(what, x):
+    try:
+        a, b = x
+        if isinstance(a, bool) or isinstance(b, bool):
+            raise TypeError
+        return float(a), float(b)
+    except (TypeError, ValueError):
+        raise ValueError("%s: a pair (a, b) of numbers, got %r" % (what, x)) from None
+
+
+def check_pg_schedule(total, lr, clip, clip_vf, ent_coef, kl_stop=0.0):
+    """The argument rules of ``bsk_fit_set_schedule`` -> (total, lr, clip, clip_vf, ent_coef, kl_stop), the four pairs as tuples of
+    floats; ValueError where it returns BSK_EINVAL.  Both ends of a pair obey the rule of the argument they stand in for: ``lr``
+    finite and not negative, ``clip`` inside (0, 1), ``clip_vf`` finite and positive, ``ent_coef`` finite and not negative;
+    ``total`` an integer in 0 .. 2^53 - 1; ``kl_stop`` 0 (no stop) or finite and positive.  Needs no device."""
+    if isinstance(total, bool) or not isinstance(total, (int, np.integer)) or not 0 <= int(total) < 2 ** 53:
+        raise ValueError("total must be an integer in 0 .. 2^53 - 1, got %r" % (total,))
+    lr, clip, clip_vf, ent_coef = (_sched_pair(w, x) for w, x in (("lr", lr), ("clip", clip), ("clip_vf", clip_vf), ("ent_coef", ent_coef)))
+    for x in lr:
+        if not np.isfinite(x) or x < 0.0:
+            raise ValueError("lr must be finite and not negative")
+    for x in clip:
+        if not (np.isfinite(x) and 0.0 < x < 1.0):
+            raise ValueError("clip must be inside (0, 1)")
+    for x in clip_vf:
+        if not np.isfinite(x) or not (x > 0.0):
+            raise ValueError("clip_vf must be finite and positive")
+    for x in ent_coef:
+        if not np.isfinite(x) or x < 0.0:
+            raise ValueError("ent_coef must be finite and not negative")
+    if isinstance(kl_stop, bool):
+        raise ValueError("kl_stop must be 0 or a positive number")
+    kl_stop = float(kl_stop)
+    if not np.isfinite(kl_stop) or kl_stop < 0.0:
+        raise ValueError("kl_stop must be 0 (no stop) or finite and positive")
+    return int(total), lr, clip, clip_vf, ent_coef, kl_stop
+
+
+def pg_schedule_ref(it, total, a, b):
+    """The rule of ``bsk_fit_schedule_begin`` restated -> numpy.float64: ``a`` exactly while ``total`` == 0 or ``it`` == 0, ``b``
+    exactly - not a + (b - a) - from ``it`` >= ``total`` on, and between them a + (b - a) * (float64(it) / float64(total)), every
+    operation rounded on its own.  ``it`` and ``total`` integers, ``total`` below 2^53.  Bit for bit the device's."""
+    it, total = int(it), int(total)
+    if it < 0 or not 0 <= total < 2 ** 53:
+        raise ValueError("it must not be negative and total must be in 0 .. 2^53 - 1")
+    a, b = np.float64(a), np.float64(b)
+    if total == 0 or it == 0:
+        return a
+    if it >= total:
+        return b
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        frac = np.float64(it) / np.float64(total)
+        span = b - a
+        return a + span * frac
+
+
+def fit_kl_gate_ref(rows, kl_stop, gate=0, skipped=0, kl_at_stop=0.0):
+    """``bsk_fit_kl_gate`` restated -> (gate, skipped, kl_at_stop, mean): the three words behind the launch and the minibatch's mean
+    KL.  ``rows`` float64 (n_rows, 8) in the loop's ``log`` layout - ``PG_STATS_COLUMNS`` then ``FIT_STATS_COLUMNS``: S = column 0
+    and N = column 7, each summed ascending FROM the first row; mean = S / N.  A closed gate stays closed; an open one closes when
+    N > 0 and not (mean <= kl_stop) - a NaN closes it, a mean exactly at ``kl_stop`` does not - and that transition alone sets
+    ``kl_at_stop`` = mean.  Closed, now or earlier: skipped + 1, and the caller's accumulation is dropped (the fit's count = 0)."""
+    rows = np.asarray(rows, np.float64)
+    if rows.ndim != 2 or rows.shape[1] != 8 or rows.shape[0] < 1:
+        raise ValueError("rows: (n_rows, 8), n_rows >= 1")
+    gate, skipped, kl_at_stop = int(gate), int(skipped), np.float64(kl_at_stop)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        S, N = rows[0, 0], rows[0, 7]
+        for r in range(1, rows.shape[0]):
+            S, N = S + rows[r, 0], N + rows[r, 7]
+        mean = S / N
+    if gate == 0 and N > 0.0 and not (mean <= np.float64(kl_stop)):
+        gate, kl_at_stop = 1, mean
+    if gate:
+        skipped = (skipped + 1) % 2 ** 64
+    return gate, skipped, kl_at_stop, mean
+
+
+def sched_words_ref(it, total, lr, clip, clip_vf, ent_coef):
+    """The eight words ``bsk_fit_schedule_begin`` leaves at iteration ``it`` -> uint64 (8,): the four values by ``pg_schedule_ref``
+    as the bits of float64 numbers, the iteration, and the gate open (three zero words)."""
+    words = np.zeros(SCHED_WORDS, np.uint64)
+    words.view(np.float64)[:4] = [pg_schedule_ref(it, total, *pair) for pair in (lr, clip, clip_vf, ent_coef)]
+    words[4] = int(it)
+    return words
+
+
+def sched_log_table_ref(rows):
+    """The schedule's ring as the device holds it -> float64 (k, 8): the rows of ``SCHED_LOG_COLUMNS`` that have been written (the
+    iteration is not a NaN), oldest first."""
+    rows = np.asarray(rows, np.float64).reshape(-1, len(SCHED_LOG_COLUMNS))
+    valid = np.flatnonzero(~np.isnan(rows[:, 0]))
+    return rows[valid[np.argsort(rows[valid, 0], kind="stable")]].copy()

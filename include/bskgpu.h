@@ -1390,6 +1390,63 @@ int64_t bsk_reward_norm_work_bytes(int n);
 int bsk_reward_norm(const double* d_reward_hist, const uint8_t* d_reason_hist, int n_steps, int n_envs, int64_t stride, double gamma,
                     double eps, double clip, int update, double* d_ret_run, void* d_state, void* d_work, double* d_out, void* stream);
 
+/* Schedules for the policy-gradient loop and a KL stop per update: lr, clip, clip_vf and ent_coef annealed over the run, and the
+ * remaining steps of an update dropped once the policy has moved too far - both as state in DEVICE words of the fit, so that a
+ * replayed graph carries them (arguments by value are baked into a capture).  Off by default; off, every entry point above enqueues
+ * the kernels it always did with the arguments it always did.
+ *
+ * The fit owns BSK_FIT_SCHEDULE_WORDS = 8 words of 8 bytes (bsk_fit_schedule_device; not part of bsk_fit_get_state / _set_state):
+ *   [0] lr now (f64)   [1] clip now (f64)   [2] clip_vf now (f64)   [3] ent_coef now (f64)   [4] iteration (uint64)
+ *   [5] gate (uint64: 0 open, 1 closed)   [6] steps skipped in this iteration (uint64)
+ *   [7] the minibatch's mean KL that closed the gate (f64), +0.0 while it is open
+ * The rule, all f64, every operation rounded on its own (no FMA), for a pair {a, b} at iteration `it` of `total`:
+ *   total == 0 or it == 0:  a, exactly;      it >= total:  b, exactly (not a + (b - a));
+ *   otherwise:  a + (b - a) * ((double)it / (double)total).
+ * PPO2's lr * (1 - (update - 1) / nupdates) is the rule with b = 0.
+ *
+ * bsk_fit_set_schedule: attaches *s (NULL: detaches).  Attaching writes the words of iteration 0 with the gate open, and
+ *  synchronises.  BSK_EINVAL unless, for BOTH ends of a pair: lr finite and not negative; clip in (0, 1); clip_vf finite and
+ *  positive; ent_coef finite and not negative; and total < 2^53; kl_stop 0 (no stop) or finite and positive.
+ * While a schedule is attached:
+ *  bsk_fit_accumulate_pg / _ppo launch scheduled instantiations of the block kernel, which take
+ *    clip_hi = 1.0f + (float)word[1],  clip_lo = 1.0f - (float)word[1],  ent_coef = (float)word[3],  clip_vf = (float)word[2]
+ *   - the roundings these entry points apply to their arguments, so a scheduled launch is bit for bit the unscheduled one called
+ *   with the words' values.  Their scalar arguments clip, ent_coef and clip_vf are still validated, and then not read.  Whether
+ *   d_logp_old and d_value_old are given still decides ratio and value clip.  bsk_fit_accumulate is untouched.
+ *  bsk_fit_step launches a scheduled instantiation of the Adam kernel, which takes lr = word[0]; the fit's own lr is not read.
+ * bsk_fit_schedule_begin - ONE launch of one thread at the start of an update: words [0..3] from word [4] by the rule; gate = 0,
+ *  skipped = 0, word [7] = +0.0.
+ * bsk_fit_kl_gate - ONE launch of one wave, in front of a step's launches: d_diag f64[n_rows][8], rows in the loop's log layout
+ *  (the policy-gradient row {kl_sum, entropy_sum, clipped, surrogate_sum}, then the diagnostics row {nll_sum, value_loss_sum,
+ *  correct, count}) of the accumulates since the last step.  S = column 0 and N = column 7, each summed ascending FROM the first
+ *  row;  mean = S / N.  The gate closes when it is closed already, or when N > 0 and !(mean <= kl_stop): a NaN mean closes it, a mean
+ *  exactly at kl_stop does not.  On the closing transition word [7] = mean.  Whenever it is closed, now or earlier: the fit's
+ *  count = 0 and skipped += 1 - the bsk_fit_step behind it is then the no-op it is with nothing accumulated: A is cleared, theta, m,
+ *  v, beta_pow and steps do not move.  The KL is the loop's estimator mean(logp_old - logp), which can be negative.  Accumulates
+ *  behind a closed gate still run and are discarded: the launch sequence is static, which is what a graph needs.
+ * bsk_fit_schedule_end - ONE launch of one thread at the end of an update: with d_ring f64[capacity][BSK_SCHED_LOG_COLS] given,
+ *  row [iteration % capacity] = {(double)iteration, lr, clip, clip_vf, ent_coef, (double)skipped, word [7], (double)gate}; then
+ *  iteration += 1.  A ring memset to 0xFF reads as NaN iterations: never written.
+ * The three allocate nothing, copy nothing and do not synchronise: capturable from the first call.  BSK_EINVAL with no schedule
+ * attached; bsk_fit_kl_gate also with kl_stop == 0, a NULL d_diag or n_rows < 1; bsk_fit_schedule_end with d_ring given and
+ * capacity < 1.
+ * bsk_fit_get_schedule_state copies the eight words out; bsk_fit_set_schedule_state writes the words of `iteration` with the gate
+ * open (BSK_EINVAL with no schedule attached) - for checkpoints; both synchronise. */
+#define BSK_FIT_SCHEDULE_WORDS 8
+#define BSK_SCHED_LOG_COLS 8
+typedef struct bsk_fit_schedule {
+    double lr[2], clip[2], clip_vf[2], ent_coef[2];     /* {a, b}: the value at iteration 0, the value from iteration `total` on */
+    uint64_t total;
+    double kl_stop;
+} bsk_fit_schedule;
+int bsk_fit_set_schedule(bsk_fit* f, const bsk_fit_schedule* s);
+int bsk_fit_schedule_begin(bsk_fit* f, void* stream);
+int bsk_fit_kl_gate(bsk_fit* f, const double* d_diag, int n_rows, void* stream);
+int bsk_fit_schedule_end(bsk_fit* f, double* d_ring, int capacity, void* stream);
+int bsk_fit_schedule_device(bsk_fit* f, const uint64_t** d_words8);
+int bsk_fit_get_schedule_state(bsk_fit* f, uint64_t* words8);
+int bsk_fit_set_schedule_state(bsk_fit* f, uint64_t iteration);
+
 /* Synchronises the handle's stream.  Like every synchronising entry point (bsk_get_obs*, bsk_get_state, bsk_get_batch_stats,
  * bsk_get_terminal_obs) it then checks the handle's device error word and returns BSK_EHIP when a kernel raised it: the
  * three-wave form's barrier-free exchange gives up after 2^20 polls instead of hanging, and says so here. */

@@ -48,6 +48,12 @@ same card.
       the parent commit this is all that runs - the parent's bands, re-measured in the same session), then `bsk_reward_norm` at
       that shape with `update = 1` (three launches: 9 bytes per sample read by the walk, 16 moved by the apply) and with
       `update = 0` (the apply alone, against its 16 bytes per sample), out of place and in place.
+  python tools/fit_measure.py sched
+      schedules and the KL stop ("Schedules and a KL stop"), timed as under `time` on the `pg` set-up:
+      `accumulate_ppo` (old log-probabilities, old values, a range of 0.2) + `step`, unscheduled (with BSKGPU_LIB naming a library
+      built from the parent commit this is all that runs - the parent's band, re-measured in the same session), then the same pair
+      with a schedule attached - the scheduled instantiations of the block and the Adam kernel -, `bsk_fit_schedule_begin` +
+      `bsk_fit_schedule_end` together (into a ring of 64 rows) and one `bsk_fit_kl_gate` over 8 rows.
 """
 import os
 import sys
@@ -457,6 +463,58 @@ def rewnorm():
     pol.close()
 
 
+def sched():
+    import torch
+    from _policy_bounds import observation_like, seeded_policy
+    from basilisk_env_amd import _lib
+    from basilisk_env_amd import policy as P
+    spec, params = seeded_policy(HIDDEN, "relu", (64,), seed=1)
+    obs = observation_like(N, 3)
+    rng = np.random.default_rng(5)
+    labels = np.where(obs[3] < 0.4, 1, np.where(obs[2] > 0.7, 2, 0)).astype(np.int32)
+    pol = P.DevicePolicy(spec, params)
+    fit = P.PolicyFit(pol, lr=1e-3)
+    side = torch.cuda.Stream()
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()      # noqa: E731
+    d_obs, d_lab, d_tgt = dev(obs), dev(labels), dev(rng.normal(size=N))
+    d_adv, d_old = dev(rng.normal(size=N).astype(np.float32)), dev((-1.1 + rng.normal(0.0, 0.3, N)).astype(np.float32))
+    d_vold = dev(rng.normal(size=N).astype(np.float32))
+    s = side.cuda_stream
+    new = hasattr(_lib.load(), "bsk_fit_set_schedule")
+    line = "device  %-40s %8.1f us  (p10 %.1f, p90 %.1f)"
+    with torch.cuda.stream(side):
+        def step():
+            fit.accumulate_ppo(d_obs, d_lab, d_adv, d_old, 0.2, 0.01, d_tgt, d_vold, 0.2, stream=s)
+            fit.step(s)
+        plain = _timed(torch, side, step)
+        print(line % (("accumulate_ppo + step",) + plain))
+        if new:
+            cap = 64
+            ring = torch.full((cap, len(P.SCHED_LOG_COLUMNS)), -1, dtype=torch.int64, device="cuda").view(torch.float64)
+            rows = dev(np.tile(np.array([[3.0, 60.0, 5.0, 1.0, 70.0, 30.0, 40000.0, 65536.0]]), (8, 1)))
+            fit.set_schedule(10 ** 6, (1e-3, 0.0), (0.2, 0.05), (0.2, 0.2), (0.01, 0.0), kl_stop=1e3)
+            with_words = _timed(torch, side, step)
+            print(line % (("the same, scheduled",) + with_words))
+            print("device  scheduled median - unscheduled p90: %+.1f us; the unscheduled band is %.1f us wide"
+                  % (with_words[0] - plain[2], plain[2] - plain[1]))
+
+            def around():
+                fit.schedule_begin(s)
+                fit.schedule_end(ring, cap, s)
+            print(line % (("schedule_begin + schedule_end",) + _timed(torch, side, around)))
+            print(line % (("kl_gate over 8 rows",) + _timed(torch, side, lambda: fit.kl_gate(rows, 8, s))))
+            print(line % (("accumulate_ppo + step, scheduled, again",) + _timed(torch, side, step)))
+            fit.clear_schedule()
+            print(line % (("accumulate_ppo + step, unscheduled, again",) + _timed(torch, side, step)))
+            torch.cuda.synchronize()
+            fit.set_schedule(10 ** 6, (1e-3, 0.0), (0.2, 0.05), (0.2, 0.2), (0.01, 0.0), kl_stop=1e3)
+            fit.set_schedule_state(WARM + ITERS)
+            st = fit.schedule_state()
+            print("device  words at iteration %d of 10^6: lr %.6e, clip %.6f; gate %d" % (st["iteration"], st["lr"], st["clip"], st["gate"]))
+    fit.close()
+    pol.close()
+
+
 if __name__ == "__main__":
     {"time": time_, "kernel": kernel, "stamps": stamps, "pg": pg, "pg-kernel": lambda: pg(trace=True),
-     "cond": cond, "shuffle": shuffle, "pglog": pglog, "rewnorm": rewnorm}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
+     "cond": cond, "shuffle": shuffle, "pglog": pglog, "rewnorm": rewnorm, "sched": sched}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
