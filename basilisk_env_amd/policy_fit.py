@@ -1,49 +1,26 @@
-"""Fitting a ``DevicePolicy`` to labelled observations on the device: the ctypes binding of ``bsk_fit_*`` (include/bskgpu.h).
+"""Training a ``DevicePolicy`` on the device: the ctypes binding of ``bsk_fit_*`` and of the launches of a policy-gradient loop
+(include/bskgpu.h).  Everything is enqueued on one stream with no copy, no synchronisation and no allocation, so it can be captured
+into a HIP graph; every kernel's arithmetic is restated bit for bit in ``policy_ref``.  Reached as ``basilisk_env_amd.policy.<name>``.
+In the file's order:
 
-``PolicyFit`` attaches to one policy.  ``accumulate`` adds the gradient of a cross-entropy against int32 labels - and, with value
-targets, of a squared error of the value network - over a batch of observations that is already in device memory; ``step`` is one
-Adam update of a float64 master copy of the parameters, written back into the policy's own device block.  Everything between the
-two is enqueued on one stream with no copy and no synchronisation, so a planner's ``d_best_action`` can be the labels with no host
-in between (``planning.distill``) and the pair can be captured into a HIP graph.  The arithmetic is a fixed order of float32 fused
-multiply-adds and float64 sums; ``policy_ref`` restates it (``fit_backward_ref``, ``fit_accumulate_ref``, ``fit_step_ref``).
-Reached as ``basilisk_env_amd.policy.PolicyFit``.
-
-``accumulate_pg`` is the same launches - and one in front, in which the policy's own code forms the log-probabilities - with the
-output deltas of a clipped policy-gradient loss (PPO; A2C without old log-probabilities) and an entropy bonus in the
-cross-entropy's place (``bsk_fit_accumulate_pg``), ``gae`` the advantage estimator
-over a rollout's histories (``bsk_gae``), and ``PolicyGradient`` the training loop made of them - rollout, advantages, epochs of
-minibatch steps - with no host in it.  Reached as ``basilisk_env_amd.policy.gae`` / ``.PolicyGradient``.
-
-What stable-baselines' PPO2 does to every minibatch beyond that is here too, each off by default: ``normalize_advantages``
-(``bsk_adv_normalize``), ``PolicyFit.max_grad_norm`` (the clip of the gradient's global norm inside ``step``) and
-``PolicyFit.apply_obs_norm`` (an ``ObsStats`` into the policy's in_scale / in_shift); ``PolicyGradient`` takes all three.
-
-The last two pieces of PPO2's update are here as well, off by default: minibatches drawn from a new permutation of all samples in
-every epoch - ``pg_gather`` (``bsk_pg_gather``) by a permutation that is never stored, a function of two device words
-``{seed, epoch}`` that ``policy_ref.pg_perm_ref`` repeats bit for bit - and the clipped value loss, ``PolicyFit.accumulate_ppo``
-(``bsk_fit_accumulate_ppo``); ``PolicyGradient(shuffle=True, cliprange_vf=...)`` runs both.
-
-And what tells whether the agent is getting better: ``pg_episodes`` / ``pg_log_update`` / ``pg_log_advance`` (``bsk_pg_episodes``,
-...) form one row per iteration in a ring on the device - episode returns, lengths and end reasons followed across rollouts,
-PPO2's explained variance, the update's diagnostics - which ``policy_ref.pg_episodes_ref`` / ``pg_log_update_ref`` repeat bit for
-bit; ``PolicyGradient(log_capacity=...)`` keeps it and ``training_log()`` reads it.
-
-And the piece of the PPO2 recipe that lives outside its update, stable-baselines' ``VecNormalize(norm_reward=True)``:
-``reward_normalize`` (``bsk_reward_norm``) divides a rollout's rewards by the running standard deviation of the discounted return -
-carried across rollouts in device memory - and clips them; ``policy_ref.reward_norm_ref`` repeats it bit for bit and
-``PolicyGradient(normalize_rewards=True)`` puts it between the rollout and ``bsk_gae``.
-
-And what PPO2 changes WHILE it trains: ``PolicyFit.set_schedule`` (``bsk_fit_set_schedule``) keeps lr, clip, clip_vf and ent_coef
-in eight device words of the fit, which scheduled instantiations of the fit's kernels read in the place of their arguments, so that
-a replayed graph anneals them; ``schedule_begin`` forms them from the iteration word by ``policy_ref.pg_schedule_ref``'s rule,
-``kl_gate`` drops the steps of an update once a minibatch's mean KL exceeds ``kl_stop`` (``policy_ref.fit_kl_gate_ref``) and
-``schedule_end`` logs the iteration and moves on.  ``PolicyGradient(total_iterations=, lr_end=, clip_end=, cliprange_vf_end=,
-ent_coef_end=, kl_stop=)`` enqueues them; all off by default."""
+- ``_pointer`` / ``_arg``: how every device-buffer argument is read - a raw pointer or anything with ``__cuda_array_interface__``.
+- ``PolicyFit``: gradients into accumulators and Adam on a float64 master copy.  ``accumulate`` (``bsk_fit_accumulate``: cross-entropy
+  against labels, squared value error), ``accumulate_pg`` (``bsk_fit_accumulate_pg``: the clipped surrogate and an entropy bonus),
+  ``accumulate_ppo`` (``bsk_fit_accumulate_ppo``: PPO2's clipped value loss besides), ``step`` (``bsk_fit_step``, under
+  ``max_grad_norm`` with the clip of the global norm), ``apply_obs_norm``; the diagnostics rows (``bsk_fit_*_device``) and their host
+  readers; ``state`` / ``set_state``; the schedule words (``bsk_fit_set_schedule``, ``bsk_fit_schedule_begin`` / ``_end``) and the KL
+  stop (``bsk_fit_kl_gate``).
+- the launches of the loop, one function each: ``gae`` (``bsk_gae``), ``normalize_advantages`` (``bsk_adv_normalize``),
+  ``reward_normalize`` (``bsk_reward_norm``), ``pg_gather`` / ``pg_shuffle_advance`` (``bsk_pg_gather``, ``bsk_pg_shuffle_advance``: a
+  minibatch by a permutation of two device words) and ``pg_episodes`` / ``pg_log_update`` / ``pg_log_advance`` (``bsk_pg_*``: one row
+  of the training log per iteration).
+- ``PolicyGradient``: the loop made of them - ``collect`` (rollout, values, advantages), ``update`` (``epoch``s of minibatch steps),
+  ``iterate`` - and the host readers of its device state, for logs and checkpoints."""
 import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _hip, _lib
 from ._lib import check
 from .policy_base import _DeviceObject, _host_block
 from .policy_ref import (FIT_STATS_COLUMNS, PG_STATS_COLUMNS, VCLIP_STATS_COLUMNS, adv_normalize_work_bytes, check_adv_normalize,
@@ -53,6 +30,23 @@ from .policy_ref import (FIT_STATS_COLUMNS, PG_STATS_COLUMNS, VCLIP_STATS_COLUMN
                          reward_norm_work_bytes, check_pg_schedule, SCHED_LOG_COLUMNS, SCHED_STATE_FIELDS, SCHED_WORDS,
                          sched_log_table_ref)
 from .policy_spec import n_params
+
+_F8, _F4, _I4, _U1, _W64 = ("<f8",), ("<f4",), ("<i4",), ("|u1", "|b1"), ("<u8", "<i8")
+
+
+def _vp(p):
+    return C.c_void_p(p) if p else None
+
+
+def _stream(stream):
+    return C.c_void_p(int(stream or 0))
+
+
+def _check_int(name, x, lo, hi, text):
+    """``x`` as an int when it is an integer - not a bool - in lo .. hi (``hi`` None: no upper bound); ``text`` words the range"""
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or int(x) < lo or (hi is not None and int(x) > hi):
+        raise ValueError("%s must be an integer %s, got %r" % (name, text, x))
+    return int(x)
 
 
 def _pointer(x, typestrs, what):
@@ -67,6 +61,20 @@ def _pointer(x, typestrs, what):
         raise ValueError("%s: a device array of %s, got %r" % (what, " / ".join(typestrs), cai["typestr"]))
     shape = tuple(cai["shape"])
     return int(cai["data"][0]), int(np.prod(shape)) if shape else 1, shape
+
+
+def _arg(x, typestrs, what, need, must=False, in_bytes=False, text=None):
+    """One device-buffer argument of a launch -> its ``c_void_p``, or None for a null pointer.  ``x`` as ``_pointer`` reads it; an
+    array must hold at least ``need`` elements - bytes with ``in_bytes``, whatever its element type - and with ``must`` a null
+    pointer is refused.  ``text`` replaces the wording of both refusals."""
+    ptr, size, _ = _pointer(x, typestrs, what)
+    if must and not ptr:
+        raise ValueError(text or "%s: a device buffer is required" % what)
+    if size is not None and in_bytes:
+        size *= int(x.__cuda_array_interface__["typestr"][2:])
+    if size is not None and size < need:
+        raise ValueError(text or "%s: at least %d elements, got %d" % (what, need, size))
+    return C.c_void_p(ptr) if ptr else None
 
 
 class PolicyFit(_DeviceObject):
@@ -100,7 +108,7 @@ class PolicyFit(_DeviceObject):
         super(PolicyFit, self).close()
         self._kept = ()
 
-    # ------------------------------------------------------------------ the two launches
+    # ------------------------------------------------------------------ the launches
     def accumulate(self, obs, labels, value_targets=None, alive=None, dlogits=None, n=None, stride=None, stream=0):
         """The gradient of one batch into the accumulators: two launches on ``stream``, no copy, no synchronisation; capturable once
         a batch of at least this size has been accumulated outside a capture.  ``obs``: a device array (5, n) float64 with
@@ -110,11 +118,9 @@ class PolicyFit(_DeviceObject):
         the output deltas are also written to, or None.  Each a raw device pointer or anything with
         ``__cuda_array_interface__``; arrays are kept alive until the next call."""
         obs_ptr, stride, n, lab, tgt, liv, dl = self._batch(obs, labels, value_targets, alive, dlogits, n, stride, "labels")
-        vp = lambda p: C.c_void_p(p) if p else None      # noqa: E731
         handle = self._handle()
         self._kept = (obs, labels, value_targets, alive, dlogits)          # (the launches read them after this call returns)
-        check(self._lib.bsk_fit_accumulate(handle, vp(obs_ptr), stride, n, vp(lab), vp(tgt), vp(liv), vp(dl), n,
-                                           C.c_void_p(int(stream or 0))))
+        check(self._lib.bsk_fit_accumulate(handle, _vp(obs_ptr), stride, n, _vp(lab), _vp(tgt), _vp(liv), _vp(dl), n, _stream(stream)))
 
     def _batch(self, obs, labels, value_targets, alive, dlogits, n, stride, noun):
         """The pointer and array rules of ``accumulate`` -> (obs pointer, stride, n, labels, targets, alive, dlogits pointers)"""
@@ -132,10 +138,10 @@ class PolicyFit(_DeviceObject):
         else:
             obs_ptr = int(obs)
         stride = int(n) if stride is None else int(stride)
-        lab, lab_n, _ = _pointer(labels, ("<i4",), noun)
-        tgt, tgt_n, _ = _pointer(value_targets, ("<f8",), "value targets")
-        liv, liv_n, _ = _pointer(alive, ("|u1", "|b1"), "alive")
-        dl, _, dl_shape = _pointer(dlogits, ("<f4",), "dlogits")
+        lab, lab_n, _ = _pointer(labels, _I4, noun)
+        tgt, tgt_n, _ = _pointer(value_targets, _F8, "value targets")
+        liv, liv_n, _ = _pointer(alive, _U1, "alive")
+        dl, _, dl_shape = _pointer(dlogits, _F4, "dlogits")
         n = check_fit_batch(self.policy.spec, n, lab_n, tgt_n if tgt_n is not None else (n if tgt else None), liv_n)
         if lab is None:
             raise ValueError("%s are required" % noun)
@@ -143,26 +149,31 @@ class PolicyFit(_DeviceObject):
             raise ValueError("dlogits: a float32 device array of shape (3, %d), got %r" % (n, dl_shape))
         return obs_ptr, stride, n, lab, tgt, liv, dl
 
+    def _pg_batch(self, obs, actions, advantages, logp_old, clip, ent_coef, value_targets, alive, dlogits, n, stride, more=()):
+        """``_batch`` and the rules ``accumulate_pg`` adds -> (``_batch``'s seven, clip, ent_coef, the pointers of advantages, old
+        log-probabilities and of every (noun, float32 (n,) array) of ``more``)"""
+        batch = self._batch(obs, actions, value_targets, alive, dlogits, n, stride, "actions")
+        named = (("advantages", advantages), ("old log-probabilities", logp_old)) + more
+        read = [_pointer(x, _F4, what) for what, x in named]
+        if read[0][0] is None:
+            raise ValueError("advantages are required")
+        for (what, _), (_, size, _) in zip(named, read):
+            if size is not None and size != batch[2]:
+                raise ValueError("%s: %d elements, got %d" % (what, batch[2], size))
+        return batch + check_pg(clip, ent_coef, read[1][0] is not None) + ([ptr for ptr, _, _ in read],)
+
     def accumulate_pg(self, obs, actions, advantages, logp_old=None, clip=0.2, ent_coef=0.0, value_targets=None, alive=None,
                       dlogits=None, n=None, stride=None, stream=0):
         """``accumulate`` with the policy-gradient output deltas (``bsk_fit_accumulate_pg``; three launches): ``actions`` int32 (n,) - the actions
         taken, in the labels' place -, ``advantages`` float32 (n,) and ``logp_old`` float32 (n,), the log-probabilities the actions
         were taken with, or None (A2C: no ratio, no clipping; ``clip`` is then not read).  ``ent_coef``: the weight of the entropy
         bonus.  Everything else, the pointer and array rules included, is ``accumulate``'s; ``pg_stats`` has the row it adds."""
-        obs_ptr, stride, n, act, tgt, liv, dl = self._batch(obs, actions, value_targets, alive, dlogits, n, stride, "actions")
-        adv, adv_n, _ = _pointer(advantages, ("<f4",), "advantages")
-        old, old_n, _ = _pointer(logp_old, ("<f4",), "old log-probabilities")
-        if adv is None:
-            raise ValueError("advantages are required")
-        for what, size in (("advantages", adv_n), ("old log-probabilities", old_n)):
-            if size is not None and size != n:
-                raise ValueError("%s: %d elements, got %d" % (what, n, size))
-        clip, ent_coef = check_pg(clip, ent_coef, old is not None)
-        vp = lambda p: C.c_void_p(p) if p else None      # noqa: E731
+        obs_ptr, stride, n, act, tgt, liv, dl, clip, ent_coef, (adv, old) = self._pg_batch(
+            obs, actions, advantages, logp_old, clip, ent_coef, value_targets, alive, dlogits, n, stride)
         handle = self._handle()
         self._kept = (obs, actions, advantages, logp_old, value_targets, alive, dlogits)
-        check(self._lib.bsk_fit_accumulate_pg(handle, vp(obs_ptr), stride, n, vp(act), vp(adv), vp(old), clip, ent_coef, vp(tgt), vp(liv),
-                                              vp(dl), n, C.c_void_p(int(stream or 0))))
+        check(self._lib.bsk_fit_accumulate_pg(handle, _vp(obs_ptr), stride, n, _vp(act), _vp(adv), _vp(old), clip, ent_coef, _vp(tgt),
+                                              _vp(liv), _vp(dl), n, _stream(stream)))
 
     def accumulate_ppo(self, obs, actions, advantages, logp_old=None, clip=0.2, ent_coef=0.0, value_targets=None, value_old=None,
                        clip_vf=None, alive=None, dlogits=None, dvalue=None, n=None, stride=None, stream=0):
@@ -171,17 +182,9 @@ class PolicyFit(_DeviceObject):
         read), and ``dvalue`` float32 (n,) or None, which receives the value network's output delta of every sample, the counterpart
         of ``dlogits``.  Either needs ``value_targets``.  With neither the launches are ``accumulate_pg``'s; ``vclip_stats`` has the
         row ``value_old`` adds.  Everything else, the pointer and array rules included, is ``accumulate_pg``'s."""
-        obs_ptr, stride, n, act, tgt, liv, dl = self._batch(obs, actions, value_targets, alive, dlogits, n, stride, "actions")
-        adv, adv_n, _ = _pointer(advantages, ("<f4",), "advantages")
-        old, old_n, _ = _pointer(logp_old, ("<f4",), "old log-probabilities")
-        vold, vold_n, _ = _pointer(value_old, ("<f4",), "old values")
-        dv, dv_n, _ = _pointer(dvalue, ("<f4",), "dvalue")
-        if adv is None:
-            raise ValueError("advantages are required")
-        for what, size in (("advantages", adv_n), ("old log-probabilities", old_n), ("old values", vold_n), ("dvalue", dv_n)):
-            if size is not None and size != n:
-                raise ValueError("%s: %d elements, got %d" % (what, n, size))
-        clip, ent_coef = check_pg(clip, ent_coef, old is not None)
+        obs_ptr, stride, n, act, tgt, liv, dl, clip, ent_coef, (adv, old, vold, dv) = self._pg_batch(
+            obs, actions, advantages, logp_old, clip, ent_coef, value_targets, alive, dlogits, n, stride,
+            (("old values", value_old), ("dvalue", dvalue)))
         if (vold is not None or dv is not None) and tgt is None:
             raise ValueError("old values and dvalue need value targets")
         if vold is None:
@@ -190,67 +193,53 @@ class PolicyFit(_DeviceObject):
             raise ValueError("clip_vf is required with old values")
         else:
             clip_vf = check_pg_shuffle(cliprange_vf=clip_vf)[2]
-        vp = lambda p: C.c_void_p(p) if p else None      # noqa: E731
         handle = self._handle()
         self._kept = (obs, actions, advantages, logp_old, value_targets, value_old, alive, dlogits, dvalue)
-        check(self._lib.bsk_fit_accumulate_ppo(handle, vp(obs_ptr), stride, n, vp(act), vp(adv), vp(old), clip, ent_coef, vp(tgt), vp(vold),
-                                               clip_vf, vp(liv), vp(dl), n, vp(dv), C.c_void_p(int(stream or 0))))
+        check(self._lib.bsk_fit_accumulate_ppo(handle, _vp(obs_ptr), stride, n, _vp(act), _vp(adv), _vp(old), clip, ent_coef, _vp(tgt),
+                                               _vp(vold), clip_vf, _vp(liv), _vp(dl), n, _vp(dv), _stream(stream)))
 
     def step(self, stream=0):
         """One Adam step of the mean gradient since the last one, then float32(theta) into the policy: three launches on
         ``stream`` - four with ``max_grad_norm`` set, the gradient's global norm in front -, no copy, no synchronisation,
         capturable.  Nothing moves when no sample has contributed."""
-        check(self._lib.bsk_fit_step(self._handle(), C.c_void_p(int(stream or 0))))
+        check(self._lib.bsk_fit_step(self._handle(), _stream(stream)))
 
     def apply_obs_norm(self, stats, std_min=1e-6, stream=0):
         """in_scale / in_shift out of an ``ObsStats`` (``obs_norm_ref``) into theta[0:10] - which no step moves - and float32(theta)
         into the policy (``bsk_fit_apply_obs_norm``): two launches on ``stream``, no copy, no synchronisation, capturable.  While
         nothing has been counted theta keeps what it has; theta[10:], m and v are never touched."""
-        check(self._lib.bsk_fit_apply_obs_norm(self._handle(), stats._handle(), float(std_min), C.c_void_p(int(stream or 0))))
+        check(self._lib.bsk_fit_apply_obs_norm(self._handle(), stats._handle(), float(std_min), _stream(stream)))
 
     # ------------------------------------------------------------------ what it holds
+    def _device_words(self, name):
+        """``bsk_fit_<name>_device``: the DEVICE pointer to words of the fit"""
+        p = C.c_void_p()
+        check(self._c(name + "_device")(self._handle(), C.byref(p)))
+        return p.value
+
     def stats_ptr(self):
         """The diagnostics row of the last ``accumulate`` as a DEVICE pointer to 4 float64, valid until ``close``."""
-        p = C.c_void_p()
-        check(self._lib.bsk_fit_stats_device(self._handle(), C.byref(p)))
-        return p.value
+        return self._device_words("stats")
 
     def pg_stats_ptr(self):
         """The policy-gradient row of the last ``accumulate_pg`` as a DEVICE pointer to 4 float64, valid until ``close``."""
-        p = C.c_void_p()
-        check(self._lib.bsk_fit_pg_stats_device(self._handle(), C.byref(p)))
-        return p.value
+        return self._device_words("pg_stats")
 
     def vclip_stats_ptr(self):
         """The value-clip row of the last ``accumulate_ppo`` with ``value_old`` as a DEVICE pointer to 2 float64, valid until
         ``close``."""
-        p = C.c_void_p()
-        check(self._lib.bsk_fit_vclip_stats_device(self._handle(), C.byref(p)))
-        return p.value
-
-    def vclip_stats(self):
-        """The last ``accumulate_ppo`` with ``value_old``'s row -> dict by ``VCLIP_STATS_COLUMNS``: ``value_clipped`` (samples whose
-        clipped branch held the max, and whose value gradient is therefore zero) and ``value_loss_unclipped_sum`` (the summed
-        0.5 (v - target)^2, whatever the branch).  A host read: synchronises."""
-        row = self._row(self.vclip_stats_ptr(), 2)
-        return dict(zip(VCLIP_STATS_COLUMNS, (int(row[0]), row[1])))
+        return self._device_words("vclip_stats")
 
     def grad_norm_ptr(self):
         """{norm, scale} of the last ``step`` taken with ``max_grad_norm`` set as a DEVICE pointer to 2 float64, valid until
         ``close``."""
-        p = C.c_void_p()
-        check(self._lib.bsk_fit_grad_norm_device(self._handle(), C.byref(p)))
-        return p.value
+        return self._device_words("grad_norm")
 
-    def grad_norm(self):
-        """-> dict ``norm`` (the global norm of the last clipped step's mean gradient, before clipping) and ``scale`` (what the
-        step multiplied it by: exactly 1.0 while the norm was within ``max_grad_norm``); (0.0, 1.0) before the first.  A host read:
-        synchronises."""
-        row = self._row(self.grad_norm_ptr(), 2)
-        return {"norm": float(row[0]), "scale": float(row[1])}
+    def schedule_ptr(self):
+        """The eight schedule words (``SCHED_STATE_FIELDS``) as a DEVICE pointer, valid until ``close``."""
+        return self._device_words("schedule")
 
     def _row(self, ptr, words=4):
-        from . import _hip
         row = np.empty(words, np.float64)
         self.sync()                                # (everything queued has written the row)
         with _hip.device_guard(self.device):
@@ -258,6 +247,13 @@ class PolicyFit(_DeviceObject):
                                                      _hip.hipMemcpyDeviceToHost, None), "hipMemcpyAsync")
         self.sync()
         return row
+
+    def stats(self):
+        """The last ``accumulate``'s row -> dict by ``FIT_STATS_COLUMNS``: ``nll_sum`` (the summed cross-entropy), ``value_loss_sum``
+        (the summed 0.5 (v - target)^2), ``correct`` (samples whose greedy action is the label) and ``count`` (samples that
+        contributed).  A host read: synchronises."""
+        row = self._row(self.stats_ptr())
+        return dict(zip(FIT_STATS_COLUMNS, (row[0], row[1], int(row[2]), int(row[3]))))
 
     def pg_stats(self):
         """The last ``accumulate_pg``'s row -> dict by ``PG_STATS_COLUMNS``: ``kl_sum`` (the summed old minus new log-probability of
@@ -267,12 +263,19 @@ class PolicyFit(_DeviceObject):
         row = self._row(self.pg_stats_ptr())
         return dict(zip(PG_STATS_COLUMNS, (row[0], row[1], int(row[2]), row[3])))
 
-    def stats(self):
-        """The last ``accumulate``'s row -> dict by ``FIT_STATS_COLUMNS``: ``nll_sum`` (the summed cross-entropy), ``value_loss_sum``
-        (the summed 0.5 (v - target)^2), ``correct`` (samples whose greedy action is the label) and ``count`` (samples that
-        contributed).  A host read: synchronises."""
-        row = self._row(self.stats_ptr())
-        return dict(zip(FIT_STATS_COLUMNS, (row[0], row[1], int(row[2]), int(row[3]))))
+    def vclip_stats(self):
+        """The last ``accumulate_ppo`` with ``value_old``'s row -> dict by ``VCLIP_STATS_COLUMNS``: ``value_clipped`` (samples whose
+        clipped branch held the max, and whose value gradient is therefore zero) and ``value_loss_unclipped_sum`` (the summed
+        0.5 (v - target)^2, whatever the branch).  A host read: synchronises."""
+        row = self._row(self.vclip_stats_ptr(), 2)
+        return dict(zip(VCLIP_STATS_COLUMNS, (int(row[0]), row[1])))
+
+    def grad_norm(self):
+        """-> dict ``norm`` (the global norm of the last clipped step's mean gradient, before clipping) and ``scale`` (what the
+        step multiplied it by: exactly 1.0 while the norm was within ``max_grad_norm``); (0.0, 1.0) before the first.  A host read:
+        synchronises."""
+        row = self._row(self.grad_norm_ptr(), 2)
+        return {"norm": float(row[0]), "scale": float(row[1])}
 
     def state(self):
         """-> dict ``theta``, ``m``, ``v`` float64 (n_params,), ``beta_pow`` float64 (2,) and ``steps``; synchronises."""
@@ -319,37 +322,27 @@ class PolicyFit(_DeviceObject):
     def schedule_begin(self, stream=0):
         """``bsk_fit_schedule_begin``: lr, clip, clip_vf and ent_coef of the iteration the words hold, the gate open - one launch on
         ``stream``, no copy, no synchronisation, capturable."""
-        check(self._lib.bsk_fit_schedule_begin(self._handle(), C.c_void_p(int(stream or 0))))
+        check(self._lib.bsk_fit_schedule_begin(self._handle(), _stream(stream)))
 
     def kl_gate(self, diag, n_rows, stream=0):
         """``bsk_fit_kl_gate`` over ``diag`` float64 [n_rows][8] - the loop's ``log`` rows of the accumulates since the last step -,
         in front of ``step``: once their mean KL is not <= ``kl_stop`` (or the gate is closed already) what has been accumulated is
         dropped, and ``step`` moves nothing.  One launch on ``stream``, no copy, no synchronisation, capturable
         (``policy_ref.fit_kl_gate_ref``)."""
-        ptr, size, _ = _pointer(diag, ("<f8",), "diag")
-        if isinstance(n_rows, bool) or not isinstance(n_rows, (int, np.integer)) or n_rows < 1:
-            raise ValueError("n_rows must be an integer >= 1, got %r" % (n_rows,))
-        if not ptr or (size is not None and size < 8 * n_rows):
-            raise ValueError("diag: a device buffer of at least %d float64" % (8 * n_rows))
-        check(self._lib.bsk_fit_kl_gate(self._handle(), C.c_void_p(ptr), int(n_rows), C.c_void_p(int(stream or 0))))
+        _pointer(diag, _F8, "diag")                # (its element type is looked at before n_rows)
+        n_rows = _check_int("n_rows", n_rows, 1, None, ">= 1")
+        diag = _arg(diag, _F8, "diag", 8 * n_rows, True, text="diag: a device buffer of at least %d float64" % (8 * n_rows))
+        check(self._lib.bsk_fit_kl_gate(self._handle(), diag, n_rows, _stream(stream)))
 
     def schedule_end(self, ring=None, capacity=0, stream=0):
         """``bsk_fit_schedule_end``: with ``ring`` float64 [capacity][8] the iteration's row of ``SCHED_LOG_COLUMNS`` into slot
         iteration % capacity; then iteration += 1.  One launch on ``stream``, no copy, no synchronisation, capturable."""
-        ptr, size, _ = _pointer(ring, ("<f8",), "ring")
-        if ptr:
-            if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity < 2 ** 31:
-                raise ValueError("capacity must be an integer in 1 .. 2^31 - 1 with a ring, got %r" % (capacity,))
-            if size is not None and size < len(SCHED_LOG_COLUMNS) * capacity:
-                raise ValueError("ring: at least %d float64" % (len(SCHED_LOG_COLUMNS) * capacity))
-        check(self._lib.bsk_fit_schedule_end(self._handle(), C.c_void_p(ptr) if ptr else None, int(capacity) if ptr else 0,
-                                             C.c_void_p(int(stream or 0))))
-
-    def schedule_ptr(self):
-        """The eight schedule words (``SCHED_STATE_FIELDS``) as a DEVICE pointer, valid until ``close``."""
-        p = C.c_void_p()
-        check(self._lib.bsk_fit_schedule_device(self._handle(), C.byref(p)))
-        return p.value
+        if _pointer(ring, _F8, "ring")[0]:
+            capacity = _check_int("capacity", capacity, 1, 2 ** 31 - 1, "in 1 .. 2^31 - 1 with a ring")
+            ring = _arg(ring, _F8, "ring", 8 * capacity, text="ring: at least %d float64" % (8 * capacity))
+        else:
+            ring, capacity = None, 0
+        check(self._lib.bsk_fit_schedule_end(self._handle(), ring, capacity, _stream(stream)))
 
     def schedule_words(self):
         """The eight words as the device holds them -> uint64 (8,).  Synchronises."""
@@ -367,9 +360,8 @@ class PolicyFit(_DeviceObject):
     def set_schedule_state(self, iteration):
         """The iteration back, for checkpoints: the words of that iteration with the gate open, as ``schedule_begin`` would leave
         them.  Synchronises."""
-        if isinstance(iteration, bool) or not isinstance(iteration, (int, np.integer)) or not 0 <= int(iteration) < 2 ** 64:
-            raise ValueError("iteration must be an integer in 0 .. 2^64 - 1, got %r" % (iteration,))
-        check(self._lib.bsk_fit_set_schedule_state(self._handle(), int(iteration)))
+        iteration = _check_int("iteration", iteration, 0, 2 ** 64 - 1, "in 0 .. 2^64 - 1")
+        check(self._lib.bsk_fit_set_schedule_state(self._handle(), iteration))
 
     @property
     def lr(self):
@@ -401,16 +393,11 @@ def gae(reward_hist, reason_hist, value_hist, last_value, n_steps, n_envs, adv, 
     ``n_envs``), ``last_value`` float32 [n_envs] or None (= 0), ``adv`` float32 and ``ret`` float64 (or None) [n_steps][stride].
     Every non-zero reason byte - the time limit included - ends the episode for the estimator (``policy_ref.gae_ref``)."""
     n_steps, n_envs, stride, gamma, lam = check_gae(n_steps, n_envs, n_envs if stride is None else stride, gamma, lam)
-    ptrs = []
-    for x, types, what, need in ((reward_hist, ("<f8",), "reward history", n_steps * stride), (reason_hist, ("|u1", "|b1"), "reason history", n_steps * stride),
-                                 (value_hist, ("<f4",), "value history", n_steps * stride), (last_value, ("<f4",), "last value", n_envs),
-                                 (adv, ("<f4",), "advantages", n_steps * stride), (ret, ("<f8",), "returns", n_steps * stride)):
-        ptr, size, _ = _pointer(x, types, what)
-        if size is not None and size < need:
-            raise ValueError("%s: at least %d elements, got %d" % (what, need, size))
-        ptrs.append(C.c_void_p(ptr) if ptr else None)
-    check(_lib.load().bsk_gae(ptrs[0], ptrs[1], ptrs[2], ptrs[3], n_steps, n_envs, stride, gamma, lam, ptrs[4], ptrs[5],
-                              C.c_void_p(int(stream or 0))))
+    N = n_steps * stride
+    reward, reason = _arg(reward_hist, _F8, "reward history", N), _arg(reason_hist, _U1, "reason history", N)
+    value, last = _arg(value_hist, _F4, "value history", N), _arg(last_value, _F4, "last value", n_envs)
+    adv, ret = _arg(adv, _F4, "advantages", N), _arg(ret, _F8, "returns", N)
+    check(_lib.load().bsk_gae(reward, reason, value, last, n_steps, n_envs, stride, gamma, lam, adv, ret, _stream(stream)))
 
 
 def normalize_advantages(adv, rows, n, out=None, alive=None, eps=1e-8, stride=None, work=None, stream=0):
@@ -423,17 +410,11 @@ def normalize_advantages(adv, rows, n, out=None, alive=None, eps=1e-8, stride=No
     rows, n, stride, eps = check_adv_normalize(rows, n, n if stride is None else stride, eps)
     if work is None:
         raise ValueError("work: a device buffer of adv_normalize_work_bytes(n) bytes is required")
-    ptrs = []
-    for x, types, what, need in ((adv, ("<f4",), "advantages", rows * stride), (alive, ("|u1", "|b1"), "alive", rows * stride),
-                                 (adv if out is None else out, ("<f4",), "out", rows * stride),
-                                 (work, ("<f8", "|u1", "<u8"), "work", None)):
-        ptr, size, _ = _pointer(x, types, what)
-        if need is None and size is not None:
-            size, need = size * int(x.__cuda_array_interface__["typestr"][2:]), adv_normalize_work_bytes(n)
-        if size is not None and size < need:
-            raise ValueError("%s: at least %d elements, got %d" % (what, need, size))
-        ptrs.append(C.c_void_p(ptr) if ptr else None)
-    check(_lib.load().bsk_adv_normalize(ptrs[0], ptrs[1], rows, n, stride, eps, ptrs[2], ptrs[3], C.c_void_p(int(stream or 0))))
+    N = rows * stride
+    src, alive = _arg(adv, _F4, "advantages", N), _arg(alive, _U1, "alive", N)
+    out = _arg(adv if out is None else out, _F4, "out", N)
+    work = _arg(work, ("<f8", "|u1", "<u8"), "work", adv_normalize_work_bytes(n), in_bytes=True)
+    check(_lib.load().bsk_adv_normalize(src, alive, rows, n, stride, eps, out, work, _stream(stream)))
 
 
 def reward_normalize(reward_hist, reason_hist, n_steps, n_envs, state, out=None, ret_run=None, work=None, gamma=0.99, eps=1e-8,
@@ -452,21 +433,13 @@ def reward_normalize(reward_hist, reason_hist, n_steps, n_envs, state, out=None,
     update = bool(update)
     N = n_steps * stride
     words = ("<f8", "|u1", "<u8", "<i8")
-    ptrs = []
-    for x, types, what, need, must in ((reward_hist, ("<f8",), "reward history", N, True), (reason_hist, ("|u1", "|b1"), "reason history", N, True),
-                                       (ret_run, ("<f8",), "ret_run", n_envs, update), (state, words, "state", 8 * REWARD_NORM_STATE_WORDS, True),
-                                       (work, words, "work", reward_norm_work_bytes(n_envs), update),
-                                       (reward_hist if out is None else out, ("<f8",), "out", N, True)):
-        ptr, size, _ = _pointer(x, types, what)
-        if must and not ptr:
-            raise ValueError("%s: a device buffer is required" % what)
-        if size is not None and what in ("state", "work"):
-            size *= int(x.__cuda_array_interface__["typestr"][2:])
-        if size is not None and size < need:
-            raise ValueError("%s: at least %d elements, got %d" % (what, need, size))
-        ptrs.append(C.c_void_p(ptr) if ptr else None)
-    check(_lib.load().bsk_reward_norm(ptrs[0], ptrs[1], n_steps, n_envs, stride, gamma, eps, clip, int(update), ptrs[2], ptrs[3], ptrs[4],
-                                      ptrs[5], C.c_void_p(int(stream or 0))))
+    reward, reason = _arg(reward_hist, _F8, "reward history", N, True), _arg(reason_hist, _U1, "reason history", N, True)
+    ret_run = _arg(ret_run, _F8, "ret_run", n_envs, update)
+    state = _arg(state, words, "state", 8 * REWARD_NORM_STATE_WORDS, True, in_bytes=True)
+    work = _arg(work, words, "work", reward_norm_work_bytes(n_envs), update, in_bytes=True)
+    out = _arg(reward_hist if out is None else out, _F8, "out", N, True)
+    check(_lib.load().bsk_reward_norm(reward, reason, n_steps, n_envs, stride, gamma, eps, clip, int(update), ret_run, state, work, out,
+                                      _stream(stream)))
 
 
 def pg_gather(state, n_steps, n_envs, q0, m, obs_hist=None, action_hist=None, adv=None, logp_hist=None, ret=None, value_hist=None,
@@ -482,38 +455,27 @@ def pg_gather(state, n_steps, n_envs, q0, m, obs_hist=None, action_hist=None, ad
     n_steps, n_envs, stride, q0, m, out_stride = check_pg_gather(n_steps, n_envs, n_envs if stride is None else stride, q0, m,
                                                                  m if out_stride is None else out_stride)
     N = n_steps * stride
-    pairs = (("observations", obs_hist, obs_out, ("<f8",), 5 * N, 4 * out_stride + m), ("actions", action_hist, action_out, ("<i4",), N, m),
-             ("advantages", adv, adv_out, ("<f4",), N, m), ("log-probabilities", logp_hist, logp_out, ("<f4",), N, m),
-             ("returns", ret, ret_out, ("<f8",), N, m), ("values", value_hist, value_out, ("<f4",), N, m))
+    pairs = (("observations", obs_hist, obs_out, _F8, 5 * N, 4 * out_stride + m), ("actions", action_hist, action_out, _I4, N, m),
+             ("advantages", adv, adv_out, _F4, N, m), ("log-probabilities", logp_hist, logp_out, _F4, N, m),
+             ("returns", ret, ret_out, _F8, N, m), ("values", value_hist, value_out, _F4, N, m))
     src, dst = [], []
     for what, a, b, types, need_a, need_b in pairs:
         if (a is None) != (b is None):
             raise ValueError("%s: a history and its output are given together or not at all" % what)
-        for x, need, to in ((a, need_a, src), (b, need_b, dst)):
-            ptr, size, _ = _pointer(x, types, what)
-            if size is not None and size < need:
-                raise ValueError("%s: at least %d elements, got %d" % (what, need, size))
-            to.append(C.c_void_p(ptr) if ptr else None)
-    idx, idx_n, _ = _pointer(index_out, ("<i4",), "index_out")
-    if idx_n is not None and idx_n < m:
-        raise ValueError("index_out: at least %d elements, got %d" % (m, idx_n))
+        src.append(_arg(a, types, what, need_a))
+        dst.append(_arg(b, types, what, need_b))
+    idx = _arg(index_out, _I4, "index_out", m)
     if not idx and not any(src):
         raise ValueError("nothing to write")
-    st, st_n, _ = _pointer(state, ("<u8", "<i8"), "state")
-    if st_n is not None and st_n < 2:
-        raise ValueError("state: two 64-bit words {seed, epoch}")
-    vp = lambda p: C.c_void_p(p) if p else None      # noqa: E731
-    check(_lib.load().bsk_pg_gather(vp(st), n_steps, n_envs, stride, q0, m, *src, dst[0], out_stride, *dst[1:], vp(idx),
-                                    C.c_void_p(int(stream or 0))))
+    state = _arg(state, _W64, "state", 2, text="state: two 64-bit words {seed, epoch}")
+    check(_lib.load().bsk_pg_gather(state, n_steps, n_envs, stride, q0, m, *src, dst[0], out_stride, *dst[1:], idx, _stream(stream)))
 
 
 def pg_shuffle_advance(state, stream=0):
     """``bsk_pg_shuffle_advance``: epoch += 1 in the two device words ``state``, one launch on ``stream``, no copy, no
     synchronisation."""
-    st, st_n, _ = _pointer(state, ("<u8", "<i8"), "state")
-    if not st or (st_n is not None and st_n < 2):
-        raise ValueError("state: two 64-bit device words {seed, epoch}")
-    check(_lib.load().bsk_pg_shuffle_advance(C.c_void_p(st), C.c_void_p(int(stream or 0))))
+    state = _arg(state, _W64, "state", 2, True, text="state: two 64-bit device words {seed, epoch}")
+    check(_lib.load().bsk_pg_shuffle_advance(state, _stream(stream)))
 
 
 def pg_episodes(reward_hist, reason_hist, n_steps, n_envs, ep_return, ep_len, work, ring, capacity, counter=None, action_hist=None,
@@ -529,22 +491,13 @@ def pg_episodes(reward_hist, reason_hist, n_steps, n_envs, ep_return, ep_len, wo
     n_steps, n_envs, stride, capacity = check_pg_episodes(n_steps, n_envs, n_envs if stride is None else stride, capacity,
                                                           value_hist is not None, ret is not None)
     N = n_steps * stride
-    ptrs = []
-    for x, types, what, need, must in ((reward_hist, ("<f8",), "reward history", N, True), (reason_hist, ("|u1", "|b1"), "reason history", N, True),
-                                       (action_hist, ("<i4",), "action history", N, False), (value_hist, ("<f4",), "value history", N, False),
-                                       (ret, ("<f8",), "returns", N, False), (ep_return, ("<f8",), "ep_return", n_envs, True),
-                                       (ep_len, ("<i4",), "ep_len", n_envs, True), (work, ("<f8", "|u1", "<u8", "<i8"), "work", None, True),
-                                       (ring, ("<f8",), "ring", capacity * PG_LOG_COLS, True), (counter, ("<u8", "<i8"), "counter", 1, False)):
-        ptr, size, _ = _pointer(x, types, what)
-        if must and not ptr:
-            raise ValueError("%s: a device buffer is required" % what)
-        if need is None and size is not None:
-            size, need = size * int(x.__cuda_array_interface__["typestr"][2:]), pg_episodes_work_bytes(n_envs)
-        if size is not None and size < need:
-            raise ValueError("%s: at least %d elements, got %d" % (what, need, size))
-        ptrs.append(C.c_void_p(ptr) if ptr else None)
-    check(_lib.load().bsk_pg_episodes(ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], n_steps, n_envs, stride, ptrs[5], ptrs[6], ptrs[7],
-                                      ptrs[8], capacity, ptrs[9], C.c_void_p(int(stream or 0))))
+    reward, reason = _arg(reward_hist, _F8, "reward history", N, True), _arg(reason_hist, _U1, "reason history", N, True)
+    action, value, ret = _arg(action_hist, _I4, "action history", N), _arg(value_hist, _F4, "value history", N), _arg(ret, _F8, "returns", N)
+    ep_return, ep_len = _arg(ep_return, _F8, "ep_return", n_envs, True), _arg(ep_len, _I4, "ep_len", n_envs, True)
+    work = _arg(work, ("<f8", "|u1", "<u8", "<i8"), "work", pg_episodes_work_bytes(n_envs), True, in_bytes=True)
+    ring, counter = _arg(ring, _F8, "ring", capacity * PG_LOG_COLS, True), _arg(counter, _W64, "counter", 1)
+    check(_lib.load().bsk_pg_episodes(reward, reason, action, value, ret, n_steps, n_envs, stride, ep_return, ep_len, work, ring, capacity,
+                                      counter, _stream(stream)))
 
 
 def pg_log_update(diag, n_rows, ring, capacity, counter=None, norms=None, n_norms=None, stream=0):
@@ -555,29 +508,25 @@ def pg_log_update(diag, n_rows, ring, capacity, counter=None, norms=None, n_norm
     if norms is not None and n_norms is None:
         raise ValueError("n_norms: the number of {norm, scale} rows is required with norms")
     n_rows, capacity, n_norms = check_pg_log(n_rows, capacity, None if norms is None else n_norms)
-    ptrs = []
-    for x, types, what, need, must in ((diag, ("<f8",), "diag", 8 * n_rows, True), (norms, ("<f8",), "norms", 2 * (n_norms or 0), False),
-                                       (ring, ("<f8",), "ring", capacity * PG_LOG_COLS, True), (counter, ("<u8", "<i8"), "counter", 1, False)):
-        ptr, size, _ = _pointer(x, types, what)
-        if must and not ptr:
-            raise ValueError("%s: a device buffer is required" % what)
-        if size is not None and size < need:
-            raise ValueError("%s: at least %d elements, got %d" % (what, need, size))
-        ptrs.append(C.c_void_p(ptr) if ptr else None)
-    check(_lib.load().bsk_pg_log_update(ptrs[0], n_rows, ptrs[1], n_norms or 0, ptrs[2], capacity, ptrs[3], C.c_void_p(int(stream or 0))))
+    n_norms = n_norms or 0
+    diag, norms = _arg(diag, _F8, "diag", 8 * n_rows, True), _arg(norms, _F8, "norms", 2 * n_norms)
+    ring, counter = _arg(ring, _F8, "ring", capacity * PG_LOG_COLS, True), _arg(counter, _W64, "counter", 1)
+    check(_lib.load().bsk_pg_log_update(diag, n_rows, norms, n_norms, ring, capacity, counter, _stream(stream)))
 
 
 def pg_log_advance(gen, capacity, counter, stream=0):
     """``bsk_pg_log_advance``: gen[counter % capacity] = counter, counter += 1 - ``gen`` uint64 [capacity], ``counter`` one uint64
     device word.  One launch on ``stream``, no copy, no synchronisation."""
     _, capacity, _ = check_pg_log(1, capacity)
-    ptrs = []
-    for x, what, need in ((gen, "gen", capacity), (counter, "counter", 1)):
-        ptr, size, _ = _pointer(x, ("<u8", "<i8"), what)
-        if not ptr or (size is not None and size < need):
-            raise ValueError("%s: %d 64-bit device words" % (what, need))
-        ptrs.append(C.c_void_p(ptr))
-    check(_lib.load().bsk_pg_log_advance(ptrs[0], capacity, ptrs[1], C.c_void_p(int(stream or 0))))
+    gen = _arg(gen, _W64, "gen", capacity, True, text="gen: %d 64-bit device words" % capacity)
+    counter = _arg(counter, _W64, "counter", 1, True, text="counter: 1 64-bit device words")
+    check(_lib.load().bsk_pg_log_advance(gen, capacity, counter, _stream(stream)))
+
+
+def _copy_row(dst, src, nbytes, stream):
+    """``nbytes`` from one device address to another, enqueued on ``stream`` of the current device"""
+    _hip.check(_hip.runtime().hipMemcpyAsync(C.c_void_p(dst), C.c_void_p(src), nbytes, _hip.hipMemcpyDeviceToDevice, C.c_void_p(stream)),
+               "hipMemcpyAsync")
 
 
 class PolicyGradient(object):
@@ -647,14 +596,10 @@ class PolicyGradient(object):
                  normalize_advantages=False, obs_stats=None, std_min=1e-6, shuffle=False, seed=0, cliprange_vf=None, log_capacity=0,
                  normalize_rewards=False, reward_clip=10.0, reward_eps=1e-8, total_iterations=None, lr_end=None, clip_end=None,
                  cliprange_vf_end=None, ent_coef_end=None, kl_stop=0.0):
-        from . import _hip
-        from ._lib import FLAG_AUTO_RESET
         (self.n_steps, self.gamma, self.lam, self.clip, self.ent_coef, self.epochs, self.minibatches,
          self.substeps) = check_pg_loop(n_steps, gamma, lam, clip, ent_coef, epochs, minibatches, substeps)
         self.shuffle, seed, self.cliprange_vf = check_pg_shuffle(shuffle, seed, cliprange_vf, self.n_steps, self.minibatches)
-        if isinstance(log_capacity, bool) or not isinstance(log_capacity, (int, np.integer)) or not 0 <= log_capacity < 2 ** 31:
-            raise ValueError("log_capacity must be an integer in 0 .. 2^31 - 1, got %r" % (log_capacity,))
-        self.log_capacity = int(log_capacity)
+        self.log_capacity = _check_int("log_capacity", log_capacity, 0, 2 ** 31 - 1, "in 0 .. 2^31 - 1")
         self.normalize_advantages, self.obs_stats, self.std_min = bool(normalize_advantages), obs_stats, float(std_min)
         if not np.isfinite(self.std_min) or not (self.std_min > 0.0):
             raise ValueError("std_min must be finite and positive")
@@ -675,7 +620,7 @@ class PolicyGradient(object):
             raise ValueError("lr_end, clip_end, cliprange_vf_end and ent_coef_end need total_iterations")
         self.kl_stop = schedule[5] if schedule else 0.0
         prop = getattr(env, "propagator", env)
-        if not (prop.cfg.flags & FLAG_AUTO_RESET):
+        if not (prop.cfg.flags & _lib.FLAG_AUTO_RESET):
             raise ValueError("the env must be created with FLAG_AUTO_RESET: episodes restart inside the rollout")
         if policy.spec.value_hidden is None:
             raise ValueError("the policy has no value network")
@@ -711,19 +656,18 @@ class PolicyGradient(object):
                 raise ValueError("obs_stats: a statistics object of at least %d envs on device %d" % (n, prop.device))
             policy.set_obs_stats(obs_stats)                # (the rollouts of collect() feed it from now on)
         self._buf = {k: _hip.DeviceBuffer(b, prop.device) for k, b in sizes.items()}
+        b, stream = self._buf, prop.stream_ptr()
+        fills = [("obs", 0), ("action", 0), ("adv", 0), ("reason", 0)]         # (buffer, the byte it starts filled with)
+        if self.log_capacity:              # every slot "never written" (all ones), everything else zero: fresh envs, iteration 0
+            fills += [("ep_return", 0), ("ep_len", 0), ("ep_work", 0), ("log_ring", 0), ("log_counter", 0), ("log_gen", 0xFF)]
+            fills += [("sched_ring", 0xFF)] if self.scheduled else []
+        if self.normalize_rewards:         # a fresh state, fresh envs
+            fills += [("reward_norm", 0), ("ret_run", 0), ("reward_state", 0), ("reward_work", 0)]
         # Whatever a first launch would allocate, here: the fit's scratch of block gradients for n samples, by an accumulate of zeros in
         # which no sample is alive - it adds +0.0 to every accumulator and nothing to the count.
-        b, stream = self._buf, prop.stream_ptr()
         with _hip.device_guard(prop.device):
-            for k in ("obs", "action", "adv", "reason"):
-                _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(b[k].ptr), 0, sizes[k], C.c_void_p(stream)), "hipMemsetAsync")
-            if self.log_capacity:          # every slot "never written" (all ones), everything else zero: fresh envs, iteration 0
-                for k, byte in ((("ep_return", 0), ("ep_len", 0), ("ep_work", 0), ("log_ring", 0), ("log_counter", 0), ("log_gen", 0xFF)) +
-                                ((("sched_ring", 0xFF),) if self.scheduled else ())):
-                    _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(b[k].ptr), byte, sizes[k], C.c_void_p(stream)), "hipMemsetAsync")
-            if self.normalize_rewards:     # a fresh state, fresh envs
-                for k in ("reward_norm", "ret_run", "reward_state", "reward_work"):
-                    _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(b[k].ptr), 0, sizes[k], C.c_void_p(stream)), "hipMemsetAsync")
+            for k, byte in fills:
+                _hip.check(_hip.runtime().hipMemsetAsync(C.c_void_p(b[k].ptr), byte, sizes[k], C.c_void_p(stream)), "hipMemsetAsync")
             fit.accumulate_pg(b["obs"].ptr, b["action"].ptr, b["adv"].ptr, None, self.clip, 0.0, None, b["reason"].ptr, n=n, stride=n,
                               stream=stream)
         if self.shuffle:
@@ -731,11 +675,27 @@ class PolicyGradient(object):
         if schedule:                       # (behind the accumulate of zeros above, which is an unscheduled launch like any before)
             fit.set_schedule(*schedule)
 
+    # ------------------------------------------------------------------ host reads and writes of the device state
+    @staticmethod
+    def _need(flag, what):
+        if not flag:
+            raise ValueError("the loop was created without " + what)
+
+    def _log_copy(self, pairs, upload):
+        """Every (host array, buffer name) of ``pairs`` from the device, or with ``upload`` to it, behind a wait for the env"""
+        self.prop.sync()
+        with _hip.device_guard(self.prop.device):
+            for host, name in pairs:
+                h, d = C.c_void_p(host.ctypes.data), C.c_void_p(self._buf[name].ptr)
+                if upload:
+                    _hip.check(_hip.runtime().hipMemcpy(d, h, host.nbytes, _hip.hipMemcpyHostToDevice), "hipMemcpy")
+                else:
+                    _hip.check(_hip.runtime().hipMemcpy(h, d, host.nbytes, _hip.hipMemcpyDeviceToHost), "hipMemcpy")
+
     def schedule_log(self):
         """-> float64 (k, 8): the rows of ``SCHED_LOG_COLUMNS`` the schedule's ring holds, oldest first - one per ``update()``, the
         last ``log_capacity`` of them.  Synchronises."""
-        if not (self.scheduled and self.log_capacity):
-            raise ValueError("the loop was created without a schedule or without log_capacity")
+        self._need(self.scheduled and self.log_capacity, "a schedule or without log_capacity")
         rows = np.empty((self.log_capacity, len(SCHED_LOG_COLUMNS)), np.float64)
         self._log_copy(((rows, "sched_ring"),), False)
         return sched_log_table_ref(rows)
@@ -743,34 +703,22 @@ class PolicyGradient(object):
     def shuffle_state(self):
         """-> (seed, epoch), the two device words of the permutation (``shuffle=True`` only); epoch is the number of epochs run
         since ``set_shuffle_state``.  For checkpoints; synchronises."""
-        return tuple(int(w) for w in self._shuffle_words(None))
+        self._need(self.shuffle, "shuffle")
+        words = np.empty(2, np.uint64)
+        self._log_copy(((words, "shuffle_state"),), False)
+        return tuple(int(w) for w in words)
 
     def set_shuffle_state(self, seed, epoch=0):
         """The two words back: with them, and the fit's state, an update resumes bit for bit.  Synchronises."""
         seed = check_pg_shuffle(True, seed)[1]
-        if isinstance(epoch, bool) or not isinstance(epoch, (int, np.integer)) or not 0 <= int(epoch) < 2 ** 64:
-            raise ValueError("epoch must be an integer in 0 .. 2^64 - 1, got %r" % (epoch,))
-        self._shuffle_words(np.array([seed, int(epoch)], np.uint64))
-
-    def _shuffle_words(self, new):
-        from . import _hip
-        if not self.shuffle:
-            raise ValueError("the loop was created without shuffle")
-        words = np.empty(2, np.uint64) if new is None else new
-        self.prop.sync()
-        with _hip.device_guard(self.prop.device):
-            ptr, host = C.c_void_p(self._buf["shuffle_state"].ptr), C.c_void_p(words.ctypes.data)
-            if new is None:
-                _hip.check(_hip.runtime().hipMemcpy(host, ptr, 16, _hip.hipMemcpyDeviceToHost), "hipMemcpy")
-            else:
-                _hip.check(_hip.runtime().hipMemcpy(ptr, host, 16, _hip.hipMemcpyHostToDevice), "hipMemcpy")
-        return words
+        epoch = _check_int("epoch", epoch, 0, 2 ** 64 - 1, "in 0 .. 2^64 - 1")
+        self._need(self.shuffle, "shuffle")
+        self._log_copy(((np.array([seed, epoch], np.uint64), "shuffle_state"),), True)
 
     def training_log(self):
         """-> (iterations uint64 (k,), rows float64 (k, 26)): the slots of the ring that have been written, oldest first - one row of
         ``PG_LOG_COLUMNS`` per ``collect()`` + ``update()``, the last ``log_capacity`` of them.  Synchronises."""
-        if not self.log_capacity:
-            raise ValueError("the loop was created without log_capacity")
+        self._need(self.log_capacity, "log_capacity")
         gen, rows = np.empty(self.log_capacity, np.uint64), np.empty((self.log_capacity, PG_LOG_COLS), np.float64)
         self._log_copy(((gen, "log_gen"), (rows, "log_ring")), False)
         return pg_log_table_ref(gen, rows)
@@ -778,8 +726,7 @@ class PolicyGradient(object):
     def episode_state(self):
         """-> (ep_return float64 (n,), ep_len int32 (n,), counter): the return and the length of every env's running episode and the
         number of the iteration being written.  For checkpoints; synchronises."""
-        if not self.log_capacity:
-            raise ValueError("the loop was created without log_capacity")
+        self._need(self.log_capacity, "log_capacity")
         R, L, c = np.empty(self.n_envs, np.float64), np.empty(self.n_envs, np.int32), np.empty(1, np.uint64)
         self._log_copy(((R, "ep_return"), (L, "ep_len"), (c, "log_counter")), False)
         return R, L, int(c[0])
@@ -787,21 +734,18 @@ class PolicyGradient(object):
     def set_episode_state(self, ep_return, ep_len, counter=0):
         """The three back: with them - and the env's own state - the log goes on as if it had not been interrupted (the ring's rows
         are not part of it).  Synchronises."""
-        if not self.log_capacity:
-            raise ValueError("the loop was created without log_capacity")
+        self._need(self.log_capacity, "log_capacity")
         R, L = np.ascontiguousarray(ep_return, np.float64).reshape(-1), np.ascontiguousarray(ep_len, np.int32).reshape(-1)
         if R.size != self.n_envs or L.size != self.n_envs:
             raise ValueError("ep_return and ep_len: one value per env (%d)" % self.n_envs)
-        if isinstance(counter, bool) or not isinstance(counter, (int, np.integer)) or not 0 <= int(counter) < 2 ** 64:
-            raise ValueError("counter must be an integer in 0 .. 2^64 - 1, got %r" % (counter,))
-        self._log_copy(((R, "ep_return"), (L, "ep_len"), (np.array([int(counter)], np.uint64), "log_counter")), True)
+        counter = _check_int("counter", counter, 0, 2 ** 64 - 1, "in 0 .. 2^64 - 1")
+        self._log_copy(((R, "ep_return"), (L, "ep_len"), (np.array([counter], np.uint64), "log_counter")), True)
 
     def reward_norm_state(self):
         """-> (state uint64 (8,), ret_run float64 (n,)): the words of the reward statistics as the device holds them
         (``policy_ref.REWARD_NORM_STATE_FIELDS``) and every env's running discounted return (``normalize_rewards=True`` only).  For
         checkpoints; synchronises."""
-        if not self.normalize_rewards:
-            raise ValueError("the loop was created without normalize_rewards")
+        self._need(self.normalize_rewards, "normalize_rewards")
         words, R = np.empty(REWARD_NORM_STATE_WORDS, np.uint64), np.empty(self.n_envs, np.float64)
         self._log_copy(((words, "reward_state"), (R, "ret_run")), False)
         return words, R
@@ -809,8 +753,7 @@ class PolicyGradient(object):
     def set_reward_norm_state(self, state, ret_run):
         """The two back: with them - and the env's own state - the scaling goes on as if it had not been interrupted.
         Synchronises."""
-        if not self.normalize_rewards:
-            raise ValueError("the loop was created without normalize_rewards")
+        self._need(self.normalize_rewards, "normalize_rewards")
         words = reward_norm_state_words(np.ascontiguousarray(state))
         R = np.ascontiguousarray(ret_run, np.float64).reshape(-1)
         if R.size != self.n_envs:
@@ -822,17 +765,6 @@ class PolicyGradient(object):
         discounted return, 1.0 before the first rollout.  A value of the value network times this is in the reward's own unit.
         Synchronises."""
         return float(reward_norm_divisor(self.reward_norm_state()[0]))
-
-    def _log_copy(self, pairs, upload):
-        from . import _hip
-        self.prop.sync()
-        with _hip.device_guard(self.prop.device):
-            for host, name in pairs:
-                h, d = C.c_void_p(host.ctypes.data), C.c_void_p(self._buf[name].ptr)
-                if upload:
-                    _hip.check(_hip.runtime().hipMemcpy(d, h, host.nbytes, _hip.hipMemcpyHostToDevice), "hipMemcpy")
-                else:
-                    _hip.check(_hip.runtime().hipMemcpy(h, d, host.nbytes, _hip.hipMemcpyDeviceToHost), "hipMemcpy")
 
     def close(self):
         if getattr(self, "_buf", None):
@@ -878,7 +810,6 @@ class PolicyGradient(object):
         statistics updated first unless ``update_reward_stats`` is False at this moment; behind all of it, with
         ``normalize_advantages`` and without ``shuffle``: every minibatch's rows of ``adv`` normalised into ``adv_norm`` (with
         ``shuffle`` the minibatches do not exist yet: ``update()`` normalises each behind its gather)."""
-        from . import _hip
         prop, b, T, n = self.prop, self._buf, self.n_steps, self.n_envs
         stream = prop.stream_ptr()
         if self.obs_stats is not None:
@@ -920,7 +851,6 @@ class PolicyGradient(object):
             ring = self._buf["sched_ring"].ptr if self.log_capacity else None
             self.fit.schedule_end(ring, self.log_capacity, self.prop.stream_ptr())
         if self.log_capacity:
-            from . import _hip
             b, stream = self._buf, self.prop.stream_ptr()
             with _hip.device_guard(self.prop.device):
                 pg_log_update(b["log"].ptr, self.epochs * self.n_steps, b["log_ring"].ptr, self.log_capacity, b["log_counter"].ptr,
@@ -934,50 +864,44 @@ class PolicyGradient(object):
         normalisation in place, then one accumulate per chunk of n of them; and behind the pass ``pg_shuffle_advance``, so that
         the next pass - or the next replay of this one from a graph - draws another permutation.  Under ``cliprange_vf`` the
         accumulates are ``accumulate_ppo`` against the recorded values."""
-        from . import _hip
-        prop, b, n, fit = self.prop, self._buf, self.n_envs, self.fit
-        adv = b["adv_norm" if self.normalize_advantages and not self.shuffle else "adv"].ptr
-        clipped = fit.max_grad_norm > 0.0
+        prop, b, n, T, fit = self.prop, self._buf, self.n_envs, self.n_steps, self.fit
+        clipped, cv = fit.max_grad_norm > 0.0, self.cliprange_vf
         gn_row = fit.grad_norm_ptr() if clipped else None
-        stream, rows = prop.stream_ptr(), self.n_steps // self.minibatches
-        rt, vp = _hip.runtime(), C.c_void_p
+        stream, rows = prop.stream_ptr(), T // self.minibatches
         pg_row, fit_row = fit.pg_stats_ptr(), fit.stats_ptr()
-        M, cv = rows * n, self.cliprange_vf
+        M, log = rows * n, b["log"].ptr
+        # where a row's samples come from: obs, actions, advantages, old log-probabilities, returns and old values, and the row stride
+        if self.shuffle:
+            names, stride = ("mb_obs", "mb_action", "mb_adv", "mb_logp", "mb_ret", "mb_value"), M
+        else:
+            names, stride = ("obs", "action", "adv_norm" if self.normalize_advantages else "adv", "logp", "ret", "value"), n
+        obs, act, adv, logp, ret, val = (b[k].ptr for k in names)
         with _hip.device_guard(prop.device):
-            slot = int(e) * self.n_steps
+            slot = int(e) * T
             for g in range(self.minibatches):
                 if self.shuffle:
-                    old = (b["value"].ptr, b["mb_value"].ptr) if cv is not None else (None, None)
-                    pg_gather(b["shuffle_state"].ptr, self.n_steps, n, g * M, M, b["obs"].ptr, b["action"].ptr, adv, b["logp"].ptr,
-                              b["ret"].ptr, old[0], b["mb_obs"].ptr, b["mb_action"].ptr, b["mb_adv"].ptr, b["mb_logp"].ptr,
-                              b["mb_ret"].ptr, old[1], stream=stream)
+                    old = (b["value"].ptr, val) if cv is not None else (None, None)
+                    pg_gather(b["shuffle_state"].ptr, T, n, g * M, M, b["obs"].ptr, b["action"].ptr, b["adv"].ptr, b["logp"].ptr,
+                              b["ret"].ptr, old[0], obs, act, adv, logp, ret, old[1], stream=stream)
                     if self.normalize_advantages:
-                        normalize_advantages(b["mb_adv"].ptr, rows, n, work=b["adv_work"].ptr, stream=stream)
+                        normalize_advantages(adv, rows, n, work=b["adv_work"].ptr, stream=stream)
                 for c in range(rows):
-                    if self.shuffle:
-                        at, stride = c * n, M
-                        src = (b["mb_obs"].ptr + 8 * at, b["mb_action"].ptr + 4 * at, b["mb_adv"].ptr + 4 * at, b["mb_logp"].ptr + 4 * at,
-                               b["mb_ret"].ptr + 8 * at, b["mb_value"].ptr + 4 * at)
-                    else:
-                        t, stride = g * rows + c, n
-                        src = (b["obs"].ptr + 8 * 5 * n * t, b["action"].ptr + 4 * n * t, adv + 4 * n * t, b["logp"].ptr + 4 * n * t,
-                               b["ret"].ptr + 8 * n * t, b["value"].ptr + 4 * n * t)
+                    at = n * (c if self.shuffle else g * rows + c)         # the row's first sample
+                    o = obs + 8 * (at if self.shuffle else 5 * at)         # (a gathered minibatch is [5][M], the history [T][5][n])
                     if cv is None:
-                        fit.accumulate_pg(src[0], src[1], src[2], src[3], self.clip, self.ent_coef, src[4], None, n=n, stride=stride,
-                                          stream=stream)
+                        fit.accumulate_pg(o, act + 4 * at, adv + 4 * at, logp + 4 * at, self.clip, self.ent_coef, ret + 8 * at, None, n=n,
+                                          stride=stride, stream=stream)
                     else:
-                        fit.accumulate_ppo(src[0], src[1], src[2], src[3], self.clip, self.ent_coef, src[4], src[5], cv, None, n=n,
-                                           stride=stride, stream=stream)
-                    for k, row in enumerate((pg_row, fit_row)):
-                        _hip.check(rt.hipMemcpyAsync(vp(b["log"].ptr + 64 * slot + 32 * k), vp(row), 32,
-                                                     _hip.hipMemcpyDeviceToDevice, vp(stream)), "hipMemcpyAsync")
+                        fit.accumulate_ppo(o, act + 4 * at, adv + 4 * at, logp + 4 * at, self.clip, self.ent_coef, ret + 8 * at,
+                                           val + 4 * at, cv, None, n=n, stride=stride, stream=stream)
+                    _copy_row(log + 64 * slot, pg_row, 32, stream)
+                    _copy_row(log + 64 * slot + 32, fit_row, 32, stream)
                     slot += 1
                 if self.kl_stop > 0.0:     # (over this minibatch's rows of the log, which the copies above have just written)
-                    fit.kl_gate(b["log"].ptr + 64 * (slot - rows), rows, stream)
+                    fit.kl_gate(log + 64 * (slot - rows), rows, stream)
                 fit.step(stream)
                 if clipped:
-                    _hip.check(rt.hipMemcpyAsync(vp(b["grad_norm_log"].ptr + 16 * (slot // rows - 1)), vp(gn_row), 16,
-                                                 _hip.hipMemcpyDeviceToDevice, vp(stream)), "hipMemcpyAsync")
+                    _copy_row(b["grad_norm_log"].ptr + 16 * (slot // rows - 1), gn_row, 16, stream)
             if self.shuffle:
                 pg_shuffle_advance(b["shuffle_state"].ptr, stream)
 
@@ -986,7 +910,6 @@ class PolicyGradient(object):
         ``FIT_STATS_COLUMNS``, each the sum over the minibatch's rows in their order, formed after the one wait at the end.
         ``grad_norms`` is afterwards the {norm, scale} row of every step, float64 (epochs * minibatches, 2), or None without
         ``fit.max_grad_norm``."""
-        from . import _hip
         out = np.empty((self.epochs * self.minibatches, self.n_steps // self.minibatches, 8), np.float64)
         self.collect()
         self.update()

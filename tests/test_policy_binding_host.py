@@ -9,7 +9,6 @@ that, and as "ptr" otherwise.  The log, the (type, message) of every exception t
 were recorded from the binding as it stood before it was split into policy_spec / policy_ref / policy and given one base class:
     PYTHONPATH=. python tests/test_policy_binding_host.py --record
 writes them anew - which is right only when the sequence of C calls is MEANT to change."""
-import ctypes as C
 import json
 import os
 import types
@@ -18,155 +17,11 @@ import zlib
 import numpy as np
 import pytest
 
+from _binding_fakes import FakeArray, FakePropagator, Recorder, _block
 from basilisk_env_amd import _hip, _lib
 from basilisk_env_amd import policy as P
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "policy_binding_calls.json")
-
-# per C function, what each argument is: v a scalar; p a pointer; s the policy spec; o an out-parameter the fake fills;
-# F / G / T host float32 of n_params / P * n_params / n_params elements read by the call; D / B host float64 of n_params / 2
-# elements read by the call; f / d / b host float32 n_params / float64 n_params / float64 2 the call fills
-KINDS = {
-    "bsk_policy_create": "sFvo", "bsk_policy_set_params": "pF", "bsk_policy_destroy": "p", "bsk_policy_set_rng": "pvv",
-    "bsk_policy_get_rng": "poo", "bsk_policy_act": "ppvvvvppppvp", "bsk_policy_rollout": "ppvvvpppppp",
-    "bsk_population_create": "svGvo", "bsk_population_destroy": "p", "bsk_population_set_rng": "pvv", "bsk_population_get_rng": "poo",
-    "bsk_population_set_params": "pG", "bsk_population_set_params_device": "ppvvp", "bsk_population_get_member": "pvf",
-    "bsk_population_act": "ppvvvvvppppvp", "bsk_population_rollout": "ppvvvvpppppppppp",
-    "bsk_es_create": "svFvvvvvo", "bsk_es_destroy": "p", "bsk_es_ask": "ppp", "bsk_es_tell": "ppp", "bsk_es_get_state": "pdo",
-    "bsk_es_set_state": "pDv", "bsk_es_generation_device": "po", "bsk_es_set_optimizer": "pvvvvv", "bsk_es_get_moments": "pddb",
-    "bsk_es_set_moments": "pDDB",
-    "hipGetDevice": "o", "hipSetDevice": "v", "hipDeviceSynchronize": "", "hipMemcpyAsync": "ppvvp",
-}
-OUT = {"bsk_policy_get_rng": (11, 22), "bsk_population_get_rng": (33, 44), "bsk_es_get_state": (55,), "hipGetDevice": (0,)}
-HOST = {"F": (np.float32, "np"), "G": (np.float32, "Pnp"), "D": (np.float64, "np"), "B": (np.float64, 2),
-        "f": (np.float32, "np"), "d": (np.float64, "np"), "b": (np.float64, 2)}
-
-
-class Recorder(object):
-    """The log, the names of the pointers the fakes hand out, and the fakes themselves."""
-
-    def __init__(self):
-        self.log, self.errors, self.names, self.count, self.sizes = [], [], {}, {}, {}
-        self.fail_next = None                      # name of the C function whose next call returns BSK_EINVAL
-        self.lib, self.rt = types.SimpleNamespace(), types.SimpleNamespace()
-        for name, kinds in KINDS.items():
-            setattr(self.rt if name.startswith("hip") else self.lib, name, self._function(name, kinds))
-        self.lib.bsk_last_error = lambda: b"fake"
-        rec = self
-
-        class DeviceBuffer(object):
-            def __init__(self, nbytes, device):
-                self.ptr, self.nbytes, self.device = rec.pointer("buf"), int(nbytes), int(device)
-                self.name = rec.names[self.ptr]
-                rec.log.append(["DeviceBuffer", self.name, nbytes, device])
-
-            def free(self):
-                if self.ptr:
-                    rec.log.append(["DeviceBuffer.free", self.name])
-                    self.ptr = None
-        self.DeviceBuffer = DeviceBuffer
-
-    def pointer(self, what):
-        """a new fake address, known by the name what#k from here on"""
-        self.count[what] = k = self.count.get(what, 0) + 1
-        addr = 0x7000000000 + 0x100000 * len(self.names)
-        self.names[addr] = "%s#%d" % (what, k)
-        return addr
-
-    def name_of(self, a):
-        if isinstance(a, C.c_void_p):
-            a = a.value
-        if hasattr(a, "_obj"):                     # (byref)
-            a = C.addressof(a._obj)
-        return None if not a else self.names.get(int(a), "ptr")
-
-    def _host(self, kind, addr, fill):
-        dt, count = HOST[kind]
-        count = self.sizes.get(count, count)
-        arr = np.ctypeslib.as_array((C.c_byte * (count * np.dtype(dt).itemsize)).from_address(addr)).view(dt)
-        if fill:
-            arr[:] = np.arange(count) * 0.5 + 1.0
-            return "%s[%d] filled" % (np.dtype(dt).str, count)
-        return "%s[%d] crc %08x" % (np.dtype(dt).str, count, zlib.crc32(arr.tobytes()))
-
-    def _function(self, name, kinds):
-        def call(*args):
-            assert len(args) == len(kinds), (name, len(args))
-            row, outs = [], list(OUT.get(name, ()))
-            for kind, a in zip(kinds, args):
-                if kind == "v":
-                    assert isinstance(a, (int, float)), (name, a)
-                    row.append(a)
-                elif kind == "p":
-                    row.append(self.name_of(a))
-                elif kind == "s":
-                    s = a._obj
-                    row.append(["spec", s.abi_version, s.struct_size, s.n_hidden, list(s.hidden), s.activation, s.has_value, s.v_n_hidden,
-                                list(s.v_hidden), s.v_activation])
-                elif kind == "o":
-                    if a is None:
-                        row.append(None)
-                        continue
-                    a._obj.value = outs.pop(0) if outs else self.pointer("generation" if name.endswith("generation_device") else name.split("_")[1])
-                    row.append("out")
-                else:
-                    addr = a.value if isinstance(a, C.c_void_p) else a
-                    row.append(None if not addr else self._host(kind, int(addr), kind in "fdb"))
-            self.log.append([name] + row)
-            if self.fail_next == name:
-                self.fail_next = None
-                return -1
-            return 0
-        return call
-
-    def note(self, *what):
-        self.log.append(["--"] + list(what))
-
-    def raises(self, fn, *args, **kw):
-        try:
-            fn(*args, **kw)
-        except Exception as e:      # noqa: BLE001 - the type is what gets recorded
-            self.errors.append([type(e).__name__, str(e)])
-            self.log.append(["raised", type(e).__name__, str(e)])
-        else:
-            raise AssertionError("nothing raised")
-
-
-class FakeArray(object):
-    def __init__(self, ptr, shape, typestr, strides=None, with_strides=True):
-        self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr, False), "version": 2}
-        if with_strides:
-            self.__cuda_array_interface__["strides"] = strides
-
-
-class FakePropagator(object):
-    def __init__(self, rec, n_envs, device, env_base=None):
-        self.rec, self.n_envs, self.device = rec, n_envs, device
-        if env_base is not None:
-            self.env_base = env_base
-        self._h, self._stream, self._obs = rec.pointer("prop"), rec.pointer("stream"), rec.pointer("obs")
-
-    def device_views(self):
-        return {"obs": FakeArray(self._obs, (5, self.n_envs), "<f8"), "stride": self.n_envs + 64}
-
-    def stream_ptr(self):
-        return self._stream
-
-    def _handle(self):
-        return C.c_void_p(self._h)
-
-    def sync(self):
-        self.rec.log.append(["prop.sync", self.rec.names[self._h]])
-
-    def reset_from_pool_shared(self, envs_per_member, epoch):
-        self.rec.log.append(["prop.reset_from_pool_shared", envs_per_member, self.rec.name_of(epoch)])
-
-    def reset_from_pool_device(self, slots):
-        self.rec.log.append(["prop.reset_from_pool_device", slots])
-
-
-def _block(n, dtype=np.float32, at=0.0):
-    return (np.arange(n) * 0.25 + at).astype(dtype)
 
 
 def _views(rec, res, objs):

@@ -54,6 +54,14 @@ same card.
       built from the parent commit this is all that runs - the parent's band, re-measured in the same session), then the same pair
       with a schedule attached - the scheduled instantiations of the block and the Adam kernel -, `bsk_fit_schedule_begin` +
       `bsk_fit_schedule_end` together (into a ring of 64 rows) and one `bsk_fit_kl_gate` over 8 rows.
+  python tools/fit_measure.py host [POLICY_FIT.py]
+      what the HOST spends enqueuing one update ("One reader for the device arguments"): the wall time
+      (`time.perf_counter`) of `PolicyGradient.update()` from the call to its return, nothing waited for in between - 4 096 envs,
+      32 steps, 4 epochs of 4 minibatches, `shuffle=True, normalize_advantages=True, cliprange_vf=0.2`, `fit.max_grad_norm = 0.5`:
+      PPO2's update, 468 calls into the library and the runtime.  10 warming and 100 timed calls with a `sync()` of the env between
+      them, outside the timed region; the median and the 10th / 90th percentile.  With POLICY_FIT.py that file is loaded in the place
+      of basilisk_env_amd/policy_fit.py - the parent commit's (`git show HEAD~1:basilisk_env_amd/policy_fit.py`) over the same
+      library is the band to compare with, re-measured in the same session.
 """
 import os
 import sys
@@ -515,6 +523,49 @@ def sched():
     pol.close()
 
 
+def host():
+    import importlib.util
+    import time
+    if len(sys.argv) > 2:                      # (before anything imports the package's own)
+        mod_spec = importlib.util.spec_from_file_location("basilisk_env_amd.policy_fit", sys.argv[2])
+        sys.modules[mod_spec.name] = mod = importlib.util.module_from_spec(mod_spec)
+        mod_spec.loader.exec_module(mod)
+    import torch
+    from _policy_bounds import seeded_policy
+    from basilisk_env_amd import policy as P
+    from basilisk_env_amd._lib import FLAG_AUTO_RESET, GRAV_PM_J2
+    from basilisk_env_amd.simulators.dynamics import BatchedPropagator, default_config
+    from basilisk_env_amd.simulators.initial_conditions.batch import sample_ic_batch
+    which = os.path.relpath(sys.modules["basilisk_env_amd.policy_fit"].__file__, ROOT)
+    n, T, warm, iters = 4096, 32, 10, 100
+    spec, params = seeded_policy(HIDDEN, "relu", (64,), seed=1)
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        cfg = default_config(4, GRAV_PM_J2)
+        cfg.flags |= FLAG_AUTO_RESET
+        root = BatchedPropagator(cfg, n, stream=side.cuda_stream)
+        root.set_ic_pool(sample_ic_batch(64, 4, seed=73))
+        root.reset(sample_ic_batch(n, 4, seed=72))
+        root.step(np.zeros(n, np.int32), 1)                     # (the observation buffers hold a step's output)
+        pol = P.DevicePolicy(spec, params)
+        fit = P.PolicyFit(pol, lr=1e-3)
+        fit.max_grad_norm = 0.5
+        pg = P.PolicyGradient(root, pol, fit, T, epochs=4, minibatches=4, shuffle=True, normalize_advantages=True, cliprange_vf=0.2)
+        pg.collect()
+        root.sync()
+        t = []
+        for _ in range(warm + iters):
+            t0 = time.perf_counter()
+            pg.update()
+            t.append(time.perf_counter() - t0)
+            root.sync()
+        t = np.array(t[warm:]) * 1e6
+        print("host    %-36s update() %8.1f us  (p10 %.1f, p90 %.1f)" % (which, np.median(t), np.percentile(t, 10), np.percentile(t, 90)))
+        pg.close()
+    fit.close()
+    pol.close()
+
+
 if __name__ == "__main__":
-    {"time": time_, "kernel": kernel, "stamps": stamps, "pg": pg, "pg-kernel": lambda: pg(trace=True),
-     "cond": cond, "shuffle": shuffle, "pglog": pglog, "rewnorm": rewnorm, "sched": sched}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
+    {"time": time_, "kernel": kernel, "stamps": stamps, "pg": pg, "pg-kernel": lambda: pg(trace=True), "cond": cond,
+     "shuffle": shuffle, "pglog": pglog, "rewnorm": rewnorm, "sched": sched, "host": host}[sys.argv[1] if len(sys.argv) > 1 else "time"]()
